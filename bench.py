@@ -22,6 +22,11 @@ N > 1 (one rank per GPU, torch.distributed.run):
                LPT-sharded over the ranks by window count; total windows/s = all windows / the
                slowest rank's time.
 
+A plain run sets up, ramps, warms up, times the --steps steps and prints the headline (value, ms_per_step).
+--full adds, after the timed steps, the figures that take runs of their own: the roofline leg, the passes
+with peaks / TSV rows, the CPU baselines and their parity check, end to end, the extra workloads and the
+secondary sw / interval metrics.  --dump-outputs DIR writes the peak records of the last timed step.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -68,6 +73,24 @@ def profiled_traffic(workload):
         except (OSError, KeyError, ValueError):
             continue
     return None, None
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, peaks, prefix=""):
+    """--dump-outputs: the compacted peak records of one pass (what a caller of WavePlan.run + peaks gets), one
+    float64 array per field (exact for u32 / i32) as DIR/<prefix>peaks_<field>.npy.  Above DUMP_LIMIT_BYTES in all,
+    a fixed, seeded sample of the records is written instead, with their indices in <prefix>peaks_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    n = int(peaks.size)
+    per_record = 8 * (len(peaks.dtype.names) + 1)
+    if n * per_record > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_LIMIT_BYTES // per_record, replace=False))
+        peaks = peaks[idx]
+        np.save(os.path.join(dirname, f"{prefix}peaks_index.npy"), idx.astype(np.float64))
+    for f in peaks.dtype.names:
+        np.save(os.path.join(dirname, f"{prefix}peaks_{f}.npy"), peaks[f].astype(np.float64))
 
 
 def window_count(n, size, step):
@@ -317,17 +340,26 @@ def main():
                          "Multi-batch workloads put batch j on HIP stream j % 4 instead")
     ap.add_argument("--one-at-a-time", action="store_true", help="every batch on one stream, depth 1 (profiling)")
     ap.add_argument("--ramp-ms", type=float, default=50.0, help="time-based clock ramp before the warm-up steps")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the S288c / beyond-L3 extra measurements")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the sw / interval metrics")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (gz / host buffers -> TSV text) block")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the S288c / beyond-L3 extra measurements")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the sw / interval metrics")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="--full: skip the end-to-end (gz / host buffers -> TSV text) block")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="join the ranks, run the bench's three collectives once, print a JSON line and stop "
                          "(no GPU work: checks the launch path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the roofline leg, the passes with peaks / rows, the CPU "
+                         "baselines and parity, end to end, the extra workloads and the secondary metrics "
+                         "(--no-cpu / --no-e2e / --no-extra / --no-secondary drop single blocks of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the peak records of the last timed step to DIR/<field>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started as plain `python bench.py --gpus N`: be our own launcher (see self_launch)
         sys.exit(self_launch(args.gpus))
@@ -447,27 +479,31 @@ def main():
         total_windows = float(my_windows)
     peaks = [p.peaks() for p in plans]
     n_exact = sum(p.exact_count() for p in plans)
+    if args.dump_outputs:
+        last = (ramp_steps + args.warmup + args.steps - 1) % nb      # the plan of the last timed step
+        dump_outputs(args.dump_outputs, peaks[last], f"rank{rank}_" if world > 1 else "")
 
-    # Roofline leg: the dominant kernel's own launch duration, one pass at a time on the library's
+    # Roofline leg (--full): the dominant kernel's own launch duration, one pass at a time on the library's
     # compute stream, HIP events on that stream (what rocprofv3 --kernel-trace reports per launch);
     # the batches still rotate, so every launch streams from HBM.
-    set_flight(False)
-    serial_steps = max(nb * 4, min(max(args.steps, 30), 300))
-    run_steps(nb * 3)
-    eng.sync()
-    eng.timer_start()
-    run_steps(serial_steps)
-    kernel_ms = eng.timer_stop()      # HIP events on the library's compute stream
-    eng.sync()
-    launch_ms = kernel_ms / serial_steps
-    kernel_name = plans[0].kernel_name()   # the instantiation this leg launched (rocprofv3's row of the same name)
-    serial_windows = sum(win_per_batch[i % nb] for i in range(serial_steps)) / serial_steps
+    if args.full:
+        set_flight(False)
+        serial_steps = max(nb * 4, min(max(args.steps, 30), 300))
+        run_steps(nb * 3)
+        eng.sync()
+        eng.timer_start()
+        run_steps(serial_steps)
+        kernel_ms = eng.timer_stop()      # HIP events on the library's compute stream
+        eng.sync()
+        launch_ms = kernel_ms / serial_steps
+        kernel_name = plans[0].kernel_name()   # the instantiation this leg launched (rocprofv3's row of the same name)
+        serial_windows = sum(win_per_batch[i % nb] for i in range(serial_steps)) / serial_steps
 
-    # run + peaks, pipelined: what a host that consumes the peaks pays per batch (wave.rs:157-214 reads them).
-    # Batch j runs on lane j; while its kernel is in flight the oldest batch's peaks are packed on the device
+    # run + peaks, pipelined (--full): what a host that consumes the peaks pays per batch (wave.rs:157-214 reads
+    # them).  Batch j runs on lane j; while its kernel is in flight the oldest batch's peaks are packed on the device
     # (wave_offsets_kernel + wave_gather_kernel on the readback stream) and fetched into page-locked memory.
     pass_with_peaks_ms, pass_with_rows_ms, rows_text_bytes, resident_to_tsv_ms = None, None, None, None
-    if world == 1 and nb > 1:
+    if args.full and world == 1 and nb > 1:
         set_flight(True)
         for p in plans:
             p.set_pipelined(True)
@@ -519,10 +555,7 @@ def main():
         set_flight(False)
 
     out = None
-    traffic, traffic_src = profiled_traffic(args.workload) if args.scale == 1.0 and args.tile == 0 else (None, None)
     if rank == 0:
-        step_bytes = prm["step"]                       # SURVEY 8(d): `step` bytes read per window
-        achieved = serial_windows * step_bytes / (launch_ms * 1e-3) / 1e9
         lengths_name, piece = WORKLOADS[args.workload][0], WORKLOADS[args.workload][1]
         out = {
             "metric": f"GC windows/s (size {prm['size']}, step {prm['step']})",
@@ -532,9 +565,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3,
-            "pass_with_peaks_ms": pass_with_peaks_ms,
-            "pass_with_rows_ms": pass_with_rows_ms,
-            "resident_to_tsv_ms": resident_to_tsv_ms,
             "higher_is_better": True,
             "scaling": scaling,
             "vs_baseline": None,
@@ -549,36 +579,43 @@ def main():
                 "windows_per_step": win_per_batch,
                 "resident_bytes_per_gpu": int(sum(sum(len(c["seq"]) for c in b) for b in batches)),
                 "peaks_per_step": [int(p.size) for p in peaks],
-                "rows_text_bytes_per_step": rows_text_bytes,
                 "exact_path_windows_per_rotation": int(n_exact),
                 "passes_in_flight": (min(nb, 4) if nb > 1 else (args.depth or 2)) if in_flight else 1,
-                "tapered_launches": "off in the timed region (passes in flight), on in the roofline leg (one pass at a time)"
+                "tapered_launches": ("off in the timed region (passes in flight)"
+                                     + (", on in the roofline leg (one pass at a time)" if args.full else ""))
                                     if in_flight else "on",
                 "clock_ramp_ms": args.ramp_ms,
                 "clock_ramp_steps": ramp_steps,
-                "windows_per_s_one_pass_at_a_time": serial_windows / (launch_ms * 1e-3),
                 "sharding": shard_note,
                 "device": arch,
                 "parallelism": f"ctg-sharded x{world}, no collective on the data path",
                 "collectives": (f"{backend}: barrier + MAX(time) + SUM(windows) around the timed region"
                                 if dist is not None else "none (one rank)"),
             },
-            "roofline": {
-                "bound": "hbm",
-                "kernel": kernel_name,
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBPS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBPS,
-                "traffic": traffic,
-                "traffic_source": (f"{traffic_src}: 2 x FETCH_SIZE + WRITE_SIZE of separate rocprofv3 --pmc passes over "
-                                   f"this command (committed profile, not measured in this run)") if traffic_src else None,
-                "algorithmic_bytes": int(serial_windows * step_bytes),
-                "bytes_per_window": step_bytes,
-                "launch_ms": launch_ms,
-                "launches_timed": serial_steps,
-                "achieved_with_passes_in_flight": total_windows / world * step_bytes / dt / 1e9,
-            },
+        }
+    if rank == 0 and args.full:
+        traffic, traffic_src = profiled_traffic(args.workload) if args.scale == 1.0 and args.tile == 0 else (None, None)
+        step_bytes = prm["step"]                       # SURVEY 8(d): `step` bytes read per window
+        achieved = serial_windows * step_bytes / (launch_ms * 1e-3) / 1e9
+        out.update(pass_with_peaks_ms=pass_with_peaks_ms, pass_with_rows_ms=pass_with_rows_ms,
+                   resident_to_tsv_ms=resident_to_tsv_ms)
+        out["config"].update(rows_text_bytes_per_step=rows_text_bytes,
+                             windows_per_s_one_pass_at_a_time=serial_windows / (launch_ms * 1e-3))
+        out["roofline"] = {
+            "bound": "hbm",
+            "kernel": kernel_name,
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBPS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBPS,
+            "traffic": traffic,
+            "traffic_source": (f"{traffic_src}: 2 x FETCH_SIZE + WRITE_SIZE of separate rocprofv3 --pmc passes over "
+                               f"this command (committed profile, not measured in this run)") if traffic_src else None,
+            "algorithmic_bytes": int(serial_windows * step_bytes),
+            "bytes_per_window": step_bytes,
+            "launch_ms": launch_ms,
+            "launches_timed": serial_steps,
+            "achieved_with_passes_in_flight": total_windows / world * step_bytes / dt / 1e9,
         }
         if not args.no_cpu and world == 1:             # the CPU legs run on rank 0 at N=1 only
             cpu_wps, used, done, res, cpu_passes, cpu_dt = cpu_baseline(batches[0], prm)
@@ -620,7 +657,7 @@ def main():
     for ss in sets:
         ss.close()
     del batches
-    if rank == 0 and world == 1 and not args.no_extra and args.scale == 1.0:
+    if args.full and rank == 0 and world == 1 and not args.no_extra and args.scale == 1.0:
         from gams_amd import synth
 
         extra = {}
@@ -704,7 +741,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             extra["error"] = f"{type(e).__name__}: {e}"
         out["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary:
         try:
             out["secondary"] = secondary_metrics(eng)
         except Exception as e:  # noqa: BLE001

@@ -75,3 +75,31 @@ def test_bench_n1_launcher_path_equals_direct_path():
     assert launched["config"]["windows_per_step"] == direct["config"]["windows_per_step"]
     assert launched["config"]["peaks_per_step"] == direct["config"]["peaks_per_step"]
     assert 0.5 < launched["value"] / direct["value"] < 2.0
+
+
+def test_bench_plain_line_dump_outputs_and_full(tmp_path):
+    """A plain run's line is the headline only; --dump-outputs writes the peak records of the LAST timed step, the
+    same in two runs with the same arguments; --full adds the roofline, CPU, end-to-end and secondary blocks."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--workload", "Atha", "--scale", "0.05", "--steps", "7", "--warmup", "2", "--ramp-ms", "5"]
+    a = _one_json_line(_bench(args + ["--dump-outputs", str(tmp_path / "a")]))
+    b = _one_json_line(_bench(args + ["--dump-outputs", str(tmp_path / "b")]))
+    for k in ("roofline", "cpu_baseline", "parity_vs_oracle", "end_to_end", "extra", "secondary", "pass_with_peaks_ms"):
+        assert k not in a
+    assert a["steps"] == 7 and a["unit"] == "windows/s" and a["higher_is_better"] is True and a["dtype"] == "u8"
+    # the ramp runs a multiple of the 3 batches, so the timed steps start at batch 2 % 3 and the last one is 8 % 3
+    w = a["config"]["windows_per_step"]
+    assert a["value"] * a["ms_per_step"] * 1e-3 == pytest.approx(sum(w[(2 + i) % 3] for i in range(7)) / 7, rel=1e-9)
+    fields = ("ctg", "window", "gc_count", "signal")
+    got = {f: np.load(tmp_path / "a" / f"peaks_{f}.npy") for f in fields}
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == sorted(f"peaks_{f}.npy" for f in fields)
+    assert all(v.dtype == np.float64 and v.size == a["config"]["peaks_per_step"][8 % 3] > 0 for v in got.values())
+    assert set(np.unique(got["signal"])) <= {-1.0, 1.0} and np.all(np.diff(got["ctg"]) >= 0)
+    for f in fields:
+        assert np.array_equal(got[f], np.load(tmp_path / "b" / f"peaks_{f}.npy"))
+
+    full = _one_json_line(_bench(args + ["--full"]))
+    assert full["config"]["windows_per_step"] == w and full["config"]["peaks_per_step"] == a["config"]["peaks_per_step"]
+    assert full["roofline"]["launch_ms"] > 0 and full["parity_vs_oracle"] is True and full["cpu_baseline"]["value"] > 0
+    assert full["pass_with_peaks_ms"] > 0 and "error" not in full["end_to_end"] and "error" not in full["secondary"]

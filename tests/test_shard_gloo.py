@@ -180,6 +180,12 @@ def test_bench_refuses_a_world_size_that_contradicts_gpus():
     assert res.returncode != 0 and "WORLD_SIZE=1" in res.stderr
 
 
+def test_bench_refuses_zero_steps():
+    """ms_per_step is the timed region over --steps: a run with no timed step has no such figure"""
+    res = _bench(["--steps", "0"])
+    assert res.returncode != 0 and "--steps must be >= 1" in res.stderr
+
+
 def test_bench_weak_deals_whole_genomes():
     import bench
 

@@ -11,7 +11,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $ROOT
-B="python3 bench.py --no-cpu --no-secondary --one-at-a-time"
+B="python3 bench.py --full --no-cpu --no-secondary --one-at-a-time"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $B "$@" > $OUT/trace.log 2>&1
 echo "trace rc=$?" >> $OUT/trace.log
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B --steps 12 --warmup 2 --ramp-ms 5 "$@" > $OUT/pmc_fetch.log 2>&1
