@@ -98,6 +98,14 @@ PROTOTYPES = {
     "gams_spans_create": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _PP]),
     "gams_spans_destroy": (None, [_VP, _VP]),
     "gams_gpu_cover": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP]),
+    "gams_names_create": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_char_p), _PP]),
+    "gams_names_destroy": (None, [_VP, _VP]),
+    "gams_gpu_locate_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]),
+    "gams_gpu_count_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64),
+                                      C.POINTER(C.c_uint64)]),
+    "gams_gpu_anno_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int, C.c_char_p, C.c_uint32,
+                                     C.c_uint32, _PP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gams_gpu_valid_spans": (C.c_int, [_VP, _VP, C.c_uint64, C.c_int32, C.c_int32, _VP, _VP, C.c_uint64,
                                        C.POINTER(C.c_uint64)]),
 }

@@ -59,6 +59,8 @@ struct gams_gpu {
     size_t sw_text_bytes = 0;
     unsigned long long *sw_words = nullptr;
     size_t sw_words_bytes = 0;
+    // gams_gpu_locate_text / count_text / anno_text: the cached device copy of the input and each entry's last text
+    struct gams_text_state *text = nullptr;
     // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel FUNCTION (per device), not to a plan:
     // the largest value any launch on this handle has asked for, per function; only ever raised (gams_lds_attr)
     // counts the launches that read a seqset (any stream of the handle): gams_seqset_upload_image queues the
@@ -84,6 +86,8 @@ inline hipError_t gams_lds_attr(gams_gpu_t *h, const void *func, size_t bytes) {
 // of the block handed out (>= bytes); pass it back to gams_pool_free.
 hipError_t gams_pool_alloc(gams_gpu_t *h, bool pinned, size_t bytes, void **out, size_t *cap);
 void gams_pool_free(gams_gpu_t *h, bool pinned, void *p, size_t cap);
+// text.hip: return the text entries' buffers to the pools (gams_gpu_destroy)
+void gams_text_free(gams_gpu_t *h);
 
 inline int gams_fail(gams_gpu_t *h, int code, const std::string &msg) {
     (void)hipGetLastError();   // a failed HIP call is reported through the code; it must not stay sticky

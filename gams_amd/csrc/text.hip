@@ -1,0 +1,848 @@
+// text.hip -- text in, text out for the interval commands: the bytes of a `locate -f` / `locate --count` /
+// `anno` input file go to the device once, and the finished TSV rows come back.
+//
+//   gams_gpu_locate_text   locate.rs:84-141 with utils.rs:7-22   "{rg}\t{ctg_id}\n"
+//   gams_gpu_count_text    locate.rs:84-141 with utils.rs:24-36  "{rg}\t{count}\n"
+//   gams_gpu_anno_text     anno.rs:95-142 (one input file)       "{line}\t{prop:.4}\n"
+//
+// Pipeline (one handle, the compute stream):
+//   1. one copy of the bytes into a cached device buffer, padded with spaces to 16 B and 16 B beyond;
+//   2. line index: every lane takes 64 contiguous bytes as four 16-B loads, counts the '\n' bytes with an exact
+//      zero-byte mask and flags bytes >= 0x80 or NUL; a one-workgroup scan of the block counts and a second pass
+//      turn them into 64-bit line starts (BufRead::lines(): split on '\n', one '\r' before it dropped);
+//   3. parse, one lane per line: the field(s), Range::from_str, the chromosome (and for anno the ctg id) looked up
+//      in a device hash table of names (gams_names_t);
+//   4. the existing lookup kernels (interval_kernels.hpp) on those device columns;
+//   5. row lengths -> block scan -> rows written at their offsets, echoing the input bytes; one read-back into
+//      page-locked memory owned by the handle.
+// Three host waits per call: the line count (to size the per-line columns), the flags and the text size (to size
+// the text), the text.
+
+#include "interval_kernels.hpp"
+#include "text_fmt.hpp"
+
+#include <algorithm>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+// one slot of the open-addressing table: 64-bit hash of the name and its position (UINT32_MAX: empty)
+struct NameSlot {
+    unsigned long long hash;
+    uint32_t idx;
+    uint32_t pad;
+};
+
+struct NameTab {
+    const NameSlot *slot;
+    const unsigned long long *off;   // n + 1 byte offsets into bytes
+    const char *bytes;
+    uint32_t mask;                   // slots - 1 (slots a power of two >= 2n: load <= 0.5)
+    uint32_t n;
+};
+
+struct gams_names {
+    NameTab t{};
+    uint8_t *arena = nullptr;
+    size_t arena_bytes = 0;
+};
+
+// What the text entries keep on the handle: the device copy of the input (grows, cached) and the page-locked
+// text of each entry's last call.
+struct gams_text_state {
+    uint8_t *d_in = nullptr;
+    size_t d_in_cap = 0;
+    char *out[3] = {};
+    size_t out_cap[3] = {};
+};
+
+void gams_text_free(gams_gpu_t *h) {
+    gams_text_state *t = h->text;
+    if (!t) return;
+    gams_pool_free(h, false, t->d_in, t->d_in_cap);
+    for (int k = 0; k < 3; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
+    delete t;
+    h->text = nullptr;
+}
+
+namespace {
+
+// FNV-1a, 64 bits, over the name's bytes (host and device)
+__host__ __device__ inline unsigned long long name_hash(const char *s, uint64_t n) {
+    unsigned long long x = 0xcbf29ce484222325ull;
+    for (uint64_t i = 0; i < n; ++i) {
+        x ^= (uint8_t)s[i];
+        x *= 0x100000001b3ull;
+    }
+    return x;
+}
+
+// position of the name s[0..n) in the table, UINT32_MAX if absent (exact byte equality)
+__device__ inline uint32_t name_find(const NameTab &t, const char *s, uint64_t n) {
+    if (t.n == 0) return UINT32_MAX;
+    const unsigned long long x = name_hash(s, n);
+    for (uint32_t i = (uint32_t)x & t.mask;; i = (i + 1u) & t.mask) {
+        const NameSlot sl = t.slot[i];
+        if (sl.idx == UINT32_MAX) return UINT32_MAX;
+        if (sl.hash != x) continue;
+        const unsigned long long b = t.off[sl.idx];
+        if (t.off[sl.idx + 1u] - b != n) continue;
+        uint64_t k = 0;
+        while (k < n && t.bytes[b + k] == s[k]) ++k;
+        if (k == n) return sl.idx;
+    }
+}
+
+enum : uint32_t {
+    W_NL = 0,      // '\n' bytes of the input
+    W_BAD = 1,     // a byte >= 0x80 or NUL
+    W_EFIELD = 2,  // anno: a line without field idx_id or idx_range
+    W_EID = 3,     // anno: a ctg id not in ctg_ids on a chromosome of the set
+    W_UNSUP = 4,   // count: a located ctg without an rg group; anno: a prop that is not finite in [0, 1]
+    W_BYTES = 5,   // text bytes
+    W_ROWS = 6,    // rows
+    W_COUNT = 8
+};
+
+constexpr uint32_t kIdxBytes = 256u * 64u;   // bytes per workgroup of the line-index kernels
+
+// 0x80 in exactly the zero bytes of y
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t y) {
+    return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
+}
+__device__ __forceinline__ uint32_t nl_mask(uint32_t w) { return zero_bytes(w ^ 0x0a0a0a0au); }
+__device__ __forceinline__ uint32_t bad_mask(uint32_t w) { return (w & 0x80808080u) | zero_bytes(w); }
+
+// pass 1: '\n' per workgroup of kIdxBytes, and the flag of refused bytes.  n16: the input rounded up to 16 B
+// (the padding holds spaces).
+__global__ __launch_bounds__(256) void text_nl_count_kernel(const uint8_t *in, uint64_t n16, uint32_t *blk_nl,
+                                                            unsigned long long *words) {
+    __shared__ uint32_t ws[4];
+    const uint64_t p0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 64u;
+    uint32_t c = 0, bad = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < 4u; ++u) {
+        const uint64_t p = p0 + 16u * u;
+        if (p >= n16) break;
+        const uint4 v = *reinterpret_cast<const uint4 *>(in + p);
+        c += __popc(nl_mask(v.x)) + __popc(nl_mask(v.y)) + __popc(nl_mask(v.z)) + __popc(nl_mask(v.w));
+        bad |= bad_mask(v.x) | bad_mask(v.y) | bad_mask(v.z) | bad_mask(v.w);
+    }
+    if (bad) words[W_BAD] = 1ull;
+    uint32_t tot;
+    (void)block_excl_scan_256<uint32_t>(c, ws, tot);
+    if (threadIdx.x == 0) blk_nl[blockIdx.x] = tot;
+}
+
+// exclusive prefix of nb block counts (one workgroup of 1024), the total into words[slot]
+template <typename T>
+__global__ __launch_bounds__(1024) void text_blk_scan_kernel(const T *blk, uint32_t nb, unsigned long long *blk_off,
+                                                             unsigned long long *words, uint32_t slot) {
+    __shared__ unsigned long long wsum[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t per = (nb + 1023u) / 1024u;
+    const uint32_t b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
+    unsigned long long mine = 0;
+    for (uint32_t b = b0; b < b1; ++b) mine += blk[b];
+    const unsigned long long inc = wave_incl_scan_u64(mine);
+    if (lane == 63u) wsum[wv] = inc;
+    __syncthreads();
+    unsigned long long base = 0, all = 0;
+    for (uint32_t w = 0; w < 16u; ++w) {
+        if (w < wv) base += wsum[w];
+        all += wsum[w];
+    }
+    unsigned long long off = base + inc - mine;
+    for (uint32_t b = b0; b < b1; ++b) {
+        blk_off[b] = off;
+        off += blk[b];
+    }
+    if (tid == 0u) {
+        blk_off[nb] = all;
+        words[slot] = all;
+    }
+}
+
+// pass 2: starts[k + 1] = position after the k-th '\n'; starts[0] = 0 and starts[nl + 1] = n + 1, so that line i
+// is [starts[i], starts[i + 1] - 1) before the '\r' rule
+__global__ __launch_bounds__(256) void text_line_start_kernel(const uint8_t *in, uint64_t n, uint64_t n16,
+                                                              const unsigned long long *blk_off, uint64_t nl,
+                                                              unsigned long long *starts) {
+    __shared__ uint32_t ws[4];
+    const uint64_t p0 = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 64u;
+    uint4 v[4];
+    uint32_t c = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < 4u; ++u) {
+        const uint64_t p = p0 + 16u * u;
+        v[u] = p < n16 ? *reinterpret_cast<const uint4 *>(in + p) : make_uint4(0u, 0u, 0u, 0u);
+        c += __popc(nl_mask(v[u].x)) + __popc(nl_mask(v[u].y)) + __popc(nl_mask(v[u].z)) + __popc(nl_mask(v[u].w));
+    }
+    uint32_t tot;
+    const uint32_t rel = block_excl_scan_256<uint32_t>(c, ws, tot);
+    unsigned long long *dst = starts + 1u + blk_off[blockIdx.x] + rel;
+#pragma unroll
+    for (uint32_t u = 0; u < 4u; ++u) {
+        const uint32_t w4[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            uint32_t m = nl_mask(w4[k]);
+            while (m) {
+                const uint32_t byte = (uint32_t)__builtin_ctz(m) >> 3;
+                *dst++ = p0 + 16u * u + 4u * k + byte + 1u;
+                m &= m - 1u;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        starts[0] = 0;
+        starts[nl + 1u] = n + 1u;
+    }
+}
+
+struct TextLines {
+    const char *in;
+    const unsigned long long *starts;
+    uint64_t nl;
+    uint32_t n_lines;
+};
+
+__device__ __forceinline__ void line_of(const TextLines &t, uint32_t i, uint64_t &b, uint64_t &e) {
+    b = t.starts[i];
+    e = t.starts[i + 1u] - 1u;
+    if (i < t.nl && e > b && t.in[e - 1u] == '\r') --e;   // "\r\n" ends the line; a last line keeps its '\r'
+}
+
+__device__ __forceinline__ bool is_word_c(char c) {
+    return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || c == '_';
+}
+__device__ __forceinline__ bool is_digit_c(char c) { return c >= '0' && c <= '9'; }
+
+// The run of digits at s[p..e), looked at up to its eleventh digit (a run of more than ten is invalid anyway): p moves
+// past what was looked at; the value is that of the first ten digits, or 0x80000000 for any value above INT32_MAX.
+// Branch-free over a fixed trip count in 32-bit arithmetic (the input buffer carries 16 bytes of padding, so the
+// eleven loads stay inside it): the branchy 64-bit form of this loop came out of the compiler returning a wrong
+// value for one of the two runs of a range.
+__device__ __forceinline__ uint32_t digits(const char *s, uint64_t &p, uint64_t e) {
+    uint32_t v = 0, nd = 0;
+    bool run = true, over = false;
+#pragma unroll
+    for (uint32_t u = 0; u < 11u; ++u) {
+        const uint32_t d = (uint32_t)(uint8_t)s[p + u] - (uint32_t)'0';
+        run = run && (p + u < e) && d < 10u;
+        const bool take = run && u < 10u;
+        over = over || (take && (v > 214748364u || v * 10u + d > 0x7fffffffu));
+        v = take && !over ? v * 10u + d : v;
+        nd += run ? 1u : 0u;
+    }
+    p += nd;
+    return over ? 0x80000000u : v;
+}
+
+// intspan Range::from_str over s[b, e) (gams_host.cpp Range::from_str, step for step): on success the chromosome
+// is s[cb, ce) and the range start..end
+struct RangeField {
+    uint64_t cb, ce;      // the chromosome: s[cb, ce)
+    uint32_t start, end;
+    bool ok;
+};
+
+__device__ RangeField parse_range(const char *s, uint64_t b, uint64_t e) {
+    RangeField r{0, 0, 0, 0, false};
+    while (e > b && (s[e - 1u] == '\r' || s[e - 1u] == '\n' || s[e - 1u] == ' ')) --e;
+    // rfind(':'): past the last colon only digits and separators can follow in a valid range
+    uint64_t c = e;
+    while (c > b) {
+        const char x = s[c - 1u];
+        if (x == ':') break;
+        if (!(is_digit_c(x) || x == '-' || x == '_')) return r;
+        --c;
+    }
+    if (c == b) return r;                 // no colon
+    const uint64_t colon = c - 1u;
+    if (colon == b || colon + 1u >= e) return r;
+    uint64_t i = colon + 1u, k;
+    const uint32_t st = digits(s, i, e);
+    if (i == colon + 1u || i - colon - 1u > 10u) return r;
+    uint32_t en = st;
+    if (i < e) {
+        uint64_t j = i;
+        while (j < e && (s[j] == '-' || s[j] == '_')) ++j;
+        if (j == i) return r;
+        k = j;
+        en = digits(s, k, e);
+        if (k == j || k != e || k - j > 10u) return r;
+    }
+    if (st > 0x7fffffffu || en > 0x7fffffffu) return r;
+    // head: [name.]chr[(strand)]
+    uint64_t hb = b, he = colon;
+    if (he > hb && s[he - 1u] == ')') {
+        uint64_t o = he - 1u;
+        while (o > hb && s[o - 1u] != '(') --o;
+        if (o == hb) return r;            // no '('
+        he = o - 1u;
+    }
+    for (uint64_t d = hb; d < he; ++d)
+        if (s[d] == '.') {
+            hb = d + 1u;
+            break;
+        }
+    if (he == hb) return r;
+    for (uint64_t d = hb; d < he; ++d) {
+        const char x = s[d];
+        if (!(is_word_c(x) || x == '-' || x == '/')) return r;
+    }
+    r.cb = hb;
+    r.ce = he;
+    r.start = st;
+    r.end = en;
+    r.ok = true;
+    return r;
+}
+
+// locate / count: rg = the line up to its first tab (locate.rs:89-91); (group, start, end) and where rg ends
+__global__ __launch_bounds__(256) void text_parse_rg_kernel(const TextLines t, const NameTab chr, uint32_t *grp,
+                                                            uint32_t *qs, uint32_t *qe, unsigned long long *fend) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= t.n_lines) return;
+    uint64_t b, e;
+    line_of(t, i, b, e);
+    uint64_t f = b;
+    while (f < e && t.in[f] != '\t') ++f;
+    const RangeField r = parse_range(t.in, b, f);
+    grp[i] = r.ok ? name_find(chr, t.in + r.cb, r.ce - r.cb) : UINT32_MAX;
+    qs[i] = r.start;
+    qe[i] = r.end;
+    fend[i] = f;
+}
+
+// count: rg group of the located ctg (UINT32_MAX for an unlocated line)
+__global__ __launch_bounds__(256) void text_rg_group_kernel(uint32_t n_lines, const int64_t *hit, const uint32_t *rg_group,
+                                                            uint32_t *cg, unsigned long long *words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_lines) return;
+    const int64_t c = hit[i];
+    uint32_t g = UINT32_MAX;
+    if (c >= 0) {
+        g = rg_group[c];
+        if (g == UINT32_MAX) words[W_UNSUP] = 1ull;   // the host path reports "not found in idx" (utils.rs:30)
+    }
+    cg[i] = g;
+}
+
+struct AnnoArgs {
+    NameTab chr, ids;
+    const int32_t *ctg_start, *ctg_end;
+    uint32_t idx_id, idx_range;
+    uint32_t first;   // 1 with a header line: line 0 is not parsed
+};
+
+// anno.rs:112-139 per line: field idx_id -> first (?i)ctg:[\w_]+:\d+ (utils.rs:118-129); field idx_range -> Range
+__global__ __launch_bounds__(256) void text_parse_anno_kernel(const TextLines t, const AnnoArgs a, uint32_t *grp,
+                                                              int32_t *cl, int32_t *ch, int32_t *qs, int32_t *qe,
+                                                              uint8_t *keep, unsigned long long *words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= t.n_lines) return;
+    grp[i] = UINT32_MAX;
+    keep[i] = 0;
+    if (i < a.first) return;
+    uint64_t b, e;
+    line_of(t, i, b, e);
+    const char *s = t.in;
+    // the two fields, 1-based
+    uint64_t ib = 0, ie = 0, rb = 0, re = 0, fb = b;
+    uint32_t nf = 0, found = 0;
+    for (;;) {
+        uint64_t fe = fb;
+        while (fe < e && s[fe] != '\t') ++fe;
+        ++nf;
+        if (nf == a.idx_id) ib = fb, ie = fe, found |= 1u;
+        if (nf == a.idx_range) rb = fb, re = fe, found |= 2u;
+        if (found == 3u || fe == e) break;
+        fb = fe + 1u;
+    }
+    if (found != 3u) {
+        words[W_EFIELD] = 1ull;                // the reference panics (anno.rs:115)
+        return;
+    }
+    uint64_t xb = 0, xe = 0;
+    bool has_id = false;
+    for (uint64_t p = ib; p + 4u <= ie && !has_id; ++p) {
+        if (!((s[p] == 'c' || s[p] == 'C') && (s[p + 1u] == 't' || s[p + 1u] == 'T') &&
+              (s[p + 2u] == 'g' || s[p + 2u] == 'G') && s[p + 3u] == ':'))
+            continue;
+        uint64_t j = p + 4u;
+        while (j < ie && is_word_c(s[j])) ++j;
+        if (j == p + 4u || j >= ie || s[j] != ':') continue;
+        uint64_t k = j + 1u;
+        while (k < ie && is_digit_c(s[k])) ++k;
+        if (k == j + 1u) continue;
+        xb = p;
+        xe = k;
+        has_id = true;
+    }
+    if (!has_id) return;                       // anno.rs:116-119
+    const RangeField r = parse_range(s, rb, re);
+    if (!r.ok) return;                         // anno.rs:123-125
+    const uint32_t g = name_find(a.chr, s + r.cb, r.ce - r.cb);
+    int32_t c0 = 0, c1 = 0;
+    if (g != UINT32_MAX) {                     // anno.rs:129
+        const uint32_t slot = name_find(a.ids, s + xb, xe - xb);
+        if (slot == UINT32_MAX) {
+            words[W_EID] = 1ull;               // the reference panics (redis.rs:133-134)
+            return;
+        }
+        c0 = a.ctg_start[slot];
+        c1 = a.ctg_end[slot];
+    }
+    grp[i] = g;
+    cl[i] = c0;
+    ch[i] = c1;
+    qs[i] = (int32_t)r.start;
+    qe[i] = (int32_t)r.end;
+    keep[i] = 1;
+}
+
+__device__ __forceinline__ uint32_t dec_len(int32_t v) {
+    uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v, n = v < 0 ? 2u : 1u;
+    while (u >= 10u) {
+        u /= 10u;
+        ++n;
+    }
+    return n;
+}
+
+__device__ __forceinline__ char *put_dec(char *q, int32_t v) {
+    const uint32_t n = dec_len(v);
+    uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+    if (v < 0) *q = '-';
+    char *p = q + n;
+    do {
+        *--p = (char)('0' + u % 10u);
+        u /= 10u;
+    } while (u);
+    return q + n;
+}
+
+__device__ __forceinline__ char *put_bytes(char *q, const char *src, uint64_t n) {
+    for (uint64_t k = 0; k < n; ++k) q[k] = src[k];
+    return q + n;
+}
+
+enum : int { K_LOCATE = 0, K_COUNT = 1, K_ANNO = 2 };
+
+struct RowArgs {
+    TextLines t;
+    int kind;
+    const unsigned long long *fend;   // locate / count: end of the rg field
+    const int64_t *hit;               // locate / count
+    NameTab ids;                      // locate: ctg id text
+    const int32_t *cnt;               // count
+    const uint8_t *keep;              // anno
+    const uint32_t *grp;              // anno: span group (UINT32_MAX: chromosome not in the set)
+    const int32_t *qs, *qe;           // anno
+    const float *prop;                // anno
+    const char *prefix;               // anno header
+    uint32_t prefix_len;
+    uint32_t header;
+    unsigned long long *blk_bytes;    // per workgroup of 256 rows
+    const unsigned long long *blk_off;
+    unsigned long long *words;
+    char *text;
+};
+
+// bytes of the row of line i (0: no row); `bad`: the value has no text of the reference's
+__device__ uint64_t row_len(const RowArgs &a, uint32_t i, bool &bad) {
+    uint64_t b, e;
+    if (a.kind == K_ANNO) {
+        line_of(a.t, i, b, e);
+        if (a.header && i == 0u) return (e - b) + 1u + a.prefix_len + 5u;   // "{line}\t{prefix}Prop\n"
+        if (!a.keep[i]) return 0;
+        const float p = a.prop[i];
+        // a reversed range on a chromosome of the set: the reference's prop is 0/0
+        if (a.grp[i] != UINT32_MAX && (a.qe[i] < a.qs[i] || !(p >= 0.0f && p <= 1.0f))) bad = true;
+        return (e - b) + 8u;                                                 // "\t0.0000\n"
+    }
+    const int64_t c = a.hit[i];
+    if (c < 0) return 0;
+    b = a.t.starts[i];
+    const uint64_t flen = a.fend[i] - b;
+    if (a.kind == K_LOCATE) return flen + 2u + (a.ids.off[c + 1] - a.ids.off[c]);
+    return flen + 2u + dec_len(a.cnt[i]);
+}
+
+__global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
+    __shared__ uint64_t ws[4];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    const uint64_t l = i < a.t.n_lines ? row_len(a, i, bad) : 0ull;
+    if (bad) a.words[W_UNSUP] = 1ull;
+    uint64_t tot;
+    (void)block_excl_scan_256<uint64_t>(l, ws, tot);
+    __shared__ uint32_t rows[4];
+    uint32_t r = __popcll(__ballot(l != 0ull));
+    if ((threadIdx.x & 63u) == 0u) rows[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        a.blk_bytes[blockIdx.x] = tot;
+        atomicAdd(a.words + W_ROWS, (unsigned long long)(rows[0] + rows[1] + rows[2] + rows[3]));
+    }
+}
+
+__global__ __launch_bounds__(256) void text_row_write_kernel(const RowArgs a) {
+    __shared__ uint64_t ws[4];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    const uint64_t l = i < a.t.n_lines ? row_len(a, i, bad) : 0ull;
+    uint64_t tot;
+    const uint64_t rel = block_excl_scan_256<uint64_t>(l, ws, tot);
+    if (l == 0ull) return;
+    char *q = a.text + a.blk_off[blockIdx.x] + rel;
+    uint64_t b, e;
+    if (a.kind == K_ANNO) {
+        line_of(a.t, i, b, e);
+        q = put_bytes(q, a.t.in + b, e - b);
+        *q++ = '\t';
+        if (a.header && i == 0u) {
+            q = put_bytes(q, a.prefix, a.prefix_len);
+            q = put_bytes(q, "Prop\n", 5u);
+            return;
+        }
+        (void)gams_fmt_prop4(a.prop[i], q);   // anno.rs:140 (checked in [0, 1] by the length pass)
+        q[6] = '\n';
+        return;
+    }
+    b = a.t.starts[i];
+    q = put_bytes(q, a.t.in + b, a.fend[i] - b);
+    *q++ = '\t';
+    if (a.kind == K_LOCATE) {
+        const int64_t c = a.hit[i];
+        const unsigned long long o = a.ids.off[c];
+        q = put_bytes(q, a.ids.bytes + o, a.ids.off[c + 1] - o);   // locate.rs:139
+    } else {
+        q = put_dec(q, a.cnt[i]);                                    // locate.rs:137
+    }
+    *q = '\n';
+}
+
+struct TextJob {
+    int kind;
+    const gams_index_t *ctg_ix;
+    const gams_index_t *rg_ix;
+    const gams_names_t *chr, *ids;
+    const uint32_t *rg_group;          // count: ctg_ix->m entries
+    const gams_spans_t *sp;
+    const int32_t *ctg_start, *ctg_end;
+    int header;
+    const char *prefix;
+    uint32_t idx_id, idx_range;
+};
+
+const char *const kEntry[3] = {"gpu_locate_text", "gpu_count_text", "gpu_anno_text"};
+
+int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_bytes, const char **text,
+             uint64_t *text_bytes, uint64_t *n_rows) {
+    const std::string who = kEntry[J.kind];
+    *text = nullptr;
+    *text_bytes = 0;
+    *n_rows = 0;
+    GAMS_HIP(h, hipSetDevice(h->device));
+    if (!h->text) h->text = new gams_text_state();
+    gams_text_state *T = h->text;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const uint64_t n16 = (n_bytes + 15u) & ~15ull;
+    // 1. upload into the cached buffer; the 16-B tail is spaces (no '\n', nothing refused)
+    const uint64_t n_pad = n16 + 16u;                 // the parse kernels may look 11 bytes past a field's end
+    if (T->d_in_cap < n_pad) {
+        gams_pool_free(h, false, T->d_in, T->d_in_cap);
+        T->d_in = nullptr;
+        T->d_in_cap = 0;
+        const hipError_t e = gams_pool_alloc(h, false, n_pad, reinterpret_cast<void **>(&T->d_in), &T->d_in_cap);
+        if (e != hipSuccess)
+            return gams_fail(h, e == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP, who + ": input buffer: " + hipGetErrorString(e));
+    }
+    hipStream_t st = h->compute;
+    const uint32_t nbi = (uint32_t)std::max<uint64_t>(1, (n16 + kIdxBytes - 1) / kIdxBytes);
+    const size_t b_words = al(W_COUNT * 8), b_bnl = al((size_t)nbi * 4), b_bnloff = al(((size_t)nbi + 1) * 8);
+    uint8_t *s0 = nullptr, *s1 = nullptr;
+    size_t s0_cap = 0, s1_cap = 0;
+    struct Guard {
+        gams_gpu_t *h;
+        uint8_t **a, **b;
+        size_t *ac, *bc;
+        ~Guard() {
+            (void)hipStreamSynchronize(h->compute);
+            gams_pool_free(h, false, *a, *ac);
+            gams_pool_free(h, false, *b, *bc);
+        }
+    } guard{h, &s0, &s1, &s0_cap, &s1_cap};
+#define T_HIP(call)                                                                                  \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return gams_fail(h, e_ == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,                 \
+                             who + ": " + #call + ": " + hipGetErrorString(e_));                     \
+    } while (0)
+    T_HIP(gams_pool_alloc(h, false, b_words + b_bnl + b_bnloff, reinterpret_cast<void **>(&s0), &s0_cap));
+    unsigned long long *d_words = reinterpret_cast<unsigned long long *>(s0);
+    uint32_t *d_bnl = reinterpret_cast<uint32_t *>(s0 + b_words);
+    unsigned long long *d_bnloff = reinterpret_cast<unsigned long long *>(s0 + b_words + b_bnl);
+    T_HIP(hipEventRecord(h->k0, st));
+    h->k_valid = false;
+    h->kq_used = 0;
+    T_HIP(hipMemsetAsync(d_words, 0, W_COUNT * 8, st));
+    if (n_bytes) T_HIP(hipMemcpyAsync(T->d_in, bytes, n_bytes, hipMemcpyHostToDevice, st));
+    T_HIP(hipMemsetAsync(T->d_in + n_bytes, ' ', n_pad - n_bytes, st));
+    // 2. line index, pass 1
+    hipLaunchKernelGGL(text_nl_count_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n16, d_bnl, d_words);
+    hipLaunchKernelGGL(text_blk_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_bnl, nbi, d_bnloff, d_words, (uint32_t)W_NL);
+    T_HIP(hipGetLastError());
+    T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, 2 * 8, hipMemcpyDeviceToHost, st));
+    T_HIP(hipStreamSynchronize(st));
+    const uint64_t nl = h->pin_scratch[W_NL];
+    if (h->pin_scratch[W_BAD])
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": the input holds a byte >= 0x80 or a NUL (use the host path)");
+    const uint64_t L64 = n_bytes == 0 ? 0 : nl + (bytes[n_bytes - 1] != '\n' ? 1u : 0u);
+    if (L64 > 0xffffffffull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 1 lines");
+    const uint32_t L = (uint32_t)L64;
+    if (J.kind == K_ANNO && L > (uint32_t)(J.header ? 1 : 0) && (J.idx_id == 0 || J.idx_range == 0))
+        return gams_fail(h, GAMS_EINVAL, who + ": field index 0 (the reference panics, anno.rs:115)");
+    if (L == 0) {
+        *text = "";
+        return GAMS_OK;
+    }
+    // per-line columns
+    const uint32_t nbr = (L + 255u) / 256u;
+    const size_t b_starts = al(((size_t)nl + 2) * 8), b_u32 = al((size_t)L * 4), b_u64 = al((size_t)L * 8),
+                 b_u8 = al(L), b_blk = al(((size_t)nbr + 1) * 8);
+    const uint64_t m_ctg = J.kind == K_ANNO ? 0 : J.ctg_ix->m, n_ids = J.ids ? J.ids->t.n : 0;
+    const size_t b_rgg = J.kind == K_COUNT ? al(std::max<uint64_t>(m_ctg, 1) * 4) : 0;
+    const size_t b_cpos = J.kind == K_ANNO ? al(std::max<uint64_t>(n_ids, 1) * 4) : 0;
+    const size_t prefix_len = J.kind == K_ANNO && J.header && J.prefix ? strlen(J.prefix) : 0;
+    const size_t b_pre = al(prefix_len + 1);
+    // grp qs qe cg cnt | fend hit | keep | blocks (bytes, offsets) | rg_group | ctg_start ctg_end | prefix
+    const size_t need = b_starts + 5 * b_u32 + 2 * b_u64 + b_u8 + 2 * b_blk + b_rgg + 2 * b_cpos + b_pre;
+    T_HIP(gams_pool_alloc(h, false, need, reinterpret_cast<void **>(&s1), &s1_cap));
+    uint8_t *p = s1;
+    auto take = [&](size_t b) {
+        uint8_t *q = p;
+        p += b;
+        return q;
+    };
+    unsigned long long *d_starts = reinterpret_cast<unsigned long long *>(take(b_starts));
+    uint32_t *d_grp = reinterpret_cast<uint32_t *>(take(b_u32));
+    uint32_t *d_qs = reinterpret_cast<uint32_t *>(take(b_u32));
+    uint32_t *d_qe = reinterpret_cast<uint32_t *>(take(b_u32));
+    uint32_t *d_cg = reinterpret_cast<uint32_t *>(take(b_u32));     // count: rg group; anno: clip lo
+    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(take(b_u32));    // count: counts; anno: clip hi
+    unsigned long long *d_fend = reinterpret_cast<unsigned long long *>(take(b_u64));   // anno: prop
+    int64_t *d_hit = reinterpret_cast<int64_t *>(take(b_u64));
+    uint8_t *d_keep = take(b_u8);
+    unsigned long long *d_bbytes = reinterpret_cast<unsigned long long *>(take(b_blk));
+    unsigned long long *d_boff = reinterpret_cast<unsigned long long *>(take(b_blk));
+    uint32_t *d_rgg = reinterpret_cast<uint32_t *>(take(b_rgg));
+    int32_t *d_cs = reinterpret_cast<int32_t *>(take(b_cpos));
+    int32_t *d_ce = reinterpret_cast<int32_t *>(take(b_cpos));
+    char *d_pre = reinterpret_cast<char *>(take(b_pre));
+    if (b_rgg && m_ctg) T_HIP(hipMemcpyAsync(d_rgg, J.rg_group, m_ctg * 4, hipMemcpyHostToDevice, st));
+    if (b_cpos && n_ids) {
+        T_HIP(hipMemcpyAsync(d_cs, J.ctg_start, n_ids * 4, hipMemcpyHostToDevice, st));
+        T_HIP(hipMemcpyAsync(d_ce, J.ctg_end, n_ids * 4, hipMemcpyHostToDevice, st));
+    }
+    if (prefix_len) T_HIP(hipMemcpyAsync(d_pre, J.prefix, prefix_len, hipMemcpyHostToDevice, st));
+    // 2. line index, pass 2
+    hipLaunchKernelGGL(text_line_start_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n_bytes, n16, d_bnloff, nl, d_starts);
+    const TextLines tl{reinterpret_cast<const char *>(T->d_in), d_starts, nl, L};
+    RowArgs ra{};
+    ra.t = tl;
+    ra.kind = J.kind;
+    ra.blk_bytes = d_bbytes;
+    ra.blk_off = d_boff;
+    ra.words = d_words;
+    // 3. parse + 4. lookups
+    if (J.kind == K_ANNO) {
+        AnnoArgs aa{J.chr->t, J.ids->t, d_cs, d_ce, J.idx_id, J.idx_range, J.header ? 1u : 0u};
+        int32_t *d_cl = reinterpret_cast<int32_t *>(d_cg), *d_ch = reinterpret_cast<int32_t *>(d_cnt);
+        float *d_prop = reinterpret_cast<float *>(d_fend);
+        hipLaunchKernelGGL(text_parse_anno_kernel, dim3(nbr), dim3(256), 0, st, tl, aa, d_grp, d_cl, d_ch,
+                           reinterpret_cast<int32_t *>(d_qs), reinterpret_cast<int32_t *>(d_qe), d_keep, d_words);
+        launch_span_cover(J.sp, d_grp, d_cl, d_ch, reinterpret_cast<const int32_t *>(d_qs),
+                          reinterpret_cast<const int32_t *>(d_qe), L, d_prop, st);
+        ra.keep = d_keep;
+        ra.grp = d_grp;
+        ra.qs = reinterpret_cast<const int32_t *>(d_qs);
+        ra.qe = reinterpret_cast<const int32_t *>(d_qe);
+        ra.prop = d_prop;
+        ra.prefix = d_pre;
+        ra.prefix_len = (uint32_t)prefix_len;
+        ra.header = J.header ? 1u : 0u;
+    } else {
+        hipLaunchKernelGGL(text_parse_rg_kernel, dim3(nbr), dim3(256), 0, st, tl, J.chr->t, d_grp, d_qs, d_qe, d_fend);
+        launch_interval_locate(J.ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
+        if (J.kind == K_COUNT) {
+            hipLaunchKernelGGL(text_rg_group_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_rgg, d_cg, d_words);
+            launch_interval_count(J.rg_ix, d_cg, d_qs, d_qe, L, reinterpret_cast<int32_t *>(d_cnt), st);
+        }
+        ra.fend = d_fend;
+        ra.hit = d_hit;
+        ra.ids = J.kind == K_LOCATE ? J.ids->t : NameTab{};
+        ra.cnt = reinterpret_cast<const int32_t *>(d_cnt);
+    }
+    // 5. row lengths and their offsets
+    hipLaunchKernelGGL(text_row_len_kernel, dim3(nbr), dim3(256), 0, st, ra);
+    hipLaunchKernelGGL(text_blk_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_bbytes, nbr, d_boff, d_words,
+                       (uint32_t)W_BYTES);
+    T_HIP(hipGetLastError());
+    T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+    T_HIP(hipStreamSynchronize(st));
+    const unsigned long long *w = h->pin_scratch;
+    if (w[W_EFIELD]) return gams_fail(h, GAMS_EINVAL, who + ": field index out of range (the reference panics, anno.rs:115)");
+    if (w[W_EID])
+        return gams_fail(h, GAMS_EINVAL, who + ": a ctg id not in ctg_ids on a chromosome of the set (the reference "
+                                               "panics, redis.rs:133-134)");
+    if (w[W_UNSUP])
+        return gams_fail(h, GAMS_EUNSUPPORTED,
+                         who + (J.kind == K_COUNT ? ": a located ctg has no rg group (use the host path)"
+                                                  : ": a prop that is not a finite value in [0, 1] (use the host path)"));
+    const uint64_t tb = w[W_BYTES], rows = w[W_ROWS];
+    // the text: device buffer from the pool, read back into the entry's page-locked buffer
+    char *&out = T->out[J.kind];
+    size_t &out_cap = T->out_cap[J.kind];
+    if (out_cap < std::max<uint64_t>(tb, 1)) {
+        gams_pool_free(h, true, out, out_cap);
+        out = nullptr;
+        out_cap = 0;
+        T_HIP(gams_pool_alloc(h, true, std::max<uint64_t>(tb, 1), reinterpret_cast<void **>(&out), &out_cap));
+    }
+    if (tb) {
+        char *d_text = nullptr;
+        size_t d_text_cap = 0;
+        T_HIP(gams_pool_alloc(h, false, tb, reinterpret_cast<void **>(&d_text), &d_text_cap));
+        ra.text = d_text;
+        hipLaunchKernelGGL(text_row_write_kernel, dim3(nbr), dim3(256), 0, st, ra);
+        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out, d_text, tb, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipEventRecord(h->k1, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(st);
+        gams_pool_free(h, false, d_text, d_text_cap);
+        if (e != hipSuccess) return gams_fail(h, GAMS_EHIP, who + ": text: " + hipGetErrorString(e));
+    } else {
+        T_HIP(hipEventRecord(h->k1, st));
+        T_HIP(hipStreamSynchronize(st));
+    }
+    h->k_valid = true;
+#undef T_HIP
+    *text = out;
+    *text_bytes = tb;
+    *n_rows = rows;
+    return GAMS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_names_t **out) {
+    if (!h || !out || (n && !names)) return gams_fail(h, GAMS_EINVAL, "names_create: null argument");
+    if (n > 0x7fffffffu) return gams_fail(h, GAMS_EUNSUPPORTED, "names_create: more than 2^31 - 1 names");
+    std::vector<unsigned long long> off((size_t)n + 1, 0);
+    std::string bytes;
+    std::unordered_set<std::string> seen;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!names[i]) return gams_fail(h, GAMS_EINVAL, "names_create: null name");
+        const std::string s(names[i]);
+        if (!seen.insert(s).second) return gams_fail(h, GAMS_EINVAL, "names_create: duplicate name '" + s + "'");
+        bytes += s;
+        off[i + 1] = bytes.size();
+    }
+    uint32_t slots = 2;
+    while (slots < 2ull * n) slots <<= 1;
+    std::vector<NameSlot> tab(slots, NameSlot{0ull, UINT32_MAX, 0u});
+    for (uint32_t i = 0; i < n; ++i) {
+        const unsigned long long x = name_hash(bytes.data() + off[i], off[i + 1] - off[i]);
+        uint32_t k = (uint32_t)x & (slots - 1u);
+        while (tab[k].idx != UINT32_MAX) k = (k + 1u) & (slots - 1u);
+        tab[k] = NameSlot{x, i, 0u};
+    }
+    GAMS_HIP(h, hipSetDevice(h->device));
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_tab = al((size_t)slots * sizeof(NameSlot)), b_off = al(off.size() * 8), b_bytes = al(bytes.size() + 1);
+    gams_names_t *nm = new gams_names_t();
+    hipError_t e = gams_pool_alloc(h, false, b_tab + b_off + b_bytes, reinterpret_cast<void **>(&nm->arena), &nm->arena_bytes);
+    if (e == hipSuccess) e = hipMemcpy(nm->arena, tab.data(), tab.size() * sizeof(NameSlot), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(nm->arena + b_tab, off.data(), off.size() * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !bytes.empty()) e = hipMemcpy(nm->arena + b_tab + b_off, bytes.data(), bytes.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        gams_names_destroy(h, nm);
+        return gams_fail(h, e == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP, std::string("names_create: ") + hipGetErrorString(e));
+    }
+    nm->t.slot = reinterpret_cast<const NameSlot *>(nm->arena);
+    nm->t.off = reinterpret_cast<const unsigned long long *>(nm->arena + b_tab);
+    nm->t.bytes = reinterpret_cast<const char *>(nm->arena + b_tab + b_off);
+    nm->t.mask = slots - 1u;
+    nm->t.n = n;
+    *out = nm;
+    return GAMS_OK;
+}
+
+void gams_names_destroy(gams_gpu_t *h, gams_names_t *nm) {
+    if (!nm) return;
+    if (h) {
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->compute);
+    }
+    gams_pool_free(h, false, nm->arena, nm->arena_bytes);
+    delete nm;
+}
+
+int gams_gpu_locate_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const gams_names_t *ctg_ids,
+                         const char *bytes, uint64_t n_bytes, const char **text, uint64_t *text_bytes, uint64_t *n_rows) {
+    if (!h || !ctg_ix || !chr_names || !ctg_ids || (n_bytes && !bytes) || !text || !text_bytes || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_locate_text: null argument");
+    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_locate_text: ctg_ids must name every interval of ctg_ix");
+    TextJob j{};
+    j.kind = K_LOCATE;
+    j.ctg_ix = ctg_ix;
+    j.chr = chr_names;
+    j.ids = ctg_ids;
+    return text_run(h, j, bytes, n_bytes, text, text_bytes, n_rows);
+}
+
+int gams_gpu_count_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, gams_index_t *rg_ix,
+                        const uint32_t *rg_group, const char *bytes, uint64_t n_bytes, const char **text,
+                        uint64_t *text_bytes, uint64_t *n_rows) {
+    if (!h || !ctg_ix || !chr_names || !rg_ix || (ctg_ix->m && !rg_group) || (n_bytes && !bytes) || !text || !text_bytes ||
+        !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_count_text: null argument");
+    TextJob j{};
+    j.kind = K_COUNT;
+    j.ctg_ix = ctg_ix;
+    j.rg_ix = rg_ix;
+    j.chr = chr_names;
+    j.rg_group = rg_group;
+    return text_run(h, j, bytes, n_bytes, text, text_bytes, n_rows);
+}
+
+int gams_gpu_anno_text(gams_gpu_t *h, gams_spans_t *sp, const gams_names_t *chr_names, const gams_names_t *ctg_ids,
+                       const int32_t *ctg_start, const int32_t *ctg_end, const char *bytes, uint64_t n_bytes, int header,
+                       const char *prefix, uint32_t idx_id, uint32_t idx_range, const char **text, uint64_t *text_bytes,
+                       uint64_t *n_rows) {
+    if (!h || !sp || !chr_names || !ctg_ids || (ctg_ids->t.n && (!ctg_start || !ctg_end)) || (n_bytes && !bytes) || !text ||
+        !text_bytes || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_anno_text: null argument");
+    TextJob j{};
+    j.kind = K_ANNO;
+    j.sp = sp;
+    j.chr = chr_names;
+    j.ids = ctg_ids;
+    j.ctg_start = ctg_start;
+    j.ctg_end = ctg_end;
+    j.header = header;
+    j.prefix = prefix;
+    j.idx_id = idx_id;
+    j.idx_range = idx_range;
+    return text_run(h, j, bytes, n_bytes, text, text_bytes, n_rows);
+}
+
+}  // extern "C"

@@ -107,6 +107,16 @@ def load():
     L.gams_host_loader_tsv.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_char_p]
     L.gams_host_peak.restype = C.c_void_p
     L.gams_host_peak.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_char_p]
+    L.gams_host_locate_text.restype = C.c_void_p
+    L.gams_host_locate_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_uint64, C.c_int,
+                                        C.c_char_p, C.POINTER(C.c_uint64)]
+    L.gams_host_anno_text.restype = C.c_void_p
+    L.gams_host_anno_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_char_p, C.c_uint64,
+                                      C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.gams_host_last_operator_device.restype = C.c_int
+    L.gams_host_last_operator_device.argtypes = []
+    L.gams_host_fmt_prop4.restype = C.c_void_p
+    L.gams_host_fmt_prop4.argtypes = [C.c_float]
     L.gams_host_gen.restype = C.c_void_p
     L.gams_host_gen.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
     L.gams_host_fmt_f32.restype = C.c_void_p
@@ -256,6 +266,36 @@ def anno(eng, ctgs, runlists, lines, header=False, prefix="", idx_id=1, idx_rang
     rl = "\n".join(f"{k}\t{v}" for k, v in runlists.items())
     return _take(load().gams_host_anno(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, rl.encode(),
                                        "\n".join(lines).encode(), int(header), prefix.encode(), idx_id, idx_range))
+
+
+def locate_text(eng, ctgs, data, count=False, rg_records=()):
+    """`locate -f` / `locate --count` over the bytes of the input file (text in, text out on the device; the array
+    path where the device refuses).  Returns the rows as bytes; rg_records as for locate()."""
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    rg_lines = "\n".join(f"{c}\t{r}" for c, r in rg_records)
+    out_len = C.c_uint64()
+    return _take_bytes(load().gams_host_locate_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, data, len(data),
+                                                    int(count), rg_lines.encode(), C.byref(out_len)), out_len)
+
+
+def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_range=2):
+    """`anno` over the bytes of one input file; runlists: dict chr -> runlist string.  Returns the rows as bytes."""
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    rl = "\n".join(f"{k}\t{v}" for k, v in runlists.items())
+    out_len = C.c_uint64()
+    return _take_bytes(load().gams_host_anno_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, rl.encode(), data,
+                                                  len(data), int(header), prefix.encode(), idx_id, idx_range,
+                                                  C.byref(out_len)), out_len)
+
+
+def last_operator_device():
+    """1 if the last locate_text / anno_text of this thread made its rows on the device, 0 if it fell back"""
+    return int(load().gams_host_last_operator_device())
+
+
+def fmt_prop4(v):
+    """`{:.4}` of an anno prop as the device formats it ("" outside [0, 1])"""
+    return _take(load().gams_host_fmt_prop4(v))
 
 
 def gen(eng, chr_id, seq, piece=500000, fill=50, min_len=5000):

@@ -1,5 +1,6 @@
 // gams_host.cpp -- see gams_host.hpp.  Citations are file:line under the reference.
 #include "gams_host.hpp"
+#include "../csrc/text_fmt.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -1074,6 +1075,8 @@ Locator::Locator(gams_gpu_t *h, const std::vector<Ctg> &ctgs) : h_(h), ctgs_(ctg
 Locator::~Locator() {
     if (ctg_ix_) gams_index_destroy(h_, ctg_ix_);
     if (rg_ix_) gams_index_destroy(h_, rg_ix_);
+    if (chr_names_) gams_names_destroy(h_, chr_names_);
+    if (ctg_ids_) gams_names_destroy(h_, ctg_ids_);
 }
 
 const Ctg *Locator::ctg(const std::string &id) const {
@@ -1244,6 +1247,45 @@ std::string Locator::locate(const std::vector<std::string> &rgs, bool is_count) 
         }
     });
     return join();
+}
+
+void Locator::text_tables() {
+    if (chr_names_) return;
+    std::vector<const char *> chr(chr_group_.size()), ids(ctgs_.size());
+    for (auto &kv : chr_group_) chr[kv.second] = kv.first.c_str();
+    for (size_t i = 0; i < ctgs_.size(); ++i) ids[i] = ctgs_[i].id.c_str();
+    check(h_, gams_names_create(h_, (uint32_t)chr.size(), chr.data(), &chr_names_));
+    check(h_, gams_names_create(h_, (uint32_t)ids.size(), ids.data(), &ctg_ids_));
+}
+
+std::string Locator::locate_text(const char *bytes, size_t n, bool is_count, bool *device) {
+    if (device) *device = false;
+    if (is_count && !rg_ix_) throw Error(GAMS_ESTATE, "locate --count: no rg index loaded");
+    text_tables();
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, rows = 0;
+    int rc;
+    if (is_count) {
+        std::vector<uint32_t> group_of(ctgs_.size(), UINT32_MAX);    // rg group of every ctg of the table
+        for (size_t c = 0; c < ctgs_.size(); ++c) {
+            auto it = rg_group_.find(ctgs_[c].id);
+            if (it != rg_group_.end()) group_of[c] = it->second;
+        }
+        rc = gams_gpu_count_text(h_, ctg_ix_, chr_names_, rg_ix_, group_of.data(), bytes, n, &text, &text_bytes, &rows);
+    } else {
+        rc = gams_gpu_locate_text(h_, ctg_ix_, chr_names_, ctg_ids_, bytes, n, &text, &text_bytes, &rows);
+    }
+    if (rc == GAMS_EUNSUPPORTED) {                                       // the array path, from the lines' first fields
+        std::vector<std::string> rgs = text_lines(bytes, n);
+        for (std::string &s : rgs) {
+            const size_t tab = s.find('\t');                             // locate.rs:89-91
+            if (tab != std::string::npos) s.resize(tab);
+        }
+        return locate(rgs, is_count);
+    }
+    check(h_, rc);
+    if (device) *device = true;
+    return std::string(text, (size_t)text_bytes);
 }
 
 std::string Locator::locate_seq(const std::vector<std::string> &rgs,
@@ -1920,6 +1962,75 @@ std::string anno(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, cons
     if (header && !lines.empty()) out += lines[0] + "\t" + prefix + "Prop\n";  // anno.rs:108
     for (unsigned t = 0; t < T; ++t) out += part[t].out;
     return out;
+}
+
+std::vector<std::string> text_lines(const char *bytes, size_t n) {
+    std::vector<std::string> lines;
+    size_t b = 0;
+    while (b < n) {
+        const char *nl = static_cast<const char *>(std::memchr(bytes + b, '\n', n - b));
+        if (!nl) {
+            lines.emplace_back(bytes + b, n - b);                        // the last line keeps a '\r'
+            break;
+        }
+        size_t e = (size_t)(nl - bytes);
+        const size_t next = e + 1;
+        if (e > b && bytes[e - 1] == '\r') --e;
+        lines.emplace_back(bytes + b, e - b);
+        b = next;
+    }
+    return lines;
+}
+
+std::string fmt_prop4(float p) {
+    char buf[8];
+    if (!gams_fmt_prop4(p, buf)) return std::string();
+    return std::string(buf, 6);
+}
+
+std::string anno_text(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, const std::vector<Ctg> &ctgs,
+                      const char *bytes, size_t n, bool header, const std::string &prefix, size_t idx_id,
+                      size_t idx_range, bool *device) {
+    if (device) *device = false;
+    // the device image of the runlists (one group per chr, in the set's order) and the two name tables
+    std::vector<uint64_t> off{0};
+    std::vector<int32_t> lo, hi;
+    std::vector<const char *> chr, ids(ctgs.size());
+    for (auto &kv : sets) {
+        chr.push_back(kv.first.c_str());
+        lo.insert(lo.end(), kv.second.lo.begin(), kv.second.lo.end());
+        hi.insert(hi.end(), kv.second.hi.begin(), kv.second.hi.end());
+        off.push_back(lo.size());
+    }
+    std::vector<int32_t> cs(ctgs.size()), ce(ctgs.size());
+    for (size_t i = 0; i < ctgs.size(); ++i) {
+        ids[i] = ctgs[i].id.c_str();
+        cs[i] = ctgs[i].chr_start;
+        ce[i] = ctgs[i].chr_end;
+    }
+    struct Guard {
+        gams_gpu_t *h;
+        gams_spans_t *sp = nullptr;
+        gams_names_t *chr = nullptr, *ids = nullptr;
+        ~Guard() {
+            if (sp) gams_spans_destroy(h, sp);
+            if (chr) gams_names_destroy(h, chr);
+            if (ids) gams_names_destroy(h, ids);
+        }
+    } g{h};
+    check(h, gams_spans_create(h, (uint32_t)chr.size(), off.data(), lo.data(), hi.data(), &g.sp));
+    check(h, gams_names_create(h, (uint32_t)chr.size(), chr.data(), &g.chr));
+    check(h, gams_names_create(h, (uint32_t)ids.size(), ids.data(), &g.ids));
+    if (idx_id > UINT32_MAX || idx_range > UINT32_MAX) throw Error(GAMS_EINVAL, "anno: field index out of range");
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, rows = 0;
+    const int rc = gams_gpu_anno_text(h, g.sp, g.chr, g.ids, cs.data(), ce.data(), bytes, n, header ? 1 : 0,
+                                      prefix.c_str(), (uint32_t)idx_id, (uint32_t)idx_range, &text, &text_bytes, &rows);
+    if (rc == GAMS_EUNSUPPORTED)
+        return anno(h, sets, ctgs, text_lines(bytes, n), header, prefix, idx_id, idx_range);
+    check(h, rc);
+    if (device) *device = true;
+    return std::string(text, (size_t)text_bytes);
 }
 
 }  // namespace gams

@@ -146,6 +146,13 @@ public:
     std::vector<std::string> find(const std::vector<Range> &rgs);
     // locate output: "{rg}\t{ctg_id}\n" or with count "{rg}\t{count}\n" (locate.rs:135-140)
     std::string locate(const std::vector<std::string> &rgs, bool is_count);
+    // locate -f / --count over the bytes of the input file (locate.rs:84-141): the same text as locate() of the
+    // lines' first fields, made on the device (gams_gpu_locate_text / gams_gpu_count_text).  Where the device
+    // refuses (GAMS_EUNSUPPORTED) the bytes are split into lines (text_lines) and locate() runs; *device (may be
+    // NULL) says which path made the rows.
+    std::string locate_text(const char *bytes, size_t n, bool is_count, bool *device = nullptr);
+    // the device name tables of locate_text (chromosome -> group, ctg slot -> id), built once; locate_text calls it
+    void text_tables();
     // locate --seq (locate.rs:124-134): ">{rg}\n{bases}\n"; seq_of maps ctg id -> gunzipped seq
     std::string locate_seq(const std::vector<std::string> &rgs, const std::map<std::string, std::string> &seq_of);
     const Ctg *ctg(const std::string &id) const;
@@ -158,6 +165,8 @@ private:
     gams_index_t *ctg_ix_ = nullptr;
     gams_index_t *rg_ix_ = nullptr;
     std::map<std::string, uint32_t> rg_group_;    // ctg id -> group of the rg index
+    gams_names_t *chr_names_ = nullptr;           // chr_group_ as a device table
+    gams_names_t *ctg_ids_ = nullptr;             // ctgs_[i].id
 };
 
 class Locator;
@@ -238,6 +247,17 @@ struct Runlist {
 std::string anno(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, const std::vector<Ctg> &ctgs,
                  const std::vector<std::string> &lines, bool header, const std::string &prefix, size_t idx_id,
                  size_t idx_range);
+
+// anno.rs:95-142 over the bytes of one input file: the same text as anno() of its lines, made on the device
+// (gams_gpu_anno_text); where the device refuses, the bytes are split into lines and anno() runs.  *device as in
+// Locator::locate_text.
+std::string anno_text(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, const std::vector<Ctg> &ctgs,
+                      const char *bytes, size_t n, bool header, const std::string &prefix, size_t idx_id,
+                      size_t idx_range, bool *device = nullptr);
+// BufRead::lines() of the bytes: split on '\n', one '\r' before a '\n' dropped, a last line without '\n' kept
+std::vector<std::string> text_lines(const char *bytes, size_t n);
+// `{:.4}` of an anno prop in [0, 1] as the device prints it (integer arithmetic, csrc/text_fmt.hpp); "" outside
+std::string fmt_prop4(float p);
 
 // ---- wire formats either side of the path (gams_wire.cpp; SURVEY 8 f-3, parity unpinned) ----------
 namespace wire {

@@ -341,10 +341,90 @@ char *gams_host_locate(gams_gpu_t *h, uint32_t n, const char *const *ids, const 
     });
 }
 
-// milliseconds the last gams_host_locate / gams_host_anno of this thread spent inside the operator itself
-// (Locator::locate, gams::anno: parsing of the range strings, device lookups, row text) -- without this wrapper's
-// splitting of its arguments into lines and, for --count, the build of the rg index, which are the caller's
+// milliseconds the last gams_host_locate / gams_host_anno / gams_host_locate_text / gams_host_anno_text of this
+// thread spent inside the operator itself (Locator::locate, gams::anno: parsing of the range strings, device lookups,
+// row text; the text forms: from the input bytes in host memory to the finished string) -- without this wrapper's
+// splitting of its arguments into lines and, for locate, the build of the ctg / rg index and its name tables, which
+// are the caller's
 double gams_host_last_operator_ms(void) { return g_operator_ms; }
+
+// 1 if the rows of the last gams_host_locate_text / gams_host_anno_text of this thread came from the device, 0 if
+// the device refused the input and the array path made them
+static thread_local int g_operator_device = 0;
+int gams_host_last_operator_device(void) { return g_operator_device; }
+
+namespace {
+std::map<std::string, std::vector<gams::Range>> rg_index_of(uint32_t n, const char *const *ids, const char *rg_lines) {
+    std::map<std::string, std::vector<gams::Range>> rg_of;
+    for (uint32_t i = 0; i < n; ++i) rg_of[ids[i]];  // build_idx_rg visits every ctg (redis.rs:279-302)
+    for (const std::string &ln : split_lines(rg_lines)) {
+        size_t tab = ln.find('\t');
+        if (tab == std::string::npos) continue;
+        gams::Range r = gams::Range::from_str(ln.substr(tab + 1));
+        if (r.valid) rg_of[ln.substr(0, tab)].push_back(r);
+    }
+    return rg_of;
+}
+
+std::map<std::string, gams::Runlist> runlists_of(const char *runlists) {
+    std::map<std::string, gams::Runlist> sets;
+    for (const std::string &ln : split_lines(runlists)) {
+        size_t tab = ln.find('\t');
+        if (tab == std::string::npos) continue;
+        gams::Runlist &rl = sets[ln.substr(0, tab)];
+        std::istringstream is(ln.substr(tab + 1));
+        std::string part;
+        while (std::getline(is, part, ',')) {
+            if (part.empty() || part == "-") continue;
+            size_t dash = part.find('-', 1);
+            int32_t lo = std::atoi(part.substr(0, dash).c_str());
+            int32_t hi = dash == std::string::npos ? lo : std::atoi(part.substr(dash + 1).c_str());
+            rl.lo.push_back(lo);
+            rl.hi.push_back(hi);
+        }
+    }
+    return sets;
+}
+}  // namespace
+
+// locate -f / --count over the bytes of the input file (bytes, n_bytes: not NUL-terminated); rg_lines as for
+// gams_host_locate.  *out_len receives the text's length.
+char *gams_host_locate_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                            const int32_t *starts, const int32_t *ends, const char *bytes, uint64_t n_bytes,
+                            int is_count, const char *rg_lines, uint64_t *out_len) {
+    return guarded_bytes(out_len, [&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        if (is_count) loc.set_rg_index(rg_index_of(n, ids, rg_lines));
+        loc.text_tables();
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = loc.locate_text(bytes, (size_t)n_bytes, is_count != 0, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        return out;
+    });
+}
+
+// anno over the bytes of one input file; runlists as for gams_host_anno
+char *gams_host_anno_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                          const int32_t *starts, const int32_t *ends, const char *runlists, const char *bytes,
+                          uint64_t n_bytes, int header, const char *prefix, uint32_t idx_id, uint32_t idx_range,
+                          uint64_t *out_len) {
+    return guarded_bytes(out_len, [&] {
+        const std::map<std::string, gams::Runlist> sets = runlists_of(runlists);
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = gams::anno_text(h, sets, cv, bytes, (size_t)n_bytes, header != 0, prefix ? prefix : "", idx_id,
+                                          idx_range, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        return out;
+    });
+}
+
+// `{:.4}` of an anno prop as the device formats it ("" outside [0, 1])
+char *gams_host_fmt_prop4(float p) { return dup(gams::fmt_prop4(p)); }
 
 // locate --seq (locate.rs:124-134).  seq_lines: "ctg_id\tbases" rows.
 char *gams_host_locate_seq(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,

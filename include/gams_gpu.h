@@ -20,6 +20,9 @@
  *   gams_gpu_locate           src/libs/utils.rs:7-22        (find_one_idx -> Lapper::find().next())
  *   gams_gpu_cover            src/cmd_gams/anno.rs:128-139  (IntSpan intersect cardinalities)
  *   gams_gpu_valid_spans      src/cmd_gams/gen.rs:86-104    (ambiguous-base scan, fill, excise)
+ *   gams_gpu_locate_text      src/cmd_gams/locate.rs:84-141 (locate -f: lines, Range::from_str, find_one_idx, rows)
+ *   gams_gpu_count_text       src/cmd_gams/locate.rs:84-141 (locate --count: the same with count_rg, utils.rs:24-36)
+ *   gams_gpu_anno_text        src/cmd_gams/anno.rs:95-142   (one input file: fields, extract_ctg_id, cover, rows)
  *
  * Measurement and tuning entries (event stopwatch, phase stamps, guard-band and tile knobs, kernel
  * names) are NOT part of this surface: they live in gams_gpu_diag.h, which a host need not bind.
@@ -52,6 +55,7 @@ typedef struct gams_seqset gams_seqset_t;
 typedef struct gams_wave_plan gams_wave_plan_t;
 typedef struct gams_index gams_index_t;
 typedef struct gams_spans gams_spans_t;
+typedef struct gams_names gams_names_t;
 
 /* ---- handle ------------------------------------------------------------ */
 int gams_gpu_create(int device, gams_gpu_t **h);
@@ -288,6 +292,51 @@ int gams_gpu_cover(gams_gpu_t *h, gams_spans_t *sp, const uint32_t *group,
                    const int32_t *clip_lo, const int32_t *clip_hi,
                    const int32_t *qs, const int32_t *qe, uint64_t nq,
                    float *prop);
+
+/* ---- text in, text out: locate -f, locate --count, anno ------------------------- */
+/* A device-resident map from a byte string to its position in names[0..n) (NUL-terminated), which also keeps the
+ * names' bytes so that kernels can print them.  Lookup is exact byte equality; a duplicate name is GAMS_EINVAL.
+ * Uses: chromosome name -> group of a ctg index or a span set; ctg id -> ctg slot (anno); ctg slot -> id (locate). */
+int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_names_t **out);
+void gams_names_destroy(gams_gpu_t *h, gams_names_t *nm);
+
+/* The three entries below take the bytes of an input file (n_bytes, any host memory; page-locked memory from
+ * gams_gpu_host_alloc copies at the rate of the link; more than 4 GiB works) and return its finished rows.  Lines are
+ * those of Rust's BufRead::lines(): split on '\n', one '\r' before a '\n' dropped, a last line without '\n' counted
+ * (it keeps any '\r'), nothing after a final '\n'.  *text (text_bytes bytes, rows in input-line order, no NUL) points
+ * into page-locked memory owned by the handle, valid until the next call of the same entry on that handle; *n_rows
+ * counts the rows, a header row included.
+ * GAMS_EUNSUPPORTED (nothing is printed; run the host path instead): a byte >= 0x80 or a NUL in the input, more than
+ * 2^32 - 1 lines, and the entry-specific cases below. */
+/* locate -f (locate.rs:84-141, utils.rs:7-22).  rg = the bytes of a line up to its first '\t' (locate.rs:89-91),
+ * parsed like intspan's Range::from_str ([name.]chr[(strand)]:start[-end], 1-10 digits, runs of '-'/'_' between the
+ * numbers, values <= INT32_MAX).  Invalid lines, lines whose chromosome is not in chr_names, and lines that
+ * gams_gpu_locate does not locate (Lapper::find(start, end) against half-open [start, end + 1): a point range on a
+ * ctg start is not located) print nothing; every other prints "{rg}\t{ctg_id}\n" (locate.rs:139).  chr_names[g]
+ * names group g of ctg_ix; ctg_ids[i] names interval i of ctg_ix in the caller's original order (what
+ * gams_gpu_locate returns), so ctg_ids has one name per interval (GAMS_EINVAL otherwise). */
+int gams_gpu_locate_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const gams_names_t *ctg_ids,
+                         const char *bytes, uint64_t n_bytes, const char **text, uint64_t *text_bytes, uint64_t *n_rows);
+/* locate --count (utils.rs:24-36): the lines locate_text locates print "{rg}\t{count}\n" (locate.rs:137), count =
+ * gams_gpu_count of the range against group rg_group[i] of rg_ix, i the located interval of ctg_ix (rg_group has one
+ * entry per interval of ctg_ix).  GAMS_EUNSUPPORTED if a located interval has rg_group[i] == UINT32_MAX: the host
+ * path reports such a ctg as "not found in idx". */
+int gams_gpu_count_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, gams_index_t *rg_ix,
+                        const uint32_t *rg_group, const char *bytes, uint64_t n_bytes, const char **text,
+                        uint64_t *text_bytes, uint64_t *n_rows);
+/* anno over one input file (anno.rs:95-142).  With `header` the first line prints "{line}\t{prefix}Prop\n"
+ * (anno.rs:98-110).  Every other line is split on '\t': field idx_id or idx_range (1-based) missing, or either
+ * index 0, is GAMS_EINVAL (the reference panics, anno.rs:115).  The ctg id is the first match of (?i)ctg:[\w_]+:\d+
+ * in field idx_id (utils.rs:118-129); no match, or an invalid range in field idx_range, drops the line.  If the
+ * range's chromosome names span group g of sp (chr_names[g]), the id must be in ctg_ids (GAMS_EINVAL otherwise, the
+ * reference panics, redis.rs:133-134) and prop is gams_gpu_cover of the range clipped to [ctg_start[k], ctg_end[k]],
+ * k the id's slot; otherwise prop is 0.  Each row is "{line}\t{prop:.4}\n" with {:.4} exact (round half to even on
+ * the binary value).  GAMS_EUNSUPPORTED for a reversed range (start > end) on a chromosome of the set, whose prop
+ * the reference computes as 0/0, and for any prop that is not a finite value in [0, 1]. */
+int gams_gpu_anno_text(gams_gpu_t *h, gams_spans_t *sp, const gams_names_t *chr_names, const gams_names_t *ctg_ids,
+                       const int32_t *ctg_start, const int32_t *ctg_end, const char *bytes, uint64_t n_bytes, int header,
+                       const char *prefix, uint32_t idx_id, uint32_t idx_range, const char **text, uint64_t *text_bytes,
+                       uint64_t *n_rows);
 
 /* ---- gen: valid regions of a chromosome (first "next" row of SURVEY section 8f) ---- */
 /* gen.rs:86-104: bases other than A C G T a c g t are ambiguous; the valid set is their
