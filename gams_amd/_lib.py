@@ -13,6 +13,7 @@ SO_PATH = os.path.join(_HERE, "libgams_gpu.so")
 
 OK, EINVAL, ENODEV, ENOMEM, EHIP, ESHORT, EUNSUPPORTED, ESTATE = range(8)
 WAVE_PEAKS, WAVE_DENSE = 1, 2
+SW_GC, SW_COUNT = 1, 2          # GAMS_SW_GC / GAMS_SW_COUNT: the action set of gams_gpu_sw_text_actions
 
 
 class GamsError(RuntimeError):
@@ -89,6 +90,11 @@ PROTOTYPES = {
                                     _VP, C.c_uint64, _VP, _VP]),
     "gams_gpu_sw_text": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.POINTER(C.c_char_p), _VP, _VP, _VP, _VP, C.POINTER(C.c_char_p),
                                    C.c_int32, C.c_int32, C.c_int32, _PP, C.POINTER(C.c_uint64), _PP, C.POINTER(C.c_uint64)]),
+    "gams_gpu_sw_text_actions": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.POINTER(C.c_char_p), _VP, _VP, _VP, _VP,
+                                           C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _VP, _VP,
+                                           _PP, C.POINTER(C.c_uint64), _PP, C.POINTER(C.c_uint64)]),
+    "gams_gpu_sw_count_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
+                                          _VP, C.c_uint64, _VP, _VP]),
     "gams_gpu_range_gc": (C.c_int, [_VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, C.c_uint32, _VP]),
     "gams_gpu_range_gc_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "gams_index_create": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _PP]),

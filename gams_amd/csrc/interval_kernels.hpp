@@ -164,18 +164,12 @@ __device__ __forceinline__ uint32_t bk_lower_bound(const uint32_t *keys, const B
     return lo;
 }
 
-__global__ __launch_bounds__(256) void interval_count_kernel(const CountGroup *groups, const uint32_t *starts,
-                                                             const uint32_t *stops, const BkRec *bk_start,
-                                                             const BkRec *bk_stop, uint32_t n_groups,
-                                                             const uint32_t *group, const uint32_t *qs,
-                                                             const uint32_t *qe, uint64_t nq, int32_t *out) {
-    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= nq) return;
-    const uint32_t g = group[q];
-    if (g >= n_groups) {  // utils.rs:29-32: ctg not in the index -> 0
-        out[q] = 0;
-        return;
-    }
+// Lapper::count(qs, qe) against group g (g >= n_groups: utils.rs:29-32, ctg not in the index -> 0).  Shared by
+// interval_count_kernel and the sw windows' rg_count (sw.hip).
+__device__ __forceinline__ int32_t lapper_count(const CountGroup *groups, const uint32_t *starts, const uint32_t *stops,
+                                                const BkRec *bk_start, const BkRec *bk_stop, uint32_t n_groups,
+                                                uint32_t g, uint32_t qs, uint32_t qe) {
+    if (g >= n_groups) return 0;
     const uint4 *gp = reinterpret_cast<const uint4 *>(groups + g);
     const uint4 g0 = gp[0], g1 = gp[1];
     const uint32_t off = g0.x, n = g0.y;
@@ -184,9 +178,19 @@ __global__ __launch_bounds__(256) void interval_count_kernel(const CountGroup *g
     // Lapper::count: first = bsearch_seq(start + 1, stops); last = bsearch_seq(stop, starts)
     // (bk_start = the interleaved array, bk_stop = bk_start + 1: a range shorter than a cell finds both of its
     // records in one 64-B line or in two neighbouring ones)
-    const uint32_t first = bk_lower_bound(stops + off, bk_stop + 2u * boff, n, dt, (uint64_t)qs[q] + 1u);
-    const uint32_t last = bk_lower_bound(starts + off, bk_start + 2u * boff, n, ds, (uint64_t)qe[q]);
-    out[q] = (int32_t)((int64_t)last - (int64_t)first);
+    const uint32_t first = bk_lower_bound(stops + off, bk_stop + 2u * boff, n, dt, (uint64_t)qs + 1u);
+    const uint32_t last = bk_lower_bound(starts + off, bk_start + 2u * boff, n, ds, (uint64_t)qe);
+    return (int32_t)((int64_t)last - (int64_t)first);
+}
+
+__global__ __launch_bounds__(256) void interval_count_kernel(const CountGroup *groups, const uint32_t *starts,
+                                                             const uint32_t *stops, const BkRec *bk_start,
+                                                             const BkRec *bk_stop, uint32_t n_groups,
+                                                             const uint32_t *group, const uint32_t *qs,
+                                                             const uint32_t *qe, uint64_t nq, int32_t *out) {
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= nq) return;
+    out[q] = lapper_count(groups, starts, stops, bk_start, bk_stop, n_groups, group[q], qs[q], qe[q]);
 }
 
 __global__ __launch_bounds__(256) void interval_locate_kernel(const IndexGroup *groups, const uint32_t *lstart,

@@ -15,8 +15,13 @@
 // and gc_count(range) = P(end+1) - P(start): 6 loads per range (4 B + 8 B each side).
 // The parent is a single span, so IntSpan index/slice/at are plain arithmetic.
 // Statistics are evaluated in the reference's f32 order (-ffp-contract=off).
+//
+// `-a count` (rg_count, the ninth column): Lapper::count(win.min(), win.max()) of every window against the
+// idx:rg: group of its ctg -- the lookup of `locate --count` (lapper_count, interval_kernels.hpp), run by the
+// same thread that holds the window.  sw_kernel<kGc, kCount> is instantiated per action set; without kGc it
+// neither needs the gc index nor touches the sequence bytes.
 
-#include "common.hpp"
+#include "interval_kernels.hpp"
 
 #include <string>
 
@@ -159,7 +164,8 @@ struct SwCtg {
     uint32_t len;
     int32_t chr_start, chr_end;
     uint32_t feat_first;  // index of the ctg's first feature in the call's feature arrays
-    uint32_t pad[2];
+    uint32_t rg_group;    // its group of the rg index (-a count); >= n_groups: none, counts are 0
+    uint32_t pad;
 };
 
 struct SwArgs {
@@ -176,6 +182,12 @@ struct SwArgs {
     int32_t size, max, resize;
     gams_sw_row_t *rows;
     uint64_t cap;
+    // -a count: the rg index (interval_kernels.hpp) and the count column, one entry per row
+    const CountGroup *cgroups;
+    const uint32_t *rg_starts, *rg_stops;
+    const BkRec *bk_start, *bk_stop;
+    uint32_t n_groups;
+    int32_t *cnt;
 };
 
 // gc_content of chromosome range [s,e] (inclusive) inside the ctg: count / len, f32
@@ -199,6 +211,9 @@ __device__ __forceinline__ uint64_t gc_prefix_at(const SwArgs &a, int64_t b) {
 // one thread per (feature, slot); slot 0 = M, 1..max = L, max+1..2max = R
 // All selected ctgs of a call in ONE launch (a ctg's ~400 features are a handful of workgroups: launched
 // per ctg the kernel is all launch latency).
+// kGc: gc_content and the flank statistics (sw.rs:167-184); kCount: rg_count into a.cnt.  Without kGc the four
+// statistics of the row are 0 and nothing reads a.pm / a.seg.
+template <bool kGc, bool kCount>
 __global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
     const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t slots = 1u + 2u * (uint32_t)a0.max;
@@ -241,6 +256,14 @@ __global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
     r.distance = dist;
     r.start = ws;
     r.end = we;
+    if (kCount)   // count_rg(idx:rg:, ctg, Range::from(chr, win.min(), win.max())) = Lapper::count(ws, we)
+        a.cnt[row] = lapper_count(a.cgroups, a.rg_starts, a.rg_stops, a.bk_start, a.bk_stop, a.n_groups, cg.rg_group,
+                                  (uint32_t)ws, (uint32_t)we);
+    if (!kGc) {
+        r.gc_content = r.gc_mean = r.gc_stddev = r.gc_cv = 0.0f;
+        a.rows[row] = r;
+        return;
+    }
     r.gc_content = round4(range_gc(a, ws, we));                         // utils.rs:161
     // flank: center_resize(parent, window, resize) cut into size-bp tiles (sw.rs:175-178)
     int32_t rs, re;
@@ -358,15 +381,19 @@ void gams_seqset_gcindex_free(gams_seqset_t *s) {
 }
 
 // ---- the rows as TSV text (sw.rs:152-190, the Display of Sw: data.rs:58-83) -------------------------------------
-// "sw:{feature id}:{serial}\t{chr}:{start}-{end}\t{M|L|R}\t{distance}\t{gc_content}\t{gc_mean}\t{gc_stddev}\t{gc_cv}\t\n"
-// (the last field, rg_count, is empty here as in `gams sw` without --rg).  The four floats are round(x, 4) values
+// "sw:{feature id}:{serial}\t{chr}:{start}-{end}\t{M|L|R}\t{distance}\t{gc_content}\t{gc_mean}\t{gc_stddev}\t{gc_cv}\t{rg_count}\n"
+// The action set decides the last five fields: without gc the four statistics are empty ("\t\t\t", data.rs:60-70),
+// without count rg_count is empty; with count it is the decimal i32 (data.rs:71-75).  The four floats are round(x, 4) values
 // (utils.rs:135-138, :161, :186): the f32 nearest to m / 10^4 for an integer m, and Rust's `{}` prints the shortest
 // digits that round-trip -- for m below 10^7 (values below 1000: gc values are below 1, cv a few units) that is m / 10^4
 // with its trailing zeros dropped, since no shorter decimal lies within half an ulp of it.  Anything else (a value of
 // 1000 or more, a negative coordinate) raises a flag and the host formats the batch as before.
 namespace {
 constexpr uint32_t kSwTextBlock = 512;     // rows per workgroup of the text kernels (256 threads x 2)
-constexpr uint32_t kSwTextStage = 49152;   // bytes of a block's text staged in LDS
+// bytes of a block's text staged in LDS: 96 B a row on average.  A row without its names is at most 88 B
+// (-a gc) and 99 B (-a gc -a count: up to 11 more for the count); a block beyond the stage is written to
+// global memory directly (sw_text_write_kernel's unstaged branch)
+constexpr uint32_t kSwTextStage = 49152;
 
 struct SwTextArgs {
     const gams_sw_row_t *rows;
@@ -386,6 +413,8 @@ struct SwTextArgs {
     char *text;
     uint64_t text_cap;
     unsigned long long *words;         // [0] = all bytes, [1] = flag (a value this formatter does not cover), [2 + k] = first byte of ctg k
+    uint32_t gc;                       // print the four statistics (else four empty fields)
+    const int32_t *cnt;                // per row rg_count (nullptr: the field stays empty)
 };
 
 __device__ __forceinline__ uint32_t sw_digits(uint32_t v) {
@@ -400,6 +429,17 @@ __device__ __forceinline__ char *sw_put_dec(char *p, uint32_t v) {
         v /= 10u;
     } while (v);
     return p + n;
+}
+// an i32 as Rust's `{}` prints it
+__device__ __forceinline__ uint32_t sw_i32_len(int32_t v) {
+    return v < 0 ? 1u + sw_digits(0u - (uint32_t)v) : sw_digits((uint32_t)v);
+}
+__device__ __forceinline__ char *sw_put_i32(char *p, int32_t v) {
+    if (v < 0) {
+        *p++ = '-';
+        return sw_put_dec(p, 0u - (uint32_t)v);
+    }
+    return sw_put_dec(p, (uint32_t)v);
 }
 // a round4 value as Rust prints it; returns the length (p == nullptr: length only); *bad set for values not covered
 __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
@@ -467,8 +507,12 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
         uint32_t n = 3u + idn + 1u + sw_digits(c.serial) + 1u + nmn + 1u + sw_digits(st);
         if (en != st) n += 1u + sw_digits(en);
         n += 1u + 1u + 1u + sw_digits(di) + 1u;
-        n += sw_put_f4(nullptr, w.gc_content, bad) + 1u + sw_put_f4(nullptr, w.gc_mean, bad) + 1u +
-             sw_put_f4(nullptr, w.gc_stddev, bad) + 1u + sw_put_f4(nullptr, w.gc_cv, bad) + 2u;
+        if (a.gc)
+            n += sw_put_f4(nullptr, w.gc_content, bad) + 1u + sw_put_f4(nullptr, w.gc_mean, bad) + 1u +
+                 sw_put_f4(nullptr, w.gc_stddev, bad) + 1u + sw_put_f4(nullptr, w.gc_cv, bad) + 2u;
+        else
+            n += 3u + 2u;
+        if (a.cnt) n += sw_i32_len(a.cnt[r]);
         return n;
     }
     char *q = p;
@@ -491,14 +535,21 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
     *q++ = '\t';
     q = sw_put_dec(q, di);
     *q++ = '\t';
-    q += sw_put_f4(q, w.gc_content, bad);
+    if (a.gc) {
+        q += sw_put_f4(q, w.gc_content, bad);
+        *q++ = '\t';
+        q += sw_put_f4(q, w.gc_mean, bad);
+        *q++ = '\t';
+        q += sw_put_f4(q, w.gc_stddev, bad);
+        *q++ = '\t';
+        q += sw_put_f4(q, w.gc_cv, bad);
+    } else {
+        *q++ = '\t';
+        *q++ = '\t';
+        *q++ = '\t';
+    }
     *q++ = '\t';
-    q += sw_put_f4(q, w.gc_mean, bad);
-    *q++ = '\t';
-    q += sw_put_f4(q, w.gc_stddev, bad);
-    *q++ = '\t';
-    q += sw_put_f4(q, w.gc_cv, bad);
-    *q++ = '\t';
+    if (a.cnt) q = sw_put_i32(q, a.cnt[r]);
     *q++ = '\n';
     return (uint32_t)(q - p);
 }
@@ -617,19 +668,57 @@ struct SwTextReq {                       // what gams_gpu_sw_text adds to a batc
     uint64_t *text_bytes;
     const uint64_t **ctg_off;
 };
+
+struct SwCountReq {                      // what -a count adds to a call: the rg index, the group of every selected ctg
+    const gams_index_t *ix;
+    const uint32_t *group;
+};
 }  // namespace
 
+// rows (gams_gpu_sw_batch: gc), count (gams_gpu_sw_count_batch: count) or tx (the text entries: any action set)
 static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                          const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
-                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, gams_sw_row_t *rows,
-                         uint64_t cap, uint64_t *row_off, uint64_t *n_rows, const SwTextReq *tx);
+                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                         const SwCountReq &cr, gams_sw_row_t *rows, int32_t *count, uint64_t cap, uint64_t *row_off,
+                         uint64_t *n_rows, const SwTextReq *tx);
 
 extern "C" int gams_gpu_sw_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                                  const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
                                  const int32_t *feat_end, int32_t size, int32_t max, int32_t resize,
                                  gams_sw_row_t *rows, uint64_t cap, uint64_t *row_off, uint64_t *n_rows) {
-    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, rows, cap,
-                         row_off, n_rows, nullptr);
+    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, GAMS_SW_GC,
+                         SwCountReq{nullptr, nullptr}, rows, nullptr, cap, row_off, n_rows, nullptr);
+}
+
+extern "C" int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                       const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                                       const int32_t *feat_end, int32_t size, int32_t max, gams_index_t *rg_ix,
+                                       const uint32_t *rg_group, int32_t *count, uint64_t cap, uint64_t *row_off,
+                                       uint64_t *n_rows) {
+    if (!rg_ix || (n_sel && !rg_group)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_count: null rg index or rg groups");
+    // resize only shapes the gc statistics, which this call does not compute: any value the checks accept
+    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, 2, GAMS_SW_COUNT,
+                         SwCountReq{rg_ix, rg_group}, nullptr, count, cap, row_off, n_rows, nullptr);
+}
+
+extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                        const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
+                                        const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
+                                        int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
+                                        const uint32_t *rg_group, const char **text, uint64_t *text_bytes,
+                                        const uint64_t **ctg_off, uint64_t *n_rows) {
+    if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
+    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: unknown action bits");
+    if ((actions & GAMS_SW_COUNT) && (!rg_ix || (n_sel && !rg_group)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: GAMS_SW_COUNT without an rg index or rg groups");
+    if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
+    const SwTextReq tx{chr, feat_id, text, text_bytes, ctg_off};
+    *text = nullptr;
+    *text_bytes = 0;
+    const SwCountReq cr = (actions & GAMS_SW_COUNT) ? SwCountReq{rg_ix, rg_group} : SwCountReq{nullptr, nullptr};
+    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions, cr,
+                         nullptr, nullptr, 0, nullptr, n_rows, &tx);
 }
 
 extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -637,22 +726,18 @@ extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel,
                                 const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
                                 int32_t size, int32_t max, int32_t resize, const char **text, uint64_t *text_bytes,
                                 const uint64_t **ctg_off, uint64_t *n_rows) {
-    if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
-    if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
-    const SwTextReq tx{chr, feat_id, text, text_bytes, ctg_off};
-    *text = nullptr;
-    *text_bytes = 0;
-    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, nullptr, 0,
-                         nullptr, n_rows, &tx);
+    return gams_gpu_sw_text_actions(h, s, n_sel, ctg_index, chr, chr_start, feat_off, feat_start, feat_end, feat_id, size,
+                                    max, resize, GAMS_SW_GC, nullptr, nullptr, text, text_bytes, ctg_off, n_rows);
 }
 
 static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                          const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
-                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, gams_sw_row_t *rows,
-                         uint64_t cap, uint64_t *row_off, uint64_t *n_rows, const SwTextReq *tx) {
+                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                         const SwCountReq &cr, gams_sw_row_t *rows, int32_t *count, uint64_t cap, uint64_t *row_off,
+                         uint64_t *n_rows, const SwTextReq *tx) {
     if (!h || !s || !n_rows || (n_sel && (!ctg_index || !chr_start || !feat_off)))
         return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
+    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
     // size or resize 1: half_resize = 0 makes center_resize slice [mid+1, mid-1] (window.rs:113-123),
     // an empty span whose min()/max() the reference then asks for -- no defined answer to mirror
     if (size < 2 || max < 0 || resize < 2)
@@ -686,7 +771,7 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
     const size_t b_i32 = ((size_t)nf * sizeof(int32_t) + 255) & ~(size_t)255;
     const size_t b_off = (((size_t)nf + 1) * sizeof(uint64_t) + 255) & ~(size_t)255;
     const size_t in_bytes = b_ctg + 3 * b_i32 + b_off;
-    const bool size_query = !tx && (!rows || cap == 0);
+    const bool size_query = !tx && ((!rows && !count) || cap == 0);
     std::vector<uint64_t> crow((size_t)n_sel + 1, 0);    // first row of every selected ctg (text mode)
     uint8_t *pin = nullptr, *dev = nullptr;
     size_t pin_cap = 0, dev_cap = 0;
@@ -717,7 +802,7 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
         const int32_t cs = chr_start[k], ce = cs + (int32_t)s->len[i] - 1;
         if (row_off) row_off[k] = tot;
         crow[k] = tot;
-        if (cg) cg[k] = SwCtg{s->off[i], s->len[i], cs, ce, (uint32_t)feat_off[k], {0u, 0u}};
+        if (cg) cg[k] = SwCtg{s->off[i], s->len[i], cs, ce, (uint32_t)feat_off[k], do_count ? cr.group[k] : UINT32_MAX, 0u};
         for (uint64_t f = feat_off[k]; f < feat_off[k + 1]; ++f) {
             // window.rs:98-110: the middle pair of the feature must be members of the ctg span --
             // IntSpan::index of a non-member has no defined answer in the reference to mirror
@@ -747,14 +832,17 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
     if (size_query) return GAMS_OK;
     if (tx) cap = tot;                                   // text mode: every row, kept on the device
 
-    int rc = gams_seqset_gcindex(h, s);
-    if (rc != GAMS_OK) {
-        release();
-        return rc;
+    if (do_gc) {   // the counts and the geometry read no sequence byte: a count-only call leaves the bytes alone
+        const int rc = gams_seqset_gcindex(h, s);
+        if (rc != GAMS_OK) {
+            release();
+            return rc;
+        }
     }
     const uint64_t n_out = std::min<uint64_t>(tot, cap);
     const size_t b_rows = (size_t)std::max<uint64_t>(n_out, 1) * sizeof(gams_sw_row_t);
-    hipError_t e = gams_pool_alloc(h, false, in_bytes + b_rows, reinterpret_cast<void **>(&dev), &dev_cap);
+    const size_t b_cnt = do_count ? (((size_t)std::max<uint64_t>(n_out, 1) * sizeof(int32_t) + 255) & ~(size_t)255) : 0;
+    hipError_t e = gams_pool_alloc(h, false, in_bytes + b_rows + b_cnt, reinterpret_cast<void **>(&dev), &dev_cap);
     if (e != hipSuccess) {
         release();
         return gams_fail(h, GAMS_ENOMEM, std::string("gpu_sw: device buffers: ") + hipGetErrorString(e));
@@ -770,9 +858,21 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
     } while (0)
     SW_HIP(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, h->compute));
     gams_sw_row_t *d_rows = reinterpret_cast<gams_sw_row_t *>(dev + in_bytes);
+    int32_t *d_cnt = do_count ? reinterpret_cast<int32_t *>(dev + in_bytes + b_rows) : nullptr;
     SwArgs a{};
-    a.pm = s->gcindex->d_pm;
-    a.seg = s->gcindex->d_seg;
+    if (do_gc) {
+        a.pm = s->gcindex->d_pm;
+        a.seg = s->gcindex->d_seg;
+    }
+    if (do_count) {
+        a.cgroups = cr.ix->d_cgroups;
+        a.rg_starts = cr.ix->d_lstart;
+        a.rg_stops = cr.ix->d_stops;
+        a.bk_start = cr.ix->d_bk_start;
+        a.bk_stop = cr.ix->d_bk_stop;
+        a.n_groups = cr.ix->n_groups;
+        a.cnt = d_cnt;
+    }
     a.ctgs = reinterpret_cast<const SwCtg *>(dev);
     a.fs = reinterpret_cast<const int32_t *>(dev + b_ctg);
     a.fe = reinterpret_cast<const int32_t *>(dev + b_ctg + b_i32);
@@ -785,7 +885,17 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
     a.rows = d_rows;
     a.cap = n_out;
     SW_HIP(hipEventRecord(h->k0, h->compute));
-    hipLaunchKernelGGL(sw_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, h->compute, a);
+    {
+        const dim3 grid((unsigned)((threads + 255) / 256));
+        if (do_gc && do_count)
+            hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(256), 0, h->compute, a);
+        else if (do_gc)
+            hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(256), 0, h->compute, a);
+        else if (do_count)
+            hipLaunchKernelGGL((sw_kernel<false, true>), grid, dim3(256), 0, h->compute, a);
+        else
+            hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(256), 0, h->compute, a);
+    }
     SW_HIP(hipGetLastError());
     SW_HIP(hipEventRecord(h->k1, h->compute));
     h->k_valid = true;
@@ -826,7 +936,7 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
         const size_t tab_bytes = t_crow + t_noff + t_names + t_ioff + t_ids;
         const size_t b_len = al((size_t)std::max<uint64_t>(n_out, 1) * 4), b_blen = al((size_t)std::max(nb, 1u) * 4),
                      b_boff = al(((size_t)nb + 1) * 8), b_words = al(((size_t)n_sel + 3) * 8);
-        const uint64_t text_cap = std::max<uint64_t>(n_out * (uint64_t)(max_id + max_name + 96), 4096);
+        const uint64_t text_cap = std::max<uint64_t>(n_out * (uint64_t)(max_id + max_name + (do_count ? 112 : 96)), 4096);
         uint8_t *tpin = nullptr, *tdev = nullptr;
         size_t tpin_cap = 0, tdev_cap = 0;
         auto release_text = [&]() {
@@ -873,6 +983,8 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
         ta.words = reinterpret_cast<unsigned long long *>(q + b_len + b_blen + b_boff);
         ta.text = reinterpret_cast<char *>(q + b_len + b_blen + b_boff + b_words);
         ta.text_cap = text_cap;
+        ta.gc = do_gc ? 1u : 0u;
+        ta.cnt = d_cnt;
         SWT_HIP(hipMemsetAsync(ta.words, 0, b_words, h->compute));
         if (nb) {
             hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
@@ -916,7 +1028,8 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
         release();
         return GAMS_OK;
     }
-    SW_HIP(hipMemcpyAsync(rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
+    if (rows) SW_HIP(hipMemcpyAsync(rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
+    if (count) SW_HIP(hipMemcpyAsync(count, d_cnt, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, h->compute));
     SW_HIP(hipStreamSynchronize(h->compute));
 #undef SW_HIP
     release();
@@ -973,7 +1086,7 @@ extern "C" int gams_gpu_range_gc_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
         const uint32_t i = ctg_index[k];
         const int32_t cs = chr_start[k];
         const int64_t ce = (int64_t)cs + s->len[i] - 1;
-        cg[k] = SwCtg{s->off[i], s->len[i], cs, (int32_t)ce, (uint32_t)range_off[k], {0u, 0u}};
+        cg[k] = SwCtg{s->off[i], s->len[i], cs, (int32_t)ce, (uint32_t)range_off[k], UINT32_MAX, 0u};
         // utils.rs:151-156 slices seq[from-1..to): a range outside the ctg (or inverted) panics there
         for (uint64_t q = range_off[k]; q < range_off[k + 1]; ++q) {
             if (range_start[q] < cs || range_end[q] > ce || range_end[q] < range_start[q]) {

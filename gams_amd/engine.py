@@ -78,12 +78,15 @@ class Engine:
 class SeqSet:
     """HBM image of a batch of ctg sequences (gams_seqset_*)."""
 
-    def __init__(self, eng, seqs):
+    def __init__(self, eng, seqs, upload=True):
+        """upload=False: the slots are created and no base is sent (a call that reads no sequence byte may run on it)"""
         self.eng = eng
         self.lengths = np.array([len(s) for s in seqs], np.uint32)
         p = C.c_void_p()
         eng.check(eng.lib.gams_seqset_create(eng.h, len(seqs), self.lengths.ctypes.data, C.byref(p)))
         self.p = p
+        if not upload:
+            return
         arrs = [_u8(s) for s in seqs]
         ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.size else None for a in arrs])
         eng.check(eng.lib.gams_seqset_upload_all(eng.h, self.p, ptrs))
@@ -105,6 +108,72 @@ class SeqSet:
             self.close()
         except Exception:
             pass
+
+
+class Index:
+    """Sorted-interval index (gams_index_create): group g holds [starts, stops) of group_off[g]..group_off[g+1]."""
+
+    def __init__(self, eng, group_off, starts, stops):
+        self.eng = eng
+        off = np.ascontiguousarray(group_off, np.uint64)
+        st = np.ascontiguousarray(starts, np.uint32)
+        sp = np.ascontiguousarray(stops, np.uint32)
+        self.n_groups = off.size - 1
+        p = C.c_void_p()
+        eng.check(eng.lib.gams_index_create(eng.h, self.n_groups, off.ctypes.data, st.ctypes.data if st.size else None,
+                                            sp.ctypes.data if sp.size else None, C.byref(p)))
+        self.p = p
+
+    def close(self):
+        if getattr(self, "p", None):
+            self.eng.lib.gams_index_destroy(self.eng.h, self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _sw_sel(sel, chr_start, feat_off, fs, fe):
+    return (np.ascontiguousarray(sel, np.uint32), np.ascontiguousarray(chr_start, np.int32),
+            np.ascontiguousarray(feat_off, np.uint64), np.ascontiguousarray(fs, np.int32),
+            np.ascontiguousarray(fe, np.int32))
+
+
+def sw_count_batch(eng, seqset, sel, chr_start, feat_off, fs, fe, size, mx, index, rg_group):
+    """gams_gpu_sw_count_batch: (rg_count per row in gams_gpu_sw_batch's order, row_off per selected ctg)"""
+    sel, cst, foff, fs, fe = _sw_sel(sel, chr_start, feat_off, fs, fe)
+    grp = np.ascontiguousarray(rg_group, np.uint32)
+    n = C.c_uint64()
+    roff = np.zeros(sel.size + 1, np.uint64)
+    args = (eng.h, seqset.p, sel.size, sel.ctypes.data, cst.ctypes.data, foff.ctypes.data, fs.ctypes.data,
+            fe.ctypes.data, size, mx, index.p, grp.ctypes.data)
+    eng.check(eng.lib.gams_gpu_sw_count_batch(*args, None, 0, roff.ctypes.data, C.byref(n)))    # size query
+    cnt = np.zeros(max(n.value, 1), np.int32)
+    eng.check(eng.lib.gams_gpu_sw_count_batch(*args, cnt.ctypes.data, cnt.size, roff.ctypes.data, C.byref(n)))
+    return cnt[:n.value], roff
+
+
+def sw_text_actions(eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids, size, mx, resize, actions,
+                    index=None, rg_group=None):
+    """gams_gpu_sw_text_actions -> (rc, text bytes, per-ctg offsets); rc != OK is returned, not raised"""
+    sel, cst, foff, fs, fe = _sw_sel(sel, chr_start, feat_off, fs, fe)
+    names = (C.c_char_p * max(sel.size, 1))(*[c.encode() for c in chr_names])
+    ids = (C.c_char_p * max(len(feat_ids), 1))(*[f.encode() for f in feat_ids])
+    grp = None if rg_group is None else np.ascontiguousarray(rg_group, np.uint32)
+    txt, nb, off, nrows = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    rc = eng.lib.gams_gpu_sw_text_actions(eng.h, seqset.p, sel.size, sel.ctypes.data, names, cst.ctypes.data,
+                                          foff.ctypes.data, fs.ctypes.data, fe.ctypes.data, ids, size, mx, resize, actions,
+                                          index.p if index is not None else None,
+                                          grp.ctypes.data if grp is not None else None, C.byref(txt), C.byref(nb),
+                                          C.byref(off), C.byref(nrows))
+    if rc != _lib.OK:
+        return rc, b"", None
+    text = C.string_at(txt.value, nb.value) if nb.value else b""
+    offs = np.frombuffer((C.c_uint64 * (sel.size + 1)).from_address(off.value), np.uint64).copy()
+    return rc, text, offs
 
 
 class WavePlan:

@@ -82,6 +82,18 @@ def load():
     L.gams_host_sw_multi.restype = C.c_void_p
     L.gams_host_sw_multi.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p,
                                      C.c_int32, C.c_int32, C.c_int32]
+    L.gams_host_sw_actions.restype = C.c_void_p
+    L.gams_host_sw_actions.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
+                                       sp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]
+    L.gams_host_sw_multi_actions.restype = C.c_void_p
+    L.gams_host_sw_multi_actions.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p]
+    L.gams_host_sw_multi_actions_timed.restype = C.c_void_p
+    L.gams_host_sw_multi_actions_timed.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, sp, sp, ip, ip, C.c_void_p,
+                                                   C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p,
+                                                   C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    L.gams_host_last_sw_index_ms.restype = C.c_double
+    L.gams_host_last_sw_index_ms.argtypes = []
     u64p = C.POINTER(C.c_uint64)
     L.gams_host_bincode_ctg_bundle.restype = C.c_void_p
     L.gams_host_bincode_ctg_bundle.argtypes = [C.c_uint32, sp, sp, ip, ip, u64p]
@@ -233,17 +245,43 @@ def wave_multi(engines, ctgs, size=100, step=10, lag=100, threshold=3.0, influen
                                              batch_bytes))
 
 
-def sw(eng, ctg, features, size=100, mx=20, resize=500):
-    """features: list of (feature_id, start, end)."""
+SW_ACTIONS = {"gc": _lib.SW_GC, "count": _lib.SW_COUNT, "gibbs": 0}   # sw.rs:28-32; gibbs is accepted, computes nothing
+
+
+def sw_actions(names):
+    """`gams sw -a NAME ...` -> the GAMS_SW_* mask; a single name may be given as a string.  ValueError for a name
+    sw.rs does not declare."""
+    if isinstance(names, str):
+        names = (names,)
+    mask = 0
+    for n in names:
+        if n not in SW_ACTIONS:
+            raise ValueError(f"sw: unknown action {n!r} (one of {', '.join(SW_ACTIONS)})")
+        mask |= SW_ACTIONS[n]
+    return mask
+
+
+def _rg_lines(rg_records):
+    return "\n".join(f"{c}\t{r}" for c, r in rg_records).encode()
+
+
+def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_records=()):
+    """features: list of (feature_id, start, end).  actions: names of `gams sw -a` (gc, count, gibbs);
+    rg_records: (ctg_id, range string) of the rg: records, the idx:rg: source of `count`."""
+    mask = sw_actions(actions)
     nf = len(features)
     fid = (C.c_char_p * max(nf, 1))(*[f[0].encode() for f in features])
     fs = np.array([f[1] for f in features], np.int32)
     fe = np.array([f[2] for f in features], np.int32)
     seq = np.ascontiguousarray(np.frombuffer(ctg["seq"], np.uint8) if not isinstance(ctg["seq"], np.ndarray)
                                else ctg["seq"])
-    return _take(load().gams_host_sw(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
-                                     ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data, fe.ctypes.data,
-                                     size, mx, resize))
+    if mask == _lib.SW_GC and not rg_records:
+        return _take(load().gams_host_sw(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
+                                         ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data, fe.ctypes.data,
+                                         size, mx, resize))
+    return _take(load().gams_host_sw_actions(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
+                                             ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data, fe.ctypes.data,
+                                             size, mx, resize, mask, _rg_lines(rg_records)))
 
 
 def locate(eng, ctgs, rgs, count=False, rg_records=()):
@@ -348,16 +386,21 @@ def loader_records(eng, ctgs, lines, tag=None):
     return [tuple(r.split("\t", 1)) for r in out.splitlines()]
 
 
-def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500):
-    """`gams sw` over several handles; features_per_ctg[i] = list of (id, start, end) of ctgs[i]."""
+def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actions=("gc",), rg_records=()):
+    """`gams sw` over several handles; features_per_ctg[i] = list of (id, start, end) of ctgs[i]; actions and
+    rg_records as for sw()."""
+    mask = sw_actions(actions)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
     bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
                                  else c["seq"]) for c in ctgs]
     seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     rows = "\n".join(f"{i}\t{fid}\t{s}\t{e}" for i, fl in enumerate(features_per_ctg) for fid, s, e in fl)
-    return _take(load().gams_host_sw_multi(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
-                                           rows.encode(), size, mx, resize))
+    if mask == _lib.SW_GC and not rg_records:
+        return _take(load().gams_host_sw_multi(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
+                                               rows.encode(), size, mx, resize))
+    return _take(load().gams_host_sw_multi_actions(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
+                                                   rows.encode(), size, mx, resize, mask, _rg_lines(rg_records)))
 
 
 def last_operator_ms():
@@ -365,9 +408,10 @@ def last_operator_ms():
     return float(load().gams_host_last_operator_ms())
 
 
-def sw_multi_timed(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500):
+def sw_multi_timed(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actions=("gc",), rg_records=()):
     """sw_multi, returning (text, ms of the operator itself: upload + kernels + row text, without this binding's
-    parsing and copies)."""
+    parsing and copies).  With actions / rg_records the ms include the rg index build; last_sw_index_ms() has it."""
+    mask = sw_actions(actions)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
     bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
                                  else c["seq"]) for c in ctgs]
@@ -376,9 +420,19 @@ def sw_multi_timed(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500)
     rows = "\n".join(f"{i}\t{fid}\t{s}\t{e}" for i, fl in enumerate(features_per_ctg) for fid, s, e in fl)
     ms = C.c_double(0.0)
     n_out = C.c_uint64(0)
-    p = load().gams_host_sw_multi_timed(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
-                                        rows.encode(), size, mx, resize, C.byref(ms), C.byref(n_out))
+    if mask == _lib.SW_GC and not rg_records:
+        p = load().gams_host_sw_multi_timed(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
+                                            rows.encode(), size, mx, resize, C.byref(ms), C.byref(n_out))
+    else:
+        p = load().gams_host_sw_multi_actions_timed(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data,
+                                                    seqs, rows.encode(), size, mx, resize, mask, _rg_lines(rg_records),
+                                                    C.byref(ms), C.byref(n_out))
     return _take_bytes(p, n_out).decode(), ms.value
+
+
+def last_sw_index_ms():
+    """ms the last sw_multi_timed with actions / rg_records of this thread spent building the rg index"""
+    return float(load().gams_host_last_sw_index_ms())
 
 
 def _check_rc(rc):

@@ -666,7 +666,8 @@ void run_shares(uint32_t n, F fn) {
 
 std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &handles, const std::vector<Ctg> &ctgs,
                                             const std::vector<const uint8_t *> &seqs,
-                                            const std::vector<std::vector<Feature>> &features, const SwArgs &a) {
+                                            const std::vector<std::vector<Feature>> &features, const SwArgs &a,
+                                            const std::map<std::string, std::vector<Range>> *rgs, double *index_ms) {
     if (handles.empty()) throw Error(GAMS_EINVAL, "sw_proc_ctgs_multi: no handles");
     if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs_multi: ctgs / seqs / features size mismatch");
@@ -674,6 +675,7 @@ std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &han
     for (size_t c = 0; c < ctgs.size(); ++c) weight[c] = features[c].size() + 1;
     const std::vector<uint32_t> owner = lpt_assign(weight, (uint32_t)handles.size());
     std::vector<std::string> out(ctgs.size());
+    std::vector<double> ix_ms(handles.size(), 0.0);
     run_shares((uint32_t)handles.size(), [&](uint32_t d) {
         std::vector<Ctg> dc;
         std::vector<const uint8_t *> ds;
@@ -686,9 +688,10 @@ std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &han
                 df.push_back(features[c]);
                 where.push_back(c);
             }
-        std::vector<std::string> rows = sw_proc_ctgs(handles[d], dc, ds, df, a);
+        std::vector<std::string> rows = sw_proc_ctgs(handles[d], dc, ds, df, a, 256ull << 20, rgs, &ix_ms[d]);
         for (size_t k = 0; k < where.size(); ++k) out[where[k]] = std::move(rows[k]);
     });
+    if (index_ms) *index_ms = *std::max_element(ix_ms.begin(), ix_ms.end());
     return out;
 }
 
@@ -834,9 +837,10 @@ std::vector<std::string> wave_proc_ctgs_multi(const std::vector<gams_gpu_t *> &h
 // sw
 // ---------------------------------------------------------------------------
 namespace {
-// TSV text of the rows of ONE ctg (sw.rs:152-190), `rows` in the device's order (feature, then M, L1.., R1..)
+// TSV text of the rows of ONE ctg (sw.rs:152-190), `rows` in the device's order (feature, then M, L1.., R1..);
+// the statistics when `actions` has GAMS_SW_GC, rg_count from cnt[] (one per row) when cnt is given
 std::string sw_format_rows(const gams_sw_row_t *rows, uint64_t nrows, const Ctg &ctg, const std::vector<Feature> &features,
-                           unsigned max_threads) {
+                           unsigned max_threads, uint32_t actions = GAMS_SW_GC, const int32_t *cnt = nullptr) {
     static const char *TYPES[3] = {"M", "L", "R"};
     // text of rows [r0, r1), r0 on a feature boundary (the serial number restarts per feature)
     auto format = [&](uint64_t r0, uint64_t r1, std::string &o) {
@@ -861,14 +865,20 @@ std::string sw_format_rows(const gams_sw_row_t *rows, uint64_t nrows, const Ctg 
             o += '\t';
             o += std::to_string(w.distance);
             o += '\t';
-            o += fmt_f32(w.gc_content);                                 // data.rs:61-67
+            if (actions & GAMS_SW_GC) {
+                o += fmt_f32(w.gc_content);                             // data.rs:61-67
+                o += '\t';
+                o += fmt_f32(w.gc_mean);
+                o += '\t';
+                o += fmt_f32(w.gc_stddev);
+                o += '\t';
+                o += fmt_f32(w.gc_cv);
+            } else {
+                o += "\t\t\t";                                          // data.rs:68-70: empty fields
+            }
             o += '\t';
-            o += fmt_f32(w.gc_mean);
-            o += '\t';
-            o += fmt_f32(w.gc_stddev);
-            o += '\t';
-            o += fmt_f32(w.gc_cv);
-            o += "\t\n";                                                // empty rg_count (data.rs:71-80)
+            if (cnt) o += std::to_string(cnt[r]);                       // data.rs:71-75 (else empty)
+            o += '\n';
         }
     };
     std::string out;
@@ -896,10 +906,55 @@ std::string sw_format_rows(const gams_sw_row_t *rows, uint64_t nrows, const Ctg 
     for (auto &x : part) out += x;
     return out;
 }
+
+// idx:rg: (redis.rs:288-299) for the ctgs of one sw call that have features: one group per distinct ctg id that `rgs`
+// has an entry for; group[c] = the group of ctgs[c], UINT32_MAX (count 0) for a ctg `rgs` lacks, which is reported once
+// ("{ctg} not found in idx", utils.rs:30).  Intervals as Locator::set_rg_index stores them: [start, end + 1).
+struct RgIndex {
+    gams_gpu_t *h;
+    gams_index_t *ix = nullptr;
+    std::vector<uint32_t> group;
+    explicit RgIndex(gams_gpu_t *hh) : h(hh) {}
+    ~RgIndex() {
+        if (ix) gams_index_destroy(h, ix);
+    }
+};
+void sw_rg_index(RgIndex &out, const std::vector<Ctg> &ctgs, const std::vector<std::vector<Feature>> &features,
+                 const std::map<std::string, std::vector<Range>> *rgs, double *index_ms) {
+    if (!rgs) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
+    const auto t0 = std::chrono::steady_clock::now();
+    out.group.assign(ctgs.size(), UINT32_MAX);
+    std::map<std::string, uint32_t> seen;
+    std::vector<uint64_t> off{0};
+    std::vector<uint32_t> st, sp;
+    uint32_t g = 0;
+    for (size_t c = 0; c < ctgs.size(); ++c) {
+        if (features[c].empty()) continue;
+        auto was = seen.find(ctgs[c].id);
+        if (was != seen.end()) {
+            out.group[c] = was->second;
+            continue;
+        }
+        auto it = rgs->find(ctgs[c].id);
+        if (it == rgs->end()) {
+            fprintf(stderr, "%s not found in idx\n", ctgs[c].id.c_str());
+            seen[ctgs[c].id] = UINT32_MAX;
+            continue;
+        }
+        for (const Range &r : it->second) {
+            st.push_back((uint32_t)r.start);
+            sp.push_back((uint32_t)r.end + 1u);
+        }
+        off.push_back(st.size());
+        seen[ctgs[c].id] = out.group[c] = g++;
+    }
+    check(out.h, gams_index_create(out.h, g, off.data(), st.data(), sp.data(), &out.ix));
+    if (index_ms) *index_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 }  // namespace
 
 std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const std::vector<Feature> &features,
-                        const SwArgs &a) {
+                        const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs) {
     const uint32_t nf = (uint32_t)features.size();
     if (nf == 0) return std::string();
     uint32_t len = (uint32_t)(ctg.chr_end - ctg.chr_start + 1);
@@ -917,7 +972,16 @@ std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const
     std::vector<gams_sw_row_t> rows(nrows ? nrows : 1);
     check(h, gams_gpu_sw(h, sg.s, 0, ctg.chr_start, fs.data(), fe.data(), nf, a.size, a.max, a.resize,
                          rows.data(), nrows, &nrows));
-    return sw_format_rows(rows.data(), nrows, ctg, features, 8);
+    if (!(a.actions & GAMS_SW_COUNT)) return sw_format_rows(rows.data(), nrows, ctg, features, 8, a.actions);
+    // rg_count through the array entry (and this host formatter), the path sw_proc_ctgs falls back to
+    RgIndex rx(h);
+    sw_rg_index(rx, std::vector<Ctg>{ctg}, std::vector<std::vector<Feature>>{features}, rgs, nullptr);
+    const uint32_t zero = 0;
+    const uint64_t feat_off[2] = {0, nf};
+    std::vector<int32_t> cnt(nrows ? nrows : 1);
+    check(h, gams_gpu_sw_count_batch(h, sg.s, 1, &zero, &ctg.chr_start, feat_off, fs.data(), fe.data(), a.size, a.max,
+                                     rx.ix, rx.group.data(), cnt.data(), nrows, nullptr, &nrows));
+    return sw_format_rows(rows.data(), nrows, ctg, features, 8, a.actions, cnt.data());
 }
 
 // Several ctgs on one handle: their sequences go into one seqset per batch of <= batch_bytes bases, all
@@ -925,13 +989,17 @@ std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const
 // into page-locked memory), and the rows of the batch's ctgs are formatted on host threads, a ctg each.
 std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                                       const std::vector<std::vector<Feature>> &features, const SwArgs &a,
-                                      uint64_t batch_bytes) {
+                                      uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
+                                      double *index_ms) {
     if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs: ctgs / seqs / features size mismatch");
     std::vector<std::string> out(ctgs.size());
     std::vector<size_t> todo;                                           // ctgs with features, in ctg order
     for (size_t c = 0; c < ctgs.size(); ++c)
         if (!features[c].empty()) todo.push_back(c);
+    const bool do_count = (a.actions & GAMS_SW_COUNT) != 0;
+    RgIndex rx(h);                                                      // -a count: the rgs of this call's ctgs, once
+    if (do_count && !todo.empty()) sw_rg_index(rx, ctgs, features, rgs, index_ms);
     for (size_t b = 0; b < todo.size();) {
         uint64_t bytes = 0;
         size_t e = b;
@@ -962,9 +1030,18 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
                 fe[feat_off[k] + f] = fv[f].end;
             }
         }
+        std::vector<uint32_t> rg_group(do_count ? n : 0);
+        for (uint32_t k = 0; k < rg_group.size(); ++k) rg_group[k] = rx.group[todo[b + k]];
         SeqSetGuard sg{h};
         check(h, gams_seqset_create(h, n, lens.data(), &sg.s));
-        check(h, gams_seqset_upload_all(h, sg.s, ptrs.data()));
+        // -a count alone reads no sequence byte on the device path: the bases go up only when a gc or the rows of
+        // the fallback below need them
+        bool uploaded = false;
+        auto upload = [&]() {
+            if (!uploaded) check(h, gams_seqset_upload_all(h, sg.s, ptrs.data()));
+            uploaded = true;
+        };
+        if (a.actions & GAMS_SW_GC) upload();
         std::vector<uint64_t> row_off(n + 1, 0);
         uint64_t nrows = 0;
         {
@@ -979,8 +1056,9 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
             const char *text = nullptr;
             uint64_t tbytes = 0;
             const uint64_t *toff = nullptr;
-            const int rc = gams_gpu_sw_text(h, sg.s, n, index.data(), chr.data(), chr_start.data(), feat_off.data(), fs.data(),
-                                            fe.data(), ids.data(), a.size, a.max, a.resize, &text, &tbytes, &toff, &nrows);
+            const int rc = gams_gpu_sw_text_actions(h, sg.s, n, index.data(), chr.data(), chr_start.data(), feat_off.data(),
+                                                    fs.data(), fe.data(), ids.data(), a.size, a.max, a.resize, a.actions,
+                                                    rx.ix, rg_group.data(), &text, &tbytes, &toff, &nrows);
             if (rc == GAMS_OK) {
                 // proc_ctg's Strings: slices of the page-locked text, copied by a few host threads (one thread moves
                 // ~10 GB/s; 313 MB for the 4.1 M rows of a 30-Mb chromosome)
@@ -1007,6 +1085,7 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
             }
             if (rc != GAMS_EUNSUPPORTED) check(h, rc);
         }
+        upload();
         check(h, gams_gpu_sw_batch(h, sg.s, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
                                    a.size, a.max, a.resize, nullptr, 0, row_off.data(), &nrows));
         // rows land in page-locked memory: the readback runs at the rate of the link
@@ -1019,6 +1098,10 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
         gams_sw_row_t *rows = static_cast<gams_sw_row_t *>(pin.p);
         check(h, gams_gpu_sw_batch(h, sg.s, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
                                    a.size, a.max, a.resize, rows, nrows, row_off.data(), &nrows));
+        std::vector<int32_t> cnt(do_count ? std::max<uint64_t>(nrows, 1) : 0);
+        if (do_count)
+            check(h, gams_gpu_sw_count_batch(h, sg.s, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
+                                             a.size, a.max, rx.ix, rg_group.data(), cnt.data(), nrows, nullptr, &nrows));
         // format: ctgs of the batch dealt to a few host threads
         const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({16, std::thread::hardware_concurrency(), (uint64_t)n}));
         std::atomic<uint32_t> next{0};
@@ -1027,7 +1110,8 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
             try {
                 for (uint32_t k = next.fetch_add(1); k < n; k = next.fetch_add(1))
                     out[todo[b + k]] = sw_format_rows(rows + row_off[k], row_off[k + 1] - row_off[k], ctgs[todo[b + k]],
-                                                      features[todo[b + k]], T > 1 ? 1 : 8);
+                                                      features[todo[b + k]], T > 1 ? 1 : 8, a.actions,
+                                                      do_count ? cnt.data() + row_off[k] : nullptr);
             } catch (...) {
                 errs[t] = std::current_exception();
             }

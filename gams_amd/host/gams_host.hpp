@@ -60,6 +60,7 @@ struct WaveArgs {          // defaults of src/cmd_gams/wave.rs:23-99
 
 struct SwArgs {            // defaults of src/cmd_gams/sw.rs:9-85
     int32_t size = 100, max = 20, resize = 500;
+    uint32_t actions = GAMS_SW_GC;   // --action (sw.rs:28-32): GAMS_SW_GC | GAMS_SW_COUNT
 };
 
 class Error : public std::runtime_error {
@@ -121,19 +122,27 @@ void cover_multi(const std::vector<gams_gpu_t *> &handles, uint32_t n_groups, co
                  const int32_t *lo, const int32_t *hi, const uint32_t *q_group, const int32_t *clip_lo,
                  const int32_t *clip_hi, const int32_t *qs, const int32_t *qe, uint64_t nq, float *prop);
 
-// sw.rs:108-194
+// sw.rs:108-194.  With GAMS_SW_COUNT in a.actions, `rgs` (what read_range returns: the rg ranges of each ctg id) is
+// the idx:rg: source; each call builds the device index of its own ctgs once.  A ctg without an entry in `rgs` counts
+// 0 and is reported once on stderr ("{ctg} not found in idx", utils.rs:30 -- the reference says it once per window).
 std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const std::vector<Feature> &features,
-                        const SwArgs &a);
+                        const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr);
 // several ctgs on one handle: one seqset, one gams_gpu_sw_batch call and one readback per batch of
-// <= batch_bytes bases; rows returned per ctg in the order given ("" for a ctg without features)
+// <= batch_bytes bases; rows returned per ctg in the order given ("" for a ctg without features).
+// index_ms (may be NULL) receives the ms of the rg index build (-a count).
 std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                                       const std::vector<std::vector<Feature>> &features, const SwArgs &a,
-                                      uint64_t batch_bytes = 256ull << 20);
+                                      uint64_t batch_bytes = 256ull << 20,
+                                      const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                                      double *index_ms = nullptr);
 // `gams sw --parallel` over several devices: ctgs split over the handles by LPT on their feature
-// counts, one host thread per handle, rows returned per ctg in the order given.
+// counts, one host thread per handle, rows returned per ctg in the order given.  Each handle indexes the rgs of the
+// ctgs it was given; index_ms = the longest of those builds.
 std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &handles, const std::vector<Ctg> &ctgs,
                                             const std::vector<const uint8_t *> &seqs,
-                                            const std::vector<std::vector<Feature>> &features, const SwArgs &a);
+                                            const std::vector<std::vector<Feature>> &features, const SwArgs &a,
+                                            const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                                            double *index_ms = nullptr);
 
 // idx:ctg: / idx:rg: on the device (redis.rs:236-324) + the locate loop (locate.rs:111-141)
 class Locator {

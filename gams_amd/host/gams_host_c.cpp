@@ -387,6 +387,94 @@ std::map<std::string, gams::Runlist> runlists_of(const char *runlists) {
 }
 }  // namespace
 
+// sw with an action set (GAMS_SW_GC | GAMS_SW_COUNT, sw.rs:28-32) and, for GAMS_SW_COUNT, the rg: records as
+// "ctg_id\trange" lines (as gams_host_locate takes them; every ctg of the call gets a group, empty or not).  The
+// entries without `actions` above are these with GAMS_SW_GC.
+namespace {
+gams::SwArgs sw_args(int32_t size, int32_t max, int32_t resize, uint32_t actions) {
+    gams::SwArgs a;
+    a.size = size;
+    a.max = max;
+    a.resize = resize;
+    a.actions = actions;
+    return a;
+}
+std::vector<std::vector<gams::Feature>> sw_feature_rows(uint32_t n, const char *features) {
+    std::vector<std::vector<gams::Feature>> f(n);
+    for (const std::string &ln : split_lines(features)) {
+        std::istringstream is(ln);
+        std::string ci, id, s0, s1;
+        std::getline(is, ci, '\t');
+        std::getline(is, id, '\t');
+        std::getline(is, s0, '\t');
+        std::getline(is, s1, '\t');
+        f.at((size_t)std::stoul(ci)).push_back(gams::Feature{id, std::stoi(s0), std::stoi(s1)});
+    }
+    return f;
+}
+thread_local double g_sw_index_ms = 0.0;
+}  // namespace
+
+char *gams_host_sw_actions(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
+                           const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
+                           const int32_t *fe, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                           const char *rg_lines) {
+    return guarded([&] {
+        const char *ids[1] = {ctg_id}, *chrs[1] = {chr};
+        gams::Ctg c = make_ctgs(1, ids, chrs, &chr_start, &chr_end)[0];
+        std::vector<gams::Feature> f(nf);
+        for (uint32_t i = 0; i < nf; ++i) f[i] = gams::Feature{feature_ids[i], fs[i], fe[i]};
+        const std::map<std::string, std::vector<gams::Range>> rg_of = rg_index_of(1, ids, rg_lines);
+        return gams::sw_proc_ctg(h, c, seq, f, sw_args(size, max, resize, actions), &rg_of);
+    });
+}
+
+char *gams_host_sw_multi_actions(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                                 const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                                 const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
+                                 int32_t resize, uint32_t actions, const char *rg_lines) {
+    return guarded([&] {
+        const std::map<std::string, std::vector<gams::Range>> rg_of = rg_index_of(n, ids, rg_lines);
+        std::string out;
+        for (auto &s : gams::sw_proc_ctgs_multi(std::vector<gams_gpu_t *>(handles, handles + n_handles),
+                                                make_ctgs(n, ids, chrs, starts, ends),
+                                                std::vector<const uint8_t *>(seqs, seqs + n), sw_feature_rows(n, features),
+                                                sw_args(size, max, resize, actions), &rg_of))
+            out += s;
+        return out;
+    });
+}
+
+// as gams_host_sw_multi_timed; operator_ms includes the build of the rg index, which gams_host_last_sw_index_ms then
+// reports on its own
+char *gams_host_sw_multi_actions_timed(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                                       const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                                       const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
+                                       int32_t resize, uint32_t actions, const char *rg_lines, double *operator_ms,
+                                       uint64_t *out_len) {
+    return guarded_bytes(out_len, [&] {
+        const std::vector<std::vector<gams::Feature>> f = sw_feature_rows(n, features);
+        const std::map<std::string, std::vector<gams::Range>> rg_of = rg_index_of(n, ids, rg_lines);
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        const std::vector<const uint8_t *> sv(seqs, seqs + n);
+        const std::vector<gams_gpu_t *> hv(handles, handles + n_handles);
+        g_sw_index_ms = 0.0;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::string> rows =
+            gams::sw_proc_ctgs_multi(hv, cv, sv, f, sw_args(size, max, resize, actions), &rg_of, &g_sw_index_ms);
+        if (operator_ms) *operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        size_t total = 0;
+        for (auto &s : rows) total += s.size();
+        std::string out;
+        out.reserve(total);
+        for (auto &s : rows) out += s;
+        return out;
+    });
+}
+
+// ms the last gams_host_sw_multi_actions_timed of this thread spent building the rg index (the longest handle's)
+double gams_host_last_sw_index_ms(void) { return g_sw_index_ms; }
+
 // locate -f / --count over the bytes of the input file (bytes, n_bytes: not NUL-terminated); rg_lines as for
 // gams_host_locate.  *out_len receives the text's length.
 char *gams_host_locate_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,

@@ -15,6 +15,7 @@
  *   gams_gpu_wave*            src/cmd_gams/wave.rs:138-155  (sliding + gc_content + thresholding_algo)
  *                             = src/libs/window.rs:78-94, bio gc_content, src/libs/stat.rs:16-56
  *   gams_gpu_sw(_batch, _text) src/cmd_gams/sw.rs:141-184   (center_sw + cache_gc_content + cache_gc_stat; _text: + the rows' text, :152-190)
+ *   gams_gpu_sw_text_actions, gams_gpu_sw_count_batch: + rg_count (sw.rs:28-32 `--action count`, fixed as count_rg)
  *                             = src/libs/window.rs:3-56,96-124, src/libs/utils.rs:141-213
  *   gams_gpu_count            src/libs/utils.rs:24-36       (count_rg -> Lapper::count)
  *   gams_gpu_locate           src/libs/utils.rs:7-22        (find_one_idx -> Lapper::find().next())
@@ -236,7 +237,7 @@ int gams_gpu_sw_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uin
 
 /* The rows of gams_gpu_sw_batch as the TSV text of `gams sw` (sw.rs:152-190 and the Display of Sw, data.rs:58-83:
  * "sw:{feature id}:{serial}\t{chr}:{start}-{end}\t{M|L|R}\t{distance}\t{gc_content}\t{gc_mean}\t{gc_stddev}\t{gc_cv}\t\n",
- * the last field -- rg_count -- empty), formatted on the device.  chr[k] = chromosome name of selected ctg k,
+ * the last field -- rg_count -- empty: gams_gpu_sw_text_actions fills it), formatted on the device.  chr[k] = chromosome name of selected ctg k,
  * feat_id[f] = id of feature f ("feature:{ctg}:{serial}", feature.rs:81-83), both NUL-terminated.  *text
  * (text_bytes bytes, no header, no NUL) and *ctg_off (n_sel + 1 offsets: the rows of selected ctg k are
  * text[ctg_off[k] .. ctg_off[k+1])) point into page-locked memory owned by the handle, valid until the handle's next
@@ -248,6 +249,34 @@ int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint
                      const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
                      int32_t size, int32_t max, int32_t resize, const char **text, uint64_t *text_bytes,
                      const uint64_t **ctg_off, uint64_t *n_rows);
+
+/* `gams sw --action` (sw.rs:28-32, :116-119): the action set of a call, a mask of these bits.  `gibbs` is accepted
+ * upstream and computes nothing: it has no bit. */
+#define GAMS_SW_GC 1u    /* gc_content, gc_mean, gc_stddev, gc_cv (fields 5-8) */
+#define GAMS_SW_COUNT 2u /* rg_count (field 9) */
+
+/* gams_gpu_sw_text with an action set.  Without GAMS_SW_GC fields 5-8 are empty ("\t\t\t", data.rs:60-70) and the
+ * call reads no sequence byte (the seqset need not be uploaded); without GAMS_SW_COUNT field 9 is empty.  With
+ * GAMS_SW_COUNT field 9 is count_rg(idx:rg:, ctg, Range::from(chr, win.min(), win.max())) (utils.rs:24-36) =
+ * Lapper::count(start, end) of the window against group rg_group[k] of rg_ix for the windows of selected ctg k --
+ * the range's end is exclusive there, as in `locate --count`; rg_group[k] >= the index's groups (e.g. UINT32_MAX):
+ * no group, the count is 0.  GAMS_EINVAL for bits beyond the two flags and for GAMS_SW_COUNT without rg_ix (or
+ * without rg_group when n_sel > 0).  Output and ownership as for gams_gpu_sw_text, which is this call with
+ * GAMS_SW_GC and no index. */
+int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                             const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
+                             const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
+                             int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
+                             const uint32_t *rg_group, const char **text, uint64_t *text_bytes,
+                             const uint64_t **ctg_off, uint64_t *n_rows);
+/* The rg_count of every window of gams_gpu_sw_batch (same arguments without resize, same row order, row_off and size
+ * query: count == NULL or cap == 0), rg_ix / rg_group as in gams_gpu_sw_text_actions: count[r] for row r.  Reads no
+ * sequence byte.  What a host formatter needs next to the rows when the text entry returns GAMS_EUNSUPPORTED. */
+int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                            const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                            const int32_t *feat_end, int32_t size, int32_t max, gams_index_t *rg_ix,
+                            const uint32_t *rg_group, int32_t *count, uint64_t cap, uint64_t *row_off,
+                            uint64_t *n_rows);
 
 /* gc_content (round4, utils.rs:141-162) of n chromosome ranges inside ctg i: what `gams peak`
  * asks per merged peak (peak.rs:79; second "next" row of SURVEY section 8f). */
