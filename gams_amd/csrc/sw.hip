@@ -22,6 +22,7 @@
 // neither needs the gc index nor touches the sequence bytes.
 
 #include "interval_kernels.hpp"
+#include "text_emit.hpp"
 
 #include <string>
 
@@ -417,30 +418,6 @@ struct SwTextArgs {
     const int32_t *cnt;                // per row rg_count (nullptr: the field stays empty)
 };
 
-__device__ __forceinline__ uint32_t sw_digits(uint32_t v) {
-    return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u
-         : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
-}
-__device__ __forceinline__ char *sw_put_dec(char *p, uint32_t v) {
-    const uint32_t n = sw_digits(v);
-    char *e = p + n;
-    do {
-        *--e = (char)('0' + v % 10u);
-        v /= 10u;
-    } while (v);
-    return p + n;
-}
-// an i32 as Rust's `{}` prints it
-__device__ __forceinline__ uint32_t sw_i32_len(int32_t v) {
-    return v < 0 ? 1u + sw_digits(0u - (uint32_t)v) : sw_digits((uint32_t)v);
-}
-__device__ __forceinline__ char *sw_put_i32(char *p, int32_t v) {
-    if (v < 0) {
-        *p++ = '-';
-        return sw_put_dec(p, 0u - (uint32_t)v);
-    }
-    return sw_put_dec(p, (uint32_t)v);
-}
 // a round4 value as Rust prints it; returns the length (p == nullptr: length only); *bad set for values not covered
 __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
     if (v != v) {
@@ -462,9 +439,9 @@ __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
         fr /= 10u;
         --nd;
     }
-    const uint32_t n = sw_digits(ip) + (nd ? 1u + nd : 0u);
+    const uint32_t n = dec_digits(ip) + (nd ? 1u + nd : 0u);
     if (p) {
-        p = sw_put_dec(p, ip);
+        p = put_dec(p, ip);
         if (nd) {
             *p++ = '.';
             char *e = p + nd;
@@ -504,15 +481,15 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
     if (w.start < 0 || w.end < 0 || w.distance < 0 || (uint32_t)w.type > 2u) *bad = true;
     const uint32_t st = (uint32_t)w.start, en = (uint32_t)w.end, di = (uint32_t)w.distance;
     if (!p) {
-        uint32_t n = 3u + idn + 1u + sw_digits(c.serial) + 1u + nmn + 1u + sw_digits(st);
-        if (en != st) n += 1u + sw_digits(en);
-        n += 1u + 1u + 1u + sw_digits(di) + 1u;
+        uint32_t n = 3u + idn + 1u + dec_digits(c.serial) + 1u + nmn + 1u + dec_digits(st);
+        if (en != st) n += 1u + dec_digits(en);
+        n += 1u + 1u + 1u + dec_digits(di) + 1u;
         if (a.gc)
             n += sw_put_f4(nullptr, w.gc_content, bad) + 1u + sw_put_f4(nullptr, w.gc_mean, bad) + 1u +
                  sw_put_f4(nullptr, w.gc_stddev, bad) + 1u + sw_put_f4(nullptr, w.gc_cv, bad) + 2u;
         else
             n += 3u + 2u;
-        if (a.cnt) n += sw_i32_len(a.cnt[r]);
+        if (a.cnt) n += i32_len(a.cnt[r]);
         return n;
     }
     char *q = p;
@@ -521,19 +498,19 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
     *q++ = ':';
     for (uint32_t i = 0; i < idn; ++i) *q++ = a.ids[id0 + i];
     *q++ = ':';
-    q = sw_put_dec(q, c.serial);
+    q = put_dec(q, c.serial);
     *q++ = '\t';
     for (uint32_t i = 0; i < nmn; ++i) *q++ = a.names[nm0 + i];
     *q++ = ':';
-    q = sw_put_dec(q, st);
+    q = put_dec(q, st);
     if (en != st) {
         *q++ = '-';
-        q = sw_put_dec(q, en);
+        q = put_dec(q, en);
     }
     *q++ = '\t';
     *q++ = "MLR"[(uint32_t)w.type > 2u ? 0u : (uint32_t)w.type];
     *q++ = '\t';
-    q = sw_put_dec(q, di);
+    q = put_dec(q, di);
     *q++ = '\t';
     if (a.gc) {
         q += sw_put_f4(q, w.gc_content, bad);
@@ -549,7 +526,7 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
         *q++ = '\t';
     }
     *q++ = '\t';
-    if (a.cnt) q = sw_put_i32(q, a.cnt[r]);
+    if (a.cnt) q = put_i32(q, a.cnt[r]);
     *q++ = '\n';
     return (uint32_t)(q - p);
 }
@@ -569,38 +546,8 @@ __global__ __launch_bounds__(256) void sw_text_len_kernel(const SwTextArgs a) {
         sum += l;
     }
     if (bad) a.words[1] = 1ull;
-    for (int d = 32; d; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
-    if ((tid & 63u) == 0u) ws[tid >> 6] = sum;
-    __syncthreads();
-    if (tid == 0u) a.blk_len[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
-}
-
-// exclusive prefix of the blocks' byte counts (one workgroup), the total behind them
-__global__ __launch_bounds__(1024) void sw_text_scan_kernel(const uint32_t *blk_len, uint32_t nb, unsigned long long *blk_off,
-                                                            unsigned long long *words) {
-    __shared__ unsigned long long wsum[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const uint32_t per = (nb + 1023u) / 1024u;
-    const uint32_t b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
-    unsigned long long mine = 0;
-    for (uint32_t b = b0; b < b1; ++b) mine += blk_len[b];
-    const unsigned long long inc = wave_incl_scan_u64(mine);
-    if (lane == 63u) wsum[wv] = inc;
-    __syncthreads();
-    unsigned long long base = 0, all = 0;
-    for (uint32_t w = 0; w < 16u; ++w) {
-        if (w < wv) base += wsum[w];
-        all += wsum[w];
-    }
-    unsigned long long off = base + inc - mine;
-    for (uint32_t b = b0; b < b1; ++b) {
-        blk_off[b] = off;
-        off += blk_len[b];
-    }
-    if (tid == 0u) {
-        blk_off[nb] = all;
-        words[0] = all;
-    }
+    const uint32_t tot = block_sum_256(sum, ws);
+    if (tid == 0u) a.blk_len[blockIdx.x] = tot;
 }
 
 __global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) {
@@ -635,15 +582,7 @@ __global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) 
     }
     if (!staged) return;
     __syncthreads();
-    const uint32_t head = min(tot, (16u - mis) & 15u);
-    char *const dst = a.text + blk0;
-    if (tid < head) dst[tid] = stage[mis + tid];
-    const uint32_t units = (tot - head) >> 4;
-    const uint4 *const su = reinterpret_cast<const uint4 *>(stage + mis + head);
-    uint4 *const du = reinterpret_cast<uint4 *>(dst + head);
-    for (uint32_t q = tid; q < units; q += 256u) du[q] = su[q];
-    const uint32_t done = head + (units << 4);
-    if (tid < tot - done) dst[done + tid] = stage[mis + done + tid];
+    stage_flush_256(stage, mis, tot, a.text + blk0);
 }
 
 // where every selected ctg's text begins: the bytes of the rows in front of its first row
@@ -988,7 +927,8 @@ static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const 
         SWT_HIP(hipMemsetAsync(ta.words, 0, b_words, h->compute));
         if (nb) {
             hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
-            hipLaunchKernelGGL(sw_text_scan_kernel, dim3(1), dim3(1024), 0, h->compute, ta.blk_len, nb, blk_off, ta.words);
+            hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, h->compute, ta.blk_len, nb, blk_off, ta.words,
+                               0u);
             hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
             hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, h->compute, ta);
             SWT_HIP(hipGetLastError());

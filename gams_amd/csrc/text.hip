@@ -19,6 +19,7 @@
 // the text), the text.
 
 #include "interval_kernels.hpp"
+#include "text_emit.hpp"
 #include "text_fmt.hpp"
 
 #include <algorithm>
@@ -132,35 +133,6 @@ __global__ __launch_bounds__(256) void text_nl_count_kernel(const uint8_t *in, u
     uint32_t tot;
     (void)block_excl_scan_256<uint32_t>(c, ws, tot);
     if (threadIdx.x == 0) blk_nl[blockIdx.x] = tot;
-}
-
-// exclusive prefix of nb block counts (one workgroup of 1024), the total into words[slot]
-template <typename T>
-__global__ __launch_bounds__(1024) void text_blk_scan_kernel(const T *blk, uint32_t nb, unsigned long long *blk_off,
-                                                             unsigned long long *words, uint32_t slot) {
-    __shared__ unsigned long long wsum[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
-    const uint32_t per = (nb + 1023u) / 1024u;
-    const uint32_t b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
-    unsigned long long mine = 0;
-    for (uint32_t b = b0; b < b1; ++b) mine += blk[b];
-    const unsigned long long inc = wave_incl_scan_u64(mine);
-    if (lane == 63u) wsum[wv] = inc;
-    __syncthreads();
-    unsigned long long base = 0, all = 0;
-    for (uint32_t w = 0; w < 16u; ++w) {
-        if (w < wv) base += wsum[w];
-        all += wsum[w];
-    }
-    unsigned long long off = base + inc - mine;
-    for (uint32_t b = b0; b < b1; ++b) {
-        blk_off[b] = off;
-        off += blk[b];
-    }
-    if (tid == 0u) {
-        blk_off[nb] = all;
-        words[slot] = all;
-    }
 }
 
 // pass 2: starts[k + 1] = position after the k-th '\n'; starts[0] = 0 and starts[nl + 1] = n + 1, so that line i
@@ -403,32 +375,6 @@ __global__ __launch_bounds__(256) void text_parse_anno_kernel(const TextLines t,
     keep[i] = 1;
 }
 
-__device__ __forceinline__ uint32_t dec_len(int32_t v) {
-    uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v, n = v < 0 ? 2u : 1u;
-    while (u >= 10u) {
-        u /= 10u;
-        ++n;
-    }
-    return n;
-}
-
-__device__ __forceinline__ char *put_dec(char *q, int32_t v) {
-    const uint32_t n = dec_len(v);
-    uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
-    if (v < 0) *q = '-';
-    char *p = q + n;
-    do {
-        *--p = (char)('0' + u % 10u);
-        u /= 10u;
-    } while (u);
-    return q + n;
-}
-
-__device__ __forceinline__ char *put_bytes(char *q, const char *src, uint64_t n) {
-    for (uint64_t k = 0; k < n; ++k) q[k] = src[k];
-    return q + n;
-}
-
 enum : int { K_LOCATE = 0, K_COUNT = 1, K_ANNO = 2 };
 
 struct RowArgs {
@@ -468,7 +414,7 @@ __device__ uint64_t row_len(const RowArgs &a, uint32_t i, bool &bad) {
     b = a.t.starts[i];
     const uint64_t flen = a.fend[i] - b;
     if (a.kind == K_LOCATE) return flen + 2u + (a.ids.off[c + 1] - a.ids.off[c]);
-    return flen + 2u + dec_len(a.cnt[i]);
+    return flen + 2u + i32_len(a.cnt[i]);
 }
 
 __global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
@@ -520,7 +466,7 @@ __global__ __launch_bounds__(256) void text_row_write_kernel(const RowArgs a) {
         const unsigned long long o = a.ids.off[c];
         q = put_bytes(q, a.ids.bytes + o, a.ids.off[c + 1] - o);   // locate.rs:139
     } else {
-        q = put_dec(q, a.cnt[i]);                                    // locate.rs:137
+        q = put_i32(q, a.cnt[i]);                                    // locate.rs:137
     }
     *q = '\n';
 }
@@ -595,7 +541,7 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     T_HIP(hipMemsetAsync(T->d_in + n_bytes, ' ', n_pad - n_bytes, st));
     // 2. line index, pass 1
     hipLaunchKernelGGL(text_nl_count_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n16, d_bnl, d_words);
-    hipLaunchKernelGGL(text_blk_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_bnl, nbi, d_bnloff, d_words, (uint32_t)W_NL);
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_bnl, nbi, d_bnloff, d_words, (uint32_t)W_NL);
     T_HIP(hipGetLastError());
     T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, 2 * 8, hipMemcpyDeviceToHost, st));
     T_HIP(hipStreamSynchronize(st));
@@ -690,7 +636,7 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     }
     // 5. row lengths and their offsets
     hipLaunchKernelGGL(text_row_len_kernel, dim3(nbr), dim3(256), 0, st, ra);
-    hipLaunchKernelGGL(text_blk_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_bbytes, nbr, d_boff, d_words,
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_bbytes, nbr, d_boff, d_words,
                        (uint32_t)W_BYTES);
     T_HIP(hipGetLastError());
     T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));

@@ -1,0 +1,96 @@
+// text_emit.hpp -- what the device paths that write finished TSV text share (device only): the wave rows and
+// `--signal` rows (wave_rows.hpp), the `sw` rows (sw.hip), the `locate` / `locate --count` / `anno` rows (text.hip).
+// Decimal output, the workgroup sum behind a block's byte count, the one-workgroup prefix over those counts, and
+// the copy of a block's text from its LDS stage to the global text.  The row composers and the three float
+// formats (gctab lookup, sw_put_f4, gams_fmt_prop4) stay with their owners.
+#pragma once
+
+#include "common.hpp"
+
+namespace {
+
+__device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
+    return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u
+         : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
+}
+// the decimal digits of v at p; returns their end
+__device__ __forceinline__ char *put_dec(char *p, uint32_t v) {
+    const uint32_t n = dec_digits(v);
+    char *e = p + n;
+    do {
+        *--e = (char)('0' + v % 10u);
+        v /= 10u;
+    } while (v);
+    return p + n;
+}
+// an i32 as Rust's `{}` prints it
+__device__ __forceinline__ uint32_t i32_len(int32_t v) {
+    return v < 0 ? 1u + dec_digits(0u - (uint32_t)v) : dec_digits((uint32_t)v);
+}
+__device__ __forceinline__ char *put_i32(char *p, int32_t v) {
+    if (v < 0) {
+        *p++ = '-';
+        return put_dec(p, 0u - (uint32_t)v);
+    }
+    return put_dec(p, (uint32_t)v);
+}
+__device__ __forceinline__ char *put_bytes(char *q, const char *src, uint64_t n) {
+    for (uint64_t k = 0; k < n; ++k) q[k] = src[k];
+    return q + n;
+}
+
+// Sum of v over a 256-thread workgroup (4 waves); `ws` is LDS scratch of 4 elements, the call holds one barrier.
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t *ws) {
+    const uint32_t tid = threadIdx.x;
+    for (int d = 32; d; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d, 64);
+    if ((tid & 63u) == 0u) ws[tid >> 6] = v;
+    __syncthreads();
+    return ws[0] + ws[1] + ws[2] + ws[3];
+}
+
+// stage[mis, mis + tot) -> dst[0, tot) by a workgroup of 256, after the barrier that completes the stage.  `stage`
+// is 16-B aligned LDS and mis = dst's offset inside a 16-B unit of the text, so the middle leaves as 16-B stores on
+// 16-B boundaries and only the ragged ends go byte by byte.
+__device__ __forceinline__ void stage_flush_256(const char *stage, uint32_t mis, uint32_t tot, char *dst) {
+    const uint32_t tid = threadIdx.x;
+    const uint32_t head = min(tot, (16u - mis) & 15u);          // bytes in front of the first 16-B boundary
+    if (tid < head) dst[tid] = stage[mis + tid];
+    const uint32_t units = (tot - head) >> 4;
+    const uint4 *const su = reinterpret_cast<const uint4 *>(stage + mis + head);   // 16-B aligned: mis + head is 0 mod 16
+    uint4 *const du = reinterpret_cast<uint4 *>(dst + head);
+    for (uint32_t q = tid; q < units; q += 256u) du[q] = su[q];
+    const uint32_t done = head + (units << 4);
+    if (tid < tot - done) dst[done + tid] = stage[mis + done + tid];
+}
+
+// exclusive prefix of nb block counts (one workgroup of 1024): blk_off[b] = bytes in front of block b, the total
+// into blk_off[nb] and words[slot]
+template <typename T>
+__global__ __launch_bounds__(1024) void blk_offsets_scan_kernel(const T *blk, uint32_t nb, unsigned long long *blk_off,
+                                                                unsigned long long *words, uint32_t slot) {
+    __shared__ unsigned long long wsum[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wv = tid >> 6;
+    const uint32_t per = (nb + 1023u) / 1024u;
+    const uint32_t b0 = min(nb, tid * per), b1 = min(nb, b0 + per);
+    unsigned long long mine = 0;
+    for (uint32_t b = b0; b < b1; ++b) mine += blk[b];
+    const unsigned long long inc = wave_incl_scan_u64(mine);
+    if (lane == 63u) wsum[wv] = inc;
+    __syncthreads();
+    unsigned long long base = 0, all = 0;
+    for (uint32_t w = 0; w < 16u; ++w) {
+        if (w < wv) base += wsum[w];
+        all += wsum[w];
+    }
+    unsigned long long off = base + inc - mine;
+    for (uint32_t b = b0; b < b1; ++b) {
+        blk_off[b] = off;
+        off += blk[b];
+    }
+    if (tid == 0u) {
+        blk_off[nb] = all;
+        words[slot] = all;
+    }
+}
+
+}  // namespace

@@ -206,6 +206,19 @@ constexpr uint32_t kMaxTileBytes = 65520;  // chunk prefix is 16 bits
 constexpr uint32_t kMaxTw = 8192;          // 2 bits/iteration in a 64-bit register
 constexpr uint32_t kOffOneGroup = 32768;   // tables up to here: wave_offsets_kernel (one workgroup, one launch)
 
+// exclusive prefix of n counts on `st`, the total and the maximum into tot[0..1]: one workgroup, or spans of
+// kOffSpan counts in three launches (wave_kernels.hpp)
+void wave_queue_offsets(hipStream_t st, const uint32_t *cnt, uint32_t n, unsigned long long *off, unsigned long long *tot) {
+    if (n <= kOffOneGroup) {
+        hipLaunchKernelGGL(wave_offsets_kernel, dim3(1), dim3(1024), 0, st, cnt, n, off, tot);
+        return;
+    }
+    const unsigned spans = (n + kOffSpan - 1u) / kOffSpan;
+    hipLaunchKernelGGL(wave_offsets_sum_kernel, dim3(spans), dim3(1024), 0, st, cnt, n, off);
+    hipLaunchKernelGGL(wave_offsets_base_kernel, dim3(1), dim3(1024), 0, st, n, off, tot);
+    hipLaunchKernelGGL(wave_offsets_scan_kernel, dim3(spans), dim3(1024), 0, st, cnt, n, off);
+}
+
 size_t wave_lds_bytes(uint32_t max_chunks, uint32_t max_win, bool wide, bool k16) {
     size_t b = 0;
     const size_t mwp = (max_win + 3u) & ~1u;
@@ -1462,18 +1475,7 @@ int gams_wave_peaks(gams_gpu_t *h, gams_wave_plan_t *p, const gams_peak_t **peak
                                         reinterpret_cast<void **>(&p->d_dense), &p->d_dense_bytes));
             p->dense_cap = p->d_dense_bytes / sizeof(gams_peak_t);
         }
-        if (nt <= kOffOneGroup) {
-            hipLaunchKernelGGL(wave_offsets_kernel, dim3(1), dim3(1024), 0, h->readback, w.d_tile_cnt, (uint32_t)nt,
-                               p->d_tile_off, d_totals);
-        } else {
-            const unsigned spans = (unsigned)((nt + kOffSpan - 1) / kOffSpan);
-            hipLaunchKernelGGL(wave_offsets_sum_kernel, dim3(spans), dim3(1024), 0, h->readback, w.d_tile_cnt, (uint32_t)nt,
-                               p->d_tile_off);
-            hipLaunchKernelGGL(wave_offsets_base_kernel, dim3(1), dim3(1024), 0, h->readback, (uint32_t)nt, p->d_tile_off,
-                               d_totals);
-            hipLaunchKernelGGL(wave_offsets_scan_kernel, dim3(spans), dim3(1024), 0, h->readback, w.d_tile_cnt, (uint32_t)nt,
-                               p->d_tile_off);
-        }
+        wave_queue_offsets(h->readback, w.d_tile_cnt, (uint32_t)nt, p->d_tile_off, d_totals);
         GAMS_HIP(h, hipGetLastError());
         hipLaunchKernelGGL(wave_gather_kernel, dim3((unsigned)nt), dim3(64), 0, h->readback, w.d_peaks,
                            p->tile_cap, w.d_tile_cnt, p->d_tile_off, p->d_dense, (unsigned long long)p->dense_cap);
@@ -1567,6 +1569,32 @@ std::string rows_fmt_f32(float v) {
         out += digits;
     }
     return out;
+}
+
+// What the row kernels print from, built on the host: the chromosome names in one blob with a RowCtg per ctg
+// (ctgs of one chromosome share its name; one copy per distinct pointer is not worth the bookkeeping: a few bytes
+// per ctg), and the gc text table, rows_fmt_f32(k / size) for every count k.  "" or what `who` has to report.
+std::string rows_text_tables(const char *who, uint32_t n_ctg, const char *const *chr, const int32_t *chr_start, int32_t size,
+                             std::vector<RowCtg> &rc, std::string &blob, std::vector<uint8_t> &gct) {
+    rc.assign(std::max<uint32_t>(n_ctg, 1), RowCtg{});
+    blob.clear();
+    for (uint32_t c = 0; c < n_ctg; ++c) {
+        const size_t len = std::strlen(chr[c]);
+        size_t at = blob.find(chr[c]);
+        if (at == std::string::npos || len == 0) {
+            at = blob.size();
+            blob += chr[c];
+        }
+        rc[c] = RowCtg{(uint32_t)at, (uint32_t)len, chr_start[c], 0u};
+    }
+    gct.assign(((size_t)size + 1) * kGcStride, 0);
+    for (int32_t k = 0; k <= size; ++k) {
+        const std::string t = rows_fmt_f32((float)k / (float)size);     // gc_content as wave.rs prints it
+        if (t.size() > kGcStride - 1) return std::string(who) + ": gc_content text too long";
+        gct[(size_t)k * kGcStride] = (uint8_t)t.size();
+        std::memcpy(&gct[(size_t)k * kGcStride + 1], t.data(), t.size());
+    }
+    return "";
 }
 
 struct RowTables {
@@ -1835,27 +1863,13 @@ int gams_wave_rows_setup(gams_gpu_t *h, gams_wave_plan_t *p, const char *const *
     WaveRows *r = p->rows;
     r->dmax = (uint32_t)dmax;
     r->begun = false;
-    // names (one copy per distinct pointer is not worth the bookkeeping: a few bytes per ctg), gc text table
-    std::vector<RowCtg> rc(std::max<uint32_t>(n_ctg, 1));
+    std::vector<RowCtg> rc;
     std::string blob;
+    std::vector<uint8_t> gct;
+    const std::string bad = rows_text_tables("wave_rows_setup", n_ctg, chr, chr_start, q.size, rc, blob, gct);
+    if (!bad.empty()) return gams_fail(h, GAMS_EUNSUPPORTED, bad);
     r->max_name = 0;
-    for (uint32_t c = 0; c < n_ctg; ++c) {
-        const size_t len = std::strlen(chr[c]);
-        size_t at = blob.find(chr[c]);   // ctgs of one chromosome share its name
-        if (at == std::string::npos || (len == 0)) {
-            at = blob.size();
-            blob += chr[c];
-        }
-        rc[c] = RowCtg{(uint32_t)at, (uint32_t)len, chr_start[c], 0u};
-        r->max_name = std::max<uint32_t>(r->max_name, (uint32_t)len);
-    }
-    std::vector<uint8_t> gct(((size_t)q.size + 1) * kGcStride, 0);
-    for (int32_t k = 0; k <= q.size; ++k) {
-        const std::string t = rows_fmt_f32((float)k / (float)q.size);     // gc_content as wave.rs prints it
-        if (t.size() > kGcStride - 1) return gams_fail(h, GAMS_EUNSUPPORTED, "wave_rows_setup: gc_content text too long");
-        gct[(size_t)k * kGcStride] = (uint8_t)t.size();
-        std::memcpy(&gct[(size_t)k * kGcStride + 1], t.data(), t.size());
-    }
+    for (const RowCtg &c : rc) r->max_name = std::max(r->max_name, c.name_len);
     const size_t b_ctgs = wave_align256(rc.size() * sizeof(RowCtg)), b_names = wave_align256(std::max<size_t>(blob.size(), 1)),
                  b_gc = wave_align256(gct.size()), b_words = wave_align256(((size_t)n_ctg + 1 + 4) * 8);
     GAMS_HIP(h, gams_pool_alloc(h, false, b_ctgs + b_names + b_gc + b_words, reinterpret_cast<void **>(&r->arena),
@@ -1983,24 +1997,11 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
         if (wrc != GAMS_OK) return wrc;
     }
     // names, gc text table (as gams_wave_rows_setup), tiles of kSigRows windows
-    std::vector<RowCtg> rc(std::max<uint32_t>(n_ctg, 1));
+    std::vector<RowCtg> rc;
     std::string blob;
-    for (uint32_t c = 0; c < n_ctg; ++c) {
-        const size_t len = std::strlen(chr[c]);
-        size_t at = blob.find(chr[c]);
-        if (at == std::string::npos || len == 0) {
-            at = blob.size();
-            blob += chr[c];
-        }
-        rc[c] = RowCtg{(uint32_t)at, (uint32_t)len, chr_start[c], 0u};
-    }
-    std::vector<uint8_t> gct(((size_t)q.size + 1) * kGcStride, 0);
-    for (int32_t k = 0; k <= q.size; ++k) {
-        const std::string t = rows_fmt_f32((float)k / (float)q.size);
-        if (t.size() > kGcStride - 1) return gams_fail(h, GAMS_EUNSUPPORTED, "wave_signal_text: gc_content text too long");
-        gct[(size_t)k * kGcStride] = (uint8_t)t.size();
-        std::memcpy(&gct[(size_t)k * kGcStride + 1], t.data(), t.size());
-    }
+    std::vector<uint8_t> gct;
+    const std::string bad = rows_text_tables("wave_signal_text", n_ctg, chr, chr_start, q.size, rc, blob, gct);
+    if (!bad.empty()) return gams_fail(h, GAMS_EUNSUPPORTED, bad);
     if (!p->sigtext) p->sigtext = new WaveSig();
     WaveSig *g = p->sigtext;
     if (!g->arena || g->names_cap < blob.size()) {
@@ -2060,14 +2061,7 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
     a.words = g->d_words;
     hipLaunchKernelGGL(sig_len_kernel, dim3(g->n_tiles), dim3(256), 0, st, a);
     unsigned long long *const d_totals = g->d_blk_off + g->n_tiles;
-    if (g->n_tiles <= kOffOneGroup) {
-        hipLaunchKernelGGL(wave_offsets_kernel, dim3(1), dim3(1024), 0, st, g->d_blk_len, g->n_tiles, g->d_blk_off, d_totals);
-    } else {
-        const unsigned spans = (g->n_tiles + kOffSpan - 1u) / kOffSpan;
-        hipLaunchKernelGGL(wave_offsets_sum_kernel, dim3(spans), dim3(1024), 0, st, g->d_blk_len, g->n_tiles, g->d_blk_off);
-        hipLaunchKernelGGL(wave_offsets_base_kernel, dim3(1), dim3(1024), 0, st, g->n_tiles, g->d_blk_off, d_totals);
-        hipLaunchKernelGGL(wave_offsets_scan_kernel, dim3(spans), dim3(1024), 0, st, g->d_blk_len, g->n_tiles, g->d_blk_off);
-    }
+    wave_queue_offsets(st, g->d_blk_len, g->n_tiles, g->d_blk_off, d_totals);
     GAMS_HIP(h, hipGetLastError());
     GAMS_HIP(h, hipMemcpyAsync(h->pin_scratch, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     GAMS_HIP(h, hipStreamSynchronize(st));       // (the staged tables above live on this call's stack until here)

@@ -23,6 +23,7 @@
 // with dmin > 1: components are no longer chains) stay with the host's union-find.
 #pragma once
 
+#include "text_emit.hpp"
 #include "wave_kernels.hpp"
 
 namespace {
@@ -70,19 +71,6 @@ struct RowArgs {
 __device__ __forceinline__ uint64_t rows_n(const RowArgs &a) {
     const unsigned long long total = a.n_rec[0], worst = a.n_rec[1];
     return (worst > a.tile_cap || total > a.cap) ? 0ull : (uint64_t)total;
-}
-
-__device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
-    return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u
-         : v < 10000000u ? 7u : v < 100000000u ? 8u : v < 1000000000u ? 9u : 10u;
-}
-// decimal digits of v ending just before `end`; returns where they start
-__device__ __forceinline__ char *put_dec_back(char *end, uint32_t v) {
-    do {
-        *--end = (char)('0' + v % 10u);
-        v /= 10u;
-    } while (v);
-    return end;
 }
 
 __global__ __launch_bounds__(256) void rows_link_kernel(const RowArgs a) {
@@ -268,12 +256,10 @@ __device__ __forceinline__ void row_put(const RowArgs &a, char *p, uint64_t i, c
         *p++ = ')';
     }
     *p++ = ':';
-    p += dec_digits(s);
-    put_dec_back(p, s);
+    p = put_dec(p, s);
     if (e != s) {
         *p++ = '-';
-        p += dec_digits(e);
-        put_dec_back(p, e);
+        p = put_dec(p, e);
     }
     *p++ = '\t';
     const uint8_t *g = a.gctab + (size_t)r.gc_count * kGcStride;
@@ -329,16 +315,7 @@ __global__ __launch_bounds__(256) void rows_write_kernel(const RowArgs a) {
     }
     if (!staged) return;
     __syncthreads();
-    // stage[mis, mis + tot) -> text[blk0, blk0 + tot): whole 16-B units in the middle
-    const uint32_t head = min(tot, (16u - mis) & 15u);          // bytes in front of the first 16-B boundary
-    char *const dst = a.text + blk0;
-    if (tid < head) dst[tid] = stage[mis + tid];
-    const uint32_t units = (tot - head) >> 4;
-    const uint4 *const su = reinterpret_cast<const uint4 *>(stage + mis + head);   // 16-B aligned: mis + head is 0 mod 16
-    uint4 *const du = reinterpret_cast<uint4 *>(dst + head);
-    for (uint32_t q = tid; q < units; q += 256u) du[q] = su[q];
-    const uint32_t done = head + (units << 4);
-    if (tid < tot - done) dst[done + tid] = stage[mis + done + tid];
+    stage_flush_256(stage, mis, tot, a.text + blk0);
 }
 
 // ---- `wave --signal`: a row for EVERY window (wave.rs:158-168) ----------------------------------------------------
@@ -383,22 +360,18 @@ __global__ __launch_bounds__(256) void sig_len_kernel(const SigArgs a) {
     const uint32_t tid = threadIdx.x, i = t.w0 + tid;
     uint32_t len = 0;
     if (i < t.n_win) len = sig_row_len(a, a.ctgs[t.ctg], i, a.cnt[t.win_base + i], a.sig[t.win_base + i]);
-    for (int d = 32; d; d >>= 1) len += (uint32_t)__shfl_xor((int)len, d, 64);
-    if ((tid & 63u) == 0u) ws[tid >> 6] = len;
-    __syncthreads();
-    if (tid == 0u) a.blk_len[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    const uint32_t tot = block_sum_256(len, ws);
+    if (tid == 0u) a.blk_len[blockIdx.x] = tot;
 }
 
 __device__ __forceinline__ void sig_row_put(const SigArgs &a, char *p, const RowCtg cg, uint32_t i, uint32_t k, int sg) {
     const uint32_t s = (uint32_t)cg.chr_start + i * a.step, e = s + a.size - 1u;
     for (uint32_t q = 0; q < cg.name_len; ++q) *p++ = a.names[cg.name_off + q];
     *p++ = ':';
-    p += dec_digits(s);
-    put_dec_back(p, s);
+    p = put_dec(p, s);
     if (e != s) {                                   // IntSpan::runlist of a single position is that position
         *p++ = '-';
-        p += dec_digits(e);
-        put_dec_back(p, e);
+        p = put_dec(p, e);
     }
     *p++ = '\t';
     const uint8_t *g = a.gctab + (size_t)k * kGcStride;
@@ -436,15 +409,7 @@ __global__ __launch_bounds__(256) void sig_write_kernel(const SigArgs a) {
     }
     if (!staged) return;
     __syncthreads();
-    const uint32_t head = min(tot, (16u - mis) & 15u);
-    char *const dst = a.text + blk0;
-    if (tid < head) dst[tid] = stage[mis + tid];
-    const uint32_t units = (tot - head) >> 4;
-    const uint4 *const su = reinterpret_cast<const uint4 *>(stage + mis + head);
-    uint4 *const du = reinterpret_cast<uint4 *>(dst + head);
-    for (uint32_t q = tid; q < units; q += 256u) du[q] = su[q];
-    const uint32_t done = head + (units << 4);
-    if (tid < tot - done) dst[done + tid] = stage[mis + done + tid];
+    stage_flush_256(stage, mis, tot, a.text + blk0);
 }
 
 }  // namespace

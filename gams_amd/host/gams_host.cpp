@@ -255,31 +255,33 @@ namespace {
 // kernels (compute stream, behind the upload event) and returns; finish() waits, fetches and
 // formats.  Starting batch k+1 before finishing batch k overlaps its upload with k's kernel and
 // k's host-side merge/formatting with k+1's kernel.
-// fn(i) for i in [0,n) on up to 8 host threads; the first exception is rethrown on the caller
+// fn(i) for i in [0,n) on `threads` host threads, the caller one of them; the first exception is rethrown on the caller
 template <typename F>
-void parallel_for(uint32_t n, F fn) {
-    const unsigned T = std::max(1u, std::min({8u, std::thread::hardware_concurrency(), n / 4u}));
-    if (T <= 1) {
+void parallel_for(uint32_t n, unsigned threads, F fn) {
+    if (threads <= 1) {
         for (uint32_t i = 0; i < n; ++i) fn(i);
         return;
     }
     std::atomic<uint32_t> next{0};
     std::exception_ptr err;
     std::mutex mu;
+    auto work = [&] {
+        try {
+            for (uint32_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i);
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!err) err = std::current_exception();
+            next.store(n);
+        }
+    };
     std::vector<std::thread> pool;
-    for (unsigned t = 0; t < T; ++t)
-        pool.emplace_back([&] {
-            try {
-                for (uint32_t i = next.fetch_add(1); i < n; i = next.fetch_add(1)) fn(i);
-            } catch (...) {
-                std::lock_guard<std::mutex> lk(mu);
-                if (!err) err = std::current_exception();
-                next.store(n);
-            }
-        });
+    for (unsigned t = 1; t < threads; ++t) pool.emplace_back(work);
+    work();
     for (auto &th : pool) th.join();
     if (err) std::rethrow_exception(err);
 }
+// threads for the per-ctg formatting of a wave batch: up to 8, one for every 4 ctgs
+unsigned ctg_threads(uint32_t n) { return std::max(1u, std::min({8u, std::thread::hardware_concurrency(), n / 4u})); }
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -472,7 +474,7 @@ std::vector<std::string> WaveJob::finish() {
             sigs[c].resize(nw ? nw : 1);
             check(h, gams_wave_dense(h, pg.p, c, cnts[c].data(), sigs[c].data()));
         }
-        parallel_for(n, [&](uint32_t c) {
+        parallel_for(n, ctg_threads(n), [&](uint32_t c) {
             const uint32_t nw = gams_wave_ctg_windows(pg.p, c);
             const std::vector<uint32_t> &cnt = cnts[c];
             const std::vector<int8_t> &sig = sigs[c];
@@ -519,7 +521,7 @@ std::vector<std::string> WaveJob::finish() {
         }
         first[n] = q;
     }
-    parallel_for(n, [&](uint32_t c) {                                   // wave.rs:169-211
+    parallel_for(n, ctg_threads(n), [&](uint32_t c) {                                   // wave.rs:169-211
         const uint64_t q = first[c], q1 = first[c + 1];
         // crests and troughs separately (:172-186)
         std::vector<uint32_t> w[2];
@@ -1064,22 +1066,7 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
                 // ~10 GB/s; 313 MB for the 4.1 M rows of a 30-Mb chromosome)
                 const unsigned T = (unsigned)std::max<uint64_t>(
                     1, std::min<uint64_t>({16, std::thread::hardware_concurrency(), (uint64_t)n, tbytes / (4u << 20) + 1}));
-                std::atomic<uint32_t> next{0};
-                std::vector<std::exception_ptr> errs(T);
-                auto work = [&](unsigned t) {
-                    try {
-                        for (uint32_t k = next.fetch_add(1); k < n; k = next.fetch_add(1))
-                            out[todo[b + k]].assign(text + toff[k], text + toff[k + 1]);
-                    } catch (...) {
-                        errs[t] = std::current_exception();
-                    }
-                };
-                std::vector<std::thread> pool;
-                for (unsigned t = 1; t < T; ++t) pool.emplace_back(work, t);
-                work(0);
-                for (auto &th : pool) th.join();
-                for (auto &er : errs)
-                    if (er) std::rethrow_exception(er);
+                parallel_for(n, T, [&](uint32_t k) { out[todo[b + k]].assign(text + toff[k], text + toff[k + 1]); });
                 b = e;
                 continue;
             }
@@ -1104,24 +1091,11 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
                                              a.size, a.max, rx.ix, rg_group.data(), cnt.data(), nrows, nullptr, &nrows));
         // format: ctgs of the batch dealt to a few host threads
         const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({16, std::thread::hardware_concurrency(), (uint64_t)n}));
-        std::atomic<uint32_t> next{0};
-        std::vector<std::exception_ptr> errs(T);
-        auto work = [&](unsigned t) {
-            try {
-                for (uint32_t k = next.fetch_add(1); k < n; k = next.fetch_add(1))
-                    out[todo[b + k]] = sw_format_rows(rows + row_off[k], row_off[k + 1] - row_off[k], ctgs[todo[b + k]],
-                                                      features[todo[b + k]], T > 1 ? 1 : 8, a.actions,
-                                                      do_count ? cnt.data() + row_off[k] : nullptr);
-            } catch (...) {
-                errs[t] = std::current_exception();
-            }
-        };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < T; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-        for (auto &er : errs)
-            if (er) std::rethrow_exception(er);
+        parallel_for(n, T, [&](uint32_t k) {
+            out[todo[b + k]] = sw_format_rows(rows + row_off[k], row_off[k + 1] - row_off[k], ctgs[todo[b + k]],
+                                              features[todo[b + k]], T > 1 ? 1 : 8, a.actions,
+                                              do_count ? cnt.data() + row_off[k] : nullptr);
+        });
         b = e;
     }
     return out;

@@ -12,29 +12,8 @@ namespace {
 thread_local std::string g_err;
 thread_local int g_code = 0;
 
-char *dup(const std::string &s) {
-    char *p = (char *)std::malloc(s.size() + 1);
-    if (p) std::memcpy(p, s.c_str(), s.size() + 1);
-    return p;
-}
-
-template <typename F>
-char *guarded(F &&f) {
-    try {
-        g_err.clear();
-        g_code = 0;
-        return dup(f());
-    } catch (const gams::Error &e) {
-        g_err = e.what();
-        g_code = e.code;
-    } catch (const std::exception &e) {
-        g_err = e.what();
-        g_code = -1;
-    }
-    return nullptr;
-}
-
-char *dup_bytes(const std::string &s, uint64_t *out_len) {
+// malloc'd copy of s with a NUL behind it; *out_len (if asked for) = its length without the NUL
+char *dup(const std::string &s, uint64_t *out_len = nullptr) {
     if (out_len) *out_len = s.size();
     char *p = (char *)std::malloc(s.size() + 1);
     if (p) {
@@ -43,12 +22,15 @@ char *dup_bytes(const std::string &s, uint64_t *out_len) {
     }
     return p;
 }
-template <typename F>
-char *guarded_bytes(uint64_t *out_len, F &&f) {
+
+// f() under the error contract of this file: the thread's last error cleared, then f's result; an exception
+// leaves its message and code behind and `fail` is returned
+template <typename R, typename F>
+R guard(R fail, F &&f) {
     try {
         g_err.clear();
         g_code = 0;
-        return dup_bytes(f(), out_len);
+        return f();
     } catch (const gams::Error &e) {
         g_err = e.what();
         g_code = e.code;
@@ -56,9 +38,17 @@ char *guarded_bytes(uint64_t *out_len, F &&f) {
         g_err = e.what();
         g_code = -1;
     }
-    return nullptr;
+    return fail;
 }
-
+// the string f() makes, as a malloc'd copy (NULL on error)
+template <typename F>
+char *guarded(uint64_t *out_len, F &&f) {
+    return guard((char *)nullptr, [&] { return dup(f(), out_len); });
+}
+template <typename F>
+char *guarded(F &&f) {
+    return guarded(nullptr, f);
+}
 
 std::vector<gams::Ctg> make_ctgs(uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
                                  const int32_t *ends) {
@@ -81,279 +71,37 @@ std::vector<std::string> split_lines(const char *text) {
     while (std::getline(is, ln)) lines.push_back(ln);
     return lines;
 }
-}  // namespace
 
-extern "C" {
-
-const char *gams_host_last_error() { return g_err.c_str(); }
-int gams_host_last_code() { return g_code; }
-void gams_host_free(void *p) { std::free(p); }
-
-// wave.rs:121-215 over n ctgs in one device pass; the per-ctg Strings are concatenated in ctg order
-char *gams_host_wave(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
-                     const int32_t *starts, const int32_t *ends, const uint8_t *const *seqs, int32_t size,
-                     int32_t step, uint32_t lag, float threshold, float influence, float coverage, int is_signal) {
-    return guarded([&] {
-        gams::WaveArgs a;
-        a.size = size;
-        a.step = step;
-        a.lag = lag;
-        a.threshold = threshold;
-        a.influence = influence;
-        a.coverage = coverage;
-        a.signal = is_signal != 0;
-        std::vector<const uint8_t *> sp(seqs, seqs + n);
-        std::string out;
-        for (auto &s : gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a)) out += s;
-        return out;
-    });
+gams::WaveArgs wave_args(int32_t size, int32_t step, uint32_t lag, float threshold, float influence, float coverage,
+                         bool signal) {
+    gams::WaveArgs a;
+    a.size = size;
+    a.step = step;
+    a.lag = lag;
+    a.threshold = threshold;
+    a.influence = influence;
+    a.coverage = coverage;
+    a.signal = signal;
+    return a;
 }
 
-namespace {
-// stages[0..9] = inflate_upload, upload, plan, kernel, peaks, format, total ms, threads, peaks fetched, reserved
-void put_stages(const gams::WaveStages &st, double *stages) {
-    if (!stages) return;
-    stages[0] = st.inflate_upload_ms;
-    stages[1] = st.upload_ms;
-    stages[2] = st.plan_ms;
-    stages[3] = st.kernel_ms;
-    stages[4] = st.peaks_ms;
-    stages[5] = st.format_ms;
-    stages[6] = st.total_ms;
-    stages[7] = (double)st.threads;
-    stages[8] = (double)st.peaks;
-    stages[9] = 0;
-}
-}  // namespace
-
-// gams_host_wave with the stage clock of gams::WaveStages (sync bit 0: the device is drained at every stage
-// boundary; bit 1: `--signal`, a row for every window); *out_len receives the length of the text
-char *gams_host_wave_timed(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
-                           const int32_t *starts, const int32_t *ends, const uint8_t *const *seqs, int32_t size,
-                           int32_t step, uint32_t lag, float threshold, float influence, float coverage, int sync,
-                           double *stages, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
-        gams::WaveArgs a;
-        a.size = size;
-        a.step = step;
-        a.lag = lag;
-        a.threshold = threshold;
-        a.influence = influence;
-        a.coverage = coverage;
-        a.signal = (sync & 2) != 0;
-        gams::WaveStages st;
-        st.sync = (sync & 1) != 0;
-        std::vector<const uint8_t *> sp(seqs, seqs + n);
-        std::vector<std::string> rows = gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a, &st);
-        put_stages(st, stages);
-        size_t total = 0;
-        for (auto &s : rows) total += s.size();
-        std::string out;
-        out.reserve(total);
-        for (auto &s : rows) out += s;
-        return out;
-    });
+// the per-ctg Strings of an operator, concatenated in ctg order
+std::string join(const std::vector<std::string> &rows) {
+    size_t total = 0;
+    for (auto &s : rows) total += s.size();
+    std::string out;
+    out.reserve(total);
+    for (auto &s : rows) out += s;
+    return out;
 }
 
-// the same from the gzip'd `seq:` values (gams::wave_proc_ctgs_gz): blobs[i] / blob_len[i] = value of ctg i
-char *gams_host_wave_gz(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
-                        const int32_t *starts, const int32_t *ends, const uint8_t *const *blobs,
-                        const uint64_t *blob_len, int32_t size, int32_t step, uint32_t lag, float threshold,
-                        float influence, float coverage, uint32_t threads, int sync, double *stages, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
-        gams::WaveArgs a;
-        a.size = size;
-        a.step = step;
-        a.lag = lag;
-        a.threshold = threshold;
-        a.influence = influence;
-        a.coverage = coverage;
-        gams::WaveStages st;
-        st.sync = sync != 0;
-        std::vector<const uint8_t *> bp(blobs, blobs + n);
-        std::vector<uint64_t> bl(blob_len, blob_len + n);
-        std::vector<std::string> rows =
-            gams::wave_proc_ctgs_gz(h, make_ctgs(n, ids, chrs, starts, ends), bp, bl, a, threads, &st);
-        put_stages(st, stages);
-        size_t total = 0;
-        for (auto &s : rows) total += s.size();
-        std::string out;
-        out.reserve(total);
-        for (auto &s : rows) out += s;
-        return out;
-    });
+// the first TSV column of every line
+std::vector<std::string> first_cols(const char *lines) {
+    std::vector<std::string> v;
+    for (const std::string &ln : split_lines(lines)) v.push_back(ln.substr(0, ln.find('\t')));
+    return v;
 }
 
-// decode_gz of n values on `threads` host threads into caller buffers: dst[i] has room for dst_cap[i] bytes,
-// got[i] receives the bytes written.  Returns 0, or -1 with the message in gams_host_last_error().
-int gams_host_decode_gz_many(uint32_t n, const uint8_t *const *blobs, const uint64_t *blob_len, uint8_t *const *dst,
-                             const uint64_t *dst_cap, uint64_t *got, uint32_t threads) {
-    try {
-        g_err.clear();
-        g_code = 0;
-        std::vector<const uint8_t *> bp(blobs, blobs + n);
-        std::vector<uint64_t> bl(blob_len, blob_len + n);
-        std::vector<std::string> out = gams::decode_gz_many(bp, bl, threads);
-        for (uint32_t i = 0; i < n; ++i) {
-            if (out[i].size() > dst_cap[i]) throw gams::Error(GAMS_EINVAL, "decode_gz_many: value " + std::to_string(i) + " does not fit");
-            std::memcpy(dst[i], out[i].data(), out[i].size());
-            got[i] = out[i].size();
-        }
-        return 0;
-    } catch (const gams::Error &e) {
-        g_err = e.what();
-        g_code = e.code;
-    } catch (const std::exception &e) {
-        g_err = e.what();
-        g_code = -1;
-    }
-    return -1;
-}
-
-// the same over several handles (one per device; tests pass two handles of one device)
-char *gams_host_wave_multi(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
-                           const char *const *chrs, const int32_t *starts, const int32_t *ends,
-                           const uint8_t *const *seqs, int32_t size, int32_t step, uint32_t lag, float threshold,
-                           float influence, float coverage, int is_signal, uint64_t batch_bytes) {
-    return guarded([&] {
-        gams::WaveArgs a;
-        a.size = size;
-        a.step = step;
-        a.lag = lag;
-        a.threshold = threshold;
-        a.influence = influence;
-        a.coverage = coverage;
-        a.signal = is_signal != 0;
-        std::vector<gams_gpu_t *> hs(handles, handles + n_handles);
-        std::vector<const uint8_t *> sp(seqs, seqs + n);
-        std::string out;
-        for (auto &s : gams::wave_proc_ctgs_multi(hs, make_ctgs(n, ids, chrs, starts, ends), sp, a, batch_bytes)) out += s;
-        return out;
-    });
-}
-
-// sw.rs:108-194 for one ctg
-char *gams_host_sw(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
-                   const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
-                   const int32_t *fe, int32_t size, int32_t max, int32_t resize) {
-    return guarded([&] {
-        const char *ids[1] = {ctg_id}, *chrs[1] = {chr};
-        gams::Ctg c = make_ctgs(1, ids, chrs, &chr_start, &chr_end)[0];
-        std::vector<gams::Feature> f(nf);
-        for (uint32_t i = 0; i < nf; ++i) f[i] = gams::Feature{feature_ids[i], fs[i], fe[i]};
-        gams::SwArgs a;
-        a.size = size;
-        a.max = max;
-        a.resize = resize;
-        return gams::sw_proc_ctg(h, c, seq, f, a);
-    });
-}
-
-// `gams sw` over several handles.  features: rows "ctg_index\tfeature_id\tstart\tend"
-char *gams_host_sw_multi(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
-                         const char *const *chrs, const int32_t *starts, const int32_t *ends,
-                         const uint8_t *const *seqs, const char *features, int32_t size, int32_t max, int32_t resize) {
-    return guarded([&] {
-        std::vector<std::vector<gams::Feature>> f(n);
-        for (const std::string &ln : split_lines(features)) {
-            std::istringstream is(ln);
-            std::string ci, id, s0, s1;
-            std::getline(is, ci, '\t');
-            std::getline(is, id, '\t');
-            std::getline(is, s0, '\t');
-            std::getline(is, s1, '\t');
-            f.at((size_t)std::stoul(ci)).push_back(gams::Feature{id, std::stoi(s0), std::stoi(s1)});
-        }
-        gams::SwArgs a;
-        a.size = size;
-        a.max = max;
-        a.resize = resize;
-        std::string out;
-        for (auto &s : gams::sw_proc_ctgs_multi(std::vector<gams_gpu_t *>(handles, handles + n_handles),
-                                                make_ctgs(n, ids, chrs, starts, ends),
-                                                std::vector<const uint8_t *>(seqs, seqs + n), f, a))
-            out += s;
-        return out;
-    });
-}
-
-// the same, also reporting the milliseconds of the operator itself (gams::sw_proc_ctgs_multi: upload, kernels, text;
-// without the parsing of `features` in front and the concatenation behind, which belong to this wrapper)
-char *gams_host_sw_multi_timed(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
-                               const char *const *chrs, const int32_t *starts, const int32_t *ends,
-                               const uint8_t *const *seqs, const char *features, int32_t size, int32_t max, int32_t resize,
-                               double *operator_ms, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
-        std::vector<std::vector<gams::Feature>> f(n);
-        for (const std::string &ln : split_lines(features)) {
-            std::istringstream is(ln);
-            std::string ci, id, s0, s1;
-            std::getline(is, ci, '\t');
-            std::getline(is, id, '\t');
-            std::getline(is, s0, '\t');
-            std::getline(is, s1, '\t');
-            f.at((size_t)std::stoul(ci)).push_back(gams::Feature{id, std::stoi(s0), std::stoi(s1)});
-        }
-        gams::SwArgs a;
-        a.size = size;
-        a.max = max;
-        a.resize = resize;
-        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
-        const std::vector<const uint8_t *> sv(seqs, seqs + n);
-        const std::vector<gams_gpu_t *> hv(handles, handles + n_handles);
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<std::string> rows = gams::sw_proc_ctgs_multi(hv, cv, sv, f, a);
-        if (operator_ms) *operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        size_t total = 0;
-        for (auto &s : rows) total += s.size();
-        std::string out;
-        out.reserve(total);
-        for (auto &s : rows) out += s;
-        return out;
-    });
-}
-
-// locate.rs:111-141.  rgs: newline-separated ranges (first TSV column already cut).
-// rg_lines (for --count): newline-separated "ctg_id\trange" rows = the rg: records per ctg.
-static thread_local double g_operator_ms = 0.0;
-
-char *gams_host_locate(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
-                       const int32_t *starts, const int32_t *ends, const char *rgs, int is_count,
-                       const char *rg_lines) {
-    return guarded([&] {
-        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
-        if (is_count) {
-            std::map<std::string, std::vector<gams::Range>> rg_of;
-            for (uint32_t i = 0; i < n; ++i) rg_of[ids[i]];  // build_idx_rg visits every ctg (redis.rs:279-302)
-            for (const std::string &ln : split_lines(rg_lines)) {
-                size_t tab = ln.find('\t');
-                if (tab == std::string::npos) continue;
-                gams::Range r = gams::Range::from_str(ln.substr(tab + 1));
-                if (r.valid) rg_of[ln.substr(0, tab)].push_back(r);
-            }
-            loc.set_rg_index(rg_of);
-        }
-        const std::vector<std::string> lines = split_lines(rgs);
-        const auto t0 = std::chrono::steady_clock::now();
-        std::string out = loc.locate(lines, is_count != 0);
-        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return out;
-    });
-}
-
-// milliseconds the last gams_host_locate / gams_host_anno / gams_host_locate_text / gams_host_anno_text of this
-// thread spent inside the operator itself (Locator::locate, gams::anno: parsing of the range strings, device lookups,
-// row text; the text forms: from the input bytes in host memory to the finished string) -- without this wrapper's
-// splitting of its arguments into lines and, for locate, the build of the ctg / rg index and its name tables, which
-// are the caller's
-double gams_host_last_operator_ms(void) { return g_operator_ms; }
-
-// 1 if the rows of the last gams_host_locate_text / gams_host_anno_text of this thread came from the device, 0 if
-// the device refused the input and the array path made them
-static thread_local int g_operator_device = 0;
-int gams_host_last_operator_device(void) { return g_operator_device; }
-
-namespace {
 std::map<std::string, std::vector<gams::Range>> rg_index_of(uint32_t n, const char *const *ids, const char *rg_lines) {
     std::map<std::string, std::vector<gams::Range>> rg_of;
     for (uint32_t i = 0; i < n; ++i) rg_of[ids[i]];  // build_idx_rg visits every ctg (redis.rs:279-302)
@@ -385,12 +133,7 @@ std::map<std::string, gams::Runlist> runlists_of(const char *runlists) {
     }
     return sets;
 }
-}  // namespace
 
-// sw with an action set (GAMS_SW_GC | GAMS_SW_COUNT, sw.rs:28-32) and, for GAMS_SW_COUNT, the rg: records as
-// "ctg_id\trange" lines (as gams_host_locate takes them; every ctg of the call gets a group, empty or not).  The
-// entries without `actions` above are these with GAMS_SW_GC.
-namespace {
 gams::SwArgs sw_args(int32_t size, int32_t max, int32_t resize, uint32_t actions) {
     gams::SwArgs a;
     a.size = size;
@@ -415,6 +158,138 @@ std::vector<std::vector<gams::Feature>> sw_feature_rows(uint32_t n, const char *
 thread_local double g_sw_index_ms = 0.0;
 }  // namespace
 
+extern "C" {
+
+const char *gams_host_last_error() { return g_err.c_str(); }
+int gams_host_last_code() { return g_code; }
+void gams_host_free(void *p) { std::free(p); }
+
+// wave.rs:121-215 over n ctgs in one device pass; the per-ctg Strings are concatenated in ctg order
+char *gams_host_wave(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                     const int32_t *starts, const int32_t *ends, const uint8_t *const *seqs, int32_t size,
+                     int32_t step, uint32_t lag, float threshold, float influence, float coverage, int is_signal) {
+    return guarded([&] {
+        const gams::WaveArgs a = wave_args(size, step, lag, threshold, influence, coverage, is_signal != 0);
+        std::vector<const uint8_t *> sp(seqs, seqs + n);
+        return join(gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a));
+    });
+}
+
+namespace {
+// stages[0..9] = inflate_upload, upload, plan, kernel, peaks, format, total ms, threads, peaks fetched, reserved
+void put_stages(const gams::WaveStages &st, double *stages) {
+    if (!stages) return;
+    stages[0] = st.inflate_upload_ms;
+    stages[1] = st.upload_ms;
+    stages[2] = st.plan_ms;
+    stages[3] = st.kernel_ms;
+    stages[4] = st.peaks_ms;
+    stages[5] = st.format_ms;
+    stages[6] = st.total_ms;
+    stages[7] = (double)st.threads;
+    stages[8] = (double)st.peaks;
+    stages[9] = 0;
+}
+}  // namespace
+
+// gams_host_wave with the stage clock of gams::WaveStages (sync bit 0: the device is drained at every stage
+// boundary; bit 1: `--signal`, a row for every window); *out_len receives the length of the text
+char *gams_host_wave_timed(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                           const int32_t *starts, const int32_t *ends, const uint8_t *const *seqs, int32_t size,
+                           int32_t step, uint32_t lag, float threshold, float influence, float coverage, int sync,
+                           double *stages, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const gams::WaveArgs a = wave_args(size, step, lag, threshold, influence, coverage, (sync & 2) != 0);
+        gams::WaveStages st;
+        st.sync = (sync & 1) != 0;
+        std::vector<const uint8_t *> sp(seqs, seqs + n);
+        std::vector<std::string> rows = gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a, &st);
+        put_stages(st, stages);
+        return join(rows);
+    });
+}
+
+// the same from the gzip'd `seq:` values (gams::wave_proc_ctgs_gz): blobs[i] / blob_len[i] = value of ctg i
+char *gams_host_wave_gz(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                        const int32_t *starts, const int32_t *ends, const uint8_t *const *blobs,
+                        const uint64_t *blob_len, int32_t size, int32_t step, uint32_t lag, float threshold,
+                        float influence, float coverage, uint32_t threads, int sync, double *stages, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const gams::WaveArgs a = wave_args(size, step, lag, threshold, influence, coverage, false);
+        gams::WaveStages st;
+        st.sync = sync != 0;
+        std::vector<const uint8_t *> bp(blobs, blobs + n);
+        std::vector<uint64_t> bl(blob_len, blob_len + n);
+        std::vector<std::string> rows =
+            gams::wave_proc_ctgs_gz(h, make_ctgs(n, ids, chrs, starts, ends), bp, bl, a, threads, &st);
+        put_stages(st, stages);
+        return join(rows);
+    });
+}
+
+// decode_gz of n values on `threads` host threads into caller buffers: dst[i] has room for dst_cap[i] bytes,
+// got[i] receives the bytes written.  Returns 0, or -1 with the message in gams_host_last_error().
+int gams_host_decode_gz_many(uint32_t n, const uint8_t *const *blobs, const uint64_t *blob_len, uint8_t *const *dst,
+                             const uint64_t *dst_cap, uint64_t *got, uint32_t threads) {
+    return guard(-1, [&] {
+        std::vector<const uint8_t *> bp(blobs, blobs + n);
+        std::vector<uint64_t> bl(blob_len, blob_len + n);
+        std::vector<std::string> out = gams::decode_gz_many(bp, bl, threads);
+        for (uint32_t i = 0; i < n; ++i) {
+            if (out[i].size() > dst_cap[i]) throw gams::Error(GAMS_EINVAL, "decode_gz_many: value " + std::to_string(i) + " does not fit");
+            std::memcpy(dst[i], out[i].data(), out[i].size());
+            got[i] = out[i].size();
+        }
+        return 0;
+    });
+}
+
+// the same over several handles (one per device; tests pass two handles of one device)
+char *gams_host_wave_multi(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                           const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                           const uint8_t *const *seqs, int32_t size, int32_t step, uint32_t lag, float threshold,
+                           float influence, float coverage, int is_signal, uint64_t batch_bytes) {
+    return guarded([&] {
+        const gams::WaveArgs a = wave_args(size, step, lag, threshold, influence, coverage, is_signal != 0);
+        std::vector<gams_gpu_t *> hs(handles, handles + n_handles);
+        std::vector<const uint8_t *> sp(seqs, seqs + n);
+        return join(gams::wave_proc_ctgs_multi(hs, make_ctgs(n, ids, chrs, starts, ends), sp, a, batch_bytes));
+    });
+}
+
+// locate.rs:111-141.  rgs: newline-separated ranges (first TSV column already cut).
+// rg_lines (for --count): newline-separated "ctg_id\trange" rows = the rg: records per ctg.
+static thread_local double g_operator_ms = 0.0;
+
+char *gams_host_locate(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                       const int32_t *starts, const int32_t *ends, const char *rgs, int is_count,
+                       const char *rg_lines) {
+    return guarded([&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        if (is_count) loc.set_rg_index(rg_index_of(n, ids, rg_lines));
+        const std::vector<std::string> lines = split_lines(rgs);
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = loc.locate(lines, is_count != 0);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return out;
+    });
+}
+
+// milliseconds the last gams_host_locate / gams_host_anno / gams_host_locate_text / gams_host_anno_text of this
+// thread spent inside the operator itself (Locator::locate, gams::anno: parsing of the range strings, device lookups,
+// row text; the text forms: from the input bytes in host memory to the finished string) -- without this wrapper's
+// splitting of its arguments into lines and, for locate, the build of the ctg / rg index and its name tables, which
+// are the caller's
+double gams_host_last_operator_ms(void) { return g_operator_ms; }
+
+// 1 if the rows of the last gams_host_locate_text / gams_host_anno_text of this thread came from the device, 0 if
+// the device refused the input and the array path made them
+static thread_local int g_operator_device = 0;
+int gams_host_last_operator_device(void) { return g_operator_device; }
+
+// sw with an action set (GAMS_SW_GC | GAMS_SW_COUNT, sw.rs:28-32) and, for GAMS_SW_COUNT, the rg: records as
+// "ctg_id\trange" lines (as gams_host_locate takes them; every ctg of the call gets a group, empty or not).
+// sw.rs:108-194 for one ctg
 char *gams_host_sw_actions(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
                            const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
                            const int32_t *fe, int32_t size, int32_t max, int32_t resize, uint32_t actions,
@@ -429,30 +304,29 @@ char *gams_host_sw_actions(gams_gpu_t *h, const char *ctg_id, const char *chr, i
     });
 }
 
+// `gams sw` over several handles.  features: rows "ctg_index\tfeature_id\tstart\tend"
 char *gams_host_sw_multi_actions(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
                                  const char *const *chrs, const int32_t *starts, const int32_t *ends,
                                  const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
                                  int32_t resize, uint32_t actions, const char *rg_lines) {
     return guarded([&] {
         const std::map<std::string, std::vector<gams::Range>> rg_of = rg_index_of(n, ids, rg_lines);
-        std::string out;
-        for (auto &s : gams::sw_proc_ctgs_multi(std::vector<gams_gpu_t *>(handles, handles + n_handles),
-                                                make_ctgs(n, ids, chrs, starts, ends),
-                                                std::vector<const uint8_t *>(seqs, seqs + n), sw_feature_rows(n, features),
-                                                sw_args(size, max, resize, actions), &rg_of))
-            out += s;
-        return out;
+        return join(gams::sw_proc_ctgs_multi(std::vector<gams_gpu_t *>(handles, handles + n_handles),
+                                             make_ctgs(n, ids, chrs, starts, ends),
+                                             std::vector<const uint8_t *>(seqs, seqs + n), sw_feature_rows(n, features),
+                                             sw_args(size, max, resize, actions), &rg_of));
     });
 }
 
-// as gams_host_sw_multi_timed; operator_ms includes the build of the rg index, which gams_host_last_sw_index_ms then
-// reports on its own
+// the same, also reporting the milliseconds of the operator itself (gams::sw_proc_ctgs_multi: upload, kernels, text;
+// without the parsing of `features` in front and the concatenation behind, which belong to this wrapper).  operator_ms
+// includes the build of the rg index, which gams_host_last_sw_index_ms then reports on its own
 char *gams_host_sw_multi_actions_timed(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
                                        const char *const *chrs, const int32_t *starts, const int32_t *ends,
                                        const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
                                        int32_t resize, uint32_t actions, const char *rg_lines, double *operator_ms,
                                        uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
+    return guarded(out_len, [&] {
         const std::vector<std::vector<gams::Feature>> f = sw_feature_rows(n, features);
         const std::map<std::string, std::vector<gams::Range>> rg_of = rg_index_of(n, ids, rg_lines);
         const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
@@ -463,24 +337,40 @@ char *gams_host_sw_multi_actions_timed(gams_gpu_t *const *handles, uint32_t n_ha
         std::vector<std::string> rows =
             gams::sw_proc_ctgs_multi(hv, cv, sv, f, sw_args(size, max, resize, actions), &rg_of, &g_sw_index_ms);
         if (operator_ms) *operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        size_t total = 0;
-        for (auto &s : rows) total += s.size();
-        std::string out;
-        out.reserve(total);
-        for (auto &s : rows) out += s;
-        return out;
+        return join(rows);
     });
 }
 
 // ms the last gams_host_sw_multi_actions_timed of this thread spent building the rg index (the longest handle's)
 double gams_host_last_sw_index_ms(void) { return g_sw_index_ms; }
 
+// the three entries without an action set: those above with GAMS_SW_GC and no rg lines (no rg range is read)
+char *gams_host_sw(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
+                   const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
+                   const int32_t *fe, int32_t size, int32_t max, int32_t resize) {
+    return gams_host_sw_actions(h, ctg_id, chr, chr_start, chr_end, seq, nf, feature_ids, fs, fe, size, max, resize,
+                                GAMS_SW_GC, nullptr);
+}
+char *gams_host_sw_multi(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                         const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                         const uint8_t *const *seqs, const char *features, int32_t size, int32_t max, int32_t resize) {
+    return gams_host_sw_multi_actions(handles, n_handles, n, ids, chrs, starts, ends, seqs, features, size, max, resize,
+                                      GAMS_SW_GC, nullptr);
+}
+char *gams_host_sw_multi_timed(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                               const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                               const uint8_t *const *seqs, const char *features, int32_t size, int32_t max, int32_t resize,
+                               double *operator_ms, uint64_t *out_len) {
+    return gams_host_sw_multi_actions_timed(handles, n_handles, n, ids, chrs, starts, ends, seqs, features, size, max,
+                                            resize, GAMS_SW_GC, nullptr, operator_ms, out_len);
+}
+
 // locate -f / --count over the bytes of the input file (bytes, n_bytes: not NUL-terminated); rg_lines as for
 // gams_host_locate.  *out_len receives the text's length.
 char *gams_host_locate_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
                             const int32_t *starts, const int32_t *ends, const char *bytes, uint64_t n_bytes,
                             int is_count, const char *rg_lines, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
+    return guarded(out_len, [&] {
         gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
         if (is_count) loc.set_rg_index(rg_index_of(n, ids, rg_lines));
         loc.text_tables();
@@ -498,7 +388,7 @@ char *gams_host_anno_text(gams_gpu_t *h, uint32_t n, const char *const *ids, con
                           const int32_t *starts, const int32_t *ends, const char *runlists, const char *bytes,
                           uint64_t n_bytes, int header, const char *prefix, uint32_t idx_id, uint32_t idx_range,
                           uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
+    return guarded(out_len, [&] {
         const std::map<std::string, gams::Runlist> sets = runlists_of(runlists);
         const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
         bool dev = false;
@@ -533,10 +423,9 @@ char *gams_host_read_range(gams_gpu_t *h, uint32_t n, const char *const *ids, co
                            const int32_t *starts, const int32_t *ends, const char *lines) {
     return guarded([&] {
         gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
-        std::vector<std::string> first_cols;
-        for (const std::string &ln : split_lines(lines)) first_cols.push_back(ln.substr(0, ln.find('\t')));
+        const std::vector<std::string> cols = first_cols(lines);
         std::string out;
-        for (auto &kv : gams::read_range(loc, first_cols))
+        for (auto &kv : gams::read_range(loc, cols))
             for (const gams::Range &r : kv.second) out += kv.first + "\t" + r.to_string() + "\n";
         return out;
     });
@@ -578,10 +467,9 @@ char *gams_host_loader_records(gams_gpu_t *h, uint32_t n, const char *const *ids
                                const int32_t *starts, const int32_t *ends, const char *lines, const char *tag) {
     return guarded([&] {
         gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
-        std::vector<std::string> first_cols;
-        for (const std::string &ln : split_lines(lines)) first_cols.push_back(ln.substr(0, ln.find('\t')));
+        const std::vector<std::string> cols = first_cols(lines);
         std::string out;
-        for (const gams::Record &r : tag ? gams::feature_records(loc, first_cols, tag) : gams::rg_records(loc, first_cols))
+        for (const gams::Record &r : tag ? gams::feature_records(loc, cols, tag) : gams::rg_records(loc, cols))
             out += r.key + "\t" + r.json + "\n";
         return out;
     });
@@ -592,20 +480,15 @@ char *gams_host_loader_tsv(gams_gpu_t *h, uint32_t n, const char *const *ids, co
                            const int32_t *starts, const int32_t *ends, const char *lines, const char *tag) {
     return guarded([&] {
         gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
-        std::vector<std::string> first_cols;
-        for (const std::string &ln : split_lines(lines)) first_cols.push_back(ln.substr(0, ln.find('\t')));
-        return gams::tsv_records(tag ? gams::feature_records(loc, first_cols, tag) : gams::rg_records(loc, first_cols),
+        const std::vector<std::string> cols = first_cols(lines);
+        return gams::tsv_records(tag ? gams::feature_records(loc, cols, tag) : gams::rg_records(loc, cols),
                                  tag != nullptr);
     });
 }
 
 // gzip framing of seq: values (redis.rs:149-161); *out_len receives the length
 char *gams_host_decode_gz(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
-    return guarded([&] {
-        std::string s = gams::decode_gz(bytes, n);
-        if (out_len) *out_len = s.size();
-        return s;
-    });
+    return guarded(out_len, [&] { return gams::decode_gz(bytes, n); });
 }
 char *gams_host_encode_gz(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
     try {
@@ -643,22 +526,7 @@ char *gams_host_anno(gams_gpu_t *h, uint32_t n, const char *const *ids, const ch
                      const int32_t *starts, const int32_t *ends, const char *runlists, const char *lines,
                      int header, const char *prefix, uint32_t idx_id, uint32_t idx_range) {
     return guarded([&] {
-        std::map<std::string, gams::Runlist> sets;
-        for (const std::string &ln : split_lines(runlists)) {
-            size_t tab = ln.find('\t');
-            if (tab == std::string::npos) continue;
-            gams::Runlist &rl = sets[ln.substr(0, tab)];
-            std::istringstream is(ln.substr(tab + 1));
-            std::string part;
-            while (std::getline(is, part, ',')) {
-                if (part.empty() || part == "-") continue;
-                size_t dash = part.find('-', 1);
-                int32_t lo = std::atoi(part.substr(0, dash).c_str());
-                int32_t hi = dash == std::string::npos ? lo : std::atoi(part.substr(dash + 1).c_str());
-                rl.lo.push_back(lo);
-                rl.hi.push_back(hi);
-            }
-        }
+        const std::map<std::string, gams::Runlist> sets = runlists_of(runlists);
         const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
         const std::vector<std::string> lv = split_lines(lines);
         const auto t0 = std::chrono::steady_clock::now();
@@ -743,7 +611,7 @@ char *gams_host_range_roundtrip(const char *s) {
 // ---- wire formats (gams_wire.cpp): byte strings out, *out_len = their length ------------------------
 char *gams_host_bincode_ctg_bundle(uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
                                    const int32_t *ends, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] { return gams::wire::bincode_ctg_bundle(make_ctgs(n, ids, chrs, starts, ends)); });
+    return guarded(out_len, [&] { return gams::wire::bincode_ctg_bundle(make_ctgs(n, ids, chrs, starts, ends)); });
 }
 // decoded bundle as the ctg.tsv text of `gams tsv` (one line per ctg, key order)
 char *gams_host_bincode_ctg_bundle_decode(const uint8_t *bytes, uint64_t n) {
@@ -752,7 +620,7 @@ char *gams_host_bincode_ctg_bundle_decode(const uint8_t *bytes, uint64_t n) {
 // intervals as parallel arrays; vals: n NUL-terminated strings (NULL = all empty, the idx:rg case)
 char *gams_host_bincode_lapper(uint64_t n, const uint32_t *starts, const uint32_t *stops, const char *const *vals,
                                uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
+    return guarded(out_len, [&] {
         std::vector<gams::wire::LapperIv> ivs(n);
         for (uint64_t i = 0; i < n; ++i) {
             ivs[i].start = starts[i];
@@ -779,14 +647,14 @@ char *gams_host_bincode_lapper_decode(const uint8_t *bytes, uint64_t n) {
 }
 // args: n byte strings (arg_len[i] bytes each)
 char *gams_host_resp_command(uint32_t n, const char *const *args, const uint64_t *arg_len, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
+    return guarded(out_len, [&] {
         std::vector<std::string> a(n);
         for (uint32_t i = 0; i < n; ++i) a[i].assign(args[i], (size_t)arg_len[i]);
         return gams::wire::resp_command(a);
     });
 }
 char *gams_host_resp_scan_values(const char *pattern, uint64_t *out_len) {
-    return guarded_bytes(out_len, [&] {
+    return guarded(out_len, [&] {
         return gams::wire::resp_eval(gams::wire::scan_values_script(), {}, {pattern ? pattern : "", "1000"});
     });
 }
@@ -802,19 +670,10 @@ char *gams_host_resp_parse(const char *bytes, uint64_t n, uint64_t *consumed) {
 
 // idx: blobs (n of them, blob i = blob_len[i] bytes) -> device index, one group per blob; NULL on error
 void *gams_host_index_from_lappers(void *h, uint32_t n, const uint8_t *const *blobs, const uint64_t *blob_len) {
-    try {
-        g_err.clear();
-        g_code = 0;
+    return guard((void *)nullptr, [&]() -> void * {
         std::vector<gams::wire::LapperBlob> dec;
         for (uint32_t i = 0; i < n; ++i) dec.push_back(gams::wire::bincode_lapper_decode(blobs[i], (size_t)blob_len[i]));
         return gams::wire::index_from_lappers(static_cast<gams_gpu_t *>(h), dec);
-    } catch (const gams::Error &e) {
-        g_err = e.what();
-        g_code = e.code;
-    } catch (const std::exception &e) {
-        g_err = e.what();
-        g_code = -1;
-    }
-    return nullptr;
+    });
 }
 }  // extern "C"

@@ -37,7 +37,8 @@ def test_binding_surface_carries_no_lab_bench():
                  "gams_wave_plan_set_taper", "gams_wave_plan_set_tile", "gams_wave_plan_kernel_name",
                  "gams_gpu_timer_start", "gams_gpu_timer_stop", "gams_gpu_last_kernel_ms", "gams_wave_exact_count"):
         assert name in diag and name not in main, name
-    for src in ("api.hip", "wave.hip", "sw.hip", "interval.hip", "gen.hip", "wave_kernels.hpp", "common.hpp"):
+    for src in ("api.hip", "wave.hip", "sw.hip", "interval.hip", "gen.hip", "wave_kernels.hpp", "common.hpp",
+                "text_emit.hpp"):
         text = open(os.path.join(ROOT, "gams_amd", "csrc", src)).read()
         assert "getenv(" not in text and "setenv(" not in text and "putenv(" not in text, src
 
