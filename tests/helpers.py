@@ -120,3 +120,65 @@ def read_runlists(name):
             hi.append(int(b))
         out[chr_id] = (np.array(lo, np.int32), np.array(hi, np.int32))
     return out
+
+
+def synth(n, seed, gc=0.4, lower=0.2, nrate=1e-4):
+    rng = np.random.default_rng(seed)
+    x = np.arange(n)
+    p = gc + 0.06 * np.sin(2 * np.pi * x / 2300) + 0.04 * np.sin(2 * np.pi * x / 97000)
+    is_gc = rng.random(n) < p
+    pick = rng.random(n) < 0.5
+    s = np.where(is_gc, np.where(pick, ord("G"), ord("C")), np.where(pick, ord("A"), ord("T"))).astype(np.uint8)
+    s = np.where(rng.random(n) < lower, s | 0x20, s).astype(np.uint8)
+    s[rng.random(n) < nrate] = ord("N")
+    return s
+
+
+def longest_run(sig):
+    """length of the longest stretch of consecutive nonzero entries"""
+    nz = np.concatenate(([0], (np.asarray(sig) != 0).astype(np.int8), [0]))
+    d = np.diff(nz)
+    starts, ends = np.flatnonzero(d == 1), np.flatnonzero(d == -1)
+    return int((ends - starts).max()) if starts.size else 0
+
+
+def sweep_model(cnt, size, lag, thr, infl, s1, max_sweeps=1000):
+    """The guess-and-iterate sweeps for influence != 1 (gams_amd/csrc/wave_repair.hpp: jac_filter_kernel, then
+    jac_eval_kernel, over every window) in strict float32 and in the kernels' order of operations: filtered[] from the
+    signals (stat.rs:42 inside runs of signalled windows, the data elsewhere), then every window i >= lag against mean / sd
+    of filtered[i-1-lag, i-1) (window `lag`: [0, lag)), both sums left to right; from the influence == 1 answer `s1` until a
+    sweep flips nothing.  -> (flips per sweep, the last one 0; the longest run of signalled windows in any state the
+    filter saw; the final signals).  The iteration of tools/experiments/jacobi_model.py, bit for bit instead of in f64."""
+    f32 = np.float32
+    x = np.asarray(cnt).astype(f32) / f32(size)
+    n = x.size
+    infl, thr, flen = f32(infl), f32(thr), f32(lag)
+    t1 = infl * x                                             # influence * x[i]
+    omi = f32(1.0) - infl
+    i = np.arange(lag, n)
+    a = np.where(i == lag, 0, i - 1 - lag)
+    sig = np.asarray(s1).astype(np.int32).copy()
+    flips, run = [], 0
+    while len(flips) < max_sweeps:
+        run = max(run, longest_run(sig))
+        f = x.copy()
+        for j in np.flatnonzero(sig):                         # left to right: f[j-1] is final when j is reached
+            f[j] = t1[j] + omi * f[j - 1]
+        total = np.zeros(i.size, f32)
+        for c in range(lag):
+            total = total + f[a + c]
+        mean = total / flen
+        sq = np.zeros(i.size, f32)
+        for c in range(lag):
+            d = f[a + c] - mean
+            sq = sq + d * d
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sd = np.sqrt(sq / (flen - f32(1.0)))
+            hit = np.abs(x[i] - mean) > thr * sd
+        new = np.zeros(n, np.int32)
+        new[i] = np.where(hit, np.where(x[i] > mean, 1, -1), 0)
+        flips.append(int(np.count_nonzero(new != sig)))
+        sig = new
+        if flips[-1] == 0:
+            break
+    return flips, run, sig
