@@ -1,6 +1,7 @@
 // api.hip -- handle, timers and HBM-resident ctg sequences of libgams_gpu.
 
 #include "common.hpp"
+#include "gc_plane.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -244,8 +245,13 @@ int gams_seqset_create(gams_gpu_t *h, uint32_t n_ctg, const uint32_t *lengths, g
     // Padding bytes are never counted, but keep them defined (the block may be a recycled one).
     // Queued on the copy stream in front of the uploads; nothing waits for it on the host.
     e = hipMemsetAsync(s->d_seq, 0, s->bytes, h->copy);
+    // the G/C plane: an eighth of the bytes (a few bytes more: the plane copy of a tile moves whole 16-B pieces)
+    if (e == hipSuccess) e = gams_pool_alloc(h, false, s->bytes / 8 + 256, reinterpret_cast<void **>(&s->d_plane), &s->plane_cap);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_plane, 0, s->bytes / 8 + 256, h->copy);
+    s->plane_ok = true;   // all zero, like the bytes
     if (e != hipSuccess) {
         gams_pool_free(h, false, s->d_seq, s->cap);
+        gams_pool_free(h, false, s->d_plane, s->plane_cap);
         delete s;
         return gams_fail(h, GAMS_EHIP, std::string("seqset_create: memset: ") + hipGetErrorString(e));
     }
@@ -286,8 +292,11 @@ int gams_seqset_upload(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, const uint8_
         const int k = h->stage_next;
         h->stage_next = (k + 1) % gams_gpu::kStageSlots;
         GAMS_HIP(h, hipEventSynchronize(h->stage_free[k]));          // the DMA that used this slot is done
-        std::memcpy(h->stage[k], seq + o, n);
+        // the bases and, in the same pass over them, their plane bits (the slot's second part)
+        uint8_t *const pl = h->stage[k] + gams_gpu::kStageBytes;
+        gams_gc_copy_classify(h->stage[k], seq + o, n, pl);
         GAMS_HIP(h, hipMemcpyAsync(s->d_seq + s->off[i] + o, h->stage[k], n, hipMemcpyHostToDevice, h->copy));
+        GAMS_HIP(h, hipMemcpyAsync(s->d_plane + ((s->off[i] + o) >> 3), pl, (n + 7) / 8, hipMemcpyHostToDevice, h->copy));
         GAMS_HIP(h, hipEventRecord(h->stage_free[k], h->copy));
     }
     GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
@@ -334,6 +343,13 @@ int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const
     }
     GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
     GAMS_HIP(h, hipStreamWaitEvent(second, s->uploaded, 0));
+    // staged bytes [x0, x1) of a window are a gap: zero them and their plane bytes (x0 follows a ctg's last base,
+    // whose plane byte is complete -- its bits past the ctg are zero already; x1 is a multiple of 8 or the window's end)
+    auto zero_gap = [](uint8_t *dst, uint8_t *pdst, uint64_t x0, uint64_t x1) {
+        std::memset(dst + x0, 0, x1 - x0);
+        const uint64_t p0 = (x0 + 7) >> 3, p1 = (x1 + 7) >> 3;
+        if (p1 > p0) std::memset(pdst + p0, 0, p1 - p0);
+    };
     auto work = [&](unsigned t) {
         hipStream_t cs = (t & 1u) ? second : h->copy;
         hipError_t e = hipSetDevice(h->device);
@@ -342,22 +358,25 @@ int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const
             e = hipEventSynchronize(h->stage_free[t]);              // the DMA that used this slot is done
             if (e != hipSuccess) break;
             uint8_t *dst = h->stage[t];
+            uint8_t *pdst = dst + gams_gpu::kStageBytes;             // the window's plane: bit of byte lo + x at pdst[x >> 3]
             // first ctg whose bytes reach into the window
             uint32_t i = (uint32_t)(std::upper_bound(s->off.begin(), s->off.end(), lo) - s->off.begin());
             i = i ? i - 1 : 0;
             uint64_t filled = lo;                                       // stage holds [lo, filled)
             for (; i < s->n_ctg && s->off[i] < hi; ++i) {
                 const uint64_t a = std::max(lo, s->off[i]), b = std::min(hi, s->off[i] + s->len[i]);
-                if (a > filled) std::memset(dst + (filled - lo), 0, a - filled);   // alignment gap
+                if (a > filled) zero_gap(dst, pdst, filled - lo, a - lo);           // alignment gap
                 if (b > a) {
-                    std::memcpy(dst + (a - lo), seqs[i] + (a - s->off[i]), b - a);
+                    // (a is a multiple of 8: ctgs and windows start on 256-B / 4-KiB boundaries)
+                    gams_gc_copy_classify(dst + (a - lo), seqs[i] + (a - s->off[i]), b - a, pdst + ((a - lo) >> 3));
                     filled = b;
                 } else if (a > filled) {
                     filled = a;
                 }
             }
-            if (hi > filled) std::memset(dst + (filled - lo), 0, hi - filled);
+            if (hi > filled) zero_gap(dst, pdst, filled - lo, hi - lo);
             e = hipMemcpyAsync(s->d_seq + lo, dst, hi - lo, hipMemcpyHostToDevice, cs);
+            if (e == hipSuccess) e = hipMemcpyAsync(s->d_plane + (lo >> 3), pdst, (hi - lo + 7) / 8, hipMemcpyHostToDevice, cs);
             if (e == hipSuccess) e = hipEventRecord(h->stage_free[t], cs);
         }
         if (e != hipSuccess) {
@@ -378,6 +397,7 @@ int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const
     GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
     s->dirty = true;
     ++s->upload_gen;
+    s->plane_ok = s->have_bytes = true;   // every ctg, bytes and plane
     return GAMS_OK;
 }
 
@@ -391,7 +411,14 @@ int gams_seqset_layout(gams_gpu_t *h, const gams_seqset_t *s, uint64_t *offsets,
 
 int gams_seqset_upload_image(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *image, uint64_t lo, uint64_t hi) {
     if (!h || !s || !image) return gams_fail(h, GAMS_EINVAL, "seqset_upload_image: null argument");
-    if (lo > hi || hi > s->bytes) return gams_fail(h, GAMS_EINVAL, "seqset_upload_image: range outside the seqset");
+    return gams_seqset_upload_ranges(h, s, image, nullptr, lo, hi);
+}
+
+int gams_seqset_upload_ranges(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *image, const uint8_t *plane_image,
+                              uint64_t lo, uint64_t hi) {
+    if (!h || !s || (!image && !plane_image)) return gams_fail(h, GAMS_EINVAL, "seqset_upload_ranges: null argument");
+    if (lo > hi || hi > s->bytes) return gams_fail(h, GAMS_EINVAL, "seqset_upload_ranges: range outside the seqset");
+    if (plane_image && (lo & 7u)) return gams_fail(h, GAMS_EINVAL, "seqset_upload_ranges: lo must be a multiple of 8");
     GAMS_HIP(h, hipSetDevice(h->device));
     if (lo == hi) return GAMS_OK;
     if (s->gcindex) {
@@ -407,7 +434,17 @@ int gams_seqset_upload_image(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *ima
         if (rc != GAMS_OK) return rc;
         s->ordered_epoch = epoch;
     }
-    GAMS_HIP(h, hipMemcpyAsync(s->d_seq + lo, image + lo, hi - lo, hipMemcpyHostToDevice, h->copy));
+    // A pass must never read a plane that does not describe the bytes: bytes that come without their plane
+    // leave it stale, a plane that comes without its bytes leaves a plane-only seqset, until gams_seqset_upload_all
+    // or a range that covers every ctg brings the missing half again
+    const bool whole = lo == 0 && s->n_ctg != 0 && hi >= s->off[s->n_ctg - 1] + s->len[s->n_ctg - 1];
+    if (image)
+        GAMS_HIP(h, hipMemcpyAsync(s->d_seq + lo, image + lo, hi - lo, hipMemcpyHostToDevice, h->copy));
+    if (plane_image)
+        GAMS_HIP(h, hipMemcpyAsync(s->d_plane + (lo >> 3), plane_image + (lo >> 3), ((hi + 7) >> 3) - (lo >> 3),
+                                   hipMemcpyHostToDevice, h->copy));
+    s->have_bytes = image ? (s->have_bytes || whole) : false;
+    s->plane_ok = plane_image ? (s->plane_ok || whole) : false;
     GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
     s->dirty = true;
     ++s->upload_gen;
@@ -425,6 +462,7 @@ void gams_seqset_destroy(gams_gpu_t *h, gams_seqset_t *s) {
     gams_seqset_gcindex_free(s);
     if (s->uploaded) (void)hipEventDestroy(s->uploaded);
     gams_pool_free(h, false, s->d_seq, s->cap);
+    gams_pool_free(h, false, s->d_plane, s->plane_cap);
     delete s;
 }
 
@@ -483,7 +521,7 @@ void gams_pool_free(gams_gpu_t *h, bool pinned, void *p, size_t cap) {
 int gams_stage_ring(gams_gpu_t *h) {
     for (int k = 0; k < gams_gpu::kStageSlots; ++k) {
         if (!h->stage[k]) {
-            GAMS_HIP(h, hipHostMalloc(reinterpret_cast<void **>(&h->stage[k]), gams_gpu::kStageBytes, hipHostMallocDefault));
+            GAMS_HIP(h, hipHostMalloc(reinterpret_cast<void **>(&h->stage[k]), gams_gpu::kStageBytes + gams_gpu::kStagePlane, hipHostMallocDefault));
             GAMS_HIP(h, hipEventCreateWithFlags(&h->stage_free[k], hipEventDisableTiming));
             GAMS_HIP(h, hipEventRecord(h->stage_free[k], h->copy));
         }

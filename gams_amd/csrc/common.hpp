@@ -37,6 +37,8 @@ struct gams_gpu {
     // pinned staging ring of the copy stream: the CPU fills slot k+1 while the DMA drains slot k
     static constexpr int kStageSlots = 4;
     static constexpr size_t kStageBytes = 16u << 20;
+    // (a slot is kStageBytes of bases followed by kStagePlane bytes of their G/C plane)
+    static constexpr size_t kStagePlane = kStageBytes / 8;
     uint8_t *stage[kStageSlots] = {};
     hipEvent_t stage_free[kStageSlots] = {};
     int stage_next = 0;
@@ -117,6 +119,13 @@ struct gams_seqset {
     uint64_t bytes = 0;             // bytes in use (with tail slack for 16-B over-reads)
     size_t cap = 0;                 // size of the pooled block behind d_seq
     uint8_t *d_seq = nullptr;
+    // the 1-bit G/C plane of d_seq: byte o of d_seq is bit o & 7 of d_plane[o >> 3] (ctgs stay on their 256-B
+    // boundaries = 32 plane bytes, gap bits zero, an eighth of the byte slack behind).  plane_ok: it describes the
+    // bytes (every upload so far brought both); have_bytes: d_seq holds the sequence (false: plane-only seqset).
+    // Host state, read when a pass is queued: the streams order the copies themselves (`uploaded`).
+    uint8_t *d_plane = nullptr;
+    size_t plane_cap = 0;
+    bool plane_ok = false, have_bytes = true;
     hipEvent_t uploaded = nullptr;    // recorded on the copy stream after the last upload; kernels wait on it
     bool dirty = false;               // an upload happened since the last wait was queued (compute stream)
     uint64_t upload_gen = 0;          // counts uploads; streams other than `compute` compare it with what they saw

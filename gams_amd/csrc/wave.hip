@@ -194,6 +194,8 @@ struct gams_wave_plan {
     WaveSig *sigtext = nullptr;         // gams_wave_signal_text
     float guard_safety = 1.5f;          // gams_wave_plan_set_guard
     bool guard_exact = false;           // every window through the exact path
+    int input_req = GAMS_WAVE_INPUT_AUTO;   // gams_wave_plan_set_input
+    std::atomic<int> last_input{GAMS_WAVE_INPUT_BYTES};   // what the most recently queued pass read (ways queue from several threads)
 };
 static void wave_launcher_stop(gams_wave_plan_t *p);
 
@@ -1014,8 +1016,22 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
         return GAMS_OK;
     }
     const gams_wave_params_t &q = p->prm;
+    // The tiled fast kernels stream the seqset's G/C plane when it describes the bytes right now (every upload so
+    // far brought both); everything else reads the bytes.  Decided when the pass is queued: a later upload queues
+    // itself behind this pass (gams_order_after_readers) and changes the state for the passes after it.
+    const bool fast_tile = p->fast_w != 0 && !p->direct;
+    const bool plane_fit = fast_tile && p->set->plane_ok && p->set->d_plane != nullptr;
+    if (p->input_req == GAMS_WAVE_INPUT_PLANE && !plane_fit)
+        return gams_fail(h, GAMS_ESTATE, fast_tile ? "wave: the seqset's G/C plane is stale" : "wave: this plan's kernels read the sequence bytes, not the G/C plane");
+    const bool use_plane = plane_fit && (p->input_req != GAMS_WAVE_INPUT_BYTES || !p->set->have_bytes);
+    if (!use_plane && !p->set->have_bytes)
+        return gams_fail(h, GAMS_ESTATE, "wave: the seqset holds the G/C plane only and this plan needs the sequence bytes");
+    if (p->input_req == GAMS_WAVE_INPUT_BYTES && use_plane)
+        return gams_fail(h, GAMS_ESTATE, "wave: the seqset holds the G/C plane only, the bytes were asked for");
+    p->last_input.store(use_plane ? GAMS_WAVE_INPUT_PLANE : GAMS_WAVE_INPUT_BYTES, std::memory_order_relaxed);
     WaveArgs a{};
     a.seq = p->set->d_seq;
+    a.plane = use_plane ? p->set->d_plane : nullptr;
     a.ctgs = p->d_ctgs;
     a.tiles = p->d_tiles;
     a.size = (uint32_t)q.size;
@@ -1165,6 +1181,21 @@ static int wave_wait_last_run(gams_gpu_t *h, gams_wave_plan_t *p) {
         GAMS_HIP(h, hipEventSynchronize(w.done));
     else
         GAMS_HIP(h, hipStreamSynchronize(wave_stream(h, p, wave_read_way_index(p))));
+    return GAMS_OK;
+}
+
+int gams_wave_plan_set_input(gams_gpu_t *h, gams_wave_plan_t *p, int mode) {
+    if (!h || !p) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_input: null argument");
+    if (mode != GAMS_WAVE_INPUT_AUTO && mode != GAMS_WAVE_INPUT_BYTES && mode != GAMS_WAVE_INPUT_PLANE)
+        return gams_fail(h, GAMS_EINVAL, "wave_plan_set_input: mode is 0 (auto), 1 (bytes) or 2 (plane)");
+    p->input_req = mode;
+    return GAMS_OK;
+}
+
+int gams_wave_plan_last_input(gams_gpu_t *h, gams_wave_plan_t *p, int *input) {
+    if (!h || !p || !input) return gams_fail(h, GAMS_EINVAL, "wave_plan_last_input: null argument");
+    if (!p->ran) return gams_fail(h, GAMS_ESTATE, "wave_plan_last_input: no run yet");
+    *input = p->last_input.load(std::memory_order_relaxed);
     return GAMS_OK;
 }
 

@@ -36,6 +36,7 @@ constexpr uint32_t kShardWords = 16;
 
 struct WaveArgs {
     const uint8_t *seq;
+    const uint8_t *plane;   // the seqset's 1-bit G/C plane (base at buffer byte o = bit o & 7 of plane[o >> 3]); NULL: classify `seq`
     const WaveCtgDev *ctgs;
     const WaveTile *tiles;
     uint32_t size, step, lag, tw;
@@ -455,6 +456,9 @@ __device__ __forceinline__ void z_decide(float nf, float kkf, float S1f, float S
 //            plain loads -- they hold / leave the halo -- the rows between with the streaming hint)
 //            -> G/C/g/c flags (v_bitop3, v_add, v_bitop3 per dword; v_dot4 gathers 4 flags) ->
 //            16-bit mask per 16-B chunk -> LDS bit stream BM (1 bit per base).
+//            With a.plane (the seqset's G/C plane, made by the upload): BM is a copy of the tile's plane
+//            bytes, 16 B per lane, and nothing is classified; the tile then starts on a multiple of 128
+//            bases (the alignment of a 16-B plane load) instead of 16, which phase 2 sees through a0 only.
 //   phase 2  window counts, rolling over the bit stream: k(w+1) = k(w) + popc(step bits
 //            entering) - popc(step bits leaving); stored as bytes K[].  Slot idx holds
 //            window vb+idx with vb = w0-lag-1; windows before the ctg start read as 0.
@@ -475,7 +479,11 @@ __device__ __forceinline__ void z_decide(float nf, float kkf, float S1f, float S
 // Interleaved A/B (tools/ab.py) on 384 Mb: W = 12 runs 115 -> 105 us with the cap.
 // SIZE/STEP/LAG != 0 bake the parameters into the instruction stream (constant bit-field offsets in phase 2);
 // LAG == 0 with SIZE/STEP != 0: the lag stays an argument; all 0 = taken from the arguments at run time.
-template <int W, int SIZE, int STEP, int LAG, bool NT, int NTH = 256>
+// PLANE: the body that copies the plane / the one that classifies bytes.  A parameter of this device function only:
+// every kernel holds both bodies and picks one by a.plane (a wave-uniform branch, wave_fast_pick), so the kernels and
+// their names are what they were, and each body is compiled as if alone (sharing one, the 16 loads per lane of the
+// W = 12 step-20 byte form spilled).
+template <int W, int SIZE, int STEP, int LAG, bool NT, int NTH = 256, bool PLANE = false>
 // `tiles` and `seq` are kernel parameters of their own, in front of the argument block: with
 // -mllvm -amdgpu-kernarg-preload-count the command processor delivers the first kernel-argument
 // dwords in SGPRs at wave start, so the tile descriptor's load does not wait for a scalar load of
@@ -519,14 +527,35 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
     const int32_t vb = (int32_t)w0 - (int32_t)lag - 1;       // window held by K slot 0 (may be < 0)
     const uint32_t wh = vb > 0 ? (uint32_t)vb : 0u;
     const uint32_t b0 = wh * step;
-    const uint32_t a0 = b0 & ~15u;
+    const uint32_t a0 = b0 & (PLANE ? ~127u : ~15u);
     const uint32_t b1 = (w1 - 1u) * step + size;
     const uint32_t nchunk = (b1 - a0 + 15u) >> 4;
     const uint4 *src = reinterpret_cast<const uint4 *>(seq_p + cg.seq_off + a0);
 
     wave_stamp(a, 0);
     // ---- phase 1: load + classify ------------------------------------------
-    if constexpr (STEP != 0) {
+    if constexpr (PLANE) {
+        // BM[c] is the mask of bases a0 + 16 c ..: exactly plane bytes 2 c, 2 c + 1 behind (seq_off + a0) / 8, which is
+        // a multiple of 16 (ctgs on 256-B boundaries, a0 on 128 bases).  Up to 7 chunks more than the byte form in
+        // front and a partly used 16-B piece behind: BM has room for max_chunks + 40 chunks, and the plane keeps an
+        // eighth of the bytes' tail slack.  Plain loads: the plane of a batch stays in the caches between passes.
+        const uint4 *const pl = reinterpret_cast<const uint4 *>(a.plane + ((cg.seq_off + a0) >> 3));
+        uint4 *const BV = reinterpret_cast<uint4 *>(smem);
+        if constexpr (STEP != 0) {
+            constexpr uint32_t NCH = (NT_ * W * STEP + SIZE + 30u) / 16u + 1u;   // as below
+            constexpr uint32_t NV = (NCH + 7u + 7u) / 8u;                        // 16-B pieces of 8 chunks
+            constexpr uint32_t NLV = (NV + NT_ - 1u) / NT_;                      // (1 for the headline tile: 242 pieces)
+            uint4 v[NLV];
+            // unconditional, clamped like the byte form's last row (lanes past the end copy the last piece again)
+#pragma unroll
+            for (uint32_t k = 0; k < NLV; ++k) v[k] = pl[min(tid + NT_ * k, NV - 1u)];
+#pragma unroll
+            for (uint32_t k = 0; k < NLV; ++k) BV[min(tid + NT_ * k, NV - 1u)] = v[k];
+        } else {
+            const uint32_t nv = (nchunk + 7u) >> 3;
+            for (uint32_t c = tid; c < nv; c += NT_) BV[c] = pl[c];
+        }
+    } else if constexpr (STEP != 0) {
         // Baked parameters: the tile never has more than NCH chunks, so every thread issues
         // all of its NLD loads back to back with no bounds logic (the bytes past the tile
         // are the next tile's or the seqset's tail slack), classifies, and stores.
@@ -1019,11 +1048,20 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
     wave_stamp(a, 6);
 }
 
+// the tile from the seqset's G/C plane when the arguments carry one, from the bytes otherwise
+template <int W, int SIZE, int STEP, int LAG, bool NT, int NTH = 256>
+__device__ __forceinline__ void wave_fast_pick(const WaveTile tl, const uint8_t *const seq_p, const WaveArgs &a) {
+    if (a.plane != nullptr)
+        wave_fast_tile<W, SIZE, STEP, LAG, NT, NTH, true>(tl, seq_p, a);
+    else
+        wave_fast_tile<W, SIZE, STEP, LAG, NT, NTH, false>(tl, seq_p, a);
+}
+
 template <int W, int SIZE, int STEP, int LAG, bool NT, int NTH = 256>
 __global__ __launch_bounds__(NTH, 8) void wave_fast_kernel(const WaveTile *const tiles_p, const uint8_t *const seq_p,
                                                            const WaveArgs a) {
     const WaveTile tl = tiles_p[blockIdx.x];         // issued before anything waits for the argument block
-    wave_fast_tile<W, SIZE, STEP, LAG, NT, NTH>(tl, seq_p, a);
+    wave_fast_pick<W, SIZE, STEP, LAG, NT, NTH>(tl, seq_p, a);
 }
 
 // Tapered launch (baked parameters): the tile table ends in tiles of 8 and then 4 windows per thread
@@ -1036,11 +1074,11 @@ __global__ __launch_bounds__(256, 8) void wave_fast_taper_kernel(const WaveTile 
                                                                  const uint8_t *const seq_p, const WaveArgs a) {
     const WaveTile tl = tiles_p[blockIdx.x];
     if (tl.pad == 12u)
-        wave_fast_tile<12, SIZE, STEP, LAG, NT>(tl, seq_p, a);
+        wave_fast_pick<12, SIZE, STEP, LAG, NT>(tl, seq_p, a);
     else if (tl.pad == 8u)
-        wave_fast_tile<8, SIZE, STEP, LAG, NT>(tl, seq_p, a);
+        wave_fast_pick<8, SIZE, STEP, LAG, NT>(tl, seq_p, a);
     else
-        wave_fast_tile<4, SIZE, STEP, LAG, NT>(tl, seq_p, a);
+        wave_fast_pick<4, SIZE, STEP, LAG, NT>(tl, seq_p, a);
 }
 
 // ---- parameters whose halo does not fit a tile (large step or lag): no tiling ---------------

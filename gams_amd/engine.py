@@ -98,6 +98,24 @@ class SeqSet:
             raise ValueError("SeqSet.upload: length differs from the ctg's slot")
         self.eng.check(self.eng.lib.gams_seqset_upload(self.eng.h, self.p, i, a.ctypes.data))
 
+    def layout(self):
+        """-> (byte offset of every ctg in the device buffer, bytes in use): gams_seqset_layout"""
+        off = np.zeros(max(self.lengths.size, 1), np.uint64)
+        nb = C.c_uint64()
+        self.eng.check(self.eng.lib.gams_seqset_layout(self.eng.h, self.p, off.ctypes.data, C.byref(nb)))
+        return off[:self.lengths.size], int(nb.value)
+
+    def upload_image(self, image, lo, hi):
+        """bytes [lo, hi) of a host image of the device buffer (keep `image` alive until the engine has synced)"""
+        self.eng.check(self.eng.lib.gams_seqset_upload_image(self.eng.h, self.p, image.ctypes.data, lo, hi))
+
+    def upload_ranges(self, image, plane, lo, hi):
+        """bytes [lo, hi) of `image` and / or their bits of `plane` (a host image of the G/C plane); either may be None.
+        image None leaves a plane-only seqset (gams_seqset_upload_ranges)"""
+        self.eng.check(self.eng.lib.gams_seqset_upload_ranges(self.eng.h, self.p,
+                                                              image.ctypes.data if image is not None else None,
+                                                              plane.ctypes.data if plane is not None else None, lo, hi))
+
     def close(self):
         if getattr(self, "p", None):
             self.eng.lib.gams_seqset_destroy(self.eng.h, self.p)
@@ -283,6 +301,16 @@ class WavePlan:
         buf = C.create_string_buffer(160)
         self.eng.check(self.eng.lib.gams_wave_plan_kernel_name(self.eng.h, self.p, buf, len(buf)))
         return buf.value.decode()
+
+    def set_input(self, mode):
+        """what the tiled fast kernels read: _lib.WAVE_INPUT_AUTO (the G/C plane when valid) / _BYTES / _PLANE"""
+        self.eng.check(self.eng.lib.gams_wave_plan_set_input(self.eng.h, self.p, mode))
+
+    def last_input(self):
+        """the input the most recently queued pass took: _lib.WAVE_INPUT_BYTES or _lib.WAVE_INPUT_PLANE"""
+        v = C.c_int()
+        self.eng.check(self.eng.lib.gams_wave_plan_last_input(self.eng.h, self.p, C.byref(v)))
+        return int(v.value)
 
     def select(self, age):
         """point peaks()/dense()/exact_count() at the run `age` runs before the most recent one"""

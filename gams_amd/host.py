@@ -168,7 +168,7 @@ def wave(eng, ctgs, size=100, step=10, lag=100, threshold=3.0, influence=1.0, co
 
 
 STAGE_NAMES = ("inflate_upload_ms", "upload_ms", "plan_ms", "kernel_ms", "peaks_ms", "format_ms", "total_ms",
-               "inflate_threads", "peaks")
+               "inflate_threads", "peaks", "plane_input")   # plane_input: 1 if the pass read the seqset's 1-bit G/C plane
 
 
 def _take_bytes(p, n):
@@ -184,6 +184,7 @@ def _stage_dict(st):
     d = {k: float(v) for k, v in zip(STAGE_NAMES, st)}
     d["inflate_threads"] = int(d["inflate_threads"])
     d["peaks"] = int(d["peaks"])
+    d["plane_input"] = int(d["plane_input"])
     return d
 
 
@@ -327,7 +328,8 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 
 def last_operator_device():
-    """1 if the last locate_text / anno_text of this thread made its rows on the device, 0 if it fell back"""
+    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text of this thread made its rows on the device,
+    0 if it fell back to the host"""
     return int(load().gams_host_last_operator_device())
 
 

@@ -1,5 +1,6 @@
 // gams_host.cpp -- see gams_host.hpp.  Citations are file:line under the reference.
 #include "gams_host.hpp"
+#include "../../include/gams_gpu_diag.h"   // the stage clock reports which input a pass read
 #include "../csrc/text_fmt.hpp"
 
 #include <algorithm>
@@ -294,18 +295,36 @@ struct WaveJob {
     SeqSetGuard sg;
     PlanGuard pg;
     uint8_t *image = nullptr;      // start_gz: page-locked image of the seqset the workers inflate into
+    uint8_t *plane = nullptr;      // page-locked image of the seqset's G/C plane the workers classify into (plane-only upload)
+    uint64_t image_end = 0;        // end of the last ctg in the device layout
+    const std::vector<const uint8_t *> *seqs_held = nullptr;   // start(): the caller's buffers, should the bytes be wanted after all
     WaveStages *st = nullptr;      // optional stage clock (wave_proc_ctgs*, see gams_host.hpp)
     double t_mark = 0;
     WaveJob(gams_gpu_t *h_, std::vector<Ctg> c, const WaveArgs &a_) : h(h_), ctgs(std::move(c)), a(a_), sg{h_}, pg{h_} {}
     ~WaveJob() {
-        if (image) {
-            (void)gams_gpu_sync(h);            // a DMA may still be reading it
-            gams_gpu_host_free(h, image);
-        }
+        // a DMA may still be reading them -- unless finish() has fetched the pass's results: the pass waited for its uploads
+        if ((image || plane) && !consumed) (void)gams_gpu_sync(h);
+        if (image) gams_gpu_host_free(h, image);
+        if (plane) gams_gpu_host_free(h, plane);
     }
+    // Parameters the library runs through its tiled fast kernels (wave.hip: wave_build_geometry), which read the 1-bit
+    // G/C plane: the upload then sends the plane alone, an eighth of the bytes.  A guess that errs is harmless: a plan
+    // that needs the bytes refuses a plane-only seqset (GAMS_ESTATE) and plan_and_run brings them.
+    bool plane_params() const {
+        return a.size >= 1 && a.size <= 255 && a.step >= 1 && a.step <= 32 && a.lag >= 2 &&
+               (uint64_t)a.lag * (uint64_t)a.size <= 65535 && (uint64_t)a.lag * (uint64_t)a.size * (uint64_t)a.size < (1ull << 24) &&
+               (uint64_t)(a.lag + 1) * (uint64_t)a.step + (uint64_t)a.size + 32 + 1024ull * (uint64_t)a.step <= 65520;
+    }
+    void bring_bytes();
     void start(const std::vector<const uint8_t *> &seqs);
     void start_gz(const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len, unsigned threads);
-    std::vector<std::string> finish();
+    std::vector<std::string> finish() {
+        std::vector<std::string> out = finish_rows();
+        consumed = true;
+        return out;
+    }
+    std::vector<std::string> finish_rows();
+    bool consumed = false;         // the pass has finished (its results were read), and with it every DMA out of image / plane
     // stage clock: with st->sync the device is drained first, so the interval belongs to the stage just queued
     void mark(double WaveStages::*slot) {
         if (!st) return;
@@ -338,9 +357,28 @@ void WaveJob::plan_and_run() {
             check(h, rc);
     }
     mark(&WaveStages::plan_ms);
-    check(h, gams_wave_run(h, pg.p));
+    {
+        int rc = gams_wave_run(h, pg.p);
+        if (rc == GAMS_ESTATE && plane) {      // the plan reads bytes: today's path
+            bring_bytes();
+            rc = gams_wave_run(h, pg.p);
+        }
+        check(h, rc);
+    }
+    if (st) {
+        int input = GAMS_WAVE_INPUT_BYTES;
+        if (gams_wave_plan_last_input(h, pg.p, &input) == GAMS_OK) st->plane_input = input == GAMS_WAVE_INPUT_PLANE;
+    }
     if (device_rows) check(h, gams_wave_rows_begin(h, pg.p));   // packing, merging, formatting and the copy queue behind the pass
     mark(&WaveStages::kernel_ms);
+}
+
+// the bytes of a plane-only seqset, for a plan that turned out to need them
+void WaveJob::bring_bytes() {
+    if (seqs_held)
+        check(h, gams_seqset_upload_all(h, sg.s, seqs_held->data()));
+    else
+        check(h, gams_seqset_upload_ranges(h, sg.s, image, plane, 0, image_end));
 }
 
 void WaveJob::start(const std::vector<const uint8_t *> &seqs) {
@@ -350,9 +388,73 @@ void WaveJob::start(const std::vector<const uint8_t *> &seqs) {
     std::vector<uint32_t> lens(n);
     for (uint32_t c = 0; c < n; ++c) lens[c] = (uint32_t)(ctgs[c].chr_end - ctgs[c].chr_start + 1);
     check(h, gams_seqset_create(h, n, lens.data(), &sg.s));
-    check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
+    if (!plane_params()) {
+        check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
+        mark(&WaveStages::upload_ms);
+        plan_and_run();
+        return;
+    }
+    // Plane-only upload: the workers classify the caller's buffers straight into a page-locked image of the plane
+    // (no copy of the bases is made), pieces of at most 4 Mb so that a few long ctgs still spread over all of them;
+    // the calling thread follows and hands every finished stretch of >= 1 MiB to the DMA engine.
+    seqs_held = &seqs;
+    std::vector<uint64_t> off(n);
+    uint64_t bytes = 0;
+    check(h, gams_seqset_layout(h, sg.s, off.data(), &bytes));
+    image_end = off[n - 1] + lens[n - 1];
+    void *blk = nullptr;
+    check(h, gams_gpu_host_alloc(h, bytes / 8 + 8, &blk));
+    plane = static_cast<uint8_t *>(blk);
+    struct Piece {
+        uint32_t ctg;
+        uint64_t lo, hi;       // bases [lo, hi) of the ctg; lo a multiple of 8
+        uint64_t stop;         // device-layout byte up to which the plane is complete once this piece is (gap included)
+    };
+    constexpr uint64_t kPieceBases = 4ull << 20;
+    std::vector<Piece> pieces;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint64_t next = i + 1 < n ? off[i + 1] : ((image_end + 7) & ~7ull);
+        uint64_t lo = 0;
+        do {
+            const uint64_t hi = std::min<uint64_t>(lens[i], lo + kPieceBases);
+            pieces.push_back(Piece{i, lo, hi, hi == lens[i] ? next : off[i] + hi});
+            lo = hi;
+        } while (lo < lens[i]);
+    }
+    const uint32_t np = (uint32_t)pieces.size();
+    const unsigned T = std::max(1u, std::min(std::min(16u, std::max(1u, std::thread::hardware_concurrency())), np));
+    std::vector<std::atomic<uint8_t>> done(np);
+    for (auto &d : done) d.store(0, std::memory_order_relaxed);
+    std::atomic<uint32_t> next_piece{0};
+    auto work = [&] {
+        for (uint32_t k = next_piece.fetch_add(1); k < np; k = next_piece.fetch_add(1)) {
+            const Piece &pc = pieces[k];
+            uint8_t *dst = plane + ((off[pc.ctg] + pc.lo) >> 3);
+            if (pc.hi > pc.lo) (void)gams_gc_plane(seqs[pc.ctg] + pc.lo, pc.hi - pc.lo, dst);
+            // the alignment gap behind the ctg's last piece: bits zero
+            const uint64_t filled = (off[pc.ctg] + pc.hi + 7) >> 3, want = (pc.stop + 7) >> 3;
+            if (want > filled) std::memset(plane + filled, 0, want - filled);
+            done[k].store(1, std::memory_order_release);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < T; ++t) pool.emplace_back(work);
+    constexpr uint64_t kStretch = 8ull << 20;      // bases: 1 MiB of plane
+    uint64_t lo = 0;
+    int rc = GAMS_OK;
+    for (uint32_t k = 0; k < np && rc == GAMS_OK; ++k) {
+        while (!done[k].load(std::memory_order_acquire)) std::this_thread::yield();
+        const uint64_t hi = k + 1 == np ? image_end : pieces[k].stop;
+        if (hi - lo >= kStretch || k + 1 == np) {
+            rc = gams_seqset_upload_ranges(h, sg.s, nullptr, plane, lo, hi);
+            lo = hi & ~7ull;
+        }
+    }
+    for (auto &th : pool) th.join();
+    check(h, rc);
     mark(&WaveStages::upload_ms);
     plan_and_run();
+    seqs_held = nullptr;       // the caller's vector is only promised for the length of this call
 }
 
 // The `seq:` values as the store holds them (gzip members, redis.rs:149-161): `threads` workers take the
@@ -374,6 +476,15 @@ void WaveJob::start_gz(const std::vector<const uint8_t *> &blobs, const std::vec
     void *blk = nullptr;
     check(h, gams_gpu_host_alloc(h, bytes, &blk));
     image = static_cast<uint8_t *>(blk);
+    image_end = off[n - 1] + lens[n - 1];
+    // parameters of the tiled fast kernels: every worker also classifies its ctg while the bases are in its cache, and
+    // the plane goes to the device INSTEAD of the bytes (an eighth of the DMA; the image stays, should a plan want it)
+    const bool send_plane = plane_params();
+    if (send_plane) {
+        void *pblk = nullptr;
+        check(h, gams_gpu_host_alloc(h, bytes / 8 + 8, &pblk));
+        plane = static_cast<uint8_t *>(pblk);
+    }
     const unsigned T = std::max(1u, std::min(threads ? threads : 16u, n));
     if (st) st->threads = T;
     std::vector<std::atomic<uint8_t>> done(n);
@@ -392,6 +503,11 @@ void WaveJob::start_gz(const std::vector<const uint8_t *> &blobs, const std::vec
                 // the alignment gap behind the ctg (never counted; kept defined)
                 const uint64_t end = off[i] + lens[i], stop = i + 1 < n ? off[i + 1] : end;
                 if (stop > end) std::memset(image + end, 0, stop - end);
+                if (send_plane) {
+                    (void)gams_gc_plane(image + off[i], lens[i], plane + (off[i] >> 3));
+                    const uint64_t filled = (end + 7) >> 3, want = (stop + 7) >> 3;
+                    if (want > filled) std::memset(plane + filled, 0, want - filled);
+                }
                 done[i].store(1, std::memory_order_release);
             }
         } catch (...) {
@@ -411,7 +527,8 @@ void WaveJob::start_gz(const std::vector<const uint8_t *> &blobs, const std::vec
         if (failed.load()) break;
         const uint64_t hi = i + 1 < n ? off[i + 1] : off[i] + lens[i];
         if (hi - lo >= kPiece || i + 1 == n) {
-            rc = gams_seqset_upload_image(h, sg.s, image, lo, hi);
+            rc = send_plane ? gams_seqset_upload_ranges(h, sg.s, nullptr, plane, lo, hi)
+                            : gams_seqset_upload_image(h, sg.s, image, lo, hi);
             lo = hi;
         }
     }
@@ -422,7 +539,7 @@ void WaveJob::start_gz(const std::vector<const uint8_t *> &blobs, const std::vec
     plan_and_run();
 }
 
-std::vector<std::string> WaveJob::finish() {
+std::vector<std::string> WaveJob::finish_rows() {
     const uint32_t n = (uint32_t)ctgs.size();
     std::vector<std::string> out(n);
     if (n == 0) return out;
@@ -441,6 +558,7 @@ std::vector<std::string> WaveJob::finish() {
             const uint64_t *off = nullptr;
             const int rc = gams_wave_signal_text(h, pg.p, chr.data(), cst.data(), &text, &bytes, &off);
             if (rc == GAMS_OK) {
+                if (st) st->device_text = true;
                 mark(&WaveStages::peaks_ms);
                 const unsigned T = (unsigned)std::max<uint64_t>(
                     1, std::min<uint64_t>({16, std::thread::hardware_concurrency(), (uint64_t)n, bytes / (4u << 20) + 1}));
@@ -499,6 +617,7 @@ std::vector<std::string> WaveJob::finish() {
         uint64_t bytes = 0;
         const uint64_t *off = nullptr;
         check(h, gams_wave_rows_end(h, pg.p, &text, &bytes, &off));
+        if (st) st->device_text = true;
         mark(&WaveStages::peaks_ms);
         for (uint32_t c = 0; c < n; ++c) out[c].assign(text + off[c], text + off[c + 1]);
         if (st) st->peaks = bytes;          // (text bytes fetched: the peak records stay on the device)

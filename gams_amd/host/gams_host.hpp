@@ -77,12 +77,16 @@ struct WaveStages {
     bool sync = false;
     unsigned threads = 0;          // inflate workers used (gz form)
     uint64_t peaks = 0;            // signalled windows fetched
+    bool plane_input = false;      // the pass read the seqset's 1-bit G/C plane, not its bytes (gams_wave_plan_last_input)
+    bool device_text = false;      // the rows came as text from the device (gams_wave_rows_* / gams_wave_signal_text)
     double inflate_upload_ms = 0;  // gz form: seq: values -> bases in a page-locked image -> HBM (overlapped)
     double upload_ms = 0;          // buffer form: host buffers -> HBM (gams_seqset_upload_all)
     double plan_ms = 0, kernel_ms = 0, peaks_ms = 0, format_ms = 0, total_ms = 0;
 };
 
-// wave.rs:121-215 for a batch of ctgs in ONE device pass; returns one String per ctg
+// wave.rs:121-215 for a batch of ctgs in ONE device pass; returns one String per ctg.  Parameters of the library's
+// tiled fast kernels (every BASELINE configuration): the workers classify the buffers into the 1-bit G/C plane and
+// only the plane is uploaded; a plan that needs the bytes after all gets them (gams_seqset_upload_all), as before.
 std::vector<std::string> wave_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs,
                                         const std::vector<const uint8_t *> &seqs, const WaveArgs &a,
                                         WaveStages *stages = nullptr);
@@ -90,7 +94,9 @@ std::vector<std::string> wave_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &c
 // blobs[i] / blob_len[i] = the value of ctgs[i], which must inflate to exactly ctgs[i].length bases.
 // `threads` workers inflate one ctg at a time each (the reference gunzips inside its --parallel workers,
 // wave.rs:288-299 -> redis.rs:142-161) straight into a page-locked image of the device buffer, and the
-// finished stretches go to the DMA engine while the rest still inflates.  threads == 0: 16.
+// finished stretches go to the DMA engine while the rest still inflates.  threads == 0: 16.  With parameters of
+// the tiled fast kernels each worker also classifies the ctg it has just inflated, and the stretches that go to
+// the device are the G/C plane's, not the bytes'.
 std::vector<std::string> wave_proc_ctgs_gz(gams_gpu_t *h, const std::vector<Ctg> &ctgs,
                                            const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len,
                                            const WaveArgs &a, unsigned threads = 0, WaveStages *stages = nullptr);

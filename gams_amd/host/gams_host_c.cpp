@@ -158,6 +158,10 @@ std::vector<std::vector<gams::Feature>> sw_feature_rows(uint32_t n, const char *
 thread_local double g_sw_index_ms = 0.0;
 }  // namespace
 
+// 1 if the rows of the last gams_host_wave* / gams_host_locate_text / gams_host_anno_text of this thread came as text
+// from the device, 0 if the device refused the input and the host made them
+static thread_local int g_operator_device = 0;
+
 extern "C" {
 
 const char *gams_host_last_error() { return g_err.c_str(); }
@@ -171,12 +175,16 @@ char *gams_host_wave(gams_gpu_t *h, uint32_t n, const char *const *ids, const ch
     return guarded([&] {
         const gams::WaveArgs a = wave_args(size, step, lag, threshold, influence, coverage, is_signal != 0);
         std::vector<const uint8_t *> sp(seqs, seqs + n);
-        return join(gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a));
+        gams::WaveStages st;
+        std::vector<std::string> rows = gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a, &st);
+        g_operator_device = st.device_text ? 1 : 0;
+        return join(rows);
     });
 }
 
 namespace {
-// stages[0..9] = inflate_upload, upload, plan, kernel, peaks, format, total ms, threads, peaks fetched, reserved
+// stages[0..9] = inflate_upload, upload, plan, kernel, peaks, format, total ms, threads, peaks fetched, 1 if the pass
+// read the G/C plane
 void put_stages(const gams::WaveStages &st, double *stages) {
     if (!stages) return;
     stages[0] = st.inflate_upload_ms;
@@ -188,7 +196,7 @@ void put_stages(const gams::WaveStages &st, double *stages) {
     stages[6] = st.total_ms;
     stages[7] = (double)st.threads;
     stages[8] = (double)st.peaks;
-    stages[9] = 0;
+    stages[9] = st.plane_input ? 1.0 : 0.0;
 }
 }  // namespace
 
@@ -204,6 +212,7 @@ char *gams_host_wave_timed(gams_gpu_t *h, uint32_t n, const char *const *ids, co
         st.sync = (sync & 1) != 0;
         std::vector<const uint8_t *> sp(seqs, seqs + n);
         std::vector<std::string> rows = gams::wave_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends), sp, a, &st);
+        g_operator_device = st.device_text ? 1 : 0;
         put_stages(st, stages);
         return join(rows);
     });
@@ -222,6 +231,7 @@ char *gams_host_wave_gz(gams_gpu_t *h, uint32_t n, const char *const *ids, const
         std::vector<uint64_t> bl(blob_len, blob_len + n);
         std::vector<std::string> rows =
             gams::wave_proc_ctgs_gz(h, make_ctgs(n, ids, chrs, starts, ends), bp, bl, a, threads, &st);
+        g_operator_device = st.device_text ? 1 : 0;
         put_stages(st, stages);
         return join(rows);
     });
@@ -282,9 +292,6 @@ char *gams_host_locate(gams_gpu_t *h, uint32_t n, const char *const *ids, const 
 // are the caller's
 double gams_host_last_operator_ms(void) { return g_operator_ms; }
 
-// 1 if the rows of the last gams_host_locate_text / gams_host_anno_text of this thread came from the device, 0 if
-// the device refused the input and the array path made them
-static thread_local int g_operator_device = 0;
 int gams_host_last_operator_device(void) { return g_operator_device; }
 
 // sw with an action set (GAMS_SW_GC | GAMS_SW_COUNT, sw.rs:28-32) and, for GAMS_SW_COUNT, the rg: records as

@@ -108,6 +108,22 @@ int gams_seqset_layout(gams_gpu_t *h, const gams_seqset_t *s, uint64_t *offsets,
  * (gams_gpu_host_alloc) go at the rate of the link; pageable ones work but stage through the driver.
  * Bytes between ctgs (alignment gaps) are never counted: they may hold anything. */
 int gams_seqset_upload_image(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *image, uint64_t lo, uint64_t hi);
+/* The 1-bit G/C plane of n bases: bit i & 7 of plane[i >> 3] says (seq[i] & 0xDB) == 0x43, i.e. base i is one
+ * of C, G, c, g; ceil(n / 8) bytes are written, bits past n are zero.  Host code, no device involved.  Next to
+ * its bytes a seqset keeps this plane (the same offsets divided by 8): gams_seqset_upload and
+ * gams_seqset_upload_all produce it while they stage the bytes, and `wave` passes of the tiled fast kernels
+ * stream it instead of the bytes.  An upload that brings bytes without their plane (gams_seqset_upload_image)
+ * marks the plane stale, and passes read the bytes again until gams_seqset_upload_all has renewed it. */
+int gams_gc_plane(const uint8_t *seq, uint64_t n, uint8_t *plane);
+/* gams_seqset_upload_image for a host that also, or only, holds the plane: bytes [lo, hi) of `image` and / or
+ * plane bytes [lo / 8, ceil(hi / 8)) of `plane_image` (a host image of the plane: byte o of the device buffer
+ * is bit o & 7 of plane_image[o >> 3], bits of alignment gaps zero) go to the device; lo must be a multiple of
+ * 8, either pointer may be NULL, not both.  image == NULL makes the seqset PLANE-ONLY: `wave` answers through
+ * the tiled fast kernels, and whatever needs the bytes (gams_gpu_sw*, gams_gpu_range_gc*, wave parameters
+ * outside the fast kernels) returns GAMS_ESTATE until gams_seqset_upload_all has brought them.
+ * plane_image == NULL is gams_seqset_upload_image. */
+int gams_seqset_upload_ranges(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *image, const uint8_t *plane_image,
+                              uint64_t lo, uint64_t hi);
 void gams_seqset_destroy(gams_gpu_t *h, gams_seqset_t *s);
 
 /* ---- wave (GC windows + smoothed z-score) ------------------------------- */

@@ -71,6 +71,23 @@ int gams_wave_stamps(gams_gpu_t *h, gams_wave_plan_t *p, double *mean_cycles /* 
 /* the raw stamp words: 16 per workgroup (tile), see wave_stamp() in gams_amd/csrc/wave.hip */
 int gams_wave_stamps_raw(gams_gpu_t *h, gams_wave_plan_t *p, uint64_t *out, uint64_t n_words);
 
+/* What the tiled fast kernels of a plan read: the seqset's 1-bit G/C plane when it is valid at queueing time
+ * (GAMS_WAVE_INPUT_AUTO, the default), always the bytes, or always the plane -- a forced input the seqset
+ * cannot serve (stale plane, plane-only seqset, a plan outside the fast kernels asked for the plane) fails
+ * the run with GAMS_ESTATE.  Results are identical; for tests and A/B runs. */
+#define GAMS_WAVE_INPUT_AUTO 0
+#define GAMS_WAVE_INPUT_BYTES 1
+#define GAMS_WAVE_INPUT_PLANE 2
+int gams_wave_plan_set_input(gams_gpu_t *h, gams_wave_plan_t *p, int mode);
+/* the input the plan's most recently queued pass took: GAMS_WAVE_INPUT_BYTES or GAMS_WAVE_INPUT_PLANE */
+int gams_wave_plan_last_input(gams_gpu_t *h, gams_wave_plan_t *p, int *input);
+/* gams_gc_plane with the body named: the AVX2 one (GAMS_EUNSUPPORTED on a CPU without it), the portable
+ * 64-bit one, or the library's choice.  Every body writes the same bytes. */
+#define GAMS_GC_BODY_AUTO 0
+#define GAMS_GC_BODY_PORTABLE 1
+#define GAMS_GC_BODY_AVX2 2
+int gams_gc_plane_with(const uint8_t *seq, uint64_t n, uint8_t *plane, int body);
+
 #ifdef __cplusplus
 }
 #endif
