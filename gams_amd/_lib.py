@@ -48,6 +48,7 @@ PROTOTYPES = {
     "gams_gpu_timer_start": (C.c_int, [_VP]),
     "gams_gpu_timer_stop": (C.c_int, [_VP, C.POINTER(C.c_float)]),
     "gams_gpu_last_kernel_ms": (C.c_int, [_VP, C.POINTER(C.c_float)]),
+    "gams_gpu_last_stage_ms": (C.c_int, [_VP, _VP, C.c_uint32, C.POINTER(C.c_uint32)]),
     "gams_gpu_host_alloc": (C.c_int, [_VP, C.c_uint64, _PP]),
     "gams_gpu_host_free": (None, [_VP, _VP]),
     "gams_window_count": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
@@ -119,6 +120,9 @@ PROTOTYPES = {
                                       C.POINTER(C.c_uint64)]),
     "gams_gpu_anno_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int, C.c_char_p, C.c_uint32,
                                      C.c_uint32, _PP, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gams_gpu_read_range_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, C.c_uint64,
+                                           C.POINTER(C.c_uint64)]),
+    "gams_index_create_range_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _PP, _VP, C.POINTER(C.c_uint64)]),
     "gams_gpu_valid_spans": (C.c_int, [_VP, _VP, C.c_uint64, C.c_int32, C.c_int32, _VP, _VP, C.c_uint64,
                                        C.POINTER(C.c_uint64)]),
 }

@@ -191,6 +191,18 @@ int gams_gpu_last_kernel_ms(gams_gpu_t *h, float *ms) {
     return GAMS_OK;
 }
 
+int gams_gpu_last_stage_ms(gams_gpu_t *h, float *ms, uint32_t cap, uint32_t *n) {
+    if (!h || !n || (cap && !ms)) return gams_fail(h, GAMS_EINVAL, "last_stage_ms: null argument");
+    if (!h->k_valid || h->kq_used <= 0 || !h->kq_staged) return gams_fail(h, GAMS_ESTATE, "last_stage_ms: the last timed call has no stages");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    *n = (uint32_t)h->kq_used;
+    for (uint32_t c = 0; c < (uint32_t)h->kq_used && c < cap; ++c) {
+        GAMS_HIP(h, hipEventSynchronize(h->kq[c].second));
+        GAMS_HIP(h, hipEventElapsedTime(ms + c, h->kq[c].first, h->kq[c].second));
+    }
+    return GAMS_OK;
+}
+
 int gams_gpu_host_alloc(gams_gpu_t *h, uint64_t bytes, void **p) {
     if (!h || !p) return gams_fail(h, GAMS_EINVAL, "host_alloc: null argument");
     GAMS_HIP(h, hipSetDevice(h->device));

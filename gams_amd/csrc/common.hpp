@@ -34,6 +34,7 @@ struct gams_gpu {
     hipEvent_t q_ev[2][3] = {};
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kq;
     int kq_used = 0;
+    bool kq_staged = false;   // the pairs are the stages of a range loader call (text.hip), not the chunks of a query call
     // pinned staging ring of the copy stream: the CPU fills slot k+1 while the DMA drains slot k
     static constexpr int kStageSlots = 4;
     static constexpr size_t kStageBytes = 16u << 20;

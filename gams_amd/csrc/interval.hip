@@ -642,6 +642,7 @@ int query_pipeline(gams_gpu_t *h, uint64_t nq, const QCol *cols, int ncol, void 
         Q_HIP(hipEventRecord(h->q_ev[s][2], h->readback));
     }
     h->kq_used = (int)nchunk;
+    h->kq_staged = false;
     h->k_valid = true;
     Q_HIP(hipStreamSynchronize(h->readback));
     return GAMS_OK;
@@ -649,18 +650,12 @@ int query_pipeline(gams_gpu_t *h, uint64_t nq, const QCol *cols, int ncol, void 
 
 }  // namespace
 
-extern "C" {
-
-int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_off, const uint32_t *starts,
-                      const uint32_t *stops, gams_index_t **out) {
-    if (!h || !out || !group_off) return gams_fail(h, GAMS_EINVAL, "index_create: null argument");
-    const uint64_t m = group_off[n_groups];
-    if (m && (!starts || !stops)) return gams_fail(h, GAMS_EINVAL, "index_create: null interval arrays");
-    for (uint32_t g = 0; g < n_groups; ++g)
-        if (group_off[g] > group_off[g + 1]) return gams_fail(h, GAMS_EINVAL, "index_create: group_off not ascending");
-    if (m > 0xfffffff0ull)
-        return gams_fail(h, GAMS_EUNSUPPORTED, "index_create: more than 2^32-16 intervals in one index");
-    GAMS_HIP(h, hipSetDevice(h->device));
+// ---- the builder behind gams_index_create (and text.hip's gams_index_create_range_text) ------------------------
+// begin: the index's arena and the build's scratch for n_groups groups of m intervals in all (m <= 2^32 - 16, checked by
+// the caller).  The caller then fills d_off32 (n_groups + 1 offsets), d_starts_in and d_stops_in (any order inside a
+// group) by work queued on the compute stream, and calls run with the largest group's size.
+int gams_index_build_begin(gams_gpu_t *h, uint32_t n_groups, uint64_t m, IndexBuild *B) {
+    *B = IndexBuild();
     // Lapper::new on the device: intervals.sort() by (start, stop) inside every group = a stable
     // segmented radix sort of the packed 64-bit keys; the stops are also sorted on their own.  The
     // bucket directories and Lapper::max_len come from three small kernels over the sorted arrays.
@@ -669,29 +664,15 @@ int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
     const size_t b_cg = al((size_t)ng1 * sizeof(CountGroup));
     const size_t b_groups = al((size_t)ng1 * sizeof(IndexGroup)), b_u32 = al(std::max<uint64_t>(m, 1) * 4),
                  b_rec = al(std::max<uint64_t>(m, 1) * sizeof(IvRec)), b_dir = al((m + n_groups + 1) * 4);
-    const uint64_t bk_slots = (m >> kCellShift) + 2ull * n_groups + 2;
-    const size_t b_bk = al(bk_slots * sizeof(BkRec));
+    B->bk_slots = (m >> kCellShift) + 2ull * n_groups + 2;
+    const size_t b_bk = al(B->bk_slots * sizeof(BkRec));
     gams_index_t *ix = new gams_index_t();
+    B->ix = ix;
     ix->n_groups = n_groups;
     ix->m = m;
     hipError_t e = gams_pool_alloc(h, false, b_groups + b_cg + 2 * b_u32 + b_rec + b_dir + 2 * b_bk,
                                    reinterpret_cast<void **>(&ix->arena), &ix->arena_bytes);
-    // scratch: raw columns, packed keys in/out, permutation in/out, 32-bit offsets, radix-sort storage
-    const size_t b_key = al(std::max<uint64_t>(m, 1) * 8), b_off = al(((size_t)n_groups + 1) * 4);
-    uint8_t *scratch = nullptr;
-    size_t scratch_bytes = 0, tmp_bytes_pairs = 0, tmp_bytes_keys = 0;
-    uint8_t *d_tmp = nullptr;
-    size_t d_tmp_bytes = 0;
-    auto fail = [&](hipError_t err, const char *what) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(h->compute);
-        gams_pool_free(h, false, scratch, scratch_bytes);
-        gams_pool_free(h, false, d_tmp, d_tmp_bytes);
-        gams_index_destroy(h, ix);
-        return gams_fail(h, err == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,
-                         std::string("index_create: ") + what + ": " + hipGetErrorString(err));
-    };
-    if (e != hipSuccess) return fail(e, "hipMalloc(index)");
+    if (e != hipSuccess) return gams_index_build_fail(h, B, e, "hipMalloc(index)");
     {
         uint8_t *p = ix->arena;
         ix->d_groups = reinterpret_cast<IndexGroup *>(p);
@@ -709,29 +690,46 @@ int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
         ix->d_bk_start = reinterpret_cast<BkRec *>(p);     // 2 * bk_slots records, interleaved: cell j = [2j] starts, [2j+1] stops
         ix->d_bk_stop = ix->d_bk_start + 1;
     }
-    e = gams_pool_alloc(h, false, 2 * b_u32 + 2 * b_key + 2 * b_u32 + b_off, reinterpret_cast<void **>(&scratch),
-                        &scratch_bytes);
-    if (e != hipSuccess) return fail(e, "hipMalloc(scratch)");
-    uint32_t *d_starts_in = reinterpret_cast<uint32_t *>(scratch);
-    uint32_t *d_stops_in = reinterpret_cast<uint32_t *>(scratch + b_u32);
-    uint64_t *d_key_in = reinterpret_cast<uint64_t *>(scratch + 2 * b_u32);
-    uint64_t *d_key_out = reinterpret_cast<uint64_t *>(scratch + 2 * b_u32 + b_key);
-    uint32_t *d_val_in = reinterpret_cast<uint32_t *>(scratch + 2 * b_u32 + 2 * b_key);
-    uint32_t *d_val_out = reinterpret_cast<uint32_t *>(scratch + 3 * b_u32 + 2 * b_key);
-    uint32_t *d_off32 = reinterpret_cast<uint32_t *>(scratch + 4 * b_u32 + 2 * b_key);
+    // scratch: raw columns, packed keys in/out, permutation in/out, 32-bit offsets, radix-sort storage
+    const size_t b_key = al(std::max<uint64_t>(m, 1) * 8), b_off = al(((size_t)n_groups + 1) * 4);
+    e = gams_pool_alloc(h, false, 2 * b_u32 + 2 * b_key + 2 * b_u32 + b_off, reinterpret_cast<void **>(&B->scratch),
+                        &B->scratch_bytes);
+    if (e != hipSuccess) return gams_index_build_fail(h, B, e, "hipMalloc(scratch)");
+    uint8_t *scratch = B->scratch;
+    B->d_starts_in = reinterpret_cast<uint32_t *>(scratch);
+    B->d_stops_in = reinterpret_cast<uint32_t *>(scratch + b_u32);
+    B->d_key_in = reinterpret_cast<uint64_t *>(scratch + 2 * b_u32);
+    B->d_key_out = reinterpret_cast<uint64_t *>(scratch + 2 * b_u32 + b_key);
+    B->d_val_in = reinterpret_cast<uint32_t *>(scratch + 2 * b_u32 + 2 * b_key);
+    B->d_val_out = reinterpret_cast<uint32_t *>(scratch + 3 * b_u32 + 2 * b_key);
+    B->d_off32 = reinterpret_cast<uint32_t *>(scratch + 4 * b_u32 + 2 * b_key);
+    return GAMS_OK;
+}
+
+// a failed build: the stream drained, everything of the build returned to the pools, the error reported
+int gams_index_build_fail(gams_gpu_t *h, IndexBuild *B, hipError_t err, const char *what) {
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(h->compute);
+    gams_pool_free(h, false, B->scratch, B->scratch_bytes);
+    gams_pool_free(h, false, B->d_tmp, B->d_tmp_bytes);
+    gams_index_destroy(h, B->ix);
+    *B = IndexBuild();
+    return gams_fail(h, err == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,
+                     std::string("index_create: ") + what + ": " + hipGetErrorString(err));
+}
+
+// run: sorts and tables from the device columns; waits for the build, frees the scratch, hands the index out
+int gams_index_build_run(gams_gpu_t *h, IndexBuild *B, uint32_t max_n, gams_index_t **out, hipEvent_t done) {
+    gams_index_t *ix = B->ix;
+    const uint32_t n_groups = ix->n_groups;
+    const uint64_t m = ix->m, bk_slots = B->bk_slots;
+    uint32_t *d_starts_in = B->d_starts_in, *d_stops_in = B->d_stops_in, *d_off32 = B->d_off32;
+    uint64_t *d_key_in = B->d_key_in, *d_key_out = B->d_key_out;
+    uint32_t *d_val_in = B->d_val_in, *d_val_out = B->d_val_out;
+    size_t tmp_bytes_pairs = 0, tmp_bytes_keys = 0;
     hipStream_t st = h->compute;
-    std::vector<uint32_t> off32((size_t)n_groups + 1);
-    for (uint32_t g = 0; g <= n_groups; ++g) off32[g] = (uint32_t)group_off[g];
-    if ((e = hipMemcpyAsync(d_off32, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
-        return fail(e, "copy offsets");
-    uint32_t max_n = 0;
-    for (uint32_t g = 0; g < n_groups; ++g) max_n = std::max(max_n, off32[g + 1] - off32[g]);
-    if (m) {
-        if ((e = hipMemcpyAsync(d_starts_in, starts, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return fail(e, "copy starts");
-        if ((e = hipMemcpyAsync(d_stops_in, stops, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
-            return fail(e, "copy stops");
-    }
+    hipError_t e;
+    auto fail = [&](hipError_t err, const char *what) { return gams_index_build_fail(h, B, err, what); };
     if (n_groups && max_n <= kBuildCap) {
         // every group fits a workgroup: sort and every derived table in one kernel, one workgroup per group
         if (max_n <= 256)
@@ -758,12 +756,12 @@ int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
                                                d_off32, d_off32 + 1, 0, 32, st);
         if (e != hipSuccess) return fail(e, "radix sort (size query)");
         e = gams_pool_alloc(h, false, std::max<size_t>(std::max(tmp_bytes_pairs, tmp_bytes_keys), 256),
-                            reinterpret_cast<void **>(&d_tmp), &d_tmp_bytes);
+                            reinterpret_cast<void **>(&B->d_tmp), &B->d_tmp_bytes);
         if (e != hipSuccess) return fail(e, "hipMalloc(sort storage)");
-        e = rocprim::segmented_radix_sort_pairs(d_tmp, tmp_bytes_pairs, d_key_in, d_key_out, d_val_in, d_val_out,
+        e = rocprim::segmented_radix_sort_pairs(B->d_tmp, tmp_bytes_pairs, d_key_in, d_key_out, d_val_in, d_val_out,
                                                 (unsigned)m, n_groups, d_off32, d_off32 + 1, 0, 64, st);
         if (e != hipSuccess) return fail(e, "radix sort of (start, stop)");
-        e = rocprim::segmented_radix_sort_keys(d_tmp, tmp_bytes_keys, d_stops_in, ix->d_stops, (unsigned)m, n_groups,
+        e = rocprim::segmented_radix_sort_keys(B->d_tmp, tmp_bytes_keys, d_stops_in, ix->d_stops, (unsigned)m, n_groups,
                                                d_off32, d_off32 + 1, 0, 32, st);
         if (e != hipSuccess) return fail(e, "radix sort of stops");
         hipLaunchKernelGGL(index_unpack_kernel, dim3(blocks), dim3(256), 0, st, d_key_out, d_val_out, m, ix->d_lstart,
@@ -782,11 +780,46 @@ int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
                            n_groups, bk_slots, ix->d_groups, ix->d_lstart, ix->d_stops, ix->d_bk_start, ix->d_bk_stop);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "bucket records");
     }
+    if (done && (e = hipEventRecord(done, st)) != hipSuccess) return fail(e, "index build");
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "index build");
-    gams_pool_free(h, false, scratch, scratch_bytes);
-    gams_pool_free(h, false, d_tmp, d_tmp_bytes);
+    gams_pool_free(h, false, B->scratch, B->scratch_bytes);
+    gams_pool_free(h, false, B->d_tmp, B->d_tmp_bytes);
+    *B = IndexBuild();
     *out = ix;
     return GAMS_OK;
+}
+
+extern "C" {
+
+int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_off, const uint32_t *starts,
+                      const uint32_t *stops, gams_index_t **out) {
+    // the host front: the checks, and the caller's arrays copied into the builder's device columns
+    if (!h || !out || !group_off) return gams_fail(h, GAMS_EINVAL, "index_create: null argument");
+    const uint64_t m = group_off[n_groups];
+    if (m && (!starts || !stops)) return gams_fail(h, GAMS_EINVAL, "index_create: null interval arrays");
+    for (uint32_t g = 0; g < n_groups; ++g)
+        if (group_off[g] > group_off[g + 1]) return gams_fail(h, GAMS_EINVAL, "index_create: group_off not ascending");
+    if (m > 0xfffffff0ull)
+        return gams_fail(h, GAMS_EUNSUPPORTED, "index_create: more than 2^32-16 intervals in one index");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    IndexBuild B;
+    const int rc = gams_index_build_begin(h, n_groups, m, &B);
+    if (rc != GAMS_OK) return rc;
+    hipStream_t st = h->compute;
+    hipError_t e;
+    std::vector<uint32_t> off32((size_t)n_groups + 1);
+    for (uint32_t g = 0; g <= n_groups; ++g) off32[g] = (uint32_t)group_off[g];
+    if ((e = hipMemcpyAsync(B.d_off32, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+        return gams_index_build_fail(h, &B, e, "copy offsets");
+    uint32_t max_n = 0;
+    for (uint32_t g = 0; g < n_groups; ++g) max_n = std::max(max_n, off32[g + 1] - off32[g]);
+    if (m) {
+        if ((e = hipMemcpyAsync(B.d_starts_in, starts, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return gams_index_build_fail(h, &B, e, "copy starts");
+        if ((e = hipMemcpyAsync(B.d_stops_in, stops, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+            return gams_index_build_fail(h, &B, e, "copy stops");
+    }
+    return gams_index_build_run(h, &B, max_n, out);
 }
 
 void gams_index_destroy(gams_gpu_t *h, gams_index_t *ix) {

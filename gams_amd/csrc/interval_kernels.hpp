@@ -80,6 +80,26 @@ struct gams_index {
     size_t arena_bytes = 0;
 };
 
+// One index build, between its two steps (interval.hip): gams_index_build_begin allocates the index and the scratch,
+// the caller queues on the compute stream whatever fills d_off32 (n_groups + 1 offsets), d_starts_in and d_stops_in,
+// and gams_index_build_run sorts, derives the tables, waits and hands the index out.  gams_index_create is the front
+// that fills the columns from host arrays; gams_index_create_range_text (text.hip) fills them by a gather kernel.
+// A step that fails has already returned everything to the pools (gams_index_build_fail does that for the caller's
+// own errors in between).
+struct IndexBuild {
+    gams_index *ix = nullptr;
+    uint32_t *d_off32 = nullptr, *d_starts_in = nullptr, *d_stops_in = nullptr;   // the builder's inputs
+    uint64_t *d_key_in = nullptr, *d_key_out = nullptr;                           // groups beyond a workgroup: the radix sort's buffers
+    uint32_t *d_val_in = nullptr, *d_val_out = nullptr;
+    uint64_t bk_slots = 0;
+    uint8_t *scratch = nullptr, *d_tmp = nullptr;
+    size_t scratch_bytes = 0, d_tmp_bytes = 0;
+};
+int gams_index_build_begin(gams_gpu_t *h, uint32_t n_groups, uint64_t m, IndexBuild *B);
+// (done, if given: an event recorded on the compute stream behind the build's last kernel, before the host waits)
+int gams_index_build_run(gams_gpu_t *h, IndexBuild *B, uint32_t max_n, gams_index_t **out, hipEvent_t done = nullptr);
+int gams_index_build_fail(gams_gpu_t *h, IndexBuild *B, hipError_t err, const char *what);
+
 // Cell record of the anno path, 64 B: everything a "covered bases up to x" lookup needs when x falls in cell b of the
 // group's grid (the grid of the `lo` directory, about one span per cell) -- the rank at the cell's edge, the span in
 // front of it with the covered bases before that one, and the next five spans inline.  One line per position instead

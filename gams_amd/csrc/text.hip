@@ -4,6 +4,10 @@
 //   gams_gpu_locate_text   locate.rs:84-141 with utils.rs:7-22   "{rg}\t{ctg_id}\n"
 //   gams_gpu_count_text    locate.rs:84-141 with utils.rs:24-36  "{rg}\t{count}\n"
 //   gams_gpu_anno_text     anno.rs:95-142 (one input file)       "{line}\t{prop:.4}\n"
+// and text in, index out for the rg loader (utils.rs:39-67 read_range, then redis.rs:288-299), behind the same
+// upload and line index (the stages are listed in front of its kernels, below):
+//   gams_gpu_read_range_text       the ranges of one .rg file bucketed per ctg, as arrays
+//   gams_index_create_range_text   the rg index of the file and the ctg -> group table
 //
 // Pipeline (one handle, the compute stream):
 //   1. one copy of the bytes into a cached device buffer, padded with spaces to 16 B and 16 B beyond;
@@ -21,6 +25,8 @@
 #include "interval_kernels.hpp"
 #include "text_emit.hpp"
 #include "text_fmt.hpp"
+
+#include <rocprim/rocprim.hpp>   // the radix sort that orders the kept lines of the range loader
 
 #include <algorithm>
 #include <string>
@@ -486,17 +492,34 @@ struct TextJob {
 
 const char *const kEntry[3] = {"gpu_locate_text", "gpu_count_text", "gpu_anno_text"};
 
-int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_bytes, const char **text,
-             uint64_t *text_bytes, uint64_t *n_rows) {
-    const std::string who = kEntry[J.kind];
-    *text = nullptr;
-    *text_bytes = 0;
-    *n_rows = 0;
-    GAMS_HIP(h, hipSetDevice(h->device));
+#define T_HIP(call)                                                                                  \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return gams_fail(h, e_ == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,                 \
+                             who + ": " + #call + ": " + hipGetErrorString(e_));                     \
+    } while (0)
+
+// What steps 1 and 2 (pass 1) of every text entry leave behind: the input in the handle's cached device buffer, the
+// words, the '\n' count of every index block with its prefix, and the line count.  s0 is the pooled block behind the
+// three small arrays; the caller frees it (after draining the stream).
+struct TextFront {
+    uint8_t *s0 = nullptr;
+    size_t s0_cap = 0;
+    unsigned long long *d_words = nullptr;
+    uint32_t *d_bnl = nullptr;
+    unsigned long long *d_bnloff = nullptr;
+    uint32_t nbi = 0;
+    uint64_t n16 = 0, nl = 0;
+    uint32_t L = 0;          // lines (BufRead::lines())
+};
+
+int text_front(gams_gpu_t *h, const std::string &who, const char *bytes, uint64_t n_bytes, TextFront &F) {
     if (!h->text) h->text = new gams_text_state();
     gams_text_state *T = h->text;
     auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const uint64_t n16 = (n_bytes + 15u) & ~15ull;
+    F.n16 = n16;
     // 1. upload into the cached buffer; the 16-B tail is spaces (no '\n', nothing refused)
     const uint64_t n_pad = n16 + 16u;                 // the parse kernels may look 11 bytes past a field's end
     if (T->d_in_cap < n_pad) {
@@ -509,30 +532,12 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     }
     hipStream_t st = h->compute;
     const uint32_t nbi = (uint32_t)std::max<uint64_t>(1, (n16 + kIdxBytes - 1) / kIdxBytes);
+    F.nbi = nbi;
     const size_t b_words = al(W_COUNT * 8), b_bnl = al((size_t)nbi * 4), b_bnloff = al(((size_t)nbi + 1) * 8);
-    uint8_t *s0 = nullptr, *s1 = nullptr;
-    size_t s0_cap = 0, s1_cap = 0;
-    struct Guard {
-        gams_gpu_t *h;
-        uint8_t **a, **b;
-        size_t *ac, *bc;
-        ~Guard() {
-            (void)hipStreamSynchronize(h->compute);
-            gams_pool_free(h, false, *a, *ac);
-            gams_pool_free(h, false, *b, *bc);
-        }
-    } guard{h, &s0, &s1, &s0_cap, &s1_cap};
-#define T_HIP(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return gams_fail(h, e_ == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,                 \
-                             who + ": " + #call + ": " + hipGetErrorString(e_));                     \
-    } while (0)
-    T_HIP(gams_pool_alloc(h, false, b_words + b_bnl + b_bnloff, reinterpret_cast<void **>(&s0), &s0_cap));
-    unsigned long long *d_words = reinterpret_cast<unsigned long long *>(s0);
-    uint32_t *d_bnl = reinterpret_cast<uint32_t *>(s0 + b_words);
-    unsigned long long *d_bnloff = reinterpret_cast<unsigned long long *>(s0 + b_words + b_bnl);
+    T_HIP(gams_pool_alloc(h, false, b_words + b_bnl + b_bnloff, reinterpret_cast<void **>(&F.s0), &F.s0_cap));
+    unsigned long long *d_words = F.d_words = reinterpret_cast<unsigned long long *>(F.s0);
+    uint32_t *d_bnl = F.d_bnl = reinterpret_cast<uint32_t *>(F.s0 + b_words);
+    unsigned long long *d_bnloff = F.d_bnloff = reinterpret_cast<unsigned long long *>(F.s0 + b_words + b_bnl);
     T_HIP(hipEventRecord(h->k0, st));
     h->k_valid = false;
     h->kq_used = 0;
@@ -545,12 +550,46 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     T_HIP(hipGetLastError());
     T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, 2 * 8, hipMemcpyDeviceToHost, st));
     T_HIP(hipStreamSynchronize(st));
-    const uint64_t nl = h->pin_scratch[W_NL];
+    F.nl = h->pin_scratch[W_NL];
     if (h->pin_scratch[W_BAD])
         return gams_fail(h, GAMS_EUNSUPPORTED, who + ": the input holds a byte >= 0x80 or a NUL (use the host path)");
-    const uint64_t L64 = n_bytes == 0 ? 0 : nl + (bytes[n_bytes - 1] != '\n' ? 1u : 0u);
+    const uint64_t L64 = n_bytes == 0 ? 0 : F.nl + (bytes[n_bytes - 1] != '\n' ? 1u : 0u);
     if (L64 > 0xffffffffull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 1 lines");
-    const uint32_t L = (uint32_t)L64;
+    F.L = (uint32_t)L64;
+    return GAMS_OK;
+}
+
+// the pooled scratch blocks of one call, returned once the stream has drained
+struct ScratchGuard {
+    gams_gpu_t *h;
+    uint8_t **a, **b;
+    size_t *ac, *bc;
+    ~ScratchGuard() {
+        (void)hipStreamSynchronize(h->compute);
+        gams_pool_free(h, false, *a, *ac);
+        gams_pool_free(h, false, *b, *bc);
+    }
+};
+
+int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_bytes, const char **text,
+             uint64_t *text_bytes, uint64_t *n_rows) {
+    const std::string who = kEntry[J.kind];
+    *text = nullptr;
+    *text_bytes = 0;
+    *n_rows = 0;
+    GAMS_HIP(h, hipSetDevice(h->device));
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    TextFront F;
+    uint8_t *s1 = nullptr;
+    size_t s1_cap = 0;
+    ScratchGuard guard{h, &F.s0, &s1, &F.s0_cap, &s1_cap};
+    const int rc_front = text_front(h, who, bytes, n_bytes, F);
+    if (rc_front != GAMS_OK) return rc_front;
+    gams_text_state *T = h->text;
+    hipStream_t st = h->compute;
+    const uint64_t n16 = F.n16, nl = F.nl;
+    const uint32_t nbi = F.nbi, L = F.L;
+    unsigned long long *d_words = F.d_words, *d_bnloff = F.d_bnloff;
     if (J.kind == K_ANNO && L > (uint32_t)(J.header ? 1 : 0) && (J.idx_id == 0 || J.idx_range == 0))
         return gams_fail(h, GAMS_EINVAL, who + ": field index 0 (the reference panics, anno.rs:115)");
     if (L == 0) {
@@ -678,12 +717,236 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
         T_HIP(hipStreamSynchronize(st));
     }
     h->k_valid = true;
-#undef T_HIP
     *text = out;
     *text_bytes = tb;
     *n_rows = rows;
     return GAMS_OK;
 }
+
+
+// ---- read_range on the device (utils.rs:39-67): the bytes of a .rg file -> the ranges bucketed per ctg ----------
+// Stages behind the line index (one lane per line unless said otherwise):
+//   parse    the WHOLE line through Range::from_str (no cut at a tab) -> (chromosome group, start, end);
+//   locate   interval_locate_kernel on those columns -> the ctg of every line (its interval of ctg_ix), or -1;
+//   first    first[c] = the smallest line number located to ctg c: the line `.or_default()` swallows;
+//   keep     keep = located and not first[c]; count[c] = kept lines of c; the sort key (c, line) of every line;
+//   offsets  exclusive scan of count -> bucket_off;
+//   order    ONE radix sort of the 64-bit keys (c << line bits | line); dropped lines carry c = n_ctg and sort
+//            behind every bucket.  The keys are unique, so the order is (ctg, line) whatever order lanes ran in;
+//   gather   start / end (or the index builder's [start, end + 1) columns) through the sorted line numbers.
+// first and keep issue one atomic per run of equal ctgs inside a wavefront: lanes are in line order, a range file is
+// sorted by position, so a wavefront usually holds one run and its leader's line is the run's smallest.  The atomics
+// are integer min and add: their result does not depend on arrival order.
+
+// the ctg of lane - 1 (lane 0: none), for the run leaders: a lane leads when its predecessor's ctg differs
+__device__ __forceinline__ bool run_leader(int64_t c) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t plo = __shfl_up((uint32_t)c, 1, 64), phi = __shfl_up((uint32_t)((uint64_t)c >> 32), 1, 64);
+    const int64_t prev = (int64_t)(((uint64_t)phi << 32) | plo);
+    return lane == 0u || prev != c;
+}
+
+__global__ __launch_bounds__(256) void rg_parse_kernel(const TextLines t, const NameTab chr, uint32_t *grp, uint32_t *qs,
+                                                       uint32_t *qe) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= t.n_lines) return;
+    uint64_t b, e;
+    line_of(t, i, b, e);
+    const RangeField r = parse_range(t.in, b, e);          // utils.rs:50: the line, not its first field
+    grp[i] = r.ok ? name_find(chr, t.in + r.cb, r.ce - r.cb) : UINT32_MAX;
+    qs[i] = r.start;
+    qe[i] = r.end;
+}
+
+__global__ __launch_bounds__(256) void rg_first_kernel(uint32_t n_lines, const int64_t *hit, uint32_t *first) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const int64_t c = i < n_lines ? hit[i] : -1;
+    if (run_leader(c) && c >= 0) atomicMin(first + c, i);
+}
+
+__global__ __launch_bounds__(256) void rg_keep_kernel(uint32_t n_lines, uint32_t n_ctg, uint32_t line_bits, const int64_t *hit,
+                                                      const uint32_t *first, uint32_t *count, unsigned long long *key) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t c = i < n_lines ? hit[i] : -1;
+    const bool keep = c >= 0 && first[c] != i;
+    const bool lead = run_leader(c);
+    const unsigned long long kept = __ballot(keep), leads = __ballot(lead);
+    if (lead && c >= 0) {
+        // the run is [lane, next leader): its kept lines, one add
+        const unsigned long long above = lane == 63u ? 0ull : leads & (~0ull << (lane + 1u));
+        const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
+        const unsigned long long run = (end == 64u ? ~0ull : (1ull << end) - 1ull) & (~0ull << lane);
+        const uint32_t n = (uint32_t)__popcll(kept & run);
+        if (n) atomicAdd(count + c, n);
+    }
+    if (i < n_lines) key[i] = ((unsigned long long)(keep ? (uint32_t)c : n_ctg) << line_bits) | i;
+}
+
+struct RgGather {
+    const unsigned long long *key;       // sorted: the first n_kept are the kept lines in (ctg, line) order
+    unsigned long long line_mask;
+    const uint32_t *qs, *qe;
+    uint64_t n_kept;
+    uint32_t *start, *end, *line;        // end = the range's end + end_plus; line may be NULL
+    uint32_t end_plus;
+    const unsigned long long *bucket_off;   // with off32: the n_off offsets narrowed for the index builder
+    uint32_t *off32;
+    uint64_t n_off;
+};
+
+__global__ __launch_bounds__(256) void rg_gather_kernel(const RgGather a) {
+    const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (k < a.n_kept) {
+        const uint32_t i = (uint32_t)(a.key[k] & a.line_mask);
+        a.start[k] = a.qs[i];
+        a.end[k] = a.qe[i] + a.end_plus;
+        if (a.line) a.line[k] = i;
+    }
+    if (a.off32 && k < a.n_off) a.off32[k] = (uint32_t)a.bucket_off[k];
+}
+
+// what the loader hands its consumer while the scratch is alive
+struct RgCols {
+    uint64_t n_ctg, n_kept;
+    const unsigned long long *bucket_off;   // host, n_ctg + 1
+    const uint32_t *first;                  // host, n_ctg: UINT32_MAX = no located line
+    RgGather g;                             // key, line_mask, qs, qe, n_kept, bucket_off (device) filled; n_kept == 0: nothing on the device
+    bool ran;                               // the input had lines: the stages up to RG_OFFSETS (with `order` RG_ORDER) were queued and timed
+};
+
+enum : int { RG_LINES = 0, RG_PARSE, RG_LOCATE, RG_FIRST, RG_KEEP, RG_OFFSETS, RG_ORDER, RG_GATHER, RG_BUILD, RG_STAGES };
+
+// Runs the stages up to the sort (`order` false: up to the offsets, for a size query) and calls consume(cols, stage) -- stage(k, open) records the stopwatch event that opens
+// or closes stage k -- which queues the gather and whatever follows.  `who` names the entry in error messages.
+template <typename Consume>
+int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, const gams_names_t *chr, const char *bytes,
+            uint64_t n_bytes, bool order, Consume consume) {
+    GAMS_HIP(h, hipSetDevice(h->device));
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    while (h->kq.size() < (size_t)RG_STAGES) {
+        hipEvent_t a = nullptr, b = nullptr;
+        GAMS_HIP(h, hipEventCreate(&a));
+        GAMS_HIP(h, hipEventCreate(&b));
+        h->kq.emplace_back(a, b);
+    }
+    hipStream_t st = h->compute;
+    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
+    TextFront F;
+    uint8_t *s1 = nullptr;
+    size_t s1_cap = 0;
+    ScratchGuard guard{h, &F.s0, &s1, &F.s0_cap, &s1_cap};
+    T_HIP(stage(RG_LINES, true));
+    const int rc_front = text_front(h, who, bytes, n_bytes, F);
+    if (rc_front != GAMS_OK) return rc_front;
+    const uint64_t n_ctg = ctg_ix->m;
+    const uint32_t L = F.L;
+    // the host's copy of bucket_off and first: page-locked, from the pool
+    struct Pin {
+        gams_gpu_t *h;
+        uint8_t *p = nullptr;
+        size_t cap = 0;
+        ~Pin() {
+            (void)hipStreamSynchronize(h->compute);   // a copy into the block may still be queued when a step failed
+            gams_pool_free(h, true, p, cap);
+        }
+    } pin{h};
+    const size_t b_hoff = al((n_ctg + 1) * 8);
+    T_HIP(gams_pool_alloc(h, true, b_hoff + std::max<uint64_t>(n_ctg, 1) * 4, reinterpret_cast<void **>(&pin.p), &pin.cap));
+    unsigned long long *h_off = reinterpret_cast<unsigned long long *>(pin.p);
+    uint32_t *h_first = reinterpret_cast<uint32_t *>(pin.p + b_hoff);
+    RgCols C{};
+    C.n_ctg = n_ctg;
+    C.bucket_off = h_off;
+    C.first = h_first;
+    if (L == 0) {
+        memset(h_off, 0, (n_ctg + 1) * 8);
+        memset(h_first, 0xff, n_ctg * 4);
+        T_HIP(stage(RG_LINES, false));
+        return consume(C, stage);
+    }
+    uint32_t line_bits = 1, ctg_bits = 1;
+    while (line_bits < 32u && (L - 1u) >> line_bits) ++line_bits;
+    while (ctg_bits < 32u && n_ctg >> ctg_bits) ++ctg_bits;
+    const uint32_t nbr = (L + 255u) / 256u;
+    const size_t b_starts = al(((size_t)F.nl + 2) * 8), b_u32 = al((size_t)L * 4), b_u64 = al((size_t)L * 8),
+                 b_tab = al(std::max<uint64_t>(n_ctg, 1) * 4), b_off = al((n_ctg + 1) * 8);
+    size_t sort_bytes = 0;
+    T_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (size_t)L, 0u,
+                                   line_bits + ctg_bits, st));
+    const size_t b_sort = al(std::max<size_t>(sort_bytes, 1));
+    // starts | grp qs qe | hit key key' | first count | bucket_off | sort storage
+    T_HIP(gams_pool_alloc(h, false, b_starts + 3 * b_u32 + 3 * b_u64 + 2 * b_tab + b_off + b_sort, reinterpret_cast<void **>(&s1),
+                          &s1_cap));
+    uint8_t *p = s1;
+    auto take = [&](size_t b) {
+        uint8_t *q = p;
+        p += b;
+        return q;
+    };
+    unsigned long long *d_starts = reinterpret_cast<unsigned long long *>(take(b_starts));
+    uint32_t *d_grp = reinterpret_cast<uint32_t *>(take(b_u32));
+    uint32_t *d_qs = reinterpret_cast<uint32_t *>(take(b_u32));
+    uint32_t *d_qe = reinterpret_cast<uint32_t *>(take(b_u32));
+    int64_t *d_hit = reinterpret_cast<int64_t *>(take(b_u64));
+    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(take(b_u64));
+    unsigned long long *d_key2 = reinterpret_cast<unsigned long long *>(take(b_u64));
+    uint32_t *d_first = reinterpret_cast<uint32_t *>(take(b_tab));
+    uint32_t *d_count = reinterpret_cast<uint32_t *>(take(b_tab));
+    unsigned long long *d_off = reinterpret_cast<unsigned long long *>(take(b_off));
+    uint8_t *d_sort = take(b_sort);
+    hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, h->text->d_in, n_bytes, F.n16, F.d_bnloff, F.nl,
+                       d_starts);
+    T_HIP(hipMemsetAsync(d_first, 0xff, b_tab, st));
+    T_HIP(hipMemsetAsync(d_count, 0, b_tab, st));
+    T_HIP(stage(RG_LINES, false));
+    const TextLines tl{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
+    T_HIP(stage(RG_PARSE, true));
+    hipLaunchKernelGGL(rg_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, chr->t, d_grp, d_qs, d_qe);
+    T_HIP(stage(RG_PARSE, false));
+    T_HIP(stage(RG_LOCATE, true));
+    launch_interval_locate(ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
+    T_HIP(stage(RG_LOCATE, false));
+    T_HIP(stage(RG_FIRST, true));
+    hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
+    T_HIP(stage(RG_FIRST, false));
+    T_HIP(stage(RG_KEEP, true));
+    hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key);
+    T_HIP(stage(RG_KEEP, false));
+    T_HIP(stage(RG_OFFSETS, true));
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, d_off, F.d_words,
+                       (uint32_t)W_ROWS);
+    T_HIP(stage(RG_OFFSETS, false));
+    T_HIP(hipGetLastError());
+    T_HIP(hipMemcpyAsync(h_off, d_off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (n_ctg) T_HIP(hipMemcpyAsync(h_first, d_first, n_ctg * 4, hipMemcpyDeviceToHost, st));
+    T_HIP(hipStreamSynchronize(st));
+    C.n_kept = h_off[n_ctg];
+    if (C.n_kept > 0xfffffff0ull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 16 kept ranges");
+    C.ran = true;
+    if (!order) return consume(C, stage);            // a size query: nothing is gathered, so nothing is sorted
+    T_HIP(stage(RG_ORDER, true));
+    if (C.n_kept) T_HIP(rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, line_bits + ctg_bits, st));
+    T_HIP(stage(RG_ORDER, false));
+    if (C.n_kept) {
+        C.g.key = d_key2;
+        C.g.line_mask = (1ull << line_bits) - 1ull;
+        C.g.qs = d_qs;
+        C.g.qe = d_qe;
+        C.g.n_kept = C.n_kept;
+        C.g.bucket_off = d_off;
+    }
+    return consume(C, stage);
+}
+
+// the stopwatch of a loader call whose input had lines: stages [0, n) of the handle's timed pairs were recorded (an
+// input without lines leaves the stopwatch invalid, as text_front set it)
+void rg_timed(gams_gpu_t *h, int n) {
+    h->kq_used = n;
+    h->kq_staged = true;
+    h->k_valid = true;
+}
+#undef T_HIP
 
 }  // namespace
 
@@ -789,6 +1052,103 @@ int gams_gpu_anno_text(gams_gpu_t *h, gams_spans_t *sp, const gams_names_t *chr_
     j.idx_id = idx_id;
     j.idx_range = idx_range;
     return text_run(h, j, bytes, n_bytes, text, text_bytes, n_rows);
+}
+
+int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const char *bytes,
+                             uint64_t n_bytes, uint64_t *bucket_off, uint8_t *seen, int32_t *start, int32_t *end,
+                             uint32_t *line, uint64_t cap, uint64_t *n_kept) {
+    if (!h || !ctg_ix || !chr_names || (n_bytes && !bytes) || !bucket_off || !n_kept || (cap && (!start || !end || !line)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_read_range_text: null argument");
+    const std::string who = "gpu_read_range_text";
+    *n_kept = 0;
+    return rg_load(h, who, ctg_ix, chr_names, bytes, n_bytes, cap != 0, [&](const RgCols &C, auto stage) -> int {
+        for (uint64_t i = 0; i <= C.n_ctg; ++i) bucket_off[i] = C.bucket_off[i];
+        if (seen)
+            for (uint64_t i = 0; i < C.n_ctg; ++i) seen[i] = C.first[i] != UINT32_MAX;
+        *n_kept = C.n_kept;
+        if (cap == 0 || C.n_kept == 0) {
+            if (C.ran) rg_timed(h, cap ? RG_GATHER : RG_ORDER);
+            return GAMS_OK;
+        }
+        if (cap < C.n_kept) return gams_fail(h, GAMS_EINVAL, who + ": cap is smaller than the kept ranges (*n_kept has them)");
+        // the three columns on the device, one read-back into pooled page-locked memory, then the caller's arrays
+        uint32_t *d_out = nullptr, *p_out = nullptr;
+        size_t d_cap = 0, p_cap = 0;
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t b_col = al(C.n_kept * 4);
+        hipError_t e = gams_pool_alloc(h, false, 3 * b_col, reinterpret_cast<void **>(&d_out), &d_cap);
+        if (e == hipSuccess) e = gams_pool_alloc(h, true, 3 * b_col, reinterpret_cast<void **>(&p_out), &p_cap);
+        if (e != hipSuccess) {
+            gams_pool_free(h, false, d_out, d_cap);
+            return gams_fail(h, e == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP, who + ": columns: " + hipGetErrorString(e));
+        }
+        RgGather g = C.g;
+        g.start = d_out;
+        g.end = d_out + b_col / 4;
+        g.line = d_out + 2 * (b_col / 4);
+        g.end_plus = 0;
+        hipStream_t st = h->compute;
+        e = stage(RG_GATHER, true);
+        hipLaunchKernelGGL(rg_gather_kernel, dim3((unsigned)((C.n_kept + 255) / 256)), dim3(256), 0, st, g);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = stage(RG_GATHER, false);
+        if (e == hipSuccess) e = hipMemcpyAsync(p_out, d_out, 3 * b_col, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        (void)hipStreamSynchronize(st);
+        if (e == hipSuccess) {
+            memcpy(start, p_out, C.n_kept * 4);
+            memcpy(end, p_out + b_col / 4, C.n_kept * 4);
+            memcpy(line, p_out + 2 * (b_col / 4), C.n_kept * 4);
+        }
+        gams_pool_free(h, false, d_out, d_cap);
+        gams_pool_free(h, true, p_out, p_cap);
+        if (e != hipSuccess) return gams_fail(h, GAMS_EHIP, who + ": columns: " + hipGetErrorString(e));
+        rg_timed(h, RG_GATHER + 1);
+        return GAMS_OK;
+    });
+}
+
+int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const char *bytes,
+                                 uint64_t n_bytes, gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept) {
+    if (!h || !ctg_ix || !chr_names || (n_bytes && !bytes) || !rg_ix || (ctg_ix->m && !rg_group) || !n_kept)
+        return gams_fail(h, GAMS_EINVAL, "index_create_range_text: null argument");
+    const std::string who = "index_create_range_text";
+    *rg_ix = nullptr;
+    *n_kept = 0;
+    return rg_load(h, who, ctg_ix, chr_names, bytes, n_bytes, true, [&](const RgCols &C, auto stage) -> int {
+        uint32_t max_n = 0;
+        for (uint64_t i = 0; i < C.n_ctg; ++i)
+            max_n = std::max<uint32_t>(max_n, (uint32_t)(C.bucket_off[i + 1] - C.bucket_off[i]));
+        IndexBuild B;
+        const int rc = gams_index_build_begin(h, (uint32_t)C.n_ctg, C.n_kept, &B);
+        if (rc != GAMS_OK) return rc;
+        hipStream_t st = h->compute;
+        hipError_t e = stage(RG_GATHER, true);
+        if (C.n_kept) {
+            RgGather g = C.g;
+            g.start = B.d_starts_in;
+            g.end = B.d_stops_in;            // [start, end + 1) (redis.rs:291-294)
+            g.line = nullptr;
+            g.end_plus = 1;
+            g.off32 = B.d_off32;
+            g.n_off = C.n_ctg + 1;
+            const uint64_t lanes = std::max<uint64_t>(C.n_kept, g.n_off);
+            hipLaunchKernelGGL(rg_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, g);
+            if (e == hipSuccess) e = hipGetLastError();
+        } else if (e == hipSuccess) {
+            e = hipMemsetAsync(B.d_off32, 0, (C.n_ctg + 1) * 4, st);   // every group empty
+        }
+        if (e == hipSuccess) e = stage(RG_GATHER, false);
+        if (e == hipSuccess) e = stage(RG_BUILD, true);
+        if (e != hipSuccess) return gams_index_build_fail(h, &B, e, "range text columns");
+        // the stage's closing event goes in behind the builder's last kernel, before its host wait
+        const int rb = gams_index_build_run(h, &B, max_n, rg_ix, h->kq[(size_t)RG_BUILD].second);
+        if (rb != GAMS_OK) return rb;
+        for (uint64_t i = 0; i < C.n_ctg; ++i) rg_group[i] = C.first[i] != UINT32_MAX ? (uint32_t)i : UINT32_MAX;
+        *n_kept = C.n_kept;
+        if (C.ran) rg_timed(h, RG_STAGES);
+        return GAMS_OK;
+    });
 }
 
 }  // extern "C"

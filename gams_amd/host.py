@@ -125,6 +125,24 @@ def load():
     L.gams_host_anno_text.restype = C.c_void_p
     L.gams_host_anno_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_char_p, C.c_uint64,
                                       C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.gams_host_locate_rg.restype = C.c_void_p
+    L.gams_host_locate_rg.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
+    L.gams_host_locate_text_rg.restype = C.c_void_p
+    L.gams_host_locate_text_rg.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_uint64, C.c_int,
+                                           C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_rg_load.restype = C.c_int64
+    L.gams_host_rg_load.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_uint64, C.c_int]
+    L.gams_host_read_range_text.restype = C.c_int
+    L.gams_host_read_range_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_uint64,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.gams_host_read_range_text_get.restype = None
+    L.gams_host_read_range_text_get.argtypes = [C.c_void_p] * 5
+    L.gams_host_sw_actions_rg.restype = C.c_void_p
+    L.gams_host_sw_actions_rg.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
+                                          sp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p, C.c_uint64]
+    L.gams_host_sw_multi_actions_rg.restype = C.c_void_p
+    L.gams_host_sw_multi_actions_rg.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p,
+                                                C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p, C.c_uint64]
     L.gams_host_last_operator_device.restype = C.c_int
     L.gams_host_last_operator_device.argtypes = []
     L.gams_host_fmt_prop4.restype = C.c_void_p
@@ -266,9 +284,21 @@ def _rg_lines(rg_records):
     return "\n".join(f"{c}\t{r}" for c, r in rg_records).encode()
 
 
-def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_records=()):
+def _one_rg_source(rg_records, rg_data):
+    """rg_records and rg_data (the bytes of an rg file) are two forms of one argument"""
+    if rg_data is not None and len(rg_records):
+        raise ValueError("rg_records and rg_data are mutually exclusive: give the rg: records or the bytes of an rg file")
+    return None if rg_data is None else bytes(rg_data)
+
+
+def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None):
     """features: list of (feature_id, start, end).  actions: names of `gams sw -a` (gc, count, gibbs);
-    rg_records: (ctg_id, range string) of the rg: records, the idx:rg: source of `count`."""
+    rg_records: (ctg_id, range string) of the rg: records, the idx:rg: source of `count`; or rg_data: the bytes of an
+    rg file, loaded on the device against THIS ctg alone.  read_range over the whole ctg table gives a range that spans
+    two ctgs to the first of them; located against one ctg it falls to that ctg, and the line drop-first swallows can
+    change.  Ranges inside one ctg (the rule: SNPs, peaks) give the same counts either way; where ranges may cross
+    ctgs use sw_multi with every ctg, or rg_records from read_range over the table."""
+    rg_data = _one_rg_source(rg_records, rg_data)
     mask = sw_actions(actions)
     nf = len(features)
     fid = (C.c_char_p * max(nf, 1))(*[f[0].encode() for f in features])
@@ -276,6 +306,10 @@ def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_reco
     fe = np.array([f[2] for f in features], np.int32)
     seq = np.ascontiguousarray(np.frombuffer(ctg["seq"], np.uint8) if not isinstance(ctg["seq"], np.ndarray)
                                else ctg["seq"])
+    if rg_data is not None:
+        return _take(load().gams_host_sw_actions_rg(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
+                                                    ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data,
+                                                    fe.ctypes.data, size, mx, resize, mask, rg_data, len(rg_data)))
     if mask == _lib.SW_GC and not rg_records:
         return _take(load().gams_host_sw(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
                                          ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data, fe.ctypes.data,
@@ -285,9 +319,14 @@ def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_reco
                                              size, mx, resize, mask, _rg_lines(rg_records)))
 
 
-def locate(eng, ctgs, rgs, count=False, rg_records=()):
-    """rgs: list of range strings; rg_records: list of (ctg_id, range string) for --count."""
+def locate(eng, ctgs, rgs, count=False, rg_records=(), rg_data=None):
+    """rgs: list of range strings; for --count rg_records: list of (ctg_id, range string), or rg_data: the bytes of an
+    rg file, loaded on the device."""
+    rg_data = _one_rg_source(rg_records, rg_data)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    if rg_data is not None:
+        return _take(load().gams_host_locate_rg(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data,
+                                                "\n".join(rgs).encode(), int(count), rg_data, len(rg_data)))
     rg_lines = "\n".join(f"{c}\t{r}" for c, r in rg_records)
     return _take(load().gams_host_locate(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data,
                                          "\n".join(rgs).encode(), int(count), rg_lines.encode()))
@@ -307,10 +346,16 @@ def anno(eng, ctgs, runlists, lines, header=False, prefix="", idx_id=1, idx_rang
                                        "\n".join(lines).encode(), int(header), prefix.encode(), idx_id, idx_range))
 
 
-def locate_text(eng, ctgs, data, count=False, rg_records=()):
+def locate_text(eng, ctgs, data, count=False, rg_records=(), rg_data=None):
     """`locate -f` / `locate --count` over the bytes of the input file (text in, text out on the device; the array
-    path where the device refuses).  Returns the rows as bytes; rg_records as for locate()."""
+    path where the device refuses).  Returns the rows as bytes; rg_records / rg_data as for locate()."""
+    rg_data = _one_rg_source(rg_records, rg_data)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    if rg_data is not None:
+        out_len = C.c_uint64()
+        return _take_bytes(load().gams_host_locate_text_rg(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, data,
+                                                           len(data), int(count), rg_data, len(rg_data),
+                                                           C.byref(out_len)), out_len)
     rg_lines = "\n".join(f"{c}\t{r}" for c, r in rg_records)
     out_len = C.c_uint64()
     return _take_bytes(load().gams_host_locate_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, data, len(data),
@@ -360,6 +405,36 @@ def read_range(eng, ctgs, lines):
     return [tuple(r.split("\t")) for r in out.splitlines()]
 
 
+def read_range_text(eng, ctgs, data):
+    """read_range over the bytes of an rg file, bucketed on the device (the host's passes where the device refuses):
+    dict(ids = the ctg id of every bucket in ctg-id order, empty buckets included; off = n_buckets + 1 offsets;
+    start, end, line = the kept ranges of bucket k at [off[k], off[k + 1]) in file order, line the 0-based line
+    number) as numpy arrays."""
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    L = load()
+    nb, nk = C.c_uint64(), C.c_uint64()
+    _check_rc(L.gams_host_read_range_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, bytes(data), len(data),
+                                          C.byref(nb), C.byref(nk)))
+    which = np.zeros(max(nb.value, 1), np.uint32)
+    off = np.zeros(nb.value + 1, np.uint64)
+    start, end = np.zeros(max(nk.value, 1), np.int32), np.zeros(max(nk.value, 1), np.int32)
+    line = np.zeros(max(nk.value, 1), np.uint32)
+    L.gams_host_read_range_text_get(which.ctypes.data, off.ctypes.data, start.ctypes.data, end.ctypes.data, line.ctypes.data)
+    return dict(ids=[ctgs[i]["id"] for i in which[:nb.value]], off=off, start=start[:nk.value], end=end[:nk.value],
+                line=line[:nk.value])
+
+
+def rg_load(eng, ctgs, data, text_path=True):
+    """Builds the rg index of an rg file's bytes over `ctgs` and drops it: a timing entry.  text_path: on the device
+    (Locator::set_rg_index_text), else read_range + set_rg_index on the host's lines.  Returns the ctgs with a group;
+    last_operator_ms() has the ms of the load, last_operator_device() the path that built it."""
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    got = load().gams_host_rg_load(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, bytes(data), len(data),
+                                   int(text_path))
+    _check_rc(0 if got >= 0 else -1)
+    return int(got)
+
+
 def decode_gz(blob):
     n = C.c_uint64()
     p = load().gams_host_decode_gz(blob, len(blob), C.byref(n))
@@ -388,9 +463,10 @@ def loader_records(eng, ctgs, lines, tag=None):
     return [tuple(r.split("\t", 1)) for r in out.splitlines()]
 
 
-def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actions=("gc",), rg_records=()):
-    """`gams sw` over several handles; features_per_ctg[i] = list of (id, start, end) of ctgs[i]; actions and
-    rg_records as for sw()."""
+def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None):
+    """`gams sw` over several handles; features_per_ctg[i] = list of (id, start, end) of ctgs[i]; actions,
+    rg_records and rg_data as for sw()."""
+    rg_data = _one_rg_source(rg_records, rg_data)
     mask = sw_actions(actions)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
     bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
@@ -398,6 +474,10 @@ def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actio
     seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     rows = "\n".join(f"{i}\t{fid}\t{s}\t{e}" for i, fl in enumerate(features_per_ctg) for fid, s, e in fl)
+    if rg_data is not None:
+        return _take(load().gams_host_sw_multi_actions_rg(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data,
+                                                          seqs, rows.encode(), size, mx, resize, mask, rg_data,
+                                                          len(rg_data)))
     if mask == _lib.SW_GC and not rg_records:
         return _take(load().gams_host_sw_multi(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
                                                rows.encode(), size, mx, resize))

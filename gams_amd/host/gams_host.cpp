@@ -16,6 +16,7 @@
 #include <memory>
 #include <numeric>
 #include <queue>
+#include <set>
 #include <thread>
 
 #include <dlfcn.h>
@@ -785,11 +786,20 @@ void run_shares(uint32_t n, F fn) {
 
 }  // namespace
 
+// sw_proc_ctgs with the ctg table an rg file is located in given apart from the ctgs to process (NULL: those)
+static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                                              const std::vector<std::vector<Feature>> &features, const SwArgs &a,
+                                              uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
+                                              double *index_ms, const char *rg_bytes, size_t rg_n,
+                                              const std::vector<Ctg> *located_in);
+
 std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &handles, const std::vector<Ctg> &ctgs,
                                             const std::vector<const uint8_t *> &seqs,
                                             const std::vector<std::vector<Feature>> &features, const SwArgs &a,
-                                            const std::map<std::string, std::vector<Range>> *rgs, double *index_ms) {
+                                            const std::map<std::string, std::vector<Range>> *rgs, double *index_ms,
+                                            const char *rg_bytes, size_t rg_n) {
     if (handles.empty()) throw Error(GAMS_EINVAL, "sw_proc_ctgs_multi: no handles");
+    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs_multi: ctgs / seqs / features size mismatch");
     std::vector<uint64_t> weight(ctgs.size());
@@ -809,7 +819,8 @@ std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &han
                 df.push_back(features[c]);
                 where.push_back(c);
             }
-        std::vector<std::string> rows = sw_proc_ctgs(handles[d], dc, ds, df, a, 256ull << 20, rgs, &ix_ms[d]);
+        std::vector<std::string> rows =
+            sw_proc_ctgs_located(handles[d], dc, ds, df, a, 256ull << 20, rgs, &ix_ms[d], rg_bytes, rg_n, &ctgs);
         for (size_t k = 0; k < where.size(); ++k) out[where[k]] = std::move(rows[k]);
     });
     if (index_ms) *index_ms = *std::max_element(ix_ms.begin(), ix_ms.end());
@@ -1031,20 +1042,42 @@ std::string sw_format_rows(const gams_sw_row_t *rows, uint64_t nrows, const Ctg 
 // idx:rg: (redis.rs:288-299) for the ctgs of one sw call that have features: one group per distinct ctg id that `rgs`
 // has an entry for; group[c] = the group of ctgs[c], UINT32_MAX (count 0) for a ctg `rgs` lacks, which is reported once
 // ("{ctg} not found in idx", utils.rs:30).  Intervals as Locator::set_rg_index stores them: [start, end + 1).
+// From the bytes of an rg file instead (rg_bytes): the index and the groups are those of a Locator over `located_in`
+// that loaded the file (Locator::set_rg_index_text); the Locator owns the index.
 struct RgIndex {
     gams_gpu_t *h;
     gams_index_t *ix = nullptr;
+    std::unique_ptr<Locator> loc;
     std::vector<uint32_t> group;
     explicit RgIndex(gams_gpu_t *hh) : h(hh) {}
     ~RgIndex() {
-        if (ix) gams_index_destroy(h, ix);
+        if (ix && !loc) gams_index_destroy(h, ix);
     }
 };
 void sw_rg_index(RgIndex &out, const std::vector<Ctg> &ctgs, const std::vector<std::vector<Feature>> &features,
-                 const std::map<std::string, std::vector<Range>> *rgs, double *index_ms) {
-    if (!rgs) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
+                 const std::map<std::string, std::vector<Range>> *rgs, double *index_ms, const char *rg_bytes = nullptr,
+                 size_t rg_n = 0, const std::vector<Ctg> *located_in = nullptr) {
+    if (!rgs && !rg_bytes) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
     const auto t0 = std::chrono::steady_clock::now();
     out.group.assign(ctgs.size(), UINT32_MAX);
+    if (rg_bytes) {
+        std::vector<Ctg> table;                                          // a ctg given twice is one ctg of the table
+        std::set<std::string> ids;
+        for (const Ctg &c : located_in ? *located_in : ctgs)
+            if (ids.insert(c.id).second) table.push_back(c);
+        out.loc.reset(new Locator(out.h, table));
+        out.loc->set_rg_index_text(rg_bytes, rg_n);
+        out.ix = out.loc->rg_index();
+        std::set<std::string> told;
+        for (size_t c = 0; c < ctgs.size(); ++c) {
+            if (features[c].empty()) continue;
+            out.group[c] = out.loc->rg_group_of(ctgs[c].id);
+            if (out.group[c] == UINT32_MAX && told.insert(ctgs[c].id).second)
+                fprintf(stderr, "%s not found in idx\n", ctgs[c].id.c_str());
+        }
+        if (index_ms) *index_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return;
+    }
     std::map<std::string, uint32_t> seen;
     std::vector<uint64_t> off{0};
     std::vector<uint32_t> st, sp;
@@ -1075,7 +1108,9 @@ void sw_rg_index(RgIndex &out, const std::vector<Ctg> &ctgs, const std::vector<s
 }  // namespace
 
 std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const std::vector<Feature> &features,
-                        const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs) {
+                        const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes,
+                        size_t rg_n) {
+    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     const uint32_t nf = (uint32_t)features.size();
     if (nf == 0) return std::string();
     uint32_t len = (uint32_t)(ctg.chr_end - ctg.chr_start + 1);
@@ -1096,7 +1131,7 @@ std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const
     if (!(a.actions & GAMS_SW_COUNT)) return sw_format_rows(rows.data(), nrows, ctg, features, 8, a.actions);
     // rg_count through the array entry (and this host formatter), the path sw_proc_ctgs falls back to
     RgIndex rx(h);
-    sw_rg_index(rx, std::vector<Ctg>{ctg}, std::vector<std::vector<Feature>>{features}, rgs, nullptr);
+    sw_rg_index(rx, std::vector<Ctg>{ctg}, std::vector<std::vector<Feature>>{features}, rgs, nullptr, rg_bytes, rg_n);
     const uint32_t zero = 0;
     const uint64_t feat_off[2] = {0, nf};
     std::vector<int32_t> cnt(nrows ? nrows : 1);
@@ -1111,7 +1146,16 @@ std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const
 std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                                       const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                       uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
-                                      double *index_ms) {
+                                      double *index_ms, const char *rg_bytes, size_t rg_n) {
+    return sw_proc_ctgs_located(h, ctgs, seqs, features, a, batch_bytes, rgs, index_ms, rg_bytes, rg_n, nullptr);
+}
+
+static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                                              const std::vector<std::vector<Feature>> &features, const SwArgs &a,
+                                              uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
+                                              double *index_ms, const char *rg_bytes, size_t rg_n,
+                                              const std::vector<Ctg> *located_in) {
+    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs: ctgs / seqs / features size mismatch");
     std::vector<std::string> out(ctgs.size());
@@ -1120,7 +1164,7 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
         if (!features[c].empty()) todo.push_back(c);
     const bool do_count = (a.actions & GAMS_SW_COUNT) != 0;
     RgIndex rx(h);                                                      // -a count: the rgs of this call's ctgs, once
-    if (do_count && !todo.empty()) sw_rg_index(rx, ctgs, features, rgs, index_ms);
+    if (do_count && !todo.empty()) sw_rg_index(rx, ctgs, features, rgs, index_ms, rg_bytes, rg_n, located_in);
     for (size_t b = 0; b < todo.size();) {
         uint64_t bytes = 0;
         size_t e = b;
@@ -1279,6 +1323,31 @@ void Locator::set_rg_index(const std::map<std::string, std::vector<Range>> &rg_o
         off.push_back(st.size());
     }
     check(h_, gams_index_create(h_, g, off.data(), st.data(), sp.data(), &rg_ix_));
+}
+
+uint32_t Locator::rg_group_of(const std::string &ctg_id) const {
+    auto it = rg_group_.find(ctg_id);
+    return it == rg_group_.end() ? UINT32_MAX : it->second;
+}
+
+void Locator::set_rg_index_text(const char *bytes, size_t n, bool *device) {
+    if (device) *device = false;
+    text_tables();
+    gams_index_t *ix = nullptr;
+    std::vector<uint32_t> group(std::max<size_t>(ctgs_.size(), 1), UINT32_MAX);
+    uint64_t kept = 0;
+    const int rc = gams_index_create_range_text(h_, ctg_ix_, chr_names_, bytes, n, &ix, group.data(), &kept);
+    if (rc == GAMS_EUNSUPPORTED) {                                       // the host passes over the lines
+        set_rg_index(read_range(*this, text_lines(bytes, n)));
+        return;
+    }
+    check(h_, rc);
+    if (rg_ix_) gams_index_destroy(h_, rg_ix_);
+    rg_ix_ = ix;
+    rg_group_.clear();
+    for (size_t i = 0; i < ctgs_.size(); ++i)
+        if (group[i] != UINT32_MAX) rg_group_[ctgs_[i].id] = group[i];
+    if (device) *device = true;
 }
 
 std::vector<std::string> Locator::find(const std::vector<Range> &rgs) {
@@ -1513,6 +1582,75 @@ std::map<std::string, std::vector<Range>> read_range(Locator &loc, const std::ve
             it->second.push_back(valid[k]);                             // and_modify(push)
     }
     return ranges_of;
+}
+
+RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device) {
+    if (device) *device = false;
+    loc.text_tables();
+    const size_t n_ctg = loc.ctgs_.size();
+    std::vector<uint64_t> off(n_ctg + 1, 0);
+    std::vector<uint8_t> seen(std::max<size_t>(n_ctg, 1), 0);
+    std::vector<int32_t> st, en;
+    std::vector<uint32_t> ln;
+    // one call: the file's lines bound the kept ranges, so the columns are sized by the newlines
+    uint64_t kept = 0;
+    const size_t cap = (size_t)std::count(bytes, bytes + n, '\n') + 1;
+    st.resize(cap);
+    en.resize(cap);
+    ln.resize(cap);
+    const int rc = gams_gpu_read_range_text(loc.h_, loc.ctg_ix_, loc.chr_names_, bytes, n, off.data(), seen.data(), st.data(),
+                                            en.data(), ln.data(), cap, &kept);
+    if (rc == GAMS_OK) {
+        st.resize(kept);
+        en.resize(kept);
+        ln.resize(kept);
+    }
+    if (rc == GAMS_EUNSUPPORTED) {
+        // utils.rs:39-67 on the host, by ctg slot: the lines whole, located, the first of every ctg dropped
+        const std::vector<std::string> lines = text_lines(bytes, n);
+        std::vector<Range> valid;
+        std::vector<uint32_t> src;
+        for (size_t i = 0; i < lines.size(); ++i) {
+            Range r = Range::from_str(lines[i]);
+            if (!r.valid) continue;
+            valid.push_back(r);
+            src.push_back((uint32_t)i);
+        }
+        const std::vector<std::string> ids = loc.find(valid);
+        std::vector<std::vector<size_t>> of(n_ctg);
+        std::fill(seen.begin(), seen.end(), 0);
+        for (size_t k = 0; k < valid.size(); ++k) {
+            if (ids[k].empty()) continue;
+            const uint32_t c = loc.ctg_slot_.at(ids[k]);
+            if (seen[c]) of[c].push_back(k);
+            seen[c] = 1;
+        }
+        st.clear(), en.clear(), ln.clear();
+        for (size_t c = 0; c < n_ctg; ++c) {
+            for (size_t k : of[c]) {
+                st.push_back(valid[k].start);
+                en.push_back(valid[k].end);
+                ln.push_back(src[k]);
+            }
+            off[c + 1] = st.size();
+        }
+    } else {
+        check(loc.h_, rc);
+        if (device) *device = true;
+    }
+    // the buckets in ctg-id order (BTreeMap<String, _>), empty ones included
+    RangeBuckets out;
+    out.off.push_back(0);
+    for (auto &kv : loc.ctg_slot_) {
+        const uint32_t c = kv.second;
+        if (!seen[c]) continue;
+        out.ids.push_back(kv.first);
+        out.start.insert(out.start.end(), st.begin() + off[c], st.begin() + off[c + 1]);
+        out.end.insert(out.end.end(), en.begin() + off[c], en.begin() + off[c + 1]);
+        out.line.insert(out.line.end(), ln.begin() + off[c], ln.begin() + off[c + 1]);
+        out.off.push_back(out.start.size());
+    }
+    return out;
 }
 
 std::map<std::string, std::vector<std::pair<Range, std::string>>> read_peak(Locator &loc,

@@ -131,8 +131,15 @@ void cover_multi(const std::vector<gams_gpu_t *> &handles, uint32_t n_groups, co
 // sw.rs:108-194.  With GAMS_SW_COUNT in a.actions, `rgs` (what read_range returns: the rg ranges of each ctg id) is
 // the idx:rg: source; each call builds the device index of its own ctgs once.  A ctg without an entry in `rgs` counts
 // 0 and is reported once on stderr ("{ctg} not found in idx", utils.rs:30 -- the reference says it once per window).
+// Instead of `rgs` the three operators take the bytes of ONE rg file (rg_bytes != NULL, rg_n bytes): a Locator over the
+// call's ctgs loads it on the device (Locator::set_rg_index_text), and a ctg with features and no bucket in the file is
+// reported the same way.  Giving both sources is GAMS_EINVAL.  The file is located among the ctgs of the CALL: sw_proc_ctg
+// sees one ctg, so a range that spans a ctg boundary, which the whole table gives to the ctg in front, lands in this
+// ctg's bucket (and may be the line drop-first swallows); a host whose ranges can cross ctgs calls sw_proc_ctgs /
+// sw_proc_ctgs_multi with every ctg, or keeps `rgs` from a read_range over the whole table.
 std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const std::vector<Feature> &features,
-                        const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr);
+                        const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                        const char *rg_bytes = nullptr, size_t rg_n = 0);
 // several ctgs on one handle: one seqset, one gams_gpu_sw_batch call and one readback per batch of
 // <= batch_bytes bases; rows returned per ctg in the order given ("" for a ctg without features).
 // index_ms (may be NULL) receives the ms of the rg index build (-a count).
@@ -140,15 +147,26 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
                                       const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                       uint64_t batch_bytes = 256ull << 20,
                                       const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                                      double *index_ms = nullptr);
+                                      double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0);
 // `gams sw --parallel` over several devices: ctgs split over the handles by LPT on their feature
 // counts, one host thread per handle, rows returned per ctg in the order given.  Each handle indexes the rgs of the
-// ctgs it was given; index_ms = the longest of those builds.
+// ctgs it was given; index_ms = the longest of those builds.  With rg_bytes every handle loads the file against ALL ctgs
+// of the call (a range is located among all of them, whichever handle owns its ctg).
 std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &handles, const std::vector<Ctg> &ctgs,
                                             const std::vector<const uint8_t *> &seqs,
                                             const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                             const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                                            double *index_ms = nullptr);
+                                            double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0);
+
+// what read_range_text returns: the buckets of read_range as arrays.  Bucket k belongs to ctg ids[k] (ctg-id order, the
+// order of the reference's BTreeMap; a ctg with one located line has a bucket, and it is empty) and holds
+// start/end/line[off[k] .. off[k+1]) in file order; line = the 0-based line number of the range in the file.
+struct RangeBuckets {
+    std::vector<std::string> ids;
+    std::vector<uint64_t> off;            // ids.size() + 1
+    std::vector<int32_t> start, end;
+    std::vector<uint32_t> line;
+};
 
 // idx:ctg: / idx:rg: on the device (redis.rs:236-324) + the locate loop (locate.rs:111-141)
 class Locator {
@@ -157,6 +175,14 @@ public:
     ~Locator();
     // idx:rg:{ctg}: ranges already bucketed per ctg (rg loader, utils.rs:39-67)
     void set_rg_index(const std::map<std::string, std::vector<Range>> &rg_of_ctg);
+    // idx:rg: from the bytes of ONE rg file, made on the device (gams_index_create_range_text): what
+    // set_rg_index(read_range(*this, text_lines(bytes, n))) builds, which is also what runs where the device refuses
+    // (GAMS_EUNSUPPORTED); *device (may be NULL) says which path built the index.  Only ctgs with a located line get a
+    // group, as in the reference's map.
+    void set_rg_index_text(const char *bytes, size_t n, bool *device = nullptr);
+    // the rg index (NULL before one is set; owned by the Locator) and the group of a ctg id in it (UINT32_MAX: none)
+    gams_index_t *rg_index() const { return rg_ix_; }
+    uint32_t rg_group_of(const std::string &ctg_id) const;
     // find_one_idx for every range; "" when not located (utils.rs:7-22)
     std::vector<std::string> find(const std::vector<Range> &rgs);
     // locate output: "{rg}\t{ctg_id}\n" or with count "{rg}\t{count}\n" (locate.rs:135-140)
@@ -171,6 +197,7 @@ public:
     // locate --seq (locate.rs:124-134): ">{rg}\n{bases}\n"; seq_of maps ctg id -> gunzipped seq
     std::string locate_seq(const std::vector<std::string> &rgs, const std::map<std::string, std::string> &seq_of);
     const Ctg *ctg(const std::string &id) const;
+    friend RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device);
 
 private:
     gams_gpu_t *h_;
@@ -199,6 +226,9 @@ std::string encode_gz(const uint8_t *bytes, size_t n);
 // the reference's quirk: `.entry(k).and_modify(push).or_default()` only creates the bucket for
 // the first range of a ctg, so that range is dropped (tests/cli.rs:250,301: 79 lines -> 69).
 std::map<std::string, std::vector<Range>> read_range(Locator &loc, const std::vector<std::string> &lines);
+// the same over the bytes of the file, bucketed on the device (gams_gpu_read_range_text), for hosts that need the
+// records themselves; where the device refuses, the lines are parsed and bucketed here.  *device as in locate_text.
+RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device = nullptr);
 
 // src/libs/data.rs:30-43
 struct Peak {

@@ -390,6 +390,124 @@ char *gams_host_locate_text(gams_gpu_t *h, uint32_t n, const char *const *ids, c
     });
 }
 
+// ---- the rg index from the bytes of an rg file (rg_data, rg_n: not NUL-terminated; Locator::set_rg_index_text) ----
+// gams_host_locate with the rg index loaded from the file's bytes instead of rg_lines
+char *gams_host_locate_rg(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                          const int32_t *starts, const int32_t *ends, const char *rgs, int is_count, const char *rg_data,
+                          uint64_t rg_n) {
+    return guarded([&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        if (is_count) loc.set_rg_index_text(rg_data ? rg_data : "", (size_t)rg_n);
+        const std::vector<std::string> lines = split_lines(rgs);
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = loc.locate(lines, is_count != 0);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return out;
+    });
+}
+
+// gams_host_locate_text likewise
+char *gams_host_locate_text_rg(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                               const int32_t *starts, const int32_t *ends, const char *bytes, uint64_t n_bytes,
+                               int is_count, const char *rg_data, uint64_t rg_n, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        if (is_count) loc.set_rg_index_text(rg_data ? rg_data : "", (size_t)rg_n);
+        loc.text_tables();
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = loc.locate_text(bytes, (size_t)n_bytes, is_count != 0, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        return out;
+    });
+}
+
+// Loads the rg index of a file over the ctg table and reports the ms of the load itself in gams_host_last_operator_ms:
+// text_path != 0 through Locator::set_rg_index_text (from the bytes in host memory to the finished index), else through
+// set_rg_index(read_range(text_lines(bytes))), the passes over strings.  gams_host_last_operator_device says which path
+// built it.  Returns the number of ctgs with a group, -1 on error.
+int64_t gams_host_rg_load(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                          const int32_t *ends, const char *rg_data, uint64_t rg_n, int text_path) {
+    return guard((int64_t)-1, [&]() -> int64_t {
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        gams::Locator loc(h, cv);
+        loc.text_tables();
+        bool dev = false;
+        const char *data = rg_data ? rg_data : "";
+        const auto t0 = std::chrono::steady_clock::now();
+        if (text_path)
+            loc.set_rg_index_text(data, (size_t)rg_n, &dev);
+        else
+            loc.set_rg_index(gams::read_range(loc, gams::text_lines(data, (size_t)rg_n)));
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        int64_t groups = 0;
+        for (const gams::Ctg &c : cv) groups += loc.rg_group_of(c.id) != UINT32_MAX;
+        return groups;
+    });
+}
+
+// gams::read_range_text over the ctg table: the call keeps the buckets (per thread) and reports their sizes,
+// gams_host_read_range_text_get copies them out: bucket_ctg[k] = the position in ids[] of bucket k's ctg, bucket_off
+// n_buckets + 1 offsets, start / end / line n_kept entries each.  Returns 0, or -1 with the message in
+// gams_host_last_error().
+namespace {
+thread_local gams::RangeBuckets g_buckets;
+thread_local std::vector<uint32_t> g_bucket_ctg;
+}  // namespace
+int gams_host_read_range_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                              const int32_t *starts, const int32_t *ends, const char *data, uint64_t n_bytes,
+                              uint64_t *n_buckets, uint64_t *n_kept) {
+    return guard(-1, [&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        bool dev = false;
+        g_buckets = gams::read_range_text(loc, data ? data : "", (size_t)n_bytes, &dev);
+        g_operator_device = dev ? 1 : 0;
+        std::map<std::string, uint32_t> pos;
+        for (uint32_t i = 0; i < n; ++i) pos[ids[i]] = i;
+        g_bucket_ctg.clear();
+        for (const std::string &id : g_buckets.ids) g_bucket_ctg.push_back(pos.at(id));
+        *n_buckets = g_buckets.ids.size();
+        *n_kept = g_buckets.start.size();
+        return 0;
+    });
+}
+void gams_host_read_range_text_get(uint32_t *bucket_ctg, uint64_t *bucket_off, int32_t *start, int32_t *end, uint32_t *line) {
+    std::copy(g_bucket_ctg.begin(), g_bucket_ctg.end(), bucket_ctg);
+    std::copy(g_buckets.off.begin(), g_buckets.off.end(), bucket_off);
+    std::copy(g_buckets.start.begin(), g_buckets.start.end(), start);
+    std::copy(g_buckets.end.begin(), g_buckets.end.end(), end);
+    std::copy(g_buckets.line.begin(), g_buckets.line.end(), line);
+}
+
+// gams_host_sw_actions / gams_host_sw_multi_actions with the bytes of an rg file as the idx:rg: source
+char *gams_host_sw_actions_rg(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
+                              const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
+                              const int32_t *fe, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                              const char *rg_data, uint64_t rg_n) {
+    return guarded([&] {
+        const char *ids[1] = {ctg_id}, *chrs[1] = {chr};
+        gams::Ctg c = make_ctgs(1, ids, chrs, &chr_start, &chr_end)[0];
+        std::vector<gams::Feature> f(nf);
+        for (uint32_t i = 0; i < nf; ++i) f[i] = gams::Feature{feature_ids[i], fs[i], fe[i]};
+        return gams::sw_proc_ctg(h, c, seq, f, sw_args(size, max, resize, actions), nullptr, rg_data ? rg_data : "",
+                                 (size_t)rg_n);
+    });
+}
+char *gams_host_sw_multi_actions_rg(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                                    const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                                    const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
+                                    int32_t resize, uint32_t actions, const char *rg_data, uint64_t rg_n) {
+    return guarded([&] {
+        return join(gams::sw_proc_ctgs_multi(std::vector<gams_gpu_t *>(handles, handles + n_handles),
+                                             make_ctgs(n, ids, chrs, starts, ends),
+                                             std::vector<const uint8_t *>(seqs, seqs + n), sw_feature_rows(n, features),
+                                             sw_args(size, max, resize, actions), nullptr, nullptr, rg_data ? rg_data : "",
+                                             (size_t)rg_n));
+    });
+}
+
 // anno over the bytes of one input file; runlists as for gams_host_anno
 char *gams_host_anno_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
                           const int32_t *starts, const int32_t *ends, const char *runlists, const char *bytes,

@@ -383,6 +383,31 @@ int gams_gpu_anno_text(gams_gpu_t *h, gams_spans_t *sp, const gams_names_t *chr_
                        const char *prefix, uint32_t idx_id, uint32_t idx_range, const char **text, uint64_t *text_bytes,
                        uint64_t *n_rows);
 
+/* ---- text in, index out: the rg loader (utils.rs:39-67 read_range, then redis.rs:288-299) ---- */
+/* The two entries below take the bytes of ONE .rg file (lines, refused bytes and the 2^32 - 1 line limit as above) and
+ * bucket its ranges per ctg the way gams::read_range does.  The WHOLE line goes through Range::from_str (utils.rs:50;
+ * unlike locate -f nothing is cut at a tab, so "I:1-100\tfoo" is invalid).  A valid line is located as gams_gpu_locate
+ * locates (group of its chromosome in chr_names, start, end) in ctg_ix; invalid lines, unknown chromosomes and
+ * unlocated lines (the point range on a ctg start among them) are skipped.  Of the located lines of a ctg the first
+ * in file order is dropped (`.entry().and_modify(push).or_default()` creates the bucket with it and pushes nothing)
+ * and the rest are kept, so a ctg with one located line has a bucket, and the bucket is empty.  Drop-first is per file:
+ * two files concatenated are not two files loaded.  Bucket / group i belongs to interval i of ctg_ix in the caller's
+ * original order (what gams_gpu_locate returns); n_ctg = the intervals of ctg_ix.  GAMS_EUNSUPPORTED also for more than
+ * 2^32 - 16 kept ranges (the limit of gams_index_create).  Zero bytes: GAMS_OK, nothing kept. */
+/* The buckets as arrays.  bucket_off has n_ctg + 1 entries; seen[i] (seen may be NULL) is 1 if ctg i had a located line,
+ * i.e. has a bucket; the kept ranges of bucket i are start/end/line[bucket_off[i] .. bucket_off[i+1]) in file order,
+ * line = the 0-based line number.  cap == 0 is the size query: bucket_off, seen and *n_kept only.  A cap smaller than
+ * *n_kept is GAMS_EINVAL (with *n_kept set).  Two calls return identical arrays. */
+int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const char *bytes,
+                             uint64_t n_bytes, uint64_t *bucket_off, uint8_t *seen, int32_t *start, int32_t *end,
+                             uint32_t *line, uint64_t cap, uint64_t *n_kept);
+/* The rg index of the file: n_ctg groups, group i = bucket i's ranges as [start, end + 1) (redis.rs:291-294), in the
+ * same canonical order gams_index_create gives the same buckets.  rg_group[i] (n_ctg entries) is i if ctg i has a
+ * bucket and UINT32_MAX otherwise: the table gams_gpu_count_text and gams_gpu_sw_text_actions take.  Destroy *rg_ix with
+ * gams_index_destroy. */
+int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const char *bytes,
+                                 uint64_t n_bytes, gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept);
+
 /* ---- gen: valid regions of a chromosome (first "next" row of SURVEY section 8f) ---- */
 /* gen.rs:86-104: bases other than A C G T a c g t are ambiguous; the valid set is their
  * complement after fill(fill-1) and excise(min_len).  Writes up to `cap` spans (1-based,
