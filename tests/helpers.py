@@ -134,6 +134,71 @@ def synth(n, seed, gc=0.4, lower=0.2, nrate=1e-4):
     return s
 
 
+GC_LETTERS, AT_LETTERS = b"GCgc", b"ATatN"
+
+
+def periodic(n, unit, letters=0):
+    """n bases whose G/C pattern is the boolean `unit` tiled: G/C positions draw from G C g c, the others from A T a t N
+    (`letters` seeds the draw).  Which letter stands where changes no count, so the window counts repeat with the unit."""
+    unit = np.asarray(unit, bool)
+    rng = np.random.default_rng(letters)
+    is_gc = np.tile(unit, n // unit.size + 1)[:n]
+    gc = np.frombuffer(GC_LETTERS, np.uint8)[rng.integers(0, len(GC_LETTERS), n)]
+    at = np.frombuffer(AT_LETTERS, np.uint8)[rng.integers(0, len(AT_LETTERS), n)]
+    return np.where(is_gc, gc, at).astype(np.uint8)
+
+
+def gc_unit(period, gc, seed):
+    """a boolean unit of `period` bases, round(period * gc) of them G/C, at seeded random places"""
+    unit = np.zeros(period, bool)
+    unit[np.random.default_rng(seed).permutation(period)[:int(round(period * gc))]] = True
+    return unit
+
+
+def lag_sums(cnt, lag):
+    """The integers the reference's z-score is made of (stat.rs:36 with :51-52), over prefix sums of the counts:
+    for every window i >= lag, S1 = sum k and S2 = sum k^2 over the counts of windows [i-1-lag, i-1) (window `lag`:
+    [0, lag)), Dn = lag*k[i] - S1 (signed) and V = lag*S2 - S1^2.  -> (i, S1, S2, Dn, V), int64 (exact below 2^63)."""
+    k = np.asarray(cnt).astype(np.int64)
+    p1 = np.concatenate(([0], np.cumsum(k)))
+    p2 = np.concatenate(([0], np.cumsum(k * k)))
+    i = np.arange(lag, k.size)
+    a = np.where(i == lag, 0, i - 1 - lag)
+    s1, s2 = p1[a + lag] - p1[a], p2[a + lag] - p2[a]
+    return i, s1, s2, lag * k[i] - s1, lag * s2 - s1 * s1
+
+
+def tie_states(cnt, lag):
+    """The plain float64 model: z = D / sqrt(lag*V/(lag-1)) with D = |lag*k - S1| for every window i >= lag.
+    -> [(z, windows)] for the distinct finite positive z, the most populous first."""
+    i, _, _, dn, v = lag_sums(cnt, lag)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.abs(dn) / np.sqrt(lag * v.astype(np.float64) / (lag - 1))
+    ok = np.isfinite(z) & (z > 0)
+    vals, inv = np.unique(z[ok], return_inverse=True)
+    out = [(float(zv), i[ok][inv == j]) for j, zv in enumerate(vals)]
+    out.sort(key=lambda t: (-t[1].size, t[0]))
+    return out
+
+
+def real_signals(cnt, lag, thr):
+    """The verdict of real arithmetic, which is what an integer decision computes: window i signals iff
+    D > thr * sqrt(lag*V/(lag-1)), for the f32 threshold the kernels are given (float64 throughout)."""
+    i, _, _, dn, v = lag_sums(cnt, lag)
+    r = float(np.float32(thr)) * np.sqrt(lag * v.astype(np.float64) / (lag - 1))
+    sig = np.zeros(np.asarray(cnt).size, np.int32)
+    sig[i] = np.where(np.abs(dn) > r, np.sign(dn), 0)
+    return sig
+
+
+KNIFE_DELTAS = (0.0, 1e-7, -1e-7, 1e-6, -1e-6, 3e-6, -3e-6, 1e-5, -1e-5, 3e-5, -3e-5)
+
+
+def knife_thresholds(z0):
+    """eleven f32 thresholds on and around the z-score z0 of one state: z0 * (1 + d)"""
+    return [float(np.float32(z0 * (1.0 + d))) for d in KNIFE_DELTAS]
+
+
 def longest_run(sig):
     """length of the longest stretch of consecutive nonzero entries"""
     nz = np.concatenate(([0], (np.asarray(sig) != 0).astype(np.int8), [0]))
