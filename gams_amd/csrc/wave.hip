@@ -44,8 +44,21 @@
 #include "wave_kernels.hpp"
 #include "wave_repair.hpp"
 #include "wave_rows.hpp"
+#include "wave_select.hpp"
 
 #include <charconv>
+
+// The instance list of wave_select.hpp as kernel pointers, a false / true pair (NT) per tuple: every wave_fast_kernel
+// and wave_fast_taper_kernel instantiation has the one signature, wave_tile_kernel the other.
+using WaveFastFn = void (*)(const WaveTile *, const uint8_t *, WaveArgs);
+using WaveTileFn = void (*)(WaveArgs);
+#define WAVE_X_PAIR(W, SIZE, STEP, LAG, NTH) \
+    {wave_fast_kernel<W, SIZE, STEP, LAG, false, NTH>, wave_fast_kernel<W, SIZE, STEP, LAG, true, NTH>},
+static const WaveFastFn kWaveFastFn[kWaveFastCount][2] = {WAVE_FAST_INSTANCES(WAVE_X_PAIR)};
+#undef WAVE_X_PAIR
+static const WaveFastFn kWaveTaperFn[2] = {wave_fast_taper_kernel<100, 10, 100, false>, wave_fast_taper_kernel<100, 10, 100, true>};
+static const WaveTileFn kWaveTileFn[2][2] = {{wave_tile_kernel<uint8_t, false>, wave_tile_kernel<uint8_t, true>},     // [k16][wide]
+                                             {wave_tile_kernel<uint16_t, false>, wave_tile_kernel<uint16_t, true>}};
 
 
 // =============================================================================
@@ -117,12 +130,9 @@ struct gams_wave_plan {
     uint32_t n_jtiles = 0;
     float *d_xtab = nullptr;      // repair: xtab[k] = k as f32 / size as f32, [size + 1] (inside arena_fixed)
     bool jac0 = false;            // repair with influence == 0: fill-forward filter + freeze guess (jac0_* kernels)
-    bool direct = false;          // halo beyond a tile: one lane per window, no tiling (wave_direct_*_kernel)
-    bool wide = false, k16 = false;
-    int fast_w = 0;               // W of wave_fast_kernel (0: generic wave_tile_kernel)
-    uint32_t tw = 0;              // windows per tile
-    uint32_t max_chunks = 0, max_win = 0;
-    size_t lds_bytes = 0;
+    WaveSelection sel;            // the tile kernel and its geometry (wave_select.hpp), made by wave_build_geometry
+    WaveFastFn fast_fn = nullptr; // ... as the pointer a pass launches: one of the two is set, neither for sel.direct
+    WaveTileFn tile_fn = nullptr;
     uint64_t total_windows = 0;
     std::vector<WaveCtgDev> ctgs;
     std::vector<WaveTile> tiles;
@@ -161,7 +171,6 @@ struct gams_wave_plan {
     uint32_t depth = 1;                         // ways in use
     uint32_t lane = 0;                          // way k runs on stream (lane + k) % kMaxWays (gams_wave_plan_set_lane)
     int taper_req = -1;                         // gams_wave_plan_set_taper: -1 auto, 0 off, 1 on
-    bool taper = false;                         // the tile table ends in W = 8 and W = 4 tiles (wave_fast_taper_kernel)
     int taper4_pct = 25, taper8_pct = 50;       // size of the two tails, % of a round of workgroup slots (gams_wave_plan_set_taper_shape)
     uint32_t queue_threads = gams_gpu::kMaxWays;   // host threads gams_wave_run_n queues from (gams_wave_plan_set_queue_threads)
     uint32_t last_way = 0;                      // way of the most recent run
@@ -172,7 +181,6 @@ struct gams_wave_plan {
     size_t h_peaks_bytes = 0;
     uint32_t tile_cap = 0, tile_cap_req = 0;
     uint32_t tw_req = 0;                        // gams_wave_plan_set_tile request (0: the library's choice)
-    uint32_t nth = 256;                         // threads per workgroup of the tile kernel (64 / 128: step-1 kernels, W = 28)
     uint32_t nth_req = 0;                       // gams_wave_plan_set_threads request (0: the library's choice)
     gams_peak_t *d_dense = nullptr;             // packed copy made by gams_wave_peaks
     uint64_t dense_cap = 0;
@@ -187,7 +195,6 @@ struct gams_wave_plan {
     bool ran = false;
     struct Launcher *launcher[gams_gpu::kMaxWays - 1] = {};   // extra queueing threads of gams_wave_run_n (made on first use)
     bool pipelined = false;       // gams_wave_plan_set_pipelined: an event per run; readers wait on it
-    bool attr_set = false;        // dynamic-LDS attribute applied for the current geometry
     float g0 = 0, g1 = 0, g2 = 0, g3 = 0;
     float sq[6] = {0, 0, 0, 0, 0, 0};   // aA, aB, gA0, gA1, gB0, gB1 (wave_squared_band)
     WaveRows *rows = nullptr;           // gams_wave_rows_setup
@@ -204,8 +211,6 @@ namespace {
 
 constexpr uint32_t kCounterRing = 128;       // one counter slot (kShards lines) per run: no per-run memset
 constexpr size_t kSlotWords = (size_t)kShards * kShardWords;
-constexpr uint32_t kMaxTileBytes = 65520;  // chunk prefix is 16 bits
-constexpr uint32_t kMaxTw = 8192;          // 2 bits/iteration in a 64-bit register
 constexpr uint32_t kOffOneGroup = 32768;   // tables up to here: wave_offsets_kernel (one workgroup, one launch)
 
 // exclusive prefix of n counts on `st`, the total and the maximum into tot[0..1]: one workgroup, or spans of
@@ -219,18 +224,6 @@ void wave_queue_offsets(hipStream_t st, const uint32_t *cnt, uint32_t n, unsigne
     hipLaunchKernelGGL(wave_offsets_sum_kernel, dim3(spans), dim3(1024), 0, st, cnt, n, off);
     hipLaunchKernelGGL(wave_offsets_base_kernel, dim3(1), dim3(1024), 0, st, n, off, tot);
     hipLaunchKernelGGL(wave_offsets_scan_kernel, dim3(spans), dim3(1024), 0, st, cnt, n, off);
-}
-
-size_t wave_lds_bytes(uint32_t max_chunks, uint32_t max_win, bool wide, bool k16) {
-    size_t b = 0;
-    const size_t mwp = (max_win + 3u) & ~1u;
-    b += mwp * (wide ? 8 : 4);                        // Q2
-    b += mwp * 4;                                     // Q1
-    b += (size_t)((max_chunks + 4) & ~1u) * 4;        // PM
-    b += 8 * 8;                                       // scratch
-    b += 132 * 4;                                     // PC
-    b += (size_t)(max_win + 8) * (k16 ? 2 : 1);       // K
-    return (b + 15) & ~(size_t)15;
 }
 
 // Guard band of the integer decision, in units of D = |n*k - S1| (see DESIGN.md
@@ -276,37 +269,11 @@ void wave_squared_band(const gams_wave_params_t &p, const float g[4], float sq[6
     sq[5] = (float)((double)g[1] / ((1.0 - gg) * sb) * hi); // gB1
 }
 
-// W of the baked instantiations of wave_fast_kernel (parameters in the instruction stream)
-// 0: the parameters are arguments; 1: size, step and lag baked into the instruction stream (BASELINE's configurations);
-// 2: size and step baked, the lag an argument (`--lag N` next to the default size: the reference's own benchmark
-// runs 100 / 5 / 200 and 100 / 20 / 50, doc/benchmark/Atha.md:55,276-280)
-int wave_baked_kind(const gams_wave_params_t &q, int w) {
-    const bool headline = q.size == 100 && q.step == 10 && q.lag == 100;   // every BASELINE step-10 config
-    const bool step1 = q.size == 100 && q.step == 1 && q.lag == 100;       // BASELINE configs[3] (GRCh38, step 1)
-    if ((headline && (w == 12 || w == 8 || w == 4)) || (step1 && (w == 28 || w == 20 || w == 12))) return 1;
-    if (q.size != 100 || q.lag + 1u > 128u * (uint32_t)w) return 0;        // at least half of the tile's slots are windows
-    if ((q.step == 5 || q.step == 10 || q.step == 20) && (w == 12 || w == 8 || w == 4)) return 2;
-    if (q.step == 1 && w == 28) return 2;
-    if ((q.step == 1 || q.step == 5) && w == 20) return 2;   // 5120 windows x 5 bases: the bytes of a W = 10 tile at step 10
-    return 0;
-}
-bool wave_is_baked(const gams_wave_params_t &q, int w) { return wave_baked_kind(q, w) != 0; }
-
-size_t wave_fast_lds_bytes(uint32_t max_chunks, uint32_t w, uint32_t lag, bool dense, uint32_t nth = 256) {
-    size_t b = (size_t)((((max_chunks + 8u) >> 1) + 16u + 3u) & ~3u) * 4;   // BM: 16 mask bits per chunk + pad
-    b += 16 * 4;                                         // scratch
-    b += (nth * w + lag + 1u + 31u) & ~15u;              // K (threads past the tile's end still read their slots)
-    b += (nth + 16) * 8;                                 // PS: block sums of the baked kernels
-    b += nth * 2;                                        // RK: ranks of phase 4b
-    if (dense) b += ((nth * w + 15u) & ~15u) + 16u;      // SG (+ the dword behind the last group, read with it)
-    return (b + 15) & ~(size_t)15;
-}
-
 void wave_fill_tiles(gams_wave_plan_t *p) {
     p->tiles.clear();
     for (uint32_t c = 0; c < p->set->n_ctg; ++c) {
         const uint32_t n = p->ctgs[c].n_win;
-        for (uint32_t w = 0; w < n; w += p->tw)
+        for (uint32_t w = 0; w < n; w += p->sel.tw)
             p->tiles.push_back(WaveTile{c, w, n, 0u, p->ctgs[c].seq_off, p->ctgs[c].win_base});
     }
 }
@@ -334,145 +301,22 @@ void wave_fill_tiles_tapered(gams_wave_plan_t *p, uint32_t slots) {
     }
 }
 
+// The plan's tile kernel, its geometry and its tile table from wave_select(); the kernel's dynamic-LDS limit is raised
+// here (the callers have set the device), so that a pass only launches.
 int wave_build_geometry(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t tw_req) {
-    const gams_wave_params_t &q = p->prm;
-    const uint64_t halo_bytes = (uint64_t)(q.lag + 1) * q.step + (uint64_t)q.size + 32;
-    p->fast_w = 0;
-    p->attr_set = false;
-    p->direct = false;
-    p->taper = false;
-    // fast kernel: 8-bit counts, 32-bit variance math with 24-bit multiplies
-    const bool fast_ok = (!p->serial || p->repair) && q.size <= 255 && q.step <= 32 && (uint64_t)q.lag * q.size <= 65535 &&
-                         (uint64_t)q.lag * q.size * q.size < (1ull << 24) && q.lag >= 2;
-    const bool step1_prm = q.size == 100 && q.step == 1 && wave_baked_kind(q, 28) != 0;
-    if (fast_ok && (tw_req == 0 || tw_req == 1024 || tw_req == 2048 || tw_req == 3072 || tw_req == 5120 ||
-                    (tw_req == 7168 && step1_prm))) {
-        static const int cand[5] = {28, 20, 12, 8, 4};
-        int pick = 0;
-        for (int w : cand) {
-            const uint64_t tw = 256ull * w;
-            if (halo_bytes + tw * q.step > kMaxTileBytes) continue;
-            if (tw_req) {
-                if (tw_req == tw) pick = w;
-                continue;
-            }
-            // Default W by the number of tiles it would give (a small genome is launch-latency
-            // bound and wants many short workgroups; a saturated chip wants the lower instruction
-            // count per window of the bigger tiles).  Measured us per pass, W = 4 / 8 / 12, one pass
-            // at a time | four in flight:
-            //   1.2 M windows   7.9 /  8.2 /  9.3  |  3.02 / 2.84 / 3.07
-            //   1.8 M           9.1 /  9.2 / 10.3  |  4.34 / 3.45 / 3.55
-            //   2.4 M          11.3 / 10.4 / 11.0  |  5.76 / 4.35 / 4.07
-            //   3.6 M          15.0 / 14.2 / 14.2  |  8.42 / 6.44 / 5.91
-            //   38 M (384 Mb)   107 /   82 /   77
-            // W = 28 / 20 for the baked step-1 kernel (3.8e8 windows: 320 us at W = 28, 334 at W = 20, 503 at
-            // W = 12 in round 1; 1.2e7 windows, less than a round of W = 28 tiles: 23.5 vs 21.0 us), otherwise
-            // only on request.
-            const uint64_t tiles = p->total_windows / tw;
-            const bool step1 = q.size == 100 && q.step == 1 && q.lag == 100;   // baked W = 20 fits 64 VGPRs
-            const bool flight = p->depth >= 2;
-            // (round 3: W = 28 tiles of ONE wave -- 64 threads, 1,691 windows at lag 100 -- from 4,096 such tiles on:
-            // 384 Mb 325 -> 285 us, 120 Mb 112 -> 100 us, 12 Mb 21.9 (W = 20) -> 21.2 us; gpurun_out/r3_ab_threads*.log)
-            const bool s1w28 = step1 || (q.size == 100 && q.step == 1 && wave_baked_kind(q, 28) == 2);
-            // (peaks only: with the dense rows the stores of a whole workgroup's windows are worth more -- 384 Mb --signal
-            // 429 us with four waves per tile, 443 with two, 464 with one; gpurun_out/r3_dense_rate2.txt)
-            const bool narrow_ok = !(p->flags & GAMS_WAVE_DENSE) && !p->serial;
-            if (pick == 0 && w == 28 && s1w28 && p->nth_req == 0 && narrow_ok && q.lag + 1u <= 32u * 28u &&
-                p->total_windows / (64u * 28u) >= 4096)
-                pick = w;
-            if (pick == 0 && w == 28 && s1w28 && tiles >= 4096)
-                pick = w;
-            if (pick == 0 && w == 20 && (step1 || (q.size == 100 && q.step == 1 && wave_baked_kind(q, 20) == 2)) && tiles >= 1024)
-                pick = w;
-            // step 5: twice the windows per byte of step 10, W = 20 amortises the per-thread work (384 Mb: 112 -> 108 us at
-            // lag 100, 131 -> 114 us at lag 200, one seqset)
-            if (pick == 0 && w == 20 && q.size == 100 && q.step == 5 && wave_baked_kind(q, 20) == 2 && tiles >= 2048) pick = w;
-            // (step 20 with size 100: 60 KB of bases per W = 12 tile; W = 8 is 2.5 % faster on 384 Mb, HBM bound either way)
-            const bool step20 = q.size == 100 && q.step == 20 && wave_baked_kind(q, 8) == 2;
-            if (pick == 0 && w == 12 && !step20 && tiles >= (flight ? 768u : 1536u)) pick = w;
-            if (pick == 0 && w == 8 && tiles >= (flight ? 512u : 1024u)) pick = w;
-            if (pick == 0 && w == 4) pick = w;
-        }
-        if (pick) {
-            p->fast_w = pick;
-            // step-1 W = 28 kernels: a tile per one or two waves instead of four (see wave_fast_tile's NTH), while at
-            // least half of the tile's slots stay windows
-            p->nth = 256;
-            if (pick == 28 && q.step == 1 && wave_is_baked(q, pick)) {
-                const bool narrow_ok = !(p->flags & GAMS_WAVE_DENSE) && !p->serial;
-                const uint32_t want = p->nth_req == 0 ? (narrow_ok ? 64u : 256u) : p->nth_req;   // the library's choice
-                if ((want == 64 || want == 128) && q.lag + 1u <= (want / 2u) * 28u) p->nth = want;
-            }
-            // (diagnostics: the headline kernel in workgroups of one or two waves, on request only -- see DESIGN 3.1)
-            if (pick == 12 && q.size == 100 && q.step == 10 && q.lag == 100 && (p->nth_req == 64 || p->nth_req == 128))
-                p->nth = p->nth_req;
-            // The W = 20 step-5 kernel (lag as an argument) sits between the two regimes: tiles of TWO waves for peaks-only
-            // plans over 4,096 such tiles or more (384 Mb 98.0 -> 89.8 us, one wave 94.8; 120 Mb 38.9 -> 38.3 us;
-            // gpurun_out/r3_ab_threads5.log)
-            if (pick == 20 && q.size == 100 && q.step == 5 && wave_baked_kind(q, 20) == 2) {
-                const bool narrow_ok = !(p->flags & GAMS_WAVE_DENSE) && !p->serial;
-                const uint32_t want = p->nth_req ? p->nth_req
-                                      : narrow_ok && p->total_windows / (128u * 20u) >= 4096 ? 128u : 256u;
-                if ((want == 64 || want == 128) && q.lag + 1u <= (want / 2u) * 20u) p->nth = want;
-            }
-            // baked kernels: the tile's windows plus the lag+1 in front fill nth*W slots exactly
-            p->tw = wave_is_baked(q, pick) ? p->nth * pick - q.lag - 1u : 256u * pick;
-            p->max_win = p->tw + q.lag + 1;
-            // rounded up to whole rows of one chunk per thread: the baked kernels store every row they load
-            p->max_chunks = ((uint32_t)((halo_bytes + (uint64_t)p->tw * q.step + 15) / 16) + 1 + p->nth - 1u) / p->nth * p->nth;
-            p->k16 = false;
-            p->wide = false;
-            p->lds_bytes = wave_fast_lds_bytes(p->max_chunks, (uint32_t)pick, q.lag,
-                                               (p->flags & GAMS_WAVE_DENSE) != 0 || p->serial, p->nth);
-            // a launch of at least a round and a half of workgroups ends in smaller tiles, unless the host
-            // keeps passes in flight (their tails overlap anyway, and the small tiles cost 3-4 % more work)
-            const uint32_t slots = 8u * (uint32_t)std::max(h->cus, 1);
-            const bool headline = q.size == 100 && q.step == 10 && q.lag == 100;
-            const bool want = p->taper_req < 0 ? p->depth == 1 : p->taper_req != 0;
-            // (not for influence != 1: the dense rows are compacted by wave_compact_kernel, which knows one tile size)
-            p->taper = want && !p->serial && tw_req == 0 && pick == 12 && headline && p->nth == 256 &&
-                       p->total_windows / p->tw >= slots + slots / 2;
-            if (p->taper)
-                wave_fill_tiles_tapered(p, slots);
-            else
-                wave_fill_tiles(p);
-            return GAMS_OK;
-        }
-    }
-    uint32_t tw = tw_req;
-    if (tw == 0) {
-        // default: ~40 KB of bases per tile, 3 workgroups per CU
-        uint64_t budget = 40960 > halo_bytes ? 40960 - halo_bytes : 0;
-        tw = (uint32_t)std::min<uint64_t>(budget / (uint64_t)q.step, 4096);
-    }
-    tw = std::min(tw, kMaxTw) & ~255u;
-    if (tw < 256) tw = 256;
-    while (tw > 256 && halo_bytes + (uint64_t)tw * q.step > kMaxTileBytes) tw -= 256;
-    auto go_direct = [&] {
-        // (lag+1)*step + size + 256*step beyond the 64-KB tile, or prefix arrays beyond the LDS:
-        // untiled kernels; the tile table only serves the peak compaction
-        p->direct = true;
-        p->tw = 1024;
-        p->max_win = 0;
-        p->max_chunks = 0;
-        p->k16 = p->wide = false;
-        p->lds_bytes = 0;
+    const WaveSelectIn in{p->prm,  p->flags,   p->serial,    p->repair, p->depth,     p->total_windows,
+                          tw_req,  p->nth_req, p->taper_req, h->cus,    p->set->bytes};
+    WaveSelection s;
+    if (!wave_select(in, s)) return gams_fail(h, GAMS_ESTATE, "wave: the instance list lacks the selected kernel");
+    p->sel = s;
+    p->fast_fn = s.entry < 0 ? nullptr : s.taper ? kWaveTaperFn[s.nt] : kWaveFastFn[s.entry][s.nt];
+    p->tile_fn = s.family == kWaveFamTile ? kWaveTileFn[s.k16][s.wide] : nullptr;
+    if (p->fast_fn) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(p->fast_fn), s.lds_bytes));
+    if (p->tile_fn) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(p->tile_fn), s.lds_bytes));
+    if (s.taper)
+        wave_fill_tiles_tapered(p, wave_slots(h->cus));
+    else
         wave_fill_tiles(p);
-        return GAMS_OK;
-    };
-    if (halo_bytes + (uint64_t)tw * q.step > kMaxTileBytes) return go_direct();
-    p->tw = tw;
-    p->max_win = tw + q.lag + 1;
-    p->max_chunks = (uint32_t)((halo_bytes + (uint64_t)tw * q.step + 15) / 16) + 1;
-    p->k16 = q.size > 255;
-    // narrow integer path: V = n*S2 - S1^2 and the tile prefix of k^2 fit 32 bits
-    const uint64_t ns = (uint64_t)q.lag * (uint64_t)q.size;
-    const uint64_t q2max = (uint64_t)(p->max_win + 1) * (uint64_t)q.size * (uint64_t)q.size;
-    p->wide = !(ns <= 65535 && q2max < (1ull << 32));
-    p->lds_bytes = wave_lds_bytes(p->max_chunks, p->max_win, p->wide, p->k16);
-    p->attr_set = false;
-    if (p->lds_bytes > 160 * 1024) return go_direct();
-    wave_fill_tiles(p);
     return GAMS_OK;
 }
 
@@ -529,7 +373,7 @@ int wave_upload_geometry(gams_gpu_t *h, gams_wave_plan_t *p) {
         gams_pool_free(h, false, p->d_dense, p->d_dense_bytes);
         p->d_dense = nullptr;
         p->dense_cap = 0;
-        p->tile_cap = std::max<uint32_t>(p->tile_cap_req ? p->tile_cap_req : p->tw / 8u, 16u);
+        p->tile_cap = std::max<uint32_t>(p->tile_cap_req ? p->tile_cap_req : p->sel.tw / 8u, 16u);
         for (auto &w : p->way) {
             gams_pool_free(h, false, w.d_peaks, w.d_peaks_bytes);
             w.d_peaks = nullptr;
@@ -582,7 +426,7 @@ JacBufs wave_jac_carve(uint8_t *base, uint64_t total_windows, const gams_wave_pl
 // per-way buffers that do not depend on the tiling: counter ring, dense rows, filtered[]
 int wave_alloc_ways(gams_gpu_t *h, gams_wave_plan_t *p) {
     const uint64_t base = std::max<uint64_t>(p->total_windows, 1);
-    const bool need_dense = (p->flags & GAMS_WAVE_DENSE) || p->serial || p->direct;
+    const bool need_dense = (p->flags & GAMS_WAVE_DENSE) || p->serial || p->sel.direct;
     for (uint32_t k = 0; k < p->depth; ++k) {
         gams_wave_plan::Way &w = p->way[k];
         if (!w.d_counters) {
@@ -608,51 +452,6 @@ int wave_alloc_ways(gams_gpu_t *h, gams_wave_plan_t *p) {
             GAMS_HIP(h, gams_pool_alloc(h, true, kJacWords * 8, reinterpret_cast<void **>(&w.h_ctl), &w.h_ctl_bytes));
         }
     }
-    return GAMS_OK;
-}
-
-template <typename KT, bool WIDE>
-int wave_launch(gams_gpu_t *h, gams_wave_plan_t *p, const WaveArgs &a, hipStream_t st) {
-    auto kern = wave_tile_kernel<KT, WIDE>;
-    if (!p->attr_set) {
-        GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kern), p->lds_bytes));
-        p->attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)p->tiles.size()), dim3(256), p->lds_bytes, st, a);
-    GAMS_HIP(h, hipGetLastError());
-    return GAMS_OK;
-}
-
-template <int W, int SIZE, int STEP, int LAG, bool NT, int NTH = 256>
-int wave_launch_fast_nt(gams_gpu_t *h, gams_wave_plan_t *p, const WaveArgs &a, hipStream_t st) {
-    auto kern = wave_fast_kernel<W, SIZE, STEP, LAG, NT, NTH>;
-    if (!p->attr_set) {
-        GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kern), p->lds_bytes));
-        p->attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)p->tiles.size()), dim3(NTH), p->lds_bytes, st, a.tiles, a.seq, a);
-    GAMS_HIP(h, hipGetLastError());
-    return GAMS_OK;
-}
-
-// sequence loads with the streaming hint once the batch is too large to live in L2 between passes
-// (kStreamBytes: twice the 32 MiB of L2)
-constexpr uint64_t kStreamBytes = 64ull << 20;
-template <int W, int SIZE, int STEP, int LAG, int NTH = 256>
-int wave_launch_fast(gams_gpu_t *h, gams_wave_plan_t *p, const WaveArgs &a, hipStream_t st) {
-    return p->set->bytes > kStreamBytes ? wave_launch_fast_nt<W, SIZE, STEP, LAG, true, NTH>(h, p, a, st)
-                                        : wave_launch_fast_nt<W, SIZE, STEP, LAG, false, NTH>(h, p, a, st);
-}
-
-template <bool NT>
-int wave_launch_taper(gams_gpu_t *h, gams_wave_plan_t *p, const WaveArgs &a, hipStream_t st) {
-    auto kern = wave_fast_taper_kernel<100, 10, 100, NT>;
-    if (!p->attr_set) {
-        GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kern), p->lds_bytes));
-        p->attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)p->tiles.size()), dim3(256), p->lds_bytes, st, a.tiles, a.seq, a);
-    GAMS_HIP(h, hipGetLastError());
     return GAMS_OK;
 }
 
@@ -819,22 +618,30 @@ uint32_t gams_wave_ctg_windows(const gams_wave_plan_t *p, uint32_t i) {
     return (p && i < p->ctgs.size()) ? p->ctgs[i].n_win : 0;
 }
 
-int gams_wave_plan_set_tile(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t tile_windows) {
-    if (!h || !p) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_tile: null argument");
-    GAMS_HIP(h, hipSetDevice(h->device));
+// The tiling again, after a setter changed what it depends on, and everything that is sized by it.  `same_taper_ok`: nothing
+// else to do when the table is tapered, or not, as before.
+static int wave_retile(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t tile_windows, bool same_taper_ok = false) {
     int rc = wave_sync_ways(h, p);
     if (rc != GAMS_OK) return rc;
+    const bool before = p->sel.taper;
     rc = wave_build_geometry(h, p, tile_windows);
     if (rc != GAMS_OK) return rc;
     p->tw_req = tile_windows;
+    if (same_taper_ok && p->sel.taper == before) return GAMS_OK;       // same tile table
     p->ran = false;
-    (void)hipFree(p->d_stamps);
+    (void)hipFree(p->d_stamps);                     // sized for the old tiling
     p->d_stamps = nullptr;
     rc = wave_upload_geometry(h, p);
     // a requested tile can move the plan from the tiled to the untiled kernels (prefix arrays beyond
     // the LDS), which need the dense rows
     if (rc == GAMS_OK) rc = wave_alloc_ways(h, p);
     return rc;
+}
+
+int gams_wave_plan_set_tile(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t tile_windows) {
+    if (!h || !p) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_tile: null argument");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    return wave_retile(h, p, tile_windows);
 }
 
 int gams_wave_plan_set_threads(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t threads) {
@@ -888,8 +695,27 @@ static JacArgs wave_jac_args(gams_wave_plan_t *p, uint32_t k) {
 static int wave_compact_dense(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k, hipStream_t st) {
     gams_wave_plan::Way &w = p->way[k];
     if (!(p->flags & GAMS_WAVE_PEAKS) || p->tiles.empty()) return GAMS_OK;
-    hipLaunchKernelGGL(wave_compact_kernel, dim3((unsigned)p->tiles.size()), dim3(256), 0, st, p->d_ctgs, p->d_tiles, p->tw,
+    hipLaunchKernelGGL(wave_compact_kernel, dim3((unsigned)p->tiles.size()), dim3(256), 0, st, p->d_ctgs, p->d_tiles, p->sel.tw,
                        w.d_dense_cnt, w.d_dense_sig, w.d_peaks, p->tile_cap, w.d_tile_cnt);
+    GAMS_HIP(h, hipGetLastError());
+    return GAMS_OK;
+}
+
+// The recurrence of influence != 1 in exact f32 order over the dense counts of way k: one wavefront per ctg with the last
+// lag + 1 filtered values in an LDS ring, or one lane per ctg with `filtered` (a float per window) beyond the ring.
+static int wave_serial_recurrence(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k, hipStream_t st, float *filtered) {
+    gams_wave_plan::Way &w = p->way[k];
+    const gams_wave_params_t &q = p->prm;
+    const uint32_t n = p->set->n_ctg;
+    if (q.lag + 1u <= kSerialRing) {
+        const size_t ring = (size_t)((q.lag + 1u + 63u) & ~63u) * sizeof(float);
+        GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(wave_serial_wave_kernel), kSerialRing * sizeof(float)));
+        hipLaunchKernelGGL(wave_serial_wave_kernel, dim3(n), dim3(64), ring, st, p->d_ctgs, n, w.d_dense_cnt,
+                           w.d_dense_sig, q.lag, q.threshold, q.influence, (float)q.size);
+    } else {
+        hipLaunchKernelGGL(wave_serial_kernel, dim3((n + 63) / 64), dim3(64), 0, st, p->d_ctgs, n, w.d_dense_cnt,
+                           w.d_dense_sig, filtered, q.lag, q.threshold, q.influence, (float)q.size);
+    }
     GAMS_HIP(h, hipGetLastError());
     return GAMS_OK;
 }
@@ -948,20 +774,9 @@ static int wave_jac_settle(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
         const bool abandon = w.h_ctl[kJacAbandon] != 0ull;
         if (fixed && !abandon) break;
         if (abandon || w.jac_sweeps >= (p->jac0 ? kJacMaxSweeps0 : kJacMaxSweeps)) {
-            const gams_wave_params_t &q = p->prm;
-            const uint32_t n = p->set->n_ctg;
-            if (q.lag + 1u <= kSerialRing) {
-                const size_t ring = (size_t)((q.lag + 1u + 63u) & ~63u) * sizeof(float);
-                GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(wave_serial_wave_kernel), kSerialRing * sizeof(float)));
-                hipLaunchKernelGGL(wave_serial_wave_kernel, dim3(n), dim3(64), ring, st, p->d_ctgs, n, w.d_dense_cnt,
-                                   w.d_dense_sig, q.lag, q.threshold, q.influence, (float)q.size);
-            } else {
-                hipLaunchKernelGGL(wave_serial_kernel, dim3((n + 63) / 64), dim3(64), 0, st, p->d_ctgs, n, w.d_dense_cnt,
-                                   w.d_dense_sig, wave_jac_carve(w.d_jac, p->total_windows).f, q.lag, q.threshold, q.influence,
-                                   (float)q.size);
-            }
-            GAMS_HIP(h, hipGetLastError());
-            int rc = wave_compact_dense(h, p, k, st);
+            int rc = wave_serial_recurrence(h, p, k, st, wave_jac_carve(w.d_jac, p->total_windows).f);
+            if (rc != GAMS_OK) return rc;
+            rc = wave_compact_dense(h, p, k, st);
             if (rc != GAMS_OK) return rc;
             GAMS_HIP(h, hipStreamSynchronize(st));
             w.jac_serial = true;
@@ -985,6 +800,48 @@ int gams_wave_plan_settled(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t *sweeps,
     *sweeps = p->repair ? p->way[k].jac_sweeps : 0u;
     *serial = p->repair ? (p->way[k].jac_serial ? 1 : 0) : (p->serial ? 1 : 0);
     return GAMS_OK;
+}
+
+// the argument block of the tile kernels for a pass on way `w` that takes counter slot `slot`
+static WaveArgs wave_args(const gams_wave_plan_t *p, const gams_wave_plan::Way &w, uint32_t slot, bool use_plane) {
+    const gams_wave_params_t &q = p->prm;
+    WaveArgs a{};
+    a.seq = p->set->d_seq;
+    a.plane = use_plane ? p->set->d_plane : nullptr;
+    a.ctgs = p->d_ctgs;
+    a.tiles = p->d_tiles;
+    a.size = (uint32_t)q.size;
+    a.step = (uint32_t)q.step;
+    a.lag = q.lag;
+    a.tw = p->sel.tw;
+    a.max_chunks = p->sel.max_chunks;
+    a.max_win = p->sel.max_win;
+    a.flags = p->serial ? GAMS_WAVE_DENSE : p->flags;
+    a.no_signal = (q.lag < 2 || (p->serial && !p->repair)) ? 1u : 0u;
+    a.thr = q.threshold;
+    a.thr_abs = std::fabs(q.threshold);
+    a.fsize = (float)q.size;
+    a.flag_f = (float)q.lag;
+    a.cvar = q.lag > 1 ? (float)((double)q.lag / ((double)q.lag - 1.0)) : 0.0f;
+    a.g0 = p->g0;
+    a.g1 = p->g1;
+    a.g2 = p->g2;
+    a.g3 = p->g3;
+    a.aA = p->sq[0];
+    a.aB = p->sq[1];
+    a.gA0 = p->sq[2];
+    a.gA1 = p->sq[3];
+    a.gB0 = p->sq[4];
+    a.gB1 = p->sq[5];
+    a.peaks = w.d_peaks;
+    a.tile_cap = p->tile_cap;
+    a.counters = w.d_counters + kSlotWords * slot;
+    a.const_sig = p->d_const_sig;
+    a.stamps = p->d_stamps;
+    a.tile_cnt = w.d_tile_cnt;
+    a.dense_cnt = w.d_dense_cnt;
+    a.dense_sig = w.d_dense_sig;
+    return a;
 }
 
 // One pass on way k: touches only that way's state and its stream (run_n drives different ways
@@ -1019,7 +876,7 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
     // The tiled fast kernels stream the seqset's G/C plane when it describes the bytes right now (every upload so
     // far brought both); everything else reads the bytes.  Decided when the pass is queued: a later upload queues
     // itself behind this pass (gams_order_after_readers) and changes the state for the passes after it.
-    const bool fast_tile = p->fast_w != 0 && !p->direct;
+    const bool fast_tile = p->fast_fn != nullptr;
     const bool plane_fit = fast_tile && p->set->plane_ok && p->set->d_plane != nullptr;
     if (p->input_req == GAMS_WAVE_INPUT_PLANE && !plane_fit)
         return gams_fail(h, GAMS_ESTATE, fast_tile ? "wave: the seqset's G/C plane is stale" : "wave: this plan's kernels read the sequence bytes, not the G/C plane");
@@ -1029,43 +886,9 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
     if (p->input_req == GAMS_WAVE_INPUT_BYTES && use_plane)
         return gams_fail(h, GAMS_ESTATE, "wave: the seqset holds the G/C plane only, the bytes were asked for");
     p->last_input.store(use_plane ? GAMS_WAVE_INPUT_PLANE : GAMS_WAVE_INPUT_BYTES, std::memory_order_relaxed);
-    WaveArgs a{};
-    a.seq = p->set->d_seq;
-    a.plane = use_plane ? p->set->d_plane : nullptr;
-    a.ctgs = p->d_ctgs;
-    a.tiles = p->d_tiles;
-    a.size = (uint32_t)q.size;
-    a.step = (uint32_t)q.step;
-    a.lag = q.lag;
-    a.tw = p->tw;
-    a.max_chunks = p->max_chunks;
-    a.max_win = p->max_win;
-    a.flags = p->serial ? GAMS_WAVE_DENSE : p->flags;
-    a.no_signal = (q.lag < 2 || (p->serial && !p->repair)) ? 1u : 0u;
-    a.thr = q.threshold;
-    a.thr_abs = std::fabs(q.threshold);
-    a.fsize = (float)q.size;
-    a.flag_f = (float)q.lag;
-    a.cvar = q.lag > 1 ? (float)((double)q.lag / ((double)q.lag - 1.0)) : 0.0f;
-    a.g0 = p->g0;
-    a.g1 = p->g1;
-    a.g2 = p->g2;
-    a.g3 = p->g3;
-    a.aA = p->sq[0];
-    a.aB = p->sq[1];
-    a.gA0 = p->sq[2];
-    a.gA1 = p->sq[3];
-    a.gB0 = p->sq[4];
-    a.gB1 = p->sq[5];
-    a.peaks = w.d_peaks;
-    a.tile_cap = p->tile_cap;
-    a.counters = w.d_counters + kSlotWords * slot;
-    a.const_sig = p->d_const_sig;
-    a.stamps = p->d_stamps;
-    a.tile_cnt = w.d_tile_cnt;
-    a.dense_cnt = w.d_dense_cnt;
-    a.dense_sig = w.d_dense_sig;
-    if (p->direct) {
+    const WaveArgs a = wave_args(p, w, slot, use_plane);
+    const unsigned nt = (unsigned)p->tiles.size();
+    if (p->sel.direct) {
         const uint64_t total = p->total_windows;
         const unsigned blocks = (unsigned)((total + 255) / 256);
         hipLaunchKernelGGL(wave_direct_count_kernel, dim3(blocks), dim3(256), 0, st, p->set->d_seq, p->d_ctgs,
@@ -1077,68 +900,17 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
                                q.lag < 2 ? 1u : 0u);
             GAMS_HIP(h, hipGetLastError());
         }
+    } else if (p->fast_fn) {
+        hipLaunchKernelGGL(p->fast_fn, dim3(nt), dim3(p->sel.nth), p->sel.lds_bytes, st, a.tiles, a.seq, a);
+        GAMS_HIP(h, hipGetLastError());
+    } else {
+        hipLaunchKernelGGL(p->tile_fn, dim3(nt), dim3(256), p->sel.lds_bytes, st, a);
+        GAMS_HIP(h, hipGetLastError());
     }
     int rc = GAMS_OK;
-    const int kind = p->fast_w ? wave_baked_kind(q, p->fast_w) : 0;
-    const bool baked = kind == 1;
-    const bool step1 = baked && q.step == 1;
-    if (p->direct)
-        ;   // counted and decided above
-    else if (kind == 2) {
-        // size and step baked, lag from the arguments
-#define GAMS_RL(WW, ST) rc = wave_launch_fast<WW, 100, ST, 0>(h, p, a, st)
-        const int key = p->fast_w * 100 + q.step;
-        switch (key) {
-        case 405: GAMS_RL(4, 5); break;
-        case 805: GAMS_RL(8, 5); break;
-        case 1205: GAMS_RL(12, 5); break;
-        case 410: GAMS_RL(4, 10); break;
-        case 810: GAMS_RL(8, 10); break;
-        case 1210: GAMS_RL(12, 10); break;
-        case 420: GAMS_RL(4, 20); break;
-        case 820: GAMS_RL(8, 20); break;
-        case 1220: GAMS_RL(12, 20); break;
-        case 2001: GAMS_RL(20, 1); break;
-        case 2005:
-            rc = p->nth == 64    ? wave_launch_fast<20, 100, 5, 0, 64>(h, p, a, st)
-                 : p->nth == 128 ? wave_launch_fast<20, 100, 5, 0, 128>(h, p, a, st)
-                                 : wave_launch_fast<20, 100, 5, 0>(h, p, a, st);
-            break;
-        case 2801:
-            rc = p->nth == 64    ? wave_launch_fast<28, 100, 1, 0, 64>(h, p, a, st)
-                 : p->nth == 128 ? wave_launch_fast<28, 100, 1, 0, 128>(h, p, a, st)
-                                 : wave_launch_fast<28, 100, 1, 0>(h, p, a, st);
-            break;
-        default: rc = gams_fail(h, GAMS_ESTATE, "wave: no kernel for this tile size / step"); break;
-        }
-#undef GAMS_RL
-    } else if (p->fast_w == 28)
-        rc = p->nth == 64    ? wave_launch_fast<28, 100, 1, 100, 64>(h, p, a, st)   // baked only (wave_build_geometry)
-             : p->nth == 128 ? wave_launch_fast<28, 100, 1, 100, 128>(h, p, a, st)
-                             : wave_launch_fast<28, 100, 1, 100>(h, p, a, st);
-    else if (p->fast_w == 20)
-        rc = baked ? wave_launch_fast<20, 100, 1, 100>(h, p, a, st) : wave_launch_fast<20, 0, 0, 0>(h, p, a, st);
-    else if (p->taper)
-        rc = p->set->bytes > kStreamBytes ? wave_launch_taper<true>(h, p, a, st) : wave_launch_taper<false>(h, p, a, st);
-    else if (p->fast_w == 12)
-        rc = !baked ? wave_launch_fast<12, 0, 0, 0>(h, p, a, st)
-             : step1 ? wave_launch_fast<12, 100, 1, 100>(h, p, a, st)
-             : p->nth == 64 ? wave_launch_fast<12, 100, 10, 100, 64>(h, p, a, st)
-             : p->nth == 128 ? wave_launch_fast<12, 100, 10, 100, 128>(h, p, a, st)
-                     : wave_launch_fast<12, 100, 10, 100>(h, p, a, st);
-    else if (p->fast_w == 8)
-        rc = baked ? wave_launch_fast<8, 100, 10, 100>(h, p, a, st) : wave_launch_fast<8, 0, 0, 0>(h, p, a, st);
-    else if (p->fast_w == 4)
-        rc = baked ? wave_launch_fast<4, 100, 10, 100>(h, p, a, st) : wave_launch_fast<4, 0, 0, 0>(h, p, a, st);
-    else if (p->k16)
-        rc = p->wide ? wave_launch<uint16_t, true>(h, p, a, st) : wave_launch<uint16_t, false>(h, p, a, st);
-    else
-        rc = p->wide ? wave_launch<uint8_t, true>(h, p, a, st) : wave_launch<uint8_t, false>(h, p, a, st);
-    if (rc != GAMS_OK) return rc;
-    if (p->direct && !p->serial && (p->flags & GAMS_WAVE_PEAKS)) {
-        hipLaunchKernelGGL(wave_compact_kernel, dim3((unsigned)p->tiles.size()), dim3(256), 0, st, p->d_ctgs,
-                           p->d_tiles, p->tw, w.d_dense_cnt, w.d_dense_sig, w.d_peaks, p->tile_cap, w.d_tile_cnt);
-        GAMS_HIP(h, hipGetLastError());
+    if (p->sel.direct && !p->serial) {
+        rc = wave_compact_dense(h, p, k, st);
+        if (rc != GAMS_OK) return rc;
     }
     if (p->repair) {
         // influence != 1, guess-and-iterate (wave_repair.hpp): the dense rows hold the counts and the S1 signals; a first
@@ -1150,23 +922,9 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
         rc = wave_jac_sweeps(h, p, k, kJacFirstBatch, true);
         if (rc != GAMS_OK) return rc;
     } else if (p->serial) {
-        const uint32_t n = p->set->n_ctg;
-        if (q.lag + 1u <= kSerialRing) {
-            // one wavefront per ctg, the last lag + 1 filtered values in an LDS ring
-            const size_t ring = (size_t)((q.lag + 1u + 63u) & ~63u) * sizeof(float);
-            GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(wave_serial_wave_kernel), kSerialRing * sizeof(float)));
-            hipLaunchKernelGGL(wave_serial_wave_kernel, dim3(n), dim3(64), ring, st, p->d_ctgs, n, w.d_dense_cnt,
-                               w.d_dense_sig, q.lag, q.threshold, q.influence, (float)q.size);
-        } else {
-            hipLaunchKernelGGL(wave_serial_kernel, dim3((n + 63) / 64), dim3(64), 0, st, p->d_ctgs, n, w.d_dense_cnt,
-                               w.d_dense_sig, w.d_filtered, q.lag, q.threshold, q.influence, (float)q.size);
-        }
-        GAMS_HIP(h, hipGetLastError());
-        if (p->flags & GAMS_WAVE_PEAKS) {
-            hipLaunchKernelGGL(wave_compact_kernel, dim3((unsigned)p->tiles.size()), dim3(256), 0, st, p->d_ctgs,
-                               p->d_tiles, p->tw, w.d_dense_cnt, w.d_dense_sig, w.d_peaks, p->tile_cap, w.d_tile_cnt);
-            GAMS_HIP(h, hipGetLastError());
-        }
+        rc = wave_serial_recurrence(h, p, k, st, w.d_filtered);
+        if (rc == GAMS_OK) rc = wave_compact_dense(h, p, k, st);
+        if (rc != GAMS_OK) return rc;
     }
     // An event per run costs a marker packet between back-to-back launches (measured: 8.8 ->
     // 11.7 us per 12-Mb pass), so it is only recorded for plans that overlap several runs.
@@ -1297,8 +1055,7 @@ int gams_wave_run_n(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t n) {
     // in flight that is slower than the device drains them (2.85 us per 12-Mb pass), so a batch is
     // queued by several threads: the caller keeps way 0, launcher threads take the other ways
     // (K = 1000 passes at depth 4: 4.4 / 3.1 / 3.0 / 3.0 us per pass with 1 / 2 / 3 / 4 threads;
-    // K = 200: 3.8 / 3.8 / 3.6 / 3.5).  The first round goes through gams_wave_run on the caller: it
-    // applies the kernel attribute and the first-use stream waits.
+    // K = 200: 3.8 / 3.8 / 3.6 / 3.5).  The first round goes through gams_wave_run on the caller.
     const uint32_t shares = std::min(p->queue_threads, p->depth);   // default: one queueing thread per way
     const bool threaded = p->depth >= 3 && shares >= 2 && n >= 4 * p->depth;
     if (!threaded) {
@@ -1355,7 +1112,7 @@ int gams_wave_plan_set_depth(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t depth)
     if (depth < 1 || depth > (uint32_t)gams_gpu::kMaxWays)
         return gams_fail(h, GAMS_EINVAL, "wave_plan_set_depth: depth must be 1.." + std::to_string(gams_gpu::kMaxWays));
     GAMS_HIP(h, hipSetDevice(h->device));
-    int rc = wave_sync_ways(h, p);
+    int rc = wave_sync_ways(h, p);                  // the ways of the old depth (wave_retile waits over the new ones)
     if (rc != GAMS_OK) return rc;
     for (uint32_t k = 1; k < depth; ++k)
         if (!h->aux[k - 1]) GAMS_HIP(h, hipStreamCreateWithFlags(&h->aux[k - 1], hipStreamNonBlocking));
@@ -1364,32 +1121,15 @@ int gams_wave_plan_set_depth(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t depth)
     p->run_idx = 0;
     p->last_way = 0;
     p->sel_age = 0;
-    rc = wave_build_geometry(h, p, p->tw_req);      // the default tile depends on the depth
-    if (rc != GAMS_OK) return rc;
-    (void)hipFree(p->d_stamps);                     // sized for the old tiling
-    p->d_stamps = nullptr;
-    rc = wave_upload_geometry(h, p);
-    if (rc == GAMS_OK) rc = wave_alloc_ways(h, p);
-    return rc;
+    return wave_retile(h, p, p->tw_req);            // the default tile depends on the depth
 }
 
 int gams_wave_plan_set_taper(gams_gpu_t *h, gams_wave_plan_t *p, int mode) {
     if (!h || !p) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_taper: null argument");
     if (mode < -1 || mode > 1) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_taper: mode must be -1 (auto), 0 or 1");
     GAMS_HIP(h, hipSetDevice(h->device));
-    int rc = wave_sync_ways(h, p);
-    if (rc != GAMS_OK) return rc;
     p->taper_req = mode;
-    const bool before = p->taper;
-    rc = wave_build_geometry(h, p, p->tw_req);
-    if (rc != GAMS_OK) return rc;
-    if (p->taper == before) return GAMS_OK;       // same tile table
-    p->ran = false;
-    (void)hipFree(p->d_stamps);
-    p->d_stamps = nullptr;
-    rc = wave_upload_geometry(h, p);
-    if (rc == GAMS_OK) rc = wave_alloc_ways(h, p);
-    return rc;
+    return wave_retile(h, p, p->tw_req, true);
 }
 
 int gams_wave_plan_set_taper_shape(gams_gpu_t *h, gams_wave_plan_t *p, int pct4, int pct8) {
@@ -1397,18 +1137,9 @@ int gams_wave_plan_set_taper_shape(gams_gpu_t *h, gams_wave_plan_t *p, int pct4,
     if (pct4 < 0 || pct4 > 100 || pct8 < 0 || pct8 > 100)
         return gams_fail(h, GAMS_EINVAL, "wave_plan_set_taper_shape: percentages must be 0..100");
     GAMS_HIP(h, hipSetDevice(h->device));
-    int rc = wave_sync_ways(h, p);
-    if (rc != GAMS_OK) return rc;
     p->taper4_pct = pct4;
     p->taper8_pct = pct8;
-    rc = wave_build_geometry(h, p, p->tw_req);
-    if (rc != GAMS_OK) return rc;
-    p->ran = false;
-    (void)hipFree(p->d_stamps);
-    p->d_stamps = nullptr;
-    rc = wave_upload_geometry(h, p);
-    if (rc == GAMS_OK) rc = wave_alloc_ways(h, p);
-    return rc;
+    return wave_retile(h, p, p->tw_req);
 }
 
 int gams_wave_plan_set_queue_threads(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t n) {
@@ -1421,26 +1152,14 @@ int gams_wave_plan_set_queue_threads(gams_gpu_t *h, gams_wave_plan_t *p, uint32_
 
 int gams_wave_plan_kernel_name(gams_gpu_t *h, gams_wave_plan_t *p, char *buf, size_t n) {
     if (!h || !p || !buf || n == 0) return gams_fail(h, GAMS_EINVAL, "wave_plan_kernel_name: null argument");
-    // the same decisions as wave_pass_on_way, spelled the way rocprofv3 prints the instantiation
-    const gams_wave_params_t &q = p->prm;
-    const int kind = p->fast_w ? wave_baked_kind(q, p->fast_w) : 0;
-    const bool baked = kind != 0;
-    const char *nt = p->set->bytes > kStreamBytes ? "true" : "false";
-    std::string name;
+    // of a repair pass's kernels (counts + S1 signals, sweeps) the one that takes longest; else the recurrence, else the
+    // plan's tile kernel
     if (p->repair)
-        name = "jac_eval_kernel";      // of the pass's kernels (counts + S1 signals, sweeps) the one that takes longest
+        std::snprintf(buf, n, "jac_eval_kernel");
     else if (p->serial)
-        name = q.lag + 1u <= kSerialRing ? "wave_serial_wave_kernel" : "wave_serial_kernel";
-    else if (p->direct)
-        name = "wave_direct_count_kernel + wave_direct_signal_kernel";
-    else if (p->taper)
-        name = std::string("wave_fast_taper_kernel<100, 10, 100, ") + nt + ">";
-    else if (p->fast_w) {
-        const std::string prm = baked ? "100, " + std::to_string(q.step) + (kind == 1 ? ", 100, " : ", 0, ") : "0, 0, 0, ";
-        name = "wave_fast_kernel<" + std::to_string(p->fast_w) + ", " + prm + nt + ", " + std::to_string(p->nth) + ">";
-    } else
-        name = std::string("wave_tile_kernel<") + (p->k16 ? "unsigned short, " : "unsigned char, ") + (p->wide ? "true>" : "false>");
-    std::snprintf(buf, n, "%s", name.c_str());
+        std::snprintf(buf, n, "%s", p->prm.lag + 1u <= kSerialRing ? "wave_serial_wave_kernel" : "wave_serial_kernel");
+    else
+        wave_selection_name(p->sel, buf, n);
     return GAMS_OK;
 }
 
@@ -1519,18 +1238,18 @@ int gams_wave_peaks(gams_gpu_t *h, gams_wave_plan_t *p, const gams_peak_t **peak
         // Buffers below are sized from these two device-written words: refuse values no pass over this
         // plan can produce (a tile signals at most its own windows, all tiles together at most the
         // batch's) instead of allocating and copying by them.
-        if (worst > p->tw || total > p->total_windows || total > (uint64_t)nt * worst)
+        if (worst > p->sel.tw || total > p->total_windows || total > (uint64_t)nt * worst)
             return gams_fail(h, GAMS_EHIP,
                              "wave_peaks: inconsistent peak counts from the device (total " + std::to_string(total) +
                                  ", fullest tile " + std::to_string(worst) + ", " + std::to_string(p->total_windows) +
-                                 " windows in " + std::to_string(nt) + " tiles of at most " + std::to_string(p->tw) + ")");
+                                 " windows in " + std::to_string(nt) + " tiles of at most " + std::to_string(p->sel.tw) + ")");
         if (worst > p->tile_cap) {
             // some tile signalled more windows than its slot holds: the device has reported the
             // fullest tile (runs are deterministic, so that is what the slots need -- at GRCh38 step 1 a
             // slot of tw records per tile would be ~50 GB per way) and every pass still held is run
             // again into the new slots: same inputs, same results.  The run counter only steps back by
             // the passes repeated, so the way rotation and the history gams_wave_plan_select sees stay.
-            p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->tw, (worst + 15u) & ~(uint64_t)15u);
+            p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->sel.tw, (worst + 15u) & ~(uint64_t)15u);
             const uint32_t age = p->sel_age;
             const uint32_t again = (uint32_t)std::min<uint64_t>(p->depth, p->run_idx);
             int rc = wave_sync_ways(h, p);
@@ -1947,13 +1666,13 @@ int gams_wave_rows_end(gams_gpu_t *h, gams_wave_plan_t *p, const char **text, ui
     for (int attempt = 0; attempt < 4; ++attempt) {
         GAMS_HIP(h, hipEventSynchronize(r->done));
         const uint64_t n_rec = r->h_words[0], bytes = r->h_words[1], total = r->h_words[2], worst = r->h_words[3];
-        if (worst > p->tw || total > p->total_windows || total > (uint64_t)nt * worst)
+        if (worst > p->sel.tw || total > p->total_windows || total > (uint64_t)nt * worst)
             return gams_fail(h, GAMS_EHIP, "wave_rows: inconsistent peak counts from the device");
         int rc = GAMS_OK;
         if (worst > p->tile_cap) {
             // a tile signalled more windows than its slot holds: larger slots, the passes still held run again
             // (see gams_wave_peaks), then the rows once more
-            p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->tw, (worst + 15u) & ~(uint64_t)15u);
+            p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->sel.tw, (worst + 15u) & ~(uint64_t)15u);
             const uint32_t age = p->sel_age;
             const uint32_t again = (uint32_t)std::min<uint64_t>(p->depth, p->run_idx);
             rc = wave_sync_ways(h, p);
