@@ -14,6 +14,7 @@
 
 #include "../../include/gams_gpu.h"
 #include "../../include/gams_gpu_diag.h"
+#include "layout.hpp"
 
 struct gams_gpu {
     int device = 0;
@@ -110,6 +111,60 @@ inline int gams_fail(gams_gpu_t *h, int code, const std::string &msg) {
                              std::string(#call) + ": " + hipGetErrorString(e_));    \
         }                                                                           \
     } while (0)
+
+// The check of a call whose scratch is owned by PoolBlocks (below): report and return, the destructors give back.
+// `who` names the entry (a std::string).  An out-of-memory failure is GAMS_ENOMEM, every other one GAMS_EHIP.
+#define GAMS_TRY(h, who, call)                                                                   \
+    do {                                                                                         \
+        hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return gams_fail((h), e_ == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,           \
+                             (who) + ": " + #call + ": " + hipGetErrorString(e_));               \
+    } while (0)
+
+// One pooled block for the length of a call (or of a build).  A block goes back to the pool only after every stream
+// that had work queued on it has drained: the streams named at construction (h->compute unless others are given).
+struct PoolBlock {
+    gams_gpu_t *h;
+    bool pinned;
+    hipStream_t drain[3];
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    PoolBlock(gams_gpu_t *h_, bool pinned_, hipStream_t a = nullptr, hipStream_t b = nullptr, hipStream_t c = nullptr)
+        : h(h_), pinned(pinned_), drain{a ? a : h_->compute, b, c} {}
+    PoolBlock(const PoolBlock &) = delete;
+    PoolBlock &operator=(const PoolBlock &) = delete;
+    ~PoolBlock() { reset(); }
+    hipError_t alloc(size_t bytes) {
+        reset();
+        return gams_pool_alloc(h, pinned, bytes, reinterpret_cast<void **>(&p), &cap);
+    }
+    void reset() {   // back to the pool now
+        if (!p) return;
+        for (hipStream_t st : drain)
+            if (st) (void)hipStreamSynchronize(st);
+        gams_pool_free(h, pinned, p, cap);
+        p = nullptr;
+        cap = 0;
+    }
+    uint8_t *release(size_t *cap_out) {   // to an owner that outlives the call
+        uint8_t *const q = p;
+        *cap_out = cap;
+        p = nullptr;
+        return q;
+    }
+};
+
+// A buffer the handle keeps between calls and only ever grows: nothing to do if it holds `need` bytes; otherwise the old
+// block goes back and one of `want` bytes takes its place (contents are not kept; p = nullptr, cap = 0 on failure).
+template <typename T>
+hipError_t gams_pool_grow(gams_gpu_t *h, bool pinned, T **p, size_t *cap, size_t need, size_t want) {
+    if (*cap >= need) return hipSuccess;
+    gams_pool_free(h, pinned, *p, *cap);
+    *p = nullptr;
+    *cap = 0;
+    return gams_pool_alloc(h, pinned, want, reinterpret_cast<void **>(p), cap);
+}
 
 struct gams_gcindex;  // sw.hip: prefix index over the seqset buffer
 

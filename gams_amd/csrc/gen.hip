@@ -84,55 +84,40 @@ extern "C" int gams_gpu_valid_spans(gams_gpu_t *h, const uint8_t *seq, uint64_t 
     const uint64_t n_chunks = (len + 15) / 16;
     // device buffers from the handle's pool (one chromosome after another reuses them): the sequence, and
     // one block holding the flip counter (first 256 B) and the flip list behind it
-    uint8_t *d_seq = nullptr, *d_blk = nullptr;
-    size_t seq_cap = 0, blk_cap = 0;
+    const std::string who = "valid_spans";
+    PoolBlock d_seq(h, false), d_blk(h, false);
     uint64_t fcap = 1u << 16;
-    auto cleanup = [&]() {
-        gams_pool_free(h, false, d_seq, seq_cap);
-        gams_pool_free(h, false, d_blk, blk_cap);
-        d_seq = d_blk = nullptr;
-    };
-#define G_HIP(call)                                                                            \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (void)hipStreamSynchronize(h->compute); /* nothing may still use the blocks */     \
-            cleanup();                                                                         \
-            return gams_fail(h, GAMS_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-        }                                                                                      \
-    } while (0)
-    G_HIP(gams_pool_alloc(h, false, n_chunks * 16 + 16, reinterpret_cast<void **>(&d_seq), &seq_cap));
-    G_HIP(hipMemsetAsync(d_seq + (n_chunks - 1) * 16, 0, 32, h->compute));
-    G_HIP(hipMemcpyAsync(d_seq, seq, len, hipMemcpyHostToDevice, h->compute));
+    GAMS_TRY(h, who, d_seq.alloc(n_chunks * 16 + 16));
+    GAMS_TRY(h, who, hipMemsetAsync(d_seq.p + (n_chunks - 1) * 16, 0, 32, h->compute));
+    GAMS_TRY(h, who, hipMemcpyAsync(d_seq.p, seq, len, hipMemcpyHostToDevice, h->compute));
     std::vector<unsigned long long> flips;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        G_HIP(gams_pool_alloc(h, false, 256 + fcap * sizeof(unsigned long long), reinterpret_cast<void **>(&d_blk), &blk_cap));
-        unsigned long long *const d_n = reinterpret_cast<unsigned long long *>(d_blk);
-        unsigned long long *const d_flips = reinterpret_cast<unsigned long long *>(d_blk + 256);
-        G_HIP(hipMemsetAsync(d_n, 0, sizeof(unsigned long long), h->compute));
-        G_HIP(hipEventRecord(h->k0, h->compute));
-        hipLaunchKernelGGL(gen_scan_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, h->compute, d_seq,
+        GAMS_TRY(h, who, d_blk.alloc(256 + fcap * sizeof(unsigned long long)));
+        unsigned long long *const d_n = reinterpret_cast<unsigned long long *>(d_blk.p);
+        unsigned long long *const d_flips = reinterpret_cast<unsigned long long *>(d_blk.p + 256);
+        GAMS_TRY(h, who, hipMemsetAsync(d_n, 0, sizeof(unsigned long long), h->compute));
+        GAMS_TRY(h, who, hipEventRecord(h->k0, h->compute));
+        hipLaunchKernelGGL(gen_scan_kernel, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, h->compute, d_seq.p,
                            len, n_chunks, d_flips, fcap, d_n);
-        G_HIP(hipGetLastError());
-        G_HIP(hipEventRecord(h->k1, h->compute));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipEventRecord(h->k1, h->compute));
         h->k_valid = true;
         h->kq_used = 0;
         // the counter comes back through the handle's page-locked scratch word
-        G_HIP(hipMemcpyAsync(h->pin_scratch, d_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->compute));
-        G_HIP(hipStreamSynchronize(h->compute));
+        GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, d_n, sizeof(unsigned long long), hipMemcpyDeviceToHost, h->compute));
+        GAMS_TRY(h, who, hipStreamSynchronize(h->compute));
         const unsigned long long nf = h->pin_scratch[0];
         if (nf > fcap) {                 // more flips than the list holds: grow once and rescan
-            gams_pool_free(h, false, d_blk, blk_cap);
-            d_blk = nullptr;
+            d_blk.reset();
             fcap = nf;
             continue;
         }
         flips.resize(nf);
-        if (nf) G_HIP(hipMemcpy(flips.data(), d_flips, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        if (nf) GAMS_TRY(h, who, hipMemcpy(flips.data(), d_flips, nf * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         break;
     }
-#undef G_HIP
-    cleanup();
+    d_seq.reset();
+    d_blk.reset();
     std::sort(flips.begin(), flips.end());
     if (flips.size() % 2 != 0) return gams_fail(h, GAMS_EHIP, "valid_spans: unpaired run boundary");
     // valid spans, 1-based inclusive (gen.rs:100-102)

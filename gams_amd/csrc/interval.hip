@@ -561,13 +561,6 @@ hipError_t to_device(T **d, const T *hsrc, size_t n) {
     return e;
 }
 
-#define Q_HIP(call)                                                                            \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return gams_fail(h, GAMS_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 // Host columns in, one host column out, through the three query kernels.  The queries go in chunks of
 // 2^21: chunk c+1 is copied in (copy stream) while chunk c is searched (compute stream) and chunk c-1 is
 // copied out (readback stream), two device slots.  With page-locked host arrays (gams_gpu_host_alloc) the
@@ -582,69 +575,54 @@ int query_pipeline(gams_gpu_t *h, uint64_t nq, const QCol *cols, int ncol, void 
     const uint64_t CH = std::min<uint64_t>(nq, 1ull << 21);
     const uint64_t nchunk = (nq + CH - 1) / CH;
     const int nslot = nchunk > 1 ? 2 : 1;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    size_t slot_bytes = al(CH * out_elem);
-    for (int k = 0; k < ncol; ++k) slot_bytes += al(CH * cols[k].elem);
-    uint8_t *block = nullptr;
-    size_t block_cap = 0;
-    hipError_t e = gams_pool_alloc(h, false, slot_bytes * nslot, reinterpret_cast<void **>(&block), &block_cap);
-    if (e != hipSuccess)
-        return gams_fail(h, e == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,
-                         std::string("query buffers: ") + hipGetErrorString(e));
-    struct Guard {
-        gams_gpu_t *h;
-        uint8_t *p;
-        size_t cap;
-        ~Guard() {
-            (void)hipStreamSynchronize(h->copy);
-            (void)hipStreamSynchronize(h->compute);
-            (void)hipStreamSynchronize(h->readback);
-            gams_pool_free(h, false, p, cap);
-        }
-    } guard{h, block, block_cap};
+    const std::string who = "query";
+    size_t slot_bytes = gams_align256(CH * out_elem);
+    for (int k = 0; k < ncol; ++k) slot_bytes += gams_align256(CH * cols[k].elem);
+    PoolBlock block(h, false, h->copy, h->compute, h->readback);   // the three streams of the pipeline
+    GAMS_TRY(h, who, block.alloc(slot_bytes * nslot));
     for (int s = 0; s < 2; ++s)
         for (int k = 0; k < 3; ++k)
-            if (!h->q_ev[s][k]) Q_HIP(hipEventCreateWithFlags(&h->q_ev[s][k], hipEventDisableTiming));
+            if (!h->q_ev[s][k]) GAMS_TRY(h, who, hipEventCreateWithFlags(&h->q_ev[s][k], hipEventDisableTiming));
     while (h->kq.size() < nchunk) {
         hipEvent_t a = nullptr, b = nullptr;
-        Q_HIP(hipEventCreate(&a));
-        Q_HIP(hipEventCreate(&b));
+        GAMS_TRY(h, who, hipEventCreate(&a));
+        GAMS_TRY(h, who, hipEventCreate(&b));
         h->kq.emplace_back(a, b);
     }
     h->kq_used = 0;
     // whatever the caller queued on the compute stream before (index build, uploads) comes first
-    Q_HIP(hipEventRecord(h->k0, h->compute));
-    Q_HIP(hipStreamWaitEvent(h->copy, h->k0, 0));
+    GAMS_TRY(h, who, hipEventRecord(h->k0, h->compute));
+    GAMS_TRY(h, who, hipStreamWaitEvent(h->copy, h->k0, 0));
     std::vector<void *> d_in((size_t)ncol);
     for (uint64_t c = 0; c < nchunk; ++c) {
         const int s = (int)(c & 1);
         const uint64_t lo = c * CH, n = std::min<uint64_t>(CH, nq - lo);
-        uint8_t *p = block + (size_t)s * slot_bytes;
-        if (c >= 2) Q_HIP(hipStreamWaitEvent(h->copy, h->q_ev[s][1], 0));       // chunk c-2's kernel has read its inputs
+        uint8_t *p = block.p + (size_t)s * slot_bytes;
+        if (c >= 2) GAMS_TRY(h, who, hipStreamWaitEvent(h->copy, h->q_ev[s][1], 0));       // chunk c-2's kernel has read its inputs
         for (int k = 0; k < ncol; ++k) {
             d_in[(size_t)k] = p;
-            Q_HIP(hipMemcpyAsync(p, static_cast<const uint8_t *>(cols[k].host) + lo * cols[k].elem, n * cols[k].elem,
+            GAMS_TRY(h, who, hipMemcpyAsync(p, static_cast<const uint8_t *>(cols[k].host) + lo * cols[k].elem, n * cols[k].elem,
                                  hipMemcpyHostToDevice, h->copy));
-            p += al(CH * cols[k].elem);
+            p += gams_align256(CH * cols[k].elem);
         }
         void *d_out = p;
-        Q_HIP(hipEventRecord(h->q_ev[s][0], h->copy));
-        Q_HIP(hipStreamWaitEvent(h->compute, h->q_ev[s][0], 0));
-        if (c >= 2) Q_HIP(hipStreamWaitEvent(h->compute, h->q_ev[s][2], 0));    // chunk c-2's results are out
-        Q_HIP(hipEventRecord(h->kq[(size_t)c].first, h->compute));
+        GAMS_TRY(h, who, hipEventRecord(h->q_ev[s][0], h->copy));
+        GAMS_TRY(h, who, hipStreamWaitEvent(h->compute, h->q_ev[s][0], 0));
+        if (c >= 2) GAMS_TRY(h, who, hipStreamWaitEvent(h->compute, h->q_ev[s][2], 0));    // chunk c-2's results are out
+        GAMS_TRY(h, who, hipEventRecord(h->kq[(size_t)c].first, h->compute));
         launch(d_in.data(), d_out, n, h->compute);
-        Q_HIP(hipGetLastError());
-        Q_HIP(hipEventRecord(h->kq[(size_t)c].second, h->compute));
-        Q_HIP(hipEventRecord(h->q_ev[s][1], h->compute));
-        Q_HIP(hipStreamWaitEvent(h->readback, h->q_ev[s][1], 0));
-        Q_HIP(hipMemcpyAsync(static_cast<uint8_t *>(out_host) + lo * out_elem, d_out, n * out_elem,
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipEventRecord(h->kq[(size_t)c].second, h->compute));
+        GAMS_TRY(h, who, hipEventRecord(h->q_ev[s][1], h->compute));
+        GAMS_TRY(h, who, hipStreamWaitEvent(h->readback, h->q_ev[s][1], 0));
+        GAMS_TRY(h, who, hipMemcpyAsync(static_cast<uint8_t *>(out_host) + lo * out_elem, d_out, n * out_elem,
                              hipMemcpyDeviceToHost, h->readback));
-        Q_HIP(hipEventRecord(h->q_ev[s][2], h->readback));
+        GAMS_TRY(h, who, hipEventRecord(h->q_ev[s][2], h->readback));
     }
     h->kq_used = (int)nchunk;
     h->kq_staged = false;
     h->k_valid = true;
-    Q_HIP(hipStreamSynchronize(h->readback));
+    GAMS_TRY(h, who, hipStreamSynchronize(h->readback));
     return GAMS_OK;
 }
 
@@ -652,68 +630,46 @@ int query_pipeline(gams_gpu_t *h, uint64_t nq, const QCol *cols, int ncol, void 
 
 // ---- the builder behind gams_index_create (and text.hip's gams_index_create_range_text) ------------------------
 // begin: the index's arena and the build's scratch for n_groups groups of m intervals in all (m <= 2^32 - 16, checked by
-// the caller).  The caller then fills d_off32 (n_groups + 1 offsets), d_starts_in and d_stops_in (any order inside a
+// the caller).  The caller then fills cols.off32 (n_groups + 1 offsets), cols.starts_in and cols.stops_in (any order inside a
 // group) by work queued on the compute stream, and calls run with the largest group's size.
 int gams_index_build_begin(gams_gpu_t *h, uint32_t n_groups, uint64_t m, IndexBuild *B) {
-    *B = IndexBuild();
     // Lapper::new on the device: intervals.sort() by (start, stop) inside every group = a stable
     // segmented radix sort of the packed 64-bit keys; the stops are also sorted on their own.  The
     // bucket directories and Lapper::max_len come from three small kernels over the sorted arrays.
-    const uint32_t ng1 = std::max<uint32_t>(n_groups, 1);
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_cg = al((size_t)ng1 * sizeof(CountGroup));
-    const size_t b_groups = al((size_t)ng1 * sizeof(IndexGroup)), b_u32 = al(std::max<uint64_t>(m, 1) * 4),
-                 b_rec = al(std::max<uint64_t>(m, 1) * sizeof(IvRec)), b_dir = al((m + n_groups + 1) * 4);
     B->bk_slots = (m >> kCellShift) + 2ull * n_groups + 2;
-    const size_t b_bk = al(B->bk_slots * sizeof(BkRec));
     gams_index_t *ix = new gams_index_t();
     B->ix = ix;
     ix->n_groups = n_groups;
     ix->m = m;
-    hipError_t e = gams_pool_alloc(h, false, b_groups + b_cg + 2 * b_u32 + b_rec + b_dir + 2 * b_bk,
-                                   reinterpret_cast<void **>(&ix->arena), &ix->arena_bytes);
+    auto arena = [&](Carver &c) { return index_arena_layout<IndexGroup, CountGroup, IvRec, BkRec>(c, n_groups, m, B->bk_slots); };
+    auto scratch = [&](Carver &c) { return index_scratch_layout(c, n_groups, m); };
+    PoolBlock blk(h, false);
+    hipError_t e = blk.alloc(layout_bytes(arena));
     if (e != hipSuccess) return gams_index_build_fail(h, B, e, "hipMalloc(index)");
-    {
-        uint8_t *p = ix->arena;
-        ix->d_groups = reinterpret_cast<IndexGroup *>(p);
-        p += b_groups;
-        ix->d_cgroups = reinterpret_cast<CountGroup *>(p);
-        p += b_cg;
-        ix->d_stops = reinterpret_cast<uint32_t *>(p);
-        p += b_u32;
-        ix->d_lstart = reinterpret_cast<uint32_t *>(p);
-        p += b_u32;
-        ix->d_lrec = reinterpret_cast<IvRec *>(p);
-        p += b_rec;
-        ix->d_dir_start = reinterpret_cast<uint32_t *>(p);
-        p += b_dir;
-        ix->d_bk_start = reinterpret_cast<BkRec *>(p);     // 2 * bk_slots records, interleaved: cell j = [2j] starts, [2j+1] stops
-        ix->d_bk_stop = ix->d_bk_start + 1;
-    }
-    // scratch: raw columns, packed keys in/out, permutation in/out, 32-bit offsets, radix-sort storage
-    const size_t b_key = al(std::max<uint64_t>(m, 1) * 8), b_off = al(((size_t)n_groups + 1) * 4);
-    e = gams_pool_alloc(h, false, 2 * b_u32 + 2 * b_key + 2 * b_u32 + b_off, reinterpret_cast<void **>(&B->scratch),
-                        &B->scratch_bytes);
+    ix->arena = blk.release(&ix->arena_bytes);           // the index owns it from here (gams_index_destroy)
+    const auto a = carve(ix->arena, arena);
+    ix->d_groups = a.groups;
+    ix->d_cgroups = a.cgroups;
+    ix->d_stops = a.stops;
+    ix->d_lstart = a.lstart;
+    ix->d_lrec = a.lrec;
+    ix->d_dir_start = a.dir_start;
+    ix->d_bk_start = a.bk;     // 2 * bk_slots records, interleaved: cell j = [2j] starts, [2j+1] stops
+    ix->d_bk_stop = a.bk + 1;
+    // scratch: raw columns, packed keys in/out, permutation in/out, 32-bit offsets
+    e = B->scratch.alloc(layout_bytes(scratch));
     if (e != hipSuccess) return gams_index_build_fail(h, B, e, "hipMalloc(scratch)");
-    uint8_t *scratch = B->scratch;
-    B->d_starts_in = reinterpret_cast<uint32_t *>(scratch);
-    B->d_stops_in = reinterpret_cast<uint32_t *>(scratch + b_u32);
-    B->d_key_in = reinterpret_cast<uint64_t *>(scratch + 2 * b_u32);
-    B->d_key_out = reinterpret_cast<uint64_t *>(scratch + 2 * b_u32 + b_key);
-    B->d_val_in = reinterpret_cast<uint32_t *>(scratch + 2 * b_u32 + 2 * b_key);
-    B->d_val_out = reinterpret_cast<uint32_t *>(scratch + 3 * b_u32 + 2 * b_key);
-    B->d_off32 = reinterpret_cast<uint32_t *>(scratch + 4 * b_u32 + 2 * b_key);
+    B->cols = carve(B->scratch.p, scratch);
     return GAMS_OK;
 }
 
-// a failed build: the stream drained, everything of the build returned to the pools, the error reported
+// a failed build: everything of the build back in the pools (each block once its stream has drained), the error reported
 int gams_index_build_fail(gams_gpu_t *h, IndexBuild *B, hipError_t err, const char *what) {
     (void)hipGetLastError();
-    (void)hipStreamSynchronize(h->compute);
-    gams_pool_free(h, false, B->scratch, B->scratch_bytes);
-    gams_pool_free(h, false, B->d_tmp, B->d_tmp_bytes);
+    B->scratch.reset();
+    B->d_tmp.reset();
     gams_index_destroy(h, B->ix);
-    *B = IndexBuild();
+    B->ix = nullptr;
     return gams_fail(h, err == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,
                      std::string("index_create: ") + what + ": " + hipGetErrorString(err));
 }
@@ -723,9 +679,7 @@ int gams_index_build_run(gams_gpu_t *h, IndexBuild *B, uint32_t max_n, gams_inde
     gams_index_t *ix = B->ix;
     const uint32_t n_groups = ix->n_groups;
     const uint64_t m = ix->m, bk_slots = B->bk_slots;
-    uint32_t *d_starts_in = B->d_starts_in, *d_stops_in = B->d_stops_in, *d_off32 = B->d_off32;
-    uint64_t *d_key_in = B->d_key_in, *d_key_out = B->d_key_out;
-    uint32_t *d_val_in = B->d_val_in, *d_val_out = B->d_val_out;
+    const IndexScratch &c = B->cols;
     size_t tmp_bytes_pairs = 0, tmp_bytes_keys = 0;
     hipStream_t st = h->compute;
     hipError_t e;
@@ -733,58 +687,57 @@ int gams_index_build_run(gams_gpu_t *h, IndexBuild *B, uint32_t max_n, gams_inde
     if (n_groups && max_n <= kBuildCap) {
         // every group fits a workgroup: sort and every derived table in one kernel, one workgroup per group
         if (max_n <= 256)
-            e = index_build_launch<256, 128>(h, st, d_off32, n_groups, d_starts_in, d_stops_in, ix);
+            e = index_build_launch<256, 128>(h, st, c.off32, n_groups, c.starts_in, c.stops_in, ix);
         else if (max_n <= 1024)
-            e = index_build_launch<1024, 512>(h, st, d_off32, n_groups, d_starts_in, d_stops_in, ix);
+            e = index_build_launch<1024, 512>(h, st, c.off32, n_groups, c.starts_in, c.stops_in, ix);
         else if (max_n <= 2048)
-            e = index_build_launch<2048, 1024>(h, st, d_off32, n_groups, d_starts_in, d_stops_in, ix);
+            e = index_build_launch<2048, 1024>(h, st, c.off32, n_groups, c.starts_in, c.stops_in, ix);
         else if (max_n <= 4096)
-            e = index_build_launch<4096, 1024>(h, st, d_off32, n_groups, d_starts_in, d_stops_in, ix);
+            e = index_build_launch<4096, 1024>(h, st, c.off32, n_groups, c.starts_in, c.stops_in, ix);
         else
-            e = index_build_launch<8192, 1024>(h, st, d_off32, n_groups, d_starts_in, d_stops_in, ix);
+            e = index_build_launch<8192, 1024>(h, st, c.off32, n_groups, c.starts_in, c.stops_in, ix);
         if (e != hipSuccess) return fail(e, "group build");
     } else if (m) {
         // a group beyond the workgroup's LDS: the library's segmented radix sort + the table kernels
         const unsigned blocks = (unsigned)((m + 255) / 256);
-        hipLaunchKernelGGL(index_pack_kernel, dim3(blocks), dim3(256), 0, st, d_starts_in, d_stops_in, m, d_key_in,
-                           d_val_in);
+        hipLaunchKernelGGL(index_pack_kernel, dim3(blocks), dim3(256), 0, st, c.starts_in, c.stops_in, m, c.key_in,
+                           c.val_in);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "pack");
-        e = rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes_pairs, d_key_in, d_key_out, d_val_in, d_val_out,
-                                                (unsigned)m, n_groups, d_off32, d_off32 + 1, 0, 64, st);
+        e = rocprim::segmented_radix_sort_pairs(nullptr, tmp_bytes_pairs, c.key_in, c.key_out, c.val_in, c.val_out,
+                                                (unsigned)m, n_groups, c.off32, c.off32 + 1, 0, 64, st);
         if (e != hipSuccess) return fail(e, "radix sort (size query)");
-        e = rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes_keys, d_stops_in, ix->d_stops, (unsigned)m, n_groups,
-                                               d_off32, d_off32 + 1, 0, 32, st);
+        e = rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes_keys, c.stops_in, ix->d_stops, (unsigned)m, n_groups,
+                                               c.off32, c.off32 + 1, 0, 32, st);
         if (e != hipSuccess) return fail(e, "radix sort (size query)");
-        e = gams_pool_alloc(h, false, std::max<size_t>(std::max(tmp_bytes_pairs, tmp_bytes_keys), 256),
-                            reinterpret_cast<void **>(&B->d_tmp), &B->d_tmp_bytes);
+        e = B->d_tmp.alloc(std::max<size_t>(std::max(tmp_bytes_pairs, tmp_bytes_keys), 256));
         if (e != hipSuccess) return fail(e, "hipMalloc(sort storage)");
-        e = rocprim::segmented_radix_sort_pairs(B->d_tmp, tmp_bytes_pairs, d_key_in, d_key_out, d_val_in, d_val_out,
-                                                (unsigned)m, n_groups, d_off32, d_off32 + 1, 0, 64, st);
+        e = rocprim::segmented_radix_sort_pairs(B->d_tmp.p, tmp_bytes_pairs, c.key_in, c.key_out, c.val_in, c.val_out,
+                                                (unsigned)m, n_groups, c.off32, c.off32 + 1, 0, 64, st);
         if (e != hipSuccess) return fail(e, "radix sort of (start, stop)");
-        e = rocprim::segmented_radix_sort_keys(B->d_tmp, tmp_bytes_keys, d_stops_in, ix->d_stops, (unsigned)m, n_groups,
-                                               d_off32, d_off32 + 1, 0, 32, st);
+        e = rocprim::segmented_radix_sort_keys(B->d_tmp.p, tmp_bytes_keys, c.stops_in, ix->d_stops, (unsigned)m, n_groups,
+                                               c.off32, c.off32 + 1, 0, 32, st);
         if (e != hipSuccess) return fail(e, "radix sort of stops");
-        hipLaunchKernelGGL(index_unpack_kernel, dim3(blocks), dim3(256), 0, st, d_key_out, d_val_out, m, ix->d_lstart,
+        hipLaunchKernelGGL(index_unpack_kernel, dim3(blocks), dim3(256), 0, st, c.key_out, c.val_out, m, ix->d_lstart,
                            ix->d_lrec);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "unpack");
     }
     if (n_groups && max_n > kBuildCap) {
-        hipLaunchKernelGGL(index_group_kernel, dim3(n_groups), dim3(64), 0, st, d_off32, n_groups, ix->d_lrec,
+        hipLaunchKernelGGL(index_group_kernel, dim3(n_groups), dim3(64), 0, st, c.off32, n_groups, ix->d_lrec,
                            ix->d_lstart, ix->d_stops, ix->d_groups, ix->d_cgroups);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "group records");
         const uint64_t slots = m + n_groups;        // the last group's directory ends at m + n_groups (inclusive slot)
-        hipLaunchKernelGGL(index_dir_kernel, dim3((unsigned)((slots + 1 + 255) / 256)), dim3(256), 0, st, d_off32,
+        hipLaunchKernelGGL(index_dir_kernel, dim3((unsigned)((slots + 1 + 255) / 256)), dim3(256), 0, st, c.off32,
                            n_groups, slots + 1, ix->d_groups, ix->d_lstart, ix->d_dir_start);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "directories");
-        hipLaunchKernelGGL(index_bk_kernel, dim3((unsigned)((bk_slots + 255) / 256)), dim3(256), 0, st, d_off32,
+        hipLaunchKernelGGL(index_bk_kernel, dim3((unsigned)((bk_slots + 255) / 256)), dim3(256), 0, st, c.off32,
                            n_groups, bk_slots, ix->d_groups, ix->d_lstart, ix->d_stops, ix->d_bk_start, ix->d_bk_stop);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "bucket records");
     }
     if (done && (e = hipEventRecord(done, st)) != hipSuccess) return fail(e, "index build");
     if ((e = hipStreamSynchronize(st)) != hipSuccess) return fail(e, "index build");
-    gams_pool_free(h, false, B->scratch, B->scratch_bytes);
-    gams_pool_free(h, false, B->d_tmp, B->d_tmp_bytes);
-    *B = IndexBuild();
+    B->scratch.reset();
+    B->d_tmp.reset();
+    B->ix = nullptr;
     *out = ix;
     return GAMS_OK;
 }
@@ -802,21 +755,21 @@ int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
     if (m > 0xfffffff0ull)
         return gams_fail(h, GAMS_EUNSUPPORTED, "index_create: more than 2^32-16 intervals in one index");
     GAMS_HIP(h, hipSetDevice(h->device));
-    IndexBuild B;
+    IndexBuild B(h);
     const int rc = gams_index_build_begin(h, n_groups, m, &B);
     if (rc != GAMS_OK) return rc;
     hipStream_t st = h->compute;
     hipError_t e;
     std::vector<uint32_t> off32((size_t)n_groups + 1);
     for (uint32_t g = 0; g <= n_groups; ++g) off32[g] = (uint32_t)group_off[g];
-    if ((e = hipMemcpyAsync(B.d_off32, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+    if ((e = hipMemcpyAsync(B.cols.off32, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
         return gams_index_build_fail(h, &B, e, "copy offsets");
     uint32_t max_n = 0;
     for (uint32_t g = 0; g < n_groups; ++g) max_n = std::max(max_n, off32[g + 1] - off32[g]);
     if (m) {
-        if ((e = hipMemcpyAsync(B.d_starts_in, starts, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+        if ((e = hipMemcpyAsync(B.cols.starts_in, starts, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
             return gams_index_build_fail(h, &B, e, "copy starts");
-        if ((e = hipMemcpyAsync(B.d_stops_in, stops, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
+        if ((e = hipMemcpyAsync(B.cols.stops_in, stops, m * 4, hipMemcpyHostToDevice, st)) != hipSuccess)
             return gams_index_build_fail(h, &B, e, "copy stops");
     }
     return gams_index_build_run(h, &B, max_n, out);

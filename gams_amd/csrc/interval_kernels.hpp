@@ -50,6 +50,8 @@ struct BkRec {
 #ifndef GAMS_CELL_SHIFT
 #define GAMS_CELL_SHIFT 1
 #endif
+static_assert(sizeof(IndexGroup) == 80 && sizeof(CountGroup) == 32 && sizeof(IvRec) == 16 && sizeof(BkRec) == 32,
+              "tests/layout_main.cpp carves the index arena with stand-ins of these sizes");
 constexpr uint32_t kCellShift = GAMS_CELL_SHIFT;   // about 2^kCellShift keys per cell of the count path's grid
 
 struct SpanRec {
@@ -81,19 +83,17 @@ struct gams_index {
 };
 
 // One index build, between its two steps (interval.hip): gams_index_build_begin allocates the index and the scratch,
-// the caller queues on the compute stream whatever fills d_off32 (n_groups + 1 offsets), d_starts_in and d_stops_in,
+// the caller queues on the compute stream whatever fills cols.off32 (n_groups + 1 offsets), cols.starts_in and cols.stops_in,
 // and gams_index_build_run sorts, derives the tables, waits and hands the index out.  gams_index_create is the front
 // that fills the columns from host arrays; gams_index_create_range_text (text.hip) fills them by a gather kernel.
 // A step that fails has already returned everything to the pools (gams_index_build_fail does that for the caller's
 // own errors in between).
 struct IndexBuild {
+    explicit IndexBuild(gams_gpu_t *h) : scratch(h, false), d_tmp(h, false) {}
     gams_index *ix = nullptr;
-    uint32_t *d_off32 = nullptr, *d_starts_in = nullptr, *d_stops_in = nullptr;   // the builder's inputs
-    uint64_t *d_key_in = nullptr, *d_key_out = nullptr;                           // groups beyond a workgroup: the radix sort's buffers
-    uint32_t *d_val_in = nullptr, *d_val_out = nullptr;
+    IndexScratch cols{};          // the builder's inputs (off32, starts_in, stops_in), and the radix sort's buffers
     uint64_t bk_slots = 0;
-    uint8_t *scratch = nullptr, *d_tmp = nullptr;
-    size_t scratch_bytes = 0, d_tmp_bytes = 0;
+    PoolBlock scratch, d_tmp;     // behind cols; the radix sort's storage
 };
 int gams_index_build_begin(gams_gpu_t *h, uint32_t n_groups, uint64_t m, IndexBuild *B);
 // (done, if given: an event recorded on the compute stream behind the build's last kernel, before the host waits)

@@ -168,6 +168,7 @@ struct SwCtg {
     uint32_t rg_group;    // its group of the rg index (-a count); >= n_groups: none, counts are 0
     uint32_t pad;
 };
+static_assert(sizeof(SwCtg) == 32, "tests/layout_main.cpp carves with a stand-in of this size");
 
 struct SwArgs {
     const uint32_t *pm;
@@ -609,25 +610,311 @@ struct SwTextReq {                       // what gams_gpu_sw_text adds to a batc
     const uint64_t **ctg_off;
 };
 
-struct SwCountReq {                      // what -a count adds to a call: the rg index, the group of every selected ctg
-    const gams_index_t *ix;
-    const uint32_t *group;
+// one call of the batch entries: rows (gams_gpu_sw_batch: gc), count (gams_gpu_sw_count_batch: count) or tx (the text
+// entries: any action set)
+struct SwReq {
+    gams_gpu_t *h;
+    gams_seqset_t *s;
+    uint32_t n_sel;
+    const uint32_t *ctg_index;
+    const int32_t *chr_start;
+    const uint64_t *feat_off;
+    const int32_t *feat_start, *feat_end;
+    int32_t size, max, resize;
+    uint32_t actions;
+    const gams_index_t *rg_ix;           // -a count: the rg index, the group of every selected ctg
+    const uint32_t *rg_group;
+    gams_sw_row_t *rows;
+    int32_t *count;
+    uint64_t cap;
+    uint64_t *row_off, *n_rows;
+    const SwTextReq *tx;
 };
-}  // namespace
 
-// rows (gams_gpu_sw_batch: gc), count (gams_gpu_sw_count_batch: count) or tx (the text entries: any action set)
-static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
-                         const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
-                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
-                         const SwCountReq &cr, gams_sw_row_t *rows, int32_t *count, uint64_t cap, uint64_t *row_off,
-                         uint64_t *n_rows, const SwTextReq *tx);
+using SwCols = SwStage<SwCtg>;
+const std::string kSw = "gpu_sw", kSwText = "gpu_sw_text", kRangeGc = "gpu_range_gc";
+
+// 1. the arguments; *nf = the features of the call, 0 with GAMS_OK: nothing to do
+int sw_check(const SwReq &q, uint32_t *nf) {
+    gams_gpu_t *h = q.h;
+    *nf = 0;
+    if (!h || !q.s || !q.n_rows || (q.n_sel && (!q.ctg_index || !q.chr_start || !q.feat_off)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
+    // size or resize 1: half_resize = 0 makes center_resize slice [mid+1, mid-1] (window.rs:113-123),
+    // an empty span whose min()/max() the reference then asks for -- no defined answer to mirror
+    if (q.size < 2 || q.max < 0 || q.resize < 2)
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw: size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
+    *q.n_rows = 0;
+    if (q.row_off)
+        for (uint32_t k = 0; k <= q.n_sel; ++k) q.row_off[k] = 0;
+    if (q.n_sel == 0) return GAMS_OK;
+    if (q.feat_off[0] != 0) return gams_fail(h, GAMS_EINVAL, "gpu_sw: feat_off[0] must be 0");
+    for (uint32_t k = 0; k < q.n_sel; ++k) {
+        if (q.ctg_index[k] >= q.s->n_ctg) return gams_fail(h, GAMS_EINVAL, "gpu_sw: ctg index out of range");
+        if (q.feat_off[k + 1] < q.feat_off[k]) return gams_fail(h, GAMS_EINVAL, "gpu_sw: feat_off must not decrease");
+        const uint32_t len = q.s->len[q.ctg_index[k]];
+        if (len == 0 || len > 0x7fffffffu) return gams_fail(h, GAMS_EINVAL, "gpu_sw: ctg length out of range");
+    }
+    const uint64_t nf64 = q.feat_off[q.n_sel];
+    if (nf64 == 0) return GAMS_OK;
+    if (!q.feat_start || !q.feat_end) return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
+    // one thread per (feature, slot); max beyond 2^24 windows a side cannot exist in a ctg of < 2^31 bases
+    // and would overflow the product
+    if (q.max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: max beyond 2^24 windows a side");
+    const uint64_t threads = nf64 * (1u + 2u * (uint64_t)q.max);
+    if (nf64 > 0xffffffffull || (threads + 255) / 256 > 0x7fffffffull)
+        return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: too many feature slots for one launch");
+    *nf = (uint32_t)nf64;
+    return GAMS_OK;
+}
+
+// 2. the rows of every feature from the closed form (window.rs:29-41) -> exclusive offsets in in.row_off, the first row
+// of every selected ctg in crow (and q.row_off), and the kernel's inputs where `in` has them (a size query has none)
+int sw_host_rows(const SwReq &q, uint32_t nf, const SwCols &in, std::vector<uint64_t> &crow, uint64_t *n_rows) {
+    const bool do_count = (q.actions & GAMS_SW_COUNT) != 0;
+    uint64_t tot = 0;
+    for (uint32_t k = 0; k < q.n_sel; ++k) {
+        const uint32_t i = q.ctg_index[k];
+        const int32_t cs = q.chr_start[k], ce = cs + (int32_t)q.s->len[i] - 1;
+        if (q.row_off) q.row_off[k] = tot;
+        crow[k] = tot;
+        if (in.ctgs)
+            in.ctgs[k] = SwCtg{q.s->off[i], q.s->len[i], cs, ce, (uint32_t)q.feat_off[k], do_count ? q.rg_group[k] : UINT32_MAX, 0u};
+        for (uint64_t f = q.feat_off[k]; f < q.feat_off[k + 1]; ++f) {
+            // window.rs:98-110: the middle pair of the feature must be members of the ctg span --
+            // IntSpan::index of a non-member has no defined answer in the reference to mirror
+            const int64_t flen = (int64_t)q.feat_end[f] - q.feat_start[f] + 1, half = flen / 2;
+            const int64_t mid_l = half == 0 ? q.feat_start[f] : (int64_t)q.feat_start[f] + half - 1;
+            const int64_t mid_r = half == 0 ? q.feat_start[f] : (int64_t)q.feat_start[f] + half;
+            if (flen < 1 || mid_l < cs || mid_r > ce)
+                return gams_fail(q.h, GAMS_EINVAL, "gpu_sw: feature " + std::to_string(f - q.feat_off[k]) +
+                                                       (q.n_sel > 1 ? " of selected ctg " + std::to_string(k) : std::string()) +
+                                                       " is empty or has its middle outside the ctg");
+            in.row_off[f] = tot;
+            const SwGeom g = sw_geometry(cs, ce, q.feat_start[f], q.feat_end[f], q.size, q.max);
+            tot += 1u + (uint64_t)g.n_l + (uint64_t)g.n_r;
+            if (in.fs) {
+                in.fs[f] = q.feat_start[f];
+                in.fe[f] = q.feat_end[f];
+                in.fctg[f] = k;
+            }
+        }
+    }
+    in.row_off[nf] = tot;
+    if (q.row_off) q.row_off[q.n_sel] = tot;
+    crow[q.n_sel] = tot;
+    *n_rows = tot;
+    return GAMS_OK;
+}
+
+// 3. the kernel over the uploaded inputs `d`: n_out rows (and counts)
+int sw_launch(const SwReq &q, uint32_t nf, uint64_t n_out, const SwCols &d, gams_sw_row_t *d_rows, int32_t *d_cnt) {
+    gams_gpu_t *h = q.h;
+    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
+    SwArgs a{};
+    if (do_gc) {
+        a.pm = q.s->gcindex->d_pm;
+        a.seg = q.s->gcindex->d_seg;
+    }
+    if (do_count) {
+        a.cgroups = q.rg_ix->d_cgroups;
+        a.rg_starts = q.rg_ix->d_lstart;
+        a.rg_stops = q.rg_ix->d_stops;
+        a.bk_start = q.rg_ix->d_bk_start;
+        a.bk_stop = q.rg_ix->d_bk_stop;
+        a.n_groups = q.rg_ix->n_groups;
+        a.cnt = d_cnt;
+    }
+    a.ctgs = d.ctgs;
+    a.fs = d.fs;
+    a.fe = d.fe;
+    a.fctg = d.fctg;
+    a.row_off = d.row_off;
+    a.nf = nf;
+    a.size = q.size;
+    a.max = q.max;
+    a.resize = q.resize;
+    a.rows = d_rows;
+    a.cap = n_out;
+    GAMS_TRY(h, kSw, hipEventRecord(h->k0, h->compute));
+    const dim3 grid((unsigned)(((uint64_t)nf * (1u + 2u * (uint64_t)q.max) + 255) / 256));
+    if (do_gc && do_count)
+        hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(256), 0, h->compute, a);
+    else if (do_gc)
+        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(256), 0, h->compute, a);
+    else if (do_count)
+        hipLaunchKernelGGL((sw_kernel<false, true>), grid, dim3(256), 0, h->compute, a);
+    else
+        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(256), 0, h->compute, a);
+    GAMS_TRY(h, kSw, hipGetLastError());
+    GAMS_TRY(h, kSw, hipEventRecord(h->k1, h->compute));
+    h->k_valid = true;
+    h->kq_used = 0;
+    return GAMS_OK;
+}
+
+// the chromosome names and the feature ids of a text call, each as one blob with its offsets, and the longest of each
+struct SwTextBlobs {
+    std::vector<uint32_t> name_off, id_off;
+    std::string names, ids;
+    size_t max_name = 0, max_id = 0;
+};
+int sw_text_blobs(const SwReq &q, uint32_t nf, SwTextBlobs &b) {
+    const SwTextReq *tx = q.tx;
+    b.name_off.resize((size_t)q.n_sel + 1);
+    b.id_off.resize((size_t)nf + 1);
+    for (uint32_t k = 0; k < q.n_sel; ++k) {
+        b.name_off[k] = (uint32_t)b.names.size();
+        if (!tx->chr[k]) return gams_fail(q.h, GAMS_EINVAL, "gpu_sw_text: null chromosome name");
+        const size_t before = b.names.size();
+        b.names += tx->chr[k];
+        b.max_name = std::max(b.max_name, b.names.size() - before);
+    }
+    b.name_off[q.n_sel] = (uint32_t)b.names.size();
+    for (uint32_t f = 0; f < nf; ++f) {
+        b.id_off[f] = (uint32_t)b.ids.size();
+        if (!tx->feat_id[f] || b.ids.size() > 0xF0000000ull)
+            return gams_fail(q.h, GAMS_EINVAL, "gpu_sw_text: null feature id, or more than 4 GB of ids");
+        const size_t before = b.ids.size();
+        b.ids += tx->feat_id[f];
+        b.max_id = std::max(b.max_id, b.ids.size() - before);
+    }
+    b.id_off[nf] = (uint32_t)b.ids.size();
+    return GAMS_OK;
+}
+
+// 4. (text entries) the n_out rows on the device -> TSV text in the handle's page-locked buffer
+int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vector<uint64_t> &crow, const SwCols &d,
+                    const gams_sw_row_t *d_rows, const int32_t *d_cnt) {
+    gams_gpu_t *h = q.h;
+    const SwTextReq *tx = q.tx;
+    const uint32_t n_sel = q.n_sel;
+    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
+    SwTextBlobs B;
+    const int rc = sw_text_blobs(q, nf, B);
+    if (rc != GAMS_OK) return rc;
+    const uint32_t nb = (uint32_t)((n_out + kSwTextBlock - 1) / kSwTextBlock);
+    const uint64_t text_cap = std::max<uint64_t>(n_out * (uint64_t)(B.max_id + B.max_name + (do_count ? 112 : 96)), 4096);
+    const size_t n_words = (size_t)n_sel + 3;
+    auto tabs = [&](Carver &c) { return sw_text_tabs_layout(c, n_sel, nf, B.names.size(), B.ids.size()); };
+    SwTextArgs ta{};
+    unsigned long long *blk_off = nullptr;
+    auto dev = [&](Carver &c) {   // tables | row lengths | block lengths and offsets | words | text
+        const SwTextTabs t = tabs(c);
+        ta.ctg_row_off = t.ctg_row_off;
+        ta.name_off = t.name_off;
+        ta.names = t.names;
+        ta.id_off = t.id_off;
+        ta.ids = t.ids;
+        ta.len = c.take<uint32_t>(std::max<uint64_t>(n_out, 1));
+        ta.blk_len = c.take<uint32_t>(std::max(nb, 1u));
+        ta.blk_off = blk_off = c.take<unsigned long long>((size_t)nb + 1);
+        ta.words = c.take<unsigned long long>(n_words);
+        ta.text = c.take<char>(text_cap);
+    };
+    const size_t tab_bytes = layout_bytes(tabs);
+    PoolBlock tdev(h, false), tpin(h, true);
+    GAMS_TRY(h, kSwText, tpin.alloc(tab_bytes));
+    GAMS_TRY(h, kSwText, tdev.alloc(layout_bytes(dev)));
+    const SwTextTabs ht = carve(tpin.p, tabs);
+    std::memcpy(ht.ctg_row_off, crow.data(), crow.size() * 8);
+    std::memcpy(ht.name_off, B.name_off.data(), B.name_off.size() * 4);
+    std::memcpy(ht.names, B.names.data(), B.names.size());
+    std::memcpy(ht.id_off, B.id_off.data(), B.id_off.size() * 4);
+    std::memcpy(ht.ids, B.ids.data(), B.ids.size());
+    GAMS_TRY(h, kSwText, hipMemcpyAsync(tdev.p, tpin.p, tab_bytes, hipMemcpyHostToDevice, h->compute));
+    carve(tdev.p, dev);
+    ta.rows = d_rows;
+    ta.n_rows = n_out;
+    ta.ctgs = d.ctgs;
+    ta.n_sel = n_sel;
+    ta.feat_row_off = d.row_off;
+    ta.nb = nb;
+    ta.text_cap = text_cap;
+    ta.gc = do_gc ? 1u : 0u;
+    ta.cnt = d_cnt;
+    GAMS_TRY(h, kSwText, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), h->compute));
+    if (nb) {
+        hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
+        hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, h->compute, ta.blk_len, nb, blk_off, ta.words,
+                           0u);
+        hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
+        hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, h->compute, ta);
+        GAMS_TRY(h, kSwText, hipGetLastError());
+    }
+    // the words first (total, flag, per-ctg offsets), then the text -- whose size they say -- into the handle's
+    // page-locked text buffer, valid until the next call
+    GAMS_TRY(h, kSwText, gams_pool_grow(h, true, &h->sw_words, &h->sw_words_bytes, n_words * 8, n_words * 8));
+    GAMS_TRY(h, kSwText, hipMemcpyAsync(h->sw_words, ta.words, n_words * 8, hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kSwText, hipStreamSynchronize(h->compute));
+    const uint64_t bytes = h->sw_words[0];
+    if (h->sw_words[1] != 0 || bytes > text_cap)
+        return gams_fail(h, GAMS_EUNSUPPORTED,
+                         "gpu_sw_text: a value this formatter does not cover (a statistic of 1000 or more, a negative "
+                         "coordinate): format gams_gpu_sw_batch's rows on the host");
+    GAMS_TRY(h, kSwText, gams_pool_grow(h, true, &h->sw_text, &h->sw_text_bytes, bytes, bytes + bytes / 8 + 4096));
+    if (bytes) GAMS_TRY(h, kSwText, hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kSwText, hipStreamSynchronize(h->compute));
+    *tx->text = bytes ? h->sw_text : nullptr;
+    *tx->text_bytes = bytes;
+    if (tx->ctg_off) *tx->ctg_off = reinterpret_cast<const uint64_t *>(h->sw_words + 2);
+    return GAMS_OK;
+}
+
+int sw_batch_impl(const SwReq &q) {
+    gams_gpu_t *h = q.h;
+    uint32_t nf = 0;
+    int rc = sw_check(q, &nf);
+    if (rc != GAMS_OK || nf == 0) return rc;
+    GAMS_HIP(h, hipSetDevice(h->device));
+    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
+    // Inputs are assembled in one page-locked block (one DMA): ctgs | fs | fe | fctg | off
+    auto inputs = [&](Carver &c) { return sw_stage_layout<SwCtg>(c, q.n_sel, nf, true); };
+    const size_t in_bytes = layout_bytes(inputs);
+    const bool size_query = !q.tx && ((!q.rows && !q.count) || q.cap == 0);
+    PoolBlock dev(h, false), pin(h, true);
+    std::vector<uint64_t> crow((size_t)q.n_sel + 1, 0);    // first row of every selected ctg (text mode)
+    std::vector<uint64_t> off_host(size_query ? (size_t)nf + 1 : 0);   // a size query: no device, no pinned memory
+    SwCols in{};
+    in.row_off = off_host.data();
+    if (!size_query) {
+        GAMS_TRY(h, kSw, pin.alloc(in_bytes));
+        in = carve(pin.p, inputs);
+    }
+    uint64_t tot = 0;
+    if ((rc = sw_host_rows(q, nf, in, crow, &tot)) != GAMS_OK) return rc;
+    *q.n_rows = tot;
+    if (size_query) return GAMS_OK;
+    // the counts and the geometry read no sequence byte: a count-only call leaves the bytes alone
+    if (do_gc && (rc = gams_seqset_gcindex(h, q.s)) != GAMS_OK) return rc;
+    const uint64_t n_out = std::min<uint64_t>(tot, q.tx ? tot : q.cap);   // text mode: every row, kept on the device
+    SwCols d{};
+    gams_sw_row_t *d_rows = nullptr;
+    int32_t *d_cnt = nullptr;
+    auto device = [&](Carver &c) {   // the inputs | rows | counts
+        d = inputs(c);
+        d_rows = c.take_tight<gams_sw_row_t>(std::max<uint64_t>(n_out, 1));
+        d_cnt = do_count ? c.take<int32_t>(std::max<uint64_t>(n_out, 1)) : nullptr;
+    };
+    GAMS_TRY(h, kSw, dev.alloc(layout_bytes(device)));
+    carve(dev.p, device);
+    GAMS_TRY(h, kSw, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
+    if ((rc = sw_launch(q, nf, n_out, d, d_rows, d_cnt)) != GAMS_OK) return rc;
+    if (q.tx) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt);
+    // 5. read back
+    if (q.rows) GAMS_TRY(h, kSw, hipMemcpyAsync(q.rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
+    if (q.count) GAMS_TRY(h, kSw, hipMemcpyAsync(q.count, d_cnt, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kSw, hipStreamSynchronize(h->compute));
+    return GAMS_OK;
+}
+}  // namespace
 
 extern "C" int gams_gpu_sw_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                                  const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
                                  const int32_t *feat_end, int32_t size, int32_t max, int32_t resize,
                                  gams_sw_row_t *rows, uint64_t cap, uint64_t *row_off, uint64_t *n_rows) {
-    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, GAMS_SW_GC,
-                         SwCountReq{nullptr, nullptr}, rows, nullptr, cap, row_off, n_rows, nullptr);
+    return sw_batch_impl(SwReq{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, GAMS_SW_GC,
+                               nullptr, nullptr, rows, nullptr, cap, row_off, n_rows, nullptr});
 }
 
 extern "C" int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -637,8 +924,8 @@ extern "C" int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
                                        uint64_t *n_rows) {
     if (!rg_ix || (n_sel && !rg_group)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_count: null rg index or rg groups");
     // resize only shapes the gc statistics, which this call does not compute: any value the checks accept
-    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, 2, GAMS_SW_COUNT,
-                         SwCountReq{rg_ix, rg_group}, nullptr, count, cap, row_off, n_rows, nullptr);
+    return sw_batch_impl(SwReq{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, 2, GAMS_SW_COUNT,
+                               rg_ix, rg_group, nullptr, count, cap, row_off, n_rows, nullptr});
 }
 
 extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -656,9 +943,9 @@ extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_
     const SwTextReq tx{chr, feat_id, text, text_bytes, ctg_off};
     *text = nullptr;
     *text_bytes = 0;
-    const SwCountReq cr = (actions & GAMS_SW_COUNT) ? SwCountReq{rg_ix, rg_group} : SwCountReq{nullptr, nullptr};
-    return sw_batch_impl(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions, cr,
-                         nullptr, nullptr, 0, nullptr, n_rows, &tx);
+    const bool cnt = (actions & GAMS_SW_COUNT) != 0;
+    return sw_batch_impl(SwReq{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions,
+                               cnt ? rg_ix : nullptr, cnt ? rg_group : nullptr, nullptr, nullptr, 0, nullptr, n_rows, &tx});
 }
 
 extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -668,313 +955,6 @@ extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel,
                                 const uint64_t **ctg_off, uint64_t *n_rows) {
     return gams_gpu_sw_text_actions(h, s, n_sel, ctg_index, chr, chr_start, feat_off, feat_start, feat_end, feat_id, size,
                                     max, resize, GAMS_SW_GC, nullptr, nullptr, text, text_bytes, ctg_off, n_rows);
-}
-
-static int sw_batch_impl(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
-                         const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
-                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
-                         const SwCountReq &cr, gams_sw_row_t *rows, int32_t *count, uint64_t cap, uint64_t *row_off,
-                         uint64_t *n_rows, const SwTextReq *tx) {
-    if (!h || !s || !n_rows || (n_sel && (!ctg_index || !chr_start || !feat_off)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
-    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
-    // size or resize 1: half_resize = 0 makes center_resize slice [mid+1, mid-1] (window.rs:113-123),
-    // an empty span whose min()/max() the reference then asks for -- no defined answer to mirror
-    if (size < 2 || max < 0 || resize < 2)
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw: size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
-    *n_rows = 0;
-    if (row_off)
-        for (uint32_t k = 0; k <= n_sel; ++k) row_off[k] = 0;
-    if (n_sel == 0) return GAMS_OK;
-    if (feat_off[0] != 0) return gams_fail(h, GAMS_EINVAL, "gpu_sw: feat_off[0] must be 0");
-    for (uint32_t k = 0; k < n_sel; ++k) {
-        if (ctg_index[k] >= s->n_ctg) return gams_fail(h, GAMS_EINVAL, "gpu_sw: ctg index out of range");
-        if (feat_off[k + 1] < feat_off[k]) return gams_fail(h, GAMS_EINVAL, "gpu_sw: feat_off must not decrease");
-        const uint32_t len = s->len[ctg_index[k]];
-        if (len == 0 || len > 0x7fffffffu) return gams_fail(h, GAMS_EINVAL, "gpu_sw: ctg length out of range");
-    }
-    const uint64_t nf64 = feat_off[n_sel];
-    if (nf64 == 0) return GAMS_OK;
-    if (!feat_start || !feat_end) return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
-    // one thread per (feature, slot); max beyond 2^24 windows a side cannot exist in a ctg of < 2^31 bases
-    // and would overflow the product
-    if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: max beyond 2^24 windows a side");
-    const uint64_t threads = nf64 * (1u + 2u * (uint64_t)max);
-    if (nf64 > 0xffffffffull || (threads + 255) / 256 > 0x7fffffffull)
-        return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: too many feature slots for one launch");
-    const uint32_t nf = (uint32_t)nf64;
-    GAMS_HIP(h, hipSetDevice(h->device));
-
-    // Inputs are assembled in one page-locked block (one DMA): ctgs | fs | fe | fctg | off; the rows per
-    // feature come from the closed form (window.rs:29-41) -> exclusive offsets.
-    const size_t b_ctg = ((size_t)n_sel * sizeof(SwCtg) + 255) & ~(size_t)255;
-    const size_t b_i32 = ((size_t)nf * sizeof(int32_t) + 255) & ~(size_t)255;
-    const size_t b_off = (((size_t)nf + 1) * sizeof(uint64_t) + 255) & ~(size_t)255;
-    const size_t in_bytes = b_ctg + 3 * b_i32 + b_off;
-    const bool size_query = !tx && ((!rows && !count) || cap == 0);
-    std::vector<uint64_t> crow((size_t)n_sel + 1, 0);    // first row of every selected ctg (text mode)
-    uint8_t *pin = nullptr, *dev = nullptr;
-    size_t pin_cap = 0, dev_cap = 0;
-    std::vector<uint64_t> off_host;                 // size query: no device, no pinned memory
-    uint64_t *off = nullptr;
-    SwCtg *cg = nullptr;
-    int32_t *fs = nullptr, *fe = nullptr;
-    uint32_t *fctg = nullptr;
-    if (size_query) {
-        off_host.resize((size_t)nf + 1);
-        off = off_host.data();
-    } else {
-        const hipError_t e = gams_pool_alloc(h, true, in_bytes, reinterpret_cast<void **>(&pin), &pin_cap);
-        if (e != hipSuccess) return gams_fail(h, GAMS_ENOMEM, std::string("gpu_sw: pinned staging: ") + hipGetErrorString(e));
-        cg = reinterpret_cast<SwCtg *>(pin);
-        fs = reinterpret_cast<int32_t *>(pin + b_ctg);
-        fe = reinterpret_cast<int32_t *>(pin + b_ctg + b_i32);
-        fctg = reinterpret_cast<uint32_t *>(pin + b_ctg + 2 * b_i32);
-        off = reinterpret_cast<uint64_t *>(pin + b_ctg + 3 * b_i32);
-    }
-    auto release = [&]() {
-        if (pin) gams_pool_free(h, true, pin, pin_cap);
-        if (dev) gams_pool_free(h, false, dev, dev_cap);
-    };
-    uint64_t tot = 0;
-    for (uint32_t k = 0; k < n_sel; ++k) {
-        const uint32_t i = ctg_index[k];
-        const int32_t cs = chr_start[k], ce = cs + (int32_t)s->len[i] - 1;
-        if (row_off) row_off[k] = tot;
-        crow[k] = tot;
-        if (cg) cg[k] = SwCtg{s->off[i], s->len[i], cs, ce, (uint32_t)feat_off[k], do_count ? cr.group[k] : UINT32_MAX, 0u};
-        for (uint64_t f = feat_off[k]; f < feat_off[k + 1]; ++f) {
-            // window.rs:98-110: the middle pair of the feature must be members of the ctg span --
-            // IntSpan::index of a non-member has no defined answer in the reference to mirror
-            const int64_t flen = (int64_t)feat_end[f] - feat_start[f] + 1, half = flen / 2;
-            const int64_t mid_l = half == 0 ? feat_start[f] : (int64_t)feat_start[f] + half - 1;
-            const int64_t mid_r = half == 0 ? feat_start[f] : (int64_t)feat_start[f] + half;
-            if (flen < 1 || mid_l < cs || mid_r > ce) {
-                release();
-                return gams_fail(h, GAMS_EINVAL, "gpu_sw: feature " + std::to_string(f - feat_off[k]) +
-                                                     (n_sel > 1 ? " of selected ctg " + std::to_string(k) : std::string()) +
-                                                     " is empty or has its middle outside the ctg");
-            }
-            off[f] = tot;
-            const SwGeom g = sw_geometry(cs, ce, feat_start[f], feat_end[f], size, max);
-            tot += 1u + (uint64_t)g.n_l + (uint64_t)g.n_r;
-            if (fs) {
-                fs[f] = feat_start[f];
-                fe[f] = feat_end[f];
-                fctg[f] = k;
-            }
-        }
-    }
-    off[nf] = tot;
-    if (row_off) row_off[n_sel] = tot;
-    crow[n_sel] = tot;
-    *n_rows = tot;
-    if (size_query) return GAMS_OK;
-    if (tx) cap = tot;                                   // text mode: every row, kept on the device
-
-    if (do_gc) {   // the counts and the geometry read no sequence byte: a count-only call leaves the bytes alone
-        const int rc = gams_seqset_gcindex(h, s);
-        if (rc != GAMS_OK) {
-            release();
-            return rc;
-        }
-    }
-    const uint64_t n_out = std::min<uint64_t>(tot, cap);
-    const size_t b_rows = (size_t)std::max<uint64_t>(n_out, 1) * sizeof(gams_sw_row_t);
-    const size_t b_cnt = do_count ? (((size_t)std::max<uint64_t>(n_out, 1) * sizeof(int32_t) + 255) & ~(size_t)255) : 0;
-    hipError_t e = gams_pool_alloc(h, false, in_bytes + b_rows + b_cnt, reinterpret_cast<void **>(&dev), &dev_cap);
-    if (e != hipSuccess) {
-        release();
-        return gams_fail(h, GAMS_ENOMEM, std::string("gpu_sw: device buffers: ") + hipGetErrorString(e));
-    }
-#define SW_HIP(call)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            (void)hipStreamSynchronize(h->compute);                                    \
-            release();                                                                 \
-            return gams_fail(h, GAMS_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-        }                                                                              \
-    } while (0)
-    SW_HIP(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, h->compute));
-    gams_sw_row_t *d_rows = reinterpret_cast<gams_sw_row_t *>(dev + in_bytes);
-    int32_t *d_cnt = do_count ? reinterpret_cast<int32_t *>(dev + in_bytes + b_rows) : nullptr;
-    SwArgs a{};
-    if (do_gc) {
-        a.pm = s->gcindex->d_pm;
-        a.seg = s->gcindex->d_seg;
-    }
-    if (do_count) {
-        a.cgroups = cr.ix->d_cgroups;
-        a.rg_starts = cr.ix->d_lstart;
-        a.rg_stops = cr.ix->d_stops;
-        a.bk_start = cr.ix->d_bk_start;
-        a.bk_stop = cr.ix->d_bk_stop;
-        a.n_groups = cr.ix->n_groups;
-        a.cnt = d_cnt;
-    }
-    a.ctgs = reinterpret_cast<const SwCtg *>(dev);
-    a.fs = reinterpret_cast<const int32_t *>(dev + b_ctg);
-    a.fe = reinterpret_cast<const int32_t *>(dev + b_ctg + b_i32);
-    a.fctg = reinterpret_cast<const uint32_t *>(dev + b_ctg + 2 * b_i32);
-    a.row_off = reinterpret_cast<const uint64_t *>(dev + b_ctg + 3 * b_i32);
-    a.nf = nf;
-    a.size = size;
-    a.max = max;
-    a.resize = resize;
-    a.rows = d_rows;
-    a.cap = n_out;
-    SW_HIP(hipEventRecord(h->k0, h->compute));
-    {
-        const dim3 grid((unsigned)((threads + 255) / 256));
-        if (do_gc && do_count)
-            hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(256), 0, h->compute, a);
-        else if (do_gc)
-            hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(256), 0, h->compute, a);
-        else if (do_count)
-            hipLaunchKernelGGL((sw_kernel<false, true>), grid, dim3(256), 0, h->compute, a);
-        else
-            hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(256), 0, h->compute, a);
-    }
-    SW_HIP(hipGetLastError());
-    SW_HIP(hipEventRecord(h->k1, h->compute));
-    h->k_valid = true;
-    h->kq_used = 0;
-    if (tx) {
-        // ---- rows -> TSV text on the device ----------------------------------------------------------------------
-        std::vector<uint32_t> name_off((size_t)n_sel + 1), id_off((size_t)nf + 1);
-        std::string names, ids;
-        size_t max_name = 0, max_id = 0;
-        for (uint32_t k = 0; k < n_sel; ++k) {
-            name_off[k] = (uint32_t)names.size();
-            if (!tx->chr[k]) {
-                (void)hipStreamSynchronize(h->compute);
-                release();
-                return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null chromosome name");
-            }
-            const size_t before = names.size();
-            names += tx->chr[k];
-            max_name = std::max(max_name, names.size() - before);
-        }
-        name_off[n_sel] = (uint32_t)names.size();
-        for (uint32_t f = 0; f < nf; ++f) {
-            id_off[f] = (uint32_t)ids.size();
-            if (!tx->feat_id[f] || ids.size() > 0xF0000000ull) {
-                (void)hipStreamSynchronize(h->compute);
-                release();
-                return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature id, or more than 4 GB of ids");
-            }
-            const size_t before = ids.size();
-            ids += tx->feat_id[f];
-            max_id = std::max(max_id, ids.size() - before);
-        }
-        id_off[nf] = (uint32_t)ids.size();
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const uint32_t nb = (uint32_t)((n_out + kSwTextBlock - 1) / kSwTextBlock);
-        const size_t t_crow = al(((size_t)n_sel + 1) * 8), t_noff = al(((size_t)n_sel + 1) * 4), t_names = al(names.size() + 1),
-                     t_ioff = al(((size_t)nf + 1) * 4), t_ids = al(ids.size() + 1);
-        const size_t tab_bytes = t_crow + t_noff + t_names + t_ioff + t_ids;
-        const size_t b_len = al((size_t)std::max<uint64_t>(n_out, 1) * 4), b_blen = al((size_t)std::max(nb, 1u) * 4),
-                     b_boff = al(((size_t)nb + 1) * 8), b_words = al(((size_t)n_sel + 3) * 8);
-        const uint64_t text_cap = std::max<uint64_t>(n_out * (uint64_t)(max_id + max_name + (do_count ? 112 : 96)), 4096);
-        uint8_t *tpin = nullptr, *tdev = nullptr;
-        size_t tpin_cap = 0, tdev_cap = 0;
-        auto release_text = [&]() {
-            if (tpin) gams_pool_free(h, true, tpin, tpin_cap);
-            if (tdev) gams_pool_free(h, false, tdev, tdev_cap);
-        };
-#define SWT_HIP(call)                                                                  \
-    do {                                                                               \
-        hipError_t e_ = (call);                                                        \
-        if (e_ != hipSuccess) {                                                        \
-            (void)hipStreamSynchronize(h->compute);                                    \
-            release_text();                                                            \
-            release();                                                                 \
-            return gams_fail(h, e_ == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,   \
-                             std::string(#call) + ": " + hipGetErrorString(e_));       \
-        }                                                                              \
-    } while (0)
-        SWT_HIP(gams_pool_alloc(h, true, tab_bytes, reinterpret_cast<void **>(&tpin), &tpin_cap));
-        SWT_HIP(gams_pool_alloc(h, false, tab_bytes + b_len + b_blen + b_boff + b_words + al(text_cap),
-                                reinterpret_cast<void **>(&tdev), &tdev_cap));
-        std::memcpy(tpin, crow.data(), crow.size() * 8);
-        std::memcpy(tpin + t_crow, name_off.data(), name_off.size() * 4);
-        std::memcpy(tpin + t_crow + t_noff, names.data(), names.size());
-        std::memcpy(tpin + t_crow + t_noff + t_names, id_off.data(), id_off.size() * 4);
-        std::memcpy(tpin + t_crow + t_noff + t_names + t_ioff, ids.data(), ids.size());
-        SWT_HIP(hipMemcpyAsync(tdev, tpin, tab_bytes, hipMemcpyHostToDevice, h->compute));
-        SwTextArgs ta{};
-        ta.rows = d_rows;
-        ta.n_rows = n_out;
-        ta.ctgs = a.ctgs;
-        ta.ctg_row_off = reinterpret_cast<const uint64_t *>(tdev);
-        ta.n_sel = n_sel;
-        ta.feat_row_off = a.row_off;
-        ta.name_off = reinterpret_cast<const uint32_t *>(tdev + t_crow);
-        ta.names = reinterpret_cast<const char *>(tdev + t_crow + t_noff);
-        ta.id_off = reinterpret_cast<const uint32_t *>(tdev + t_crow + t_noff + t_names);
-        ta.ids = reinterpret_cast<const char *>(tdev + t_crow + t_noff + t_names + t_ioff);
-        uint8_t *q = tdev + tab_bytes;
-        ta.len = reinterpret_cast<uint32_t *>(q);
-        ta.blk_len = reinterpret_cast<uint32_t *>(q + b_len);
-        unsigned long long *blk_off = reinterpret_cast<unsigned long long *>(q + b_len + b_blen);
-        ta.blk_off = blk_off;
-        ta.nb = nb;
-        ta.words = reinterpret_cast<unsigned long long *>(q + b_len + b_blen + b_boff);
-        ta.text = reinterpret_cast<char *>(q + b_len + b_blen + b_boff + b_words);
-        ta.text_cap = text_cap;
-        ta.gc = do_gc ? 1u : 0u;
-        ta.cnt = d_cnt;
-        SWT_HIP(hipMemsetAsync(ta.words, 0, b_words, h->compute));
-        if (nb) {
-            hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
-            hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, h->compute, ta.blk_len, nb, blk_off, ta.words,
-                               0u);
-            hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
-            hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, h->compute, ta);
-            SWT_HIP(hipGetLastError());
-        }
-        // the words first (total, flag, per-ctg offsets), then the text -- whose size they say -- into the handle's
-        // page-locked text buffer, valid until the next call
-        const size_t n_words = (size_t)n_sel + 3;
-        if (h->sw_words_bytes < n_words * 8) {
-            gams_pool_free(h, true, h->sw_words, h->sw_words_bytes);
-            h->sw_words = nullptr;
-            h->sw_words_bytes = 0;
-            SWT_HIP(gams_pool_alloc(h, true, n_words * 8, reinterpret_cast<void **>(&h->sw_words), &h->sw_words_bytes));
-        }
-        SWT_HIP(hipMemcpyAsync(h->sw_words, ta.words, n_words * 8, hipMemcpyDeviceToHost, h->compute));
-        SWT_HIP(hipStreamSynchronize(h->compute));
-        const uint64_t bytes = h->sw_words[0];
-        if (h->sw_words[1] != 0 || bytes > text_cap) {
-            release_text();
-            release();
-            return gams_fail(h, GAMS_EUNSUPPORTED,
-                             "gpu_sw_text: a value this formatter does not cover (a statistic of 1000 or more, a negative "
-                             "coordinate): format gams_gpu_sw_batch's rows on the host");
-        }
-        if (h->sw_text_bytes < bytes) {
-            gams_pool_free(h, true, h->sw_text, h->sw_text_bytes);
-            h->sw_text = nullptr;
-            h->sw_text_bytes = 0;
-            SWT_HIP(gams_pool_alloc(h, true, bytes + bytes / 8 + 4096, reinterpret_cast<void **>(&h->sw_text), &h->sw_text_bytes));
-        }
-        if (bytes) SWT_HIP(hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, h->compute));
-        SWT_HIP(hipStreamSynchronize(h->compute));
-#undef SWT_HIP
-        *tx->text = bytes ? h->sw_text : nullptr;
-        *tx->text_bytes = bytes;
-        if (tx->ctg_off) *tx->ctg_off = reinterpret_cast<const uint64_t *>(h->sw_words + 2);
-        release_text();
-        release();
-        return GAMS_OK;
-    }
-    if (rows) SW_HIP(hipMemcpyAsync(rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
-    if (count) SW_HIP(hipMemcpyAsync(count, d_cnt, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, h->compute));
-    SW_HIP(hipStreamSynchronize(h->compute));
-#undef SW_HIP
-    release();
-    return GAMS_OK;
 }
 
 extern "C" int gams_gpu_sw(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_start,
@@ -1009,76 +989,51 @@ extern "C" int gams_gpu_range_gc_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
     const uint32_t n = (uint32_t)n64;
     GAMS_HIP(h, hipSetDevice(h->device));
     // inputs in one page-locked block (one DMA): ctgs | rs | re | rctg; results in the same device block
-    const size_t b_ctg = ((size_t)n_sel * sizeof(SwCtg) + 255) & ~(size_t)255;
-    const size_t b_i32 = ((size_t)n * sizeof(int32_t) + 255) & ~(size_t)255;
-    const size_t in_bytes = b_ctg + 3 * b_i32;
-    uint8_t *pin = nullptr, *dev = nullptr;
-    size_t pin_cap = 0, dev_cap = 0;
-    hipError_t e = gams_pool_alloc(h, true, in_bytes, reinterpret_cast<void **>(&pin), &pin_cap);
-    if (e != hipSuccess) return gams_fail(h, GAMS_ENOMEM, std::string("gpu_range_gc: pinned staging: ") + hipGetErrorString(e));
-    auto release = [&]() {
-        if (pin) gams_pool_free(h, true, pin, pin_cap);
-        if (dev) gams_pool_free(h, false, dev, dev_cap);
-    };
-    SwCtg *cg = reinterpret_cast<SwCtg *>(pin);
-    int32_t *rs = reinterpret_cast<int32_t *>(pin + b_ctg), *re = reinterpret_cast<int32_t *>(pin + b_ctg + b_i32);
-    uint32_t *rctg = reinterpret_cast<uint32_t *>(pin + b_ctg + 2 * b_i32);
+    auto inputs = [&](Carver &c) { return sw_stage_layout<SwCtg>(c, n_sel, n, false); };
+    const size_t in_bytes = layout_bytes(inputs);
+    PoolBlock dev(h, false), pin(h, true);
+    GAMS_TRY(h, kRangeGc, pin.alloc(in_bytes));
+    const SwCols in = carve(pin.p, inputs);
     for (uint32_t k = 0; k < n_sel; ++k) {
         const uint32_t i = ctg_index[k];
         const int32_t cs = chr_start[k];
         const int64_t ce = (int64_t)cs + s->len[i] - 1;
-        cg[k] = SwCtg{s->off[i], s->len[i], cs, (int32_t)ce, (uint32_t)range_off[k], UINT32_MAX, 0u};
+        in.ctgs[k] = SwCtg{s->off[i], s->len[i], cs, (int32_t)ce, (uint32_t)range_off[k], UINT32_MAX, 0u};
         // utils.rs:151-156 slices seq[from-1..to): a range outside the ctg (or inverted) panics there
         for (uint64_t q = range_off[k]; q < range_off[k + 1]; ++q) {
-            if (range_start[q] < cs || range_end[q] > ce || range_end[q] < range_start[q]) {
-                release();
+            if (range_start[q] < cs || range_end[q] > ce || range_end[q] < range_start[q])
                 return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: range " + std::to_string(q - range_off[k]) +
                                                      (n_sel > 1 ? " of selected ctg " + std::to_string(k) : std::string()) +
                                                      " is not inside the ctg");
-            }
-            rs[q] = range_start[q];
-            re[q] = range_end[q];
-            rctg[q] = k;
+            in.fs[q] = range_start[q];
+            in.fe[q] = range_end[q];
+            in.fctg[q] = k;
         }
     }
-    int rc = gams_seqset_gcindex(h, s);
-    if (rc != GAMS_OK) {
-        release();
-        return rc;
-    }
-    e = gams_pool_alloc(h, false, in_bytes + b_i32, reinterpret_cast<void **>(&dev), &dev_cap);
-    if (e != hipSuccess) {
-        release();
-        return gams_fail(h, GAMS_ENOMEM, std::string("gpu_range_gc: device buffers: ") + hipGetErrorString(e));
-    }
-#define R_HIP(call)                                                                            \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess) {                                                                \
-            (void)hipStreamSynchronize(h->compute);                                            \
-            release();                                                                         \
-            return gams_fail(h, GAMS_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-        }                                                                                      \
-    } while (0)
-    R_HIP(hipMemcpyAsync(dev, pin, in_bytes, hipMemcpyHostToDevice, h->compute));
-    float *d_gc = reinterpret_cast<float *>(dev + in_bytes);
+    const int rc = gams_seqset_gcindex(h, s);
+    if (rc != GAMS_OK) return rc;
+    SwCols d{};
+    float *d_gc = nullptr;
+    auto device = [&](Carver &c) {   // the inputs | results
+        d = inputs(c);
+        d_gc = c.take<float>(n);
+    };
+    GAMS_TRY(h, kRangeGc, dev.alloc(layout_bytes(device)));
+    carve(dev.p, device);
+    GAMS_TRY(h, kRangeGc, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
     SwArgs a{};
     a.pm = s->gcindex->d_pm;
     a.seg = s->gcindex->d_seg;
-    a.ctgs = reinterpret_cast<const SwCtg *>(dev);
-    a.fctg = reinterpret_cast<const uint32_t *>(dev + b_ctg + 2 * b_i32);
-    R_HIP(hipEventRecord(h->k0, h->compute));
-    hipLaunchKernelGGL(range_gc_kernel, dim3((n + 255) / 256), dim3(256), 0, h->compute, a,
-                       reinterpret_cast<const int32_t *>(dev + b_ctg), reinterpret_cast<const int32_t *>(dev + b_ctg + b_i32), n,
-                       d_gc);
-    R_HIP(hipGetLastError());
-    R_HIP(hipEventRecord(h->k1, h->compute));
+    a.ctgs = d.ctgs;
+    a.fctg = d.fctg;
+    GAMS_TRY(h, kRangeGc, hipEventRecord(h->k0, h->compute));
+    hipLaunchKernelGGL(range_gc_kernel, dim3((n + 255) / 256), dim3(256), 0, h->compute, a, d.fs, d.fe, n, d_gc);
+    GAMS_TRY(h, kRangeGc, hipGetLastError());
+    GAMS_TRY(h, kRangeGc, hipEventRecord(h->k1, h->compute));
     h->k_valid = true;
     h->kq_used = 0;
-    R_HIP(hipMemcpyAsync(gc, d_gc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->compute));
-    R_HIP(hipStreamSynchronize(h->compute));
-#undef R_HIP
-    release();
+    GAMS_TRY(h, kRangeGc, hipMemcpyAsync(gc, d_gc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kRangeGc, hipStreamSynchronize(h->compute));
     return GAMS_OK;
 }
 

@@ -492,20 +492,12 @@ struct TextJob {
 
 const char *const kEntry[3] = {"gpu_locate_text", "gpu_count_text", "gpu_anno_text"};
 
-#define T_HIP(call)                                                                                  \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return gams_fail(h, e_ == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP,                 \
-                             who + ": " + #call + ": " + hipGetErrorString(e_));                     \
-    } while (0)
-
 // What steps 1 and 2 (pass 1) of every text entry leave behind: the input in the handle's cached device buffer, the
 // words, the '\n' count of every index block with its prefix, and the line count.  s0 is the pooled block behind the
-// three small arrays; the caller frees it (after draining the stream).
+// three small arrays.
 struct TextFront {
-    uint8_t *s0 = nullptr;
-    size_t s0_cap = 0;
+    explicit TextFront(gams_gpu_t *h) : s0(h, false) {}
+    PoolBlock s0;
     unsigned long long *d_words = nullptr;
     uint32_t *d_bnl = nullptr;
     unsigned long long *d_bnloff = nullptr;
@@ -517,39 +509,34 @@ struct TextFront {
 int text_front(gams_gpu_t *h, const std::string &who, const char *bytes, uint64_t n_bytes, TextFront &F) {
     if (!h->text) h->text = new gams_text_state();
     gams_text_state *T = h->text;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const uint64_t n16 = (n_bytes + 15u) & ~15ull;
     F.n16 = n16;
     // 1. upload into the cached buffer; the 16-B tail is spaces (no '\n', nothing refused)
     const uint64_t n_pad = n16 + 16u;                 // the parse kernels may look 11 bytes past a field's end
-    if (T->d_in_cap < n_pad) {
-        gams_pool_free(h, false, T->d_in, T->d_in_cap);
-        T->d_in = nullptr;
-        T->d_in_cap = 0;
-        const hipError_t e = gams_pool_alloc(h, false, n_pad, reinterpret_cast<void **>(&T->d_in), &T->d_in_cap);
-        if (e != hipSuccess)
-            return gams_fail(h, e == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP, who + ": input buffer: " + hipGetErrorString(e));
-    }
+    GAMS_TRY(h, who, gams_pool_grow(h, false, &T->d_in, &T->d_in_cap, n_pad, n_pad));
     hipStream_t st = h->compute;
     const uint32_t nbi = (uint32_t)std::max<uint64_t>(1, (n16 + kIdxBytes - 1) / kIdxBytes);
     F.nbi = nbi;
-    const size_t b_words = al(W_COUNT * 8), b_bnl = al((size_t)nbi * 4), b_bnloff = al(((size_t)nbi + 1) * 8);
-    T_HIP(gams_pool_alloc(h, false, b_words + b_bnl + b_bnloff, reinterpret_cast<void **>(&F.s0), &F.s0_cap));
-    unsigned long long *d_words = F.d_words = reinterpret_cast<unsigned long long *>(F.s0);
-    uint32_t *d_bnl = F.d_bnl = reinterpret_cast<uint32_t *>(F.s0 + b_words);
-    unsigned long long *d_bnloff = F.d_bnloff = reinterpret_cast<unsigned long long *>(F.s0 + b_words + b_bnl);
-    T_HIP(hipEventRecord(h->k0, st));
+    auto front = [&](Carver &c) {         // words | '\n' per index block | their prefix
+        F.d_words = c.take<unsigned long long>(W_COUNT);
+        F.d_bnl = c.take<uint32_t>(nbi);
+        F.d_bnloff = c.take<unsigned long long>((size_t)nbi + 1);
+    };
+    GAMS_TRY(h, who, F.s0.alloc(layout_bytes(front)));
+    carve(F.s0.p, front);
+    unsigned long long *const d_words = F.d_words;
+    GAMS_TRY(h, who, hipEventRecord(h->k0, st));
     h->k_valid = false;
     h->kq_used = 0;
-    T_HIP(hipMemsetAsync(d_words, 0, W_COUNT * 8, st));
-    if (n_bytes) T_HIP(hipMemcpyAsync(T->d_in, bytes, n_bytes, hipMemcpyHostToDevice, st));
-    T_HIP(hipMemsetAsync(T->d_in + n_bytes, ' ', n_pad - n_bytes, st));
+    GAMS_TRY(h, who, hipMemsetAsync(d_words, 0, W_COUNT * 8, st));
+    if (n_bytes) GAMS_TRY(h, who, hipMemcpyAsync(T->d_in, bytes, n_bytes, hipMemcpyHostToDevice, st));
+    GAMS_TRY(h, who, hipMemsetAsync(T->d_in + n_bytes, ' ', n_pad - n_bytes, st));
     // 2. line index, pass 1
-    hipLaunchKernelGGL(text_nl_count_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n16, d_bnl, d_words);
-    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_bnl, nbi, d_bnloff, d_words, (uint32_t)W_NL);
-    T_HIP(hipGetLastError());
-    T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, 2 * 8, hipMemcpyDeviceToHost, st));
-    T_HIP(hipStreamSynchronize(st));
+    hipLaunchKernelGGL(text_nl_count_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n16, F.d_bnl, d_words);
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, F.d_bnl, nbi, F.d_bnloff, d_words, (uint32_t)W_NL);
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, d_words, 2 * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
     F.nl = h->pin_scratch[W_NL];
     if (h->pin_scratch[W_BAD])
         return gams_fail(h, GAMS_EUNSUPPORTED, who + ": the input holds a byte >= 0x80 or a NUL (use the host path)");
@@ -559,18 +546,6 @@ int text_front(gams_gpu_t *h, const std::string &who, const char *bytes, uint64_
     return GAMS_OK;
 }
 
-// the pooled scratch blocks of one call, returned once the stream has drained
-struct ScratchGuard {
-    gams_gpu_t *h;
-    uint8_t **a, **b;
-    size_t *ac, *bc;
-    ~ScratchGuard() {
-        (void)hipStreamSynchronize(h->compute);
-        gams_pool_free(h, false, *a, *ac);
-        gams_pool_free(h, false, *b, *bc);
-    }
-};
-
 int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_bytes, const char **text,
              uint64_t *text_bytes, uint64_t *n_rows) {
     const std::string who = kEntry[J.kind];
@@ -578,11 +553,8 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     *text_bytes = 0;
     *n_rows = 0;
     GAMS_HIP(h, hipSetDevice(h->device));
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    TextFront F;
-    uint8_t *s1 = nullptr;
-    size_t s1_cap = 0;
-    ScratchGuard guard{h, &F.s0, &s1, &F.s0_cap, &s1_cap};
+    PoolBlock s1(h, false);
+    TextFront F(h);
     const int rc_front = text_front(h, who, bytes, n_bytes, F);
     if (rc_front != GAMS_OK) return rc_front;
     gams_text_state *T = h->text;
@@ -598,88 +570,64 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     }
     // per-line columns
     const uint32_t nbr = (L + 255u) / 256u;
-    const size_t b_starts = al(((size_t)nl + 2) * 8), b_u32 = al((size_t)L * 4), b_u64 = al((size_t)L * 8),
-                 b_u8 = al(L), b_blk = al(((size_t)nbr + 1) * 8);
     const uint64_t m_ctg = J.kind == K_ANNO ? 0 : J.ctg_ix->m, n_ids = J.ids ? J.ids->t.n : 0;
-    const size_t b_rgg = J.kind == K_COUNT ? al(std::max<uint64_t>(m_ctg, 1) * 4) : 0;
-    const size_t b_cpos = J.kind == K_ANNO ? al(std::max<uint64_t>(n_ids, 1) * 4) : 0;
+    const size_t n_rgg = J.kind == K_COUNT ? std::max<uint64_t>(m_ctg, 1) : 0;
+    const size_t n_cpos = J.kind == K_ANNO ? std::max<uint64_t>(n_ids, 1) : 0;
     const size_t prefix_len = J.kind == K_ANNO && J.header && J.prefix ? strlen(J.prefix) : 0;
-    const size_t b_pre = al(prefix_len + 1);
-    // grp qs qe cg cnt | fend hit | keep | blocks (bytes, offsets) | rg_group | ctg_start ctg_end | prefix
-    const size_t need = b_starts + 5 * b_u32 + 2 * b_u64 + b_u8 + 2 * b_blk + b_rgg + 2 * b_cpos + b_pre;
-    T_HIP(gams_pool_alloc(h, false, need, reinterpret_cast<void **>(&s1), &s1_cap));
-    uint8_t *p = s1;
-    auto take = [&](size_t b) {
-        uint8_t *q = p;
-        p += b;
-        return q;
-    };
-    unsigned long long *d_starts = reinterpret_cast<unsigned long long *>(take(b_starts));
-    uint32_t *d_grp = reinterpret_cast<uint32_t *>(take(b_u32));
-    uint32_t *d_qs = reinterpret_cast<uint32_t *>(take(b_u32));
-    uint32_t *d_qe = reinterpret_cast<uint32_t *>(take(b_u32));
-    uint32_t *d_cg = reinterpret_cast<uint32_t *>(take(b_u32));     // count: rg group; anno: clip lo
-    uint32_t *d_cnt = reinterpret_cast<uint32_t *>(take(b_u32));    // count: counts; anno: clip hi
-    unsigned long long *d_fend = reinterpret_cast<unsigned long long *>(take(b_u64));   // anno: prop
-    int64_t *d_hit = reinterpret_cast<int64_t *>(take(b_u64));
-    uint8_t *d_keep = take(b_u8);
-    unsigned long long *d_bbytes = reinterpret_cast<unsigned long long *>(take(b_blk));
-    unsigned long long *d_boff = reinterpret_cast<unsigned long long *>(take(b_blk));
-    uint32_t *d_rgg = reinterpret_cast<uint32_t *>(take(b_rgg));
-    int32_t *d_cs = reinterpret_cast<int32_t *>(take(b_cpos));
-    int32_t *d_ce = reinterpret_cast<int32_t *>(take(b_cpos));
-    char *d_pre = reinterpret_cast<char *>(take(b_pre));
-    if (b_rgg && m_ctg) T_HIP(hipMemcpyAsync(d_rgg, J.rg_group, m_ctg * 4, hipMemcpyHostToDevice, st));
-    if (b_cpos && n_ids) {
-        T_HIP(hipMemcpyAsync(d_cs, J.ctg_start, n_ids * 4, hipMemcpyHostToDevice, st));
-        T_HIP(hipMemcpyAsync(d_ce, J.ctg_end, n_ids * 4, hipMemcpyHostToDevice, st));
+    auto cols = [&](Carver &cv) { return text_cols_layout(cv, nl, L, nbr, n_rgg, n_cpos, prefix_len); };
+    GAMS_TRY(h, who, s1.alloc(layout_bytes(cols)));
+    const TextCols c = carve(s1.p, cols);
+    if (n_rgg && m_ctg) GAMS_TRY(h, who, hipMemcpyAsync(c.rgg, J.rg_group, m_ctg * 4, hipMemcpyHostToDevice, st));
+    if (n_cpos && n_ids) {
+        GAMS_TRY(h, who, hipMemcpyAsync(c.cs, J.ctg_start, n_ids * 4, hipMemcpyHostToDevice, st));
+        GAMS_TRY(h, who, hipMemcpyAsync(c.ce, J.ctg_end, n_ids * 4, hipMemcpyHostToDevice, st));
     }
-    if (prefix_len) T_HIP(hipMemcpyAsync(d_pre, J.prefix, prefix_len, hipMemcpyHostToDevice, st));
+    if (prefix_len) GAMS_TRY(h, who, hipMemcpyAsync(c.prefix, J.prefix, prefix_len, hipMemcpyHostToDevice, st));
     // 2. line index, pass 2
-    hipLaunchKernelGGL(text_line_start_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n_bytes, n16, d_bnloff, nl, d_starts);
-    const TextLines tl{reinterpret_cast<const char *>(T->d_in), d_starts, nl, L};
+    hipLaunchKernelGGL(text_line_start_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n_bytes, n16, d_bnloff, nl, c.starts);
+    const TextLines tl{reinterpret_cast<const char *>(T->d_in), c.starts, nl, L};
     RowArgs ra{};
     ra.t = tl;
     ra.kind = J.kind;
-    ra.blk_bytes = d_bbytes;
-    ra.blk_off = d_boff;
+    ra.blk_bytes = c.blk_bytes;
+    ra.blk_off = c.blk_off;
     ra.words = d_words;
     // 3. parse + 4. lookups
     if (J.kind == K_ANNO) {
-        AnnoArgs aa{J.chr->t, J.ids->t, d_cs, d_ce, J.idx_id, J.idx_range, J.header ? 1u : 0u};
-        int32_t *d_cl = reinterpret_cast<int32_t *>(d_cg), *d_ch = reinterpret_cast<int32_t *>(d_cnt);
-        float *d_prop = reinterpret_cast<float *>(d_fend);
-        hipLaunchKernelGGL(text_parse_anno_kernel, dim3(nbr), dim3(256), 0, st, tl, aa, d_grp, d_cl, d_ch,
-                           reinterpret_cast<int32_t *>(d_qs), reinterpret_cast<int32_t *>(d_qe), d_keep, d_words);
-        launch_span_cover(J.sp, d_grp, d_cl, d_ch, reinterpret_cast<const int32_t *>(d_qs),
-                          reinterpret_cast<const int32_t *>(d_qe), L, d_prop, st);
-        ra.keep = d_keep;
-        ra.grp = d_grp;
-        ra.qs = reinterpret_cast<const int32_t *>(d_qs);
-        ra.qe = reinterpret_cast<const int32_t *>(d_qe);
+        AnnoArgs aa{J.chr->t, J.ids->t, c.cs, c.ce, J.idx_id, J.idx_range, J.header ? 1u : 0u};
+        int32_t *d_cl = reinterpret_cast<int32_t *>(c.cg), *d_ch = reinterpret_cast<int32_t *>(c.cnt);
+        float *d_prop = reinterpret_cast<float *>(c.fend);
+        hipLaunchKernelGGL(text_parse_anno_kernel, dim3(nbr), dim3(256), 0, st, tl, aa, c.grp, d_cl, d_ch,
+                           reinterpret_cast<int32_t *>(c.qs), reinterpret_cast<int32_t *>(c.qe), c.keep, d_words);
+        launch_span_cover(J.sp, c.grp, d_cl, d_ch, reinterpret_cast<const int32_t *>(c.qs),
+                          reinterpret_cast<const int32_t *>(c.qe), L, d_prop, st);
+        ra.keep = c.keep;
+        ra.grp = c.grp;
+        ra.qs = reinterpret_cast<const int32_t *>(c.qs);
+        ra.qe = reinterpret_cast<const int32_t *>(c.qe);
         ra.prop = d_prop;
-        ra.prefix = d_pre;
+        ra.prefix = c.prefix;
         ra.prefix_len = (uint32_t)prefix_len;
         ra.header = J.header ? 1u : 0u;
     } else {
-        hipLaunchKernelGGL(text_parse_rg_kernel, dim3(nbr), dim3(256), 0, st, tl, J.chr->t, d_grp, d_qs, d_qe, d_fend);
-        launch_interval_locate(J.ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
+        hipLaunchKernelGGL(text_parse_rg_kernel, dim3(nbr), dim3(256), 0, st, tl, J.chr->t, c.grp, c.qs, c.qe, c.fend);
+        launch_interval_locate(J.ctg_ix, c.grp, c.qs, c.qe, L, c.hit, st);
         if (J.kind == K_COUNT) {
-            hipLaunchKernelGGL(text_rg_group_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_rgg, d_cg, d_words);
-            launch_interval_count(J.rg_ix, d_cg, d_qs, d_qe, L, reinterpret_cast<int32_t *>(d_cnt), st);
+            hipLaunchKernelGGL(text_rg_group_kernel, dim3(nbr), dim3(256), 0, st, L, c.hit, c.rgg, c.cg, d_words);
+            launch_interval_count(J.rg_ix, c.cg, c.qs, c.qe, L, reinterpret_cast<int32_t *>(c.cnt), st);
         }
-        ra.fend = d_fend;
-        ra.hit = d_hit;
+        ra.fend = c.fend;
+        ra.hit = c.hit;
         ra.ids = J.kind == K_LOCATE ? J.ids->t : NameTab{};
-        ra.cnt = reinterpret_cast<const int32_t *>(d_cnt);
+        ra.cnt = reinterpret_cast<const int32_t *>(c.cnt);
     }
     // 5. row lengths and their offsets
     hipLaunchKernelGGL(text_row_len_kernel, dim3(nbr), dim3(256), 0, st, ra);
-    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_bbytes, nbr, d_boff, d_words,
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, c.blk_bytes, nbr, c.blk_off, d_words,
                        (uint32_t)W_BYTES);
-    T_HIP(hipGetLastError());
-    T_HIP(hipMemcpyAsync(h->pin_scratch, d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-    T_HIP(hipStreamSynchronize(st));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
     const unsigned long long *w = h->pin_scratch;
     if (w[W_EFIELD]) return gams_fail(h, GAMS_EINVAL, who + ": field index out of range (the reference panics, anno.rs:115)");
     if (w[W_EID])
@@ -693,28 +641,19 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     // the text: device buffer from the pool, read back into the entry's page-locked buffer
     char *&out = T->out[J.kind];
     size_t &out_cap = T->out_cap[J.kind];
-    if (out_cap < std::max<uint64_t>(tb, 1)) {
-        gams_pool_free(h, true, out, out_cap);
-        out = nullptr;
-        out_cap = 0;
-        T_HIP(gams_pool_alloc(h, true, std::max<uint64_t>(tb, 1), reinterpret_cast<void **>(&out), &out_cap));
-    }
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &out, &out_cap, std::max<uint64_t>(tb, 1), std::max<uint64_t>(tb, 1)));
     if (tb) {
-        char *d_text = nullptr;
-        size_t d_text_cap = 0;
-        T_HIP(gams_pool_alloc(h, false, tb, reinterpret_cast<void **>(&d_text), &d_text_cap));
-        ra.text = d_text;
+        PoolBlock d_text(h, false);
+        GAMS_TRY(h, who, d_text.alloc(tb));
+        ra.text = reinterpret_cast<char *>(d_text.p);
         hipLaunchKernelGGL(text_row_write_kernel, dim3(nbr), dim3(256), 0, st, ra);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out, d_text, tb, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipEventRecord(h->k1, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipStreamSynchronize(st);
-        gams_pool_free(h, false, d_text, d_text_cap);
-        if (e != hipSuccess) return gams_fail(h, GAMS_EHIP, who + ": text: " + hipGetErrorString(e));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipMemcpyAsync(out, d_text.p, tb, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipEventRecord(h->k1, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
     } else {
-        T_HIP(hipEventRecord(h->k1, st));
-        T_HIP(hipStreamSynchronize(st));
+        GAMS_TRY(h, who, hipEventRecord(h->k1, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
     }
     h->k_valid = true;
     *text = out;
@@ -823,7 +762,6 @@ template <typename Consume>
 int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, const gams_names_t *chr, const char *bytes,
             uint64_t n_bytes, bool order, Consume consume) {
     GAMS_HIP(h, hipSetDevice(h->device));
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     while (h->kq.size() < (size_t)RG_STAGES) {
         hipEvent_t a = nullptr, b = nullptr;
         GAMS_HIP(h, hipEventCreate(&a));
@@ -832,29 +770,24 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     }
     hipStream_t st = h->compute;
     auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
-    TextFront F;
-    uint8_t *s1 = nullptr;
-    size_t s1_cap = 0;
-    ScratchGuard guard{h, &F.s0, &s1, &F.s0_cap, &s1_cap};
-    T_HIP(stage(RG_LINES, true));
+    PoolBlock s1(h, false);
+    TextFront F(h);
+    GAMS_TRY(h, who, stage(RG_LINES, true));
     const int rc_front = text_front(h, who, bytes, n_bytes, F);
     if (rc_front != GAMS_OK) return rc_front;
     const uint64_t n_ctg = ctg_ix->m;
     const uint32_t L = F.L;
-    // the host's copy of bucket_off and first: page-locked, from the pool
-    struct Pin {
-        gams_gpu_t *h;
-        uint8_t *p = nullptr;
-        size_t cap = 0;
-        ~Pin() {
-            (void)hipStreamSynchronize(h->compute);   // a copy into the block may still be queued when a step failed
-            gams_pool_free(h, true, p, cap);
-        }
-    } pin{h};
-    const size_t b_hoff = al((n_ctg + 1) * 8);
-    T_HIP(gams_pool_alloc(h, true, b_hoff + std::max<uint64_t>(n_ctg, 1) * 4, reinterpret_cast<void **>(&pin.p), &pin.cap));
-    unsigned long long *h_off = reinterpret_cast<unsigned long long *>(pin.p);
-    uint32_t *h_first = reinterpret_cast<uint32_t *>(pin.p + b_hoff);
+    // the host's copy of bucket_off and first: page-locked, from the pool (a copy into the block may still be queued
+    // when a step fails: the block waits for the stream like the others)
+    PoolBlock pin(h, true);
+    unsigned long long *h_off = nullptr;
+    uint32_t *h_first = nullptr;
+    auto host_cols = [&](Carver &c) {
+        h_off = c.take<unsigned long long>(n_ctg + 1);
+        h_first = c.take_tight<uint32_t>(std::max<uint64_t>(n_ctg, 1));
+    };
+    GAMS_TRY(h, who, pin.alloc(layout_bytes(host_cols)));
+    carve(pin.p, host_cols);
     RgCols C{};
     C.n_ctg = n_ctg;
     C.bucket_off = h_off;
@@ -862,72 +795,69 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     if (L == 0) {
         memset(h_off, 0, (n_ctg + 1) * 8);
         memset(h_first, 0xff, n_ctg * 4);
-        T_HIP(stage(RG_LINES, false));
+        GAMS_TRY(h, who, stage(RG_LINES, false));
         return consume(C, stage);
     }
     uint32_t line_bits = 1, ctg_bits = 1;
     while (line_bits < 32u && (L - 1u) >> line_bits) ++line_bits;
     while (ctg_bits < 32u && n_ctg >> ctg_bits) ++ctg_bits;
     const uint32_t nbr = (L + 255u) / 256u;
-    const size_t b_starts = al(((size_t)F.nl + 2) * 8), b_u32 = al((size_t)L * 4), b_u64 = al((size_t)L * 8),
-                 b_tab = al(std::max<uint64_t>(n_ctg, 1) * 4), b_off = al((n_ctg + 1) * 8);
     size_t sort_bytes = 0;
-    T_HIP(rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr, (size_t)L, 0u,
-                                   line_bits + ctg_bits, st));
-    const size_t b_sort = al(std::max<size_t>(sort_bytes, 1));
-    // starts | grp qs qe | hit key key' | first count | bucket_off | sort storage
-    T_HIP(gams_pool_alloc(h, false, b_starts + 3 * b_u32 + 3 * b_u64 + 2 * b_tab + b_off + b_sort, reinterpret_cast<void **>(&s1),
-                          &s1_cap));
-    uint8_t *p = s1;
-    auto take = [&](size_t b) {
-        uint8_t *q = p;
-        p += b;
-        return q;
+    GAMS_TRY(h, who, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                              (size_t)L, 0u, line_bits + ctg_bits, st));
+    const size_t n_tab = std::max<uint64_t>(n_ctg, 1), b_tab = gams_align256(n_tab * 4);
+    unsigned long long *d_starts = nullptr, *d_key = nullptr, *d_key2 = nullptr, *d_off = nullptr;
+    uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr, *d_first = nullptr, *d_count = nullptr;
+    int64_t *d_hit = nullptr;
+    uint8_t *d_sort = nullptr;
+    auto cols = [&](Carver &c) {   // starts | grp qs qe | hit key key' | first count | bucket_off | sort storage
+        d_starts = c.take<unsigned long long>((size_t)F.nl + 2);
+        d_grp = c.take<uint32_t>(L);
+        d_qs = c.take<uint32_t>(L);
+        d_qe = c.take<uint32_t>(L);
+        d_hit = c.take<int64_t>(L);
+        d_key = c.take<unsigned long long>(L);
+        d_key2 = c.take<unsigned long long>(L);
+        d_first = c.take<uint32_t>(n_tab);
+        d_count = c.take<uint32_t>(n_tab);
+        d_off = c.take<unsigned long long>(n_ctg + 1);
+        d_sort = c.take<uint8_t>(std::max<size_t>(sort_bytes, 1));
     };
-    unsigned long long *d_starts = reinterpret_cast<unsigned long long *>(take(b_starts));
-    uint32_t *d_grp = reinterpret_cast<uint32_t *>(take(b_u32));
-    uint32_t *d_qs = reinterpret_cast<uint32_t *>(take(b_u32));
-    uint32_t *d_qe = reinterpret_cast<uint32_t *>(take(b_u32));
-    int64_t *d_hit = reinterpret_cast<int64_t *>(take(b_u64));
-    unsigned long long *d_key = reinterpret_cast<unsigned long long *>(take(b_u64));
-    unsigned long long *d_key2 = reinterpret_cast<unsigned long long *>(take(b_u64));
-    uint32_t *d_first = reinterpret_cast<uint32_t *>(take(b_tab));
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(take(b_tab));
-    unsigned long long *d_off = reinterpret_cast<unsigned long long *>(take(b_off));
-    uint8_t *d_sort = take(b_sort);
+    GAMS_TRY(h, who, s1.alloc(layout_bytes(cols)));
+    carve(s1.p, cols);
     hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, h->text->d_in, n_bytes, F.n16, F.d_bnloff, F.nl,
                        d_starts);
-    T_HIP(hipMemsetAsync(d_first, 0xff, b_tab, st));
-    T_HIP(hipMemsetAsync(d_count, 0, b_tab, st));
-    T_HIP(stage(RG_LINES, false));
+    GAMS_TRY(h, who, hipMemsetAsync(d_first, 0xff, b_tab, st));
+    GAMS_TRY(h, who, hipMemsetAsync(d_count, 0, b_tab, st));
+    GAMS_TRY(h, who, stage(RG_LINES, false));
     const TextLines tl{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
-    T_HIP(stage(RG_PARSE, true));
+    GAMS_TRY(h, who, stage(RG_PARSE, true));
     hipLaunchKernelGGL(rg_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, chr->t, d_grp, d_qs, d_qe);
-    T_HIP(stage(RG_PARSE, false));
-    T_HIP(stage(RG_LOCATE, true));
+    GAMS_TRY(h, who, stage(RG_PARSE, false));
+    GAMS_TRY(h, who, stage(RG_LOCATE, true));
     launch_interval_locate(ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
-    T_HIP(stage(RG_LOCATE, false));
-    T_HIP(stage(RG_FIRST, true));
+    GAMS_TRY(h, who, stage(RG_LOCATE, false));
+    GAMS_TRY(h, who, stage(RG_FIRST, true));
     hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
-    T_HIP(stage(RG_FIRST, false));
-    T_HIP(stage(RG_KEEP, true));
+    GAMS_TRY(h, who, stage(RG_FIRST, false));
+    GAMS_TRY(h, who, stage(RG_KEEP, true));
     hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key);
-    T_HIP(stage(RG_KEEP, false));
-    T_HIP(stage(RG_OFFSETS, true));
+    GAMS_TRY(h, who, stage(RG_KEEP, false));
+    GAMS_TRY(h, who, stage(RG_OFFSETS, true));
     hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, d_off, F.d_words,
                        (uint32_t)W_ROWS);
-    T_HIP(stage(RG_OFFSETS, false));
-    T_HIP(hipGetLastError());
-    T_HIP(hipMemcpyAsync(h_off, d_off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (n_ctg) T_HIP(hipMemcpyAsync(h_first, d_first, n_ctg * 4, hipMemcpyDeviceToHost, st));
-    T_HIP(hipStreamSynchronize(st));
+    GAMS_TRY(h, who, stage(RG_OFFSETS, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(h_off, d_off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (n_ctg) GAMS_TRY(h, who, hipMemcpyAsync(h_first, d_first, n_ctg * 4, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
     C.n_kept = h_off[n_ctg];
     if (C.n_kept > 0xfffffff0ull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 16 kept ranges");
     C.ran = true;
     if (!order) return consume(C, stage);            // a size query: nothing is gathered, so nothing is sorted
-    T_HIP(stage(RG_ORDER, true));
-    if (C.n_kept) T_HIP(rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, line_bits + ctg_bits, st));
-    T_HIP(stage(RG_ORDER, false));
+    GAMS_TRY(h, who, stage(RG_ORDER, true));
+    if (C.n_kept) GAMS_TRY(h, who, rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, line_bits + ctg_bits, st));
+    GAMS_TRY(h, who, stage(RG_ORDER, false));
     if (C.n_kept) {
         C.g.key = d_key2;
         C.g.line_mask = (1ull << line_bits) - 1ull;
@@ -946,7 +876,6 @@ void rg_timed(gams_gpu_t *h, int n) {
     h->kq_staged = true;
     h->k_valid = true;
 }
-#undef T_HIP
 
 }  // namespace
 
@@ -975,8 +904,8 @@ int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_
         tab[k] = NameSlot{x, i, 0u};
     }
     GAMS_HIP(h, hipSetDevice(h->device));
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t b_tab = al((size_t)slots * sizeof(NameSlot)), b_off = al(off.size() * 8), b_bytes = al(bytes.size() + 1);
+    const size_t b_tab = gams_align256((size_t)slots * sizeof(NameSlot)), b_off = gams_align256(off.size() * 8),
+                 b_bytes = gams_align256(bytes.size() + 1);
     gams_names_t *nm = new gams_names_t();
     hipError_t e = gams_pool_alloc(h, false, b_tab + b_off + b_bytes, reinterpret_cast<void **>(&nm->arena), &nm->arena_bytes);
     if (e == hipSuccess) e = hipMemcpy(nm->arena, tab.data(), tab.size() * sizeof(NameSlot), hipMemcpyHostToDevice);
@@ -1072,37 +1001,30 @@ int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_nam
         }
         if (cap < C.n_kept) return gams_fail(h, GAMS_EINVAL, who + ": cap is smaller than the kept ranges (*n_kept has them)");
         // the three columns on the device, one read-back into pooled page-locked memory, then the caller's arrays
-        uint32_t *d_out = nullptr, *p_out = nullptr;
-        size_t d_cap = 0, p_cap = 0;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t b_col = al(C.n_kept * 4);
-        hipError_t e = gams_pool_alloc(h, false, 3 * b_col, reinterpret_cast<void **>(&d_out), &d_cap);
-        if (e == hipSuccess) e = gams_pool_alloc(h, true, 3 * b_col, reinterpret_cast<void **>(&p_out), &p_cap);
-        if (e != hipSuccess) {
-            gams_pool_free(h, false, d_out, d_cap);
-            return gams_fail(h, e == hipErrorOutOfMemory ? GAMS_ENOMEM : GAMS_EHIP, who + ": columns: " + hipGetErrorString(e));
-        }
+        PoolBlock d_out(h, false), p_out(h, true);
         RgGather g = C.g;
-        g.start = d_out;
-        g.end = d_out + b_col / 4;
-        g.line = d_out + 2 * (b_col / 4);
+        auto three = [&](Carver &c) {
+            g.start = c.take<uint32_t>(C.n_kept);
+            g.end = c.take<uint32_t>(C.n_kept);
+            g.line = c.take<uint32_t>(C.n_kept);
+        };
+        const size_t b_cols = layout_bytes(three);
+        GAMS_TRY(h, who, d_out.alloc(b_cols));
+        GAMS_TRY(h, who, p_out.alloc(b_cols));
+        carve(p_out.p, three);
+        const uint32_t *p_start = g.start, *p_end = g.end, *p_line = g.line;
+        carve(d_out.p, three);
         g.end_plus = 0;
         hipStream_t st = h->compute;
-        e = stage(RG_GATHER, true);
+        GAMS_TRY(h, who, stage(RG_GATHER, true));
         hipLaunchKernelGGL(rg_gather_kernel, dim3((unsigned)((C.n_kept + 255) / 256)), dim3(256), 0, st, g);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = stage(RG_GATHER, false);
-        if (e == hipSuccess) e = hipMemcpyAsync(p_out, d_out, 3 * b_col, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipStreamSynchronize(st);
-        if (e == hipSuccess) {
-            memcpy(start, p_out, C.n_kept * 4);
-            memcpy(end, p_out + b_col / 4, C.n_kept * 4);
-            memcpy(line, p_out + 2 * (b_col / 4), C.n_kept * 4);
-        }
-        gams_pool_free(h, false, d_out, d_cap);
-        gams_pool_free(h, true, p_out, p_cap);
-        if (e != hipSuccess) return gams_fail(h, GAMS_EHIP, who + ": columns: " + hipGetErrorString(e));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, stage(RG_GATHER, false));
+        GAMS_TRY(h, who, hipMemcpyAsync(p_out.p, d_out.p, b_cols, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
+        memcpy(start, p_start, C.n_kept * 4);
+        memcpy(end, p_end, C.n_kept * 4);
+        memcpy(line, p_line, C.n_kept * 4);
         rg_timed(h, RG_GATHER + 1);
         return GAMS_OK;
     });
@@ -1119,24 +1041,24 @@ int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams
         uint32_t max_n = 0;
         for (uint64_t i = 0; i < C.n_ctg; ++i)
             max_n = std::max<uint32_t>(max_n, (uint32_t)(C.bucket_off[i + 1] - C.bucket_off[i]));
-        IndexBuild B;
+        IndexBuild B(h);
         const int rc = gams_index_build_begin(h, (uint32_t)C.n_ctg, C.n_kept, &B);
         if (rc != GAMS_OK) return rc;
         hipStream_t st = h->compute;
         hipError_t e = stage(RG_GATHER, true);
         if (C.n_kept) {
             RgGather g = C.g;
-            g.start = B.d_starts_in;
-            g.end = B.d_stops_in;            // [start, end + 1) (redis.rs:291-294)
+            g.start = B.cols.starts_in;
+            g.end = B.cols.stops_in;            // [start, end + 1) (redis.rs:291-294)
             g.line = nullptr;
             g.end_plus = 1;
-            g.off32 = B.d_off32;
+            g.off32 = B.cols.off32;
             g.n_off = C.n_ctg + 1;
             const uint64_t lanes = std::max<uint64_t>(C.n_kept, g.n_off);
             hipLaunchKernelGGL(rg_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, g);
             if (e == hipSuccess) e = hipGetLastError();
         } else if (e == hipSuccess) {
-            e = hipMemsetAsync(B.d_off32, 0, (C.n_ctg + 1) * 4, st);   // every group empty
+            e = hipMemsetAsync(B.cols.off32, 0, (C.n_ctg + 1) * 4, st);   // every group empty
         }
         if (e == hipSuccess) e = stage(RG_GATHER, false);
         if (e == hipSuccess) e = stage(RG_BUILD, true);

@@ -330,8 +330,6 @@ void wave_set_band(gams_wave_plan_t *p) {
     wave_squared_band(p->prm, g, p->sq);
 }
 
-inline size_t wave_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the stream way k runs on: the handle's compute stream, or one of its auxiliary streams
 hipStream_t wave_stream(gams_gpu_t *h, const gams_wave_plan_t *p, uint32_t k) {
     const uint32_t si = (p->lane + k) % (uint32_t)gams_gpu::kMaxWays;
@@ -357,9 +355,9 @@ int wave_upload_geometry(gams_gpu_t *h, gams_wave_plan_t *p) {
     p->d_tiles = nullptr;
     p->d_tile_off = nullptr;
     const size_t nt = std::max<size_t>(p->tiles.size(), 1);
-    const size_t b_tiles = wave_align256(nt * sizeof(WaveTile));
-    const size_t b_off = wave_align256((nt + 2) * sizeof(unsigned long long));   // + the two totals
-    const size_t b_cnt = wave_align256(nt * sizeof(uint32_t));
+    const size_t b_tiles = gams_align256(nt * sizeof(WaveTile));
+    const size_t b_off = gams_align256((nt + 2) * sizeof(unsigned long long));   // + the two totals
+    const size_t b_cnt = gams_align256(nt * sizeof(uint32_t));
     for (auto &w : p->way) w.d_tile_cnt = nullptr;
     GAMS_HIP(h, gams_pool_alloc(h, false, b_tiles + b_off + b_cnt * p->depth,
                                 reinterpret_cast<void **>(&p->arena_geom), &p->arena_geom_bytes));
@@ -401,25 +399,20 @@ struct JacBufs {
     size_t bytes;
 };
 JacBufs wave_jac_carve(uint8_t *base, uint64_t total_windows, const gams_wave_plan_t *p = nullptr) {
-    size_t o = 0;
-    auto take = [&](size_t b) {
-        uint8_t *q = base ? base + o : nullptr;
-        o += wave_align256(b);
-        return q;
-    };
+    Carver c(base);
     JacBufs z{};
-    z.f = reinterpret_cast<float *>(take(std::max<uint64_t>(total_windows, 1) * 4));
-    z.fblk = reinterpret_cast<uint32_t *>(take((size_t)(total_windows / kJacTile + 2) * 4));
-    z.ctl = reinterpret_cast<unsigned long long *>(take(kJacWords * 8));
+    z.f = c.take<float>(std::max<uint64_t>(total_windows, 1));
+    z.fblk = c.take<uint32_t>((size_t)(total_windows / kJacTile + 2));
+    z.ctl = c.take<unsigned long long>(kJacWords);
     if (p && p->jac0) {
         const size_t size1 = (size_t)p->prm.size + 1;
-        z.lastu = reinterpret_cast<int32_t *>(take(std::max<uint64_t>(total_windows, 1) * 4));
-        z.tile_last = reinterpret_cast<int32_t *>(take(std::max<size_t>(p->n_jtiles, 1) * 4));
-        z.freeze = reinterpret_cast<unsigned long long *>(take(std::max<size_t>(p->set->n_ctg, 1) * 2 * 8));
-        z.ftab = reinterpret_cast<int8_t *>(take(size1 * size1));
-        z.frow = reinterpret_cast<uint8_t *>(take(size1));
+        z.lastu = c.take<int32_t>(std::max<uint64_t>(total_windows, 1));
+        z.tile_last = c.take<int32_t>(std::max<size_t>(p->n_jtiles, 1));
+        z.freeze = c.take<unsigned long long>(std::max<size_t>(p->set->n_ctg, 1) * 2);
+        z.ftab = c.take<int8_t>(size1 * size1);
+        z.frow = c.take<uint8_t>(size1);
     }
-    z.bytes = o;
+    z.bytes = c.bytes();
     return z;
 }
 
@@ -519,9 +512,9 @@ int gams_wave_plan_create(gams_gpu_t *h, gams_seqset_t *s, const gams_wave_param
         }                                                                                 \
     } while (0)
     {
-        const size_t b_ctgs = wave_align256(std::max<size_t>(s->n_ctg, 1) * sizeof(WaveCtgDev));
-        const size_t b_const = wave_align256((size_t)params->size + 1);
-        const size_t b_xtab = p->repair ? wave_align256(((size_t)params->size + 1) * sizeof(float)) : 0;
+        const size_t b_ctgs = gams_align256(std::max<size_t>(s->n_ctg, 1) * sizeof(WaveCtgDev));
+        const size_t b_const = gams_align256((size_t)params->size + 1);
+        const size_t b_xtab = p->repair ? gams_align256(((size_t)params->size + 1) * sizeof(float)) : 0;
         PLAN_HIP(gams_pool_alloc(h, false, b_ctgs + b_const + b_xtab, reinterpret_cast<void **>(&p->arena_fixed),
                                  &p->arena_fixed_bytes));
         p->d_ctgs = reinterpret_cast<WaveCtgDev *>(p->arena_fixed);
@@ -1357,22 +1350,17 @@ struct RowTables {
 };
 RowTables rows_carve(uint8_t *base, uint64_t cap) {
     const uint32_t nb = (uint32_t)((cap + kRowsBlock - 1) / kRowsBlock);
-    size_t o = 0;
-    auto take = [&](size_t b) {
-        uint8_t *q = base ? base + o : nullptr;
-        o += wave_align256(b);
-        return q;
-    };
+    Carver c(base);
     RowTables t{};
-    t.headpos = reinterpret_cast<int2 *>(take(cap * 8));
-    t.tailwin = reinterpret_cast<uint32_t *>(take(cap * 4));
-    t.len = reinterpret_cast<uint32_t *>(take(cap * 4));
-    t.flags = take(cap);
-    t.blk_head = reinterpret_cast<int2 *>(take((size_t)nb * 8));
-    t.blk_len = reinterpret_cast<uint32_t *>(take((size_t)nb * 4));
-    t.blk_off = reinterpret_cast<unsigned long long *>(take(((size_t)nb + 2) * 8));
+    t.headpos = c.take<int2>(cap);
+    t.tailwin = c.take<uint32_t>(cap);
+    t.len = c.take<uint32_t>(cap);
+    t.flags = c.take<uint8_t>(cap);
+    t.blk_head = c.take<int2>(nb);
+    t.blk_len = c.take<uint32_t>(nb);
+    t.blk_off = c.take<unsigned long long>((size_t)nb + 2);
     t.nb_cap = nb;
-    t.bytes = o;
+    t.bytes = c.bytes();
     return t;
 }
 
@@ -1620,8 +1608,8 @@ int gams_wave_rows_setup(gams_gpu_t *h, gams_wave_plan_t *p, const char *const *
     if (!bad.empty()) return gams_fail(h, GAMS_EUNSUPPORTED, bad);
     r->max_name = 0;
     for (const RowCtg &c : rc) r->max_name = std::max(r->max_name, c.name_len);
-    const size_t b_ctgs = wave_align256(rc.size() * sizeof(RowCtg)), b_names = wave_align256(std::max<size_t>(blob.size(), 1)),
-                 b_gc = wave_align256(gct.size()), b_words = wave_align256(((size_t)n_ctg + 1 + 4) * 8);
+    const size_t b_ctgs = gams_align256(rc.size() * sizeof(RowCtg)), b_names = gams_align256(std::max<size_t>(blob.size(), 1)),
+                 b_gc = gams_align256(gct.size()), b_words = gams_align256(((size_t)n_ctg + 1 + 4) * 8);
     GAMS_HIP(h, gams_pool_alloc(h, false, b_ctgs + b_names + b_gc + b_words, reinterpret_cast<void **>(&r->arena),
                                 &r->arena_bytes));
     r->d_ctgs = reinterpret_cast<RowCtg *>(r->arena);
@@ -1764,19 +1752,17 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
         g->n_tiles = (uint32_t)st.size();
         g->names_cap = std::max<size_t>(blob.size(), 64) * 2;
         const size_t nt = std::max<size_t>(st.size(), 1);
-        const size_t b_tiles = wave_align256(nt * sizeof(SigTile)), b_len = wave_align256(nt * 4), b_off = wave_align256((nt + 2) * 8),
-                     b_ctgs = wave_align256(rc.size() * sizeof(RowCtg)), b_names = wave_align256(g->names_cap),
-                     b_gc = wave_align256(gct.size()), b_words = wave_align256(std::max<size_t>(n_ctg, 1) * 8);
-        GAMS_HIP(h, gams_pool_alloc(h, false, b_tiles + b_len + b_off + b_ctgs + b_names + b_gc + b_words,
-                                    reinterpret_cast<void **>(&g->arena), &g->arena_bytes));
-        uint8_t *o = g->arena;
-        g->d_tiles = reinterpret_cast<SigTile *>(o), o += b_tiles;
-        g->d_blk_len = reinterpret_cast<uint32_t *>(o), o += b_len;
-        g->d_blk_off = reinterpret_cast<unsigned long long *>(o), o += b_off;
-        g->d_ctgs = reinterpret_cast<RowCtg *>(o), o += b_ctgs;
-        g->d_names = reinterpret_cast<char *>(o), o += b_names;
-        g->d_gctab = o, o += b_gc;
-        g->d_words = reinterpret_cast<unsigned long long *>(o);
+        auto arena = [&](Carver &c) {
+            g->d_tiles = c.take<SigTile>(nt);
+            g->d_blk_len = c.take<uint32_t>(nt);
+            g->d_blk_off = c.take<unsigned long long>(nt + 2);
+            g->d_ctgs = c.take<RowCtg>(rc.size());
+            g->d_names = c.take<char>(g->names_cap);
+            g->d_gctab = c.take<uint8_t>(gct.size());
+            g->d_words = c.take<unsigned long long>(std::max<size_t>(n_ctg, 1));
+        };
+        GAMS_HIP(h, gams_pool_alloc(h, false, layout_bytes(arena), reinterpret_cast<void **>(&g->arena), &g->arena_bytes));
+        carve(g->arena, arena);
         if (!st.empty()) GAMS_HIP(h, hipMemcpy(g->d_tiles, st.data(), st.size() * sizeof(SigTile), hipMemcpyHostToDevice));
         gams_pool_free(h, true, g->h_words, g->h_words_bytes);
         g->h_words = nullptr;
@@ -1816,18 +1802,8 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
     GAMS_HIP(h, hipMemcpyAsync(h->pin_scratch, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     GAMS_HIP(h, hipStreamSynchronize(st));       // (the staged tables above live on this call's stack until here)
     const uint64_t total = h->pin_scratch[0];
-    if (total > g->d_text_bytes) {
-        gams_pool_free(h, false, g->d_text, g->d_text_bytes);
-        g->d_text = nullptr;
-        g->d_text_bytes = 0;
-        GAMS_HIP(h, gams_pool_alloc(h, false, total + total / 16 + 4096, reinterpret_cast<void **>(&g->d_text), &g->d_text_bytes));
-    }
-    if (total > g->h_text_bytes) {
-        gams_pool_free(h, true, g->h_text, g->h_text_bytes);
-        g->h_text = nullptr;
-        g->h_text_bytes = 0;
-        GAMS_HIP(h, gams_pool_alloc(h, true, total + total / 16 + 4096, reinterpret_cast<void **>(&g->h_text), &g->h_text_bytes));
-    }
+    GAMS_HIP(h, gams_pool_grow(h, false, &g->d_text, &g->d_text_bytes, total, total + total / 16 + 4096));
+    GAMS_HIP(h, gams_pool_grow(h, true, &g->h_text, &g->h_text_bytes, total, total + total / 16 + 4096));
     a.text = g->d_text;
     a.text_cap = total;
     hipLaunchKernelGGL(sig_write_kernel, dim3(g->n_tiles), dim3(256), 0, st, a);
