@@ -315,13 +315,19 @@ int gams_index_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
                       gams_index_t **ix);
 void gams_index_destroy(gams_gpu_t *h, gams_index_t *ix);
 /* Lapper::count(qs,qe) per query against its group (utils.rs:35).
- * group[q] >= n_groups (e.g. UINT32_MAX) -> 0 (utils.rs:29-32). */
+ * group[q] >= n_groups (e.g. UINT32_MAX) -> 0 (utils.rs:29-32).
+ * The count is #{start < qe} - #{stop <= qs}, the starts and the stops each
+ * sorted on their own.  Of a reversed query (qe <= qs) or over reversed
+ * intervals (stop < start) it is that signed difference, which can be
+ * negative; the reference itself has no defined answer there. */
 int gams_gpu_count(gams_gpu_t *h, gams_index_t *ix, const uint32_t *group,
                    const uint32_t *qs, const uint32_t *qe, uint64_t nq,
                    int32_t *count);
 /* Lapper::find(qs,qe).next() per query (utils.rs:16): index (into the
  * caller's original interval order) of the first hit in (start,stop) order,
- * or -1. */
+ * or -1.  Among equal (start, stop) pairs the one earliest in the caller's
+ * order is returned: the build sorts like the stable intervals.sort() of
+ * redis.rs:253,299, whatever the size of the group. */
 int gams_gpu_locate(gams_gpu_t *h, gams_index_t *ix, const uint32_t *group,
                     const uint32_t *qs, const uint32_t *qe, uint64_t nq,
                     int64_t *hit);

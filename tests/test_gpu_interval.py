@@ -89,9 +89,8 @@ def test_count_and_locate_on_skewed_keys(eng):
             if k < 0:
                 assert hit[q] == -1
             else:
-                # equal (start, stop) pairs are interchangeable: compare the interval, not the index
-                j = int(hit[q]) - int(off[g])
-                assert (st[j], sp[j]) == (ls[k], lt[k]), (g, q)
+                # lexsort is stable: order[k] is the first of its equal (start, stop) pairs in the caller's order
+                assert int(hit[q]) == int(off[g]) + int(order[k]), (g, q)
     unknown = qg >= len(groups)
     assert np.all(cnt[unknown] == 0) and np.all(hit[unknown] == -1)
 
@@ -265,7 +264,7 @@ def test_index_build_at_every_workgroup_capacity(eng, sizes):
     the stable intervals.sort() of redis.rs:253,299) up to 8,192 intervals per group and hands larger ones to the
     library's segmented radix sort: groups of every size around the kernel's capacities, with many equal starts and
     equal (start, stop) pairs.  count against the closed form on all queries, locate against the oracle's scan
-    (first hit in (start, stop) order; equal pairs are interchangeable)."""
+    (first hit in (start, stop) order; of equal pairs the first in the caller's order, by its index)."""
     rng = np.random.default_rng(sum(sizes))
     groups = []
     for n in sizes:
@@ -298,6 +297,5 @@ def test_index_build_at_every_workgroup_capacity(eng, sizes):
             if k < 0:
                 assert hit[q] == -1
             else:
-                j = int(hit[q]) - int(off[g])
-                assert 0 <= j < st.size and (st[j], sp[j]) == (ls[k], lt[k]), (g, q)
+                assert int(hit[q]) == int(off[g]) + int(order[k]), (g, q)   # lexsort is stable: min(original index)
     eng.lib.gams_index_destroy(eng.h, ix)
