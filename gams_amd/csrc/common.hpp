@@ -166,6 +166,31 @@ hipError_t gams_pool_grow(gams_gpu_t *h, bool pinned, T **p, size_t *cap, size_t
     return gams_pool_alloc(h, pinned, want, reinterpret_cast<void **>(p), cap);
 }
 
+// One pooled block that its owner (a wave plan, its ways, its rows) keeps between calls.  Nothing here waits for a
+// stream: the owner drains whatever may still use the block before it grows or frees it.  Reads as its pointer.
+template <typename T>
+struct Kept {
+    T *p = nullptr;
+    size_t cap = 0;   // bytes
+    bool pinned;
+    explicit Kept(bool pinned_ = false) : pinned(pinned_) {}
+    operator T *() const { return p; }
+    // gams_pool_grow: nothing to do if the block holds `need` bytes, else one of `want` bytes takes its place
+    hipError_t grow(gams_gpu_t *h, size_t need, size_t want) { return gams_pool_grow(h, pinned, &p, &cap, need, want); }
+    // ... without headroom: on an empty or freed block, the request for `bytes`
+    hipError_t reserve(gams_gpu_t *h, size_t bytes) { return grow(h, bytes, bytes); }
+    void free(gams_gpu_t *h) {
+        gams_pool_free(h, pinned, p, cap);
+        p = nullptr;
+        cap = 0;
+    }
+};
+// an owner's release(h): its blocks back to the pools, in the order given
+template <typename... K>
+void gams_free_all(gams_gpu_t *h, K &...blocks) {
+    (blocks.free(h), ...);
+}
+
 struct gams_gcindex;  // sw.hip: prefix index over the seqset buffer
 
 struct gams_seqset {

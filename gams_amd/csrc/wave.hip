@@ -37,6 +37,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <type_traits>
@@ -67,21 +68,16 @@ static const WaveTileFn kWaveTileFn[2][2] = {{wave_tile_kernel<uint8_t, false>, 
 // gams_wave_rows_*: the plan's TSV rows made on the device (wave_rows.hpp)
 struct WaveRows {
     uint32_t dmax = 0, max_name = 0;
-    uint8_t *arena = nullptr;                 // RowCtg[n_ctg] | names | gc text table | words[4 + n_ctg + 1]
-    size_t arena_bytes = 0;
+    Kept<uint8_t> arena;                      // RowCtg[n_ctg] | names | gc text table | words[4 + n_ctg + 1]
     RowCtg *d_ctgs = nullptr;
     char *d_names = nullptr;
     uint8_t *d_gctab = nullptr;
     unsigned long long *d_words = nullptr;     // [0] records, [1] text bytes, [2] peaks, [3] fullest tile, [4 ..] ctg_off[n_ctg + 1]
-    uint8_t *tmp = nullptr;                   // per-record and per-block tables, room for `cap` records
-    size_t tmp_bytes = 0;
+    Kept<uint8_t> tmp;                        // per-record and per-block tables, room for `cap` records
     uint64_t cap = 0;
-    char *d_text = nullptr;
-    size_t d_text_bytes = 0;
-    char *h_text = nullptr;                   // page-locked
-    size_t h_text_bytes = 0;
-    unsigned long long *h_words = nullptr;    // page-locked: [0] records, [1] text bytes, [2] peaks (offsets kernel), [3] fullest tile, [4..] ctg_off
-    size_t h_words_bytes = 0;
+    Kept<char> d_text;
+    Kept<char> h_text{true};                  // page-locked
+    Kept<unsigned long long> h_words{true};   // page-locked: [0] records, [1] text bytes, [2] peaks (offsets kernel), [3] fullest tile, [4..] ctg_off
     uint64_t copy_bytes = 0;                  // size of the speculative text copy (held by the captured graphs)
     bool use_graph = true;
     struct RowGraphKey {
@@ -97,12 +93,12 @@ struct WaveRows {
     uint64_t last_bytes = 0;                  // text bytes of the previous pass (sizes the speculative copy)
     hipEvent_t done = nullptr;
     bool begun = false;
+    void release(gams_gpu_t *h) { gams_free_all(h, arena, tmp, d_text, h_text, h_words); }
 };
 
 // gams_wave_signal_text: the `--signal` rows of a pass as text (wave_rows.hpp, sig_*_kernel)
 struct WaveSig {
-    uint8_t *arena = nullptr;                 // SigTile[nt] | blk_len[nt] | blk_off[nt + 2] | RowCtg[n_ctg] | names | gc table | words[n_ctg]
-    size_t arena_bytes = 0;
+    Kept<uint8_t> arena;                      // SigTile[nt] | blk_len[nt] | blk_off[nt + 2] | RowCtg[n_ctg] | names | gc table | words[n_ctg]
     uint32_t n_tiles = 0;
     SigTile *d_tiles = nullptr;
     uint32_t *d_blk_len = nullptr;
@@ -111,10 +107,9 @@ struct WaveSig {
     char *d_names = nullptr;
     uint8_t *d_gctab = nullptr;
     size_t names_cap = 0;
-    char *d_text = nullptr, *h_text = nullptr;      // h_text: page-locked
-    size_t d_text_bytes = 0, h_text_bytes = 0;
-    unsigned long long *h_words = nullptr;          // page-locked: words[n_ctg], then ctg_off[n_ctg + 1] made on the host
-    size_t h_words_bytes = 0;
+    Kept<char> d_text, h_text{true};                // h_text: page-locked
+    Kept<unsigned long long> h_words{true};         // page-locked: words[n_ctg], then ctg_off[n_ctg + 1] made on the host
+    void release(gams_gpu_t *h) { gams_free_all(h, arena, d_text, h_text, h_words); }
 };
 
 struct Launcher;
@@ -125,8 +120,7 @@ struct gams_wave_plan {
     bool serial = false;          // influence != 1
     bool repair = false;          // ... by guess-and-iterate (wave_repair.hpp): the kernels run as for influence == 1 into
                                   // the dense rows, then filtered[] and the signals are iterated to their fixed point
-    JacTile *d_jtiles = nullptr;  // repair: tiles of 256 windows (pooled block)
-    size_t d_jtiles_bytes = 0;
+    Kept<JacTile> d_jtiles;       // repair: tiles of 256 windows
     uint32_t n_jtiles = 0;
     float *d_xtab = nullptr;      // repair: xtab[k] = k as f32 / size as f32, [size + 1] (inside arena_fixed)
     bool jac0 = false;            // repair with influence == 0: fill-forward filter + freeze guess (jac0_* kernels)
@@ -143,29 +137,25 @@ struct gams_wave_plan {
     // calls rotate over them, each way on its own HIP stream, so that independent passes overlap
     // on the device (a 12-Mb pass alone is launch-latency bound).
     struct Way {
-        gams_peak_t *d_peaks = nullptr;         // one slot of tile_cap records per tile (pooled block)
-        size_t d_peaks_bytes = 0;
+        Kept<gams_peak_t> d_peaks;              // one slot of tile_cap records per tile
         uint32_t *d_tile_cnt = nullptr;         // inside arena_geom
-        unsigned long long *d_counters = nullptr;   // ring of kCounterRing slots, zeroed once per lap (pooled)
-        size_t d_counters_bytes = 0;
+        Kept<unsigned long long> d_counters;    // ring of kCounterRing slots, zeroed once per lap
         uint64_t runs = 0;                      // passes this way has run
         uint32_t last_ring = 0;                 // ring slot of its last pass
-        uint32_t *d_dense_cnt = nullptr;        // --signal rows / input of the serial kernel (pooled)
-        int8_t *d_dense_sig = nullptr;
-        float *d_filtered = nullptr;
-        size_t d_dense_cnt_bytes = 0, d_dense_sig_bytes = 0, d_filtered_bytes = 0;
-        uint8_t *d_jac = nullptr;               // repair: filtered[] | dirty blocks | control words (one pooled block)
-        size_t d_jac_bytes = 0;
+        Kept<uint32_t> d_dense_cnt;             // --signal rows / input of the serial kernel
+        Kept<int8_t> d_dense_sig;
+        Kept<float> d_filtered;
+        Kept<uint8_t> d_jac;                    // repair: filtered[] | dirty blocks | control words (one block)
         bool jac0_table = false;                // influence == 0: the freeze table of this way has been filled
         bool jac_serial = false;                // the last pass was handed to the one-wavefront-per-ctg recurrence
-        unsigned long long *h_ctl = nullptr;    // page-locked copy of the control words, made behind every batch of sweeps
-        size_t h_ctl_bytes = 0;
+        Kept<unsigned long long> h_ctl{true};   // page-locked copy of the control words, made behind every batch of sweeps
         uint32_t jac_sweeps = 0;                // sweeps queued for the way's current pass
         bool jac_settled = true;                // the host has seen a sweep without a flip (or ran the fallback)
         hipEvent_t done = nullptr;              // pipelined mode: recorded behind each run's kernels
         hipEvent_t ran_ev = nullptr;            // lets the readback stream queue behind the last run
         uint64_t seen_upload = 0;               // seqset upload generation this way's stream has waited for
         bool seen_ready = false;                // ... and the plan's const table
+        void release(gams_gpu_t *h) { gams_free_all(h, d_peaks, d_counters, d_dense_cnt, d_dense_sig, d_filtered, d_jac, h_ctl); }
     };
     Way way[gams_gpu::kMaxWays];
     uint32_t depth = 1;                         // ways in use
@@ -176,22 +166,19 @@ struct gams_wave_plan {
     uint32_t last_way = 0;                      // way of the most recent run
     uint32_t sel_age = 0;                       // readers look at the run `sel_age` before the most recent one
     hipEvent_t ready = nullptr;                 // recorded on the compute stream behind the const table
-    size_t d_dense_bytes = 0;
-    gams_peak_t *h_peaks = nullptr;             // pinned: packed peaks of the last gams_wave_peaks
-    size_t h_peaks_bytes = 0;
+    Kept<gams_peak_t> h_peaks{true};            // pinned: packed peaks of the last gams_wave_peaks
     uint32_t tile_cap = 0, tile_cap_req = 0;
     uint32_t tw_req = 0;                        // gams_wave_plan_set_tile request (0: the library's choice)
     uint32_t nth_req = 0;                       // gams_wave_plan_set_threads request (0: the library's choice)
-    gams_peak_t *d_dense = nullptr;             // packed copy made by gams_wave_peaks
-    uint64_t dense_cap = 0;
+    Kept<gams_peak_t> d_dense;                  // packed copy made by gams_wave_peaks and the rows
+    uint64_t dense_cap() const { return d_dense.cap / sizeof(gams_peak_t); }   // ... in records
     uint64_t run_idx = 0;
     int8_t *d_const_sig = nullptr;              // [size+1], see wave_const_table_kernel
     unsigned long long *d_stamps = nullptr;     // diagnostics, [tiles][8]
     unsigned long long *d_tile_off = nullptr;
     // two pooled arenas hold the small tables: `fixed` = ctgs | const_sig (life of the plan),
     // `geom` = tiles | tile_off (+2 totals) | tile_cnt per way (replaced when the tiling changes)
-    uint8_t *arena_fixed = nullptr, *arena_geom = nullptr;
-    size_t arena_fixed_bytes = 0, arena_geom_bytes = 0;
+    Kept<uint8_t> arena_fixed, arena_geom;
     bool ran = false;
     struct Launcher *launcher[gams_gpu::kMaxWays - 1] = {};   // extra queueing threads of gams_wave_run_n (made on first use)
     bool pipelined = false;       // gams_wave_plan_set_pipelined: an event per run; readers wait on it
@@ -203,6 +190,13 @@ struct gams_wave_plan {
     bool guard_exact = false;           // every window through the exact path
     int input_req = GAMS_WAVE_INPUT_AUTO;   // gams_wave_plan_set_input
     std::atomic<int> last_input{GAMS_WAVE_INPUT_BYTES};   // what the most recently queued pass read (ways queue from several threads)
+    // every pooled block of the plan back to the pools (the caller has drained the streams)
+    void release(gams_gpu_t *h) {
+        if (rows) rows->release(h);
+        if (sigtext) sigtext->release(h);
+        gams_free_all(h, arena_fixed, arena_geom, d_jtiles, d_dense, h_peaks);
+        for (Way &w : way) w.release(h);
+    }
 };
 static void wave_launcher_stop(gams_wave_plan_t *p);
 
@@ -213,18 +207,72 @@ constexpr uint32_t kCounterRing = 128;       // one counter slot (kShards lines)
 constexpr size_t kSlotWords = (size_t)kShards * kShardWords;
 constexpr uint32_t kOffOneGroup = 32768;   // tables up to here: wave_offsets_kernel (one workgroup, one launch)
 
-// exclusive prefix of n counts on `st`, the total and the maximum into tot[0..1]: one workgroup, or spans of
-// kOffSpan counts in three launches (wave_kernels.hpp)
-void wave_queue_offsets(hipStream_t st, const uint32_t *cnt, uint32_t n, unsigned long long *off, unsigned long long *tot) {
-    if (n <= kOffOneGroup) {
-        hipLaunchKernelGGL(wave_offsets_kernel, dim3(1), dim3(1024), 0, st, cnt, n, off, tot);
-        return;
+// What the readers queue behind a pass, in order: kernels and copies to the host, launched on `st` as they come
+// (graph == nullptr) or added to `graph` as a chain of nodes.  Argument blocks are read when the launch / the node is made.
+// The first failure stays in `err` and nothing is queued behind it.
+struct Chain {
+    hipStream_t st;
+    hipGraph_t graph = nullptr;
+    hipGraphNode_t last = nullptr;
+    hipError_t err = hipSuccess;
+    void kernel(const void *fn, unsigned grid, unsigned block, void **args) {
+        if (err != hipSuccess) return;
+        if (!graph) {
+            err = hipLaunchKernel(fn, dim3(grid), dim3(block), args, 0, st);
+            return;
+        }
+        hipKernelNodeParams kp{};
+        kp.func = const_cast<void *>(fn);
+        kp.gridDim = dim3(grid);
+        kp.blockDim = dim3(block);
+        kp.sharedMemBytes = 0;
+        kp.kernelParams = args;
+        kp.extra = nullptr;
+        hipGraphNode_t node = nullptr;
+        err = hipGraphAddKernelNode(&node, graph, last ? &last : nullptr, last ? 1 : 0, &kp);
+        last = node;
     }
-    const unsigned spans = (n + kOffSpan - 1u) / kOffSpan;
-    hipLaunchKernelGGL(wave_offsets_sum_kernel, dim3(spans), dim3(1024), 0, st, cnt, n, off);
-    hipLaunchKernelGGL(wave_offsets_base_kernel, dim3(1), dim3(1024), 0, st, n, off, tot);
-    hipLaunchKernelGGL(wave_offsets_scan_kernel, dim3(spans), dim3(1024), 0, st, cnt, n, off);
-}
+    void copy(void *dst, const void *src, size_t bytes) {
+        if (err != hipSuccess || bytes == 0) return;
+        if (!graph) {
+            err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
+            return;
+        }
+        hipGraphNode_t node = nullptr;
+        err = hipGraphAddMemcpyNode1D(&node, graph, last ? &last : nullptr, last ? 1 : 0, dst, src, bytes, hipMemcpyDeviceToHost);
+        last = node;
+    }
+    // exclusive prefix of n counts, the total and the maximum into tot[0..1]: one workgroup, or spans of kOffSpan
+    // counts in three launches (wave_kernels.hpp)
+    void offsets(const uint32_t *cnt, uint32_t n, unsigned long long *off, unsigned long long *tot) {
+        void *all4[] = {&cnt, &n, &off, &tot}, *cnt_n_off[] = {&cnt, &n, &off}, *n_off_tot[] = {&n, &off, &tot};
+        if (n <= kOffOneGroup) {
+            kernel(reinterpret_cast<const void *>(wave_offsets_kernel), 1, 1024, all4);
+            return;
+        }
+        const unsigned spans = (n + kOffSpan - 1u) / kOffSpan;
+        kernel(reinterpret_cast<const void *>(wave_offsets_sum_kernel), spans, 1024, cnt_n_off);
+        kernel(reinterpret_cast<const void *>(wave_offsets_base_kernel), 1, 1024, n_off_tot);
+        kernel(reinterpret_cast<const void *>(wave_offsets_scan_kernel), spans, 1024, cnt_n_off);
+    }
+    // the tile slots of way `w` packed into d_dense (at most dense_cap records): the tiles' offsets, with the total and
+    // the fullest tile in the two words behind them, then the gather
+    void gather(const gams_wave_plan_t *p, const gams_wave_plan::Way &w) {
+        const gams_peak_t *slots = w.d_peaks;
+        uint32_t tile_cap = p->tile_cap;
+        const uint32_t *tile_cnt = w.d_tile_cnt;
+        const unsigned long long *tile_off = p->d_tile_off;
+        gams_peak_t *dense = p->d_dense;
+        unsigned long long dense_cap = p->dense_cap();
+        void *args[] = {&slots, &tile_cap, &tile_cnt, &tile_off, &dense, &dense_cap};
+        kernel(reinterpret_cast<const void *>(wave_gather_kernel), (unsigned)p->tiles.size(), 64, args);
+    }
+    void pack(const gams_wave_plan_t *p, const gams_wave_plan::Way &w) {
+        const uint32_t nt = (uint32_t)p->tiles.size();
+        offsets(w.d_tile_cnt, nt, p->d_tile_off, p->d_tile_off + nt);
+        gather(p, w);
+    }
+};
 
 // Guard band of the integer decision, in units of D = |n*k - S1| (see DESIGN.md
 // "z-score guard band" for the derivation).  u = 2^-24.
@@ -349,36 +397,34 @@ int wave_sync_ways(gams_gpu_t *h, gams_wave_plan_t *p) {
     return GAMS_OK;
 }
 
+// A freed arena anew: a block of the bytes `layout` takes, carved by it.  (Sizing runs the layout over no block, which
+// leaves its pointers null should the request fail.)
+template <typename F>
+hipError_t wave_arena(gams_gpu_t *h, Kept<uint8_t> &arena, F layout) {
+    arena.free(h);
+    const size_t bytes = layout_bytes(layout);
+    const hipError_t e = arena.reserve(h, bytes);
+    if (e == hipSuccess) carve(arena, layout);
+    return e;
+}
+
 int wave_upload_geometry(gams_gpu_t *h, gams_wave_plan_t *p) {
-    gams_pool_free(h, false, p->arena_geom, p->arena_geom_bytes);
-    p->arena_geom = nullptr;
-    p->d_tiles = nullptr;
-    p->d_tile_off = nullptr;
     const size_t nt = std::max<size_t>(p->tiles.size(), 1);
-    const size_t b_tiles = gams_align256(nt * sizeof(WaveTile));
-    const size_t b_off = gams_align256((nt + 2) * sizeof(unsigned long long));   // + the two totals
-    const size_t b_cnt = gams_align256(nt * sizeof(uint32_t));
     for (auto &w : p->way) w.d_tile_cnt = nullptr;
-    GAMS_HIP(h, gams_pool_alloc(h, false, b_tiles + b_off + b_cnt * p->depth,
-                                reinterpret_cast<void **>(&p->arena_geom), &p->arena_geom_bytes));
-    p->d_tiles = reinterpret_cast<WaveTile *>(p->arena_geom);
-    p->d_tile_off = reinterpret_cast<unsigned long long *>(p->arena_geom + b_tiles);
-    for (uint32_t k = 0; k < p->depth; ++k)
-        p->way[k].d_tile_cnt = reinterpret_cast<uint32_t *>(p->arena_geom + b_tiles + b_off + b_cnt * k);
+    auto geom = [&](Carver &c) {
+        p->d_tiles = c.take<WaveTile>(nt);
+        p->d_tile_off = c.take<unsigned long long>(nt + 2);   // + the two totals
+        for (uint32_t k = 0; k < p->depth; ++k) p->way[k].d_tile_cnt = c.take<uint32_t>(nt);
+    };
+    GAMS_HIP(h, wave_arena(h, p->arena_geom, geom));
     if (p->flags & GAMS_WAVE_PEAKS) {
         // a slot of tw/8 records per tile (typical density is 1-2 % of the windows); a tile that
-        // overflows makes gams_wave_peaks() regrow the slots to tw records and run again
-        gams_pool_free(h, false, p->d_dense, p->d_dense_bytes);
-        p->d_dense = nullptr;
-        p->dense_cap = 0;
+        // overflows makes the first reader regrow the slots to the fullest tile and run again (wave_regrow_slots)
+        p->d_dense.free(h);
         p->tile_cap = std::max<uint32_t>(p->tile_cap_req ? p->tile_cap_req : p->sel.tw / 8u, 16u);
-        for (auto &w : p->way) {
-            gams_pool_free(h, false, w.d_peaks, w.d_peaks_bytes);
-            w.d_peaks = nullptr;
-        }
-        for (uint32_t k = 0; k < p->depth; ++k)
-            GAMS_HIP(h, gams_pool_alloc(h, false, nt * (size_t)p->tile_cap * sizeof(gams_peak_t),
-                                        reinterpret_cast<void **>(&p->way[k].d_peaks), &p->way[k].d_peaks_bytes));
+        for (auto &w : p->way) w.d_peaks.free(h);
+        const size_t slots = nt * (size_t)p->tile_cap * sizeof(gams_peak_t);
+        for (uint32_t k = 0; k < p->depth; ++k) GAMS_HIP(h, p->way[k].d_peaks.reserve(h, slots));
     }
     if (!p->tiles.empty())
         GAMS_HIP(h, hipMemcpy(p->d_tiles, p->tiles.data(), p->tiles.size() * sizeof(WaveTile),
@@ -423,28 +469,57 @@ int wave_alloc_ways(gams_gpu_t *h, gams_wave_plan_t *p) {
     for (uint32_t k = 0; k < p->depth; ++k) {
         gams_wave_plan::Way &w = p->way[k];
         if (!w.d_counters) {
-            GAMS_HIP(h, gams_pool_alloc(h, false, kCounterRing * kSlotWords * sizeof(unsigned long long),
-                                        reinterpret_cast<void **>(&w.d_counters), &w.d_counters_bytes));
+            const size_t ring = kCounterRing * kSlotWords * sizeof(unsigned long long);
+            GAMS_HIP(h, w.d_counters.reserve(h, ring));
             // queued in front of the way's first run on its own stream
-            GAMS_HIP(h, hipMemsetAsync(w.d_counters, 0, kCounterRing * kSlotWords * sizeof(unsigned long long),
-                                       wave_stream(h, p, k)));
+            GAMS_HIP(h, hipMemsetAsync(w.d_counters, 0, ring, wave_stream(h, p, k)));
             w.runs = 0;
         }
         if (need_dense && !w.d_dense_cnt) {
-            GAMS_HIP(h, gams_pool_alloc(h, false, base * sizeof(uint32_t), reinterpret_cast<void **>(&w.d_dense_cnt),
-                                        &w.d_dense_cnt_bytes));
-            GAMS_HIP(h, gams_pool_alloc(h, false, base, reinterpret_cast<void **>(&w.d_dense_sig),
-                                        &w.d_dense_sig_bytes));
+            GAMS_HIP(h, w.d_dense_cnt.reserve(h, base * sizeof(uint32_t)));
+            GAMS_HIP(h, w.d_dense_sig.reserve(h, base));
         }
         if (p->serial && !p->repair && !w.d_filtered)
-            GAMS_HIP(h, gams_pool_alloc(h, false, base * sizeof(float), reinterpret_cast<void **>(&w.d_filtered),
-                                        &w.d_filtered_bytes));
+            GAMS_HIP(h, w.d_filtered.reserve(h, base * sizeof(float)));
         if (p->repair && !w.d_jac) {
-            GAMS_HIP(h, gams_pool_alloc(h, false, wave_jac_carve(nullptr, p->total_windows, p).bytes,
-                                        reinterpret_cast<void **>(&w.d_jac), &w.d_jac_bytes));
-            GAMS_HIP(h, gams_pool_alloc(h, true, kJacWords * 8, reinterpret_cast<void **>(&w.h_ctl), &w.h_ctl_bytes));
+            const size_t jac = wave_jac_carve(nullptr, p->total_windows, p).bytes;
+            GAMS_HIP(h, w.d_jac.reserve(h, jac));
+            GAMS_HIP(h, w.h_ctl.reserve(h, kJacWords * 8));
         }
     }
+    return GAMS_OK;
+}
+
+// ---- what the readers of a pass share ---------------------------------------------------------------------------
+// Buffers are sized from two device-written words, the peaks of the pass and of its fullest tile: are they something
+// a pass over this plan can produce?  (A tile signals at most its own windows, all tiles together at most the batch's.)
+bool wave_totals_plausible(const gams_wave_plan_t *p, uint64_t total, uint64_t worst) {
+    return worst <= p->sel.tw && total <= p->total_windows && total <= (uint64_t)p->tiles.size() * worst;
+}
+
+// Some tile signalled more windows than its slot holds.  The device has reported the fullest tile (runs are
+// deterministic, so that is what the slots need -- at GRCh38 step 1 a slot of tw records per tile would be ~50 GB per
+// way) and every pass still held is run again into the new slots: same inputs, same results.  The run counter only
+// steps back by the passes repeated, so the way rotation and the history gams_wave_plan_select sees stay.
+int wave_regrow_slots(gams_gpu_t *h, gams_wave_plan_t *p, uint64_t worst) {
+    p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->sel.tw, (worst + 15u) & ~(uint64_t)15u);
+    const uint32_t age = p->sel_age;
+    const uint32_t again = (uint32_t)std::min<uint64_t>(p->depth, p->run_idx);
+    int rc = wave_sync_ways(h, p);
+    if (rc == GAMS_OK) rc = wave_upload_geometry(h, p);
+    if (rc == GAMS_OK) {
+        p->run_idx -= again;
+        for (uint32_t k = 0; k < again && rc == GAMS_OK; ++k) rc = gams_wave_run(h, p);
+        p->sel_age = age;
+    }
+    return rc;
+}
+
+// the first d_dense of a tiling: typical density is 1-3 % of the windows; a fuller result makes its reader regrow it
+int wave_first_dense(gams_gpu_t *h, gams_wave_plan_t *p) {
+    if (p->d_dense) return GAMS_OK;
+    const size_t want = (size_t)(p->total_windows / 16 + 4096) * sizeof(gams_peak_t);
+    GAMS_HIP(h, p->d_dense.reserve(h, want));
     return GAMS_OK;
 }
 
@@ -498,58 +573,42 @@ int gams_wave_plan_create(gams_gpu_t *h, gams_seqset_t *s, const gams_wave_param
         return rc;
     }
     wave_set_band(p);
-    auto fail = [&](int code) {
-        gams_wave_plan_destroy(h, p);
-        return code;
+    // from here on the plan takes blocks and events: every early return gives the half-built plan to gams_wave_plan_destroy
+    auto destroy = [h](gams_wave_plan_t *q) { gams_wave_plan_destroy(h, q); };
+    std::unique_ptr<gams_wave_plan_t, decltype(destroy)> half_built(p, destroy);
+    const size_t size1 = (size_t)params->size + 1;
+    auto fixed = [&](Carver &c) {
+        p->d_ctgs = c.take<WaveCtgDev>(std::max<size_t>(s->n_ctg, 1));
+        p->d_const_sig = c.take<int8_t>(size1);
+        p->d_xtab = p->repair ? c.take<float>(size1) : nullptr;
     };
-#define PLAN_HIP(call)                                                                    \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            (void)hipGetLastError();                                                      \
-            h->err = std::string(#call) + ": " + hipGetErrorString(e_);                   \
-            return fail(GAMS_EHIP);                                                       \
-        }                                                                                 \
-    } while (0)
-    {
-        const size_t b_ctgs = gams_align256(std::max<size_t>(s->n_ctg, 1) * sizeof(WaveCtgDev));
-        const size_t b_const = gams_align256((size_t)params->size + 1);
-        const size_t b_xtab = p->repair ? gams_align256(((size_t)params->size + 1) * sizeof(float)) : 0;
-        PLAN_HIP(gams_pool_alloc(h, false, b_ctgs + b_const + b_xtab, reinterpret_cast<void **>(&p->arena_fixed),
-                                 &p->arena_fixed_bytes));
-        p->d_ctgs = reinterpret_cast<WaveCtgDev *>(p->arena_fixed);
-        p->d_const_sig = reinterpret_cast<int8_t *>(p->arena_fixed + b_ctgs);
-        if (p->repair) {
-            // the data value of a window with k G/C bases, as the reference computes it: k as f32 / size as f32
-            p->d_xtab = reinterpret_cast<float *>(p->arena_fixed + b_ctgs + b_const);
-            std::vector<float> xt((size_t)params->size + 1);
-            for (size_t k = 0; k < xt.size(); ++k) xt[k] = (float)k / (float)params->size;
-            PLAN_HIP(hipMemcpy(p->d_xtab, xt.data(), xt.size() * sizeof(float), hipMemcpyHostToDevice));
-            std::vector<JacTile> jt;
-            for (uint32_t c = 0; c < s->n_ctg; ++c)
-                for (uint32_t w0 = 0; w0 < p->ctgs[c].n_win; w0 += kJacTile)
-                    jt.push_back(JacTile{c, w0, p->ctgs[c].n_win, 0u, p->ctgs[c].win_base});
-            p->n_jtiles = (uint32_t)jt.size();
-            PLAN_HIP(gams_pool_alloc(h, false, std::max<size_t>(jt.size(), 1) * sizeof(JacTile),
-                                     reinterpret_cast<void **>(&p->d_jtiles), &p->d_jtiles_bytes));
-            if (!jt.empty())
-                PLAN_HIP(hipMemcpy(p->d_jtiles, jt.data(), jt.size() * sizeof(JacTile), hipMemcpyHostToDevice));
-        }
+    GAMS_HIP(h, wave_arena(h, p->arena_fixed, fixed));
+    if (p->repair) {
+        // the data value of a window with k G/C bases, as the reference computes it: k as f32 / size as f32
+        std::vector<float> xt(size1);
+        for (size_t k = 0; k < xt.size(); ++k) xt[k] = (float)k / (float)params->size;
+        GAMS_HIP(h, hipMemcpy(p->d_xtab, xt.data(), xt.size() * sizeof(float), hipMemcpyHostToDevice));
+        std::vector<JacTile> jt;
+        for (uint32_t c = 0; c < s->n_ctg; ++c)
+            for (uint32_t w0 = 0; w0 < p->ctgs[c].n_win; w0 += kJacTile)
+                jt.push_back(JacTile{c, w0, p->ctgs[c].n_win, 0u, p->ctgs[c].win_base});
+        p->n_jtiles = (uint32_t)jt.size();
+        const size_t jt_bytes = std::max<size_t>(jt.size(), 1) * sizeof(JacTile);
+        GAMS_HIP(h, p->d_jtiles.reserve(h, jt_bytes));
+        if (!jt.empty()) GAMS_HIP(h, hipMemcpy(p->d_jtiles, jt.data(), jt.size() * sizeof(JacTile), hipMemcpyHostToDevice));
     }
-    if (s->n_ctg)
-        PLAN_HIP(hipMemcpy(p->d_ctgs, p->ctgs.data(), s->n_ctg * sizeof(WaveCtgDev), hipMemcpyHostToDevice));
+    if (s->n_ctg) GAMS_HIP(h, hipMemcpy(p->d_ctgs, p->ctgs.data(), s->n_ctg * sizeof(WaveCtgDev), hipMemcpyHostToDevice));
     rc = wave_upload_geometry(h, p);
-    if (rc != GAMS_OK) return fail(rc);
+    if (rc != GAMS_OK) return rc;
     rc = wave_alloc_ways(h, p);
-    if (rc != GAMS_OK) return fail(rc);
+    if (rc != GAMS_OK) return rc;
     hipLaunchKernelGGL(wave_const_table_kernel, dim3((params->size + 256) / 256), dim3(256), 0, h->compute,
                        p->d_const_sig, (uint32_t)params->size, params->lag, params->threshold);
-    PLAN_HIP(hipGetLastError());
-    PLAN_HIP(hipEventCreateWithFlags(&p->ready, hipEventDisableTiming));
-    PLAN_HIP(hipEventRecord(p->ready, h->compute));
+    GAMS_HIP(h, hipGetLastError());
+    GAMS_HIP(h, hipEventCreateWithFlags(&p->ready, hipEventDisableTiming));
+    GAMS_HIP(h, hipEventRecord(p->ready, h->compute));
     p->way[0].seen_ready = true;   // same stream
-#undef PLAN_HIP
-    *out = p;
+    *out = half_built.release();
     return GAMS_OK;
 }
 
@@ -562,41 +621,15 @@ void gams_wave_plan_destroy(gams_gpu_t *h, gams_wave_plan_t *p) {
             if (wave_stream(h, p, k)) (void)hipStreamSynchronize(wave_stream(h, p, k));
         if (h->readback) (void)hipStreamSynchronize(h->readback);
     }
+    p->release(h);
     if (p->rows) {
-        WaveRows *r = p->rows;
-        gams_pool_free(h, false, r->arena, r->arena_bytes);
-        gams_pool_free(h, false, r->tmp, r->tmp_bytes);
-        gams_pool_free(h, false, r->d_text, r->d_text_bytes);
-        gams_pool_free(h, true, r->h_text, r->h_text_bytes);
-        gams_pool_free(h, true, r->h_words, r->h_words_bytes);
-        if (r->done) (void)hipEventDestroy(r->done);
-        for (auto &g : r->graph)
+        if (p->rows->done) (void)hipEventDestroy(p->rows->done);
+        for (auto &g : p->rows->graph)
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
-        delete r;
-        p->rows = nullptr;
+        delete p->rows;
     }
-    if (p->sigtext) {
-        WaveSig *g = p->sigtext;
-        gams_pool_free(h, false, g->arena, g->arena_bytes);
-        gams_pool_free(h, false, g->d_text, g->d_text_bytes);
-        gams_pool_free(h, true, g->h_text, g->h_text_bytes);
-        gams_pool_free(h, true, g->h_words, g->h_words_bytes);
-        delete g;
-        p->sigtext = nullptr;
-    }
-    gams_pool_free(h, false, p->arena_fixed, p->arena_fixed_bytes);
-    gams_pool_free(h, false, p->arena_geom, p->arena_geom_bytes);
-    gams_pool_free(h, false, p->d_jtiles, p->d_jtiles_bytes);
-    gams_pool_free(h, false, p->d_dense, p->d_dense_bytes);
-    gams_pool_free(h, true, p->h_peaks, p->h_peaks_bytes);
+    delete p->sigtext;
     for (auto &w : p->way) {
-        gams_pool_free(h, false, w.d_peaks, w.d_peaks_bytes);
-        gams_pool_free(h, false, w.d_counters, w.d_counters_bytes);
-        gams_pool_free(h, false, w.d_dense_cnt, w.d_dense_cnt_bytes);
-        gams_pool_free(h, false, w.d_dense_sig, w.d_dense_sig_bytes);
-        gams_pool_free(h, false, w.d_filtered, w.d_filtered_bytes);
-        gams_pool_free(h, false, w.d_jac, w.d_jac_bytes);
-        gams_pool_free(h, true, w.h_ctl, w.h_ctl_bytes);
         if (w.done) (void)hipEventDestroy(w.done);
         if (w.ran_ev) (void)hipEventDestroy(w.ran_ev);
     }
@@ -969,9 +1002,6 @@ int gams_wave_run(gams_gpu_t *h, gams_wave_plan_t *p) {
     return GAMS_OK;
 }
 
-// The second queueing thread of gams_wave_run_n.  It lives as long as the plan (binding a new host
-// thread to the device costs ~100 us, more than a short batch), sleeps between batches and, once
-// armed, spins until the caller has queued the first round.
 // A queueing thread of gams_wave_run_n.  It lives as long as the plan (binding a new host thread
 // to the device costs ~100 us, more than a short batch), sleeps between batches and, once armed,
 // spins until the caller has queued the first round.
@@ -1211,75 +1241,41 @@ int gams_wave_peaks(gams_gpu_t *h, gams_wave_plan_t *p, const gams_peak_t **peak
             GAMS_HIP(h, hipEventRecord(w.ran_ev, wave_stream(h, p, wave_read_way_index(p))));
             GAMS_HIP(h, hipStreamWaitEvent(h->readback, w.ran_ev, 0));
         }
-        if (!p->d_dense) {
-            // typical density is 1-3 % of the windows; a fuller result regrows below
-            const uint64_t want = p->total_windows / 16 + 4096;
-            GAMS_HIP(h, gams_pool_alloc(h, false, want * sizeof(gams_peak_t),
-                                        reinterpret_cast<void **>(&p->d_dense), &p->d_dense_bytes));
-            p->dense_cap = p->d_dense_bytes / sizeof(gams_peak_t);
+        {
+            const int drc = wave_first_dense(h, p);
+            if (drc != GAMS_OK) return drc;
         }
-        wave_queue_offsets(h->readback, w.d_tile_cnt, (uint32_t)nt, p->d_tile_off, d_totals);
-        GAMS_HIP(h, hipGetLastError());
-        hipLaunchKernelGGL(wave_gather_kernel, dim3((unsigned)nt), dim3(64), 0, h->readback, w.d_peaks,
-                           p->tile_cap, w.d_tile_cnt, p->d_tile_off, p->d_dense, (unsigned long long)p->dense_cap);
-        GAMS_HIP(h, hipGetLastError());
+        Chain ch{h->readback};
+        ch.pack(p, w);
+        GAMS_HIP(h, ch.err);
         GAMS_HIP(h, hipMemcpyAsync(h->pin_scratch, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                    h->readback));
         GAMS_HIP(h, hipStreamSynchronize(h->readback));
         const uint64_t total = h->pin_scratch[0];
         const uint64_t worst = h->pin_scratch[1];
-        // Buffers below are sized from these two device-written words: refuse values no pass over this
-        // plan can produce (a tile signals at most its own windows, all tiles together at most the
-        // batch's) instead of allocating and copying by them.
-        if (worst > p->sel.tw || total > p->total_windows || total > (uint64_t)nt * worst)
+        // (values no pass over this plan can produce are refused instead of allocating and copying by them)
+        if (!wave_totals_plausible(p, total, worst))
             return gams_fail(h, GAMS_EHIP,
                              "wave_peaks: inconsistent peak counts from the device (total " + std::to_string(total) +
                                  ", fullest tile " + std::to_string(worst) + ", " + std::to_string(p->total_windows) +
                                  " windows in " + std::to_string(nt) + " tiles of at most " + std::to_string(p->sel.tw) + ")");
         if (worst > p->tile_cap) {
-            // some tile signalled more windows than its slot holds: the device has reported the
-            // fullest tile (runs are deterministic, so that is what the slots need -- at GRCh38 step 1 a
-            // slot of tw records per tile would be ~50 GB per way) and every pass still held is run
-            // again into the new slots: same inputs, same results.  The run counter only steps back by
-            // the passes repeated, so the way rotation and the history gams_wave_plan_select sees stay.
-            p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->sel.tw, (worst + 15u) & ~(uint64_t)15u);
-            const uint32_t age = p->sel_age;
-            const uint32_t again = (uint32_t)std::min<uint64_t>(p->depth, p->run_idx);
-            int rc = wave_sync_ways(h, p);
-            if (rc == GAMS_OK) rc = wave_upload_geometry(h, p);
-            if (rc == GAMS_OK) {
-                p->run_idx -= again;
-                for (uint32_t k = 0; k < again && rc == GAMS_OK; ++k) rc = gams_wave_run(h, p);
-                p->sel_age = age;
-            }
+            const int rc = wave_regrow_slots(h, p, worst);
             if (rc != GAMS_OK) return rc;
             continue;
         }
         if (total) {
-            if (total > p->dense_cap) {
-                gams_pool_free(h, false, p->d_dense, p->d_dense_bytes);
-                p->d_dense = nullptr;
-                p->dense_cap = 0;
-                const uint64_t want = total + total / 4 + 1024;
-                GAMS_HIP(h, gams_pool_alloc(h, false, want * sizeof(gams_peak_t),
-                                            reinterpret_cast<void **>(&p->d_dense), &p->d_dense_bytes));
-                p->dense_cap = p->d_dense_bytes / sizeof(gams_peak_t);
-                hipLaunchKernelGGL(wave_gather_kernel, dim3((unsigned)nt), dim3(64), 0, h->readback, w.d_peaks,
-                                   p->tile_cap, w.d_tile_cnt, p->d_tile_off, p->d_dense,
-                                   (unsigned long long)p->dense_cap);
-                GAMS_HIP(h, hipGetLastError());
+            const size_t grown = (total + total / 4 + 1024) * sizeof(gams_peak_t);
+            if (total > p->dense_cap()) {
+                GAMS_HIP(h, p->d_dense.grow(h, total * sizeof(gams_peak_t), grown));
+                ch.gather(p, w);
+                GAMS_HIP(h, ch.err);
             }
-            if (total * sizeof(gams_peak_t) > p->h_peaks_bytes) {
-                gams_pool_free(h, true, p->h_peaks, p->h_peaks_bytes);
-                p->h_peaks = nullptr;
-                p->h_peaks_bytes = 0;
-                GAMS_HIP(h, gams_pool_alloc(h, true, (total + total / 4 + 1024) * sizeof(gams_peak_t),
-                                            reinterpret_cast<void **>(&p->h_peaks), &p->h_peaks_bytes));
-            }
-                GAMS_HIP(h, hipMemcpyAsync(p->h_peaks, p->d_dense, total * sizeof(gams_peak_t),
-                                       hipMemcpyDeviceToHost, h->readback));
-                GAMS_HIP(h, hipStreamSynchronize(h->readback));
-            }
+            GAMS_HIP(h, p->h_peaks.grow(h, total * sizeof(gams_peak_t), grown));
+            GAMS_HIP(h, hipMemcpyAsync(p->h_peaks, p->d_dense, total * sizeof(gams_peak_t), hipMemcpyDeviceToHost,
+                                       h->readback));
+            GAMS_HIP(h, hipStreamSynchronize(h->readback));
+        }
         *peaks = p->h_peaks;   // NULL when there is none
         *n_peaks = total;
         return GAMS_OK;
@@ -1340,6 +1336,16 @@ std::string rows_text_tables(const char *who, uint32_t n_ctg, const char *const 
     return "";
 }
 
+// what both text entries ask of the chromosome table (GAMS_EINVAL): "" or what `who` has to report
+std::string rows_check_chr(const char *who, const gams_wave_plan_t *p, const char *const *chr, const int32_t *chr_start) {
+    for (uint32_t c = 0; c < p->set->n_ctg; ++c) {
+        if (!chr[c]) return std::string(who) + ": null chromosome name";
+        if (chr_start[c] < 0 || (int64_t)chr_start[c] + p->ctgs[c].len >= 0x7FFFFFFFll)
+            return std::string(who) + ": chromosome coordinates must be in [0, 2^31)";
+    }
+    return "";
+}
+
 struct RowTables {
     uint8_t *flags;
     int2 *headpos, *blk_head;
@@ -1369,15 +1375,13 @@ RowTables rows_carve(uint8_t *base, uint64_t cap) {
 // by what OTHER host threads do meanwhile, and the host layer runs one thread per handle.)
 int rows_emit(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t wi, hipStream_t st, uint64_t copy_bytes, hipGraph_t graph) {
     WaveRows *r = p->rows;
-    const size_t nt = p->tiles.size();
-    unsigned long long *d_totals = p->d_tile_off + nt;
     gams_wave_plan::Way &w = p->way[wi];
     const RowTables t = rows_carve(r->tmp, r->cap);
     const uint32_t n_ctg = p->set->n_ctg;
     RowArgs a{};
     a.rec = p->d_dense;
-    a.n_rec = d_totals;
-    a.cap = std::min<uint64_t>(r->cap, p->dense_cap);
+    a.n_rec = p->d_tile_off + p->tiles.size();   // the total behind the tiles' offsets
+    a.cap = std::min<uint64_t>(r->cap, p->dense_cap());
     a.tile_cap = p->tile_cap;
     a.ctgs = r->d_ctgs;
     a.n_ctg = n_ctg;
@@ -1395,82 +1399,25 @@ int rows_emit(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t wi, hipStream_t st, u
     a.blk_off = t.blk_off;
     a.nb_cap = t.nb_cap;
     a.text = r->d_text;
-    a.text_cap = r->d_text_bytes;
+    a.text_cap = r->d_text.cap;
     a.words = r->d_words;
-    hipGraphNode_t last = nullptr;
-    hipError_t err = hipSuccess;
-    auto kernel = [&](const void *fn, unsigned grid, unsigned block, void **args) {
-        if (err != hipSuccess) return;
-        if (!graph) {
-            err = hipLaunchKernel(fn, dim3(grid), dim3(block), args, 0, st);
-            return;
-        }
-        hipKernelNodeParams kp{};
-        kp.func = const_cast<void *>(fn);
-        kp.gridDim = dim3(grid);
-        kp.blockDim = dim3(block);
-        kp.sharedMemBytes = 0;
-        kp.kernelParams = args;
-        kp.extra = nullptr;
-        hipGraphNode_t node = nullptr;
-        err = hipGraphAddKernelNode(&node, graph, last ? &last : nullptr, last ? 1 : 0, &kp);
-        last = node;
-    };
-    auto copy = [&](void *dst, const void *src, size_t bytes) {
-        if (err != hipSuccess || bytes == 0) return;
-        if (!graph) {
-            err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-            return;
-        }
-        hipGraphNode_t node = nullptr;
-        err = hipGraphAddMemcpyNode1D(&node, graph, last ? &last : nullptr, last ? 1 : 0, dst, src, bytes, hipMemcpyDeviceToHost);
-        last = node;
-    };
-    // argument blocks (read when the launch / the node is made)
-    uint32_t *tile_cnt = w.d_tile_cnt;
-    uint32_t nt32 = (uint32_t)nt;
-    unsigned long long *tile_off = p->d_tile_off;
-    void *args_off1[] = {&tile_cnt, &nt32, &tile_off, &d_totals};
-    const gams_peak_t *slots = w.d_peaks;
-    uint32_t tile_cap = p->tile_cap;
-    const uint32_t *ctile_cnt = w.d_tile_cnt;
-    const unsigned long long *ctile_off = p->d_tile_off;
-    gams_peak_t *dense = p->d_dense;
-    unsigned long long dense_cap = p->dense_cap;
-    void *args_gather[] = {&slots, &tile_cap, &ctile_cnt, &ctile_off, &dense, &dense_cap};
+    Chain ch{st, graph};
     void *args_rows[] = {&a};
-    const uint32_t *blk_len = t.blk_len;
-    uint32_t nb = t.nb_cap;
-    unsigned long long *blk_off = t.blk_off, *blk_tot = t.blk_off + nb;
-    void *args_off2[] = {&blk_len, &nb, &blk_off, &blk_tot};
-    // (exclusive prefix of n counts: one workgroup, or spans of kOffSpan counts in three launches -- wave_kernels.hpp)
-    auto offsets = [&](void **all4, void **cnt_n_off, void **n_off_tot, uint32_t n) {
-        if (n <= kOffOneGroup) {
-            kernel(reinterpret_cast<const void *>(wave_offsets_kernel), 1, 1024, all4);
-            return;
-        }
-        const unsigned spans = (n + kOffSpan - 1u) / kOffSpan;
-        kernel(reinterpret_cast<const void *>(wave_offsets_sum_kernel), spans, 1024, cnt_n_off);
-        kernel(reinterpret_cast<const void *>(wave_offsets_base_kernel), 1, 1024, n_off_tot);
-        kernel(reinterpret_cast<const void *>(wave_offsets_scan_kernel), spans, 1024, cnt_n_off);
-    };
-    void *args_off1a[] = {&tile_cnt, &nt32, &tile_off}, *args_off1b[] = {&nt32, &tile_off, &d_totals};
-    offsets(args_off1, args_off1a, args_off1b, nt32);
-    kernel(reinterpret_cast<const void *>(wave_gather_kernel), (unsigned)nt, 64, args_gather);
-    kernel(reinterpret_cast<const void *>(rows_link_kernel), nb, 256, args_rows);
-    kernel(reinterpret_cast<const void *>(rows_heads_kernel), 1, 1024, args_rows);
-    kernel(reinterpret_cast<const void *>(rows_tail_kernel), (unsigned)((r->cap + 255) / 256), 256, args_rows);
-    kernel(reinterpret_cast<const void *>(rows_len_kernel), nb, 256, args_rows);
-    void *args_off2a[] = {&blk_len, &nb, &blk_off}, *args_off2b[] = {&nb, &blk_off, &blk_tot};
-    offsets(args_off2, args_off2a, args_off2b, nb);
-    kernel(reinterpret_cast<const void *>(rows_write_kernel), nb, 256, args_rows);
+    const uint32_t nb = t.nb_cap;
+    ch.pack(p, w);
+    ch.kernel(reinterpret_cast<const void *>(rows_link_kernel), nb, 256, args_rows);
+    ch.kernel(reinterpret_cast<const void *>(rows_heads_kernel), 1, 1024, args_rows);
+    ch.kernel(reinterpret_cast<const void *>(rows_tail_kernel), (unsigned)((r->cap + 255) / 256), 256, args_rows);
+    ch.kernel(reinterpret_cast<const void *>(rows_len_kernel), nb, 256, args_rows);
+    ch.offsets(t.blk_len, nb, t.blk_off, t.blk_off + nb);
+    ch.kernel(reinterpret_cast<const void *>(rows_write_kernel), nb, 256, args_rows);
     // the words (sizes, totals, per-ctg offsets: one block) and -- sized by the previous pass -- the text itself go to the
     // host behind the kernels
-    copy(r->h_words, r->d_words, ((size_t)n_ctg + 1 + 4) * 8);
-    copy(r->h_text, r->d_text, copy_bytes);
-    if (err != hipSuccess) {
+    ch.copy(r->h_words, r->d_words, ((size_t)n_ctg + 1 + 4) * 8);
+    ch.copy(r->h_text, r->d_text, copy_bytes);
+    if (ch.err != hipSuccess) {
         (void)hipGetLastError();
-        return gams_fail(h, GAMS_EHIP, std::string("wave_rows: ") + hipGetErrorString(err));
+        return gams_fail(h, GAMS_EHIP, std::string("wave_rows: ") + hipGetErrorString(ch.err));
     }
     return GAMS_OK;
 }
@@ -1490,40 +1437,28 @@ int rows_queue(gams_gpu_t *h, gams_wave_plan_t *p) {
     // on different lanes run side by side (eight short dependent kernels and a 2-MB copy per batch: on one shared
     // stream they were 117 us per batch for three plans in flight, the passes themselves 22).
     hipStream_t st = wave_stream(h, p, wi);
-    if (!p->d_dense) {
-        const uint64_t want = p->total_windows / 16 + 4096;
-        GAMS_HIP(h, gams_pool_alloc(h, false, want * sizeof(gams_peak_t), reinterpret_cast<void **>(&p->d_dense),
-                                    &p->d_dense_bytes));
-        p->dense_cap = p->d_dense_bytes / sizeof(gams_peak_t);
+    {
+        const int drc = wave_first_dense(h, p);
+        if (drc != GAMS_OK) return drc;
     }
-    const uint64_t cap = std::min<uint64_t>(p->dense_cap, 0x7FFFFF00ull);
-    if (r->cap < cap) {
-        gams_pool_free(h, false, r->tmp, r->tmp_bytes);
-        r->tmp = nullptr;
+    const uint64_t cap = std::min<uint64_t>(p->dense_cap(), 0x7FFFFF00ull);
+    if (r->cap < cap) {   // (in records: the block is replaced even where the pool had rounded it up far enough)
+        r->tmp.free(h);
         r->cap = 0;
-        GAMS_HIP(h, gams_pool_alloc(h, false, rows_carve(nullptr, cap).bytes, reinterpret_cast<void **>(&r->tmp), &r->tmp_bytes));
+        const size_t tables = rows_carve(nullptr, cap).bytes;
+        GAMS_HIP(h, r->tmp.reserve(h, tables));
         r->cap = cap;
     }
     const uint64_t want_text = std::max<uint64_t>(r->cap * ((uint64_t)r->max_name + 44u), 1u << 20);
-    if (r->d_text_bytes < want_text) {
-        gams_pool_free(h, false, r->d_text, r->d_text_bytes);
-        r->d_text = nullptr;
-        r->d_text_bytes = 0;
-        GAMS_HIP(h, gams_pool_alloc(h, false, want_text, reinterpret_cast<void **>(&r->d_text), &r->d_text_bytes));
-    }
+    GAMS_HIP(h, r->d_text.reserve(h, want_text));
     // the text's speculative copy: sized by the previous pass, kept while it still fits (the graph holds the size)
     uint64_t copy_bytes = r->copy_bytes;
     if (r->last_bytes && (copy_bytes < r->last_bytes || copy_bytes > 2 * r->last_bytes + (1u << 20)))
-        copy_bytes = std::min<uint64_t>(r->d_text_bytes, (r->last_bytes + r->last_bytes / 8 + 65536) & ~(uint64_t)65535);
-    if (copy_bytes > r->h_text_bytes) {
-        gams_pool_free(h, true, r->h_text, r->h_text_bytes);
-        r->h_text = nullptr;
-        r->h_text_bytes = 0;
-        GAMS_HIP(h, gams_pool_alloc(h, true, copy_bytes, reinterpret_cast<void **>(&r->h_text), &r->h_text_bytes));
-    }
+        copy_bytes = std::min<uint64_t>(r->d_text.cap, (r->last_bytes + r->last_bytes / 8 + 65536) & ~(uint64_t)65535);
+    GAMS_HIP(h, r->h_text.reserve(h, copy_bytes));
     r->copy_bytes = copy_bytes;
     r->copied = copy_bytes;
-    const WaveRows::RowGraphKey key{p->d_dense, r->tmp, r->d_text, r->h_text, w.d_peaks, w.d_tile_cnt, p->d_tile_off, p->dense_cap,
+    const WaveRows::RowGraphKey key{p->d_dense, r->tmp, r->d_text, r->h_text, w.d_peaks, w.d_tile_cnt, p->d_tile_off, p->dense_cap(),
                           r->cap, copy_bytes, p->tile_cap, (uint32_t)p->tiles.size()};
     WaveRows::RowGraph &g = r->graph[wi];
     bool launched = false;
@@ -1578,19 +1513,16 @@ int gams_wave_rows_setup(gams_gpu_t *h, gams_wave_plan_t *p, const char *const *
                              "peaks on the host (gams_wave_peaks)");
     }
     const uint32_t n_ctg = p->set->n_ctg;
-    for (uint32_t c = 0; c < n_ctg; ++c) {
-        if (!chr[c]) return gams_fail(h, GAMS_EINVAL, "wave_rows_setup: null chromosome name");
-        if (chr_start[c] < 0 || (int64_t)chr_start[c] + p->ctgs[c].len >= 0x7FFFFFFFll)
-            return gams_fail(h, GAMS_EINVAL, "wave_rows_setup: chromosome coordinates must be in [0, 2^31)");
+    {
+        const std::string bad = rows_check_chr("wave_rows_setup", p, chr, chr_start);
+        if (!bad.empty()) return gams_fail(h, GAMS_EINVAL, bad);
     }
     GAMS_HIP(h, hipSetDevice(h->device));
     if (p->rows) {                       // set up again (other names / coverage): drop the old tables
         GAMS_HIP(h, hipStreamSynchronize(h->readback));
         WaveRows *r = p->rows;
-        gams_pool_free(h, false, r->arena, r->arena_bytes);
-        gams_pool_free(h, true, r->h_words, r->h_words_bytes);
-        r->arena = nullptr;
-        r->h_words = nullptr;
+        r->arena.free(h);
+        r->h_words.free(h);
         for (auto &g : r->graph) {
             if (g.exec) (void)hipGraphExecDestroy(g.exec);
             g.exec = nullptr;
@@ -1608,18 +1540,18 @@ int gams_wave_rows_setup(gams_gpu_t *h, gams_wave_plan_t *p, const char *const *
     if (!bad.empty()) return gams_fail(h, GAMS_EUNSUPPORTED, bad);
     r->max_name = 0;
     for (const RowCtg &c : rc) r->max_name = std::max(r->max_name, c.name_len);
-    const size_t b_ctgs = gams_align256(rc.size() * sizeof(RowCtg)), b_names = gams_align256(std::max<size_t>(blob.size(), 1)),
-                 b_gc = gams_align256(gct.size()), b_words = gams_align256(((size_t)n_ctg + 1 + 4) * 8);
-    GAMS_HIP(h, gams_pool_alloc(h, false, b_ctgs + b_names + b_gc + b_words, reinterpret_cast<void **>(&r->arena),
-                                &r->arena_bytes));
-    r->d_ctgs = reinterpret_cast<RowCtg *>(r->arena);
-    r->d_names = reinterpret_cast<char *>(r->arena + b_ctgs);
-    r->d_gctab = r->arena + b_ctgs + b_names;
-    r->d_words = reinterpret_cast<unsigned long long *>(r->arena + b_ctgs + b_names + b_gc);
+    const size_t n_words = (size_t)n_ctg + 1 + 4;
+    auto arena = [&](Carver &c) {
+        r->d_ctgs = c.take<RowCtg>(rc.size());
+        r->d_names = c.take<char>(std::max<size_t>(blob.size(), 1));
+        r->d_gctab = c.take<uint8_t>(gct.size());
+        r->d_words = c.take<unsigned long long>(n_words);
+    };
+    GAMS_HIP(h, wave_arena(h, r->arena, arena));
     GAMS_HIP(h, hipMemcpy(r->d_ctgs, rc.data(), rc.size() * sizeof(RowCtg), hipMemcpyHostToDevice));
     if (!blob.empty()) GAMS_HIP(h, hipMemcpy(r->d_names, blob.data(), blob.size(), hipMemcpyHostToDevice));
     GAMS_HIP(h, hipMemcpy(r->d_gctab, gct.data(), gct.size(), hipMemcpyHostToDevice));
-    GAMS_HIP(h, gams_pool_alloc(h, true, ((size_t)n_ctg + 1 + 4) * 8, reinterpret_cast<void **>(&r->h_words), &r->h_words_bytes));
+    GAMS_HIP(h, r->h_words.reserve(h, n_words * 8));
     return GAMS_OK;
 }
 
@@ -1650,48 +1582,32 @@ int gams_wave_rows_end(gams_gpu_t *h, gams_wave_plan_t *p, const char **text, ui
         if (ctg_off) *ctg_off = reinterpret_cast<const uint64_t *>(r->h_words + 4);
         return GAMS_OK;
     }
-    const size_t nt = p->tiles.size();
     for (int attempt = 0; attempt < 4; ++attempt) {
         GAMS_HIP(h, hipEventSynchronize(r->done));
         const uint64_t n_rec = r->h_words[0], bytes = r->h_words[1], total = r->h_words[2], worst = r->h_words[3];
-        if (worst > p->sel.tw || total > p->total_windows || total > (uint64_t)nt * worst)
+        if (!wave_totals_plausible(p, total, worst))
             return gams_fail(h, GAMS_EHIP, "wave_rows: inconsistent peak counts from the device");
         int rc = GAMS_OK;
         if (worst > p->tile_cap) {
-            // a tile signalled more windows than its slot holds: larger slots, the passes still held run again
-            // (see gams_wave_peaks), then the rows once more
-            p->tile_cap_req = (uint32_t)std::min<uint64_t>(p->sel.tw, (worst + 15u) & ~(uint64_t)15u);
-            const uint32_t age = p->sel_age;
-            const uint32_t again = (uint32_t)std::min<uint64_t>(p->depth, p->run_idx);
-            rc = wave_sync_ways(h, p);
-            if (rc == GAMS_OK) rc = wave_upload_geometry(h, p);
-            if (rc == GAMS_OK) {
-                p->run_idx -= again;
-                for (uint32_t k = 0; k < again && rc == GAMS_OK; ++k) rc = gams_wave_run(h, p);
-                p->sel_age = age;
-            }
-        } else if (total > p->dense_cap || total > r->cap) {
+            rc = wave_regrow_slots(h, p, worst);   // ... then the rows once more
+        } else if (total > p->dense_cap() || total > r->cap) {
             if (total > 0x7FFFFF00ull) return gams_fail(h, GAMS_EUNSUPPORTED, "wave_rows: more than 2^31 peaks in one pass");
-            gams_pool_free(h, false, p->d_dense, p->d_dense_bytes);
-            p->d_dense = nullptr;
-            p->dense_cap = 0;
-            GAMS_HIP(h, gams_pool_alloc(h, false, (total + total / 4 + 1024) * sizeof(gams_peak_t),
-                                        reinterpret_cast<void **>(&p->d_dense), &p->d_dense_bytes));
-            p->dense_cap = p->d_dense_bytes / sizeof(gams_peak_t);
-        } else if (bytes > r->d_text_bytes) {
+            const size_t grown = (total + total / 4 + 1024) * sizeof(gams_peak_t);
+            p->d_dense.free(h);
+            GAMS_HIP(h, p->d_dense.reserve(h, grown));
+        } else if (bytes > r->d_text.cap) {
             return gams_fail(h, GAMS_EHIP, "wave_rows: text beyond its bound");
         } else {
             (void)n_rec;
             if (bytes > r->copied) {
                 // the speculative copy fell short (the first pass, or more text than last time): the rest now
-                if (r->h_text_bytes < bytes) {
-                    char *nt_ = nullptr;
-                    size_t nb_ = 0;
-                    GAMS_HIP(h, gams_pool_alloc(h, true, bytes + bytes / 4 + 4096, reinterpret_cast<void **>(&nt_), &nb_));
-                    if (r->copied) std::memcpy(nt_, r->h_text, r->copied);
-                    gams_pool_free(h, true, r->h_text, r->h_text_bytes);
-                    r->h_text = nt_;
-                    r->h_text_bytes = nb_;
+                if (r->h_text.cap < bytes) {
+                    // the new block first: the old one still holds the part already copied
+                    Kept<char> blk{true};
+                    GAMS_HIP(h, blk.reserve(h, bytes + bytes / 4 + 4096));
+                    if (r->copied) std::memcpy(blk, r->h_text, r->copied);
+                    std::swap(blk, r->h_text);
+                    blk.free(h);
                 }
                 GAMS_HIP(h, hipMemcpyAsync(r->h_text + r->copied, r->d_text + r->copied, bytes - r->copied,
                                            hipMemcpyDeviceToHost, h->readback));
@@ -1703,7 +1619,7 @@ int gams_wave_rows_end(gams_gpu_t *h, gams_wave_plan_t *p, const char **text, ui
             off[n_ctg] = bytes;
             for (uint32_t c = n_ctg; c-- > 0;)
                 if (off[c] == ~0ull) off[c] = off[c + 1];
-            *text = bytes ? r->h_text : nullptr;
+            *text = bytes ? r->h_text.p : nullptr;
             *text_bytes = bytes;
             if (ctg_off) *ctg_off = reinterpret_cast<const uint64_t *>(off);
             return GAMS_OK;
@@ -1723,10 +1639,9 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
     if (!p->ran) return gams_fail(h, GAMS_ESTATE, "wave_signal_text: no run to read");
     const gams_wave_params_t &q = p->prm;
     const uint32_t n_ctg = p->set->n_ctg;
-    for (uint32_t c = 0; c < n_ctg; ++c) {
-        if (!chr[c]) return gams_fail(h, GAMS_EINVAL, "wave_signal_text: null chromosome name");
-        if (chr_start[c] < 0 || (int64_t)chr_start[c] + p->ctgs[c].len >= 0x7FFFFFFFll)
-            return gams_fail(h, GAMS_EINVAL, "wave_signal_text: chromosome coordinates must be in [0, 2^31)");
+    {
+        const std::string bad = rows_check_chr("wave_signal_text", p, chr, chr_start);
+        if (!bad.empty()) return gams_fail(h, GAMS_EINVAL, bad);
     }
     GAMS_HIP(h, hipSetDevice(h->device));
     {
@@ -1743,8 +1658,6 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
     if (!p->sigtext) p->sigtext = new WaveSig();
     WaveSig *g = p->sigtext;
     if (!g->arena || g->names_cap < blob.size()) {
-        gams_pool_free(h, false, g->arena, g->arena_bytes);
-        g->arena = nullptr;
         std::vector<SigTile> st;
         for (uint32_t c = 0; c < n_ctg; ++c)
             for (uint32_t w0 = 0; w0 < p->ctgs[c].n_win; w0 += kSigRows)
@@ -1761,12 +1674,10 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
             g->d_gctab = c.take<uint8_t>(gct.size());
             g->d_words = c.take<unsigned long long>(std::max<size_t>(n_ctg, 1));
         };
-        GAMS_HIP(h, gams_pool_alloc(h, false, layout_bytes(arena), reinterpret_cast<void **>(&g->arena), &g->arena_bytes));
-        carve(g->arena, arena);
+        GAMS_HIP(h, wave_arena(h, g->arena, arena));
         if (!st.empty()) GAMS_HIP(h, hipMemcpy(g->d_tiles, st.data(), st.size() * sizeof(SigTile), hipMemcpyHostToDevice));
-        gams_pool_free(h, true, g->h_words, g->h_words_bytes);
-        g->h_words = nullptr;
-        GAMS_HIP(h, gams_pool_alloc(h, true, ((size_t)2 * n_ctg + 2) * 8, reinterpret_cast<void **>(&g->h_words), &g->h_words_bytes));
+        g->h_words.free(h);
+        GAMS_HIP(h, g->h_words.reserve(h, ((size_t)2 * n_ctg + 2) * 8));
     }
     *text = nullptr;
     *text_bytes = 0;
@@ -1796,14 +1707,16 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
     a.blk_off = g->d_blk_off;
     a.words = g->d_words;
     hipLaunchKernelGGL(sig_len_kernel, dim3(g->n_tiles), dim3(256), 0, st, a);
-    unsigned long long *const d_totals = g->d_blk_off + g->n_tiles;
-    wave_queue_offsets(st, g->d_blk_len, g->n_tiles, g->d_blk_off, d_totals);
     GAMS_HIP(h, hipGetLastError());
+    unsigned long long *const d_totals = g->d_blk_off + g->n_tiles;
+    Chain ch{st};
+    ch.offsets(g->d_blk_len, g->n_tiles, g->d_blk_off, d_totals);
+    GAMS_HIP(h, ch.err);
     GAMS_HIP(h, hipMemcpyAsync(h->pin_scratch, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     GAMS_HIP(h, hipStreamSynchronize(st));       // (the staged tables above live on this call's stack until here)
     const uint64_t total = h->pin_scratch[0];
-    GAMS_HIP(h, gams_pool_grow(h, false, &g->d_text, &g->d_text_bytes, total, total + total / 16 + 4096));
-    GAMS_HIP(h, gams_pool_grow(h, true, &g->h_text, &g->h_text_bytes, total, total + total / 16 + 4096));
+    GAMS_HIP(h, g->d_text.grow(h, total, total + total / 16 + 4096));
+    GAMS_HIP(h, g->h_text.grow(h, total, total + total / 16 + 4096));
     a.text = g->d_text;
     a.text_cap = total;
     hipLaunchKernelGGL(sig_write_kernel, dim3(g->n_tiles), dim3(256), 0, st, a);
