@@ -123,6 +123,8 @@ PROTOTYPES = {
     "gams_gpu_read_range_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, C.c_uint64,
                                            C.POINTER(C.c_uint64)]),
     "gams_index_create_range_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _PP, _VP, C.POINTER(C.c_uint64)]),
+    "gams_gpu_peak_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64), _VP,
+                                     C.POINTER(C.c_uint64)]),
     "gams_gpu_valid_spans": (C.c_int, [_VP, _VP, C.c_uint64, C.c_int32, C.c_int32, _VP, _VP, C.c_uint64,
                                        C.POINTER(C.c_uint64)]),
 }

@@ -221,6 +221,13 @@ int gams_stage_ring(gams_gpu_t *h);   // allocate the pinned staging slots on fi
 int gams_order_after_readers(gams_gpu_t *h, hipStream_t st);
 int gams_seqset_gcindex(gams_gpu_t *h, gams_seqset_t *s);
 void gams_seqset_gcindex_free(gams_seqset_t *s);
+// sw.hip, for text.hip: gc[q] = round4(gc_content) of chromosome range [rs[q], re[q]] inside the ctg rctg[q] names,
+// one lane per range on `st`, over device columns: ctg c begins at byte seq_off[c] of the seqset's buffer, has len[c]
+// bases (0: no sequence, gc = 0) and starts at chr_start[c].  The seqset's gc index must exist (gams_seqset_gcindex).
+// A range that leaves its ctg is clamped into it (never read outside); the caller checks.
+void gams_launch_range_gc_cols(const gams_seqset_t *s, const unsigned long long *seq_off, const uint32_t *len,
+                               const int32_t *chr_start, const uint32_t *rctg, const uint32_t *rs, const uint32_t *re,
+                               uint32_t n, float *gc, hipStream_t st);
 
 // 16 bytes of sequence that this kernel will not read again: non-temporal load (global_load ... nt).
 // A pure streaming read runs at 7.06 TB/s with the hint, 6.3 TB/s without (profiles/r02_stream_read.txt).

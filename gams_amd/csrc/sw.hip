@@ -339,7 +339,32 @@ __global__ __launch_bounds__(256) void range_gc_kernel(const SwArgs a0, const in
     gc[q] = round4(range_gc(a, rs[q], re[q]));                          // utils.rs:157-161
 }
 
+// the same over device columns (gams_gpu_peak_text): range q lies in the ctg whose record is entry rctg[q] of the
+// three per-ctg columns; a ctg of length 0 has no sequence and gives 0
+__global__ __launch_bounds__(256) void range_gc_cols_kernel(const uint32_t *pm, const uint64_t *seg,
+                                                            const unsigned long long *seq_off, const uint32_t *len,
+                                                            const int32_t *chr_start, const uint32_t *rctg,
+                                                            const uint32_t *rs, const uint32_t *re, uint32_t n, float *gc) {
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const uint32_t c = rctg[q];
+    SwArgs a{};
+    a.pm = pm;
+    a.seg = seg;
+    a.seq_off = seq_off[c];
+    a.len = len[c];
+    a.chr_start = chr_start[c];
+    gc[q] = a.len ? round4(range_gc(a, (int32_t)rs[q], (int32_t)re[q])) : 0.0f;
+}
+
 }  // namespace
+
+void gams_launch_range_gc_cols(const gams_seqset_t *s, const unsigned long long *seq_off, const uint32_t *len,
+                               const int32_t *chr_start, const uint32_t *rctg, const uint32_t *rs, const uint32_t *re,
+                               uint32_t n, float *gc, hipStream_t st) {
+    hipLaunchKernelGGL(range_gc_cols_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, s->gcindex->d_pm, s->gcindex->d_seg,
+                       seq_off, len, chr_start, rctg, rs, re, n, gc);
+}
 
 // lazily built per seqset; owned by the seqset (freed in gams_seqset_destroy)
 int gams_seqset_gcindex(gams_gpu_t *h, gams_seqset_t *s) {
@@ -419,42 +444,6 @@ struct SwTextArgs {
     uint32_t gc;                       // print the four statistics (else four empty fields)
     const int32_t *cnt;                // per row rg_count (nullptr: the field stays empty)
 };
-
-// a round4 value as Rust prints it; returns the length (p == nullptr: length only); *bad set for values not covered
-__device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
-    if (v != v) {
-        if (p) { p[0] = 'N'; p[1] = 'a'; p[2] = 'N'; }
-        return 3u;
-    }
-    if (!(v >= 0.0f) || !(v < 1000.0f)) {
-        *bad = true;
-        return 1u;
-    }
-    if (v == 0.0f && (__float_as_uint(v) >> 31)) {        // round(x, 4) of a tiny negative: Rust prints "-0"
-        if (p) { p[0] = '-'; p[1] = '0'; }
-        return 2u;
-    }
-    const uint32_t m = (uint32_t)((double)v * 10000.0 + 0.5);     // v is the f32 nearest to m / 10^4: exact in double
-    const uint32_t ip = m / 10000u;
-    uint32_t fr = m % 10000u, nd = 4u;
-    while (nd && fr % 10u == 0u) {
-        fr /= 10u;
-        --nd;
-    }
-    const uint32_t n = dec_digits(ip) + (nd ? 1u + nd : 0u);
-    if (p) {
-        p = put_dec(p, ip);
-        if (nd) {
-            *p++ = '.';
-            char *e = p + nd;
-            for (uint32_t q = 0; q < nd; ++q) {
-                *--e = (char)('0' + fr % 10u);
-                fr /= 10u;
-            }
-        }
-    }
-    return n;
-}
 
 struct SwRowCtx {
     uint32_t k, f, serial;    // selected ctg, feature (index into the call's arrays), 1-based row of the feature

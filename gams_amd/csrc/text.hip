@@ -8,6 +8,8 @@
 // upload and line index (the stages are listed in front of its kernels, below):
 //   gams_gpu_read_range_text       the ranges of one .rg file bucketed per ctg, as arrays
 //   gams_index_create_range_text   the rg index of the file and the ctg -> group table
+// and, on the loader's stages, `gams peak` (utils.rs:83-116 read_peak, then peak.rs:41-160):
+//   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
 //
 // Pipeline (one handle, the compute stream):
 //   1. one copy of the bytes into a cached device buffer, padded with spaces to 16 B and 16 B beyond;
@@ -59,15 +61,15 @@ struct gams_names {
 struct gams_text_state {
     uint8_t *d_in = nullptr;
     size_t d_in_cap = 0;
-    char *out[3] = {};
-    size_t out_cap[3] = {};
+    char *out[4] = {};          // locate, count, anno, peak
+    size_t out_cap[4] = {};
 };
 
 void gams_text_free(gams_gpu_t *h) {
     gams_text_state *t = h->text;
     if (!t) return;
     gams_pool_free(h, false, t->d_in, t->d_in_cap);
-    for (int k = 0; k < 3; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
+    for (int k = 0; k < 4; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
     delete t;
     h->text = nullptr;
 }
@@ -103,11 +105,13 @@ __device__ inline uint32_t name_find(const NameTab &t, const char *s, uint64_t n
 enum : uint32_t {
     W_NL = 0,      // '\n' bytes of the input
     W_BAD = 1,     // a byte >= 0x80 or NUL
-    W_EFIELD = 2,  // anno: a line without field idx_id or idx_range
-    W_EID = 3,     // anno: a ctg id not in ctg_ids on a chromosome of the set
-    W_UNSUP = 4,   // count: a located ctg without an rg group; anno: a prop that is not finite in [0, 1]
+    W_EFIELD = 2,  // anno: a line without field idx_id or idx_range; peak: a valid range without a third field
+    W_EID = 3,     // anno: a ctg id not in ctg_ids on a chromosome of the set; peak: a kept peak that leaves its ctg
+    W_UNSUP = 4,   // count: a located ctg without an rg group; anno: a prop that is not finite in [0, 1]; peak: a float
+                   // the formatters do not cover
     W_BYTES = 5,   // text bytes
     W_ROWS = 6,    // rows
+    W_ENOSEQ = 7,  // peak: a kept peak in a ctg without a sequence
     W_COUNT = 8
 };
 
@@ -381,7 +385,7 @@ __global__ __launch_bounds__(256) void text_parse_anno_kernel(const TextLines t,
     keep[i] = 1;
 }
 
-enum : int { K_LOCATE = 0, K_COUNT = 1, K_ANNO = 2 };
+enum : int { K_LOCATE = 0, K_COUNT = 1, K_ANNO = 2, K_PEAK = 3 };   // K_PEAK: the slot of its text only (peak_run)
 
 struct RowArgs {
     TextLines t;
@@ -668,7 +672,8 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
 //   parse    the WHOLE line through Range::from_str (no cut at a tab) -> (chromosome group, start, end);
 //   locate   interval_locate_kernel on those columns -> the ctg of every line (its interval of ctg_ix), or -1;
 //   first    first[c] = the smallest line number located to ctg c: the line `.or_default()` swallows;
-//   keep     keep = located and not first[c]; count[c] = kept lines of c; the sort key (c, line) of every line;
+//   keep     keep = located and not first[c]; count[c] = kept lines of c; the sort key (c, line) of every line
+//            (the peak entry puts the range's start between the two: (c, start, line));
 //   offsets  exclusive scan of count -> bucket_off;
 //   order    ONE radix sort of the 64-bit keys (c << line bits | line); dropped lines carry c = n_ctg and sort
 //            behind every bucket.  The keys are unique, so the order is (ctg, line) whatever order lanes ran in;
@@ -704,7 +709,8 @@ __global__ __launch_bounds__(256) void rg_first_kernel(uint32_t n_lines, const i
 }
 
 __global__ __launch_bounds__(256) void rg_keep_kernel(uint32_t n_lines, uint32_t n_ctg, uint32_t line_bits, const int64_t *hit,
-                                                      const uint32_t *first, uint32_t *count, unsigned long long *key) {
+                                                      const uint32_t *first, uint32_t *count, unsigned long long *key,
+                                                      const uint32_t *qs, uint32_t start_bits) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t c = i < n_lines ? hit[i] : -1;
@@ -719,7 +725,10 @@ __global__ __launch_bounds__(256) void rg_keep_kernel(uint32_t n_lines, uint32_t
         const uint32_t n = (uint32_t)__popcll(kept & run);
         if (n) atomicAdd(count + c, n);
     }
-    if (i < n_lines) key[i] = ((unsigned long long)(keep ? (uint32_t)c : n_ctg) << line_bits) | i;
+    // (qs: the start of a kept line goes between ctg and line, start_bits wide; the rg loader passes none)
+    if (i < n_lines)
+        key[i] = ((unsigned long long)(keep ? (uint32_t)c : n_ctg) << (start_bits + line_bits)) |
+                 ((unsigned long long)(qs && keep ? qs[i] : 0u) << line_bits) | i;
 }
 
 struct RgGather {
@@ -841,7 +850,8 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
     GAMS_TRY(h, who, stage(RG_FIRST, false));
     GAMS_TRY(h, who, stage(RG_KEEP, true));
-    hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key);
+    hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
+                       (const uint32_t *)nullptr, 0u);
     GAMS_TRY(h, who, stage(RG_KEEP, false));
     GAMS_TRY(h, who, stage(RG_OFFSETS, true));
     hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, d_off, F.d_words,
@@ -877,6 +887,436 @@ void rg_timed(gams_gpu_t *h, int n) {
     h->k_valid = true;
 }
 
+
+// ---- `gams peak` on the device (utils.rs:83-116 read_peak, then peak.rs:41-160): the bytes of a wave TSV -> Peak rows --
+// Stages behind the line index (one lane per line up to the sort, one lane per kept peak behind it):
+//   parse    parts[0] (the line up to its first tab) through Range::from_str; a valid range needs parts[2], the signal;
+//            where the chromosome, the "name." prefix and the signal lie in the input;
+//   locate, first, keep, offsets   the range loader's (above), with the key (ctg, start, line): utils.rs:109-112 drops the
+//            first located line of a ctg, peak.rs:49 sorts the rest by start, stably;
+//   order    ONE radix sort of those 64-bit keys.  The line number makes the keys unique and breaks ties on start in
+//            file order, which is what the reference's stable sort leaves; a key wider than 64 bits is refused;
+//   gc       gather (line, ctg, start, end) through the sorted keys, check every kept peak against its ctg and the ctg
+//            for a sequence (flags), then round4(range_gc) of every kept peak (sw.hip);
+//   rows     the length of every row (it reads the neighbours' end / start / gc / signal inside the bucket), their block
+//            sums and the blocks' prefix;
+//   write    the rows at their offsets -- a block's 256 rows composed in LDS and copied out in 16-B units, or written
+//            straight to global memory when they exceed the stage -- and the offset of every ctg's first row.
+// Rows come out in key order: grouped by ctg in the caller's order, by start inside a ctg.
+struct PeakLines {
+    unsigned long long *cb, *sb;      // per line: where the chromosome and the signal field begin
+    uint32_t *clen, *slen, *nlen;     // their lengths; nlen: bytes of the "name." prefix at the line's start (0: none)
+};
+
+__global__ __launch_bounds__(256) void peak_parse_kernel(const TextLines t, const NameTab chr, uint32_t *grp, uint32_t *qs,
+                                                         uint32_t *qe, const PeakLines p, unsigned long long *words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= t.n_lines) return;
+    uint64_t b, e;
+    line_of(t, i, b, e);
+    const char *s = t.in;
+    uint64_t f = b;
+    while (f < e && s[f] != '\t') ++f;
+    const RangeField r = parse_range(s, b, f);                 // utils.rs:96-99: parts[0]
+    uint32_t g = UINT32_MAX;
+    uint64_t sb = 0, se = 0;
+    if (r.ok) {
+        bool third = false;
+        if (f < e) {
+            uint64_t f2 = f + 1u;
+            while (f2 < e && s[f2] != '\t') ++f2;
+            if (f2 < e) {
+                sb = se = f2 + 1u;
+                while (se < e && s[se] != '\t') ++se;
+                third = true;
+            }
+        }
+        if (third)
+            g = name_find(chr, s + r.cb, r.ce - r.cb);
+        else
+            words[W_EFIELD] = 1ull;                            // the reference panics (utils.rs:102)
+    }
+    grp[i] = g;
+    qs[i] = r.start;
+    qe[i] = r.end;
+    p.cb[i] = r.cb;
+    p.clen[i] = (uint32_t)(r.ce - r.cb);
+    p.nlen[i] = r.ok && r.cb - b >= 2u ? (uint32_t)(r.cb - b) : 0u;   // an empty name prints no prefix (Range::to_string)
+    p.sb[i] = sb;
+    p.slen[i] = (uint32_t)(se - sb);
+}
+
+struct PeakArgs {
+    TextLines t;
+    PeakLines p;
+    const unsigned long long *key;            // sorted: the first n_kept are the kept lines in (ctg, start, line) order
+    uint32_t line_bits;
+    uint32_t n_kept;
+    const uint32_t *qs, *qe;                  // per line
+    const unsigned long long *bucket_off;     // n_ctg + 1
+    const int32_t *cs, *ce;                   // per ctg
+    const uint32_t *seq_len;                  // per ctg: 0 = no sequence in the seqset
+    NameTab ids;
+    uint32_t *kline, *kctg, *ks, *ke;         // per kept peak
+    float *gc;
+    uint32_t *row_len;
+    unsigned long long *blk_bytes;            // per workgroup of 256 rows
+    const unsigned long long *blk_off;
+    unsigned long long *text_off;             // per ctg with rows: the offset of its first row
+    unsigned long long *words;
+    char *text;
+};
+
+__global__ __launch_bounds__(256) void peak_gather_kernel(const PeakArgs a) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= a.n_kept) return;
+    const unsigned long long key = a.key[k];
+    const uint32_t i = (uint32_t)(key & ((1ull << a.line_bits) - 1ull));
+    const uint32_t c = (uint32_t)(key >> (31u + a.line_bits));
+    const uint32_t s = a.qs[i], e = a.qe[i];
+    a.kline[k] = i;
+    a.kctg[k] = c;
+    a.ks[k] = s;
+    a.ke[k] = e;
+    // peak_check_inside: the reference slices the ctg's sequence with the range (utils.rs:155)
+    if ((int32_t)s < a.cs[c] || (int32_t)e > a.ce[c] || e < s) a.words[W_EID] = 1ull;
+    if (a.seq_len[c] == 0u) a.words[W_ENOSEQ] = 1ull;
+}
+
+// a row's bytes: written at q, or only counted (q == nullptr)
+struct RowOut {
+    char *q;
+    uint32_t n;
+    __device__ __forceinline__ void bytes(const char *src, uint32_t len) {
+        if (q) q = put_bytes(q, src, len);
+        n += len;
+    }
+    __device__ __forceinline__ void ch(char c) {
+        if (q) *q++ = c;
+        ++n;
+    }
+    __device__ __forceinline__ void dec(uint32_t v) {
+        if (q) q = put_dec(q, v);
+        n += dec_digits(v);
+    }
+    __device__ __forceinline__ void i32(int32_t v) {
+        if (q) q = put_i32(q, v);
+        n += i32_len(v);
+    }
+    __device__ __forceinline__ void f4(float v, bool &bad) {           // a round4 value
+        const uint32_t l = sw_put_f4(q, v, &bad);
+        if (q) q += l;
+        n += l;
+    }
+    __device__ __forceinline__ void f32s(float v, bool &bad) {         // `{}` of an amplitude
+        uint32_t l = gams_fmt_f32_short(v, q);
+        if (l == 0u) {
+            bad = true;
+            l = 1u;
+        }
+        if (q) q += l;
+        n += l;
+    }
+};
+
+// peak.rs:65-158 for kept peak k, as gams_host_peak prints it; returns the row's length
+__device__ uint32_t peak_row(const PeakArgs &a, uint32_t k, char *q, bool &bad) {
+    const uint32_t c = a.kctg[k];
+    const uint32_t o0 = (uint32_t)a.bucket_off[c], o1 = (uint32_t)a.bucket_off[c + 1u];
+    const bool has_prev = k > o0, has_next = k + 1u < o1;
+    const uint32_t i = a.kline[k], ip = has_prev ? a.kline[k - 1u] : i, in = has_next ? a.kline[k + 1u] : i;
+    const uint32_t s = a.ks[k], e = a.ke[k];
+    const float g = a.gc[k], gp = has_prev ? a.gc[k - 1u] : g, gn = has_next ? a.gc[k + 1u] : g;
+    const uint32_t prev_end = has_prev ? a.ke[k - 1u] : (uint32_t)a.cs[c];           // peak.rs:112-133
+    const uint32_t next_start = has_next ? a.ks[k + 1u] : (uint32_t)a.ce[c];         // peak.rs:135-157
+    const char *in_ = a.t.in;
+    RowOut o{q, 0u};
+    o.bytes("peak:", 5u);
+    const unsigned long long io = a.ids.off[c];
+    o.bytes(a.ids.bytes + io, (uint32_t)(a.ids.off[c + 1u] - io));
+    o.ch(':');
+    o.dec(k - o0 + 1u);
+    o.ch('\t');
+    o.bytes(in_ + a.t.starts[i], a.p.nlen[i]);                 // Range::to_string() with the strand cleared
+    o.bytes(in_ + a.p.cb[i], a.p.clen[i]);
+    o.ch(':');
+    o.dec(s);
+    if (e != s) {
+        o.ch('-');
+        o.dec(e);
+    }
+    o.ch('\t');
+    o.i32((int32_t)(e - s + 1u));
+    o.ch('\t');
+    o.f4(g, bad);
+    o.ch('\t');
+    o.bytes(in_ + a.p.sb[i], a.p.slen[i]);
+    o.ch('\t');
+    o.i32((int32_t)(s - prev_end + 1u));
+    o.ch('\t');
+    o.f32s(fabsf(g - gp), bad);
+    o.ch('\t');
+    o.bytes(in_ + a.p.sb[ip], a.p.slen[ip]);
+    o.ch('\t');
+    o.i32((int32_t)(next_start - e + 1u));
+    o.ch('\t');
+    o.f32s(fabsf(g - gn), bad);
+    o.ch('\t');
+    o.bytes(in_ + a.p.sb[in], a.p.slen[in]);
+    o.ch('\n');
+    return o.n;
+}
+
+__global__ __launch_bounds__(256) void peak_row_len_kernel(const PeakArgs a) {
+    __shared__ uint64_t ws[4];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    const uint32_t l = k < a.n_kept ? peak_row(a, k, nullptr, bad) : 0u;
+    if (k < a.n_kept) a.row_len[k] = l;
+    if (bad) a.words[W_UNSUP] = 1ull;
+    uint64_t tot;
+    (void)block_excl_scan_256<uint64_t>((uint64_t)l, ws, tot);
+    if (threadIdx.x == 0) a.blk_bytes[blockIdx.x] = tot;
+}
+
+// bytes of a block's rows staged in LDS: 256 rows of ~90 B are 23 KB; a block beyond the stage (long names, ids or
+// signals) writes its rows to global memory directly
+constexpr uint32_t kPeakStage = 32768;
+
+__global__ __launch_bounds__(256) void peak_row_write_kernel(const PeakArgs a) {
+    __shared__ uint64_t ws[4];
+    __shared__ __align__(16) char stage[kPeakStage + 16];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t l = k < a.n_kept ? a.row_len[k] : 0ull;
+    uint64_t tot;
+    const uint64_t rel = block_excl_scan_256<uint64_t>(l, ws, tot);
+    const unsigned long long blk0 = a.blk_off[blockIdx.x];     // the block's first byte in the text
+    const uint32_t mis = (uint32_t)(blk0 & 15u);               // the stage starts at the same offset inside a 16-B unit
+    const bool staged = tot <= kPeakStage;                     // (the same for every lane of the block)
+    if (k < a.n_kept) {
+        const uint32_t c = a.kctg[k];
+        if (k == (uint32_t)a.bucket_off[c]) a.text_off[c] = blk0 + rel;
+        bool bad = false;                      // (the length pass flagged what has no text: nothing is written then)
+        (void)peak_row(a, k, staged ? stage + mis + (uint32_t)rel : a.text + blk0 + rel, bad);
+    }
+    if (!staged) return;
+    __syncthreads();
+    stage_flush_256(stage, mis, (uint32_t)tot, a.text + blk0);
+}
+
+enum : int { PK_LINES = 0, PK_PARSE, PK_LOCATE, PK_FIRST, PK_KEEP, PK_OFFSETS, PK_ORDER, PK_GC, PK_ROWS, PK_WRITE, PK_STAGES };
+
+struct PeakJob {
+    gams_seqset_t *s;
+    const gams_index_t *ctg_ix;
+    const gams_names_t *chr, *ids;
+    const uint32_t *ctg_index;
+    const int32_t *chr_start, *chr_end;
+};
+
+int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_bytes, const char **text, uint64_t *text_bytes,
+             uint64_t *text_off, uint64_t *n_rows) {
+    const std::string who = "gpu_peak_text";
+    const uint64_t n_ctg = J.ctg_ix->m;
+    *text = "";
+    *text_bytes = 0;
+    *n_rows = 0;
+    memset(text_off, 0, (n_ctg + 1) * 8);
+    for (uint64_t c = 0; c < n_ctg; ++c) {
+        if (J.chr_end[c] < J.chr_start[c]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg ends before it starts");
+        const uint32_t slot = J.ctg_index[c];
+        if (slot == UINT32_MAX) continue;
+        if (slot >= J.s->n_ctg || (int64_t)J.s->len[slot] != (int64_t)J.chr_end[c] - J.chr_start[c] + 1)
+            return gams_fail(h, GAMS_EINVAL, who + ": ctg_index does not name a sequence of the ctg's length");
+    }
+    GAMS_HIP(h, hipSetDevice(h->device));
+    const int rc_gc = gams_seqset_gcindex(h, J.s);             // GAMS_ESTATE for a plane-only seqset
+    if (rc_gc != GAMS_OK) return rc_gc;
+    while (h->kq.size() < (size_t)PK_STAGES) {
+        hipEvent_t a = nullptr, b = nullptr;
+        GAMS_HIP(h, hipEventCreate(&a));
+        GAMS_HIP(h, hipEventCreate(&b));
+        h->kq.emplace_back(a, b);
+    }
+    hipStream_t st = h->compute;
+    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
+    PoolBlock s1(h, false), s2(h, false), d_tab(h, false), pin(h, true), d_text(h, false);
+    TextFront F(h);
+    GAMS_TRY(h, who, stage(PK_LINES, true));
+    const int rc_front = text_front(h, who, bytes, n_bytes, F);
+    if (rc_front != GAMS_OK) return rc_front;
+    const uint32_t L = F.L;
+    if (L == 0) return GAMS_OK;
+    uint32_t line_bits = 1, ctg_bits = 1;
+    while (line_bits < 32u && (L - 1u) >> line_bits) ++line_bits;
+    while (ctg_bits < 32u && n_ctg >> ctg_bits) ++ctg_bits;
+    const uint32_t key_bits = ctg_bits + 31u + line_bits;
+    if (key_bits > 64u)
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": (ctg, start, line) does not fit a 64-bit sort key (use the host path)");
+    const uint32_t nbr = (L + 255u) / 256u;
+    size_t sort_bytes = 0;
+    GAMS_TRY(h, who, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                              (size_t)L, 0u, key_bits, st));
+    // the per-ctg tables: one page-locked image, one copy (the offsets and the text offsets come back into it)
+    const size_t n_tab = std::max<uint64_t>(n_ctg, 1);
+    struct Tabs {
+        unsigned long long *seq_off, *off, *toff;
+        int32_t *cs, *ce;
+        uint32_t *seq_len;
+    };
+    auto tabs = [&](Carver &c) {
+        Tabs t{};
+        t.seq_off = c.take<unsigned long long>(n_tab);
+        t.cs = c.take<int32_t>(n_tab);
+        t.ce = c.take<int32_t>(n_tab);
+        t.seq_len = c.take<uint32_t>(n_tab);
+        t.off = c.take<unsigned long long>(n_ctg + 1);
+        t.toff = c.take<unsigned long long>(n_ctg + 1);
+        return t;
+    };
+    const size_t b_tabs = layout_bytes(tabs);
+    GAMS_TRY(h, who, pin.alloc(b_tabs));
+    GAMS_TRY(h, who, d_tab.alloc(b_tabs));
+    const Tabs ht = carve(pin.p, tabs), dt = carve(d_tab.p, tabs);
+    for (uint64_t c = 0; c < n_ctg; ++c) {
+        const uint32_t slot = J.ctg_index[c];
+        ht.seq_off[c] = slot == UINT32_MAX ? 0ull : J.s->off[slot];
+        ht.seq_len[c] = slot == UINT32_MAX ? 0u : J.s->len[slot];
+        ht.cs[c] = J.chr_start[c];
+        ht.ce[c] = J.chr_end[c];
+    }
+    const size_t b_in = reinterpret_cast<uint8_t *>(ht.off) - pin.p;     // the four input columns
+    GAMS_TRY(h, who, hipMemcpyAsync(d_tab.p, pin.p, b_in, hipMemcpyHostToDevice, st));
+    unsigned long long *d_starts = nullptr, *d_key = nullptr, *d_key2 = nullptr;
+    uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr, *d_first = nullptr, *d_count = nullptr;
+    int64_t *d_hit = nullptr;
+    uint8_t *d_sort = nullptr;
+    PeakLines pl{};
+    auto cols = [&](Carver &c) {   // starts | grp qs qe | hit key key' | the fields | first count | sort storage
+        d_starts = c.take<unsigned long long>((size_t)F.nl + 2);
+        d_grp = c.take<uint32_t>(L);
+        d_qs = c.take<uint32_t>(L);
+        d_qe = c.take<uint32_t>(L);
+        d_hit = c.take<int64_t>(L);
+        d_key = c.take<unsigned long long>(L);
+        d_key2 = c.take<unsigned long long>(L);
+        pl.cb = c.take<unsigned long long>(L);
+        pl.sb = c.take<unsigned long long>(L);
+        pl.clen = c.take<uint32_t>(L);
+        pl.slen = c.take<uint32_t>(L);
+        pl.nlen = c.take<uint32_t>(L);
+        d_first = c.take<uint32_t>(n_tab);
+        d_count = c.take<uint32_t>(n_tab);
+        d_sort = c.take<uint8_t>(std::max<size_t>(sort_bytes, 1));
+    };
+    GAMS_TRY(h, who, s1.alloc(layout_bytes(cols)));
+    carve(s1.p, cols);
+    const size_t b_tab = gams_align256(n_tab * 4);
+    hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, h->text->d_in, n_bytes, F.n16, F.d_bnloff, F.nl,
+                       d_starts);
+    GAMS_TRY(h, who, hipMemsetAsync(d_first, 0xff, b_tab, st));
+    GAMS_TRY(h, who, hipMemsetAsync(d_count, 0, b_tab, st));
+    GAMS_TRY(h, who, stage(PK_LINES, false));
+    const TextLines tl{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
+    GAMS_TRY(h, who, stage(PK_PARSE, true));
+    hipLaunchKernelGGL(peak_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, J.chr->t, d_grp, d_qs, d_qe, pl, F.d_words);
+    GAMS_TRY(h, who, stage(PK_PARSE, false));
+    GAMS_TRY(h, who, stage(PK_LOCATE, true));
+    launch_interval_locate(J.ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
+    GAMS_TRY(h, who, stage(PK_LOCATE, false));
+    GAMS_TRY(h, who, stage(PK_FIRST, true));
+    hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
+    GAMS_TRY(h, who, stage(PK_FIRST, false));
+    GAMS_TRY(h, who, stage(PK_KEEP, true));
+    hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
+                       (const uint32_t *)d_qs, 31u);
+    GAMS_TRY(h, who, stage(PK_KEEP, false));
+    GAMS_TRY(h, who, stage(PK_OFFSETS, true));
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, dt.off, F.d_words,
+                       (uint32_t)W_ROWS);
+    GAMS_TRY(h, who, stage(PK_OFFSETS, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(ht.off, dt.off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    if (h->pin_scratch[W_EFIELD])
+        return gams_fail(h, GAMS_EINVAL, who + ": a row has no signal column (the reference panics, utils.rs:102)");
+    const uint64_t n_kept = ht.off[n_ctg];
+    if (n_kept == 0) return GAMS_OK;
+    const uint32_t K = (uint32_t)n_kept, nbk = (K + 255u) / 256u;        // n_kept <= L < 2^32
+    GAMS_TRY(h, who, stage(PK_ORDER, true));
+    GAMS_TRY(h, who, rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, key_bits, st));
+    GAMS_TRY(h, who, stage(PK_ORDER, false));
+    PeakArgs a{};
+    a.t = tl;
+    a.p = pl;
+    a.key = d_key2;
+    a.line_bits = line_bits;
+    a.n_kept = K;
+    a.qs = d_qs;
+    a.qe = d_qe;
+    a.bucket_off = dt.off;
+    a.cs = dt.cs;
+    a.ce = dt.ce;
+    a.seq_len = dt.seq_len;
+    a.ids = J.ids->t;
+    a.text_off = dt.toff;
+    a.words = F.d_words;
+    auto kept = [&](Carver &c) {   // line ctg start end | gc | row lengths | the blocks' bytes and prefix
+        a.kline = c.take<uint32_t>(K);
+        a.kctg = c.take<uint32_t>(K);
+        a.ks = c.take<uint32_t>(K);
+        a.ke = c.take<uint32_t>(K);
+        a.gc = c.take<float>(K);
+        a.row_len = c.take<uint32_t>(K);
+        a.blk_bytes = c.take<unsigned long long>((size_t)nbk + 1);
+        unsigned long long *const off = c.take<unsigned long long>((size_t)nbk + 1);
+        a.blk_off = off;
+        return off;
+    };
+    GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
+    unsigned long long *const d_blk_off = carve(s2.p, kept);
+    GAMS_TRY(h, who, stage(PK_GC, true));
+    hipLaunchKernelGGL(peak_gather_kernel, dim3(nbk), dim3(256), 0, st, a);
+    gams_launch_range_gc_cols(J.s, dt.seq_off, dt.seq_len, dt.cs, a.kctg, a.ks, a.ke, K, a.gc, st);
+    GAMS_TRY(h, who, stage(PK_GC, false));
+    GAMS_TRY(h, who, stage(PK_ROWS, true));
+    hipLaunchKernelGGL(peak_row_len_kernel, dim3(nbk), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbk, d_blk_off,
+                       F.d_words, (uint32_t)W_BYTES);
+    GAMS_TRY(h, who, stage(PK_ROWS, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    const unsigned long long *w = h->pin_scratch;
+    if (w[W_EID])
+        return gams_fail(h, GAMS_EINVAL, who + ": a peak is not inside its ctg (the reference panics on the slice, utils.rs:155)");
+    if (w[W_ENOSEQ]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with peaks has no sequence in the seqset");
+    if (w[W_UNSUP])
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a gc or an amplitude the device formatters do not cover (use the host path)");
+    const uint64_t tb = w[W_BYTES];
+    gams_text_state *T = h->text;
+    char *&out = T->out[K_PEAK];
+    size_t &out_cap = T->out_cap[K_PEAK];
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &out, &out_cap, tb, tb));
+    GAMS_TRY(h, who, d_text.alloc(tb));
+    a.text = reinterpret_cast<char *>(d_text.p);
+    GAMS_TRY(h, who, stage(PK_WRITE, true));
+    hipLaunchKernelGGL(peak_row_write_kernel, dim3(nbk), dim3(256), 0, st, a);
+    GAMS_TRY(h, who, stage(PK_WRITE, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(out, d_text.p, tb, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipMemcpyAsync(ht.toff, dt.toff, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    // a ctg without rows begins where the next one does
+    text_off[n_ctg] = tb;
+    for (uint64_t c = n_ctg; c-- > 0;) text_off[c] = ht.off[c + 1] > ht.off[c] ? ht.toff[c] : text_off[c + 1];
+    rg_timed(h, PK_STAGES);
+    *text = out;
+    *text_bytes = tb;
+    *n_rows = n_kept;
+    return GAMS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1071,6 +1511,18 @@ int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams
         if (C.ran) rg_timed(h, RG_STAGES);
         return GAMS_OK;
     });
+}
+
+int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                       const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start, const int32_t *chr_end,
+                       const char *bytes, uint64_t n_bytes, const char **text, uint64_t *text_bytes, uint64_t *text_off,
+                       uint64_t *n_rows) {
+    if (!h || !s || !ctg_ix || !chr_names || !ctg_ids || (ctg_ix->m && (!ctg_index || !chr_start || !chr_end)) ||
+        (n_bytes && !bytes) || !text || !text_bytes || !text_off || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_peak_text: null argument");
+    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_peak_text: ctg_ids must name every interval of ctg_ix");
+    return peak_run(h, PeakJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end}, bytes, n_bytes, text, text_bytes,
+                    text_off, n_rows);
 }
 
 }  // extern "C"

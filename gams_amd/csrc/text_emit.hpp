@@ -1,8 +1,9 @@
 // text_emit.hpp -- what the device paths that write finished TSV text share (device only): the wave rows and
-// `--signal` rows (wave_rows.hpp), the `sw` rows (sw.hip), the `locate` / `locate --count` / `anno` rows (text.hip).
+// `--signal` rows (wave_rows.hpp), the `sw` rows (sw.hip), the `locate` / `locate --count` / `anno` / `peak` rows (text.hip).
 // Decimal output, the workgroup sum behind a block's byte count, the one-workgroup prefix over those counts, and
-// the copy of a block's text from its LDS stage to the global text.  The row composers and the three float
-// formats (gctab lookup, sw_put_f4, gams_fmt_prop4) stay with their owners.
+// the copy of a block's text from its LDS stage to the global text, and the round4 float format of the `sw` and
+// `peak` rows (sw_put_f4).  The row composers and the other float formats (gctab lookup; gams_fmt_prop4 and
+// gams_fmt_f32_short, text_fmt.hpp) stay with their owners.
 #pragma once
 
 #include "common.hpp"
@@ -37,6 +38,43 @@ __device__ __forceinline__ char *put_i32(char *p, int32_t v) {
 __device__ __forceinline__ char *put_bytes(char *q, const char *src, uint64_t n) {
     for (uint64_t k = 0; k < n; ++k) q[k] = src[k];
     return q + n;
+}
+
+// a round4 value (the f32 nearest to m / 10^4) as Rust prints it; returns the length (p == nullptr: length only);
+// *bad set for values not covered
+__device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
+    if (v != v) {
+        if (p) { p[0] = 'N'; p[1] = 'a'; p[2] = 'N'; }
+        return 3u;
+    }
+    if (!(v >= 0.0f) || !(v < 1000.0f)) {
+        *bad = true;
+        return 1u;
+    }
+    if (v == 0.0f && (__float_as_uint(v) >> 31)) {        // round(x, 4) of a tiny negative: Rust prints "-0"
+        if (p) { p[0] = '-'; p[1] = '0'; }
+        return 2u;
+    }
+    const uint32_t m = (uint32_t)((double)v * 10000.0 + 0.5);     // v is the f32 nearest to m / 10^4: exact in double
+    const uint32_t ip = m / 10000u;
+    uint32_t fr = m % 10000u, nd = 4u;
+    while (nd && fr % 10u == 0u) {
+        fr /= 10u;
+        --nd;
+    }
+    const uint32_t n = dec_digits(ip) + (nd ? 1u + nd : 0u);
+    if (p) {
+        p = put_dec(p, ip);
+        if (nd) {
+            *p++ = '.';
+            char *e = p + nd;
+            for (uint32_t q = 0; q < nd; ++q) {
+                *--e = (char)('0' + fr % 10u);
+                fr /= 10u;
+            }
+        }
+    }
+    return n;
 }
 
 // Sum of v over a 256-thread workgroup (4 waves); `ws` is LDS scratch of 4 elements, the call holds one barrier.

@@ -1,5 +1,6 @@
-// text_fmt.hpp -- `{:.4}` of an anno proportion in integer arithmetic, shared by the device formatter
-// (text.hip) and the host layer (gams_host_c.cpp exposes it to the tests).  Plain C++: no HIP header needed.
+// text_fmt.hpp -- the two float formats of the text entries in integer arithmetic, shared by the device formatters
+// (text.hip) and the host layer (gams_host_c.cpp exposes them to the tests): `{:.4}` of an anno proportion and the
+// shortest round-trip `{}` of a peak amplitude.  Plain C++: no HIP header needed.
 #pragma once
 
 #include <stdint.h>
@@ -38,4 +39,61 @@ GAMS_HD inline bool gams_fmt_prop4(float p, char *out) {
     out[4] = (char)('0' + q / 10u % 10u);
     out[5] = (char)('0' + q % 10u);
     return true;
+}
+
+// peak.rs prints the f32 amplitudes |gc - gc'| with `{}`: the shortest decimal that parses back to the same f32, the
+// closest to v where several are equally short, in positional notation ("0", "0.0268", "0.026800007", "1") -- what
+// gams::fmt_f32 makes of std::to_chars.  For a finite v in [0, 1] the text goes to out[0..len) and len is returned;
+// out == nullptr: the length only.  Returns 0 (nothing written) for NaN, -0, anything outside [0, 1] and a nonzero v
+// below 2^-64, which the 128-bit arithmetic below does not cover: the caller flags such a value.  len <= 31.
+//
+// v = m * 2^-s with m < 2^24 (23 <= s <= 87).  With q decimals the two candidates are D = floor(v * 10^q) and D + 1;
+// in units of 2^-s * 10^-q they lie rl = m * 10^q - D * 2^s below and rh = 2^s - rl above v, and one of them parses
+// back to v when it is within half the gap to v's neighbour on that side: 2 * r <= 10^q (the bound itself only for an
+// even m: ties parse to even).  Below a power of two the gap is half as wide (4 * rl <= 10^q), so there the closer
+// candidate may fail where the other one passes: both are tried, the closer of those that pass is taken.  The first q
+// with a passing candidate gives the shortest text; nine significant digits always pass, so q <= 28 and every product
+// stays below 2^124.  No division wider than 64 bits (there is no 128-bit divide on the device).
+GAMS_HD inline uint32_t gams_fmt_f32_short(float v, char *out) {
+    __extension__ typedef unsigned __int128 u128;
+    if (!(v >= 0.0f && v <= 1.0f)) return 0;        // NaN fails both
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    if (b == 0u) {
+        if (out) out[0] = '0';
+        return 1;
+    }
+    const uint32_t ex = b >> 23;
+    if ((b >> 31) || ex < 63u) return 0;            // -0; below 2^-64
+    const uint64_t m = (uint64_t)((b & 0x7fffffu) | 0x800000u);
+    const uint32_t s = 150u - ex;                   // v = m / 2^s
+    const bool even = !(m & 1u), pow2 = (b & 0x7fffffu) == 0u;
+    const u128 one = (u128)1 << s;
+    u128 p10 = 1;
+    for (uint32_t q = 0; q <= 28u; ++q, p10 *= 10u) {
+        const u128 num = (u128)m * p10;
+        const u128 d = num >> s;
+        const u128 rl = num - (d << s), rh = one - rl;
+        const u128 wl = pow2 ? 4u * rl : 2u * rl, wh = 2u * rh;
+        const bool okl = d != 0u && (even ? wl <= p10 : wl < p10);
+        const bool okh = even ? wh <= p10 : wh < p10;
+        if (!okl && !okh) continue;
+        if ((d >> 40) != 0u) return 0;              // (more than nine digits: cannot happen)
+        uint64_t r = (uint64_t)d;
+        if (!okl || (okh && (rh < rl || (rh == rl && (r & 1u))))) ++r;
+        if (q == 0u) {                              // r == 1: v is 1
+            if (out) out[0] = '1';
+            return 1;
+        }
+        if (out) {                                  // "0." and r as q decimals
+            out[0] = '0';
+            out[1] = '.';
+            for (uint32_t k = q; k > 0u; --k) {
+                out[1u + k] = (char)('0' + r % 10u);
+                r /= 10u;
+            }
+        }
+        return 2u + q;
+    }
+    return 0;
 }

@@ -147,6 +147,11 @@ def load():
     L.gams_host_last_operator_device.argtypes = []
     L.gams_host_fmt_prop4.restype = C.c_void_p
     L.gams_host_fmt_prop4.argtypes = [C.c_float]
+    L.gams_host_fmt_f32_short.restype = C.c_void_p
+    L.gams_host_fmt_f32_short.argtypes = [C.c_float]
+    L.gams_host_peak_text.restype = C.c_void_p
+    L.gams_host_peak_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                      C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.gams_host_gen.restype = C.c_void_p
     L.gams_host_gen.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
     L.gams_host_fmt_f32.restype = C.c_void_p
@@ -373,7 +378,7 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 
 def last_operator_device():
-    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text of this thread made its rows on the device,
+    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text / peak_text of this thread made its rows on the device,
     0 if it fell back to the host"""
     return int(load().gams_host_last_operator_device())
 
@@ -596,6 +601,32 @@ def peak(eng, ctgs, lines):
     seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
     return _take(load().gams_host_peak(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs,
                                        "\n".join(lines).encode()))
+
+
+def peak_text(eng, ctgs, data, seqset=None):
+    """`gams peak` over the bytes of a wave TSV, made on the device from the bytes to the rows (the host's passes where
+    the device refuses): the rows of peak() with every ctg's peaks sorted by start, as bytes.  Without `seqset` the
+    ctgs carry their bases in c["seq"], uploaded for the call; with a resident engine.SeqSet its slot i holds
+    ctgs[i] (a ctg dict may name another in c["slot"]; None: no sequence)."""
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    out_len = C.c_uint64()
+    if seqset is None:
+        bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
+                                     else c["seq"]) for c in ctgs]
+        seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        p = load().gams_host_peak_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, bytes(data),
+                                       len(data), C.byref(out_len))
+    else:
+        slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
+        slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
+        p = load().gams_host_peak_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
+                                       slots.ctypes.data, bytes(data), len(data), C.byref(out_len))
+    return _take_bytes(p, out_len)
+
+
+def fmt_f32_short(v):
+    """`{}` of an f32 in [0, 1] as the device formats a peak amplitude ("" where it refuses: NaN, outside [0, 1])"""
+    return _take(load().gams_host_fmt_f32_short(v))
 
 
 def fmt_f32(v):

@@ -1809,6 +1809,87 @@ std::vector<std::vector<Peak>> peak_records_batch(gams_gpu_t *h, const std::vect
     return out;
 }
 
+std::string peak_rows(const std::vector<Peak> &recs) {
+    std::string out;
+    for (const Peak &p : recs)
+        out += p.id + "\t" + p.range + "\t" + std::to_string(p.length) + "\t" + fmt_f32(p.gc) + "\t" + p.signal + "\t" +
+               std::to_string(p.left_wave_length) + "\t" + fmt_f32(p.left_amplitude) + "\t" + p.left_signal + "\t" +
+               std::to_string(p.right_wave_length) + "\t" + fmt_f32(p.right_amplitude) + "\t" + p.right_signal + "\n";
+    return out;
+}
+
+std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                      const char *bytes, size_t n, bool *device) {
+    if (device) *device = false;
+    if (!seqset || slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "peak_text: one seqset slot per ctg");
+    Locator loc(h, ctgs);
+    loc.text_tables();
+    const size_t n_ctg = loc.ctgs_.size();
+    // per interval of the ctg index (the Locator's order): seqset slot, chr_start, chr_end
+    std::vector<uint32_t> slot(std::max<size_t>(n_ctg, 1), UINT32_MAX);
+    std::vector<int32_t> cs(std::max<size_t>(n_ctg, 1), 0), ce(std::max<size_t>(n_ctg, 1), 0);
+    for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
+    for (size_t c = 0; c < n_ctg; ++c) {
+        cs[c] = loc.ctgs_[c].chr_start;
+        ce[c] = loc.ctgs_[c].chr_end;
+    }
+    std::vector<uint64_t> off(n_ctg + 1, 0);
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, rows = 0;
+    const int rc = gams_gpu_peak_text(h, seqset, loc.ctg_ix_, loc.chr_names_, loc.ctg_ids_, slot.data(), cs.data(), ce.data(),
+                                      bytes, n, &text, &text_bytes, off.data(), &rows);
+    std::string out;
+    if (rc != GAMS_EUNSUPPORTED) {
+        check(h, rc);
+        if (device) *device = true;
+        out.reserve((size_t)text_bytes);
+        for (auto &kv : loc.ctg_slot_)                                   // ctg-id order
+            out.append(text + off[kv.second], (size_t)(off[kv.second + 1] - off[kv.second]));
+        return out;
+    }
+    // the host's passes: read_peak, every bucket sorted by start (peak.rs:49), the gc of all ranges in one call
+    auto peaks_of = read_peak(loc, text_lines(bytes, n));
+    std::vector<uint32_t> sel, index;
+    std::vector<int32_t> sel_start, rs, re;
+    std::vector<uint64_t> roff{0};
+    for (auto &kv : peaks_of) {
+        auto &pv = kv.second;
+        if (pv.empty()) continue;
+        std::stable_sort(pv.begin(), pv.end(), [](const auto &a, const auto &b) { return a.first.start < b.first.start; });
+        const uint32_t c = loc.ctg_slot_.at(kv.first);
+        peak_check_inside(loc.ctgs_[c], pv);
+        if (slot[c] == UINT32_MAX) throw Error(GAMS_EINVAL, "peak_text: no sequence for " + kv.first);
+        sel.push_back(c);
+        index.push_back(slot[c]);
+        sel_start.push_back(cs[c]);
+        for (const auto &pk : pv) {
+            rs.push_back(pk.first.start);
+            re.push_back(pk.first.end);
+        }
+        roff.push_back(rs.size());
+    }
+    std::vector<float> gc(std::max<size_t>(rs.size(), 1));
+    check(h, gams_gpu_range_gc_batch(h, seqset, (uint32_t)sel.size(), index.data(), sel_start.data(), roff.data(), rs.data(),
+                                     re.data(), gc.data()));
+    for (size_t k = 0; k < sel.size(); ++k)                              // (peaks_of, hence sel, is in ctg-id order)
+        out += peak_rows(peak_fill(loc.ctgs_[sel[k]], peaks_of[loc.ctgs_[sel[k]].id], gc.data() + roff[k]));
+    return out;
+}
+
+std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
+                      size_t n, bool *device) {
+    if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, "peak_text: ctgs / seqs size mismatch");
+    std::vector<uint32_t> lens(std::max<size_t>(ctgs.size(), 1), 0), slots(ctgs.size());
+    for (size_t i = 0; i < ctgs.size(); ++i) {
+        lens[i] = (uint32_t)(ctgs[i].chr_end - ctgs[i].chr_start + 1);
+        slots[i] = (uint32_t)i;
+    }
+    SeqSetGuard sg{h};
+    check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
+    check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
+    return peak_text(h, ctgs, sg.s, slots, bytes, n, device);
+}
+
 namespace {
 std::string json_escape(const std::string &v) {
     std::string o;
@@ -2295,6 +2376,11 @@ std::vector<std::string> text_lines(const char *bytes, size_t n) {
         b = next;
     }
     return lines;
+}
+
+std::string fmt_f32_short(float v) {
+    char buf[40];
+    return std::string(buf, gams_fmt_f32_short(v, buf));
 }
 
 std::string fmt_prop4(float p) {

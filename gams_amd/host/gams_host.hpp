@@ -198,6 +198,8 @@ public:
     std::string locate_seq(const std::vector<std::string> &rgs, const std::map<std::string, std::string> &seq_of);
     const Ctg *ctg(const std::string &id) const;
     friend RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device);
+    friend std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
+                                 const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device);
 
 private:
     gams_gpu_t *h_;
@@ -254,6 +256,21 @@ std::vector<std::vector<Peak>> peak_records_batch(gams_gpu_t *h, const std::vect
                                                   const std::vector<std::vector<std::pair<Range, std::string>>> &peaks,
                                                   uint64_t batch_bytes = 256ull << 20);
 
+// the TSV rows `gams peak` prints for these records: the eleven fields of Peak, tab-separated, floats as `{}`
+std::string peak_rows(const std::vector<Peak> &recs);
+// `gams peak` over the bytes of one wave TSV (utils.rs:83-116, peak.rs:41-160): the rows of every ctg, the ctgs in id
+// order (the reference's BTreeMap), made on the device (gams_gpu_peak_text) from the bytes to the text.  Unlike
+// read_peak + peak_records_batch, which take the bucket order as given, the kept peaks of a ctg are sorted by start
+// (stably) before they are numbered, as peak.rs:49 does.  seqs[i] = the bases of ctgs[i]: one seqset is built and
+// uploaded for the call.  Where the device refuses (GAMS_EUNSUPPORTED) the lines go through read_peak, the same
+// sort, the gc of the ranges (gams_gpu_range_gc_batch) and peak_rows; *device as in Locator::locate_text.
+std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                      const char *bytes, size_t n, bool *device = nullptr);
+// ... on a resident seqset (a host that has just run `wave` from these bases): slots[i] = the seqset slot that holds
+// ctgs[i], UINT32_MAX if none does (peaks in such a ctg are an error)
+std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
+                      const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device = nullptr);
+
 // src/cmd_gams/rg.rs:41-77 / feature.rs:47-95: the records the loaders SET, as (key, JSON) pairs in
 // the reference's order (ctg id order, then file order), serials from 1 per ctg (a fresh cnt:).
 // JSON text as serde_json writes the structs of src/libs/data.rs:16-28 (field order, no spaces).
@@ -303,6 +320,8 @@ std::string anno_text(gams_gpu_t *h, const std::map<std::string, Runlist> &sets,
 std::vector<std::string> text_lines(const char *bytes, size_t n);
 // `{:.4}` of an anno prop in [0, 1] as the device prints it (integer arithmetic, csrc/text_fmt.hpp); "" outside
 std::string fmt_prop4(float p);
+// `{}` of an f32 in [0, 1] as the device prints a peak amplitude (csrc/text_fmt.hpp); "" where it refuses
+std::string fmt_f32_short(float v);
 
 // ---- wire formats either side of the path (gams_wire.cpp; SURVEY 8 f-3, parity unpinned) ----------
 namespace wire {

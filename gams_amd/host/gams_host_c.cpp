@@ -528,6 +528,8 @@ char *gams_host_anno_text(gams_gpu_t *h, uint32_t n, const char *const *ids, con
 
 // `{:.4}` of an anno prop as the device formats it ("" outside [0, 1])
 char *gams_host_fmt_prop4(float p) { return dup(gams::fmt_prop4(p)); }
+// `{}` of an f32 in [0, 1] as the device formats a peak amplitude ("" where it refuses)
+char *gams_host_fmt_f32_short(float v) { return dup(gams::fmt_f32_short(v)); }
 
 // locate --seq (locate.rs:124-134).  seq_lines: "ctg_id\tbases" rows.
 char *gams_host_locate_seq(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
@@ -577,12 +579,28 @@ char *gams_host_peak(gams_gpu_t *h, uint32_t n, const char *const *ids, const ch
             ps.push_back(seqs[slot]);
             pp.push_back(kv.second);
         }
-        for (const std::vector<gams::Peak> &recs : gams::peak_records_batch(h, pc, ps, pp))
-            for (const gams::Peak &p : recs)
-                out += p.id + "\t" + p.range + "\t" + std::to_string(p.length) + "\t" + gams::fmt_f32(p.gc) + "\t" +
-                       p.signal + "\t" + std::to_string(p.left_wave_length) + "\t" + gams::fmt_f32(p.left_amplitude) +
-                       "\t" + p.left_signal + "\t" + std::to_string(p.right_wave_length) + "\t" +
-                       gams::fmt_f32(p.right_amplitude) + "\t" + p.right_signal + "\n";
+        for (const std::vector<gams::Peak> &recs : gams::peak_records_batch(h, pc, ps, pp)) out += gams::peak_rows(recs);
+        return out;
+    });
+}
+
+// `gams peak` over the bytes of a wave TSV (bytes, n_bytes: not NUL-terminated; gams::peak_text): the rows of
+// gams_host_peak with every ctg's peaks sorted by start, made on the device.  seqset == NULL: seqs[i] = the bases of
+// ctg i, uploaded for the call; else the resident seqset and slots[i] = its slot of ctg i (UINT32_MAX: none), seqs unused.
+char *gams_host_peak_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                          const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                          const char *bytes, uint64_t n_bytes, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        bool dev = false;
+        std::string out;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (seqset)
+            out = gams::peak_text(h, cv, seqset, std::vector<uint32_t>(slots, slots + n), bytes, (size_t)n_bytes, &dev);
+        else
+            out = gams::peak_text(h, cv, std::vector<const uint8_t *>(seqs, seqs + n), bytes, (size_t)n_bytes, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
         return out;
     });
 }

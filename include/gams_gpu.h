@@ -24,6 +24,8 @@
  *   gams_gpu_locate_text      src/cmd_gams/locate.rs:84-141 (locate -f: lines, Range::from_str, find_one_idx, rows)
  *   gams_gpu_count_text       src/cmd_gams/locate.rs:84-141 (locate --count: the same with count_rg, utils.rs:24-36)
  *   gams_gpu_anno_text        src/cmd_gams/anno.rs:95-142   (one input file: fields, extract_ctg_id, cover, rows)
+ *   gams_gpu_peak_text        src/libs/utils.rs:83-116 read_peak + src/cmd_gams/peak.rs:41-160 (one wave TSV: fields,
+ *                             find_one_idx, drop-first, sort by start, cache_gc_content, neighbours, the Peak rows)
  *
  * Measurement and tuning entries (event stopwatch, phase stamps, guard-band and tile knobs, kernel
  * names) are NOT part of this surface: they live in gams_gpu_diag.h, which a host need not bind.
@@ -413,6 +415,39 @@ int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_nam
  * gams_index_destroy. */
 int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const char *bytes,
                                  uint64_t n_bytes, gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept);
+
+/* ---- text in, text out: peak (utils.rs:83-116 read_peak, then peak.rs:41-160) ---- */
+/* The bytes of ONE wave TSV ("{range}\t{gc_content}\t{signal}" rows; lines, refused bytes and the 2^32 - 1 line limit as
+ * for the text entries above) -> the rows `gams peak` makes of it, as gams_host_peak prints them:
+ *   "peak:{ctg_id}:{serial}\t{range}\t{length}\t{gc}\t{signal}\t{left_wave_length}\t{left_amplitude}\t{left_signal}\t"
+ *   "{right_wave_length}\t{right_amplitude}\t{right_signal}\n"
+ * ctg_ix, chr_names, ctg_ids as for gams_gpu_locate_text.  ctg_index[i], chr_start[i], chr_end[i] describe interval i of
+ * ctg_ix in the caller's original order: the slot of s that holds the ctg's bases (UINT32_MAX: none; otherwise a slot
+ * of chr_end - chr_start + 1 bases, GAMS_EINVAL if not) and the ctg's place on its chromosome.
+ * parts[0], the line up to its first '\t', goes through Range::from_str; an invalid one (the header row) skips the
+ * line.  A line with a valid range and fewer than three fields is GAMS_EINVAL, located or not (the reference panics,
+ * utils.rs:102).  The strand is dropped, the range is located as gams_gpu_locate locates; unknown chromosomes and
+ * unlocated lines are skipped.  Of the located lines of a ctg the first in file order is dropped (utils.rs:109-112, as
+ * in the rg loader): it is never looked at again, and a ctg with one located line prints nothing.  The kept peaks of a
+ * ctg are ordered by start, ties in file order (peak.rs:49, a stable sort), and numbered from 1.  Every kept peak must
+ * lie inside its ctg (chr_start <= start <= end <= chr_end) and its ctg must have a sequence: GAMS_EINVAL otherwise.
+ * gc = gams_gpu_range_gc of the range.  With k the peak's rank among the n of its ctg: left_wave_length = start -
+ * (k ? end[k-1] : chr_start) + 1, left_amplitude = |gc - gc[k-1]| (0 for k = 0), left_signal = the third field of peak
+ * k - 1 (its own for k = 0); the right side mirrors it with start[k+1] / chr_end.  Wave lengths are signed i32.
+ * {range} is the range reprinted with the strand cleared: the "name." prefix if the name is not empty, the chromosome,
+ * ':', start, and "-end" only when end != start; gc and the amplitudes print as Rust's `{}` prints an f32 (shortest
+ * round trip), the signals are echoed.
+ * *text (text_bytes bytes, no NUL; page-locked memory owned by the handle, valid until the next call of this entry on
+ * the handle) holds the rows grouped by ctg in the caller's order: those of interval i are text[text_off[i] ..
+ * text_off[i+1]) (text_off has n_ctg + 1 entries; `gams peak` prints the ctgs in id order).  *n_rows counts the rows.
+ * Two calls return identical text.  Zero bytes or no kept peak: GAMS_OK, no rows, text_off all zero.
+ * GAMS_ESTATE for a seqset without the sequence bytes (plane-only).  GAMS_EUNSUPPORTED (nothing is printed; run the
+ * host path) also when (ctg, start, line) does not fit a 64-bit sort key -- bits(n_ctg) + 31 + bits(lines - 1) > 64 --
+ * and for a gc or amplitude the device formatters do not cover (none on valid input). */
+int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                       const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                       const int32_t *chr_end, const char *bytes, uint64_t n_bytes, const char **text,
+                       uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_rows);
 
 /* ---- gen: valid regions of a chromosome (first "next" row of SURVEY section 8f) ---- */
 /* gen.rs:86-104: bases other than A C G T a c g t are ambiguous; the valid set is their

@@ -22,13 +22,15 @@ int gams_gpu_timer_start(gams_gpu_t *h);
 int gams_gpu_timer_stop(gams_gpu_t *h, float *ms);
 /* Device time (HIP events around the kernel, excluding the host<->device copies) of the last
  * gams_gpu_sw / gams_gpu_count / gams_gpu_locate / gams_gpu_cover call on this handle; after a range loader call
- * (gams_gpu_read_range_text / gams_index_create_range_text) the sum of its stages. */
+ * (gams_gpu_read_range_text / gams_index_create_range_text) or gams_gpu_peak_text the sum of its stages. */
 int gams_gpu_last_kernel_ms(gams_gpu_t *h, float *ms);
 
 /* The stages of the last gams_gpu_read_range_text / gams_index_create_range_text call on this handle, in ms (HIP events
  * around each): lines (upload + line index), parse, locate, first, keep, offsets, order, gather, and for the index entry
- * build.  Writes up to cap values; *n = the stages the call ran (gams_gpu_last_kernel_ms is their sum).  GAMS_ESTATE
- * when the last timed call was not one of the two (or its input had no line). */
+ * build.  After gams_gpu_peak_text, its ten: lines, parse, locate, first, keep, offsets, order, gc (gather, checks and
+ * range gc), rows (row lengths and their prefix), write.  Writes up to cap values; *n = the stages the call ran
+ * (gams_gpu_last_kernel_ms is their sum).  GAMS_ESTATE when the last timed call was none of the three (or its input had
+ * no line; for the peak entry: no kept peak). */
 int gams_gpu_last_stage_ms(gams_gpu_t *h, float *ms, uint32_t cap, uint32_t *n);
 
 /* Tapered launches.  A launch of the headline parameters (size 100, step 10, lag 100) over at least a
