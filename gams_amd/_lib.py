@@ -29,6 +29,11 @@ class WaveParams(C.Structure):
                 ("threshold", C.c_float), ("influence", C.c_float)]
 
 
+class GenParams(C.Structure):
+    _fields_ = [("piece", C.c_int32), ("fill", C.c_int32), ("min_len", C.c_int32)]
+
+
+GEN_CTG_DTYPE = np.dtype([("chr", np.uint32), ("serial", np.uint32), ("chr_start", np.int32), ("chr_end", np.int32)])
 PEAK_DTYPE = np.dtype([("ctg", np.uint32), ("window", np.uint32), ("gc_count", np.uint32),
                        ("signal", np.int32)])
 SW_ROW_DTYPE = np.dtype([("feature", np.uint32), ("type", np.int32), ("distance", np.int32),
@@ -62,6 +67,7 @@ PROTOTYPES = {
     "gams_gc_plane_with": (C.c_int, [_VP, C.c_uint64, _VP, C.c_int]),
     "gams_wave_plan_set_input": (C.c_int, [_VP, _VP, C.c_int]),
     "gams_wave_plan_last_input": (C.c_int, [_VP, _VP, C.POINTER(C.c_int)]),
+    "gams_seqset_download": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP]),
     "gams_seqset_destroy": (None, [_VP, _VP]),
     "gams_wave_plan_create": (C.c_int, [_VP, _VP, C.POINTER(WaveParams), C.c_uint32, _PP]),
     "gams_wave_plan_destroy": (None, [_VP, _VP]),
@@ -127,6 +133,12 @@ PROTOTYPES = {
                                      C.POINTER(C.c_uint64)]),
     "gams_gpu_valid_spans": (C.c_int, [_VP, _VP, C.c_uint64, C.c_int32, C.c_int32, _VP, _VP, C.c_uint64,
                                        C.POINTER(C.c_uint64)]),
+    "gams_gpu_gen_text": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(GenParams), _PP]),
+    "gams_gen_counts": (C.c_int, [_VP, _VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    "gams_gen_chrs": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "gams_gen_ctgs": (C.c_int, [_VP, _VP, _VP]),
+    "gams_gen_seqset": (C.c_int, [_VP, _VP, _PP]),
+    "gams_gen_destroy": (None, [_VP, _VP]),
 }
 
 _lib = None

@@ -463,6 +463,20 @@ int gams_seqset_upload_ranges(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *im
     return GAMS_OK;
 }
 
+int gams_seqset_download(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, uint8_t *seq, uint8_t *plane) {
+    if (!h || !s) return gams_fail(h, GAMS_EINVAL, "seqset_download: null argument");
+    if (i >= s->n_ctg) return gams_fail(h, GAMS_EINVAL, "seqset_download: ctg index out of range");
+    if (seq && !s->have_bytes)
+        return gams_fail(h, GAMS_ESTATE, "seqset_download: the seqset holds the G/C plane only");
+    if (plane && !s->plane_ok) return gams_fail(h, GAMS_ESTATE, "seqset_download: the G/C plane is stale");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    if (s->uploaded) GAMS_HIP(h, hipEventSynchronize(s->uploaded));   // everything that wrote the buffers so far
+    const uint64_t n = s->len[i];
+    if (seq && n) GAMS_HIP(h, hipMemcpy(seq, s->d_seq + s->off[i], n, hipMemcpyDeviceToHost));
+    if (plane && n) GAMS_HIP(h, hipMemcpy(plane, s->d_plane + (s->off[i] >> 3), (n + 7) / 8, hipMemcpyDeviceToHost));
+    return GAMS_OK;
+}
+
 void gams_seqset_destroy(gams_gpu_t *h, gams_seqset_t *s) {
     if (!s) return;
     if (h) {

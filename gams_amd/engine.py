@@ -91,6 +91,24 @@ class SeqSet:
         ptrs = (C.c_void_p * max(len(arrs), 1))(*[a.ctypes.data if a.size else None for a in arrs])
         eng.check(eng.lib.gams_seqset_upload_all(eng.h, self.p, ptrs))
 
+    @classmethod
+    def adopt(cls, eng, ptr, lengths):
+        """a seqset the library built itself (gams_gen_seqset): `ptr` its handle, lengths[i] the bases of slot i"""
+        self = cls.__new__(cls)
+        self.eng = eng
+        self.lengths = np.array(lengths, np.uint32)
+        self.p = C.c_void_p(ptr)
+        return self
+
+    def download(self, i, plane=False):
+        """the bases of ctg i as they lie on the device (plane=True: the ceil(len / 8) bytes of its G/C plane), as
+        bytes: gams_seqset_download"""
+        n = int(self.lengths[i])
+        buf = np.zeros(max((n + 7) // 8 if plane else n, 1), np.uint8)
+        self.eng.check(self.eng.lib.gams_seqset_download(self.eng.h, self.p, i, None if plane else buf.ctypes.data,
+                                                         buf.ctypes.data if plane else None))
+        return buf[:(n + 7) // 8 if plane else n].tobytes()
+
     def upload(self, i, seq):
         """replace ctg i (same length) with new bases"""
         a = _u8(seq)

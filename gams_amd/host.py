@@ -154,6 +154,11 @@ def load():
                                       C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.gams_host_gen.restype = C.c_void_p
     L.gams_host_gen.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
+    L.gams_host_read_fasta.restype = C.c_void_p
+    L.gams_host_read_fasta.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_gen_text.restype = C.c_void_p
+    L.gams_host_gen_text.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
     L.gams_host_fmt_f32.restype = C.c_void_p
     L.gams_host_fmt_f32.argtypes = [C.c_float]
     L.gams_host_range_roundtrip.restype = C.c_void_p
@@ -378,7 +383,7 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 
 def last_operator_device():
-    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text / peak_text of this thread made its rows on the device,
+    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text / peak_text / gen_text of this thread made its rows on the device,
     0 if it fell back to the host"""
     return int(load().gams_host_last_operator_device())
 
@@ -392,6 +397,42 @@ def gen(eng, chr_id, seq, piece=500000, fill=50, min_len=5000):
     """ctg rows (id, range, chr_id, chr_start, chr_end, chr_strand, length) of one chromosome."""
     a = np.ascontiguousarray(np.frombuffer(seq, np.uint8) if not isinstance(seq, np.ndarray) else seq)
     return _take(load().gams_host_gen(eng.h, chr_id.encode(), a.ctypes.data, a.size, piece, fill, min_len))
+
+
+def read_fasta(data):
+    """The records of a FASTA file's bytes as the reference's reader gives them (gams::read_fasta; no engine):
+    [(id, bases)] in file order, trailing white space of every sequence line trimmed."""
+    out_len = C.c_uint64()
+    blob = _take_bytes(load().gams_host_read_fasta(bytes(data), len(data), C.byref(out_len)), out_len)
+    head, _, seqs = blob.partition(b"\n\n") if not blob.startswith(b"\n") else (b"", b"", blob[1:])   # no record: "\n"
+    recs, at = [], 0
+    for row in (head.split(b"\n") if head else []):
+        name, n = row.split(b"\t")
+        recs.append((name.decode("latin-1"), seqs[at:at + int(n)]))
+        at += int(n)
+    return recs
+
+
+def gen_text(eng, data, piece=500000, fill=50, min_len=5000):
+    """`gams gen` over the bytes of one FASTA file, made on the device from one upload of them (the host's passes where
+    the device refuses; last_operator_device says which): -> (ctgs, chr_len, seqset).  ctgs: dicts with id, chr_id,
+    chr_start, chr_end, range, length, chromosomes in file order; chr_len: {chromosome: bases}; seqset: the resident
+    engine.SeqSet of the ctgs' bases and G/C plane, slot k = ctgs[k]."""
+    from . import engine
+
+    out_len, ptr = C.c_uint64(), C.c_void_p()
+    text = _take_bytes(load().gams_host_gen_text(eng.h, bytes(data), len(data), piece, fill, min_len, C.byref(ptr),
+                                                 C.byref(out_len)), out_len).decode("latin-1")   # an id may hold any byte
+    ctgs, chr_len = [], {}
+    for row in text.split("\n")[:-1]:
+        f = row.split("\t")
+        if f[0] == "chr":
+            chr_len[f[1]] = int(f[2])
+        else:
+            s, e = int(f[3]), int(f[4])
+            ctgs.append(dict(id=f[1], chr_id=f[2], chr_start=s, chr_end=e, range=f"{f[2]}:{s}-{e}" if e != s else f"{f[2]}:{s}",
+                             length=e - s + 1))
+    return ctgs, chr_len, engine.SeqSet.adopt(eng, ptr.value, [c["length"] for c in ctgs])
 
 
 def locate_seq(eng, ctgs, rgs):

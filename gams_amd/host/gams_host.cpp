@@ -1,6 +1,7 @@
 // gams_host.cpp -- see gams_host.hpp.  Citations are file:line under the reference.
 #include "gams_host.hpp"
 #include "../../include/gams_gpu_diag.h"   // the stage clock reports which input a pass read
+#include "../csrc/gen_split.hpp"
 #include "../csrc/text_fmt.hpp"
 
 #include <algorithm>
@@ -2185,6 +2186,21 @@ std::string encode_gz(const uint8_t *bytes, size_t n) {
 // ---------------------------------------------------------------------------
 // gen
 // ---------------------------------------------------------------------------
+namespace {
+// gen.rs:131-150
+Ctg make_ctg(const std::string &chr_id, int64_t serial, int32_t start, int32_t end) {
+    Ctg c;
+    c.id = "ctg:" + chr_id + ":" + std::to_string(serial);
+    c.chr_id = chr_id;
+    c.chr_start = start;
+    c.chr_end = end;
+    c.chr_strand = "+";
+    c.length = end - start + 1;
+    c.range = chr_id + ":" + runlist(start, end);
+    return c;
+}
+}  // namespace
+
 std::vector<Ctg> gen_ctgs(gams_gpu_t *h, const std::string &chr_id, const uint8_t *seq, uint64_t len,
                           const GenArgs &a) {
     // one scan of the chromosome; a second only if it has more valid regions than a generous first guess
@@ -2199,29 +2215,90 @@ std::vector<Ctg> gen_ctgs(gams_gpu_t *h, const std::string &chr_id, const uint8_
     std::vector<Ctg> out;
     int32_t serial = 0;
     for (uint64_t i = 0; i < n; ++i) {                                 // gen.rs:108-126
-        int64_t pos = lo[i];
-        const int64_t max = hi[i];
-        std::vector<std::pair<int64_t, int64_t>> cur;
-        while (max - pos + 1 > a.piece) {
-            cur.emplace_back(pos, pos + a.piece - 1);
-            pos += a.piece;
+        gams_piece_split(lo[i], hi[i], a.piece,
+                         [&](int64_t s0, int64_t e0) { out.push_back(make_ctg(chr_id, ++serial, (int32_t)s0, (int32_t)e0)); });
+    }
+    return out;
+}
+
+std::vector<FastaRecord> read_fasta(const char *bytes, size_t n) {
+    std::vector<FastaRecord> out;
+    if (n == 0) return out;
+    if (bytes[0] != '>') throw Error(GAMS_EINVAL, "read_fasta: Expected > at record start");
+    for (size_t b = 0; b < n;) {
+        const char *nl = (const char *)std::memchr(bytes + b, '\n', n - b);
+        const size_t end = nl ? (size_t)(nl - bytes) : n;   // the line is bytes[b, end)
+        if (bytes[b] == '>') {
+            size_t e = b + 1;
+            while (e < end && !gams_fasta_space((uint8_t)bytes[e])) ++e;
+            out.push_back(FastaRecord{std::string(bytes + b + 1, bytes + e), std::string()});
+        } else {
+            size_t e = end;
+            while (e > b && gams_fasta_space((uint8_t)bytes[e - 1])) --e;
+            out.back().seq.append(bytes + b, bytes + e);
         }
-        if (cur.empty())
-            cur.emplace_back(pos, max);
-        else
-            cur.back().second = max;                                   // the last piece absorbs the remainder
-        for (auto &r : cur) {                                          // gen.rs:131-150
-            Ctg c;
-            c.id = "ctg:" + chr_id + ":" + std::to_string(++serial);
-            c.chr_id = chr_id;
-            c.chr_start = (int32_t)r.first;
-            c.chr_end = (int32_t)r.second;
-            c.chr_strand = "+";
-            c.length = c.chr_end - c.chr_start + 1;
-            c.range = chr_id + ":" + runlist(r.first, r.second);
-            out.push_back(c);
+        b = end + 1;
+    }
+    return out;
+}
+
+GenText gen_text(gams_gpu_t *h, const char *bytes, size_t n, const GenArgs &a, bool *device) {
+    GenText out;
+    SeqSetGuard guard{h};
+    const gams_gen_params_t prm{a.piece, a.fill, a.min};
+    gams_gen_t *g = nullptr;
+    const int rc = gams_gpu_gen_text(h, bytes, n, &prm, &g);
+    if (device) *device = rc == GAMS_OK;
+    if (rc == GAMS_OK) {
+        struct GenGuard {
+            gams_gpu_t *h;
+            gams_gen_t *g;
+            ~GenGuard() { gams_gen_destroy(h, g); }
+        } gg{h, g};
+        uint32_t n_chr = 0, n_ctg = 0;
+        uint64_t name_bytes = 0;
+        check(h, gams_gen_counts(h, g, &n_chr, &n_ctg, &name_bytes));
+        std::string names(name_bytes, '\0');
+        std::vector<uint64_t> name_off((size_t)n_chr + 1);
+        std::vector<uint32_t> len(n_chr);
+        std::vector<gams_gen_ctg_t> tab(n_ctg);
+        check(h, gams_gen_chrs(h, g, names.data(), name_off.data(), len.data()));
+        check(h, gams_gen_ctgs(h, g, tab.data()));
+        for (uint32_t c = 0; c < n_chr; ++c)
+            out.chr_len.emplace_back(names.substr(name_off[c], name_off[c + 1] - name_off[c]), len[c]);
+        out.ctgs.reserve(n_ctg);
+        for (const gams_gen_ctg_t &t : tab) out.ctgs.push_back(make_ctg(out.chr_len[t.chr].first, t.serial, t.chr_start, t.chr_end));
+        check(h, gams_gen_seqset(h, g, &out.seqset));
+        return out;
+    }
+    if (rc != GAMS_EUNSUPPORTED) throw Error(rc, gams_gpu_last_error(h));
+    // the host passes
+    const std::vector<FastaRecord> recs = read_fasta(bytes, n);
+    std::map<std::string, int64_t> serial;      // cnt:ctg:{chr}
+    std::map<std::string, size_t> len_slot;     // len_of
+    std::vector<const uint8_t *> seqs;
+    std::vector<uint32_t> lengths;
+    for (const FastaRecord &r : recs) {
+        auto it = len_slot.find(r.id);
+        if (it == len_slot.end()) {
+            len_slot[r.id] = out.chr_len.size();
+            out.chr_len.emplace_back(r.id, r.seq.size());
+        } else {
+            out.chr_len[it->second].second = r.seq.size();
+        }
+        if (r.seq.empty()) continue;
+        if (r.seq.size() > 0x7fffffffull) throw Error(GAMS_EUNSUPPORTED, "gen_text: " + r.id + " has more than 2^31 - 1 bases");
+        int64_t &sn = serial[r.id];
+        for (const Ctg &c : gen_ctgs(h, r.id, (const uint8_t *)r.seq.data(), r.seq.size(), a)) {
+            out.ctgs.push_back(make_ctg(r.id, ++sn, c.chr_start, c.chr_end));
+            seqs.push_back((const uint8_t *)r.seq.data() + (c.chr_start - 1));
+            lengths.push_back((uint32_t)c.length);
         }
     }
+    check(h, gams_seqset_create(h, (uint32_t)lengths.size(), lengths.data(), &guard.s));
+    check(h, gams_seqset_upload_all(h, guard.s, seqs.data()));   // (staged when it returns: `recs` may go)
+    out.seqset = guard.s;
+    guard.s = nullptr;
     return out;
 }
 

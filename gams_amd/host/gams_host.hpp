@@ -302,6 +302,27 @@ struct GenArgs {            // defaults of src/cmd_gams/gen.rs:26-49
 std::vector<Ctg> gen_ctgs(gams_gpu_t *h, const std::string &chr_id, const uint8_t *seq, uint64_t len,
                           const GenArgs &a);
 
+// bio::io::fasta::Reader as gen.rs:67-78 uses it, over the bytes of a file: lines split on '\n' (a last line without
+// one counts); a line that begins with '>' starts a record whose id is what follows up to the first ASCII white space;
+// every other line is trimmed of trailing ASCII white space and appended to the record's sequence.  No bytes: no
+// records; a first byte other than '>' is GAMS_EINVAL (the reference panics: "Expected > at record start").
+struct FastaRecord {
+    std::string id, seq;
+};
+std::vector<FastaRecord> read_fasta(const char *bytes, size_t n);
+
+// `gams gen` over the bytes of one FASTA file: the ctgs (chromosomes in file order, then serial), the chromosome
+// lengths, and the resident seqset of the ctgs' bases with its G/C plane (slot k = ctgs[k]; the caller destroys it).
+// Made on the device from one upload of the bytes (gams_gpu_gen_text).  Where the device refuses (GAMS_EUNSUPPORTED) the
+// host passes run: read_fasta, gen_ctgs per record, gams_seqset_upload_all; a duplicate id then continues its serial
+// counter and keeps its last length, as cnt:ctg:{chr} and len_of do (gen.rs:78, :133).  *device as in locate_text.
+struct GenText {
+    std::vector<Ctg> ctgs;
+    std::vector<std::pair<std::string, uint64_t>> chr_len;   // in order of first appearance
+    gams_seqset_t *seqset = nullptr;
+};
+GenText gen_text(gams_gpu_t *h, const char *bytes, size_t n, const GenArgs &a, bool *device = nullptr);
+
 // anno.rs:95-142; `sets` = runlists per chr (sorted disjoint spans)
 struct Runlist {
     std::vector<int32_t> lo, hi;

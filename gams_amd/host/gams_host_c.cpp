@@ -696,6 +696,43 @@ char *gams_host_gen(gams_gpu_t *h, const char *chr_id, const uint8_t *seq, uint6
     });
 }
 
+// gams::read_fasta over the bytes of a file (no device work): a "{id}\t{length}\n" row per record, an empty line, then
+// the records' sequences one behind the other (a sequence may hold any byte but '\n', so it is given by length)
+char *gams_host_read_fasta(const char *bytes, uint64_t n_bytes, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const std::vector<gams::FastaRecord> recs = gams::read_fasta(bytes, (size_t)n_bytes);
+        std::string out;
+        for (const gams::FastaRecord &r : recs) out += r.id + "\t" + std::to_string(r.seq.size()) + "\n";
+        out += "\n";
+        for (const gams::FastaRecord &r : recs) out += r.seq;
+        return out;
+    });
+}
+
+// `gams gen` over the bytes of one FASTA file (gams::gen_text): "chr\t{id}\t{length}\n" per chromosome, then
+// "ctg\t{id}\t{chr_id}\t{chr_start}\t{chr_end}\n" per ctg; *seqset receives the resident seqset (slot k = ctg k; the
+// caller destroys it with gams_seqset_destroy).  gams_host_last_operator_device says which path ran.
+char *gams_host_gen_text(gams_gpu_t *h, const char *bytes, uint64_t n_bytes, int32_t piece, int32_t fill, int32_t min_len,
+                         gams_seqset_t **seqset, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        gams::GenArgs a;
+        a.piece = piece;
+        a.fill = fill;
+        a.min = min_len;
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        gams::GenText g = gams::gen_text(h, bytes, (size_t)n_bytes, a, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        *seqset = g.seqset;
+        std::string out;
+        for (auto &c : g.chr_len) out += "chr\t" + c.first + "\t" + std::to_string(c.second) + "\n";
+        for (const gams::Ctg &c : g.ctgs)
+            out += "ctg\t" + c.id + "\t" + c.chr_id + "\t" + std::to_string(c.chr_start) + "\t" + std::to_string(c.chr_end) + "\n";
+        return out;
+    });
+}
+
 // tsv.rs:31-71 for "ctg:*" (no device work)
 char *gams_host_tsv_ctgs(uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
                          const int32_t *ends) {

@@ -21,6 +21,7 @@
  *   gams_gpu_locate           src/libs/utils.rs:7-22        (find_one_idx -> Lapper::find().next())
  *   gams_gpu_cover            src/cmd_gams/anno.rs:128-139  (IntSpan intersect cardinalities)
  *   gams_gpu_valid_spans      src/cmd_gams/gen.rs:86-104    (ambiguous-base scan, fill, excise)
+ *   gams_gpu_gen_text         src/cmd_gams/gen.rs:67-157    (one FASTA file: records, the scan, fill, excise, --piece, the ctgs' bases)
  *   gams_gpu_locate_text      src/cmd_gams/locate.rs:84-141 (locate -f: lines, Range::from_str, find_one_idx, rows)
  *   gams_gpu_count_text       src/cmd_gams/locate.rs:84-141 (locate --count: the same with count_rg, utils.rs:24-36)
  *   gams_gpu_anno_text        src/cmd_gams/anno.rs:95-142   (one input file: fields, extract_ctg_id, cover, rows)
@@ -59,6 +60,7 @@ typedef struct gams_wave_plan gams_wave_plan_t;
 typedef struct gams_index gams_index_t;
 typedef struct gams_spans gams_spans_t;
 typedef struct gams_names gams_names_t;
+typedef struct gams_gen gams_gen_t;
 
 /* ---- handle ------------------------------------------------------------ */
 int gams_gpu_create(int device, gams_gpu_t **h);
@@ -126,6 +128,10 @@ int gams_gc_plane(const uint8_t *seq, uint64_t n, uint8_t *plane);
  * plane_image == NULL is gams_seqset_upload_image. */
 int gams_seqset_upload_ranges(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *image, const uint8_t *plane_image,
                               uint64_t lo, uint64_t hi);
+/* Wait for the uploads queued so far and copy ctg i back: its lengths[i] bases to seq and / or the ceil(lengths[i] / 8)
+ * bytes of its G/C plane to plane (either may be NULL).  What a host that fills a store needs after gams_gpu_gen_text.
+ * GAMS_ESTATE for the bases of a plane-only seqset and for the plane while it is stale. */
+int gams_seqset_download(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, uint8_t *seq, uint8_t *plane);
 void gams_seqset_destroy(gams_gpu_t *h, gams_seqset_t *s);
 
 /* ---- wave (GC windows + smoothed z-score) ------------------------------- */
@@ -456,6 +462,47 @@ int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, co
 int gams_gpu_valid_spans(gams_gpu_t *h, const uint8_t *seq, uint64_t len, int32_t fill,
                          int32_t min_len, int32_t *span_lo, int32_t *span_hi, uint64_t cap,
                          uint64_t *n_spans);
+
+/* ---- gen from the bytes of a FASTA file (gen.rs:67-157) ---- */
+/* The bytes of ONE FASTA file (any host memory, as for the text entries; they cross the link once) -> the chromosomes,
+ * the ctg table, and a seqset of the ctgs' bases with its G/C plane, built on the device from the copy just uploaded.
+ * Lines are split on '\n'; a last line without '\n' counts.  A line whose first byte is '>' starts a record: its id is
+ * the bytes behind the '>' up to the first ASCII white space or the line's end.  Every other line contributes its bytes
+ * as bases, without a '\r' that stands directly before the '\n' or at the end of the input; a '>' that is not in column
+ * 0 is a base (an ambiguous one); empty lines contribute nothing; a record without bases is a chromosome of length 0
+ * without ctgs.  Zero bytes: GAMS_OK, no chromosomes.  Otherwise the first byte must be '>' (GAMS_EINVAL; the reference
+ * panics); piece, fill or min_len < 1 is GAMS_EINVAL.
+ * Bases other than A C G T a c g t are ambiguous; per chromosome the valid set is their complement after fill(fill - 1)
+ * and excise(min_len), and a valid span longer than `piece` is cut into pieces of `piece` bases, the last one taking the
+ * remainder (gen.rs:86-126: gams_gpu_valid_spans per chromosome and the split).  Chromosomes come in file order; ctgs in
+ * chromosome order, then ascending serial, which counts from 1 inside each chromosome; the id of a ctg is
+ * "ctg:{name of chr}:{serial}"; chr_start / chr_end are 1-based, inclusive.  Ctg k of the table is slot k of the seqset.
+ * GAMS_EUNSUPPORTED (run the host path): a byte >= 0x80 or a NUL; inside a sequence line a '\r' anywhere else, a space, a
+ * tab, 0x0B or 0x0C (the reference trims trailing white space; the host path does); an empty id; a duplicate id; a
+ * chromosome of more than INT32_MAX bases; more than 2^32 - 1 ctgs; more than 2^40 bytes of input.  Two calls on the same bytes return identical tables
+ * and identical device bytes. */
+typedef struct {
+    int32_t piece, fill, min_len; /* --piece, --fill, --min (gen.rs:28-50) */
+} gams_gen_params_t;
+typedef struct {
+    uint32_t chr, serial; /* chromosome (file order) and serial inside it, from 1 */
+    int32_t chr_start, chr_end;
+} gams_gen_ctg_t;
+int gams_gpu_gen_text(gams_gpu_t *h, const char *bytes, uint64_t n_bytes, const gams_gen_params_t *params,
+                      gams_gen_t **g);
+/* sizes of the result (any pointer may be NULL): chromosomes, ctgs, and the bytes of all ids together */
+int gams_gen_counts(gams_gpu_t *h, const gams_gen_t *g, uint32_t *n_chr, uint32_t *n_ctg, uint64_t *name_bytes);
+/* the chromosomes (any pointer may be NULL): the id of chromosome c is names[name_off[c] .. name_off[c + 1]) (name_bytes
+ * bytes, no NUL; name_off has n_chr + 1 entries), chr_len[c] its bases */
+int gams_gen_chrs(gams_gpu_t *h, const gams_gen_t *g, char *names, uint64_t *name_off, uint32_t *chr_len);
+/* the ctg table, n_ctg records */
+int gams_gen_ctgs(gams_gpu_t *h, const gams_gen_t *g, gams_gen_ctg_t *ctgs);
+/* The seqset, handed to the caller ONCE (a second call is GAMS_ESTATE); destroy it with gams_seqset_destroy.  An
+ * ordinary seqset in the layout of gams_seqset_create with bytes and a valid plane, gaps zero: `wave`, `sw`, range_gc
+ * and peak_text read it like an uploaded one, and gams_seqset_download brings a ctg's bases back for the store. */
+int gams_gen_seqset(gams_gpu_t *h, gams_gen_t *g, gams_seqset_t **s);
+/* frees the tables, and the seqset if it was not handed out */
+void gams_gen_destroy(gams_gpu_t *h, gams_gen_t *g);
 
 #ifdef __cplusplus
 }

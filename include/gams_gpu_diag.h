@@ -28,8 +28,9 @@ int gams_gpu_last_kernel_ms(gams_gpu_t *h, float *ms);
 /* The stages of the last gams_gpu_read_range_text / gams_index_create_range_text call on this handle, in ms (HIP events
  * around each): lines (upload + line index), parse, locate, first, keep, offsets, order, gather, and for the index entry
  * build.  After gams_gpu_peak_text, its ten: lines, parse, locate, first, keep, offsets, order, gc (gather, checks and
- * range gc), rows (row lengths and their prefix), write.  Writes up to cap values; *n = the stages the call ran
- * (gams_gpu_last_kernel_ms is their sum).  GAMS_ESTATE when the last timed call was none of the three (or its input had
+ * range gc), rows (row lengths and their prefix), write.  After gams_gpu_gen_text (of an input that is not empty), its
+ * five: upload, pack (mark, carry, count, offsets, compact), scan, table (the host's part), place.  Writes up to cap values; *n = the stages the call ran
+ * (gams_gpu_last_kernel_ms is their sum).  GAMS_ESTATE when the last timed call was none of these (or its input had
  * no line; for the peak entry: no kept peak). */
 int gams_gpu_last_stage_ms(gams_gpu_t *h, float *ms, uint32_t cap, uint32_t *n);
 
