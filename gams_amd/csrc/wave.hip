@@ -58,6 +58,7 @@ using WaveTileFn = void (*)(WaveArgs);
 static const WaveFastFn kWaveFastFn[kWaveFastCount][2] = {WAVE_FAST_INSTANCES(WAVE_X_PAIR)};
 #undef WAVE_X_PAIR
 static const WaveFastFn kWaveTaperFn[2] = {wave_fast_taper_kernel<100, 10, 100, false>, wave_fast_taper_kernel<100, 10, 100, true>};
+static const WaveFastFn kWaveNarrowFn = wave_fast_narrow_kernel;   // the narrow body of the headline tile (wave_select_body)
 static const WaveTileFn kWaveTileFn[2][2] = {{wave_tile_kernel<uint8_t, false>, wave_tile_kernel<uint8_t, true>},     // [k16][wide]
                                              {wave_tile_kernel<uint16_t, false>, wave_tile_kernel<uint16_t, true>}};
 
@@ -127,6 +128,7 @@ struct gams_wave_plan {
     WaveSelection sel;            // the tile kernel and its geometry (wave_select.hpp), made by wave_build_geometry
     WaveFastFn fast_fn = nullptr; // ... as the pointer a pass launches: one of the two is set, neither for sel.direct
     WaveTileFn tile_fn = nullptr;
+    WaveBody body;                // plane-fed passes of the headline entry: wave_fast_narrow_kernel over the same tiles (wave_select_body)
     uint64_t total_windows = 0;
     std::vector<WaveCtgDev> ctgs;
     std::vector<WaveTile> tiles;
@@ -190,6 +192,8 @@ struct gams_wave_plan {
     bool guard_exact = false;           // every window through the exact path
     int input_req = GAMS_WAVE_INPUT_AUTO;   // gams_wave_plan_set_input
     std::atomic<int> last_input{GAMS_WAVE_INPUT_BYTES};   // what the most recently queued pass read (ways queue from several threads)
+    int body_req = GAMS_WAVE_BODY_AUTO;     // gams_wave_plan_set_body
+    std::atomic<int> last_body{GAMS_WAVE_BODY_WIDE};      // the body of the most recently queued pass
     // every pooled block of the plan back to the pools (the caller has drained the streams)
     void release(gams_gpu_t *h) {
         if (rows) rows->release(h);
@@ -361,6 +365,8 @@ int wave_build_geometry(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t tw_req) {
     p->tile_fn = s.family == kWaveFamTile ? kWaveTileFn[s.k16][s.wide] : nullptr;
     if (p->fast_fn) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(p->fast_fn), s.lds_bytes));
     if (p->tile_fn) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(p->tile_fn), s.lds_bytes));
+    p->body = wave_select_body(in, s);
+    if (p->body.narrow) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kWaveNarrowFn), p->body.lds_bytes));
     if (s.taper)
         wave_fill_tiles_tapered(p, wave_slots(h->cus));
     else
@@ -895,6 +901,8 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
     w.last_ring = slot;
     if (p->pipelined && !w.done) GAMS_HIP(h, hipEventCreateWithFlags(&w.done, hipEventDisableTiming));
     if (p->tiles.empty()) {
+        // nothing to launch, whatever input or body was asked for: no kernel ran, so not the narrow one
+        p->last_body.store(GAMS_WAVE_BODY_WIDE, std::memory_order_relaxed);
         if (p->pipelined) GAMS_HIP(h, hipEventRecord(w.done, st));
         return GAMS_OK;
     }
@@ -912,6 +920,14 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
     if (p->input_req == GAMS_WAVE_INPUT_BYTES && use_plane)
         return gams_fail(h, GAMS_ESTATE, "wave: the seqset holds the G/C plane only, the bytes were asked for");
     p->last_input.store(use_plane ? GAMS_WAVE_INPUT_PLANE : GAMS_WAVE_INPUT_BYTES, std::memory_order_relaxed);
+    // The headline entry's plane-fed passes run the narrow body (128 threads x 24 windows over the same tiles); passes
+    // that read the bytes -- a stale plane, forced bytes -- keep the wide kernel, which holds the byte body.
+    const bool narrow_fit = use_plane && p->body.narrow;
+    if (p->body_req == GAMS_WAVE_BODY_NARROW && !narrow_fit)
+        return gams_fail(h, GAMS_ESTATE, p->body.narrow ? "wave: the narrow body reads the G/C plane, this pass reads the bytes"
+                                                        : "wave: this plan has no narrow body");
+    const bool narrow = narrow_fit && p->body_req != GAMS_WAVE_BODY_WIDE;
+    p->last_body.store(narrow ? GAMS_WAVE_BODY_NARROW : GAMS_WAVE_BODY_WIDE, std::memory_order_relaxed);
     const WaveArgs a = wave_args(p, w, slot, use_plane);
     const unsigned nt = (unsigned)p->tiles.size();
     if (p->sel.direct) {
@@ -926,6 +942,9 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
                                q.lag < 2 ? 1u : 0u);
             GAMS_HIP(h, hipGetLastError());
         }
+    } else if (narrow) {
+        hipLaunchKernelGGL(kWaveNarrowFn, dim3(nt), dim3(p->body.nth), p->body.lds_bytes, st, a.tiles, a.seq, a);
+        GAMS_HIP(h, hipGetLastError());
     } else if (p->fast_fn) {
         hipLaunchKernelGGL(p->fast_fn, dim3(nt), dim3(p->sel.nth), p->sel.lds_bytes, st, a.tiles, a.seq, a);
         GAMS_HIP(h, hipGetLastError());
@@ -980,6 +999,21 @@ int gams_wave_plan_last_input(gams_gpu_t *h, gams_wave_plan_t *p, int *input) {
     if (!h || !p || !input) return gams_fail(h, GAMS_EINVAL, "wave_plan_last_input: null argument");
     if (!p->ran) return gams_fail(h, GAMS_ESTATE, "wave_plan_last_input: no run yet");
     *input = p->last_input.load(std::memory_order_relaxed);
+    return GAMS_OK;
+}
+
+int gams_wave_plan_set_body(gams_gpu_t *h, gams_wave_plan_t *p, int mode) {
+    if (!h || !p) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_body: null argument");
+    if (mode != GAMS_WAVE_BODY_AUTO && mode != GAMS_WAVE_BODY_WIDE && mode != GAMS_WAVE_BODY_NARROW)
+        return gams_fail(h, GAMS_EINVAL, "wave_plan_set_body: mode is 0 (auto), 1 (wide) or 2 (narrow)");
+    p->body_req = mode;
+    return GAMS_OK;
+}
+
+int gams_wave_plan_last_body(gams_gpu_t *h, gams_wave_plan_t *p, int *body) {
+    if (!h || !p || !body) return gams_fail(h, GAMS_EINVAL, "wave_plan_last_body: null argument");
+    if (!p->ran) return gams_fail(h, GAMS_ESTATE, "wave_plan_last_body: no run yet");
+    *body = p->last_body.load(std::memory_order_relaxed);
     return GAMS_OK;
 }
 

@@ -451,6 +451,9 @@ __device__ __forceinline__ void z_decide(float nf, float kkf, float S1f, float S
 // plans: a tile per one or two waves, see NTH below), W windows per thread; a tile holds NTH*W - lag - 1
 // windows when the parameters are baked in, 256*W otherwise.  wave_fast_kernel runs one tile size per launch,
 // wave_fast_taper_kernel W = 12 tiles followed by W = 8 and W = 4 tiles (the launch's tail).
+// NTH = 128 at step 10, W = 24 (wave_fast_narrow_kernel): the headline tile of 256 x 12 slots cut as 128 x 24, for
+// plane-fed peaks-only passes.  K is then touched in qwords (a 24-byte lane stride: three qwords, odd), the incoming
+// counts and the LAG % W counts of the lag sums come from one run of four qwords, and phase 4b is the per-thread form.
 //
 //   phase 1  tile bytes HBM -> registers (16 B/lane, coalesced; NT: the first and last row with
 //            plain loads -- they hold / leave the halo -- the rows between with the streaming hint)
@@ -489,7 +492,12 @@ template <int W, int SIZE, int STEP, int LAG, bool NT, int NTH = 256, bool PLANE
 // dwords in SGPRs at wave start, so the tile descriptor's load does not wait for a scalar load of
 // the arguments first (two dependent round trips before a workgroup's first sequence load -> one).
 __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t *const seq_p, const WaveArgs &a) {
-    static_assert(W % 4 == 0 && W <= 28 && (((W / 4) & 1) == 1 || W == 8), "W/4 odd (LDS bank stride), or W = 8 (64-bit reads); one mask bit per window");
+    static_assert(W % 4 == 0 && W <= 28 && (((W / 4) & 1) == 1 || W == 8 || W == 24),
+                  "W/4 odd (LDS bank stride), or W = 8 / 24 (64-bit accesses, an odd number of qwords between lanes); one mask bit per window");
+    // W = 24 (the narrow body of the headline tile): K is touched in whole qwords, three per lane.  The qwords that hold
+    // the incoming counts start at K byte 24 t + 96, which is the byte LAG % W counts begin at too: built for LAG = 100.
+    constexpr bool QW = W == 24;
+    static_assert(!QW || LAG == 100, "W = 24: the 64-bit K accesses of phase 3 assume lag 100");
     static_assert((SIZE == 0) == (STEP == 0) && (LAG == 0 || STEP != 0), "bake size and step together; lag only with them");
     // NTH threads per workgroup.  256 everywhere except the step-1 kernels, which may run a tile per one or two
     // waves (NTH = 64 / 128, W > 12, baked): every barrier of the tile then waits for fewer waves (see
@@ -640,6 +648,19 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
                 if constexpr (SIZE % 32 != 0) k += __popc(r[SIZE / 32] & ((1u << (SIZE % 32)) - 1u));
                 uint32_t packed = k;
                 uint32_t s1 = 0, s2 = 0;                                  // block sums for phase 3
+                // four counts to K slots idx0 + j4 ..; W = 24 (a 6-dword lane stride: two lanes a bank with dword
+                // stores): the even dword of a pair waits for the odd one and both leave as one 64-bit store
+                uint32_t held = 0;
+                auto put = [&](uint32_t j4, uint32_t four) {
+                    if constexpr (QW) {
+                        if ((j4 & 4u) == 0u)
+                            held = four;
+                        else if (idx0 + j4 - 4u < nK)
+                            reinterpret_cast<uint2 *>(K)[(idx0 + j4 - 4u) >> 3] = make_uint2(held, four);
+                    } else {
+                        if (idx0 + j4 < nK) reinterpret_cast<uint32_t *>(K)[(idx0 + j4) >> 2] = four;
+                    }
+                };
 #pragma unroll
                 for (uint32_t j = 1; j < RUN; ++j) {
                     k += __popc(field((uint32_t)SIZE + (j - 1u) * (uint32_t)STEP));
@@ -650,7 +671,7 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
                         // although it is three instructions per store: the load phase of the OTHER tiles on the CU
                         // grows from 6,250 to 9,770 cycles, everything else stays; gpurun_out/r3_stamps_ab3.txt.
                         // Yield points put into the z-score loop instead do nothing, profiles/r03_step1_valu_attempts.txt.)
-                        if (idx0 + j - 4u < nK) reinterpret_cast<uint32_t *>(K)[(idx0 + j - 4u) >> 2] = packed;
+                        put(j - 4u, packed);
                         s1 = __builtin_amdgcn_udot4(packed, 0x01010101u, s1, false);
                         s2 = __builtin_amdgcn_udot4(packed, packed, s2, false);
                         packed = k;
@@ -658,7 +679,7 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
                         packed |= k << (8u * (j & 3u));
                     }
                 }
-                if (idx0 + RUN - 4u < nK) reinterpret_cast<uint32_t *>(K)[(idx0 + RUN - 4u) >> 2] = packed;
+                put(RUN - 4u, packed);
                 s1 = __builtin_amdgcn_udot4(packed, 0x01010101u, s1, false);
                 s2 = __builtin_amdgcn_udot4(packed, packed, s2, false);
                 PS[tid] = make_uint2(s1, s2);   // slots past nK only reach windows past the tile's end
@@ -727,7 +748,9 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
 
     // ---- phase 3: rolling sums + decision, W consecutive windows per thread ---
     const bool want_peaks = (a.flags & GAMS_WAVE_PEAKS) != 0;
-    const bool want_dense = (a.flags & GAMS_WAVE_DENSE) != 0;
+    // (W = 24: peaks only -- wave_select_body refuses plans with dense rows, and the narrow launch's LDS carve ends
+    // behind RK, without SG; the dense phase is compiled out of that body)
+    const bool want_dense = !QW && (a.flags & GAMS_WAVE_DENSE) != 0;
     const uint32_t base = tid * (uint32_t)W;        // K slot of the outgoing count of window q = 0
     uint32_t crest = 0, trough = 0;                  // one bit per owned window
     uint32_t pend = 0;                               // windows whose decision sits inside the guard band
@@ -738,8 +761,28 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
         // allocation and their decisions are masked off.
         const uint32_t bw = base >> 2;               // dword index (W % 4 == 0)
         uint32_t og[WD];                             // outgoing counts K[base + q]
+        // W = 24: K bytes [24 t + 96, 24 t + 128) as four qwords -- dword 0 holds the LAG % W = 4 counts that close the
+        // lag sums, dwords 1..7 are in[]
+        uint32_t kq[QW ? 8 : 1];
+        if constexpr (QW) {
+            const uint2 *const K2 = reinterpret_cast<const uint2 *>(K) + tid * 3u;
 #pragma unroll
-        for (int d = 0; d < WD; ++d) og[d] = KW[bw + d];
+            for (int d = 0; d < 3; ++d) {
+                const uint2 t = K2[d];
+                og[2 * d] = t.x;
+                og[2 * d + 1] = t.y;
+            }
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                const uint2 t = K2[12 + d];
+                kq[2 * d] = t.x;
+                kq[2 * d + 1] = t.y;
+            }
+        } else {
+            (void)kq;
+#pragma unroll
+            for (int d = 0; d < WD; ++d) og[d] = KW[bw + d];
+        }
         // S1, S2 over K[base, base+lag)
         uint32_t S1 = 0, S2 = 0;
         const uint32_t nfull = lag >> 2;
@@ -759,9 +802,14 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
                         S1 += ps.x;
                         S2 += ps.y;
                     }
+                    static_assert(!QW || (FULL * (uint32_t)WD == 24u && REM == 4u), "W = 24: kq[0] closes the lag sums");
 #pragma unroll
                     for (uint32_t d = 0; d < (REM + 3u) / 4u; ++d) {
-                        uint32_t x = KW[bw + FULL * (uint32_t)WD + d];
+                        uint32_t x;
+                        if constexpr (QW)
+                            x = kq[0];
+                        else
+                            x = KW[bw + FULL * (uint32_t)WD + d];
                         if (d == REM / 4u && (REM & 3u)) x &= (1u << (8u * (REM & 3u))) - 1u;
                         S1 = __builtin_amdgcn_udot4(x, 0x01010101u, S1, false);
                         S2 = __builtin_amdgcn_udot4(x, x, S2, false);
@@ -803,7 +851,10 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
         }
         {
             const uint32_t ib = bw + nfull;
-            if constexpr (LAG != 0 && (LAG & 3) == 0) {          // whole dwords (v_alignbyte by 0 is not folded away)
+            if constexpr (QW) {                                  // dwords 25 .. 31 behind the thread's first slot
+#pragma unroll
+                for (int d = 0; d <= WD; ++d) in[d] = kq[d + 1];
+            } else if constexpr (LAG != 0 && (LAG & 3) == 0) {   // whole dwords (v_alignbyte by 0 is not folded away)
 #pragma unroll
                 for (int d = 0; d <= WD; ++d) in[d] = KW[ib + d];
             } else {
@@ -828,16 +879,26 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
         // grows by at most `size` per window): two fma's per thread instead of two per window.
         // S1, S2 and the counts are carried as f32 from here on: integers below 2^24, every
         // update exact (S2 drops the outgoing square before it takes the incoming one).
+        // W = 24: the bound is taken again at q = 12, from the S1 of that window -- each half has the band of the
+        // W = 12 thread that owns the same twelve windows, so both cuts of the tile send the same windows down the exact path.
+        constexpr uint32_t WB = QW ? (uint32_t)W / 2u : (uint32_t)W;      // windows a bound on S1 covers
         uint32_t sigm = 0, nosm = 0, dnm = 0;
         const float nf = (float)lag, aA = a.aA, aB = a.aB;
-        const float s1ub = (float)(S1 + (uint32_t)W * size);
-        const float cA = __builtin_fmaf(a.gA1, s1ub, a.gA0), cB = __builtin_fmaf(a.gB1, s1ub, a.gB0);
+        const float s1ub = (float)(S1 + WB * size);
+        float cA = __builtin_fmaf(a.gA1, s1ub, a.gA0), cB = __builtin_fmaf(a.gB1, s1ub, a.gB0);
         float S1f = (float)S1, S2f = (float)S2;
         float kinf = (float)(in[0] & 0xFFu);
 #pragma unroll
         for (int q = 0; q < W; ++q) {
             const float koutf = (float)((og[q >> 2] >> (8 * (q & 3))) & 0xFFu);              // v_cvt_f32_ubyteN
             const float kkf = (float)((in[(q + 1) >> 2] >> (8 * ((q + 1) & 3))) & 0xFFu);
+            if constexpr (QW) {
+                if (q == (int)WB) {
+                    const float ub = S1f + (float)(WB * size);           // integers below 2^24: exact
+                    cA = __builtin_fmaf(a.gA1, ub, a.gA0);
+                    cB = __builtin_fmaf(a.gB1, ub, a.gB0);
+                }
+            }
             uint32_t xs, xn, dn;
             z_decide(nf, kkf, S1f, S2f, aA, aB, cA, cB, xs, xn, dn);
             // one bit per test, shifted in MSB first: (acc << 1) | sign(x) is a single v_alignbit
@@ -977,12 +1038,14 @@ __device__ __forceinline__ void wave_fast_tile(const WaveTile tl, const uint8_t 
     // owner (six-step search over the wave's ranks), its window (the n-th set bit of the owner's
     // mask) and stores 16 B next to its neighbours': a fixed ~80 instructions per 256 records.
     // 384 Mb at step 1: 361 -> 336 us; at step 10 the dealt-out form is no faster (27.4 -> 27.1 us
-    // on 120 Mb, 64.8 -> 65.7 on 384 Mb: the LDS search lengthens every workgroup's life), hence W.
+    // on 120 Mb, 64.8 -> 65.7 on 384 Mb: the LDS search lengthens every workgroup's life).  What decides is how many
+    // peaks a thread holds, i.e. the step: the W = 24 body of the step-10 tile takes the per-thread form too.
     if (want_peaks) {
         const uint32_t both = crest | trough;
         const uint32_t mine = (uint32_t)__popc(both);
         gams_peak_t *const region = a.peaks + (size_t)blockIdx.x * a.tile_cap;
-        if constexpr (W <= 12) {
+        constexpr bool kFewPeaksAThread = W <= 12 || STEP >= 10;
+        if constexpr (kFewPeaksAThread) {
             uint32_t tot;
             const uint32_t ex = block_excl_scan_256<uint32_t, NTH>(mine, scr, tot);
             if (tid == 0) a.tile_cnt[blockIdx.x] = tot;
@@ -1079,6 +1142,19 @@ __global__ __launch_bounds__(256, 8) void wave_fast_taper_kernel(const WaveTile 
         wave_fast_pick<8, SIZE, STEP, LAG, NT>(tl, seq_p, a);
     else
         wave_fast_pick<4, SIZE, STEP, LAG, NT>(tl, seq_p, a);
+}
+
+// The narrow body of the headline tile (wave_select_body): the (12, 100, 10, 100, 256) tile -- 3,072 K slots, 2,971
+// windows -- cut as 128 threads x 24 windows.  Same tile table, slots and arguments as wave_fast_kernel<12, 100, 10,
+// 100, NT, 256>; what a thread does once, whatever W is (tile setup, the plane copy, the lag sums, the masks, the scan
+// of phase 4b: about 140 of its 490 vector instructions at W = 12), is spread over twice the windows, and a barrier
+// waits for two waves.  Plane-fed passes only: no byte body, and the plane is read with plain loads, so no NT half.
+// Peaks only: the body has no dense phase (a.flags' GAMS_WAVE_DENSE is ignored) and its LDS carve no SG -- the host
+// launches it for plans without dense rows alone (wave_select_body).
+__global__ __launch_bounds__(128, 8) void wave_fast_narrow_kernel(const WaveTile *const tiles_p, const uint8_t *const seq_p,
+                                                                  const WaveArgs a) {
+    const WaveTile tl = tiles_p[blockIdx.x];
+    wave_fast_tile<24, 100, 10, 100, false, 128, true>(tl, seq_p, a);
 }
 
 // ---- parameters whose halo does not fit a tile (large step or lag): no tiling ---------------

@@ -21,7 +21,8 @@ namespace {
 //   SIZE, STEP, LAG = 0: size and step baked, the lag an argument (`--lag N` next to the default size: the reference's own
 //                        benchmark runs 100 / 5 / 200 and 100 / 20 / 50, doc/benchmark/Atha.md:55,276-280)
 // Beside them: wave_fast_taper_kernel<100, 10, 100, NT> (the tapered table of the (12, 100, 10, 100, 256) entry) and
-// wave_tile_kernel<KT, WIDE> for KT = unsigned char / unsigned short, WIDE = false / true.
+// wave_tile_kernel<KT, WIDE> for KT = unsigned char / unsigned short, WIDE = false / true; and wave_fast_narrow_kernel,
+// the (12, 100, 10, 100, 256) tile as 128 threads x 24 windows (wave_select_body below decides who takes it).
 #define WAVE_FAST_INSTANCES(X)                                                                        \
     X(20, 0, 0, 0, 256) X(12, 0, 0, 0, 256) X(8, 0, 0, 0, 256) X(4, 0, 0, 0, 256)                     \
     X(28, 100, 1, 100, 64) X(28, 100, 1, 100, 128) X(28, 100, 1, 100, 256)                            \
@@ -263,6 +264,32 @@ inline bool wave_select(const WaveSelectIn &in, WaveSelection &out) {
     out.lds_bytes = wave_lds_bytes(out.max_chunks, out.max_win, out.wide, out.k16);
     if (out.lds_bytes > 160 * 1024) return go_direct();
     return true;
+}
+
+// The narrow body of the headline tile: the tile of the (12, 100, 10, 100, 256) entry -- 3,072 K slots, 2,971 windows --
+// is also 128 threads x 24 windows, so a plan of that entry may run its plane-fed passes in wave_fast_narrow_kernel
+// (two waves a tile, half the per-thread fixed work per window) over the very same tile table, slots and readers.
+struct WaveBody {
+    bool narrow = false;          // plane-fed passes of this plan take wave_fast_narrow_kernel
+    uint32_t nth = 0, w = 0;      // its threads per workgroup and windows per thread
+    size_t lds_bytes = 0;         // its carve: PS and RK for 128 threads (sixteen workgroups fit a CU's 160 KB)
+};
+constexpr int kWaveNarrowW = 24, kWaveNarrowNth = 128;
+
+// Whether the plan that wave_select() answered `sel` for runs the narrow body, and that body's launch shape.  Only
+// the headline entry as the library chose it: peaks only and influence 1 (the dense rows want a whole workgroup's
+// stores, see narrow_ok above), no thread-count request, no taper (its W = 8 / W = 4 tiles have no narrow form).
+inline WaveBody wave_select_body(const WaveSelectIn &in, const WaveSelection &sel) {
+    WaveBody b;
+    if (sel.family != kWaveFamFast || sel.entry < 0 || sel.taper) return b;
+    const WaveInstance &e = kWaveFast[sel.entry];
+    if (!(e.w == 12 && e.size == 100 && e.step == 10 && e.lag == 100 && e.nth == 256)) return b;
+    if ((in.flags & GAMS_WAVE_DENSE) || in.serial || in.nth_req != 0) return b;
+    b.narrow = true;
+    b.nth = (uint32_t)kWaveNarrowNth;
+    b.w = (uint32_t)kWaveNarrowW;
+    b.lds_bytes = wave_fast_lds_bytes(sel.max_chunks, b.w, (uint32_t)e.lag, false, b.nth);
+    return b;
 }
 
 // the tile kernel of a selection, spelled the way rocprofv3 prints the instantiation

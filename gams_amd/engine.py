@@ -330,6 +330,16 @@ class WavePlan:
         self.eng.check(self.eng.lib.gams_wave_plan_last_input(self.eng.h, self.p, C.byref(v)))
         return int(v.value)
 
+    def set_body(self, mode):
+        """the body of a headline plan's plane-fed passes: _lib.WAVE_BODY_AUTO / _WIDE (256 x 12) / _NARROW (128 x 24)"""
+        self.eng.check(self.eng.lib.gams_wave_plan_set_body(self.eng.h, self.p, mode))
+
+    def last_body(self):
+        """the body the most recently queued pass ran: _lib.WAVE_BODY_WIDE or _lib.WAVE_BODY_NARROW"""
+        v = C.c_int()
+        self.eng.check(self.eng.lib.gams_wave_plan_last_body(self.eng.h, self.p, C.byref(v)))
+        return int(v.value)
+
     def select(self, age):
         """point peaks()/dense()/exact_count() at the run `age` runs before the most recent one"""
         self.eng.check(self.eng.lib.gams_wave_plan_select(self.eng.h, self.p, age))

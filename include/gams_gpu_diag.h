@@ -91,6 +91,20 @@ int gams_wave_stamps_raw(gams_gpu_t *h, gams_wave_plan_t *p, uint64_t *out, uint
 int gams_wave_plan_set_input(gams_gpu_t *h, gams_wave_plan_t *p, int mode);
 /* the input the plan's most recently queued pass took: GAMS_WAVE_INPUT_BYTES or GAMS_WAVE_INPUT_PLANE */
 int gams_wave_plan_last_input(gams_gpu_t *h, gams_wave_plan_t *p, int *input);
+/* The body the plane-fed passes of a headline plan run (size 100, step 10, lag 100, peaks only, influence 1, the
+ * library's own tile and thread count, no taper).  The tile of wave_fast_kernel<12, 100, 10, 100, NT, 256> -- 3,072
+ * count slots -- is also 128 threads x 24 windows: GAMS_WAVE_BODY_NARROW launches wave_fast_narrow_kernel (that is the
+ * name rocprofv3 --kernel-trace prints for it; it has no template arguments) over the same tile table, with workgroups
+ * of two waves; GAMS_WAVE_BODY_WIDE keeps the 256-thread kernel; GAMS_WAVE_BODY_AUTO (the default) is the library's
+ * choice.  gams_wave_plan_kernel_name names the list entry the plan selected either way.  A forced NARROW on a plan
+ * without that body, or on a pass that reads the bytes (stale plane, forced bytes), fails the run with GAMS_ESTATE.
+ * Results are identical; for tests and A/B runs. */
+#define GAMS_WAVE_BODY_AUTO 0
+#define GAMS_WAVE_BODY_WIDE 1
+#define GAMS_WAVE_BODY_NARROW 2
+int gams_wave_plan_set_body(gams_gpu_t *h, gams_wave_plan_t *p, int mode);
+/* the body the plan's most recently queued pass ran: GAMS_WAVE_BODY_WIDE (every kernel but the narrow one) or _NARROW */
+int gams_wave_plan_last_body(gams_gpu_t *h, gams_wave_plan_t *p, int *body);
 /* gams_gc_plane with the body named: the AVX2 one (GAMS_EUNSUPPORTED on a CPU without it), the portable
  * 64-bit one, or the library's choice.  Every body writes the same bytes. */
 #define GAMS_GC_BODY_AUTO 0
