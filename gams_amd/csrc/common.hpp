@@ -229,6 +229,38 @@ void gams_launch_range_gc_cols(const gams_seqset_t *s, const unsigned long long 
                                const int32_t *chr_start, const uint32_t *rctg, const uint32_t *rs, const uint32_t *re,
                                uint32_t n, float *gc, hipStream_t st);
 
+// sw.hip, for text.hip (gams_gpu_sw_feature_text): stages 2-5 of that entry over device columns -- the rows of every
+// feature (sw_geometry), their 64-bit prefix and the first row of every interval, one read-back of the total and the
+// flags, sw_kernel, and the text with the ids composed on the device.  Interval i of the ctg index owns features
+// [bucket_off[i], bucket_off[i + 1]) of fs / fe / fctg (device, nf entries; fctg[f] = i), in file order.
+struct SwColsJob {
+    gams_seqset_t *s;                           // NULL without GAMS_SW_GC; its gc index exists (gams_seqset_gcindex)
+    uint32_t n_ctg, nf;
+    const int32_t *fs, *fe;                     // device
+    const uint32_t *fctg;                       // device
+    const unsigned long long *d_bucket_off;     // device, n_ctg + 1
+    const unsigned long long *bucket_off;       // host, n_ctg + 1
+    const uint32_t *ctg_index;                  // host, per interval: the seqset slot (UINT32_MAX: none)
+    const int32_t *chr_start, *chr_end;         // host, per interval
+    int32_t size, max, resize;
+    uint32_t actions;
+    const gams_index_t *rg_ix;                  // GAMS_SW_COUNT
+    const uint32_t *rg_group;                   // host, per interval
+    const uint32_t *igrp;                       // device, per interval: its group of the ctg index = its chromosome name
+    const unsigned long long *chr_off, *id_off; // device: the name tables' offsets (chr_names by group, ctg_ids by interval)
+    const char *chr_bytes, *id_bytes;
+    uint32_t max_chr, max_id;                   // the longest name of each table, in bytes
+    // device, 3 words: [0] receives the rows; [1] != 0: a kept feature has its middle outside its ctg, [2] = the
+    // smallest such line number (both written by the caller's gather, queued in front)
+    unsigned long long *words;
+};
+// the timed pairs of the handle (gams_gpu::kq) these stages record: behind the range loader's lines .. order (0 .. 6)
+enum : int { SWF_GATHER = 7, SWF_GEOM, SWF_ROWS, SWF_TLEN, SWF_TWRITE, SWF_STAGES };
+// *text (the handle's page-locked sw text, valid until the next sw call), text_off[n_ctg + 1], *n_rows.  GAMS_EINVAL for
+// the flag in words[1] (the message names the line), GAMS_EUNSUPPORTED for what the formatter does not cover.
+int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
+                        uint64_t *n_rows);
+
 // 16 bytes of sequence that this kernel will not read again: non-temporal load (global_load ... nt).
 // A pure streaming read runs at 7.06 TB/s with the hint, 6.3 TB/s without (profiles/r02_stream_read.txt).
 __device__ __forceinline__ uint4 load_once16(const uint4 *p) {

@@ -443,6 +443,13 @@ struct SwTextArgs {
     unsigned long long *words;         // [0] = all bytes, [1] = flag (a value this formatter does not cover), [2 + k] = first byte of ctg k
     uint32_t gc;                       // print the four statistics (else four empty fields)
     const int32_t *cnt;                // per row rg_count (nullptr: the field stays empty)
+    // gams_gpu_sw_feature_text: the id is composed here, "feature:" + the id of the row's interval + ':' + its 1-based
+    // number among the interval's features, and the chromosome is the name of the interval's group; ids / id_off /
+    // names / name_off above are unused
+    uint32_t dev_ids;
+    const unsigned long long *cid_off, *chr_off;   // ctg_ids by interval, chr_names by group
+    const char *cid_bytes, *chr_bytes;
+    const uint32_t *igrp;                          // per interval: its group
 };
 
 struct SwRowCtx {
@@ -467,12 +474,26 @@ __device__ __forceinline__ SwRowCtx sw_row_ctx(const SwTextArgs &a, uint64_t r, 
 __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r, char *p, bool *bad) {
     const gams_sw_row_t w = a.rows[r];
     const SwRowCtx c = sw_row_ctx(a, r, w);
-    const uint32_t id0 = a.id_off[c.f], idn = a.id_off[c.f + 1u] - id0;
-    const uint32_t nm0 = a.name_off[c.k], nmn = a.name_off[c.k + 1u] - nm0;
+    const char *id, *nm;
+    uint32_t idn, nmn, num = 0u;                         // num: the feature's number behind a composed id
+    if (a.dev_ids) {
+        const unsigned long long i0 = a.cid_off[c.k], g0 = a.chr_off[a.igrp[c.k]];
+        id = a.cid_bytes + i0;
+        idn = (uint32_t)(a.cid_off[c.k + 1u] - i0);
+        nm = a.chr_bytes + g0;
+        nmn = (uint32_t)(a.chr_off[a.igrp[c.k] + 1u] - g0);
+        num = w.feature + 1u;                            // feature.rs:74-86: from 1 on a fresh cnt:feature:
+    } else {
+        id = a.ids + a.id_off[c.f];
+        idn = a.id_off[c.f + 1u] - a.id_off[c.f];
+        nm = a.names + a.name_off[c.k];
+        nmn = a.name_off[c.k + 1u] - a.name_off[c.k];
+    }
     if (w.start < 0 || w.end < 0 || w.distance < 0 || (uint32_t)w.type > 2u) *bad = true;
     const uint32_t st = (uint32_t)w.start, en = (uint32_t)w.end, di = (uint32_t)w.distance;
     if (!p) {
         uint32_t n = 3u + idn + 1u + dec_digits(c.serial) + 1u + nmn + 1u + dec_digits(st);
+        if (num) n += 8u + 1u + dec_digits(num);
         if (en != st) n += 1u + dec_digits(en);
         n += 1u + 1u + 1u + dec_digits(di) + 1u;
         if (a.gc)
@@ -487,11 +508,16 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
     *q++ = 's';
     *q++ = 'w';
     *q++ = ':';
-    for (uint32_t i = 0; i < idn; ++i) *q++ = a.ids[id0 + i];
+    if (num) q = put_bytes(q, "feature:", 8u);
+    for (uint32_t i = 0; i < idn; ++i) *q++ = id[i];
+    if (num) {
+        *q++ = ':';
+        q = put_dec(q, num);
+    }
     *q++ = ':';
     q = put_dec(q, c.serial);
     *q++ = '\t';
-    for (uint32_t i = 0; i < nmn; ++i) *q++ = a.names[nm0 + i];
+    for (uint32_t i = 0; i < nmn; ++i) *q++ = nm[i];
     *q++ = ':';
     q = put_dec(q, st);
     if (en != st) {
@@ -589,6 +615,44 @@ __global__ __launch_bounds__(64) void sw_text_ctg_kernel(const SwTextArgs a) {
         off += ((unsigned long long)hi << 32) | lo;
     }
     if (lane == 0) a.words[2u + k] = (b < a.nb ? a.blk_off[b] : a.blk_off[a.nb]) + off;
+}
+
+// ---- the row offsets of gams_gpu_sw_feature_text, made on the device (what sw_host_rows walks on the host) -------------
+// 1 + n_l + n_r of every feature (window.rs:29-41) and their sum per workgroup, carried in 64 bits: 256 features of
+// 1 + 2 * max rows each pass 2^32 from max = 2^23 on
+__global__ __launch_bounds__(256) void sw_geom_kernel(const SwCtg *ctgs, const uint32_t *fctg, const int32_t *fs,
+                                                      const int32_t *fe, uint32_t nf, int32_t size, int32_t max,
+                                                      uint32_t *cnt, unsigned long long *blk) {
+    __shared__ uint64_t ws[4];
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    uint32_t n = 0;
+    if (f < nf) {
+        const SwCtg cg = ctgs[fctg[f]];
+        const SwGeom g = sw_geometry(cg.chr_start, cg.chr_end, fs[f], fe[f], size, max);
+        n = 1u + (uint32_t)g.n_l + (uint32_t)g.n_r;
+        cnt[f] = n;
+    }
+    uint64_t tot;
+    (void)block_excl_scan_256<uint64_t>((uint64_t)n, ws, tot);
+    if (threadIdx.x == 0u) blk[blockIdx.x] = tot;
+}
+
+// row_off[f] = the rows in front of feature f: the workgroup's prefix + the scan inside it; row_off[nf] = all rows
+__global__ __launch_bounds__(256) void sw_row_off_kernel(const uint32_t *cnt, const unsigned long long *blk_off, uint32_t nf,
+                                                         uint32_t nb, unsigned long long *row_off) {
+    __shared__ uint64_t ws[4];
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    uint64_t tot;
+    const uint64_t rel = block_excl_scan_256<uint64_t>(f < nf ? (uint64_t)cnt[f] : 0ull, ws, tot);
+    if (f < nf) row_off[f] = blk_off[blockIdx.x] + rel;
+    if (f == 0u) row_off[nf] = blk_off[nb];
+}
+
+// the first row of every interval (entry n_ctg = all rows): bucket_off[i] <= nf indexes row_off[nf + 1]
+__global__ __launch_bounds__(256) void sw_ctg_row_off_kernel(const unsigned long long *row_off, const unsigned long long *bucket_off,
+                                                             uint32_t n_ctg, unsigned long long *ctg_row_off) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i <= n_ctg) ctg_row_off[i] = row_off[bucket_off[i]];
 }
 
 struct SwTextReq {                       // what gams_gpu_sw_text adds to a batch call
@@ -897,6 +961,147 @@ int sw_batch_impl(const SwReq &q) {
     return GAMS_OK;
 }
 }  // namespace
+
+int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
+                        uint64_t *n_rows) {
+    const std::string who = "gpu_sw_feature_text";
+    const bool do_gc = (J.actions & GAMS_SW_GC) != 0, do_count = (J.actions & GAMS_SW_COUNT) != 0;
+    const uint32_t n_ctg = J.n_ctg, nf = J.nf;
+    hipStream_t st = h->compute;
+    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
+    // the interval table: a few KB, one copy
+    const uint32_t nbf = (nf + 255u) / 256u;
+    SwCtg *d_ctgs = nullptr;
+    uint32_t *d_cnt_f = nullptr;
+    unsigned long long *d_blk = nullptr, *d_blk_off = nullptr, *d_row_off = nullptr, *d_ctg_row_off = nullptr;
+    auto geom = [&](Carver &c) {   // ctgs | rows per feature | block sums and prefix | row_off | ctg_row_off
+        d_ctgs = c.take<SwCtg>(std::max(n_ctg, 1u));
+        d_cnt_f = c.take<uint32_t>(nf);
+        d_blk = c.take<unsigned long long>((size_t)nbf + 1);
+        d_blk_off = c.take<unsigned long long>((size_t)nbf + 1);
+        d_row_off = c.take<unsigned long long>((size_t)nf + 1);
+        d_ctg_row_off = c.take<unsigned long long>((size_t)n_ctg + 1);
+    };
+    PoolBlock g_dev(h, false), g_pin(h, true), r_dev(h, false), t_dev(h, false);
+    GAMS_TRY(h, who, g_dev.alloc(layout_bytes(geom)));
+    GAMS_TRY(h, who, g_pin.alloc(gams_align256(std::max(n_ctg, 1u) * sizeof(SwCtg))));
+    carve(g_dev.p, geom);
+    SwCtg *const h_ctgs = reinterpret_cast<SwCtg *>(g_pin.p);
+    for (uint32_t i = 0; i < n_ctg; ++i) {
+        const uint32_t slot = do_gc ? J.ctg_index[i] : UINT32_MAX;
+        const bool has = slot != UINT32_MAX && J.bucket_off[i + 1] > J.bucket_off[i];   // (checked by the caller)
+        h_ctgs[i] = SwCtg{has ? J.s->off[slot] : 0ull,
+                          has ? J.s->len[slot] : (uint32_t)((int64_t)J.chr_end[i] - J.chr_start[i] + 1),
+                          J.chr_start[i], J.chr_end[i], (uint32_t)J.bucket_off[i], do_count ? J.rg_group[i] : UINT32_MAX, 0u};
+    }
+    GAMS_TRY(h, who, hipMemcpyAsync(d_ctgs, h_ctgs, (size_t)n_ctg * sizeof(SwCtg), hipMemcpyHostToDevice, st));
+    // 2. geometry: rows per feature -> row_off, ctg_row_off
+    GAMS_TRY(h, who, stage(SWF_GEOM, true));
+    hipLaunchKernelGGL(sw_geom_kernel, dim3(nbf), dim3(256), 0, st, d_ctgs, J.fctg, J.fs, J.fe, nf, J.size, J.max, d_cnt_f, d_blk);
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_blk, nbf, d_blk_off, J.words, 0u);
+    hipLaunchKernelGGL(sw_row_off_kernel, dim3(nbf), dim3(256), 0, st, d_cnt_f, d_blk_off, nf, nbf, d_row_off);
+    hipLaunchKernelGGL(sw_ctg_row_off_kernel, dim3(n_ctg / 256u + 1u), dim3(256), 0, st, d_row_off, J.d_bucket_off, n_ctg,
+                       d_ctg_row_off);
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, stage(SWF_GEOM, false));
+    // 3. the one read-back: the rows and the flags
+    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, J.words, 3 * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    const uint64_t tot = h->pin_scratch[0];
+    if (h->pin_scratch[1])
+        return gams_fail(h, GAMS_EINVAL, who + ": the feature on line " + std::to_string(h->pin_scratch[2] + 1ull) +
+                                             " is empty or has its middle outside its ctg");
+    // 4. the rows
+    gams_sw_row_t *d_rows = nullptr;
+    int32_t *d_cnt = nullptr;
+    auto rows = [&](Carver &c) {
+        d_rows = c.take<gams_sw_row_t>(std::max<uint64_t>(tot, 1));
+        d_cnt = do_count ? c.take<int32_t>(std::max<uint64_t>(tot, 1)) : nullptr;
+    };
+    GAMS_TRY(h, who, r_dev.alloc(layout_bytes(rows)));
+    carve(r_dev.p, rows);
+    SwReq q{};
+    q.h = h;
+    q.s = J.s;
+    q.size = J.size;
+    q.max = J.max;
+    q.resize = J.resize;
+    q.actions = J.actions;
+    q.rg_ix = do_count ? J.rg_ix : nullptr;
+    SwCols d{};
+    d.ctgs = d_ctgs;
+    d.fs = const_cast<int32_t *>(J.fs);
+    d.fe = const_cast<int32_t *>(J.fe);
+    d.fctg = const_cast<uint32_t *>(J.fctg);
+    d.row_off = reinterpret_cast<uint64_t *>(d_row_off);
+    GAMS_TRY(h, who, stage(SWF_ROWS, true));
+    const int rc = sw_launch(q, nf, tot, d, d_rows, d_cnt);
+    if (rc != GAMS_OK) return rc;
+    GAMS_TRY(h, who, stage(SWF_ROWS, false));
+    // 5. the text: lengths, block prefix, rows at their offsets, the first byte of every interval
+    const uint32_t nb = (uint32_t)((tot + kSwTextBlock - 1) / kSwTextBlock);
+    const uint64_t per_row = 8ull + J.max_id + 1ull + 10ull + J.max_chr + (do_count ? 112ull : 96ull);
+    const uint64_t text_cap = std::max<uint64_t>(tot * per_row, 4096);
+    const size_t n_words = (size_t)n_ctg + 3;
+    SwTextArgs ta{};
+    unsigned long long *blk_off = nullptr;
+    auto txt = [&](Carver &c) {   // row lengths | block lengths and offsets | words | text
+        ta.len = c.take<uint32_t>(std::max<uint64_t>(tot, 1));
+        ta.blk_len = c.take<uint32_t>(std::max(nb, 1u));
+        ta.blk_off = blk_off = c.take<unsigned long long>((size_t)nb + 1);
+        ta.words = c.take<unsigned long long>(n_words);
+        ta.text = c.take<char>(text_cap);
+    };
+    GAMS_TRY(h, who, t_dev.alloc(layout_bytes(txt)));
+    carve(t_dev.p, txt);
+    ta.rows = d_rows;
+    ta.n_rows = tot;
+    ta.ctgs = d_ctgs;
+    ta.ctg_row_off = reinterpret_cast<const uint64_t *>(d_ctg_row_off);
+    ta.n_sel = n_ctg;
+    ta.feat_row_off = reinterpret_cast<const uint64_t *>(d_row_off);
+    ta.nb = nb;
+    ta.text_cap = text_cap;
+    ta.gc = do_gc ? 1u : 0u;
+    ta.cnt = d_cnt;
+    ta.dev_ids = 1u;
+    ta.cid_off = J.id_off;
+    ta.cid_bytes = J.id_bytes;
+    ta.chr_off = J.chr_off;
+    ta.chr_bytes = J.chr_bytes;
+    ta.igrp = J.igrp;
+    GAMS_TRY(h, who, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), st));
+    GAMS_TRY(h, who, stage(SWF_TLEN, true));
+    if (nb) {
+        hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, st, ta);
+        hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, ta.blk_len, nb, blk_off, ta.words, 0u);
+    }
+    GAMS_TRY(h, who, stage(SWF_TLEN, false));
+    GAMS_TRY(h, who, stage(SWF_TWRITE, true));
+    if (nb) {
+        hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, st, ta);
+        hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_ctg + 1), dim3(64), 0, st, ta);
+    }
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, stage(SWF_TWRITE, false));
+    // the final read-back, as in gams_gpu_sw_text: the words (total, flag, per-interval offsets), which say the text's
+    // size, then the text into the handle's page-locked buffer
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_words, &h->sw_words_bytes, n_words * 8, n_words * 8));
+    GAMS_TRY(h, who, hipMemcpyAsync(h->sw_words, ta.words, n_words * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    const uint64_t bytes = h->sw_words[0];
+    if (h->sw_words[1] != 0 || bytes > text_cap)
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a value this formatter does not cover (a statistic of 1000 or more, a "
+                                                     "negative coordinate): use the host path");
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_text, &h->sw_text_bytes, bytes, bytes + bytes / 8 + 4096));
+    if (bytes) GAMS_TRY(h, who, hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    *text = bytes ? h->sw_text : "";
+    *text_bytes = bytes;
+    *n_rows = tot;
+    for (uint32_t i = 0; i <= n_ctg; ++i) text_off[i] = nb ? h->sw_words[2u + i] : 0ull;
+    return GAMS_OK;
+}
 
 extern "C" int gams_gpu_sw_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                                  const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,

@@ -10,6 +10,8 @@
 //   gams_index_create_range_text   the rg index of the file and the ctg -> group table
 // and, on the loader's stages, `gams peak` (utils.rs:83-116 read_peak, then peak.rs:41-160):
 //   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
+// and, on the loader itself, `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
+//   gams_gpu_sw_feature_text       the bytes of one range file -> the sw rows of its features (stages 2-5 in sw.hip)
 //
 // Pipeline (one handle, the compute stream):
 //   1. one copy of the bytes into a cached device buffer, padded with spaces to 16 B and 16 B beyond;
@@ -54,6 +56,7 @@ struct gams_names {
     NameTab t{};
     uint8_t *arena = nullptr;
     size_t arena_bytes = 0;
+    uint32_t max_len = 0;            // the longest name, in bytes (bounds a row that prints one)
 };
 
 // What the text entries keep on the handle: the device copy of the input (grows, cached) and the page-locked
@@ -1317,6 +1320,187 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
     *n_rows = n_kept;
     return GAMS_OK;
 }
+
+
+// ---- `gams sw` from the bytes of a feature file (feature.rs:50-54 read_range, then sw.rs:132-191) ---------------------
+// The range loader as it is (key (ctg, line): the kept lines of a ctg in file order, which is the order feature.rs:74-86
+// numbers them in), then, one lane per kept feature, the gather below; the stages behind it are sw.hip's
+// (gams_launch_sw_cols): the rows per feature and their prefix, sw_kernel over these columns, and the text with
+// "feature:{ctg id}:{k}" composed on the device.
+static_assert(SWF_GATHER == RG_GATHER, "the sw stages continue the loader's stopwatch behind `order`");
+
+struct SwGather {
+    const unsigned long long *key;            // sorted: the first n_kept are the kept lines in (ctg, line) order
+    unsigned long long line_mask;
+    const uint32_t *qs, *qe;                  // per line
+    uint32_t n_kept, n_ctg;
+    const int32_t *cs, *ce;                   // per interval
+    const CountGroup *groups;                 // the ctg index's groups: group g owns intervals [off, off + n)
+    uint32_t n_groups;
+    int32_t *fs, *fe;                         // per kept feature
+    uint32_t *fctg;
+    uint32_t *igrp;                           // per interval: its group (UINT32_MAX: none owns it)
+    unsigned long long *words;                // [1] a kept feature leaves its ctg with its middle, [2] the smallest such line
+};
+
+__global__ __launch_bounds__(256) void sw_gather_kernel(const SwGather a) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < a.n_kept) {
+        const unsigned long long key = a.key[k];
+        const uint32_t i = (uint32_t)(key & a.line_mask);
+        const uint32_t c = (uint32_t)(key >> __popcll(a.line_mask));
+        const int64_t s = a.qs[i], e = a.qe[i];
+        a.fs[k] = (int32_t)s;
+        a.fe[k] = (int32_t)e;
+        a.fctg[k] = c;
+        // window.rs:98-110: the middle pair of the feature must be members of the ctg span (sw_host_rows on the host);
+        // located by overlap does not imply it.  Integer min: the line reported does not depend on arrival order
+        const int64_t flen = e - s + 1, half = flen / 2;
+        const int64_t mid_l = half == 0 ? s : s + half - 1, mid_r = half == 0 ? s : s + half;
+        if (flen < 1 || mid_l < a.cs[c] || mid_r > a.ce[c]) {
+            a.words[1] = 1ull;
+            atomicMin(a.words + 2, (unsigned long long)i);
+        }
+    }
+    if (k < a.n_ctg) {                        // the last group that begins at or before interval k holds it
+        uint32_t lo = 0, hi = a.n_groups;
+        while (hi - lo > 1u) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.groups[mid].off <= k)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        a.igrp[k] = a.n_groups && k - a.groups[lo].off < a.groups[lo].n ? lo : UINT32_MAX;
+    }
+}
+
+struct SwFeatJob {
+    gams_seqset_t *s;
+    const gams_index_t *ctg_ix;
+    const gams_names_t *chr, *ids;
+    const uint32_t *ctg_index;
+    const int32_t *chr_start, *chr_end;
+    int32_t size, max, resize;
+    uint32_t actions;
+    const gams_index_t *rg_ix;
+    const uint32_t *rg_group;
+};
+
+int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_t n_bytes, const char **text,
+                   uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_features, uint64_t *n_rows) {
+    const std::string who = "gpu_sw_feature_text";
+    const uint64_t n_ctg = J.ctg_ix->m;
+    const bool do_gc = (J.actions & GAMS_SW_GC) != 0;
+    *text = "";
+    *text_bytes = 0;
+    *n_features = 0;
+    *n_rows = 0;
+    memset(text_off, 0, (n_ctg + 1) * 8);
+    for (uint64_t c = 0; c < n_ctg; ++c)
+        if (J.chr_end[c] < J.chr_start[c]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg ends before it starts");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    if (do_gc) {
+        const int rc_gc = gams_seqset_gcindex(h, J.s);             // GAMS_ESTATE for a plane-only seqset
+        if (rc_gc != GAMS_OK) return rc_gc;
+    }
+    while (h->kq.size() < (size_t)SWF_STAGES) {
+        hipEvent_t a = nullptr, b = nullptr;
+        GAMS_HIP(h, hipEventCreate(&a));
+        GAMS_HIP(h, hipEventCreate(&b));
+        h->kq.emplace_back(a, b);
+    }
+    return rg_load(h, who, J.ctg_ix, J.chr, bytes, n_bytes, true, [&](const RgCols &C, auto stage) -> int {
+        *n_features = C.n_kept;
+        if (C.n_kept == 0) {
+            if (C.ran) rg_timed(h, RG_ORDER + 1);
+            return GAMS_OK;
+        }
+        // one thread per (feature, slot), as sw_check bounds it
+        const uint64_t threads = C.n_kept * (1u + 2u * (uint64_t)J.max);
+        if ((threads + 255) / 256 > 0x7fffffffull)
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": too many feature slots for one launch");
+        if (do_gc)
+            for (uint64_t c = 0; c < n_ctg; ++c) {
+                if (C.bucket_off[c + 1] == C.bucket_off[c]) continue;
+                const uint32_t slot = J.ctg_index[c];
+                if (slot == UINT32_MAX) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with features has no sequence in the seqset");
+                if (slot >= J.s->n_ctg || (int64_t)J.s->len[slot] != (int64_t)J.chr_end[c] - J.chr_start[c] + 1)
+                    return gams_fail(h, GAMS_EINVAL, who + ": ctg_index does not name a sequence of the ctg's length");
+            }
+        const uint32_t K = (uint32_t)C.n_kept, nc = (uint32_t)n_ctg;
+        hipStream_t st = h->compute;
+        PoolBlock d_cols(h, false), pin(h, true);
+        SwGather g{};
+        int32_t *d_cs = nullptr, *d_ce = nullptr;
+        auto cols = [&](Carver &c) {   // cs ce | fs fe fctg | igrp | words
+            d_cs = c.take<int32_t>(nc);
+            d_ce = c.take<int32_t>(nc);
+            g.fs = c.take<int32_t>(K);
+            g.fe = c.take<int32_t>(K);
+            g.fctg = c.take<uint32_t>(K);
+            g.igrp = c.take<uint32_t>(nc);
+            g.words = c.take<unsigned long long>(3);
+        };
+        GAMS_TRY(h, who, d_cols.alloc(layout_bytes(cols)));
+        carve(d_cols.p, cols);
+        const size_t b_place = 2 * gams_align256((size_t)nc * 4);       // cs | ce, as the layout places them
+        GAMS_TRY(h, who, pin.alloc(b_place));
+        int32_t *const h_cs = reinterpret_cast<int32_t *>(pin.p), *const h_ce = reinterpret_cast<int32_t *>(pin.p + b_place / 2);
+        memcpy(h_cs, J.chr_start, (size_t)nc * 4);
+        memcpy(h_ce, J.chr_end, (size_t)nc * 4);
+        GAMS_TRY(h, who, hipMemcpyAsync(d_cs, pin.p, b_place, hipMemcpyHostToDevice, st));
+        unsigned long long *const hw = h->pin_scratch;                  // words: rows, flag, smallest offending line
+        hw[0] = hw[1] = 0ull;
+        hw[2] = ~0ull;
+        GAMS_TRY(h, who, hipMemcpyAsync(g.words, hw, 3 * 8, hipMemcpyHostToDevice, st));
+        g.key = C.g.key;
+        g.line_mask = C.g.line_mask;
+        g.qs = C.g.qs;
+        g.qe = C.g.qe;
+        g.n_kept = K;
+        g.n_ctg = nc;
+        g.cs = d_cs;
+        g.ce = d_ce;
+        g.groups = J.ctg_ix->d_cgroups;
+        g.n_groups = J.ctg_ix->n_groups;
+        GAMS_TRY(h, who, stage(SWF_GATHER, true));
+        hipLaunchKernelGGL(sw_gather_kernel, dim3((std::max(K, nc) + 255u) / 256u), dim3(256), 0, st, g);
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, stage(SWF_GATHER, false));
+        // (the copy of the words must have left pin_scratch before the launcher reads back into it: same stream, in order)
+        SwColsJob S{};
+        S.s = do_gc ? J.s : nullptr;
+        S.n_ctg = nc;
+        S.nf = K;
+        S.fs = g.fs;
+        S.fe = g.fe;
+        S.fctg = g.fctg;
+        S.d_bucket_off = C.g.bucket_off;
+        S.bucket_off = C.bucket_off;
+        S.ctg_index = J.ctg_index;
+        S.chr_start = J.chr_start;
+        S.chr_end = J.chr_end;
+        S.size = J.size;
+        S.max = J.max;
+        S.resize = J.resize;
+        S.actions = J.actions;
+        S.rg_ix = J.rg_ix;
+        S.rg_group = J.rg_group;
+        S.igrp = g.igrp;
+        S.chr_off = J.chr->t.off;
+        S.chr_bytes = J.chr->t.bytes;
+        S.id_off = J.ids->t.off;
+        S.id_bytes = J.ids->t.bytes;
+        S.max_chr = J.chr->max_len;
+        S.max_id = J.ids->max_len;
+        S.words = g.words;
+        const int rc = gams_launch_sw_cols(h, S, text, text_bytes, text_off, n_rows);
+        if (rc != GAMS_OK) return rc;
+        rg_timed(h, SWF_STAGES);
+        return GAMS_OK;
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -1327,12 +1511,14 @@ int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_
     std::vector<unsigned long long> off((size_t)n + 1, 0);
     std::string bytes;
     std::unordered_set<std::string> seen;
+    size_t max_len = 0;
     for (uint32_t i = 0; i < n; ++i) {
         if (!names[i]) return gams_fail(h, GAMS_EINVAL, "names_create: null name");
         const std::string s(names[i]);
         if (!seen.insert(s).second) return gams_fail(h, GAMS_EINVAL, "names_create: duplicate name '" + s + "'");
         bytes += s;
         off[i + 1] = bytes.size();
+        max_len = std::max<size_t>(max_len, s.size());
     }
     uint32_t slots = 2;
     while (slots < 2ull * n) slots <<= 1;
@@ -1360,6 +1546,7 @@ int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_
     nm->t.bytes = reinterpret_cast<const char *>(nm->arena + b_tab + b_off);
     nm->t.mask = slots - 1u;
     nm->t.n = n;
+    nm->max_len = (uint32_t)std::min<size_t>(max_len, UINT32_MAX);
     *out = nm;
     return GAMS_OK;
 }
@@ -1523,6 +1710,33 @@ int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, co
     if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_peak_text: ctg_ids must name every interval of ctg_ix");
     return peak_run(h, PeakJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end}, bytes, n_bytes, text, text_bytes,
                     text_off, n_rows);
+}
+
+int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                             const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                             const int32_t *chr_end, const char *bytes, uint64_t n_bytes, int32_t size, int32_t max,
+                             int32_t resize, uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
+                             const char **text, uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_features,
+                             uint64_t *n_rows) {
+    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
+    if (!h || !ctg_ix || !chr_names || !ctg_ids || (ctg_ix->m && (!chr_start || !chr_end)) || (n_bytes && !bytes) || !text ||
+        !text_bytes || !text_off || !n_features || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: null argument");
+    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: unknown action bits");
+    if (do_gc && (!s || (ctg_ix->m && !ctg_index)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: GAMS_SW_GC without a seqset or the ctgs' slots");
+    if (do_count && (!rg_ix || (ctg_ix->m && !rg_group)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: GAMS_SW_COUNT without an rg index or rg groups");
+    // size or resize 1: center_resize of 1 bp is an empty span (sw_check, sw.hip)
+    if (size < 2 || max < 0 || resize < 2)
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
+    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: ctg_ids must name every interval of ctg_ix");
+    if (chr_names->t.n < ctg_ix->n_groups)
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: chr_names must name every group of ctg_ix");
+    if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw_feature_text: max beyond 2^24 windows a side");
+    return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
+                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr},
+                          bytes, n_bytes, text, text_bytes, text_off, n_features, n_rows);
 }
 
 }  // extern "C"

@@ -152,6 +152,10 @@ def load():
     L.gams_host_peak_text.restype = C.c_void_p
     L.gams_host_peak_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                       C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_sw_text.restype = C.c_void_p
+    L.gams_host_sw_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                    C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p,
+                                    C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.gams_host_gen.restype = C.c_void_p
     L.gams_host_gen.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
     L.gams_host_read_fasta.restype = C.c_void_p
@@ -383,7 +387,7 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 
 def last_operator_device():
-    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text / peak_text / gen_text of this thread made its rows on the device,
+    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text / peak_text / sw_text / gen_text of this thread made its rows on the device,
     0 if it fell back to the host"""
     return int(load().gams_host_last_operator_device())
 
@@ -662,6 +666,35 @@ def peak_text(eng, ctgs, data, seqset=None):
         slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
         p = load().gams_host_peak_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
                                        slots.ctypes.data, bytes(data), len(data), C.byref(out_len))
+    return _take_bytes(p, out_len)
+
+
+def sw_text(eng, ctgs, data, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None, seqset=None):
+    """`gams sw` over the bytes of a feature (range) file, made on the device from the bytes to the rows (the host's
+    passes where the device refuses; last_operator_device says which): the features are the kept lines of every ctg in
+    file order, "feature:{ctg_id}:{k}" from 1, as `gams feature` stores them; the rows of sw_multi over them, the ctgs
+    in id order, as bytes.  Without `seqset` the ctgs carry their bases in c["seq"], uploaded for the call (not needed
+    without the gc action); with a resident engine.SeqSet its slot i holds ctgs[i] (a ctg dict may name another in
+    c["slot"]; None: no sequence).  actions, rg_records, rg_data as for sw_multi."""
+    rg_data = _one_rg_source(rg_records, rg_data)
+    mask = sw_actions(actions)
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    out_len = C.c_uint64()
+    rg_lines = _rg_lines(rg_records) if (mask & _lib.SW_COUNT) and rg_data is None else None
+    tail = (bytes(data), len(data), size, mx, resize, mask, rg_lines, rg_data, 0 if rg_data is None else len(rg_data),
+            C.byref(out_len))
+    if seqset is None:
+        seqs = None
+        if mask & _lib.SW_GC:
+            bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
+                                         else c["seq"]) for c in ctgs]
+            seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        p = load().gams_host_sw_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, *tail)
+    else:
+        slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
+        slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
+        p = load().gams_host_sw_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
+                                     slots.ctypes.data, *tail)
     return _take_bytes(p, out_len)
 
 

@@ -1891,6 +1891,155 @@ std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::ve
     return peak_text(h, ctgs, sg.s, slots, bytes, n, device);
 }
 
+std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                    const char *bytes, size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs,
+                    const char *rg_bytes, size_t rg_n, bool *device, const TextSink *sink) {
+    if (device) *device = false;
+    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+    const bool do_gc = (a.actions & GAMS_SW_GC) != 0, do_count = (a.actions & GAMS_SW_COUNT) != 0;
+    auto done = [&](std::string &&rows) {                                // a finished string: into the sink, if there is one
+        if (!sink) return std::move(rows);
+        char *dst = (*sink)(rows.size());
+        if (!rows.empty()) std::memcpy(dst, rows.data(), rows.size());
+        return std::string();
+    };
+    if (do_gc && !seqset) throw Error(GAMS_EINVAL, "sw_text: --action gc needs a seqset");
+    if (seqset && slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "sw_text: one seqset slot per ctg");
+    if (do_count && !rgs && !rg_bytes) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
+    Locator loc(h, ctgs);
+    loc.text_tables();
+    const size_t n_ctg = loc.ctgs_.size();
+    // per interval of the ctg index (the Locator's order): seqset slot, chr_start, chr_end, rg group
+    std::vector<uint32_t> slot(std::max<size_t>(n_ctg, 1), UINT32_MAX), rg_group(std::max<size_t>(n_ctg, 1), UINT32_MAX);
+    std::vector<int32_t> cs(std::max<size_t>(n_ctg, 1), 0), ce(std::max<size_t>(n_ctg, 1), 0);
+    if (seqset)
+        for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
+    if (do_count) {                                                      // idx:rg: on the call's ctg table, once
+        if (rg_bytes)
+            loc.set_rg_index_text(rg_bytes, rg_n);
+        else
+            loc.set_rg_index(*rgs);
+    }
+    for (size_t c = 0; c < n_ctg; ++c) {
+        cs[c] = loc.ctgs_[c].chr_start;
+        ce[c] = loc.ctgs_[c].chr_end;
+        if (do_count) rg_group[c] = loc.rg_group_of(loc.ctgs_[c].id);
+    }
+    std::vector<uint64_t> off(n_ctg + 1, 0);
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, feats = 0, rows = 0;
+    const int rc = gams_gpu_sw_feature_text(h, do_gc ? seqset : nullptr, loc.ctg_ix_, loc.chr_names_, loc.ctg_ids_, slot.data(),
+                                            cs.data(), ce.data(), bytes, n, a.size, a.max, a.resize, a.actions, loc.rg_index(),
+                                            rg_group.data(), &text, &text_bytes, off.data(), &feats, &rows);
+    std::string out;
+    if (rc != GAMS_EUNSUPPORTED) {
+        check(h, rc);
+        if (device) *device = true;
+        if (!sink) {
+            out.reserve((size_t)text_bytes);
+            for (auto &kv : loc.ctg_slot_)                               // ctg-id order (sw.rs:97)
+                out.append(text + off[kv.second], (size_t)(off[kv.second + 1] - off[kv.second]));
+            return out;
+        }
+        // ... by a few host threads, a ctg at a time (one thread moves ~10 GB/s and pays every page fault of the target)
+        char *const dst = (*sink)((size_t)text_bytes);
+        std::vector<std::pair<uint32_t, uint64_t>> part;                 // (interval, where its slice goes)
+        uint64_t at = 0;
+        for (auto &kv : loc.ctg_slot_) {
+            part.emplace_back(kv.second, at);
+            at += off[kv.second + 1] - off[kv.second];
+        }
+        const unsigned T = (unsigned)std::max<uint64_t>(
+            1, std::min<uint64_t>({16, std::thread::hardware_concurrency(), (uint64_t)part.size(), text_bytes / (4u << 20) + 1}));
+        parallel_for((uint32_t)part.size(), T, [&](uint32_t k) {
+            const uint32_t c = part[k].first;
+            if (off[c + 1] > off[c]) std::memcpy(dst + part[k].second, text + off[c], (size_t)(off[c + 1] - off[c]));
+        });
+        return out;
+    }
+    // the host's passes: read_range over the lines, the ids of feature_records, the existing text entry on the same
+    // seqset (without gc no sequence is read: a seqset of the lengths alone stands in)
+    const auto ranges_of = read_range(loc, text_lines(bytes, n));
+    std::vector<uint32_t> sel, index, lens, group;
+    std::vector<int32_t> sel_start, fs, fe;
+    std::vector<uint64_t> feat_off{0};
+    std::vector<std::string> ids;
+    std::vector<std::vector<Feature>> feat_of;
+    for (auto &kv : ranges_of) {                                         // BTreeMap order = ctg id order
+        if (kv.second.empty()) continue;
+        const uint32_t c = loc.ctg_slot_.at(kv.first);
+        if (do_gc && slot[c] == UINT32_MAX) throw Error(GAMS_EINVAL, "sw_text: no sequence for " + kv.first);
+        index.push_back(do_gc ? slot[c] : (uint32_t)sel.size());
+        sel.push_back(c);
+        lens.push_back((uint32_t)(ce[c] - cs[c] + 1));
+        sel_start.push_back(cs[c]);
+        group.push_back(rg_group[c]);
+        feat_of.emplace_back();
+        int32_t serial = 0;
+        for (const Range &r : kv.second) {
+            ids.push_back("feature:" + kv.first + ":" + std::to_string(++serial));   // feature.rs:81-83
+            fs.push_back(r.start);
+            fe.push_back(r.end);
+            feat_of.back().push_back(Feature{ids.back(), r.start, r.end});
+        }
+        feat_off.push_back(fs.size());
+    }
+    const uint32_t n_sel = (uint32_t)sel.size();
+    if (n_sel == 0) return done(std::move(out));
+    SeqSetGuard sg{h};
+    gams_seqset_t *s = seqset;
+    if (!do_gc) {
+        check(h, gams_seqset_create(h, n_sel, lens.data(), &sg.s));
+        s = sg.s;
+    }
+    std::vector<const char *> chr(n_sel), idp(ids.size());
+    for (uint32_t k = 0; k < n_sel; ++k) chr[k] = loc.ctgs_[sel[k]].chr_id.c_str();
+    for (size_t f = 0; f < ids.size(); ++f) idp[f] = ids[f].c_str();
+    const uint64_t *toff = nullptr;
+    const int rt = gams_gpu_sw_text_actions(h, s, n_sel, index.data(), chr.data(), sel_start.data(), feat_off.data(), fs.data(),
+                                            fe.data(), idp.data(), a.size, a.max, a.resize, a.actions, loc.rg_index(),
+                                            group.data(), &text, &text_bytes, &toff, &rows);
+    if (rt != GAMS_EUNSUPPORTED) {
+        check(h, rt);
+        return done(std::string(text, (size_t)text_bytes));              // (the selected ctgs are in id order)
+    }
+    // a value the device formatter does not cover: the rows (and counts) as arrays, formatted here.  Without gc the only
+    // such value is a negative coordinate, and the array entry needs the bases this call never had
+    if (!do_gc) check(h, rt);
+    std::vector<uint64_t> row_off(n_sel + 1, 0);
+    check(h, gams_gpu_sw_batch(h, s, n_sel, index.data(), sel_start.data(), feat_off.data(), fs.data(), fe.data(), a.size,
+                               a.max, a.resize, nullptr, 0, row_off.data(), &rows));
+    std::vector<gams_sw_row_t> rv(std::max<uint64_t>(rows, 1));
+    std::vector<int32_t> cnt(do_count ? std::max<uint64_t>(rows, 1) : 0);
+    check(h, gams_gpu_sw_batch(h, s, n_sel, index.data(), sel_start.data(), feat_off.data(), fs.data(), fe.data(), a.size,
+                               a.max, a.resize, rv.data(), rows, row_off.data(), &rows));
+    if (do_count)
+        check(h, gams_gpu_sw_count_batch(h, s, n_sel, index.data(), sel_start.data(), feat_off.data(), fs.data(), fe.data(),
+                                         a.size, a.max, loc.rg_index(), group.data(), cnt.data(), rows, nullptr, &rows));
+    for (uint32_t k = 0; k < n_sel; ++k)
+        out += sw_format_rows(rv.data() + row_off[k], row_off[k + 1] - row_off[k], loc.ctgs_[sel[k]], feat_of[k], 8, a.actions,
+                              do_count ? cnt.data() + row_off[k] : nullptr);
+    return done(std::move(out));
+}
+
+std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
+                    size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes,
+                    size_t rg_n, bool *device, const TextSink *sink) {
+    if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, "sw_text: ctgs / seqs size mismatch");
+    if (!(a.actions & GAMS_SW_GC))                                       // nothing reads a base: nothing goes up
+        return sw_text(h, ctgs, static_cast<gams_seqset_t *>(nullptr), std::vector<uint32_t>(), bytes, n, a, rgs, rg_bytes, rg_n,
+                       device, sink);
+    std::vector<uint32_t> lens(std::max<size_t>(ctgs.size(), 1), 0), slots(ctgs.size());
+    for (size_t i = 0; i < ctgs.size(); ++i) {
+        lens[i] = (uint32_t)(ctgs[i].chr_end - ctgs[i].chr_start + 1);
+        slots[i] = (uint32_t)i;
+    }
+    SeqSetGuard sg{h};
+    check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
+    check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
+    return sw_text(h, ctgs, sg.s, slots, bytes, n, a, rgs, rg_bytes, rg_n, device, sink);
+}
+
 namespace {
 std::string json_escape(const std::string &v) {
     std::string o;

@@ -12,6 +12,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include <string>
@@ -200,6 +201,10 @@ public:
     friend RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device);
     friend std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                                  const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device);
+    friend std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
+                               const std::vector<uint32_t> &slots, const char *bytes, size_t n, const SwArgs &a,
+                               const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes, size_t rg_n,
+                               bool *device, const std::function<char *(size_t)> *sink);
 
 private:
     gams_gpu_t *h_;
@@ -270,6 +275,28 @@ std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::ve
 // ctgs[i], UINT32_MAX if none does (peaks in such a ctg are an error)
 std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                       const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device = nullptr);
+
+// `gams feature` + `gams sw` over the bytes of one range file (feature.rs:50-54 read_range, feature.rs:74-86 ids,
+// sw.rs:132-191 rows): the rows of every ctg, the ctgs in id order (sw.rs:97), made on the device from the bytes to the
+// text (gams_gpu_sw_feature_text).  The features are those feature_records would store: the kept lines of a ctg in file
+// order, "feature:{ctg_id}:{k}" from 1.  seqs[i] = the bases of ctgs[i]: one seqset is built and uploaded for the call
+// (nothing goes up without GAMS_SW_GC in a.actions).  The idx:rg: source of GAMS_SW_COUNT is `rgs` or the bytes of one rg
+// file, as for sw_proc_ctgs (located among the ctgs of the call; both is GAMS_EINVAL).  Where the device refuses
+// (GAMS_EUNSUPPORTED) the lines go through read_range, the ids are made here and gams_gpu_sw_text_actions runs on the
+// same seqset: the text is the same; *device as in Locator::locate_text.
+// With `sink` the rows go to the memory (*sink)(n) hands out -- it is called once, with the bytes of all rows -- and the
+// string returned is empty: the device path copies the slices there with a few threads, each touching its own pages first
+// (313 MB of rows into one fresh std::string cost one thread more than everything else in the call).
+using TextSink = std::function<char *(size_t)>;
+std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
+                    size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                    const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr);
+// ... on a resident seqset (a host that holds the seqset of gen_text): slots[i] = the seqset slot that holds ctgs[i],
+// UINT32_MAX if none does (features in such a ctg are an error under GAMS_SW_GC).  Without GAMS_SW_GC seqset may be NULL
+// (slots is then not looked at).
+std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                    const char *bytes, size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                    const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr);
 
 // src/cmd_gams/rg.rs:41-77 / feature.rs:47-95: the records the loaders SET, as (key, JSON) pairs in
 // the reference's order (ctg id order, then file order), serials from 1 per ctg (a fresh cnt:).

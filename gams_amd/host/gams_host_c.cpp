@@ -605,6 +605,54 @@ char *gams_host_peak_text(gams_gpu_t *h, uint32_t n, const char *const *ids, con
     });
 }
 
+// `gams sw` over the bytes of a feature file (bytes, n_bytes: not NUL-terminated; gams::sw_text): the rows of every ctg
+// in id order, made on the device.  seqset == NULL: seqs[i] = the bases of ctg i, uploaded for the call (seqs may be NULL
+// without GAMS_SW_GC); else the resident seqset and slots[i] = its slot of ctg i (UINT32_MAX: none), seqs unused.  The
+// idx:rg: source of GAMS_SW_COUNT: rg_lines ("ctg_id\trange" rows, as gams_host_sw_multi_actions takes them; NULL: none)
+// or rg_data (the rg_n bytes of an rg file; NULL: none); both is GAMS_EINVAL.
+char *gams_host_sw_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                        const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                        const char *bytes, uint64_t n_bytes, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                        const char *rg_lines, const char *rg_data, uint64_t rg_n, uint64_t *out_len) {
+    // the rows go straight into the buffer this call returns (gams::TextSink): no string in between
+    struct Out {
+        char *p = nullptr;
+        size_t n = 0;
+        ~Out() { std::free(p); }
+    };
+    return guard((char *)nullptr, [&] {
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        std::map<std::string, std::vector<gams::Range>> rg_of;
+        if (rg_lines) rg_of = rg_index_of(n, ids, rg_lines);
+        const gams::SwArgs a = sw_args(size, max, resize, actions);
+        const char *data = bytes ? bytes : "";
+        bool dev = false;
+        Out out;
+        const gams::TextSink sink = [&](size_t len) {
+            std::free(out.p);
+            out.p = static_cast<char *>(std::malloc(len + 1));
+            if (!out.p) throw std::bad_alloc();
+            out.p[len] = 0;
+            out.n = len;
+            return out.p;
+        };
+        const auto t0 = std::chrono::steady_clock::now();
+        if (seqset || !seqs)
+            gams::sw_text(h, cv, seqset, seqset ? std::vector<uint32_t>(slots, slots + n) : std::vector<uint32_t>(), data,
+                          (size_t)n_bytes, a, rg_lines ? &rg_of : nullptr, rg_data, (size_t)rg_n, &dev, &sink);
+        else
+            gams::sw_text(h, cv, std::vector<const uint8_t *>(seqs, seqs + n), data, (size_t)n_bytes, a,
+                          rg_lines ? &rg_of : nullptr, rg_data, (size_t)rg_n, &dev, &sink);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        if (!out.p) (void)sink(0);
+        if (out_len) *out_len = out.n;
+        char *const p = out.p;
+        out.p = nullptr;
+        return p;
+    });
+}
+
 // rg.rs:41-77 / feature.rs:47-95: rows "key\tjson" of the records the loaders SET (tag == NULL: rg)
 char *gams_host_loader_records(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
                                const int32_t *starts, const int32_t *ends, const char *lines, const char *tag) {

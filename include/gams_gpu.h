@@ -455,6 +455,38 @@ int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, co
                        const int32_t *chr_end, const char *bytes, uint64_t n_bytes, const char **text,
                        uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_rows);
 
+/* ---- text in, text out: sw from a feature file (feature.rs:50-54 read_range, then sw.rs:132-191) ---- */
+/* The bytes of ONE range file (lines, refused bytes and limits as for the rg loader above) -> the rows `gams sw` prints
+ * for the features `gams feature` would have stored from it.  ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end
+ * as for gams_gpu_peak_text (chr_names names every group of ctg_ix); size, max, resize, actions, rg_ix as for
+ * gams_gpu_sw_text_actions, rg_group[i] belonging to interval i of ctg_ix.
+ * The file is read as gams_gpu_read_range_text reads it: the whole line through Range::from_str, located by overlap, the
+ * first located line of a ctg dropped.  The kept lines of a ctg keep file order; the k-th of them, from 1, is the
+ * feature "feature:{ctg_id}:{k}" (feature.rs:74-86 on a fresh cnt:feature:).  Every kept feature prints the rows of
+ * sw.rs:141-191, byte-equal to what gams_gpu_sw_text_actions prints for the same features and ids.
+ * *text (text_bytes bytes, no NUL; page-locked memory owned by the handle, valid until the handle's next sw call) holds
+ * the rows grouped by interval in the caller's order: those of interval i are text[text_off[i] .. text_off[i+1])
+ * (text_off has n_ctg + 1 entries; `gams sw` prints the ctgs in id order).  *n_features = the kept lines ("There are N
+ * features in this file"), *n_rows the rows.  Two calls return identical text.  Zero bytes or no kept line: GAMS_OK,
+ * no rows, text_off all zero.
+ * Without GAMS_SW_GC no sequence byte is read: s and ctg_index may be NULL.  With it, a ctg that has kept features needs a
+ * slot of chr_end - chr_start + 1 bases.
+ * GAMS_EINVAL: null arguments; size < 2, max < 0 or resize < 2; unknown action bits; GAMS_SW_COUNT without rg_ix; a kept
+ * feature whose middle pair lies outside its ctg (located by overlap does not imply it; the message names the smallest
+ * such line; a dropped first line is never looked at); with GAMS_SW_GC a ctg with kept features and no slot, or a slot
+ * of another length.  GAMS_ESTATE: GAMS_SW_GC on a seqset without the sequence bytes.  GAMS_EUNSUPPORTED (nothing is
+ * printed; run the host path): what the rg loader refuses, a value the sw formatter does not cover, more feature
+ * slots than one launch takes, max beyond 2^24.
+ * gams_gpu_last_stage_ms then reports twelve stages: the loader's lines, parse, locate, first, keep, offsets, order,
+ * then gather, geometry, rows, text lengths, text write (seven when no line is kept). */
+int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                             const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                             const int32_t *chr_end, const char *bytes, uint64_t n_bytes,
+                             int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                             gams_index_t *rg_ix, const uint32_t *rg_group,
+                             const char **text, uint64_t *text_bytes, uint64_t *text_off,
+                             uint64_t *n_features, uint64_t *n_rows);
+
 /* ---- gen: valid regions of a chromosome (first "next" row of SURVEY section 8f) ---- */
 /* gen.rs:86-104: bases other than A C G T a c g t are ambiguous; the valid set is their
  * complement after fill(fill-1) and excise(min_len).  Writes up to `cap` spans (1-based,
