@@ -122,6 +122,26 @@ inline int gams_fail(gams_gpu_t *h, int code, const std::string &msg) {
                              (who) + ": " + #call + ": " + hipGetErrorString(e_));               \
     } while (0)
 
+// The stopwatch of the staged calls: gams_gpu::kq holds one timed pair of events per stage (per chunk of a query call).
+// gams_stopwatch_reserve grows it to n pairs; a StageClock records the event that opens or closes stage k on its stream.
+inline hipError_t gams_stopwatch_reserve(gams_gpu_t *h, size_t n) {
+    while (h->kq.size() < n) {
+        hipEvent_t a = nullptr, b = nullptr;
+        hipError_t e = hipEventCreate(&a);
+        if (e == hipSuccess) e = hipEventCreate(&b);
+        if (e != hipSuccess) return e;
+        h->kq.emplace_back(a, b);
+    }
+    return hipSuccess;
+}
+struct StageClock {
+    gams_gpu_t *h;
+    hipStream_t st;
+    hipError_t operator()(int k, bool open) const {
+        return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st);
+    }
+};
+
 // One pooled block for the length of a call (or of a build).  A block goes back to the pool only after every stream
 // that had work queued on it has drained: the streams named at construction (h->compute unless others are given).
 struct PoolBlock {

@@ -467,15 +467,8 @@ extern "C" int gams_gpu_gen_text(gams_gpu_t *h, const char *bytes, uint64_t n_by
     std::vector<GenHdr> hdrs;
     unsigned long long total = 0;
     PoolBlock d_cat(h, false);
-    if (n_bytes) {
-        while (h->kq.size() < (size_t)GEN_STAGES) {
-            hipEvent_t a = nullptr, b = nullptr;
-            GAMS_HIP(h, hipEventCreate(&a));
-            GAMS_HIP(h, hipEventCreate(&b));
-            h->kq.emplace_back(a, b);
-        }
-    }
-    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
+    if (n_bytes) GAMS_HIP(h, gams_stopwatch_reserve(h, GEN_STAGES));
+    const StageClock stage{h, st};
     if (n_bytes) {
         // 1. the bytes, once; '\n' up to whole blocks and 64 B behind them, so that no kernel below guards a load
         const uint32_t nb = (uint32_t)((n_bytes + kGenBlk - 1) / kGenBlk);

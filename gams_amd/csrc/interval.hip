@@ -583,12 +583,8 @@ int query_pipeline(gams_gpu_t *h, uint64_t nq, const QCol *cols, int ncol, void 
     for (int s = 0; s < 2; ++s)
         for (int k = 0; k < 3; ++k)
             if (!h->q_ev[s][k]) GAMS_TRY(h, who, hipEventCreateWithFlags(&h->q_ev[s][k], hipEventDisableTiming));
-    while (h->kq.size() < nchunk) {
-        hipEvent_t a = nullptr, b = nullptr;
-        GAMS_TRY(h, who, hipEventCreate(&a));
-        GAMS_TRY(h, who, hipEventCreate(&b));
-        h->kq.emplace_back(a, b);
-    }
+    GAMS_TRY(h, who, gams_stopwatch_reserve(h, nchunk));
+    const StageClock chunk{h, h->compute};             // one timed pair per chunk
     h->kq_used = 0;
     // whatever the caller queued on the compute stream before (index build, uploads) comes first
     GAMS_TRY(h, who, hipEventRecord(h->k0, h->compute));
@@ -609,10 +605,10 @@ int query_pipeline(gams_gpu_t *h, uint64_t nq, const QCol *cols, int ncol, void 
         GAMS_TRY(h, who, hipEventRecord(h->q_ev[s][0], h->copy));
         GAMS_TRY(h, who, hipStreamWaitEvent(h->compute, h->q_ev[s][0], 0));
         if (c >= 2) GAMS_TRY(h, who, hipStreamWaitEvent(h->compute, h->q_ev[s][2], 0));    // chunk c-2's results are out
-        GAMS_TRY(h, who, hipEventRecord(h->kq[(size_t)c].first, h->compute));
+        GAMS_TRY(h, who, chunk((int)c, true));
         launch(d_in.data(), d_out, n, h->compute);
         GAMS_TRY(h, who, hipGetLastError());
-        GAMS_TRY(h, who, hipEventRecord(h->kq[(size_t)c].second, h->compute));
+        GAMS_TRY(h, who, chunk((int)c, false));
         GAMS_TRY(h, who, hipEventRecord(h->q_ev[s][1], h->compute));
         GAMS_TRY(h, who, hipStreamWaitEvent(h->readback, h->q_ev[s][1], 0));
         GAMS_TRY(h, who, hipMemcpyAsync(static_cast<uint8_t *>(out_host) + lo * out_elem, d_out, n * out_elem,

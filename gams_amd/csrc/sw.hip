@@ -436,7 +436,7 @@ struct SwTextArgs {
     const char *ids;
     uint32_t *len;                     // per row
     uint32_t *blk_len;                 // per block
-    const unsigned long long *blk_off; // exclusive prefix, [nb] = all bytes
+    unsigned long long *blk_off;       // exclusive prefix, [nb] = all bytes
     uint32_t nb;
     char *text;
     uint64_t text_cap;
@@ -470,8 +470,9 @@ __device__ __forceinline__ SwRowCtx sw_row_ctx(const SwTextArgs &a, uint64_t r, 
     c.serial = (uint32_t)(r - a.feat_row_off[c.f]) + 1u;    // sw.rs:148: the serial restarts with every feature
     return c;
 }
-// the row's text at p (nullptr: its length only)
-__device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r, char *p, bool *bad) {
+// the row's text, counted or written; `bad`: a value this formatter does not cover
+template <bool kWrite>
+__device__ __forceinline__ void sw_row_text(const SwTextArgs &a, uint64_t r, RowOut<kWrite> &o, bool &bad) {
     const gams_sw_row_t w = a.rows[r];
     const SwRowCtx c = sw_row_ctx(a, r, w);
     const char *id, *nm;
@@ -489,63 +490,44 @@ __device__ __forceinline__ uint32_t sw_row_text(const SwTextArgs &a, uint64_t r,
         nm = a.names + a.name_off[c.k];
         nmn = a.name_off[c.k + 1u] - a.name_off[c.k];
     }
-    if (w.start < 0 || w.end < 0 || w.distance < 0 || (uint32_t)w.type > 2u) *bad = true;
+    if (w.start < 0 || w.end < 0 || w.distance < 0 || (uint32_t)w.type > 2u) bad = true;
     const uint32_t st = (uint32_t)w.start, en = (uint32_t)w.end, di = (uint32_t)w.distance;
-    if (!p) {
-        uint32_t n = 3u + idn + 1u + dec_digits(c.serial) + 1u + nmn + 1u + dec_digits(st);
-        if (num) n += 8u + 1u + dec_digits(num);
-        if (en != st) n += 1u + dec_digits(en);
-        n += 1u + 1u + 1u + dec_digits(di) + 1u;
-        if (a.gc)
-            n += sw_put_f4(nullptr, w.gc_content, bad) + 1u + sw_put_f4(nullptr, w.gc_mean, bad) + 1u +
-                 sw_put_f4(nullptr, w.gc_stddev, bad) + 1u + sw_put_f4(nullptr, w.gc_cv, bad) + 2u;
-        else
-            n += 3u + 2u;
-        if (a.cnt) n += i32_len(a.cnt[r]);
-        return n;
-    }
-    char *q = p;
-    *q++ = 's';
-    *q++ = 'w';
-    *q++ = ':';
-    if (num) q = put_bytes(q, "feature:", 8u);
-    for (uint32_t i = 0; i < idn; ++i) *q++ = id[i];
+    o.bytes("sw:", 3u);
+    if (num) o.bytes("feature:", 8u);
+    o.bytes(id, idn);
     if (num) {
-        *q++ = ':';
-        q = put_dec(q, num);
+        o.ch(':');
+        o.dec(num);
     }
-    *q++ = ':';
-    q = put_dec(q, c.serial);
-    *q++ = '\t';
-    for (uint32_t i = 0; i < nmn; ++i) *q++ = nm[i];
-    *q++ = ':';
-    q = put_dec(q, st);
+    o.ch(':');
+    o.dec(c.serial);
+    o.ch('\t');
+    o.bytes(nm, nmn);
+    o.ch(':');
+    o.dec(st);
     if (en != st) {
-        *q++ = '-';
-        q = put_dec(q, en);
+        o.ch('-');
+        o.dec(en);
     }
-    *q++ = '\t';
-    *q++ = "MLR"[(uint32_t)w.type > 2u ? 0u : (uint32_t)w.type];
-    *q++ = '\t';
-    q = put_dec(q, di);
-    *q++ = '\t';
+    o.ch('\t');
+    o.ch("MLR"[(uint32_t)w.type > 2u ? 0u : (uint32_t)w.type]);
+    o.ch('\t');
+    o.dec(di);
+    o.ch('\t');
     if (a.gc) {
-        q += sw_put_f4(q, w.gc_content, bad);
-        *q++ = '\t';
-        q += sw_put_f4(q, w.gc_mean, bad);
-        *q++ = '\t';
-        q += sw_put_f4(q, w.gc_stddev, bad);
-        *q++ = '\t';
-        q += sw_put_f4(q, w.gc_cv, bad);
+        o.f4(w.gc_content, bad);
+        o.ch('\t');
+        o.f4(w.gc_mean, bad);
+        o.ch('\t');
+        o.f4(w.gc_stddev, bad);
+        o.ch('\t');
+        o.f4(w.gc_cv, bad);
     } else {
-        *q++ = '\t';
-        *q++ = '\t';
-        *q++ = '\t';
+        o.bytes("\t\t\t", 3u);                           // four empty statistics
     }
-    *q++ = '\t';
-    if (a.cnt) q = put_i32(q, a.cnt[r]);
-    *q++ = '\n';
-    return (uint32_t)(q - p);
+    o.ch('\t');
+    if (a.cnt) o.i32(a.cnt[r]);
+    o.ch('\n');
 }
 
 __global__ __launch_bounds__(256) void sw_text_len_kernel(const SwTextArgs a) {
@@ -558,9 +540,10 @@ __global__ __launch_bounds__(256) void sw_text_len_kernel(const SwTextArgs a) {
     for (uint32_t u = 0; u < 2u; ++u) {
         const uint64_t r = base + 2u * tid + u;
         if (r >= a.n_rows) continue;
-        const uint32_t l = sw_row_text(a, r, nullptr, &bad);
-        a.len[r] = l;
-        sum += l;
+        RowOut<false> n;
+        sw_row_text(a, r, n, bad);
+        a.len[r] = n.n;
+        sum += n.n;
     }
     if (bad) a.words[1] = 1ull;
     const uint32_t tot = block_sum_256(sum, ws);
@@ -591,10 +574,13 @@ __global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) 
     for (uint32_t u = 0; u < 2u; ++u) {
         const uint64_t r = base + 2u * tid + u;
         if (r >= a.n_rows) break;
-        if (staged)
-            (void)sw_row_text(a, r, stage + mis + at, &bad);
-        else if (fits)
-            (void)sw_row_text(a, r, a.text + blk0 + at, &bad);
+        if (staged) {
+            RowOut<true> o{stage + mis + at};
+            sw_row_text(a, r, o, bad);
+        } else if (fits) {
+            RowOut<true> o{a.text + blk0 + at};
+            sw_row_text(a, r, o, bad);
+        }
         at += l[u];
     }
     if (!staged) return;
@@ -836,6 +822,65 @@ int sw_text_blobs(const SwReq &q, uint32_t nf, SwTextBlobs &b) {
     return GAMS_OK;
 }
 
+// The back half of both text paths.  sw_text_cols carves what it writes -- row lengths | block lengths and offsets |
+// words | text -- behind whatever the caller carved in front, for n_rows rows of at most per_row bytes each in n_sel
+// ctgs.  sw_text_tail then queues the length of every row, the blocks' prefix, the rows at their offsets and the first
+// byte of every ctg, and reads back the words (total, flag, per-ctg offsets), which say the text's size, and the text into
+// the handle's page-locked buffer, valid until the next call.  `ta` comes with its sources filled as well (the rows, the
+// ctgs, the row offsets, the ids and names of either kind, gc, cnt).  `stage`, where given, records SWF_TLEN and
+// SWF_TWRITE; `advice` ends the refusal's message.
+void sw_text_cols(Carver &c, SwTextArgs &ta, uint64_t n_rows, uint32_t n_sel, uint64_t per_row) {
+    ta.n_rows = n_rows;
+    ta.n_sel = n_sel;
+    ta.nb = (uint32_t)((n_rows + kSwTextBlock - 1) / kSwTextBlock);
+    ta.text_cap = std::max<uint64_t>(n_rows * per_row, 4096);
+    ta.len = c.take<uint32_t>(std::max<uint64_t>(n_rows, 1));
+    ta.blk_len = c.take<uint32_t>(std::max(ta.nb, 1u));
+    ta.blk_off = c.take<unsigned long long>((size_t)ta.nb + 1);
+    ta.words = c.take<unsigned long long>((size_t)n_sel + 3);
+    ta.text = c.take<char>(ta.text_cap);
+}
+struct SwText {
+    const char *text;                  // nullptr: no byte
+    uint64_t bytes;
+    const unsigned long long *words;   // [2 + k] = the first byte of ctg k, [2 + n_sel] = bytes
+};
+int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, const SwTextArgs &ta, const StageClock *stage,
+                 SwText *out) {
+    hipStream_t st = h->compute;
+    const uint32_t nb = ta.nb, n_sel = ta.n_sel;
+    const uint64_t text_cap = ta.text_cap;
+    const size_t n_words = (size_t)n_sel + 3;
+    GAMS_TRY(h, who, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), st));
+    if (stage) GAMS_TRY(h, who, (*stage)(SWF_TLEN, true));
+    if (nb) {
+        hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, st, ta);
+        hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, ta.blk_len, nb, ta.blk_off, ta.words, 0u);
+    }
+    if (stage) {
+        GAMS_TRY(h, who, (*stage)(SWF_TLEN, false));
+        GAMS_TRY(h, who, (*stage)(SWF_TWRITE, true));
+    }
+    if (nb) {
+        hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, st, ta);
+        hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, st, ta);
+    }
+    GAMS_TRY(h, who, hipGetLastError());
+    if (stage) GAMS_TRY(h, who, (*stage)(SWF_TWRITE, false));
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_words, &h->sw_words_bytes, n_words * 8, n_words * 8));
+    GAMS_TRY(h, who, hipMemcpyAsync(h->sw_words, ta.words, n_words * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    const uint64_t bytes = h->sw_words[0];
+    if (h->sw_words[1] != 0 || bytes > text_cap)
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a value this formatter does not cover (a statistic of 1000 or more, a "
+                                                     "negative coordinate): " + advice);
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_text, &h->sw_text_bytes, bytes, bytes + bytes / 8 + 4096));
+    if (bytes) GAMS_TRY(h, who, hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    *out = SwText{bytes ? h->sw_text : nullptr, bytes, h->sw_words};
+    return GAMS_OK;
+}
+
 // 4. (text entries) the n_out rows on the device -> TSV text in the handle's page-locked buffer
 int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vector<uint64_t> &crow, const SwCols &d,
                     const gams_sw_row_t *d_rows, const int32_t *d_cnt) {
@@ -846,24 +891,17 @@ int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vect
     SwTextBlobs B;
     const int rc = sw_text_blobs(q, nf, B);
     if (rc != GAMS_OK) return rc;
-    const uint32_t nb = (uint32_t)((n_out + kSwTextBlock - 1) / kSwTextBlock);
-    const uint64_t text_cap = std::max<uint64_t>(n_out * (uint64_t)(B.max_id + B.max_name + (do_count ? 112 : 96)), 4096);
-    const size_t n_words = (size_t)n_sel + 3;
+    const uint64_t per_row = B.max_id + B.max_name + (do_count ? 112 : 96);
     auto tabs = [&](Carver &c) { return sw_text_tabs_layout(c, n_sel, nf, B.names.size(), B.ids.size()); };
     SwTextArgs ta{};
-    unsigned long long *blk_off = nullptr;
-    auto dev = [&](Carver &c) {   // tables | row lengths | block lengths and offsets | words | text
+    auto dev = [&](Carver &c) {   // tables | what the tail writes
         const SwTextTabs t = tabs(c);
         ta.ctg_row_off = t.ctg_row_off;
         ta.name_off = t.name_off;
         ta.names = t.names;
         ta.id_off = t.id_off;
         ta.ids = t.ids;
-        ta.len = c.take<uint32_t>(std::max<uint64_t>(n_out, 1));
-        ta.blk_len = c.take<uint32_t>(std::max(nb, 1u));
-        ta.blk_off = blk_off = c.take<unsigned long long>((size_t)nb + 1);
-        ta.words = c.take<unsigned long long>(n_words);
-        ta.text = c.take<char>(text_cap);
+        sw_text_cols(c, ta, n_out, n_sel, per_row);
     };
     const size_t tab_bytes = layout_bytes(tabs);
     PoolBlock tdev(h, false), tpin(h, true);
@@ -878,39 +916,16 @@ int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vect
     GAMS_TRY(h, kSwText, hipMemcpyAsync(tdev.p, tpin.p, tab_bytes, hipMemcpyHostToDevice, h->compute));
     carve(tdev.p, dev);
     ta.rows = d_rows;
-    ta.n_rows = n_out;
     ta.ctgs = d.ctgs;
-    ta.n_sel = n_sel;
     ta.feat_row_off = d.row_off;
-    ta.nb = nb;
-    ta.text_cap = text_cap;
     ta.gc = do_gc ? 1u : 0u;
     ta.cnt = d_cnt;
-    GAMS_TRY(h, kSwText, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), h->compute));
-    if (nb) {
-        hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
-        hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, h->compute, ta.blk_len, nb, blk_off, ta.words,
-                           0u);
-        hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, h->compute, ta);
-        hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, h->compute, ta);
-        GAMS_TRY(h, kSwText, hipGetLastError());
-    }
-    // the words first (total, flag, per-ctg offsets), then the text -- whose size they say -- into the handle's
-    // page-locked text buffer, valid until the next call
-    GAMS_TRY(h, kSwText, gams_pool_grow(h, true, &h->sw_words, &h->sw_words_bytes, n_words * 8, n_words * 8));
-    GAMS_TRY(h, kSwText, hipMemcpyAsync(h->sw_words, ta.words, n_words * 8, hipMemcpyDeviceToHost, h->compute));
-    GAMS_TRY(h, kSwText, hipStreamSynchronize(h->compute));
-    const uint64_t bytes = h->sw_words[0];
-    if (h->sw_words[1] != 0 || bytes > text_cap)
-        return gams_fail(h, GAMS_EUNSUPPORTED,
-                         "gpu_sw_text: a value this formatter does not cover (a statistic of 1000 or more, a negative "
-                         "coordinate): format gams_gpu_sw_batch's rows on the host");
-    GAMS_TRY(h, kSwText, gams_pool_grow(h, true, &h->sw_text, &h->sw_text_bytes, bytes, bytes + bytes / 8 + 4096));
-    if (bytes) GAMS_TRY(h, kSwText, hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, h->compute));
-    GAMS_TRY(h, kSwText, hipStreamSynchronize(h->compute));
-    *tx->text = bytes ? h->sw_text : nullptr;
-    *tx->text_bytes = bytes;
-    if (tx->ctg_off) *tx->ctg_off = reinterpret_cast<const uint64_t *>(h->sw_words + 2);
+    SwText T{};
+    const int rt = sw_text_tail(h, kSwText, "format gams_gpu_sw_batch's rows on the host", ta, nullptr, &T);
+    if (rt != GAMS_OK) return rt;
+    *tx->text = T.text;
+    *tx->text_bytes = T.bytes;
+    if (tx->ctg_off) *tx->ctg_off = reinterpret_cast<const uint64_t *>(T.words + 2);
     return GAMS_OK;
 }
 
@@ -968,7 +983,7 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     const bool do_gc = (J.actions & GAMS_SW_GC) != 0, do_count = (J.actions & GAMS_SW_COUNT) != 0;
     const uint32_t n_ctg = J.n_ctg, nf = J.nf;
     hipStream_t st = h->compute;
-    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
+    const StageClock stage{h, st};
     // the interval table: a few KB, one copy
     const uint32_t nbf = (nf + 255u) / 256u;
     SwCtg *d_ctgs = nullptr;
@@ -1038,30 +1053,16 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     const int rc = sw_launch(q, nf, tot, d, d_rows, d_cnt);
     if (rc != GAMS_OK) return rc;
     GAMS_TRY(h, who, stage(SWF_ROWS, false));
-    // 5. the text: lengths, block prefix, rows at their offsets, the first byte of every interval
-    const uint32_t nb = (uint32_t)((tot + kSwTextBlock - 1) / kSwTextBlock);
+    // 5. the text, with the ids composed on the device
     const uint64_t per_row = 8ull + J.max_id + 1ull + 10ull + J.max_chr + (do_count ? 112ull : 96ull);
-    const uint64_t text_cap = std::max<uint64_t>(tot * per_row, 4096);
-    const size_t n_words = (size_t)n_ctg + 3;
     SwTextArgs ta{};
-    unsigned long long *blk_off = nullptr;
-    auto txt = [&](Carver &c) {   // row lengths | block lengths and offsets | words | text
-        ta.len = c.take<uint32_t>(std::max<uint64_t>(tot, 1));
-        ta.blk_len = c.take<uint32_t>(std::max(nb, 1u));
-        ta.blk_off = blk_off = c.take<unsigned long long>((size_t)nb + 1);
-        ta.words = c.take<unsigned long long>(n_words);
-        ta.text = c.take<char>(text_cap);
-    };
+    auto txt = [&](Carver &c) { sw_text_cols(c, ta, tot, n_ctg, per_row); };
     GAMS_TRY(h, who, t_dev.alloc(layout_bytes(txt)));
     carve(t_dev.p, txt);
     ta.rows = d_rows;
-    ta.n_rows = tot;
     ta.ctgs = d_ctgs;
     ta.ctg_row_off = reinterpret_cast<const uint64_t *>(d_ctg_row_off);
-    ta.n_sel = n_ctg;
     ta.feat_row_off = reinterpret_cast<const uint64_t *>(d_row_off);
-    ta.nb = nb;
-    ta.text_cap = text_cap;
     ta.gc = do_gc ? 1u : 0u;
     ta.cnt = d_cnt;
     ta.dev_ids = 1u;
@@ -1070,36 +1071,13 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     ta.chr_off = J.chr_off;
     ta.chr_bytes = J.chr_bytes;
     ta.igrp = J.igrp;
-    GAMS_TRY(h, who, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), st));
-    GAMS_TRY(h, who, stage(SWF_TLEN, true));
-    if (nb) {
-        hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, st, ta);
-        hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, ta.blk_len, nb, blk_off, ta.words, 0u);
-    }
-    GAMS_TRY(h, who, stage(SWF_TLEN, false));
-    GAMS_TRY(h, who, stage(SWF_TWRITE, true));
-    if (nb) {
-        hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, st, ta);
-        hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_ctg + 1), dim3(64), 0, st, ta);
-    }
-    GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, stage(SWF_TWRITE, false));
-    // the final read-back, as in gams_gpu_sw_text: the words (total, flag, per-interval offsets), which say the text's
-    // size, then the text into the handle's page-locked buffer
-    GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_words, &h->sw_words_bytes, n_words * 8, n_words * 8));
-    GAMS_TRY(h, who, hipMemcpyAsync(h->sw_words, ta.words, n_words * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
-    const uint64_t bytes = h->sw_words[0];
-    if (h->sw_words[1] != 0 || bytes > text_cap)
-        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a value this formatter does not cover (a statistic of 1000 or more, a "
-                                                     "negative coordinate): use the host path");
-    GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_text, &h->sw_text_bytes, bytes, bytes + bytes / 8 + 4096));
-    if (bytes) GAMS_TRY(h, who, hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
-    *text = bytes ? h->sw_text : "";
-    *text_bytes = bytes;
+    SwText T{};
+    const int rt = sw_text_tail(h, who, "use the host path", ta, &stage, &T);
+    if (rt != GAMS_OK) return rt;
+    *text = T.bytes ? T.text : "";
+    *text_bytes = T.bytes;
     *n_rows = tot;
-    for (uint32_t i = 0; i <= n_ctg; ++i) text_off[i] = nb ? h->sw_words[2u + i] : 0ull;
+    for (uint32_t i = 0; i <= n_ctg; ++i) text_off[i] = T.words[2u + i];   // (no rows: the words are zero)
     return GAMS_OK;
 }
 

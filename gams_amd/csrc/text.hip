@@ -8,9 +8,10 @@
 // upload and line index (the stages are listed in front of its kernels, below):
 //   gams_gpu_read_range_text       the ranges of one .rg file bucketed per ctg, as arrays
 //   gams_index_create_range_text   the rg index of the file and the ctg -> group table
-// and, on the loader's stages, `gams peak` (utils.rs:83-116 read_peak, then peak.rs:41-160):
+// and, on the loader itself (rg_load, each with a spec and a consumer of its own), `gams peak` (utils.rs:83-116 read_peak,
+// then peak.rs:41-160):
 //   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
-// and, on the loader itself, `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
+// and `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
 //   gams_gpu_sw_feature_text       the bytes of one range file -> the sw rows of its features (stages 2-5 in sw.hip)
 //
 // Pipeline (one handle, the compute stream):
@@ -410,31 +411,53 @@ struct RowArgs {
     char *text;
 };
 
-// bytes of the row of line i (0: no row); `bad`: the value has no text of the reference's
-__device__ uint64_t row_len(const RowArgs &a, uint32_t i, bool &bad) {
+// The row of line i (none for a line that has none), counted or written; `bad`: the value has no text of the reference's
+template <bool kWrite>
+__device__ void text_row(const RowArgs &a, uint32_t i, RowOut<kWrite, uint64_t> &o, bool &bad) {
     uint64_t b, e;
     if (a.kind == K_ANNO) {
+        const bool head = a.header && i == 0u;
+        if (!head && !a.keep[i]) return;
         line_of(a.t, i, b, e);
-        if (a.header && i == 0u) return (e - b) + 1u + a.prefix_len + 5u;   // "{line}\t{prefix}Prop\n"
-        if (!a.keep[i]) return 0;
+        o.bytes(a.t.in + b, e - b);
+        o.ch('\t');
+        if (head) {                                     // "{line}\t{prefix}Prop\n"
+            o.bytes(a.prefix, a.prefix_len);
+            o.bytes("Prop\n", 5u);
+            return;
+        }
         const float p = a.prop[i];
         // a reversed range on a chromosome of the set: the reference's prop is 0/0
         if (a.grp[i] != UINT32_MAX && (a.qe[i] < a.qs[i] || !(p >= 0.0f && p <= 1.0f))) bad = true;
-        return (e - b) + 8u;                                                 // "\t0.0000\n"
+        o.prop4(p);                                     // anno.rs:140
+        o.ch('\n');
+        return;
     }
     const int64_t c = a.hit[i];
-    if (c < 0) return 0;
+    if (c < 0) return;
     b = a.t.starts[i];
-    const uint64_t flen = a.fend[i] - b;
-    if (a.kind == K_LOCATE) return flen + 2u + (a.ids.off[c + 1] - a.ids.off[c]);
-    return flen + 2u + i32_len(a.cnt[i]);
+    o.bytes(a.t.in + b, a.fend[i] - b);
+    o.ch('\t');
+    if (a.kind == K_LOCATE) {
+        const unsigned long long io = a.ids.off[c];
+        o.bytes(a.ids.bytes + io, a.ids.off[c + 1] - io);   // locate.rs:139
+    } else {
+        o.i32(a.cnt[i]);                                    // locate.rs:137
+    }
+    o.ch('\n');
+}
+
+__device__ __forceinline__ uint64_t text_row_len(const RowArgs &a, uint32_t i, bool &bad) {
+    RowOut<false, uint64_t> n;
+    if (i < a.t.n_lines) text_row(a, i, n, bad);
+    return n.n;
 }
 
 __global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
     __shared__ uint64_t ws[4];
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     bool bad = false;
-    const uint64_t l = i < a.t.n_lines ? row_len(a, i, bad) : 0ull;
+    const uint64_t l = text_row_len(a, i, bad);
     if (bad) a.words[W_UNSUP] = 1ull;
     uint64_t tot;
     (void)block_excl_scan_256<uint64_t>(l, ws, tot);
@@ -451,37 +474,13 @@ __global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
 __global__ __launch_bounds__(256) void text_row_write_kernel(const RowArgs a) {
     __shared__ uint64_t ws[4];
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    bool bad = false;
-    const uint64_t l = i < a.t.n_lines ? row_len(a, i, bad) : 0ull;
+    bool bad = false;                          // (the length pass flagged what has no text)
+    const uint64_t l = text_row_len(a, i, bad);
     uint64_t tot;
     const uint64_t rel = block_excl_scan_256<uint64_t>(l, ws, tot);
     if (l == 0ull) return;
-    char *q = a.text + a.blk_off[blockIdx.x] + rel;
-    uint64_t b, e;
-    if (a.kind == K_ANNO) {
-        line_of(a.t, i, b, e);
-        q = put_bytes(q, a.t.in + b, e - b);
-        *q++ = '\t';
-        if (a.header && i == 0u) {
-            q = put_bytes(q, a.prefix, a.prefix_len);
-            q = put_bytes(q, "Prop\n", 5u);
-            return;
-        }
-        (void)gams_fmt_prop4(a.prop[i], q);   // anno.rs:140 (checked in [0, 1] by the length pass)
-        q[6] = '\n';
-        return;
-    }
-    b = a.t.starts[i];
-    q = put_bytes(q, a.t.in + b, a.fend[i] - b);
-    *q++ = '\t';
-    if (a.kind == K_LOCATE) {
-        const int64_t c = a.hit[i];
-        const unsigned long long o = a.ids.off[c];
-        q = put_bytes(q, a.ids.bytes + o, a.ids.off[c + 1] - o);   // locate.rs:139
-    } else {
-        q = put_i32(q, a.cnt[i]);                                    // locate.rs:137
-    }
-    *q = '\n';
+    RowOut<true, uint64_t> o{a.text + a.blk_off[blockIdx.x] + rel};
+    text_row(a, i, o, bad);
 }
 
 struct TextJob {
@@ -763,25 +762,41 @@ struct RgCols {
     const unsigned long long *bucket_off;   // host, n_ctg + 1
     const uint32_t *first;                  // host, n_ctg: UINT32_MAX = no located line
     RgGather g;                             // key, line_mask, qs, qe, n_kept, bucket_off (device) filled; n_kept == 0: nothing on the device
+    TextLines t;                            // the line index (device), with lines
+    unsigned long long *words;              // device: the W_* words of the call
     bool ran;                               // the input had lines: the stages up to RG_OFFSETS (with `order` RG_ORDER) were queued and timed
 };
 
 enum : int { RG_LINES = 0, RG_PARSE, RG_LOCATE, RG_FIRST, RG_KEEP, RG_OFFSETS, RG_ORDER, RG_GATHER, RG_BUILD, RG_STAGES };
 
-// Runs the stages up to the sort (`order` false: up to the offsets, for a size query) and calls consume(cols, stage) -- stage(k, open) records the stopwatch event that opens
-// or closes stage k -- which queues the gather and whatever follows.  `who` names the entry in error messages.
-template <typename Consume>
-int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, const gams_names_t *chr, const char *bytes,
-            uint64_t n_bytes, bool order, Consume consume) {
-    GAMS_HIP(h, hipSetDevice(h->device));
-    while (h->kq.size() < (size_t)RG_STAGES) {
-        hipEvent_t a = nullptr, b = nullptr;
-        GAMS_HIP(h, hipEventCreate(&a));
-        GAMS_HIP(h, hipEventCreate(&b));
-        h->kq.emplace_back(a, b);
+// What the range entries ask of the loader: the whole line is the range, nothing else is kept of it, key (ctg, line).
+// A caller's own spec (PeakLoad, below) has the same members:
+//   mid_bits  31: the start of a kept line is the key's middle field, (ctg, start, line); 0: none
+//   efield    the message for a line its parse kernel flags W_EFIELD: the words are read back with the offsets and
+//             the call is refused there, in front of every later check (nullptr: no such flag, no read-back)
+//   cols      its per-line columns, carved behind key' in the loader's pooled block
+//   parse     launches its parse kernel, which fills grp / qs / qe (and its columns) for every line
+struct RgPlain {
+    NameTab chr;
+    static constexpr uint32_t mid_bits = 0;
+    static constexpr const char *efield = nullptr;
+    void cols(Carver &, uint32_t) {}
+    void parse(const TextLines &tl, uint32_t *grp, uint32_t *qs, uint32_t *qe, unsigned long long *, uint32_t nbr, hipStream_t st) const {
+        hipLaunchKernelGGL(rg_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, chr, grp, qs, qe);
     }
+};
+
+// Runs the stages up to the sort (`order` false: up to the offsets, for a size query) as `spec` shapes them and calls
+// consume(cols, stage) -- stage(k, open) records the stopwatch event that opens or closes stage k -- which queues the
+// gather and whatever follows.  One host wait of its own besides text_front's, behind the offsets.  `who` names the entry
+// in error messages.
+template <typename Spec, typename Consume>
+int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, const char *bytes, uint64_t n_bytes,
+            bool order, Consume consume) {
+    GAMS_HIP(h, hipSetDevice(h->device));
+    GAMS_HIP(h, gams_stopwatch_reserve(h, RG_STAGES));
     hipStream_t st = h->compute;
-    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
+    const StageClock stage{h, st};
     PoolBlock s1(h, false);
     TextFront F(h);
     GAMS_TRY(h, who, stage(RG_LINES, true));
@@ -813,16 +828,19 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     uint32_t line_bits = 1, ctg_bits = 1;
     while (line_bits < 32u && (L - 1u) >> line_bits) ++line_bits;
     while (ctg_bits < 32u && n_ctg >> ctg_bits) ++ctg_bits;
+    const uint32_t key_bits = ctg_bits + spec.mid_bits + line_bits;      // (at most 64 without a middle field)
+    if (key_bits > 64u)
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": (ctg, start, line) does not fit a 64-bit sort key (use the host path)");
     const uint32_t nbr = (L + 255u) / 256u;
     size_t sort_bytes = 0;
     GAMS_TRY(h, who, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                              (size_t)L, 0u, line_bits + ctg_bits, st));
+                                              (size_t)L, 0u, key_bits, st));
     const size_t n_tab = std::max<uint64_t>(n_ctg, 1), b_tab = gams_align256(n_tab * 4);
     unsigned long long *d_starts = nullptr, *d_key = nullptr, *d_key2 = nullptr, *d_off = nullptr;
     uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr, *d_first = nullptr, *d_count = nullptr;
     int64_t *d_hit = nullptr;
     uint8_t *d_sort = nullptr;
-    auto cols = [&](Carver &c) {   // starts | grp qs qe | hit key key' | first count | bucket_off | sort storage
+    auto cols = [&](Carver &c) {   // starts | grp qs qe | hit key key' | the spec's | first count | bucket_off | sort storage
         d_starts = c.take<unsigned long long>((size_t)F.nl + 2);
         d_grp = c.take<uint32_t>(L);
         d_qs = c.take<uint32_t>(L);
@@ -830,6 +848,7 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
         d_hit = c.take<int64_t>(L);
         d_key = c.take<unsigned long long>(L);
         d_key2 = c.take<unsigned long long>(L);
+        spec.cols(c, L);
         d_first = c.take<uint32_t>(n_tab);
         d_count = c.take<uint32_t>(n_tab);
         d_off = c.take<unsigned long long>(n_ctg + 1);
@@ -842,9 +861,10 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     GAMS_TRY(h, who, hipMemsetAsync(d_first, 0xff, b_tab, st));
     GAMS_TRY(h, who, hipMemsetAsync(d_count, 0, b_tab, st));
     GAMS_TRY(h, who, stage(RG_LINES, false));
-    const TextLines tl{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
+    C.t = TextLines{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
+    C.words = F.d_words;
     GAMS_TRY(h, who, stage(RG_PARSE, true));
-    hipLaunchKernelGGL(rg_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, chr->t, d_grp, d_qs, d_qe);
+    spec.parse(C.t, d_grp, d_qs, d_qe, F.d_words, nbr, st);
     GAMS_TRY(h, who, stage(RG_PARSE, false));
     GAMS_TRY(h, who, stage(RG_LOCATE, true));
     launch_interval_locate(ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
@@ -854,7 +874,7 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     GAMS_TRY(h, who, stage(RG_FIRST, false));
     GAMS_TRY(h, who, stage(RG_KEEP, true));
     hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
-                       (const uint32_t *)nullptr, 0u);
+                       spec.mid_bits ? (const uint32_t *)d_qs : (const uint32_t *)nullptr, (uint32_t)spec.mid_bits);
     GAMS_TRY(h, who, stage(RG_KEEP, false));
     GAMS_TRY(h, who, stage(RG_OFFSETS, true));
     hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, d_off, F.d_words,
@@ -863,13 +883,15 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, c
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, hipMemcpyAsync(h_off, d_off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
     if (n_ctg) GAMS_TRY(h, who, hipMemcpyAsync(h_first, d_first, n_ctg * 4, hipMemcpyDeviceToHost, st));
+    if (spec.efield) GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
     GAMS_TRY(h, who, hipStreamSynchronize(st));
+    if (spec.efield && h->pin_scratch[W_EFIELD]) return gams_fail(h, GAMS_EINVAL, who + spec.efield);
     C.n_kept = h_off[n_ctg];
     if (C.n_kept > 0xfffffff0ull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 16 kept ranges");
     C.ran = true;
     if (!order) return consume(C, stage);            // a size query: nothing is gathered, so nothing is sorted
     GAMS_TRY(h, who, stage(RG_ORDER, true));
-    if (C.n_kept) GAMS_TRY(h, who, rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, line_bits + ctg_bits, st));
+    if (C.n_kept) GAMS_TRY(h, who, rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, key_bits, st));
     GAMS_TRY(h, who, stage(RG_ORDER, false));
     if (C.n_kept) {
         C.g.key = d_key2;
@@ -892,13 +914,15 @@ void rg_timed(gams_gpu_t *h, int n) {
 
 
 // ---- `gams peak` on the device (utils.rs:83-116 read_peak, then peak.rs:41-160): the bytes of a wave TSV -> Peak rows --
-// Stages behind the line index (one lane per line up to the sort, one lane per kept peak behind it):
-//   parse    parts[0] (the line up to its first tab) through Range::from_str; a valid range needs parts[2], the signal;
-//            where the chromosome, the "name." prefix and the signal lie in the input;
-//   locate, first, keep, offsets   the range loader's (above), with the key (ctg, start, line): utils.rs:109-112 drops the
-//            first located line of a ctg, peak.rs:49 sorts the rest by start, stably;
-//   order    ONE radix sort of those 64-bit keys.  The line number makes the keys unique and breaks ties on start in
-//            file order, which is what the reference's stable sort leaves; a key wider than 64 bits is refused;
+// The range loader itself (rg_load with the PeakLoad spec), then three stages of its own; ten stages in all:
+//   lines .. order   the loader's, with these differences:
+//     parse    peak_parse_kernel: parts[0] (the line up to its first tab) through Range::from_str; a valid range needs
+//              parts[2], the signal (else W_EFIELD: refused at the loader's read-back of the offsets); five more columns
+//              per line say where the chromosome, the "name." prefix and the signal lie in the input;
+//     keep     the key is (ctg, start, line): utils.rs:109-112 drops the first located line of a ctg, peak.rs:49 sorts
+//              the rest by start, stably;
+//     order    the line number makes the keys unique and breaks ties on start in file order, which is what the
+//              reference's stable sort leaves; a key wider than 64 bits is refused;
 //   gc       gather (line, ctg, start, end) through the sorted keys, check every kept peak against its ctg and the ctg
 //            for a sequence (flags), then round4(range_gc) of every kept peak (sw.hip);
 //   rows     the length of every row (it reads the neighbours' end / start / gc / signal inside the bucket), their block
@@ -949,6 +973,25 @@ __global__ __launch_bounds__(256) void peak_parse_kernel(const TextLines t, cons
     p.slen[i] = (uint32_t)(se - sb);
 }
 
+// what peak asks of the loader (see RgPlain)
+struct PeakLoad {
+    NameTab chr;
+    PeakLines pl;
+    static constexpr uint32_t mid_bits = 31;
+    static constexpr const char *efield = ": a row has no signal column (the reference panics, utils.rs:102)";
+    void cols(Carver &c, uint32_t L) {
+        pl.cb = c.take<unsigned long long>(L);
+        pl.sb = c.take<unsigned long long>(L);
+        pl.clen = c.take<uint32_t>(L);
+        pl.slen = c.take<uint32_t>(L);
+        pl.nlen = c.take<uint32_t>(L);
+    }
+    void parse(const TextLines &tl, uint32_t *grp, uint32_t *qs, uint32_t *qe, unsigned long long *words, uint32_t nbr,
+               hipStream_t st) const {
+        hipLaunchKernelGGL(peak_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, chr, grp, qs, qe, pl, words);
+    }
+};
+
 struct PeakArgs {
     TextLines t;
     PeakLines p;
@@ -986,44 +1029,9 @@ __global__ __launch_bounds__(256) void peak_gather_kernel(const PeakArgs a) {
     if (a.seq_len[c] == 0u) a.words[W_ENOSEQ] = 1ull;
 }
 
-// a row's bytes: written at q, or only counted (q == nullptr)
-struct RowOut {
-    char *q;
-    uint32_t n;
-    __device__ __forceinline__ void bytes(const char *src, uint32_t len) {
-        if (q) q = put_bytes(q, src, len);
-        n += len;
-    }
-    __device__ __forceinline__ void ch(char c) {
-        if (q) *q++ = c;
-        ++n;
-    }
-    __device__ __forceinline__ void dec(uint32_t v) {
-        if (q) q = put_dec(q, v);
-        n += dec_digits(v);
-    }
-    __device__ __forceinline__ void i32(int32_t v) {
-        if (q) q = put_i32(q, v);
-        n += i32_len(v);
-    }
-    __device__ __forceinline__ void f4(float v, bool &bad) {           // a round4 value
-        const uint32_t l = sw_put_f4(q, v, &bad);
-        if (q) q += l;
-        n += l;
-    }
-    __device__ __forceinline__ void f32s(float v, bool &bad) {         // `{}` of an amplitude
-        uint32_t l = gams_fmt_f32_short(v, q);
-        if (l == 0u) {
-            bad = true;
-            l = 1u;
-        }
-        if (q) q += l;
-        n += l;
-    }
-};
-
-// peak.rs:65-158 for kept peak k, as gams_host_peak prints it; returns the row's length
-__device__ uint32_t peak_row(const PeakArgs &a, uint32_t k, char *q, bool &bad) {
+// peak.rs:65-158 for kept peak k, as gams_host_peak prints it
+template <bool kWrite>
+__device__ void peak_row(const PeakArgs &a, uint32_t k, RowOut<kWrite> &o, bool &bad) {
     const uint32_t c = a.kctg[k];
     const uint32_t o0 = (uint32_t)a.bucket_off[c], o1 = (uint32_t)a.bucket_off[c + 1u];
     const bool has_prev = k > o0, has_next = k + 1u < o1;
@@ -1033,7 +1041,6 @@ __device__ uint32_t peak_row(const PeakArgs &a, uint32_t k, char *q, bool &bad) 
     const uint32_t prev_end = has_prev ? a.ke[k - 1u] : (uint32_t)a.cs[c];           // peak.rs:112-133
     const uint32_t next_start = has_next ? a.ks[k + 1u] : (uint32_t)a.ce[c];         // peak.rs:135-157
     const char *in_ = a.t.in;
-    RowOut o{q, 0u};
     o.bytes("peak:", 5u);
     const unsigned long long io = a.ids.off[c];
     o.bytes(a.ids.bytes + io, (uint32_t)(a.ids.off[c + 1u] - io));
@@ -1067,15 +1074,18 @@ __device__ uint32_t peak_row(const PeakArgs &a, uint32_t k, char *q, bool &bad) 
     o.ch('\t');
     o.bytes(in_ + a.p.sb[in], a.p.slen[in]);
     o.ch('\n');
-    return o.n;
 }
 
 __global__ __launch_bounds__(256) void peak_row_len_kernel(const PeakArgs a) {
     __shared__ uint64_t ws[4];
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     bool bad = false;
-    const uint32_t l = k < a.n_kept ? peak_row(a, k, nullptr, bad) : 0u;
-    if (k < a.n_kept) a.row_len[k] = l;
+    RowOut<false> n;
+    if (k < a.n_kept) {
+        peak_row(a, k, n, bad);
+        a.row_len[k] = n.n;
+    }
+    const uint32_t l = n.n;
     if (bad) a.words[W_UNSUP] = 1ull;
     uint64_t tot;
     (void)block_excl_scan_256<uint64_t>((uint64_t)l, ws, tot);
@@ -1100,14 +1110,15 @@ __global__ __launch_bounds__(256) void peak_row_write_kernel(const PeakArgs a) {
         const uint32_t c = a.kctg[k];
         if (k == (uint32_t)a.bucket_off[c]) a.text_off[c] = blk0 + rel;
         bool bad = false;                      // (the length pass flagged what has no text: nothing is written then)
-        (void)peak_row(a, k, staged ? stage + mis + (uint32_t)rel : a.text + blk0 + rel, bad);
+        RowOut<true> o{staged ? stage + mis + (uint32_t)rel : a.text + blk0 + rel};
+        peak_row(a, k, o, bad);
     }
     if (!staged) return;
     __syncthreads();
     stage_flush_256(stage, mis, (uint32_t)tot, a.text + blk0);
 }
 
-enum : int { PK_LINES = 0, PK_PARSE, PK_LOCATE, PK_FIRST, PK_KEEP, PK_OFFSETS, PK_ORDER, PK_GC, PK_ROWS, PK_WRITE, PK_STAGES };
+enum : int { PK_GC = RG_GATHER, PK_ROWS, PK_WRITE, PK_STAGES };   // behind the loader's lines .. order
 
 struct PeakJob {
     gams_seqset_t *s;
@@ -1135,35 +1146,14 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
     GAMS_HIP(h, hipSetDevice(h->device));
     const int rc_gc = gams_seqset_gcindex(h, J.s);             // GAMS_ESTATE for a plane-only seqset
     if (rc_gc != GAMS_OK) return rc_gc;
-    while (h->kq.size() < (size_t)PK_STAGES) {
-        hipEvent_t a = nullptr, b = nullptr;
-        GAMS_HIP(h, hipEventCreate(&a));
-        GAMS_HIP(h, hipEventCreate(&b));
-        h->kq.emplace_back(a, b);
-    }
+    GAMS_HIP(h, gams_stopwatch_reserve(h, PK_STAGES));
     hipStream_t st = h->compute;
-    auto stage = [&](int k, bool open) { return hipEventRecord(open ? h->kq[(size_t)k].first : h->kq[(size_t)k].second, st); };
-    PoolBlock s1(h, false), s2(h, false), d_tab(h, false), pin(h, true), d_text(h, false);
-    TextFront F(h);
-    GAMS_TRY(h, who, stage(PK_LINES, true));
-    const int rc_front = text_front(h, who, bytes, n_bytes, F);
-    if (rc_front != GAMS_OK) return rc_front;
-    const uint32_t L = F.L;
-    if (L == 0) return GAMS_OK;
-    uint32_t line_bits = 1, ctg_bits = 1;
-    while (line_bits < 32u && (L - 1u) >> line_bits) ++line_bits;
-    while (ctg_bits < 32u && n_ctg >> ctg_bits) ++ctg_bits;
-    const uint32_t key_bits = ctg_bits + 31u + line_bits;
-    if (key_bits > 64u)
-        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": (ctg, start, line) does not fit a 64-bit sort key (use the host path)");
-    const uint32_t nbr = (L + 255u) / 256u;
-    size_t sort_bytes = 0;
-    GAMS_TRY(h, who, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
-                                              (size_t)L, 0u, key_bits, st));
-    // the per-ctg tables: one page-locked image, one copy (the offsets and the text offsets come back into it)
+    // the per-ctg tables: one page-locked image, one copy, queued in front of the loader (the text offsets come back
+    // into the image)
+    PoolBlock d_tab(h, false), pin(h, true);
     const size_t n_tab = std::max<uint64_t>(n_ctg, 1);
     struct Tabs {
-        unsigned long long *seq_off, *off, *toff;
+        unsigned long long *seq_off, *toff;
         int32_t *cs, *ce;
         uint32_t *seq_len;
     };
@@ -1173,7 +1163,6 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
         t.cs = c.take<int32_t>(n_tab);
         t.ce = c.take<int32_t>(n_tab);
         t.seq_len = c.take<uint32_t>(n_tab);
-        t.off = c.take<unsigned long long>(n_ctg + 1);
         t.toff = c.take<unsigned long long>(n_ctg + 1);
         return t;
     };
@@ -1188,137 +1177,84 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
         ht.cs[c] = J.chr_start[c];
         ht.ce[c] = J.chr_end[c];
     }
-    const size_t b_in = reinterpret_cast<uint8_t *>(ht.off) - pin.p;     // the four input columns
+    const size_t b_in = reinterpret_cast<uint8_t *>(ht.toff) - pin.p;    // the four input columns
     GAMS_TRY(h, who, hipMemcpyAsync(d_tab.p, pin.p, b_in, hipMemcpyHostToDevice, st));
-    unsigned long long *d_starts = nullptr, *d_key = nullptr, *d_key2 = nullptr;
-    uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr, *d_first = nullptr, *d_count = nullptr;
-    int64_t *d_hit = nullptr;
-    uint8_t *d_sort = nullptr;
-    PeakLines pl{};
-    auto cols = [&](Carver &c) {   // starts | grp qs qe | hit key key' | the fields | first count | sort storage
-        d_starts = c.take<unsigned long long>((size_t)F.nl + 2);
-        d_grp = c.take<uint32_t>(L);
-        d_qs = c.take<uint32_t>(L);
-        d_qe = c.take<uint32_t>(L);
-        d_hit = c.take<int64_t>(L);
-        d_key = c.take<unsigned long long>(L);
-        d_key2 = c.take<unsigned long long>(L);
-        pl.cb = c.take<unsigned long long>(L);
-        pl.sb = c.take<unsigned long long>(L);
-        pl.clen = c.take<uint32_t>(L);
-        pl.slen = c.take<uint32_t>(L);
-        pl.nlen = c.take<uint32_t>(L);
-        d_first = c.take<uint32_t>(n_tab);
-        d_count = c.take<uint32_t>(n_tab);
-        d_sort = c.take<uint8_t>(std::max<size_t>(sort_bytes, 1));
-    };
-    GAMS_TRY(h, who, s1.alloc(layout_bytes(cols)));
-    carve(s1.p, cols);
-    const size_t b_tab = gams_align256(n_tab * 4);
-    hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, h->text->d_in, n_bytes, F.n16, F.d_bnloff, F.nl,
-                       d_starts);
-    GAMS_TRY(h, who, hipMemsetAsync(d_first, 0xff, b_tab, st));
-    GAMS_TRY(h, who, hipMemsetAsync(d_count, 0, b_tab, st));
-    GAMS_TRY(h, who, stage(PK_LINES, false));
-    const TextLines tl{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
-    GAMS_TRY(h, who, stage(PK_PARSE, true));
-    hipLaunchKernelGGL(peak_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, J.chr->t, d_grp, d_qs, d_qe, pl, F.d_words);
-    GAMS_TRY(h, who, stage(PK_PARSE, false));
-    GAMS_TRY(h, who, stage(PK_LOCATE, true));
-    launch_interval_locate(J.ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
-    GAMS_TRY(h, who, stage(PK_LOCATE, false));
-    GAMS_TRY(h, who, stage(PK_FIRST, true));
-    hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
-    GAMS_TRY(h, who, stage(PK_FIRST, false));
-    GAMS_TRY(h, who, stage(PK_KEEP, true));
-    hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
-                       (const uint32_t *)d_qs, 31u);
-    GAMS_TRY(h, who, stage(PK_KEEP, false));
-    GAMS_TRY(h, who, stage(PK_OFFSETS, true));
-    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, dt.off, F.d_words,
-                       (uint32_t)W_ROWS);
-    GAMS_TRY(h, who, stage(PK_OFFSETS, false));
-    GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(ht.off, dt.off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
-    if (h->pin_scratch[W_EFIELD])
-        return gams_fail(h, GAMS_EINVAL, who + ": a row has no signal column (the reference panics, utils.rs:102)");
-    const uint64_t n_kept = ht.off[n_ctg];
-    if (n_kept == 0) return GAMS_OK;
-    const uint32_t K = (uint32_t)n_kept, nbk = (K + 255u) / 256u;        // n_kept <= L < 2^32
-    GAMS_TRY(h, who, stage(PK_ORDER, true));
-    GAMS_TRY(h, who, rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, key_bits, st));
-    GAMS_TRY(h, who, stage(PK_ORDER, false));
-    PeakArgs a{};
-    a.t = tl;
-    a.p = pl;
-    a.key = d_key2;
-    a.line_bits = line_bits;
-    a.n_kept = K;
-    a.qs = d_qs;
-    a.qe = d_qe;
-    a.bucket_off = dt.off;
-    a.cs = dt.cs;
-    a.ce = dt.ce;
-    a.seq_len = dt.seq_len;
-    a.ids = J.ids->t;
-    a.text_off = dt.toff;
-    a.words = F.d_words;
-    auto kept = [&](Carver &c) {   // line ctg start end | gc | row lengths | the blocks' bytes and prefix
-        a.kline = c.take<uint32_t>(K);
-        a.kctg = c.take<uint32_t>(K);
-        a.ks = c.take<uint32_t>(K);
-        a.ke = c.take<uint32_t>(K);
-        a.gc = c.take<float>(K);
-        a.row_len = c.take<uint32_t>(K);
-        a.blk_bytes = c.take<unsigned long long>((size_t)nbk + 1);
-        unsigned long long *const off = c.take<unsigned long long>((size_t)nbk + 1);
-        a.blk_off = off;
-        return off;
-    };
-    GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
-    unsigned long long *const d_blk_off = carve(s2.p, kept);
-    GAMS_TRY(h, who, stage(PK_GC, true));
-    hipLaunchKernelGGL(peak_gather_kernel, dim3(nbk), dim3(256), 0, st, a);
-    gams_launch_range_gc_cols(J.s, dt.seq_off, dt.seq_len, dt.cs, a.kctg, a.ks, a.ke, K, a.gc, st);
-    GAMS_TRY(h, who, stage(PK_GC, false));
-    GAMS_TRY(h, who, stage(PK_ROWS, true));
-    hipLaunchKernelGGL(peak_row_len_kernel, dim3(nbk), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbk, d_blk_off,
-                       F.d_words, (uint32_t)W_BYTES);
-    GAMS_TRY(h, who, stage(PK_ROWS, false));
-    GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
-    const unsigned long long *w = h->pin_scratch;
-    if (w[W_EID])
-        return gams_fail(h, GAMS_EINVAL, who + ": a peak is not inside its ctg (the reference panics on the slice, utils.rs:155)");
-    if (w[W_ENOSEQ]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with peaks has no sequence in the seqset");
-    if (w[W_UNSUP])
-        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a gc or an amplitude the device formatters do not cover (use the host path)");
-    const uint64_t tb = w[W_BYTES];
-    gams_text_state *T = h->text;
-    char *&out = T->out[K_PEAK];
-    size_t &out_cap = T->out_cap[K_PEAK];
-    GAMS_TRY(h, who, gams_pool_grow(h, true, &out, &out_cap, tb, tb));
-    GAMS_TRY(h, who, d_text.alloc(tb));
-    a.text = reinterpret_cast<char *>(d_text.p);
-    GAMS_TRY(h, who, stage(PK_WRITE, true));
-    hipLaunchKernelGGL(peak_row_write_kernel, dim3(nbk), dim3(256), 0, st, a);
-    GAMS_TRY(h, who, stage(PK_WRITE, false));
-    GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(out, d_text.p, tb, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipMemcpyAsync(ht.toff, dt.toff, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
-    // a ctg without rows begins where the next one does
-    text_off[n_ctg] = tb;
-    for (uint64_t c = n_ctg; c-- > 0;) text_off[c] = ht.off[c + 1] > ht.off[c] ? ht.toff[c] : text_off[c + 1];
-    rg_timed(h, PK_STAGES);
-    *text = out;
-    *text_bytes = tb;
-    *n_rows = n_kept;
-    return GAMS_OK;
+    PeakLoad load{J.chr->t, PeakLines{}};
+    return rg_load(h, who, J.ctg_ix, load, bytes, n_bytes, true, [&](const RgCols &C, const StageClock &stage) -> int {
+        // (no rg_timed on the two early ends: an input without lines, or without a kept line, leaves the stopwatch invalid)
+        if (C.n_kept == 0) return GAMS_OK;
+        const uint32_t K = (uint32_t)C.n_kept, nbk = (K + 255u) / 256u;  // n_kept <= L < 2^32
+        PoolBlock s2(h, false), d_text(h, false);
+        PeakArgs a{};
+        a.t = C.t;
+        a.p = load.pl;
+        a.key = C.g.key;
+        a.line_bits = (uint32_t)__builtin_popcountll(C.g.line_mask);
+        a.n_kept = K;
+        a.qs = C.g.qs;
+        a.qe = C.g.qe;
+        a.bucket_off = C.g.bucket_off;
+        a.cs = dt.cs;
+        a.ce = dt.ce;
+        a.seq_len = dt.seq_len;
+        a.ids = J.ids->t;
+        a.text_off = dt.toff;
+        a.words = C.words;
+        auto kept = [&](Carver &c) {   // line ctg start end | gc | row lengths | the blocks' bytes and prefix
+            a.kline = c.take<uint32_t>(K);
+            a.kctg = c.take<uint32_t>(K);
+            a.ks = c.take<uint32_t>(K);
+            a.ke = c.take<uint32_t>(K);
+            a.gc = c.take<float>(K);
+            a.row_len = c.take<uint32_t>(K);
+            a.blk_bytes = c.take<unsigned long long>((size_t)nbk + 1);
+            unsigned long long *const off = c.take<unsigned long long>((size_t)nbk + 1);
+            a.blk_off = off;
+            return off;
+        };
+        GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
+        unsigned long long *const d_blk_off = carve(s2.p, kept);
+        GAMS_TRY(h, who, stage(PK_GC, true));
+        hipLaunchKernelGGL(peak_gather_kernel, dim3(nbk), dim3(256), 0, st, a);
+        gams_launch_range_gc_cols(J.s, dt.seq_off, dt.seq_len, dt.cs, a.kctg, a.ks, a.ke, K, a.gc, st);
+        GAMS_TRY(h, who, stage(PK_GC, false));
+        GAMS_TRY(h, who, stage(PK_ROWS, true));
+        hipLaunchKernelGGL(peak_row_len_kernel, dim3(nbk), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbk, d_blk_off,
+                           C.words, (uint32_t)W_BYTES);
+        GAMS_TRY(h, who, stage(PK_ROWS, false));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, C.words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
+        const unsigned long long *w = h->pin_scratch;
+        if (w[W_EID])
+            return gams_fail(h, GAMS_EINVAL, who + ": a peak is not inside its ctg (the reference panics on the slice, utils.rs:155)");
+        if (w[W_ENOSEQ]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with peaks has no sequence in the seqset");
+        if (w[W_UNSUP])
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a gc or an amplitude the device formatters do not cover (use the host path)");
+        const uint64_t tb = w[W_BYTES];
+        gams_text_state *T = h->text;
+        char *&out = T->out[K_PEAK];
+        size_t &out_cap = T->out_cap[K_PEAK];
+        GAMS_TRY(h, who, gams_pool_grow(h, true, &out, &out_cap, tb, tb));
+        GAMS_TRY(h, who, d_text.alloc(tb));
+        a.text = reinterpret_cast<char *>(d_text.p);
+        GAMS_TRY(h, who, stage(PK_WRITE, true));
+        hipLaunchKernelGGL(peak_row_write_kernel, dim3(nbk), dim3(256), 0, st, a);
+        GAMS_TRY(h, who, stage(PK_WRITE, false));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipMemcpyAsync(out, d_text.p, tb, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipMemcpyAsync(ht.toff, dt.toff, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
+        // a ctg without rows begins where the next one does
+        text_off[n_ctg] = tb;
+        for (uint64_t c = n_ctg; c-- > 0;) text_off[c] = C.bucket_off[c + 1] > C.bucket_off[c] ? ht.toff[c] : text_off[c + 1];
+        rg_timed(h, PK_STAGES);
+        *text = out;
+        *text_bytes = tb;
+        *n_rows = C.n_kept;
+        return GAMS_OK;
+    });
 }
 
 
@@ -1404,13 +1340,8 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         const int rc_gc = gams_seqset_gcindex(h, J.s);             // GAMS_ESTATE for a plane-only seqset
         if (rc_gc != GAMS_OK) return rc_gc;
     }
-    while (h->kq.size() < (size_t)SWF_STAGES) {
-        hipEvent_t a = nullptr, b = nullptr;
-        GAMS_HIP(h, hipEventCreate(&a));
-        GAMS_HIP(h, hipEventCreate(&b));
-        h->kq.emplace_back(a, b);
-    }
-    return rg_load(h, who, J.ctg_ix, J.chr, bytes, n_bytes, true, [&](const RgCols &C, auto stage) -> int {
+    GAMS_HIP(h, gams_stopwatch_reserve(h, SWF_STAGES));
+    return rg_load(h, who, J.ctg_ix, RgPlain{J.chr->t}, bytes, n_bytes, true, [&](const RgCols &C, const StageClock &stage) -> int {
         *n_features = C.n_kept;
         if (C.n_kept == 0) {
             if (C.ran) rg_timed(h, RG_ORDER + 1);
@@ -1617,7 +1548,7 @@ int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_nam
         return gams_fail(h, GAMS_EINVAL, "gpu_read_range_text: null argument");
     const std::string who = "gpu_read_range_text";
     *n_kept = 0;
-    return rg_load(h, who, ctg_ix, chr_names, bytes, n_bytes, cap != 0, [&](const RgCols &C, auto stage) -> int {
+    return rg_load(h, who, ctg_ix, RgPlain{chr_names->t}, bytes, n_bytes, cap != 0, [&](const RgCols &C, const StageClock &stage) -> int {
         for (uint64_t i = 0; i <= C.n_ctg; ++i) bucket_off[i] = C.bucket_off[i];
         if (seen)
             for (uint64_t i = 0; i < C.n_ctg; ++i) seen[i] = C.first[i] != UINT32_MAX;
@@ -1664,7 +1595,7 @@ int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams
     const std::string who = "index_create_range_text";
     *rg_ix = nullptr;
     *n_kept = 0;
-    return rg_load(h, who, ctg_ix, chr_names, bytes, n_bytes, true, [&](const RgCols &C, auto stage) -> int {
+    return rg_load(h, who, ctg_ix, RgPlain{chr_names->t}, bytes, n_bytes, true, [&](const RgCols &C, const StageClock &stage) -> int {
         uint32_t max_n = 0;
         for (uint64_t i = 0; i < C.n_ctg; ++i)
             max_n = std::max<uint32_t>(max_n, (uint32_t)(C.bucket_off[i + 1] - C.bucket_off[i]));

@@ -1,12 +1,14 @@
 // text_emit.hpp -- what the device paths that write finished TSV text share (device only): the wave rows and
 // `--signal` rows (wave_rows.hpp), the `sw` rows (sw.hip), the `locate` / `locate --count` / `anno` / `peak` rows (text.hip).
-// Decimal output, the workgroup sum behind a block's byte count, the one-workgroup prefix over those counts, and
-// the copy of a block's text from its LDS stage to the global text, and the round4 float format of the `sw` and
-// `peak` rows (sw_put_f4).  The row composers and the other float formats (gctab lookup; gams_fmt_prop4 and
-// gams_fmt_f32_short, text_fmt.hpp) stay with their owners.
+// Decimal output, the round4 float format of the `sw` and `peak` rows (sw_put_f4), RowOut -- the field sequence of a row
+// written once, for the pass that counts its bytes and the pass that writes them --, the workgroup sum behind a block's
+// byte count, the one-workgroup prefix over those counts, and the copy of a block's text from its LDS stage to the
+// global text.  The row composers and the gctab lookup stay with their owners; the other two float formats
+// (gams_fmt_prop4 and gams_fmt_f32_short) are text_fmt.hpp's, which the host layer shares.
 #pragma once
 
 #include "common.hpp"
+#include "text_fmt.hpp"
 
 namespace {
 
@@ -76,6 +78,45 @@ __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
     }
     return n;
 }
+
+// The bytes of one row.  A row is described once, as a sequence of fields put to a RowOut: RowOut<false> only adds up
+// their lengths in n, RowOut<true> writes them at q.  Len is the type of a length (a line echoed by the text entries
+// may pass 4 GB).  `bad` is set for a value that has no text of the reference's.
+template <bool kWrite, typename Len = uint32_t>
+struct RowOut;
+template <typename Len>
+struct RowOut<false, Len> {
+    Len n = 0;
+    __device__ __forceinline__ void bytes(const char *, Len len) { n += len; }
+    __device__ __forceinline__ void ch(char) { ++n; }
+    __device__ __forceinline__ void dec(uint32_t v) { n += dec_digits(v); }
+    __device__ __forceinline__ void i32(int32_t v) { n += i32_len(v); }
+    __device__ __forceinline__ void f4(float v, bool &bad) { n += sw_put_f4(nullptr, v, &bad); }   // a round4 value
+    __device__ __forceinline__ void prop4(float) { n += 6u; }                                      // `{:.4}` of a prop in [0, 1]
+    __device__ __forceinline__ void f32s(float v, bool &bad) {                                     // `{}` of an amplitude
+        const uint32_t l = gams_fmt_f32_short(v, nullptr);
+        if (l == 0u) bad = true;
+        n += l ? l : 1u;
+    }
+};
+template <typename Len>
+struct RowOut<true, Len> {
+    char *q;
+    __device__ __forceinline__ void bytes(const char *src, Len len) { q = put_bytes(q, src, len); }
+    __device__ __forceinline__ void ch(char c) { *q++ = c; }
+    __device__ __forceinline__ void dec(uint32_t v) { q = put_dec(q, v); }
+    __device__ __forceinline__ void i32(int32_t v) { q = put_i32(q, v); }
+    __device__ __forceinline__ void f4(float v, bool &bad) { q += sw_put_f4(q, v, &bad); }
+    __device__ __forceinline__ void prop4(float v) {       // (the counting pass flags a prop outside [0, 1]: nothing is written)
+        (void)gams_fmt_prop4(v, q);
+        q += 6;
+    }
+    __device__ __forceinline__ void f32s(float v, bool &bad) {
+        const uint32_t l = gams_fmt_f32_short(v, q);
+        if (l == 0u) bad = true;
+        q += l ? l : 1u;
+    }
+};
 
 // Sum of v over a 256-thread workgroup (4 waves); `ws` is LDS scratch of 4 elements, the call holds one barrier.
 __device__ __forceinline__ uint32_t block_sum_256(uint32_t v, uint32_t *ws) {

@@ -120,6 +120,29 @@ def test_entry_slices_determinism_and_refusals(eng, synth):
         ss.close()
 
 
+def test_early_ends_and_the_row_without_a_signal(eng, synth):
+    """An input without lines, and one whose every located line is the first of its ctg (nothing kept): GAMS_OK, no text,
+    no rows, and the stopwatch of the call invalid (a full call in front of each leaves ten stages to forget).  A valid
+    range without a signal column is refused with its message, in front of every later check."""
+    ctgs, data, _ = synth
+    ss = engine.SeqSet(eng, seq_arrays(ctgs))
+    T = PeakTables(eng, ctgs)
+    ms, n = (C.c_float * 16)(), C.c_uint32()
+    try:
+        for early in (b"", b"I:5-9\t0.1\t1\nII:2000-2004\t0.2\t1\n"):       # two ctgs, one line in each
+            assert abi_peak(eng, T, ss, data)[0] == 0
+            assert L.gams_gpu_last_stage_ms(eng.h, ms, 16, C.byref(n)) == 0 and n.value == 10
+            rc, text, off, rows = abi_peak(eng, T, ss, early)
+            assert (rc, text, rows) == (0, b"", 0) and not off.any()
+            assert L.gams_gpu_last_stage_ms(eng.h, ms, 16, C.byref(n)) == _lib.ESTATE
+        # (the second line alone would end as above: nothing kept)
+        assert abi_peak(eng, T, ss, b"I:5-9\t0.1\nII:2000-2004\t0.2\t1\n")[0] == _lib.EINVAL
+        assert L.gams_gpu_last_error(eng.h) == b"gpu_peak_text: a row has no signal column (the reference panics, utils.rs:102)"
+    finally:
+        T.close()
+        ss.close()
+
+
 def test_missing_sequence_and_plane_only_seqset(eng, synth):
     ctgs, data, _ = synth
     seqs = seq_arrays(ctgs)
