@@ -562,30 +562,21 @@ __global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) 
         l[u] = r < a.n_rows ? a.len[r] : 0u;
         mine += l[u];
     }
-    uint32_t tot;
-    const uint32_t rel = block_excl_scan_256<uint32_t>(mine, scr, tot);
-    const uint64_t blk0 = a.blk_off[blockIdx.x];
-    const uint32_t mis = (uint32_t)(blk0 & 15u);
-    const bool fits = blk0 + tot <= a.text_cap;
-    const bool staged = tot <= kSwTextStage && fits;
-    uint32_t at = rel;
+    BlockWriter<uint32_t> w(mine, scr, a.blk_off, a.text, a.text_cap);
+    w.stage_if(w.tot <= kSwTextStage, stage);
+    uint32_t at = w.rel;
     bool bad = false;
 #pragma unroll
     for (uint32_t u = 0; u < 2u; ++u) {
         const uint64_t r = base + 2u * tid + u;
         if (r >= a.n_rows) break;
-        if (staged) {
-            RowOut<true> o{stage + mis + at};
+        w.put(at, [&](char *p) {
+            RowOut<true> o{p};
             sw_row_text(a, r, o, bad);
-        } else if (fits) {
-            RowOut<true> o{a.text + blk0 + at};
-            sw_row_text(a, r, o, bad);
-        }
+        });
         at += l[u];
     }
-    if (!staged) return;
-    __syncthreads();
-    stage_flush_256(stage, mis, tot, a.text + blk0);
+    w.flush();
 }
 
 // where every selected ctg's text begins: the bytes of the rows in front of its first row

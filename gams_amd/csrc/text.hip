@@ -1101,21 +1101,18 @@ __global__ __launch_bounds__(256) void peak_row_write_kernel(const PeakArgs a) {
     __shared__ __align__(16) char stage[kPeakStage + 16];
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     const uint64_t l = k < a.n_kept ? a.row_len[k] : 0ull;
-    uint64_t tot;
-    const uint64_t rel = block_excl_scan_256<uint64_t>(l, ws, tot);
-    const unsigned long long blk0 = a.blk_off[blockIdx.x];     // the block's first byte in the text
-    const uint32_t mis = (uint32_t)(blk0 & 15u);               // the stage starts at the same offset inside a 16-B unit
-    const bool staged = tot <= kPeakStage;                     // (the same for every lane of the block)
+    BlockWriter<uint64_t> w(l, ws, a.blk_off, a.text, ~0ull);   // (the text holds all rows: no bound)
+    w.stage_if(w.tot <= kPeakStage, stage);
     if (k < a.n_kept) {
         const uint32_t c = a.kctg[k];
-        if (k == (uint32_t)a.bucket_off[c]) a.text_off[c] = blk0 + rel;
+        if (k == (uint32_t)a.bucket_off[c]) a.text_off[c] = w.blk0 + w.rel;
         bool bad = false;                      // (the length pass flagged what has no text: nothing is written then)
-        RowOut<true> o{staged ? stage + mis + (uint32_t)rel : a.text + blk0 + rel};
-        peak_row(a, k, o, bad);
+        w.put(w.rel, [&](char *p) {
+            RowOut<true> o{p};
+            peak_row(a, k, o, bad);
+        });
     }
-    if (!staged) return;
-    __syncthreads();
-    stage_flush_256(stage, mis, (uint32_t)tot, a.text + blk0);
+    w.flush();
 }
 
 enum : int { PK_GC = RG_GATHER, PK_ROWS, PK_WRITE, PK_STAGES };   // behind the loader's lines .. order

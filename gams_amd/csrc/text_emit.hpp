@@ -2,8 +2,10 @@
 // `--signal` rows (wave_rows.hpp), the `sw` rows (sw.hip), the `locate` / `locate --count` / `anno` / `peak` rows (text.hip).
 // Decimal output, the round4 float format of the `sw` and `peak` rows (sw_put_f4), RowOut -- the field sequence of a row
 // written once, for the pass that counts its bytes and the pass that writes them --, the workgroup sum behind a block's
-// byte count, the one-workgroup prefix over those counts, and the copy of a block's text from its LDS stage to the
-// global text.  The row composers and the gctab lookup stay with their owners; the other two float formats
+// byte count, the one-workgroup prefix over those counts, the copy of a block's text from its LDS stage to the global
+// text, and BlockWriter -- the prefix inside a block, the choice between the stage and the text, and that copy, written
+// once for the four kernels that stage a block (`locate` / `anno` rows are never staged: text_row_write_kernel keeps its
+// own few lines).  The row composers and the gctab lookup stay with their owners; the other two float formats
 // (gams_fmt_prop4 and gams_fmt_f32_short) are text_fmt.hpp's, which the host layer shares.
 #pragma once
 
@@ -141,6 +143,47 @@ __device__ __forceinline__ void stage_flush_256(const char *stage, uint32_t mis,
     const uint32_t done = head + (units << 4);
     if (tid < tot - done) dst[done + tid] = stage[mis + done + tid];
 }
+
+// The writer of a block's rows, one contiguous stretch of the text.  Every thread of a workgroup of 256 gives the bytes
+// of its own rows (`mine`): `rel` is where they begin inside the block, `tot` the block's bytes, blk0 = blk_off[block]
+// its first byte in the text.  A block that fits the kernel's stage -- stage_if(tot <= its bound, stage): 16-B aligned
+// LDS of that bound + 16 bytes, begun at the offset blk0 has inside a 16-B unit, where a row's single-byte stores cost
+// nothing -- is put together there and leaves through flush() as 16-B stores; a longer one is written to the text
+// directly, and one that would end beyond text_cap is not written at all.  T is the type of the scan, `scr` its 4
+// elements of LDS.
+template <typename T>
+struct BlockWriter {
+    char *stage = nullptr, *dst;     // dst: the block's first byte
+    T rel, tot;
+    uint64_t blk0;
+    uint32_t mis;
+    bool staged = false, fits;       // (the same for every thread of the block)
+    __device__ __forceinline__ BlockWriter(T mine, T *scr, const unsigned long long *blk_off, char *text, uint64_t text_cap) {
+        rel = block_excl_scan_256<T>(mine, scr, tot);
+        blk0 = blk_off[blockIdx.x];
+        dst = text + blk0;
+        mis = (uint32_t)(blk0 & 15u);
+        fits = blk0 + tot <= text_cap;
+    }
+    __device__ __forceinline__ void stage_if(bool small, char *stage_) {
+        stage = stage_;
+        staged = small && fits;
+    }
+    // row(p) writes the row that begins `off` bytes into the block at p, where it goes
+    template <typename F>
+    __device__ __forceinline__ void put(T off, F row) const {
+        if (staged)
+            row(stage + mis + (uint32_t)off);
+        else if (fits)
+            row(dst + off);
+    }
+    // behind the block's last put()
+    __device__ __forceinline__ void flush() const {
+        if (!staged) return;
+        __syncthreads();
+        stage_flush_256(stage, mis, (uint32_t)tot, dst);
+    }
+};
 
 // exclusive prefix of nb block counts (one workgroup of 1024): blk_off[b] = bytes in front of block b, the total
 // into blk_off[nb] and words[slot]

@@ -47,8 +47,6 @@
 #include "wave_rows.hpp"
 #include "wave_select.hpp"
 
-#include <charconv>
-
 // The instance list of wave_select.hpp as kernel pointers, a false / true pair (NT) per tuple: every wave_fast_kernel
 // and wave_fast_taper_kernel instantiation has the one signature, wave_tile_kernel the other.
 using WaveFastFn = void (*)(const WaveTile *, const uint8_t *, WaveArgs);
@@ -70,9 +68,7 @@ static const WaveTileFn kWaveTileFn[2][2] = {{wave_tile_kernel<uint8_t, false>, 
 struct WaveRows {
     uint32_t dmax = 0, max_name = 0;
     Kept<uint8_t> arena;                      // RowCtg[n_ctg] | names | gc text table | words[4 + n_ctg + 1]
-    RowCtg *d_ctgs = nullptr;
-    char *d_names = nullptr;
-    uint8_t *d_gctab = nullptr;
+    RowTabsDev tabs;
     unsigned long long *d_words = nullptr;     // [0] records, [1] text bytes, [2] peaks, [3] fullest tile, [4 ..] ctg_off[n_ctg + 1]
     Kept<uint8_t> tmp;                        // per-record and per-block tables, room for `cap` records
     uint64_t cap = 0;
@@ -104,9 +100,7 @@ struct WaveSig {
     SigTile *d_tiles = nullptr;
     uint32_t *d_blk_len = nullptr;
     unsigned long long *d_blk_off = nullptr, *d_words = nullptr;
-    RowCtg *d_ctgs = nullptr;
-    char *d_names = nullptr;
-    uint8_t *d_gctab = nullptr;
+    RowTabsDev tabs;
     size_t names_cap = 0;
     Kept<char> d_text, h_text{true};                // h_text: page-locked
     Kept<unsigned long long> h_words{true};         // page-locked: words[n_ctg], then ctg_off[n_ctg + 1] made on the host
@@ -1320,54 +1314,65 @@ int gams_wave_peaks(gams_gpu_t *h, gams_wave_plan_t *p, const gams_peak_t **peak
 // ---- rows as text ---------------------------------------------------------------------------------
 }  // extern "C"
 namespace {
-// Rust's `{}` of an f32: the shortest digits that round-trip, positional notation (what wave.rs:196 prints)
-std::string rows_fmt_f32(float v) {
-    if (v == 0.0f) return "0";
-    char buf[64];
-    auto r = std::to_chars(buf, buf + sizeof buf, v, std::chars_format::scientific);
-    std::string sci(buf, r.ptr), digits, out;             // d[.ddd]e[+-]XX  (v > 0 here)
-    size_t i = 0;
-    for (; i < sci.size() && sci[i] != 'e'; ++i)
-        if (sci[i] != '.') digits += sci[i];
-    const int ex = std::atoi(sci.c_str() + i + 1), nd = (int)digits.size();
-    if (ex >= 0) {
-        for (int k = 0; k <= ex; ++k) out += k < nd ? digits[k] : '0';
-        if (nd > ex + 1) {
-            out += '.';
-            out.append(digits, ex + 1, std::string::npos);
-        }
-    } else {
-        out += "0.";
-        out.append((size_t)(-ex - 1), '0');
-        out += digits;
-    }
-    return out;
-}
-
 // What the row kernels print from, built on the host: the chromosome names in one blob with a RowCtg per ctg
 // (ctgs of one chromosome share its name; one copy per distinct pointer is not worth the bookkeeping: a few bytes
-// per ctg), and the gc text table, rows_fmt_f32(k / size) for every count k.  "" or what `who` has to report.
-std::string rows_text_tables(const char *who, uint32_t n_ctg, const char *const *chr, const int32_t *chr_start, int32_t size,
-                             std::vector<RowCtg> &rc, std::string &blob, std::vector<uint8_t> &gct) {
-    rc.assign(std::max<uint32_t>(n_ctg, 1), RowCtg{});
-    blob.clear();
-    for (uint32_t c = 0; c < n_ctg; ++c) {
-        const size_t len = std::strlen(chr[c]);
-        size_t at = blob.find(chr[c]);
-        if (at == std::string::npos || len == 0) {
-            at = blob.size();
-            blob += chr[c];
+// per ctg), and the gc text table, Rust's `{}` of the f32 k / size (what wave.rs:196 prints) for every count k.
+struct RowTabs {
+    std::vector<RowCtg> rc;
+    std::string blob;
+    std::vector<uint8_t> gct;
+    // "" or what `who` has to report (GAMS_EUNSUPPORTED)
+    std::string fill(const char *who, uint32_t n_ctg, const char *const *chr, const int32_t *chr_start, int32_t size) {
+        rc.assign(std::max<uint32_t>(n_ctg, 1), RowCtg{});
+        for (uint32_t c = 0; c < n_ctg; ++c) {
+            const size_t len = std::strlen(chr[c]);
+            size_t at = blob.find(chr[c]);
+            if (at == std::string::npos || len == 0) {
+                at = blob.size();
+                blob += chr[c];
+            }
+            rc[c] = RowCtg{(uint32_t)at, (uint32_t)len, chr_start[c], 0u};
         }
-        rc[c] = RowCtg{(uint32_t)at, (uint32_t)len, chr_start[c], 0u};
+        gct.assign(((size_t)size + 1) * kGcStride, 0);
+        for (int32_t k = 0; k <= size; ++k) {
+            char t[32];
+            const uint32_t len = gams_fmt_f32_short((float)k / (float)size, t);     // gc_content as wave.rs prints it
+            if (len == 0u || len > kGcStride - 1) return std::string(who) + ": gc_content text too long";
+            gct[(size_t)k * kGcStride] = (uint8_t)len;
+            std::memcpy(&gct[(size_t)k * kGcStride + 1], t, len);
+        }
+        return "";
     }
-    gct.assign(((size_t)size + 1) * kGcStride, 0);
-    for (int32_t k = 0; k <= size; ++k) {
-        const std::string t = rows_fmt_f32((float)k / (float)size);     // gc_content as wave.rs prints it
-        if (t.size() > kGcStride - 1) return std::string(who) + ": gc_content text too long";
-        gct[(size_t)k * kGcStride] = (uint8_t)t.size();
-        std::memcpy(&gct[(size_t)k * kGcStride + 1], t.data(), t.size());
+    // the three tables' place in their owner's arena, with room for names_cap bytes of names
+    RowTabsDev take(Carver &c, size_t names_cap) const {
+        RowTabsDev d;
+        d.ctgs = c.take<RowCtg>(rc.size());
+        d.names = c.take<char>(names_cap);
+        d.gctab = c.take<uint8_t>(gct.size());
+        return d;
     }
-    return "";
+    // ... and their bytes, copied before the call returns, or queued on `st` (the tables must outlive that copy)
+    hipError_t upload(const RowTabsDev &d) const {
+        return each(d, [](void *dst, const void *src, size_t n) { return hipMemcpy(dst, src, n, hipMemcpyHostToDevice); });
+    }
+    hipError_t upload_async(const RowTabsDev &d, hipStream_t st) const {
+        return each(d, [st](void *dst, const void *src, size_t n) { return hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, st); });
+    }
+    template <typename Copy>
+    hipError_t each(const RowTabsDev &d, Copy copy) const {
+        hipError_t e = copy(d.ctgs, rc.data(), rc.size() * sizeof(RowCtg));
+        if (e == hipSuccess && !blob.empty()) e = copy(d.names, blob.data(), blob.size());
+        if (e == hipSuccess) e = copy(d.gctab, gct.data(), gct.size());
+        return e;
+    }
+};
+
+// where every ctg's rows begin, from where those of the ctgs that have rows do (~0: a ctg without): it begins where the
+// next one does, the last at the text's end
+void rows_fill_ctg_off(unsigned long long *off, uint32_t n_ctg, unsigned long long bytes) {
+    off[n_ctg] = bytes;
+    for (uint32_t c = n_ctg; c-- > 0;)
+        if (off[c] == ~0ull) off[c] = off[c + 1];
 }
 
 // what both text entries ask of the chromosome table (GAMS_EINVAL): "" or what `who` has to report
@@ -1417,10 +1422,10 @@ int rows_emit(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t wi, hipStream_t st, u
     a.n_rec = p->d_tile_off + p->tiles.size();   // the total behind the tiles' offsets
     a.cap = std::min<uint64_t>(r->cap, p->dense_cap());
     a.tile_cap = p->tile_cap;
-    a.ctgs = r->d_ctgs;
+    a.ctgs = r->tabs.ctgs;
     a.n_ctg = n_ctg;
-    a.names = r->d_names;
-    a.gctab = r->d_gctab;
+    a.names = r->tabs.names;
+    a.gctab = r->tabs.gctab;
     a.size = (uint32_t)p->prm.size;
     a.step = (uint32_t)p->prm.step;
     a.dmax = r->dmax;
@@ -1567,24 +1572,18 @@ int gams_wave_rows_setup(gams_gpu_t *h, gams_wave_plan_t *p, const char *const *
     WaveRows *r = p->rows;
     r->dmax = (uint32_t)dmax;
     r->begun = false;
-    std::vector<RowCtg> rc;
-    std::string blob;
-    std::vector<uint8_t> gct;
-    const std::string bad = rows_text_tables("wave_rows_setup", n_ctg, chr, chr_start, q.size, rc, blob, gct);
+    RowTabs tabs;
+    const std::string bad = tabs.fill("wave_rows_setup", n_ctg, chr, chr_start, q.size);
     if (!bad.empty()) return gams_fail(h, GAMS_EUNSUPPORTED, bad);
     r->max_name = 0;
-    for (const RowCtg &c : rc) r->max_name = std::max(r->max_name, c.name_len);
+    for (const RowCtg &c : tabs.rc) r->max_name = std::max(r->max_name, c.name_len);
     const size_t n_words = (size_t)n_ctg + 1 + 4;
     auto arena = [&](Carver &c) {
-        r->d_ctgs = c.take<RowCtg>(rc.size());
-        r->d_names = c.take<char>(std::max<size_t>(blob.size(), 1));
-        r->d_gctab = c.take<uint8_t>(gct.size());
+        r->tabs = tabs.take(c, std::max<size_t>(tabs.blob.size(), 1));
         r->d_words = c.take<unsigned long long>(n_words);
     };
     GAMS_HIP(h, wave_arena(h, r->arena, arena));
-    GAMS_HIP(h, hipMemcpy(r->d_ctgs, rc.data(), rc.size() * sizeof(RowCtg), hipMemcpyHostToDevice));
-    if (!blob.empty()) GAMS_HIP(h, hipMemcpy(r->d_names, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    GAMS_HIP(h, hipMemcpy(r->d_gctab, gct.data(), gct.size(), hipMemcpyHostToDevice));
+    GAMS_HIP(h, tabs.upload(r->tabs));
     GAMS_HIP(h, r->h_words.reserve(h, n_words * 8));
     return GAMS_OK;
 }
@@ -1648,11 +1647,8 @@ int gams_wave_rows_end(gams_gpu_t *h, gams_wave_plan_t *p, const char **text, ui
                 GAMS_HIP(h, hipStreamSynchronize(h->readback));
             }
             r->last_bytes = bytes;
-            // ctgs without a row begin where the next ctg's rows begin
             unsigned long long *off = r->h_words + 4;
-            off[n_ctg] = bytes;
-            for (uint32_t c = n_ctg; c-- > 0;)
-                if (off[c] == ~0ull) off[c] = off[c + 1];
+            rows_fill_ctg_off(off, n_ctg, bytes);
             *text = bytes ? r->h_text.p : nullptr;
             *text_bytes = bytes;
             if (ctg_off) *ctg_off = reinterpret_cast<const uint64_t *>(off);
@@ -1684,28 +1680,24 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
         if (wrc != GAMS_OK) return wrc;
     }
     // names, gc text table (as gams_wave_rows_setup), tiles of kSigRows windows
-    std::vector<RowCtg> rc;
-    std::string blob;
-    std::vector<uint8_t> gct;
-    const std::string bad = rows_text_tables("wave_signal_text", n_ctg, chr, chr_start, q.size, rc, blob, gct);
+    RowTabs tabs;
+    const std::string bad = tabs.fill("wave_signal_text", n_ctg, chr, chr_start, q.size);
     if (!bad.empty()) return gams_fail(h, GAMS_EUNSUPPORTED, bad);
     if (!p->sigtext) p->sigtext = new WaveSig();
     WaveSig *g = p->sigtext;
-    if (!g->arena || g->names_cap < blob.size()) {
+    if (!g->arena || g->names_cap < tabs.blob.size()) {
         std::vector<SigTile> st;
         for (uint32_t c = 0; c < n_ctg; ++c)
             for (uint32_t w0 = 0; w0 < p->ctgs[c].n_win; w0 += kSigRows)
                 st.push_back(SigTile{c, w0, p->ctgs[c].n_win, 0u, p->ctgs[c].win_base});
         g->n_tiles = (uint32_t)st.size();
-        g->names_cap = std::max<size_t>(blob.size(), 64) * 2;
+        g->names_cap = std::max<size_t>(tabs.blob.size(), 64) * 2;
         const size_t nt = std::max<size_t>(st.size(), 1);
         auto arena = [&](Carver &c) {
             g->d_tiles = c.take<SigTile>(nt);
             g->d_blk_len = c.take<uint32_t>(nt);
             g->d_blk_off = c.take<unsigned long long>(nt + 2);
-            g->d_ctgs = c.take<RowCtg>(rc.size());
-            g->d_names = c.take<char>(g->names_cap);
-            g->d_gctab = c.take<uint8_t>(gct.size());
+            g->tabs = tabs.take(c, g->names_cap);
             g->d_words = c.take<unsigned long long>(std::max<size_t>(n_ctg, 1));
         };
         GAMS_HIP(h, wave_arena(h, g->arena, arena));
@@ -1722,9 +1714,7 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
         return GAMS_OK;
     }
     hipStream_t st = h->readback;
-    GAMS_HIP(h, hipMemcpyAsync(g->d_ctgs, rc.data(), rc.size() * sizeof(RowCtg), hipMemcpyHostToDevice, st));
-    if (!blob.empty()) GAMS_HIP(h, hipMemcpyAsync(g->d_names, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-    GAMS_HIP(h, hipMemcpyAsync(g->d_gctab, gct.data(), gct.size(), hipMemcpyHostToDevice, st));
+    GAMS_HIP(h, tabs.upload_async(g->tabs, st));
     GAMS_HIP(h, hipMemsetAsync(g->d_words, 0xFF, std::max<size_t>(n_ctg, 1) * 8, st));
     gams_wave_plan::Way &w = wave_read_way(p);
     SigArgs a{};
@@ -1732,35 +1722,34 @@ int gams_wave_signal_text(gams_gpu_t *h, gams_wave_plan_t *p, const char *const 
     a.n_tiles = g->n_tiles;
     a.cnt = w.d_dense_cnt;
     a.sig = w.d_dense_sig;
-    a.ctgs = g->d_ctgs;
-    a.names = g->d_names;
-    a.gctab = g->d_gctab;
+    a.ctgs = g->tabs.ctgs;
+    a.names = g->tabs.names;
+    a.gctab = g->tabs.gctab;
     a.size = (uint32_t)q.size;
     a.step = (uint32_t)q.step;
     a.blk_len = g->d_blk_len;
     a.blk_off = g->d_blk_off;
     a.words = g->d_words;
-    hipLaunchKernelGGL(sig_len_kernel, dim3(g->n_tiles), dim3(256), 0, st, a);
-    GAMS_HIP(h, hipGetLastError());
     unsigned long long *const d_totals = g->d_blk_off + g->n_tiles;
     Chain ch{st};
+    void *args_sig[] = {&a};                     // (read at each launch: the write kernel sees the text set below)
+    ch.kernel(reinterpret_cast<const void *>(sig_len_kernel), g->n_tiles, 256, args_sig);
     ch.offsets(g->d_blk_len, g->n_tiles, g->d_blk_off, d_totals);
+    ch.copy(h->pin_scratch, d_totals, 2 * sizeof(unsigned long long));
     GAMS_HIP(h, ch.err);
-    GAMS_HIP(h, hipMemcpyAsync(h->pin_scratch, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    GAMS_HIP(h, hipStreamSynchronize(st));       // (the staged tables above live on this call's stack until here)
+    GAMS_HIP(h, hipStreamSynchronize(st));       // (`tabs` lives on this call's stack until here)
     const uint64_t total = h->pin_scratch[0];
     GAMS_HIP(h, g->d_text.grow(h, total, total + total / 16 + 4096));
     GAMS_HIP(h, g->h_text.grow(h, total, total + total / 16 + 4096));
     a.text = g->d_text;
     a.text_cap = total;
-    hipLaunchKernelGGL(sig_write_kernel, dim3(g->n_tiles), dim3(256), 0, st, a);
-    GAMS_HIP(h, hipGetLastError());
-    GAMS_HIP(h, hipMemcpyAsync(g->h_words, g->d_words, std::max<size_t>(n_ctg, 1) * 8, hipMemcpyDeviceToHost, st));
-    if (total) GAMS_HIP(h, hipMemcpyAsync(g->h_text, g->d_text, total, hipMemcpyDeviceToHost, st));
+    ch.kernel(reinterpret_cast<const void *>(sig_write_kernel), g->n_tiles, 256, args_sig);
+    ch.copy(g->h_words, g->d_words, std::max<size_t>(n_ctg, 1) * 8);
+    ch.copy(g->h_text, g->d_text, total);
+    GAMS_HIP(h, ch.err);
     GAMS_HIP(h, hipStreamSynchronize(st));
-    // where each ctg's rows begin: ctgs without a window begin where the next one does
-    off[n_ctg] = total;
-    for (uint32_t c = n_ctg; c-- > 0;) off[c] = p->ctgs[c].n_win ? g->h_words[c] : off[c + 1];
+    std::copy(g->h_words.p, g->h_words.p + n_ctg, off);    // where the rows of the ctgs that have a window begin
+    rows_fill_ctg_off(off, n_ctg, total);
     *text = g->h_text;
     *text_bytes = total;
     *ctg_off = reinterpret_cast<const uint64_t *>(off);

@@ -40,6 +40,12 @@ struct RowCtg {                              // per ctg, 16 B
     uint32_t pad;
 };
 
+struct RowTabsDev {                          // what the rows print from, on the device: RowCtg per ctg, the names' blob,
+    RowCtg *ctgs = nullptr;                  // the gc_content text table [size + 1][kGcStride]
+    char *names = nullptr;
+    uint8_t *gctab = nullptr;
+};
+
 struct RowArgs {
     const gams_peak_t *rec;                  // packed peaks of the pass, ordered by (ctg, window)
     const unsigned long long *n_rec;         // [0] = how many, [1] = the fullest tile (device side: nobody waited for the pass)
@@ -205,17 +211,28 @@ __global__ __launch_bounds__(256) void rows_tail_kernel(const RowArgs a) {
     a.tailwin[head] = r.window;             // a tail's component has a head at or before it, in the same ctg
 }
 
-// bytes of the row record i prints (0: it is printed with its component's head)
-__device__ __forceinline__ uint32_t row_len(const RowArgs &a, uint64_t i, const gams_peak_t r, uint8_t f) {
-    if (!(f & kRowHead)) return 0u;
+// the row of head record i with flags f, counted or written: "{chr}[(+)]:{s}[-{e}]\t{gc_content}\t{signal}\n"
+template <bool kWrite>
+__device__ __forceinline__ void wave_row(const RowArgs &a, uint64_t i, const gams_peak_t r, uint8_t f, RowOut<kWrite> &o) {
     const RowCtg cg = a.ctgs[r.ctg];
     const uint32_t s = (uint32_t)cg.chr_start + r.window * a.step;
     const uint32_t lastw = (f & kRowMerged) ? a.tailwin[i] : r.window;
     const uint32_t e = (uint32_t)cg.chr_start + lastw * a.step + a.size - 1u;
-    uint32_t len = cg.name_len + ((f & kRowMerged) ? 3u : 0u) + 1u + dec_digits(s);
-    if (e != s) len += 1u + dec_digits(e);                      // IntSpan runlist: "s" for a single position
-    len += 1u + a.gctab[(size_t)r.gc_count * kGcStride] + 1u + (r.signal > 0 ? 1u : 2u) + 1u;
-    return len;
+    o.bytes(a.names + cg.name_off, cg.name_len);
+    if (f & kRowMerged) o.bytes("(+)", 3u);
+    o.ch(':');
+    o.dec(s);
+    if (e != s) {                                               // IntSpan runlist: "s" for a single position
+        o.ch('-');
+        o.dec(e);
+    }
+    o.ch('\t');
+    const uint8_t *g = a.gctab + (size_t)r.gc_count * kGcStride;
+    o.bytes(reinterpret_cast<const char *>(g + 1), g[0]);
+    o.ch('\t');
+    if (r.signal < 0) o.ch('-');
+    o.ch('1');
+    o.ch('\n');
 }
 
 __global__ __launch_bounds__(256) void rows_len_kernel(const RowArgs a) {
@@ -232,9 +249,12 @@ __global__ __launch_bounds__(256) void rows_len_kernel(const RowArgs a) {
     for (uint32_t u = 0; u < kRowsPer; ++u) {
         const uint64_t i = base + kRowsPer * tid + u;
         if (i >= n) continue;
-        const uint32_t l = row_len(a, i, a.rec[i], a.flags[i]);
-        a.len[i] = l;
-        sum += l;
+        const gams_peak_t r = a.rec[i];                         // (both loads at once, whatever the flags say)
+        const uint8_t f = a.flags[i];
+        RowOut<false> o;
+        if (f & kRowHead) wave_row(a, i, r, f, o);              // (others: printed with their component's head)
+        a.len[i] = o.n;
+        sum += o.n;
     }
     for (int d = 32; d; d >>= 1) sum += (uint32_t)__shfl_xor((int)sum, d, 64);
     if ((tid & 63u) == 0u) ws[tid >> 6] = sum;
@@ -242,37 +262,8 @@ __global__ __launch_bounds__(256) void rows_len_kernel(const RowArgs a) {
     if (tid == 0u) a.blk_len[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
 
-// one row's bytes at p (global or LDS)
-__device__ __forceinline__ void row_put(const RowArgs &a, char *p, uint64_t i, const gams_peak_t r) {
-    const uint8_t f = a.flags[i];
-    const RowCtg cg = a.ctgs[r.ctg];
-    const uint32_t s = (uint32_t)cg.chr_start + r.window * a.step;
-    const uint32_t lastw = (f & kRowMerged) ? a.tailwin[i] : r.window;
-    const uint32_t e = (uint32_t)cg.chr_start + lastw * a.step + a.size - 1u;
-    for (uint32_t q = 0; q < cg.name_len; ++q) *p++ = a.names[cg.name_off + q];
-    if (f & kRowMerged) {
-        *p++ = '(';
-        *p++ = '+';
-        *p++ = ')';
-    }
-    *p++ = ':';
-    p = put_dec(p, s);
-    if (e != s) {
-        *p++ = '-';
-        p = put_dec(p, e);
-    }
-    *p++ = '\t';
-    const uint8_t *g = a.gctab + (size_t)r.gc_count * kGcStride;
-    for (uint32_t q = 0; q < g[0]; ++q) *p++ = (char)g[1u + q];
-    *p++ = '\t';
-    if (r.signal < 0) *p++ = '-';
-    *p++ = '1';
-    *p++ = '\n';
-}
-
-// The rows of a block are one contiguous stretch of the text: they are put together in LDS (where a row's ~28
-// single-byte stores cost nothing) and leave as 16-B stores on 16-B boundaries of the text, the ragged ends byte by
-// byte.  A block whose text does not fit the stage (long names) writes its rows straight to the text.
+// The rows of a block are one contiguous stretch of the text (BlockWriter, text_emit.hpp): put together in LDS and
+// stored in 16-B units, or -- a block whose text does not fit the stage (long names) -- written straight to the text.
 __global__ __launch_bounds__(256) void rows_write_kernel(const RowArgs a) {
     __shared__ uint32_t scr[4];
     __shared__ __align__(16) char stage[kRowsStage + 16];
@@ -293,29 +284,23 @@ __global__ __launch_bounds__(256) void rows_write_kernel(const RowArgs a) {
         l[u] = i < n ? a.len[i] : 0u;
         mine += l[u];
     }
-    uint32_t tot;
-    const uint32_t rel = block_excl_scan_256<uint32_t>(mine, scr, tot);
-    const uint64_t blk0 = a.blk_off[blockIdx.x];               // the block's first byte in the text
-    const uint32_t mis = (uint32_t)(blk0 & 15u);               // the stage starts at the same offset inside a 16-B unit
-    const bool staged = tot <= kRowsStage && blk0 + tot <= a.text_cap;
-    uint32_t at = rel;
+    BlockWriter<uint32_t> w(mine, scr, a.blk_off, a.text, a.text_cap);
+    w.stage_if(w.tot <= kRowsStage, stage);
+    uint32_t at = w.rel;
 #pragma unroll
     for (uint32_t u = 0; u < kRowsPer; ++u) {
         const uint64_t i = base + kRowsPer * tid + u;
         if (i >= n) break;
         const gams_peak_t r = a.rec[i];
-        if (i == 0 || a.rec[i - 1].ctg != r.ctg) a.words[4u + r.ctg] = blk0 + at;   // the ctg's rows begin here (its first record is a head)
-        if (l[u]) {
-            if (staged)
-                row_put(a, stage + mis + at, i, r);
-            else if (blk0 + at + l[u] <= a.text_cap)
-                row_put(a, a.text + blk0 + at, i, r);
-        }
+        if (i == 0 || a.rec[i - 1].ctg != r.ctg) a.words[4u + r.ctg] = w.blk0 + at;   // the ctg's rows begin here (its first record is a head)
+        if (l[u])                                              // a head
+            w.put(at, [&](char *p) {
+                RowOut<true> o{p};
+                wave_row(a, i, r, a.flags[i], o);
+            });
         at += l[u];
     }
-    if (!staged) return;
-    __syncthreads();
-    stage_flush_256(stage, mis, tot, a.text + blk0);
+    w.flush();
 }
 
 // ---- `wave --signal`: a row for EVERY window (wave.rs:158-168) ----------------------------------------------------
@@ -348,38 +333,34 @@ struct SigArgs {
     unsigned long long *words;               // per ctg: where its rows begin (ctgs without a window keep ~0)
 };
 
-__device__ __forceinline__ uint32_t sig_row_len(const SigArgs &a, const RowCtg cg, uint32_t i, uint32_t k, int sg) {
+// the row of window i of a ctg (count k, signal sg), counted or written
+template <bool kWrite>
+__device__ __forceinline__ void sig_row(const SigArgs &a, const RowCtg cg, uint32_t i, uint32_t k, int sg, RowOut<kWrite> &o) {
     const uint32_t s = (uint32_t)cg.chr_start + i * a.step, e = s + a.size - 1u;
-    return cg.name_len + 1u + dec_digits(s) + (e != s ? 1u + dec_digits(e) : 0u) + 1u + a.gctab[(size_t)k * kGcStride] + 1u +
-           (sg < 0 ? 2u : 1u) + 1u;
+    o.bytes(a.names + cg.name_off, cg.name_len);
+    o.ch(':');
+    o.dec(s);
+    if (e != s) {                                   // IntSpan::runlist of a single position is that position
+        o.ch('-');
+        o.dec(e);
+    }
+    o.ch('\t');
+    const uint8_t *g = a.gctab + (size_t)k * kGcStride;
+    o.bytes(reinterpret_cast<const char *>(g + 1), g[0]);
+    o.ch('\t');
+    if (sg < 0) o.ch('-');
+    o.ch(sg == 0 ? '0' : '1');
+    o.ch('\n');
 }
 
 __global__ __launch_bounds__(256) void sig_len_kernel(const SigArgs a) {
     __shared__ uint32_t ws[4];
     const SigTile t = a.tiles[blockIdx.x];
     const uint32_t tid = threadIdx.x, i = t.w0 + tid;
-    uint32_t len = 0;
-    if (i < t.n_win) len = sig_row_len(a, a.ctgs[t.ctg], i, a.cnt[t.win_base + i], a.sig[t.win_base + i]);
-    const uint32_t tot = block_sum_256(len, ws);
+    RowOut<false> o;
+    if (i < t.n_win) sig_row(a, a.ctgs[t.ctg], i, a.cnt[t.win_base + i], a.sig[t.win_base + i], o);
+    const uint32_t tot = block_sum_256(o.n, ws);
     if (tid == 0u) a.blk_len[blockIdx.x] = tot;
-}
-
-__device__ __forceinline__ void sig_row_put(const SigArgs &a, char *p, const RowCtg cg, uint32_t i, uint32_t k, int sg) {
-    const uint32_t s = (uint32_t)cg.chr_start + i * a.step, e = s + a.size - 1u;
-    for (uint32_t q = 0; q < cg.name_len; ++q) *p++ = a.names[cg.name_off + q];
-    *p++ = ':';
-    p = put_dec(p, s);
-    if (e != s) {                                   // IntSpan::runlist of a single position is that position
-        *p++ = '-';
-        p = put_dec(p, e);
-    }
-    *p++ = '\t';
-    const uint8_t *g = a.gctab + (size_t)k * kGcStride;
-    for (uint32_t q = 0; q < g[0]; ++q) *p++ = (char)g[1u + q];
-    *p++ = '\t';
-    if (sg < 0) *p++ = '-';
-    *p++ = sg == 0 ? '0' : '1';
-    *p++ = '\n';
 }
 
 __global__ __launch_bounds__(256) void sig_write_kernel(const SigArgs a) {
@@ -388,28 +369,20 @@ __global__ __launch_bounds__(256) void sig_write_kernel(const SigArgs a) {
     const SigTile t = a.tiles[blockIdx.x];
     const uint32_t tid = threadIdx.x, i = t.w0 + tid;
     const RowCtg cg = a.ctgs[t.ctg];
-    uint32_t k = 0, len = 0;
-    int sg = 0;
-    if (i < t.n_win) {
-        k = a.cnt[t.win_base + i];
-        sg = a.sig[t.win_base + i];
-        len = sig_row_len(a, cg, i, k, sg);
-    }
-    uint32_t tot;
-    const uint32_t rel = block_excl_scan_256<uint32_t>(len, scr, tot);
-    const uint64_t blk0 = a.blk_off[blockIdx.x];
-    if (t.w0 == 0u && tid == 0u) a.words[t.ctg] = blk0;
-    const uint32_t mis = (uint32_t)(blk0 & 15u);
-    const bool staged = tot <= kRowsStage && blk0 + tot <= a.text_cap;
-    if (len) {
-        if (staged)
-            sig_row_put(a, stage + mis + rel, cg, i, k, sg);
-        else if (blk0 + rel + len <= a.text_cap)
-            sig_row_put(a, a.text + blk0 + rel, cg, i, k, sg);
-    }
-    if (!staged) return;
-    __syncthreads();
-    stage_flush_256(stage, mis, tot, a.text + blk0);
+    const bool mine = i < t.n_win;                  // (a tile's last threads may have no window)
+    const uint32_t k = mine ? a.cnt[t.win_base + i] : 0u;
+    const int sg = mine ? a.sig[t.win_base + i] : 0;
+    RowOut<false> len;
+    if (mine) sig_row(a, cg, i, k, sg, len);
+    BlockWriter<uint32_t> w(len.n, scr, a.blk_off, a.text, a.text_cap);
+    w.stage_if(w.tot <= kRowsStage, stage);
+    if (t.w0 == 0u && tid == 0u) a.words[t.ctg] = w.blk0;
+    if (mine)
+        w.put(w.rel, [&](char *p) {
+            RowOut<true> o{p};
+            sig_row(a, cg, i, k, sg, o);
+        });
+    w.flush();
 }
 
 }  // namespace

@@ -3,7 +3,8 @@
 byte against the models of tests/text_edges.py and the oracle.  test_text_edges_cpu.py proves the models and shows that
 the inputs used here reach what they are for: blocks beyond the stage (the branch that writes to global memory directly),
 blocks within 64 bytes of `tot <= stage` on either side, staged blocks at every offset inside a 16-byte unit, more blocks
-than the one-workgroup scans have threads, chains across block seams, every decimal width, a plan's rows set up again."""
+than the one-workgroup scans have threads, chains across block seams, every decimal width, a plan's rows set up again,
+`--signal` rows of a single position, gc_content texts beyond 10 bytes."""
 import numpy as np
 import pytest
 
@@ -169,6 +170,42 @@ def test_signal_rows_beyond_the_stage_and_other_names_on_one_plan(eng):
         assert_text(text, off, exp, ("signal", names[0]))
     plan.close()
     ss.close()
+
+
+def signal_model_text(eng, case):
+    """-> (text, offsets) of gams_wave_signal_text for the case, the rows of te.signal_rows_model per ctg"""
+    ctgs, size, step = case["ctgs"], case["size"], case["step"]
+    ss = engine.SeqSet(eng, [c["seq"] for c in ctgs])
+    plan = engine.WavePlan(eng, ss, size, step, case["lag"], case["threshold"], 1.0, flags=_lib.WAVE_DENSE)
+    plan.run()
+    text, off = plan.signal_text([c["chr_id"] for c in ctgs], [c["chr_start"] for c in ctgs])
+    exp = [te.signal_rows_model(c, *te.oracle_windows(c["seq"], size, step, case["lag"], case["threshold"]), size, step)[0]
+           for c in ctgs]
+    plan.close()
+    ss.close()
+    return text, off, exp
+
+
+def test_signal_rows_of_a_single_position(eng):
+    """size 1, step 1: every row's range is one position and prints without an end (sig_row's `e != s`), from coordinate 1
+    and across 10^4 inside a tile"""
+    text, off, exp = signal_model_text(eng, te.point_signal_case())
+    assert_text(text, off, exp, "single positions")
+
+
+def test_rows_with_gc_texts_beyond_ten_bytes(eng):
+    """size 82: gc_content texts of 11 and 12 bytes from the table, in single and merged peak rows and in `--signal` rows"""
+    case = te.gc_long_case()
+    ctgs, size, step = case["ctgs"], case["size"], case["step"]
+    exp, _, _, _ = te.wave_rows_model(ctgs, case["peaks"], size, step)
+    ss = engine.SeqSet(eng, [c["seq"] for c in ctgs])
+    plan = engine.WavePlan(eng, ss, size, step, case["lag"], case["threshold"], 1.0, flags=_lib.WAVE_PEAKS)
+    plan.rows_setup([c["chr_id"] for c in ctgs], [c["chr_start"] for c in ctgs], 0.2)
+    rows_twice(plan, exp, "long gc texts")
+    plan.close()
+    ss.close()
+    text, off, exp = signal_model_text(eng, case)
+    assert_text(text, off, exp, "long gc texts, --signal")
 
 
 # ---- `sw` -----------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """CPU checks of `gams peak` on the device (gams_gpu_peak_text, host.peak_text): the shortest round-trip f32 formatter
-of the amplitudes (gams_fmt_f32_short, csrc/text_fmt.hpp) against std::to_chars over its whole domain, the pure-Python
+of the amplitudes (gams_fmt_f32_short, csrc/text_fmt.hpp) against std::to_chars over its whole domain and over the
+gc_content tables of the wave rows, which the host fills with the same formatter, the pure-Python
 model (tests/peak_text.py) against the golden rows, the cases the synthetic input of the GPU test must carry, and the
 loud failure without a device.  tests/test_gpu_peak_text.py checks the device against the model."""
 import ctypes as C
@@ -21,7 +22,7 @@ ROOT = os.path.dirname(HERE)
 # Every amplitude of `gams peak` is |a - b| in f32 of two round4 gc values a = fl(i / 10^4), b = fl(j / 10^4): all
 # pairs 0 <= j <= i <= 10^4.  The reference text is std::to_chars' shortest digits laid out positionally (what
 # gams::fmt_f32 prints and Rust's `{}`).  Prints: mismatches, then the count of values per number of significant digits.
-DRIVER = r"""
+POSITIONAL = r"""
 #include "text_fmt.hpp"
 #include <charconv>
 #include <cmath>
@@ -42,6 +43,8 @@ static std::string positional(float v, int *nd) {
     if (ex >= 0) return digits;                       // v <= 1: "1"
     return "0." + std::string((size_t)(-ex - 1), '0') + digits;
 }
+"""
+DRIVER = POSITIONAL + r"""
 int main() {
     long bad = 0, hist[12] = {0};
     for (int i = 0; i <= 10000; ++i)
@@ -66,17 +69,69 @@ int main() {
 
 
 def test_fmt_f32_short_is_exact_over_the_amplitude_domain(tmp_path):
-    src = tmp_path / "fmt_main.cpp"
-    src.write_text(DRIVER)
-    exe = tmp_path / "fmt_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "gams_amd", "csrc"),
-                           str(src), "-o", str(exe)])
-    out = subprocess.run([str(exe)], stdout=subprocess.PIPE, text=True, check=True).stdout.split()
+    exe = compile_driver(tmp_path, "fmt_main", DRIVER)
+    out = subprocess.run([exe], stdout=subprocess.PIPE, text=True, check=True).stdout.split()
     bad, hist = int(out[0]), [int(x) for x in out[1:]]
     print("mismatches", bad, "values per significant digits", hist)
     assert sum(hist) == 10001 * 10002 // 2
     assert bad == 0
     assert hist[8] > 0 and hist[9] > 0 and sum(hist[10:]) == 0
+
+
+# The gc_content table of the wave rows (RowTabs::fill, csrc/wave.hip): the text of the f32 k / size for every count
+# 0 <= k <= size, for every size up to 2048 and the 15 largest a plan takes.  Prints: mismatches, values, the longest text,
+# texts longer than 10 bytes, and -- among the sizes up to 255 -- the longest text and the first size and k that have it.
+GC_DRIVER = POSITIONAL + r"""
+int main() {
+    long bad = 0, n = 0, longer = 0;
+    unsigned longest = 0, longest255 = 0, size255 = 0, k255 = 0;
+    for (int size = 1; size <= 65535; size = size == 2048 ? 65521 : size + 1)
+        for (int k = 0; k <= size; ++k, ++n) {
+            const float v = (float)k / (float)size;
+            char b[64];
+            const uint32_t len = gams_fmt_f32_short(v, b), len0 = gams_fmt_f32_short(v, nullptr);
+            int nd;
+            const std::string want = positional(v, &nd);
+            if (len != len0 || std::string(b, len) != want) {
+                if (bad < 10) fprintf(stderr, "%d/%d: got '%s' want '%s'\n", k, size, std::string(b, len).c_str(), want.c_str());
+                ++bad;
+            }
+            if (len > longest) longest = len;
+            if (len > 10u) ++longer;
+            if (size <= 255 && len > longest255) longest255 = len, size255 = (unsigned)size, k255 = (unsigned)k;
+        }
+    printf("%ld %ld %u %ld %u %u %u\n", bad, n, longest, longer, longest255, size255, k255);
+    return 0;
+}
+"""
+
+
+def compile_driver(tmp_path, name, text):
+    src = tmp_path / (name + ".cpp")
+    src.write_text(text)
+    exe = tmp_path / name
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "gams_amd", "csrc"),
+                           str(src), "-o", str(exe)])
+    return str(exe)
+
+
+def test_the_gc_content_table_is_the_references_text(tmp_path):
+    """gams_fmt_f32_short(k / size) against to_chars' positional form for every entry of every table of the sizes 1..2048
+    and 65521..65535: no mismatch, no text beyond an entry of the table, and texts of more than 10 bytes among them.  The
+    size the GPU tests take for a long gc text (text_edges.GC_LONG_SIZE) is the first up to 255 with the longest text."""
+    import text_edges as te
+
+    out = subprocess.run([compile_driver(tmp_path, "gc_main", GC_DRIVER)], stdout=subprocess.PIPE, text=True, check=True).stdout
+    bad, n, longest, longer, longest255, size255, k255 = (int(x) for x in out.split())
+    print("mismatches", bad, "values", n, "longest", longest, "longer than 10 bytes", longer, "up to size 255:", longest255,
+          "bytes at", k255, "/", size255)
+    rows_hpp = open(os.path.join(ROOT, "gams_amd", "csrc", "wave_rows.hpp")).read()
+    stride = int(re.search(r"constexpr uint32_t kGcStride = (\d+);", rows_hpp).group(1))
+    assert n == sum(s + 1 for s in list(range(1, 2049)) + list(range(65521, 65536))) > 3_000_000
+    assert bad == 0
+    assert longest <= stride - 1 and longer > 0
+    assert (te.GC_LONG_SIZE, te.GC_LONG_BYTES) == (size255, longest255) and longest255 > 10
+    assert len(te.gc_texts(size255)[k255]) == longest255 == max(len(t) for t in te.gc_texts(size255))
 
 
 def test_fmt_f32_short_edges():

@@ -7,6 +7,7 @@
 3. The inputs of every new GPU case meet the conditions the case was made for: blocks beyond twice the stage, blocks on
    both sides of `tot <= stage` within 64 bytes, staged blocks at every offset inside a 16-byte unit, more blocks than
    the one-workgroup scans have threads, chains across block seams, every decimal width.
+4. The `--signal` rows of single positions print no end, and the size-82 case carries gc texts of 11 and 12 bytes.
 These are conditions on the inputs: when one fails, the input is changed, never the assertion."""
 import numpy as np
 import pytest
@@ -246,3 +247,38 @@ def test_digit_inputs():
     for what in ("peak rows", "--signal"):
         gcs = {len(r.split(b"\t")[1]) for r in texts[what].split(b"\n") if r}
         assert max(gcs) >= 9 and min(gcs) == 1, (what, gcs)
+
+
+# ---- 4. single positions and long gc texts --------------------------------------------------------------------------
+def test_point_signal_inputs():
+    """size 1: no expected `--signal` row has a `-` in its range field; the coordinates gain a digit inside a tile"""
+    case = te.point_signal_case()
+    assert (case["size"], case["step"]) == (1, 1) and [c["chr_start"] for c in case["ctgs"]] == [1, 10 ** 4 - 1500]
+    for c in case["ctgs"]:
+        cnt, sig = te.oracle_windows(c["seq"], 1, 1, case["lag"], case["threshold"])
+        text, rb = te.signal_rows_model(c, cnt, sig, 1, 1)
+        kw = dict(size=1, step=1, lag=case["lag"], threshold=case["threshold"], influence=1.0)
+        assert text.decode() == ora.wave_proc_ctg(c["chr_id"], c["chr_start"], c["chr_end"], c["seq"], is_signal=True, **kw)
+        rows = text.split(b"\n")[:-1]
+        assert len(rows) == cnt.size == c["seq"].size > 10 * te.SIG_BLOCK and cnt.size % te.SIG_BLOCK
+        assert all(b"-" not in r.split(b"\t")[0] for r in rows)
+        assert {r.split(b"\t")[2] for r in rows} == {b"-1", b"0", b"1"} and {r.split(b"\t")[1] for r in rows} == {b"0", b"1"}
+    w = 10 ** 4 - case["ctgs"][1]["chr_start"]                     # the window at 10^4
+    assert 0 < w % te.SIG_BLOCK < te.SIG_BLOCK - 1 and w < case["ctgs"][1]["seq"].size
+
+
+def test_gc_long_inputs():
+    """size 82: peak rows, single and merged, and `--signal` rows carry gc texts of 11 and 12 bytes"""
+    case = te.gc_long_case()
+    c, size, step = case["ctgs"][0], case["size"], case["step"]
+    assert size <= 255 and max(len(t) for t in te.gc_texts(size)) == te.GC_LONG_BYTES > 10
+    rows = te.wave_rows_model(case["ctgs"], case["peaks"], size, step)[0][0]
+    exp = ora.wave_proc_ctg(c["chr_id"], c["chr_start"], c["chr_end"], c["seq"], size, step, case["lag"], case["threshold"], 1.0, 0.2)
+    assert rows.decode() == exp
+    sig = te.signal_rows_model(c, *case["per_ctg"][0], size, step)[0]
+    for what, text in (("peak rows", rows), ("--signal", sig)):
+        f = [r.split(b"\t") for r in text.split(b"\n")[:-1]]
+        assert {len(r[1]) for r in f} >= {11, te.GC_LONG_BYTES}, what
+        assert sum(len(r[1]) > 10 for r in f) >= 20, what
+    long_rows = [r.split(b"\t") for r in rows.split(b"\n")[:-1] if len(r.split(b"\t")[1]) > 10]
+    assert any(b"(+)" in r[0] for r in long_rows) and any(b"(+)" not in r[0] for r in long_rows)

@@ -432,6 +432,40 @@ def signal_name_sets(case):
     return short, medium, full
 
 
+# ---- single positions, and gc texts beyond 10 bytes -------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def point_signal_case():
+    """`wave --signal` at size 1, step 1, lag 4, threshold -1: every window is one position, so every row prints "{chr}:{s}"
+    without an end (IntSpan's runlist of a single position).  I at 1, and d4 across 10^4 inside a tile of 256 windows.  (A
+    plan takes no ctg with fewer than `lag` windows: there is no ctg without rows to put between them.)"""
+    ctgs = [ctg("I", 1, helpers.synth(3001, 91)), ctg("d4", 10 ** 4 - 1500, helpers.synth(2777, 92))]
+    return dict(ctgs=ctgs, size=1, step=1, lag=ROWS_LAG, threshold=ROWS_THR)
+
+
+# The first size up to 255 whose gc text table holds the longest text found among those sizes, and that text's bytes
+# ("0.0121951215" = 1 / 82; test_peak_text_cpu.py finds both with the formatter's driver).  The counts 1, 2, 3, 4 and 7 of
+# that table have texts of 11 and 12 bytes.
+GC_LONG_SIZE, GC_LONG_BYTES = 82, 12
+GC_LONG_STEP = 41                      # dmax 1: single rows and merged ones
+
+
+@functools.lru_cache(maxsize=None)
+def gc_long_case():
+    """One ctg of 20 kb for the peak rows and the `--signal` rows at size 82: the second half is A / T with a G or a C
+    every 12 to 80 bases, so that its windows hold the few G/C whose gc_content text is longer than 10 bytes."""
+    rng = np.random.default_rng(93)
+    seq = helpers.synth(20_000, 94).copy()
+    poor = np.where(rng.random(10_000) < 0.5, ord("A"), ord("T")).astype(np.uint8)
+    at = np.cumsum(rng.integers(12, 81, 400))
+    at = at[at < poor.size]
+    poor[at] = np.where(rng.random(at.size) < 0.5, ord("G"), ord("c"))
+    seq[10_000:] = poor
+    c = ctg(LONG_B, 10 ** 6 - 9000, seq)
+    per = [oracle_windows(seq, GC_LONG_SIZE, GC_LONG_STEP, ROWS_LAG, ROWS_THR)]
+    return dict(ctgs=[c], per_ctg=per, peaks=pack_peaks(per), size=GC_LONG_SIZE, step=GC_LONG_STEP, lag=ROWS_LAG,
+                threshold=ROWS_THR)
+
+
 # ---- `sw` ---------------------------------------------------------------------------------------------------------
 SW_SIZE, SW_MAX, SW_RESIZE = 10, 20, 50
 SW_ACTIONS = (("gc",), ("count",), ("gc", "count"))
