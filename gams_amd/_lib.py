@@ -15,6 +15,7 @@ OK, EINVAL, ENODEV, ENOMEM, EHIP, ESHORT, EUNSUPPORTED, ESTATE = range(8)
 WAVE_PEAKS, WAVE_DENSE = 1, 2
 WAVE_INPUT_AUTO, WAVE_INPUT_BYTES, WAVE_INPUT_PLANE = 0, 1, 2   # gams_wave_plan_set_input / _last_input
 WAVE_BODY_AUTO, WAVE_BODY_WIDE, WAVE_BODY_NARROW = 0, 1, 2      # gams_wave_plan_set_body / _last_body
+WAVE_CUT_AUTO, WAVE_CUT_TWO_WAVES, WAVE_CUT_ONE_WAVE = 0, 1, 2  # gams_wave_plan_set_cut / _last_cut
 GC_BODY_AUTO, GC_BODY_PORTABLE, GC_BODY_AVX2 = 0, 1, 2          # gams_gc_plane_with
 SW_GC, SW_COUNT = 1, 2          # GAMS_SW_GC / GAMS_SW_COUNT: the action set of gams_gpu_sw_text_actions
 
@@ -70,6 +71,8 @@ PROTOTYPES = {
     "gams_wave_plan_last_input": (C.c_int, [_VP, _VP, C.POINTER(C.c_int)]),
     "gams_wave_plan_set_body": (C.c_int, [_VP, _VP, C.c_int]),
     "gams_wave_plan_last_body": (C.c_int, [_VP, _VP, C.POINTER(C.c_int)]),
+    "gams_wave_plan_set_cut": (C.c_int, [_VP, _VP, C.c_int]),
+    "gams_wave_plan_last_cut": (C.c_int, [_VP, _VP, C.POINTER(C.c_int)]),
     "gams_seqset_download": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP]),
     "gams_seqset_destroy": (None, [_VP, _VP]),
     "gams_wave_plan_create": (C.c_int, [_VP, _VP, C.POINTER(WaveParams), C.c_uint32, _PP]),

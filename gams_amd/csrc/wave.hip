@@ -57,6 +57,10 @@ static const WaveFastFn kWaveFastFn[kWaveFastCount][2] = {WAVE_FAST_INSTANCES(WA
 #undef WAVE_X_PAIR
 static const WaveFastFn kWaveTaperFn[2] = {wave_fast_taper_kernel<100, 10, 100, false>, wave_fast_taper_kernel<100, 10, 100, true>};
 static const WaveFastFn kWaveNarrowFn = wave_fast_narrow_kernel;   // the narrow body of the headline tile (wave_select_body)
+static const WaveFastFn kWaveOneWaveFn = wave_fast_onewave_kernel; // ... cut as one wave x 48 windows (wave_select_cut)
+static_assert(kOneWaveLds == wave_onewave_lds_bytes() && kOneWavePad == kWaveOneWavePad, "the one-wave carve of wave_select.hpp is the kernel's");
+static_assert(kWaveCutAuto == GAMS_WAVE_CUT_AUTO && kWaveCutTwoWaves == GAMS_WAVE_CUT_TWO_WAVES && kWaveCutOneWave == GAMS_WAVE_CUT_ONE_WAVE,
+              "wave_select.hpp names the cuts as gams_gpu_diag.h does");
 static const WaveTileFn kWaveTileFn[2][2] = {{wave_tile_kernel<uint8_t, false>, wave_tile_kernel<uint8_t, true>},     // [k16][wide]
                                              {wave_tile_kernel<uint16_t, false>, wave_tile_kernel<uint16_t, true>}};
 
@@ -188,6 +192,8 @@ struct gams_wave_plan {
     std::atomic<int> last_input{GAMS_WAVE_INPUT_BYTES};   // what the most recently queued pass read (ways queue from several threads)
     int body_req = GAMS_WAVE_BODY_AUTO;     // gams_wave_plan_set_body
     std::atomic<int> last_body{GAMS_WAVE_BODY_WIDE};      // the body of the most recently queued pass
+    int cut_req = GAMS_WAVE_CUT_AUTO;       // gams_wave_plan_set_cut
+    std::atomic<int> last_cut{GAMS_WAVE_CUT_AUTO};        // the cut of the most recently queued pass (0: not the narrow body)
     // every pooled block of the plan back to the pools (the caller has drained the streams)
     void release(gams_gpu_t *h) {
         if (rows) rows->release(h);
@@ -360,7 +366,10 @@ int wave_build_geometry(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t tw_req) {
     if (p->fast_fn) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(p->fast_fn), s.lds_bytes));
     if (p->tile_fn) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(p->tile_fn), s.lds_bytes));
     p->body = wave_select_body(in, s);
-    if (p->body.narrow) GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kWaveNarrowFn), p->body.lds_bytes));
+    if (p->body.narrow) {
+        GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kWaveNarrowFn), p->body.lds_bytes));
+        GAMS_HIP(h, gams_lds_attr(h, reinterpret_cast<const void *>(kWaveOneWaveFn), wave_onewave_lds_bytes()));
+    }
     if (s.taper)
         wave_fill_tiles_tapered(p, wave_slots(h->cus));
     else
@@ -897,6 +906,7 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
     if (p->tiles.empty()) {
         // nothing to launch, whatever input or body was asked for: no kernel ran, so not the narrow one
         p->last_body.store(GAMS_WAVE_BODY_WIDE, std::memory_order_relaxed);
+        p->last_cut.store(GAMS_WAVE_CUT_AUTO, std::memory_order_relaxed);
         if (p->pipelined) GAMS_HIP(h, hipEventRecord(w.done, st));
         return GAMS_OK;
     }
@@ -922,6 +932,12 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
                                                         : "wave: this plan has no narrow body");
     const bool narrow = narrow_fit && p->body_req != GAMS_WAVE_BODY_WIDE;
     p->last_body.store(narrow ? GAMS_WAVE_BODY_NARROW : GAMS_WAVE_BODY_WIDE, std::memory_order_relaxed);
+    // ... in one of its two cuts of the tile: two waves x 24 windows or one wave x 48 (wave_select_cut)
+    if (p->cut_req == GAMS_WAVE_CUT_ONE_WAVE && !narrow_fit)
+        return gams_fail(h, GAMS_ESTATE, p->body.narrow ? "wave: the one-wave cut reads the G/C plane, this pass reads the bytes"
+                                                        : "wave: this plan has no narrow body to cut");
+    const WaveCut cut = narrow ? wave_select_cut(p->body, p->cut_req) : WaveCut{};
+    p->last_cut.store(cut.cut, std::memory_order_relaxed);
     const WaveArgs a = wave_args(p, w, slot, use_plane);
     const unsigned nt = (unsigned)p->tiles.size();
     if (p->sel.direct) {
@@ -937,7 +953,8 @@ static int wave_pass_on_way(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t k) {
             GAMS_HIP(h, hipGetLastError());
         }
     } else if (narrow) {
-        hipLaunchKernelGGL(kWaveNarrowFn, dim3(nt), dim3(p->body.nth), p->body.lds_bytes, st, a.tiles, a.seq, a);
+        const WaveFastFn cut_fn = cut.cut == GAMS_WAVE_CUT_ONE_WAVE ? kWaveOneWaveFn : kWaveNarrowFn;
+        hipLaunchKernelGGL(cut_fn, dim3(nt), dim3(cut.nth), cut.lds_bytes, st, a.tiles, a.seq, a);
         GAMS_HIP(h, hipGetLastError());
     } else if (p->fast_fn) {
         hipLaunchKernelGGL(p->fast_fn, dim3(nt), dim3(p->sel.nth), p->sel.lds_bytes, st, a.tiles, a.seq, a);
@@ -1008,6 +1025,21 @@ int gams_wave_plan_last_body(gams_gpu_t *h, gams_wave_plan_t *p, int *body) {
     if (!h || !p || !body) return gams_fail(h, GAMS_EINVAL, "wave_plan_last_body: null argument");
     if (!p->ran) return gams_fail(h, GAMS_ESTATE, "wave_plan_last_body: no run yet");
     *body = p->last_body.load(std::memory_order_relaxed);
+    return GAMS_OK;
+}
+
+int gams_wave_plan_set_cut(gams_gpu_t *h, gams_wave_plan_t *p, int mode) {
+    if (!h || !p) return gams_fail(h, GAMS_EINVAL, "wave_plan_set_cut: null argument");
+    if (mode != GAMS_WAVE_CUT_AUTO && mode != GAMS_WAVE_CUT_TWO_WAVES && mode != GAMS_WAVE_CUT_ONE_WAVE)
+        return gams_fail(h, GAMS_EINVAL, "wave_plan_set_cut: mode is 0 (auto), 1 (two waves) or 2 (one wave)");
+    p->cut_req = mode;
+    return GAMS_OK;
+}
+
+int gams_wave_plan_last_cut(gams_gpu_t *h, gams_wave_plan_t *p, int *cut) {
+    if (!h || !p || !cut) return gams_fail(h, GAMS_EINVAL, "wave_plan_last_cut: null argument");
+    if (!p->ran) return gams_fail(h, GAMS_ESTATE, "wave_plan_last_cut: no run yet");
+    *cut = p->last_cut.load(std::memory_order_relaxed);
     return GAMS_OK;
 }
 

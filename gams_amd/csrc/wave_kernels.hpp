@@ -1157,6 +1157,312 @@ __global__ __launch_bounds__(128, 8) void wave_fast_narrow_kernel(const WaveTile
     wave_fast_tile<24, 100, 10, 100, false, 128, true>(tl, seq_p, a);
 }
 
+// The one-wave cut of the narrow body (wave_select_cut): the same tile -- 3,072 K slots, 2,971 windows -- as 64 threads x
+// 48 windows, a workgroup of ONE wave.  Same tile table, slots, arguments and readers as the two-wave cut; the per-thread
+// fixed work is spread over twice the windows again and no workgroup barrier is left (__syncthreads() in a workgroup of
+// one wave is a wait for the wave's own LDS traffic).  What differs from wave_fast_tile<24, ..., 128, true>:
+//   LDS      pad (128 B of zeros) | BM (the tile's plane bytes, 3,872 B) and, OVER both, K (3,200 B) | PS (80 entries).
+//            Every lane pulls the 580 bits of its 48 slots into registers, the wave waits, and only then is any count
+//            stored: K may lie over the bit stream.  No scratch (the scan of phase 4b is a wave scan) and no RK: 4,640 B
+//            a workgroup (wave_onewave_lds_bytes), so the 32 waves a CU may hold all find room in its 160 KB.
+//   phase 2  the baked form for EVERY tile, the ones at a ctg start (vb < 0) included: their slots in front of the ctg
+//            start read the zeroed pad (bit -1,010 at the lowest: 1,024 bits of pad), which keeps the rolling count of
+//            the first real window right; the owners of those slots (threads 0 .. 2) then clear them in K and take their
+//            block sums again from K -- K, PS, the lag sums and the bound on S1 are then what the other cuts' run-time
+//            counting path leaves, and the tiles behind a ctg start pay nothing for it.
+//   phase 3  a thread's 48 windows as two runs of 24, each exactly the z-score loop of the two-wave cut's thread 2 t + r
+//            (og[] / in[] of the run re-read from K: 14 count dwords live instead of 25), S1f / S2f carried across the
+//            seam and the lag sums assembled once (two PS blocks + the four counts at K byte 48 t + 96).  The bound on
+//            S1 is renewed every twelve windows, from that window's S1: every cut sends the same windows down the exact
+//            path.  Window q of run r sits at bit 24 r + q of the 64-bit masks.
+constexpr uint32_t kOneWavePad = 128;                                             // bytes of zeros in front of the bit stream
+constexpr uint32_t kOneWavePieces = (((64u * 48u * 10u + 100u + 30u) / 16u + 1u) + 7u + 7u) / 8u;   // 16-B pieces of plane bytes: 242
+constexpr uint32_t kOneWaveLds = kOneWavePad + kOneWavePieces * 16u + (64u + 16u) * 8u;             // pad | BM (K over both) | PS
+__device__ __forceinline__ void wave_onewave_tile(const WaveTile tl, const uint8_t *const seq_p, const WaveArgs &a) {
+    constexpr uint32_t W = 48, HW = 24, NT_ = 64, SIZE = 100, STEP = 10, LAG = 100;
+    constexpr uint32_t TW = NT_ * W - LAG - 1u;
+    constexpr uint32_t PAD = kOneWavePad, NV = kOneWavePieces;
+    static_assert(NV == (((NT_ * W * STEP + SIZE + 30u) / 16u + 1u) + 7u + 7u) / 8u, "the pieces of wave_fast_tile's plane copy");
+    constexpr uint32_t NLV = (NV + NT_ - 1u) / NT_;
+    constexpr uint32_t NBITS = W * STEP + SIZE;
+    constexpr uint32_t NDW = (NBITS + 31u) / 32u + 1u;              // + 1 for the realignment
+    constexpr uint32_t OVER = PAD + NV * 16u;                       // pad | BM, and K over them
+    static_assert(PAD * 8u >= (LAG + 1u) * STEP, "the pad holds every bit in front of a ctg start");
+    static_assert(((PAD * 8u + 127u + (NT_ - 1u) * W * STEP) >> 5) + NDW <= OVER / 4u, "phase 2 reads inside pad | BM");
+    static_assert((NT_ - 1u) * W + LAG + W + 8u <= OVER, "K (with the slots masked threads read) fits under pad | BM");
+    static_assert(LAG / W == 2u && LAG % W == 4u && W % 8u == 0u, "lag sums: two PS blocks + the dword at K byte 48 t + 96, a qword's first");
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t *BW = reinterpret_cast<const uint32_t *>(smem);
+    uint8_t *K = smem;
+    uint2 *PS = reinterpret_cast<uint2 *>(smem + OVER);
+
+    const uint32_t tid = threadIdx.x;
+    if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 16 + 10] = __builtin_amdgcn_s_memrealtime();
+    const uint32_t lag = LAG;
+    const uint32_t w0 = tl.w0;
+    const uint32_t w1 = min(w0 + TW, tl.n_win);
+    const uint32_t nvalid = w1 - w0;
+    const int32_t vb = (int32_t)w0 - (int32_t)LAG - 1;       // window held by K slot 0 (may be < 0)
+    const uint32_t wh = vb > 0 ? (uint32_t)vb : 0u;
+    const uint32_t a0 = (wh * STEP) & ~127u;
+
+    wave_stamp(a, 0);
+    // ---- phase 1: the tile's plane bytes behind the zeroed pad ------------------------------------
+    {
+        const uint4 *const pl = reinterpret_cast<const uint4 *>(a.plane + ((tl.seq_off + a0) >> 3));
+        uint4 *const BV = reinterpret_cast<uint4 *>(smem + PAD);
+        uint4 v[NLV];
+#pragma unroll
+        for (uint32_t k = 0; k < NLV; ++k) v[k] = pl[min(tid + NT_ * k, NV - 1u)];
+        if (tid < PAD / 16u) reinterpret_cast<uint4 *>(smem)[tid] = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+        for (uint32_t k = 0; k < NLV; ++k) BV[min(tid + NT_ * k, NV - 1u)] = v[k];
+    }
+    __syncthreads();
+    wave_stamp(a, 1);
+    wave_stamp(a, 2);
+
+    // ---- phase 2: k of the thread's 48 slots, from bits held in registers ---------------------------
+    const uint32_t nK = LAG + 1u + nvalid;
+    const uint32_t base = tid * W;                  // first K slot of the thread = slot of the outgoing count of window q = 0
+    uint32_t r[NDW];
+    {
+        // bit of slot `base`: (vb + base) * STEP - a0 behind the pad; >= 14 for every tile (vb >= -101)
+        const uint32_t x0 = (uint32_t)((vb + (int32_t)base) * (int32_t)STEP - (int32_t)a0 + (int32_t)(PAD * 8u));
+        const uint32_t d0 = x0 >> 5, sh = x0 & 31u;
+#pragma unroll
+        for (uint32_t i = 0; i < NDW; ++i) r[i] = BW[d0 + i];
+#pragma unroll
+        for (uint32_t i = 0; i + 1u < NDW; ++i) r[i] = __builtin_amdgcn_alignbit(r[i + 1u], r[i], sh);
+    }
+    __syncthreads();                                // every lane holds its bits: K may now be stored over the bit stream
+    if (base < nK) {
+        auto field = [&](uint32_t off) -> uint32_t {
+            const uint32_t d = off >> 5, s = off & 31u;
+            if (s + STEP <= 32u) return __builtin_amdgcn_ubfe(r[d], s, STEP);
+            return __builtin_amdgcn_alignbit(r[d + 1u], r[d], s) & ((1u << STEP) - 1u);
+        };
+        uint32_t k = 0;
+#pragma unroll
+        for (uint32_t d = 0; d < SIZE / 32u; ++d) k += __popc(r[d]);
+        k += __popc(r[SIZE / 32u] & ((1u << (SIZE % 32u)) - 1u));
+        uint32_t packed = k, held = 0, s1 = 0, s2 = 0;
+        auto put = [&](uint32_t j4, uint32_t four) {            // four counts of slots base + j4 ..
+            s1 = __builtin_amdgcn_udot4(four, 0x01010101u, s1, false);
+            s2 = __builtin_amdgcn_udot4(four, four, s2, false);
+            if ((j4 & 4u) == 0u)
+                held = four;
+            else if (base + j4 - 4u < nK)
+                reinterpret_cast<uint2 *>(K)[(base + j4 - 4u) >> 3] = make_uint2(held, four);
+        };
+#pragma unroll
+        for (uint32_t j = 1; j < W; ++j) {
+            k += __popc(field(SIZE + (j - 1u) * STEP));
+            k -= __popc(field((j - 1u) * STEP));
+            if ((j & 3u) == 0u) {
+                put(j - 4u, packed);
+                packed = k;
+            } else {
+                packed |= k << (8u * (j & 3u));
+            }
+        }
+        put(W - 4u, packed);
+        PS[tid] = make_uint2(s1, s2);   // slots past nK only reach windows past the tile's end
+    }
+    // A tile at a ctg start (6 % of the headline's): the slots in front of the ctg start -- the first -vb <= 101, i.e.
+    // threads 0 .. 2 -- read 0.  Their owners clear them in K and take their block sums again, from K.
+    if (vb < 0) {
+        __syncthreads();
+        const uint32_t nz = (uint32_t)(-vb);
+        if (base < nz) {
+            uint32_t *const KT = reinterpret_cast<uint32_t *>(K) + (base >> 2);
+            uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+            for (uint32_t d = 0; d < W / 4u; ++d) {
+                uint32_t x = KT[d];
+                const uint32_t j4 = base + 4u * d;               // the dword's first slot
+                if (nz > j4) x = nz >= j4 + 4u ? 0u : x & (~0u << (8u * (nz - j4)));
+                KT[d] = x;
+                s1 = __builtin_amdgcn_udot4(x, 0x01010101u, s1, false);
+                s2 = __builtin_amdgcn_udot4(x, x, s2, false);
+            }
+            PS[tid] = make_uint2(s1, s2);
+        }
+    }
+    __syncthreads();
+    wave_stamp(a, 3);
+
+    // ---- phase 3: rolling sums + decision, two runs of 24 windows ------------------------------------
+    uint64_t crest = 0, trough = 0, pend = 0;        // one bit per owned window
+    {
+        const uint2 *const K2 = reinterpret_cast<const uint2 *>(K) + tid * (W / 8u);
+        uint64_t can = 0;
+        if (!a.no_signal && base < nvalid) {
+            const uint32_t hi_q = min(W, nvalid - base);                                   // q < hi_q
+            const uint32_t lo_q = w0 + base >= lag ? 0u : min(W, lag - (w0 + base));       // q >= lo_q
+            can = ((1ull << hi_q) - 1ull) & ~((1ull << lo_q) - 1ull);
+        }
+        const float nf = (float)LAG, aA = a.aA, aB = a.aB;
+        float S1f = 0.0f, S2f = 0.0f, kinf = 0.0f;
+        uint64_t sig64 = 0, nos64 = 0, dn64 = 0;
+#pragma unroll
+        for (uint32_t run = 0; run < 2u; ++run) {
+            uint32_t og[HW / 4u], kq[8];             // outgoing counts; K bytes [48 t + 24 run + 96, + 32): kq[1 ..] are in[]
+            // (the seam: the second run's counts are not to be loaded while the first run's are live -- 28 dwords)
+            if (run != 0u) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (uint32_t d = 0; d < 3u; ++d) {
+                const uint2 t = K2[3u * run + d];
+                og[2u * d] = t.x;
+                og[2u * d + 1u] = t.y;
+            }
+#pragma unroll
+            for (uint32_t d = 0; d < 4u; ++d) {
+                const uint2 t = K2[12u + 3u * run + d];
+                kq[2u * d] = t.x;
+                kq[2u * d + 1u] = t.y;
+            }
+            if (run == 0u) {
+                // S1, S2 over K[base, base + lag): two blocks of PS and the four counts of kq[0]
+                const uint2 p0 = PS[tid], p1 = PS[tid + 1u];
+                uint32_t S1 = p0.x + p1.x, S2 = p0.y + p1.y;
+                S1 = __builtin_amdgcn_udot4(kq[0], 0x01010101u, S1, false);
+                S2 = __builtin_amdgcn_udot4(kq[0], kq[0], S2, false);
+                S1f = (float)S1;
+                S2f = (float)S2;
+                kinf = (float)(kq[1] & 0xFFu);
+            }
+            uint32_t sigm = 0, nosm = 0, dnm = 0;
+            float cA = 0.0f, cB = 0.0f;
+#pragma unroll
+            for (uint32_t q = 0; q < HW; ++q) {
+                if (q % 12u == 0u) {                                     // the bound on S1 of the next twelve windows
+                    const float ub = S1f + (float)(12u * SIZE);          // integers below 2^24: exact
+                    cA = __builtin_fmaf(a.gA1, ub, a.gA0);
+                    cB = __builtin_fmaf(a.gB1, ub, a.gB0);
+                }
+                const float koutf = (float)((og[q >> 2] >> (8u * (q & 3u))) & 0xFFu);
+                const float kkf = (float)((kq[1u + ((q + 1u) >> 2)] >> (8u * ((q + 1u) & 3u))) & 0xFFu);
+                uint32_t xs, xn, dn;
+                z_decide(nf, kkf, S1f, S2f, aA, aB, cA, cB, xs, xn, dn);
+                sigm = __builtin_amdgcn_alignbit(sigm, xs, 31);
+                nosm = __builtin_amdgcn_alignbit(nosm, xn, 31);
+                dnm = __builtin_amdgcn_alignbit(dnm, dn, 31);
+                S1f = (S1f - koutf) + kinf;
+                S2f = __builtin_fmaf(-koutf, koutf, S2f);
+                S2f = __builtin_fmaf(kinf, kinf, S2f);
+                kinf = kkf;
+            }
+            // window q of the run sits at bit 23 - q of the accumulators: flip to bit q, then to bit 24 run + q
+            sig64 |= (uint64_t)(__brev(sigm) >> (32u - HW)) << (HW * run);
+            nos64 |= (uint64_t)(__brev(nosm) >> (32u - HW)) << (HW * run);
+            dn64 |= (uint64_t)(__brev(dnm) >> (32u - HW)) << (HW * run);
+        }
+        if (!(a.g0 < INFINITY)) sig64 = nos64 = 0;   // thresholds outside the decidable range: every window is exact
+        uint64_t decided = sig64 | nos64;
+        crest = sig64 & ~dn64;
+        trough = sig64 & dn64;
+        // window i == lag averages windows [0, lag) like i == lag + 1 (see wave_fast_tile): redone by its owner
+        const uint32_t qlag = lag - (w0 + base);                             // wraps when i == lag is not here
+        if (qlag < W) {
+            const uint64_t bit = 1ull << qlag;
+            uint32_t s1 = 0, s2 = 0;
+            for (uint32_t j = 0; j < lag; ++j) {
+                const uint32_t kv = K[base + qlag + 1u + j];
+                s1 += kv;
+                s2 += kv * kv;
+            }
+            const uint32_t kk = K[base + qlag + lag + 1u];
+            uint32_t xs, xn, dn;
+            z_decide(nf, (float)kk, (float)s1, (float)s2, aA, aB, __builtin_fmaf(a.gA1, (float)s1, a.gA0),
+                     __builtin_fmaf(a.gB1, (float)s1, a.gB0), xs, xn, dn);
+            const bool sg = (xs >> 31) != 0u, no = (xn >> 31) != 0u, below = (dn >> 31) != 0u;
+            const bool exact_all = !(a.g0 < INFINITY);
+            decided = ((sg || no) && !exact_all) ? (decided | bit) : (decided & ~bit);
+            crest = (sg && !below) ? (crest | bit) : (crest & ~bit);
+            trough = (sg && below) ? (trough | bit) : (trough & ~bit);
+        }
+        crest &= can & decided;
+        trough &= can & decided;
+        pend = can & ~decided;
+        // homopolymer / N runs: settled by the precomputed table, tested for pending windows only
+        if (__ballot(pend != 0ull)) {
+            uint64_t todo = pend;
+            while (todo) {
+                const uint32_t q = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+                todo &= todo - 1ull;
+                const uint32_t i = w0 + base + q;
+                const uint32_t tj = base + q + (i == lag ? 1u : 0u);
+                const uint32_t kk = K[base + q + lag + 1u];
+                bool same = true;
+                for (uint32_t j = 0; j < lag && same; ++j) same = K[tj + j] == kk;
+                if (same) {
+                    const int sg = a.const_sig[kk];
+                    pend &= ~(1ull << q);
+                    crest |= sg > 0 ? 1ull << q : 0ull;
+                    trough |= sg < 0 ? 1ull << q : 0ull;
+                }
+            }
+        }
+    }
+    wave_stamp(a, 4);
+    // Guard-band windows: exact f32 order, one window at a time by the whole wave.
+    {
+        unsigned long long bal = __ballot(pend != 0ull);
+        uint32_t n_exact = 0;
+        while (bal) {
+            const int L = __ffsll(bal) - 1;                                   // wave-uniform
+            const uint32_t plo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pend, L);
+            const uint32_t phi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pend >> 32), L);
+            const uint32_t q = plo ? (uint32_t)__ffs((int)plo) - 1u : 31u + (uint32_t)__ffs((int)phi);
+            const uint32_t baseL = (uint32_t)L * W;
+            const uint32_t first = (w0 + baseL + q == lag) ? 1u : 0u;
+            const int sg = exact_signal_wave(K, baseL + q + first, baseL + q + lag + 1u, lag, a.fsize, a.thr);
+            if (tid == (uint32_t)L) {
+                pend &= ~(1ull << q);
+                crest |= sg > 0 ? 1ull << q : 0ull;
+                trough |= sg < 0 ? 1ull << q : 0ull;
+            }
+            ++n_exact;
+            bal = __ballot(pend != 0ull);
+        }
+        if (n_exact && tid == 0)
+            atomicAdd(&a.counters[(blockIdx.x & (kShards - 1u)) * kShardWords + 1u], (unsigned long long)n_exact);
+    }
+    wave_stamp(a, 5);
+    // ---- phase 4b: every thread writes its own records at its rank in the tile (a wave scan) ----------
+    if ((a.flags & GAMS_WAVE_PEAKS) != 0) {
+        const uint64_t both = crest | trough;
+        const uint32_t mine = (uint32_t)__popcll((unsigned long long)both);
+        gams_peak_t *const region = a.peaks + (size_t)blockIdx.x * a.tile_cap;
+        const uint32_t inc = wave_incl_scan(mine);
+        const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        if (tid == 0) a.tile_cnt[blockIdx.x] = tot;
+        uint32_t pos = inc - mine;
+        uint64_t bits = both;
+        while (bits) {
+            const uint32_t q = (uint32_t)__ffsll((unsigned long long)bits) - 1u;
+            bits &= bits - 1ull;
+            if (pos < a.tile_cap) {
+                gams_peak_t pk;
+                pk.ctg = tl.ctg;
+                pk.window = w0 + base + q;
+                pk.gc_count = K[base + q + lag + 1u];
+                pk.signal = ((crest >> q) & 1ull) ? 1 : -1;
+                region[pos] = pk;
+            }
+            ++pos;
+        }
+    }
+    wave_stamp(a, 6);
+}
+
+__global__ __launch_bounds__(64, 8) void wave_fast_onewave_kernel(const WaveTile *const tiles_p, const uint8_t *const seq_p,
+                                                                  const WaveArgs a) {
+    const WaveTile tl = tiles_p[blockIdx.x];
+    wave_onewave_tile(tl, seq_p, a);
+}
+
 // ---- parameters whose halo does not fit a tile (large step or lag): no tiling ---------------
 // (lag+1)*step + size + 256*step > 64 KB, or the LDS prefix arrays > 160 KB: one lane per window
 // counts its own bases straight from HBM (windows barely overlap at such steps), a second kernel

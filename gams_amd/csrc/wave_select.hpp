@@ -3,6 +3,9 @@
 // Plain C++17, no HIP: the one list of wave_fast_kernel instantiations the library builds (wave.hip expands it into its
 // table of kernel pointers) and the one function that chooses from it.  A new instantiation is one line in
 // WAVE_FAST_INSTANCES plus a recipe in tests/wave_instances.py; tests/test_wave_select_cpu.py pins every choice made here.
+// Beside the list: wave_select_body (which plans run their plane-fed passes in the narrow body of the headline tile,
+// tests/test_wave_body_cpu.py) and wave_select_cut (that body in two waves x 24 windows or one wave x 48,
+// tests/test_wave_cut_cpu.py).
 #pragma once
 
 #include <algorithm>
@@ -22,7 +25,8 @@ namespace {
 //                        benchmark runs 100 / 5 / 200 and 100 / 20 / 50, doc/benchmark/Atha.md:55,276-280)
 // Beside them: wave_fast_taper_kernel<100, 10, 100, NT> (the tapered table of the (12, 100, 10, 100, 256) entry) and
 // wave_tile_kernel<KT, WIDE> for KT = unsigned char / unsigned short, WIDE = false / true; and wave_fast_narrow_kernel,
-// the (12, 100, 10, 100, 256) tile as 128 threads x 24 windows (wave_select_body below decides who takes it).
+// the (12, 100, 10, 100, 256) tile as 128 threads x 24 windows (wave_select_body below decides who takes it), and
+// wave_fast_onewave_kernel, the same tile as 64 threads x 48 windows (wave_select_cut).
 #define WAVE_FAST_INSTANCES(X)                                                                        \
     X(20, 0, 0, 0, 256) X(12, 0, 0, 0, 256) X(8, 0, 0, 0, 256) X(4, 0, 0, 0, 256)                     \
     X(28, 100, 1, 100, 64) X(28, 100, 1, 100, 128) X(28, 100, 1, 100, 256)                            \
@@ -290,6 +294,50 @@ inline WaveBody wave_select_body(const WaveSelectIn &in, const WaveSelection &se
     b.w = (uint32_t)kWaveNarrowW;
     b.lds_bytes = wave_fast_lds_bytes(sel.max_chunks, b.w, (uint32_t)e.lag, false, b.nth);
     return b;
+}
+
+// The cuts of the narrow body.  The headline tile's 3,072 K slots are 128 threads x 24 windows (two waves a tile,
+// wave_fast_narrow_kernel) and also 64 threads x 48 windows (ONE wave a tile, wave_fast_onewave_kernel): the fixed work
+// of a thread is spread over twice the windows again and no workgroup barrier is left.  The one-wave launch lays K over
+// the tile's bit stream (every lane holds its bits in registers before any count is stored), has no scratch and no RK,
+// and serves the tiles at a ctg start from the baked path too, through a zeroed pad in front of the bit stream: its
+// carve is pad | BM | PS, which lets all 32 waves a CU may hold find room in the CU's 160 KB.
+enum : int { kWaveCutAuto = 0, kWaveCutTwoWaves = 1, kWaveCutOneWave = 2 };   // GAMS_WAVE_CUT_* of gams_gpu_diag.h
+struct WaveCut {
+    int cut = 0;                   // kWaveCutTwoWaves / kWaveCutOneWave; 0: the plan has no narrow body
+    uint32_t nth = 0, w = 0;       // threads per workgroup and windows per thread of the narrow pass
+    size_t lds_bytes = 0;
+};
+constexpr int kWaveOneWaveW = 48, kWaveOneWaveNth = 64;
+// the library's choice (kWaveCutAuto): whichever cut met the project's bar on the headline, profiles/one_wave_cut.txt
+constexpr int kWaveCutDefault = kWaveCutOneWave;
+constexpr uint32_t kWaveOneWavePad = 128;   // bytes of zeros in front of the bit stream: (lag + 1) * step = 1,010 bits at most
+
+// pad | BM: the tile's plane bytes in the 16-byte pieces of eight chunks wave_fast_tile's plane copy moves
+constexpr size_t wave_onewave_bm_bytes() {
+    const uint32_t chunks = ((uint32_t)(kWaveOneWaveNth * kWaveOneWaveW) * 10u + 100u + 30u) / 16u + 1u;
+    return kWaveOneWavePad + (size_t)((chunks + 7u + 7u) / 8u) * 16u;
+}
+// K as the one-wave cut reads it: a masked thread still reads the qwords of its second run, 48 t + 120 .. 48 t + 152
+constexpr size_t wave_onewave_k_bytes() { return (size_t)(kWaveOneWaveNth - 1) * kWaveOneWaveW + 152u; }
+constexpr size_t wave_onewave_lds_bytes() { return wave_onewave_bm_bytes() + (size_t)(kWaveOneWaveNth + 16) * 8u; }
+
+// The cut a narrow pass of the plan runs: `cut_req` (gams_wave_plan_set_cut) when it names one, else the library's choice.
+// Nothing (cut 0) for a plan without the narrow body.
+inline WaveCut wave_select_cut(const WaveBody &body, int cut_req) {
+    WaveCut c;
+    if (!body.narrow) return c;
+    c.cut = cut_req == kWaveCutAuto ? kWaveCutDefault : cut_req;
+    if (c.cut == kWaveCutOneWave) {
+        c.nth = (uint32_t)kWaveOneWaveNth;
+        c.w = (uint32_t)kWaveOneWaveW;
+        c.lds_bytes = wave_onewave_lds_bytes();
+    } else {
+        c.nth = body.nth;
+        c.w = body.w;
+        c.lds_bytes = body.lds_bytes;
+    }
+    return c;
 }
 
 // the tile kernel of a selection, spelled the way rocprofv3 prints the instantiation

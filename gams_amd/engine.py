@@ -340,6 +340,16 @@ class WavePlan:
         self.eng.check(self.eng.lib.gams_wave_plan_last_body(self.eng.h, self.p, C.byref(v)))
         return int(v.value)
 
+    def set_cut(self, mode):
+        """the cut of the narrow body: _lib.WAVE_CUT_AUTO / _TWO_WAVES (128 x 24) / _ONE_WAVE (64 x 48)"""
+        self.eng.check(self.eng.lib.gams_wave_plan_set_cut(self.eng.h, self.p, mode))
+
+    def last_cut(self):
+        """the cut of the most recently queued pass: _lib.WAVE_CUT_TWO_WAVES / _ONE_WAVE, 0 when it did not run the narrow body"""
+        v = C.c_int()
+        self.eng.check(self.eng.lib.gams_wave_plan_last_cut(self.eng.h, self.p, C.byref(v)))
+        return int(v.value)
+
     def select(self, age):
         """point peaks()/dense()/exact_count() at the run `age` runs before the most recent one"""
         self.eng.check(self.eng.lib.gams_wave_plan_select(self.eng.h, self.p, age))

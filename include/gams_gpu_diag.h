@@ -107,6 +107,19 @@ int gams_wave_plan_last_input(gams_gpu_t *h, gams_wave_plan_t *p, int *input);
 int gams_wave_plan_set_body(gams_gpu_t *h, gams_wave_plan_t *p, int mode);
 /* the body the plan's most recently queued pass ran: GAMS_WAVE_BODY_WIDE (every kernel but the narrow one) or _NARROW */
 int gams_wave_plan_last_body(gams_gpu_t *h, gams_wave_plan_t *p, int *body);
+/* The cut of the narrow body: its tile of 3,072 count slots as 128 threads x 24 windows (GAMS_WAVE_CUT_TWO_WAVES,
+ * wave_fast_narrow_kernel) or as 64 threads x 48 windows, a workgroup of one wave (GAMS_WAVE_CUT_ONE_WAVE,
+ * wave_fast_onewave_kernel), over the same tile table; GAMS_WAVE_CUT_AUTO (the default) is the library's choice.
+ * gams_wave_plan_last_body says NARROW for both.  A forced ONE_WAVE on a pass the narrow body cannot take (a plan
+ * without it, a pass that reads the bytes) fails the run with GAMS_ESTATE, as a forced NARROW does; a pass kept on the
+ * wide kernel by GAMS_WAVE_BODY_WIDE has no cut.  Results are identical; for tests and A/B runs. */
+#define GAMS_WAVE_CUT_AUTO 0
+#define GAMS_WAVE_CUT_TWO_WAVES 1
+#define GAMS_WAVE_CUT_ONE_WAVE 2
+int gams_wave_plan_set_cut(gams_gpu_t *h, gams_wave_plan_t *p, int mode);
+/* the cut of the plan's most recently queued pass: GAMS_WAVE_CUT_TWO_WAVES or _ONE_WAVE when it ran the narrow body,
+ * GAMS_WAVE_CUT_AUTO (0) when it did not */
+int gams_wave_plan_last_cut(gams_gpu_t *h, gams_wave_plan_t *p, int *cut);
 /* gams_gc_plane with the body named: the AVX2 one (GAMS_EUNSUPPORTED on a CPU without it), the portable
  * 64-bit one, or the library's choice.  Every body writes the same bytes. */
 #define GAMS_GC_BODY_AUTO 0

@@ -60,8 +60,9 @@ for arm in args.arms:
     ps = [engine.WavePlan(eng, ss, 100, args.step, 100, 3.0, 1.0, flags=_lib.WAVE_PEAKS) for ss in sets]
     # plan.body=1|2 (wide | narrow) wants plan.taper=0 in front of it in BOTH arms, e.g. `plan.taper=0,plan.body=1
     # plan.taper=0,plan.body=2`: a plan of depth 1 takes the tapered table (--flight does not turn it off), which has no
-    # narrow body, and a forced plan.body=2 then fails the run with GAMS_ESTATE
-    for k, v in kv.items():                     # plan.taper=0|1|-1, plan.tile=3072, plan.depth=2, plan.body=1|2, plan.taper_shape=25050
+    # narrow body, and a forced plan.body=2 then fails the run with GAMS_ESTATE.  plan.cut=1|2 (the narrow body in two waves x
+    # 24 windows | one wave x 48) likewise: `plan.taper=0,plan.cut=1 plan.taper=0,plan.cut=2`
+    for k, v in kv.items():                     # plan.taper=0|1|-1, plan.tile=3072, plan.depth=2, plan.body=1|2, plan.cut=1|2, plan.taper_shape=25050
                                                 # (pct4 * 1000 + pct8; was GAMS_TAPER4/8 in the environment): setters of the plan
         if k.startswith("plan."):
             for p in ps:
