@@ -140,6 +140,9 @@ PROTOTYPES = {
     "gams_gpu_sw_feature_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_uint32, _VP, _VP, _PP, C.POINTER(C.c_uint64), _VP,
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gams_gpu_locate_seq_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64),
+                                           C.POINTER(C.c_uint64)]),
+    "gams_gpu_locate_seq_chunk": (C.c_uint32, []),
     "gams_gpu_valid_spans": (C.c_int, [_VP, _VP, C.c_uint64, C.c_int32, C.c_int32, _VP, _VP, C.c_uint64,
                                        C.POINTER(C.c_uint64)]),
     "gams_gpu_gen_text": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(GenParams), _PP]),

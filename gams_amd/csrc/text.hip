@@ -13,6 +13,8 @@
 //   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
 // and `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
 //   gams_gpu_sw_feature_text       the bytes of one range file -> the sw rows of its features (stages 2-5 in sw.hip)
+// and `locate --seq` (locate.rs:124-134), behind the front of locate_text, with a writer of its own (a row may be a whole ctg):
+//   gams_gpu_locate_seq_text       the bytes of one range file -> ">{rg}\n{bases}\n" of every located line
 //
 // Pipeline (one handle, the compute stream):
 //   1. one copy of the bytes into a cached device buffer, padded with spaces to 16 B and 16 B beyond;
@@ -28,6 +30,7 @@
 // the text), the text.
 
 #include "interval_kernels.hpp"
+#include "seq_text_plan.hpp"
 #include "text_emit.hpp"
 #include "text_fmt.hpp"
 
@@ -67,6 +70,8 @@ struct gams_text_state {
     size_t d_in_cap = 0;
     char *out[4] = {};          // locate, count, anno, peak
     size_t out_cap[4] = {};
+    char *seq_out = nullptr;    // locate --seq: a buffer of its own (a text of whole ctgs would be held by the others for good)
+    size_t seq_out_cap = 0;
 };
 
 void gams_text_free(gams_gpu_t *h) {
@@ -74,6 +79,7 @@ void gams_text_free(gams_gpu_t *h) {
     if (!t) return;
     gams_pool_free(h, false, t->d_in, t->d_in_cap);
     for (int k = 0; k < 4; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
+    gams_pool_free(h, true, t->seq_out, t->seq_out_cap);
     delete t;
     h->text = nullptr;
 }
@@ -453,12 +459,9 @@ __device__ __forceinline__ uint64_t text_row_len(const RowArgs &a, uint32_t i, b
     return n.n;
 }
 
-__global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
+// behind a block's row lengths (l: this thread's, 0 = no row): the block's bytes, and its rows added to words[W_ROWS]
+__device__ __forceinline__ void row_block_totals(uint64_t l, unsigned long long *blk_bytes, unsigned long long *words) {
     __shared__ uint64_t ws[4];
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    bool bad = false;
-    const uint64_t l = text_row_len(a, i, bad);
-    if (bad) a.words[W_UNSUP] = 1ull;
     uint64_t tot;
     (void)block_excl_scan_256<uint64_t>(l, ws, tot);
     __shared__ uint32_t rows[4];
@@ -466,9 +469,17 @@ __global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
     if ((threadIdx.x & 63u) == 0u) rows[threadIdx.x >> 6] = r;
     __syncthreads();
     if (threadIdx.x == 0) {
-        a.blk_bytes[blockIdx.x] = tot;
-        atomicAdd(a.words + W_ROWS, (unsigned long long)(rows[0] + rows[1] + rows[2] + rows[3]));
+        blk_bytes[blockIdx.x] = tot;
+        atomicAdd(words + W_ROWS, (unsigned long long)(rows[0] + rows[1] + rows[2] + rows[3]));
     }
+}
+
+__global__ __launch_bounds__(256) void text_row_len_kernel(const RowArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    const uint64_t l = text_row_len(a, i, bad);
+    if (bad) a.words[W_UNSUP] = 1ull;
+    row_block_totals(l, a.blk_bytes, a.words);
 }
 
 __global__ __launch_bounds__(256) void text_row_write_kernel(const RowArgs a) {
@@ -1429,6 +1440,316 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         return GAMS_OK;
     });
 }
+
+
+// ---- `locate --seq` (locate.rs:124-134): the bytes of a range file -> ">{rg}\n{bases}\n" of every located line --------
+// Behind the front of locate_text (line index, text_parse_rg_kernel, interval_locate_kernel), six stages in all:
+//   lines, parse, locate   as for locate_text;
+//   lengths  one lane per line: a located line must lie inside its ctg and the ctg needs a slot of its length (flags,
+//            and the smallest line that leaves its ctg); its row is 1 + rg + 1 + bases + 1 bytes, and its first base is
+//            byte src of the seqset's buffer; the block sums of the lengths;
+//   offsets  their prefix over the blocks, then row_off[line] = the block's offset + the prefix inside the block.
+//            Unlike the other entries the per-line offsets are kept: the copy searches them;
+//   copy     seq_copy_kernel, below.
+// A row is 3 bytes or a whole ctg, so the writer gives lanes to bytes of the text, not to rows (seq_text_plan.hpp): one
+// workgroup per chunk of kSeqTextChunk bytes, one thread per 16-B unit of the text at a time.  A unit that lies inside
+// the bases of one row -- nearly all of them once rows are long -- is four aligned dwords and a fifth of the seqset,
+// realigned in registers (v_alignbyte) and stored as one dwordx4; a unit that holds a seam between pieces or rows -- all of
+// them when the rows are point ranges -- is put together run by run, each run the aligned dwords that hold it, shifted to
+// its place in two 64-bit registers, and leaves as one dwordx4 all the same.  Only the last unit of the whole text, when
+// the text is no multiple of 16, is stored byte by byte.  Thread 0 searches row_off for the chunk's first and last row;
+// their offsets go to LDS and every unit finds its row there by binary search; a line without a row has zero bytes and
+// is never found.
+enum : uint32_t { W_SEQ_LINE = W_EFIELD };   // this entry's use of the word: the smallest line that leaves its ctg
+enum : int { SQ_LINES = 0, SQ_PARSE, SQ_LOCATE, SQ_LENGTHS, SQ_OFFSETS, SQ_COPY, SQ_STAGES };
+
+struct SeqTextArgs {
+    TextLines t;
+    const unsigned long long *fend;           // per line: where rg ends
+    const int64_t *hit;                       // per line: the located interval, or -1
+    const uint32_t *qs, *qe;                  // per line
+    const unsigned long long *seq_off;        // per interval: the first byte of its slot in seq (~0: no slot of the ctg's length)
+    const int32_t *cs, *ce;                   // per interval
+    unsigned long long *row_off;              // n_lines + 1 (the lengths pass leaves the lengths here)
+    unsigned long long *src;                  // per line with a row: its first base in seq
+    unsigned long long *blk_bytes;            // per workgroup of 256 lines
+    const unsigned long long *blk_off;
+    unsigned long long *words;
+    const uint8_t *seq;
+    char *text;
+    uint64_t total;                           // bytes of the text
+};
+
+__global__ __launch_bounds__(256) void seq_row_len_kernel(const SeqTextArgs a) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint64_t l = 0;
+    if (i < a.t.n_lines) {
+        const int64_t c = a.hit[i];
+        if (c >= 0) {
+            const int64_t s = a.qs[i], e = a.qe[i];
+            const unsigned long long so = a.seq_off[c];
+            if (s < a.cs[c] || e > a.ce[c] || e < s) {       // the reference panics on the slice (locate.rs:133)
+                a.words[W_EID] = 1ull;
+                atomicMin(a.words + W_SEQ_LINE, (unsigned long long)i);   // integer min: whatever order lanes ran in
+            } else if (so == ~0ull) {
+                a.words[W_ENOSEQ] = 1ull;
+            } else {
+                l = seq_plan_row_len(a.fend[i] - a.t.starts[i], (uint64_t)(e - s + 1));
+                a.src[i] = so + (uint64_t)(s - a.cs[c]);
+            }
+        }
+        a.row_off[i] = l;
+    }
+    row_block_totals(l, a.blk_bytes, a.words);
+}
+
+__global__ __launch_bounds__(256) void seq_row_off_kernel(const SeqTextArgs a) {
+    __shared__ uint64_t ws[4];
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t l = i < a.t.n_lines ? a.row_off[i] : 0ull;
+    uint64_t tot;
+    const uint64_t at = a.blk_off[blockIdx.x] + block_excl_scan_256<uint64_t>(l, ws, tot);
+    if (i < a.t.n_lines) a.row_off[i] = at;
+    if (i + 1u == a.t.n_lines) a.row_off[i + 1u] = at + l;
+}
+
+// 16 bytes from p, which is 4-B aligned: one dwordx4 load (global memory takes it at dword alignment)
+struct __attribute__((packed, aligned(4))) Dwords4 {
+    uint32_t x, y, z, w;
+};
+
+// Bytes [0, len) of `from`, 1 <= len <= 16, as a little-endian value of 128 bits (lo, hi), zero above them: aligned
+// dword loads, issued together, of the dwords that hold a byte of the run and of no other -- each lies inside the
+// buffer the run lies in --, realigned in registers.
+__device__ __forceinline__ void load_run16(const uint8_t *from, uint32_t len, uint64_t &lo, uint64_t &hi) {
+    const uint32_t sh = (uint32_t)reinterpret_cast<uintptr_t>(from) & 3u, need = sh + len;
+    const uint32_t *const w = reinterpret_cast<const uint32_t *>(from - sh);
+    const uint32_t w0 = w[0], w1 = need > 4u ? w[1] : 0u, w2 = need > 8u ? w[2] : 0u, w3 = need > 12u ? w[3] : 0u,
+                   w4 = need > 16u ? w[4] : 0u;
+    lo = __builtin_amdgcn_alignbyte(w1, w0, sh) | (uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32;
+    hi = __builtin_amdgcn_alignbyte(w3, w2, sh) | (uint64_t)__builtin_amdgcn_alignbyte(w4, w3, sh) << 32;
+    if (len < 8u) {
+        lo &= (1ull << (8u * len)) - 1ull;
+        hi = 0ull;
+    } else if (len < 16u) {
+        hi &= (1ull << (8u * (len - 8u))) - 1ull;
+    }
+}
+
+// rows of a chunk whose offsets are searched in LDS (16 KiB of it); a chunk with more -- long runs of lines without
+// rows -- searches them in global memory
+constexpr uint32_t kSeqStageRows = 2048;
+
+// The units of chunk [c0, c1) that belong to this thread.  `ro` holds the offsets of the chunk's rows and the one behind
+// them, n_rows + 1 entries, entry 0 being row `base` of the text: a.row_off + base itself, or its copy in LDS.
+__device__ __forceinline__ void seq_copy_units(const SeqTextArgs &a, const unsigned long long *ro, uint64_t base, uint64_t n_rows,
+                                               uint64_t c0, uint64_t c1) {
+    for (uint64_t p = c0 + 16u * threadIdx.x; p < c1; p += 16u * 256u) {
+        const uint64_t pe = p + 16u < c1 ? p + 16u : c1;
+        uint64_t r = seq_plan_row_at(ro, 0, n_rows, p);
+        // the row: where it begins and ends in the text, its rg in the input, its first base in the seqset
+        uint64_t r_at = ro[r], r_end = ro[r + 1u], rg_at = a.t.starts[base + r], rg_len = a.fend[base + r] - rg_at, src = a.src[base + r];
+        SeqRun u = seq_plan_run(r_at, rg_len, r_end - r_at - rg_len - 3u, p, pe);
+        uint64_t lo = 0, hi = 0;
+        if (u.piece == SEQ_BASES && u.len == 16u) {
+            // the unit lies inside the bases of one row: four aligned dwords and, off the dword grid, a fifth (it holds
+            // byte 15 of the unit, so it begins inside the ctg)
+            const uint64_t s = src + u.src_off;
+            const uint8_t *const s4 = a.seq + (s & ~3ull);
+            const uint32_t sh = (uint32_t)s & 3u;
+            const Dwords4 v = *reinterpret_cast<const Dwords4 *>(s4);
+            const uint32_t v4 = sh ? *reinterpret_cast<const uint32_t *>(s4 + 16) : 0u;
+            lo = __builtin_amdgcn_alignbyte(v.y, v.x, sh) | (uint64_t)__builtin_amdgcn_alignbyte(v.z, v.y, sh) << 32;
+            hi = __builtin_amdgcn_alignbyte(v.w, v.z, sh) | (uint64_t)__builtin_amdgcn_alignbyte(v4, v.w, sh) << 32;
+        } else {
+            // a seam inside the unit: run by run, each shifted to its place
+            for (;;) {
+                uint64_t b_lo = u.piece == SEQ_GT ? (uint64_t)'>' : (uint64_t)'\n', b_hi = 0;
+                if (u.piece == SEQ_RG) load_run16(reinterpret_cast<const uint8_t *>(a.t.in) + rg_at + u.src_off, (uint32_t)u.len, b_lo, b_hi);
+                if (u.piece == SEQ_BASES) load_run16(a.seq + src + u.src_off, (uint32_t)u.len, b_lo, b_hi);
+                const uint32_t j = (uint32_t)(u.dst_off - p);  // the run's first byte in the unit; it ends inside it
+                if (j == 0u) {
+                    lo |= b_lo;
+                    hi |= b_hi;
+                } else if (j < 8u) {
+                    lo |= b_lo << (8u * j);
+                    hi |= (b_hi << (8u * j)) | (b_lo >> (64u - 8u * j));
+                } else {
+                    hi |= b_lo << (8u * (j - 8u));
+                }
+                const uint64_t pos = u.dst_off + u.len;
+                if (pos >= pe) break;
+                if (pos == r_end) {
+                    r = seq_plan_next_row(ro, r, n_rows, pos);
+                    r_at = ro[r], r_end = ro[r + 1u], rg_at = a.t.starts[base + r], rg_len = a.fend[base + r] - rg_at, src = a.src[base + r];
+                }
+                u = seq_plan_run(r_at, rg_len, r_end - r_at - rg_len - 3u, pos, pe);
+            }
+        }
+        if (pe - p == 16u) {
+            *reinterpret_cast<uint4 *>(a.text + p) = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+        } else {                                               // the ragged tail of the whole text
+            for (uint32_t j = 0; j < (uint32_t)(pe - p); ++j) a.text[p + j] = (char)((j < 8u ? lo >> (8u * j) : hi >> (8u * (j - 8u))) & 0xffu);
+        }
+    }
+}
+
+// Never launched when the lengths pass set an error word, nor for an empty text: every row it reads was checked there.
+__global__ __launch_bounds__(256) void seq_copy_kernel(const SeqTextArgs a) {
+    __shared__ uint64_t rows[2];
+    __shared__ unsigned long long srow[kSeqStageRows + 1];
+    const uint64_t c0 = seq_plan_chunk_begin(blockIdx.x), c1 = seq_plan_chunk_end(blockIdx.x, a.total);
+    if (threadIdx.x == 0) {
+        rows[0] = seq_plan_row_at(a.row_off, 0, a.t.n_lines, c0);
+        rows[1] = seq_plan_row_at(a.row_off, rows[0], a.t.n_lines, c1 - 1u) + 1u;
+    }
+    __syncthreads();
+    const uint64_t r_lo = rows[0], n_rows = rows[1] - rows[0];   // the chunk's rows: [r_lo, r_lo + n_rows)
+    if (n_rows <= kSeqStageRows) {
+        for (uint32_t k = threadIdx.x; k <= (uint32_t)n_rows; k += 256u) srow[k] = a.row_off[r_lo + k];
+        __syncthreads();
+        seq_copy_units(a, srow, r_lo, n_rows, c0, c1);
+    } else {
+        seq_copy_units(a, a.row_off + r_lo, r_lo, n_rows, c0, c1);
+    }
+}
+
+struct SeqJob {
+    gams_seqset_t *s;
+    const gams_index_t *ctg_ix;
+    const gams_names_t *chr;
+    const uint32_t *ctg_index;
+    const int32_t *chr_start, *chr_end;
+};
+
+int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n_bytes, const char **text, uint64_t *text_bytes,
+                   uint64_t *n_rows) {
+    const std::string who = "gpu_locate_seq_text";
+    const uint64_t n_ctg = J.ctg_ix->m;
+    *text = "";
+    *text_bytes = 0;
+    *n_rows = 0;
+    if (!J.s->have_bytes)
+        return gams_fail(h, GAMS_ESTATE, who + ": the seqset holds the G/C plane only: this call needs the sequence bytes");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    GAMS_HIP(h, gams_stopwatch_reserve(h, SQ_STAGES));
+    hipStream_t st = h->compute;
+    const StageClock stage{h, st};
+    // the per-ctg tables: one page-locked image, one copy, queued in front of the line index
+    PoolBlock d_tab(h, false), pin(h, true), s1(h, false);
+    const size_t n_tab = std::max<uint64_t>(n_ctg, 1);
+    struct Tabs {
+        unsigned long long *seq_off;
+        int32_t *cs, *ce;
+    };
+    auto tabs = [&](Carver &c) {
+        Tabs t{};
+        t.seq_off = c.take<unsigned long long>(n_tab);
+        t.cs = c.take<int32_t>(n_tab);
+        t.ce = c.take<int32_t>(n_tab);
+        return t;
+    };
+    const size_t b_tabs = layout_bytes(tabs);
+    GAMS_TRY(h, who, pin.alloc(b_tabs));
+    GAMS_TRY(h, who, d_tab.alloc(b_tabs));
+    const Tabs ht = carve(pin.p, tabs), dt = carve(d_tab.p, tabs);
+    for (uint64_t c = 0; c < n_ctg; ++c) {
+        // a slot that does not hold the ctg is an error only where a line is located to the ctg: the lengths pass says so
+        const uint32_t slot = J.ctg_index[c];
+        const bool holds = slot != UINT32_MAX && slot < J.s->n_ctg &&
+                           (int64_t)J.s->len[slot] == (int64_t)J.chr_end[c] - J.chr_start[c] + 1;
+        ht.seq_off[c] = holds ? J.s->off[slot] : ~0ull;
+        ht.cs[c] = J.chr_start[c];
+        ht.ce[c] = J.chr_end[c];
+    }
+    GAMS_TRY(h, who, hipMemcpyAsync(d_tab.p, pin.p, b_tabs, hipMemcpyHostToDevice, st));
+    TextFront F(h);
+    GAMS_TRY(h, who, stage(SQ_LINES, true));
+    const int rc_front = text_front(h, who, bytes, n_bytes, F);
+    if (rc_front != GAMS_OK) return rc_front;
+    const uint32_t L = F.L;
+    if (L == 0) return GAMS_OK;                                // (the stopwatch stays invalid, as text_front left it)
+    gams_text_state *T = h->text;
+    const uint32_t nbr = (L + 255u) / 256u;
+    SeqTextArgs a{};
+    unsigned long long *d_starts = nullptr, *d_fend = nullptr, *d_blk_off = nullptr;
+    uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr;
+    int64_t *d_hit = nullptr;
+    auto cols = [&](Carver &c) {   // starts | grp qs qe | fend hit | src row_off | the blocks' bytes and prefix
+        d_starts = c.take<unsigned long long>((size_t)F.nl + 2);
+        d_grp = c.take<uint32_t>(L);
+        d_qs = c.take<uint32_t>(L);
+        d_qe = c.take<uint32_t>(L);
+        d_fend = c.take<unsigned long long>(L);
+        d_hit = c.take<int64_t>(L);
+        a.src = c.take<unsigned long long>(L);
+        a.row_off = c.take<unsigned long long>((size_t)L + 1);
+        a.blk_bytes = c.take<unsigned long long>((size_t)nbr + 1);
+        d_blk_off = c.take<unsigned long long>((size_t)nbr + 1);
+    };
+    GAMS_TRY(h, who, s1.alloc(layout_bytes(cols)));
+    carve(s1.p, cols);
+    hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, T->d_in, n_bytes, F.n16, F.d_bnloff, F.nl, d_starts);
+    GAMS_TRY(h, who, hipMemsetAsync(F.d_words + W_SEQ_LINE, 0xff, 8, st));
+    GAMS_TRY(h, who, stage(SQ_LINES, false));
+    a.t = TextLines{reinterpret_cast<const char *>(T->d_in), d_starts, F.nl, L};
+    a.fend = d_fend;
+    a.hit = d_hit;
+    a.qs = d_qs;
+    a.qe = d_qe;
+    a.seq_off = dt.seq_off;
+    a.cs = dt.cs;
+    a.ce = dt.ce;
+    a.blk_off = d_blk_off;
+    a.words = F.d_words;
+    a.seq = J.s->d_seq;
+    GAMS_TRY(h, who, stage(SQ_PARSE, true));
+    hipLaunchKernelGGL(text_parse_rg_kernel, dim3(nbr), dim3(256), 0, st, a.t, J.chr->t, d_grp, d_qs, d_qe, d_fend);
+    GAMS_TRY(h, who, stage(SQ_PARSE, false));
+    GAMS_TRY(h, who, stage(SQ_LOCATE, true));
+    launch_interval_locate(J.ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
+    GAMS_TRY(h, who, stage(SQ_LOCATE, false));
+    GAMS_TRY(h, who, stage(SQ_LENGTHS, true));
+    hipLaunchKernelGGL(seq_row_len_kernel, dim3(nbr), dim3(256), 0, st, a);
+    GAMS_TRY(h, who, stage(SQ_LENGTHS, false));
+    GAMS_TRY(h, who, stage(SQ_OFFSETS, true));
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbr, d_blk_off,
+                       F.d_words, (uint32_t)W_BYTES);
+    hipLaunchKernelGGL(seq_row_off_kernel, dim3(nbr), dim3(256), 0, st, a);
+    GAMS_TRY(h, who, stage(SQ_OFFSETS, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    const unsigned long long *w = h->pin_scratch;
+    // an error word ends the call here: the copy kernel is never launched over rows the lengths pass refused
+    if (w[W_EID])
+        return gams_fail(h, GAMS_EINVAL, who + ": the range on 0-based line " + std::to_string(w[W_SEQ_LINE]) +
+                                             " is not inside the ctg it is located to (the reference panics, locate.rs:133)");
+    if (w[W_ENOSEQ])
+        return gams_fail(h, GAMS_EINVAL, who + ": a located ctg has no slot of the seqset, or one of another length");
+    const uint64_t tb = w[W_BYTES], rows = w[W_ROWS];
+    if (tb == 0) return GAMS_OK;                               // no located line: nothing to copy, no stages to report
+    if (seq_plan_chunks(tb) > 0x7fffffffull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more text than one launch copies");
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &T->seq_out, &T->seq_out_cap, tb, tb));
+    PoolBlock d_text(h, false);
+    GAMS_TRY(h, who, d_text.alloc(tb));
+    a.text = reinterpret_cast<char *>(d_text.p);
+    a.total = tb;
+    h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the copy reads the sequence bytes
+    const int wrc = gams_seqset_wait_uploads(h, J.s);
+    if (wrc != GAMS_OK) return wrc;
+    GAMS_TRY(h, who, stage(SQ_COPY, true));
+    hipLaunchKernelGGL(seq_copy_kernel, dim3((uint32_t)seq_plan_chunks(tb)), dim3(256), 0, st, a);
+    GAMS_TRY(h, who, stage(SQ_COPY, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(T->seq_out, d_text.p, tb, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    rg_timed(h, SQ_STAGES);
+    *text = T->seq_out;
+    *text_bytes = tb;
+    *n_rows = rows;
+    return GAMS_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1666,5 +1987,16 @@ int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_
                                        do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr},
                           bytes, n_bytes, text, text_bytes, text_off, n_features, n_rows);
 }
+
+int gams_gpu_locate_seq_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                             const uint32_t *ctg_index, const int32_t *chr_start, const int32_t *chr_end, const char *bytes,
+                             uint64_t n_bytes, const char **text, uint64_t *text_bytes, uint64_t *n_rows) {
+    if (!h || !s || !ctg_ix || !chr_names || (ctg_ix->m && (!ctg_index || !chr_start || !chr_end)) || (n_bytes && !bytes) ||
+        !text || !text_bytes || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_locate_seq_text: null argument");
+    return locate_seq_run(h, SeqJob{s, ctg_ix, chr_names, ctg_index, chr_start, chr_end}, bytes, n_bytes, text, text_bytes, n_rows);
+}
+
+uint32_t gams_gpu_locate_seq_chunk(void) { return kSeqTextChunk; }
 
 }  // extern "C"

@@ -152,6 +152,9 @@ def load():
     L.gams_host_peak_text.restype = C.c_void_p
     L.gams_host_peak_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                       C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_locate_seq_text.restype = C.c_void_p
+    L.gams_host_locate_seq_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p,
+                                            C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.gams_host_sw_text.restype = C.c_void_p
     L.gams_host_sw_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                     C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p,
@@ -387,7 +390,7 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 
 def last_operator_device():
-    """1 if the last wave / wave_timed / wave_gz / locate_text / anno_text / peak_text / sw_text / gen_text of this thread made its rows on the device,
+    """1 if the last wave / wave_timed / wave_gz / locate_text / locate_seq_text / anno_text / peak_text / sw_text / gen_text of this thread made its rows on the device,
     0 if it fell back to the host"""
     return int(load().gams_host_last_operator_device())
 
@@ -445,6 +448,28 @@ def locate_seq(eng, ctgs, rgs):
     seq_lines = "\n".join(f"{c['id']}\t{bytes(c['seq']).decode()}" for c in ctgs)
     return _take(load().gams_host_locate_seq(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data,
                                              "\n".join(rgs).encode(), seq_lines.encode()))
+
+
+def locate_seq_text(eng, ctgs, data, seqset=None):
+    """`gams locate --seq` over the bytes of a range file: the FASTA records of the located lines, as bytes, copied on
+    the device out of a seqset (the host's passes where the device refuses; last_operator_device says which).  Without
+    `seqset` the ctgs carry their bases in c["seq"], uploaded for the call; with a resident engine.SeqSet -- what
+    gen_text returns -- its slot i holds ctgs[i] (a ctg dict may name another in c["slot"]; None: no sequence).  The
+    sequence bytes are copied as they are, whatever their values."""
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    out_len = C.c_uint64()
+    if seqset is None:
+        bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
+                                     else c["seq"]) for c in ctgs]
+        seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        p = load().gams_host_locate_seq_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None,
+                                             bytes(data), len(data), C.byref(out_len))
+    else:
+        slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
+        slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
+        p = load().gams_host_locate_seq_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
+                                             slots.ctypes.data, bytes(data), len(data), C.byref(out_len))
+    return _take_bytes(p, out_len)
 
 
 def read_range(eng, ctgs, lines):

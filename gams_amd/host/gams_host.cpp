@@ -1291,6 +1291,7 @@ Locator::Locator(gams_gpu_t *h, const std::vector<Ctg> &ctgs) : h_(h), ctgs_(ctg
     ctgs_ = ordered;  // hit indices refer to this order
     ctg_slot_.clear();
     for (uint32_t i = 0; i < ctgs_.size(); ++i) ctg_slot_[ctgs_[i].id] = i;
+    for (const Ctg &c : ctgs) given_.push_back(ctg_slot_.at(c.id));
     check(h_, gams_index_create(h_, g, off.data(), st.data(), sp.data(), &ctg_ix_));
 }
 
@@ -1561,6 +1562,70 @@ std::string Locator::locate_seq(const std::vector<std::string> &rgs,
         out += ">" + rgs[src[k]] + "\n" + it->second.substr((size_t)from - 1, (size_t)(to - from + 1)) + "\n";
     }
     return out;
+}
+
+std::string Locator::locate_seq_text(const char *bytes, size_t n, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                                     bool *device) {
+    if (device) *device = false;
+    if (!seqset || slots.size() != given_.size()) throw Error(GAMS_EINVAL, "locate_seq_text: one seqset slot per ctg");
+    text_tables();
+    // per interval of the ctg index (ctgs_' order): seqset slot, chr_start, chr_end
+    const size_t n_ctg = ctgs_.size();
+    std::vector<uint32_t> slot(std::max<size_t>(n_ctg, 1), UINT32_MAX);
+    std::vector<int32_t> cs(std::max<size_t>(n_ctg, 1), 0), ce(std::max<size_t>(n_ctg, 1), 0);
+    for (size_t i = 0; i < given_.size(); ++i) slot[given_[i]] = slots[i];
+    for (size_t c = 0; c < n_ctg; ++c) {
+        cs[c] = ctgs_[c].chr_start;
+        ce[c] = ctgs_[c].chr_end;
+    }
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, rows = 0;
+    const int rc = gams_gpu_locate_seq_text(h_, seqset, ctg_ix_, chr_names_, slot.data(), cs.data(), ce.data(), bytes, n, &text,
+                                            &text_bytes, &rows);
+    if (rc != GAMS_EUNSUPPORTED) {
+        check(h_, rc);
+        if (device) *device = true;
+        return std::string(text, (size_t)text_bytes);
+    }
+    // the host's passes: the lines' first fields (locate.rs:89-91) through locate_seq, over the sequences of the ctgs
+    // they are located to, brought back from the seqset
+    std::vector<std::string> rgs = text_lines(bytes, n);
+    std::vector<Range> valid;
+    for (std::string &s : rgs) {
+        const size_t tab = s.find('\t');
+        if (tab != std::string::npos) s.resize(tab);
+        Range r = Range::from_str(s);
+        if (!r.valid) continue;
+        r.strand.clear();
+        valid.push_back(r);
+    }
+    std::map<std::string, std::string> seq_of;
+    // (a slot's length is not the host's to see: any slot fits a buffer of the whole seqset, and the ctg's bases are its head)
+    uint64_t set_bytes = 0;
+    check(h_, gams_seqset_layout(h_, seqset, nullptr, &set_bytes));
+    std::vector<uint8_t> whole;
+    for (const std::string &id : find(valid)) {
+        if (id.empty() || seq_of.count(id)) continue;
+        const uint32_t c = ctg_slot_.at(id);
+        if (slot[c] == UINT32_MAX) continue;                             // locate_seq reports it
+        whole.resize((size_t)set_bytes + 1);
+        check(h_, gams_seqset_download(h_, seqset, slot[c], whole.data(), nullptr));
+        seq_of[id].assign(reinterpret_cast<const char *>(whole.data()), (size_t)((int64_t)ce[c] - cs[c] + 1));
+    }
+    return locate_seq(rgs, seq_of);
+}
+
+std::string Locator::locate_seq_text(const char *bytes, size_t n, const std::vector<const uint8_t *> &seqs, bool *device) {
+    if (seqs.size() != given_.size()) throw Error(GAMS_EINVAL, "locate_seq_text: ctgs / seqs size mismatch");
+    std::vector<uint32_t> lens(std::max<size_t>(given_.size(), 1), 0), slots(given_.size());
+    for (size_t i = 0; i < given_.size(); ++i) {
+        lens[i] = (uint32_t)(ctgs_[given_[i]].chr_end - ctgs_[given_[i]].chr_start + 1);
+        slots[i] = (uint32_t)i;
+    }
+    SeqSetGuard sg{h_};
+    check(h_, gams_seqset_create(h_, (uint32_t)given_.size(), lens.data(), &sg.s));
+    check(h_, gams_seqset_upload_all(h_, sg.s, seqs.data()));
+    return locate_seq_text(bytes, n, sg.s, slots, device);
 }
 
 // ---------------------------------------------------------------------------

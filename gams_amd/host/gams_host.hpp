@@ -197,6 +197,17 @@ public:
     void text_tables();
     // locate --seq (locate.rs:124-134): ">{rg}\n{bases}\n"; seq_of maps ctg id -> gunzipped seq
     std::string locate_seq(const std::vector<std::string> &rgs, const std::map<std::string, std::string> &seq_of);
+    // locate --seq over the bytes of a range file and a resident seqset (a host that has the ctgs from gen_text, or has
+    // just run `wave` from these bases): the text of locate_seq() of the lines' first fields, copied on the device
+    // (gams_gpu_locate_seq_text); the sequence bytes are not interpreted.  slots[i] = the seqset slot that holds the
+    // i-th ctg given to the constructor, UINT32_MAX if none does (a line located to such a ctg is an error).  Where the
+    // device refuses (GAMS_EUNSUPPORTED) the lines are cut at their first tab as locate_text cuts them, the ctgs they
+    // are located to come back through gams_seqset_download and locate_seq() runs (that path checks a slot's index, not
+    // its length, which the host cannot see); *device as in locate_text.
+    std::string locate_seq_text(const char *bytes, size_t n, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                                bool *device = nullptr);
+    // ... seqs[i] = the bases of the i-th ctg given to the constructor: one seqset is built and uploaded for the call
+    std::string locate_seq_text(const char *bytes, size_t n, const std::vector<const uint8_t *> &seqs, bool *device = nullptr);
     const Ctg *ctg(const std::string &id) const;
     friend RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device);
     friend std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
@@ -211,6 +222,7 @@ private:
     std::vector<Ctg> ctgs_;                       // in index order
     std::map<std::string, uint32_t> chr_group_;   // chr -> group of the ctg index
     std::map<std::string, uint32_t> ctg_slot_;    // ctg id -> position in ctgs_
+    std::vector<uint32_t> given_;                 // the i-th ctg given to the constructor -> position in ctgs_
     gams_index_t *ctg_ix_ = nullptr;
     gams_index_t *rg_ix_ = nullptr;
     std::map<std::string, uint32_t> rg_group_;    // ctg id -> group of the rg index

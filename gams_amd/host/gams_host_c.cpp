@@ -545,6 +545,28 @@ char *gams_host_locate_seq(gams_gpu_t *h, uint32_t n, const char *const *ids, co
     });
 }
 
+// locate --seq over the bytes of a range file (bytes, n_bytes: not NUL-terminated; Locator::locate_seq_text): the FASTA
+// records of the located lines, copied on the device.  seqset == NULL: seqs[i] = the bases of ctg i, uploaded for the call;
+// else the resident seqset and slots[i] = its slot of ctg i (UINT32_MAX: none), seqs unused.
+char *gams_host_locate_seq_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                                const int32_t *starts, const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset,
+                                const uint32_t *slots, const char *bytes, uint64_t n_bytes, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        loc.text_tables();
+        bool dev = false;
+        std::string out;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (seqset)
+            out = loc.locate_seq_text(bytes, (size_t)n_bytes, seqset, std::vector<uint32_t>(slots, slots + n), &dev);
+        else
+            out = loc.locate_seq_text(bytes, (size_t)n_bytes, std::vector<const uint8_t *>(seqs, seqs + n), &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        return out;
+    });
+}
+
 // utils.rs:39-67 read_range with the drop-first quirk: rows "ctg_id\trange" in bucket order
 char *gams_host_read_range(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
                            const int32_t *starts, const int32_t *ends, const char *lines) {

@@ -487,6 +487,36 @@ int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_
                              const char **text, uint64_t *text_bytes, uint64_t *text_off,
                              uint64_t *n_features, uint64_t *n_rows);
 
+/* ---- text in, text out: locate --seq (locate.rs:124-134) ---- */
+/* The bytes of ONE range file (lines, refused bytes and the 2^32 - 1 line limit as for gams_gpu_locate_text) -> the bases
+ * of its ranges as FASTA, copied on the device out of a resident seqset.  ctg_ix, chr_names as for gams_gpu_locate_text;
+ * ctg_index, chr_start, chr_end as for gams_gpu_peak_text: per interval of ctg_ix in the caller's order, the slot of s
+ * that holds the ctg's bases (UINT32_MAX: none) and the ctg's place on its chromosome.
+ * rg = the bytes of a line up to its first '\t', parsed like Range::from_str; the strand is not used by the lookup; a
+ * line is located as gams_gpu_locate locates.  Invalid lines, unknown chromosomes and unlocated lines (the point range on
+ * a ctg start among them) print nothing.  Every located line prints ">" rg "\n" bases "\n" (locate.rs:134): rg echoed
+ * byte for byte as it stands in the file, name prefix and strand kept; bases = bytes [start - chr_start, end - chr_start]
+ * of the ctg's slot, copied verbatim -- the sequence bytes are not interpreted, so lower case, N and any byte value,
+ * 0 and >= 0x80 included, pass through (the refused bytes are refused in the input, not in the sequences).  Nothing is
+ * reverse-complemented and nothing is wrapped, as in the reference.
+ * *text (text_bytes bytes, rows in input-line order, no NUL) is page-locked memory owned by the handle, a buffer of this
+ * entry's own, valid until the next call of this entry on the handle; *n_rows counts the records.  Two calls return
+ * identical text.  Zero bytes, or no located line: GAMS_OK, no rows, *text_bytes == 0.
+ * GAMS_EINVAL: null arguments; a located line that does not satisfy chr_start <= start <= end <= chr_end of its ctg (the
+ * reference panics on the slice, locate.rs:133; a range that spans a ctg boundary is located to the ctg in front and
+ * lands here; a reversed range that is located does too) -- the message names the smallest such line, 0-based; a located
+ * ctg with no slot, or with a slot whose length is not chr_end - chr_start + 1 (a ctg no line is located to may have
+ * either).  GAMS_ESTATE: a seqset without the sequence bytes (plane-only).  GAMS_EUNSUPPORTED (nothing is printed; run
+ * the host path): a byte >= 0x80 or a NUL in the input, more than 2^32 - 1 lines.
+ * All byte arithmetic is 64-bit: a row alone may be 2^31 bytes and the text may pass 4 GiB, as far as one device
+ * allocation and one page-locked buffer hold it; no test runs a text beyond 4 GiB.
+ * gams_gpu_last_stage_ms then reports six stages: lines (upload + line index), parse, locate, lengths (row lengths and
+ * the checks), offsets (the per-line offsets), copy (GAMS_ESTATE when no line was located: nothing was copied). */
+int gams_gpu_locate_seq_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                             const uint32_t *ctg_index, const int32_t *chr_start, const int32_t *chr_end,
+                             const char *bytes, uint64_t n_bytes,
+                             const char **text, uint64_t *text_bytes, uint64_t *n_rows);
+
 /* ---- gen: valid regions of a chromosome (first "next" row of SURVEY section 8f) ---- */
 /* gen.rs:86-104: bases other than A C G T a c g t are ambiguous; the valid set is their
  * complement after fill(fill-1) and excise(min_len).  Writes up to `cap` spans (1-based,

@@ -31,10 +31,14 @@ int gams_gpu_last_kernel_ms(gams_gpu_t *h, float *ms);
  * range gc), rows (row lengths and their prefix), write.  After gams_gpu_sw_feature_text, its twelve: the loader's lines ..
  * order, then gather (with the middle check), geometry (rows per feature and their prefix), rows (sw_kernel), text lengths,
  * text write (seven when no line is kept).  After gams_gpu_gen_text (of an input that is not empty), its
- * five: upload, pack (mark, carry, count, offsets, compact), scan, table (the host's part), place.  Writes up to cap values; *n = the stages the call ran
+ * five: upload, pack (mark, carry, count, offsets, compact), scan, table (the host's part), place.  After
+ * gams_gpu_locate_seq_text (with a located line), its six: lines, parse, locate, lengths, offsets, copy.  Writes up to cap values; *n = the stages the call ran
  * (gams_gpu_last_kernel_ms is their sum).  GAMS_ESTATE when the last timed call was none of these (or its input had
  * no line; for the peak entry: no kept peak). */
 int gams_gpu_last_stage_ms(gams_gpu_t *h, float *ms, uint32_t cap, uint32_t *n);
+/* The chunk of gams_gpu_locate_seq_text's copy: the bytes of text one workgroup writes, a power of two and a multiple of
+ * 16 (kSeqTextChunk, seq_text_plan.hpp).  Tests place rows on the seams between chunks with it. */
+uint32_t gams_gpu_locate_seq_chunk(void);
 
 /* Tapered launches.  A launch of the headline parameters (size 100, step 10, lag 100) over at least a
  * round and a half of workgroups ends in smaller tiles (the ctgs holding the last 17 % / 8 % of the
