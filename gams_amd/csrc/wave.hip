@@ -332,22 +332,18 @@ void wave_fill_tiles(gams_wave_plan_t *p) {
 
 // Tapered tile table for the baked W = 12 kernel: the ctgs holding the last windows of the batch are
 // cut into W = 4 tiles, the ones before them into W = 8 tiles (see wave_fast_taper_kernel).  The two
-// tails are a quarter / half a round of workgroup slots, and at most 8 % / 17 % of the batch.
+// tails are a quarter / half a round of workgroup slots, and at most 8 % / 17 % of the batch: the arithmetic is
+// wave_taper_tails / wave_taper_width of wave_select.hpp (plain C++, pinned on the CPU).
 void wave_fill_tiles_tapered(gams_wave_plan_t *p, uint32_t slots) {
-    const gams_wave_params_t &q = p->prm;
-    const uint32_t tw12 = 256u * 12u - q.lag - 1u, tw8 = 256u * 8u - q.lag - 1u, tw4 = 256u * 4u - q.lag - 1u;
     const uint64_t T = p->total_windows;
-    // % of a round of workgroup slots for the W = 4 / W = 8 tails (defaults from gpurun_out/r2_taper_sweep.log:
-    // 384 Mb 71.6 us without tails, 70.0 at 50/50, 68.5 at 25/50, 70.9 at 100/100; the 120-Mb launch 28.4-28.7 for all)
-    const int k4 = p->taper4_pct, k8 = p->taper8_pct;                       // gams_wave_plan_set_taper_shape (0..100)
-    const uint64_t x4 = std::min<uint64_t>((uint64_t)slots * k4 / 100 * tw4, T * 8 / 100);
-    const uint64_t y8 = std::min<uint64_t>((uint64_t)slots * k8 / 100 * tw8, T * 17 / 100);
+    // gams_wave_plan_set_taper_shape (0..100)
+    const WaveTaper t = wave_taper_tails(T, slots, p->prm.lag, p->taper4_pct, p->taper8_pct);
     p->tiles.clear();
     for (uint32_t c = 0; c < p->set->n_ctg; ++c) {
         const uint32_t n = p->ctgs[c].n_win;
         const uint64_t after = T - p->ctgs[c].win_base;           // windows from this ctg's first to the end of the batch
-        const uint32_t w_kind = after <= x4 ? 4u : after <= x4 + y8 ? 8u : 12u;
-        const uint32_t tw = w_kind == 4u ? tw4 : w_kind == 8u ? tw8 : tw12;
+        const uint32_t w_kind = wave_taper_width(t, after);
+        const uint32_t tw = wave_taper_tile_windows(t, w_kind);
         for (uint32_t w = 0; w < n; w += tw)
             p->tiles.push_back(WaveTile{c, w, n, w_kind, p->ctgs[c].seq_off, p->ctgs[c].win_base});
     }
@@ -1223,6 +1219,20 @@ int gams_wave_plan_set_taper_shape(gams_gpu_t *h, gams_wave_plan_t *p, int pct4,
     p->taper4_pct = pct4;
     p->taper8_pct = pct8;
     return wave_retile(h, p, p->tw_req);
+}
+
+int gams_wave_plan_tiles(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t *out, uint64_t cap, uint64_t *n) {
+    if (!h || !p || !n || (cap && !out)) return gams_fail(h, GAMS_EINVAL, "wave_plan_tiles: null argument");
+    // the host's copy of the table the tile kernel reads: no device work
+    *n = p->tiles.size();
+    const uint64_t m = std::min<uint64_t>(cap, p->tiles.size());
+    for (uint64_t i = 0; i < m; ++i) {
+        const WaveTile &t = p->tiles[i];
+        out[3 * i] = t.ctg;
+        out[3 * i + 1] = t.w0;
+        out[3 * i + 2] = t.pad;                    // W of a tapered table's tile, 0 in every other table
+    }
+    return GAMS_OK;
 }
 
 int gams_wave_plan_set_queue_threads(gams_gpu_t *h, gams_wave_plan_t *p, uint32_t n) {

@@ -85,6 +85,36 @@ struct WaveSelection {
 // a round of workgroup slots: what the taper's threshold and the size of its tails are counted in
 inline uint32_t wave_slots(int cus) { return 8u * (uint32_t)std::max(cus, 1); }
 
+// The tapered tile table of the baked W = 12 kernel (wave_fast_taper_kernel): the ctgs holding the last windows of the
+// batch are cut into W = 4 tiles, the ones before them into W = 8 tiles.  The two tails are pct4 / pct8 % of a round of
+// workgroup slots (whole slots, a tile of that width each) and at most 8 % / 17 % of the batch.
+// tests/test_wave_taper_cpu.py holds this arithmetic against the model of tests/taper.py.
+struct WaveTaper {
+    uint32_t tw4 = 0, tw8 = 0, tw12 = 0;   // windows of a W = 4 / 8 / 12 tile: 256 * W - lag - 1
+    uint64_t x4 = 0, y8 = 0;               // windows of the W = 4 tail, and of the W = 8 tail in front of it
+};
+
+// % of a round of workgroup slots for the W = 4 / W = 8 tails (defaults 25 / 50 from profiles/r02_taper_sweep.txt:
+// 384 Mb 71.6 us without tails, 70.0 at 50/50, 68.5 at 25/50, 70.9 at 100/100; the 120-Mb launch 28.4-28.7 for all)
+inline WaveTaper wave_taper_tails(uint64_t total_windows, uint32_t slots, uint32_t lag, int pct4, int pct8) {
+    WaveTaper t;
+    t.tw12 = 256u * 12u - lag - 1u;
+    t.tw8 = 256u * 8u - lag - 1u;
+    t.tw4 = 256u * 4u - lag - 1u;
+    const uint64_t T = total_windows;
+    t.x4 = std::min<uint64_t>((uint64_t)slots * (uint64_t)pct4 / 100 * t.tw4, T * 8 / 100);
+    t.y8 = std::min<uint64_t>((uint64_t)slots * (uint64_t)pct8 / 100 * t.tw8, T * 17 / 100);
+    return t;
+}
+
+// the tile width of a ctg: `after` = the windows from its first window to the end of the batch
+inline uint32_t wave_taper_width(const WaveTaper &t, uint64_t after) {
+    return after <= t.x4 ? 4u : after <= t.x4 + t.y8 ? 8u : 12u;
+}
+inline uint32_t wave_taper_tile_windows(const WaveTaper &t, uint32_t w_kind) {
+    return w_kind == 4u ? t.tw4 : w_kind == 8u ? t.tw8 : t.tw12;
+}
+
 inline size_t wave_lds_bytes(uint32_t max_chunks, uint32_t max_win, bool wide, bool k16) {
     size_t b = 0;
     const size_t mwp = (max_win + 3u) & ~1u;

@@ -310,6 +310,16 @@ class WavePlan:
             pct4, pct8 = divmod(int(pct4), 1000)
         self.eng.check(self.eng.lib.gams_wave_plan_set_taper_shape(self.eng.h, self.p, pct4, pct8))
 
+    def tiles(self):
+        """the plan's tile table, one row (ctg, first window, W) per tile; W is 0 unless the table is tapered
+        (gams_wave_plan_tiles: a copy of the host's table, no device work)"""
+        n = C.c_uint64()
+        self.eng.check(self.eng.lib.gams_wave_plan_tiles(self.eng.h, self.p, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 3), np.uint32)
+        if n.value:
+            self.eng.check(self.eng.lib.gams_wave_plan_tiles(self.eng.h, self.p, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
     def set_queue_threads(self, n):
         """host threads run_n queues a long batch of passes from (1..4)"""
         self.eng.check(self.eng.lib.gams_wave_plan_set_queue_threads(self.eng.h, self.p, n))

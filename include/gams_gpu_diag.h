@@ -51,6 +51,12 @@ int gams_wave_plan_set_taper(gams_gpu_t *h, gams_wave_plan_t *plan, int mode);
  * holding the last pct4 % of a round are cut into the smallest tiles, the pct8 % before them into the
  * middle ones; at most 8 % / 17 % of the batch.  0..100, default 25 / 50 (profiles/r02_taper_sweep.txt). */
 int gams_wave_plan_set_taper_shape(gams_gpu_t *h, gams_wave_plan_t *plan, int pct4, int pct8);
+/* The plan's tile table as the tile kernel reads it, for tests: three words per tile -- the ctg, the tile's first
+ * window in it, and W (4, 8 or 12 windows per thread: a tile of 256 * W - lag - 1 windows) for a tapered table, 0
+ * for every other table.  *n = the tiles of the table; the first min(cap, *n) tiles are written to out, which holds
+ * room for cap of them (cap 0, out NULL: only the count).  Copied from the host's table, no device work; follows
+ * the plan's current settings like gams_wave_plan_kernel_name. */
+int gams_wave_plan_tiles(gams_gpu_t *h, gams_wave_plan_t *plan, uint32_t *out, uint64_t cap, uint64_t *n);
 /* Host threads gams_wave_run_n queues a long batch of passes from (1..4, default one per way). */
 int gams_wave_plan_set_queue_threads(gams_gpu_t *h, gams_wave_plan_t *plan, uint32_t n);
 /* Name of the kernel that does the plan's work, spelled as rocprofv3 --kernel-trace prints the

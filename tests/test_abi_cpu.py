@@ -34,7 +34,7 @@ def test_binding_surface_carries_no_lab_bench():
     diag = set(declared_functions(("gams_gpu_diag.h",)))
     assert not (main & diag)
     for name in ("gams_wave_plan_set_stamps", "gams_wave_stamps", "gams_wave_stamps_raw", "gams_wave_plan_set_guard",
-                 "gams_wave_plan_set_taper", "gams_wave_plan_set_tile", "gams_wave_plan_kernel_name",
+                 "gams_wave_plan_set_taper", "gams_wave_plan_set_tile", "gams_wave_plan_kernel_name", "gams_wave_plan_tiles",
                  "gams_gpu_timer_start", "gams_gpu_timer_stop", "gams_gpu_last_kernel_ms", "gams_wave_exact_count"):
         assert name in diag and name not in main, name
     for src in ("api.hip", "wave.hip", "sw.hip", "interval.hip", "gen.hip", "wave_kernels.hpp", "common.hpp",

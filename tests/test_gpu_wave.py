@@ -324,6 +324,51 @@ def test_run_n_equals_repeated_run(eng, s288c, depth, n):
     ss.close()
 
 
+@pytest.fixture(scope="module")
+def genome12(eng):
+    """an S288c-sized synthetic genome (12 Mb, 1.2 M windows) resident, and the oracle's peaks over it"""
+    from gams_amd import synth as gsynth
+
+    ctgs = gsynth.genome_ctgs(gsynth.S288C_LENGTHS, 500000)
+    ss = engine.SeqSet(eng, [c["seq"] for c in ctgs])
+    exp = []
+    for c, ctg in enumerate(ctgs):
+        cnt, _, sig = ora.wave_windows(ctg["seq"], 100, 10, 100, 3.0, 1.0)
+        idx = np.flatnonzero(sig)
+        rec = np.zeros(idx.size, _lib.PEAK_DTYPE)
+        rec["ctg"], rec["window"], rec["gc_count"], rec["signal"] = c, idx, cnt[idx], sig[idx]
+        exp.append(rec)
+    yield ss, np.concatenate(exp)
+    ss.close()
+
+
+@pytest.mark.parametrize("threads", [1, 2, 3, 4])
+@pytest.mark.parametrize("depth", [3, 4])
+def test_run_n_from_every_number_of_queueing_threads(eng, genome12, depth, threads):
+    """gams_wave_plan_set_queue_threads: the ways of a batch shared among 1 .. 4 host threads -- fewer than, as many as
+    and more than the plan has ways (the share is capped by the depth) -- for batches of exactly the threaded minimum
+    (4 * depth), one more, and a long one: every held pass gives the oracle's peaks and the exact count of a single
+    gams_wave_run at that depth."""
+    ss, exp = genome12
+    plan = engine.WavePlan(eng, ss, flags=_lib.WAVE_PEAKS)
+    plan.set_depth(depth)
+    plan.run()
+    assert np.array_equal(plan.peaks(), exp)
+    ref_exact = plan.exact_count()
+    for bad in (0, 5):
+        with pytest.raises(_lib.GamsError) as ei:
+            plan.set_queue_threads(bad)
+        assert ei.value.code == _lib.EINVAL
+    plan.set_queue_threads(threads)
+    for n in (4 * depth, 4 * depth + 1, 101):
+        plan.run_n(n)
+        for age in range(depth):
+            plan.select(age)
+            assert np.array_equal(plan.peaks(), exp), (n, age)
+            assert plan.exact_count() == ref_exact, (n, age)
+    plan.close()
+
+
 @pytest.mark.parametrize("prm", [(100, 10, 100, 3.0), (100, 1, 100, 3.0), (50, 7, 33, 2.0), (255, 8, 60, 1.0)])
 @pytest.mark.parametrize("tile", [1024, 2048, 3072, 5120, 7168])
 def test_every_fast_tile_size_matches_the_oracle(eng, s288c, prm, tile):

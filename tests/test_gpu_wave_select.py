@@ -1,6 +1,7 @@
 """Every kernel pointer of wave.hip's instance table launched once, through the recipes of wave_instances.py: the NT =
 false half on a small ragged seqset, the NT = true half on a seqset just over 64 MiB (that threshold itself).  The name
-is asserted, one pass is run and compared with the CPU oracle.  (wave_fast_taper_kernel: test_gpu_fullsize.py.)"""
+is asserted, one pass is run and compared with the CPU oracle.  (wave_fast_taper_kernel needs at least
+12 * cus * 2,971 windows: test_gpu_wave_taper.py holds it, over the world of tests/taper.py.)"""
 import numpy as np
 import pytest
 

@@ -4,8 +4,12 @@
 //                                size step lag flags serial repair depth total_windows tw_req nth_req taper_req cus set_bytes
 //                              prints per case, tab-separated:
 //                                kernel nth tw max_win max_chunks lds_bytes taper direct
+//   wave_select_main taper     reads batches from stdin (tests/test_wave_taper_cpu.py), one per line:
+//                                cus pct4 pct8 lag n_ctg  then the n_ctg window counts of the batch's ctgs
+//                              prints per batch one line: the two tail sizes x4 y8, then per ctg its tile width and tiles
 #include <cstring>
 #include <iostream>
+#include <vector>
 
 #include "../gams_amd/csrc/wave_select.hpp"
 
@@ -17,6 +21,28 @@ int main(int argc, char **argv) {
         for (s.entry = 0; s.entry < kWaveFastCount; ++s.entry) {
             wave_selection_name(s, name, sizeof name);
             std::printf("%s\n", name);
+        }
+        return 0;
+    }
+    if (argc > 1 && std::strcmp(argv[1], "taper") == 0) {
+        long long cus, pct4, pct8, lag, n;
+        while (std::cin >> cus >> pct4 >> pct8 >> lag >> n) {
+            std::vector<unsigned long long> win((size_t)n);
+            unsigned long long total = 0;
+            for (auto &w : win) {
+                std::cin >> w;
+                total += w;
+            }
+            const WaveTaper t = wave_taper_tails(total, wave_slots((int)cus), (uint32_t)lag, (int)pct4, (int)pct8);
+            std::printf("%llu %llu", (unsigned long long)t.x4, (unsigned long long)t.y8);
+            unsigned long long base = 0;
+            for (unsigned long long w : win) {
+                const uint32_t kind = wave_taper_width(t, total - base);
+                const uint32_t tw = wave_taper_tile_windows(t, kind);
+                std::printf(" %u %llu", kind, (w + tw - 1) / tw);
+                base += w;
+            }
+            std::printf("\n");
         }
         return 0;
     }
