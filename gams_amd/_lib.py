@@ -18,6 +18,8 @@ WAVE_BODY_AUTO, WAVE_BODY_WIDE, WAVE_BODY_NARROW = 0, 1, 2      # gams_wave_plan
 WAVE_CUT_AUTO, WAVE_CUT_TWO_WAVES, WAVE_CUT_ONE_WAVE = 0, 1, 2  # gams_wave_plan_set_cut / _last_cut
 GC_BODY_AUTO, GC_BODY_PORTABLE, GC_BODY_AVX2 = 0, 1, 2          # gams_gc_plane_with
 SW_GC, SW_COUNT = 1, 2          # GAMS_SW_GC / GAMS_SW_COUNT: the action set of gams_gpu_sw_text_actions
+LOADER_RG, LOADER_FEATURE = 0, 1                      # gams_gpu_loader_text: kind
+LOADER_RECORDS, LOADER_TSV, LOADER_RESP = 0, 1, 2     # ... and format
 
 
 class GamsError(RuntimeError):
@@ -136,6 +138,9 @@ PROTOTYPES = {
     "gams_gpu_read_range_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _VP, _VP, _VP, _VP, _VP, C.c_uint64,
                                            C.POINTER(C.c_uint64)]),
     "gams_index_create_range_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint64, _PP, _VP, C.POINTER(C.c_uint64)]),
+    "gams_index_create_range_files": (C.c_int, [_VP, _VP, _VP, C.c_uint32, _VP, _VP, _PP, _VP, C.POINTER(C.c_uint64)]),
+    "gams_gpu_loader_text": (C.c_int, [_VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, C.c_int, C.c_char_p, C.c_uint64, C.c_int, _VP,
+                                       _PP, C.POINTER(C.c_uint64), _VP, _VP, _VP, C.POINTER(C.c_uint64)]),
     "gams_gpu_peak_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64), _VP,
                                      C.POINTER(C.c_uint64)]),
     "gams_gpu_sw_feature_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int32, C.c_int32,

@@ -13,6 +13,9 @@
 //   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
 // and `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
 //   gams_gpu_sw_feature_text       the bytes of one range file -> the sw rows of its features (stages 2-5 in sw.hip)
+// and several files in one load (rg.rs:40, feature.rs:47: one read_range per file), on rg_load_in:
+//   gams_index_create_range_files  the rg index of `gams rg f1 f2 ...`
+//   gams_gpu_loader_text           the records `gams rg` / `gams feature` SET, as "{id}\t{json}" rows, TSV or RESP
 // and `locate --seq` (locate.rs:124-134), behind the front of locate_text, with a writer of its own (a row may be a whole ctg):
 //   gams_gpu_locate_seq_text       the bytes of one range file -> ">{rg}\n{bases}\n" of every located line
 //
@@ -68,10 +71,12 @@ struct gams_names {
 struct gams_text_state {
     uint8_t *d_in = nullptr;
     size_t d_in_cap = 0;
-    char *out[4] = {};          // locate, count, anno, peak
+    char *out[4] = {};          // locate, count, anno, peak (the records of the loaders: rec_out)
     size_t out_cap[4] = {};
     char *seq_out = nullptr;    // locate --seq: a buffer of its own (a text of whole ctgs would be held by the others for good)
     size_t seq_out_cap = 0;
+    char *rec_out = nullptr;    // the loader's records (gams_gpu_loader_text)
+    size_t rec_out_cap = 0;
 };
 
 void gams_text_free(gams_gpu_t *h) {
@@ -80,6 +85,7 @@ void gams_text_free(gams_gpu_t *h) {
     gams_pool_free(h, false, t->d_in, t->d_in_cap);
     for (int k = 0; k < 4; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
     gams_pool_free(h, true, t->seq_out, t->seq_out_cap);
+    gams_pool_free(h, true, t->rec_out, t->rec_out_cap);
     delete t;
     h->text = nullptr;
 }
@@ -512,9 +518,23 @@ const char *const kEntry[3] = {"gpu_locate_text", "gpu_count_text", "gpu_anno_te
 // What steps 1 and 2 (pass 1) of every text entry leave behind: the input in the handle's cached device buffer, the
 // words, the '\n' count of every index block with its prefix, and the line count.  s0 is the pooled block behind the
 // three small arrays.
+// several input files of one load (the rg / feature loaders): n files, file f = bytes[f][0 .. n_bytes[f])
+struct TextFiles {
+    uint32_t n;
+    const char *const *bytes;
+    const uint64_t *n_bytes;
+};
+
 struct TextFront {
     explicit TextFront(gams_gpu_t *h) : s0(h, false) {}
     PoolBlock s0;
+    // set by the caller in front of text_front: the input is these files, uploaded back to back with a '\n' put behind
+    // a file that lacks its last one and has a file behind it, so that no line runs across a seam and the line numbers
+    // of the buffer rise with (file, line).  (The '\r' such a line keeps in the reference is dropped with the '\n' here;
+    // Range::from_str trims it either way.)  text_front leaves where every file begins, and the end, in file_off.
+    const TextFiles *files = nullptr;
+    std::vector<uint64_t> file_off;
+    uint64_t n_in = 0;       // bytes of the input as uploaded
     unsigned long long *d_words = nullptr;
     uint32_t *d_bnl = nullptr;
     unsigned long long *d_bnloff = nullptr;
@@ -526,6 +546,26 @@ struct TextFront {
 int text_front(gams_gpu_t *h, const std::string &who, const char *bytes, uint64_t n_bytes, TextFront &F) {
     if (!h->text) h->text = new gams_text_state();
     gams_text_state *T = h->text;
+    bool last_nl = n_bytes && bytes[n_bytes - 1] == '\n';
+    if (F.files) {
+        const TextFiles &S = *F.files;
+        F.file_off.assign((size_t)S.n + 1, 0);
+        uint64_t at = 0;
+        for (uint32_t f = 0; f < S.n; ++f) {
+            F.file_off[f] = at;
+            const uint64_t nb = S.n_bytes[f];
+            if (nb == 0) continue;
+            at += nb;
+            last_nl = S.bytes[f][nb - 1] == '\n';
+            if (!last_nl && f + 1u < S.n) {
+                ++at;
+                last_nl = true;
+            }
+        }
+        F.file_off[S.n] = at;
+        n_bytes = at;
+    }
+    F.n_in = n_bytes;
     const uint64_t n16 = (n_bytes + 15u) & ~15ull;
     F.n16 = n16;
     // 1. upload into the cached buffer; the 16-B tail is spaces (no '\n', nothing refused)
@@ -546,7 +586,15 @@ int text_front(gams_gpu_t *h, const std::string &who, const char *bytes, uint64_
     h->k_valid = false;
     h->kq_used = 0;
     GAMS_TRY(h, who, hipMemsetAsync(d_words, 0, W_COUNT * 8, st));
-    if (n_bytes) GAMS_TRY(h, who, hipMemcpyAsync(T->d_in, bytes, n_bytes, hipMemcpyHostToDevice, st));
+    if (F.files) {
+        for (uint32_t f = 0; f < F.files->n; ++f) {
+            const uint64_t nb = F.files->n_bytes[f], at = F.file_off[f];
+            if (nb) GAMS_TRY(h, who, hipMemcpyAsync(T->d_in + at, F.files->bytes[f], nb, hipMemcpyHostToDevice, st));
+            if (F.file_off[f + 1] - at > nb) GAMS_TRY(h, who, hipMemsetAsync(T->d_in + at + nb, '\n', 1, st));
+        }
+    } else if (n_bytes) {
+        GAMS_TRY(h, who, hipMemcpyAsync(T->d_in, bytes, n_bytes, hipMemcpyHostToDevice, st));
+    }
     GAMS_TRY(h, who, hipMemsetAsync(T->d_in + n_bytes, ' ', n_pad - n_bytes, st));
     // 2. line index, pass 1
     hipLaunchKernelGGL(text_nl_count_kernel, dim3(nbi), dim3(256), 0, st, T->d_in, n16, F.d_bnl, d_words);
@@ -557,7 +605,7 @@ int text_front(gams_gpu_t *h, const std::string &who, const char *bytes, uint64_
     F.nl = h->pin_scratch[W_NL];
     if (h->pin_scratch[W_BAD])
         return gams_fail(h, GAMS_EUNSUPPORTED, who + ": the input holds a byte >= 0x80 or a NUL (use the host path)");
-    const uint64_t L64 = n_bytes == 0 ? 0 : F.nl + (bytes[n_bytes - 1] != '\n' ? 1u : 0u);
+    const uint64_t L64 = n_bytes == 0 ? 0 : F.nl + (last_nl ? 0u : 1u);
     if (L64 > 0xffffffffull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 1 lines");
     F.L = (uint32_t)L64;
     return GAMS_OK;
@@ -744,6 +792,75 @@ __global__ __launch_bounds__(256) void rg_keep_kernel(uint32_t n_lines, uint32_t
                  ((unsigned long long)(qs && keep ? qs[i] : 0u) << line_bits) | i;
 }
 
+// ---- several files in one load (rg.rs:40, feature.rs:47: one read_range per file) ----
+// The files lie back to back in the input buffer (TextFront::files), every file beginning at a line start, so the line
+// numbers of the buffer rise with (file, line).  line0[f] = the first line of file f (n_files + 1 entries, the last one
+// the line count): the position of the file's first byte among the line starts.  A line's file is the last one whose first
+// line is not behind it (an empty file shares its first line with the next one and is never that).  Drop-first is per
+// file: first[] is keyed by file * n_ctg + ctg, and a run of equal ctgs ends where the file changes.  The bucket a kept
+// line is counted and sorted into is (file, ctg) for the records and the ctg alone for the index.
+struct RgFileTab {
+    const uint32_t *line0;
+    uint32_t n_files, n_ctg;
+};
+
+__global__ __launch_bounds__(256) void rg_file_lines_kernel(const unsigned long long *starts, uint64_t nl,
+                                                            const unsigned long long *file_off, uint32_t n_files, uint32_t *line0) {
+    const uint32_t f = blockIdx.x * 256u + threadIdx.x;
+    if (f > n_files) return;
+    const unsigned long long at = file_off[f];
+    uint64_t lo = 0, hi = nl + 2u;                    // lower bound over starts[0, nl + 2); starts[nl + 1] = n + 1 > at
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (starts[mid] < at)
+            lo = mid + 1u;
+        else
+            hi = mid;
+    }
+    line0[f] = (uint32_t)lo;
+}
+
+__device__ __forceinline__ uint32_t rg_file_of(const RgFileTab &F, uint32_t i) {
+    uint32_t lo = 0, hi = F.n_files;                  // line0[0] = 0 <= i
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (F.line0[mid] <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void rg_first_files_kernel(uint32_t n_lines, const int64_t *hit, const RgFileTab F, uint32_t *first) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const int64_t c = i < n_lines ? hit[i] : -1;
+    const int64_t b = c >= 0 ? (int64_t)rg_file_of(F, i) * F.n_ctg + c : -1;
+    if (run_leader(b) && b >= 0) atomicMin(first + b, i);
+}
+
+// rg_keep_kernel with the runs and first[] by (file, ctg); by_file: so are count[] and the key's bucket, else the ctg is
+__global__ __launch_bounds__(256) void rg_keep_files_kernel(uint32_t n_lines, uint32_t n_bkt, uint32_t line_bits, const int64_t *hit,
+                                                            const RgFileTab F, uint32_t by_file, const uint32_t *first,
+                                                            uint32_t *count, unsigned long long *key) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t c = i < n_lines ? hit[i] : -1;
+    const int64_t b = c >= 0 ? (int64_t)rg_file_of(F, i) * F.n_ctg + c : -1;
+    const bool keep = b >= 0 && first[b] != i;
+    const bool lead = run_leader(b);
+    const unsigned long long kept = __ballot(keep), leads = __ballot(lead);
+    const uint32_t bucket = by_file ? (uint32_t)b : (uint32_t)c;
+    if (lead && b >= 0) {
+        const unsigned long long above = lane == 63u ? 0ull : leads & (~0ull << (lane + 1u));
+        const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
+        const unsigned long long run = (end == 64u ? ~0ull : (1ull << end) - 1ull) & (~0ull << lane);
+        const uint32_t n = (uint32_t)__popcll(kept & run);
+        if (n) atomicAdd(count + bucket, n);
+    }
+    if (i < n_lines) key[i] = ((unsigned long long)(keep ? bucket : n_bkt) << line_bits) | i;
+}
+
 struct RgGather {
     const unsigned long long *key;       // sorted: the first n_kept are the kept lines in (ctg, line) order
     unsigned long long line_mask;
@@ -770,8 +887,16 @@ __global__ __launch_bounds__(256) void rg_gather_kernel(const RgGather a) {
 // what the loader hands its consumer while the scratch is alive
 struct RgCols {
     uint64_t n_ctg, n_kept;
-    const unsigned long long *bucket_off;   // host, n_ctg + 1
-    const uint32_t *first;                  // host, n_ctg: UINT32_MAX = no located line
+    // a load of one file: one bucket and one entry of first[] per ctg.  Of several files (rg_load_in): first[] has one
+    // entry per (file, ctg), file-major, and the buckets are the (file, ctg) pairs or the ctgs (RgInput::by_file)
+    uint64_t n_files, n_bkt, n_first;
+    const unsigned long long *bucket_off;   // host, n_bkt + 1
+    const uint32_t *first;                  // host, n_first: UINT32_MAX = no located line
+    bool seen(uint64_t ctg) const {         // a located line in any file
+        for (uint64_t f = 0; f < n_files; ++f)
+            if (first[f * n_ctg + ctg] != UINT32_MAX) return true;
+        return false;
+    }
     RgGather g;                             // key, line_mask, qs, qe, n_kept, bucket_off (device) filled; n_kept == 0: nothing on the device
     TextLines t;                            // the line index (device), with lines
     unsigned long long *words;              // device: the W_* words of the call
@@ -801,44 +926,71 @@ struct RgPlain {
 // consume(cols, stage) -- stage(k, open) records the stopwatch event that opens or closes stage k -- which queues the
 // gather and whatever follows.  One host wait of its own besides text_front's, behind the offsets.  `who` names the entry
 // in error messages.
+// The input of a load: the bytes of one file, or `files` (then bytes / n_bytes are not looked at).  One file given as
+// `files` is loaded exactly as the bytes of one file are, and no file as zero bytes.  Several files are loaded as the
+// reference loads them one after another (RgFileTab, above): by_file says what the buckets are.  Refused beyond
+// kRgMaxFileCtg (file, ctg) pairs, the size of the tables by them.
+struct RgInput {
+    const char *bytes;
+    uint64_t n_bytes;
+    const TextFiles *files;
+    bool by_file;
+};
+constexpr uint64_t kRgMaxFileCtg = 1ull << 24;
+
 template <typename Spec, typename Consume>
-int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, const char *bytes, uint64_t n_bytes,
-            bool order, Consume consume) {
+int rg_load_in(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, RgInput in, bool order,
+               Consume consume) {
+    if (in.files && in.files->n <= 1u) {
+        in.bytes = in.files->n ? in.files->bytes[0] : nullptr;
+        in.n_bytes = in.files->n ? in.files->n_bytes[0] : 0;
+        in.files = nullptr;
+    }
+    const bool multi = in.files != nullptr;
+    const uint64_t n_files = multi ? in.files->n : 1;
+    if (multi && spec.mid_bits) return gams_fail(h, GAMS_EINVAL, who + ": several files with a middle key field");
+    if (multi && n_files * ctg_ix->m > kRgMaxFileCtg)
+        return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^24 (file, ctg) pairs (use the host path)");
     GAMS_HIP(h, hipSetDevice(h->device));
     GAMS_HIP(h, gams_stopwatch_reserve(h, RG_STAGES));
     hipStream_t st = h->compute;
     const StageClock stage{h, st};
     PoolBlock s1(h, false);
     TextFront F(h);
+    F.files = in.files;
     GAMS_TRY(h, who, stage(RG_LINES, true));
-    const int rc_front = text_front(h, who, bytes, n_bytes, F);
+    const int rc_front = text_front(h, who, in.bytes, in.n_bytes, F);
     if (rc_front != GAMS_OK) return rc_front;
-    const uint64_t n_ctg = ctg_ix->m;
+    const uint64_t n_ctg = ctg_ix->m, n_first = n_files * n_ctg, n_bkt = multi && in.by_file ? n_first : n_ctg;
     const uint32_t L = F.L;
     // the host's copy of bucket_off and first: page-locked, from the pool (a copy into the block may still be queued
     // when a step fails: the block waits for the stream like the others)
     PoolBlock pin(h, true);
-    unsigned long long *h_off = nullptr;
+    unsigned long long *h_off = nullptr, *h_foff = nullptr;
     uint32_t *h_first = nullptr;
     auto host_cols = [&](Carver &c) {
-        h_off = c.take<unsigned long long>(n_ctg + 1);
-        h_first = c.take_tight<uint32_t>(std::max<uint64_t>(n_ctg, 1));
+        h_off = c.take<unsigned long long>(n_bkt + 1);
+        h_foff = c.take<unsigned long long>(multi ? n_files + 1 : 0);
+        h_first = c.take_tight<uint32_t>(std::max<uint64_t>(n_first, 1));
     };
     GAMS_TRY(h, who, pin.alloc(layout_bytes(host_cols)));
     carve(pin.p, host_cols);
     RgCols C{};
     C.n_ctg = n_ctg;
+    C.n_files = n_files;
+    C.n_bkt = n_bkt;
+    C.n_first = n_first;
     C.bucket_off = h_off;
     C.first = h_first;
     if (L == 0) {
-        memset(h_off, 0, (n_ctg + 1) * 8);
-        memset(h_first, 0xff, n_ctg * 4);
+        memset(h_off, 0, (n_bkt + 1) * 8);
+        memset(h_first, 0xff, n_first * 4);
         GAMS_TRY(h, who, stage(RG_LINES, false));
         return consume(C, stage);
     }
     uint32_t line_bits = 1, ctg_bits = 1;
     while (line_bits < 32u && (L - 1u) >> line_bits) ++line_bits;
-    while (ctg_bits < 32u && n_ctg >> ctg_bits) ++ctg_bits;
+    while (ctg_bits < 32u && n_bkt >> ctg_bits) ++ctg_bits;
     const uint32_t key_bits = ctg_bits + spec.mid_bits + line_bits;      // (at most 64 without a middle field)
     if (key_bits > 64u)
         return gams_fail(h, GAMS_EUNSUPPORTED, who + ": (ctg, start, line) does not fit a 64-bit sort key (use the host path)");
@@ -846,9 +998,9 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, S
     size_t sort_bytes = 0;
     GAMS_TRY(h, who, rocprim::radix_sort_keys(nullptr, sort_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                               (size_t)L, 0u, key_bits, st));
-    const size_t n_tab = std::max<uint64_t>(n_ctg, 1), b_tab = gams_align256(n_tab * 4);
-    unsigned long long *d_starts = nullptr, *d_key = nullptr, *d_key2 = nullptr, *d_off = nullptr;
-    uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr, *d_first = nullptr, *d_count = nullptr;
+    const size_t n_tab = std::max<uint64_t>(n_bkt, 1), n_ftab = std::max<uint64_t>(n_first, 1);
+    unsigned long long *d_starts = nullptr, *d_key = nullptr, *d_key2 = nullptr, *d_off = nullptr, *d_foff = nullptr;
+    uint32_t *d_grp = nullptr, *d_qs = nullptr, *d_qe = nullptr, *d_first = nullptr, *d_count = nullptr, *d_line0 = nullptr;
     int64_t *d_hit = nullptr;
     uint8_t *d_sort = nullptr;
     auto cols = [&](Carver &c) {   // starts | grp qs qe | hit key key' | the spec's | first count | bucket_off | sort storage
@@ -860,17 +1012,26 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, S
         d_key = c.take<unsigned long long>(L);
         d_key2 = c.take<unsigned long long>(L);
         spec.cols(c, L);
-        d_first = c.take<uint32_t>(n_tab);
+        d_first = c.take<uint32_t>(n_ftab);
         d_count = c.take<uint32_t>(n_tab);
-        d_off = c.take<unsigned long long>(n_ctg + 1);
+        d_off = c.take<unsigned long long>(n_bkt + 1);
         d_sort = c.take<uint8_t>(std::max<size_t>(sort_bytes, 1));
+        d_foff = c.take<unsigned long long>(multi ? n_files + 1 : 0);       // (several files: where they begin, their first lines)
+        d_line0 = c.take<uint32_t>(multi ? n_files + 1 : 0);
     };
     GAMS_TRY(h, who, s1.alloc(layout_bytes(cols)));
     carve(s1.p, cols);
-    hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, h->text->d_in, n_bytes, F.n16, F.d_bnloff, F.nl,
+    hipLaunchKernelGGL(text_line_start_kernel, dim3(F.nbi), dim3(256), 0, st, h->text->d_in, F.n_in, F.n16, F.d_bnloff, F.nl,
                        d_starts);
-    GAMS_TRY(h, who, hipMemsetAsync(d_first, 0xff, b_tab, st));
-    GAMS_TRY(h, who, hipMemsetAsync(d_count, 0, b_tab, st));
+    GAMS_TRY(h, who, hipMemsetAsync(d_first, 0xff, gams_align256(n_ftab * 4), st));
+    GAMS_TRY(h, who, hipMemsetAsync(d_count, 0, gams_align256(n_tab * 4), st));
+    const RgFileTab ftab{d_line0, (uint32_t)n_files, (uint32_t)n_ctg};
+    if (multi) {
+        memcpy(h_foff, F.file_off.data(), (n_files + 1) * 8);
+        GAMS_TRY(h, who, hipMemcpyAsync(d_foff, h_foff, (n_files + 1) * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(rg_file_lines_kernel, dim3((unsigned)(n_files / 256 + 1)), dim3(256), 0, st, d_starts, F.nl, d_foff,
+                           (uint32_t)n_files, d_line0);
+    }
     GAMS_TRY(h, who, stage(RG_LINES, false));
     C.t = TextLines{reinterpret_cast<const char *>(h->text->d_in), d_starts, F.nl, L};
     C.words = F.d_words;
@@ -881,23 +1042,30 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, S
     launch_interval_locate(ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
     GAMS_TRY(h, who, stage(RG_LOCATE, false));
     GAMS_TRY(h, who, stage(RG_FIRST, true));
-    hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
+    if (multi)
+        hipLaunchKernelGGL(rg_first_files_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, ftab, d_first);
+    else
+        hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
     GAMS_TRY(h, who, stage(RG_FIRST, false));
     GAMS_TRY(h, who, stage(RG_KEEP, true));
-    hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
-                       spec.mid_bits ? (const uint32_t *)d_qs : (const uint32_t *)nullptr, (uint32_t)spec.mid_bits);
+    if (multi)
+        hipLaunchKernelGGL(rg_keep_files_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_bkt, line_bits, d_hit, ftab,
+                           in.by_file ? 1u : 0u, d_first, d_count, d_key);
+    else
+        hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
+                           spec.mid_bits ? (const uint32_t *)d_qs : (const uint32_t *)nullptr, (uint32_t)spec.mid_bits);
     GAMS_TRY(h, who, stage(RG_KEEP, false));
     GAMS_TRY(h, who, stage(RG_OFFSETS, true));
-    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_ctg, d_off, F.d_words,
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_bkt, d_off, F.d_words,
                        (uint32_t)W_ROWS);
     GAMS_TRY(h, who, stage(RG_OFFSETS, false));
     GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(h_off, d_off, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
-    if (n_ctg) GAMS_TRY(h, who, hipMemcpyAsync(h_first, d_first, n_ctg * 4, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipMemcpyAsync(h_off, d_off, (n_bkt + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (n_first) GAMS_TRY(h, who, hipMemcpyAsync(h_first, d_first, n_first * 4, hipMemcpyDeviceToHost, st));
     if (spec.efield) GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
     GAMS_TRY(h, who, hipStreamSynchronize(st));
     if (spec.efield && h->pin_scratch[W_EFIELD]) return gams_fail(h, GAMS_EINVAL, who + spec.efield);
-    C.n_kept = h_off[n_ctg];
+    C.n_kept = h_off[n_bkt];
     if (C.n_kept > 0xfffffff0ull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more than 2^32 - 16 kept ranges");
     C.ran = true;
     if (!order) return consume(C, stage);            // a size query: nothing is gathered, so nothing is sorted
@@ -913,6 +1081,12 @@ int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, S
         C.g.bucket_off = d_off;
     }
     return consume(C, stage);
+}
+
+template <typename Spec, typename Consume>
+int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, const char *bytes, uint64_t n_bytes,
+            bool order, Consume consume) {
+    return rg_load_in(h, who, ctg_ix, spec, RgInput{bytes, n_bytes, nullptr, false}, order, consume);
 }
 
 // the stopwatch of a loader call whose input had lines: stages [0, n) of the handle's timed pairs were recorded (an
@@ -1442,6 +1616,384 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
 }
 
 
+// ---- the records of `gams rg` / `gams feature` (rg.rs:40-82, feature.rs:47-96) as text -----------------------------------
+// The range loader over several files with (file, ctg) buckets (rg_load_in, by_file) and a parse kernel that also says
+// where the name, the chromosome and the strand of every line lie, then three stages of its own; ten in all:
+//   serials  per kept line in key order -- grouped by (file, ctg), in line order inside a group --: its line, its bucket
+//            and its serial = sbase[bucket] + its rank in the bucket + 1.  sbase is the host's, from the buckets' sizes:
+//            cnt:{kind}:{ctg} before the load plus the kept lines of the ctg in the files in front (rg.rs:63-75);
+//   rows     the length of every row, the check of its name and strand for control bytes, the block sums and their prefix;
+//   write    the rows at their offsets (BlockWriter, as the peak rows) and the offset of every bucket's first row.
+// A row is described once (rec_row) for the three formats; RESP needs the lengths of the id and of the JSON in front of
+// them, which the same descriptions give through a counting RowOut.
+struct RecLines {
+    unsigned long long *cb;           // per line: where the chromosome begins
+    uint32_t *clen, *nlen, *slen;     // its length; the name's (without the '.'; 0: none); the strand's (0: none), which
+};                                    // begins behind the '(' that follows the chromosome
+
+__global__ __launch_bounds__(256) void rec_parse_kernel(const TextLines t, const NameTab chr, uint32_t *grp, uint32_t *qs,
+                                                        uint32_t *qe, const RecLines p) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= t.n_lines) return;
+    uint64_t b, e;
+    line_of(t, i, b, e);
+    const char *s = t.in;
+    const RangeField r = parse_range(s, b, e);                 // utils.rs:50: the line, not its first field
+    uint64_t nlen = 0, slen = 0;
+    if (r.ok) {
+        nlen = r.cb > b ? r.cb - b - 1u : 0u;                  // the name ends at the first '.', which the chromosome follows
+        if (s[r.ce] == '(') {                                  // "(strand)" up to the last ':' of the trimmed line
+            uint64_t c = e;
+            while (c > r.ce && s[c - 1u] != ':') --c;
+            slen = c - r.ce - 3u;                              // c - 1: the colon, c - 2: the ')'
+        }
+    }
+    grp[i] = r.ok ? name_find(chr, s + r.cb, r.ce - r.cb) : UINT32_MAX;
+    qs[i] = r.start;
+    qe[i] = r.end;
+    p.cb[i] = r.cb;
+    p.clen[i] = (uint32_t)(r.ce - r.cb);
+    p.nlen[i] = (uint32_t)(nlen < 0xffffffffull ? nlen : 0xffffffffull);
+    p.slen[i] = (uint32_t)(slen < 0xffffffffull ? slen : 0xffffffffull);
+}
+
+// what the records ask of the loader (see RgPlain)
+struct RecLoad {
+    NameTab chr;
+    RecLines rl;
+    static constexpr uint32_t mid_bits = 0;
+    static constexpr const char *efield = nullptr;
+    void cols(Carver &c, uint32_t L) {
+        rl.cb = c.take<unsigned long long>(L);
+        rl.clen = c.take<uint32_t>(L);
+        rl.nlen = c.take<uint32_t>(L);
+        rl.slen = c.take<uint32_t>(L);
+    }
+    void parse(const TextLines &tl, uint32_t *grp, uint32_t *qs, uint32_t *qe, unsigned long long *, uint32_t nbr, hipStream_t st) const {
+        hipLaunchKernelGGL(rec_parse_kernel, dim3(nbr), dim3(256), 0, st, tl, chr, grp, qs, qe, rl);
+    }
+};
+
+constexpr uint32_t kRecMaxField = 1u << 30;   // a name or strand of this many bytes is refused: a row's lengths stay below 2^32
+
+struct RecArgs {
+    TextLines t;
+    RecLines p;
+    const unsigned long long *key;            // sorted: the first n_kept are the kept lines in (file, ctg, line) order
+    uint32_t line_bits;
+    uint32_t n_kept, n_ctg;
+    const uint32_t *qs, *qe;                  // per line
+    const unsigned long long *bucket_off;     // n_bkt + 1
+    const uint32_t *sbase;                    // per bucket: the serial in front of its first row's
+    NameTab ids;
+    const char *tag;
+    uint32_t tag_len;
+    int kind, format;
+    uint32_t *kline, *kbkt, *kserial;         // per kept line
+    unsigned long long *row_len;
+    unsigned long long *blk_bytes;            // per workgroup of 256 rows
+    const unsigned long long *blk_off;
+    unsigned long long *text_off;             // per bucket with rows: the offset of its first row
+    unsigned long long *words;
+    char *text;
+};
+
+__global__ __launch_bounds__(256) void rec_serial_kernel(const RecArgs a) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= a.n_kept) return;
+    const unsigned long long key = a.key[k];
+    const uint32_t b = (uint32_t)(key >> a.line_bits);
+    a.kline[k] = (uint32_t)(key & ((1ull << a.line_bits) - 1ull));
+    a.kbkt[k] = b;
+    a.kserial[k] = a.sbase[b] + (k - (uint32_t)a.bucket_off[b]) + 1u;
+}
+
+// "{kind}:{ctg_id}:{serial}" (rg.rs:64-66, feature.rs:81-83); json: inside a JSON string
+template <bool kWrite>
+__device__ __forceinline__ void rec_id(const RecArgs &a, uint32_t k, RowOut<kWrite, uint64_t> &o, bool json) {
+    if (a.kind == GAMS_LOADER_FEATURE)
+        o.bytes("feature:", 8u);
+    else
+        o.bytes("rg:", 3u);
+    const uint32_t c = a.kbkt[k] % a.n_ctg;
+    const unsigned long long io = a.ids.off[c], il = a.ids.off[c + 1u] - io;
+    if (json)
+        o.esc(a.ids.bytes + io, il);
+    else
+        o.bytes(a.ids.bytes + io, il);
+    o.ch(':');
+    o.dec(a.kserial[k]);
+}
+
+// Range::to_string() of the parsed line: canonical, not echoed
+template <bool kWrite>
+__device__ __forceinline__ void rec_range(const RecArgs &a, uint32_t i, RowOut<kWrite, uint64_t> &o, bool json) {
+    const char *in_ = a.t.in;
+    const uint64_t cb = a.p.cb[i], clen = a.p.clen[i], nlen = a.p.nlen[i], slen = a.p.slen[i];
+    if (nlen) {
+        if (json)
+            o.esc(in_ + a.t.starts[i], nlen);
+        else
+            o.bytes(in_ + a.t.starts[i], nlen);
+        o.ch('.');
+    }
+    o.bytes(in_ + cb, clen);
+    if (slen) {
+        o.ch('(');
+        if (json)
+            o.esc(in_ + cb + clen + 1u, slen);
+        else
+            o.bytes(in_ + cb + clen + 1u, slen);
+        o.ch(')');
+    }
+    o.ch(':');
+    const uint32_t s = a.qs[i], e = a.qe[i];
+    o.dec(s);
+    if (e != s) {
+        o.ch('-');
+        o.dec(e);
+    }
+}
+
+// serde_json of Rg / Feature (data.rs:16-28): field order, no spaces
+template <bool kWrite>
+__device__ __forceinline__ void rec_json(const RecArgs &a, uint32_t k, RowOut<kWrite, uint64_t> &o) {
+    const uint32_t i = a.kline[k];
+    o.bytes("{\"id\":\"", 7u);
+    rec_id(a, k, o, true);
+    o.bytes("\",\"range\":\"", 11u);
+    rec_range(a, i, o, true);
+    if (a.kind == GAMS_LOADER_FEATURE) {
+        o.bytes("\",\"length\":", 11u);
+        o.i32((int32_t)(a.qe[i] - a.qs[i] + 1u));              // feature.rs:88: end - start + 1, an i32
+        o.bytes(",\"tag\":\"", 8u);
+        o.esc(a.tag, (uint64_t)a.tag_len);
+    }
+    o.bytes("\"}", 2u);
+}
+
+template <bool kWrite>
+__device__ void rec_row(const RecArgs &a, uint32_t k, RowOut<kWrite, uint64_t> &o) {
+    if (a.format == GAMS_LOADER_TSV) {                         // tsv.rs: the values in field order
+        const uint32_t i = a.kline[k];
+        rec_id(a, k, o, false);
+        o.ch('\t');
+        rec_range(a, i, o, false);
+        if (a.kind == GAMS_LOADER_FEATURE) {
+            o.ch('\t');
+            o.i32((int32_t)(a.qe[i] - a.qs[i] + 1u));
+            o.ch('\t');
+            o.bytes(a.tag, (uint64_t)a.tag_len);
+        }
+        o.ch('\n');
+    } else if (a.format == GAMS_LOADER_RESP) {                 // wire::resp_command({"SET", id, json})
+        RowOut<false, uint64_t> li, lj;
+        rec_id(a, k, li, false);
+        rec_json(a, k, lj);
+        o.bytes("*3\r\n$3\r\nSET\r\n$", 14u);
+        o.dec((uint32_t)li.n);
+        o.bytes("\r\n", 2u);
+        rec_id(a, k, o, false);
+        o.bytes("\r\n$", 3u);
+        o.dec((uint32_t)lj.n);
+        o.bytes("\r\n", 2u);
+        rec_json(a, k, o);
+        o.bytes("\r\n", 2u);
+    } else {                                                   // "{id}\t{json}\n"
+        rec_id(a, k, o, false);
+        o.ch('\t');
+        rec_json(a, k, o);
+        o.ch('\n');
+    }
+}
+
+__global__ __launch_bounds__(256) void rec_row_len_kernel(const RecArgs a) {
+    __shared__ uint64_t ws[4];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    RowOut<false, uint64_t> n;
+    if (k < a.n_kept) {
+        const uint32_t i = a.kline[k];
+        const uint32_t nlen = a.p.nlen[i], slen = a.p.slen[i];
+        bool bad = nlen >= kRecMaxField || slen >= kRecMaxField;
+        if (!bad) {
+            // a control byte in a string value: serde_json writes \uXXXX and the like, this writer does not
+            const char *nm = a.t.in + a.t.starts[i], *sd = a.t.in + a.p.cb[i] + a.p.clen[i] + 1u;
+            for (uint32_t j = 0; j < nlen; ++j) bad |= (uint8_t)nm[j] < 0x20u;
+            for (uint32_t j = 0; j < slen; ++j) bad |= (uint8_t)sd[j] < 0x20u;
+        }
+        if (bad)
+            a.words[W_UNSUP] = 1ull;
+        else
+            rec_row(a, k, n);
+        a.row_len[k] = n.n;
+    }
+    uint64_t tot;
+    (void)block_excl_scan_256<uint64_t>(n.n, ws, tot);
+    if (threadIdx.x == 0) a.blk_bytes[blockIdx.x] = tot;
+}
+
+// bytes of a block's rows staged in LDS: 256 RESP rows of a feature are ~36 KB; a block beyond the stage (long names or
+// tags) writes its rows to global memory directly
+constexpr uint32_t kRecStage = 49152;
+
+// Never launched when the length pass set W_UNSUP: every row it writes was measured there.
+__global__ __launch_bounds__(256) void rec_row_write_kernel(const RecArgs a) {
+    __shared__ uint64_t ws[4];
+    __shared__ __align__(16) char stage[kRecStage + 16];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t l = k < a.n_kept ? a.row_len[k] : 0ull;
+    BlockWriter<uint64_t> w(l, ws, a.blk_off, a.text, ~0ull);   // (the text holds all rows: no bound)
+    w.stage_if(w.tot <= kRecStage, stage);
+    if (k < a.n_kept) {
+        const uint32_t b = a.kbkt[k];
+        if (k == (uint32_t)a.bucket_off[b]) a.text_off[b] = w.blk0 + w.rel;
+        w.put(w.rel, [&](char *p) {
+            RowOut<true, uint64_t> o{p};
+            rec_row(a, k, o);
+        });
+    }
+    w.flush();
+}
+
+enum : int { LT_SERIALS = RG_GATHER, LT_ROWS, LT_WRITE, LT_STAGES };   // behind the loader's lines .. order
+
+struct RecJob {
+    const gams_index_t *ctg_ix;
+    const gams_names_t *chr, *ids;
+    TextFiles files;
+    int kind, format;
+    const char *tag;
+    uint64_t tag_bytes;
+    const int32_t *serial_base;
+};
+
+int loader_text_run(gams_gpu_t *h, const RecJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
+                    int32_t *serial_next, uint64_t *n_in_file, uint64_t *n_rows) {
+    const std::string who = "gpu_loader_text";
+    const uint64_t n_ctg = J.ctg_ix->m, n_files = J.files.n, n_pairs = n_files * n_ctg;
+    *text = "";
+    *text_bytes = 0;
+    *n_rows = 0;
+    memset(text_off, 0, (n_pairs + 1) * 8);
+    for (uint64_t f = 0; f < n_files; ++f)
+        if (n_in_file) n_in_file[f] = 0;
+    for (uint64_t c = 0; c < n_ctg; ++c) {
+        const int32_t base = J.serial_base ? J.serial_base[c] : 0;
+        if (base < 0) return gams_fail(h, GAMS_EINVAL, who + ": a negative serial_base");
+        if (serial_next) serial_next[c] = base;
+    }
+    GAMS_HIP(h, hipSetDevice(h->device));
+    GAMS_HIP(h, gams_stopwatch_reserve(h, LT_STAGES));
+    RecLoad load{J.chr->t, RecLines{}};
+    return rg_load_in(h, who, J.ctg_ix, load, RgInput{nullptr, 0, &J.files, true}, true, [&](const RgCols &C, const StageClock &stage) -> int {
+        if (C.n_kept == 0) {
+            if (C.ran) rg_timed(h, RG_ORDER + 1);
+            return GAMS_OK;
+        }
+        // (kept lines: there is a file, and with one file the buckets are the ctgs: n_bkt = n_files * n_ctg either way)
+        const uint64_t n_bkt = C.n_bkt;
+        const uint32_t K = (uint32_t)C.n_kept, nbk = (K + 255u) / 256u;  // n_kept <= L < 2^32
+        hipStream_t st = h->compute;
+        PoolBlock s2(h, false), pin(h, true), d_text(h, false);
+        // the serials: the buckets of a ctg, file by file, continue its counter
+        struct Tabs {
+            uint32_t *sbase;
+            unsigned long long *toff;
+        };
+        auto tabs = [&](Carver &c) {
+            Tabs t{};
+            t.sbase = c.take<uint32_t>(n_bkt);
+            t.toff = c.take<unsigned long long>(n_bkt + 1);
+            return t;
+        };
+        GAMS_TRY(h, who, pin.alloc(layout_bytes(tabs)));
+        const Tabs ht = carve(pin.p, tabs);
+        std::vector<int64_t> next(n_ctg);
+        for (uint64_t c = 0; c < n_ctg; ++c) next[c] = J.serial_base ? J.serial_base[c] : 0;
+        for (uint64_t b = 0; b < n_bkt; ++b) {
+            const uint64_t c = b % n_ctg, n = C.bucket_off[b + 1] - C.bucket_off[b];
+            ht.sbase[b] = (uint32_t)next[c];
+            next[c] += (int64_t)n;
+            if (n && next[c] > INT32_MAX) return gams_fail(h, GAMS_EINVAL, who + ": a serial beyond INT32_MAX");
+        }
+        RecArgs a{};
+        char *d_tag = nullptr;
+        Tabs dt{};
+        auto kept = [&](Carver &c) {   // sbase text_off | line bucket serial | row lengths | the blocks' bytes and prefix | tag
+            dt = tabs(c);
+            a.kline = c.take<uint32_t>(K);
+            a.kbkt = c.take<uint32_t>(K);
+            a.kserial = c.take<uint32_t>(K);
+            a.row_len = c.take<unsigned long long>(K);
+            a.blk_bytes = c.take<unsigned long long>((size_t)nbk + 1);
+            unsigned long long *const off = c.take<unsigned long long>((size_t)nbk + 1);
+            a.blk_off = off;
+            d_tag = c.take<char>(std::max<uint64_t>(J.tag_bytes, 1));
+            return off;
+        };
+        GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
+        unsigned long long *const d_blk_off = carve(s2.p, kept);
+        a.t = C.t;
+        a.p = load.rl;
+        a.key = C.g.key;
+        a.line_bits = (uint32_t)__builtin_popcountll(C.g.line_mask);
+        a.n_kept = K;
+        a.n_ctg = (uint32_t)n_ctg;
+        a.qs = C.g.qs;
+        a.qe = C.g.qe;
+        a.bucket_off = C.g.bucket_off;
+        a.sbase = dt.sbase;
+        a.ids = J.ids->t;
+        a.tag = d_tag;
+        a.tag_len = (uint32_t)J.tag_bytes;
+        a.kind = J.kind;
+        a.format = J.format;
+        a.text_off = dt.toff;
+        a.words = C.words;
+        GAMS_TRY(h, who, stage(LT_SERIALS, true));
+        GAMS_TRY(h, who, hipMemcpyAsync(dt.sbase, ht.sbase, n_bkt * 4, hipMemcpyHostToDevice, st));
+        if (J.tag_bytes) GAMS_TRY(h, who, hipMemcpyAsync(d_tag, J.tag, J.tag_bytes, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(rec_serial_kernel, dim3(nbk), dim3(256), 0, st, a);
+        GAMS_TRY(h, who, stage(LT_SERIALS, false));
+        GAMS_TRY(h, who, stage(LT_ROWS, true));
+        hipLaunchKernelGGL(rec_row_len_kernel, dim3(nbk), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbk, d_blk_off,
+                           C.words, (uint32_t)W_BYTES);
+        GAMS_TRY(h, who, stage(LT_ROWS, false));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, C.words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
+        const unsigned long long *w = h->pin_scratch;
+        if (w[W_UNSUP])
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a kept line's name or strand holds a control byte, or 2^30 bytes (use the host path)");
+        const uint64_t tb = w[W_BYTES];
+        gams_text_state *T = h->text;
+        GAMS_TRY(h, who, gams_pool_grow(h, true, &T->rec_out, &T->rec_out_cap, tb, tb));
+        GAMS_TRY(h, who, d_text.alloc(tb));
+        a.text = reinterpret_cast<char *>(d_text.p);
+        GAMS_TRY(h, who, stage(LT_WRITE, true));
+        hipLaunchKernelGGL(rec_row_write_kernel, dim3(nbk), dim3(256), 0, st, a);
+        GAMS_TRY(h, who, stage(LT_WRITE, false));
+        GAMS_TRY(h, who, hipGetLastError());
+        GAMS_TRY(h, who, hipMemcpyAsync(T->rec_out, d_text.p, tb, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipMemcpyAsync(ht.toff, dt.toff, (n_bkt + 1) * 8, hipMemcpyDeviceToHost, st));
+        GAMS_TRY(h, who, hipStreamSynchronize(st));
+        // a bucket without rows begins where the next one does
+        text_off[n_bkt] = tb;
+        for (uint64_t b = n_bkt; b-- > 0;) text_off[b] = C.bucket_off[b + 1] > C.bucket_off[b] ? ht.toff[b] : text_off[b + 1];
+        for (uint64_t f = 0; f < n_files; ++f)
+            if (n_in_file) n_in_file[f] = C.bucket_off[(f + 1) * n_ctg] - C.bucket_off[f * n_ctg];
+        if (serial_next)
+            for (uint64_t c = 0; c < n_ctg; ++c) serial_next[c] = (int32_t)next[c];
+        rg_timed(h, LT_STAGES);
+        *text = T->rec_out;
+        *text_bytes = tb;
+        *n_rows = C.n_kept;
+        return GAMS_OK;
+    });
+}
+
+
 // ---- `locate --seq` (locate.rs:124-134): the bytes of a range file -> ">{rg}\n{bases}\n" of every located line --------
 // Behind the front of locate_text (line index, text_parse_rg_kernel, interval_locate_kernel), six stages in all:
 //   lines, parse, locate   as for locate_text;
@@ -1750,6 +2302,46 @@ int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n
     *n_rows = rows;
     return GAMS_OK;
 }
+// The rg index of a load (one file or several, the buckets by ctg): the gather into the builder's columns, then the build.
+int rg_index_run(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, const gams_names_t *chr_names, const RgInput &in,
+                 gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept) {
+    *rg_ix = nullptr;
+    *n_kept = 0;
+    return rg_load_in(h, who, ctg_ix, RgPlain{chr_names->t}, in, true, [&](const RgCols &C, const StageClock &stage) -> int {
+        uint32_t max_n = 0;
+        for (uint64_t i = 0; i < C.n_ctg; ++i)
+            max_n = std::max<uint32_t>(max_n, (uint32_t)(C.bucket_off[i + 1] - C.bucket_off[i]));
+        IndexBuild B(h);
+        const int rc = gams_index_build_begin(h, (uint32_t)C.n_ctg, C.n_kept, &B);
+        if (rc != GAMS_OK) return rc;
+        hipStream_t st = h->compute;
+        hipError_t e = stage(RG_GATHER, true);
+        if (C.n_kept) {
+            RgGather g = C.g;
+            g.start = B.cols.starts_in;
+            g.end = B.cols.stops_in;            // [start, end + 1) (redis.rs:291-294)
+            g.line = nullptr;
+            g.end_plus = 1;
+            g.off32 = B.cols.off32;
+            g.n_off = C.n_ctg + 1;
+            const uint64_t lanes = std::max<uint64_t>(C.n_kept, g.n_off);
+            hipLaunchKernelGGL(rg_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, g);
+            if (e == hipSuccess) e = hipGetLastError();
+        } else if (e == hipSuccess) {
+            e = hipMemsetAsync(B.cols.off32, 0, (C.n_ctg + 1) * 4, st);   // every group empty
+        }
+        if (e == hipSuccess) e = stage(RG_GATHER, false);
+        if (e == hipSuccess) e = stage(RG_BUILD, true);
+        if (e != hipSuccess) return gams_index_build_fail(h, &B, e, "range text columns");
+        // the stage's closing event goes in behind the builder's last kernel, before its host wait
+        const int rb = gams_index_build_run(h, &B, max_n, rg_ix, h->kq[(size_t)RG_BUILD].second);
+        if (rb != GAMS_OK) return rb;
+        for (uint64_t i = 0; i < C.n_ctg; ++i) rg_group[i] = C.seen(i) ? (uint32_t)i : UINT32_MAX;
+        *n_kept = C.n_kept;
+        if (C.ran) rg_timed(h, RG_STAGES);
+        return GAMS_OK;
+    });
+}
 }  // namespace
 
 extern "C" {
@@ -1910,43 +2502,42 @@ int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams
                                  uint64_t n_bytes, gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept) {
     if (!h || !ctg_ix || !chr_names || (n_bytes && !bytes) || !rg_ix || (ctg_ix->m && !rg_group) || !n_kept)
         return gams_fail(h, GAMS_EINVAL, "index_create_range_text: null argument");
-    const std::string who = "index_create_range_text";
-    *rg_ix = nullptr;
-    *n_kept = 0;
-    return rg_load(h, who, ctg_ix, RgPlain{chr_names->t}, bytes, n_bytes, true, [&](const RgCols &C, const StageClock &stage) -> int {
-        uint32_t max_n = 0;
-        for (uint64_t i = 0; i < C.n_ctg; ++i)
-            max_n = std::max<uint32_t>(max_n, (uint32_t)(C.bucket_off[i + 1] - C.bucket_off[i]));
-        IndexBuild B(h);
-        const int rc = gams_index_build_begin(h, (uint32_t)C.n_ctg, C.n_kept, &B);
-        if (rc != GAMS_OK) return rc;
-        hipStream_t st = h->compute;
-        hipError_t e = stage(RG_GATHER, true);
-        if (C.n_kept) {
-            RgGather g = C.g;
-            g.start = B.cols.starts_in;
-            g.end = B.cols.stops_in;            // [start, end + 1) (redis.rs:291-294)
-            g.line = nullptr;
-            g.end_plus = 1;
-            g.off32 = B.cols.off32;
-            g.n_off = C.n_ctg + 1;
-            const uint64_t lanes = std::max<uint64_t>(C.n_kept, g.n_off);
-            hipLaunchKernelGGL(rg_gather_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, g);
-            if (e == hipSuccess) e = hipGetLastError();
-        } else if (e == hipSuccess) {
-            e = hipMemsetAsync(B.cols.off32, 0, (C.n_ctg + 1) * 4, st);   // every group empty
-        }
-        if (e == hipSuccess) e = stage(RG_GATHER, false);
-        if (e == hipSuccess) e = stage(RG_BUILD, true);
-        if (e != hipSuccess) return gams_index_build_fail(h, &B, e, "range text columns");
-        // the stage's closing event goes in behind the builder's last kernel, before its host wait
-        const int rb = gams_index_build_run(h, &B, max_n, rg_ix, h->kq[(size_t)RG_BUILD].second);
-        if (rb != GAMS_OK) return rb;
-        for (uint64_t i = 0; i < C.n_ctg; ++i) rg_group[i] = C.first[i] != UINT32_MAX ? (uint32_t)i : UINT32_MAX;
-        *n_kept = C.n_kept;
-        if (C.ran) rg_timed(h, RG_STAGES);
-        return GAMS_OK;
-    });
+    return rg_index_run(h, "index_create_range_text", ctg_ix, chr_names, RgInput{bytes, n_bytes, nullptr, false}, rg_ix, rg_group, n_kept);
+}
+
+int gams_index_create_range_files(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, uint32_t n_files,
+                                  const char *const *bytes, const uint64_t *n_bytes, gams_index_t **rg_ix, uint32_t *rg_group,
+                                  uint64_t *n_kept) {
+    if (!h || !ctg_ix || !chr_names || (n_files && (!bytes || !n_bytes)) || !rg_ix || (ctg_ix->m && !rg_group) || !n_kept)
+        return gams_fail(h, GAMS_EINVAL, "index_create_range_files: null argument");
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (n_bytes[f] && !bytes[f]) return gams_fail(h, GAMS_EINVAL, "index_create_range_files: null argument");
+    const TextFiles files{n_files, bytes, n_bytes};
+    return rg_index_run(h, "index_create_range_files", ctg_ix, chr_names, RgInput{nullptr, 0, &files, false}, rg_ix, rg_group, n_kept);
+}
+
+int gams_gpu_loader_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const gams_names_t *ctg_ids,
+                         uint32_t n_files, const char *const *bytes, const uint64_t *n_bytes, int kind, const char *tag,
+                         uint64_t tag_bytes, int format, const int32_t *serial_base, const char **text, uint64_t *text_bytes,
+                         uint64_t *text_off, int32_t *serial_next, uint64_t *n_in_file, uint64_t *n_rows) {
+    if (!h || !ctg_ix || !chr_names || !ctg_ids || (n_files && (!bytes || !n_bytes)) || !text || !text_bytes || !text_off || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_loader_text: null argument");
+    for (uint32_t f = 0; f < n_files; ++f)
+        if (n_bytes[f] && !bytes[f]) return gams_fail(h, GAMS_EINVAL, "gpu_loader_text: null argument");
+    if (kind != GAMS_LOADER_RG && kind != GAMS_LOADER_FEATURE) return gams_fail(h, GAMS_EINVAL, "gpu_loader_text: unknown kind");
+    if (format != GAMS_LOADER_RECORDS && format != GAMS_LOADER_TSV && format != GAMS_LOADER_RESP)
+        return gams_fail(h, GAMS_EINVAL, "gpu_loader_text: unknown format");
+    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_loader_text: ctg_ids must name every interval of ctg_ix");
+    if (kind != GAMS_LOADER_FEATURE) tag_bytes = 0;
+    if (tag_bytes && !tag) return gams_fail(h, GAMS_EINVAL, "gpu_loader_text: null argument");
+    if ((uint64_t)n_files * ctg_ix->m > kRgMaxFileCtg)     // (before text_off, which has an entry per pair, is touched)
+        return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_loader_text: more than 2^24 (file, ctg) pairs (use the host path)");
+    if (tag_bytes >= kRecMaxField) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_loader_text: a tag of 2^30 bytes or more (use the host path)");
+    for (uint64_t k = 0; k < tag_bytes; ++k)
+        if ((uint8_t)tag[k] < 0x20u || (uint8_t)tag[k] >= 0x80u)
+            return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_loader_text: the tag holds a control byte or a byte >= 0x80 (use the host path)");
+    return loader_text_run(h, RecJob{ctg_ix, chr_names, ctg_ids, TextFiles{n_files, bytes, n_bytes}, kind, format, tag, tag_bytes, serial_base},
+                           text, text_bytes, text_off, serial_next, n_in_file, n_rows);
 }
 
 int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,

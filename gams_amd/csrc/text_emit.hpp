@@ -90,6 +90,11 @@ template <typename Len>
 struct RowOut<false, Len> {
     Len n = 0;
     __device__ __forceinline__ void bytes(const char *, Len len) { n += len; }
+    __device__ __forceinline__ void esc(const char *src, Len len) {   // inside a JSON string: '"' and '\\' get a backslash
+        Len x = 0;
+        for (Len k = 0; k < len; ++k) x += (src[k] == '"' || src[k] == '\\') ? 1u : 0u;
+        n += len + x;
+    }
     __device__ __forceinline__ void ch(char) { ++n; }
     __device__ __forceinline__ void dec(uint32_t v) { n += dec_digits(v); }
     __device__ __forceinline__ void i32(int32_t v) { n += i32_len(v); }
@@ -105,6 +110,13 @@ template <typename Len>
 struct RowOut<true, Len> {
     char *q;
     __device__ __forceinline__ void bytes(const char *src, Len len) { q = put_bytes(q, src, len); }
+    __device__ __forceinline__ void esc(const char *src, Len len) {
+        for (Len k = 0; k < len; ++k) {
+            const char c = src[k];
+            if (c == '"' || c == '\\') *q++ = '\\';
+            *q++ = c;
+        }
+    }
     __device__ __forceinline__ void ch(char c) { *q++ = c; }
     __device__ __forceinline__ void dec(uint32_t v) { q = put_dec(q, v); }
     __device__ __forceinline__ void i32(int32_t v) { q = put_i32(q, v); }

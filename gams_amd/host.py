@@ -143,6 +143,25 @@ def load():
     L.gams_host_sw_multi_actions_rg.restype = C.c_void_p
     L.gams_host_sw_multi_actions_rg.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p,
                                                 C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p, C.c_uint64]
+    vp, fl = C.POINTER(C.c_void_p), C.c_void_p        # several files: their pointers, their lengths (uint64)
+    L.gams_host_locate_rgs.restype = C.c_void_p
+    L.gams_host_locate_rgs.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_int, C.c_uint32, vp, fl]
+    L.gams_host_locate_text_rgs.restype = C.c_void_p
+    L.gams_host_locate_text_rgs.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_uint64, C.c_int,
+                                            C.c_uint32, vp, fl, C.POINTER(C.c_uint64)]
+    L.gams_host_sw_actions_rgs.restype = C.c_void_p
+    L.gams_host_sw_actions_rgs.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32,
+                                           sp, ip, ip, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, fl]
+    L.gams_host_sw_multi_actions_rgs.restype = C.c_void_p
+    L.gams_host_sw_multi_actions_rgs.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, fl]
+    L.gams_host_sw_text_rgs.restype = C.c_void_p
+    L.gams_host_sw_text_rgs.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                        C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, fl,
+                                        C.POINTER(C.c_uint64)]
+    L.gams_host_loader_text.restype = C.c_void_p
+    L.gams_host_loader_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_uint32, vp, fl, C.c_int, C.c_char_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     L.gams_host_last_operator_device.restype = C.c_int
     L.gams_host_last_operator_device.argtypes = []
     L.gams_host_fmt_prop4.restype = C.c_void_p
@@ -302,10 +321,21 @@ def _rg_lines(rg_records):
 
 
 def _one_rg_source(rg_records, rg_data):
-    """rg_records and rg_data (the bytes of an rg file) are two forms of one argument"""
+    """rg_records and rg_data (the bytes of an rg file, or a list / tuple of them: several files loaded one after
+    another, as `gams rg f1 f2 ...` loads them) are two forms of one argument"""
     if rg_data is not None and len(rg_records):
         raise ValueError("rg_records and rg_data are mutually exclusive: give the rg: records or the bytes of an rg file")
+    if isinstance(rg_data, (list, tuple)):
+        return [bytes(d) for d in rg_data]
     return None if rg_data is None else bytes(rg_data)
+
+
+def _files(datas):
+    """(n, pointers, lengths, the buffers that must outlive the call) of several files' bytes"""
+    bufs = [np.frombuffer(bytes(d), np.uint8) for d in datas]
+    ptrs = (C.c_void_p * max(len(bufs), 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    lens = np.array([b.size for b in bufs], np.uint64)
+    return len(bufs), ptrs, lens.ctypes.data, (bufs, lens)
 
 
 def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None):
@@ -323,6 +353,11 @@ def sw(eng, ctg, features, size=100, mx=20, resize=500, actions=("gc",), rg_reco
     fe = np.array([f[2] for f in features], np.int32)
     seq = np.ascontiguousarray(np.frombuffer(ctg["seq"], np.uint8) if not isinstance(ctg["seq"], np.ndarray)
                                else ctg["seq"])
+    if isinstance(rg_data, list):
+        nr, rp, rl, _keep = _files(rg_data)
+        return _take(load().gams_host_sw_actions_rgs(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
+                                                     ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data,
+                                                     fe.ctypes.data, size, mx, resize, mask, nr, rp, rl))
     if rg_data is not None:
         return _take(load().gams_host_sw_actions_rg(eng.h, ctg["id"].encode(), ctg["chr_id"].encode(), ctg["chr_start"],
                                                     ctg["chr_end"], seq.ctypes.data, nf, fid, fs.ctypes.data,
@@ -341,6 +376,10 @@ def locate(eng, ctgs, rgs, count=False, rg_records=(), rg_data=None):
     rg file, loaded on the device."""
     rg_data = _one_rg_source(rg_records, rg_data)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    if isinstance(rg_data, list):
+        nr, rp, rl, _keep = _files(rg_data)
+        return _take(load().gams_host_locate_rgs(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data,
+                                                 "\n".join(rgs).encode(), int(count), nr, rp, rl))
     if rg_data is not None:
         return _take(load().gams_host_locate_rg(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data,
                                                 "\n".join(rgs).encode(), int(count), rg_data, len(rg_data)))
@@ -368,6 +407,11 @@ def locate_text(eng, ctgs, data, count=False, rg_records=(), rg_data=None):
     path where the device refuses).  Returns the rows as bytes; rg_records / rg_data as for locate()."""
     rg_data = _one_rg_source(rg_records, rg_data)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    if isinstance(rg_data, list):
+        nr, rp, rl, _keep = _files(rg_data)
+        out_len = C.c_uint64()
+        return _take_bytes(load().gams_host_locate_text_rgs(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, data,
+                                                            len(data), int(count), nr, rp, rl, C.byref(out_len)), out_len)
     if rg_data is not None:
         out_len = C.c_uint64()
         return _take_bytes(load().gams_host_locate_text_rg(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, data,
@@ -538,6 +582,32 @@ def loader_records(eng, ctgs, lines, tag=None):
     return [tuple(r.split("\t", 1)) for r in out.splitlines()]
 
 
+LOADER_KINDS = {"rg": _lib.LOADER_RG, "feature": _lib.LOADER_FEATURE}
+LOADER_FORMATS = {"records": _lib.LOADER_RECORDS, "tsv": _lib.LOADER_TSV, "resp": _lib.LOADER_RESP}
+
+
+def loader_text(eng, ctgs, files, kind="rg", tag="feature", fmt="records", serial_base=None):
+    """`gams rg f1 f2 ...` (kind "rg") / `gams feature --tag TAG f1 f2 ...` (kind "feature") over the bytes of the files:
+    the records the loader would SET, written on the device (the host's passes where it refuses; last_operator_device
+    says which), in the reference's order: file by file, the ctgs by id, file order inside a ctg.  fmt: "records"
+    ("{key}\\t{json}\\n"), "tsv" (the rows of loader_tsv without its header) or "resp" (resp_command(["SET", key, json])
+    of every record).  serial_base: {ctg id: the ctg's cnt: before the load} (absent: 0).
+    -> (bytes, {ctg id: the counter after the load} for every ctg, [records of every file])"""
+    if kind not in LOADER_KINDS or fmt not in LOADER_FORMATS:
+        raise ValueError(f"loader_text: kind is one of {list(LOADER_KINDS)}, fmt one of {list(LOADER_FORMATS)}")
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    nf, fp, fl, _keep = _files(files)
+    base = np.array([(serial_base or {}).get(c["id"], 0) for c in ctgs], np.int32)
+    nxt = np.zeros(max(n, 1), np.int32)
+    per = np.zeros(max(nf, 1), np.uint64)
+    out_len = C.c_uint64()
+    text = _take_bytes(load().gams_host_loader_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, nf, fp, fl,
+                                                    LOADER_KINDS[kind], tag.encode("latin-1") if isinstance(tag, str) else tag,
+                                                    LOADER_FORMATS[fmt], base.ctypes.data if n else None, nxt.ctypes.data,
+                                                    per.ctypes.data, C.byref(out_len)), out_len)
+    return text, {c["id"]: int(v) for c, v in zip(ctgs, nxt)}, [int(v) for v in per[:nf]]
+
+
 def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None):
     """`gams sw` over several handles; features_per_ctg[i] = list of (id, start, end) of ctgs[i]; actions,
     rg_records and rg_data as for sw()."""
@@ -549,6 +619,10 @@ def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actio
     seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
     hs = (C.c_void_p * len(engines))(*[e.h.value for e in engines])
     rows = "\n".join(f"{i}\t{fid}\t{s}\t{e}" for i, fl in enumerate(features_per_ctg) for fid, s, e in fl)
+    if isinstance(rg_data, list):
+        nr, rp, rl, _keep = _files(rg_data)
+        return _take(load().gams_host_sw_multi_actions_rgs(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data,
+                                                           seqs, rows.encode(), size, mx, resize, mask, nr, rp, rl))
     if rg_data is not None:
         return _take(load().gams_host_sw_multi_actions_rg(hs, len(engines), n, ids, chrs, st.ctypes.data, en.ctypes.data,
                                                           seqs, rows.encode(), size, mx, resize, mask, rg_data,
@@ -706,20 +780,24 @@ def sw_text(eng, ctgs, data, size=100, mx=20, resize=500, actions=("gc",), rg_re
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
     out_len = C.c_uint64()
     rg_lines = _rg_lines(rg_records) if (mask & _lib.SW_COUNT) and rg_data is None else None
+    entry = load().gams_host_sw_text
     tail = (bytes(data), len(data), size, mx, resize, mask, rg_lines, rg_data, 0 if rg_data is None else len(rg_data),
             C.byref(out_len))
+    if isinstance(rg_data, list):
+        nr, rp, rl, _keep = _files(rg_data)
+        entry = load().gams_host_sw_text_rgs
+        tail = (bytes(data), len(data), size, mx, resize, mask, nr, rp, rl, C.byref(out_len))
     if seqset is None:
         seqs = None
         if mask & _lib.SW_GC:
             bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
                                          else c["seq"]) for c in ctgs]
             seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
-        p = load().gams_host_sw_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, *tail)
+        p = entry(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, *tail)
     else:
         slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
         slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
-        p = load().gams_host_sw_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
-                                     slots.ctypes.data, *tail)
+        p = entry(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p, slots.ctypes.data, *tail)
     return _take_bytes(p, out_len)
 
 

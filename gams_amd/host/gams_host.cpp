@@ -792,15 +792,15 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
                                               const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                               uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
                                               double *index_ms, const char *rg_bytes, size_t rg_n,
-                                              const std::vector<Ctg> *located_in);
+                                              const std::vector<Ctg> *located_in, const std::vector<FileBytes> *rg_files);
 
 std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &handles, const std::vector<Ctg> &ctgs,
                                             const std::vector<const uint8_t *> &seqs,
                                             const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                             const std::map<std::string, std::vector<Range>> *rgs, double *index_ms,
-                                            const char *rg_bytes, size_t rg_n) {
+                                            const char *rg_bytes, size_t rg_n, const std::vector<FileBytes> *rg_files) {
     if (handles.empty()) throw Error(GAMS_EINVAL, "sw_proc_ctgs_multi: no handles");
-    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+    if (rgs && (rg_bytes || rg_files)) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs_multi: ctgs / seqs / features size mismatch");
     std::vector<uint64_t> weight(ctgs.size());
@@ -821,7 +821,7 @@ std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &han
                 where.push_back(c);
             }
         std::vector<std::string> rows =
-            sw_proc_ctgs_located(handles[d], dc, ds, df, a, 256ull << 20, rgs, &ix_ms[d], rg_bytes, rg_n, &ctgs);
+            sw_proc_ctgs_located(handles[d], dc, ds, df, a, 256ull << 20, rgs, &ix_ms[d], rg_bytes, rg_n, &ctgs, rg_files);
         for (size_t k = 0; k < where.size(); ++k) out[where[k]] = std::move(rows[k]);
     });
     if (index_ms) *index_ms = *std::max_element(ix_ms.begin(), ix_ms.end());
@@ -1057,17 +1057,20 @@ struct RgIndex {
 };
 void sw_rg_index(RgIndex &out, const std::vector<Ctg> &ctgs, const std::vector<std::vector<Feature>> &features,
                  const std::map<std::string, std::vector<Range>> *rgs, double *index_ms, const char *rg_bytes = nullptr,
-                 size_t rg_n = 0, const std::vector<Ctg> *located_in = nullptr) {
-    if (!rgs && !rg_bytes) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
+                 size_t rg_n = 0, const std::vector<Ctg> *located_in = nullptr, const std::vector<FileBytes> *rg_files = nullptr) {
+    if (!rgs && !rg_bytes && !rg_files) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
     const auto t0 = std::chrono::steady_clock::now();
     out.group.assign(ctgs.size(), UINT32_MAX);
-    if (rg_bytes) {
+    if (rg_bytes || rg_files) {
         std::vector<Ctg> table;                                          // a ctg given twice is one ctg of the table
         std::set<std::string> ids;
         for (const Ctg &c : located_in ? *located_in : ctgs)
             if (ids.insert(c.id).second) table.push_back(c);
         out.loc.reset(new Locator(out.h, table));
-        out.loc->set_rg_index_text(rg_bytes, rg_n);
+        if (rg_files)
+            out.loc->set_rg_index_text(*rg_files);
+        else
+            out.loc->set_rg_index_text(rg_bytes, rg_n);
         out.ix = out.loc->rg_index();
         std::set<std::string> told;
         for (size_t c = 0; c < ctgs.size(); ++c) {
@@ -1110,8 +1113,8 @@ void sw_rg_index(RgIndex &out, const std::vector<Ctg> &ctgs, const std::vector<s
 
 std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const std::vector<Feature> &features,
                         const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes,
-                        size_t rg_n) {
-    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+                        size_t rg_n, const std::vector<FileBytes> *rg_files) {
+    if (rgs && (rg_bytes || rg_files)) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     const uint32_t nf = (uint32_t)features.size();
     if (nf == 0) return std::string();
     uint32_t len = (uint32_t)(ctg.chr_end - ctg.chr_start + 1);
@@ -1132,7 +1135,7 @@ std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const
     if (!(a.actions & GAMS_SW_COUNT)) return sw_format_rows(rows.data(), nrows, ctg, features, 8, a.actions);
     // rg_count through the array entry (and this host formatter), the path sw_proc_ctgs falls back to
     RgIndex rx(h);
-    sw_rg_index(rx, std::vector<Ctg>{ctg}, std::vector<std::vector<Feature>>{features}, rgs, nullptr, rg_bytes, rg_n);
+    sw_rg_index(rx, std::vector<Ctg>{ctg}, std::vector<std::vector<Feature>>{features}, rgs, nullptr, rg_bytes, rg_n, nullptr, rg_files);
     const uint32_t zero = 0;
     const uint64_t feat_off[2] = {0, nf};
     std::vector<int32_t> cnt(nrows ? nrows : 1);
@@ -1147,16 +1150,16 @@ std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const
 std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                                       const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                       uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
-                                      double *index_ms, const char *rg_bytes, size_t rg_n) {
-    return sw_proc_ctgs_located(h, ctgs, seqs, features, a, batch_bytes, rgs, index_ms, rg_bytes, rg_n, nullptr);
+                                      double *index_ms, const char *rg_bytes, size_t rg_n, const std::vector<FileBytes> *rg_files) {
+    return sw_proc_ctgs_located(h, ctgs, seqs, features, a, batch_bytes, rgs, index_ms, rg_bytes, rg_n, nullptr, rg_files);
 }
 
 static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                                               const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                               uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
                                               double *index_ms, const char *rg_bytes, size_t rg_n,
-                                              const std::vector<Ctg> *located_in) {
-    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+                                              const std::vector<Ctg> *located_in, const std::vector<FileBytes> *rg_files) {
+    if (rgs && (rg_bytes || rg_files)) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs: ctgs / seqs / features size mismatch");
     std::vector<std::string> out(ctgs.size());
@@ -1165,7 +1168,7 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
         if (!features[c].empty()) todo.push_back(c);
     const bool do_count = (a.actions & GAMS_SW_COUNT) != 0;
     RgIndex rx(h);                                                      // -a count: the rgs of this call's ctgs, once
-    if (do_count && !todo.empty()) sw_rg_index(rx, ctgs, features, rgs, index_ms, rg_bytes, rg_n, located_in);
+    if (do_count && !todo.empty()) sw_rg_index(rx, ctgs, features, rgs, index_ms, rg_bytes, rg_n, located_in, rg_files);
     for (size_t b = 0; b < todo.size();) {
         uint64_t bytes = 0;
         size_t e = b;
@@ -1341,6 +1344,39 @@ void Locator::set_rg_index_text(const char *bytes, size_t n, bool *device) {
     const int rc = gams_index_create_range_text(h_, ctg_ix_, chr_names_, bytes, n, &ix, group.data(), &kept);
     if (rc == GAMS_EUNSUPPORTED) {                                       // the host passes over the lines
         set_rg_index(read_range(*this, text_lines(bytes, n)));
+        return;
+    }
+    check(h_, rc);
+    if (rg_ix_) gams_index_destroy(h_, rg_ix_);
+    rg_ix_ = ix;
+    rg_group_.clear();
+    for (size_t i = 0; i < ctgs_.size(); ++i)
+        if (group[i] != UINT32_MAX) rg_group_[ctgs_[i].id] = group[i];
+    if (device) *device = true;
+}
+
+void Locator::set_rg_index_text(const std::vector<FileBytes> &files, bool *device) {
+    if (device) *device = false;
+    text_tables();
+    std::vector<const char *> fb;
+    std::vector<uint64_t> fn;
+    for (const FileBytes &f : files) {
+        fb.push_back(f.first);
+        fn.push_back(f.second);
+    }
+    gams_index_t *ix = nullptr;
+    std::vector<uint32_t> group(std::max<size_t>(ctgs_.size(), 1), UINT32_MAX);
+    uint64_t kept = 0;
+    const int rc = gams_index_create_range_files(h_, ctg_ix_, chr_names_, (uint32_t)files.size(), fb.data(), fn.data(), &ix,
+                                                 group.data(), &kept);
+    if (rc == GAMS_EUNSUPPORTED) {                                       // read_range per file, the buckets appended
+        std::map<std::string, std::vector<Range>> all;
+        for (const FileBytes &f : files)
+            for (auto &kv : read_range(*this, text_lines(f.first, f.second))) {
+                std::vector<Range> &b = all[kv.first];
+                b.insert(b.end(), kv.second.begin(), kv.second.end());
+            }
+        set_rg_index(all);
         return;
     }
     check(h_, rc);
@@ -1958,9 +1994,9 @@ std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::ve
 
 std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
                     const char *bytes, size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs,
-                    const char *rg_bytes, size_t rg_n, bool *device, const TextSink *sink) {
+                    const char *rg_bytes, size_t rg_n, bool *device, const TextSink *sink, const std::vector<FileBytes> *rg_files) {
     if (device) *device = false;
-    if (rgs && rg_bytes) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+    if (rgs && (rg_bytes || rg_files)) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
     const bool do_gc = (a.actions & GAMS_SW_GC) != 0, do_count = (a.actions & GAMS_SW_COUNT) != 0;
     auto done = [&](std::string &&rows) {                                // a finished string: into the sink, if there is one
         if (!sink) return std::move(rows);
@@ -1970,7 +2006,7 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *
     };
     if (do_gc && !seqset) throw Error(GAMS_EINVAL, "sw_text: --action gc needs a seqset");
     if (seqset && slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "sw_text: one seqset slot per ctg");
-    if (do_count && !rgs && !rg_bytes) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
+    if (do_count && !rgs && !rg_bytes && !rg_files) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
     Locator loc(h, ctgs);
     loc.text_tables();
     const size_t n_ctg = loc.ctgs_.size();
@@ -1980,7 +2016,9 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *
     if (seqset)
         for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
     if (do_count) {                                                      // idx:rg: on the call's ctg table, once
-        if (rg_bytes)
+        if (rg_files)
+            loc.set_rg_index_text(*rg_files);
+        else if (rg_bytes)
             loc.set_rg_index_text(rg_bytes, rg_n);
         else
             loc.set_rg_index(*rgs);
@@ -2089,11 +2127,11 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *
 
 std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
                     size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes,
-                    size_t rg_n, bool *device, const TextSink *sink) {
+                    size_t rg_n, bool *device, const TextSink *sink, const std::vector<FileBytes> *rg_files) {
     if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, "sw_text: ctgs / seqs size mismatch");
     if (!(a.actions & GAMS_SW_GC))                                       // nothing reads a base: nothing goes up
         return sw_text(h, ctgs, static_cast<gams_seqset_t *>(nullptr), std::vector<uint32_t>(), bytes, n, a, rgs, rg_bytes, rg_n,
-                       device, sink);
+                       device, sink, rg_files);
     std::vector<uint32_t> lens(std::max<size_t>(ctgs.size(), 1), 0), slots(ctgs.size());
     for (size_t i = 0; i < ctgs.size(); ++i) {
         lens[i] = (uint32_t)(ctgs[i].chr_end - ctgs[i].chr_start + 1);
@@ -2102,7 +2140,7 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vect
     SeqSetGuard sg{h};
     check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
     check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
-    return sw_text(h, ctgs, sg.s, slots, bytes, n, a, rgs, rg_bytes, rg_n, device, sink);
+    return sw_text(h, ctgs, sg.s, slots, bytes, n, a, rgs, rg_bytes, rg_n, device, sink, rg_files);
 }
 
 namespace {
@@ -2208,29 +2246,110 @@ std::string tsv_records(const std::vector<Record> &records, bool features) {
     return out;
 }
 
-std::vector<Record> rg_records(Locator &loc, const std::vector<std::string> &lines) {
+namespace {
+std::string rg_json(const std::string &id, const Range &r) {
+    return "{\"id\":\"" + json_escape(id) + "\",\"range\":\"" + json_escape(r.to_string()) + "\"}";
+}
+std::string feature_json(const std::string &id, const Range &r, const std::string &tag) {            // feature.rs:85-92
+    return "{\"id\":\"" + json_escape(id) + "\",\"range\":\"" + json_escape(r.to_string()) + "\",\"length\":" +
+           std::to_string(r.end - r.start + 1) + ",\"tag\":\"" + json_escape(tag) + "\"}";
+}
+// the records of one file: the kept ranges of every ctg (BTreeMap order = ctg id order) numbered behind cnt[ctg]
+template <typename Json>
+std::vector<Record> loader_records(Locator &loc, const std::vector<std::string> &lines, const char *kind,
+                                   std::map<std::string, int32_t> &cnt, Json json) {
     std::vector<Record> out;
-    for (auto &kv : read_range(loc, lines)) {                           // BTreeMap order = ctg id order
-        int32_t serial = 0;
+    for (auto &kv : read_range(loc, lines)) {
+        if (kv.second.empty()) continue;
+        int64_t serial = cnt[kv.first];
         for (const Range &r : kv.second) {
-            const std::string id = "rg:" + kv.first + ":" + std::to_string(++serial);   // rg.rs:64-66
-            out.push_back({id, "{\"id\":\"" + json_escape(id) + "\",\"range\":\"" + json_escape(r.to_string()) + "\"}"});
+            if (++serial > INT32_MAX) throw Error(GAMS_EINVAL, "loader: a serial beyond INT32_MAX");
+            const std::string id = std::string(kind) + ":" + kv.first + ":" + std::to_string(serial);   // rg.rs:64-66, feature.rs:81-83
+            out.push_back({id, json(id, r)});
         }
+        cnt[kv.first] = (int32_t)serial;
     }
     return out;
 }
+}  // namespace
+
+std::vector<Record> rg_records(Locator &loc, const std::vector<std::string> &lines, std::map<std::string, int32_t> &cnt) {
+    return loader_records(loc, lines, "rg", cnt, [](const std::string &id, const Range &r) { return rg_json(id, r); });
+}
+
+std::vector<Record> feature_records(Locator &loc, const std::vector<std::string> &lines, const std::string &tag,
+                                    std::map<std::string, int32_t> &cnt) {
+    return loader_records(loc, lines, "feature", cnt, [&](const std::string &id, const Range &r) { return feature_json(id, r, tag); });
+}
+
+std::vector<Record> rg_records(Locator &loc, const std::vector<std::string> &lines) {
+    std::map<std::string, int32_t> fresh;                               // serials from 1 (a fresh cnt:rg:)
+    return rg_records(loc, lines, fresh);
+}
 
 std::vector<Record> feature_records(Locator &loc, const std::vector<std::string> &lines, const std::string &tag) {
-    std::vector<Record> out;
-    for (auto &kv : read_range(loc, lines)) {
-        int32_t serial = 0;
-        for (const Range &r : kv.second) {
-            const std::string id = "feature:" + kv.first + ":" + std::to_string(++serial);   // feature.rs:81-83
-            out.push_back({id, "{\"id\":\"" + json_escape(id) + "\",\"range\":\"" + json_escape(r.to_string()) +
-                                   "\",\"length\":" + std::to_string(r.end - r.start + 1) + ",\"tag\":\"" +
-                                   json_escape(tag) + "\"}"});                               // feature.rs:85-92
+    std::map<std::string, int32_t> fresh;
+    return feature_records(loc, lines, tag, fresh);
+}
+
+LoaderText loader_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<FileBytes> &files, int kind,
+                       const std::string &tag, int format, const std::map<std::string, int32_t> &serial_base, bool *device) {
+    if (device) *device = false;
+    if ((kind != GAMS_LOADER_RG && kind != GAMS_LOADER_FEATURE) ||
+        (format != GAMS_LOADER_RECORDS && format != GAMS_LOADER_TSV && format != GAMS_LOADER_RESP))
+        throw Error(GAMS_EINVAL, "loader_text: unknown kind or format");
+    Locator loc(h, ctgs);
+    loc.text_tables();
+    const size_t n_ctg = loc.ctgs_.size(), n_files = files.size();
+    LoaderText out;
+    out.n_in_file.assign(n_files, 0);
+    std::vector<int32_t> base(std::max<size_t>(n_ctg, 1), 0), next(std::max<size_t>(n_ctg, 1), 0);
+    for (size_t i = 0; i < n_ctg; ++i) {
+        auto it = serial_base.find(loc.ctgs_[i].id);
+        if (it != serial_base.end()) base[i] = it->second;
+        if (base[i] < 0) throw Error(GAMS_EINVAL, "loader_text: a negative serial_base");
+    }
+    std::vector<const char *> fb;
+    std::vector<uint64_t> fn;
+    for (const FileBytes &f : files) {
+        fb.push_back(f.first);
+        fn.push_back(f.second);
+    }
+    const char *text = nullptr;
+    uint64_t tbytes = 0, rows = 0;
+    std::vector<uint64_t> toff(n_files * n_ctg + 1, 0);
+    const int rc = gams_gpu_loader_text(h, loc.ctg_ix_, loc.chr_names_, loc.ctg_ids_, (uint32_t)n_files, fb.data(), fn.data(), kind,
+                                        tag.data(), tag.size(), format, base.data(), &text, &tbytes, toff.data(), next.data(),
+                                        out.n_in_file.data(), &rows);
+    if (rc == GAMS_OK) {
+        // the reference's SET order: file by file, the ctgs by id
+        out.text.reserve(tbytes);
+        for (size_t f = 0; f < n_files; ++f)
+            for (auto &kv : loc.ctg_slot_) {
+                const size_t b = f * n_ctg + kv.second;
+                out.text.append(text + toff[b], text + toff[b + 1]);
+            }
+        for (size_t i = 0; i < n_ctg; ++i) out.serial_next[loc.ctgs_[i].id] = next[i];
+        if (device) *device = true;
+        return out;
+    }
+    if (rc != GAMS_EUNSUPPORTED) check(h, rc);
+    // the host's passes, file after file, the counters carried on
+    std::map<std::string, int32_t> cnt;
+    for (size_t i = 0; i < n_ctg; ++i) cnt[loc.ctgs_[i].id] = base[i];
+    for (size_t f = 0; f < n_files; ++f) {
+        const std::vector<std::string> lines = text_lines(files[f].first, files[f].second);
+        const std::vector<Record> recs = kind == GAMS_LOADER_FEATURE ? feature_records(loc, lines, tag, cnt) : rg_records(loc, lines, cnt);
+        out.n_in_file[f] = recs.size();
+        if (format == GAMS_LOADER_TSV) {
+            const std::string t = tsv_records(recs, kind == GAMS_LOADER_FEATURE);
+            out.text.append(t, t.find('\n') + 1, std::string::npos);     // without the header
+        } else {
+            for (const Record &r : recs)
+                out.text += format == GAMS_LOADER_RESP ? wire::resp_command({"SET", r.key, r.json}) : r.key + "\t" + r.json + "\n";
         }
     }
+    out.serial_next = cnt;
     return out;
 }
 

@@ -129,6 +129,9 @@ void cover_multi(const std::vector<gams_gpu_t *> &handles, uint32_t n_groups, co
                  const int32_t *lo, const int32_t *hi, const uint32_t *q_group, const int32_t *clip_lo,
                  const int32_t *clip_hi, const int32_t *qs, const int32_t *qe, uint64_t nq, float *prop);
 
+// the bytes of one input file of a load that takes several (`gams rg f1 f2 ...`): not NUL-terminated
+using FileBytes = std::pair<const char *, size_t>;
+
 // sw.rs:108-194.  With GAMS_SW_COUNT in a.actions, `rgs` (what read_range returns: the rg ranges of each ctg id) is
 // the idx:rg: source; each call builds the device index of its own ctgs once.  A ctg without an entry in `rgs` counts
 // 0 and is reported once on stderr ("{ctg} not found in idx", utils.rs:30 -- the reference says it once per window).
@@ -138,9 +141,11 @@ void cover_multi(const std::vector<gams_gpu_t *> &handles, uint32_t n_groups, co
 // sees one ctg, so a range that spans a ctg boundary, which the whole table gives to the ctg in front, lands in this
 // ctg's bucket (and may be the line drop-first swallows); a host whose ranges can cross ctgs calls sw_proc_ctgs /
 // sw_proc_ctgs_multi with every ctg, or keeps `rgs` from a read_range over the whole table.
+// Several rg files loaded one after another (`gams rg f1 f2 ...`) are given as rg_files, a third form of the same source
+// (Locator::set_rg_index_text over several files), for these operators and for sw_text.
 std::string sw_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const std::vector<Feature> &features,
                         const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                        const char *rg_bytes = nullptr, size_t rg_n = 0);
+                        const char *rg_bytes = nullptr, size_t rg_n = 0, const std::vector<FileBytes> *rg_files = nullptr);
 // several ctgs on one handle: one seqset, one gams_gpu_sw_batch call and one readback per batch of
 // <= batch_bytes bases; rows returned per ctg in the order given ("" for a ctg without features).
 // index_ms (may be NULL) receives the ms of the rg index build (-a count).
@@ -148,7 +153,8 @@ std::vector<std::string> sw_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctg
                                       const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                       uint64_t batch_bytes = 256ull << 20,
                                       const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                                      double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0);
+                                      double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0,
+                                      const std::vector<FileBytes> *rg_files = nullptr);
 // `gams sw --parallel` over several devices: ctgs split over the handles by LPT on their feature
 // counts, one host thread per handle, rows returned per ctg in the order given.  Each handle indexes the rgs of the
 // ctgs it was given; index_ms = the longest of those builds.  With rg_bytes every handle loads the file against ALL ctgs
@@ -157,7 +163,8 @@ std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &han
                                             const std::vector<const uint8_t *> &seqs,
                                             const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                             const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                                            double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0);
+                                            double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0,
+                                            const std::vector<FileBytes> *rg_files = nullptr);
 
 // what read_range_text returns: the buckets of read_range as arrays.  Bucket k belongs to ctg ids[k] (ctg-id order, the
 // order of the reference's BTreeMap; a ctg with one located line has a bucket, and it is empty) and holds
@@ -168,6 +175,8 @@ struct RangeBuckets {
     std::vector<int32_t> start, end;
     std::vector<uint32_t> line;
 };
+
+struct LoaderText;
 
 // idx:ctg: / idx:rg: on the device (redis.rs:236-324) + the locate loop (locate.rs:111-141)
 class Locator {
@@ -181,6 +190,10 @@ public:
     // (GAMS_EUNSUPPORTED); *device (may be NULL) says which path built the index.  Only ctgs with a located line get a
     // group, as in the reference's map.
     void set_rg_index_text(const char *bytes, size_t n, bool *device = nullptr);
+    // ... from several rg files loaded one after another, as `gams rg f1 f2 ...` loads them (rg.rs:40): drop-first is per
+    // file, a ctg's ranges from all files share its group (gams_index_create_range_files).  Where the device refuses,
+    // read_range runs per file and the buckets are appended.
+    void set_rg_index_text(const std::vector<FileBytes> &files, bool *device = nullptr);
     // the rg index (NULL before one is set; owned by the Locator) and the group of a ctg id in it (UINT32_MAX: none)
     gams_index_t *rg_index() const { return rg_ix_; }
     uint32_t rg_group_of(const std::string &ctg_id) const;
@@ -210,12 +223,15 @@ public:
     std::string locate_seq_text(const char *bytes, size_t n, const std::vector<const uint8_t *> &seqs, bool *device = nullptr);
     const Ctg *ctg(const std::string &id) const;
     friend RangeBuckets read_range_text(Locator &loc, const char *bytes, size_t n, bool *device);
+    friend LoaderText loader_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<FileBytes> &files, int kind,
+                                  const std::string &tag, int format, const std::map<std::string, int32_t> &serial_base,
+                                  bool *device);
     friend std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                                  const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device);
     friend std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                                const std::vector<uint32_t> &slots, const char *bytes, size_t n, const SwArgs &a,
                                const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes, size_t rg_n,
-                               bool *device, const std::function<char *(size_t)> *sink);
+                               bool *device, const std::function<char *(size_t)> *sink, const std::vector<FileBytes> *rg_files);
 
 private:
     gams_gpu_t *h_;
@@ -302,13 +318,15 @@ std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t
 using TextSink = std::function<char *(size_t)>;
 std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
                     size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                    const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr);
+                    const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr,
+                    const std::vector<FileBytes> *rg_files = nullptr);
 // ... on a resident seqset (a host that holds the seqset of gen_text): slots[i] = the seqset slot that holds ctgs[i],
 // UINT32_MAX if none does (features in such a ctg are an error under GAMS_SW_GC).  Without GAMS_SW_GC seqset may be NULL
 // (slots is then not looked at).
 std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
                     const char *bytes, size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                    const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr);
+                    const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr,
+                    const std::vector<FileBytes> *rg_files = nullptr);
 
 // src/cmd_gams/rg.rs:41-77 / feature.rs:47-95: the records the loaders SET, as (key, JSON) pairs in
 // the reference's order (ctg id order, then file order), serials from 1 per ctg (a fresh cnt:).
@@ -332,6 +350,26 @@ std::string tsv_ctgs(const std::vector<Ctg> &ctgs);
 std::string tsv_records(const std::vector<Record> &records, bool features);
 std::vector<Record> rg_records(Locator &loc, const std::vector<std::string> &lines);
 std::vector<Record> feature_records(Locator &loc, const std::vector<std::string> &lines, const std::string &tag);
+// ... on a store that already holds records: cnt[ctg id] is cnt:rg:{ctg} / cnt:feature:{ctg} (absent: 0); the serials of
+// a ctg continue behind it and cnt is left at the counter after the load (incr_sn_n, rg.rs:63-75), ready for the next file
+std::vector<Record> rg_records(Locator &loc, const std::vector<std::string> &lines, std::map<std::string, int32_t> &cnt);
+std::vector<Record> feature_records(Locator &loc, const std::vector<std::string> &lines, const std::string &tag,
+                                    std::map<std::string, int32_t> &cnt);
+
+// `gams rg f1 f2 ...` (kind GAMS_LOADER_RG) / `gams feature --tag T f1 f2 ...` (GAMS_LOADER_FEATURE) over the bytes of the
+// files: the records the loader would SET, as text in `format` (GAMS_LOADER_RECORDS: "{key}\t{json}\n"; GAMS_LOADER_TSV: the
+// rows of tsv_records without the header; GAMS_LOADER_RESP: wire::resp_command({"SET", key, json}) of every record), in
+// the reference's order: file by file, the ctgs by id, file order inside a ctg.  serial_base[ctg id] is the ctg's counter
+// before the load (absent: 0).  Made on the device (gams_gpu_loader_text); where it refuses (GAMS_EUNSUPPORTED) the
+// lines of every file go through rg_records / feature_records with the counters carried on; *device says which.
+struct LoaderText {
+    std::string text;
+    std::map<std::string, int32_t> serial_next;   // the counter of every ctg of the call after the load
+    std::vector<uint64_t> n_in_file;              // records per file ("There are N rgs in this file")
+};
+LoaderText loader_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<FileBytes> &files, int kind,
+                       const std::string &tag, int format, const std::map<std::string, int32_t> &serial_base = {},
+                       bool *device = nullptr);
 
 // gen.rs:81-157 for one chromosome: ambiguous-base scan (device), fill, excise, --piece split;
 // ctg ids "ctg:{chr}:{serial}" with serial from 1 (gen.rs:133-134).  `seq` is the whole chromosome.

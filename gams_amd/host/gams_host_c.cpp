@@ -114,6 +114,13 @@ std::map<std::string, std::vector<gams::Range>> rg_index_of(uint32_t n, const ch
     return rg_of;
 }
 
+// several files given as arrays of pointers and lengths (a NULL pointer with length 0 is an empty file)
+std::vector<gams::FileBytes> files_of(uint32_t n, const char *const *data, const uint64_t *len) {
+    std::vector<gams::FileBytes> v(n);
+    for (uint32_t i = 0; i < n; ++i) v[i] = gams::FileBytes(data[i] ? data[i] : "", (size_t)len[i]);
+    return v;
+}
+
 std::map<std::string, gams::Runlist> runlists_of(const char *runlists) {
     std::map<std::string, gams::Runlist> sets;
     for (const std::string &ln : split_lines(runlists)) {
@@ -423,6 +430,36 @@ char *gams_host_locate_text_rg(gams_gpu_t *h, uint32_t n, const char *const *ids
     });
 }
 
+// ... and with several rg files loaded one after another (`gams rg f1 f2 ...`): n_rg files, rg_data[f] of rg_n[f] bytes
+char *gams_host_locate_rgs(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                           const int32_t *ends, const char *rgs, int is_count, uint32_t n_rg, const char *const *rg_data,
+                           const uint64_t *rg_n) {
+    return guarded([&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        if (is_count) loc.set_rg_index_text(files_of(n_rg, rg_data, rg_n));
+        const std::vector<std::string> lines = split_lines(rgs);
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = loc.locate(lines, is_count != 0);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return out;
+    });
+}
+char *gams_host_locate_text_rgs(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                                const int32_t *starts, const int32_t *ends, const char *bytes, uint64_t n_bytes, int is_count,
+                                uint32_t n_rg, const char *const *rg_data, const uint64_t *rg_n, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        gams::Locator loc(h, make_ctgs(n, ids, chrs, starts, ends));
+        if (is_count) loc.set_rg_index_text(files_of(n_rg, rg_data, rg_n));
+        loc.text_tables();
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = loc.locate_text(bytes, (size_t)n_bytes, is_count != 0, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        return out;
+    });
+}
+
 // Loads the rg index of a file over the ctg table and reports the ms of the load itself in gams_host_last_operator_ms:
 // text_path != 0 through Locator::set_rg_index_text (from the bytes in host memory to the finished index), else through
 // set_rg_index(read_range(text_lines(bytes))), the passes over strings.  gams_host_last_operator_device says which path
@@ -505,6 +542,34 @@ char *gams_host_sw_multi_actions_rg(gams_gpu_t *const *handles, uint32_t n_handl
                                              std::vector<const uint8_t *>(seqs, seqs + n), sw_feature_rows(n, features),
                                              sw_args(size, max, resize, actions), nullptr, nullptr, rg_data ? rg_data : "",
                                              (size_t)rg_n));
+    });
+}
+
+// ... with several rg files (as gams_host_locate_rgs takes them)
+char *gams_host_sw_actions_rgs(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
+                               const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
+                               const int32_t *fe, int32_t size, int32_t max, int32_t resize, uint32_t actions, uint32_t n_rg,
+                               const char *const *rg_data, const uint64_t *rg_n) {
+    return guarded([&] {
+        const char *ids[1] = {ctg_id}, *chrs[1] = {chr};
+        gams::Ctg c = make_ctgs(1, ids, chrs, &chr_start, &chr_end)[0];
+        std::vector<gams::Feature> f(nf);
+        for (uint32_t i = 0; i < nf; ++i) f[i] = gams::Feature{feature_ids[i], fs[i], fe[i]};
+        const std::vector<gams::FileBytes> files = files_of(n_rg, rg_data, rg_n);
+        return gams::sw_proc_ctg(h, c, seq, f, sw_args(size, max, resize, actions), nullptr, nullptr, 0, &files);
+    });
+}
+char *gams_host_sw_multi_actions_rgs(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n, const char *const *ids,
+                                     const char *const *chrs, const int32_t *starts, const int32_t *ends,
+                                     const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
+                                     int32_t resize, uint32_t actions, uint32_t n_rg, const char *const *rg_data,
+                                     const uint64_t *rg_n) {
+    return guarded([&] {
+        const std::vector<gams::FileBytes> files = files_of(n_rg, rg_data, rg_n);
+        return join(gams::sw_proc_ctgs_multi(std::vector<gams_gpu_t *>(handles, handles + n_handles),
+                                             make_ctgs(n, ids, chrs, starts, ends),
+                                             std::vector<const uint8_t *>(seqs, seqs + n), sw_feature_rows(n, features),
+                                             sw_args(size, max, resize, actions), nullptr, nullptr, nullptr, 0, &files));
     });
 }
 
@@ -632,10 +697,12 @@ char *gams_host_peak_text(gams_gpu_t *h, uint32_t n, const char *const *ids, con
 // without GAMS_SW_GC); else the resident seqset and slots[i] = its slot of ctg i (UINT32_MAX: none), seqs unused.  The
 // idx:rg: source of GAMS_SW_COUNT: rg_lines ("ctg_id\trange" rows, as gams_host_sw_multi_actions takes them; NULL: none)
 // or rg_data (the rg_n bytes of an rg file; NULL: none); both is GAMS_EINVAL.
-char *gams_host_sw_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
-                        const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
-                        const char *bytes, uint64_t n_bytes, int32_t size, int32_t max, int32_t resize, uint32_t actions,
-                        const char *rg_lines, const char *rg_data, uint64_t rg_n, uint64_t *out_len) {
+namespace {
+char *host_sw_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                   const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                   const char *bytes, uint64_t n_bytes, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                   const char *rg_lines, const char *rg_data, uint64_t rg_n, const std::vector<gams::FileBytes> *rg_files,
+                   uint64_t *out_len) {
     // the rows go straight into the buffer this call returns (gams::TextSink): no string in between
     struct Out {
         char *p = nullptr;
@@ -661,10 +728,10 @@ char *gams_host_sw_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const
         const auto t0 = std::chrono::steady_clock::now();
         if (seqset || !seqs)
             gams::sw_text(h, cv, seqset, seqset ? std::vector<uint32_t>(slots, slots + n) : std::vector<uint32_t>(), data,
-                          (size_t)n_bytes, a, rg_lines ? &rg_of : nullptr, rg_data, (size_t)rg_n, &dev, &sink);
+                          (size_t)n_bytes, a, rg_lines ? &rg_of : nullptr, rg_data, (size_t)rg_n, &dev, &sink, rg_files);
         else
             gams::sw_text(h, cv, std::vector<const uint8_t *>(seqs, seqs + n), data, (size_t)n_bytes, a,
-                          rg_lines ? &rg_of : nullptr, rg_data, (size_t)rg_n, &dev, &sink);
+                          rg_lines ? &rg_of : nullptr, rg_data, (size_t)rg_n, &dev, &sink, rg_files);
         g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         g_operator_device = dev ? 1 : 0;
         if (!out.p) (void)sink(0);
@@ -672,6 +739,46 @@ char *gams_host_sw_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const
         char *const p = out.p;
         out.p = nullptr;
         return p;
+    });
+}
+}  // namespace
+char *gams_host_sw_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                        const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                        const char *bytes, uint64_t n_bytes, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                        const char *rg_lines, const char *rg_data, uint64_t rg_n, uint64_t *out_len) {
+    return host_sw_text(h, n, ids, chrs, starts, ends, seqs, seqset, slots, bytes, n_bytes, size, max, resize, actions, rg_lines,
+                        rg_data, rg_n, nullptr, out_len);
+}
+// ... with several rg files as the idx:rg: source (as gams_host_locate_rgs takes them)
+char *gams_host_sw_text_rgs(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                            const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                            const char *bytes, uint64_t n_bytes, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                            uint32_t n_rg, const char *const *rg_data, const uint64_t *rg_n, uint64_t *out_len) {
+    const std::vector<gams::FileBytes> files = files_of(n_rg, rg_data, rg_n);
+    return host_sw_text(h, n, ids, chrs, starts, ends, seqs, seqset, slots, bytes, n_bytes, size, max, resize, actions, nullptr,
+                        nullptr, 0, &files, out_len);
+}
+
+// `gams rg f1 f2 ...` (kind 0) / `gams feature --tag T f1 f2 ...` (kind 1) over the bytes of the files (gams::loader_text):
+// the records as text in `format` (GAMS_LOADER_RECORDS / _TSV / _RESP), in the reference's SET order.  serial_base[i] (NULL:
+// all 0) = the counter of ctg i before the load; serial_next[i] and n_in_file[f] (either may be NULL) receive the counters
+// after it and the records of every file.
+char *gams_host_loader_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                            const int32_t *ends, uint32_t n_files, const char *const *data, const uint64_t *n_bytes, int kind,
+                            const char *tag, int format, const int32_t *serial_base, int32_t *serial_next, uint64_t *n_in_file,
+                            uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        std::map<std::string, int32_t> base;
+        for (uint32_t i = 0; i < n && serial_base; ++i) base[ids[i]] = serial_base[i];
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        gams::LoaderText r = gams::loader_text(h, make_ctgs(n, ids, chrs, starts, ends), files_of(n_files, data, n_bytes), kind,
+                                               tag ? tag : "", format, base, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        for (uint32_t i = 0; i < n && serial_next; ++i) serial_next[i] = r.serial_next.at(ids[i]);
+        for (uint32_t f = 0; f < n_files && n_in_file; ++f) n_in_file[f] = r.n_in_file[f];
+        return std::move(r.text);
     });
 }
 

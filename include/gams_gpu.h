@@ -27,6 +27,8 @@
  *   gams_gpu_anno_text        src/cmd_gams/anno.rs:95-142   (one input file: fields, extract_ctg_id, cover, rows)
  *   gams_gpu_peak_text        src/libs/utils.rs:83-116 read_peak + src/cmd_gams/peak.rs:41-160 (one wave TSV: fields,
  *                             find_one_idx, drop-first, sort by start, cache_gc_content, neighbours, the Peak rows)
+ *   gams_index_create_range_files, gams_gpu_loader_text: src/cmd_gams/rg.rs:40-82, feature.rs:47-96 (several files:
+ *                             read_range per file, the serials behind cnt:, the records' JSON / TSV / SET commands)
  *
  * Measurement and tuning entries (event stopwatch, phase stamps, guard-band and tile knobs, kernel
  * names) are NOT part of this surface: they live in gams_gpu_diag.h, which a host need not bind.
@@ -421,6 +423,51 @@ int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_nam
  * gams_index_destroy. */
 int gams_index_create_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const char *bytes,
                                  uint64_t n_bytes, gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept);
+
+/* ---- several files in one load: `gams rg f1 f2 ...` / `gams feature f1 f2 ...` (rg.rs:40, feature.rs:47) ---- */
+/* The two entries below take n_files files, file f = bytes[f][0 .. n_bytes[f]) (bytes[f] may be NULL where n_bytes[f] is
+ * 0), and load them as the reference does, one after another: lines are per file (a last line without '\n' ends at its
+ * file's end and never joins the next file's first line; an empty file has no lines), every line is parsed and located as
+ * above, and of the located lines of a ctg the first IN EACH FILE is dropped.  The kept lines of a ctg are ordered by
+ * (file, line).  No file, or one: exactly the load of zero bytes, or of that file's bytes.
+ * GAMS_EUNSUPPORTED as for the one-file entries -- a byte >= 0x80 or a NUL in any file, 2^32 - 1 lines in all, 2^32 - 16
+ * kept -- and for more than 2^24 (file, ctg) pairs, n_files * n_ctg (the tables by them). */
+/* The rg index of the load: group i = the kept ranges of ctg i from all files as [start, end + 1); rg_group as in
+ * gams_index_create_range_text (i if ctg i had a located line in any file).  With one file the result is that entry's. */
+int gams_index_create_range_files(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, uint32_t n_files,
+                                  const char *const *bytes, const uint64_t *n_bytes, gams_index_t **rg_ix, uint32_t *rg_group,
+                                  uint64_t *n_kept);
+
+#define GAMS_LOADER_RG 0      /* kind: the records of `gams rg` */
+#define GAMS_LOADER_FEATURE 1 /*       the records of `gams feature` (with length and tag) */
+#define GAMS_LOADER_RECORDS 0 /* format: "{id}\t{json}\n" */
+#define GAMS_LOADER_TSV 1     /*         the values of the record in field order, tab-separated (tsv.rs), no header */
+#define GAMS_LOADER_RESP 2    /*         "*3\r\n$3\r\nSET\r\n${len(id)}\r\n{id}\r\n${len(json)}\r\n{json}\r\n" */
+/* The records the loaders SET (rg.rs:62-82, feature.rs:73-96), as text written on the device.  ctg_ix, chr_names, ctg_ids
+ * as for gams_gpu_locate_text; tag (tag_bytes bytes, no NUL needed) is used by GAMS_LOADER_FEATURE only.
+ * serial_base[i] (NULL: all 0) is cnt:{kind}:{ctg i} before the load, i an interval of ctg_ix in the caller's order; the
+ * k-th kept line (from 1) of ctg i in (file, line) order gets serial serial_base[i] + k, which is what incr_sn_n and
+ * `serial - cnt` give over successive files; serial_next[i] (serial_next may be NULL) is the counter after the load.  A
+ * negative base, or a serial beyond INT32_MAX, is GAMS_EINVAL.
+ * id = "{rg|feature}:{ctg_id}:{serial}".  range = Range::to_string() of the parsed line -- "name." if the name is not
+ * empty, the chromosome, "(strand)" if not empty, ':', start, and "-end" only when end != start --, canonical and not
+ * echoed ("I:007_9 " prints "I:7-9").  json = {"id":"..","range":".."} or, for a feature,
+ * {"id":"..","range":"..","length":N,"tag":".."} with N = end - start + 1 as a signed i32 (data.rs:16-28, serde's field
+ * order).  Inside the JSON '"' and '\' get a backslash; nowhere else.
+ * Rows are grouped by (file, interval of ctg_ix in the caller's order), in line order inside a group: those of file f and
+ * interval i are text[text_off[f * n_ctg + i] .. text_off[f * n_ctg + i + 1]) (text_off has n_files * n_ctg + 1 entries; a
+ * host that prints file by file with the ctgs in id order has the reference's SET order).  n_in_file[f] (may be NULL)
+ * counts the kept lines of file f, *n_rows all of them.  *text (text_bytes bytes, no NUL) is page-locked memory of this
+ * entry's own on the handle, valid until its next call.  Two calls return identical text.  No file, only empty files or
+ * nothing kept: GAMS_OK, no rows, text_off all zero, serial_next = serial_base.
+ * GAMS_EUNSUPPORTED (run the host path) as above, and: a kept line whose name or strand holds a byte < 0x20 (serde_json
+ * escapes those) or 2^30 bytes; a tag with a byte < 0x20 or >= 0x80, or of 2^30 bytes.  ctg ids are printed as given.
+ * gams_gpu_last_stage_ms then reports ten stages: the loader's lines, parse, locate, first, keep, offsets, order, then
+ * serials, row lengths, write (seven when nothing was kept; GAMS_ESTATE for an input without lines). */
+int gams_gpu_loader_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_names_t *chr_names, const gams_names_t *ctg_ids,
+                         uint32_t n_files, const char *const *bytes, const uint64_t *n_bytes, int kind, const char *tag,
+                         uint64_t tag_bytes, int format, const int32_t *serial_base, const char **text, uint64_t *text_bytes,
+                         uint64_t *text_off, int32_t *serial_next, uint64_t *n_in_file, uint64_t *n_rows);
 
 /* ---- text in, text out: peak (utils.rs:83-116 read_peak, then peak.rs:41-160) ---- */
 /* The bytes of ONE wave TSV ("{range}\t{gc_content}\t{signal}" rows; lines, refused bytes and the 2^32 - 1 line limit as
