@@ -8,12 +8,12 @@
 // upload and line index (the stages are listed in front of its kernels, below):
 //   gams_gpu_read_range_text       the ranges of one .rg file bucketed per ctg, as arrays
 //   gams_index_create_range_text   the rg index of the file and the ctg -> group table
-// and, on the loader itself (rg_load, each with a spec and a consumer of its own), `gams peak` (utils.rs:83-116 read_peak,
-// then peak.rs:41-160):
+// and, on the loader itself (rg_load, each with a spec and a consumer of its own, which takes the kept lines as an
+// RgKept), `gams peak` (utils.rs:83-116 read_peak, then peak.rs:41-160), its rows through the keyed row writer:
 //   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
 // and `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
 //   gams_gpu_sw_feature_text       the bytes of one range file -> the sw rows of its features (stages 2-5 in sw.hip)
-// and several files in one load (rg.rs:40, feature.rs:47: one read_range per file), on rg_load_in:
+// and several files in one load (rg.rs:40, feature.rs:47: one read_range per file), an RgInput of files:
 //   gams_index_create_range_files  the rg index of `gams rg f1 f2 ...`
 //   gams_gpu_loader_text           the records `gams rg` / `gams feature` SET, as "{id}\t{json}" rows, TSV or RESP
 // and `locate --seq` (locate.rs:124-134), behind the front of locate_text, with a writer of its own (a row may be a whole ctg):
@@ -66,26 +66,23 @@ struct gams_names {
     uint32_t max_len = 0;            // the longest name, in bytes (bounds a row that prints one)
 };
 
-// What the text entries keep on the handle: the device copy of the input (grows, cached) and the page-locked
-// text of each entry's last call.
+// The entries that own a text: each keeps the page-locked text of its last call in a slot of its own (gams_gpu.h: valid
+// until the next call of THAT entry; and a text of whole ctgs from locate --seq is not held by the others for good).
+enum TextSlot : int { TEXT_LOCATE = 0, TEXT_COUNT, TEXT_ANNO, TEXT_PEAK, TEXT_RECORDS, TEXT_SEQ, TEXT_SLOTS };
+
+// What the text entries keep on the handle: the device copy of the input (grows, cached) and the text slots.
 struct gams_text_state {
     uint8_t *d_in = nullptr;
     size_t d_in_cap = 0;
-    char *out[4] = {};          // locate, count, anno, peak (the records of the loaders: rec_out)
-    size_t out_cap[4] = {};
-    char *seq_out = nullptr;    // locate --seq: a buffer of its own (a text of whole ctgs would be held by the others for good)
-    size_t seq_out_cap = 0;
-    char *rec_out = nullptr;    // the loader's records (gams_gpu_loader_text)
-    size_t rec_out_cap = 0;
+    char *out[TEXT_SLOTS] = {};
+    size_t out_cap[TEXT_SLOTS] = {};
 };
 
 void gams_text_free(gams_gpu_t *h) {
     gams_text_state *t = h->text;
     if (!t) return;
     gams_pool_free(h, false, t->d_in, t->d_in_cap);
-    for (int k = 0; k < 4; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
-    gams_pool_free(h, true, t->seq_out, t->seq_out_cap);
-    gams_pool_free(h, true, t->rec_out, t->rec_out_cap);
+    for (int k = 0; k < TEXT_SLOTS; ++k) gams_pool_free(h, true, t->out[k], t->out_cap[k]);
     delete t;
     h->text = nullptr;
 }
@@ -130,6 +127,13 @@ enum : uint32_t {
     W_ENOSEQ = 7,  // peak: a kept peak in a ctg without a sequence
     W_COUNT = 8
 };
+
+// the words of the call in h->pin_scratch, once everything queued on the compute stream has run: one host wait
+hipError_t read_words(gams_gpu_t *h, const unsigned long long *d_words) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(h->pin_scratch, d_words, W_COUNT * 8, hipMemcpyDeviceToHost, h->compute);
+    return e == hipSuccess ? hipStreamSynchronize(h->compute) : e;
+}
 
 constexpr uint32_t kIdxBytes = 256u * 64u;   // bytes per workgroup of the line-index kernels
 
@@ -401,7 +405,7 @@ __global__ __launch_bounds__(256) void text_parse_anno_kernel(const TextLines t,
     keep[i] = 1;
 }
 
-enum : int { K_LOCATE = 0, K_COUNT = 1, K_ANNO = 2, K_PEAK = 3 };   // K_PEAK: the slot of its text only (peak_run)
+enum : int { K_LOCATE = TEXT_LOCATE, K_COUNT = TEXT_COUNT, K_ANNO = TEXT_ANNO };   // a kind of text_run is the slot of its text
 
 struct RowArgs {
     TextLines t;
@@ -515,9 +519,6 @@ struct TextJob {
 
 const char *const kEntry[3] = {"gpu_locate_text", "gpu_count_text", "gpu_anno_text"};
 
-// What steps 1 and 2 (pass 1) of every text entry leave behind: the input in the handle's cached device buffer, the
-// words, the '\n' count of every index block with its prefix, and the line count.  s0 is the pooled block behind the
-// three small arrays.
 // several input files of one load (the rg / feature loaders): n files, file f = bytes[f][0 .. n_bytes[f])
 struct TextFiles {
     uint32_t n;
@@ -525,6 +526,9 @@ struct TextFiles {
     const uint64_t *n_bytes;
 };
 
+// What steps 1 and 2 (pass 1) of every text entry leave behind: the input in the handle's cached device buffer, the
+// words, the '\n' count of every index block with its prefix, and the line count.  s0 is the pooled block behind the
+// three small arrays.
 struct TextFront {
     explicit TextFront(gams_gpu_t *h) : s0(h, false) {}
     PoolBlock s0;
@@ -690,9 +694,7 @@ int text_run(gams_gpu_t *h, const TextJob &J, const char *bytes, uint64_t n_byte
     hipLaunchKernelGGL(text_row_len_kernel, dim3(nbr), dim3(256), 0, st, ra);
     hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, c.blk_bytes, nbr, c.blk_off, d_words,
                        (uint32_t)W_BYTES);
-    GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    GAMS_TRY(h, who, read_words(h, d_words));
     const unsigned long long *w = h->pin_scratch;
     if (w[W_EFIELD]) return gams_fail(h, GAMS_EINVAL, who + ": field index out of range (the reference panics, anno.rs:115)");
     if (w[W_EID])
@@ -763,35 +765,6 @@ __global__ __launch_bounds__(256) void rg_parse_kernel(const TextLines t, const 
     qe[i] = r.end;
 }
 
-__global__ __launch_bounds__(256) void rg_first_kernel(uint32_t n_lines, const int64_t *hit, uint32_t *first) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const int64_t c = i < n_lines ? hit[i] : -1;
-    if (run_leader(c) && c >= 0) atomicMin(first + c, i);
-}
-
-__global__ __launch_bounds__(256) void rg_keep_kernel(uint32_t n_lines, uint32_t n_ctg, uint32_t line_bits, const int64_t *hit,
-                                                      const uint32_t *first, uint32_t *count, unsigned long long *key,
-                                                      const uint32_t *qs, uint32_t start_bits) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
-    const int64_t c = i < n_lines ? hit[i] : -1;
-    const bool keep = c >= 0 && first[c] != i;
-    const bool lead = run_leader(c);
-    const unsigned long long kept = __ballot(keep), leads = __ballot(lead);
-    if (lead && c >= 0) {
-        // the run is [lane, next leader): its kept lines, one add
-        const unsigned long long above = lane == 63u ? 0ull : leads & (~0ull << (lane + 1u));
-        const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
-        const unsigned long long run = (end == 64u ? ~0ull : (1ull << end) - 1ull) & (~0ull << lane);
-        const uint32_t n = (uint32_t)__popcll(kept & run);
-        if (n) atomicAdd(count + c, n);
-    }
-    // (qs: the start of a kept line goes between ctg and line, start_bits wide; the rg loader passes none)
-    if (i < n_lines)
-        key[i] = ((unsigned long long)(keep ? (uint32_t)c : n_ctg) << (start_bits + line_bits)) |
-                 ((unsigned long long)(qs && keep ? qs[i] : 0u) << line_bits) | i;
-}
-
 // ---- several files in one load (rg.rs:40, feature.rs:47: one read_range per file) ----
 // The files lie back to back in the input buffer (TextFront::files), every file beginning at a line start, so the line
 // numbers of the buffer rise with (file, line).  line0[f] = the first line of file f (n_files + 1 entries, the last one
@@ -832,62 +805,86 @@ __device__ __forceinline__ uint32_t rg_file_of(const RgFileTab &F, uint32_t i) {
     return lo;
 }
 
-__global__ __launch_bounds__(256) void rg_first_files_kernel(uint32_t n_lines, const int64_t *hit, const RgFileTab F, uint32_t *first) {
+// The run key of line i, located to ctg c (-1: not located): what first[] is indexed by and where a run of equal lanes
+// ends.  A load of one file (kFiles false) searches no file and reads nothing of F: the key is the ctg.
+template <bool kFiles>
+__device__ __forceinline__ int64_t rg_run_key(const RgFileTab &F, uint32_t i, int64_t c) {
+    if constexpr (kFiles)
+        return c >= 0 ? (int64_t)rg_file_of(F, i) * F.n_ctg + c : -1;
+    else
+        return c;
+}
+
+template <bool kFiles>
+__global__ __launch_bounds__(256) void rg_first_kernel(uint32_t n_lines, const int64_t *hit, const RgFileTab F, uint32_t *first) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const int64_t c = i < n_lines ? hit[i] : -1;
-    const int64_t b = c >= 0 ? (int64_t)rg_file_of(F, i) * F.n_ctg + c : -1;
+    const int64_t b = rg_run_key<kFiles>(F, i, i < n_lines ? hit[i] : -1);
     if (run_leader(b) && b >= 0) atomicMin(first + b, i);
 }
 
-// rg_keep_kernel with the runs and first[] by (file, ctg); by_file: so are count[] and the key's bucket, else the ctg is
-__global__ __launch_bounds__(256) void rg_keep_files_kernel(uint32_t n_lines, uint32_t n_bkt, uint32_t line_bits, const int64_t *hit,
-                                                            const RgFileTab F, uint32_t by_file, const uint32_t *first,
-                                                            uint32_t *count, unsigned long long *key) {
+// by_file (several files): count[] and the key's bucket are by (file, ctg) like the runs, else by ctg.  qs (one file): the
+// start of a kept line goes between bucket and line, mid_bits wide; the rg loader passes none.
+template <bool kFiles>
+__global__ __launch_bounds__(256) void rg_keep_kernel(uint32_t n_lines, uint32_t n_bkt, uint32_t line_bits, const int64_t *hit,
+                                                      const RgFileTab F, uint32_t by_file, const uint32_t *first, uint32_t *count,
+                                                      unsigned long long *key, const uint32_t *qs, uint32_t mid_bits) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t c = i < n_lines ? hit[i] : -1;
-    const int64_t b = c >= 0 ? (int64_t)rg_file_of(F, i) * F.n_ctg + c : -1;
+    const int64_t b = rg_run_key<kFiles>(F, i, c);
     const bool keep = b >= 0 && first[b] != i;
     const bool lead = run_leader(b);
     const unsigned long long kept = __ballot(keep), leads = __ballot(lead);
-    const uint32_t bucket = by_file ? (uint32_t)b : (uint32_t)c;
+    const uint32_t bucket = kFiles && by_file ? (uint32_t)b : (uint32_t)c;
     if (lead && b >= 0) {
+        // the run is [lane, next leader): its kept lines, one add
         const unsigned long long above = lane == 63u ? 0ull : leads & (~0ull << (lane + 1u));
         const uint32_t end = above ? (uint32_t)__builtin_ctzll(above) : 64u;
         const unsigned long long run = (end == 64u ? ~0ull : (1ull << end) - 1ull) & (~0ull << lane);
         const uint32_t n = (uint32_t)__popcll(kept & run);
         if (n) atomicAdd(count + bucket, n);
     }
-    if (i < n_lines) key[i] = ((unsigned long long)(keep ? bucket : n_bkt) << line_bits) | i;
+    const uint32_t mid = kFiles ? 0u : mid_bits;
+    if (i < n_lines)
+        key[i] = ((unsigned long long)(keep ? bucket : n_bkt) << (mid + line_bits)) |
+                 ((unsigned long long)(!kFiles && qs && keep ? qs[i] : 0u) << line_bits) | i;
 }
 
+// The kept lines of a load in key order, as the loader hands them to its consumer's kernels.  A key is taken apart here
+// and nowhere else.
+struct RgKept {
+    const unsigned long long *key;          // sorted: the first n_kept are the kept lines in (bucket[, start], line) order
+    uint16_t line_bits, mid_bits;           // the key: bucket << (mid_bits + line_bits) | start << line_bits | line
+    uint32_t n_kept;
+    const uint32_t *qs, *qe;                // per line
+    const unsigned long long *bucket_off;   // device, one per bucket and the end
+    __device__ __forceinline__ uint32_t line(uint32_t k) const { return (uint32_t)(key[k] & ((1ull << line_bits) - 1ull)); }
+    __device__ __forceinline__ uint32_t bucket(uint32_t k) const { return (uint32_t)(key[k] >> (mid_bits + line_bits)); }
+};
+
 struct RgGather {
-    const unsigned long long *key;       // sorted: the first n_kept are the kept lines in (ctg, line) order
-    unsigned long long line_mask;
-    const uint32_t *qs, *qe;
-    uint64_t n_kept;
+    RgKept v;
     uint32_t *start, *end, *line;        // end = the range's end + end_plus; line may be NULL
     uint32_t end_plus;
-    const unsigned long long *bucket_off;   // with off32: the n_off offsets narrowed for the index builder
-    uint32_t *off32;
+    uint32_t *off32;                     // not NULL: v.bucket_off, n_off of them, narrowed for the index builder
     uint64_t n_off;
 };
 
 __global__ __launch_bounds__(256) void rg_gather_kernel(const RgGather a) {
     const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (k < a.n_kept) {
-        const uint32_t i = (uint32_t)(a.key[k] & a.line_mask);
-        a.start[k] = a.qs[i];
-        a.end[k] = a.qe[i] + a.end_plus;
+    if (k < a.v.n_kept) {
+        const uint32_t i = a.v.line((uint32_t)k);
+        a.start[k] = a.v.qs[i];
+        a.end[k] = a.v.qe[i] + a.end_plus;
         if (a.line) a.line[k] = i;
     }
-    if (a.off32 && k < a.n_off) a.off32[k] = (uint32_t)a.bucket_off[k];
+    if (a.off32 && k < a.n_off) a.off32[k] = (uint32_t)a.v.bucket_off[k];
 }
 
 // what the loader hands its consumer while the scratch is alive
 struct RgCols {
     uint64_t n_ctg, n_kept;
-    // a load of one file: one bucket and one entry of first[] per ctg.  Of several files (rg_load_in): first[] has one
+    // a load of one file: one bucket and one entry of first[] per ctg.  Of several files (RgInput::files): first[] has one
     // entry per (file, ctg), file-major, and the buckets are the (file, ctg) pairs or the ctgs (RgInput::by_file)
     uint64_t n_files, n_bkt, n_first;
     const unsigned long long *bucket_off;   // host, n_bkt + 1
@@ -897,7 +894,7 @@ struct RgCols {
             if (first[f * n_ctg + ctg] != UINT32_MAX) return true;
         return false;
     }
-    RgGather g;                             // key, line_mask, qs, qe, n_kept, bucket_off (device) filled; n_kept == 0: nothing on the device
+    RgKept v;                               // the kept lines on the device; n_kept == 0: nothing there, all zero
     TextLines t;                            // the line index (device), with lines
     unsigned long long *words;              // device: the W_* words of the call
     bool ran;                               // the input had lines: the stages up to RG_OFFSETS (with `order` RG_ORDER) were queued and timed
@@ -922,10 +919,6 @@ struct RgPlain {
     }
 };
 
-// Runs the stages up to the sort (`order` false: up to the offsets, for a size query) as `spec` shapes them and calls
-// consume(cols, stage) -- stage(k, open) records the stopwatch event that opens or closes stage k -- which queues the
-// gather and whatever follows.  One host wait of its own besides text_front's, behind the offsets.  `who` names the entry
-// in error messages.
 // The input of a load: the bytes of one file, or `files` (then bytes / n_bytes are not looked at).  One file given as
 // `files` is loaded exactly as the bytes of one file are, and no file as zero bytes.  Several files are loaded as the
 // reference loads them one after another (RgFileTab, above): by_file says what the buckets are.  Refused beyond
@@ -938,9 +931,13 @@ struct RgInput {
 };
 constexpr uint64_t kRgMaxFileCtg = 1ull << 24;
 
+// Runs the stages up to the sort (`order` false: up to the offsets, for a size query) as `spec` shapes them and calls
+// consume(cols, stage) -- stage(k, open) records the stopwatch event that opens or closes stage k -- which queues the
+// gather and whatever follows.  One host wait of its own besides text_front's, behind the offsets.  `who` names the entry
+// in error messages.
 template <typename Spec, typename Consume>
-int rg_load_in(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, RgInput in, bool order,
-               Consume consume) {
+int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, RgInput in, bool order,
+            Consume consume) {
     if (in.files && in.files->n <= 1u) {
         in.bytes = in.files->n ? in.files->bytes[0] : nullptr;
         in.n_bytes = in.files->n ? in.files->n_bytes[0] : 0;
@@ -1042,18 +1039,12 @@ int rg_load_in(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix
     launch_interval_locate(ctg_ix, d_grp, d_qs, d_qe, L, d_hit, st);
     GAMS_TRY(h, who, stage(RG_LOCATE, false));
     GAMS_TRY(h, who, stage(RG_FIRST, true));
-    if (multi)
-        hipLaunchKernelGGL(rg_first_files_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, ftab, d_first);
-    else
-        hipLaunchKernelGGL(rg_first_kernel, dim3(nbr), dim3(256), 0, st, L, d_hit, d_first);
+    hipLaunchKernelGGL(multi ? rg_first_kernel<true> : rg_first_kernel<false>, dim3(nbr), dim3(256), 0, st, L, d_hit, ftab, d_first);
     GAMS_TRY(h, who, stage(RG_FIRST, false));
     GAMS_TRY(h, who, stage(RG_KEEP, true));
-    if (multi)
-        hipLaunchKernelGGL(rg_keep_files_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_bkt, line_bits, d_hit, ftab,
-                           in.by_file ? 1u : 0u, d_first, d_count, d_key);
-    else
-        hipLaunchKernelGGL(rg_keep_kernel, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_ctg, line_bits, d_hit, d_first, d_count, d_key,
-                           spec.mid_bits ? (const uint32_t *)d_qs : (const uint32_t *)nullptr, (uint32_t)spec.mid_bits);
+    hipLaunchKernelGGL(multi ? rg_keep_kernel<true> : rg_keep_kernel<false>, dim3(nbr), dim3(256), 0, st, L, (uint32_t)n_bkt,
+                       line_bits, d_hit, ftab, in.by_file ? 1u : 0u, d_first, d_count, d_key,
+                       spec.mid_bits ? (const uint32_t *)d_qs : (const uint32_t *)nullptr, (uint32_t)spec.mid_bits);
     GAMS_TRY(h, who, stage(RG_KEEP, false));
     GAMS_TRY(h, who, stage(RG_OFFSETS, true));
     hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, d_count, (uint32_t)n_bkt, d_off, F.d_words,
@@ -1072,21 +1063,13 @@ int rg_load_in(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix
     GAMS_TRY(h, who, stage(RG_ORDER, true));
     if (C.n_kept) GAMS_TRY(h, who, rocprim::radix_sort_keys(d_sort, sort_bytes, d_key, d_key2, (size_t)L, 0u, key_bits, st));
     GAMS_TRY(h, who, stage(RG_ORDER, false));
-    if (C.n_kept) {
-        C.g.key = d_key2;
-        C.g.line_mask = (1ull << line_bits) - 1ull;
-        C.g.qs = d_qs;
-        C.g.qe = d_qe;
-        C.g.n_kept = C.n_kept;
-        C.g.bucket_off = d_off;
-    }
+    if (C.n_kept) C.v = RgKept{d_key2, (uint16_t)line_bits, (uint16_t)spec.mid_bits, (uint32_t)C.n_kept, d_qs, d_qe, d_off};
     return consume(C, stage);
 }
 
-template <typename Spec, typename Consume>
-int rg_load(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_ix, Spec &&spec, const char *bytes, uint64_t n_bytes,
-            bool order, Consume consume) {
-    return rg_load_in(h, who, ctg_ix, spec, RgInput{bytes, n_bytes, nullptr, false}, order, consume);
+// slot `slot` of the seqset holds a sequence of the length of a ctg at [chr_start, chr_end] (UINT32_MAX names no slot)
+bool seq_slot_holds(const gams_seqset_t *s, uint32_t slot, int32_t chr_start, int32_t chr_end) {
+    return slot < s->n_ctg && (int64_t)s->len[slot] == (int64_t)chr_end - chr_start + 1;
 }
 
 // the stopwatch of a loader call whose input had lines: stages [0, n) of the handle's timed pairs were recorded (an
@@ -1098,8 +1081,120 @@ void rg_timed(gams_gpu_t *h, int n) {
 }
 
 
+// ---- the keyed row writer: one row per kept line, in key order, and where the rows of every bucket begin --------------
+// Behind a consumer's own gather, two stages and two host waits:
+//   rows     one lane per kept line k: the row is measured (or refused: nothing is measured, W_UNSUP is set) and its length
+//            stored; the sums of the blocks of 256 rows and their prefix; the words are read back, the consumer's refusals
+//            end the call here;
+//   write    the rows at their offsets -- a block's rows composed in LDS and copied out in 16-B units, or written straight to
+//            global memory when they exceed the stage (BlockWriter) -- and, by the lane that opens it, the offset of every
+//            bucket's first row.  Never launched after a refusal: every row it writes was measured.
+// A consumer describes its rows in a struct D:
+//   Args     its kernel arguments, with the kept lines as `v` (RgKept) and this writer's part as `o` (KeyedText<Len>);
+//   Len      the type of a row's length;
+//   kStage   bytes of the LDS stage;
+//   row<kWrite>(a, k, out, bad)   composes row k into a RowOut; bad: a value it has no text for;
+//   bucket(a, k)                  the bucket of row k;
+//   refused(a, k)                 device: row k cannot be written at all;
+//   check(h, who, w)              host: GAMS_OK, or the failure the words w of the rows stage ask for.
+template <typename Len>
+struct KeyedText {
+    Len *row_len;                         // per kept line
+    unsigned long long *blk_bytes;        // per workgroup of 256 rows
+    unsigned long long *blk_off;
+    unsigned long long *text_off;         // per bucket with rows: the offset of its first row
+    unsigned long long *words;
+    char *text;
+    void carve(Carver &c, uint32_t n_kept) {   // row lengths | the blocks' bytes and prefix
+        const size_t nbk = (n_kept + 255u) / 256u;
+        row_len = c.take<Len>(n_kept);
+        blk_bytes = c.take<unsigned long long>(nbk + 1);
+        blk_off = c.take<unsigned long long>(nbk + 1);
+    }
+};
+
+template <typename D>
+__global__ __launch_bounds__(256) void keyed_row_len_kernel(const typename D::Args a) {
+    __shared__ uint64_t ws[4];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    bool bad = false;
+    RowOut<false, typename D::Len> n;
+    if (k < a.v.n_kept) {
+        if (D::refused(a, k))
+            a.o.words[W_UNSUP] = 1ull;
+        else
+            D::template row<false>(a, k, n, bad);
+        a.o.row_len[k] = n.n;
+    }
+    if (bad) a.o.words[W_UNSUP] = 1ull;
+    uint64_t tot;
+    (void)block_excl_scan_256<uint64_t>((uint64_t)n.n, ws, tot);
+    if (threadIdx.x == 0) a.o.blk_bytes[blockIdx.x] = tot;
+}
+
+template <typename D>
+__global__ __launch_bounds__(256) void keyed_row_write_kernel(const typename D::Args a) {
+    __shared__ uint64_t ws[4];
+    __shared__ __align__(16) char stage[D::kStage + 16];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t l = k < a.v.n_kept ? a.o.row_len[k] : 0ull;
+    BlockWriter<uint64_t> w(l, ws, a.o.blk_off, a.o.text, ~0ull);   // (the text holds all rows: no bound)
+    w.stage_if(w.tot <= D::kStage, stage);
+    if (k < a.v.n_kept) {
+        const uint32_t b = D::bucket(a, k);
+        if (k == (uint32_t)a.v.bucket_off[b]) a.o.text_off[b] = w.blk0 + w.rel;
+        bool bad = false;                      // (the length pass flagged what has no text: nothing is written then)
+        w.put(w.rel, [&](char *p) {
+            RowOut<true, typename D::Len> o{p};
+            D::template row<true>(a, k, o, bad);
+        });
+    }
+    w.flush();
+}
+
+// The two stages, rows_stage and the one behind it, over the arguments `a` the consumer has filled but for o.text; the
+// text into the entry's slot, text_off (one per bucket of the load and the end) through the page-locked h_toff.
+template <typename D>
+int keyed_text_run(gams_gpu_t *h, const std::string &who, const RgCols &C, const StageClock &stage, int rows_stage,
+                   typename D::Args &a, TextSlot slot, unsigned long long *h_toff, const char **text, uint64_t *text_bytes,
+                   uint64_t *text_off, uint64_t *n_rows) {
+    hipStream_t st = h->compute;
+    const uint32_t nbk = (a.v.n_kept + 255u) / 256u;
+    GAMS_TRY(h, who, stage(rows_stage, true));
+    hipLaunchKernelGGL(keyed_row_len_kernel<D>, dim3(nbk), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.o.blk_bytes, nbk, a.o.blk_off,
+                       a.o.words, (uint32_t)W_BYTES);
+    GAMS_TRY(h, who, stage(rows_stage, false));
+    GAMS_TRY(h, who, read_words(h, a.o.words));
+    const int rc = D::check(h, who, h->pin_scratch);
+    if (rc != GAMS_OK) return rc;
+    const uint64_t tb = h->pin_scratch[W_BYTES];
+    gams_text_state *T = h->text;
+    PoolBlock d_text(h, false);
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &T->out[slot], &T->out_cap[slot], tb, tb));
+    GAMS_TRY(h, who, d_text.alloc(tb));
+    a.o.text = reinterpret_cast<char *>(d_text.p);
+    GAMS_TRY(h, who, stage(rows_stage + 1, true));
+    hipLaunchKernelGGL(keyed_row_write_kernel<D>, dim3(nbk), dim3(256), 0, st, a);
+    GAMS_TRY(h, who, stage(rows_stage + 1, false));
+    GAMS_TRY(h, who, hipGetLastError());
+    GAMS_TRY(h, who, hipMemcpyAsync(T->out[slot], d_text.p, tb, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipMemcpyAsync(h_toff, a.o.text_off, (C.n_bkt + 1) * 8, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    // a bucket without rows begins where the next one does
+    text_off[C.n_bkt] = tb;
+    for (uint64_t b = C.n_bkt; b-- > 0;) text_off[b] = C.bucket_off[b + 1] > C.bucket_off[b] ? h_toff[b] : text_off[b + 1];
+    rg_timed(h, rows_stage + 2);
+    *text = T->out[slot];
+    *text_bytes = tb;
+    *n_rows = C.n_kept;
+    return GAMS_OK;
+}
+
+
 // ---- `gams peak` on the device (utils.rs:83-116 read_peak, then peak.rs:41-160): the bytes of a wave TSV -> Peak rows --
-// The range loader itself (rg_load with the PeakLoad spec), then three stages of its own; ten stages in all:
+// The range loader itself (rg_load with the PeakLoad spec), then a stage of its own and the two of the keyed row writer
+// (PeakRows); ten stages in all:
 //   lines .. order   the loader's, with these differences:
 //     parse    peak_parse_kernel: parts[0] (the line up to its first tab) through Range::from_str; a valid range needs
 //              parts[2], the signal (else W_EFIELD: refused at the loader's read-back of the offsets); five more columns
@@ -1110,10 +1205,8 @@ void rg_timed(gams_gpu_t *h, int n) {
 //              reference's stable sort leaves; a key wider than 64 bits is refused;
 //   gc       gather (line, ctg, start, end) through the sorted keys, check every kept peak against its ctg and the ctg
 //            for a sequence (flags), then round4(range_gc) of every kept peak (sw.hip);
-//   rows     the length of every row (it reads the neighbours' end / start / gc / signal inside the bucket), their block
-//            sums and the blocks' prefix;
-//   write    the rows at their offsets -- a block's 256 rows composed in LDS and copied out in 16-B units, or written
-//            straight to global memory when they exceed the stage -- and the offset of every ctg's first row.
+//   rows     the length of every row (it reads the neighbours' end / start / gc / signal inside the bucket);
+//   write    the rows at their offsets and the offset of every ctg's first row.
 // Rows come out in key order: grouped by ctg in the caller's order, by start inside a ctg.
 struct PeakLines {
     unsigned long long *cb, *sb;      // per line: where the chromosome and the signal field begin
@@ -1180,45 +1273,34 @@ struct PeakLoad {
 struct PeakArgs {
     TextLines t;
     PeakLines p;
-    const unsigned long long *key;            // sorted: the first n_kept are the kept lines in (ctg, start, line) order
-    uint32_t line_bits;
-    uint32_t n_kept;
-    const uint32_t *qs, *qe;                  // per line
-    const unsigned long long *bucket_off;     // n_ctg + 1
+    RgKept v;                                 // the kept lines in (ctg, start, line) order
     const int32_t *cs, *ce;                   // per ctg
     const uint32_t *seq_len;                  // per ctg: 0 = no sequence in the seqset
     NameTab ids;
     uint32_t *kline, *kctg, *ks, *ke;         // per kept peak
     float *gc;
-    uint32_t *row_len;
-    unsigned long long *blk_bytes;            // per workgroup of 256 rows
-    const unsigned long long *blk_off;
-    unsigned long long *text_off;             // per ctg with rows: the offset of its first row
-    unsigned long long *words;
-    char *text;
+    KeyedText<uint32_t> o;
 };
 
 __global__ __launch_bounds__(256) void peak_gather_kernel(const PeakArgs a) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k >= a.n_kept) return;
-    const unsigned long long key = a.key[k];
-    const uint32_t i = (uint32_t)(key & ((1ull << a.line_bits) - 1ull));
-    const uint32_t c = (uint32_t)(key >> (31u + a.line_bits));
-    const uint32_t s = a.qs[i], e = a.qe[i];
+    if (k >= a.v.n_kept) return;
+    const uint32_t i = a.v.line(k), c = a.v.bucket(k);
+    const uint32_t s = a.v.qs[i], e = a.v.qe[i];
     a.kline[k] = i;
     a.kctg[k] = c;
     a.ks[k] = s;
     a.ke[k] = e;
     // peak_check_inside: the reference slices the ctg's sequence with the range (utils.rs:155)
-    if ((int32_t)s < a.cs[c] || (int32_t)e > a.ce[c] || e < s) a.words[W_EID] = 1ull;
-    if (a.seq_len[c] == 0u) a.words[W_ENOSEQ] = 1ull;
+    if ((int32_t)s < a.cs[c] || (int32_t)e > a.ce[c] || e < s) a.o.words[W_EID] = 1ull;
+    if (a.seq_len[c] == 0u) a.o.words[W_ENOSEQ] = 1ull;
 }
 
 // peak.rs:65-158 for kept peak k, as gams_host_peak prints it
 template <bool kWrite>
 __device__ void peak_row(const PeakArgs &a, uint32_t k, RowOut<kWrite> &o, bool &bad) {
     const uint32_t c = a.kctg[k];
-    const uint32_t o0 = (uint32_t)a.bucket_off[c], o1 = (uint32_t)a.bucket_off[c + 1u];
+    const uint32_t o0 = (uint32_t)a.v.bucket_off[c], o1 = (uint32_t)a.v.bucket_off[c + 1u];
     const bool has_prev = k > o0, has_next = k + 1u < o1;
     const uint32_t i = a.kline[k], ip = has_prev ? a.kline[k - 1u] : i, in = has_next ? a.kline[k + 1u] : i;
     const uint32_t s = a.ks[k], e = a.ke[k];
@@ -1261,44 +1343,28 @@ __device__ void peak_row(const PeakArgs &a, uint32_t k, RowOut<kWrite> &o, bool 
     o.ch('\n');
 }
 
-__global__ __launch_bounds__(256) void peak_row_len_kernel(const PeakArgs a) {
-    __shared__ uint64_t ws[4];
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    bool bad = false;
-    RowOut<false> n;
-    if (k < a.n_kept) {
-        peak_row(a, k, n, bad);
-        a.row_len[k] = n.n;
-    }
-    const uint32_t l = n.n;
-    if (bad) a.words[W_UNSUP] = 1ull;
-    uint64_t tot;
-    (void)block_excl_scan_256<uint64_t>((uint64_t)l, ws, tot);
-    if (threadIdx.x == 0) a.blk_bytes[blockIdx.x] = tot;
-}
-
 // bytes of a block's rows staged in LDS: 256 rows of ~90 B are 23 KB; a block beyond the stage (long names, ids or
 // signals) writes its rows to global memory directly
 constexpr uint32_t kPeakStage = 32768;
 
-__global__ __launch_bounds__(256) void peak_row_write_kernel(const PeakArgs a) {
-    __shared__ uint64_t ws[4];
-    __shared__ __align__(16) char stage[kPeakStage + 16];
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    const uint64_t l = k < a.n_kept ? a.row_len[k] : 0ull;
-    BlockWriter<uint64_t> w(l, ws, a.blk_off, a.text, ~0ull);   // (the text holds all rows: no bound)
-    w.stage_if(w.tot <= kPeakStage, stage);
-    if (k < a.n_kept) {
-        const uint32_t c = a.kctg[k];
-        if (k == (uint32_t)a.bucket_off[c]) a.text_off[c] = w.blk0 + w.rel;
-        bool bad = false;                      // (the length pass flagged what has no text: nothing is written then)
-        w.put(w.rel, [&](char *p) {
-            RowOut<true> o{p};
-            peak_row(a, k, o, bad);
-        });
+// the Peak rows for the keyed row writer: every kept peak has a row
+struct PeakRows {
+    using Args = PeakArgs;
+    using Len = uint32_t;
+    static constexpr uint32_t kStage = kPeakStage;
+    template <bool kWrite>
+    static __device__ __forceinline__ void row(const Args &a, uint32_t k, RowOut<kWrite> &o, bool &bad) { peak_row(a, k, o, bad); }
+    static __device__ __forceinline__ uint32_t bucket(const Args &a, uint32_t k) { return a.kctg[k]; }
+    static __device__ __forceinline__ bool refused(const Args &, uint32_t) { return false; }
+    static int check(gams_gpu_t *h, const std::string &who, const unsigned long long *w) {
+        if (w[W_EID])
+            return gams_fail(h, GAMS_EINVAL, who + ": a peak is not inside its ctg (the reference panics on the slice, utils.rs:155)");
+        if (w[W_ENOSEQ]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with peaks has no sequence in the seqset");
+        if (w[W_UNSUP])
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a gc or an amplitude the device formatters do not cover (use the host path)");
+        return GAMS_OK;
     }
-    w.flush();
-}
+};
 
 enum : int { PK_GC = RG_GATHER, PK_ROWS, PK_WRITE, PK_STAGES };   // behind the loader's lines .. order
 
@@ -1320,9 +1386,7 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
     memset(text_off, 0, (n_ctg + 1) * 8);
     for (uint64_t c = 0; c < n_ctg; ++c) {
         if (J.chr_end[c] < J.chr_start[c]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg ends before it starts");
-        const uint32_t slot = J.ctg_index[c];
-        if (slot == UINT32_MAX) continue;
-        if (slot >= J.s->n_ctg || (int64_t)J.s->len[slot] != (int64_t)J.chr_end[c] - J.chr_start[c] + 1)
+        if (J.ctg_index[c] != UINT32_MAX && !seq_slot_holds(J.s, J.ctg_index[c], J.chr_start[c], J.chr_end[c]))
             return gams_fail(h, GAMS_EINVAL, who + ": ctg_index does not name a sequence of the ctg's length");
     }
     GAMS_HIP(h, hipSetDevice(h->device));
@@ -1362,80 +1426,37 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
     const size_t b_in = reinterpret_cast<uint8_t *>(ht.toff) - pin.p;    // the four input columns
     GAMS_TRY(h, who, hipMemcpyAsync(d_tab.p, pin.p, b_in, hipMemcpyHostToDevice, st));
     PeakLoad load{J.chr->t, PeakLines{}};
-    return rg_load(h, who, J.ctg_ix, load, bytes, n_bytes, true, [&](const RgCols &C, const StageClock &stage) -> int {
+    return rg_load(h, who, J.ctg_ix, load, RgInput{bytes, n_bytes, nullptr, false}, true,
+                   [&](const RgCols &C, const StageClock &stage) -> int {
         // (no rg_timed on the two early ends: an input without lines, or without a kept line, leaves the stopwatch invalid)
         if (C.n_kept == 0) return GAMS_OK;
-        const uint32_t K = (uint32_t)C.n_kept, nbk = (K + 255u) / 256u;  // n_kept <= L < 2^32
-        PoolBlock s2(h, false), d_text(h, false);
+        const uint32_t K = C.v.n_kept;
+        PoolBlock s2(h, false);
         PeakArgs a{};
         a.t = C.t;
         a.p = load.pl;
-        a.key = C.g.key;
-        a.line_bits = (uint32_t)__builtin_popcountll(C.g.line_mask);
-        a.n_kept = K;
-        a.qs = C.g.qs;
-        a.qe = C.g.qe;
-        a.bucket_off = C.g.bucket_off;
+        a.v = C.v;
         a.cs = dt.cs;
         a.ce = dt.ce;
         a.seq_len = dt.seq_len;
         a.ids = J.ids->t;
-        a.text_off = dt.toff;
-        a.words = C.words;
-        auto kept = [&](Carver &c) {   // line ctg start end | gc | row lengths | the blocks' bytes and prefix
+        a.o.text_off = dt.toff;
+        a.o.words = C.words;
+        auto kept = [&](Carver &c) {   // line ctg start end | gc | the writer's
             a.kline = c.take<uint32_t>(K);
             a.kctg = c.take<uint32_t>(K);
             a.ks = c.take<uint32_t>(K);
             a.ke = c.take<uint32_t>(K);
             a.gc = c.take<float>(K);
-            a.row_len = c.take<uint32_t>(K);
-            a.blk_bytes = c.take<unsigned long long>((size_t)nbk + 1);
-            unsigned long long *const off = c.take<unsigned long long>((size_t)nbk + 1);
-            a.blk_off = off;
-            return off;
+            a.o.carve(c, K);
         };
         GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
-        unsigned long long *const d_blk_off = carve(s2.p, kept);
+        carve(s2.p, kept);
         GAMS_TRY(h, who, stage(PK_GC, true));
-        hipLaunchKernelGGL(peak_gather_kernel, dim3(nbk), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(peak_gather_kernel, dim3((K + 255u) / 256u), dim3(256), 0, st, a);
         gams_launch_range_gc_cols(J.s, dt.seq_off, dt.seq_len, dt.cs, a.kctg, a.ks, a.ke, K, a.gc, st);
         GAMS_TRY(h, who, stage(PK_GC, false));
-        GAMS_TRY(h, who, stage(PK_ROWS, true));
-        hipLaunchKernelGGL(peak_row_len_kernel, dim3(nbk), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbk, d_blk_off,
-                           C.words, (uint32_t)W_BYTES);
-        GAMS_TRY(h, who, stage(PK_ROWS, false));
-        GAMS_TRY(h, who, hipGetLastError());
-        GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, C.words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-        GAMS_TRY(h, who, hipStreamSynchronize(st));
-        const unsigned long long *w = h->pin_scratch;
-        if (w[W_EID])
-            return gams_fail(h, GAMS_EINVAL, who + ": a peak is not inside its ctg (the reference panics on the slice, utils.rs:155)");
-        if (w[W_ENOSEQ]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with peaks has no sequence in the seqset");
-        if (w[W_UNSUP])
-            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a gc or an amplitude the device formatters do not cover (use the host path)");
-        const uint64_t tb = w[W_BYTES];
-        gams_text_state *T = h->text;
-        char *&out = T->out[K_PEAK];
-        size_t &out_cap = T->out_cap[K_PEAK];
-        GAMS_TRY(h, who, gams_pool_grow(h, true, &out, &out_cap, tb, tb));
-        GAMS_TRY(h, who, d_text.alloc(tb));
-        a.text = reinterpret_cast<char *>(d_text.p);
-        GAMS_TRY(h, who, stage(PK_WRITE, true));
-        hipLaunchKernelGGL(peak_row_write_kernel, dim3(nbk), dim3(256), 0, st, a);
-        GAMS_TRY(h, who, stage(PK_WRITE, false));
-        GAMS_TRY(h, who, hipGetLastError());
-        GAMS_TRY(h, who, hipMemcpyAsync(out, d_text.p, tb, hipMemcpyDeviceToHost, st));
-        GAMS_TRY(h, who, hipMemcpyAsync(ht.toff, dt.toff, (n_ctg + 1) * 8, hipMemcpyDeviceToHost, st));
-        GAMS_TRY(h, who, hipStreamSynchronize(st));
-        // a ctg without rows begins where the next one does
-        text_off[n_ctg] = tb;
-        for (uint64_t c = n_ctg; c-- > 0;) text_off[c] = C.bucket_off[c + 1] > C.bucket_off[c] ? ht.toff[c] : text_off[c + 1];
-        rg_timed(h, PK_STAGES);
-        *text = out;
-        *text_bytes = tb;
-        *n_rows = C.n_kept;
-        return GAMS_OK;
+        return keyed_text_run<PeakRows>(h, who, C, stage, PK_ROWS, a, TEXT_PEAK, ht.toff, text, text_bytes, text_off, n_rows);
     });
 }
 
@@ -1448,10 +1469,8 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
 static_assert(SWF_GATHER == RG_GATHER, "the sw stages continue the loader's stopwatch behind `order`");
 
 struct SwGather {
-    const unsigned long long *key;            // sorted: the first n_kept are the kept lines in (ctg, line) order
-    unsigned long long line_mask;
-    const uint32_t *qs, *qe;                  // per line
-    uint32_t n_kept, n_ctg;
+    RgKept v;                                 // the kept lines in (ctg, line) order
+    uint32_t n_ctg;
     const int32_t *cs, *ce;                   // per interval
     const CountGroup *groups;                 // the ctg index's groups: group g owns intervals [off, off + n)
     uint32_t n_groups;
@@ -1463,11 +1482,9 @@ struct SwGather {
 
 __global__ __launch_bounds__(256) void sw_gather_kernel(const SwGather a) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k < a.n_kept) {
-        const unsigned long long key = a.key[k];
-        const uint32_t i = (uint32_t)(key & a.line_mask);
-        const uint32_t c = (uint32_t)(key >> __popcll(a.line_mask));
-        const int64_t s = a.qs[i], e = a.qe[i];
+    if (k < a.v.n_kept) {
+        const uint32_t i = a.v.line(k), c = a.v.bucket(k);
+        const int64_t s = a.v.qs[i], e = a.v.qe[i];
         a.fs[k] = (int32_t)s;
         a.fe[k] = (int32_t)e;
         a.fctg[k] = c;
@@ -1523,7 +1540,8 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         if (rc_gc != GAMS_OK) return rc_gc;
     }
     GAMS_HIP(h, gams_stopwatch_reserve(h, SWF_STAGES));
-    return rg_load(h, who, J.ctg_ix, RgPlain{J.chr->t}, bytes, n_bytes, true, [&](const RgCols &C, const StageClock &stage) -> int {
+    return rg_load(h, who, J.ctg_ix, RgPlain{J.chr->t}, RgInput{bytes, n_bytes, nullptr, false}, true,
+                   [&](const RgCols &C, const StageClock &stage) -> int {
         *n_features = C.n_kept;
         if (C.n_kept == 0) {
             if (C.ran) rg_timed(h, RG_ORDER + 1);
@@ -1538,7 +1556,7 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
                 if (C.bucket_off[c + 1] == C.bucket_off[c]) continue;
                 const uint32_t slot = J.ctg_index[c];
                 if (slot == UINT32_MAX) return gams_fail(h, GAMS_EINVAL, who + ": a ctg with features has no sequence in the seqset");
-                if (slot >= J.s->n_ctg || (int64_t)J.s->len[slot] != (int64_t)J.chr_end[c] - J.chr_start[c] + 1)
+                if (!seq_slot_holds(J.s, slot, J.chr_start[c], J.chr_end[c]))
                     return gams_fail(h, GAMS_EINVAL, who + ": ctg_index does not name a sequence of the ctg's length");
             }
         const uint32_t K = (uint32_t)C.n_kept, nc = (uint32_t)n_ctg;
@@ -1567,11 +1585,7 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         hw[0] = hw[1] = 0ull;
         hw[2] = ~0ull;
         GAMS_TRY(h, who, hipMemcpyAsync(g.words, hw, 3 * 8, hipMemcpyHostToDevice, st));
-        g.key = C.g.key;
-        g.line_mask = C.g.line_mask;
-        g.qs = C.g.qs;
-        g.qe = C.g.qe;
-        g.n_kept = K;
+        g.v = C.v;
         g.n_ctg = nc;
         g.cs = d_cs;
         g.ce = d_ce;
@@ -1589,7 +1603,7 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         S.fs = g.fs;
         S.fe = g.fe;
         S.fctg = g.fctg;
-        S.d_bucket_off = C.g.bucket_off;
+        S.d_bucket_off = C.v.bucket_off;
         S.bucket_off = C.bucket_off;
         S.ctg_index = J.ctg_index;
         S.chr_start = J.chr_start;
@@ -1617,13 +1631,14 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
 
 
 // ---- the records of `gams rg` / `gams feature` (rg.rs:40-82, feature.rs:47-96) as text -----------------------------------
-// The range loader over several files with (file, ctg) buckets (rg_load_in, by_file) and a parse kernel that also says
-// where the name, the chromosome and the strand of every line lie, then three stages of its own; ten in all:
+// The range loader over several files with (file, ctg) buckets (RgInput::files, by_file) and a parse kernel that also says
+// where the name, the chromosome and the strand of every line lie, then a stage of its own and the two of the keyed row
+// writer (RecRows); ten in all:
 //   serials  per kept line in key order -- grouped by (file, ctg), in line order inside a group --: its line, its bucket
 //            and its serial = sbase[bucket] + its rank in the bucket + 1.  sbase is the host's, from the buckets' sizes:
 //            cnt:{kind}:{ctg} before the load plus the kept lines of the ctg in the files in front (rg.rs:63-75);
-//   rows     the length of every row, the check of its name and strand for control bytes, the block sums and their prefix;
-//   write    the rows at their offsets (BlockWriter, as the peak rows) and the offset of every bucket's first row.
+//   rows     the check of a row's name and strand for control bytes, and its length;
+//   write    the rows at their offsets and the offset of every bucket's first row.
 // A row is described once (rec_row) for the three formats; RESP needs the lengths of the id and of the JSON in front of
 // them, which the same descriptions give through a counting RowOut.
 struct RecLines {
@@ -1679,33 +1694,24 @@ constexpr uint32_t kRecMaxField = 1u << 30;   // a name or strand of this many b
 struct RecArgs {
     TextLines t;
     RecLines p;
-    const unsigned long long *key;            // sorted: the first n_kept are the kept lines in (file, ctg, line) order
-    uint32_t line_bits;
-    uint32_t n_kept, n_ctg;
-    const uint32_t *qs, *qe;                  // per line
-    const unsigned long long *bucket_off;     // n_bkt + 1
+    RgKept v;                                 // the kept lines in (file, ctg, line) order
+    uint32_t n_ctg;
     const uint32_t *sbase;                    // per bucket: the serial in front of its first row's
     NameTab ids;
     const char *tag;
     uint32_t tag_len;
     int kind, format;
     uint32_t *kline, *kbkt, *kserial;         // per kept line
-    unsigned long long *row_len;
-    unsigned long long *blk_bytes;            // per workgroup of 256 rows
-    const unsigned long long *blk_off;
-    unsigned long long *text_off;             // per bucket with rows: the offset of its first row
-    unsigned long long *words;
-    char *text;
+    KeyedText<unsigned long long> o;
 };
 
 __global__ __launch_bounds__(256) void rec_serial_kernel(const RecArgs a) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    if (k >= a.n_kept) return;
-    const unsigned long long key = a.key[k];
-    const uint32_t b = (uint32_t)(key >> a.line_bits);
-    a.kline[k] = (uint32_t)(key & ((1ull << a.line_bits) - 1ull));
+    if (k >= a.v.n_kept) return;
+    const uint32_t b = a.v.bucket(k);
+    a.kline[k] = a.v.line(k);
     a.kbkt[k] = b;
-    a.kserial[k] = a.sbase[b] + (k - (uint32_t)a.bucket_off[b]) + 1u;
+    a.kserial[k] = a.sbase[b] + (k - (uint32_t)a.v.bucket_off[b]) + 1u;
 }
 
 // "{kind}:{ctg_id}:{serial}" (rg.rs:64-66, feature.rs:81-83); json: inside a JSON string
@@ -1747,7 +1753,7 @@ __device__ __forceinline__ void rec_range(const RecArgs &a, uint32_t i, RowOut<k
         o.ch(')');
     }
     o.ch(':');
-    const uint32_t s = a.qs[i], e = a.qe[i];
+    const uint32_t s = a.v.qs[i], e = a.v.qe[i];
     o.dec(s);
     if (e != s) {
         o.ch('-');
@@ -1765,7 +1771,7 @@ __device__ __forceinline__ void rec_json(const RecArgs &a, uint32_t k, RowOut<kW
     rec_range(a, i, o, true);
     if (a.kind == GAMS_LOADER_FEATURE) {
         o.bytes("\",\"length\":", 11u);
-        o.i32((int32_t)(a.qe[i] - a.qs[i] + 1u));              // feature.rs:88: end - start + 1, an i32
+        o.i32((int32_t)(a.v.qe[i] - a.v.qs[i] + 1u));              // feature.rs:88: end - start + 1, an i32
         o.bytes(",\"tag\":\"", 8u);
         o.esc(a.tag, (uint64_t)a.tag_len);
     }
@@ -1781,7 +1787,7 @@ __device__ void rec_row(const RecArgs &a, uint32_t k, RowOut<kWrite, uint64_t> &
         rec_range(a, i, o, false);
         if (a.kind == GAMS_LOADER_FEATURE) {
             o.ch('\t');
-            o.i32((int32_t)(a.qe[i] - a.qs[i] + 1u));
+            o.i32((int32_t)(a.v.qe[i] - a.v.qs[i] + 1u));
             o.ch('\t');
             o.bytes(a.tag, (uint64_t)a.tag_len);
         }
@@ -1807,53 +1813,36 @@ __device__ void rec_row(const RecArgs &a, uint32_t k, RowOut<kWrite, uint64_t> &
     }
 }
 
-__global__ __launch_bounds__(256) void rec_row_len_kernel(const RecArgs a) {
-    __shared__ uint64_t ws[4];
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    RowOut<false, uint64_t> n;
-    if (k < a.n_kept) {
-        const uint32_t i = a.kline[k];
-        const uint32_t nlen = a.p.nlen[i], slen = a.p.slen[i];
-        bool bad = nlen >= kRecMaxField || slen >= kRecMaxField;
-        if (!bad) {
-            // a control byte in a string value: serde_json writes \uXXXX and the like, this writer does not
-            const char *nm = a.t.in + a.t.starts[i], *sd = a.t.in + a.p.cb[i] + a.p.clen[i] + 1u;
-            for (uint32_t j = 0; j < nlen; ++j) bad |= (uint8_t)nm[j] < 0x20u;
-            for (uint32_t j = 0; j < slen; ++j) bad |= (uint8_t)sd[j] < 0x20u;
-        }
-        if (bad)
-            a.words[W_UNSUP] = 1ull;
-        else
-            rec_row(a, k, n);
-        a.row_len[k] = n.n;
-    }
-    uint64_t tot;
-    (void)block_excl_scan_256<uint64_t>(n.n, ws, tot);
-    if (threadIdx.x == 0) a.blk_bytes[blockIdx.x] = tot;
-}
-
 // bytes of a block's rows staged in LDS: 256 RESP rows of a feature are ~36 KB; a block beyond the stage (long names or
 // tags) writes its rows to global memory directly
 constexpr uint32_t kRecStage = 49152;
 
-// Never launched when the length pass set W_UNSUP: every row it writes was measured there.
-__global__ __launch_bounds__(256) void rec_row_write_kernel(const RecArgs a) {
-    __shared__ uint64_t ws[4];
-    __shared__ __align__(16) char stage[kRecStage + 16];
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    const uint64_t l = k < a.n_kept ? a.row_len[k] : 0ull;
-    BlockWriter<uint64_t> w(l, ws, a.blk_off, a.text, ~0ull);   // (the text holds all rows: no bound)
-    w.stage_if(w.tot <= kRecStage, stage);
-    if (k < a.n_kept) {
-        const uint32_t b = a.kbkt[k];
-        if (k == (uint32_t)a.bucket_off[b]) a.text_off[b] = w.blk0 + w.rel;
-        w.put(w.rel, [&](char *p) {
-            RowOut<true, uint64_t> o{p};
-            rec_row(a, k, o);
-        });
+// the records for the keyed row writer
+struct RecRows {
+    using Args = RecArgs;
+    using Len = uint64_t;
+    static constexpr uint32_t kStage = kRecStage;
+    template <bool kWrite>
+    static __device__ __forceinline__ void row(const Args &a, uint32_t k, RowOut<kWrite, uint64_t> &o, bool &) { rec_row(a, k, o); }
+    static __device__ __forceinline__ uint32_t bucket(const Args &a, uint32_t k) { return a.kbkt[k]; }
+    // a name or strand of kRecMaxField bytes, or with a control byte: serde_json writes \uXXXX and the like, this writer does not
+    static __device__ __forceinline__ bool refused(const Args &a, uint32_t k) {
+        const uint32_t i = a.kline[k];
+        const uint32_t nlen = a.p.nlen[i], slen = a.p.slen[i];
+        bool bad = nlen >= kRecMaxField || slen >= kRecMaxField;
+        if (!bad) {
+            const char *nm = a.t.in + a.t.starts[i], *sd = a.t.in + a.p.cb[i] + a.p.clen[i] + 1u;
+            for (uint32_t j = 0; j < nlen; ++j) bad |= (uint8_t)nm[j] < 0x20u;
+            for (uint32_t j = 0; j < slen; ++j) bad |= (uint8_t)sd[j] < 0x20u;
+        }
+        return bad;
     }
-    w.flush();
-}
+    static int check(gams_gpu_t *h, const std::string &who, const unsigned long long *w) {
+        if (w[W_UNSUP])
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a kept line's name or strand holds a control byte, or 2^30 bytes (use the host path)");
+        return GAMS_OK;
+    }
+};
 
 enum : int { LT_SERIALS = RG_GATHER, LT_ROWS, LT_WRITE, LT_STAGES };   // behind the loader's lines .. order
 
@@ -1885,16 +1874,16 @@ int loader_text_run(gams_gpu_t *h, const RecJob &J, const char **text, uint64_t 
     GAMS_HIP(h, hipSetDevice(h->device));
     GAMS_HIP(h, gams_stopwatch_reserve(h, LT_STAGES));
     RecLoad load{J.chr->t, RecLines{}};
-    return rg_load_in(h, who, J.ctg_ix, load, RgInput{nullptr, 0, &J.files, true}, true, [&](const RgCols &C, const StageClock &stage) -> int {
+    return rg_load(h, who, J.ctg_ix, load, RgInput{nullptr, 0, &J.files, true}, true, [&](const RgCols &C, const StageClock &stage) -> int {
         if (C.n_kept == 0) {
             if (C.ran) rg_timed(h, RG_ORDER + 1);
             return GAMS_OK;
         }
         // (kept lines: there is a file, and with one file the buckets are the ctgs: n_bkt = n_files * n_ctg either way)
         const uint64_t n_bkt = C.n_bkt;
-        const uint32_t K = (uint32_t)C.n_kept, nbk = (K + 255u) / 256u;  // n_kept <= L < 2^32
+        const uint32_t K = C.v.n_kept;
         hipStream_t st = h->compute;
-        PoolBlock s2(h, false), pin(h, true), d_text(h, false);
+        PoolBlock s2(h, false), pin(h, true);
         // the serials: the buckets of a ctg, file by file, continue its counter
         struct Tabs {
             uint32_t *sbase;
@@ -1919,76 +1908,39 @@ int loader_text_run(gams_gpu_t *h, const RecJob &J, const char **text, uint64_t 
         RecArgs a{};
         char *d_tag = nullptr;
         Tabs dt{};
-        auto kept = [&](Carver &c) {   // sbase text_off | line bucket serial | row lengths | the blocks' bytes and prefix | tag
+        auto kept = [&](Carver &c) {   // sbase text_off | line bucket serial | the writer's | tag
             dt = tabs(c);
             a.kline = c.take<uint32_t>(K);
             a.kbkt = c.take<uint32_t>(K);
             a.kserial = c.take<uint32_t>(K);
-            a.row_len = c.take<unsigned long long>(K);
-            a.blk_bytes = c.take<unsigned long long>((size_t)nbk + 1);
-            unsigned long long *const off = c.take<unsigned long long>((size_t)nbk + 1);
-            a.blk_off = off;
+            a.o.carve(c, K);
             d_tag = c.take<char>(std::max<uint64_t>(J.tag_bytes, 1));
-            return off;
         };
         GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
-        unsigned long long *const d_blk_off = carve(s2.p, kept);
+        carve(s2.p, kept);
         a.t = C.t;
         a.p = load.rl;
-        a.key = C.g.key;
-        a.line_bits = (uint32_t)__builtin_popcountll(C.g.line_mask);
-        a.n_kept = K;
+        a.v = C.v;
         a.n_ctg = (uint32_t)n_ctg;
-        a.qs = C.g.qs;
-        a.qe = C.g.qe;
-        a.bucket_off = C.g.bucket_off;
         a.sbase = dt.sbase;
         a.ids = J.ids->t;
         a.tag = d_tag;
         a.tag_len = (uint32_t)J.tag_bytes;
         a.kind = J.kind;
         a.format = J.format;
-        a.text_off = dt.toff;
-        a.words = C.words;
+        a.o.text_off = dt.toff;
+        a.o.words = C.words;
         GAMS_TRY(h, who, stage(LT_SERIALS, true));
         GAMS_TRY(h, who, hipMemcpyAsync(dt.sbase, ht.sbase, n_bkt * 4, hipMemcpyHostToDevice, st));
         if (J.tag_bytes) GAMS_TRY(h, who, hipMemcpyAsync(d_tag, J.tag, J.tag_bytes, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(rec_serial_kernel, dim3(nbk), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(rec_serial_kernel, dim3((K + 255u) / 256u), dim3(256), 0, st, a);
         GAMS_TRY(h, who, stage(LT_SERIALS, false));
-        GAMS_TRY(h, who, stage(LT_ROWS, true));
-        hipLaunchKernelGGL(rec_row_len_kernel, dim3(nbk), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, a.blk_bytes, nbk, d_blk_off,
-                           C.words, (uint32_t)W_BYTES);
-        GAMS_TRY(h, who, stage(LT_ROWS, false));
-        GAMS_TRY(h, who, hipGetLastError());
-        GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, C.words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-        GAMS_TRY(h, who, hipStreamSynchronize(st));
-        const unsigned long long *w = h->pin_scratch;
-        if (w[W_UNSUP])
-            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a kept line's name or strand holds a control byte, or 2^30 bytes (use the host path)");
-        const uint64_t tb = w[W_BYTES];
-        gams_text_state *T = h->text;
-        GAMS_TRY(h, who, gams_pool_grow(h, true, &T->rec_out, &T->rec_out_cap, tb, tb));
-        GAMS_TRY(h, who, d_text.alloc(tb));
-        a.text = reinterpret_cast<char *>(d_text.p);
-        GAMS_TRY(h, who, stage(LT_WRITE, true));
-        hipLaunchKernelGGL(rec_row_write_kernel, dim3(nbk), dim3(256), 0, st, a);
-        GAMS_TRY(h, who, stage(LT_WRITE, false));
-        GAMS_TRY(h, who, hipGetLastError());
-        GAMS_TRY(h, who, hipMemcpyAsync(T->rec_out, d_text.p, tb, hipMemcpyDeviceToHost, st));
-        GAMS_TRY(h, who, hipMemcpyAsync(ht.toff, dt.toff, (n_bkt + 1) * 8, hipMemcpyDeviceToHost, st));
-        GAMS_TRY(h, who, hipStreamSynchronize(st));
-        // a bucket without rows begins where the next one does
-        text_off[n_bkt] = tb;
-        for (uint64_t b = n_bkt; b-- > 0;) text_off[b] = C.bucket_off[b + 1] > C.bucket_off[b] ? ht.toff[b] : text_off[b + 1];
+        const int rc = keyed_text_run<RecRows>(h, who, C, stage, LT_ROWS, a, TEXT_RECORDS, ht.toff, text, text_bytes, text_off, n_rows);
+        if (rc != GAMS_OK) return rc;
         for (uint64_t f = 0; f < n_files; ++f)
             if (n_in_file) n_in_file[f] = C.bucket_off[(f + 1) * n_ctg] - C.bucket_off[f * n_ctg];
         if (serial_next)
             for (uint64_t c = 0; c < n_ctg; ++c) serial_next[c] = (int32_t)next[c];
-        rg_timed(h, LT_STAGES);
-        *text = T->rec_out;
-        *text_bytes = tb;
-        *n_rows = C.n_kept;
         return GAMS_OK;
     });
 }
@@ -2208,9 +2160,7 @@ int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n
     for (uint64_t c = 0; c < n_ctg; ++c) {
         // a slot that does not hold the ctg is an error only where a line is located to the ctg: the lengths pass says so
         const uint32_t slot = J.ctg_index[c];
-        const bool holds = slot != UINT32_MAX && slot < J.s->n_ctg &&
-                           (int64_t)J.s->len[slot] == (int64_t)J.chr_end[c] - J.chr_start[c] + 1;
-        ht.seq_off[c] = holds ? J.s->off[slot] : ~0ull;
+        ht.seq_off[c] = seq_slot_holds(J.s, slot, J.chr_start[c], J.chr_end[c]) ? J.s->off[slot] : ~0ull;
         ht.cs[c] = J.chr_start[c];
         ht.ce[c] = J.chr_end[c];
     }
@@ -2269,9 +2219,7 @@ int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n
                        F.d_words, (uint32_t)W_BYTES);
     hipLaunchKernelGGL(seq_row_off_kernel, dim3(nbr), dim3(256), 0, st, a);
     GAMS_TRY(h, who, stage(SQ_OFFSETS, false));
-    GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(h->pin_scratch, F.d_words, W_COUNT * 8, hipMemcpyDeviceToHost, st));
-    GAMS_TRY(h, who, hipStreamSynchronize(st));
+    GAMS_TRY(h, who, read_words(h, F.d_words));
     const unsigned long long *w = h->pin_scratch;
     // an error word ends the call here: the copy kernel is never launched over rows the lengths pass refused
     if (w[W_EID])
@@ -2282,7 +2230,7 @@ int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n
     const uint64_t tb = w[W_BYTES], rows = w[W_ROWS];
     if (tb == 0) return GAMS_OK;                               // no located line: nothing to copy, no stages to report
     if (seq_plan_chunks(tb) > 0x7fffffffull) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": more text than one launch copies");
-    GAMS_TRY(h, who, gams_pool_grow(h, true, &T->seq_out, &T->seq_out_cap, tb, tb));
+    GAMS_TRY(h, who, gams_pool_grow(h, true, &T->out[TEXT_SEQ], &T->out_cap[TEXT_SEQ], tb, tb));
     PoolBlock d_text(h, false);
     GAMS_TRY(h, who, d_text.alloc(tb));
     a.text = reinterpret_cast<char *>(d_text.p);
@@ -2294,10 +2242,10 @@ int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n
     hipLaunchKernelGGL(seq_copy_kernel, dim3((uint32_t)seq_plan_chunks(tb)), dim3(256), 0, st, a);
     GAMS_TRY(h, who, stage(SQ_COPY, false));
     GAMS_TRY(h, who, hipGetLastError());
-    GAMS_TRY(h, who, hipMemcpyAsync(T->seq_out, d_text.p, tb, hipMemcpyDeviceToHost, st));
+    GAMS_TRY(h, who, hipMemcpyAsync(T->out[TEXT_SEQ], d_text.p, tb, hipMemcpyDeviceToHost, st));
     GAMS_TRY(h, who, hipStreamSynchronize(st));
     rg_timed(h, SQ_STAGES);
-    *text = T->seq_out;
+    *text = T->out[TEXT_SEQ];
     *text_bytes = tb;
     *n_rows = rows;
     return GAMS_OK;
@@ -2307,7 +2255,7 @@ int rg_index_run(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_
                  gams_index_t **rg_ix, uint32_t *rg_group, uint64_t *n_kept) {
     *rg_ix = nullptr;
     *n_kept = 0;
-    return rg_load_in(h, who, ctg_ix, RgPlain{chr_names->t}, in, true, [&](const RgCols &C, const StageClock &stage) -> int {
+    return rg_load(h, who, ctg_ix, RgPlain{chr_names->t}, in, true, [&](const RgCols &C, const StageClock &stage) -> int {
         uint32_t max_n = 0;
         for (uint64_t i = 0; i < C.n_ctg; ++i)
             max_n = std::max<uint32_t>(max_n, (uint32_t)(C.bucket_off[i + 1] - C.bucket_off[i]));
@@ -2317,7 +2265,8 @@ int rg_index_run(gams_gpu_t *h, const std::string &who, const gams_index_t *ctg_
         hipStream_t st = h->compute;
         hipError_t e = stage(RG_GATHER, true);
         if (C.n_kept) {
-            RgGather g = C.g;
+            RgGather g{};
+            g.v = C.v;
             g.start = B.cols.starts_in;
             g.end = B.cols.stops_in;            // [start, end + 1) (redis.rs:291-294)
             g.line = nullptr;
@@ -2458,7 +2407,8 @@ int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_nam
         return gams_fail(h, GAMS_EINVAL, "gpu_read_range_text: null argument");
     const std::string who = "gpu_read_range_text";
     *n_kept = 0;
-    return rg_load(h, who, ctg_ix, RgPlain{chr_names->t}, bytes, n_bytes, cap != 0, [&](const RgCols &C, const StageClock &stage) -> int {
+    return rg_load(h, who, ctg_ix, RgPlain{chr_names->t}, RgInput{bytes, n_bytes, nullptr, false}, cap != 0,
+                   [&](const RgCols &C, const StageClock &stage) -> int {
         for (uint64_t i = 0; i <= C.n_ctg; ++i) bucket_off[i] = C.bucket_off[i];
         if (seen)
             for (uint64_t i = 0; i < C.n_ctg; ++i) seen[i] = C.first[i] != UINT32_MAX;
@@ -2470,7 +2420,8 @@ int gams_gpu_read_range_text(gams_gpu_t *h, gams_index_t *ctg_ix, const gams_nam
         if (cap < C.n_kept) return gams_fail(h, GAMS_EINVAL, who + ": cap is smaller than the kept ranges (*n_kept has them)");
         // the three columns on the device, one read-back into pooled page-locked memory, then the caller's arrays
         PoolBlock d_out(h, false), p_out(h, true);
-        RgGather g = C.g;
+        RgGather g{};
+        g.v = C.v;
         auto three = [&](Carver &c) {
             g.start = c.take<uint32_t>(C.n_kept);
             g.end = c.take<uint32_t>(C.n_kept);
