@@ -273,11 +273,28 @@ struct SwColsJob {
     // device, 3 words: [0] receives the rows; [1] != 0: a kept feature has its middle outside its ctg, [2] = the
     // smallest such line number (both written by the caller's gather, queued in front)
     unsigned long long *words;
+    // gams_gpu_sw_feature_summary: the stages stop before the text -- the rows are added into tag slot `tag` of `summary`
+    // and never stored; the name tables above and the text outputs of the launcher are unused (NULL)
+    gams_sw_summary_t *summary;
+    uint32_t tag;
 };
+
+// The accumulator of the sw summaries (sw.hip): n_tags x (max + 1) groups of GAMS_SW_SUMMARY_WORDS 64-bit
+// integers in device memory, and the table of one call ((max + 1) groups, then a flag word) that the summarising
+// sw_kernel adds into and that is merged into a tag's groups only when the call met no value it does not cover.
+struct gams_sw_summary {
+    int32_t size = 0, max = 0, resize = 0;
+    uint32_t actions = 0, n_tags = 0;
+    unsigned long long *d_acc = nullptr, *d_call = nullptr;
+};
+// the call's parameters against the accumulator's binding and the tag slot against its tags: GAMS_EINVAL otherwise
+int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, int32_t size, int32_t max,
+                          int32_t resize, uint32_t actions, uint32_t tag);
 // the timed pairs of the handle (gams_gpu::kq) these stages record: behind the range loader's lines .. order (0 .. 6)
 enum : int { SWF_GATHER = 7, SWF_GEOM, SWF_ROWS, SWF_TLEN, SWF_TWRITE, SWF_STAGES };
 // *text (the handle's page-locked sw text, valid until the next sw call), text_off[n_ctg + 1], *n_rows.  GAMS_EINVAL for
-// the flag in words[1] (the message names the line), GAMS_EUNSUPPORTED for what the formatter does not cover.
+// the flag in words[1] (the message names the line), GAMS_EUNSUPPORTED for what the formatter does not cover.  With
+// J.summary the stages end behind SWF_ROWS and only *n_rows is written.
 int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
                         uint64_t *n_rows);
 

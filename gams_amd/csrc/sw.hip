@@ -19,7 +19,8 @@
 // `-a count` (rg_count, the ninth column): Lapper::count(win.min(), win.max()) of every window against the
 // idx:rg: group of its ctg -- the lookup of `locate --count` (lapper_count, interval_kernels.hpp), run by the
 // same thread that holds the window.  sw_kernel<kGc, kCount> is instantiated per action set; without kGc it
-// neither needs the gc index nor touches the sequence bytes.
+// neither needs the gc index nor touches the sequence bytes.  A third flag, kSum, keeps the row in registers and adds it
+// into the per-distance summary instead of storing it.
 
 #include "interval_kernels.hpp"
 #include "text_emit.hpp"
@@ -190,6 +191,9 @@ struct SwArgs {
     const BkRec *bk_start, *bk_stop;
     uint32_t n_groups;
     int32_t *cnt;
+    // the summarising instantiation: the call's table, (max + 1) groups, its flag word, and the chunks of 256 slots
+    unsigned long long *sum, *sum_bad;
+    uint64_t sum_chunks;
 };
 
 // gc_content of chromosome range [s,e] (inclusive) inside the ctg: count / len, f32
@@ -215,13 +219,14 @@ __device__ __forceinline__ uint64_t gc_prefix_at(const SwArgs &a, int64_t b) {
 // per ctg the kernel is all launch latency).
 // kGc: gc_content and the flank statistics (sw.rs:167-184); kCount: rg_count into a.cnt.  Without kGc the four
 // statistics of the row are 0 and nothing reads a.pm / a.seg.
-template <bool kGc, bool kCount>
-__global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
-    const uint64_t gid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// kSum: the row and its count stay with the thread (r, cnt) for the summary; nothing is stored and a.row_off, a.rows,
+// a.cnt and a.cap are not looked at.  gid = the thread's (feature, slot) number; returns whether that slot holds a window.
+template <bool kGc, bool kCount, bool kSum>
+__device__ __forceinline__ bool sw_row(const SwArgs &a0, uint64_t gid, gams_sw_row_t &r, int32_t &cnt) {
     const uint32_t slots = 1u + 2u * (uint32_t)a0.max;
     const uint64_t f = gid / slots;
     const uint32_t slot = (uint32_t)(gid % slots);
-    if (f >= a0.nf) return;
+    if (f >= a0.nf) return false;
     const SwCtg cg = a0.ctgs[a0.fctg[f]];
     SwArgs a = a0;
     a.seq_off = cg.seq_off;
@@ -230,7 +235,7 @@ __global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
     a.chr_end = cg.chr_end;
     const SwGeom g = sw_geometry(a.chr_start, a.chr_end, a.fs[f], a.fe[f], a.size, a.max);
     int32_t type, dist, ws, we;
-    uint64_t row = a.row_off[f];
+    uint64_t row = kSum ? 0ull : a.row_off[f];
     if (slot == 0) {
         type = 0;
         dist = 0;
@@ -238,33 +243,34 @@ __global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
         we = g.m_e;
     } else if (slot <= (uint32_t)a.max) {
         dist = (int32_t)slot;
-        if (dist > g.n_l) return;
+        if (dist > g.n_l) return false;
         type = 1;
         we = g.m_s - 1 - (dist - 1) * a.size;   // window.rs:24,48-49
         ws = we - a.size + 1;
         row += (uint64_t)dist;
     } else {
         dist = (int32_t)slot - a.max;
-        if (dist > g.n_r) return;
+        if (dist > g.n_r) return false;
         type = 2;
         ws = g.m_e + 1 + (dist - 1) * a.size;   // window.rs:21,45-46
         we = ws + a.size - 1;
         row += (uint64_t)g.n_l + (uint64_t)dist;
     }
-    if (row >= a.cap) return;
-    gams_sw_row_t r;
+    if (!kSum && row >= a.cap) return false;
     r.feature = (uint32_t)f - cg.feat_first;
     r.type = type;
     r.distance = dist;
     r.start = ws;
     r.end = we;
-    if (kCount)   // count_rg(idx:rg:, ctg, Range::from(chr, win.min(), win.max())) = Lapper::count(ws, we)
-        a.cnt[row] = lapper_count(a.cgroups, a.rg_starts, a.rg_stops, a.bk_start, a.bk_stop, a.n_groups, cg.rg_group,
-                                  (uint32_t)ws, (uint32_t)we);
+    if (kCount) { // count_rg(idx:rg:, ctg, Range::from(chr, win.min(), win.max())) = Lapper::count(ws, we)
+        cnt = lapper_count(a.cgroups, a.rg_starts, a.rg_stops, a.bk_start, a.bk_stop, a.n_groups, cg.rg_group,
+                           (uint32_t)ws, (uint32_t)we);
+        if (!kSum) a.cnt[row] = cnt;
+    }
     if (!kGc) {
         r.gc_content = r.gc_mean = r.gc_stddev = r.gc_cv = 0.0f;
-        a.rows[row] = r;
-        return;
+        if (!kSum) a.rows[row] = r;
+        return true;
     }
     r.gc_content = round4(range_gc(a, ws, we));                         // utils.rs:161
     // flank: center_resize(parent, window, resize) cut into size-bp tiles (sw.rs:175-178)
@@ -321,7 +327,93 @@ __global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
     r.gc_mean = round4(mean);
     r.gc_stddev = round4(sd);
     r.gc_cv = round4(cv);
-    a.rows[row] = r;
+    if (!kSum) a.rows[row] = r;
+    return true;
+}
+
+// ---- the per-distance summary of the rows --------------------------------------------------------------
+// A group -- one distance of one tag -- is GAMS_SW_SUMMARY_WORDS 64-bit integers: COUNT, the sums S of the four
+// statistics' m (sw_f4_units: what sw_put_f4 prints), their four NaN counters, and C, the sum of rg_count.  All integers:
+// the result does not depend on the order of the additions.
+constexpr uint32_t kSumWords = GAMS_SW_SUMMARY_WORDS;
+enum : uint32_t { SUM_COUNT = 0, SUM_S = 1, SUM_NAN = 5, SUM_C = 9 };
+// The distances of a call that a workgroup reduces in LDS before it touches global memory: 256 groups x 10 words x 8 B =
+// 20 KiB, an eighth of a CU's 160 KiB, so the table never lowers the 8 workgroups of 256 threads a CU holds.  A call with
+// more distances (max >= 256) adds to global memory directly.
+constexpr uint32_t kSumLdsGroups = 256;
+
+// one row into group `g` (LDS or global); `bad`: a statistic the text formatter does not cover either
+template <bool kGc, bool kCount>
+__device__ __forceinline__ void sw_sum_put(unsigned long long *g, const gams_sw_row_t &r, int32_t cnt, bool &bad) {
+    atomicAdd(g + SUM_COUNT, 1ull);
+    if (kGc) {
+        const float v[4] = {r.gc_content, r.gc_mean, r.gc_stddev, r.gc_cv};
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k) {
+            if (v[k] != v[k])
+                atomicAdd(g + SUM_NAN + k, 1ull);
+            else if (!(v[k] >= 0.0f) || !(v[k] < 1000.0f))     // (sw_put_f4's refusal; -0 passes and adds 0)
+                bad = true;
+            else if (const uint32_t m = sw_f4_units(v[k]))
+                atomicAdd(g + SUM_S + k, (unsigned long long)m);
+        }
+    }
+    if (kCount && cnt) atomicAdd(g + SUM_C, (unsigned long long)(long long)cnt);
+}
+
+// The summarising kernel.  The slots are dealt out as in the storing kernel -- 256 consecutive (feature, slot) numbers a
+// workgroup and trip -- but a workgroup takes every gridDim.x-th such chunk and keeps its table across them, so the
+// global atomics of the flush are paid once per resident workgroup, not once per 256 rows: flushed per chunk, the
+// 16 000 chunks of the kept workload queued 1.7e6 atomics on the same 105 words and the stage took 0.37 ms
+// (profiles/sw_summary.txt).  The table: the call's distances in LDS, flushed once, non-zero bins only, or -- beyond
+// kSumLdsGroups distances -- the call's table in global memory directly.
+template <bool kGc, bool kCount>
+__device__ __forceinline__ void sw_sum_chunks(const SwArgs &a, uint64_t n_chunks) {
+    __shared__ unsigned long long bins[kSumLdsGroups * kSumWords];
+    const uint32_t words = ((uint32_t)a.max + 1u) * kSumWords;
+    const bool lds = (uint32_t)a.max < kSumLdsGroups;          // uniform
+    bool bad = false;
+    if (lds) {
+        for (uint32_t i = threadIdx.x; i < words; i += 256u) bins[i] = 0ull;
+        __syncthreads();
+    }
+    for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        gams_sw_row_t r;
+        int32_t cnt = 0;
+        if (!sw_row<kGc, kCount, true>(a, chunk * 256u + threadIdx.x, r, cnt)) continue;
+        if (lds)
+            sw_sum_put<kGc, kCount>(bins + (uint32_t)r.distance * kSumWords, r, cnt, bad);
+        else
+            sw_sum_put<kGc, kCount>(a.sum + (uint64_t)(uint32_t)r.distance * kSumWords, r, cnt, bad);
+    }
+    if (bad) *a.sum_bad = 1ull;
+    if (lds) {
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < words; i += 256u) {
+            const unsigned long long v = bins[i];
+            if (v) atomicAdd(a.sum + i, v);
+        }
+    }
+}
+
+template <bool kGc, bool kCount, bool kSum = false>
+__global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
+    if constexpr (kSum) {
+        sw_sum_chunks<kGc, kCount>(a0, a0.sum_chunks);
+    } else {
+        gams_sw_row_t r;
+        int32_t cnt = 0;
+        (void)sw_row<kGc, kCount, false>(a0, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, r, cnt);
+    }
+}
+
+// the call's table into the accumulator's groups of its tag, unless the call met a value it does not cover
+__global__ __launch_bounds__(256) void sw_sum_merge_kernel(const unsigned long long *call, const unsigned long long *bad,
+                                                           unsigned long long *acc, uint32_t words) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= words || *bad) return;
+    const unsigned long long v = call[i];
+    if (v) acc[i] += v;
 }
 
 // peak (src/cmd_gams/peak.rs:79) / any caller of cache_gc_content: one lane per range, the ranges of every
@@ -659,10 +751,12 @@ struct SwReq {
     uint64_t cap;
     uint64_t *row_off, *n_rows;
     const SwTextReq *tx;
+    gams_sw_summary_t *sum;              // gams_gpu_sw_summary_batch: the rows go into tag slot `tag` of it
+    uint32_t tag;
 };
 
 using SwCols = SwStage<SwCtg>;
-const std::string kSw = "gpu_sw", kSwText = "gpu_sw_text", kRangeGc = "gpu_range_gc";
+const std::string kSw = "gpu_sw", kSwText = "gpu_sw_text", kRangeGc = "gpu_range_gc", kSwSum = "gpu_sw_summary";
 
 // 1. the arguments; *nf = the features of the call, 0 with GAMS_OK: nothing to do
 int sw_check(const SwReq &q, uint32_t *nf) {
@@ -737,6 +831,43 @@ int sw_host_rows(const SwReq &q, uint32_t nf, const SwCols &in, std::vector<uint
     return GAMS_OK;
 }
 
+// 3'. the summarising kernel: the call's table zeroed, the rows added into it, the table merged into the tag's groups
+// unless the flag word behind it was raised; one read-back, of that word
+int sw_sum_launch(const SwReq &q, SwArgs &a, dim3 grid) {
+    gams_gpu_t *h = q.h;
+    gams_sw_summary_t *sum = q.sum;
+    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
+    const uint32_t words = ((uint32_t)sum->max + 1u) * kSumWords;
+    a.sum = sum->d_call;
+    a.sum_bad = sum->d_call + words;
+    a.sum_chunks = grid.x;                                     // what the storing kernel launches, walked by ...
+    grid.x = std::min<uint32_t>(grid.x, 8u * (uint32_t)std::max(h->cus, 1));   // ... the workgroups a device holds at once
+    hipStream_t st = h->compute;
+    GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_call, 0, ((size_t)words + 1) * 8, st));
+    if (do_gc && do_count)
+        hipLaunchKernelGGL((sw_kernel<true, true, true>), grid, dim3(256), 0, st, a);
+    else if (do_gc)
+        hipLaunchKernelGGL((sw_kernel<true, false, true>), grid, dim3(256), 0, st, a);
+    else if (do_count)
+        hipLaunchKernelGGL((sw_kernel<false, true, true>), grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL((sw_kernel<false, false, true>), grid, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(sw_sum_merge_kernel, dim3((words + 255u) / 256u), dim3(256), 0, st, sum->d_call, a.sum_bad,
+                       sum->d_acc + (size_t)q.tag * words, words);
+    GAMS_TRY(h, kSwSum, hipGetLastError());
+    return GAMS_OK;
+}
+// ... and the verdict, once the stream has run (the caller's stage mark may lie in between)
+int sw_sum_verdict(gams_gpu_t *h, const gams_sw_summary_t *sum) {
+    const uint32_t words = ((uint32_t)sum->max + 1u) * kSumWords;
+    GAMS_TRY(h, kSwSum, hipMemcpyAsync(h->pin_scratch, sum->d_call + words, 8, hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kSwSum, hipStreamSynchronize(h->compute));
+    if (h->pin_scratch[0])
+        return gams_fail(h, GAMS_EUNSUPPORTED, kSwSum + ": a statistic of 1000 or more (or below 0): summarise gams_gpu_sw_batch's "
+                                                        "rows on the host");
+    return GAMS_OK;
+}
+
 // 3. the kernel over the uploaded inputs `d`: n_out rows (and counts)
 int sw_launch(const SwReq &q, uint32_t nf, uint64_t n_out, const SwCols &d, gams_sw_row_t *d_rows, int32_t *d_cnt) {
     gams_gpu_t *h = q.h;
@@ -766,9 +897,12 @@ int sw_launch(const SwReq &q, uint32_t nf, uint64_t n_out, const SwCols &d, gams
     a.resize = q.resize;
     a.rows = d_rows;
     a.cap = n_out;
-    GAMS_TRY(h, kSw, hipEventRecord(h->k0, h->compute));
     const dim3 grid((unsigned)(((uint64_t)nf * (1u + 2u * (uint64_t)q.max) + 255) / 256));
-    if (do_gc && do_count)
+    GAMS_TRY(h, kSw, hipEventRecord(h->k0, h->compute));
+    if (q.sum) {
+        const int rc = sw_sum_launch(q, a, grid);
+        if (rc != GAMS_OK) return rc;
+    } else if (do_gc && do_count)
         hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(256), 0, h->compute, a);
     else if (do_gc)
         hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(256), 0, h->compute, a);
@@ -930,7 +1064,7 @@ int sw_batch_impl(const SwReq &q) {
     // Inputs are assembled in one page-locked block (one DMA): ctgs | fs | fe | fctg | off
     auto inputs = [&](Carver &c) { return sw_stage_layout<SwCtg>(c, q.n_sel, nf, true); };
     const size_t in_bytes = layout_bytes(inputs);
-    const bool size_query = !q.tx && ((!q.rows && !q.count) || q.cap == 0);
+    const bool size_query = !q.tx && !q.sum && ((!q.rows && !q.count) || q.cap == 0);
     PoolBlock dev(h, false), pin(h, true);
     std::vector<uint64_t> crow((size_t)q.n_sel + 1, 0);    // first row of every selected ctg (text mode)
     std::vector<uint64_t> off_host(size_query ? (size_t)nf + 1 : 0);   // a size query: no device, no pinned memory
@@ -946,7 +1080,8 @@ int sw_batch_impl(const SwReq &q) {
     if (size_query) return GAMS_OK;
     // the counts and the geometry read no sequence byte: a count-only call leaves the bytes alone
     if (do_gc && (rc = gams_seqset_gcindex(h, q.s)) != GAMS_OK) return rc;
-    const uint64_t n_out = std::min<uint64_t>(tot, q.tx ? tot : q.cap);   // text mode: every row, kept on the device
+    // text mode: every row, kept on the device; the summary stores none
+    const uint64_t n_out = q.sum ? 0 : std::min<uint64_t>(tot, q.tx ? tot : q.cap);
     SwCols d{};
     gams_sw_row_t *d_rows = nullptr;
     int32_t *d_cnt = nullptr;
@@ -959,6 +1094,7 @@ int sw_batch_impl(const SwReq &q) {
     carve(dev.p, device);
     GAMS_TRY(h, kSw, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
     if ((rc = sw_launch(q, nf, n_out, d, d_rows, d_cnt)) != GAMS_OK) return rc;
+    if (q.sum) return sw_sum_verdict(h, q.sum);
     if (q.tx) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt);
     // 5. read back
     if (q.rows) GAMS_TRY(h, kSw, hipMemcpyAsync(q.rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
@@ -970,7 +1106,7 @@ int sw_batch_impl(const SwReq &q) {
 
 int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
                         uint64_t *n_rows) {
-    const std::string who = "gpu_sw_feature_text";
+    const std::string who = J.summary ? "gpu_sw_feature_summary" : "gpu_sw_feature_text";
     const bool do_gc = (J.actions & GAMS_SW_GC) != 0, do_count = (J.actions & GAMS_SW_COUNT) != 0;
     const uint32_t n_ctg = J.n_ctg, nf = J.nf;
     hipStream_t st = h->compute;
@@ -1005,9 +1141,11 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     GAMS_TRY(h, who, stage(SWF_GEOM, true));
     hipLaunchKernelGGL(sw_geom_kernel, dim3(nbf), dim3(256), 0, st, d_ctgs, J.fctg, J.fs, J.fe, nf, J.size, J.max, d_cnt_f, d_blk);
     hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_blk, nbf, d_blk_off, J.words, 0u);
-    hipLaunchKernelGGL(sw_row_off_kernel, dim3(nbf), dim3(256), 0, st, d_cnt_f, d_blk_off, nf, nbf, d_row_off);
-    hipLaunchKernelGGL(sw_ctg_row_off_kernel, dim3(n_ctg / 256u + 1u), dim3(256), 0, st, d_row_off, J.d_bucket_off, n_ctg,
-                       d_ctg_row_off);
+    if (!J.summary) {   // (the summary asks where no row lies)
+        hipLaunchKernelGGL(sw_row_off_kernel, dim3(nbf), dim3(256), 0, st, d_cnt_f, d_blk_off, nf, nbf, d_row_off);
+        hipLaunchKernelGGL(sw_ctg_row_off_kernel, dim3(n_ctg / 256u + 1u), dim3(256), 0, st, d_row_off, J.d_bucket_off, n_ctg,
+                           d_ctg_row_off);
+    }
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, stage(SWF_GEOM, false));
     // 3. the one read-back: the rows and the flags
@@ -1024,9 +1162,13 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
         d_rows = c.take<gams_sw_row_t>(std::max<uint64_t>(tot, 1));
         d_cnt = do_count ? c.take<int32_t>(std::max<uint64_t>(tot, 1)) : nullptr;
     };
-    GAMS_TRY(h, who, r_dev.alloc(layout_bytes(rows)));
-    carve(r_dev.p, rows);
+    if (!J.summary) {
+        GAMS_TRY(h, who, r_dev.alloc(layout_bytes(rows)));
+        carve(r_dev.p, rows);
+    }
     SwReq q{};
+    q.sum = J.summary;
+    q.tag = J.tag;
     q.h = h;
     q.s = J.s;
     q.size = J.size;
@@ -1044,6 +1186,10 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     const int rc = sw_launch(q, nf, tot, d, d_rows, d_cnt);
     if (rc != GAMS_OK) return rc;
     GAMS_TRY(h, who, stage(SWF_ROWS, false));
+    if (J.summary) {   // 4'. the rows went into the accumulator: nothing to print
+        *n_rows = tot;
+        return sw_sum_verdict(h, J.summary);
+    }
     // 5. the text, with the ids composed on the device
     const uint64_t per_row = 8ull + J.max_id + 1ull + 10ull + J.max_chr + (do_count ? 112ull : 96ull);
     SwTextArgs ta{};
@@ -1118,6 +1264,99 @@ extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel,
                                 const uint64_t **ctg_off, uint64_t *n_rows) {
     return gams_gpu_sw_text_actions(h, s, n_sel, ctg_index, chr, chr_start, feat_off, feat_start, feat_end, feat_id, size,
                                     max, resize, GAMS_SW_GC, nullptr, nullptr, text, text_bytes, ctg_off, n_rows);
+}
+
+// ---- the accumulator of the sw summaries -----------------------------------------------------------------------------
+int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, int32_t size, int32_t max,
+                          int32_t resize, uint32_t actions, uint32_t tag) {
+    if (!sum) return gams_fail(h, GAMS_EINVAL, who + ": null argument");
+    if (sum->size != size || sum->max != max || sum->resize != resize || sum->actions != actions)
+        return gams_fail(h, GAMS_EINVAL, who + ": the accumulator was created for other size, max, resize or actions");
+    if (tag >= sum->n_tags) return gams_fail(h, GAMS_EINVAL, who + ": tag slot beyond the accumulator's tags");
+    return GAMS_OK;
+}
+
+extern "C" int gams_sw_summary_create(gams_gpu_t *h, int32_t max, uint32_t n_tags, uint32_t actions, int32_t size,
+                                      int32_t resize, gams_sw_summary_t **out) {
+    if (!h || !out) return gams_fail(h, GAMS_EINVAL, "sw_summary_create: null argument");
+    *out = nullptr;
+    if (n_tags == 0 || size < 2 || max < 0 || max > (1 << 24) || resize < 2 || (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)))
+        return gams_fail(h, GAMS_EINVAL, "sw_summary_create: n_tags >= 1, size >= 2, 0 <= max <= 2^24, resize >= 2, known action bits");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    const size_t words = ((size_t)max + 1) * kSumWords;
+    gams_sw_summary_t *sum = new gams_sw_summary_t();
+    sum->size = size;
+    sum->max = max;
+    sum->resize = resize;
+    sum->actions = actions;
+    sum->n_tags = n_tags;
+    hipError_t e = hipMalloc(&sum->d_acc, words * n_tags * 8);
+    if (e == hipSuccess) e = hipMalloc(&sum->d_call, (words + 1) * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(sum->d_acc, 0, words * n_tags * 8, h->compute);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();   // reported below, not left sticky
+        (void)hipFree(sum->d_acc);
+        (void)hipFree(sum->d_call);
+        delete sum;
+        return gams_fail(h, GAMS_ENOMEM, std::string("sw_summary_create: ") + hipGetErrorString(e));
+    }
+    *out = sum;
+    return GAMS_OK;
+}
+
+extern "C" int gams_sw_summary_reset(gams_gpu_t *h, gams_sw_summary_t *sum) {
+    if (!h || !sum) return gams_fail(h, GAMS_EINVAL, "sw_summary_reset: null argument");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_acc, 0, ((size_t)sum->max + 1) * kSumWords * sum->n_tags * 8, h->compute));
+    return GAMS_OK;
+}
+
+extern "C" int gams_sw_summary_read(gams_gpu_t *h, gams_sw_summary_t *sum, uint64_t *count, uint64_t *s, uint64_t *nan,
+                                    uint64_t *rg_count) {
+    if (!h || !sum) return gams_fail(h, GAMS_EINVAL, "sw_summary_read: null argument");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    const size_t n = ((size_t)sum->max + 1) * sum->n_tags;
+    std::vector<unsigned long long> w(n * kSumWords);
+    GAMS_TRY(h, kSwSum, hipMemcpyAsync(w.data(), sum->d_acc, w.size() * 8, hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kSwSum, hipStreamSynchronize(h->compute));
+    for (size_t g = 0; g < n; ++g) {
+        const unsigned long long *v = w.data() + g * kSumWords;
+        if (count) count[g] = v[SUM_COUNT];
+        if (rg_count) rg_count[g] = v[SUM_C];
+        for (uint32_t k = 0; k < 4u; ++k) {
+            if (s) s[4 * g + k] = v[SUM_S + k];
+            if (nan) nan[4 * g + k] = v[SUM_NAN + k];
+        }
+    }
+    return GAMS_OK;
+}
+
+extern "C" void gams_sw_summary_destroy(gams_gpu_t *h, gams_sw_summary_t *sum) {
+    if (!sum) return;
+    if (h) {
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->compute);   // a call into it may still be queued
+    }
+    (void)hipFree(sum->d_acc);
+    (void)hipFree(sum->d_call);
+    delete sum;
+}
+
+extern "C" int gams_gpu_sw_summary_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                         const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                                         const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                                         gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
+                                         uint64_t *n_rows) {
+    if (!h || !n_rows || (n_sel && !feat_off)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: null argument");
+    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: unknown action bits");
+    if ((actions & GAMS_SW_COUNT) && (!rg_ix || (n_sel && !rg_group)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: GAMS_SW_COUNT without an rg index or rg groups");
+    const int rc = gams_sw_summary_check(h, kSwSum, sum, size, max, resize, actions, tag);
+    if (rc != GAMS_OK) return rc;
+    const bool cnt = (actions & GAMS_SW_COUNT) != 0;
+    SwReq q{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions,
+            cnt ? rg_ix : nullptr, cnt ? rg_group : nullptr, nullptr, nullptr, 0, nullptr, n_rows, nullptr, sum, tag};
+    return sw_batch_impl(q);
 }
 
 extern "C" int gams_gpu_sw(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_start,

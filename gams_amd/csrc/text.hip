@@ -1520,18 +1520,22 @@ struct SwFeatJob {
     uint32_t actions;
     const gams_index_t *rg_ix;
     const uint32_t *rg_group;
+    gams_sw_summary_t *summary;               // gams_gpu_sw_feature_summary: the rows go into tag slot `tag` of it, and
+    uint32_t tag;                             // the three text outputs below are NULL
 };
 
 int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_t n_bytes, const char **text,
                    uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_features, uint64_t *n_rows) {
-    const std::string who = "gpu_sw_feature_text";
+    const std::string who = J.summary ? "gpu_sw_feature_summary" : "gpu_sw_feature_text";
     const uint64_t n_ctg = J.ctg_ix->m;
     const bool do_gc = (J.actions & GAMS_SW_GC) != 0;
-    *text = "";
-    *text_bytes = 0;
     *n_features = 0;
     *n_rows = 0;
-    memset(text_off, 0, (n_ctg + 1) * 8);
+    if (!J.summary) {
+        *text = "";
+        *text_bytes = 0;
+        memset(text_off, 0, (n_ctg + 1) * 8);
+    }
     for (uint64_t c = 0; c < n_ctg; ++c)
         if (J.chr_end[c] < J.chr_start[c]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg ends before it starts");
     GAMS_HIP(h, hipSetDevice(h->device));
@@ -1622,9 +1626,11 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         S.max_chr = J.chr->max_len;
         S.max_id = J.ids->max_len;
         S.words = g.words;
+        S.summary = J.summary;
+        S.tag = J.tag;
         const int rc = gams_launch_sw_cols(h, S, text, text_bytes, text_off, n_rows);
         if (rc != GAMS_OK) return rc;
-        rg_timed(h, SWF_STAGES);
+        rg_timed(h, J.summary ? SWF_ROWS + 1 : SWF_STAGES);
         return GAMS_OK;
     });
 }
@@ -2526,8 +2532,36 @@ int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_
         return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: chr_names must name every group of ctg_ix");
     if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw_feature_text: max beyond 2^24 windows a side");
     return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
-                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr},
+                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, nullptr, 0u},
                           bytes, n_bytes, text, text_bytes, text_off, n_features, n_rows);
+}
+
+int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                                const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                                const int32_t *chr_end, const char *bytes, uint64_t n_bytes, int32_t size, int32_t max,
+                                int32_t resize, uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
+                                gams_sw_summary_t *sum, uint32_t tag, uint64_t *n_features, uint64_t *n_rows) {
+    // the checks of gams_gpu_sw_feature_text, in its order, then the accumulator's
+    const std::string who = "gpu_sw_feature_summary";
+    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
+    if (!h || !ctg_ix || !chr_names || !ctg_ids || (ctg_ix->m && (!chr_start || !chr_end)) || (n_bytes && !bytes) || !sum ||
+        !n_features || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, who + ": null argument");
+    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, who + ": unknown action bits");
+    if (do_gc && (!s || (ctg_ix->m && !ctg_index)))
+        return gams_fail(h, GAMS_EINVAL, who + ": GAMS_SW_GC without a seqset or the ctgs' slots");
+    if (do_count && (!rg_ix || (ctg_ix->m && !rg_group)))
+        return gams_fail(h, GAMS_EINVAL, who + ": GAMS_SW_COUNT without an rg index or rg groups");
+    if (size < 2 || max < 0 || resize < 2)
+        return gams_fail(h, GAMS_EINVAL, who + ": size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
+    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, who + ": ctg_ids must name every interval of ctg_ix");
+    if (chr_names->t.n < ctg_ix->n_groups) return gams_fail(h, GAMS_EINVAL, who + ": chr_names must name every group of ctg_ix");
+    if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": max beyond 2^24 windows a side");
+    const int rc = gams_sw_summary_check(h, who, sum, size, max, resize, actions, tag);
+    if (rc != GAMS_OK) return rc;
+    return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
+                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, sum, tag},
+                          bytes, n_bytes, nullptr, nullptr, nullptr, n_features, n_rows);
 }
 
 int gams_gpu_locate_seq_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,

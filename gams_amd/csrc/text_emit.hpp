@@ -44,6 +44,10 @@ __device__ __forceinline__ char *put_bytes(char *q, const char *src, uint64_t n)
     return q + n;
 }
 
+// the integer m of a round4 value v in [0, 1000), the f32 nearest to m / 10^4: exact in double.  What sw_put_f4 prints
+// and what the sw summary adds up (sw.hip), so that the table and the text cannot disagree
+__device__ __forceinline__ uint32_t sw_f4_units(float v) { return (uint32_t)((double)v * 10000.0 + 0.5); }
+
 // a round4 value (the f32 nearest to m / 10^4) as Rust prints it; returns the length (p == nullptr: length only);
 // *bad set for values not covered
 __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
@@ -59,7 +63,7 @@ __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
         if (p) { p[0] = '-'; p[1] = '0'; }
         return 2u;
     }
-    const uint32_t m = (uint32_t)((double)v * 10000.0 + 0.5);     // v is the f32 nearest to m / 10^4: exact in double
+    const uint32_t m = sw_f4_units(v);
     const uint32_t ip = m / 10000u;
     uint32_t fr = m % 10000u, nd = 4u;
     while (nd && fr % 10u == 0u) {

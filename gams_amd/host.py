@@ -178,6 +178,15 @@ def load():
     L.gams_host_sw_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                     C.c_char_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_char_p,
                                     C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_sw_summary.restype = C.c_void_p
+    L.gams_host_sw_summary.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
+                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_uint64)]
+    L.gams_host_sw_summarise_rows.restype = C.c_int
+    L.gams_host_sw_summarise_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p]
+    L.gams_host_sw_summary_text.restype = C.c_void_p
+    L.gams_host_sw_summary_text.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.gams_host_gen.restype = C.c_void_p
     L.gams_host_gen.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_int32]
     L.gams_host_read_fasta.restype = C.c_void_p
@@ -799,6 +808,87 @@ def sw_text(eng, ctgs, data, size=100, mx=20, resize=500, actions=("gc",), rg_re
         slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
         p = entry(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p, slots.ctypes.data, *tail)
     return _take_bytes(p, out_len)
+
+
+def _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset):
+    """-> (text, the distinct tags in byte order or None, the table's words as [slots, mx + 1, SW_SUMMARY_WORDS])"""
+    rg_data = _one_rg_source(rg_records, rg_data)
+    mask = sw_actions(actions)
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    datas = list(data) if isinstance(data, (list, tuple)) else [data]
+    if tags is not None:
+        if isinstance(tags, (str, bytes)) or len(tags) != len(datas):
+            raise ValueError("sw_summary: tags is None or one tag per file")
+        tags = [t.encode("latin-1") if isinstance(t, str) else bytes(t) for t in tags]
+        if any(b"\0" in t for t in tags):
+            raise ValueError("sw_summary: a tag holds a NUL")
+    nf, fp, fl, _keep = _files(datas)
+    tagp = None if tags is None else (C.c_char_p * max(nf, 1))(*tags)
+    slots_of = None if tags is None else sorted(set(tags))
+    rg_lines = _rg_lines(rg_records) if (mask & _lib.SW_COUNT) and rg_data is None else None
+    nr, rp, rl, _keep_rg = _files(rg_data if isinstance(rg_data, list) else ([] if rg_data is None else [rg_data]))
+    table = np.zeros((1 if tags is None else len(slots_of), mx + 1, _lib.SW_SUMMARY_WORDS), np.uint64)
+    out_len = C.c_uint64()
+    tail = (nf, fp, fl, tagp, size, mx, resize, mask, rg_lines, nr, rp, rl, table.ctypes.data, C.byref(out_len))
+    if seqset is None:
+        seqs = None
+        if mask & _lib.SW_GC:
+            bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
+                                         else c["seq"]) for c in ctgs]
+            seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        p = load().gams_host_sw_summary(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, *tail)
+    else:
+        slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
+        slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
+        p = load().gams_host_sw_summary(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
+                                        slots.ctypes.data, *tail)
+    return _take_bytes(p, out_len), slots_of, table
+
+
+def _sw_summary_arrays(slots_of, table):
+    return {"tags": slots_of, "count": table[:, :, 0].copy(), "sum": table[:, :, 1:5].copy(), "nan": table[:, :, 5:9].copy(),
+            "rg_count": table[:, :, 9].copy()}
+
+
+def sw_summary(eng, ctgs, data, tags=None, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None,
+               seqset=None):
+    """The table the rows of sw_text are loaded for (fsw-distance.tera.sql; with tags fsw-distance-tag.tera.sql), reduced
+    on the device -- no row leaves it (the host's passes for a file the device refuses; last_operator_device says
+    whether every file took the device's route).  data: one feature file's bytes or a list of them, each read as sw_text
+    reads it (drop-first is per file); tags: None or one string per file.  Returns the text as bytes: a header, then one
+    line per distance with rows -- per (tag, distance), ordered by tag bytes, then distance --: the averages of
+    gc_content, gc_mean, gc_stddev and gc_cv (with the gc action), of rg_count (with count) and COUNT, the rows.  An
+    average is the exact sum of the printed values over COUNT, rounded to 4 places, ties to even, trailing zeros dropped;
+    `nan` where a row's value is NaN.  seqset, the per-ctg slot, actions, rg_records and rg_data as for sw_text."""
+    return _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset)[0]
+
+
+def sw_summary_table(eng, ctgs, data, tags=None, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None,
+                     seqset=None):
+    """sw_summary's raw integers: {"tags": the distinct tags in byte order (None without tags), "count": [slots, mx + 1],
+    "sum": [slots, mx + 1, 4] (the sums of m, a statistic being m / 10^4, for gc_content, gc_mean, gc_stddev, gc_cv),
+    "nan": [slots, mx + 1, 4] (the rows whose statistic is NaN, left out of the sums), "rg_count": [slots, mx + 1]},
+    uint64, one slot without tags"""
+    _, slots_of, table = _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset)
+    return _sw_summary_arrays(slots_of, table)
+
+
+def sw_summarise_rows(rows, counts=None, mx=20, actions=("gc",), table=False):
+    """The host's summariser over rows of _lib.SW_ROW_DTYPE (and their rg counts, int32, with the count action): the text
+    of sw_summary without tags, or with table=True the integers as sw_summary_table gives them.  No engine."""
+    L = load()
+    mask = sw_actions(actions)
+    rows = np.ascontiguousarray(rows, _lib.SW_ROW_DTYPE)
+    cnt = None if counts is None else np.ascontiguousarray(counts, np.int32)
+    if cnt is not None and cnt.size != rows.size:
+        raise ValueError("sw_summarise_rows: one count per row")
+    words = np.zeros((1, mx + 1, _lib.SW_SUMMARY_WORDS), np.uint64)
+    _check_rc(L.gams_host_sw_summarise_rows(rows.ctypes.data, None if cnt is None else cnt.ctypes.data, rows.size, mx, mask,
+                                            words.ctypes.data))
+    if table:
+        return _sw_summary_arrays(None, words)
+    out_len = C.c_uint64()
+    return _take_bytes(L.gams_host_sw_summary_text(words.ctypes.data, 1, None, mx, mask, C.byref(out_len)), out_len)
 
 
 def fmt_f32_short(v):

@@ -1992,6 +1992,77 @@ std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::ve
     return peak_text(h, ctgs, sg.s, slots, bytes, n, device);
 }
 
+// What sw_text and sw_summary set up once for a call: the Locator with its text tables and, under GAMS_SW_COUNT, its rg
+// index, and per interval of the ctg index (the Locator's order) the seqset slot, chr_start, chr_end and the rg group
+struct SwSetup {
+    Locator loc;
+    size_t n_ctg;
+    std::vector<uint32_t> slot, rg_group;
+    std::vector<int32_t> cs, ce;
+    SwSetup(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots, bool do_count,
+            const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes, size_t rg_n,
+            const std::vector<FileBytes> *rg_files)
+        : loc(h, ctgs) {
+        loc.text_tables();
+        n_ctg = loc.ctgs_.size();
+        slot.assign(std::max<size_t>(n_ctg, 1), UINT32_MAX);
+        rg_group.assign(std::max<size_t>(n_ctg, 1), UINT32_MAX);
+        cs.assign(std::max<size_t>(n_ctg, 1), 0);
+        ce.assign(std::max<size_t>(n_ctg, 1), 0);
+        if (seqset)
+            for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
+        if (do_count) {                                                  // idx:rg: on the call's ctg table, once
+            if (rg_files)
+                loc.set_rg_index_text(*rg_files);
+            else if (rg_bytes)
+                loc.set_rg_index_text(rg_bytes, rg_n);
+            else
+                loc.set_rg_index(*rgs);
+        }
+        for (size_t c = 0; c < n_ctg; ++c) {
+            cs[c] = loc.ctgs_[c].chr_start;
+            ce[c] = loc.ctgs_[c].chr_end;
+            if (do_count) rg_group[c] = loc.rg_group_of(loc.ctgs_[c].id);
+        }
+    }
+    gams_index_t *ctg_ix() const { return loc.ctg_ix_; }
+    const gams_names_t *chr_names() const { return loc.chr_names_; }
+    const gams_names_t *ctg_ids() const { return loc.ctg_ids_; }
+    // the host's passes over one feature file: read_range over the lines and the ids of feature_records, as the arrays
+    // the batch entries take -- the ctgs with kept features in id order (BTreeMap order)
+    struct Arrays {
+        std::vector<uint32_t> sel, index, lens, group;
+        std::vector<int32_t> sel_start, fs, fe;
+        std::vector<uint64_t> feat_off{0};
+        std::vector<std::string> ids;
+        std::vector<std::vector<Feature>> feat_of;
+    };
+    Arrays arrays(const char *bytes, size_t n, bool do_gc, const char *who) {
+        Arrays A;
+        const auto ranges_of = read_range(loc, text_lines(bytes, n));
+        for (auto &kv : ranges_of) {
+            if (kv.second.empty()) continue;
+            const uint32_t c = loc.ctg_slot_.at(kv.first);
+            if (do_gc && slot[c] == UINT32_MAX) throw Error(GAMS_EINVAL, std::string(who) + ": no sequence for " + kv.first);
+            A.index.push_back(do_gc ? slot[c] : (uint32_t)A.sel.size());
+            A.sel.push_back(c);
+            A.lens.push_back((uint32_t)(ce[c] - cs[c] + 1));
+            A.sel_start.push_back(cs[c]);
+            A.group.push_back(rg_group[c]);
+            A.feat_of.emplace_back();
+            int32_t serial = 0;
+            for (const Range &r : kv.second) {
+                A.ids.push_back("feature:" + kv.first + ":" + std::to_string(++serial));   // feature.rs:81-83
+                A.fs.push_back(r.start);
+                A.fe.push_back(r.end);
+                A.feat_of.back().push_back(Feature{A.ids.back(), r.start, r.end});
+            }
+            A.feat_off.push_back(A.fs.size());
+        }
+        return A;
+    }
+};
+
 std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
                     const char *bytes, size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs,
                     const char *rg_bytes, size_t rg_n, bool *device, const TextSink *sink, const std::vector<FileBytes> *rg_files) {
@@ -2007,27 +2078,11 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *
     if (do_gc && !seqset) throw Error(GAMS_EINVAL, "sw_text: --action gc needs a seqset");
     if (seqset && slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "sw_text: one seqset slot per ctg");
     if (do_count && !rgs && !rg_bytes && !rg_files) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
-    Locator loc(h, ctgs);
-    loc.text_tables();
-    const size_t n_ctg = loc.ctgs_.size();
-    // per interval of the ctg index (the Locator's order): seqset slot, chr_start, chr_end, rg group
-    std::vector<uint32_t> slot(std::max<size_t>(n_ctg, 1), UINT32_MAX), rg_group(std::max<size_t>(n_ctg, 1), UINT32_MAX);
-    std::vector<int32_t> cs(std::max<size_t>(n_ctg, 1), 0), ce(std::max<size_t>(n_ctg, 1), 0);
-    if (seqset)
-        for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
-    if (do_count) {                                                      // idx:rg: on the call's ctg table, once
-        if (rg_files)
-            loc.set_rg_index_text(*rg_files);
-        else if (rg_bytes)
-            loc.set_rg_index_text(rg_bytes, rg_n);
-        else
-            loc.set_rg_index(*rgs);
-    }
-    for (size_t c = 0; c < n_ctg; ++c) {
-        cs[c] = loc.ctgs_[c].chr_start;
-        ce[c] = loc.ctgs_[c].chr_end;
-        if (do_count) rg_group[c] = loc.rg_group_of(loc.ctgs_[c].id);
-    }
+    SwSetup U(h, ctgs, seqset, slots, do_count, rgs, rg_bytes, rg_n, rg_files);
+    Locator &loc = U.loc;
+    const size_t n_ctg = U.n_ctg;
+    const std::vector<uint32_t> &slot = U.slot, &rg_group = U.rg_group;
+    const std::vector<int32_t> &cs = U.cs, &ce = U.ce;
     std::vector<uint64_t> off(n_ctg + 1, 0);
     const char *text = nullptr;
     uint64_t text_bytes = 0, feats = 0, rows = 0;
@@ -2062,31 +2117,12 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *
     }
     // the host's passes: read_range over the lines, the ids of feature_records, the existing text entry on the same
     // seqset (without gc no sequence is read: a seqset of the lengths alone stands in)
-    const auto ranges_of = read_range(loc, text_lines(bytes, n));
-    std::vector<uint32_t> sel, index, lens, group;
-    std::vector<int32_t> sel_start, fs, fe;
-    std::vector<uint64_t> feat_off{0};
-    std::vector<std::string> ids;
-    std::vector<std::vector<Feature>> feat_of;
-    for (auto &kv : ranges_of) {                                         // BTreeMap order = ctg id order
-        if (kv.second.empty()) continue;
-        const uint32_t c = loc.ctg_slot_.at(kv.first);
-        if (do_gc && slot[c] == UINT32_MAX) throw Error(GAMS_EINVAL, "sw_text: no sequence for " + kv.first);
-        index.push_back(do_gc ? slot[c] : (uint32_t)sel.size());
-        sel.push_back(c);
-        lens.push_back((uint32_t)(ce[c] - cs[c] + 1));
-        sel_start.push_back(cs[c]);
-        group.push_back(rg_group[c]);
-        feat_of.emplace_back();
-        int32_t serial = 0;
-        for (const Range &r : kv.second) {
-            ids.push_back("feature:" + kv.first + ":" + std::to_string(++serial));   // feature.rs:81-83
-            fs.push_back(r.start);
-            fe.push_back(r.end);
-            feat_of.back().push_back(Feature{ids.back(), r.start, r.end});
-        }
-        feat_off.push_back(fs.size());
-    }
+    const SwSetup::Arrays A = U.arrays(bytes, n, do_gc, "sw_text");
+    const std::vector<uint32_t> &sel = A.sel, &index = A.index, &lens = A.lens, &group = A.group;
+    const std::vector<int32_t> &sel_start = A.sel_start, &fs = A.fs, &fe = A.fe;
+    const std::vector<uint64_t> &feat_off = A.feat_off;
+    const std::vector<std::string> &ids = A.ids;
+    const std::vector<std::vector<Feature>> &feat_of = A.feat_of;
     const uint32_t n_sel = (uint32_t)sel.size();
     if (n_sel == 0) return done(std::move(out));
     SeqSetGuard sg{h};
@@ -2141,6 +2177,188 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vect
     check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
     check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
     return sw_text(h, ctgs, sg.s, slots, bytes, n, a, rgs, rg_bytes, rg_n, device, sink, rg_files);
+}
+
+// ---- the per-distance summary of the sw rows ---------------------------------------------------------
+void sw_summarise_rows(const gams_sw_row_t *rows, const int32_t *counts, uint64_t n, int32_t max, uint32_t actions,
+                       uint64_t *table) {
+    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
+    if (do_count && n && !counts) throw Error(GAMS_EINVAL, "sw_summarise_rows: GAMS_SW_COUNT without the counts");
+    for (uint64_t r = 0; r < n; ++r) {
+        const gams_sw_row_t &w = rows[r];
+        if (w.distance < 0 || w.distance > max) throw Error(GAMS_EINVAL, "sw_summarise_rows: a distance outside [0, max]");
+        uint64_t *g = table + (size_t)w.distance * GAMS_SW_SUMMARY_WORDS;
+        g[0] += 1;
+        if (do_gc) {
+            const float v[4] = {w.gc_content, w.gc_mean, w.gc_stddev, w.gc_cv};
+            for (int k = 0; k < 4; ++k) {
+                if (v[k] != v[k])
+                    g[5 + k] += 1;
+                else if (!(v[k] >= 0.0f) || std::isinf(v[k]))
+                    throw Error(GAMS_EUNSUPPORTED, "sw_summarise_rows: a negative or infinite statistic has no place in the table");
+                else   // the integer nearest to v * 10^4 -- below 1000 the m the text prints (sw_put_f4), beyond it its continuation
+                    g[1 + k] += (uint64_t)((double)v[k] * 10000.0 + 0.5);
+            }
+        }
+        if (do_count) g[9] += (uint64_t)(int64_t)counts[r];
+    }
+}
+
+std::string sw_summary_header(uint32_t actions, bool tagged) {
+    std::string o = tagged ? "tag\tdistance" : "distance";
+    if (actions & GAMS_SW_GC) o += "\tAVG_gc_content\tAVG_gc_mean\tAVG_gc_stddev\tAVG_gc_cv";
+    if (actions & GAMS_SW_COUNT) o += "\tAVG_rg_count";
+    return o + "\tCOUNT\n";
+}
+
+namespace {
+// num / den to the nearest integer, ties to even, printed as q / 10^4 with the trailing zeros dropped (as sw_put_f4 prints)
+std::string sw_avg4(unsigned __int128 num, uint64_t den) {
+    unsigned __int128 q = num / den;
+    const unsigned __int128 r2 = (num % den) * 2;
+    if (r2 > den || (r2 == den && (q & 1))) ++q;
+    std::string ip, o;
+    unsigned __int128 i = q / 10000;
+    do {
+        ip.insert(ip.begin(), (char)('0' + (int)(i % 10)));
+        i /= 10;
+    } while (i);
+    uint32_t fr = (uint32_t)(q % 10000), nd = 4;
+    while (nd && fr % 10 == 0) {
+        fr /= 10;
+        --nd;
+    }
+    o = ip;
+    if (nd) {
+        char buf[8];
+        std::snprintf(buf, sizeof buf, ".%0*u", (int)nd, fr);
+        o += buf;
+    }
+    return o;
+}
+}  // namespace
+
+std::string SwSummaryTable::text() const {
+    const bool tagged = !tags.empty();
+    std::string o = sw_summary_header(actions, tagged);
+    const size_t n_tags = tagged ? tags.size() : 1;
+    for (size_t t = 0; t < n_tags; ++t)
+        for (int32_t d = 0; d <= max; ++d) {
+            const uint64_t *g = words.data() + (t * ((size_t)max + 1) + (size_t)d) * GAMS_SW_SUMMARY_WORDS;
+            if (g[0] == 0) continue;
+            if (tagged) o += tags[t] + "\t";
+            o += std::to_string(d);
+            if (actions & GAMS_SW_GC)
+                for (int k = 0; k < 4; ++k) o += "\t" + (g[5 + k] ? std::string("nan") : sw_avg4(g[1 + k], g[0]));
+            if (actions & GAMS_SW_COUNT) o += "\t" + sw_avg4((unsigned __int128)g[9] * 10000u, g[0]);
+            o += "\t" + std::to_string(g[0]) + "\n";
+        }
+    return o;
+}
+
+SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                          const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
+                          const std::map<std::string, std::vector<Range>> *rgs, const std::vector<FileBytes> *rg_files,
+                          bool *device) {
+    if (device) *device = false;
+    if (rgs && rg_files) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+    const bool do_gc = (a.actions & GAMS_SW_GC) != 0, do_count = (a.actions & GAMS_SW_COUNT) != 0;
+    if (do_gc && !seqset) throw Error(GAMS_EINVAL, "sw_summary: --action gc needs a seqset");
+    if (seqset && slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "sw_summary: one seqset slot per ctg");
+    if (do_count && !rgs && !rg_files) throw Error(GAMS_EINVAL, "sw: --action count needs the rg ranges");
+    if (tags && tags->size() != files.size()) throw Error(GAMS_EINVAL, "sw_summary: one tag per file");
+    if (a.max < 0) throw Error(GAMS_EINVAL, "sw_summary: max >= 0");
+    SwSummaryTable T;
+    T.max = a.max;
+    T.actions = a.actions;
+    if (tags) {                                                          // the slots: the distinct tags in byte order
+        T.tags = *tags;
+        std::sort(T.tags.begin(), T.tags.end());
+        T.tags.erase(std::unique(T.tags.begin(), T.tags.end()), T.tags.end());
+    }
+    const uint32_t n_tags = (uint32_t)std::max<size_t>(T.tags.size(), 1);
+    const size_t group_words = ((size_t)a.max + 1) * GAMS_SW_SUMMARY_WORDS;
+    T.words.assign(group_words * n_tags, 0);                             // what the host's passes add; the device's joins below
+    SwSetup U(h, ctgs, seqset, slots, do_count, rgs, nullptr, 0, rg_files);
+    struct Acc {
+        gams_gpu_t *h;
+        gams_sw_summary_t *p = nullptr;
+        ~Acc() { gams_sw_summary_destroy(h, p); }
+    } acc{h};
+    check(h, gams_sw_summary_create(h, a.max, n_tags, a.actions, a.size, a.resize, &acc.p));
+    bool all_device = true;
+    for (size_t f = 0; f < files.size(); ++f) {
+        const uint32_t tag = tags ? (uint32_t)(std::lower_bound(T.tags.begin(), T.tags.end(), (*tags)[f]) - T.tags.begin()) : 0u;
+        const char *bytes = files[f].first ? files[f].first : "";
+        uint64_t feats = 0, rows = 0;
+        const int rc = gams_gpu_sw_feature_summary(h, do_gc ? seqset : nullptr, U.ctg_ix(), U.chr_names(), U.ctg_ids(),
+                                                   U.slot.data(), U.cs.data(), U.ce.data(), bytes, files[f].second, a.size, a.max,
+                                                   a.resize, a.actions, U.loc.rg_index(), U.rg_group.data(), acc.p, tag, &feats,
+                                                   &rows);
+        if (rc != GAMS_EUNSUPPORTED) {
+            check(h, rc);
+            continue;
+        }
+        // the host's passes for this file: read_range and the arrays; with gc the rows of gams_gpu_sw_batch (and their
+        // counts) summarised here, without it -- no statistic, nothing to refuse -- the array entry of the device
+        all_device = false;
+        const SwSetup::Arrays A = U.arrays(bytes, files[f].second, do_gc, "sw_summary");
+        const uint32_t n_sel = (uint32_t)A.sel.size();
+        if (n_sel == 0) continue;
+        if (!do_gc) {
+            SeqSetGuard sg{h};
+            check(h, gams_seqset_create(h, n_sel, A.lens.data(), &sg.s));
+            check(h, gams_gpu_sw_summary_batch(h, sg.s, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
+                                               A.fe.data(), a.size, a.max, a.resize, a.actions, U.loc.rg_index(), A.group.data(),
+                                               acc.p, tag, &rows));
+            continue;
+        }
+        check(h, gams_gpu_sw_batch(h, seqset, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
+                                   A.fe.data(), a.size, a.max, a.resize, nullptr, 0, nullptr, &rows));
+        std::vector<gams_sw_row_t> rv(std::max<uint64_t>(rows, 1));
+        std::vector<int32_t> cnt(do_count ? std::max<uint64_t>(rows, 1) : 0);
+        check(h, gams_gpu_sw_batch(h, seqset, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
+                                   A.fe.data(), a.size, a.max, a.resize, rv.data(), rows, nullptr, &rows));
+        if (do_count)
+            check(h, gams_gpu_sw_count_batch(h, seqset, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
+                                             A.fe.data(), a.size, a.max, U.loc.rg_index(), A.group.data(), cnt.data(), rows,
+                                             nullptr, &rows));
+        sw_summarise_rows(rv.data(), do_count ? cnt.data() : nullptr, rows, a.max, a.actions, T.words.data() + tag * group_words);
+    }
+    // one small read-back: the device's integers join the host's
+    const size_t n = ((size_t)a.max + 1) * n_tags;
+    std::vector<uint64_t> count(n), s(4 * n), nan(4 * n), c(n);
+    check(h, gams_sw_summary_read(h, acc.p, count.data(), s.data(), nan.data(), c.data()));
+    for (size_t g = 0; g < n; ++g) {
+        uint64_t *w = T.words.data() + g * GAMS_SW_SUMMARY_WORDS;
+        w[0] += count[g];
+        w[9] += c[g];
+        for (int k = 0; k < 4; ++k) {
+            w[1 + k] += s[4 * g + k];
+            w[5 + k] += nan[4 * g + k];
+        }
+    }
+    if (device) *device = all_device;
+    return T;
+}
+
+SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                          const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
+                          const std::map<std::string, std::vector<Range>> *rgs, const std::vector<FileBytes> *rg_files,
+                          bool *device) {
+    if (!(a.actions & GAMS_SW_GC))                                       // nothing reads a base: nothing goes up
+        return sw_summary(h, ctgs, static_cast<gams_seqset_t *>(nullptr), std::vector<uint32_t>(), files, tags, a, rgs, rg_files,
+                          device);
+    if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, "sw_summary: ctgs / seqs size mismatch");
+    std::vector<uint32_t> lens(std::max<size_t>(ctgs.size(), 1), 0), slots(ctgs.size());
+    for (size_t i = 0; i < ctgs.size(); ++i) {
+        lens[i] = (uint32_t)(ctgs[i].chr_end - ctgs[i].chr_start + 1);
+        slots[i] = (uint32_t)i;
+    }
+    SeqSetGuard sg{h};
+    check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
+    check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
+    return sw_summary(h, ctgs, sg.s, slots, files, tags, a, rgs, rg_files, device);
 }
 
 namespace {

@@ -228,6 +228,7 @@ public:
                                   bool *device);
     friend std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                                  const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device);
+    friend struct SwSetup;                        // what sw_text and sw_summary set up once (gams_host.cpp)
     friend std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                                const std::vector<uint32_t> &slots, const char *bytes, size_t n, const SwArgs &a,
                                const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes, size_t rg_n,
@@ -327,6 +328,39 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *
                     const char *bytes, size_t n, const SwArgs &a, const std::map<std::string, std::vector<Range>> *rgs = nullptr,
                     const char *rg_bytes = nullptr, size_t rg_n = 0, bool *device = nullptr, const TextSink *sink = nullptr,
                     const std::vector<FileBytes> *rg_files = nullptr);
+
+// The table the sw rows are loaded for (templates/dql/fsw-distance.tera.sql, fsw-distance-tag.tera.sql):
+// per distance -- per (tag, distance) with tags -- the average of the four statistics, of rg_count, and the rows, kept as
+// the exact integers of GAMS_SW_SUMMARY_WORDS (include/gams_gpu.h): group (t, d) at words[(t * (max + 1) + d) * 10 ..).
+struct SwSummaryTable {
+    int32_t max = 0;
+    uint32_t actions = 0;
+    std::vector<std::string> tags;        // the distinct tags in byte order, one slot each; empty: no tags, one slot
+    std::vector<uint64_t> words;
+    // the header and one line per group with COUNT > 0, ordered by tag bytes, then distance; an average is S / COUNT to
+    // the nearest integer, ties to even, printed as q / 10^4 without trailing zeros; `nan` where a row's statistic was NaN
+    std::string text() const;
+};
+std::string sw_summary_header(uint32_t actions, bool tagged);
+// n rows (and, under GAMS_SW_COUNT, their counts) added into `table`, (max + 1) groups: the host's summariser, which runs
+// where the device refuses.  A statistic of 1000 or more adds the integer nearest to v * 10^4; GAMS_EINVAL for a distance
+// outside [0, max], GAMS_EUNSUPPORTED for a negative or infinite statistic.
+void sw_summarise_rows(const gams_sw_row_t *rows, const int32_t *counts, uint64_t n, int32_t max, uint32_t actions,
+                       uint64_t *table);
+// `gams feature` + `gams sw` + the summary over the bytes of one or several range files, files[f] under (*tags)[f] (tags
+// NULL: no tag column): per file gams_gpu_sw_feature_summary into one accumulator on the device -- no row leaves it -- and
+// one read-back of the integers.  Drop-first is per file.  seqs, seqset, slots, rgs, rg_files as for sw_text.  Where the
+// device refuses a file (GAMS_EUNSUPPORTED) its lines go through read_range and, with GAMS_SW_GC, the rows of
+// gams_gpu_sw_batch through sw_summarise_rows (without it through gams_gpu_sw_summary_batch); *device (may be NULL):
+// every file took the device's route.
+SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                          const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
+                          const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                          const std::vector<FileBytes> *rg_files = nullptr, bool *device = nullptr);
+SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                          const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
+                          const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                          const std::vector<FileBytes> *rg_files = nullptr, bool *device = nullptr);
 
 // src/cmd_gams/rg.rs:41-77 / feature.rs:47-95: the records the loaders SET, as (key, JSON) pairs in
 // the reference's order (ctg id order, then file order), serials from 1 per ctg (a fresh cnt:).

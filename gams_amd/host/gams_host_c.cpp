@@ -759,6 +759,61 @@ char *gams_host_sw_text_rgs(gams_gpu_t *h, uint32_t n, const char *const *ids, c
                         nullptr, 0, &files, out_len);
 }
 
+// The per-distance summary of the sw rows over the bytes of n_files feature files (gams::sw_summary), reduced on the
+// device: the table's text (header, then one line per tag and distance with rows).  ctgs, seqs / seqset / slots, actions
+// and rg_lines as for gams_host_sw_text; tags: NULL, or one NUL-terminated tag per file; the rg files (n_rg, rg_data,
+// rg_n; n_rg 0: none) as for gams_host_sw_text_rgs.  table (may be NULL) receives the raw integers, n_slots * (max + 1)
+// groups of GAMS_SW_SUMMARY_WORDS words, n_slots = the distinct tags (1 without tags), in byte order.
+char *gams_host_sw_summary(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                           const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                           uint32_t n_files, const char *const *data, const uint64_t *n_bytes, const char *const *tags,
+                           int32_t size, int32_t max, int32_t resize, uint32_t actions, const char *rg_lines, uint32_t n_rg,
+                           const char *const *rg_data, const uint64_t *rg_n, uint64_t *table, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        std::map<std::string, std::vector<gams::Range>> rg_of;
+        if (rg_lines) rg_of = rg_index_of(n, ids, rg_lines);
+        const gams::SwArgs a = sw_args(size, max, resize, actions);
+        const std::vector<gams::FileBytes> files = files_of(n_files, data, n_bytes), rg_files = files_of(n_rg, rg_data, rg_n);
+        std::vector<std::string> tv;
+        if (tags) tv.assign(tags, tags + n_files);
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        const gams::SwSummaryTable T =
+            (seqset || !seqs) ? gams::sw_summary(h, cv, seqset, seqset ? std::vector<uint32_t>(slots, slots + n) : std::vector<uint32_t>(),
+                                                 files, tags ? &tv : nullptr, a, rg_lines ? &rg_of : nullptr, n_rg ? &rg_files : nullptr, &dev)
+                              : gams::sw_summary(h, cv, std::vector<const uint8_t *>(seqs, seqs + n), files, tags ? &tv : nullptr, a,
+                                                 rg_lines ? &rg_of : nullptr, n_rg ? &rg_files : nullptr, &dev);
+        std::string out = T.text();
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        if (table) std::memcpy(table, T.words.data(), T.words.size() * 8);
+        return out;
+    });
+}
+// The host's summariser on its own (gams::sw_summarise_rows): n rows of gams_gpu_sw_batch and, under GAMS_SW_COUNT, their
+// counts, added into table ((max + 1) groups of GAMS_SW_SUMMARY_WORDS words, which the caller zeroes).  0, or -1 with the
+// thread's last error set.
+int gams_host_sw_summarise_rows(const gams_sw_row_t *rows, const int32_t *counts, uint64_t n, int32_t max, uint32_t actions,
+                                uint64_t *table) {
+    return guard(-1, [&] {
+        gams::sw_summarise_rows(rows, counts, n, max, actions, table);
+        return 0;
+    });
+}
+// The text of a table of n_slots * (max + 1) groups; tags: NULL (n_slots = 1, no tag column) or the n_slots tags in byte order.
+char *gams_host_sw_summary_text(const uint64_t *table, uint32_t n_slots, const char *const *tags, int32_t max, uint32_t actions,
+                                uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        gams::SwSummaryTable T;
+        T.max = max;
+        T.actions = actions;
+        if (tags) T.tags.assign(tags, tags + n_slots);
+        T.words.assign(table, table + (size_t)(tags ? n_slots : 1) * ((size_t)max + 1) * GAMS_SW_SUMMARY_WORDS);
+        return T.text();
+    });
+}
+
 // `gams rg f1 f2 ...` (kind 0) / `gams feature --tag T f1 f2 ...` (kind 1) over the bytes of the files (gams::loader_text):
 // the records as text in `format` (GAMS_LOADER_RECORDS / _TSV / _RESP), in the reference's SET order.  serial_base[i] (NULL:
 // all 0) = the counter of ctg i before the load; serial_next[i] and n_in_file[f] (either may be NULL) receive the counters

@@ -63,6 +63,7 @@ typedef struct gams_index gams_index_t;
 typedef struct gams_spans gams_spans_t;
 typedef struct gams_names gams_names_t;
 typedef struct gams_gen gams_gen_t;
+typedef struct gams_sw_summary gams_sw_summary_t;
 
 /* ---- handle ------------------------------------------------------------ */
 int gams_gpu_create(int device, gams_gpu_t **h);
@@ -304,6 +305,39 @@ int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, con
                             const uint32_t *rg_group, int32_t *count, uint64_t cap, uint64_t *row_off,
                             uint64_t *n_rows);
 
+/* ---- sw summary: the rows reduced per distance on the device (templates/dql/fsw-distance.tera.sql) ---- */
+/* What the user plots is not the rows but their table per distance: avg(gc_content), avg(gc_mean), avg(gc_stddev),
+ * avg(gc_cv) and count, L and R together; fsw-distance-tag.tera.sql is the same per (tag, distance).  The accumulator
+ * below holds that table as exact integers in device memory: n_tags x (max + 1) groups, group (t, d) at words
+ * [(t * (max + 1) + d) * GAMS_SW_SUMMARY_WORDS ..), each
+ *   [0] COUNT, the rows; [1..4] S, the sum of m over the rows for gc_content, gc_mean, gc_stddev, gc_cv, a statistic
+ *   being printed as m / 10^4 (the integer the text entries print); [5..8] the rows whose statistic is NaN (left out of
+ *   S); [9] C, the sum of rg_count.
+ * A -0 adds 0.  Without GAMS_SW_GC words 1..8 stay 0, without GAMS_SW_COUNT word 9.  The sums are integers, so neither
+ * the order of the calls nor of the additions inside one shows in them.  An accumulator is bound to size, max, resize
+ * and actions: a call with other values is GAMS_EINVAL.  It belongs to the handle it was made on. */
+#define GAMS_SW_SUMMARY_WORDS 10u
+/* GAMS_EINVAL: n_tags == 0, size < 2, max < 0 or beyond 2^24, resize < 2, unknown action bits.  All groups start at 0. */
+int gams_sw_summary_create(gams_gpu_t *h, int32_t max, uint32_t n_tags, uint32_t actions, int32_t size, int32_t resize,
+                           gams_sw_summary_t **out);
+int gams_sw_summary_reset(gams_gpu_t *h, gams_sw_summary_t *sum);   /* every group back to 0 */
+/* The raw integers, one small read-back; n = n_tags * (max + 1) groups in (tag, distance) order: count[n], sum[4 * n]
+ * and nan[4 * n] (group-major: the four statistics of a group side by side), rg_count[n].  Any of the four may be NULL. */
+int gams_sw_summary_read(gams_gpu_t *h, gams_sw_summary_t *sum, uint64_t *count, uint64_t *s, uint64_t *nan,
+                         uint64_t *rg_count);
+void gams_sw_summary_destroy(gams_gpu_t *h, gams_sw_summary_t *sum);
+/* The rows gams_gpu_sw_text_actions prints for these arguments (it takes them without the names and ids), added into tag
+ * slot `tag` of `sum` and never stored: for hosts that hold their features as arrays.  *n_rows = the rows of the call.
+ * Checks and return codes as for gams_gpu_sw_text_actions, and GAMS_EINVAL for tag >= n_tags and for size, max, resize
+ * or actions other than the accumulator's.  GAMS_EUNSUPPORTED where that entry answers it for a statistic (a non-NaN
+ * value outside [0, 1000)): the accumulator is then as it was before the call -- summarise the rows of
+ * gams_gpu_sw_batch on the host. */
+int gams_gpu_sw_summary_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                              const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                              const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                              gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
+                              uint64_t *n_rows);
+
 /* gc_content (round4, utils.rs:141-162) of n chromosome ranges inside ctg i: what `gams peak`
  * asks per merged peak (peak.rs:79; second "next" row of SURVEY section 8f). */
 int gams_gpu_range_gc(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_start,
@@ -533,6 +567,22 @@ int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_
                              gams_index_t *rg_ix, const uint32_t *rg_group,
                              const char **text, uint64_t *text_bytes, uint64_t *text_off,
                              uint64_t *n_features, uint64_t *n_rows);
+/* From the bytes of ONE range file to the sw summary: the rows gams_gpu_sw_feature_text would print for the same
+ * arguments (it takes them without the text outputs), added into tag slot `tag` of `sum` on the device and never stored
+ * -- no row buffer, no text, no read-back but the counts and two flag words.  Drop-first is per file and per ctg, as
+ * there; several files, tagged or not, are several calls into one accumulator (feature ids play no part in the table).
+ * *n_features = the kept lines, *n_rows = the rows added.  Checks and return codes as for gams_gpu_sw_feature_text, and
+ * GAMS_EINVAL for tag >= n_tags and for size, max, resize or actions other than the accumulator's; on any code but
+ * GAMS_OK the accumulator is as it was before the call.  GAMS_EUNSUPPORTED (run the host path) for what the loader
+ * refuses and for a non-NaN statistic outside [0, 1000).
+ * gams_gpu_last_stage_ms then reports ten stages: the loader's lines, parse, locate, first, keep, offsets, order, then
+ * gather, geometry, rows (seven when no line is kept). */
+int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                                const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                                const int32_t *chr_end, const char *bytes, uint64_t n_bytes,
+                                int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                                gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
+                                uint64_t *n_features, uint64_t *n_rows);
 
 /* ---- text in, text out: locate --seq (locate.rs:124-134) ---- */
 /* The bytes of ONE range file (lines, refused bytes and the 2^32 - 1 line limit as for gams_gpu_locate_text) -> the bases

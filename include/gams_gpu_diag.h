@@ -30,7 +30,8 @@ int gams_gpu_last_kernel_ms(gams_gpu_t *h, float *ms);
  * build.  After gams_gpu_peak_text, its ten: lines, parse, locate, first, keep, offsets, order, gc (gather, checks and
  * range gc), rows (row lengths and their prefix), write.  After gams_gpu_sw_feature_text, its twelve: the loader's lines ..
  * order, then gather (with the middle check), geometry (rows per feature and their prefix), rows (sw_kernel), text lengths,
- * text write (seven when no line is kept).  After gams_gpu_gen_text (of an input that is not empty), its
+ * text write (seven when no line is kept).  After gams_gpu_sw_feature_summary, its ten: the same up to rows (the
+ * summarising sw_kernel and the merge into the accumulator; no text stages).  After gams_gpu_gen_text (of an input that is not empty), its
  * five: upload, pack (mark, carry, count, offsets, compact), scan, table (the host's part), place.  After
  * gams_gpu_locate_seq_text (with a located line), its six: lines, parse, locate, lengths, offsets, copy.  Writes up to cap values; *n = the stages the call ran
  * (gams_gpu_last_kernel_ms is their sum).  GAMS_ESTATE when the last timed call was none of these (or its input had
