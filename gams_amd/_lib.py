@@ -128,7 +128,11 @@ PROTOTYPES = {
     "gams_spans_create": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _PP]),
     "gams_spans_destroy": (None, [_VP, _VP]),
     "gams_gpu_cover": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP]),
+    "gams_spans_create_runlist_text": (C.c_int, [_VP, _VP, C.c_uint64, _PP, _PP, C.POINTER(C.c_uint32),
+                                                 C.POINTER(C.c_uint64)]),
+    "gams_spans_read": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
     "gams_names_create": (C.c_int, [_VP, C.c_uint32, C.POINTER(C.c_char_p), _PP]),
+    "gams_names_read": (C.c_int, [_VP, _VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), _VP, _VP]),
     "gams_names_destroy": (None, [_VP, _VP]),
     "gams_gpu_locate_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64),
                                        C.POINTER(C.c_uint64)]),

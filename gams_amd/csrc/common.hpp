@@ -92,6 +92,8 @@ hipError_t gams_pool_alloc(gams_gpu_t *h, bool pinned, size_t bytes, void **out,
 void gams_pool_free(gams_gpu_t *h, bool pinned, void *p, size_t cap);
 // text.hip: return the text entries' buffers to the pools (gams_gpu_destroy)
 void gams_text_free(gams_gpu_t *h);
+// text.hip, for runlist.hip: the text entries' cached device copy of an input, grown to hold `bytes`
+hipError_t gams_text_input(gams_gpu_t *h, size_t bytes, uint8_t **d_in);
 
 inline int gams_fail(gams_gpu_t *h, int code, const std::string &msg) {
     (void)hipGetLastError();   // a failed HIP call is reported through the code; it must not stay sticky

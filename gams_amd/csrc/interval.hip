@@ -98,19 +98,6 @@ __global__ __launch_bounds__(256) void index_unpack_kernel(const uint64_t *key, 
     lrec[i] = IvRec{(uint32_t)(k >> 32), (uint32_t)k, (uint64_t)perm[i]};
 }
 
-__device__ __forceinline__ KeyDir dir_params(uint32_t first, uint32_t last, uint32_t n) {
-    KeyDir d{0u, 0u, 0u, 0u};
-    if (n == 0) return d;
-    d.key0 = first;
-    // 64-bit range: a one-key grid (n == 1, e.g. the cell grid of a one-interval group [0, 2^31 + 1)) needs
-    // range >> shift == 0, i.e. shift == 32 when the range has bit 31 set -- a 32-bit shift by 32 is masked
-    // to 0 on this hardware and the loop would never end.  Every consumer shifts in 64 bits.
-    const uint64_t range = (uint64_t)last - (uint64_t)first;
-    while ((range >> d.shift) >= n) ++d.shift;     // (range >> shift) + 1 <= n buckets; ends at shift <= 32
-    d.nb = (uint32_t)(range >> d.shift) + 1u;
-    return d;
-}
-
 // one wavefront per group: max(stop - start) (Lapper::max_len) and the directory headers
 __global__ __launch_bounds__(64) void index_group_kernel(const uint32_t *off32, uint32_t n_groups,
                                                          const IvRec *lrec, const uint32_t *lstart,
@@ -863,6 +850,20 @@ int gams_spans_create(gams_gpu_t *h, uint32_t n_groups, const uint64_t *group_of
     *out = sp;
     return GAMS_OK;
 }
+
+}  // extern "C"
+
+// for runlist.hip, whose set is built on the device: the cell records of a set whose groups, records and directory are
+// in place, queued on `st`
+hipError_t gams_spans_launch_cells(const gams_spans_t *sp, hipStream_t st) {
+    const uint64_t slots = sp->m + sp->n_groups + 1;
+    if (sp->n_groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(span_cell_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, sp->d_groups, sp->n_groups,
+                       sp->d_rec, sp->d_dir_lo, slots, sp->d_cells);
+    return hipGetLastError();
+}
+
+extern "C" {
 
 void gams_spans_destroy(gams_gpu_t *h, gams_spans_t *sp) {
     if (!sp) return;

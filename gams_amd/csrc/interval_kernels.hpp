@@ -122,7 +122,24 @@ struct gams_spans {
     SpanCell *d_cells = nullptr;     // m + n_groups + 1 records: group g's cell b at off[g] + g + b (like its directory)
 };
 
+// interval.hip, for runlist.hip: span_cell_kernel over a set whose groups, records and directory are in place, on `st`
+hipError_t gams_spans_launch_cells(const gams_spans_t *sp, hipStream_t st);
+
 namespace {
+
+// the directory header of n ascending keys first .. last: build_dir's rule (interval.hip), on the device
+__device__ __forceinline__ KeyDir dir_params(uint32_t first, uint32_t last, uint32_t n) {
+    KeyDir d{0u, 0u, 0u, 0u};
+    if (n == 0) return d;
+    d.key0 = first;
+    // 64-bit range: a one-key grid (n == 1, e.g. the cell grid of a one-interval group [0, 2^31 + 1)) needs
+    // range >> shift == 0, i.e. shift == 32 when the range has bit 31 set -- a 32-bit shift by 32 is masked
+    // to 0 on this hardware and the loop would never end.  Every consumer shifts in 64 bits.
+    const uint64_t range = (uint64_t)last - (uint64_t)first;
+    while ((range >> d.shift) >= n) ++d.shift;     // (range >> shift) + 1 <= n buckets; ends at shift <= 32
+    d.nb = (uint32_t)(range >> d.shift) + 1u;
+    return d;
+}
 
 // Number of keys < key among the group's n ascending keys a[0..n) (rank of the lower bound).
 // BIAS = 0x80000000 compares int32 keys stored as they are (x ^ BIAS is order preserving).

@@ -87,6 +87,14 @@ void gams_text_free(gams_gpu_t *h) {
     h->text = nullptr;
 }
 
+hipError_t gams_text_input(gams_gpu_t *h, size_t bytes, uint8_t **d_in) {
+    if (!h->text) h->text = new gams_text_state();
+    gams_text_state *T = h->text;
+    const hipError_t e = gams_pool_grow(h, false, &T->d_in, &T->d_in_cap, bytes, bytes);
+    *d_in = T->d_in;
+    return e;
+}
+
 namespace {
 
 // FNV-1a, 64 bits, over the name's bytes (host and device)
@@ -137,10 +145,6 @@ hipError_t read_words(gams_gpu_t *h, const unsigned long long *d_words) {
 
 constexpr uint32_t kIdxBytes = 256u * 64u;   // bytes per workgroup of the line-index kernels
 
-// 0x80 in exactly the zero bytes of y
-__device__ __forceinline__ uint32_t zero_bytes(uint32_t y) {
-    return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
-}
 __device__ __forceinline__ uint32_t nl_mask(uint32_t w) { return zero_bytes(w ^ 0x0a0a0a0au); }
 __device__ __forceinline__ uint32_t bad_mask(uint32_t w) { return (w & 0x80808080u) | zero_bytes(w); }
 
@@ -217,28 +221,6 @@ __device__ __forceinline__ void line_of(const TextLines &t, uint32_t i, uint64_t
 
 __device__ __forceinline__ bool is_word_c(char c) {
     return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || c == '_';
-}
-__device__ __forceinline__ bool is_digit_c(char c) { return c >= '0' && c <= '9'; }
-
-// The run of digits at s[p..e), looked at up to its eleventh digit (a run of more than ten is invalid anyway): p moves
-// past what was looked at; the value is that of the first ten digits, or 0x80000000 for any value above INT32_MAX.
-// Branch-free over a fixed trip count in 32-bit arithmetic (the input buffer carries 16 bytes of padding, so the
-// eleven loads stay inside it): the branchy 64-bit form of this loop came out of the compiler returning a wrong
-// value for one of the two runs of a range.
-__device__ __forceinline__ uint32_t digits(const char *s, uint64_t &p, uint64_t e) {
-    uint32_t v = 0, nd = 0;
-    bool run = true, over = false;
-#pragma unroll
-    for (uint32_t u = 0; u < 11u; ++u) {
-        const uint32_t d = (uint32_t)(uint8_t)s[p + u] - (uint32_t)'0';
-        run = run && (p + u < e) && d < 10u;
-        const bool take = run && u < 10u;
-        over = over || (take && (v > 214748364u || v * 10u + d > 0x7fffffffu));
-        v = take && !over ? v * 10u + d : v;
-        nd += run ? 1u : 0u;
-    }
-    p += nd;
-    return over ? 0x80000000u : v;
 }
 
 // intspan Range::from_str over s[b, e) (gams_host.cpp Range::from_str, step for step): on success the chromosome
@@ -2344,6 +2326,18 @@ int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_
     nm->t.n = n;
     nm->max_len = (uint32_t)std::min<size_t>(max_len, UINT32_MAX);
     *out = nm;
+    return GAMS_OK;
+}
+
+int gams_names_read(gams_gpu_t *h, const gams_names_t *nm, uint32_t *n, uint64_t *n_bytes, char *bytes, uint64_t *off) {
+    if (!h || !nm || !n || !n_bytes) return gams_fail(h, GAMS_EINVAL, "names_read: null argument");
+    GAMS_HIP(h, hipSetDevice(h->device));
+    std::vector<unsigned long long> o((size_t)nm->t.n + 1);
+    GAMS_HIP(h, hipMemcpy(o.data(), nm->t.off, o.size() * 8, hipMemcpyDeviceToHost));
+    *n = nm->t.n;
+    *n_bytes = o[nm->t.n];
+    if (off) std::copy(o.begin(), o.end(), off);
+    if (bytes && o[nm->t.n]) GAMS_HIP(h, hipMemcpy(bytes, nm->t.bytes, o[nm->t.n], hipMemcpyDeviceToHost));
     return GAMS_OK;
 }
 

@@ -6,13 +6,42 @@
 // text, and BlockWriter -- the prefix inside a block, the choice between the stage and the text, and that copy, written
 // once for the four kernels that stage a block (`locate` / `anno` rows are never staged: text_row_write_kernel keeps its
 // own few lines).  The row composers and the gctab lookup stay with their owners; the other two float formats
-// (gams_fmt_prop4 and gams_fmt_f32_short) are text_fmt.hpp's, which the host layer shares.
+// (gams_fmt_prop4 and gams_fmt_f32_short) are text_fmt.hpp's, which the host layer shares.  In front of them, the two
+// helpers the units that READ text share (text.hip, runlist.hip): the exact zero-byte mask and the run of digits.
 #pragma once
 
 #include "common.hpp"
 #include "text_fmt.hpp"
 
 namespace {
+
+// ---- what the kernels that read text share (text.hip, runlist.hip)
+// 0x80 in exactly the zero bytes of y
+__device__ __forceinline__ uint32_t zero_bytes(uint32_t y) {
+    return ~(((y & 0x7f7f7f7fu) + 0x7f7f7f7fu) | y | 0x7f7f7f7fu);
+}
+__device__ __forceinline__ bool is_digit_c(char c) { return c >= '0' && c <= '9'; }
+
+// The run of digits at s[p..e), looked at up to its eleventh digit (a run of more than ten is invalid anyway): p moves
+// past what was looked at; the value is that of the first ten digits, or 0x80000000 for any value above INT32_MAX.
+// Branch-free over a fixed trip count in 32-bit arithmetic (the input buffer carries 16 bytes of padding, so the
+// eleven loads stay inside it): the branchy 64-bit form of this loop came out of the compiler returning a wrong
+// value for one of the two runs of a range.
+__device__ __forceinline__ uint32_t digits(const char *s, uint64_t &p, uint64_t e) {
+    uint32_t v = 0, nd = 0;
+    bool run = true, over = false;
+#pragma unroll
+    for (uint32_t u = 0; u < 11u; ++u) {
+        const uint32_t d = (uint32_t)(uint8_t)s[p + u] - (uint32_t)'0';
+        run = run && (p + u < e) && d < 10u;
+        const bool take = run && u < 10u;
+        over = over || (take && (v > 214748364u || v * 10u + d > 0x7fffffffu));
+        v = take && !over ? v * 10u + d : v;
+        nd += run ? 1u : 0u;
+    }
+    p += nd;
+    return over ? 0x80000000u : v;
+}
 
 __device__ __forceinline__ uint32_t dec_digits(uint32_t v) {
     return v < 10u ? 1u : v < 100u ? 2u : v < 1000u ? 3u : v < 10000u ? 4u : v < 100000u ? 5u : v < 1000000u ? 6u

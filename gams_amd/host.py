@@ -125,6 +125,29 @@ def load():
     L.gams_host_anno_text.restype = C.c_void_p
     L.gams_host_anno_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_char_p, C.c_uint64,
                                       C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.gams_host_anno_set_create.restype = C.c_void_p
+    L.gams_host_anno_set_create.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
+    L.gams_host_anno_set_destroy.restype = None
+    L.gams_host_anno_set_destroy.argtypes = [C.c_void_p]
+    L.gams_host_anno_set_device.restype = C.c_int
+    L.gams_host_anno_set_device.argtypes = [C.c_void_p]
+    L.gams_host_anno_set_spans.restype = C.c_void_p
+    L.gams_host_anno_set_spans.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.gams_host_anno_set_names.restype = C.c_void_p
+    L.gams_host_anno_set_names.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.gams_host_anno_text_set.restype = C.c_void_p
+    L.gams_host_anno_text_set.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p, C.c_uint64,
+                                          C.c_int, C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.gams_host_anno_set.restype = C.c_void_p
+    L.gams_host_anno_set.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p, C.c_int,
+                                     C.c_char_p, C.c_uint32, C.c_uint32]
+    L.gams_host_read_runlist_json.restype = C.c_int
+    L.gams_host_read_runlist_json.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                              C.POINTER(C.c_uint64)]
+    L.gams_host_read_runlist_json_get.restype = None
+    L.gams_host_read_runlist_json_get.argtypes = [C.c_void_p] * 5
+    L.gams_host_runlist_load.restype = C.c_int64
+    L.gams_host_runlist_load.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int]
     L.gams_host_locate_rg.restype = C.c_void_p
     L.gams_host_locate_rg.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_int, C.c_char_p, C.c_uint64]
     L.gams_host_locate_text_rg.restype = C.c_void_p
@@ -403,9 +426,126 @@ def find(eng, ctgs, rgs):
     return out.split("\n")[:len(rgs)]
 
 
+class AnnoSet:
+    """The span set of an anno run, built once from the bytes of the runlist JSON file (gams::AnnoSet): on the device
+    (gams_spans_create_runlist_text), by the host reader where the device refuses.  `device` says which route built
+    it; HostError with code EINVAL where the host reader refuses the file.  Pass it as `runlists` to anno() /
+    anno_text(); several input files share it."""
+
+    def __init__(self, eng, data):
+        data = bytes(data)
+        self.eng = eng
+        self.p = load().gams_host_anno_set_create(eng.h, data, len(data))
+        if not self.p:
+            _check_rc(-1)
+        L = load()
+        self.device = bool(L.gams_host_anno_set_device(self.p))
+        ng, ns = C.c_uint32(), C.c_uint64()
+        self._sp = L.gams_host_anno_set_spans(self.p, C.byref(ng), C.byref(ns))
+        self.n_groups, self.n_spans = ng.value, ns.value
+        out_len = C.c_uint64()
+        flat = _take_bytes(L.gams_host_anno_set_names(self.p, C.byref(out_len)), out_len)
+        self.names = [s.decode(errors="surrogateescape") for s in flat.split(b"\0")[:-1]]
+
+    def spans(self):
+        """{chr: (lo, hi)} of the resident set, in group order (gams_spans_read)"""
+        return _read_spans(self.eng, self._sp, self.names)
+
+    def close(self):
+        if getattr(self, "p", None):
+            load().gams_host_anno_set_destroy(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _read_spans(eng, sp, names):
+    lib = _lib.load()
+    ns = C.c_uint64()
+    off = np.zeros(len(names) + 1, np.uint64)
+    eng.check(lib.gams_spans_read(eng.h, sp, off.ctypes.data, None, None, 0, C.byref(ns)))
+    lo, hi = np.zeros(max(ns.value, 1), np.int32), np.zeros(max(ns.value, 1), np.int32)
+    if ns.value:
+        eng.check(lib.gams_spans_read(eng.h, sp, off.ctypes.data, lo.ctypes.data, hi.ctypes.data, ns.value, C.byref(ns)))
+    return {k: (lo[int(off[g]):int(off[g + 1])].copy(), hi[int(off[g]):int(off[g + 1])].copy()) for g, k in enumerate(names)}
+
+
+def read_runlist_text(eng, data):
+    """The runlist JSON bytes through the device entry (gams_spans_create_runlist_text) and gams_spans_read:
+    {chr: (lo, hi)} as numpy arrays, in file order.  GamsError (EUNSUPPORTED) where the device refuses."""
+    lib = _lib.load()
+    data = bytes(data)
+    sp, nm = C.c_void_p(), C.c_void_p()
+    ng, ns = C.c_uint32(), C.c_uint64()
+    eng.check(lib.gams_spans_create_runlist_text(eng.h, data, len(data), C.byref(sp), C.byref(nm), C.byref(ng), C.byref(ns)))
+    try:
+        n, nb = C.c_uint32(), C.c_uint64()
+        eng.check(lib.gams_names_read(eng.h, nm, C.byref(n), C.byref(nb), None, None))
+        flat = C.create_string_buffer(max(nb.value, 1))
+        off = np.zeros(n.value + 1, np.uint64)
+        eng.check(lib.gams_names_read(eng.h, nm, C.byref(n), C.byref(nb), flat, off.ctypes.data))
+        names = [flat.raw[int(off[g]):int(off[g + 1])].decode() for g in range(n.value)]
+        assert n.value == ng.value
+        return _read_spans(eng, sp, names)
+    finally:
+        lib.gams_spans_destroy(eng.h, sp)
+        lib.gams_names_destroy(eng.h, nm)
+
+
+def read_runlist_json(data):
+    """The host reader of a runlist JSON file (gams::read_runlist_json): {chr: (lo, hi)} as numpy arrays, in file
+    order (a key that comes twice keeps its first place and its last value), every set normalised.  HostError with
+    code EINVAL where the reference panics."""
+    L = load()
+    data = bytes(data)
+    ng, ns, nb = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    _check_rc(L.gams_host_read_runlist_json(data, len(data), C.byref(ng), C.byref(ns), C.byref(nb)))
+    names = C.create_string_buffer(max(nb.value, 1))
+    noff, goff = np.zeros(ng.value + 1, np.uint64), np.zeros(ng.value + 1, np.uint64)
+    lo, hi = np.zeros(max(ns.value, 1), np.int32), np.zeros(max(ns.value, 1), np.int32)
+    L.gams_host_read_runlist_json_get(names, noff.ctypes.data, goff.ctypes.data, lo.ctypes.data, hi.ctypes.data)
+    out = {}
+    for g in range(ng.value):
+        key = names.raw[int(noff[g]):int(noff[g + 1])].decode()
+        out[key] = (lo[int(goff[g]):int(goff[g + 1])].copy(), hi[int(goff[g]):int(goff[g + 1])].copy())
+    return out
+
+
+def runlist_load(eng, data, device_route=True):
+    """Builds the span set of a runlist JSON file's bytes and drops it: a timing entry.  device_route: through
+    gams::AnnoSet (the device entry), else the host reader + gams_spans_create.  Returns the spans of the set;
+    last_operator_ms() has the ms of the load, last_operator_device() the route that built it."""
+    data = bytes(data)
+    got = load().gams_host_runlist_load(eng.h, data, len(data), int(device_route))
+    _check_rc(0 if got >= 0 else -1)
+    return int(got)
+
+
+def _anno_set(eng, runlists):
+    """(the AnnoSet behind a bytes / AnnoSet `runlists` argument, whether this call owns it); (None, False) for a dict"""
+    if isinstance(runlists, AnnoSet):
+        return runlists, False
+    if isinstance(runlists, (bytes, bytearray, memoryview)):
+        return AnnoSet(eng, runlists), True
+    return None, False
+
+
 def anno(eng, ctgs, runlists, lines, header=False, prefix="", idx_id=1, idx_range=2):
-    """runlists: dict chr -> runlist string."""
+    """runlists: dict chr -> runlist string, the bytes of the runlist JSON file, or an AnnoSet."""
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    aset, own = _anno_set(eng, runlists)
+    if aset is not None:
+        try:
+            return _take(load().gams_host_anno_set(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, aset.p,
+                                                   "\n".join(lines).encode(), int(header), prefix.encode(), idx_id,
+                                                   idx_range))
+        finally:
+            if own:
+                aset.close()
     rl = "\n".join(f"{k}\t{v}" for k, v in runlists.items())
     return _take(load().gams_host_anno(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, rl.encode(),
                                        "\n".join(lines).encode(), int(header), prefix.encode(), idx_id, idx_range))
@@ -433,10 +573,20 @@ def locate_text(eng, ctgs, data, count=False, rg_records=(), rg_data=None):
 
 
 def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_range=2):
-    """`anno` over the bytes of one input file; runlists: dict chr -> runlist string.  Returns the rows as bytes."""
+    """`anno` over the bytes of one input file; runlists: dict chr -> runlist string, the bytes of the runlist JSON
+    file, or an AnnoSet (one set for several input files).  Returns the rows as bytes."""
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
-    rl = "\n".join(f"{k}\t{v}" for k, v in runlists.items())
     out_len = C.c_uint64()
+    aset, own = _anno_set(eng, runlists)
+    if aset is not None:
+        try:
+            return _take_bytes(load().gams_host_anno_text_set(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, aset.p,
+                                                              data, len(data), int(header), prefix.encode(), idx_id,
+                                                              idx_range, C.byref(out_len)), out_len)
+        finally:
+            if own:
+                aset.close()
+    rl = "\n".join(f"{k}\t{v}" for k, v in runlists.items())
     return _take_bytes(load().gams_host_anno_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, rl.encode(), data,
                                                   len(data), int(header), prefix.encode(), idx_id, idx_range,
                                                   C.byref(out_len)), out_len)
@@ -444,7 +594,7 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 def last_operator_device():
     """1 if the last wave / wave_timed / wave_gz / locate_text / locate_seq_text / anno_text / peak_text / sw_text / gen_text of this thread made its rows on the device,
-    0 if it fell back to the host"""
+    0 if it fell back to the host; after AnnoSet(...) / runlist_load: 1 if the device built the set from the bytes"""
     return int(load().gams_host_last_operator_device())
 
 

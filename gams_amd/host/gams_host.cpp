@@ -2878,29 +2878,84 @@ bool extract_ctg_id(const std::string &s, std::string &id) {
 
 }  // namespace
 
+AnnoSet::AnnoSet(gams_gpu_t *h, const char *bytes, size_t n) : h_(h) {
+    uint32_t n_groups = 0;
+    const int rc = gams_spans_create_runlist_text(h, bytes, n, &sp_, &names_, &n_groups, &n_spans_);
+    if (rc == GAMS_EUNSUPPORTED) {                    // the host reader judges the file; its set goes up as arrays
+        const RunlistJson js = read_runlist_json(bytes, n);
+        std::vector<const Runlist *> sets;
+        for (const Runlist &r : js.sets) sets.push_back(&r);
+        from_arrays(js.chr, sets);
+        return;
+    }
+    check(h, rc);
+    device_ = true;
+    // the keys as the device read them, for the lines path of anno()
+    uint64_t name_bytes = 0;
+    int rc2 = gams_names_read(h, names_, &n_groups, &name_bytes, nullptr, nullptr);
+    std::string flat((size_t)name_bytes, '\0');
+    std::vector<uint64_t> off((size_t)n_groups + 1, 0);
+    if (rc2 == GAMS_OK) rc2 = gams_names_read(h, names_, &n_groups, &name_bytes, &flat[0], off.data());
+    if (rc2 != GAMS_OK) {
+        gams_spans_destroy(h, sp_);
+        gams_names_destroy(h, names_);
+        check(h, rc2);
+    }
+    for (uint32_t g = 0; g < n_groups; ++g) chr_.push_back(flat.substr((size_t)off[g], (size_t)(off[g + 1] - off[g])));
+}
+
+AnnoSet::AnnoSet(gams_gpu_t *h, const std::map<std::string, Runlist> &sets) : h_(h) {
+    std::vector<std::string> chr;
+    std::vector<const Runlist *> rl;
+    for (auto &kv : sets) {
+        chr.push_back(kv.first);
+        rl.push_back(&kv.second);
+    }
+    from_arrays(chr, rl);
+}
+
+void AnnoSet::from_arrays(const std::vector<std::string> &chr, const std::vector<const Runlist *> &sets) {
+    std::vector<uint64_t> off{0};
+    std::vector<int32_t> lo, hi;
+    std::vector<const char *> names;
+    for (size_t g = 0; g < chr.size(); ++g) {
+        if (chr[g].find('\0') != std::string::npos) throw Error(GAMS_EUNSUPPORTED, "anno: a chr name holds a NUL");
+        names.push_back(chr[g].c_str());
+        lo.insert(lo.end(), sets[g]->lo.begin(), sets[g]->lo.end());
+        hi.insert(hi.end(), sets[g]->hi.begin(), sets[g]->hi.end());
+        off.push_back(lo.size());
+    }
+    check(h_, gams_spans_create(h_, (uint32_t)chr.size(), off.data(), lo.data(), hi.data(), &sp_));
+    const int rc = gams_names_create(h_, (uint32_t)chr.size(), names.data(), &names_);
+    if (rc != GAMS_OK) {
+        gams_spans_destroy(h_, sp_);
+        sp_ = nullptr;
+        check(h_, rc);
+    }
+    chr_ = chr;
+    n_spans_ = lo.size();
+}
+
+AnnoSet::~AnnoSet() {
+    if (sp_) gams_spans_destroy(h_, sp_);
+    if (names_) gams_names_destroy(h_, names_);
+}
+
 std::string anno(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, const std::vector<Ctg> &ctgs,
                  const std::vector<std::string> &lines, bool header, const std::string &prefix, size_t idx_id,
                  size_t idx_range) {
+    const AnnoSet set(h, sets);
+    return anno(h, set, ctgs, lines, header, prefix, idx_id, idx_range);
+}
+
+std::string anno(gams_gpu_t *h, const AnnoSet &set, const std::vector<Ctg> &ctgs, const std::vector<std::string> &lines,
+                 bool header, const std::string &prefix, size_t idx_id, size_t idx_range) {
     std::map<std::string, const Ctg *> ctg_of;
     for (const Ctg &c : ctgs) ctg_of[c.id] = &c;
-    // device image of the runlists: one group per chr
+    // the set's groups: one per chr
     std::map<std::string, uint32_t> group_of;
-    std::vector<uint64_t> off{0};
-    std::vector<int32_t> lo, hi;
-    uint32_t g = 0;
-    for (auto &kv : sets) {
-        group_of[kv.first] = g++;
-        lo.insert(lo.end(), kv.second.lo.begin(), kv.second.lo.end());
-        hi.insert(hi.end(), kv.second.hi.begin(), kv.second.hi.end());
-        off.push_back(lo.size());
-    }
-    gams_spans_t *sp = nullptr;
-    check(h, gams_spans_create(h, g, off.data(), lo.data(), hi.data(), &sp));
-    struct Guard {
-        gams_gpu_t *h;
-        gams_spans_t *sp;
-        ~Guard() { gams_spans_destroy(h, sp); }
-    } guard{h, sp};
+    for (uint32_t g = 0; g < set.chrs().size(); ++g) group_of[set.chrs()[g]] = g;
+    gams_spans_t *const sp = set.spans();
 
     // parse the lines on several threads (each a contiguous run, results concatenated in order),
     // one device call, then format the rows the same way
@@ -3021,16 +3076,15 @@ std::string anno_text(gams_gpu_t *h, const std::map<std::string, Runlist> &sets,
                       const char *bytes, size_t n, bool header, const std::string &prefix, size_t idx_id,
                       size_t idx_range, bool *device) {
     if (device) *device = false;
-    // the device image of the runlists (one group per chr, in the set's order) and the two name tables
-    std::vector<uint64_t> off{0};
-    std::vector<int32_t> lo, hi;
-    std::vector<const char *> chr, ids(ctgs.size());
-    for (auto &kv : sets) {
-        chr.push_back(kv.first.c_str());
-        lo.insert(lo.end(), kv.second.lo.begin(), kv.second.lo.end());
-        hi.insert(hi.end(), kv.second.hi.begin(), kv.second.hi.end());
-        off.push_back(lo.size());
-    }
+    // the device image of the runlists (one group per chr, in the set's order) and its name table, for this call
+    const AnnoSet set(h, sets);
+    return anno_text(h, set, ctgs, bytes, n, header, prefix, idx_id, idx_range, device);
+}
+
+std::string anno_text(gams_gpu_t *h, const AnnoSet &set, const std::vector<Ctg> &ctgs, const char *bytes, size_t n,
+                      bool header, const std::string &prefix, size_t idx_id, size_t idx_range, bool *device) {
+    if (device) *device = false;
+    std::vector<const char *> ids(ctgs.size());
     std::vector<int32_t> cs(ctgs.size()), ce(ctgs.size());
     for (size_t i = 0; i < ctgs.size(); ++i) {
         ids[i] = ctgs[i].id.c_str();
@@ -3039,24 +3093,19 @@ std::string anno_text(gams_gpu_t *h, const std::map<std::string, Runlist> &sets,
     }
     struct Guard {
         gams_gpu_t *h;
-        gams_spans_t *sp = nullptr;
-        gams_names_t *chr = nullptr, *ids = nullptr;
+        gams_names_t *ids = nullptr;
         ~Guard() {
-            if (sp) gams_spans_destroy(h, sp);
-            if (chr) gams_names_destroy(h, chr);
             if (ids) gams_names_destroy(h, ids);
         }
     } g{h};
-    check(h, gams_spans_create(h, (uint32_t)chr.size(), off.data(), lo.data(), hi.data(), &g.sp));
-    check(h, gams_names_create(h, (uint32_t)chr.size(), chr.data(), &g.chr));
     check(h, gams_names_create(h, (uint32_t)ids.size(), ids.data(), &g.ids));
     if (idx_id > UINT32_MAX || idx_range > UINT32_MAX) throw Error(GAMS_EINVAL, "anno: field index out of range");
     const char *text = nullptr;
     uint64_t text_bytes = 0, rows = 0;
-    const int rc = gams_gpu_anno_text(h, g.sp, g.chr, g.ids, cs.data(), ce.data(), bytes, n, header ? 1 : 0,
+    const int rc = gams_gpu_anno_text(h, set.spans(), set.chr_names(), g.ids, cs.data(), ce.data(), bytes, n, header ? 1 : 0,
                                       prefix.c_str(), (uint32_t)idx_id, (uint32_t)idx_range, &text, &text_bytes, &rows);
     if (rc == GAMS_EUNSUPPORTED)
-        return anno(h, sets, ctgs, text_lines(bytes, n), header, prefix, idx_id, idx_range);
+        return anno(h, set, ctgs, text_lines(bytes, n), header, prefix, idx_id, idx_range);
     check(h, rc);
     if (device) *device = true;
     return std::string(text, (size_t)text_bytes);

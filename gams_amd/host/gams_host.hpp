@@ -448,6 +448,51 @@ std::string anno(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, cons
 std::string anno_text(gams_gpu_t *h, const std::map<std::string, Runlist> &sets, const std::vector<Ctg> &ctgs,
                       const char *bytes, size_t n, bool header, const std::string &prefix, size_t idx_id,
                       size_t idx_range, bool *device = nullptr);
+
+// The runlist JSON file `anno` loads first (anno.rs:84-87), read on the host (gams_runlist.cpp): the complete reader --
+// escapes, any white space, a key that comes twice keeps its first place and its last value -- and the fallback
+// behind gams_spans_create_runlist_text.  chr[g] names sets[g], in file order; every set is normalised (sorted,
+// overlapping and adjacent spans joined).  GAMS_EINVAL where the reference panics: not an object, a value that is no
+// string, a runlist character that is no digit / '-' / ',', a > b, a number outside i32 (and any malformed document).
+struct RunlistJson {
+    std::vector<std::string> chr;
+    std::vector<Runlist> sets;
+};
+RunlistJson read_runlist_json(const char *bytes, size_t n);
+// one runlist string: what the device accepts, negative numbers (-5--1) and empty tokens next to a comma
+Runlist parse_runlist(const std::string &text);
+
+// The span set of an anno run, built once from the bytes of the runlist JSON file and shared by every input file
+// (anno.rs:84-87 in front of the loop at anno.rs:95): gams_spans_create_runlist_text first; where the device refuses
+// (GAMS_EUNSUPPORTED), read_runlist_json and gams_spans_create.  Owns the span set and the chr name table.
+class AnnoSet {
+public:
+    AnnoSet(gams_gpu_t *h, const char *bytes, size_t n);
+    AnnoSet(gams_gpu_t *h, const std::map<std::string, Runlist> &sets);   // one group per chr, in the map's order
+    ~AnnoSet();
+    AnnoSet(const AnnoSet &) = delete;
+    AnnoSet &operator=(const AnnoSet &) = delete;
+    bool device() const { return device_; }                // the device built it from the bytes
+    gams_spans_t *spans() const { return sp_; }
+    const gams_names_t *chr_names() const { return names_; }
+    const std::vector<std::string> &chrs() const { return chr_; }   // chrs()[g] names group g
+    uint64_t n_spans() const { return n_spans_; }
+
+private:
+    void from_arrays(const std::vector<std::string> &chr, const std::vector<const Runlist *> &sets);
+    gams_gpu_t *h_;
+    gams_spans_t *sp_ = nullptr;
+    gams_names_t *names_ = nullptr;
+    std::vector<std::string> chr_;
+    uint64_t n_spans_ = 0;
+    bool device_ = false;
+};
+// anno() / anno_text() over a set built once
+std::string anno(gams_gpu_t *h, const AnnoSet &set, const std::vector<Ctg> &ctgs, const std::vector<std::string> &lines,
+                 bool header, const std::string &prefix, size_t idx_id, size_t idx_range);
+std::string anno_text(gams_gpu_t *h, const AnnoSet &set, const std::vector<Ctg> &ctgs, const char *bytes, size_t n,
+                      bool header, const std::string &prefix, size_t idx_id, size_t idx_range, bool *device = nullptr);
+
 // BufRead::lines() of the bytes: split on '\n', one '\r' before a '\n' dropped, a last line without '\n' kept
 std::vector<std::string> text_lines(const char *bytes, size_t n);
 // `{:.4}` of an anno prop in [0, 1] as the device prints it (integer arithmetic, csrc/text_fmt.hpp); "" outside

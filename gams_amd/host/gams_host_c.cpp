@@ -591,6 +591,130 @@ char *gams_host_anno_text(gams_gpu_t *h, uint32_t n, const char *const *ids, con
     });
 }
 
+// ---- the span set of an anno run, built once from the bytes of the runlist JSON file (gams::AnnoSet) ----
+// NULL on error (GAMS_EINVAL in gams_host_last_code where the host reader refuses the file).
+// gams_host_last_operator_ms has the ms from the bytes to the usable set, gams_host_last_operator_device the route.
+void *gams_host_anno_set_create(gams_gpu_t *h, const char *data, uint64_t n_bytes) {
+    return guard((void *)nullptr, [&]() -> void * {
+        const auto t0 = std::chrono::steady_clock::now();
+        gams::AnnoSet *set = new gams::AnnoSet(h, data ? data : "", (size_t)n_bytes);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = set->device() ? 1 : 0;
+        return set;
+    });
+}
+void gams_host_anno_set_destroy(void *set) { delete static_cast<gams::AnnoSet *>(set); }
+// 1 if the device built the set from the bytes, 0 if the host reader did
+int gams_host_anno_set_device(const void *set) { return static_cast<const gams::AnnoSet *>(set)->device() ? 1 : 0; }
+// the set's span set (owned by the set; for gams_spans_read and gams_gpu_cover) and its sizes
+gams_spans_t *gams_host_anno_set_spans(const void *set, uint32_t *n_groups, uint64_t *n_spans) {
+    const gams::AnnoSet *s = static_cast<const gams::AnnoSet *>(set);
+    if (n_groups) *n_groups = (uint32_t)s->chrs().size();
+    if (n_spans) *n_spans = s->n_spans();
+    return s->spans();
+}
+// the chr names of the groups, in group order, each followed by a NUL; *out_len = the bytes of all of them
+char *gams_host_anno_set_names(const void *set, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        std::string flat;
+        for (const std::string &c : static_cast<const gams::AnnoSet *>(set)->chrs()) flat += c + '\0';
+        return flat;
+    });
+}
+
+// anno over the bytes of one input file, against a set built once (anno.rs:95: one set, several input files)
+char *gams_host_anno_text_set(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                              const int32_t *starts, const int32_t *ends, const void *set, const char *bytes,
+                              uint64_t n_bytes, int header, const char *prefix, uint32_t idx_id, uint32_t idx_range,
+                              uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        bool dev = false;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::string out = gams::anno_text(h, *static_cast<const gams::AnnoSet *>(set), cv, bytes, (size_t)n_bytes, header != 0,
+                                          prefix ? prefix : "", idx_id, idx_range, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        return out;
+    });
+}
+// ... and over lines, as gams_host_anno
+char *gams_host_anno_set(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                         const int32_t *ends, const void *set, const char *lines, int header, const char *prefix,
+                         uint32_t idx_id, uint32_t idx_range) {
+    return guarded([&] {
+        return gams::anno(h, *static_cast<const gams::AnnoSet *>(set), make_ctgs(n, ids, chrs, starts, ends), split_lines(lines),
+                          header != 0, prefix ? prefix : "", idx_id, idx_range);
+    });
+}
+
+// gams::read_runlist_json: the call keeps the set (per thread) and reports its sizes, gams_host_read_runlist_json_get
+// copies it out: names = the keys back to back, name_off n_groups + 1 offsets into them, group_off n_groups + 1
+// offsets into lo / hi.  Returns 0, or -1 with the message in gams_host_last_error() (code GAMS_EINVAL).
+namespace {
+thread_local gams::RunlistJson g_runlists;
+}  // namespace
+int gams_host_read_runlist_json(const char *data, uint64_t n_bytes, uint32_t *n_groups, uint64_t *n_spans,
+                                uint64_t *name_bytes) {
+    return guard(-1, [&] {
+        g_runlists = gams::read_runlist_json(data ? data : "", (size_t)n_bytes);
+        *n_groups = (uint32_t)g_runlists.chr.size();
+        *n_spans = 0;
+        *name_bytes = 0;
+        for (size_t g = 0; g < g_runlists.chr.size(); ++g) {
+            *n_spans += g_runlists.sets[g].lo.size();
+            *name_bytes += g_runlists.chr[g].size();
+        }
+        return 0;
+    });
+}
+void gams_host_read_runlist_json_get(char *names, uint64_t *name_off, uint64_t *group_off, int32_t *lo, int32_t *hi) {
+    uint64_t nb = 0, ns = 0;
+    for (size_t g = 0; g < g_runlists.chr.size(); ++g) {
+        const std::string &c = g_runlists.chr[g];
+        const gams::Runlist &r = g_runlists.sets[g];
+        name_off[g] = nb;
+        group_off[g] = ns;
+        std::memcpy(names + nb, c.data(), c.size());
+        if (!r.lo.empty()) {
+            std::memcpy(lo + ns, r.lo.data(), r.lo.size() * sizeof(int32_t));
+            std::memcpy(hi + ns, r.hi.data(), r.hi.size() * sizeof(int32_t));
+        }
+        nb += c.size();
+        ns += r.lo.size();
+    }
+    name_off[g_runlists.chr.size()] = nb;
+    group_off[g_runlists.chr.size()] = ns;
+}
+
+// Loads the span set of a runlist JSON file and drops it, reporting the ms of the load itself in
+// gams_host_last_operator_ms: device_route != 0 through gams::AnnoSet (the device entry; the host reader where it
+// refuses), else the host reader and gams_spans_create.  gams_host_last_operator_device says which route built it.
+// Returns the spans of the set, -1 on error.
+int64_t gams_host_runlist_load(gams_gpu_t *h, const char *data, uint64_t n_bytes, int device_route) {
+    return guard((int64_t)-1, [&]() -> int64_t {
+        const char *bytes = data ? data : "";
+        const auto t0 = std::chrono::steady_clock::now();
+        uint64_t spans = 0;
+        bool dev = false;
+        if (device_route) {
+            const gams::AnnoSet set(h, bytes, (size_t)n_bytes);
+            spans = set.n_spans();
+            dev = set.device();
+            g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        } else {
+            gams::RunlistJson js = gams::read_runlist_json(bytes, (size_t)n_bytes);
+            std::map<std::string, gams::Runlist> sets;
+            for (size_t g = 0; g < js.chr.size(); ++g) sets[js.chr[g]] = std::move(js.sets[g]);
+            const gams::AnnoSet set(h, sets);
+            spans = set.n_spans();
+            g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        g_operator_device = dev ? 1 : 0;
+        return (int64_t)spans;
+    });
+}
+
 // `{:.4}` of an anno prop as the device formats it ("" outside [0, 1])
 char *gams_host_fmt_prop4(float p) { return dup(gams::fmt_prop4(p)); }
 // `{}` of an f32 in [0, 1] as the device formats a peak amplitude ("" where it refuses)

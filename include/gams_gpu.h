@@ -393,6 +393,9 @@ int gams_gpu_cover(gams_gpu_t *h, gams_spans_t *sp, const uint32_t *group,
  * names' bytes so that kernels can print them.  Lookup is exact byte equality; a duplicate name is GAMS_EINVAL.
  * Uses: chromosome name -> group of a ctg index or a span set; ctg id -> ctg slot (anno); ctg slot -> id (locate). */
 int gams_names_create(gams_gpu_t *h, uint32_t n, const char *const *names, gams_names_t **out);
+/* The names of a table back (one that gams_spans_create_runlist_text made, for instance): *n names, *n_bytes bytes;
+ * with `bytes` / `off` not NULL the names' bytes back to back (no NUL between) and the n + 1 offsets into them. */
+int gams_names_read(gams_gpu_t *h, const gams_names_t *nm, uint32_t *n, uint64_t *n_bytes, char *bytes, uint64_t *off);
 void gams_names_destroy(gams_gpu_t *h, gams_names_t *nm);
 
 /* The three entries below take the bytes of an input file (n_bytes, any host memory; page-locked memory from
@@ -432,6 +435,30 @@ int gams_gpu_anno_text(gams_gpu_t *h, gams_spans_t *sp, const gams_names_t *chr_
                        const int32_t *ctg_start, const int32_t *ctg_end, const char *bytes, uint64_t n_bytes, int header,
                        const char *prefix, uint32_t idx_id, uint32_t idx_range, const char **text, uint64_t *text_bytes,
                        uint64_t *n_rows);
+
+/* ---- text in, span set out: the runlist JSON of anno (anno.rs:84-87: intspan::read_json, then json2set) ---- */
+/* The bytes of a runlist JSON file -- one flat object {"chr": "runlist", ...} -- to a span set that behaves under
+ * gams_gpu_cover and gams_gpu_anno_text exactly like one from gams_spans_create on the normalised spans
+ * (IntSpan::add_runlist: the union of the spans, overlapping and adjacent ones joined).  Group g is the g-th key of
+ * the object in file order and *chr_names names the groups in that order (for gams_gpu_anno_text); *n_groups and
+ * *n_spans receive the sizes.  A runlist is tokens separated by ',', each `a` or `a-b` of 1-10 decimal digits with
+ * a <= b <= INT32_MAX, in any order; the values "" and "-" are the empty set.  White space between the strings is
+ * free (compact, pretty-printed, CRLF); "{}" is a set with no group.
+ * GAMS_EUNSUPPORTED (run the host reader instead, which is the judge of what is invalid: this entry never answers
+ * GAMS_EINVAL for the file's content): a backslash, a byte >= 0x80 or a NUL anywhere; a control character (below
+ * 0x20) inside a key; anything that is not a flat
+ * object of string values (a nested value, a number, null, an array, a missing brace, text behind the '}'); inside
+ * a runlist any byte that is no digit, '-' or ',' (white space included), an empty token, more than 10 digits, a
+ * value above INT32_MAX, a > b, a negative number; a duplicate key; more than 2^32 - 16 tokens.
+ * On any return but GAMS_OK nothing is created, *sp and *chr_names are NULL and the handle stays usable.  Release
+ * with gams_spans_destroy and gams_names_destroy. */
+int gams_spans_create_runlist_text(gams_gpu_t *h, const char *bytes, uint64_t n_bytes, gams_spans_t **sp,
+                                   gams_names_t **chr_names, uint32_t *n_groups, uint64_t *n_spans);
+/* A span set as arrays, for hosts and tests: group_off[n_groups + 1], and lo / hi (cap entries each) when
+ * cap >= *n_spans.  cap = 0 is the size query: only group_off and *n_spans are written.  GAMS_EINVAL for a cap
+ * between 1 and the set's size. */
+int gams_spans_read(gams_gpu_t *h, const gams_spans_t *sp, uint64_t *group_off, int32_t *lo, int32_t *hi, uint64_t cap,
+                    uint64_t *n_spans);
 
 /* ---- text in, index out: the rg loader (utils.rs:39-67 read_range, then redis.rs:288-299) ---- */
 /* The two entries below take the bytes of ONE .rg file (lines, refused bytes and the 2^32 - 1 line limit as above) and
