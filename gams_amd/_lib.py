@@ -18,6 +18,7 @@ WAVE_BODY_AUTO, WAVE_BODY_WIDE, WAVE_BODY_NARROW = 0, 1, 2      # gams_wave_plan
 WAVE_CUT_AUTO, WAVE_CUT_TWO_WAVES, WAVE_CUT_ONE_WAVE = 0, 1, 2  # gams_wave_plan_set_cut / _last_cut
 GC_BODY_AUTO, GC_BODY_PORTABLE, GC_BODY_AVX2 = 0, 1, 2          # gams_gc_plane_with
 SW_GC, SW_COUNT = 1, 2          # GAMS_SW_GC / GAMS_SW_COUNT: the action set of gams_gpu_sw_text_actions
+SW_SUMMARY_MAX_ANNO = 4         # GAMS_SW_SUMMARY_MAX_ANNO: the span sets (Prop columns) of one sw summary
 SW_SUMMARY_WORDS = 10           # GAMS_SW_SUMMARY_WORDS: COUNT, four S, four NaN counters, C of a summary group
 LOADER_RG, LOADER_FEATURE = 0, 1                      # gams_gpu_loader_text: kind
 LOADER_RECORDS, LOADER_TSV, LOADER_RESP = 0, 1, 2     # ... and format
@@ -160,6 +161,14 @@ PROTOTYPES = {
     "gams_sw_summary_destroy": (None, [_VP, _VP]),
     "gams_gpu_sw_summary_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "gams_sw_summary_create_anno": (C.c_int, [_VP, C.c_int32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, _PP]),
+    "gams_sw_summary_read_anno": (C.c_int, [_VP, _VP, _VP]),
+    "gams_gpu_sw_summary_batch_anno": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP,
+                                                 C.POINTER(C.c_uint64)]),
+    "gams_gpu_sw_feature_summary_anno": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int32, C.c_int32,
+                                                   C.c_int32, C.c_uint32, _VP, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP,
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gams_gpu_locate_seq_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64),
                                            C.POINTER(C.c_uint64)]),
     "gams_gpu_locate_seq_chunk": (C.c_uint32, []),

@@ -279,6 +279,11 @@ struct SwColsJob {
     // and never stored; the name tables above and the text outputs of the launcher are unused (NULL)
     gams_sw_summary_t *summary;
     uint32_t tag;
+    // gams_gpu_sw_feature_summary_anno: the span sets of the Prop columns and, per set, a host column of n_ctg groups
+    // (set_group[a][i] = the group of interval i's chromosome in set a, UINT32_MAX: absent); n_anno 0: none
+    uint32_t n_anno;
+    gams_spans_t *const *sets;
+    const uint32_t *const *set_group;
 };
 
 // The accumulator of the sw summaries (sw.hip): n_tags x (max + 1) groups of GAMS_SW_SUMMARY_WORDS 64-bit
@@ -288,10 +293,16 @@ struct gams_sw_summary {
     int32_t size = 0, max = 0, resize = 0;
     uint32_t actions = 0, n_tags = 0;
     unsigned long long *d_acc = nullptr, *d_call = nullptr;
+    // with span sets (gams_sw_summary_create_anno): the Prop sums, n_tags x (max + 1) x n_anno words beside d_acc, and
+    // (max + 1) x n_anno more words of the call's table behind its flag word
+    uint32_t n_anno = 0;
+    unsigned long long *d_prop = nullptr;
 };
-// the call's parameters against the accumulator's binding and the tag slot against its tags: GAMS_EINVAL otherwise
+// the call's parameters against the accumulator's binding, the tag slot against its tags and the span sets against the
+// number it was made for (none of them NULL; need_cols: nor a set_group column): GAMS_EINVAL otherwise
 int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, int32_t size, int32_t max,
-                          int32_t resize, uint32_t actions, uint32_t tag);
+                          int32_t resize, uint32_t actions, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
+                          const uint32_t *const *set_group, bool need_cols);
 // the timed pairs of the handle (gams_gpu::kq) these stages record: behind the range loader's lines .. order (0 .. 6)
 enum : int { SWF_GATHER = 7, SWF_GEOM, SWF_ROWS, SWF_TLEN, SWF_TWRITE, SWF_STAGES };
 // *text (the handle's page-locked sw text, valid until the next sw call), text_off[n_ctg + 1], *n_rows.  GAMS_EINVAL for

@@ -354,6 +354,35 @@ __device__ __forceinline__ SpanCell load_cell(const SpanCell *p) {
     return u.c;
 }
 
+// |spans of group G (number g of its set) ∩ [L, H]| for H >= L: one 64-B cell record per end of the range (the same
+// record when both ends fall in one cell); a cell that starts more than five spans takes the directory, a search and the
+// walk instead.  Shared by span_cover_kernel and the sw summary's Prop columns (sw.hip).
+__device__ __forceinline__ uint64_t span_cover_card(const SpanGroup *groups, const SpanRec *rec, const uint32_t *dir,
+                                                    const SpanCell *cells, uint32_t g, int32_t L, int32_t H) {
+    const SpanGroup G = groups[g];
+    uint32_t bh = 0, bl = 0;
+    uint64_t upto_h = 0, upto_l = 0;
+    bool ok_h = true, ok_l = true;
+    const bool any_h = span_cell_of(G, H, bh);
+    const bool any_l = L > INT32_MIN && span_cell_of(G, L - 1, bl);
+    if (any_h) {
+        const SpanCell ch = load_cell(cells + G.off + g + bh);
+        upto_h = covered_cell(ch, G.n, H, ok_h);
+        if (any_l) {
+            if (bl == bh)
+                upto_l = covered_cell(ch, G.n, L - 1, ok_l);
+            else
+                upto_l = covered_cell(load_cell(cells + G.off + g + bl), G.n, L - 1, ok_l);
+        }
+    }
+    if (!(ok_h && ok_l)) {                     // a crowded cell: directory + search + walk
+        uint32_t rank_h;
+        upto_h = covered_upto(rec, dir, G, g, H, &rank_h);
+        upto_l = L > INT32_MIN ? covered_upto_below(rec, dir, G, g, L - 1, rank_h) : 0;
+    }
+    return upto_h - upto_l;
+}
+
 __global__ __launch_bounds__(256) void span_cover_kernel(const SpanGroup *groups, const SpanRec *rec,
                                                          const uint32_t *dir, const SpanCell *cells, uint32_t n_groups,
                                                          const uint32_t *group, const int32_t *clip_lo,
@@ -368,31 +397,7 @@ __global__ __launch_bounds__(256) void span_cover_kernel(const SpanGroup *groups
         const int32_t L = s > clip_lo[q] ? s : clip_lo[q];
         const int32_t H = e < clip_hi[q] ? e : clip_hi[q];
         uint64_t card = 0;
-        if (H >= L) {
-            const SpanGroup G = groups[g];
-            // one 64-B cell record per end of the range (the same record when both ends fall in one cell)
-            uint32_t bh = 0, bl = 0;
-            uint64_t upto_h = 0, upto_l = 0;
-            bool ok_h = true, ok_l = true;
-            const bool any_h = span_cell_of(G, H, bh);
-            const bool any_l = L > INT32_MIN && span_cell_of(G, L - 1, bl);
-            if (any_h) {
-                const SpanCell ch = load_cell(cells + G.off + g + bh);
-                upto_h = covered_cell(ch, G.n, H, ok_h);
-                if (any_l) {
-                    if (bl == bh)
-                        upto_l = covered_cell(ch, G.n, L - 1, ok_l);
-                    else
-                        upto_l = covered_cell(load_cell(cells + G.off + g + bl), G.n, L - 1, ok_l);
-                }
-            }
-            if (!(ok_h && ok_l)) {                     // a crowded cell: directory + search + walk
-                uint32_t rank_h;
-                upto_h = covered_upto(rec, dir, G, g, H, &rank_h);
-                upto_l = L > INT32_MIN ? covered_upto_below(rec, dir, G, g, L - 1, rank_h) : 0;
-            }
-            card = upto_h - upto_l;
-        }
+        if (H >= L) card = span_cover_card(groups, rec, dir, cells, g, L, H);
         const int32_t total = (int32_t)((int64_t)e - s + 1);
         prop = (float)(int32_t)card / (float)total;  // cardinality() as f32 / cardinality() as f32
     }

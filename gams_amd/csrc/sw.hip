@@ -20,7 +20,9 @@
 // idx:rg: group of its ctg -- the lookup of `locate --count` (lapper_count, interval_kernels.hpp), run by the
 // same thread that holds the window.  sw_kernel<kGc, kCount> is instantiated per action set; without kGc it
 // neither needs the gc index nor touches the sequence bytes.  A third flag, kSum, keeps the row in registers and adds it
-// into the per-distance summary instead of storing it.
+// into the per-distance summary instead of storing it.  sw_anno_kernel<kGc, kCount> is that summarising
+// kernel joined with up to four resident span sets: per row and set the covered share of the window (span_cover_card, the
+// lookup of `anno`), summed as the integer the text would print -- the Prop columns of fsw-distance-tag.tera.sql.
 
 #include "interval_kernels.hpp"
 #include "text_emit.hpp"
@@ -196,6 +198,24 @@ struct SwArgs {
     uint64_t sum_chunks;
 };
 
+// The span sets of a summarising call with Prop columns, a kernel argument of its own so that SwArgs and
+// the instantiations without sets stay what they are: per set the four tables of its gams_spans_t, its groups, and
+// set_group[k] = the group of ctg k's chromosome in it (UINT32_MAX: the chromosome is absent, the prop is 0), k as
+// a.fctg numbers the ctgs.  prop: the call's Prop sums, (max + 1) x n words, group-major.
+struct SwAnnoOne {
+    const SpanGroup *groups;
+    const SpanRec *rec;
+    const uint32_t *dir;
+    const SpanCell *cells;
+    const uint32_t *set_group;
+    uint32_t n_groups, pad;
+};
+struct SwAnno {
+    SwAnnoOne set[GAMS_SW_SUMMARY_MAX_ANNO];
+    unsigned long long *prop;
+    uint32_t n, pad;
+};
+
 // gc_content of chromosome range [s,e] (inclusive) inside the ctg: count / len, f32
 __device__ __forceinline__ float range_gc(const SwArgs &a, int32_t s, int32_t e) {
     // parent.index(): from = s - chr_start + 1 (1-based), bytes [from-1, to)
@@ -341,6 +361,10 @@ enum : uint32_t { SUM_COUNT = 0, SUM_S = 1, SUM_NAN = 5, SUM_C = 9 };
 // 20 KiB, an eighth of a CU's 160 KiB, so the table never lowers the 8 workgroups of 256 threads a CU holds.  A call with
 // more distances (max >= 256) adds to global memory directly.
 constexpr uint32_t kSumLdsGroups = 256;
+// With n span sets a group has n more words, the Prop sums P_a, kept behind the groups' ten words in the same 20 KiB: the
+// call reduces in LDS while (max + 1) x (10 + n) <= 256 x 10 = 2560 words -- max <= 255, 231, 212, 195, 181 for n = 0 .. 4
+// -- so the table never grows and the 8 workgroups a CU stay.
+constexpr uint32_t kSumLdsWords = kSumLdsGroups * kSumWords;
 
 // one row into group `g` (LDS or global); `bad`: a statistic the text formatter does not cover either
 template <bool kGc, bool kCount>
@@ -367,24 +391,50 @@ __device__ __forceinline__ void sw_sum_put(unsigned long long *g, const gams_sw_
 // 16 000 chunks of the kept workload queued 1.7e6 atomics on the same 105 words and the stage took 0.37 ms
 // (profiles/sw_summary.txt).  The table: the call's distances in LDS, flushed once, non-zero bins only, or -- beyond
 // kSumLdsGroups distances -- the call's table in global memory directly.
-template <bool kGc, bool kCount>
-__device__ __forceinline__ void sw_sum_chunks(const SwArgs &a, uint64_t n_chunks) {
-    __shared__ unsigned long long bins[kSumLdsGroups * kSumWords];
+// The Prop units of the window [ws, we] of ctg k against every set, into the group's n words at p (LDS or global):
+// anno.rs:122-140 with the ctg clip left out (a window lies inside its ctg) -- the covered cardinality by span_cover_kernel's
+// lookup, two cell records a set, prop = |.| as f32 / len as f32 and the q that `{:.4}` prints.  Zero adds nothing.
+__device__ __forceinline__ void sw_sum_put_anno(unsigned long long *p, const SwAnno &an, uint32_t k, int32_t ws, int32_t we) {
+    const float len = (float)(int32_t)((int64_t)we - ws + 1);
+#pragma unroll
+    for (uint32_t s = 0; s < GAMS_SW_SUMMARY_MAX_ANNO; ++s) {
+        if (s >= an.n) break;
+        const SwAnnoOne &A = an.set[s];
+        const uint32_t g = A.set_group[k];
+        if (g >= A.n_groups) continue;                         // anno.rs:128: the chromosome is not in the set
+        const uint64_t card = span_cover_card(A.groups, A.rec, A.dir, A.cells, g, ws, we);
+        const float prop = (float)(int32_t)card / len;
+        if (!(prop >= 0.0f && prop <= 1.0f)) continue;         // (cannot happen: card <= len)
+        if (const uint32_t q = gams_prop4_units(prop)) atomicAdd(p + s, (unsigned long long)q);
+    }
+}
+
+template <bool kGc, bool kCount, bool kAnno>
+__device__ __forceinline__ void sw_sum_chunks(const SwArgs &a, uint64_t n_chunks, const SwAnno *an) {
+    __shared__ unsigned long long bins[kSumLdsWords];
     const uint32_t words = ((uint32_t)a.max + 1u) * kSumWords;
-    const bool lds = (uint32_t)a.max < kSumLdsGroups;          // uniform
+    const uint32_t n_anno = kAnno ? an->n : 0u, pwords = ((uint32_t)a.max + 1u) * n_anno;
+    // uniform; with sets, both tables in the same 2560 words (the sum below stays under 2^32: max <= 2^24)
+    const bool lds = kAnno ? (uint64_t)words + pwords <= kSumLdsWords : (uint32_t)a.max < kSumLdsGroups;
     bool bad = false;
     if (lds) {
-        for (uint32_t i = threadIdx.x; i < words; i += 256u) bins[i] = 0ull;
+        for (uint32_t i = threadIdx.x; i < words + pwords; i += 256u) bins[i] = 0ull;
         __syncthreads();
     }
     for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         gams_sw_row_t r;
         int32_t cnt = 0;
-        if (!sw_row<kGc, kCount, true>(a, chunk * 256u + threadIdx.x, r, cnt)) continue;
+        const uint64_t gid = chunk * 256u + threadIdx.x;
+        if (!sw_row<kGc, kCount, true>(a, gid, r, cnt)) continue;
         if (lds)
             sw_sum_put<kGc, kCount>(bins + (uint32_t)r.distance * kSumWords, r, cnt, bad);
         else
             sw_sum_put<kGc, kCount>(a.sum + (uint64_t)(uint32_t)r.distance * kSumWords, r, cnt, bad);
+        if constexpr (kAnno) {
+            const uint32_t k = a.fctg[gid / (1u + 2u * (uint32_t)a.max)];   // the row's ctg, as sw_row found it
+            unsigned long long *const p = lds ? bins + words : an->prop;
+            sw_sum_put_anno(p + (uint64_t)(uint32_t)r.distance * n_anno, *an, k, r.start, r.end);
+        }
     }
     if (bad) *a.sum_bad = 1ull;
     if (lds) {
@@ -393,18 +443,29 @@ __device__ __forceinline__ void sw_sum_chunks(const SwArgs &a, uint64_t n_chunks
             const unsigned long long v = bins[i];
             if (v) atomicAdd(a.sum + i, v);
         }
+        if constexpr (kAnno)
+            for (uint32_t i = threadIdx.x; i < pwords; i += 256u) {
+                const unsigned long long v = bins[words + i];
+                if (v) atomicAdd(an->prop + i, v);
+            }
     }
 }
 
 template <bool kGc, bool kCount, bool kSum = false>
 __global__ __launch_bounds__(256) void sw_kernel(const SwArgs a0) {
     if constexpr (kSum) {
-        sw_sum_chunks<kGc, kCount>(a0, a0.sum_chunks);
+        sw_sum_chunks<kGc, kCount, false>(a0, a0.sum_chunks, nullptr);
     } else {
         gams_sw_row_t r;
         int32_t cnt = 0;
         (void)sw_row<kGc, kCount, false>(a0, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, r, cnt);
     }
+}
+
+// the summarising kernel with Prop columns: sw_kernel<kGc, kCount, true> with the sets beside its arguments
+template <bool kGc, bool kCount>
+__global__ __launch_bounds__(256) void sw_anno_kernel(const SwArgs a0, const SwAnno an) {
+    sw_sum_chunks<kGc, kCount, true>(a0, a0.sum_chunks, &an);
 }
 
 // the call's table into the accumulator's groups of its tag, unless the call met a value it does not cover
@@ -753,6 +814,11 @@ struct SwReq {
     const SwTextReq *tx;
     gams_sw_summary_t *sum;              // gams_gpu_sw_summary_batch: the rows go into tag slot `tag` of it
     uint32_t tag;
+    // gams_gpu_sw_summary_batch_anno: the span sets of the Prop columns and, per set, the group of every selected ctg
+    uint32_t n_anno;
+    gams_spans_t *const *sets;
+    const uint32_t *const *set_group;
+    const SwAnno *an;                    // sw_launch: what SwAnnoStage made of them (NULL: no set)
 };
 
 using SwCols = SwStage<SwCtg>;
@@ -831,6 +897,39 @@ int sw_host_rows(const SwReq &q, uint32_t nf, const SwCols &in, std::vector<uint
     return GAMS_OK;
 }
 
+// The sets of a summarising call for the kernel: the set_group columns (n_cols entries each, the caller's host arrays) on
+// the device through one page-locked block, and the tables of every gams_spans_t.  Lives until the call has drained.
+struct SwAnnoStage {
+    PoolBlock dev, pin;
+    SwAnno an{};
+    explicit SwAnnoStage(gams_gpu_t *h) : dev(h, false), pin(h, true) {}
+    int put(gams_gpu_t *h, const gams_sw_summary_t *sum, uint32_t n, gams_spans_t *const *sets,
+            const uint32_t *const *set_group, uint32_t n_cols) {
+        const size_t col = gams_align256((size_t)std::max(n_cols, 1u) * 4);
+        GAMS_TRY(h, kSwSum, pin.alloc(col * n));
+        GAMS_TRY(h, kSwSum, dev.alloc(col * n));
+        for (uint32_t a = 0; a < n; ++a) {
+            std::memcpy(pin.p + a * col, set_group[a], (size_t)n_cols * 4);
+            an.set[a] = SwAnnoOne{sets[a]->d_groups, sets[a]->d_rec, sets[a]->d_dir_lo, sets[a]->d_cells,
+                                  reinterpret_cast<const uint32_t *>(dev.p + a * col), sets[a]->n_groups, 0u};
+        }
+        GAMS_TRY(h, kSwSum, hipMemcpyAsync(dev.p, pin.p, col * n, hipMemcpyHostToDevice, h->compute));
+        an.n = n;
+        an.prop = sum->d_call + ((size_t)sum->max + 1) * kSumWords + 1;   // behind the call's table and its flag word
+        return GAMS_OK;
+    }
+};
+// the sets of an _anno entry against the accumulator
+int sw_anno_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, uint32_t n_anno,
+                  gams_spans_t *const *sets, const uint32_t *const *set_group, bool need_cols) {
+    if (n_anno > GAMS_SW_SUMMARY_MAX_ANNO) return gams_fail(h, GAMS_EINVAL, who + ": more than GAMS_SW_SUMMARY_MAX_ANNO span sets");
+    if (n_anno != sum->n_anno) return gams_fail(h, GAMS_EINVAL, who + ": the accumulator was created for another number of span sets");
+    if (n_anno && (!sets || !set_group)) return gams_fail(h, GAMS_EINVAL, who + ": null span sets or set groups");
+    for (uint32_t a = 0; a < n_anno; ++a)
+        if (!sets[a] || (need_cols && !set_group[a])) return gams_fail(h, GAMS_EINVAL, who + ": a null span set or set group column");
+    return GAMS_OK;
+}
+
 // 3'. the summarising kernel: the call's table zeroed, the rows added into it, the table merged into the tag's groups
 // unless the flag word behind it was raised; one read-back, of that word
 int sw_sum_launch(const SwReq &q, SwArgs &a, dim3 grid) {
@@ -843,8 +942,20 @@ int sw_sum_launch(const SwReq &q, SwArgs &a, dim3 grid) {
     a.sum_chunks = grid.x;                                     // what the storing kernel launches, walked by ...
     grid.x = std::min<uint32_t>(grid.x, 8u * (uint32_t)std::max(h->cus, 1));   // ... the workgroups a device holds at once
     hipStream_t st = h->compute;
-    GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_call, 0, ((size_t)words + 1) * 8, st));
-    if (do_gc && do_count)
+    const uint32_t pwords = ((uint32_t)sum->max + 1u) * sum->n_anno;
+    GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_call, 0, ((size_t)words + 1 + pwords) * 8, st));
+    if (q.an) {                                                // (sum->n_anno sets: the entries checked)
+        if (do_gc && do_count)
+            hipLaunchKernelGGL((sw_anno_kernel<true, true>), grid, dim3(256), 0, st, a, *q.an);
+        else if (do_gc)
+            hipLaunchKernelGGL((sw_anno_kernel<true, false>), grid, dim3(256), 0, st, a, *q.an);
+        else if (do_count)
+            hipLaunchKernelGGL((sw_anno_kernel<false, true>), grid, dim3(256), 0, st, a, *q.an);
+        else
+            hipLaunchKernelGGL((sw_anno_kernel<false, false>), grid, dim3(256), 0, st, a, *q.an);
+        hipLaunchKernelGGL(sw_sum_merge_kernel, dim3((pwords + 255u) / 256u), dim3(256), 0, st, q.an->prop, a.sum_bad,
+                           sum->d_prop + (size_t)q.tag * pwords, pwords);
+    } else if (do_gc && do_count)
         hipLaunchKernelGGL((sw_kernel<true, true, true>), grid, dim3(256), 0, st, a);
     else if (do_gc)
         hipLaunchKernelGGL((sw_kernel<true, false, true>), grid, dim3(256), 0, st, a);
@@ -1093,7 +1204,13 @@ int sw_batch_impl(const SwReq &q) {
     GAMS_TRY(h, kSw, dev.alloc(layout_bytes(device)));
     carve(dev.p, device);
     GAMS_TRY(h, kSw, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
-    if ((rc = sw_launch(q, nf, n_out, d, d_rows, d_cnt)) != GAMS_OK) return rc;
+    SwAnnoStage sets(h);
+    SwReq ql = q;
+    if (q.sum && q.n_anno) {
+        if ((rc = sets.put(h, q.sum, q.n_anno, q.sets, q.set_group, q.n_sel)) != GAMS_OK) return rc;
+        ql.an = &sets.an;
+    }
+    if ((rc = sw_launch(ql, nf, n_out, d, d_rows, d_cnt)) != GAMS_OK) return rc;
     if (q.sum) return sw_sum_verdict(h, q.sum);
     if (q.tx) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt);
     // 5. read back
@@ -1167,6 +1284,12 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
         carve(r_dev.p, rows);
     }
     SwReq q{};
+    SwAnnoStage sets(h);
+    if (J.summary && J.n_anno) {
+        const int ra = sets.put(h, J.summary, J.n_anno, J.sets, J.set_group, n_ctg);
+        if (ra != GAMS_OK) return ra;
+        q.an = &sets.an;
+    }
     q.sum = J.summary;
     q.tag = J.tag;
     q.h = h;
@@ -1268,8 +1391,11 @@ extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel,
 
 // ---- the accumulator of the sw summaries -----------------------------------------------------------------------------
 int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, int32_t size, int32_t max,
-                          int32_t resize, uint32_t actions, uint32_t tag) {
+                          int32_t resize, uint32_t actions, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
+                          const uint32_t *const *set_group, bool need_cols) {
     if (!sum) return gams_fail(h, GAMS_EINVAL, who + ": null argument");
+    const int ra = sw_anno_check(h, who, sum, n_anno, sets, set_group, need_cols);
+    if (ra != GAMS_OK) return ra;
     if (sum->size != size || sum->max != max || sum->resize != resize || sum->actions != actions)
         return gams_fail(h, GAMS_EINVAL, who + ": the accumulator was created for other size, max, resize or actions");
     if (tag >= sum->n_tags) return gams_fail(h, GAMS_EINVAL, who + ": tag slot beyond the accumulator's tags");
@@ -1278,8 +1404,15 @@ int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_s
 
 extern "C" int gams_sw_summary_create(gams_gpu_t *h, int32_t max, uint32_t n_tags, uint32_t actions, int32_t size,
                                       int32_t resize, gams_sw_summary_t **out) {
+    return gams_sw_summary_create_anno(h, max, n_tags, actions, size, resize, 0u, out);
+}
+
+extern "C" int gams_sw_summary_create_anno(gams_gpu_t *h, int32_t max, uint32_t n_tags, uint32_t actions, int32_t size,
+                                           int32_t resize, uint32_t n_anno, gams_sw_summary_t **out) {
     if (!h || !out) return gams_fail(h, GAMS_EINVAL, "sw_summary_create: null argument");
     *out = nullptr;
+    if (n_anno > GAMS_SW_SUMMARY_MAX_ANNO)
+        return gams_fail(h, GAMS_EINVAL, "sw_summary_create: more than GAMS_SW_SUMMARY_MAX_ANNO span sets");
     if (n_tags == 0 || size < 2 || max < 0 || max > (1 << 24) || resize < 2 || (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)))
         return gams_fail(h, GAMS_EINVAL, "sw_summary_create: n_tags >= 1, size >= 2, 0 <= max <= 2^24, resize >= 2, known action bits");
     GAMS_HIP(h, hipSetDevice(h->device));
@@ -1290,13 +1423,18 @@ extern "C" int gams_sw_summary_create(gams_gpu_t *h, int32_t max, uint32_t n_tag
     sum->resize = resize;
     sum->actions = actions;
     sum->n_tags = n_tags;
+    sum->n_anno = n_anno;
+    const size_t pwords = ((size_t)max + 1) * n_anno;          // the Prop sums, beside the ten words of every group
     hipError_t e = hipMalloc(&sum->d_acc, words * n_tags * 8);
-    if (e == hipSuccess) e = hipMalloc(&sum->d_call, (words + 1) * 8);
+    if (e == hipSuccess) e = hipMalloc(&sum->d_call, (words + 1 + pwords) * 8);
     if (e == hipSuccess) e = hipMemsetAsync(sum->d_acc, 0, words * n_tags * 8, h->compute);
+    if (e == hipSuccess && pwords) e = hipMalloc(&sum->d_prop, pwords * n_tags * 8);
+    if (e == hipSuccess && pwords) e = hipMemsetAsync(sum->d_prop, 0, pwords * n_tags * 8, h->compute);
     if (e != hipSuccess) {
         (void)hipGetLastError();   // reported below, not left sticky
         (void)hipFree(sum->d_acc);
         (void)hipFree(sum->d_call);
+        (void)hipFree(sum->d_prop);
         delete sum;
         return gams_fail(h, GAMS_ENOMEM, std::string("sw_summary_create: ") + hipGetErrorString(e));
     }
@@ -1308,6 +1446,18 @@ extern "C" int gams_sw_summary_reset(gams_gpu_t *h, gams_sw_summary_t *sum) {
     if (!h || !sum) return gams_fail(h, GAMS_EINVAL, "sw_summary_reset: null argument");
     GAMS_HIP(h, hipSetDevice(h->device));
     GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_acc, 0, ((size_t)sum->max + 1) * kSumWords * sum->n_tags * 8, h->compute));
+    if (sum->d_prop)
+        GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_prop, 0, ((size_t)sum->max + 1) * sum->n_anno * sum->n_tags * 8, h->compute));
+    return GAMS_OK;
+}
+
+extern "C" int gams_sw_summary_read_anno(gams_gpu_t *h, gams_sw_summary_t *sum, uint64_t *prop) {
+    if (!h || !sum || (sum->n_anno && !prop)) return gams_fail(h, GAMS_EINVAL, "sw_summary_read_anno: null argument");
+    if (!sum->n_anno) return GAMS_OK;
+    GAMS_HIP(h, hipSetDevice(h->device));
+    const size_t n = ((size_t)sum->max + 1) * sum->n_tags * sum->n_anno;
+    GAMS_TRY(h, kSwSum, hipMemcpyAsync(prop, sum->d_prop, n * 8, hipMemcpyDeviceToHost, h->compute));
+    GAMS_TRY(h, kSwSum, hipStreamSynchronize(h->compute));
     return GAMS_OK;
 }
 
@@ -1339,7 +1489,27 @@ extern "C" void gams_sw_summary_destroy(gams_gpu_t *h, gams_sw_summary_t *sum) {
     }
     (void)hipFree(sum->d_acc);
     (void)hipFree(sum->d_call);
+    (void)hipFree(sum->d_prop);
     delete sum;
+}
+
+extern "C" int gams_gpu_sw_summary_batch_anno(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                              const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                                              const int32_t *feat_end, int32_t size, int32_t max, int32_t resize,
+                                              uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
+                                              gams_sw_summary_t *sum, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
+                                              const uint32_t *const *set_group, uint64_t *n_rows) {
+    if (!h || !n_rows || (n_sel && !feat_off)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: null argument");
+    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: unknown action bits");
+    if ((actions & GAMS_SW_COUNT) && (!rg_ix || (n_sel && !rg_group)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: GAMS_SW_COUNT without an rg index or rg groups");
+    const int rc = gams_sw_summary_check(h, kSwSum, sum, size, max, resize, actions, tag, n_anno, sets, set_group, n_sel != 0);
+    if (rc != GAMS_OK) return rc;
+    const bool cnt = (actions & GAMS_SW_COUNT) != 0;
+    SwReq q{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions,
+            cnt ? rg_ix : nullptr, cnt ? rg_group : nullptr, nullptr, nullptr, 0, nullptr, n_rows, nullptr, sum, tag,
+            n_anno, sets, set_group, nullptr};
+    return sw_batch_impl(q);
 }
 
 extern "C" int gams_gpu_sw_summary_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -1347,16 +1517,8 @@ extern "C" int gams_gpu_sw_summary_batch(gams_gpu_t *h, gams_seqset_t *s, uint32
                                          const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
                                          gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
                                          uint64_t *n_rows) {
-    if (!h || !n_rows || (n_sel && !feat_off)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: null argument");
-    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: unknown action bits");
-    if ((actions & GAMS_SW_COUNT) && (!rg_ix || (n_sel && !rg_group)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: GAMS_SW_COUNT without an rg index or rg groups");
-    const int rc = gams_sw_summary_check(h, kSwSum, sum, size, max, resize, actions, tag);
-    if (rc != GAMS_OK) return rc;
-    const bool cnt = (actions & GAMS_SW_COUNT) != 0;
-    SwReq q{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions,
-            cnt ? rg_ix : nullptr, cnt ? rg_group : nullptr, nullptr, nullptr, 0, nullptr, n_rows, nullptr, sum, tag};
-    return sw_batch_impl(q);
+    return gams_gpu_sw_summary_batch_anno(h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize,
+                                          actions, rg_ix, rg_group, sum, tag, 0u, nullptr, nullptr, n_rows);
 }
 
 extern "C" int gams_gpu_sw(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_start,

@@ -1504,6 +1504,9 @@ struct SwFeatJob {
     const uint32_t *rg_group;
     gams_sw_summary_t *summary;               // gams_gpu_sw_feature_summary: the rows go into tag slot `tag` of it, and
     uint32_t tag;                             // the three text outputs below are NULL
+    uint32_t n_anno;                          // gams_gpu_sw_feature_summary_anno: the span sets and their per-interval groups
+    gams_spans_t *const *sets;
+    const uint32_t *const *set_group;
 };
 
 int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_t n_bytes, const char **text,
@@ -1610,6 +1613,9 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         S.words = g.words;
         S.summary = J.summary;
         S.tag = J.tag;
+        S.n_anno = J.n_anno;
+        S.sets = J.sets;
+        S.set_group = J.set_group;
         const int rc = gams_launch_sw_cols(h, S, text, text_bytes, text_off, n_rows);
         if (rc != GAMS_OK) return rc;
         rg_timed(h, J.summary ? SWF_ROWS + 1 : SWF_STAGES);
@@ -2526,15 +2532,16 @@ int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_
         return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: chr_names must name every group of ctg_ix");
     if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw_feature_text: max beyond 2^24 windows a side");
     return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
-                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, nullptr, 0u},
+                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, nullptr, 0u, 0u, nullptr, nullptr},
                           bytes, n_bytes, text, text_bytes, text_off, n_features, n_rows);
 }
 
-int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+int gams_gpu_sw_feature_summary_anno(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
                                 const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
                                 const int32_t *chr_end, const char *bytes, uint64_t n_bytes, int32_t size, int32_t max,
                                 int32_t resize, uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
-                                gams_sw_summary_t *sum, uint32_t tag, uint64_t *n_features, uint64_t *n_rows) {
+                                gams_sw_summary_t *sum, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
+                                const uint32_t *const *set_group, uint64_t *n_features, uint64_t *n_rows) {
     // the checks of gams_gpu_sw_feature_text, in its order, then the accumulator's
     const std::string who = "gpu_sw_feature_summary";
     const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
@@ -2551,11 +2558,21 @@ int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *c
     if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, who + ": ctg_ids must name every interval of ctg_ix");
     if (chr_names->t.n < ctg_ix->n_groups) return gams_fail(h, GAMS_EINVAL, who + ": chr_names must name every group of ctg_ix");
     if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": max beyond 2^24 windows a side");
-    const int rc = gams_sw_summary_check(h, who, sum, size, max, resize, actions, tag);
+    const int rc = gams_sw_summary_check(h, who, sum, size, max, resize, actions, tag, n_anno, sets, set_group, ctg_ix->m != 0);
     if (rc != GAMS_OK) return rc;
     return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
-                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, sum, tag},
+                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, sum, tag, n_anno, sets, set_group},
                           bytes, n_bytes, nullptr, nullptr, nullptr, n_features, n_rows);
+}
+
+int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                                const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                                const int32_t *chr_end, const char *bytes, uint64_t n_bytes, int32_t size, int32_t max,
+                                int32_t resize, uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
+                                gams_sw_summary_t *sum, uint32_t tag, uint64_t *n_features, uint64_t *n_rows) {
+    return gams_gpu_sw_feature_summary_anno(h, s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, bytes, n_bytes, size,
+                                            max, resize, actions, rg_ix, rg_group, sum, tag, 0u, nullptr, nullptr, n_features,
+                                            n_rows);
 }
 
 int gams_gpu_locate_seq_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,

@@ -13,25 +13,29 @@
 #endif
 
 // anno.rs:140 prints the f32 prop as `{:.4}`: the exact binary value rounded half to even at the fourth decimal
-// (what "%.4f" of the widened double prints).  For p in [0, 1] the text is always six bytes "d.dddd", written to
-// out[0..6).  p = m * 2^e with m < 2^24: below 2^-15 (< 5e-5) the answer is 0.0000; otherwise e >= -38, so
-// m * 10^4 < 2^38 and the quotient and remainder by 2^-e are exact in 64 bits.  Returns false (nothing written)
-// when p is not a finite value in [0, 1].
-GAMS_HD inline bool gams_fmt_prop4(float p, char *out) {
-    if (!(p >= 0.0f && p <= 1.0f)) return false;   // NaN fails both
+// (what "%.4f" of the widened double prints).  For p in [0, 1] that is q / 10^4 with the integer q below, 0 .. 10000.
+// p = m * 2^e with m < 2^24: below 2^-15 (< 5e-5) the answer is 0; otherwise e >= -38, so m * 10^4 < 2^38 and the
+// quotient and remainder by 2^-e are exact in 64 bits.  p must be a finite value in [0, 1] (the callers check).
+// Shared by the text (gams_fmt_prop4) and the sw summary's Prop sums, as sw_f4_units / sw_put_f4 are.
+GAMS_HD inline uint32_t gams_prop4_units(float p) {
     uint32_t b;
     memcpy(&b, &p, 4);
     const uint32_t ex = (b >> 23) & 0xffu;
-    uint32_t q = 0;
-    if (ex >= 112u) {                               // p >= 2^-15; ex <= 127 since p <= 1
-        const uint64_t m = (uint64_t)((b & 0x7fffffu) | 0x800000u);
-        const uint32_t s = 150u - ex;               // p = m / 2^s, 23 <= s <= 38
-        const uint64_t num = m * 10000u;
-        uint64_t qq = num >> s;
-        const uint64_t r = num & ((1ull << s) - 1u), half = 1ull << (s - 1u);
-        if (r > half || (r == half && (qq & 1u))) ++qq;
-        q = (uint32_t)qq;
-    }
+    if (ex < 112u) return 0u;                       // p < 2^-15; ex <= 127 since p <= 1
+    const uint64_t m = (uint64_t)((b & 0x7fffffu) | 0x800000u);
+    const uint32_t s = 150u - ex;                   // p = m / 2^s, 23 <= s <= 38
+    const uint64_t num = m * 10000u;
+    uint64_t qq = num >> s;
+    const uint64_t r = num & ((1ull << s) - 1u), half = 1ull << (s - 1u);
+    if (r > half || (r == half && (qq & 1u))) ++qq;
+    return (uint32_t)qq;
+}
+
+// ... as text: always six bytes "d.dddd", written to out[0..6).  Returns false (nothing written) when p is not a finite
+// value in [0, 1].
+GAMS_HD inline bool gams_fmt_prop4(float p, char *out) {
+    if (!(p >= 0.0f && p <= 1.0f)) return false;   // NaN fails both
+    const uint32_t q = gams_prop4_units(p);
     out[0] = (char)('0' + q / 10000u);
     out[1] = '.';
     out[2] = (char)('0' + q / 1000u % 10u);

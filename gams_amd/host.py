@@ -2,6 +2,7 @@
 reference's per-ctg operators (wave/sw proc_ctg, locate, anno) on top of the C ABI."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
@@ -206,6 +207,17 @@ def load():
                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_uint64)]
+    L.gams_host_sw_summary_anno.restype = C.c_void_p
+    L.gams_host_sw_summary_anno.argtypes = L.gams_host_sw_summary.argtypes[:-2] + [
+        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.gams_host_sw_summarise_rows_props.restype = C.c_int
+    L.gams_host_sw_summarise_rows_props.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p,
+                                                    C.c_uint32, C.c_void_p, C.c_void_p]
+    L.gams_host_sw_summary_text_props.restype = C.c_void_p
+    L.gams_host_sw_summary_text_props.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.gams_host_prop4_units.restype = C.c_int32
+    L.gams_host_prop4_units.argtypes = [C.c_float]
     L.gams_host_sw_summarise_rows.restype = C.c_int
     L.gams_host_sw_summarise_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p]
     L.gams_host_sw_summary_text.restype = C.c_void_p
@@ -960,8 +972,41 @@ def sw_text(eng, ctgs, data, size=100, mx=20, resize=500, actions=("gc",), rg_re
     return _take_bytes(p, out_len)
 
 
-def _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset):
-    """-> (text, the distinct tags in byte order or None, the table's words as [slots, mx + 1, SW_SUMMARY_WORDS])"""
+_CTG_ID_ANNO = re.compile(r"ctg:[A-Za-z0-9_]+:[0-9]+", re.IGNORECASE)
+
+
+def _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset, anno=None):
+    """-> (text, the distinct tags in byte order or None, the table's words as [slots, mx + 1, SW_SUMMARY_WORDS], the Prop
+    sums as [slots, mx + 1, n_anno] or None without anno)"""
+    cols = list(anno) if anno else []
+    if len(cols) > _lib.SW_SUMMARY_MAX_ANNO:
+        raise ValueError("sw_summary: at most %d span sets" % _lib.SW_SUMMARY_MAX_ANNO)
+    if cols:
+        for c in ctgs:                                         # utils.rs:118-129 must find the id whole in a row's id
+            if not _CTG_ID_ANNO.fullmatch(c["id"]):
+                raise ValueError("sw_summary: `gams anno` would not find the ctg id %r in its rows" % (c["id"],))
+    owned = []
+    try:
+        sets = []
+        for prefix, rl in cols:
+            aset, own = _anno_set(eng, rl)
+            if aset is None:
+                raise ValueError("sw_summary: anno takes (prefix, AnnoSet or the bytes of the runlist JSON)")
+            if own:
+                owned.append(aset)
+            sets.append(aset)
+        prefixes = [p.encode("latin-1") if isinstance(p, str) else bytes(p) for p, _ in cols]
+        if any(b"\0" in p for p in prefixes):
+            raise ValueError("sw_summary: a prefix holds a NUL")
+        return _sw_summary_call_sets(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset,
+                                     prefixes, sets, anno is not None)
+    finally:
+        for aset in owned:
+            aset.close()
+
+
+def _sw_summary_call_sets(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset, prefixes, sets,
+                          with_prop):
     rg_data = _one_rg_source(rg_records, rg_data)
     mask = sw_actions(actions)
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
@@ -979,29 +1024,37 @@ def _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_record
     nr, rp, rl, _keep_rg = _files(rg_data if isinstance(rg_data, list) else ([] if rg_data is None else [rg_data]))
     table = np.zeros((1 if tags is None else len(slots_of), mx + 1, _lib.SW_SUMMARY_WORDS), np.uint64)
     out_len = C.c_uint64()
-    tail = (nf, fp, fl, tagp, size, mx, resize, mask, rg_lines, nr, rp, rl, table.ctypes.data, C.byref(out_len))
+    na = len(sets)
+    prop = np.zeros((table.shape[0], mx + 1, na), np.uint64) if with_prop else None
+    prep = (C.c_char_p * max(na, 1))(*prefixes)
+    setp = (C.c_void_p * max(na, 1))(*[a.p for a in sets])
+    tail = (nf, fp, fl, tagp, size, mx, resize, mask, rg_lines, nr, rp, rl, na, prep, setp, table.ctypes.data,
+            prop.ctypes.data if na else None, C.byref(out_len))
     if seqset is None:
         seqs = None
         if mask & _lib.SW_GC:
             bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
                                          else c["seq"]) for c in ctgs]
             seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
-        p = load().gams_host_sw_summary(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, *tail)
+        p = load().gams_host_sw_summary_anno(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, None, None, *tail)
     else:
         slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
         slots = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
-        p = load().gams_host_sw_summary(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
-                                        slots.ctypes.data, *tail)
-    return _take_bytes(p, out_len), slots_of, table
+        p = load().gams_host_sw_summary_anno(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, None, seqset.p,
+                                             slots.ctypes.data, *tail)
+    return _take_bytes(p, out_len), slots_of, table, prop
 
 
-def _sw_summary_arrays(slots_of, table):
-    return {"tags": slots_of, "count": table[:, :, 0].copy(), "sum": table[:, :, 1:5].copy(), "nan": table[:, :, 5:9].copy(),
-            "rg_count": table[:, :, 9].copy()}
+def _sw_summary_arrays(slots_of, table, prop=None):
+    out = {"tags": slots_of, "count": table[:, :, 0].copy(), "sum": table[:, :, 1:5].copy(), "nan": table[:, :, 5:9].copy(),
+           "rg_count": table[:, :, 9].copy()}
+    if prop is not None:
+        out["prop"] = prop
+    return out
 
 
 def sw_summary(eng, ctgs, data, tags=None, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None,
-               seqset=None):
+               seqset=None, anno=None):
     """The table the rows of sw_text are loaded for (fsw-distance.tera.sql; with tags fsw-distance-tag.tera.sql), reduced
     on the device -- no row leaves it (the host's passes for a file the device refuses; last_operator_device says
     whether every file took the device's route).  data: one feature file's bytes or a list of them, each read as sw_text
@@ -1009,23 +1062,30 @@ def sw_summary(eng, ctgs, data, tags=None, size=100, mx=20, resize=500, actions=
     line per distance with rows -- per (tag, distance), ordered by tag bytes, then distance --: the averages of
     gc_content, gc_mean, gc_stddev and gc_cv (with the gc action), of rg_count (with count) and COUNT, the rows.  An
     average is the exact sum of the printed values over COUNT, rounded to 4 places, ties to even, trailing zeros dropped;
-    `nan` where a row's value is NaN.  seqset, the per-ctg slot, actions, rg_records and rg_data as for sw_text."""
-    return _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset)[0]
+    `nan` where a row's value is NaN.  seqset, the per-ctg slot, actions, rg_records and rg_data as for sw_text.
+    anno: None, or a list of up to four (prefix, AnnoSet | the bytes of a runlist JSON file; bytes build a set for the
+    call): one column AVG_{prefix}Prop per set behind AVG_gc_cv -- what `gams anno set.json stdin -H` adds to every row
+    before the table is made (fsw-distance-tag.tera.sql's cdsProp, repeatsProp), joined with the rows on the device.  The
+    columns do not depend on the actions.  ValueError for a ctg id `gams anno` would not find whole in a row's id."""
+    return _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset, anno)[0]
 
 
 def sw_summary_table(eng, ctgs, data, tags=None, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None,
-                     seqset=None):
+                     seqset=None, anno=None):
     """sw_summary's raw integers: {"tags": the distinct tags in byte order (None without tags), "count": [slots, mx + 1],
     "sum": [slots, mx + 1, 4] (the sums of m, a statistic being m / 10^4, for gc_content, gc_mean, gc_stddev, gc_cv),
     "nan": [slots, mx + 1, 4] (the rows whose statistic is NaN, left out of the sums), "rg_count": [slots, mx + 1]},
-    uint64, one slot without tags"""
-    _, slots_of, table = _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset)
-    return _sw_summary_arrays(slots_of, table)
+    uint64, one slot without tags; with anno (as for sw_summary) also "prop": [slots, mx + 1, n_anno], the sums of q, a
+    row's prop being printed as q / 10^4"""
+    _, slots_of, table, prop = _sw_summary_call(eng, ctgs, data, tags, size, mx, resize, actions, rg_records, rg_data, seqset,
+                                                anno)
+    return _sw_summary_arrays(slots_of, table, prop)
 
 
-def sw_summarise_rows(rows, counts=None, mx=20, actions=("gc",), table=False):
+def sw_summarise_rows(rows, counts=None, mx=20, actions=("gc",), table=False, props=None, prefixes=None):
     """The host's summariser over rows of _lib.SW_ROW_DTYPE (and their rg counts, int32, with the count action): the text
-    of sw_summary without tags, or with table=True the integers as sw_summary_table gives them.  No engine."""
+    of sw_summary without tags, or with table=True the integers as sw_summary_table gives them.  props: None, or one
+    column of Prop units per set (uint32, one entry per row, at most 10000), printed under prefixes.  No engine."""
     L = load()
     mask = sw_actions(actions)
     rows = np.ascontiguousarray(rows, _lib.SW_ROW_DTYPE)
@@ -1033,12 +1093,39 @@ def sw_summarise_rows(rows, counts=None, mx=20, actions=("gc",), table=False):
     if cnt is not None and cnt.size != rows.size:
         raise ValueError("sw_summarise_rows: one count per row")
     words = np.zeros((1, mx + 1, _lib.SW_SUMMARY_WORDS), np.uint64)
-    _check_rc(L.gams_host_sw_summarise_rows(rows.ctypes.data, None if cnt is None else cnt.ctypes.data, rows.size, mx, mask,
-                                            words.ctypes.data))
+    if props is None:
+        if prefixes:
+            raise ValueError("sw_summarise_rows: prefixes without props")
+        _check_rc(L.gams_host_sw_summarise_rows(rows.ctypes.data, None if cnt is None else cnt.ctypes.data, rows.size, mx,
+                                                mask, words.ctypes.data))
+        if table:
+            return _sw_summary_arrays(None, words)
+        out_len = C.c_uint64()
+        return _take_bytes(L.gams_host_sw_summary_text(words.ctypes.data, 1, None, mx, mask, C.byref(out_len)), out_len)
+    cols = [np.ascontiguousarray(p, np.uint32) for p in props]
+    if any(c.size != rows.size for c in cols) or len(prefixes or ()) != len(cols):
+        raise ValueError("sw_summarise_rows: one unit per row in every column of props, one prefix per column")
+    pre = [p.encode("latin-1") if isinstance(p, str) else bytes(p) for p in prefixes]
+    colp = (C.c_void_p * max(len(cols), 1))(*[c.ctypes.data if c.size else None for c in cols])
+    prep = (C.c_char_p * max(len(cols), 1))(*pre)
+    prop = np.zeros((1, mx + 1, len(cols)), np.uint64)
+    if not rows.size:                                          # (an empty column has no address to give)
+        colp = (C.c_void_p * max(len(cols), 1))(*[prop.ctypes.data] * len(cols))
+    _check_rc(L.gams_host_sw_summarise_rows_props(rows.ctypes.data, None if cnt is None else cnt.ctypes.data, rows.size, mx,
+                                                  mask, words.ctypes.data, len(cols), colp, prop.ctypes.data))
     if table:
-        return _sw_summary_arrays(None, words)
+        return _sw_summary_arrays(None, words, prop)
     out_len = C.c_uint64()
-    return _take_bytes(L.gams_host_sw_summary_text(words.ctypes.data, 1, None, mx, mask, C.byref(out_len)), out_len)
+    return _take_bytes(L.gams_host_sw_summary_text_props(words.ctypes.data, 1, None, mx, mask, len(cols), prep, prop.ctypes.data,
+                                                         C.byref(out_len)), out_len)
+
+
+def prop4_units(p):
+    """The integer q of an anno prop in [0, 1]: `{:.4}` prints q / 10^4 (the expression the device shares between
+    anno_text and the sw summary's Prop sums).  HostError (EINVAL) outside [0, 1]."""
+    q = load().gams_host_prop4_units(p)
+    _check_rc(0 if q >= 0 else -1)
+    return int(q)
 
 
 def fmt_f32_short(v):

@@ -2028,6 +2028,7 @@ struct SwSetup {
     gams_index_t *ctg_ix() const { return loc.ctg_ix_; }
     const gams_names_t *chr_names() const { return loc.chr_names_; }
     const gams_names_t *ctg_ids() const { return loc.ctg_ids_; }
+    const std::string &chr_of(size_t c) const { return loc.ctgs_[c].chr_id; }   // the chromosome of interval c
     // the host's passes over one feature file: read_range over the lines and the ids of feature_records, as the arrays
     // the batch entries take -- the ctgs with kept features in id order (BTreeMap order)
     struct Arrays {
@@ -2180,88 +2181,27 @@ std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vect
 }
 
 // ---- the per-distance summary of the sw rows ---------------------------------------------------------
-void sw_summarise_rows(const gams_sw_row_t *rows, const int32_t *counts, uint64_t n, int32_t max, uint32_t actions,
-                       uint64_t *table) {
-    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
-    if (do_count && n && !counts) throw Error(GAMS_EINVAL, "sw_summarise_rows: GAMS_SW_COUNT without the counts");
-    for (uint64_t r = 0; r < n; ++r) {
-        const gams_sw_row_t &w = rows[r];
-        if (w.distance < 0 || w.distance > max) throw Error(GAMS_EINVAL, "sw_summarise_rows: a distance outside [0, max]");
-        uint64_t *g = table + (size_t)w.distance * GAMS_SW_SUMMARY_WORDS;
-        g[0] += 1;
-        if (do_gc) {
-            const float v[4] = {w.gc_content, w.gc_mean, w.gc_stddev, w.gc_cv};
-            for (int k = 0; k < 4; ++k) {
-                if (v[k] != v[k])
-                    g[5 + k] += 1;
-                else if (!(v[k] >= 0.0f) || std::isinf(v[k]))
-                    throw Error(GAMS_EUNSUPPORTED, "sw_summarise_rows: a negative or infinite statistic has no place in the table");
-                else   // the integer nearest to v * 10^4 -- below 1000 the m the text prints (sw_put_f4), beyond it its continuation
-                    g[1 + k] += (uint64_t)((double)v[k] * 10000.0 + 0.5);
-            }
-        }
-        if (do_count) g[9] += (uint64_t)(int64_t)counts[r];
-    }
-}
-
-std::string sw_summary_header(uint32_t actions, bool tagged) {
-    std::string o = tagged ? "tag\tdistance" : "distance";
-    if (actions & GAMS_SW_GC) o += "\tAVG_gc_content\tAVG_gc_mean\tAVG_gc_stddev\tAVG_gc_cv";
-    if (actions & GAMS_SW_COUNT) o += "\tAVG_rg_count";
-    return o + "\tCOUNT\n";
-}
-
+// (the summariser itself -- sw_summarise_rows, the header and SwSummaryTable::text -- is gams_sw_summary.cpp: no device call)
 namespace {
-// num / den to the nearest integer, ties to even, printed as q / 10^4 with the trailing zeros dropped (as sw_put_f4 prints)
-std::string sw_avg4(unsigned __int128 num, uint64_t den) {
-    unsigned __int128 q = num / den;
-    const unsigned __int128 r2 = (num % den) * 2;
-    if (r2 > den || (r2 == den && (q & 1))) ++q;
-    std::string ip, o;
-    unsigned __int128 i = q / 10000;
-    do {
-        ip.insert(ip.begin(), (char)('0' + (int)(i % 10)));
-        i /= 10;
-    } while (i);
-    uint32_t fr = (uint32_t)(q % 10000), nd = 4;
-    while (nd && fr % 10 == 0) {
-        fr /= 10;
-        --nd;
-    }
-    o = ip;
-    if (nd) {
-        char buf[8];
-        std::snprintf(buf, sizeof buf, ".%0*u", (int)nd, fr);
-        o += buf;
-    }
-    return o;
-}
+bool extract_ctg_id(const std::string &s, std::string &id);            // (with anno's helpers, below)
 }  // namespace
-
-std::string SwSummaryTable::text() const {
-    const bool tagged = !tags.empty();
-    std::string o = sw_summary_header(actions, tagged);
-    const size_t n_tags = tagged ? tags.size() : 1;
-    for (size_t t = 0; t < n_tags; ++t)
-        for (int32_t d = 0; d <= max; ++d) {
-            const uint64_t *g = words.data() + (t * ((size_t)max + 1) + (size_t)d) * GAMS_SW_SUMMARY_WORDS;
-            if (g[0] == 0) continue;
-            if (tagged) o += tags[t] + "\t";
-            o += std::to_string(d);
-            if (actions & GAMS_SW_GC)
-                for (int k = 0; k < 4; ++k) o += "\t" + (g[5 + k] ? std::string("nan") : sw_avg4(g[1 + k], g[0]));
-            if (actions & GAMS_SW_COUNT) o += "\t" + sw_avg4((unsigned __int128)g[9] * 10000u, g[0]);
-            o += "\t" + std::to_string(g[0]) + "\n";
-        }
-    return o;
-}
 
 SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
                           const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
                           const std::map<std::string, std::vector<Range>> *rgs, const std::vector<FileBytes> *rg_files,
-                          bool *device) {
+                          bool *device, const std::vector<SwAnnoCol> *anno) {
     if (device) *device = false;
     if (rgs && rg_files) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
+    const uint32_t n_anno = anno ? (uint32_t)anno->size() : 0u;
+    if (anno && anno->size() > GAMS_SW_SUMMARY_MAX_ANNO) throw Error(GAMS_EINVAL, "sw_summary: more than GAMS_SW_SUMMARY_MAX_ANNO span sets");
+    for (uint32_t a = 0; a < n_anno; ++a)
+        if (!(*anno)[a].set) throw Error(GAMS_EINVAL, "sw_summary: a null span set");
+    if (n_anno)   // utils.rs:118-129 on "sw:feature:{ctg_id}:{k}:{sn}" must give the ctg id back whole
+        for (const Ctg &c : ctgs) {
+            std::string got;
+            if (!extract_ctg_id(c.id, got) || got != c.id)
+                throw Error(GAMS_EINVAL, "sw_summary: `gams anno` would not find the ctg id " + c.id + " in its rows (ctg:[A-Za-z0-9_]+:\\d+)");
+        }
     const bool do_gc = (a.actions & GAMS_SW_GC) != 0, do_count = (a.actions & GAMS_SW_COUNT) != 0;
     if (do_gc && !seqset) throw Error(GAMS_EINVAL, "sw_summary: --action gc needs a seqset");
     if (seqset && slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "sw_summary: one seqset slot per ctg");
@@ -2279,22 +2219,40 @@ SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqs
     const uint32_t n_tags = (uint32_t)std::max<size_t>(T.tags.size(), 1);
     const size_t group_words = ((size_t)a.max + 1) * GAMS_SW_SUMMARY_WORDS;
     T.words.assign(group_words * n_tags, 0);                             // what the host's passes add; the device's joins below
+    const size_t group_props = ((size_t)a.max + 1) * n_anno;
+    T.prop.assign(group_props * n_tags, 0);
     SwSetup U(h, ctgs, seqset, slots, do_count, rgs, nullptr, 0, rg_files);
+    // per set: the group of every interval's chromosome in it (UINT32_MAX: the set does not hold the chromosome)
+    std::vector<std::vector<uint32_t>> set_group(n_anno, std::vector<uint32_t>(std::max<size_t>(U.n_ctg, 1), UINT32_MAX));
+    std::vector<gams_spans_t *> sets(n_anno);
+    std::vector<const uint32_t *> set_group_p(n_anno);
+    for (uint32_t s = 0; s < n_anno; ++s) {
+        const AnnoSet &as = *(*anno)[s].set;
+        T.prefixes.push_back((*anno)[s].prefix);
+        std::map<std::string, uint32_t> group_of;
+        for (uint32_t g = 0; g < as.chrs().size(); ++g) group_of.emplace(as.chrs()[g], g);
+        for (size_t c = 0; c < U.n_ctg; ++c) {
+            const auto it = group_of.find(U.chr_of(c));
+            if (it != group_of.end()) set_group[s][c] = it->second;
+        }
+        sets[s] = as.spans();
+        set_group_p[s] = set_group[s].data();
+    }
     struct Acc {
         gams_gpu_t *h;
         gams_sw_summary_t *p = nullptr;
         ~Acc() { gams_sw_summary_destroy(h, p); }
     } acc{h};
-    check(h, gams_sw_summary_create(h, a.max, n_tags, a.actions, a.size, a.resize, &acc.p));
+    check(h, gams_sw_summary_create_anno(h, a.max, n_tags, a.actions, a.size, a.resize, n_anno, &acc.p));
     bool all_device = true;
     for (size_t f = 0; f < files.size(); ++f) {
         const uint32_t tag = tags ? (uint32_t)(std::lower_bound(T.tags.begin(), T.tags.end(), (*tags)[f]) - T.tags.begin()) : 0u;
         const char *bytes = files[f].first ? files[f].first : "";
         uint64_t feats = 0, rows = 0;
-        const int rc = gams_gpu_sw_feature_summary(h, do_gc ? seqset : nullptr, U.ctg_ix(), U.chr_names(), U.ctg_ids(),
-                                                   U.slot.data(), U.cs.data(), U.ce.data(), bytes, files[f].second, a.size, a.max,
-                                                   a.resize, a.actions, U.loc.rg_index(), U.rg_group.data(), acc.p, tag, &feats,
-                                                   &rows);
+        const int rc = gams_gpu_sw_feature_summary_anno(h, do_gc ? seqset : nullptr, U.ctg_ix(), U.chr_names(), U.ctg_ids(),
+                                                        U.slot.data(), U.cs.data(), U.ce.data(), bytes, files[f].second, a.size,
+                                                        a.max, a.resize, a.actions, U.loc.rg_index(), U.rg_group.data(), acc.p, tag,
+                                                        n_anno, sets.data(), set_group_p.data(), &feats, &rows);
         if (rc != GAMS_EUNSUPPORTED) {
             check(h, rc);
             continue;
@@ -2305,25 +2263,56 @@ SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqs
         const SwSetup::Arrays A = U.arrays(bytes, files[f].second, do_gc, "sw_summary");
         const uint32_t n_sel = (uint32_t)A.sel.size();
         if (n_sel == 0) continue;
+        std::vector<std::vector<uint32_t>> sel_group(n_anno, std::vector<uint32_t>(n_sel));   // set_group of the selected ctgs
+        std::vector<const uint32_t *> sel_group_p(n_anno);
+        for (uint32_t s = 0; s < n_anno; ++s) {
+            for (uint32_t k = 0; k < n_sel; ++k) sel_group[s][k] = set_group[s][A.sel[k]];
+            sel_group_p[s] = sel_group[s].data();
+        }
         if (!do_gc) {
             SeqSetGuard sg{h};
             check(h, gams_seqset_create(h, n_sel, A.lens.data(), &sg.s));
-            check(h, gams_gpu_sw_summary_batch(h, sg.s, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
-                                               A.fe.data(), a.size, a.max, a.resize, a.actions, U.loc.rg_index(), A.group.data(),
-                                               acc.p, tag, &rows));
+            check(h, gams_gpu_sw_summary_batch_anno(h, sg.s, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(),
+                                                    A.fs.data(), A.fe.data(), a.size, a.max, a.resize, a.actions, U.loc.rg_index(),
+                                                    A.group.data(), acc.p, tag, n_anno, sets.data(), sel_group_p.data(), &rows));
             continue;
         }
         check(h, gams_gpu_sw_batch(h, seqset, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
                                    A.fe.data(), a.size, a.max, a.resize, nullptr, 0, nullptr, &rows));
         std::vector<gams_sw_row_t> rv(std::max<uint64_t>(rows, 1));
         std::vector<int32_t> cnt(do_count ? std::max<uint64_t>(rows, 1) : 0);
+        std::vector<uint64_t> row_off((size_t)n_sel + 1, 0);
         check(h, gams_gpu_sw_batch(h, seqset, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
-                                   A.fe.data(), a.size, a.max, a.resize, rv.data(), rows, nullptr, &rows));
+                                   A.fe.data(), a.size, a.max, a.resize, rv.data(), rows, row_off.data(), &rows));
+        // the Prop units of the rows: gams_gpu_cover over their windows, once per set (the clip is the row's ctg)
+        std::vector<std::vector<uint32_t>> units(n_anno, std::vector<uint32_t>(std::max<uint64_t>(rows, 1), 0u));
+        std::vector<const uint32_t *> units_p(n_anno);
+        if (n_anno) {
+            const size_t nr = (size_t)std::max<uint64_t>(rows, 1);
+            std::vector<uint32_t> grp(nr);
+            std::vector<int32_t> cl(nr), ch(nr), qs(nr), qe(nr);
+            std::vector<float> prop(nr);
+            for (uint32_t k = 0; k < n_sel; ++k)
+                for (uint64_t r = row_off[k]; r < row_off[k + 1]; ++r) {
+                    cl[r] = U.cs[A.sel[k]];
+                    ch[r] = U.ce[A.sel[k]];
+                    qs[r] = rv[r].start;
+                    qe[r] = rv[r].end;
+                }
+            for (uint32_t s = 0; s < n_anno; ++s) {
+                for (uint32_t k = 0; k < n_sel; ++k)
+                    std::fill(grp.begin() + row_off[k], grp.begin() + row_off[k + 1], sel_group[s][k]);
+                check(h, gams_gpu_cover(h, sets[s], grp.data(), cl.data(), ch.data(), qs.data(), qe.data(), rows, prop.data()));
+                for (uint64_t r = 0; r < rows; ++r) units[s][r] = prop4_units(prop[r]);
+                units_p[s] = units[s].data();
+            }
+        }
         if (do_count)
             check(h, gams_gpu_sw_count_batch(h, seqset, n_sel, A.index.data(), A.sel_start.data(), A.feat_off.data(), A.fs.data(),
                                              A.fe.data(), a.size, a.max, U.loc.rg_index(), A.group.data(), cnt.data(), rows,
                                              nullptr, &rows));
-        sw_summarise_rows(rv.data(), do_count ? cnt.data() : nullptr, rows, a.max, a.actions, T.words.data() + tag * group_words);
+        sw_summarise_rows(rv.data(), do_count ? cnt.data() : nullptr, rows, a.max, a.actions, T.words.data() + tag * group_words,
+                          n_anno, units_p.data(), T.prop.data() + tag * group_props);
     }
     // one small read-back: the device's integers join the host's
     const size_t n = ((size_t)a.max + 1) * n_tags;
@@ -2338,6 +2327,11 @@ SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqs
             w[5 + k] += nan[4 * g + k];
         }
     }
+    if (n_anno) {
+        std::vector<uint64_t> p(T.prop.size());
+        check(h, gams_sw_summary_read_anno(h, acc.p, p.data()));
+        for (size_t i = 0; i < p.size(); ++i) T.prop[i] += p[i];
+    }
     if (device) *device = all_device;
     return T;
 }
@@ -2345,10 +2339,10 @@ SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqs
 SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                           const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
                           const std::map<std::string, std::vector<Range>> *rgs, const std::vector<FileBytes> *rg_files,
-                          bool *device) {
+                          bool *device, const std::vector<SwAnnoCol> *anno) {
     if (!(a.actions & GAMS_SW_GC))                                       // nothing reads a base: nothing goes up
         return sw_summary(h, ctgs, static_cast<gams_seqset_t *>(nullptr), std::vector<uint32_t>(), files, tags, a, rgs, rg_files,
-                          device);
+                          device, anno);
     if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, "sw_summary: ctgs / seqs size mismatch");
     std::vector<uint32_t> lens(std::max<size_t>(ctgs.size(), 1), 0), slots(ctgs.size());
     for (size_t i = 0; i < ctgs.size(); ++i) {
@@ -2358,7 +2352,7 @@ SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std
     SeqSetGuard sg{h};
     check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
     check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
-    return sw_summary(h, ctgs, sg.s, slots, files, tags, a, rgs, rg_files, device);
+    return sw_summary(h, ctgs, sg.s, slots, files, tags, a, rgs, rg_files, device, anno);
 }
 
 namespace {

@@ -337,30 +337,53 @@ struct SwSummaryTable {
     uint32_t actions = 0;
     std::vector<std::string> tags;        // the distinct tags in byte order, one slot each; empty: no tags, one slot
     std::vector<uint64_t> words;
+    // the Prop columns (AVG_{prefix}Prop, one per span set, in the order given): prop[(t * (max + 1) + d) * n + a] = P_a,
+    // the sum over the group's rows of the q that `gams anno` prints as q / 10^4 for set a; both empty without sets
+    std::vector<std::string> prefixes;
+    std::vector<uint64_t> prop;
     // the header and one line per group with COUNT > 0, ordered by tag bytes, then distance; an average is S / COUNT to
-    // the nearest integer, ties to even, printed as q / 10^4 without trailing zeros; `nan` where a row's statistic was NaN
+    // the nearest integer, ties to even, printed as q / 10^4 without trailing zeros; `nan` where a row's statistic was NaN.
+    // The Prop columns stand behind AVG_gc_cv (the SQL's order), in front of AVG_rg_count and COUNT.
     std::string text() const;
 };
-std::string sw_summary_header(uint32_t actions, bool tagged);
+std::string sw_summary_header(uint32_t actions, bool tagged, const std::vector<std::string> &prefixes = {});
+// the q of a prop in [0, 1]: `{:.4}` prints q / 10^4 (csrc/text_fmt.hpp); GAMS_EINVAL outside
+uint32_t prop4_units(float p);
 // n rows (and, under GAMS_SW_COUNT, their counts) added into `table`, (max + 1) groups: the host's summariser, which runs
 // where the device refuses.  A statistic of 1000 or more adds the integer nearest to v * 10^4; GAMS_EINVAL for a distance
 // outside [0, max], GAMS_EUNSUPPORTED for a negative or infinite statistic.
+// With n_props columns of Prop units (props[a][r] = q of row r against set a, at most 10000) they are added into
+// prop_table, (max + 1) x n_props words, group-major.
 void sw_summarise_rows(const gams_sw_row_t *rows, const int32_t *counts, uint64_t n, int32_t max, uint32_t actions,
-                       uint64_t *table);
+                       uint64_t *table, uint32_t n_props = 0, const uint32_t *const *props = nullptr,
+                       uint64_t *prop_table = nullptr);
 // `gams feature` + `gams sw` + the summary over the bytes of one or several range files, files[f] under (*tags)[f] (tags
 // NULL: no tag column): per file gams_gpu_sw_feature_summary into one accumulator on the device -- no row leaves it -- and
 // one read-back of the integers.  Drop-first is per file.  seqs, seqset, slots, rgs, rg_files as for sw_text.  Where the
 // device refuses a file (GAMS_EUNSUPPORTED) its lines go through read_range and, with GAMS_SW_GC, the rows of
 // gams_gpu_sw_batch through sw_summarise_rows (without it through gams_gpu_sw_summary_batch); *device (may be NULL):
 // every file took the device's route.
+// anno (may be NULL): the span sets of the Prop columns, each under the prefix of its column (upstream: the file stem of the
+// runlist JSON up to its first '.'), at most GAMS_SW_SUMMARY_MAX_ANNO; a set is built once (AnnoSet, either route) and shared
+// by the calls.  The join is made on the device with the rows (gams_gpu_sw_feature_summary_anno); where the device refuses
+// a file, the rows of gams_gpu_sw_batch go through gams_gpu_cover once per set and prop4_units here.  With sets, a ctg id
+// that `gams anno` would not find whole in a row's id (utils.rs:118-129: ctg:[A-Za-z0-9_]+:\d+) is GAMS_EINVAL: upstream
+// drops such rows from the table, which is not emulated.
+class AnnoSet;
+struct SwAnnoCol {
+    std::string prefix;
+    const AnnoSet *set;
+};
 SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
                           const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
                           const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                          const std::vector<FileBytes> *rg_files = nullptr, bool *device = nullptr);
+                          const std::vector<FileBytes> *rg_files = nullptr, bool *device = nullptr,
+                          const std::vector<SwAnnoCol> *anno = nullptr);
 SwSummaryTable sw_summary(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
                           const std::vector<FileBytes> &files, const std::vector<std::string> *tags, const SwArgs &a,
                           const std::map<std::string, std::vector<Range>> *rgs = nullptr,
-                          const std::vector<FileBytes> *rg_files = nullptr, bool *device = nullptr);
+                          const std::vector<FileBytes> *rg_files = nullptr, bool *device = nullptr,
+                          const std::vector<SwAnnoCol> *anno = nullptr);
 
 // src/cmd_gams/rg.rs:41-77 / feature.rs:47-95: the records the loaders SET, as (key, JSON) pairs in
 // the reference's order (ctg id order, then file order), serials from 1 per ctg (a fresh cnt:).

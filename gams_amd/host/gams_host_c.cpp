@@ -888,12 +888,18 @@ char *gams_host_sw_text_rgs(gams_gpu_t *h, uint32_t n, const char *const *ids, c
 // and rg_lines as for gams_host_sw_text; tags: NULL, or one NUL-terminated tag per file; the rg files (n_rg, rg_data,
 // rg_n; n_rg 0: none) as for gams_host_sw_text_rgs.  table (may be NULL) receives the raw integers, n_slots * (max + 1)
 // groups of GAMS_SW_SUMMARY_WORDS words, n_slots = the distinct tags (1 without tags), in byte order.
-char *gams_host_sw_summary(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
-                           const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
-                           uint32_t n_files, const char *const *data, const uint64_t *n_bytes, const char *const *tags,
-                           int32_t size, int32_t max, int32_t resize, uint32_t actions, const char *rg_lines, uint32_t n_rg,
-                           const char *const *rg_data, const uint64_t *rg_n, uint64_t *table, uint64_t *out_len) {
+// ... with the Prop columns: n_anno span sets (gams_host_anno_set_create), each under the NUL-terminated prefix of its
+// column; prop_table (may be NULL) receives n_slots * (max + 1) * n_anno words, group-major.  n_anno 0: the entry below.
+char *gams_host_sw_summary_anno(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                                const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                                uint32_t n_files, const char *const *data, const uint64_t *n_bytes, const char *const *tags,
+                                int32_t size, int32_t max, int32_t resize, uint32_t actions, const char *rg_lines, uint32_t n_rg,
+                                const char *const *rg_data, const uint64_t *rg_n, uint32_t n_anno, const char *const *prefixes,
+                                const void *const *sets, uint64_t *table, uint64_t *prop_table, uint64_t *out_len) {
     return guarded(out_len, [&] {
+        std::vector<gams::SwAnnoCol> anno;
+        for (uint32_t k = 0; k < n_anno; ++k)
+            anno.push_back(gams::SwAnnoCol{prefixes[k] ? prefixes[k] : "", static_cast<const gams::AnnoSet *>(sets[k])});
         const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
         std::map<std::string, std::vector<gams::Range>> rg_of;
         if (rg_lines) rg_of = rg_index_of(n, ids, rg_lines);
@@ -905,15 +911,25 @@ char *gams_host_sw_summary(gams_gpu_t *h, uint32_t n, const char *const *ids, co
         const auto t0 = std::chrono::steady_clock::now();
         const gams::SwSummaryTable T =
             (seqset || !seqs) ? gams::sw_summary(h, cv, seqset, seqset ? std::vector<uint32_t>(slots, slots + n) : std::vector<uint32_t>(),
-                                                 files, tags ? &tv : nullptr, a, rg_lines ? &rg_of : nullptr, n_rg ? &rg_files : nullptr, &dev)
+                                                 files, tags ? &tv : nullptr, a, rg_lines ? &rg_of : nullptr, n_rg ? &rg_files : nullptr, &dev,
+                                                 n_anno ? &anno : nullptr)
                               : gams::sw_summary(h, cv, std::vector<const uint8_t *>(seqs, seqs + n), files, tags ? &tv : nullptr, a,
-                                                 rg_lines ? &rg_of : nullptr, n_rg ? &rg_files : nullptr, &dev);
+                                                 rg_lines ? &rg_of : nullptr, n_rg ? &rg_files : nullptr, &dev, n_anno ? &anno : nullptr);
         std::string out = T.text();
         g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         g_operator_device = dev ? 1 : 0;
         if (table) std::memcpy(table, T.words.data(), T.words.size() * 8);
+        if (prop_table && !T.prop.empty()) std::memcpy(prop_table, T.prop.data(), T.prop.size() * 8);
         return out;
     });
+}
+char *gams_host_sw_summary(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                           const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                           uint32_t n_files, const char *const *data, const uint64_t *n_bytes, const char *const *tags,
+                           int32_t size, int32_t max, int32_t resize, uint32_t actions, const char *rg_lines, uint32_t n_rg,
+                           const char *const *rg_data, const uint64_t *rg_n, uint64_t *table, uint64_t *out_len) {
+    return gams_host_sw_summary_anno(h, n, ids, chrs, starts, ends, seqs, seqset, slots, n_files, data, n_bytes, tags, size, max,
+                                     resize, actions, rg_lines, n_rg, rg_data, rg_n, 0, nullptr, nullptr, table, nullptr, out_len);
 }
 // The host's summariser on its own (gams::sw_summarise_rows): n rows of gams_gpu_sw_batch and, under GAMS_SW_COUNT, their
 // counts, added into table ((max + 1) groups of GAMS_SW_SUMMARY_WORDS words, which the caller zeroes).  0, or -1 with the
@@ -925,17 +941,38 @@ int gams_host_sw_summarise_rows(const gams_sw_row_t *rows, const int32_t *counts
         return 0;
     });
 }
-// The text of a table of n_slots * (max + 1) groups; tags: NULL (n_slots = 1, no tag column) or the n_slots tags in byte order.
-char *gams_host_sw_summary_text(const uint64_t *table, uint32_t n_slots, const char *const *tags, int32_t max, uint32_t actions,
-                                uint64_t *out_len) {
+// ... with n_props columns of Prop units (props[a][r]) into prop_table, (max + 1) * n_props words the caller zeroes
+int gams_host_sw_summarise_rows_props(const gams_sw_row_t *rows, const int32_t *counts, uint64_t n, int32_t max, uint32_t actions,
+                                      uint64_t *table, uint32_t n_props, const uint32_t *const *props, uint64_t *prop_table) {
+    return guard(-1, [&] {
+        gams::sw_summarise_rows(rows, counts, n, max, actions, table, n_props, props, prop_table);
+        return 0;
+    });
+}
+// The text of a table of n_slots * (max + 1) groups; tags: NULL (n_slots = 1, no tag column) or the n_slots tags in byte order;
+// n_props Prop columns under `prefixes` with their sums in prop_table (n_props 0: none).
+char *gams_host_sw_summary_text_props(const uint64_t *table, uint32_t n_slots, const char *const *tags, int32_t max,
+                                      uint32_t actions, uint32_t n_props, const char *const *prefixes, const uint64_t *prop_table,
+                                      uint64_t *out_len) {
     return guarded(out_len, [&] {
         gams::SwSummaryTable T;
         T.max = max;
         T.actions = actions;
         if (tags) T.tags.assign(tags, tags + n_slots);
-        T.words.assign(table, table + (size_t)(tags ? n_slots : 1) * ((size_t)max + 1) * GAMS_SW_SUMMARY_WORDS);
+        const size_t groups = (size_t)(tags ? n_slots : 1) * ((size_t)max + 1);
+        T.words.assign(table, table + groups * GAMS_SW_SUMMARY_WORDS);
+        for (uint32_t k = 0; k < n_props; ++k) T.prefixes.push_back(prefixes[k] ? prefixes[k] : "");
+        if (n_props) T.prop.assign(prop_table, prop_table + groups * n_props);
         return T.text();
     });
+}
+char *gams_host_sw_summary_text(const uint64_t *table, uint32_t n_slots, const char *const *tags, int32_t max, uint32_t actions,
+                                uint64_t *out_len) {
+    return gams_host_sw_summary_text_props(table, n_slots, tags, max, actions, 0, nullptr, nullptr, out_len);
+}
+// the q of a prop in [0, 1] (`{:.4}` prints q / 10^4), as the device computes it; -1 outside
+int32_t gams_host_prop4_units(float p) {
+    return guard((int32_t)-1, [&] { return (int32_t)gams::prop4_units(p); });
 }
 
 // `gams rg f1 f2 ...` (kind 0) / `gams feature --tag T f1 f2 ...` (kind 1) over the bytes of the files (gams::loader_text):

@@ -338,6 +338,33 @@ int gams_gpu_sw_summary_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, c
                               gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
                               uint64_t *n_rows);
 
+/* ---- the Prop columns of fsw-distance-tag.tera.sql: AVG_{prefix}Prop per span set ----
+ * The reference's rows pass `gams anno <runlist.json> stdin -H` once per set before they are loaded; to anno a row is its
+ * window {chr}:{start}-{end} in its ctg, and prop = |set[chr] n window| as f32 / |window| as f32 (anno.rs:122-140; 0 when
+ * the chromosome is absent from the set), printed {:.4} = q / 10^4.  An accumulator made for n_anno sets keeps, beside
+ * the ten words of every group, P_a = the exact sum of q over the group's rows for set a; the layout above,
+ * GAMS_SW_SUMMARY_WORDS and gams_sw_summary_read are unchanged, gams_sw_summary_reset zeroes the Prop sums too.
+ * The sets are resident gams_spans_t (gams_spans_create, gams_spans_create_runlist_text), shared by any number of calls.
+ * The Prop sums do not depend on the action mask: coverage reads no sequence byte. */
+#define GAMS_SW_SUMMARY_MAX_ANNO 4u
+/* gams_sw_summary_create for n_anno sets (0: that entry itself); GAMS_EINVAL also for n_anno > GAMS_SW_SUMMARY_MAX_ANNO */
+int gams_sw_summary_create_anno(gams_gpu_t *h, int32_t max, uint32_t n_tags, uint32_t actions, int32_t size, int32_t resize,
+                                uint32_t n_anno, gams_sw_summary_t **out);
+/* The Prop sums: prop[(g * n_anno) + a] for group g of the n = n_tags * (max + 1) groups in (tag, distance) order and set
+ * a (group-major).  Nothing is written for an accumulator without sets. */
+int gams_sw_summary_read_anno(gams_gpu_t *h, gams_sw_summary_t *sum, uint64_t *prop);
+/* gams_gpu_sw_summary_batch with the sets: sets[a] and set_group[a], a host column indexed as ctg_index is --
+ * set_group[a][k] = the group of selected ctg k's chromosome in sets[a], UINT32_MAX (or anything >= the set's groups) for
+ * an absent chromosome, which adds 0.  GAMS_EINVAL for n_anno other than the accumulator's (so the entries without sets
+ * refuse an accumulator made with sets), for n_anno > GAMS_SW_SUMMARY_MAX_ANNO and for a NULL set or column; on every
+ * code but GAMS_OK the accumulator, Prop sums included, is as it was before the call. */
+int gams_gpu_sw_summary_batch_anno(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                   const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                                   const int32_t *feat_end, int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                                   gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
+                                   uint32_t n_anno, gams_spans_t *const *sets, const uint32_t *const *set_group,
+                                   uint64_t *n_rows);
+
 /* gc_content (round4, utils.rs:141-162) of n chromosome ranges inside ctg i: what `gams peak`
  * asks per merged peak (peak.rs:79; second "next" row of SURVEY section 8f). */
 int gams_gpu_range_gc(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_start,
@@ -610,6 +637,16 @@ int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *c
                                 int32_t size, int32_t max, int32_t resize, uint32_t actions,
                                 gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
                                 uint64_t *n_features, uint64_t *n_rows);
+
+/* gams_gpu_sw_feature_summary with span sets (see gams_gpu_sw_summary_batch_anno): set_group[a][i] for interval i of
+ * ctg_ix in the caller's order, as ctg_index is.  The same stages. */
+int gams_gpu_sw_feature_summary_anno(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                                     const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                                     const int32_t *chr_end, const char *bytes, uint64_t n_bytes,
+                                     int32_t size, int32_t max, int32_t resize, uint32_t actions,
+                                     gams_index_t *rg_ix, const uint32_t *rg_group, gams_sw_summary_t *sum, uint32_t tag,
+                                     uint32_t n_anno, gams_spans_t *const *sets, const uint32_t *const *set_group,
+                                     uint64_t *n_features, uint64_t *n_rows);
 
 /* ---- text in, text out: locate --seq (locate.rs:124-134) ---- */
 /* The bytes of ONE range file (lines, refused bytes and the 2^32 - 1 line limit as for gams_gpu_locate_text) -> the bases
