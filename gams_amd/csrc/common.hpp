@@ -251,41 +251,6 @@ void gams_launch_range_gc_cols(const gams_seqset_t *s, const unsigned long long 
                                const int32_t *chr_start, const uint32_t *rctg, const uint32_t *rs, const uint32_t *re,
                                uint32_t n, float *gc, hipStream_t st);
 
-// sw.hip, for text.hip (gams_gpu_sw_feature_text): stages 2-5 of that entry over device columns -- the rows of every
-// feature (sw_geometry), their 64-bit prefix and the first row of every interval, one read-back of the total and the
-// flags, sw_kernel, and the text with the ids composed on the device.  Interval i of the ctg index owns features
-// [bucket_off[i], bucket_off[i + 1]) of fs / fe / fctg (device, nf entries; fctg[f] = i), in file order.
-struct SwColsJob {
-    gams_seqset_t *s;                           // NULL without GAMS_SW_GC; its gc index exists (gams_seqset_gcindex)
-    uint32_t n_ctg, nf;
-    const int32_t *fs, *fe;                     // device
-    const uint32_t *fctg;                       // device
-    const unsigned long long *d_bucket_off;     // device, n_ctg + 1
-    const unsigned long long *bucket_off;       // host, n_ctg + 1
-    const uint32_t *ctg_index;                  // host, per interval: the seqset slot (UINT32_MAX: none)
-    const int32_t *chr_start, *chr_end;         // host, per interval
-    int32_t size, max, resize;
-    uint32_t actions;
-    const gams_index_t *rg_ix;                  // GAMS_SW_COUNT
-    const uint32_t *rg_group;                   // host, per interval
-    const uint32_t *igrp;                       // device, per interval: its group of the ctg index = its chromosome name
-    const unsigned long long *chr_off, *id_off; // device: the name tables' offsets (chr_names by group, ctg_ids by interval)
-    const char *chr_bytes, *id_bytes;
-    uint32_t max_chr, max_id;                   // the longest name of each table, in bytes
-    // device, 3 words: [0] receives the rows; [1] != 0: a kept feature has its middle outside its ctg, [2] = the
-    // smallest such line number (both written by the caller's gather, queued in front)
-    unsigned long long *words;
-    // gams_gpu_sw_feature_summary: the stages stop before the text -- the rows are added into tag slot `tag` of `summary`
-    // and never stored; the name tables above and the text outputs of the launcher are unused (NULL)
-    gams_sw_summary_t *summary;
-    uint32_t tag;
-    // gams_gpu_sw_feature_summary_anno: the span sets of the Prop columns and, per set, a host column of n_ctg groups
-    // (set_group[a][i] = the group of interval i's chromosome in set a, UINT32_MAX: absent); n_anno 0: none
-    uint32_t n_anno;
-    gams_spans_t *const *sets;
-    const uint32_t *const *set_group;
-};
-
 // The accumulator of the sw summaries (sw.hip): n_tags x (max + 1) groups of GAMS_SW_SUMMARY_WORDS 64-bit
 // integers in device memory, and the table of one call ((max + 1) groups, then a flag word) that the summarising
 // sw_kernel adds into and that is merged into a tag's groups only when the call met no value it does not cover.
@@ -298,16 +263,75 @@ struct gams_sw_summary {
     uint32_t n_anno = 0;
     unsigned long long *d_prop = nullptr;
 };
-// the call's parameters against the accumulator's binding, the tag slot against its tags and the span sets against the
-// number it was made for (none of them NULL; need_cols: nor a set_group column): GAMS_EINVAL otherwise
-int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, int32_t size, int32_t max,
-                          int32_t resize, uint32_t actions, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
-                          const uint32_t *const *set_group, bool need_cols);
+
+// What every sw call shares, whichever entry it came through and wherever its columns live: filled once, at the extern "C"
+// entry, and carried from there (SwReq in sw.hip, SwFeatJob in text.hip, SwColsJob below hold one each).
+struct SwCall {
+    int32_t size = 0, max = 0, resize = 0;
+    uint32_t actions = 0;
+    const gams_index_t *rg_ix = nullptr;        // GAMS_SW_COUNT: the rg index and (host) the group of every selected ctg / interval
+    const uint32_t *rg_group = nullptr;
+    gams_sw_summary_t *summary = nullptr;       // the summary entries: the rows go into tag slot `tag` of it and are never stored
+    uint32_t tag = 0;
+    // the _anno entries: the span sets of the Prop columns and, per set, a host column of groups (set_group[a][k] = the group
+    // of ctg / interval k's chromosome in set a, UINT32_MAX: absent); n_anno 0: none
+    uint32_t n_anno = 0;
+    gams_spans_t *const *sets = nullptr;
+    const uint32_t *const *set_group = nullptr;
+
+    SwCall() = default;
+    // (the rg index and groups are kept only where the call counts)
+    SwCall(int32_t size_, int32_t max_, int32_t resize_, uint32_t actions_, const gams_index_t *ix = nullptr, const uint32_t *group = nullptr)
+        : size(size_), max(max_), resize(resize_), actions(actions_), rg_ix(count() ? ix : nullptr), rg_group(count() ? group : nullptr) {}
+    bool gc() const { return (actions & GAMS_SW_GC) != 0; }
+    bool count() const { return (actions & GAMS_SW_COUNT) != 0; }
+    uint32_t variant() const { return (gc() ? 2u : 0u) | (count() ? 1u : 0u); }   // the kernel tables' index
+    bool known_actions() const { return (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) == 0; }
+    // size or resize 1: half_resize = 0 makes center_resize slice [mid+1, mid-1] (window.rs:113-123), an empty span whose
+    // min()/max() the reference then asks for -- no defined answer to mirror
+    bool window_ok() const { return size >= 2 && max >= 0 && resize >= 2; }
+    // one thread per (feature, slot): more than 2^24 windows a side cannot exist in a ctg of < 2^31 bases and would overflow
+    bool max_ok() const { return max <= (1 << 24); }
+};
+// The one check of a call's shared parameters, for the entry `who` names.  The entries differ in what of their own they
+// test in between, so each names the `parts` to test at that point; inside a call they are tested in the enumerators' order:
+// the action bits, GC without a seqset (have_seq: what the entry found; entries without that rule pass true), COUNT without
+// an rg index or (n_ctgs != 0) rg groups, the three lower bounds -- GAMS_EINVAL --, max beyond 2^24 (GAMS_EUNSUPPORTED),
+// the call against the accumulator's binding, tags and number of span sets, none of them NULL nor (n_ctgs != 0) a set_group
+// column (GAMS_EINVAL), and the slots of `nf` features against one launch (GAMS_EUNSUPPORTED).
+enum : uint32_t { SWC_ACTIONS = 1u, SWC_WINDOW = 2u, SWC_MAX = 4u, SWC_SUMMARY = 8u, SWC_SLOTS = 16u };
+int gams_sw_call_check(gams_gpu_t *h, const std::string &who, const SwCall &c, uint32_t parts, uint64_t n_ctgs,
+                       bool have_seq = true, uint64_t nf = 0);
+
+// sw.hip, for text.hip (gams_gpu_sw_feature_text): stages 2-5 of that entry over device columns -- the rows of every
+// feature (sw_geometry), their 64-bit prefix and the first row of every interval, one read-back of the total and the
+// flags, sw_kernel, and the text with the ids composed on the device.  Interval i of the ctg index owns features
+// [bucket_off[i], bucket_off[i + 1]) of fs / fe / fctg (device, nf entries; fctg[f] = i), in file order.
+// With call.summary the stages stop before the text; the name tables and the text outputs of the launcher are unused (NULL).
+struct SwColsJob {
+    SwCall call;                                // (rg_group, set_group: per interval)
+    gams_seqset_t *s;                           // NULL without GAMS_SW_GC; its gc index exists (gams_seqset_gcindex)
+    uint32_t n_ctg, nf;
+    const int32_t *fs, *fe;                     // device
+    const uint32_t *fctg;                       // device
+    const unsigned long long *d_bucket_off;     // device, n_ctg + 1
+    const unsigned long long *bucket_off;       // host, n_ctg + 1
+    const uint32_t *ctg_index;                  // host, per interval: the seqset slot (UINT32_MAX: none)
+    const int32_t *chr_start, *chr_end;         // host, per interval
+    const uint32_t *igrp;                       // device, per interval: its group of the ctg index = its chromosome name
+    const unsigned long long *chr_off, *id_off; // device: the name tables' offsets (chr_names by group, ctg_ids by interval)
+    const char *chr_bytes, *id_bytes;
+    uint32_t max_chr, max_id;                   // the longest name of each table, in bytes
+    // device, 3 words: [0] receives the rows; [1] != 0: a kept feature has its middle outside its ctg, [2] = the
+    // smallest such line number (both written by the caller's gather, queued in front)
+    unsigned long long *words;
+};
+
 // the timed pairs of the handle (gams_gpu::kq) these stages record: behind the range loader's lines .. order (0 .. 6)
 enum : int { SWF_GATHER = 7, SWF_GEOM, SWF_ROWS, SWF_TLEN, SWF_TWRITE, SWF_STAGES };
 // *text (the handle's page-locked sw text, valid until the next sw call), text_off[n_ctg + 1], *n_rows.  GAMS_EINVAL for
 // the flag in words[1] (the message names the line), GAMS_EUNSUPPORTED for what the formatter does not cover.  With
-// J.summary the stages end behind SWF_ROWS and only *n_rows is written.
+// J.call.summary the stages end behind SWF_ROWS and only *n_rows is written.
 int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
                         uint64_t *n_rows);
 

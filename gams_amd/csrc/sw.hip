@@ -526,31 +526,24 @@ int gams_seqset_gcindex(gams_gpu_t *h, gams_seqset_t *s) {
     h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the build reads the sequence bytes
     int wrc = gams_seqset_wait_uploads(h, s);
     if (wrc != GAMS_OK) return wrc;
-    gams_gcindex *ix = new gams_gcindex();
+    gams_gcindex *ix = s->gcindex = new gams_gcindex();   // the seqset's from here on: one way out, gams_seqset_gcindex_free
     ix->n_chunks = s->bytes / 16;
     ix->n_segs = (ix->n_chunks + 4095) / 4096;
+    bool launched = false;
     hipError_t e = hipMalloc(&ix->d_pm, ix->n_chunks * sizeof(uint32_t));
     if (e == hipSuccess) e = hipMalloc(&ix->d_seg, (ix->n_segs + 1) * sizeof(uint64_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // reported below, not left sticky
-        (void)hipFree(ix->d_pm);
-        (void)hipFree(ix->d_seg);
-        delete ix;
-        return gams_fail(h, GAMS_ENOMEM, std::string("gcindex: hipMalloc: ") + hipGetErrorString(e));
+    if (e == hipSuccess) {
+        launched = true;
+        hipLaunchKernelGGL(gc_index_build, dim3((unsigned)ix->n_segs), dim3(256), 0, h->compute, s->d_seq,
+                           ix->n_chunks, ix->d_pm, ix->d_seg);
+        hipLaunchKernelGGL(gc_index_scan, dim3(1), dim3(256), 0, h->compute, ix->d_seg, ix->n_segs);
+        e = hipGetLastError();
     }
-    hipLaunchKernelGGL(gc_index_build, dim3((unsigned)ix->n_segs), dim3(256), 0, h->compute, s->d_seq,
-                       ix->n_chunks, ix->d_pm, ix->d_seg);
-    hipLaunchKernelGGL(gc_index_scan, dim3(1), dim3(256), 0, h->compute, ix->d_seg, ix->n_segs);
-    e = hipGetLastError();
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // reported below, not left sticky
-        (void)hipFree(ix->d_pm);
-        (void)hipFree(ix->d_seg);
-        delete ix;
-        return gams_fail(h, GAMS_EHIP, std::string("gcindex: launch: ") + hipGetErrorString(e));
-    }
-    s->gcindex = ix;
-    return GAMS_OK;
+    if (e == hipSuccess) return GAMS_OK;
+    (void)hipGetLastError();   // reported below, not left sticky
+    gams_seqset_gcindex_free(s);
+    return gams_fail(h, launched ? GAMS_EHIP : GAMS_ENOMEM,
+                     std::string(launched ? "gcindex: launch: " : "gcindex: hipMalloc: ") + hipGetErrorString(e));
 }
 
 void gams_seqset_gcindex_free(gams_seqset_t *s) {
@@ -785,7 +778,7 @@ __global__ __launch_bounds__(256) void sw_ctg_row_off_kernel(const unsigned long
     if (i <= n_ctg) ctg_row_off[i] = row_off[bucket_off[i]];
 }
 
-struct SwTextReq {                       // what gams_gpu_sw_text adds to a batch call
+struct SwTextReq {                       // what the text entries add to a batch call
     const char *const *chr;              // per selected ctg
     const char *const *feat_id;          // per feature
     const char **text;
@@ -793,9 +786,11 @@ struct SwTextReq {                       // what gams_gpu_sw_text adds to a batc
     const uint64_t **ctg_off;
 };
 
-// one call of the batch entries: rows (gams_gpu_sw_batch: gc), count (gams_gpu_sw_count_batch: count) or tx (the text
-// entries: any action set)
+// One call of the batch entries.  What it is asked for: the rows (gams_gpu_sw_batch) or the counts (gams_gpu_sw_count_batch)
+// in the caller's array, the rows as text (the text entries) or the rows added into call.summary (the summary entries).
+enum class SwMode { Rows, Counts, Text, Summary };
 struct SwReq {
+    SwMode mode;
     gams_gpu_t *h;
     gams_seqset_t *s;
     uint32_t n_sel;
@@ -803,26 +798,37 @@ struct SwReq {
     const int32_t *chr_start;
     const uint64_t *feat_off;
     const int32_t *feat_start, *feat_end;
-    int32_t size, max, resize;
-    uint32_t actions;
-    const gams_index_t *rg_ix;           // -a count: the rg index, the group of every selected ctg
-    const uint32_t *rg_group;
-    gams_sw_row_t *rows;
-    int32_t *count;
-    uint64_t cap;
-    uint64_t *row_off, *n_rows;
-    const SwTextReq *tx;
-    gams_sw_summary_t *sum;              // gams_gpu_sw_summary_batch: the rows go into tag slot `tag` of it
-    uint32_t tag;
-    // gams_gpu_sw_summary_batch_anno: the span sets of the Prop columns and, per set, the group of every selected ctg
-    uint32_t n_anno;
-    gams_spans_t *const *sets;
-    const uint32_t *const *set_group;
-    const SwAnno *an;                    // sw_launch: what SwAnnoStage made of them (NULL: no set)
+    SwCall call;                         // (rg_group, set_group: per selected ctg)
+    uint64_t *n_rows;                    // what every entry passes; below, what the entry of a mode names besides
+    gams_sw_row_t *rows = nullptr;       // Rows, Counts: the caller's array of `cap` entries and the first row of every ctg
+    int32_t *count = nullptr;
+    uint64_t cap = 0;
+    uint64_t *row_off = nullptr;
+    SwTextReq tx{};                      // Text
+    SwReq(SwMode mode_, gams_gpu_t *h_, gams_seqset_t *s_, uint32_t n_sel_, const uint32_t *ctg_index_, const int32_t *chr_start_,
+          const uint64_t *feat_off_, const int32_t *feat_start_, const int32_t *feat_end_, const SwCall &call_, uint64_t *n_rows_)
+        : mode(mode_), h(h_), s(s_), n_sel(n_sel_), ctg_index(ctg_index_), chr_start(chr_start_), feat_off(feat_off_),
+          feat_start(feat_start_), feat_end(feat_end_), call(call_), n_rows(n_rows_) {}
+    // only *n_rows and row_off are wanted: neither text nor summary, and no array to fill or no room in it
+    bool size_query() const { return mode == SwMode::Rows ? !rows || !cap : mode == SwMode::Counts && (!count || !cap); }
 };
 
 using SwCols = SwStage<SwCtg>;
 const std::string kSw = "gpu_sw", kSwText = "gpu_sw_text", kRangeGc = "gpu_range_gc", kSwSum = "gpu_sw_summary";
+
+// the selected ctgs of a batch call (sw and range gc): every index names a ctg of a length the kernels carry, and `off`
+// (named `off_name` in the messages) begins at 0 and does not decrease
+int sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
+                       const uint32_t *ctg_index, const uint64_t *off) {
+    if (off[0] != 0) return gams_fail(h, GAMS_EINVAL, who + ": " + off_name + "[0] must be 0");
+    for (uint32_t k = 0; k < n_sel; ++k) {
+        if (ctg_index[k] >= s->n_ctg) return gams_fail(h, GAMS_EINVAL, who + ": ctg index out of range");
+        if (off[k + 1] < off[k]) return gams_fail(h, GAMS_EINVAL, who + ": " + off_name + " must not decrease");
+        const uint32_t len = s->len[ctg_index[k]];
+        if (len == 0 || len > 0x7fffffffu) return gams_fail(h, GAMS_EINVAL, who + ": ctg length out of range");
+    }
+    return GAMS_OK;
+}
 
 // 1. the arguments; *nf = the features of the call, 0 with GAMS_OK: nothing to do
 int sw_check(const SwReq &q, uint32_t *nf) {
@@ -830,30 +836,17 @@ int sw_check(const SwReq &q, uint32_t *nf) {
     *nf = 0;
     if (!h || !q.s || !q.n_rows || (q.n_sel && (!q.ctg_index || !q.chr_start || !q.feat_off)))
         return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
-    // size or resize 1: half_resize = 0 makes center_resize slice [mid+1, mid-1] (window.rs:113-123),
-    // an empty span whose min()/max() the reference then asks for -- no defined answer to mirror
-    if (q.size < 2 || q.max < 0 || q.resize < 2)
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw: size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
+    int rc = gams_sw_call_check(h, kSw, q.call, SWC_WINDOW, q.n_sel);
+    if (rc != GAMS_OK) return rc;
     *q.n_rows = 0;
     if (q.row_off)
         for (uint32_t k = 0; k <= q.n_sel; ++k) q.row_off[k] = 0;
     if (q.n_sel == 0) return GAMS_OK;
-    if (q.feat_off[0] != 0) return gams_fail(h, GAMS_EINVAL, "gpu_sw: feat_off[0] must be 0");
-    for (uint32_t k = 0; k < q.n_sel; ++k) {
-        if (q.ctg_index[k] >= q.s->n_ctg) return gams_fail(h, GAMS_EINVAL, "gpu_sw: ctg index out of range");
-        if (q.feat_off[k + 1] < q.feat_off[k]) return gams_fail(h, GAMS_EINVAL, "gpu_sw: feat_off must not decrease");
-        const uint32_t len = q.s->len[q.ctg_index[k]];
-        if (len == 0 || len > 0x7fffffffu) return gams_fail(h, GAMS_EINVAL, "gpu_sw: ctg length out of range");
-    }
+    if ((rc = sw_check_selection(h, kSw, "feat_off", q.s, q.n_sel, q.ctg_index, q.feat_off)) != GAMS_OK) return rc;
     const uint64_t nf64 = q.feat_off[q.n_sel];
     if (nf64 == 0) return GAMS_OK;
     if (!q.feat_start || !q.feat_end) return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
-    // one thread per (feature, slot); max beyond 2^24 windows a side cannot exist in a ctg of < 2^31 bases
-    // and would overflow the product
-    if (q.max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: max beyond 2^24 windows a side");
-    const uint64_t threads = nf64 * (1u + 2u * (uint64_t)q.max);
-    if (nf64 > 0xffffffffull || (threads + 255) / 256 > 0x7fffffffull)
-        return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: too many feature slots for one launch");
+    if ((rc = gams_sw_call_check(h, kSw, q.call, SWC_MAX | SWC_SLOTS, q.n_sel, true, nf64)) != GAMS_OK) return rc;
     *nf = (uint32_t)nf64;
     return GAMS_OK;
 }
@@ -861,7 +854,7 @@ int sw_check(const SwReq &q, uint32_t *nf) {
 // 2. the rows of every feature from the closed form (window.rs:29-41) -> exclusive offsets in in.row_off, the first row
 // of every selected ctg in crow (and q.row_off), and the kernel's inputs where `in` has them (a size query has none)
 int sw_host_rows(const SwReq &q, uint32_t nf, const SwCols &in, std::vector<uint64_t> &crow, uint64_t *n_rows) {
-    const bool do_count = (q.actions & GAMS_SW_COUNT) != 0;
+    const SwCall &c = q.call;
     uint64_t tot = 0;
     for (uint32_t k = 0; k < q.n_sel; ++k) {
         const uint32_t i = q.ctg_index[k];
@@ -869,7 +862,7 @@ int sw_host_rows(const SwReq &q, uint32_t nf, const SwCols &in, std::vector<uint
         if (q.row_off) q.row_off[k] = tot;
         crow[k] = tot;
         if (in.ctgs)
-            in.ctgs[k] = SwCtg{q.s->off[i], q.s->len[i], cs, ce, (uint32_t)q.feat_off[k], do_count ? q.rg_group[k] : UINT32_MAX, 0u};
+            in.ctgs[k] = SwCtg{q.s->off[i], q.s->len[i], cs, ce, (uint32_t)q.feat_off[k], c.count() ? c.rg_group[k] : UINT32_MAX, 0u};
         for (uint64_t f = q.feat_off[k]; f < q.feat_off[k + 1]; ++f) {
             // window.rs:98-110: the middle pair of the feature must be members of the ctg span --
             // IntSpan::index of a non-member has no defined answer in the reference to mirror
@@ -881,7 +874,7 @@ int sw_host_rows(const SwReq &q, uint32_t nf, const SwCols &in, std::vector<uint
                                                        (q.n_sel > 1 ? " of selected ctg " + std::to_string(k) : std::string()) +
                                                        " is empty or has its middle outside the ctg");
             in.row_off[f] = tot;
-            const SwGeom g = sw_geometry(cs, ce, q.feat_start[f], q.feat_end[f], q.size, q.max);
+            const SwGeom g = sw_geometry(cs, ce, q.feat_start[f], q.feat_end[f], c.size, c.max);
             tot += 1u + (uint64_t)g.n_l + (uint64_t)g.n_r;
             if (in.fs) {
                 in.fs[f] = q.feat_start[f];
@@ -903,39 +896,45 @@ struct SwAnnoStage {
     PoolBlock dev, pin;
     SwAnno an{};
     explicit SwAnnoStage(gams_gpu_t *h) : dev(h, false), pin(h, true) {}
-    int put(gams_gpu_t *h, const gams_sw_summary_t *sum, uint32_t n, gams_spans_t *const *sets,
-            const uint32_t *const *set_group, uint32_t n_cols) {
+    const SwAnno *staged() const { return an.n ? &an : nullptr; }   // what sw_launch takes (NULL: no set)
+    // the one place the sets of a call are staged; a call without a summary or without sets stages nothing
+    int put(gams_gpu_t *h, const SwCall &c, uint32_t n_cols) {
+        const uint32_t n = c.summary ? c.n_anno : 0u;
+        if (!n) return GAMS_OK;
         const size_t col = gams_align256((size_t)std::max(n_cols, 1u) * 4);
         GAMS_TRY(h, kSwSum, pin.alloc(col * n));
         GAMS_TRY(h, kSwSum, dev.alloc(col * n));
         for (uint32_t a = 0; a < n; ++a) {
-            std::memcpy(pin.p + a * col, set_group[a], (size_t)n_cols * 4);
-            an.set[a] = SwAnnoOne{sets[a]->d_groups, sets[a]->d_rec, sets[a]->d_dir_lo, sets[a]->d_cells,
-                                  reinterpret_cast<const uint32_t *>(dev.p + a * col), sets[a]->n_groups, 0u};
+            const gams_spans_t *set = c.sets[a];
+            std::memcpy(pin.p + a * col, c.set_group[a], (size_t)n_cols * 4);
+            an.set[a] = SwAnnoOne{set->d_groups, set->d_rec, set->d_dir_lo, set->d_cells,
+                                  reinterpret_cast<const uint32_t *>(dev.p + a * col), set->n_groups, 0u};
         }
         GAMS_TRY(h, kSwSum, hipMemcpyAsync(dev.p, pin.p, col * n, hipMemcpyHostToDevice, h->compute));
         an.n = n;
-        an.prop = sum->d_call + ((size_t)sum->max + 1) * kSumWords + 1;   // behind the call's table and its flag word
+        an.prop = c.summary->d_call + ((size_t)c.summary->max + 1) * kSumWords + 1;   // behind the call's table and its flag word
         return GAMS_OK;
     }
 };
-// the sets of an _anno entry against the accumulator
-int sw_anno_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, uint32_t n_anno,
-                  gams_spans_t *const *sets, const uint32_t *const *set_group, bool need_cols) {
-    if (n_anno > GAMS_SW_SUMMARY_MAX_ANNO) return gams_fail(h, GAMS_EINVAL, who + ": more than GAMS_SW_SUMMARY_MAX_ANNO span sets");
-    if (n_anno != sum->n_anno) return gams_fail(h, GAMS_EINVAL, who + ": the accumulator was created for another number of span sets");
-    if (n_anno && (!sets || !set_group)) return gams_fail(h, GAMS_EINVAL, who + ": null span sets or set groups");
-    for (uint32_t a = 0; a < n_anno; ++a)
-        if (!sets[a] || (need_cols && !set_group[a])) return gams_fail(h, GAMS_EINVAL, who + ": a null span set or set group column");
-    return GAMS_OK;
+
+// The twelve instantiations, named here and nowhere else: entry SwCall::variant() of the storing, the summarising and the
+// summarising kernel with span sets; and their one launch, 256 threads a workgroup
+using SwKernel = void (*)(SwArgs);
+using SwAnnoKernel = void (*)(SwArgs, SwAnno);
+const SwKernel kSwStoring[4] = {sw_kernel<false, false>, sw_kernel<false, true>, sw_kernel<true, false>, sw_kernel<true, true>};
+const SwKernel kSwSumming[4] = {sw_kernel<false, false, true>, sw_kernel<false, true, true>, sw_kernel<true, false, true>,
+                                sw_kernel<true, true, true>};
+const SwAnnoKernel kSwSummingSets[4] = {sw_anno_kernel<false, false>, sw_anno_kernel<false, true>, sw_anno_kernel<true, false>,
+                                        sw_anno_kernel<true, true>};
+template <typename... A>
+void sw_run(void (*const *table)(A...), const SwCall &c, dim3 grid, hipStream_t st, const A &...a) {
+    hipLaunchKernelGGL(table[c.variant()], grid, dim3(256), 0, st, a...);
 }
 
 // 3'. the summarising kernel: the call's table zeroed, the rows added into it, the table merged into the tag's groups
 // unless the flag word behind it was raised; one read-back, of that word
-int sw_sum_launch(const SwReq &q, SwArgs &a, dim3 grid) {
-    gams_gpu_t *h = q.h;
-    gams_sw_summary_t *sum = q.sum;
-    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
+int sw_sum_launch(gams_gpu_t *h, const SwCall &c, SwArgs &a, dim3 grid, const SwAnno *an) {
+    gams_sw_summary_t *sum = c.summary;
     const uint32_t words = ((uint32_t)sum->max + 1u) * kSumWords;
     a.sum = sum->d_call;
     a.sum_bad = sum->d_call + words;
@@ -944,27 +943,14 @@ int sw_sum_launch(const SwReq &q, SwArgs &a, dim3 grid) {
     hipStream_t st = h->compute;
     const uint32_t pwords = ((uint32_t)sum->max + 1u) * sum->n_anno;
     GAMS_TRY(h, kSwSum, hipMemsetAsync(sum->d_call, 0, ((size_t)words + 1 + pwords) * 8, st));
-    if (q.an) {                                                // (sum->n_anno sets: the entries checked)
-        if (do_gc && do_count)
-            hipLaunchKernelGGL((sw_anno_kernel<true, true>), grid, dim3(256), 0, st, a, *q.an);
-        else if (do_gc)
-            hipLaunchKernelGGL((sw_anno_kernel<true, false>), grid, dim3(256), 0, st, a, *q.an);
-        else if (do_count)
-            hipLaunchKernelGGL((sw_anno_kernel<false, true>), grid, dim3(256), 0, st, a, *q.an);
-        else
-            hipLaunchKernelGGL((sw_anno_kernel<false, false>), grid, dim3(256), 0, st, a, *q.an);
-        hipLaunchKernelGGL(sw_sum_merge_kernel, dim3((pwords + 255u) / 256u), dim3(256), 0, st, q.an->prop, a.sum_bad,
-                           sum->d_prop + (size_t)q.tag * pwords, pwords);
-    } else if (do_gc && do_count)
-        hipLaunchKernelGGL((sw_kernel<true, true, true>), grid, dim3(256), 0, st, a);
-    else if (do_gc)
-        hipLaunchKernelGGL((sw_kernel<true, false, true>), grid, dim3(256), 0, st, a);
-    else if (do_count)
-        hipLaunchKernelGGL((sw_kernel<false, true, true>), grid, dim3(256), 0, st, a);
-    else
-        hipLaunchKernelGGL((sw_kernel<false, false, true>), grid, dim3(256), 0, st, a);
+    if (an) {                                                  // (sum->n_anno sets: the entries checked)
+        sw_run(kSwSummingSets, c, grid, st, a, *an);
+        hipLaunchKernelGGL(sw_sum_merge_kernel, dim3((pwords + 255u) / 256u), dim3(256), 0, st, an->prop, a.sum_bad,
+                           sum->d_prop + (size_t)c.tag * pwords, pwords);
+    } else
+        sw_run(kSwSumming, c, grid, st, a);
     hipLaunchKernelGGL(sw_sum_merge_kernel, dim3((words + 255u) / 256u), dim3(256), 0, st, sum->d_call, a.sum_bad,
-                       sum->d_acc + (size_t)q.tag * words, words);
+                       sum->d_acc + (size_t)c.tag * words, words);
     GAMS_TRY(h, kSwSum, hipGetLastError());
     return GAMS_OK;
 }
@@ -979,22 +965,21 @@ int sw_sum_verdict(gams_gpu_t *h, const gams_sw_summary_t *sum) {
     return GAMS_OK;
 }
 
-// 3. the kernel over the uploaded inputs `d`: n_out rows (and counts)
-int sw_launch(const SwReq &q, uint32_t nf, uint64_t n_out, const SwCols &d, gams_sw_row_t *d_rows, int32_t *d_cnt) {
-    gams_gpu_t *h = q.h;
-    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
+// 3. the kernel over the uploaded inputs `d`: n_out rows (and counts), or every row into c.summary (`an`: its staged sets)
+int sw_launch(gams_gpu_t *h, const SwCall &c, const gams_seqset_t *s, uint32_t nf, uint64_t n_out, const SwCols &d,
+              gams_sw_row_t *d_rows, int32_t *d_cnt, const SwAnno *an) {
     SwArgs a{};
-    if (do_gc) {
-        a.pm = q.s->gcindex->d_pm;
-        a.seg = q.s->gcindex->d_seg;
+    if (c.gc()) {
+        a.pm = s->gcindex->d_pm;
+        a.seg = s->gcindex->d_seg;
     }
-    if (do_count) {
-        a.cgroups = q.rg_ix->d_cgroups;
-        a.rg_starts = q.rg_ix->d_lstart;
-        a.rg_stops = q.rg_ix->d_stops;
-        a.bk_start = q.rg_ix->d_bk_start;
-        a.bk_stop = q.rg_ix->d_bk_stop;
-        a.n_groups = q.rg_ix->n_groups;
+    if (c.count()) {
+        a.cgroups = c.rg_ix->d_cgroups;
+        a.rg_starts = c.rg_ix->d_lstart;
+        a.rg_stops = c.rg_ix->d_stops;
+        a.bk_start = c.rg_ix->d_bk_start;
+        a.bk_stop = c.rg_ix->d_bk_stop;
+        a.n_groups = c.rg_ix->n_groups;
         a.cnt = d_cnt;
     }
     a.ctgs = d.ctgs;
@@ -1003,24 +988,18 @@ int sw_launch(const SwReq &q, uint32_t nf, uint64_t n_out, const SwCols &d, gams
     a.fctg = d.fctg;
     a.row_off = d.row_off;
     a.nf = nf;
-    a.size = q.size;
-    a.max = q.max;
-    a.resize = q.resize;
+    a.size = c.size;
+    a.max = c.max;
+    a.resize = c.resize;
     a.rows = d_rows;
     a.cap = n_out;
-    const dim3 grid((unsigned)(((uint64_t)nf * (1u + 2u * (uint64_t)q.max) + 255) / 256));
+    const dim3 grid((unsigned)(((uint64_t)nf * (1u + 2u * (uint64_t)c.max) + 255) / 256));
     GAMS_TRY(h, kSw, hipEventRecord(h->k0, h->compute));
-    if (q.sum) {
-        const int rc = sw_sum_launch(q, a, grid);
+    if (c.summary) {
+        const int rc = sw_sum_launch(h, c, a, grid, an);
         if (rc != GAMS_OK) return rc;
-    } else if (do_gc && do_count)
-        hipLaunchKernelGGL((sw_kernel<true, true>), grid, dim3(256), 0, h->compute, a);
-    else if (do_gc)
-        hipLaunchKernelGGL((sw_kernel<true, false>), grid, dim3(256), 0, h->compute, a);
-    else if (do_count)
-        hipLaunchKernelGGL((sw_kernel<false, true>), grid, dim3(256), 0, h->compute, a);
-    else
-        hipLaunchKernelGGL((sw_kernel<false, false>), grid, dim3(256), 0, h->compute, a);
+    } else
+        sw_run(kSwStoring, c, grid, h->compute, a);
     GAMS_TRY(h, kSw, hipGetLastError());
     GAMS_TRY(h, kSw, hipEventRecord(h->k1, h->compute));
     h->k_valid = true;
@@ -1035,7 +1014,7 @@ struct SwTextBlobs {
     size_t max_name = 0, max_id = 0;
 };
 int sw_text_blobs(const SwReq &q, uint32_t nf, SwTextBlobs &b) {
-    const SwTextReq *tx = q.tx;
+    const SwTextReq *tx = &q.tx;
     b.name_off.resize((size_t)q.n_sel + 1);
     b.id_off.resize((size_t)nf + 1);
     for (uint32_t k = 0; k < q.n_sel; ++k) {
@@ -1075,6 +1054,14 @@ void sw_text_cols(Carver &c, SwTextArgs &ta, uint64_t n_rows, uint32_t n_sel, ui
     ta.blk_off = c.take<unsigned long long>((size_t)ta.nb + 1);
     ta.words = c.take<unsigned long long>((size_t)n_sel + 3);
     ta.text = c.take<char>(ta.text_cap);
+}
+// ... and the sources both paths fill alike: the call's rows and counts on the device, their ctgs, the first row of every feature
+void sw_text_rows(SwTextArgs &ta, const SwCall &c, const SwCols &d, const gams_sw_row_t *d_rows, const int32_t *d_cnt) {
+    ta.rows = d_rows;
+    ta.ctgs = d.ctgs;
+    ta.feat_row_off = d.row_off;
+    ta.gc = c.gc() ? 1u : 0u;
+    ta.cnt = d_cnt;
 }
 struct SwText {
     const char *text;                  // nullptr: no byte
@@ -1121,13 +1108,12 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
 int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vector<uint64_t> &crow, const SwCols &d,
                     const gams_sw_row_t *d_rows, const int32_t *d_cnt) {
     gams_gpu_t *h = q.h;
-    const SwTextReq *tx = q.tx;
+    const SwTextReq *tx = &q.tx;
     const uint32_t n_sel = q.n_sel;
-    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
     SwTextBlobs B;
     const int rc = sw_text_blobs(q, nf, B);
     if (rc != GAMS_OK) return rc;
-    const uint64_t per_row = B.max_id + B.max_name + (do_count ? 112 : 96);
+    const uint64_t per_row = B.max_id + B.max_name + (q.call.count() ? 112 : 96);
     auto tabs = [&](Carver &c) { return sw_text_tabs_layout(c, n_sel, nf, B.names.size(), B.ids.size()); };
     SwTextArgs ta{};
     auto dev = [&](Carver &c) {   // tables | what the tail writes
@@ -1151,11 +1137,7 @@ int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vect
     std::memcpy(ht.ids, B.ids.data(), B.ids.size());
     GAMS_TRY(h, kSwText, hipMemcpyAsync(tdev.p, tpin.p, tab_bytes, hipMemcpyHostToDevice, h->compute));
     carve(tdev.p, dev);
-    ta.rows = d_rows;
-    ta.ctgs = d.ctgs;
-    ta.feat_row_off = d.row_off;
-    ta.gc = do_gc ? 1u : 0u;
-    ta.cnt = d_cnt;
+    sw_text_rows(ta, q.call, d, d_rows, d_cnt);
     SwText T{};
     const int rt = sw_text_tail(h, kSwText, "format gams_gpu_sw_batch's rows on the host", ta, nullptr, &T);
     if (rt != GAMS_OK) return rt;
@@ -1167,15 +1149,16 @@ int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vect
 
 int sw_batch_impl(const SwReq &q) {
     gams_gpu_t *h = q.h;
+    const SwCall &c = q.call;
+    const bool text = q.mode == SwMode::Text, summary = q.mode == SwMode::Summary;
     uint32_t nf = 0;
     int rc = sw_check(q, &nf);
     if (rc != GAMS_OK || nf == 0) return rc;
     GAMS_HIP(h, hipSetDevice(h->device));
-    const bool do_gc = (q.actions & GAMS_SW_GC) != 0, do_count = (q.actions & GAMS_SW_COUNT) != 0;
     // Inputs are assembled in one page-locked block (one DMA): ctgs | fs | fe | fctg | off
-    auto inputs = [&](Carver &c) { return sw_stage_layout<SwCtg>(c, q.n_sel, nf, true); };
+    auto inputs = [&](Carver &cv) { return sw_stage_layout<SwCtg>(cv, q.n_sel, nf, true); };
     const size_t in_bytes = layout_bytes(inputs);
-    const bool size_query = !q.tx && !q.sum && ((!q.rows && !q.count) || q.cap == 0);
+    const bool size_query = q.size_query();
     PoolBlock dev(h, false), pin(h, true);
     std::vector<uint64_t> crow((size_t)q.n_sel + 1, 0);    // first row of every selected ctg (text mode)
     std::vector<uint64_t> off_host(size_query ? (size_t)nf + 1 : 0);   // a size query: no device, no pinned memory
@@ -1190,29 +1173,25 @@ int sw_batch_impl(const SwReq &q) {
     *q.n_rows = tot;
     if (size_query) return GAMS_OK;
     // the counts and the geometry read no sequence byte: a count-only call leaves the bytes alone
-    if (do_gc && (rc = gams_seqset_gcindex(h, q.s)) != GAMS_OK) return rc;
+    if (c.gc() && (rc = gams_seqset_gcindex(h, q.s)) != GAMS_OK) return rc;
     // text mode: every row, kept on the device; the summary stores none
-    const uint64_t n_out = q.sum ? 0 : std::min<uint64_t>(tot, q.tx ? tot : q.cap);
+    const uint64_t n_out = summary ? 0 : std::min<uint64_t>(tot, text ? tot : q.cap);
     SwCols d{};
     gams_sw_row_t *d_rows = nullptr;
     int32_t *d_cnt = nullptr;
-    auto device = [&](Carver &c) {   // the inputs | rows | counts
-        d = inputs(c);
-        d_rows = c.take_tight<gams_sw_row_t>(std::max<uint64_t>(n_out, 1));
-        d_cnt = do_count ? c.take<int32_t>(std::max<uint64_t>(n_out, 1)) : nullptr;
+    auto device = [&](Carver &cv) {   // the inputs | rows | counts
+        d = inputs(cv);
+        d_rows = cv.take_tight<gams_sw_row_t>(std::max<uint64_t>(n_out, 1));
+        d_cnt = c.count() ? cv.take<int32_t>(std::max<uint64_t>(n_out, 1)) : nullptr;
     };
     GAMS_TRY(h, kSw, dev.alloc(layout_bytes(device)));
     carve(dev.p, device);
     GAMS_TRY(h, kSw, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
     SwAnnoStage sets(h);
-    SwReq ql = q;
-    if (q.sum && q.n_anno) {
-        if ((rc = sets.put(h, q.sum, q.n_anno, q.sets, q.set_group, q.n_sel)) != GAMS_OK) return rc;
-        ql.an = &sets.an;
-    }
-    if ((rc = sw_launch(ql, nf, n_out, d, d_rows, d_cnt)) != GAMS_OK) return rc;
-    if (q.sum) return sw_sum_verdict(h, q.sum);
-    if (q.tx) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt);
+    if ((rc = sets.put(h, c, q.n_sel)) != GAMS_OK) return rc;
+    if ((rc = sw_launch(h, c, q.s, nf, n_out, d, d_rows, d_cnt, sets.staged())) != GAMS_OK) return rc;
+    if (summary) return sw_sum_verdict(h, c.summary);
+    if (text) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt);
     // 5. read back
     if (q.rows) GAMS_TRY(h, kSw, hipMemcpyAsync(q.rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
     if (q.count) GAMS_TRY(h, kSw, hipMemcpyAsync(q.count, d_cnt, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, h->compute));
@@ -1223,8 +1202,8 @@ int sw_batch_impl(const SwReq &q) {
 
 int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
                         uint64_t *n_rows) {
-    const std::string who = J.summary ? "gpu_sw_feature_summary" : "gpu_sw_feature_text";
-    const bool do_gc = (J.actions & GAMS_SW_GC) != 0, do_count = (J.actions & GAMS_SW_COUNT) != 0;
+    const SwCall &call = J.call;
+    const std::string who = call.summary ? "gpu_sw_feature_summary" : "gpu_sw_feature_text";
     const uint32_t n_ctg = J.n_ctg, nf = J.nf;
     hipStream_t st = h->compute;
     const StageClock stage{h, st};
@@ -1247,18 +1226,18 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     carve(g_dev.p, geom);
     SwCtg *const h_ctgs = reinterpret_cast<SwCtg *>(g_pin.p);
     for (uint32_t i = 0; i < n_ctg; ++i) {
-        const uint32_t slot = do_gc ? J.ctg_index[i] : UINT32_MAX;
+        const uint32_t slot = call.gc() ? J.ctg_index[i] : UINT32_MAX;
         const bool has = slot != UINT32_MAX && J.bucket_off[i + 1] > J.bucket_off[i];   // (checked by the caller)
         h_ctgs[i] = SwCtg{has ? J.s->off[slot] : 0ull,
                           has ? J.s->len[slot] : (uint32_t)((int64_t)J.chr_end[i] - J.chr_start[i] + 1),
-                          J.chr_start[i], J.chr_end[i], (uint32_t)J.bucket_off[i], do_count ? J.rg_group[i] : UINT32_MAX, 0u};
+                          J.chr_start[i], J.chr_end[i], (uint32_t)J.bucket_off[i], call.count() ? call.rg_group[i] : UINT32_MAX, 0u};
     }
     GAMS_TRY(h, who, hipMemcpyAsync(d_ctgs, h_ctgs, (size_t)n_ctg * sizeof(SwCtg), hipMemcpyHostToDevice, st));
     // 2. geometry: rows per feature -> row_off, ctg_row_off
     GAMS_TRY(h, who, stage(SWF_GEOM, true));
-    hipLaunchKernelGGL(sw_geom_kernel, dim3(nbf), dim3(256), 0, st, d_ctgs, J.fctg, J.fs, J.fe, nf, J.size, J.max, d_cnt_f, d_blk);
+    hipLaunchKernelGGL(sw_geom_kernel, dim3(nbf), dim3(256), 0, st, d_ctgs, J.fctg, J.fs, J.fe, nf, call.size, call.max, d_cnt_f, d_blk);
     hipLaunchKernelGGL(blk_offsets_scan_kernel<unsigned long long>, dim3(1), dim3(1024), 0, st, d_blk, nbf, d_blk_off, J.words, 0u);
-    if (!J.summary) {   // (the summary asks where no row lies)
+    if (!call.summary) {   // (the summary asks where no row lies)
         hipLaunchKernelGGL(sw_row_off_kernel, dim3(nbf), dim3(256), 0, st, d_cnt_f, d_blk_off, nf, nbf, d_row_off);
         hipLaunchKernelGGL(sw_ctg_row_off_kernel, dim3(n_ctg / 256u + 1u), dim3(256), 0, st, d_row_off, J.d_bucket_off, n_ctg,
                            d_ctg_row_off);
@@ -1277,28 +1256,15 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     int32_t *d_cnt = nullptr;
     auto rows = [&](Carver &c) {
         d_rows = c.take<gams_sw_row_t>(std::max<uint64_t>(tot, 1));
-        d_cnt = do_count ? c.take<int32_t>(std::max<uint64_t>(tot, 1)) : nullptr;
+        d_cnt = call.count() ? c.take<int32_t>(std::max<uint64_t>(tot, 1)) : nullptr;
     };
-    if (!J.summary) {
+    if (!call.summary) {
         GAMS_TRY(h, who, r_dev.alloc(layout_bytes(rows)));
         carve(r_dev.p, rows);
     }
-    SwReq q{};
     SwAnnoStage sets(h);
-    if (J.summary && J.n_anno) {
-        const int ra = sets.put(h, J.summary, J.n_anno, J.sets, J.set_group, n_ctg);
-        if (ra != GAMS_OK) return ra;
-        q.an = &sets.an;
-    }
-    q.sum = J.summary;
-    q.tag = J.tag;
-    q.h = h;
-    q.s = J.s;
-    q.size = J.size;
-    q.max = J.max;
-    q.resize = J.resize;
-    q.actions = J.actions;
-    q.rg_ix = do_count ? J.rg_ix : nullptr;
+    const int ra = sets.put(h, call, n_ctg);
+    if (ra != GAMS_OK) return ra;
     SwCols d{};
     d.ctgs = d_ctgs;
     d.fs = const_cast<int32_t *>(J.fs);
@@ -1306,25 +1272,21 @@ int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, ui
     d.fctg = const_cast<uint32_t *>(J.fctg);
     d.row_off = reinterpret_cast<uint64_t *>(d_row_off);
     GAMS_TRY(h, who, stage(SWF_ROWS, true));
-    const int rc = sw_launch(q, nf, tot, d, d_rows, d_cnt);
+    const int rc = sw_launch(h, call, J.s, nf, tot, d, d_rows, d_cnt, sets.staged());
     if (rc != GAMS_OK) return rc;
     GAMS_TRY(h, who, stage(SWF_ROWS, false));
-    if (J.summary) {   // 4'. the rows went into the accumulator: nothing to print
+    if (call.summary) {   // 4'. the rows went into the accumulator: nothing to print
         *n_rows = tot;
-        return sw_sum_verdict(h, J.summary);
+        return sw_sum_verdict(h, call.summary);
     }
     // 5. the text, with the ids composed on the device
-    const uint64_t per_row = 8ull + J.max_id + 1ull + 10ull + J.max_chr + (do_count ? 112ull : 96ull);
+    const uint64_t per_row = 8ull + J.max_id + 1ull + 10ull + J.max_chr + (call.count() ? 112ull : 96ull);
     SwTextArgs ta{};
     auto txt = [&](Carver &c) { sw_text_cols(c, ta, tot, n_ctg, per_row); };
     GAMS_TRY(h, who, t_dev.alloc(layout_bytes(txt)));
     carve(t_dev.p, txt);
-    ta.rows = d_rows;
-    ta.ctgs = d_ctgs;
+    sw_text_rows(ta, call, d, d_rows, d_cnt);
     ta.ctg_row_off = reinterpret_cast<const uint64_t *>(d_ctg_row_off);
-    ta.feat_row_off = reinterpret_cast<const uint64_t *>(d_row_off);
-    ta.gc = do_gc ? 1u : 0u;
-    ta.cnt = d_cnt;
     ta.dev_ids = 1u;
     ta.cid_off = J.id_off;
     ta.cid_bytes = J.id_bytes;
@@ -1345,8 +1307,12 @@ extern "C" int gams_gpu_sw_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel
                                  const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
                                  const int32_t *feat_end, int32_t size, int32_t max, int32_t resize,
                                  gams_sw_row_t *rows, uint64_t cap, uint64_t *row_off, uint64_t *n_rows) {
-    return sw_batch_impl(SwReq{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, GAMS_SW_GC,
-                               nullptr, nullptr, rows, nullptr, cap, row_off, n_rows, nullptr});
+    const SwCall c(size, max, resize, GAMS_SW_GC);
+    SwReq q(SwMode::Rows, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
+    q.rows = rows;
+    q.cap = cap;
+    q.row_off = row_off;
+    return sw_batch_impl(q);
 }
 
 extern "C" int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -1356,8 +1322,12 @@ extern "C" int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
                                        uint64_t *n_rows) {
     if (!rg_ix || (n_sel && !rg_group)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_count: null rg index or rg groups");
     // resize only shapes the gc statistics, which this call does not compute: any value the checks accept
-    return sw_batch_impl(SwReq{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, 2, GAMS_SW_COUNT,
-                               rg_ix, rg_group, nullptr, count, cap, row_off, n_rows, nullptr});
+    const SwCall c(size, max, 2, GAMS_SW_COUNT, rg_ix, rg_group);
+    SwReq q(SwMode::Counts, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
+    q.count = count;
+    q.cap = cap;
+    q.row_off = row_off;
+    return sw_batch_impl(q);
 }
 
 extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -1368,16 +1338,15 @@ extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_
                                         const uint64_t **ctg_off, uint64_t *n_rows) {
     if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
         return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
-    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: unknown action bits");
-    if ((actions & GAMS_SW_COUNT) && (!rg_ix || (n_sel && !rg_group)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: GAMS_SW_COUNT without an rg index or rg groups");
+    SwCall c(size, max, resize, actions, rg_ix, rg_group);
+    const int rc = gams_sw_call_check(h, kSwText, c, SWC_ACTIONS, n_sel);
+    if (rc != GAMS_OK) return rc;
     if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
-    const SwTextReq tx{chr, feat_id, text, text_bytes, ctg_off};
+    SwReq q(SwMode::Text, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
+    q.tx = SwTextReq{chr, feat_id, text, text_bytes, ctg_off};
     *text = nullptr;
     *text_bytes = 0;
-    const bool cnt = (actions & GAMS_SW_COUNT) != 0;
-    return sw_batch_impl(SwReq{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions,
-                               cnt ? rg_ix : nullptr, cnt ? rg_group : nullptr, nullptr, nullptr, 0, nullptr, n_rows, &tx});
+    return sw_batch_impl(q);
 }
 
 extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -1390,15 +1359,42 @@ extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel,
 }
 
 // ---- the accumulator of the sw summaries -----------------------------------------------------------------------------
-int gams_sw_summary_check(gams_gpu_t *h, const std::string &who, const gams_sw_summary_t *sum, int32_t size, int32_t max,
-                          int32_t resize, uint32_t actions, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
-                          const uint32_t *const *set_group, bool need_cols) {
+// the call's parameters against the accumulator's binding, the tag slot against its tags and the span sets against the
+// number it was made for (none of them NULL; need_cols: nor a set_group column): GAMS_EINVAL otherwise
+static int sw_summary_check(gams_gpu_t *h, const std::string &who, const SwCall &c, bool need_cols) {
+    const gams_sw_summary_t *sum = c.summary;
     if (!sum) return gams_fail(h, GAMS_EINVAL, who + ": null argument");
-    const int ra = sw_anno_check(h, who, sum, n_anno, sets, set_group, need_cols);
-    if (ra != GAMS_OK) return ra;
-    if (sum->size != size || sum->max != max || sum->resize != resize || sum->actions != actions)
+    if (c.n_anno > GAMS_SW_SUMMARY_MAX_ANNO) return gams_fail(h, GAMS_EINVAL, who + ": more than GAMS_SW_SUMMARY_MAX_ANNO span sets");
+    if (c.n_anno != sum->n_anno) return gams_fail(h, GAMS_EINVAL, who + ": the accumulator was created for another number of span sets");
+    if (c.n_anno && (!c.sets || !c.set_group)) return gams_fail(h, GAMS_EINVAL, who + ": null span sets or set groups");
+    for (uint32_t a = 0; a < c.n_anno; ++a)
+        if (!c.sets[a] || (need_cols && !c.set_group[a])) return gams_fail(h, GAMS_EINVAL, who + ": a null span set or set group column");
+    if (sum->size != c.size || sum->max != c.max || sum->resize != c.resize || sum->actions != c.actions)
         return gams_fail(h, GAMS_EINVAL, who + ": the accumulator was created for other size, max, resize or actions");
-    if (tag >= sum->n_tags) return gams_fail(h, GAMS_EINVAL, who + ": tag slot beyond the accumulator's tags");
+    if (c.tag >= sum->n_tags) return gams_fail(h, GAMS_EINVAL, who + ": tag slot beyond the accumulator's tags");
+    return GAMS_OK;
+}
+
+int gams_sw_call_check(gams_gpu_t *h, const std::string &who, const SwCall &c, uint32_t parts, uint64_t n_ctgs, bool have_seq,
+                       uint64_t nf) {
+    if (parts & SWC_ACTIONS) {
+        if (!c.known_actions()) return gams_fail(h, GAMS_EINVAL, who + ": unknown action bits");
+        if (c.gc() && !have_seq) return gams_fail(h, GAMS_EINVAL, who + ": GAMS_SW_GC without a seqset or the ctgs' slots");
+        if (c.count() && (!c.rg_ix || (n_ctgs && !c.rg_group)))
+            return gams_fail(h, GAMS_EINVAL, who + ": GAMS_SW_COUNT without an rg index or rg groups");
+    }
+    if ((parts & SWC_WINDOW) && !c.window_ok())
+        return gams_fail(h, GAMS_EINVAL, who + ": size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
+    if ((parts & SWC_MAX) && !c.max_ok()) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": max beyond 2^24 windows a side");
+    if (parts & SWC_SUMMARY) {
+        const int rc = sw_summary_check(h, who, c, n_ctgs != 0);
+        if (rc != GAMS_OK) return rc;
+    }
+    if (parts & SWC_SLOTS) {
+        const uint64_t threads = nf * (1u + 2u * (uint64_t)c.max);
+        if (nf > 0xffffffffull || (threads + 255) / 256 > 0x7fffffffull)
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": too many feature slots for one launch");
+    }
     return GAMS_OK;
 }
 
@@ -1413,7 +1409,8 @@ extern "C" int gams_sw_summary_create_anno(gams_gpu_t *h, int32_t max, uint32_t 
     *out = nullptr;
     if (n_anno > GAMS_SW_SUMMARY_MAX_ANNO)
         return gams_fail(h, GAMS_EINVAL, "sw_summary_create: more than GAMS_SW_SUMMARY_MAX_ANNO span sets");
-    if (n_tags == 0 || size < 2 || max < 0 || max > (1 << 24) || resize < 2 || (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)))
+    const SwCall c(size, max, resize, actions);
+    if (n_tags == 0 || !c.window_ok() || !c.max_ok() || !c.known_actions())
         return gams_fail(h, GAMS_EINVAL, "sw_summary_create: n_tags >= 1, size >= 2, 0 <= max <= 2^24, resize >= 2, known action bits");
     GAMS_HIP(h, hipSetDevice(h->device));
     const size_t words = ((size_t)max + 1) * kSumWords;
@@ -1500,16 +1497,15 @@ extern "C" int gams_gpu_sw_summary_batch_anno(gams_gpu_t *h, gams_seqset_t *s, u
                                               gams_sw_summary_t *sum, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
                                               const uint32_t *const *set_group, uint64_t *n_rows) {
     if (!h || !n_rows || (n_sel && !feat_off)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: null argument");
-    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: unknown action bits");
-    if ((actions & GAMS_SW_COUNT) && (!rg_ix || (n_sel && !rg_group)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_summary: GAMS_SW_COUNT without an rg index or rg groups");
-    const int rc = gams_sw_summary_check(h, kSwSum, sum, size, max, resize, actions, tag, n_anno, sets, set_group, n_sel != 0);
+    SwCall c(size, max, resize, actions, rg_ix, rg_group);
+    c.summary = sum;
+    c.tag = tag;
+    c.n_anno = n_anno;
+    c.sets = sets;
+    c.set_group = set_group;
+    const int rc = gams_sw_call_check(h, kSwSum, c, SWC_ACTIONS | SWC_SUMMARY, n_sel);
     if (rc != GAMS_OK) return rc;
-    const bool cnt = (actions & GAMS_SW_COUNT) != 0;
-    SwReq q{h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, size, max, resize, actions,
-            cnt ? rg_ix : nullptr, cnt ? rg_group : nullptr, nullptr, nullptr, 0, nullptr, n_rows, nullptr, sum, tag,
-            n_anno, sets, set_group, nullptr};
-    return sw_batch_impl(q);
+    return sw_batch_impl(SwReq(SwMode::Summary, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows));
 }
 
 extern "C" int gams_gpu_sw_summary_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -1539,13 +1535,8 @@ extern "C" int gams_gpu_range_gc_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
     if (!h || !s || (n_sel && (!ctg_index || !chr_start || !range_off)))
         return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: null argument");
     if (n_sel == 0) return GAMS_OK;
-    if (range_off[0] != 0) return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: range_off[0] must be 0");
-    for (uint32_t k = 0; k < n_sel; ++k) {
-        if (ctg_index[k] >= s->n_ctg) return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: ctg index out of range");
-        if (range_off[k + 1] < range_off[k]) return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: range_off must not decrease");
-        const uint32_t len = s->len[ctg_index[k]];
-        if (len == 0 || len > 0x7fffffffu) return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: ctg length out of range");
-    }
+    int rc = sw_check_selection(h, kRangeGc, "range_off", s, n_sel, ctg_index, range_off);
+    if (rc != GAMS_OK) return rc;
     const uint64_t n64 = range_off[n_sel];
     if (n64 == 0) return GAMS_OK;
     if (!range_start || !range_end || !gc) return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: null argument");
@@ -1574,8 +1565,7 @@ extern "C" int gams_gpu_range_gc_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
             in.fctg[q] = k;
         }
     }
-    const int rc = gams_seqset_gcindex(h, s);
-    if (rc != GAMS_OK) return rc;
+    if ((rc = gams_seqset_gcindex(h, s)) != GAMS_OK) return rc;
     SwCols d{};
     float *d_gc = nullptr;
     auto device = [&](Carver &c) {   // the inputs | results

@@ -1493,30 +1493,23 @@ __global__ __launch_bounds__(256) void sw_gather_kernel(const SwGather a) {
 }
 
 struct SwFeatJob {
+    SwCall call;                              // (with call.summary the three text outputs below are NULL)
     gams_seqset_t *s;
     const gams_index_t *ctg_ix;
     const gams_names_t *chr, *ids;
     const uint32_t *ctg_index;
     const int32_t *chr_start, *chr_end;
-    int32_t size, max, resize;
-    uint32_t actions;
-    const gams_index_t *rg_ix;
-    const uint32_t *rg_group;
-    gams_sw_summary_t *summary;               // gams_gpu_sw_feature_summary: the rows go into tag slot `tag` of it, and
-    uint32_t tag;                             // the three text outputs below are NULL
-    uint32_t n_anno;                          // gams_gpu_sw_feature_summary_anno: the span sets and their per-interval groups
-    gams_spans_t *const *sets;
-    const uint32_t *const *set_group;
 };
 
 int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_t n_bytes, const char **text,
                    uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_features, uint64_t *n_rows) {
-    const std::string who = J.summary ? "gpu_sw_feature_summary" : "gpu_sw_feature_text";
+    const SwCall &call = J.call;
+    const std::string who = call.summary ? "gpu_sw_feature_summary" : "gpu_sw_feature_text";
     const uint64_t n_ctg = J.ctg_ix->m;
-    const bool do_gc = (J.actions & GAMS_SW_GC) != 0;
+    const bool do_gc = call.gc();
     *n_features = 0;
     *n_rows = 0;
-    if (!J.summary) {
+    if (!call.summary) {
         *text = "";
         *text_bytes = 0;
         memset(text_off, 0, (n_ctg + 1) * 8);
@@ -1537,9 +1530,8 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
             return GAMS_OK;
         }
         // one thread per (feature, slot), as sw_check bounds it
-        const uint64_t threads = C.n_kept * (1u + 2u * (uint64_t)J.max);
-        if ((threads + 255) / 256 > 0x7fffffffull)
-            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": too many feature slots for one launch");
+        const int rs = gams_sw_call_check(h, who, call, SWC_SLOTS, n_ctg, true, C.n_kept);
+        if (rs != GAMS_OK) return rs;
         if (do_gc)
             for (uint64_t c = 0; c < n_ctg; ++c) {
                 if (C.bucket_off[c + 1] == C.bucket_off[c]) continue;
@@ -1586,6 +1578,7 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         GAMS_TRY(h, who, stage(SWF_GATHER, false));
         // (the copy of the words must have left pin_scratch before the launcher reads back into it: same stream, in order)
         SwColsJob S{};
+        S.call = call;
         S.s = do_gc ? J.s : nullptr;
         S.n_ctg = nc;
         S.nf = K;
@@ -1597,12 +1590,6 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         S.ctg_index = J.ctg_index;
         S.chr_start = J.chr_start;
         S.chr_end = J.chr_end;
-        S.size = J.size;
-        S.max = J.max;
-        S.resize = J.resize;
-        S.actions = J.actions;
-        S.rg_ix = J.rg_ix;
-        S.rg_group = J.rg_group;
         S.igrp = g.igrp;
         S.chr_off = J.chr->t.off;
         S.chr_bytes = J.chr->t.bytes;
@@ -1611,18 +1598,26 @@ int sw_feature_run(gams_gpu_t *h, const SwFeatJob &J, const char *bytes, uint64_
         S.max_chr = J.chr->max_len;
         S.max_id = J.ids->max_len;
         S.words = g.words;
-        S.summary = J.summary;
-        S.tag = J.tag;
-        S.n_anno = J.n_anno;
-        S.sets = J.sets;
-        S.set_group = J.set_group;
         const int rc = gams_launch_sw_cols(h, S, text, text_bytes, text_off, n_rows);
         if (rc != GAMS_OK) return rc;
-        rg_timed(h, J.summary ? SWF_ROWS + 1 : SWF_STAGES);
+        rg_timed(h, call.summary ? SWF_ROWS + 1 : SWF_STAGES);
         return GAMS_OK;
     });
 }
 
+// What the feature entries test behind their own null arguments, in this order: the actions, gc without a seqset, count
+// without an index, the bounds (GAMS_EINVAL), the name tables, max beyond 2^24 (GAMS_EUNSUPPORTED) and, for a summary, the
+// accumulator and its span sets; then the run.
+int sw_feature_checked(gams_gpu_t *h, const std::string &who, const SwFeatJob &J, const char *bytes, uint64_t n_bytes,
+                       const char **text, uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_features, uint64_t *n_rows) {
+    const uint64_t m = J.ctg_ix->m;
+    int rc = gams_sw_call_check(h, who, J.call, SWC_ACTIONS | SWC_WINDOW, m, J.s && (!m || J.ctg_index));
+    if (rc != GAMS_OK) return rc;
+    if (J.ids->t.n != m) return gams_fail(h, GAMS_EINVAL, who + ": ctg_ids must name every interval of ctg_ix");
+    if (J.chr->t.n < J.ctg_ix->n_groups) return gams_fail(h, GAMS_EINVAL, who + ": chr_names must name every group of ctg_ix");
+    if ((rc = gams_sw_call_check(h, who, J.call, SWC_MAX | (J.call.summary ? SWC_SUMMARY : 0u), m)) != GAMS_OK) return rc;
+    return sw_feature_run(h, J, bytes, n_bytes, text, text_bytes, text_off, n_features, n_rows);
+}
 
 // ---- the records of `gams rg` / `gams feature` (rg.rs:40-82, feature.rs:47-96) as text -----------------------------------
 // The range loader over several files with (file, ctg) buckets (RgInput::files, by_file) and a parse kernel that also says
@@ -2515,25 +2510,12 @@ int gams_gpu_sw_feature_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_
                              int32_t resize, uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
                              const char **text, uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_features,
                              uint64_t *n_rows) {
-    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
     if (!h || !ctg_ix || !chr_names || !ctg_ids || (ctg_ix->m && (!chr_start || !chr_end)) || (n_bytes && !bytes) || !text ||
         !text_bytes || !text_off || !n_features || !n_rows)
         return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: null argument");
-    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: unknown action bits");
-    if (do_gc && (!s || (ctg_ix->m && !ctg_index)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: GAMS_SW_GC without a seqset or the ctgs' slots");
-    if (do_count && (!rg_ix || (ctg_ix->m && !rg_group)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: GAMS_SW_COUNT without an rg index or rg groups");
-    // size or resize 1: center_resize of 1 bp is an empty span (sw_check, sw.hip)
-    if (size < 2 || max < 0 || resize < 2)
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
-    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: ctg_ids must name every interval of ctg_ix");
-    if (chr_names->t.n < ctg_ix->n_groups)
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_text: chr_names must name every group of ctg_ix");
-    if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw_feature_text: max beyond 2^24 windows a side");
-    return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
-                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, nullptr, 0u, 0u, nullptr, nullptr},
-                          bytes, n_bytes, text, text_bytes, text_off, n_features, n_rows);
+    SwCall c(size, max, resize, actions, rg_ix, rg_group);
+    return sw_feature_checked(h, "gpu_sw_feature_text", SwFeatJob{c, s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end}, bytes,
+                              n_bytes, text, text_bytes, text_off, n_features, n_rows);
 }
 
 int gams_gpu_sw_feature_summary_anno(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
@@ -2542,27 +2524,17 @@ int gams_gpu_sw_feature_summary_anno(gams_gpu_t *h, gams_seqset_t *s, gams_index
                                 int32_t resize, uint32_t actions, gams_index_t *rg_ix, const uint32_t *rg_group,
                                 gams_sw_summary_t *sum, uint32_t tag, uint32_t n_anno, gams_spans_t *const *sets,
                                 const uint32_t *const *set_group, uint64_t *n_features, uint64_t *n_rows) {
-    // the checks of gams_gpu_sw_feature_text, in its order, then the accumulator's
-    const std::string who = "gpu_sw_feature_summary";
-    const bool do_gc = (actions & GAMS_SW_GC) != 0, do_count = (actions & GAMS_SW_COUNT) != 0;
     if (!h || !ctg_ix || !chr_names || !ctg_ids || (ctg_ix->m && (!chr_start || !chr_end)) || (n_bytes && !bytes) || !sum ||
         !n_features || !n_rows)
-        return gams_fail(h, GAMS_EINVAL, who + ": null argument");
-    if (actions & ~(GAMS_SW_GC | GAMS_SW_COUNT)) return gams_fail(h, GAMS_EINVAL, who + ": unknown action bits");
-    if (do_gc && (!s || (ctg_ix->m && !ctg_index)))
-        return gams_fail(h, GAMS_EINVAL, who + ": GAMS_SW_GC without a seqset or the ctgs' slots");
-    if (do_count && (!rg_ix || (ctg_ix->m && !rg_group)))
-        return gams_fail(h, GAMS_EINVAL, who + ": GAMS_SW_COUNT without an rg index or rg groups");
-    if (size < 2 || max < 0 || resize < 2)
-        return gams_fail(h, GAMS_EINVAL, who + ": size >= 2, max >= 0, resize >= 2 (center_resize of 1 bp is an empty span)");
-    if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, who + ": ctg_ids must name every interval of ctg_ix");
-    if (chr_names->t.n < ctg_ix->n_groups) return gams_fail(h, GAMS_EINVAL, who + ": chr_names must name every group of ctg_ix");
-    if (max > (1 << 24)) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": max beyond 2^24 windows a side");
-    const int rc = gams_sw_summary_check(h, who, sum, size, max, resize, actions, tag, n_anno, sets, set_group, ctg_ix->m != 0);
-    if (rc != GAMS_OK) return rc;
-    return sw_feature_run(h, SwFeatJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end, size, max, resize, actions,
-                                       do_count ? rg_ix : nullptr, do_count ? rg_group : nullptr, sum, tag, n_anno, sets, set_group},
-                          bytes, n_bytes, nullptr, nullptr, nullptr, n_features, n_rows);
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_feature_summary: null argument");
+    SwCall c(size, max, resize, actions, rg_ix, rg_group);
+    c.summary = sum;
+    c.tag = tag;
+    c.n_anno = n_anno;
+    c.sets = sets;
+    c.set_group = set_group;
+    return sw_feature_checked(h, "gpu_sw_feature_summary", SwFeatJob{c, s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end},
+                              bytes, n_bytes, nullptr, nullptr, nullptr, n_features, n_rows);
 }
 
 int gams_gpu_sw_feature_summary(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,

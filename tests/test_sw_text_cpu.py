@@ -35,6 +35,20 @@ def test_null_arguments_are_einval():
     n = C.c_uint64()
     assert lib.gams_gpu_sw_feature_text(None, None, None, None, None, None, None, None, b"I:1-2\n", 6, 100, 20, 500, 1, None,
                                         None, None, C.byref(n), None, C.byref(n), C.byref(n)) == _lib.EINVAL
+    # the batch entries and the range gc: no handle, no seqset or no outputs, refused before anything touches a device
+    # (tests/test_gpu_sw_refusals.py holds the refusals that need a handle)
+    assert lib.gams_gpu_sw_batch(None, None, 0, None, None, None, None, None, 100, 20, 500, None, 0, None, C.byref(n)) == _lib.EINVAL
+    assert lib.gams_gpu_sw_batch(None, None, 0, None, None, None, None, None, 100, 20, 500, None, 0, None, None) == _lib.EINVAL
+    assert lib.gams_gpu_sw_count_batch(None, None, 0, None, None, None, None, None, 100, 20, None, None, None, 0, None,
+                                       C.byref(n)) == _lib.EINVAL
+    text, nb = C.c_void_p(), C.c_uint64()
+    assert lib.gams_gpu_sw_text_actions(None, None, 0, None, None, None, None, None, None, None, 100, 20, 500, 1, None, None,
+                                        C.byref(text), C.byref(nb), None, C.byref(n)) == _lib.EINVAL
+    assert lib.gams_gpu_sw_text(None, None, 0, None, None, None, None, None, None, None, 100, 20, 500, None, None, None,
+                                None) == _lib.EINVAL
+    assert lib.gams_gpu_range_gc_batch(None, None, 0, None, None, None, None, None, None) == _lib.EINVAL
+    assert lib.gams_gpu_range_gc(None, None, 0, 1, None, None, 0, None) == _lib.EINVAL
+    assert lib.gams_gpu_sw(None, None, 0, 1, None, None, 0, 100, 20, 500, None, 0, None) == _lib.EINVAL
 
 
 class _NoDevice:
