@@ -149,6 +149,8 @@ PROTOTYPES = {
                                        _PP, C.POINTER(C.c_uint64), _VP, _VP, _VP, C.POINTER(C.c_uint64)]),
     "gams_gpu_peak_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _PP, C.POINTER(C.c_uint64), _VP,
                                      C.POINTER(C.c_uint64)]),
+    "gams_gpu_peak_records_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int, _VP, _PP,
+                                             C.POINTER(C.c_uint64), _VP, _VP, C.POINTER(C.c_uint64)]),
     "gams_gpu_sw_feature_text": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_uint64, C.c_int32, C.c_int32,
                                            C.c_int32, C.c_uint32, _VP, _VP, _PP, C.POINTER(C.c_uint64), _VP,
                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

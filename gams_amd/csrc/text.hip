@@ -11,6 +11,7 @@
 // and, on the loader itself (rg_load, each with a spec and a consumer of its own, which takes the kept lines as an
 // RgKept), `gams peak` (utils.rs:83-116 read_peak, then peak.rs:41-160), its rows through the keyed row writer:
 //   gams_gpu_peak_text             the bytes of one wave TSV -> the Peak rows of every ctg
+//   gams_gpu_peak_records_text     ... -> the records `gams peak` SETs: "{id}\t{json}" rows, TSV or RESP, serials behind a counter
 // and `gams sw` from a feature file (feature.rs:50-86 read_range and ids, then sw.rs:132-191):
 //   gams_gpu_sw_feature_text       the bytes of one range file -> the sw rows of its features (stages 2-5 in sw.hip)
 // and several files in one load (rg.rs:40, feature.rs:47: one read_range per file), an RgInput of files:
@@ -41,6 +42,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 #include <unordered_set>
 #include <vector>
 
@@ -68,7 +70,7 @@ struct gams_names {
 
 // The entries that own a text: each keeps the page-locked text of its last call in a slot of its own (gams_gpu.h: valid
 // until the next call of THAT entry; and a text of whole ctgs from locate --seq is not held by the others for good).
-enum TextSlot : int { TEXT_LOCATE = 0, TEXT_COUNT, TEXT_ANNO, TEXT_PEAK, TEXT_RECORDS, TEXT_SEQ, TEXT_SLOTS };
+enum TextSlot : int { TEXT_LOCATE = 0, TEXT_COUNT, TEXT_ANNO, TEXT_PEAK, TEXT_RECORDS, TEXT_SEQ, TEXT_PEAK_RECORDS, TEXT_SLOTS };
 
 // What the text entries keep on the handle: the device copy of the input (grows, cached) and the text slots.
 struct gams_text_state {
@@ -1134,6 +1136,34 @@ __global__ __launch_bounds__(256) void keyed_row_write_kernel(const typename D::
     w.flush();
 }
 
+// The same writer behind a stage the launch sizes: a description with stage_bytes(a) instead of kStage gets its stage as
+// dynamic LDS, stage_bytes(a) + 16 bytes of it (a static array ends at 64 KB; gfx950 gives a workgroup up to 160 KB).  The
+// body is keyed_row_write_kernel's, kept apart so that the kernels of the static descriptions compile as they did.
+template <typename D>
+__global__ __launch_bounds__(256) void keyed_row_write_dyn_kernel(const typename D::Args a) {
+    __shared__ uint64_t ws[4];
+    extern __shared__ __align__(16) char dyn_stage[];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    const uint64_t l = k < a.v.n_kept ? a.o.row_len[k] : 0ull;
+    BlockWriter<uint64_t> w(l, ws, a.o.blk_off, a.o.text, ~0ull);
+    w.stage_if(w.tot <= D::stage_bytes(a), dyn_stage);
+    if (k < a.v.n_kept) {
+        const uint32_t b = D::bucket(a, k);
+        if (k == (uint32_t)a.v.bucket_off[b]) a.o.text_off[b] = w.blk0 + w.rel;
+        bool bad = false;
+        w.put(w.rel, [&](char *p) {
+            RowOut<true, typename D::Len> o{p};
+            D::template row<true>(a, k, o, bad);
+        });
+    }
+    w.flush();
+}
+
+template <typename D, typename = void>
+struct KeyedDynStage : std::false_type {};
+template <typename D>
+struct KeyedDynStage<D, std::void_t<decltype(&D::stage_bytes)>> : std::true_type {};
+
 // The two stages, rows_stage and the one behind it, over the arguments `a` the consumer has filled but for o.text; the
 // text into the entry's slot, text_off (one per bucket of the load and the end) through the page-locked h_toff.
 template <typename D>
@@ -1156,8 +1186,13 @@ int keyed_text_run(gams_gpu_t *h, const std::string &who, const RgCols &C, const
     GAMS_TRY(h, who, gams_pool_grow(h, true, &T->out[slot], &T->out_cap[slot], tb, tb));
     GAMS_TRY(h, who, d_text.alloc(tb));
     a.o.text = reinterpret_cast<char *>(d_text.p);
+    if constexpr (KeyedDynStage<D>::value)
+        GAMS_TRY(h, who, gams_lds_attr(h, reinterpret_cast<const void *>(keyed_row_write_dyn_kernel<D>), D::stage_bytes(a) + 16u));
     GAMS_TRY(h, who, stage(rows_stage + 1, true));
-    hipLaunchKernelGGL(keyed_row_write_kernel<D>, dim3(nbk), dim3(256), 0, st, a);
+    if constexpr (KeyedDynStage<D>::value)
+        hipLaunchKernelGGL(keyed_row_write_dyn_kernel<D>, dim3(nbk), dim3(256), D::stage_bytes(a) + 16u, st, a);
+    else
+        hipLaunchKernelGGL(keyed_row_write_kernel<D>, dim3(nbk), dim3(256), 0, st, a);
     GAMS_TRY(h, who, stage(rows_stage + 1, false));
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, hipMemcpyAsync(T->out[slot], d_text.p, tb, hipMemcpyDeviceToHost, st));
@@ -1348,6 +1383,238 @@ struct PeakRows {
     }
 };
 
+// ---- the records `gams peak` stores (peak.rs:68-78,163-171: SET peak:{ctg_id}:{serial} serde_json(Peak)) as text --------
+// The stages of gams_gpu_peak_text up to the gc, then the keyed row writer over a second description of the same eleven
+// fields: the serial continues cnt:peak:{ctg} (sbase, the host's: one file, so a bucket is a ctg), the row is the TSV row,
+// "{id}\t{json}\n" or the RESP SET command (the formats of the rg / feature records, rec_row), and a block's rows are
+// staged in LDS the launch sizes.  The JSON is data.rs:30-43 in serde's field order, without spaces.
+struct PeakRecArgs {
+    PeakArgs pk;                              // what peak_gather_kernel and the gc fill (of its `o` only the words are used)
+    RgKept v;                                 // pk.v, where the keyed row writer looks for it
+    const uint32_t *sbase;                    // per ctg: cnt:peak:{ctg} before the load
+    int format;
+    uint32_t stage;                           // bytes of the LDS stage of this launch
+    KeyedText<unsigned long long> o;
+};
+
+// a name prefix or a signal of this many bytes is refused (RECORDS, RESP): a row's lengths stay below 2^32
+constexpr uint32_t kPeakRecMaxField = 1u << 30;
+
+// the fields of kept peak k (peak.rs:65-158, as peak_row takes them) and its serial
+struct PeakRec {
+    uint32_t c, serial, i, ip, in, s, e;      // ctg; the lines of the peak and of its neighbours (its own at a ctg's ends)
+    float g, la, ra;
+    int32_t lw, rw;
+};
+
+__device__ __forceinline__ PeakRec peak_rec(const PeakRecArgs &A, uint32_t k) {
+    const PeakArgs &a = A.pk;
+    PeakRec r;
+    r.c = a.kctg[k];
+    const uint32_t o0 = (uint32_t)a.v.bucket_off[r.c], o1 = (uint32_t)a.v.bucket_off[r.c + 1u];
+    const bool has_prev = k > o0, has_next = k + 1u < o1;
+    r.serial = A.sbase[r.c] + (k - o0) + 1u;                                          // peak.rs:71-77
+    r.i = a.kline[k];
+    r.ip = has_prev ? a.kline[k - 1u] : r.i;
+    r.in = has_next ? a.kline[k + 1u] : r.i;
+    r.s = a.ks[k];
+    r.e = a.ke[k];
+    r.g = a.gc[k];
+    r.la = fabsf(r.g - (has_prev ? a.gc[k - 1u] : r.g));
+    r.ra = fabsf(r.g - (has_next ? a.gc[k + 1u] : r.g));
+    r.lw = (int32_t)(r.s - (has_prev ? a.ke[k - 1u] : (uint32_t)a.cs[r.c]) + 1u);     // peak.rs:112-133
+    r.rw = (int32_t)((has_next ? a.ks[k + 1u] : (uint32_t)a.ce[r.c]) - r.e + 1u);     // peak.rs:135-157
+    return r;
+}
+
+template <typename Out, size_t N>
+__device__ __forceinline__ void put_lit(Out &o, const char (&s)[N]) { o.bytes(s, (uint64_t)(N - 1)); }
+
+// a length below 10^18 in decimal (four fields of up to 2^30 bytes, every byte escaped, pass 2^32)
+__device__ __forceinline__ uint32_t u64_digits(uint64_t v) {
+    return v < 1000000000ull ? dec_digits((uint32_t)v) : 9u + dec_digits((uint32_t)(v / 1000000000ull));
+}
+template <typename Out>
+__device__ __forceinline__ void put_u64(Out &o, uint64_t v) {
+    if (v < 1000000000ull) {
+        o.dec((uint32_t)v);
+        return;
+    }
+    o.dec((uint32_t)(v / 1000000000ull));
+    const uint32_t lo = (uint32_t)(v % 1000000000ull);
+    for (uint32_t p = 100000000u; p; p /= 10u) o.ch((char)('0' + lo / p % 10u));
+}
+
+// "peak:{ctg_id}:{serial}"; json: inside a JSON string
+template <bool kWrite>
+__device__ __forceinline__ void peak_rec_id(const PeakRecArgs &A, const PeakRec &r, RowOut<kWrite, uint64_t> &o, bool json) {
+    put_lit(o, "peak:");
+    const unsigned long long io = A.pk.ids.off[r.c], il = A.pk.ids.off[r.c + 1u] - io;
+    if (json)
+        o.esc(A.pk.ids.bytes + io, il);
+    else
+        o.bytes(A.pk.ids.bytes + io, il);
+    o.ch(':');
+    o.dec(r.serial);
+}
+
+// Range::to_string() with the strand cleared, as peak_row reprints it
+template <bool kWrite>
+__device__ __forceinline__ void peak_rec_range(const PeakRecArgs &A, const PeakRec &r, RowOut<kWrite, uint64_t> &o, bool json) {
+    const PeakArgs &a = A.pk;
+    if (json)
+        o.esc(a.t.in + a.t.starts[r.i], (uint64_t)a.p.nlen[r.i]);
+    else
+        o.bytes(a.t.in + a.t.starts[r.i], (uint64_t)a.p.nlen[r.i]);
+    o.bytes(a.t.in + a.p.cb[r.i], (uint64_t)a.p.clen[r.i]);
+    o.ch(':');
+    o.dec(r.s);
+    if (r.e != r.s) {
+        o.ch('-');
+        o.dec(r.e);
+    }
+}
+
+// the signal of line i
+template <bool kWrite>
+__device__ __forceinline__ void peak_rec_signal(const PeakRecArgs &A, uint32_t i, RowOut<kWrite, uint64_t> &o, bool json) {
+    if (json)
+        o.esc(A.pk.t.in + A.pk.p.sb[i], (uint64_t)A.pk.p.slen[i]);
+    else
+        o.bytes(A.pk.t.in + A.pk.p.sb[i], (uint64_t)A.pk.p.slen[i]);
+}
+
+template <bool kWrite>
+__device__ __forceinline__ void peak_rec_json(const PeakRecArgs &A, const PeakRec &r, RowOut<kWrite, uint64_t> &o, bool &bad) {
+    put_lit(o, "{\"id\":\"");
+    peak_rec_id(A, r, o, true);
+    put_lit(o, "\",\"range\":\"");
+    peak_rec_range(A, r, o, true);
+    put_lit(o, "\",\"length\":");
+    o.i32((int32_t)(r.e - r.s + 1u));
+    put_lit(o, ",\"gc\":");
+    o.f4j(r.g, bad);
+    put_lit(o, ",\"signal\":\"");
+    peak_rec_signal(A, r.i, o, true);
+    put_lit(o, "\",\"left_wave_length\":");
+    o.i32(r.lw);
+    put_lit(o, ",\"left_amplitude\":");
+    o.f32j(r.la, bad);
+    put_lit(o, ",\"left_signal\":\"");
+    peak_rec_signal(A, r.ip, o, true);
+    put_lit(o, "\",\"right_wave_length\":");
+    o.i32(r.rw);
+    put_lit(o, ",\"right_amplitude\":");
+    o.f32j(r.ra, bad);
+    put_lit(o, ",\"right_signal\":\"");
+    peak_rec_signal(A, r.in, o, true);
+    put_lit(o, "\"}");
+}
+
+template <bool kWrite>
+__device__ void peak_rec_row(const PeakRecArgs &A, uint32_t k, RowOut<kWrite, uint64_t> &o, bool &bad) {
+    const PeakRec r = peak_rec(A, k);
+    if (A.format == GAMS_LOADER_TSV) {                         // the row of peak_row but for the serial
+        peak_rec_id(A, r, o, false);
+        o.ch('\t');
+        peak_rec_range(A, r, o, false);
+        o.ch('\t');
+        o.i32((int32_t)(r.e - r.s + 1u));
+        o.ch('\t');
+        o.f4(r.g, bad);
+        o.ch('\t');
+        peak_rec_signal(A, r.i, o, false);
+        o.ch('\t');
+        o.i32(r.lw);
+        o.ch('\t');
+        o.f32s(r.la, bad);
+        o.ch('\t');
+        peak_rec_signal(A, r.ip, o, false);
+        o.ch('\t');
+        o.i32(r.rw);
+        o.ch('\t');
+        o.f32s(r.ra, bad);
+        o.ch('\t');
+        peak_rec_signal(A, r.in, o, false);
+        o.ch('\n');
+    } else if (A.format == GAMS_LOADER_RESP) {                 // wire::resp_command({"SET", id, json})
+        // The two lengths go in front of what they count.  The length pass measures the JSON with a counting RowOut (three
+        // floats formatted, every string scanned for escapes); the write pass takes it from the row's stored length instead,
+        // which is 23 + li + digits(li) + lj + digits(lj): x + digits(x) grows with x, so one lj fits.
+        RowOut<false, uint64_t> li, lj;
+        peak_rec_id(A, r, li, false);
+        if constexpr (kWrite) {
+            const uint64_t t = A.o.row_len[k] - 23u - li.n - u64_digits(li.n);
+            uint32_t d = 1u;
+            while (d < 19u && u64_digits(t - d) != d) ++d;     // (d <= 10 for a measured row; bounded whatever is stored)
+            lj.n = t - d;
+        } else {
+            bool b2 = false;                                   // (flagged where the JSON itself is counted, below)
+            peak_rec_json(A, r, lj, b2);
+        }
+        put_lit(o, "*3\r\n$3\r\nSET\r\n$");
+        put_u64(o, li.n);
+        put_lit(o, "\r\n");
+        peak_rec_id(A, r, o, false);
+        put_lit(o, "\r\n$");
+        put_u64(o, lj.n);
+        put_lit(o, "\r\n");
+        peak_rec_json(A, r, o, bad);
+        put_lit(o, "\r\n");
+    } else {                                                   // "{id}\t{json}\n"
+        peak_rec_id(A, r, o, false);
+        o.ch('\t');
+        peak_rec_json(A, r, o, bad);
+        o.ch('\n');
+    }
+}
+
+// Bytes of a block's rows staged in LDS.  256 RESP rows of ~305 B are 78 KB (RECORDS: ~270 B, 69 KB), beyond kPeakStage,
+// where every block would go byte by byte to global memory; 96 KB holds them, and a block beyond it (long names, ids or
+// signals) still takes that path.  A stage of this size leaves room for ONE workgroup per CU (160 KB of LDS a CU), four
+// waves: the write stage trades occupancy for 16-B stores, which pays for these rows and not for the TSV ones.  Those are
+// the rows of peak_text (~90 B) and keep its stage: behind the big one they are written no faster when every CU has one
+// block and 2.6 times slower when it has fifteen (profiles/peak_records.txt has both formats measured either way; the two
+// constants can be set when compiling, which is how that file was made).
+#ifndef GAMS_PEAK_REC_STAGE
+#define GAMS_PEAK_REC_STAGE 98304
+#endif
+#ifndef GAMS_PEAK_REC_TSV_STAGE
+#define GAMS_PEAK_REC_TSV_STAGE kPeakStage
+#endif
+constexpr uint32_t kPeakRecStage = GAMS_PEAK_REC_STAGE, kPeakRecTsvStage = GAMS_PEAK_REC_TSV_STAGE;
+static_assert(kPeakRecStage + 16u <= 160u * 1024u && kPeakRecTsvStage + 16u <= 160u * 1024u, "a workgroup's LDS on gfx950");
+
+// the Peak records for the keyed row writer: every kept peak has a row
+struct PeakRecRows {
+    using Args = PeakRecArgs;
+    using Len = uint64_t;
+    static __host__ __device__ __forceinline__ uint32_t stage_bytes(const Args &a) { return a.stage; }
+    template <bool kWrite>
+    static __device__ __forceinline__ void row(const Args &a, uint32_t k, RowOut<kWrite, uint64_t> &o, bool &bad) { peak_rec_row(a, k, o, bad); }
+    static __device__ __forceinline__ uint32_t bucket(const Args &a, uint32_t k) { return a.pk.kctg[k]; }
+    // RECORDS / RESP: a name prefix or signal of kPeakRecMaxField bytes, or with a control byte (serde_json writes \uXXXX and
+    // the short escapes, this writer does not).  Every neighbour is a kept line itself, so a row checks its own line only.
+    static __device__ __forceinline__ bool refused(const Args &a, uint32_t k) {
+        if (a.format == GAMS_LOADER_TSV) return false;
+        const uint32_t i = a.pk.kline[k];
+        const uint32_t nlen = a.pk.p.nlen[i], slen = a.pk.p.slen[i];
+        bool bad = nlen >= kPeakRecMaxField || slen >= kPeakRecMaxField;
+        if (!bad) {
+            const char *nm = a.pk.t.in + a.pk.t.starts[i], *sg = a.pk.t.in + a.pk.p.sb[i];
+            for (uint32_t j = 0; j < nlen; ++j) bad |= (uint8_t)nm[j] < 0x20u;
+            for (uint32_t j = 0; j < slen; ++j) bad |= (uint8_t)sg[j] < 0x20u;
+        }
+        return bad;
+    }
+    static int check(gams_gpu_t *h, const std::string &who, const unsigned long long *w) {
+        if (w[W_UNSUP] && !w[W_EID] && !w[W_ENOSEQ])
+            return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a kept line's name or signal holds a control byte or 2^30 bytes, or a gc or "
+                                                         "an amplitude the device formatters do not cover (use the host path)");
+        return PeakRows::check(h, who, w);
+    }
+};
+
 enum : int { PK_GC = RG_GATHER, PK_ROWS, PK_WRITE, PK_STAGES };   // behind the loader's lines .. order
 
 struct PeakJob {
@@ -1358,14 +1625,26 @@ struct PeakJob {
     const int32_t *chr_start, *chr_end;
 };
 
-int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_bytes, const char **text, uint64_t *text_bytes,
-             uint64_t *text_off, uint64_t *n_rows) {
-    const std::string who = "gpu_peak_text";
+// what gams_gpu_peak_records_text asks on top of the job (nullptr: the rows of gams_gpu_peak_text)
+struct PeakRecJob {
+    int format;
+    const int32_t *serial_base;
+    int32_t *serial_next;
+};
+
+int peak_run(gams_gpu_t *h, const PeakJob &J, const PeakRecJob *R, const char *bytes, uint64_t n_bytes, const char **text,
+             uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_rows) {
+    const std::string who = R ? "gpu_peak_records_text" : "gpu_peak_text";
     const uint64_t n_ctg = J.ctg_ix->m;
     *text = "";
     *text_bytes = 0;
     *n_rows = 0;
     memset(text_off, 0, (n_ctg + 1) * 8);
+    for (uint64_t c = 0; R && c < n_ctg; ++c) {
+        const int32_t base = R->serial_base ? R->serial_base[c] : 0;
+        if (base < 0) return gams_fail(h, GAMS_EINVAL, who + ": a negative serial_base");
+        if (R->serial_next) R->serial_next[c] = base;
+    }
     for (uint64_t c = 0; c < n_ctg; ++c) {
         if (J.chr_end[c] < J.chr_start[c]) return gams_fail(h, GAMS_EINVAL, who + ": a ctg ends before it starts");
         if (J.ctg_index[c] != UINT32_MAX && !seq_slot_holds(J.s, J.ctg_index[c], J.chr_start[c], J.chr_end[c]))
@@ -1383,7 +1662,7 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
     struct Tabs {
         unsigned long long *seq_off, *toff;
         int32_t *cs, *ce;
-        uint32_t *seq_len;
+        uint32_t *seq_len, *sbase;                               // sbase: the records only
     };
     auto tabs = [&](Carver &c) {
         Tabs t{};
@@ -1391,6 +1670,7 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
         t.cs = c.take<int32_t>(n_tab);
         t.ce = c.take<int32_t>(n_tab);
         t.seq_len = c.take<uint32_t>(n_tab);
+        t.sbase = c.take<uint32_t>(R ? n_tab : 0);
         t.toff = c.take<unsigned long long>(n_ctg + 1);
         return t;
     };
@@ -1404,17 +1684,24 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
         ht.seq_len[c] = slot == UINT32_MAX ? 0u : J.s->len[slot];
         ht.cs[c] = J.chr_start[c];
         ht.ce[c] = J.chr_end[c];
+        if (R) ht.sbase[c] = (uint32_t)(R->serial_base ? R->serial_base[c] : 0);
     }
-    const size_t b_in = reinterpret_cast<uint8_t *>(ht.toff) - pin.p;    // the four input columns
+    const size_t b_in = reinterpret_cast<uint8_t *>(ht.toff) - pin.p;    // the input columns
     GAMS_TRY(h, who, hipMemcpyAsync(d_tab.p, pin.p, b_in, hipMemcpyHostToDevice, st));
     PeakLoad load{J.chr->t, PeakLines{}};
     return rg_load(h, who, J.ctg_ix, load, RgInput{bytes, n_bytes, nullptr, false}, true,
                    [&](const RgCols &C, const StageClock &stage) -> int {
         // (no rg_timed on the two early ends: an input without lines, or without a kept line, leaves the stopwatch invalid)
         if (C.n_kept == 0) return GAMS_OK;
+        // the records: a serial beyond INT32_MAX is decided here, from the buckets' sizes, before anything is written
+        for (uint64_t c = 0; R && c < n_ctg; ++c) {
+            const uint64_t n = C.bucket_off[c + 1] - C.bucket_off[c];
+            if (n && (uint64_t)ht.sbase[c] + n > (uint64_t)INT32_MAX) return gams_fail(h, GAMS_EINVAL, who + ": a serial beyond INT32_MAX");
+        }
         const uint32_t K = C.v.n_kept;
         PoolBlock s2(h, false);
-        PeakArgs a{};
+        PeakRecArgs ra{};
+        PeakArgs &a = ra.pk;
         a.t = C.t;
         a.p = load.pl;
         a.v = C.v;
@@ -1430,7 +1717,10 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
             a.ks = c.take<uint32_t>(K);
             a.ke = c.take<uint32_t>(K);
             a.gc = c.take<float>(K);
-            a.o.carve(c, K);
+            if (R)
+                ra.o.carve(c, K);
+            else
+                a.o.carve(c, K);
         };
         GAMS_TRY(h, who, s2.alloc(layout_bytes(kept)));
         carve(s2.p, kept);
@@ -1438,7 +1728,19 @@ int peak_run(gams_gpu_t *h, const PeakJob &J, const char *bytes, uint64_t n_byte
         hipLaunchKernelGGL(peak_gather_kernel, dim3((K + 255u) / 256u), dim3(256), 0, st, a);
         gams_launch_range_gc_cols(J.s, dt.seq_off, dt.seq_len, dt.cs, a.kctg, a.ks, a.ke, K, a.gc, st);
         GAMS_TRY(h, who, stage(PK_GC, false));
-        return keyed_text_run<PeakRows>(h, who, C, stage, PK_ROWS, a, TEXT_PEAK, ht.toff, text, text_bytes, text_off, n_rows);
+        if (!R) return keyed_text_run<PeakRows>(h, who, C, stage, PK_ROWS, a, TEXT_PEAK, ht.toff, text, text_bytes, text_off, n_rows);
+        ra.v = a.v;
+        ra.sbase = dt.sbase;
+        ra.format = R->format;
+        ra.stage = R->format == GAMS_LOADER_TSV ? kPeakRecTsvStage : kPeakRecStage;
+        ra.o.text_off = a.o.text_off;
+        ra.o.words = a.o.words;
+        const int rc = keyed_text_run<PeakRecRows>(h, who, C, stage, PK_ROWS, ra, TEXT_PEAK_RECORDS, ht.toff, text, text_bytes, text_off,
+                                                   n_rows);
+        if (rc != GAMS_OK) return rc;
+        if (R->serial_next)
+            for (uint64_t c = 0; c < n_ctg; ++c) R->serial_next[c] = (int32_t)(ht.sbase[c] + (C.bucket_off[c + 1] - C.bucket_off[c]));
+        return GAMS_OK;
     });
 }
 
@@ -2500,7 +2802,23 @@ int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, co
         (n_bytes && !bytes) || !text || !text_bytes || !text_off || !n_rows)
         return gams_fail(h, GAMS_EINVAL, "gpu_peak_text: null argument");
     if (ctg_ids->t.n != ctg_ix->m) return gams_fail(h, GAMS_EINVAL, "gpu_peak_text: ctg_ids must name every interval of ctg_ix");
-    return peak_run(h, PeakJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end}, bytes, n_bytes, text, text_bytes,
+    return peak_run(h, PeakJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end}, nullptr, bytes, n_bytes, text, text_bytes,
+                    text_off, n_rows);
+}
+
+int gams_gpu_peak_records_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                               const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                               const int32_t *chr_end, const char *bytes, uint64_t n_bytes, int format, const int32_t *serial_base,
+                               const char **text, uint64_t *text_bytes, uint64_t *text_off, int32_t *serial_next, uint64_t *n_rows) {
+    if (!h || !s || !ctg_ix || !chr_names || !ctg_ids || (ctg_ix->m && (!ctg_index || !chr_start || !chr_end)) ||
+        (n_bytes && !bytes) || !text || !text_bytes || !text_off || !n_rows)
+        return gams_fail(h, GAMS_EINVAL, "gpu_peak_records_text: null argument");
+    if (format != GAMS_LOADER_RECORDS && format != GAMS_LOADER_TSV && format != GAMS_LOADER_RESP)
+        return gams_fail(h, GAMS_EINVAL, "gpu_peak_records_text: unknown format");
+    if (ctg_ids->t.n != ctg_ix->m)
+        return gams_fail(h, GAMS_EINVAL, "gpu_peak_records_text: ctg_ids must name every interval of ctg_ix");
+    const PeakRecJob R{format, serial_base, serial_next};
+    return peak_run(h, PeakJob{s, ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end}, &R, bytes, n_bytes, text, text_bytes,
                     text_off, n_rows);
 }
 

@@ -114,6 +114,11 @@ __device__ __forceinline__ uint32_t sw_put_f4(char *p, float v, bool *bad) {
     return n;
 }
 
+// serde_json prints an f32 through ryu: the shortest round-trip digits, always with a decimal point, positional for a
+// value that is 0 or lies in [1e-5, 1] -- there it is the text sw_put_f4 / gams_fmt_f32_short make, with ".0" behind a
+// text without a point ("0", "1": the only ones of one byte).  Nothing else is covered (-0, NaN, ryu's exponent form).
+__device__ __forceinline__ bool json_f32_covered(float v) { return __float_as_uint(v) == 0u || (v >= 1e-5f && v <= 1.0f); }
+
 // The bytes of one row.  A row is described once, as a sequence of fields put to a RowOut: RowOut<false> only adds up
 // their lengths in n, RowOut<true> writes them at q.  Len is the type of a length (a line echoed by the text entries
 // may pass 4 GB).  `bad` is set for a value that has no text of the reference's.
@@ -137,6 +142,17 @@ struct RowOut<false, Len> {
         const uint32_t l = gams_fmt_f32_short(v, nullptr);
         if (l == 0u) bad = true;
         n += l ? l : 1u;
+    }
+    // the same two values as JSON numbers (json_f32_covered)
+    __device__ __forceinline__ void f4j(float v, bool &bad) {
+        const uint32_t l = json_f32_covered(v) ? sw_put_f4(nullptr, v, &bad) : 0u;
+        if (l == 0u) bad = true;
+        n += l > 1u ? l : 3u;
+    }
+    __device__ __forceinline__ void f32j(float v, bool &bad) {
+        const uint32_t l = json_f32_covered(v) ? gams_fmt_f32_short(v, nullptr) : 0u;
+        if (l == 0u) bad = true;
+        n += l > 1u ? l : 3u;
     }
 };
 template <typename Len>
@@ -162,6 +178,16 @@ struct RowOut<true, Len> {
         const uint32_t l = gams_fmt_f32_short(v, q);
         if (l == 0u) bad = true;
         q += l ? l : 1u;
+    }
+    __device__ __forceinline__ void f4j(float v, bool &bad) {      // (a value not covered: flagged by the counting pass)
+        const uint32_t l = json_f32_covered(v) ? sw_put_f4(q, v, &bad) : 0u;
+        if (l == 1u) { q[1] = '.'; q[2] = '0'; }
+        q += l > 1u ? l : 3u;
+    }
+    __device__ __forceinline__ void f32j(float v, bool &bad) {
+        const uint32_t l = json_f32_covered(v) ? gams_fmt_f32_short(v, q) : 0u;
+        if (l == 1u) { q[1] = '.'; q[2] = '0'; }
+        q += l > 1u ? l : 3u;
     }
 };
 

@@ -195,6 +195,14 @@ def load():
     L.gams_host_peak_text.restype = C.c_void_p
     L.gams_host_peak_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
                                       C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_peak_records_text.restype = C.c_void_p
+    L.gams_host_peak_records_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p,
+                                              C.c_void_p, C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_uint64)]
+    L.gams_host_peak_rows_records.restype = C.c_void_p
+    L.gams_host_peak_rows_records.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+    L.gams_host_fmt_f32_json.restype = C.c_void_p
+    L.gams_host_fmt_f32_json.argtypes = [C.c_float]
     L.gams_host_locate_seq_text.restype = C.c_void_p
     L.gams_host_locate_seq_text.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.POINTER(C.c_void_p), C.c_void_p,
                                             C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -605,7 +613,7 @@ def anno_text(eng, ctgs, runlists, data, header=False, prefix="", idx_id=1, idx_
 
 
 def last_operator_device():
-    """1 if the last wave / wave_timed / wave_gz / locate_text / locate_seq_text / anno_text / peak_text / sw_text / gen_text of this thread made its rows on the device,
+    """1 if the last wave / wave_timed / wave_gz / locate_text / locate_seq_text / anno_text / peak_text / peak_records_text / sw_text / gen_text of this thread made its rows on the device,
     0 if it fell back to the host; after AnnoSet(...) / runlist_load: 1 if the device built the set from the bytes"""
     return int(load().gams_host_last_operator_device())
 
@@ -939,6 +947,41 @@ def peak_text(eng, ctgs, data, seqset=None):
     return _take_bytes(p, out_len)
 
 
+def peak_records_text(eng, ctgs, data, fmt="records", serial_base=None, seqset=None):
+    """What `gams peak` stores over the bytes of a wave TSV: the Peak record of every kept peak, written on the device (the
+    host's passes where it refuses; last_operator_device says which), the ctgs in id order.  fmt: "tsv" (the rows of
+    peak_text), "records" ("{id}\\t{json}\\n") or "resp" (resp_command(["SET", id, json]) of every record).  serial_base:
+    {ctg id: cnt:peak:{ctg} before the load} (absent: 0); the serials of a ctg continue behind it.  ctgs and seqset as for
+    peak_text.  -> (bytes, {ctg id: the counter after the load} for every ctg)"""
+    if fmt not in LOADER_FORMATS:
+        raise ValueError(f"peak_records_text: fmt is one of {list(LOADER_FORMATS)}")
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    base = np.array([(serial_base or {}).get(c["id"], 0) for c in ctgs], np.int32)
+    nxt = np.zeros(max(n, 1), np.int32)
+    out_len = C.c_uint64()
+    if seqset is None:
+        bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
+                                     else c["seq"]) for c in ctgs]
+        seqs, ss, slots = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs]), None, None
+    else:
+        slot = [c.get("slot", i) for i, c in enumerate(ctgs)]
+        slot = np.array([0xffffffff if k is None else k for k in slot], np.uint32)
+        seqs, ss, slots = None, seqset.p, slot.ctypes.data
+    p = load().gams_host_peak_records_text(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, ss, slots, bytes(data),
+                                           len(data), LOADER_FORMATS[fmt], base.ctypes.data if n else None, nxt.ctypes.data,
+                                           C.byref(out_len))
+    return _take_bytes(p, out_len), {c["id"]: int(v) for c, v in zip(ctgs, nxt)}
+
+
+def peak_rows_records(rows, fmt="records"):
+    """The host formatter behind peak_records_text's host route, over rows peak_text printed (ids as they stand): the
+    same records in fmt, as bytes."""
+    if fmt not in LOADER_FORMATS:
+        raise ValueError(f"peak_rows_records: fmt is one of {list(LOADER_FORMATS)}")
+    out_len = C.c_uint64()
+    return _take_bytes(load().gams_host_peak_rows_records(bytes(rows), len(rows), LOADER_FORMATS[fmt], C.byref(out_len)), out_len)
+
+
 def sw_text(eng, ctgs, data, size=100, mx=20, resize=500, actions=("gc",), rg_records=(), rg_data=None, seqset=None):
     """`gams sw` over the bytes of a feature (range) file, made on the device from the bytes to the rows (the host's
     passes where the device refuses; last_operator_device says which): the features are the kept lines of every ctg in
@@ -1131,6 +1174,12 @@ def prop4_units(p):
 def fmt_f32_short(v):
     """`{}` of an f32 in [0, 1] as the device formats a peak amplitude ("" where it refuses: NaN, outside [0, 1])"""
     return _take(load().gams_host_fmt_f32_short(v))
+
+
+def fmt_f32_json(v):
+    """An f32 as serde_json prints it where that is positional: +0 and [1e-5, 1] (the text of fmt_f32_short, ".0" behind one
+    without a point).  HostError for anything else (NaN, -0, below 1e-5, above 1)."""
+    return _take(load().gams_host_fmt_f32_json(v))
 
 
 def fmt_f32(v):

@@ -1920,76 +1920,215 @@ std::string peak_rows(const std::vector<Peak> &recs) {
     return out;
 }
 
-std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
-                      const char *bytes, size_t n, bool *device) {
-    if (device) *device = false;
-    if (!seqset || slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, "peak_text: one seqset slot per ctg");
-    Locator loc(h, ctgs);
-    loc.text_tables();
-    const size_t n_ctg = loc.ctgs_.size();
-    // per interval of the ctg index (the Locator's order): seqset slot, chr_start, chr_end
-    std::vector<uint32_t> slot(std::max<size_t>(n_ctg, 1), UINT32_MAX);
-    std::vector<int32_t> cs(std::max<size_t>(n_ctg, 1), 0), ce(std::max<size_t>(n_ctg, 1), 0);
-    for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
-    for (size_t c = 0; c < n_ctg; ++c) {
-        cs[c] = loc.ctgs_[c].chr_start;
-        ce[c] = loc.ctgs_[c].chr_end;
+// What peak_text and peak_records_text set up once for a call: the Locator with its text tables and, per interval of the
+// ctg index (the Locator's order), the seqset slot, chr_start and chr_end; and the host's passes both fall back on
+struct PeakSetup {
+    gams_gpu_t *h;
+    gams_seqset_t *seqset;
+    Locator loc;
+    size_t n_ctg;
+    std::vector<uint32_t> slot;
+    std::vector<int32_t> cs, ce;
+    PeakSetup(gams_gpu_t *h_, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset_, const std::vector<uint32_t> &slots,
+              const std::string &who)
+        : h(h_), seqset(seqset_), loc(h_, ctgs) {
+        if (!seqset || slots.size() != ctgs.size()) throw Error(GAMS_EINVAL, who + ": one seqset slot per ctg");
+        loc.text_tables();
+        n_ctg = loc.ctgs_.size();
+        slot.assign(std::max<size_t>(n_ctg, 1), UINT32_MAX);
+        cs.assign(std::max<size_t>(n_ctg, 1), 0);
+        ce.assign(std::max<size_t>(n_ctg, 1), 0);
+        for (size_t i = 0; i < ctgs.size(); ++i) slot[loc.ctg_slot_.at(ctgs[i].id)] = slots[i];
+        for (size_t c = 0; c < n_ctg; ++c) {
+            cs[c] = loc.ctgs_[c].chr_start;
+            ce[c] = loc.ctgs_[c].chr_end;
+        }
     }
-    std::vector<uint64_t> off(n_ctg + 1, 0);
-    const char *text = nullptr;
-    uint64_t text_bytes = 0, rows = 0;
-    const int rc = gams_gpu_peak_text(h, seqset, loc.ctg_ix_, loc.chr_names_, loc.ctg_ids_, slot.data(), cs.data(), ce.data(),
-                                      bytes, n, &text, &text_bytes, off.data(), &rows);
-    std::string out;
-    if (rc != GAMS_EUNSUPPORTED) {
-        check(h, rc);
-        if (device) *device = true;
+    gams_index_t *ctg_ix() const { return loc.ctg_ix_; }
+    gams_names_t *chr_names() const { return loc.chr_names_; }
+    gams_names_t *ctg_ids() const { return loc.ctg_ids_; }
+    const Ctg &ctg(size_t c) const { return loc.ctgs_[c]; }
+    // the text of a device call (rows grouped by interval, off per interval and the end) with the ctgs in id order
+    std::string by_id(const char *text, uint64_t text_bytes, const std::vector<uint64_t> &off) const {
+        std::string out;
         out.reserve((size_t)text_bytes);
-        for (auto &kv : loc.ctg_slot_)                                   // ctg-id order
-            out.append(text + off[kv.second], (size_t)(off[kv.second + 1] - off[kv.second]));
+        for (auto &kv : loc.ctg_slot_) out.append(text + off[kv.second], (size_t)(off[kv.second + 1] - off[kv.second]));
         return out;
     }
-    // the host's passes: read_peak, every bucket sorted by start (peak.rs:49), the gc of all ranges in one call
-    auto peaks_of = read_peak(loc, text_lines(bytes, n));
-    std::vector<uint32_t> sel, index;
-    std::vector<int32_t> sel_start, rs, re;
-    std::vector<uint64_t> roff{0};
-    for (auto &kv : peaks_of) {
-        auto &pv = kv.second;
-        if (pv.empty()) continue;
-        std::stable_sort(pv.begin(), pv.end(), [](const auto &a, const auto &b) { return a.first.start < b.first.start; });
-        const uint32_t c = loc.ctg_slot_.at(kv.first);
-        peak_check_inside(loc.ctgs_[c], pv);
-        if (slot[c] == UINT32_MAX) throw Error(GAMS_EINVAL, "peak_text: no sequence for " + kv.first);
-        sel.push_back(c);
-        index.push_back(slot[c]);
-        sel_start.push_back(cs[c]);
-        for (const auto &pk : pv) {
-            rs.push_back(pk.first.start);
-            re.push_back(pk.first.end);
+    // the host's passes: read_peak, every bucket sorted by start (peak.rs:49), the gc of all ranges in one call -> the
+    // Peak records (serials from 1) of every ctg with kept peaks and its interval, the ctgs in id order
+    std::vector<std::pair<uint32_t, std::vector<Peak>>> host_peaks(const char *bytes, size_t n, const std::string &who) {
+        auto peaks_of = read_peak(loc, text_lines(bytes, n));
+        std::vector<uint32_t> sel, index;
+        std::vector<int32_t> sel_start, rs, re;
+        std::vector<uint64_t> roff{0};
+        for (auto &kv : peaks_of) {
+            auto &pv = kv.second;
+            if (pv.empty()) continue;
+            std::stable_sort(pv.begin(), pv.end(), [](const auto &a, const auto &b) { return a.first.start < b.first.start; });
+            const uint32_t c = loc.ctg_slot_.at(kv.first);
+            peak_check_inside(loc.ctgs_[c], pv);
+            if (slot[c] == UINT32_MAX) throw Error(GAMS_EINVAL, who + ": no sequence for " + kv.first);
+            sel.push_back(c);
+            index.push_back(slot[c]);
+            sel_start.push_back(cs[c]);
+            for (const auto &pk : pv) {
+                rs.push_back(pk.first.start);
+                re.push_back(pk.first.end);
+            }
+            roff.push_back(rs.size());
         }
-        roff.push_back(rs.size());
+        std::vector<float> gc(std::max<size_t>(rs.size(), 1));
+        check(h, gams_gpu_range_gc_batch(h, seqset, (uint32_t)sel.size(), index.data(), sel_start.data(), roff.data(), rs.data(),
+                                         re.data(), gc.data()));
+        std::vector<std::pair<uint32_t, std::vector<Peak>>> out;
+        for (size_t k = 0; k < sel.size(); ++k)                              // (peaks_of, hence sel, is in ctg-id order)
+            out.emplace_back(sel[k], peak_fill(loc.ctgs_[sel[k]], peaks_of[loc.ctgs_[sel[k]].id], gc.data() + roff[k]));
+        return out;
     }
-    std::vector<float> gc(std::max<size_t>(rs.size(), 1));
-    check(h, gams_gpu_range_gc_batch(h, seqset, (uint32_t)sel.size(), index.data(), sel_start.data(), roff.data(), rs.data(),
-                                     re.data(), gc.data()));
-    for (size_t k = 0; k < sel.size(); ++k)                              // (peaks_of, hence sel, is in ctg-id order)
-        out += peak_rows(peak_fill(loc.ctgs_[sel[k]], peaks_of[loc.ctgs_[sel[k]].id], gc.data() + roff[k]));
-    return out;
-}
+};
 
-std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
-                      size_t n, bool *device) {
-    if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, "peak_text: ctgs / seqs size mismatch");
+// one seqset of the ctgs' bases, uploaded for a call: slot i holds ctgs[i]
+static std::vector<uint32_t> peak_upload(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                                         SeqSetGuard &sg, const std::string &who) {
+    if (ctgs.size() != seqs.size()) throw Error(GAMS_EINVAL, who + ": ctgs / seqs size mismatch");
     std::vector<uint32_t> lens(std::max<size_t>(ctgs.size(), 1), 0), slots(ctgs.size());
     for (size_t i = 0; i < ctgs.size(); ++i) {
         lens[i] = (uint32_t)(ctgs[i].chr_end - ctgs[i].chr_start + 1);
         slots[i] = (uint32_t)i;
     }
-    SeqSetGuard sg{h};
     check(h, gams_seqset_create(h, (uint32_t)ctgs.size(), lens.data(), &sg.s));
     check(h, gams_seqset_upload_all(h, sg.s, seqs.data()));
+    return slots;
+}
+
+std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                      const char *bytes, size_t n, bool *device) {
+    if (device) *device = false;
+    PeakSetup S(h, ctgs, seqset, slots, "peak_text");
+    std::vector<uint64_t> off(S.n_ctg + 1, 0);
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, rows = 0;
+    const int rc = gams_gpu_peak_text(h, seqset, S.ctg_ix(), S.chr_names(), S.ctg_ids(), S.slot.data(), S.cs.data(),
+                                      S.ce.data(), bytes, n, &text, &text_bytes, off.data(), &rows);
+    if (rc != GAMS_EUNSUPPORTED) {
+        check(h, rc);
+        if (device) *device = true;
+        return S.by_id(text, text_bytes, off);
+    }
+    std::string out;
+    for (const auto &cp : S.host_peaks(bytes, n, "peak_text")) out += peak_rows(cp.second);
+    return out;
+}
+
+std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs, const char *bytes,
+                      size_t n, bool *device) {
+    SeqSetGuard sg{h};
+    const std::vector<uint32_t> slots = peak_upload(h, ctgs, seqs, sg, "peak_text");
     return peak_text(h, ctgs, sg.s, slots, bytes, n, device);
+}
+
+std::string fmt_f32_json(float v) {
+    if (!((v == 0.0f && !std::signbit(v)) || (v >= 1e-5f && v <= 1.0f)))
+        throw Error(GAMS_EUNSUPPORTED, "fmt_f32_json: " + fmt_f32(v) + " is not 0 or in [1e-5, 1] (serde_json's exponent form is not implemented)");
+    std::string t = fmt_f32_short(v);
+    if (t.find('.') == std::string::npos) t += ".0";
+    return t;
+}
+
+std::string json_escape_serde(const std::string &v) {
+    static const char hex[] = "0123456789abcdef";
+    std::string o;
+    o.reserve(v.size());
+    for (const char ch : v) {
+        const unsigned char c = (unsigned char)ch;
+        switch (c) {
+        case '"': o += "\\\""; break;
+        case '\\': o += "\\\\"; break;
+        case '\b': o += "\\b"; break;
+        case '\t': o += "\\t"; break;
+        case '\n': o += "\\n"; break;
+        case '\f': o += "\\f"; break;
+        case '\r': o += "\\r"; break;
+        default:
+            if (c < 0x20) {
+                o += "\\u00";
+                o += hex[c >> 4];
+                o += hex[c & 15];
+            } else {
+                o += ch;
+            }
+        }
+    }
+    return o;
+}
+
+std::string peak_json(const Peak &p) {                                   // data.rs:30-43, serde's field order
+    return "{\"id\":\"" + json_escape_serde(p.id) + "\",\"range\":\"" + json_escape_serde(p.range) + "\",\"length\":" +
+           std::to_string(p.length) + ",\"gc\":" + fmt_f32_json(p.gc) + ",\"signal\":\"" + json_escape_serde(p.signal) +
+           "\",\"left_wave_length\":" + std::to_string(p.left_wave_length) + ",\"left_amplitude\":" +
+           fmt_f32_json(p.left_amplitude) + ",\"left_signal\":\"" + json_escape_serde(p.left_signal) +
+           "\",\"right_wave_length\":" + std::to_string(p.right_wave_length) + ",\"right_amplitude\":" +
+           fmt_f32_json(p.right_amplitude) + ",\"right_signal\":\"" + json_escape_serde(p.right_signal) + "\"}";
+}
+
+std::string peak_records_rows(const std::vector<Peak> &recs, int format) {
+    if (format == GAMS_LOADER_TSV) return peak_rows(recs);
+    if (format != GAMS_LOADER_RECORDS && format != GAMS_LOADER_RESP) throw Error(GAMS_EINVAL, "peak_records_rows: unknown format");
+    std::string out;
+    for (const Peak &p : recs)
+        out += format == GAMS_LOADER_RESP ? wire::resp_command({"SET", p.id, peak_json(p)}) : p.id + "\t" + peak_json(p) + "\n";
+    return out;
+}
+
+PeakRecords peak_records_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset, const std::vector<uint32_t> &slots,
+                              const char *bytes, size_t n, int format, const std::map<std::string, int32_t> &serial_base,
+                              bool *device) {
+    if (device) *device = false;
+    if (format != GAMS_LOADER_RECORDS && format != GAMS_LOADER_TSV && format != GAMS_LOADER_RESP)
+        throw Error(GAMS_EINVAL, "peak_records_text: unknown format");
+    PeakSetup S(h, ctgs, seqset, slots, "peak_records_text");
+    std::vector<int32_t> base(std::max<size_t>(S.n_ctg, 1), 0), next(std::max<size_t>(S.n_ctg, 1), 0);
+    for (size_t i = 0; i < S.n_ctg; ++i) {
+        auto it = serial_base.find(S.ctg(i).id);
+        if (it != serial_base.end()) base[i] = it->second;
+        if (base[i] < 0) throw Error(GAMS_EINVAL, "peak_records_text: a negative serial_base");
+    }
+    PeakRecords out;
+    std::vector<uint64_t> off(S.n_ctg + 1, 0);
+    const char *text = nullptr;
+    uint64_t text_bytes = 0, rows = 0;
+    const int rc = gams_gpu_peak_records_text(h, seqset, S.ctg_ix(), S.chr_names(), S.ctg_ids(), S.slot.data(),
+                                              S.cs.data(), S.ce.data(), bytes, n, format, base.data(), &text, &text_bytes,
+                                              off.data(), next.data(), &rows);
+    if (rc != GAMS_EUNSUPPORTED) {
+        check(h, rc);
+        if (device) *device = true;
+        out.text = S.by_id(text, text_bytes, off);
+        for (size_t i = 0; i < S.n_ctg; ++i) out.serial_next[S.ctg(i).id] = next[i];
+        return out;
+    }
+    // the host's passes, renumbered behind the counters
+    for (size_t i = 0; i < S.n_ctg; ++i) out.serial_next[S.ctg(i).id] = base[i];
+    for (auto &cp : S.host_peaks(bytes, n, "peak_records_text")) {
+        const Ctg &ctg = S.ctg(cp.first);
+        int64_t serial = base[cp.first];
+        for (Peak &p : cp.second) {
+            if (++serial > INT32_MAX) throw Error(GAMS_EINVAL, "peak_records_text: a serial beyond INT32_MAX");
+            p.id = "peak:" + ctg.id + ":" + std::to_string(serial);      // peak.rs:71-77
+        }
+        out.serial_next[ctg.id] = (int32_t)serial;
+        out.text += peak_records_rows(cp.second, format);
+    }
+    return out;
+}
+
+PeakRecords peak_records_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                              const char *bytes, size_t n, int format, const std::map<std::string, int32_t> &serial_base,
+                              bool *device) {
+    SeqSetGuard sg{h};
+    const std::vector<uint32_t> slots = peak_upload(h, ctgs, seqs, sg, "peak_records_text");
+    return peak_records_text(h, ctgs, sg.s, slots, bytes, n, format, serial_base, device);
 }
 
 // What sw_text and sw_summary set up once for a call: the Locator with its text tables and, under GAMS_SW_COUNT, its rg

@@ -226,9 +226,8 @@ public:
     friend LoaderText loader_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<FileBytes> &files, int kind,
                                   const std::string &tag, int format, const std::map<std::string, int32_t> &serial_base,
                                   bool *device);
-    friend std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
-                                 const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device);
-    friend struct SwSetup;                        // what sw_text and sw_summary set up once (gams_host.cpp)
+    friend struct PeakSetup;                      // what peak_text and peak_records_text set up once (gams_host.cpp)
+    friend struct SwSetup;                       // what sw_text and sw_summary set up once (gams_host.cpp)
     friend std::string sw_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                                const std::vector<uint32_t> &slots, const char *bytes, size_t n, const SwArgs &a,
                                const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes, size_t rg_n,
@@ -304,6 +303,32 @@ std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::ve
 // ctgs[i], UINT32_MAX if none does (peaks in such a ctg are an error)
 std::string peak_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
                       const std::vector<uint32_t> &slots, const char *bytes, size_t n, bool *device = nullptr);
+
+// What `gams peak` stores, not prints (peak.rs:68-78,163-171: SET peak:{ctg_id}:{serial} serde_json(Peak)): the records of
+// every ctg as text in `format` (GAMS_LOADER_TSV: the rows of peak_text; GAMS_LOADER_RECORDS: "{id}\t{json}\n";
+// GAMS_LOADER_RESP: wire::resp_command({"SET", id, json})), the ctgs in id order, made on the device
+// (gams_gpu_peak_records_text).  serial_base[ctg id] is cnt:peak:{ctg} before the load (absent: 0): the k-th kept peak of
+// a ctg in sorted order gets base + k; serial_next holds the counter of every ctg of the call afterwards.  Where the
+// device refuses (GAMS_EUNSUPPORTED: a control byte in a name or signal) the host's passes of peak_text run and
+// peak_records_rows formats; *device says which.  seqs / (seqset, slots) as for peak_text.
+struct PeakRecords {
+    std::string text;
+    std::map<std::string, int32_t> serial_next;
+};
+PeakRecords peak_records_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                              const char *bytes, size_t n, int format, const std::map<std::string, int32_t> &serial_base = {},
+                              bool *device = nullptr);
+PeakRecords peak_records_text(gams_gpu_t *h, const std::vector<Ctg> &ctgs, gams_seqset_t *seqset,
+                              const std::vector<uint32_t> &slots, const char *bytes, size_t n, int format,
+                              const std::map<std::string, int32_t> &serial_base = {}, bool *device = nullptr);
+// the host formatter of that route: the records as they stand (ids and all) in `format`
+std::string peak_records_rows(const std::vector<Peak> &recs, int format);
+// serde_json::to_string of one Peak (data.rs:30-43): field order, no spaces, strings through json_escape_serde, floats
+// through fmt_f32_json
+std::string peak_json(const Peak &p);
+// a JSON string's contents as serde_json writes them: '"' and '\' behind a backslash, \b \t \n \f \r, every other byte
+// below 0x20 as \u00xx in lower-case hex
+std::string json_escape_serde(const std::string &v);
 
 // `gams feature` + `gams sw` over the bytes of one range file (feature.rs:50-54 read_range, feature.rs:74-86 ids,
 // sw.rs:132-191 rows): the rows of every ctg, the ctgs in id order (sw.rs:97), made on the device from the bytes to the
@@ -522,6 +547,10 @@ std::vector<std::string> text_lines(const char *bytes, size_t n);
 std::string fmt_prop4(float p);
 // `{}` of an f32 in [0, 1] as the device prints a peak amplitude (csrc/text_fmt.hpp); "" where it refuses
 std::string fmt_f32_short(float v);
+// an f32 as serde_json prints it (ryu: shortest round trip, always a decimal point) where that is positional: for +0 and
+// for [1e-5, 1] the text of fmt_f32_short, with ".0" behind one without a point.  Anything else throws (the exponent
+// form is not implemented; parity with serde_json is its documented behaviour, not pinned: DESIGN.md)
+std::string fmt_f32_json(float v);
 
 // ---- wire formats either side of the path (gams_wire.cpp; SURVEY 8 f-3, parity unpinned) ----------
 namespace wire {

@@ -816,6 +816,68 @@ char *gams_host_peak_text(gams_gpu_t *h, uint32_t n, const char *const *ids, con
     });
 }
 
+// What `gams peak` stores (gams::peak_records_text): the records of every ctg in id order as text in `format`
+// (GAMS_LOADER_RECORDS / _TSV / _RESP), made on the device.  seqs / seqset / slots as for gams_host_peak_text; serial_base[i]
+// (NULL: all 0) = cnt:peak:{ctg i} before the load, serial_next[i] (may be NULL) receives the counter after it.
+char *gams_host_peak_records_text(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                                  const int32_t *ends, const uint8_t *const *seqs, gams_seqset_t *seqset, const uint32_t *slots,
+                                  const char *bytes, uint64_t n_bytes, int format, const int32_t *serial_base, int32_t *serial_next,
+                                  uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const std::vector<gams::Ctg> cv = make_ctgs(n, ids, chrs, starts, ends);
+        std::map<std::string, int32_t> base;
+        for (uint32_t i = 0; i < n && serial_base; ++i) base[ids[i]] = serial_base[i];
+        bool dev = false;
+        gams::PeakRecords r;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (seqset)
+            r = gams::peak_records_text(h, cv, seqset, std::vector<uint32_t>(slots, slots + n), bytes, (size_t)n_bytes, format, base, &dev);
+        else
+            r = gams::peak_records_text(h, cv, std::vector<const uint8_t *>(seqs, seqs + n), bytes, (size_t)n_bytes, format, base, &dev);
+        g_operator_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        g_operator_device = dev ? 1 : 0;
+        for (uint32_t i = 0; i < n && serial_next; ++i) serial_next[i] = r.serial_next.at(ids[i]);
+        return std::move(r.text);
+    });
+}
+
+// The host formatter of that operator's host route over rows `gams peak` printed (the eleven tab-separated fields of
+// gams_host_peak_text, ids as they stand): gams::peak_records_rows of them in `format`.
+char *gams_host_peak_rows_records(const char *rows, uint64_t n_bytes, int format, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        std::vector<gams::Peak> recs;
+        const std::string all(rows ? rows : "", (size_t)n_bytes);
+        for (size_t lb = 0, le; lb < all.size(); lb = le + 1) {         // rows end at '\n' and nowhere else (a signal may end in '\r')
+            le = std::min(all.find('\n', lb), all.size());
+            const std::string ln = all.substr(lb, le - lb);
+            std::vector<std::string> f;
+            size_t b = 0;
+            for (size_t t; (t = ln.find('\t', b)) != std::string::npos; b = t + 1) f.push_back(ln.substr(b, t - b));
+            f.push_back(ln.substr(b));
+            if (f.size() != 11) throw gams::Error(GAMS_EINVAL, "peak_rows_records: a row without eleven fields");
+            gams::Peak p;
+            p.id = f[0];
+            p.range = f[1];
+            p.length = (int32_t)std::stol(f[2]);
+            p.gc = std::stof(f[3]);
+            p.signal = f[4];
+            p.left_wave_length = (int32_t)std::stol(f[5]);
+            p.left_amplitude = std::stof(f[6]);
+            p.left_signal = f[7];
+            p.right_wave_length = (int32_t)std::stol(f[8]);
+            p.right_amplitude = std::stof(f[9]);
+            p.right_signal = f[10];
+            recs.push_back(std::move(p));
+        }
+        return gams::peak_records_rows(recs, format);
+    });
+}
+
+// an f32 as serde_json prints it, for +0 and [1e-5, 1] (gams::fmt_f32_json); NULL with the error set elsewhere
+char *gams_host_fmt_f32_json(float v) {
+    return guarded([&] { return gams::fmt_f32_json(v); });
+}
+
 // `gams sw` over the bytes of a feature file (bytes, n_bytes: not NUL-terminated; gams::sw_text): the rows of every ctg
 // in id order, made on the device.  seqset == NULL: seqs[i] = the bases of ctg i, uploaded for the call (seqs may be NULL
 // without GAMS_SW_GC); else the resident seqset and slots[i] = its slot of ctg i (UINT32_MAX: none), seqs unused.  The

@@ -590,6 +590,35 @@ int gams_gpu_peak_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, co
                        const int32_t *chr_end, const char *bytes, uint64_t n_bytes, const char **text,
                        uint64_t *text_bytes, uint64_t *text_off, uint64_t *n_rows);
 
+/* The records `gams peak` stores (peak.rs:68-78,163-171: SET peak:{ctg_id}:{serial} serde_json(Peak)), as text written on
+ * the device.  Inputs, checks and return codes are exactly those of gams_gpu_peak_text; format is one of GAMS_LOADER_RECORDS
+ * / _TSV / _RESP (anything else: GAMS_EINVAL):
+ *   TSV      the row of gams_gpu_peak_text, byte for byte, but for the serial;
+ *   RECORDS  "{id}\t{json}\n";
+ *   RESP     "*3\r\n$3\r\nSET\r\n${len(id)}\r\n{id}\r\n${len(json)}\r\n{json}\r\n", the lengths in bytes as written.
+ * serial_base[i] (NULL: all 0) is cnt:peak:{ctg i} before the load, i an interval of ctg_ix in the caller's order; the k-th
+ * kept peak (from 1) of ctg i in sorted order gets serial serial_base[i] + k (peak.rs:71-77); serial_next[i] (serial_next
+ * may be NULL) is the counter afterwards, the base for a ctg without kept peaks.  A negative base, or a serial beyond
+ * INT32_MAX, is GAMS_EINVAL (decided before any row is written; the handle stays usable).
+ * json = {"id":"peak:{ctg_id}:{serial}","range":"{range}","length":N,"gc":F,"signal":"S","left_wave_length":N,
+ * "left_amplitude":F,"left_signal":"S","right_wave_length":N,"right_amplitude":F,"right_signal":"S"} (data.rs:30-43, serde's
+ * field order, no spaces), the fields those of the TSV row.  Inside its strings '"' and '\' get a backslash (the ctg id, the
+ * name prefix, the signals).  A float prints as serde_json prints an f32 (ryu: shortest round trip, always a decimal point):
+ * for 0 and for [1e-5, 1] -- every gc and amplitude -- the text of the TSV row with ".0" behind one without a point ("0.0",
+ * "1.0", "0.0268").  Parity with serde_json / ryu is their documented behaviour, not pinned against a run.
+ * GAMS_EUNSUPPORTED (nothing is printed; run the host path) for what gams_gpu_peak_text refuses; in RECORDS and RESP only,
+ * for a kept line whose name prefix or signal holds a byte < 0x20 (serde_json writes \uXXXX and the short escapes) or 2^30
+ * bytes; and for a float outside the set above (NaN, -0, a nonzero value below 1e-5: ryu's exponent form).
+ * *text (text_bytes bytes, no NUL) is page-locked memory of this entry's own on the handle, valid until its next call: a
+ * text of gams_gpu_peak_text stays valid across it.  text_off (n_ctg + 1 entries), *n_rows, the grouping of the rows and
+ * the ten stages of gams_gpu_last_stage_ms as for gams_gpu_peak_text.  Two calls return identical text.  Zero bytes or no
+ * kept peak: GAMS_OK, no rows, text_off all zero, serial_next = serial_base. */
+int gams_gpu_peak_records_text(gams_gpu_t *h, gams_seqset_t *s, gams_index_t *ctg_ix, const gams_names_t *chr_names,
+                               const gams_names_t *ctg_ids, const uint32_t *ctg_index, const int32_t *chr_start,
+                               const int32_t *chr_end, const char *bytes, uint64_t n_bytes, int format,
+                               const int32_t *serial_base, const char **text, uint64_t *text_bytes,
+                               uint64_t *text_off, int32_t *serial_next, uint64_t *n_rows);
+
 /* ---- text in, text out: sw from a feature file (feature.rs:50-54 read_range, then sw.rs:132-191) ---- */
 /* The bytes of ONE range file (lines, refused bytes and limits as for the rg loader above) -> the rows `gams sw` prints
  * for the features `gams feature` would have stored from it.  ctg_ix, chr_names, ctg_ids, ctg_index, chr_start, chr_end

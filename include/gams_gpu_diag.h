@@ -27,7 +27,7 @@ int gams_gpu_last_kernel_ms(gams_gpu_t *h, float *ms);
 
 /* The stages of the last gams_gpu_read_range_text / gams_index_create_range_text call on this handle, in ms (HIP events
  * around each): lines (upload + line index), parse, locate, first, keep, offsets, order, gather, and for the index entry
- * build.  After gams_gpu_peak_text, its ten: lines, parse, locate, first, keep, offsets, order, gc (gather, checks and
+ * build.  After gams_gpu_peak_text or gams_gpu_peak_records_text, its ten: lines, parse, locate, first, keep, offsets, order, gc (gather, checks and
  * range gc), rows (row lengths and their prefix), write.  After gams_gpu_sw_feature_text, its twelve: the loader's lines ..
  * order, then gather (with the middle check), geometry (rows per feature and their prefix), rows (sw_kernel), text lengths,
  * text write (seven when no line is kept).  After gams_gpu_sw_feature_summary, its ten: the same up to rows (the
