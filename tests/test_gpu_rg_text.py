@@ -74,6 +74,10 @@ def abi_index(eng, T, data, n_ctg):
     return rc, ix, grp[:n_ctg], n.value
 
 
+def index_destroy(eng, ix):
+    L.gams_index_destroy(eng.h, ix)
+
+
 def index_of(eng, off, start, end):
     """gams_index_create over buckets given as arrays: intervals [start, end + 1)"""
     ix = C.c_void_p()

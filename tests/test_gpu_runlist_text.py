@@ -34,6 +34,27 @@ def create(eng, data):
     return rc, sp, nm, ng.value, ns.value
 
 
+def read_set(eng, sp, nm):
+    """(names, [lo per group], [hi per group]) of a set and its name table, through gams_names_read and gams_spans_read"""
+    n, nb, ns = C.c_uint32(), C.c_uint64(), C.c_uint64()
+    eng.check(L.gams_names_read(eng.h, nm, C.byref(n), C.byref(nb), None, None))
+    flat, noff = C.create_string_buffer(max(nb.value, 1)), np.zeros(n.value + 1, np.uint64)
+    eng.check(L.gams_names_read(eng.h, nm, C.byref(n), C.byref(nb), flat, noff.ctypes.data))
+    names = [flat.raw[int(noff[g]):int(noff[g + 1])].decode() for g in range(n.value)]
+    off = np.zeros(n.value + 1, np.uint64)
+    eng.check(L.gams_spans_read(eng.h, sp, off.ctypes.data, None, None, 0, C.byref(ns)))
+    lo, hi = np.zeros(max(ns.value, 1), np.int32), np.zeros(max(ns.value, 1), np.int32)
+    if ns.value:
+        eng.check(L.gams_spans_read(eng.h, sp, off.ctypes.data, lo.ctypes.data, hi.ctypes.data, ns.value, C.byref(ns)))
+    cut = lambda a: [a[int(off[g]):int(off[g + 1])].tolist() for g in range(n.value)]
+    return names, cut(lo), cut(hi)
+
+
+def destroy_set(eng, sp, nm):
+    L.gams_spans_destroy(eng.h, sp)
+    L.gams_names_destroy(eng.h, nm)
+
+
 def spans_from_arrays(eng, sets):
     off, lo, hi = rt.as_arrays(sets)
     lo, hi = np.append(lo, np.int32(0)), np.append(hi, np.int32(0))       # (never an empty buffer)

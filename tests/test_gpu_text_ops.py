@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import helpers
+from fuzz_text import assemble, fuzz_ranges
 from gams_amd import _lib, engine, host
 from test_text_ops_cpu import fmt4_exact
 
@@ -238,58 +239,6 @@ def fuzz_ctgs(rng):
             ctgs.append(dict(id=f"ctg:{chr_id}:{k + 1}", chr_id=chr_id, chr_start=pos, chr_end=pos + ln - 1, seq=b""))
             pos += ln + int(rng.integers(0, 3000))
     return ctgs
-
-
-def fuzz_ranges(rng, ctgs, n):
-    """range strings of every kind the grammar and the lookups distinguish"""
-    pick = rng.integers(0, len(ctgs), n)
-    kind = rng.integers(0, 16, n)
-    span = rng.choice([0, 1, 10, 500, 5000, 70000], n)
-    off = rng.integers(-200, 60000, n)
-    out = []
-    for p, k, w, o in zip(pick, kind, span, off):
-        c = ctgs[p]
-        s = max(1, c["chr_start"] + int(o))
-        e = s + int(w)
-        chrom = c["chr_id"]
-        if k == 0:
-            out.append(f"{chrom}:{c['chr_start']}")                       # point range on a ctg start
-        elif k == 1:
-            out.append(f"{chrom}(+):{s}-{e}")
-        elif k == 2:
-            out.append(f"nm.{chrom}(-):{s}_{e}")
-        elif k == 3:
-            out.append(f"{chrom}:{s}--_{e}")
-        elif k == 4:
-            out.append(f"chrUn:{s}-{e}")                                   # unknown chromosome
-        elif k == 5:
-            out.append(f"{chrom}:{12345678901 if o % 2 else 3000000000}-{e}")   # 11 digits / > INT32_MAX
-        elif k == 6:
-            out.append(f"{chrom}-{s}-{e}")                                 # no colon
-        elif k == 7:
-            out.append(f"{chrom}:{c['chr_end'] - 5}-{c['chr_end'] + 4000}")  # across ctgs
-        elif k == 8:
-            out.append(f"{chrom}:{s}-")
-        elif k == 9:
-            out.append(f"{chrom}:{s} ")
-        else:
-            out.append(f"{chrom}:{s}-{e}" if e != s else f"{chrom}:{s}")
-    return out
-
-
-def assemble(rng, lines, allow_empty=True):
-    """lines with \\n or \\r\\n endings, the last one without"""
-    parts = []
-    n = len(lines)
-    crlf = rng.random(n) < 0.3
-    empty = rng.random(n) < (0.02 if allow_empty else 0.0)
-    for i, ln in enumerate(lines):
-        if empty[i]:
-            parts.append("\r\n" if crlf[i] else "\n")
-        parts.append(ln)
-        if i + 1 < n:
-            parts.append("\r\n" if crlf[i] else "\n")
-    return "".join(parts).encode()
 
 
 N_FUZZ = 1_000_000
