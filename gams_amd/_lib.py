@@ -22,6 +22,8 @@ SW_SUMMARY_MAX_ANNO = 4         # GAMS_SW_SUMMARY_MAX_ANNO: the span sets (Prop 
 SW_SUMMARY_WORDS = 10           # GAMS_SW_SUMMARY_WORDS: COUNT, four S, four NaN counters, C of a summary group
 LOADER_RG, LOADER_FEATURE = 0, 1                      # gams_gpu_loader_text: kind
 LOADER_RECORDS, LOADER_TSV, LOADER_RESP = 0, 1, 2     # ... and format
+SEQ_GZ_BLOCK = 32768            # GAMS_SEQ_GZ_BLOCK: input bytes per deflate block of a `seq:` member
+SEQ_GZ_MEMBERS = 3              # GAMS_SEQ_GZ_MEMBERS: gams_gpu_seq_gz's format beside LOADER_RESP
 
 
 class GamsError(RuntimeError):
@@ -182,6 +184,11 @@ PROTOTYPES = {
     "gams_gen_ctgs": (C.c_int, [_VP, _VP, _VP]),
     "gams_gen_seqset": (C.c_int, [_VP, _VP, _PP]),
     "gams_gen_destroy": (None, [_VP, _VP]),
+    "gams_deflate_lengths": (C.c_int, [_VP, C.c_uint32, C.c_uint32, _VP]),
+    "gams_seq_gz_host": (C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gams_seq_gz_host_block": (C.c_int, [_VP, C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gams_gpu_seq_gz": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_int, _PP, C.POINTER(C.c_uint64), _VP]),
+    "gams_gpu_seq_gz_set_block": (C.c_int, [_VP, C.c_uint32]),
 }
 
 _lib = None

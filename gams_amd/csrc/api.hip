@@ -82,6 +82,7 @@ void gams_gpu_destroy(gams_gpu_t *h) {
     for (auto &e : h->rd_ev)
         if (e) (void)hipEventDestroy(e);
     gams_text_free(h);
+    gams_seq_gz_free(h);
     gams_pool_free(h, true, h->sw_text, h->sw_text_bytes);      // back to the pool, which is released below
     gams_pool_free(h, true, h->sw_words, h->sw_words_bytes);
     h->sw_text = nullptr;

@@ -65,6 +65,8 @@ struct gams_gpu {
     size_t sw_words_bytes = 0;
     // gams_gpu_locate_text / count_text / anno_text: the cached device copy of the input and each entry's last text
     struct gams_text_state *text = nullptr;
+    // gams_gpu_seq_gz: its block size and the page-locked bytes of its last call (seq_gz.hip)
+    struct gams_seq_gz_state *seq_gz = nullptr;
     // hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel FUNCTION (per device), not to a plan:
     // the largest value any launch on this handle has asked for, per function; only ever raised (gams_lds_attr)
     // counts the launches that read a seqset (any stream of the handle): gams_seqset_upload_image queues the
@@ -94,6 +96,10 @@ void gams_pool_free(gams_gpu_t *h, bool pinned, void *p, size_t cap);
 void gams_text_free(gams_gpu_t *h);
 // text.hip, for runlist.hip: the text entries' cached device copy of an input, grown to hold `bytes`
 hipError_t gams_text_input(gams_gpu_t *h, size_t bytes, uint8_t **d_in);
+// text.hip, for seq_gz.hip: a name table's device bytes -- name i is bytes[off[i] .. off[i + 1]) -- and its size
+void gams_names_view(const gams_names_t *nm, const unsigned long long **off, const char **bytes, uint32_t *n);
+// seq_gz.hip: return the entry's buffer to the pool (gams_gpu_destroy)
+void gams_seq_gz_free(gams_gpu_t *h);
 
 inline int gams_fail(gams_gpu_t *h, int code, const std::string &msg) {
     (void)hipGetLastError();   // a failed HIP call is reported through the code; it must not stay sticky

@@ -89,6 +89,12 @@ void gams_text_free(gams_gpu_t *h) {
     h->text = nullptr;
 }
 
+void gams_names_view(const gams_names_t *nm, const unsigned long long **off, const char **bytes, uint32_t *n) {
+    *off = nm->t.off;
+    *bytes = nm->t.bytes;
+    *n = nm->t.n;
+}
+
 hipError_t gams_text_input(gams_gpu_t *h, size_t bytes, uint8_t **d_in) {
     if (!h->text) h->text = new gams_text_state();
     gams_text_state *T = h->text;

@@ -146,6 +146,23 @@ class SeqSet:
             pass
 
 
+def seq_gz(eng, seqset, first, count, fmt=_lib.SEQ_GZ_MEMBERS, ctg_ids=None):
+    """gams_gpu_seq_gz: the `seq:` values of slots first .. first + count as gzip members deflated on the device (fmt
+    SEQ_GZ_MEMBERS), or their SET stream (LOADER_RESP; ctg_ids: one id per slot) -> (bytes, count + 1 offsets)"""
+    nm = C.c_void_p()
+    if ctg_ids is not None:
+        arr = (C.c_char_p * max(len(ctg_ids), 1))(*[i.encode("latin-1") for i in ctg_ids])
+        eng.check(eng.lib.gams_names_create(eng.h, len(ctg_ids), arr, C.byref(nm)))
+    try:
+        out, n = C.c_void_p(), C.c_uint64()
+        off = np.zeros(count + 1, np.uint64)
+        eng.check(eng.lib.gams_gpu_seq_gz(eng.h, seqset.p, first, count, nm, fmt, C.byref(out), C.byref(n), off.ctypes.data))
+        return C.string_at(out, n.value) if n.value else b"", off
+    finally:
+        if nm:
+            eng.lib.gams_names_destroy(eng.h, nm)
+
+
 class Index:
     """Sorted-interval index (gams_index_create): group g holds [starts, stops) of group_off[g]..group_off[g+1]."""
 

@@ -69,6 +69,10 @@ def load():
     L.gams_host_decode_gz.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.gams_host_encode_gz.restype = C.c_void_p
     L.gams_host_encode_gz.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_encode_gz_fast.restype = C.c_void_p
+    L.gams_host_encode_gz_fast.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_seq_gz.restype = C.c_void_p
+    L.gams_host_seq_gz.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, sp, C.c_void_p, C.POINTER(C.c_uint64)]
     L.gams_host_loader_records.restype = C.c_void_p
     L.gams_host_loader_records.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_char_p]
     L.gams_host_count_multi.restype = C.c_int
@@ -751,6 +755,40 @@ def encode_gz(data):
     out = C.string_at(p, n.value)
     load().gams_host_free(p)
     return out
+
+
+def encode_gz_fast(data):
+    """The `seq:` value of `data` as the literal-only gzip member the device writes for the same bases
+    (gams_seq_gz_host), for hosts that hold them; decode_gz and every gzip reader inflate it."""
+    n = C.c_uint64()
+    return _take_bytes(load().gams_host_encode_gz_fast(bytes(data), len(data), C.byref(n)), n)
+
+
+def _seq_gz(eng, seqset, first, count, ids):
+    count = len(seqset.lengths) - first if count is None else count
+    off = np.zeros(max(count, 0) + 1, np.uint64)
+    n = C.c_uint64()
+    names = None if ids is None else (C.c_char_p * max(count, 1))(*[i.encode("latin-1") for i in ids])
+    data = _take_bytes(load().gams_host_seq_gz(eng.h, seqset.p, first, count, names, off.ctypes.data, C.byref(n)), n)
+    return data, off
+
+
+def seq_gz(eng, seqset, first=0, count=None):
+    """The `seq:` values of slots first .. first + count (None: to the end) of a resident engine.SeqSet, deflated on the
+    device: a list of gzip members, one per slot."""
+    data, off = _seq_gz(eng, seqset, first, count, None)
+    return [data[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
+
+
+def seq_records(eng, seqset, ctgs, fmt="resp"):
+    """What `gams gen` stores under seq:{ctg} (redis.rs:137-140) for every ctg of gen_text's result -- slot k of
+    `seqset` is ctgs[k] --, as the SET stream resp_command(["SET", "seq:" + id, member]) of every ctg, written on the
+    device: FASTA bytes -> gen_text -> seq_records never brings a base back."""
+    if fmt != "resp":
+        raise ValueError("seq_records: fmt is 'resp'")
+    if len(ctgs) != len(seqset.lengths):
+        raise ValueError("seq_records: one ctg per slot of the seqset")
+    return _seq_gz(eng, seqset, 0, len(ctgs), [c["id"] for c in ctgs])[0]
 
 
 def loader_records(eng, ctgs, lines, tag=None):

@@ -2867,6 +2867,37 @@ std::string encode_gz(const uint8_t *bytes, size_t n) {
     return out;
 }
 
+std::string encode_gz_fast(const uint8_t *bytes, size_t n) {
+    uint64_t need = 0;
+    if (gams_seq_gz_host(bytes, n, nullptr, 0, &need) != GAMS_OK) throw Error(GAMS_EINVAL, "encode_gz_fast: bad argument");
+    std::string out((size_t)need, '\0');
+    if (gams_seq_gz_host(bytes, n, reinterpret_cast<uint8_t *>(&out[0]), need, &need) != GAMS_OK)
+        throw Error(GAMS_EINVAL, "encode_gz_fast: bad argument");
+    return out;
+}
+
+SeqGz seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count, const std::vector<std::string> *ctg_ids) {
+    struct Names {
+        gams_gpu_t *h;
+        gams_names_t *nm = nullptr;
+        ~Names() { gams_names_destroy(h, nm); }
+    } names{h};
+    if (ctg_ids) {
+        if (ctg_ids->size() != count) throw Error(GAMS_EINVAL, "seq_gz: one ctg id per slot");
+        std::vector<const char *> p(std::max<size_t>(count, 1), "");
+        for (uint32_t i = 0; i < count; ++i) p[i] = (*ctg_ids)[i].c_str();
+        check(h, gams_names_create(h, count, p.data(), &names.nm));
+    }
+    SeqGz out;
+    out.off.assign((size_t)count + 1, 0);
+    const char *bytes = nullptr;
+    uint64_t n = 0;
+    check(h, gams_gpu_seq_gz(h, seqset, first, count, names.nm, ctg_ids ? GAMS_LOADER_RESP : GAMS_SEQ_GZ_MEMBERS, &bytes, &n,
+                             out.off.data()));
+    out.bytes.assign(bytes, (size_t)n);
+    return out;
+}
+
 // ---------------------------------------------------------------------------
 // gen
 // ---------------------------------------------------------------------------

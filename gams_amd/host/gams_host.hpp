@@ -256,6 +256,18 @@ size_t decode_gz_into(const uint8_t *bytes, size_t n, uint8_t *dst, size_t cap);
 std::vector<std::string> decode_gz_many(const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len,
                                         unsigned threads = 0);
 std::string encode_gz(const uint8_t *bytes, size_t n);
+// the same value as a literal-only member (gams_seq_gz_host): what the device writes for these bases, for hosts that
+// hold them; any gzip reader, decode_gz included, inflates it
+std::string encode_gz_fast(const uint8_t *bytes, size_t n);
+// The `seq:` values of slots first .. first + count of a resident seqset, deflated on the device (gams_gpu_seq_gz): the
+// members back to back, or with ctg_ids (one per slot) the `SET seq:{id} {member}` stream of redis.rs:137-140; the bytes
+// of slot first + i are bytes[off[i] .. off[i + 1]).
+struct SeqGz {
+    std::string bytes;
+    std::vector<uint64_t> off;
+};
+SeqGz seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count,
+             const std::vector<std::string> *ctg_ids = nullptr);
 
 // src/libs/utils.rs:39-67 read_range: locate every valid range and bucket it by ctg, INCLUDING
 // the reference's quirk: `.entry(k).and_modify(push).or_default()` only creates the bucket for

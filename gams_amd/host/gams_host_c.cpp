@@ -1101,6 +1101,22 @@ char *gams_host_encode_gz(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
     }
 }
 
+char *gams_host_encode_gz_fast(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
+    return guarded(out_len, [&] { return gams::encode_gz_fast(bytes, n); });
+}
+// gams::seq_gz: the members of slots first .. first + count (ids == NULL) or their SET stream; off receives count + 1
+// offsets into the returned bytes
+char *gams_host_seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count, const char *const *ids,
+                       uint64_t *off, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        std::vector<std::string> v;
+        if (ids) v.assign(ids, ids + count);
+        gams::SeqGz g = gams::seq_gz(h, seqset, first, count, ids ? &v : nullptr);
+        std::copy(g.off.begin(), g.off.end(), off);
+        return g.bytes;
+    });
+}
+
 // utils.rs:7-22 for many ranges: one ctg id (or empty) per line
 char *gams_host_find(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
                      const int32_t *starts, const int32_t *ends, const char *rgs) {

@@ -756,6 +756,40 @@ int gams_gen_seqset(gams_gpu_t *h, gams_gen_t *g, gams_seqset_t **s);
 /* frees the tables, and the seqset if it was not handed out */
 void gams_gen_destroy(gams_gpu_t *h, gams_gen_t *g);
 
+/* ---- gen: the `seq:{ctg}` values (gen.rs:153-156 -> redis.rs:137-154 insert_seq / encode_gz) ---- */
+/* The value stored under seq:{ctg} is a gzip member of the ctg's bases.  The members made here are literal-only
+ * deflate: one dynamic-Huffman block per GAMS_SEQ_GZ_BLOCK bases, no matches, which on DNA text is smaller than what
+ * flate2 writes at Compression::fast().  Any RFC 1952 decoder inflates them to the bases (flate2, zlib, libdeflate,
+ * this project's decode_gz); the bytes are not flate2's.  A ctg of length 0 is the fixed 30-byte empty member.  The
+ * framing, the block structure and the code construction are described in gams_amd/csrc/seq_gz_code.hpp. */
+#define GAMS_SEQ_GZ_BLOCK 32768u /* input bytes per deflate block */
+#define GAMS_SEQ_GZ_MEMBERS 3    /* format, beside GAMS_LOADER_RESP: the members back to back */
+/* Code lengths of a length-limited prefix code (host code, no device involved): len[s] in 1..limit for the symbols
+ * with freq[s] != 0 among n_sym, 0 for the others; complete (Kraft sum exactly 1) for two or more used symbols, length
+ * 1 for a single one.  Integer-only and a function of the histogram alone.  GAMS_EINVAL: n_sym 0 or above 288, limit 0
+ * or above 15, more used symbols than 2^limit. */
+int gams_deflate_lengths(const uint32_t *freq, uint32_t n_sym, uint32_t limit, uint8_t *len);
+/* The member of n bases (any byte values), on the host: the very bytes gams_gpu_seq_gz writes for a slot that holds
+ * them.  *n_out = the member's bytes; cap == 0 is the size query, a cap below *n_out is GAMS_EINVAL (nothing written). */
+int gams_seq_gz_host(const uint8_t *seq, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *n_out);
+/* The members of slots first .. first + count of a resident seqset, deflated on the device; only the finished bytes
+ * cross the link.  format GAMS_SEQ_GZ_MEMBERS: the members back to back (ctg_ids may be NULL).  GAMS_LOADER_RESP:
+ * "*3\r\n$3\r\nSET\r\n${len}\r\nseq:{ctg_id}\r\n${len}\r\n{member}\r\n" per slot, ctg_ids entry i naming slot
+ * first + i, the lengths in bytes as written, the member passing through as the binary it is.  The bytes of slot
+ * first + i are out[out_off[i] .. out_off[i + 1]) (out_off has count + 1 entries, *out_bytes = out_off[count]).
+ * *out is page-locked memory of this entry's own on the handle, valid until its next call; the texts of the other
+ * entries stay valid across it.  Two calls return identical bytes.  The call waits for the uploads queued so far, as
+ * gams_seqset_download does.  count == 0: GAMS_OK, no bytes.
+ * GAMS_ESTATE: a seqset without the sequence bytes (plane-only).  GAMS_EINVAL: null arguments, a range outside the
+ * set, a format other than the two, GAMS_LOADER_RESP without ctg_ids or with fewer than count of them.
+ * GAMS_EUNSUPPORTED: more than 2^31 - 1 blocks in the range.
+ * gams_gpu_last_stage_ms then reports five stages: hist (per block, the byte histogram and the raw CRC-32 from one
+ * read of the bases), codes (per block, the code lengths, the codes and the header's bits), sizes (per ctg, the bit
+ * offset of every block, the CRC-32 joined from its blocks' and the member's length), pack (the frames, headers and
+ * trailers, then every block's bits), copy (the finished bytes to the host).  (GAMS_ESTATE for count == 0.) */
+int gams_gpu_seq_gz(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, const gams_names_t *ctg_ids,
+                    int format, const char **out, uint64_t *out_bytes, uint64_t *out_off);
+
 #ifdef __cplusplus
 }
 #endif

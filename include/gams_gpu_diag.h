@@ -137,6 +137,12 @@ int gams_wave_plan_last_cut(gams_gpu_t *h, gams_wave_plan_t *p, int *cut);
 #define GAMS_GC_BODY_PORTABLE 1
 #define GAMS_GC_BODY_AVX2 2
 int gams_gc_plane_with(const uint8_t *seq, uint64_t n, uint8_t *plane, int body);
+/* The block size of the `seq:` members, for measuring it: gams_seq_gz_host with the input bytes per deflate block
+ * named, and the size gams_gpu_seq_gz uses on this handle from now on (GAMS_SEQ_GZ_BLOCK until set).  A block size is
+ * a multiple of 4096 between 4096 and 2^24 (GAMS_EINVAL otherwise).  The device entry and the host twin agree byte
+ * for byte at every size. */
+int gams_seq_gz_host_block(const uint8_t *seq, uint64_t n, uint32_t block, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int gams_gpu_seq_gz_set_block(gams_gpu_t *h, uint32_t block);
 
 #ifdef __cplusplus
 }
