@@ -24,6 +24,9 @@ LOADER_RG, LOADER_FEATURE = 0, 1                      # gams_gpu_loader_text: ki
 LOADER_RECORDS, LOADER_TSV, LOADER_RESP = 0, 1, 2     # ... and format
 SEQ_GZ_BLOCK = 32768            # GAMS_SEQ_GZ_BLOCK: input bytes per deflate block of a `seq:` member
 SEQ_GZ_MEMBERS = 3              # GAMS_SEQ_GZ_MEMBERS: gams_gpu_seq_gz's format beside LOADER_RESP
+SEQ_GZ_INDEXED = 0x100          # GAMS_SEQ_GZ_INDEXED: ORed into either format, the members carry their chunk index
+SEQ_GZ_CHUNK = 1024             # GAMS_SEQ_GZ_CHUNK: bases per index entry
+SEQ_GZ_DONE, SEQ_GZ_FOREIGN = 0, 1      # gams_seqset_upload_gz / gams_seq_gunzip_host: the status of a value
 
 
 class GamsError(RuntimeError):
@@ -189,6 +192,13 @@ PROTOTYPES = {
     "gams_seq_gz_host_block": (C.c_int, [_VP, C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
     "gams_gpu_seq_gz": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, C.c_int, _PP, C.POINTER(C.c_uint64), _VP]),
     "gams_gpu_seq_gz_set_block": (C.c_int, [_VP, C.c_uint32]),
+    "gams_seq_gz_host_indexed": (C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gams_seq_gz_host_indexed_block": (C.c_int, [_VP, C.c_uint64, C.c_uint32, _VP, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gams_seq_gz_host_indexed_chunk": (C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_uint32, _VP, C.c_uint64,
+                                                 C.POINTER(C.c_uint64)]),
+    "gams_gpu_seq_gz_set_chunk": (C.c_int, [_VP, C.c_uint32]),
+    "gams_seq_gunzip_host": (C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "gams_seqset_upload_gz": (C.c_int, [_VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP, _VP, C.POINTER(C.c_uint32)]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@
 //   copy   the finished bytes to the handle's page-locked buffer of this entry
 #include "common.hpp"
 #include "seq_gz_code.hpp"
+#include "seq_gz_crc.hpp"
 
 #include <algorithm>
 #include <string>
@@ -29,6 +30,7 @@
 
 struct gams_seq_gz_state {
     uint32_t block = GAMS_SEQ_GZ_BLOCK;
+    uint32_t chunk = GAMS_SEQ_GZ_CHUNK;   // of the indexed members (GAMS_SEQ_GZ_INDEXED)
     char *out = nullptr;
     size_t out_cap = 0;
 };
@@ -49,13 +51,12 @@ enum : int { GZ_HIST = 0, GZ_CODES, GZ_SIZES, GZ_PACK, GZ_COPY, GZ_STAGES };
 
 constexpr uint32_t kHistCopies = 8;                  // interleaved: bin s of copy c is word s * 8 + c
 constexpr uint32_t kTabStride = 260;                 // words per block of the (length, code) tables
-constexpr uint32_t kShift16 = 512;                   // entries of the x^(128 j) table: a lane's last piece ends < 8192 bytes before its block does
 constexpr uint32_t kStageWords = (31 + kTile * 15 + 31) / 32 + 4;   // a tile's bits behind a carry of < 32, and the word they may spill into
 
-// per block of the call: where its bases are, how many, and which ctg of the call it belongs to
+// per block of the call: where its bases are, how many, which ctg of the call it belongs to and where in it it begins
 struct GzBlocks {
     const uint64_t *src;
-    const uint32_t *n, *ctg;
+    const uint32_t *n, *ctg, *at;
 };
 
 __global__ __launch_bounds__(256) void gz_hist_kernel(const uint8_t *seq, GzBlocks B, uint32_t x_gap, const uint32_t *shift16,
@@ -67,55 +68,33 @@ __global__ __launch_bounds__(256) void gz_hist_kernel(const uint8_t *seq, GzBloc
     const uint32_t tid = threadIdx.x, b = blockIdx.x;
     for (uint32_t k = 0; k < kHistCopies; ++k) cnt[tid + 256u * k] = 0;
     if (tid == 0) tail_crc = 0;
-    uint32_t t = crc_table0(tid);
-    T[0][tid] = t;
-    __syncthreads();
-    for (uint32_t k = 1; k < 4; ++k) {
-        t = (t >> 8) ^ T[0][t & 0xffu];
-        T[k][tid] = t;
-    }
-    __syncthreads();
+    crc_slices_build(T, tid);
     const uint32_t n = B.n[b], copy = tid & (kHistCopies - 1);
     const uint8_t *p = seq + B.src[b];
-    uint32_t acc = 0, end = 0;
-    bool whole = true;   // the lane's last piece had all 16 bytes
+    CrcPieces crc;   // (seq_gz_crc.hpp)
     for (uint32_t base = tid * 16u; base < n; base += kTile) {
         const uint32_t m = n - base < 16u ? n - base : 16u;
         const uint4 v = *reinterpret_cast<const uint4 *>(p + base);   // (a slot's tail may be read past: the seqset carries slack)
-        acc = gf2_mul(acc, x_gap);
+        crc.piece(T, x_gap, v, m, base);
         if (m == 16u) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const uint32_t w = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-                acc ^= w;
-                acc = T[3][acc & 0xffu] ^ T[2][(acc >> 8) & 0xffu] ^ T[1][(acc >> 16) & 0xffu] ^ T[0][acc >> 24];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) atomicAdd(&cnt[((w >> (8 * k)) & 0xffu) * kHistCopies + copy], 1u);
             }
         } else {
             const uint64_t lo = ((uint64_t)v.y << 32) | v.x, hi = ((uint64_t)v.w << 32) | v.z;
-            for (uint32_t k = 0; k < m; ++k) {
-                const uint32_t c = (uint32_t)((k < 8u ? lo >> (8u * k) : hi >> (8u * (k - 8u))) & 0xffu);
-                acc = T[0][(acc ^ c) & 0xffu] ^ (acc >> 8);
-                atomicAdd(&cnt[c * kHistCopies + copy], 1u);
-            }
-            whole = false;
+            for (uint32_t k = 0; k < m; ++k)
+                atomicAdd(&cnt[(uint32_t)((k < 8u ? lo >> (8u * k) : hi >> (8u * (k - 8u))) & 0xffu) * kHistCopies + copy], 1u);
         }
-        end = base + m;
     }
-    // every whole piece ends 16 q + (n & 15) bytes before the block does; the one short piece ends with it
-    uint32_t term = 0;
-    if (end != 0 && whole) term = gf2_mul(acc, shift16[(n - end) >> 4]);
-    if (end != 0 && !whole) tail_crc = acc;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) term ^= __shfl_xor(term, d, 64);
-    if ((tid & 63u) == 0) red[tid >> 6] = term;
-    __syncthreads();
+    const uint32_t raw = crc.finish(n, shift16, red, &tail_crc);
     uint32_t s = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kHistCopies; ++k) s += cnt[tid * kHistCopies + k];
     hist[(uint64_t)b * 256u + tid] = s;
-    if (tid == 0) blk_crc[b] = gf2_mul(red[0] ^ red[1] ^ red[2] ^ red[3], gf2_xpow8(n & 15u)) ^ tail_crc;
+    if (tid == 0) blk_crc[b] = raw;
 }
 
 __global__ __launch_bounds__(64) void gz_codes_kernel(uint32_t n_blk, const uint32_t *blk_ctg, const uint32_t *hist, uint32_t *tab,
@@ -131,7 +110,7 @@ __global__ __launch_bounds__(64) void gz_codes_kernel(uint32_t n_blk, const uint
 }
 
 // one wave per ctg of the call
-__global__ __launch_bounds__(64) void gz_sizes_kernel(const uint32_t *ctg_blk0, const uint32_t *ctg_len, uint32_t block,
+__global__ __launch_bounds__(64) void gz_sizes_kernel(const uint32_t *ctg_blk0, const uint32_t *ctg_len, uint32_t block, uint32_t chunk,
                                                        const uint64_t *blk_bits, const uint32_t *blk_crc,
                                                        const unsigned long long *id_off, uint64_t *blk_bit0, uint32_t *ctg_crc,
                                                        uint64_t *sizes) {
@@ -155,7 +134,7 @@ __global__ __launch_bounds__(64) void gz_sizes_kernel(const uint32_t *ctg_blk0, 
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) raw ^= __shfl_xor(raw, d, 64);
     if (lane == 0) {
-        const uint64_t member = kHead + (run + 7u) / 8u + kTail;
+        const uint64_t member = kHead + idx_extra(len, chunk) + (run + 7u) / 8u + kTail;   // (chunk 0: no index)
         ctg_crc[i] = crc_finish(raw, len);
         sizes[2u * i] = member;
         sizes[2u * i + 1u] = id_off ? resp_front(id_off[i + 1u] - id_off[i], member) + member + 2u : member;
@@ -175,8 +154,8 @@ __device__ __forceinline__ uint8_t *gz_put(uint8_t *p, const char *s, uint32_t n
 // one lane per ctg: everything of its bytes that is not the deflate body, and where that body begins
 __global__ __launch_bounds__(256) void gz_frames_kernel(uint32_t count, const uint64_t *out_off, const uint64_t *sizes,
                                                          const uint32_t *ctg_crc, const uint32_t *ctg_len,
-                                                         const unsigned long long *id_off, const char *id_bytes, uint8_t *out,
-                                                         uint64_t *body_bit0) {
+                                                         const unsigned long long *id_off, const char *id_bytes, uint32_t block,
+                                                         uint32_t chunk, uint8_t *out, uint64_t *body_bit0) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= count) return;
     const uint64_t member = sizes[2u * i];
@@ -193,9 +172,20 @@ __global__ __launch_bounds__(256) void gz_frames_kernel(uint32_t count, const ui
     }
     const uint8_t head[kHead] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 0xff};
     for (uint32_t k = 0; k < kHead; ++k) q[k] = head[k];
-    body_bit0[i] = 8u * (uint64_t)(q + kHead - out);
-    uint8_t *t = q + member - kTail;
     const uint32_t crc = ctg_crc[i], len = ctg_len[i];
+    const uint32_t extra = idx_extra(len, chunk);
+    if (extra) {   // the index's fixed part; the pack kernel ORs the entries into the zeros behind it
+        q[3] = 4;
+        const uint32_t xlen = extra - 2u, sub = xlen - 4u;
+        const uint8_t fixed[6] = {(uint8_t)xlen, (uint8_t)(xlen >> 8), 'G', 'I', (uint8_t)sub, (uint8_t)(sub >> 8)};
+        for (uint32_t k = 0; k < 6; ++k) q[kHead + k] = fixed[k];
+        for (uint32_t k = 0; k < 4; ++k) {
+            q[kHead + 6u + k] = (uint8_t)(block >> (8u * k));
+            q[kHead + 10u + k] = (uint8_t)(chunk >> (8u * k));
+        }
+    }
+    body_bit0[i] = 8u * (uint64_t)(q + kHead + extra - out);
+    uint8_t *t = q + member - kTail;
     for (uint32_t k = 0; k < 4; ++k) {
         t[k] = (uint8_t)(crc >> (8u * k));
         t[4u + k] = (uint8_t)(len >> (8u * k));
@@ -234,7 +224,7 @@ __device__ __forceinline__ void gz_flush(uint32_t *stage, uint32_t total, uint32
 
 __global__ __launch_bounds__(256) void gz_pack_kernel(const uint8_t *seq, GzBlocks B, const uint32_t *tab_all, const uint32_t *hdr_all,
                                                        const uint32_t *hdr_bits, const uint64_t *blk_bit0, const uint64_t *body_bit0,
-                                                       uint32_t *out) {
+                                                       const uint32_t *ctg_len, uint32_t chunk, uint32_t *out) {
     __shared__ uint32_t tab[kLit];
     __shared__ uint32_t stage[kStageWords];
     __shared__ uint32_t ws[4];
@@ -243,7 +233,10 @@ __global__ __launch_bounds__(256) void gz_pack_kernel(const uint8_t *seq, GzBloc
     for (uint32_t k = tid; k < kStageWords; k += 256u) stage[k] = 0;
     const uint32_t n = B.n[b];
     const uint8_t *p = seq + B.src[b];
-    const uint64_t bit0 = body_bit0[B.ctg[b]] + blk_bit0[b];   // of the output
+    const uint64_t body = body_bit0[B.ctg[b]], bit0 = body + blk_bit0[b];   // of the output
+    // the indexed member: a lane that begins a chunk writes that chunk's entry (chunk divides kTile and is a multiple of 16)
+    const uint32_t n_entries = chunk && idx_extra(ctg_len[B.ctg[b]], chunk) ? (uint32_t)idx_entries(ctg_len[B.ctg[b]], chunk) : 0u;
+    const bool heads_chunk = n_entries && ((tid * 16u) & (chunk - 1u)) == 0;
     uint64_t gw = bit0 >> 5;
     uint32_t carry = (uint32_t)(bit0 & 31u);
     bool head_shared = carry != 0;
@@ -272,6 +265,15 @@ __global__ __launch_bounds__(256) void gz_pack_kernel(const uint8_t *seq, GzBloc
         }
         uint32_t tile_bits = 0;
         const uint32_t pos = carry + block_excl_scan_256<uint32_t>(mine, ws, tile_bits);
+        if (heads_chunk && m) {
+            // the block's first lane names the block's first bit, every other one the first bit of its first literal; the
+            // entries lie byte-aligned in front of the body, in words that other lanes and the body's first word may share
+            const uint32_t v = base == 0 ? (uint32_t)blk_bit0[b] : (uint32_t)(gw * 32u + pos - body);
+            const uint64_t a = (body >> 3) - 4ull * n_entries + 4ull * ((B.at[b] + base) / chunk);
+            const uint32_t sh = 8u * (uint32_t)(a & 3u);
+            atomicOr(out + (a >> 2), v << sh);
+            if (sh) atomicOr(out + (a >> 2) + 1u, v >> (32u - sh));
+        }
         // the lane's bits: its first and last stage word may be shared with its neighbours, the ones between are its own
         uint32_t sw = pos >> 5, nb = pos & 31u;
         uint64_t acc = 0;
@@ -317,10 +319,10 @@ uint32_t blocks_of(uint64_t n, uint32_t per) { return (uint32_t)std::max<uint64_
 int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, const gams_names_t *ctg_ids, int format,
                const char **out, uint64_t *out_bytes, uint64_t *out_off) {
     const std::string who = "seq_gz";
-    const bool resp = format == GAMS_LOADER_RESP;
+    const bool resp = (format & ~GAMS_SEQ_GZ_INDEXED) == GAMS_LOADER_RESP;
     if (!h->seq_gz) h->seq_gz = new gams_seq_gz_state();
     gams_seq_gz_state *S = h->seq_gz;
-    const uint32_t block = S->block;
+    const uint32_t block = S->block, chunk = (format & GAMS_SEQ_GZ_INDEXED) ? S->chunk : 0u;
     h->k_valid = false;
     h->kq_used = 0;
     *out = S->out;
@@ -346,13 +348,14 @@ int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, 
     // what the host knows: the blocks, the ctgs' first blocks and lengths, the shift table of the hist kernel
     struct Desc {
         uint64_t *src;
-        uint32_t *n, *ctg, *blk0, *len, *shift16;
+        uint32_t *n, *ctg, *at, *blk0, *len, *shift16;
     };
     auto desc = [&](Carver &c) {
         Desc d{};
         d.src = c.take<uint64_t>(n_blk);
         d.n = c.take<uint32_t>(n_blk);
         d.ctg = c.take<uint32_t>(n_blk);
+        d.at = c.take<uint32_t>(n_blk);
         d.blk0 = c.take<uint32_t>((size_t)count + 1);
         d.len = c.take<uint32_t>(count);
         d.shift16 = c.take<uint32_t>(kShift16);
@@ -391,11 +394,12 @@ int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, 
             hd.src[b] = s->off[first + i] + k * block;
             hd.n[b] = (uint32_t)std::min<uint64_t>(block, len - k * block);
             hd.ctg[b] = i;
+            hd.at[b] = (uint32_t)(k * block);
         }
     }
     hd.blk0[count] = b;
-    for (uint32_t j = 0; j < kShift16; ++j) hd.shift16[j] = gf2_xpow8(16u * j);
-    const GzBlocks B{dd.src, dd.n, dd.ctg};
+    crc_shift16_fill(hd.shift16);
+    const GzBlocks B{dd.src, dd.n, dd.ctg, dd.at};
 
     h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the kernels read the sequence bytes
     const int wrc = gams_seqset_wait_uploads(h, s);
@@ -403,7 +407,7 @@ int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, 
     GAMS_TRY(h, who, hipEventRecord(h->k0, st));
     GAMS_TRY(h, who, stage(GZ_HIST, true));
     GAMS_TRY(h, who, hipMemcpyAsync(d_desc.p, pin.p, b_desc, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(gz_hist_kernel, dim3(n_blk), dim3(256), 0, st, s->d_seq, B, gf2_xpow8(kTile - 16u), dd.shift16, d_hist, d_crc);
+    hipLaunchKernelGGL(gz_hist_kernel, dim3(n_blk), dim3(256), 0, st, s->d_seq, B, crc_x_gap(), dd.shift16, d_hist, d_crc);
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, stage(GZ_HIST, false));
     GAMS_TRY(h, who, stage(GZ_CODES, true));
@@ -411,7 +415,7 @@ int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, 
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, stage(GZ_CODES, false));
     GAMS_TRY(h, who, stage(GZ_SIZES, true));
-    hipLaunchKernelGGL(gz_sizes_kernel, dim3(count), dim3(64), 0, st, dd.blk0, dd.len, block, d_bits, d_crc, id_off, d_bit0, d_ctg_crc,
+    hipLaunchKernelGGL(gz_sizes_kernel, dim3(count), dim3(64), 0, st, dd.blk0, dd.len, block, chunk, d_bits, d_crc, id_off, d_bit0, d_ctg_crc,
                        d_sizes);
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, hipMemcpyAsync(h_sizes, d_sizes, b_sizes, hipMemcpyDeviceToHost, st));
@@ -431,9 +435,9 @@ int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, 
     GAMS_TRY(h, who, hipMemcpyAsync(d_off, h_off, b_off, hipMemcpyHostToDevice, st));
     GAMS_TRY(h, who, hipMemsetAsync(d_out.p, 0, out_alloc, st));
     hipLaunchKernelGGL(gz_frames_kernel, dim3(blocks_of(count, 256)), dim3(256), 0, st, count, d_off, d_sizes, d_ctg_crc, dd.len, id_off,
-                       id_bytes, d_out.p, d_body);
+                       id_bytes, block, chunk, d_out.p, d_body);
     hipLaunchKernelGGL(gz_pack_kernel, dim3(n_blk), dim3(256), 0, st, s->d_seq, B, d_tab, d_hdr, d_hbits, d_bit0, d_body,
-                       reinterpret_cast<uint32_t *>(d_out.p));
+                       dd.len, chunk, reinterpret_cast<uint32_t *>(d_out.p));
     GAMS_TRY(h, who, hipGetLastError());
     GAMS_TRY(h, who, stage(GZ_PACK, false));
     GAMS_TRY(h, who, stage(GZ_COPY, true));
@@ -457,8 +461,9 @@ extern "C" {
 int gams_gpu_seq_gz(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, const gams_names_t *ctg_ids, int format,
                     const char **out, uint64_t *out_bytes, uint64_t *out_off) {
     if (!h || !s || !out || !out_bytes || !out_off) return gams_fail(h, GAMS_EINVAL, "seq_gz: null argument");
-    if (format != GAMS_SEQ_GZ_MEMBERS && format != GAMS_LOADER_RESP) return gams_fail(h, GAMS_EINVAL, "seq_gz: unknown format");
-    if (format == GAMS_LOADER_RESP && !ctg_ids) return gams_fail(h, GAMS_EINVAL, "seq_gz: the SET stream needs the ctg ids");
+    const int framing = format & ~GAMS_SEQ_GZ_INDEXED;   // the indexed form of either
+    if (framing != GAMS_SEQ_GZ_MEMBERS && framing != GAMS_LOADER_RESP) return gams_fail(h, GAMS_EINVAL, "seq_gz: unknown format");
+    if (framing == GAMS_LOADER_RESP && !ctg_ids) return gams_fail(h, GAMS_EINVAL, "seq_gz: the SET stream needs the ctg ids");
     if (first > s->n_ctg || count > s->n_ctg - first) return gams_fail(h, GAMS_EINVAL, "seq_gz: slots outside the seqset");
     if (!s->have_bytes) return gams_fail(h, GAMS_ESTATE, "seq_gz: the seqset holds the G/C plane only");
     return seq_gz_run(h, s, first, count, ctg_ids, format, out, out_bytes, out_off);
@@ -469,6 +474,14 @@ int gams_gpu_seq_gz_set_block(gams_gpu_t *h, uint32_t block) {
     if (!gams_gz::block_ok(block)) return gams_fail(h, GAMS_EINVAL, "seq_gz_set_block: a multiple of 4096 between 4096 and 2^24");
     if (!h->seq_gz) h->seq_gz = new gams_seq_gz_state();
     h->seq_gz->block = block;
+    return GAMS_OK;
+}
+
+int gams_gpu_seq_gz_set_chunk(gams_gpu_t *h, uint32_t chunk) {
+    if (!h) return GAMS_EINVAL;
+    if (!gams_gz::chunk_ok(chunk)) return gams_fail(h, GAMS_EINVAL, "seq_gz_set_chunk: 512, 1024, 2048 or 4096");
+    if (!h->seq_gz) h->seq_gz = new gams_seq_gz_state();
+    h->seq_gz->chunk = chunk;
     return GAMS_OK;
 }
 

@@ -37,6 +37,25 @@ constexpr uint32_t kHead = 10, kTail = 8;
 GAMS_GZ_HD inline bool block_ok(uint32_t block) { return block >= kMinBlock && block <= kMaxBlock && block % kTile == 0; }
 GAMS_GZ_HD inline uint64_t n_blocks(uint64_t n, uint32_t block) { return n ? (n + block - 1) / block : 1; }
 
+// ---- the indexed member (GAMS_SEQ_GZ_INDEXED): FLG = 4 (FEXTRA, RFC 1952 2.3.1.1), and between the ten header bytes
+// and the body
+//   XLEN (u16)   'G' 'I' LEN (u16)   block (u32)   chunk (u32)   ceil(n / chunk) bit offsets (u32)      all little-endian
+// LEN = XLEN - 4 = 8 + 4 * entries.  Entry j is relative to the first bit of the body: where j * chunk is a multiple of
+// `block` it is the BFINAL bit of the block that begins with base j * chunk, everywhere else the first bit of the
+// literal code of base j * chunk.  Body and trailer are those of the plain member, bit for bit; every gzip reader skips
+// the field.  `chunk` divides kTile and is a multiple of 16: a chunk begins with a lane of the pack kernel.  An index
+// that would not fit XLEN <= 65535 (more than kIdxMaxEntries chunks: 67,092,480 bases at chunk 4096) is not written:
+// that ctg gets the plain member.
+constexpr uint32_t kIdxFixed = 2 + 4 + 8;                      // XLEN, the subfield's head, block and chunk
+constexpr uint32_t kIdxMaxEntries = (65535u - 12u) / 4u;       // 16,380
+GAMS_GZ_HD inline bool chunk_ok(uint32_t c) { return c == 512u || c == 1024u || c == 2048u || c == 4096u; }
+GAMS_GZ_HD inline uint64_t idx_entries(uint64_t n, uint32_t chunk) { return (n + chunk - 1) / chunk; }
+// the bytes between header and body of the member of n bases: 0 without an index (chunk 0, or one that does not fit)
+GAMS_GZ_HD inline uint32_t idx_extra(uint64_t n, uint32_t chunk) {
+    if (chunk == 0 || idx_entries(n, chunk) > kIdxMaxEntries) return 0;
+    return kIdxFixed + 4u * (uint32_t)idx_entries(n, chunk);
+}
+
 // ---- CRC-32 (the reflected polynomial 0xEDB88320): bit 31 of a word is the coefficient of x^0
 constexpr uint32_t kPoly = 0xEDB88320u;
 // a * b mod P
@@ -271,5 +290,7 @@ GAMS_GZ_HD inline uint64_t resp_front(uint64_t id_bytes, uint64_t member_bytes) 
 
 }  // namespace gams_gz
 
-// the host twin with the block size as an argument (gams_seq_gz_host_block of gams_gpu_diag.h)
-int gams_seq_gz_host_with(const uint8_t *seq, uint64_t n, uint32_t block, uint8_t *out, uint64_t cap, uint64_t *n_out);
+// the host twin with the block size and the index's chunk (0: the plain member) as arguments (gams_seq_gz_host_block,
+// gams_seq_gz_host_indexed_chunk of gams_gpu_diag.h)
+int gams_seq_gz_host_with(const uint8_t *seq, uint64_t n, uint32_t block, uint32_t chunk, uint8_t *out, uint64_t cap,
+                          uint64_t *n_out);

@@ -100,6 +100,27 @@ class SeqSet:
         self.p = C.c_void_p(ptr)
         return self
 
+    @classmethod
+    def from_gz(cls, eng, blobs, threads=0):
+        """a seqset from the `seq:` values of its ctgs (gzip members; the lengths are their ISIZE fields): indexed members
+        are inflated on the device (gams_seqset_upload_gz), anything else on the host and uploaded.  self.went: how
+        many values went each way, (device, host)"""
+        import struct
+
+        from . import host
+        blobs = [bytes(b) for b in blobs]
+        for b in blobs:
+            if len(b) < 18:
+                raise ValueError("SeqSet.from_gz: not a gzip member")
+        self = cls.__new__(cls)
+        self.eng = eng
+        self.lengths = np.array([struct.unpack("<I", b[-4:])[0] for b in blobs], np.uint32)
+        p = C.c_void_p()
+        eng.check(eng.lib.gams_seqset_create(eng.h, len(blobs), self.lengths.ctypes.data, C.byref(p)))
+        self.p = p
+        self.went = host.seqset_upload_gz(eng, self, blobs, 0, threads) if blobs else (0, 0)
+        return self
+
     def download(self, i, plane=False):
         """the bases of ctg i as they lie on the device (plane=True: the ceil(len / 8) bytes of its G/C plane), as
         bytes: gams_seqset_download"""

@@ -73,6 +73,17 @@ def load():
     L.gams_host_encode_gz_fast.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     L.gams_host_seq_gz.restype = C.c_void_p
     L.gams_host_seq_gz.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, sp, C.c_void_p, C.POINTER(C.c_uint64)]
+    L.gams_host_seq_gz_indexed.restype = C.c_void_p
+    L.gams_host_seq_gz_indexed.argtypes = L.gams_host_seq_gz.argtypes
+    L.gams_host_encode_gz_indexed.restype = C.c_void_p
+    L.gams_host_encode_gz_indexed.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_decode_gz_indexed.restype = C.c_void_p
+    L.gams_host_decode_gz_indexed.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.gams_host_wave_gz_device.restype = C.c_void_p
+    L.gams_host_wave_gz_device.argtypes = L.gams_host_wave_gz.argtypes
+    L.gams_host_seqset_upload_gz.restype = C.c_int
+    L.gams_host_seqset_upload_gz.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.c_void_p,
+                                             C.c_void_p, C.c_uint32, C.c_void_p]
     L.gams_host_loader_records.restype = C.c_void_p
     L.gams_host_loader_records.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_char_p, C.c_char_p]
     L.gams_host_count_multi.restype = C.c_int
@@ -311,18 +322,23 @@ def wave_timed(eng, ctgs, size=100, step=10, lag=100, threshold=3.0, influence=1
     return _take_bytes(p, ln), _stage_dict(stages)
 
 
-def wave_gz(eng, ctgs, size=100, step=10, lag=100, threshold=3.0, influence=1.0, coverage=0.2, threads=0, sync=False):
+def wave_gz(eng, ctgs, size=100, step=10, lag=100, threshold=3.0, influence=1.0, coverage=0.2, threads=0, sync=False,
+            inflate="host"):
     """`wave` from the gzip'd `seq:` values (ctg dicts with id, chr_id, chr_start, chr_end, gz = bytes): `threads`
     host threads inflate one ctg at a time each into a page-locked image of the device buffer (0: 16)
-    -> (TSV bytes, stage clock dict)."""
+    -> (TSV bytes, stage clock dict).  inflate="device": indexed members (seq_gz(..., indexed=True)) go up as they are
+    and are inflated on the device (gams_seqset_upload_gz); the host threads inflate only what it does not take."""
+    if inflate not in ("host", "device"):
+        raise ValueError("wave_gz: inflate is 'host' or 'device'")
     n, ids, chrs, st, en = _ctg_arrays(ctgs)
     bufs = [np.frombuffer(c["gz"], np.uint8) for c in ctgs]
     blobs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
     lens = np.array([b.size for b in bufs], np.uint64)
     stages = (C.c_double * 10)()
     ln = C.c_uint64()
-    p = load().gams_host_wave_gz(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, blobs, lens.ctypes.data, size, step,
-                                 lag, threshold, influence, coverage, threads, int(sync), stages, C.byref(ln))
+    entry = load().gams_host_wave_gz_device if inflate == "device" else load().gams_host_wave_gz
+    p = entry(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, blobs, lens.ctypes.data, size, step,
+              lag, threshold, influence, coverage, threads, int(sync), stages, C.byref(ln))
     return _take_bytes(p, ln), _stage_dict(stages)
 
 
@@ -757,30 +773,58 @@ def encode_gz(data):
     return out
 
 
-def encode_gz_fast(data):
+def encode_gz_fast(data, indexed=False):
     """The `seq:` value of `data` as the literal-only gzip member the device writes for the same bases
-    (gams_seq_gz_host), for hosts that hold them; decode_gz and every gzip reader inflate it."""
+    (gams_seq_gz_host), for hosts that hold them; decode_gz and every gzip reader inflate it.  indexed: with the chunk
+    index in its FEXTRA field (gams_seq_gz_host_indexed), which the device inflater needs."""
     n = C.c_uint64()
-    return _take_bytes(load().gams_host_encode_gz_fast(bytes(data), len(data), C.byref(n)), n)
+    entry = load().gams_host_encode_gz_indexed if indexed else load().gams_host_encode_gz_fast
+    return _take_bytes(entry(bytes(data), len(data), C.byref(n)), n)
 
 
-def _seq_gz(eng, seqset, first, count, ids):
+def decode_gz_indexed(blob):
+    """An indexed member inflated by the host twin of the device inflater (gams_seq_gunzip_host: the same decoder core,
+    chunk by chunk); HostError for anything that is not an intact indexed member."""
+    n = C.c_uint64()
+    return _take_bytes(load().gams_host_decode_gz_indexed(bytes(blob), len(blob), C.byref(n)), n)
+
+
+def seqset_upload_gz(eng, seqset, blobs, first=0, threads=0):
+    """Slots first .. first + len(blobs) of an engine.SeqSet from their `seq:` values (gams::seqset_upload_gz): the
+    device inflates the indexed members, `threads` host threads (0: 16) whatever it does not take
+    -> (values inflated on the device, on the host)."""
+    n = len(blobs)
+    bufs = [np.frombuffer(bytes(b), np.uint8) for b in blobs]
+    ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data if b.size else None for b in bufs])
+    lens = np.array([b.size for b in bufs], np.uint64)
+    slot = np.ascontiguousarray(seqset.lengths[first:first + n], np.uint32)
+    if slot.size != n:
+        raise ValueError("seqset_upload_gz: slots outside the seqset")
+    went = np.zeros(2, np.uint32)
+    _check_rc(load().gams_host_seqset_upload_gz(eng.h, seqset.p, first, n, ptrs, lens.ctypes.data, slot.ctypes.data, threads,
+                                                went.ctypes.data))
+    return int(went[0]), int(went[1])
+
+
+def _seq_gz(eng, seqset, first, count, ids, indexed=False):
     count = len(seqset.lengths) - first if count is None else count
     off = np.zeros(max(count, 0) + 1, np.uint64)
     n = C.c_uint64()
     names = None if ids is None else (C.c_char_p * max(count, 1))(*[i.encode("latin-1") for i in ids])
-    data = _take_bytes(load().gams_host_seq_gz(eng.h, seqset.p, first, count, names, off.ctypes.data, C.byref(n)), n)
+    entry = load().gams_host_seq_gz_indexed if indexed else load().gams_host_seq_gz
+    data = _take_bytes(entry(eng.h, seqset.p, first, count, names, off.ctypes.data, C.byref(n)), n)
     return data, off
 
 
-def seq_gz(eng, seqset, first=0, count=None):
+def seq_gz(eng, seqset, first=0, count=None, indexed=False):
     """The `seq:` values of slots first .. first + count (None: to the end) of a resident engine.SeqSet, deflated on the
-    device: a list of gzip members, one per slot."""
-    data, off = _seq_gz(eng, seqset, first, count, None)
+    device: a list of gzip members, one per slot.  indexed: each with its chunk index (GAMS_SEQ_GZ_INDEXED), the form
+    SeqSet.from_gz and wave_gz(inflate="device") inflate on the device."""
+    data, off = _seq_gz(eng, seqset, first, count, None, indexed)
     return [data[int(off[i]):int(off[i + 1])] for i in range(len(off) - 1)]
 
 
-def seq_records(eng, seqset, ctgs, fmt="resp"):
+def seq_records(eng, seqset, ctgs, fmt="resp", indexed=False):
     """What `gams gen` stores under seq:{ctg} (redis.rs:137-140) for every ctg of gen_text's result -- slot k of
     `seqset` is ctgs[k] --, as the SET stream resp_command(["SET", "seq:" + id, member]) of every ctg, written on the
     device: FASTA bytes -> gen_text -> seq_records never brings a base back."""
@@ -788,7 +832,7 @@ def seq_records(eng, seqset, ctgs, fmt="resp"):
         raise ValueError("seq_records: fmt is 'resp'")
     if len(ctgs) != len(seqset.lengths):
         raise ValueError("seq_records: one ctg per slot of the seqset")
-    return _seq_gz(eng, seqset, 0, len(ctgs), [c["id"] for c in ctgs])[0]
+    return _seq_gz(eng, seqset, 0, len(ctgs), [c["id"] for c in ctgs], indexed)[0]
 
 
 def loader_records(eng, ctgs, lines, tag=None):

@@ -320,6 +320,7 @@ struct WaveJob {
     void bring_bytes();
     void start(const std::vector<const uint8_t *> &seqs);
     void start_gz(const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len, unsigned threads);
+    void start_gz_device(const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len, unsigned threads);
     std::vector<std::string> finish() {
         std::vector<std::string> out = finish_rows();
         consumed = true;
@@ -541,6 +542,21 @@ void WaveJob::start_gz(const std::vector<const uint8_t *> &blobs, const std::vec
     plan_and_run();
 }
 
+// The same values through the device inflater (seqset_upload_gz): bytes and plane are resident when it returns.
+void WaveJob::start_gz_device(const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len,
+                              unsigned threads) {
+    const uint32_t n = (uint32_t)ctgs.size();
+    if (n == 0) return;
+    t_mark = now_ms();
+    std::vector<uint32_t> lens(n);
+    for (uint32_t c = 0; c < n; ++c) lens[c] = (uint32_t)(ctgs[c].chr_end - ctgs[c].chr_start + 1);
+    check(h, gams_seqset_create(h, n, lens.data(), &sg.s));
+    const UploadGz went = seqset_upload_gz(h, sg.s, 0, blobs, blob_len, lens, threads);
+    if (st) st->threads = went.host ? std::max(1u, std::min(threads ? threads : 16u, went.host)) : 0;
+    mark(&WaveStages::inflate_upload_ms);
+    plan_and_run();
+}
+
 std::vector<std::string> WaveJob::finish_rows() {
     const uint32_t n = (uint32_t)ctgs.size();
     std::vector<std::string> out(n);
@@ -711,6 +727,20 @@ std::vector<std::string> wave_proc_ctgs_gz(gams_gpu_t *h, const std::vector<Ctg>
     WaveJob job(h, ctgs, a);
     job.st = stages;
     job.start_gz(blobs, blob_len, threads);
+    std::vector<std::string> out = job.finish();
+    if (stages) stages->total_ms += now_ms() - t0;
+    return out;
+}
+
+std::vector<std::string> wave_proc_ctgs_gz_device(gams_gpu_t *h, const std::vector<Ctg> &ctgs,
+                                                  const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len,
+                                                  const WaveArgs &a, unsigned threads, WaveStages *stages) {
+    if (ctgs.size() != blobs.size() || ctgs.size() != blob_len.size())
+        throw Error(GAMS_EINVAL, "wave_proc_ctgs_gz_device: ctgs/blobs size mismatch");
+    const double t0 = now_ms();
+    WaveJob job(h, ctgs, a);
+    job.st = stages;
+    job.start_gz_device(blobs, blob_len, threads);
     std::vector<std::string> out = job.finish();
     if (stages) stages->total_ms += now_ms() - t0;
     return out;
@@ -2867,16 +2897,88 @@ std::string encode_gz(const uint8_t *bytes, size_t n) {
     return out;
 }
 
-std::string encode_gz_fast(const uint8_t *bytes, size_t n) {
+std::string encode_gz_fast(const uint8_t *bytes, size_t n, bool indexed) {
+    const auto twin = indexed ? gams_seq_gz_host_indexed : gams_seq_gz_host;
     uint64_t need = 0;
-    if (gams_seq_gz_host(bytes, n, nullptr, 0, &need) != GAMS_OK) throw Error(GAMS_EINVAL, "encode_gz_fast: bad argument");
+    if (twin(bytes, n, nullptr, 0, &need) != GAMS_OK) throw Error(GAMS_EINVAL, "encode_gz_fast: bad argument");
     std::string out((size_t)need, '\0');
-    if (gams_seq_gz_host(bytes, n, reinterpret_cast<uint8_t *>(&out[0]), need, &need) != GAMS_OK)
+    if (twin(bytes, n, reinterpret_cast<uint8_t *>(&out[0]), need, &need) != GAMS_OK)
         throw Error(GAMS_EINVAL, "encode_gz_fast: bad argument");
     return out;
 }
 
-SeqGz seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count, const std::vector<std::string> *ctg_ids) {
+std::string decode_gz_indexed(const uint8_t *bytes, size_t n) {
+    // no room first: the twin checks header, subfield and trailer against one another and says how many bases the member
+    // holds (at most 16,380 chunks of 4096); only then is anything allocated
+    uint64_t got = 0;
+    int status = GAMS_SEQ_GZ_FOREIGN;
+    uint8_t spare = 0;
+    int rc = gams_seq_gunzip_host(bytes, n, &spare, 0, &got, &status);
+    std::string out;
+    if (rc == GAMS_EINVAL && bytes && got != 0) {
+        out.resize((size_t)got);
+        rc = gams_seq_gunzip_host(bytes, n, reinterpret_cast<uint8_t *>(&out[0]), out.size(), &got, &status);
+    }
+    if (rc != GAMS_OK || status != GAMS_SEQ_GZ_DONE) throw Error(GAMS_EINVAL, "decode_gz_indexed: not an intact indexed member");
+    out.resize((size_t)got);
+    return out;
+}
+
+UploadGz seqset_upload_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, const std::vector<const uint8_t *> &blobs,
+                          const std::vector<uint64_t> &blob_len, const std::vector<uint32_t> &slot_len, unsigned threads) {
+    if (blobs.size() != blob_len.size() || blobs.size() != slot_len.size()) throw Error(GAMS_EINVAL, "seqset_upload_gz: blobs/lengths size mismatch");
+    const uint32_t n = (uint32_t)blobs.size();
+    UploadGz went;
+    if (n == 0) return went;
+    std::vector<uint8_t> status(n, GAMS_SEQ_GZ_FOREIGN);
+    uint32_t n_foreign = 0;
+    check(h, gams_seqset_upload_gz(h, seqset, first, n, blobs.data(), blob_len.data(), status.data(), &n_foreign));
+    went.device = n - n_foreign;
+    went.host = n_foreign;
+    if (n_foreign == 0) return went;
+    // the host's way for what is left: inflate on the workers, upload from the calling thread as the values finish
+    std::vector<uint32_t> todo;
+    for (uint32_t i = 0; i < n; ++i)
+        if (status[i] != GAMS_SEQ_GZ_DONE) todo.push_back(i);
+    std::vector<std::string> bases(todo.size());
+    const unsigned T = std::max(1u, std::min(threads ? threads : 16u, (unsigned)todo.size()));
+    std::atomic<uint32_t> next{0};
+    std::exception_ptr err;
+    std::mutex mu;
+    auto work = [&] {
+        try {
+            for (uint32_t k = next.fetch_add(1); k < todo.size(); k = next.fetch_add(1)) {
+                const uint32_t i = todo[k];
+                if (blob_len[i] < 18) throw Error(GAMS_EINVAL, "seqset_upload_gz: value " + std::to_string(i) + " is no gzip member");
+                bases[k].resize(std::max<size_t>(slot_len[i], 1));   // (a longer value is decode_gz_into's error)
+                const size_t got = decode_gz_into(blobs[i], (size_t)blob_len[i], reinterpret_cast<uint8_t *>(&bases[k][0]), slot_len[i]);
+                bases[k].resize(got);
+            }
+        } catch (...) {
+            std::lock_guard<std::mutex> lk(mu);
+            if (!err) err = std::current_exception();
+            next.store((uint32_t)todo.size());
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned t = 1; t < T; ++t) pool.emplace_back(work);
+    work();
+    for (auto &th : pool) th.join();
+    if (err) std::rethrow_exception(err);
+    for (size_t k = 0; k < todo.size(); ++k) {
+        // (gams_seqset_upload reads the slot's length from the buffer: a value of another length is not sent)
+        if (bases[k].size() != slot_len[todo[k]])
+            throw Error(GAMS_EINVAL, "seqset_upload_gz: value " + std::to_string(todo[k]) + " inflates to " +
+                                         std::to_string(bases[k].size()) + " bases, its slot holds " + std::to_string(slot_len[todo[k]]));
+        if (!bases[k].empty())
+            check(h, gams_seqset_upload(h, seqset, first + todo[k], reinterpret_cast<const uint8_t *>(bases[k].data())));
+    }
+    check(h, gams_gpu_sync(h));   // the uploads read `bases`
+    return went;
+}
+
+SeqGz seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count, const std::vector<std::string> *ctg_ids,
+             bool indexed) {
     struct Names {
         gams_gpu_t *h;
         gams_names_t *nm = nullptr;
@@ -2892,7 +2994,7 @@ SeqGz seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t coun
     out.off.assign((size_t)count + 1, 0);
     const char *bytes = nullptr;
     uint64_t n = 0;
-    check(h, gams_gpu_seq_gz(h, seqset, first, count, names.nm, ctg_ids ? GAMS_LOADER_RESP : GAMS_SEQ_GZ_MEMBERS, &bytes, &n,
+    check(h, gams_gpu_seq_gz(h, seqset, first, count, names.nm, (ctg_ids ? GAMS_LOADER_RESP : GAMS_SEQ_GZ_MEMBERS) | (indexed ? GAMS_SEQ_GZ_INDEXED : 0), &bytes, &n,
                              out.off.data()));
     out.bytes.assign(bytes, (size_t)n);
     return out;

@@ -101,6 +101,12 @@ std::vector<std::string> wave_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &c
 std::vector<std::string> wave_proc_ctgs_gz(gams_gpu_t *h, const std::vector<Ctg> &ctgs,
                                            const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len,
                                            const WaveArgs &a, unsigned threads = 0, WaveStages *stages = nullptr);
+// The same values through the device inflater: the seqset is filled by seqset_upload_gz (below) -- indexed members are
+// uploaded as they are and inflated on the device, anything else is inflated here on `threads` threads and uploaded --
+// and the pass runs over the resident seqset.  inflate_upload_ms covers the filling.
+std::vector<std::string> wave_proc_ctgs_gz_device(gams_gpu_t *h, const std::vector<Ctg> &ctgs,
+                                                  const std::vector<const uint8_t *> &blobs, const std::vector<uint64_t> &blob_len,
+                                                  const WaveArgs &a, unsigned threads = 0, WaveStages *stages = nullptr);
 std::string wave_proc_ctg(gams_gpu_t *h, const Ctg &ctg, const uint8_t *seq, const WaveArgs &a);
 // The multi-GPU form: ctgs are split over the handles by longest-
 // processing-time-first on their window counts, one host thread per handle, each thread walks
@@ -258,7 +264,19 @@ std::vector<std::string> decode_gz_many(const std::vector<const uint8_t *> &blob
 std::string encode_gz(const uint8_t *bytes, size_t n);
 // the same value as a literal-only member (gams_seq_gz_host): what the device writes for these bases, for hosts that
 // hold them; any gzip reader, decode_gz included, inflates it
-std::string encode_gz_fast(const uint8_t *bytes, size_t n);
+// (indexed: the member with its chunk index in the FEXTRA field, gams_seq_gz_host_indexed, which the device inflates)
+std::string encode_gz_fast(const uint8_t *bytes, size_t n, bool indexed = false);
+// an indexed member inflated by the host twin of the device inflater (gams_seq_gunzip_host); anything else is an Error
+std::string decode_gz_indexed(const uint8_t *bytes, size_t n);
+// Slots first .. first + blobs.size() of a seqset from their `seq:` values: the device first (gams_seqset_upload_gz);
+// every value it leaves FOREIGN is inflated here (decode_gz_into, `threads` threads, 0: 16) and uploaded
+// (gams_seqset_upload); slot_len[i] is the length of slot first + i.  A value the host's inflate refuses too, or that
+// does not hold its slot's bases, is the Error.
+struct UploadGz {
+    uint32_t device = 0, host = 0;   // how many went each way
+};
+UploadGz seqset_upload_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, const std::vector<const uint8_t *> &blobs,
+                          const std::vector<uint64_t> &blob_len, const std::vector<uint32_t> &slot_len, unsigned threads = 0);
 // The `seq:` values of slots first .. first + count of a resident seqset, deflated on the device (gams_gpu_seq_gz): the
 // members back to back, or with ctg_ids (one per slot) the `SET seq:{id} {member}` stream of redis.rs:137-140; the bytes
 // of slot first + i are bytes[off[i] .. off[i + 1]).
@@ -266,8 +284,9 @@ struct SeqGz {
     std::string bytes;
     std::vector<uint64_t> off;
 };
+// (indexed: GAMS_SEQ_GZ_INDEXED)
 SeqGz seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count,
-             const std::vector<std::string> *ctg_ids = nullptr);
+             const std::vector<std::string> *ctg_ids = nullptr, bool indexed = false);
 
 // src/libs/utils.rs:39-67 read_range: locate every valid range and bucket it by ctg, INCLUDING
 // the reference's quirk: `.entry(k).and_modify(push).or_default()` only creates the bucket for

@@ -244,6 +244,39 @@ char *gams_host_wave_gz(gams_gpu_t *h, uint32_t n, const char *const *ids, const
     });
 }
 
+// ... through the device inflater (gams::wave_proc_ctgs_gz_device)
+char *gams_host_wave_gz_device(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs,
+                               const int32_t *starts, const int32_t *ends, const uint8_t *const *blobs,
+                               const uint64_t *blob_len, int32_t size, int32_t step, uint32_t lag, float threshold,
+                               float influence, float coverage, uint32_t threads, int sync, double *stages, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        const gams::WaveArgs a = wave_args(size, step, lag, threshold, influence, coverage, false);
+        gams::WaveStages st;
+        st.sync = sync != 0;
+        std::vector<const uint8_t *> bp(blobs, blobs + n);
+        std::vector<uint64_t> bl(blob_len, blob_len + n);
+        std::vector<std::string> rows =
+            gams::wave_proc_ctgs_gz_device(h, make_ctgs(n, ids, chrs, starts, ends), bp, bl, a, threads, &st);
+        g_operator_device = st.device_text ? 1 : 0;
+        put_stages(st, stages);
+        return join(rows);
+    });
+}
+
+// gams::seqset_upload_gz: slots first .. first + n from their `seq:` values; went[0] / went[1] receive how many the device
+// and the host inflated.  Returns 0, or -1 with the message in gams_host_last_error().
+int gams_host_seqset_upload_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t n, const uint8_t *const *blobs,
+                               const uint64_t *blob_len, const uint32_t *slot_len, uint32_t threads, uint32_t *went) {
+    return guard(-1, [&] {
+        std::vector<const uint8_t *> bp(blobs, blobs + n);
+        std::vector<uint64_t> bl(blob_len, blob_len + n);
+        std::vector<uint32_t> sl(slot_len, slot_len + n);
+        const gams::UploadGz w = gams::seqset_upload_gz(h, seqset, first, bp, bl, sl, threads);
+        if (went) went[0] = w.device, went[1] = w.host;
+        return 0;
+    });
+}
+
 // decode_gz of n values on `threads` host threads into caller buffers: dst[i] has room for dst_cap[i] bytes,
 // got[i] receives the bytes written.  Returns 0, or -1 with the message in gams_host_last_error().
 int gams_host_decode_gz_many(uint32_t n, const uint8_t *const *blobs, const uint64_t *blob_len, uint8_t *const *dst,
@@ -1104,6 +1137,13 @@ char *gams_host_encode_gz(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
 char *gams_host_encode_gz_fast(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
     return guarded(out_len, [&] { return gams::encode_gz_fast(bytes, n); });
 }
+// ... with the chunk index (gams_seq_gz_host_indexed), and the host twin of the device inflater for such a member
+char *gams_host_encode_gz_indexed(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
+    return guarded(out_len, [&] { return gams::encode_gz_fast(bytes, n, true); });
+}
+char *gams_host_decode_gz_indexed(const uint8_t *bytes, uint64_t n, uint64_t *out_len) {
+    return guarded(out_len, [&] { return gams::decode_gz_indexed(bytes, n); });
+}
 // gams::seq_gz: the members of slots first .. first + count (ids == NULL) or their SET stream; off receives count + 1
 // offsets into the returned bytes
 char *gams_host_seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count, const char *const *ids,
@@ -1112,6 +1152,17 @@ char *gams_host_seq_gz(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uin
         std::vector<std::string> v;
         if (ids) v.assign(ids, ids + count);
         gams::SeqGz g = gams::seq_gz(h, seqset, first, count, ids ? &v : nullptr);
+        std::copy(g.off.begin(), g.off.end(), off);
+        return g.bytes;
+    });
+}
+// ... the indexed form of either (GAMS_SEQ_GZ_INDEXED)
+char *gams_host_seq_gz_indexed(gams_gpu_t *h, gams_seqset_t *seqset, uint32_t first, uint32_t count, const char *const *ids,
+                               uint64_t *off, uint64_t *out_len) {
+    return guarded(out_len, [&] {
+        std::vector<std::string> v;
+        if (ids) v.assign(ids, ids + count);
+        gams::SeqGz g = gams::seq_gz(h, seqset, first, count, ids ? &v : nullptr, true);
         std::copy(g.off.begin(), g.off.end(), off);
         return g.bytes;
     });

@@ -790,6 +790,47 @@ int gams_seq_gz_host(const uint8_t *seq, uint64_t n, uint8_t *out, uint64_t cap,
 int gams_gpu_seq_gz(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, const gams_names_t *ctg_ids,
                     int format, const char **out, uint64_t *out_bytes, uint64_t *out_off);
 
+/* ---- the `seq:{ctg}` values back into a seqset: indexed members, inflated on the device ---- */
+/* GAMS_SEQ_GZ_INDEXED, ORed into `format` of gams_gpu_seq_gz (either format), writes the indexed form of the members:
+ * FLG = 4 and, in the FEXTRA field (RFC 1952 2.3.1.1, which every gzip reader skips), one subfield 'G' 'I' holding
+ * u32 block, u32 chunk and ceil(n / chunk) u32 bit offsets into the deflate body, all little-endian: entry j is the
+ * BFINAL bit of the block that begins with base j * chunk where j * chunk is a multiple of `block`, the first bit of
+ * that base's literal code everywhere else.  Body and trailer are the plain member's, bit for bit; without the flag
+ * every byte is what it was.  The index costs 4 bytes per GAMS_SEQ_GZ_CHUNK bases.  A ctg whose index would not fit
+ * XLEN <= 65535 (more than 16,380 chunks) gets the plain member: the indexed writers never fail for size.
+ * (gams_amd/csrc/seq_gz_code.hpp has the layout.) */
+#define GAMS_SEQ_GZ_INDEXED 0x100
+#define GAMS_SEQ_GZ_CHUNK 1024u /* bases per index entry */
+/* host twin of the indexed writer: the very bytes gams_gpu_seq_gz writes with GAMS_SEQ_GZ_INDEXED (sized like
+ * gams_seq_gz_host) */
+int gams_seq_gz_host_indexed(const uint8_t *seq, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *n_out);
+#define GAMS_SEQ_GZ_DONE 0    /* slot holds the bases and their plane */
+#define GAMS_SEQ_GZ_FOREIGN 1 /* not taken: the host inflates this value and uploads it */
+/* Host twin of the device inflater: the same decoder core, chunk by chunk on one core.  *status = GAMS_SEQ_GZ_DONE and
+ * out[0, *n_out) the bases, or GAMS_SEQ_GZ_FOREIGN (*n_out = 0 where the header, subfield and trailer already disagree)
+ * for anything that is not an intact indexed member; nothing in the member is trusted and no byte outside
+ * [member, member + n_bytes) is read.  GAMS_EINVAL: null arguments, or a member that passed the O(1) checks and whose
+ * ISIZE (then in *n_out) exceeds cap. */
+int gams_seq_gunzip_host(const uint8_t *member, uint64_t n_bytes, uint8_t *out, uint64_t cap, uint64_t *n_out, int *status);
+/* Slots first .. first + count of a seqset from their `seq:` values: members[i] / member_bytes[i] is the value of slot
+ * first + i.  Indexed members with a chunk of 512, 1024, 2048 or 4096 and a block of 4096 .. 65,536 (a multiple of
+ * 4096; larger blocks are refused: a block is staged in LDS) are uploaded as they are -- a third of the bases -- and
+ * inflated on the device straight into their slots, bases and G/C plane; CRC-32 and ISIZE are verified.  status[i] is
+ * GAMS_SEQ_GZ_DONE, or GAMS_SEQ_GZ_FOREIGN for a value the device does not take (*n_foreign counts them): plain or
+ * foreign gzip (matches, stored blocks), anything damaged.  A value refused by the O(1) checks of its header,
+ * subfield and trailer is not uploaded and its slot is not touched; one refused on the device (a chunk that does not
+ * land on the next entry, a bad code, a CRC mismatch) leaves its slot's content unspecified.  No byte outside a taken
+ * slot and its plane bytes is written.  The caller inflates FOREIGN values itself (gams_seqset_upload).
+ * The call queues behind every pass already reading the seqset and returns when the statuses are known; later passes
+ * wait for it like for an upload.  The plane stays valid if it was.
+ * GAMS_EINVAL: null arguments, slots outside the set, or a member that passed the O(1) checks and whose ISIZE is not
+ * its slot's length (nothing is written).  GAMS_ESTATE: a plane-only seqset.  count == 0: GAMS_OK.
+ * gams_gpu_last_stage_ms then reports four stages: upload (the members and the block table), tables (per block, the
+ * header into a decode table), decode (per block: chunks decoded by one lane each into LDS, then the bases, the plane
+ * and the block's raw CRC-32), join (per ctg: the CRC-32 against the trailer, the status bytes back). */
+int gams_seqset_upload_gz(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, const uint8_t *const *members,
+                          const uint64_t *member_bytes, uint8_t *status, uint32_t *n_foreign);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,13 @@ int gams_gc_plane_with(const uint8_t *seq, uint64_t n, uint8_t *plane, int body)
  * for byte at every size. */
 int gams_seq_gz_host_block(const uint8_t *seq, uint64_t n, uint32_t block, uint8_t *out, uint64_t cap, uint64_t *n_out);
 int gams_gpu_seq_gz_set_block(gams_gpu_t *h, uint32_t block);
+/* The same for the indexed members: the host twin with the block size named (and GAMS_SEQ_GZ_CHUNK), with block size
+ * and chunk named, and the chunk gams_gpu_seq_gz writes with GAMS_SEQ_GZ_INDEXED on this handle from now on.  A chunk
+ * is 512, 1024, 2048 or 4096 (GAMS_EINVAL otherwise). */
+int gams_seq_gz_host_indexed_block(const uint8_t *seq, uint64_t n, uint32_t block, uint8_t *out, uint64_t cap, uint64_t *n_out);
+int gams_seq_gz_host_indexed_chunk(const uint8_t *seq, uint64_t n, uint32_t block, uint32_t chunk, uint8_t *out, uint64_t cap,
+                                   uint64_t *n_out);
+int gams_gpu_seq_gz_set_chunk(gams_gpu_t *h, uint32_t chunk);
 
 #ifdef __cplusplus
 }
