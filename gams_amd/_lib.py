@@ -18,6 +18,8 @@ WAVE_BODY_AUTO, WAVE_BODY_WIDE, WAVE_BODY_NARROW = 0, 1, 2      # gams_wave_plan
 WAVE_CUT_AUTO, WAVE_CUT_TWO_WAVES, WAVE_CUT_ONE_WAVE = 0, 1, 2  # gams_wave_plan_set_cut / _last_cut
 GC_BODY_AUTO, GC_BODY_PORTABLE, GC_BODY_AVX2 = 0, 1, 2          # gams_gc_plane_with
 SW_GC, SW_COUNT = 1, 2          # GAMS_SW_GC / GAMS_SW_COUNT: the action set of gams_gpu_sw_text_actions
+DG_STAGE_BASES = 512            # GAMS_DG_STAGE_BASES: bases per stage of the ΔG kernel (gams_gpu_diag.h)
+DG_TABLE_LDS, DG_TABLE_BPERMUTE = 0, 1                # gams_gpu_dg_set_table
 SW_SUMMARY_MAX_ANNO = 4         # GAMS_SW_SUMMARY_MAX_ANNO: the span sets (Prop columns) of one sw summary
 SW_SUMMARY_WORDS = 10           # GAMS_SW_SUMMARY_WORDS: COUNT, four S, four NaN counters, C of a summary group
 LOADER_RG, LOADER_FEATURE = 0, 1                      # gams_gpu_loader_text: kind
@@ -38,6 +40,11 @@ class GamsError(RuntimeError):
 class WaveParams(C.Structure):
     _fields_ = [("size", C.c_int32), ("step", C.c_int32), ("lag", C.c_uint32),
                 ("threshold", C.c_float), ("influence", C.c_float)]
+
+
+class DgTable(C.Structure):
+    """gams_dg_table_t: the 21 f32 terms of the nearest-neighbour ΔG"""
+    _fields_ = [("nn", C.c_float * 16), ("init", C.c_float * 4), ("sym", C.c_float)]
 
 
 class GenParams(C.Structure):
@@ -127,6 +134,15 @@ PROTOTYPES = {
                                           _VP, C.c_uint64, _VP, _VP]),
     "gams_gpu_range_gc": (C.c_int, [_VP, _VP, C.c_uint32, C.c_int32, _VP, _VP, C.c_uint32, _VP]),
     "gams_gpu_range_gc_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "gams_dg_table": (C.c_int, [C.c_float, C.c_float, _VP]),
+    "gams_dg_polymer_host": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(C.c_float)]),
+    "gams_gpu_range_dg_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "gams_gpu_sw_dg_batch": (C.c_int, [_VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP,
+                                       C.c_uint64, _VP, _VP]),
+    "gams_gpu_sw_text_dg": (C.c_int, [_VP, _VP, C.c_uint32, _VP, C.POINTER(C.c_char_p), _VP, _VP, _VP, _VP,
+                                      C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_uint32, _VP, _VP, _VP,
+                                      _PP, C.POINTER(C.c_uint64), _PP, C.POINTER(C.c_uint64)]),
+    "gams_gpu_dg_set_table": (C.c_int, [_VP, C.c_int]),
     "gams_index_create": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _PP]),
     "gams_index_destroy": (None, [_VP, _VP]),
     "gams_gpu_count": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_uint64, _VP]),

@@ -74,6 +74,7 @@ struct gams_gpu {
     std::atomic<uint64_t> reader_epoch{1};
     std::unordered_map<const void *, size_t> lds_attr;
     std::mutex lds_mu;
+    int dg_table = GAMS_DG_TABLE_LDS;   // where the ΔG kernel keeps its dimer terms (gams_gpu_dg_set_table)
 };
 
 // Make sure launches of `func` on the handle's device may use `bytes` of dynamic LDS.  Plans with different
@@ -256,6 +257,19 @@ void gams_seqset_gcindex_free(gams_seqset_t *s);
 void gams_launch_range_gc_cols(const gams_seqset_t *s, const unsigned long long *seq_off, const uint32_t *len,
                                const int32_t *chr_start, const uint32_t *rctg, const uint32_t *rs, const uint32_t *re,
                                uint32_t n, float *gc, hipStream_t st);
+
+// dg.hip: the nearest-neighbour ΔG.  The table of a call: not NULL, every entry finite (GAMS_EINVAL under
+// the entry `who` names); the seqset's bytes: present (GAMS_ESTATE) and the compute stream behind their uploads; and the
+// kernel on the compute stream over device columns: dg[q] of the len[q] <= 65535 bases at byte off[q] of the seqset's
+// buffer, NaN for None, with the table in device memory.
+int gams_dg_table_check(gams_gpu_t *h, const std::string &who, const gams_dg_table_t *t);
+int gams_dg_seq_ready(gams_gpu_t *h, gams_seqset_t *s);
+void gams_launch_dg(gams_gpu_t *h, const gams_seqset_t *s, const unsigned long long *d_off, const uint32_t *d_len, uint32_t n,
+                    const gams_dg_table_t *d_table, float *d_dg);
+// sw.hip, for dg.hip: the selected ctgs of a batch call against the seqset, `off` (named off_name in the messages) from 0
+// and not decreasing -- the check gams_gpu_range_gc_batch makes, under the entry `who` names
+int gams_sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
+                            const uint32_t *ctg_index, const uint64_t *off);
 
 // The accumulator of the sw summaries (sw.hip): n_tags x (max + 1) groups of GAMS_SW_SUMMARY_WORDS 64-bit
 // integers in device memory, and the table of one call ((max + 1) groups, then a flag word) that the summarising

@@ -616,9 +616,12 @@ __device__ __forceinline__ SwRowCtx sw_row_ctx(const SwTextArgs &a, uint64_t r, 
     c.serial = (uint32_t)(r - a.feat_row_off[c.f]) + 1u;    // sw.rs:148: the serial restarts with every feature
     return c;
 }
-// the row's text, counted or written; `bad`: a value this formatter does not cover
-template <bool kWrite>
-__device__ __forceinline__ void sw_row_text(const SwTextArgs &a, uint64_t r, RowOut<kWrite> &o, bool &bad) {
+// the row's text, counted or written; `bad`: a value this formatter does not cover.  kDg: the tenth field behind rg_count,
+// dg[r] printed `{:.4}` and empty for NaN (gams_gpu_sw_text_dg); the column is an argument of its own, so SwTextArgs and
+// the kernels without it stay what they are
+template <bool kWrite, bool kDg = false>
+__device__ __forceinline__ void sw_row_text(const SwTextArgs &a, uint64_t r, RowOut<kWrite> &o, bool &bad,
+                                            const float *dg = nullptr) {
     const gams_sw_row_t w = a.rows[r];
     const SwRowCtx c = sw_row_ctx(a, r, w);
     const char *id, *nm;
@@ -673,6 +676,10 @@ __device__ __forceinline__ void sw_row_text(const SwTextArgs &a, uint64_t r, Row
     }
     o.ch('\t');
     if (a.cnt) o.i32(a.cnt[r]);
+    if (kDg) {
+        o.ch('\t');
+        o.dg4(dg[r], bad);
+    }
     o.ch('\n');
 }
 
@@ -719,6 +726,57 @@ __global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) 
         w.put(at, [&](char *p) {
             RowOut<true> o{p};
             sw_row_text(a, r, o, bad);
+        });
+        at += l[u];
+    }
+    w.flush();
+}
+
+// The same two kernels with the tenth field (gams_gpu_sw_text_dg).  They are kernels of their own, not a flag of the two
+// above, so that the code of those stays what it was, instruction for instruction (profiles/dg.txt).
+__global__ __launch_bounds__(256) void sw_text_dg_len_kernel(const SwTextArgs a, const float *dg) {
+    __shared__ uint32_t ws[4];
+    const uint64_t base = (uint64_t)blockIdx.x * kSwTextBlock;
+    const uint32_t tid = threadIdx.x;
+    uint32_t sum = 0;
+    bool bad = false;
+#pragma unroll
+    for (uint32_t u = 0; u < 2u; ++u) {
+        const uint64_t r = base + 2u * tid + u;
+        if (r >= a.n_rows) continue;
+        RowOut<false> n;
+        sw_row_text<false, true>(a, r, n, bad, dg);
+        a.len[r] = n.n;
+        sum += n.n;
+    }
+    if (bad) a.words[1] = 1ull;
+    const uint32_t tot = block_sum_256(sum, ws);
+    if (tid == 0u) a.blk_len[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void sw_text_dg_write_kernel(const SwTextArgs a, const float *dg) {
+    __shared__ uint32_t scr[4];
+    __shared__ __align__(16) char stage[kSwTextStage + 16];
+    const uint64_t base = (uint64_t)blockIdx.x * kSwTextBlock;
+    const uint32_t tid = threadIdx.x;
+    uint32_t l[2], mine = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < 2u; ++u) {
+        const uint64_t r = base + 2u * tid + u;
+        l[u] = r < a.n_rows ? a.len[r] : 0u;
+        mine += l[u];
+    }
+    BlockWriter<uint32_t> w(mine, scr, a.blk_off, a.text, a.text_cap);
+    w.stage_if(w.tot <= kSwTextStage, stage);
+    uint32_t at = w.rel;
+    bool bad = false;
+#pragma unroll
+    for (uint32_t u = 0; u < 2u; ++u) {
+        const uint64_t r = base + 2u * tid + u;
+        if (r >= a.n_rows) break;
+        w.put(at, [&](char *p) {
+            RowOut<true> o{p};
+            sw_row_text<true, true>(a, r, o, bad, dg);
         });
         at += l[u];
     }
@@ -778,6 +836,29 @@ __global__ __launch_bounds__(256) void sw_ctg_row_off_kernel(const unsigned long
     if (i <= n_ctg) ctg_row_off[i] = row_off[bucket_off[i]];
 }
 
+// ---- the stored rows as the columns of the ΔG kernel (dg.hip): where the bases of row r's window begin in the seqset's
+// buffer, and how many they are.  Row r belongs to the last feature whose first row is <= r (every feature has its M row).
+__global__ __launch_bounds__(256) void sw_dg_cols_kernel(const gams_sw_row_t *rows, uint64_t n_rows, const SwCtg *ctgs,
+                                                         const uint32_t *fctg, const uint64_t *row_off, uint32_t nf,
+                                                         unsigned long long *off, uint32_t *len) {
+    const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n_rows) return;
+    uint32_t lo = 0, hi = nf;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (row_off[mid] <= r)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const SwCtg cg = ctgs[fctg[lo]];
+    const gams_sw_row_t w = rows[r];
+    // (a window lies inside its ctg and has at most `size` <= 65535 bases: anything else would read no byte and answer NaN)
+    const bool inside = w.start >= cg.chr_start && w.end <= cg.chr_end && w.end >= w.start && w.end - w.start < 65535;
+    off[r] = cg.seq_off + (inside ? (uint64_t)((int64_t)w.start - cg.chr_start) : 0ull);
+    len[r] = inside ? (uint32_t)(w.end - w.start + 1) : 0u;
+}
+
 struct SwTextReq {                       // what the text entries add to a batch call
     const char *const *chr;              // per selected ctg
     const char *const *feat_id;          // per feature
@@ -788,7 +869,9 @@ struct SwTextReq {                       // what the text entries add to a batch
 
 // One call of the batch entries.  What it is asked for: the rows (gams_gpu_sw_batch) or the counts (gams_gpu_sw_count_batch)
 // in the caller's array, the rows as text (the text entries) or the rows added into call.summary (the summary entries).
-enum class SwMode { Rows, Counts, Text, Summary };
+// With dg_table a call also computes the ΔG of every stored row's window: Dg hands the values to the
+// caller's array (gams_gpu_sw_dg_batch), Text prints them as the tenth field (gams_gpu_sw_text_dg).
+enum class SwMode { Rows, Counts, Text, Summary, Dg };
 struct SwReq {
     SwMode mode;
     gams_gpu_t *h;
@@ -805,12 +888,17 @@ struct SwReq {
     uint64_t cap = 0;
     uint64_t *row_off = nullptr;
     SwTextReq tx{};                      // Text
+    const gams_dg_table_t *dg_table = nullptr;   // Dg, and Text with the ΔG column: the call's terms ...
+    float *dg = nullptr;                 // ... Dg: the caller's array of `cap` entries
     SwReq(SwMode mode_, gams_gpu_t *h_, gams_seqset_t *s_, uint32_t n_sel_, const uint32_t *ctg_index_, const int32_t *chr_start_,
           const uint64_t *feat_off_, const int32_t *feat_start_, const int32_t *feat_end_, const SwCall &call_, uint64_t *n_rows_)
         : mode(mode_), h(h_), s(s_), n_sel(n_sel_), ctg_index(ctg_index_), chr_start(chr_start_), feat_off(feat_off_),
           feat_start(feat_start_), feat_end(feat_end_), call(call_), n_rows(n_rows_) {}
     // only *n_rows and row_off are wanted: neither text nor summary, and no array to fill or no room in it
-    bool size_query() const { return mode == SwMode::Rows ? !rows || !cap : mode == SwMode::Counts && (!count || !cap); }
+    bool size_query() const {
+        if (mode == SwMode::Dg) return !dg || !cap;
+        return mode == SwMode::Rows ? !rows || !cap : mode == SwMode::Counts && (!count || !cap);
+    }
 };
 
 using SwCols = SwStage<SwCtg>;
@@ -1068,8 +1156,9 @@ struct SwText {
     uint64_t bytes;
     const unsigned long long *words;   // [2 + k] = the first byte of ctg k, [2 + n_sel] = bytes
 };
+// `dg`, where given: the ΔG of every row on the device, printed as the tenth field (the kernels with the column).
 int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, const SwTextArgs &ta, const StageClock *stage,
-                 SwText *out) {
+                 SwText *out, const float *dg = nullptr) {
     hipStream_t st = h->compute;
     const uint32_t nb = ta.nb, n_sel = ta.n_sel;
     const uint64_t text_cap = ta.text_cap;
@@ -1077,7 +1166,10 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
     GAMS_TRY(h, who, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), st));
     if (stage) GAMS_TRY(h, who, (*stage)(SWF_TLEN, true));
     if (nb) {
-        hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, st, ta);
+        if (dg)
+            hipLaunchKernelGGL(sw_text_dg_len_kernel, dim3(nb), dim3(256), 0, st, ta, dg);
+        else
+            hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, st, ta);
         hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, ta.blk_len, nb, ta.blk_off, ta.words, 0u);
     }
     if (stage) {
@@ -1085,7 +1177,10 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
         GAMS_TRY(h, who, (*stage)(SWF_TWRITE, true));
     }
     if (nb) {
-        hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, st, ta);
+        if (dg)
+            hipLaunchKernelGGL(sw_text_dg_write_kernel, dim3(nb), dim3(256), 0, st, ta, dg);
+        else
+            hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, st, ta);
         hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, st, ta);
     }
     GAMS_TRY(h, who, hipGetLastError());
@@ -1096,7 +1191,7 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
     const uint64_t bytes = h->sw_words[0];
     if (h->sw_words[1] != 0 || bytes > text_cap)
         return gams_fail(h, GAMS_EUNSUPPORTED, who + ": a value this formatter does not cover (a statistic of 1000 or more, a "
-                                                     "negative coordinate): " + advice);
+                                                     "negative coordinate" + (dg ? ", a dG of 2^20 or more" : "") + "): " + advice);
     GAMS_TRY(h, who, gams_pool_grow(h, true, &h->sw_text, &h->sw_text_bytes, bytes, bytes + bytes / 8 + 4096));
     if (bytes) GAMS_TRY(h, who, hipMemcpyAsync(h->sw_text, ta.text, bytes, hipMemcpyDeviceToHost, st));
     GAMS_TRY(h, who, hipStreamSynchronize(st));
@@ -1106,14 +1201,15 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
 
 // 4. (text entries) the n_out rows on the device -> TSV text in the handle's page-locked buffer
 int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vector<uint64_t> &crow, const SwCols &d,
-                    const gams_sw_row_t *d_rows, const int32_t *d_cnt) {
+                    const gams_sw_row_t *d_rows, const int32_t *d_cnt, const float *d_dg) {
     gams_gpu_t *h = q.h;
     const SwTextReq *tx = &q.tx;
     const uint32_t n_sel = q.n_sel;
     SwTextBlobs B;
     const int rc = sw_text_blobs(q, nf, B);
     if (rc != GAMS_OK) return rc;
-    const uint64_t per_row = B.max_id + B.max_name + (q.call.count() ? 112 : 96);
+    // (the tenth field: a tab and at most kGamsDg4MaxLen bytes)
+    const uint64_t per_row = B.max_id + B.max_name + (q.call.count() ? 112 : 96) + (d_dg ? 1u + kGamsDg4MaxLen : 0u);
     auto tabs = [&](Carver &c) { return sw_text_tabs_layout(c, n_sel, nf, B.names.size(), B.ids.size()); };
     SwTextArgs ta{};
     auto dev = [&](Carver &c) {   // tables | what the tail writes
@@ -1139,7 +1235,7 @@ int sw_rows_to_text(const SwReq &q, uint32_t nf, uint64_t n_out, const std::vect
     carve(tdev.p, dev);
     sw_text_rows(ta, q.call, d, d_rows, d_cnt);
     SwText T{};
-    const int rt = sw_text_tail(h, kSwText, "format gams_gpu_sw_batch's rows on the host", ta, nullptr, &T);
+    const int rt = sw_text_tail(h, kSwText, "format gams_gpu_sw_batch's rows on the host", ta, nullptr, &T, d_dg);
     if (rt != GAMS_OK) return rt;
     *tx->text = T.text;
     *tx->text_bytes = T.bytes;
@@ -1155,8 +1251,18 @@ int sw_batch_impl(const SwReq &q) {
     int rc = sw_check(q, &nf);
     if (rc != GAMS_OK || nf == 0) return rc;
     GAMS_HIP(h, hipSetDevice(h->device));
-    // Inputs are assembled in one page-locked block (one DMA): ctgs | fs | fe | fctg | off
-    auto inputs = [&](Carver &cv) { return sw_stage_layout<SwCtg>(cv, q.n_sel, nf, true); };
+    // Inputs are assembled in one page-locked block (one DMA): ctgs | fs | fe | fctg | off (| the ΔG terms)
+    const bool want_dg = q.dg_table != nullptr;
+    struct Inputs {
+        SwCols cols;
+        gams_dg_table_t *tab;            // the ΔG terms of the block carved (nullptr without the column)
+    };
+    auto inputs = [&](Carver &cv) {
+        Inputs i{};
+        i.cols = sw_stage_layout<SwCtg>(cv, q.n_sel, nf, true);
+        i.tab = want_dg ? cv.take<gams_dg_table_t>(1) : nullptr;
+        return i;
+    };
     const size_t in_bytes = layout_bytes(inputs);
     const bool size_query = q.size_query();
     PoolBlock dev(h, false), pin(h, true);
@@ -1166,7 +1272,9 @@ int sw_batch_impl(const SwReq &q) {
     in.row_off = off_host.data();
     if (!size_query) {
         GAMS_TRY(h, kSw, pin.alloc(in_bytes));
-        in = carve(pin.p, inputs);
+        const Inputs pinned = carve(pin.p, inputs);
+        in = pinned.cols;
+        if (want_dg) *pinned.tab = *q.dg_table;
     }
     uint64_t tot = 0;
     if ((rc = sw_host_rows(q, nf, in, crow, &tot)) != GAMS_OK) return rc;
@@ -1174,15 +1282,29 @@ int sw_batch_impl(const SwReq &q) {
     if (size_query) return GAMS_OK;
     // the counts and the geometry read no sequence byte: a count-only call leaves the bytes alone
     if (c.gc() && (rc = gams_seqset_gcindex(h, q.s)) != GAMS_OK) return rc;
+    if (want_dg && (rc = gams_dg_seq_ready(h, q.s)) != GAMS_OK) return rc;
     // text mode: every row, kept on the device; the summary stores none
     const uint64_t n_out = summary ? 0 : std::min<uint64_t>(tot, text ? tot : q.cap);
+    if (want_dg && n_out > 0x7fffff00ull) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_sw: too many rows for one ΔG launch");
     SwCols d{};
     gams_sw_row_t *d_rows = nullptr;
     int32_t *d_cnt = nullptr;
-    auto device = [&](Carver &cv) {   // the inputs | rows | counts
-        d = inputs(cv);
+    unsigned long long *d_dg_off = nullptr;
+    uint32_t *d_dg_len = nullptr;
+    float *d_dg = nullptr;
+    const gams_dg_table_t *d_tab = nullptr;
+    auto device = [&](Carver &cv) {   // the inputs | rows | counts (| the ΔG kernel's columns and its values)
+        const Inputs i = inputs(cv);
+        d = i.cols;
+        d_tab = i.tab;
         d_rows = cv.take_tight<gams_sw_row_t>(std::max<uint64_t>(n_out, 1));
         d_cnt = c.count() ? cv.take<int32_t>(std::max<uint64_t>(n_out, 1)) : nullptr;
+        if (want_dg) {
+            (void)cv.step(gams_align256(cv.off) - cv.off);   // (the rows are carved tight: back onto a 256-B slot)
+            d_dg_off = cv.take<unsigned long long>(std::max<uint64_t>(n_out, 1));
+            d_dg_len = cv.take<uint32_t>(std::max<uint64_t>(n_out, 1));
+            d_dg = cv.take<float>(std::max<uint64_t>(n_out, 1));
+        }
     };
     GAMS_TRY(h, kSw, dev.alloc(layout_bytes(device)));
     carve(dev.p, device);
@@ -1191,14 +1313,26 @@ int sw_batch_impl(const SwReq &q) {
     if ((rc = sets.put(h, c, q.n_sel)) != GAMS_OK) return rc;
     if ((rc = sw_launch(h, c, q.s, nf, n_out, d, d_rows, d_cnt, sets.staged())) != GAMS_OK) return rc;
     if (summary) return sw_sum_verdict(h, c.summary);
-    if (text) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt);
+    if (want_dg && n_out) {   // 3''. the windows' bytes from the stored rows, and their ΔG
+        hipLaunchKernelGGL(sw_dg_cols_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, h->compute, d_rows, n_out,
+                           d.ctgs, d.fctg, d.row_off, nf, d_dg_off, d_dg_len);
+        gams_launch_dg(h, q.s, d_dg_off, d_dg_len, (uint32_t)n_out, d_tab, d_dg);
+        GAMS_TRY(h, kSw, hipGetLastError());
+    }
+    if (text) return sw_rows_to_text(q, nf, n_out, crow, d, d_rows, d_cnt, d_dg);
     // 5. read back
     if (q.rows) GAMS_TRY(h, kSw, hipMemcpyAsync(q.rows, d_rows, n_out * sizeof(gams_sw_row_t), hipMemcpyDeviceToHost, h->compute));
     if (q.count) GAMS_TRY(h, kSw, hipMemcpyAsync(q.count, d_cnt, n_out * sizeof(int32_t), hipMemcpyDeviceToHost, h->compute));
+    if (q.dg) GAMS_TRY(h, kSw, hipMemcpyAsync(q.dg, d_dg, n_out * sizeof(float), hipMemcpyDeviceToHost, h->compute));
     GAMS_TRY(h, kSw, hipStreamSynchronize(h->compute));
     return GAMS_OK;
 }
 }  // namespace
+
+int gams_sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
+                            const uint32_t *ctg_index, const uint64_t *off) {
+    return sw_check_selection(h, who, off_name, s, n_sel, ctg_index, off);
+}
 
 int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
                         uint64_t *n_rows) {
@@ -1344,6 +1478,52 @@ extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_
     if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
     SwReq q(SwMode::Text, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
     q.tx = SwTextReq{chr, feat_id, text, text_bytes, ctg_off};
+    *text = nullptr;
+    *text_bytes = 0;
+    return sw_batch_impl(q);
+}
+
+// ---- the ΔG of the windows: the rows' geometry from the kernel without actions, then dg.hip over them --
+// a window has at most `size` bases (M is the feature resized to `size`, window.rs:96-124), so the kernel's limit is one on size
+static int sw_dg_check(gams_gpu_t *h, const std::string &who, const gams_dg_table_t *table, int32_t size) {
+    const int rc = gams_dg_table_check(h, who, table);
+    if (rc != GAMS_OK) return rc;
+    if (size > 65535) return gams_fail(h, GAMS_EUNSUPPORTED, who + ": windows of more than 65535 bases");
+    return GAMS_OK;
+}
+
+extern "C" int gams_gpu_sw_dg_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                    const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                                    const int32_t *feat_end, int32_t size, int32_t max, const gams_dg_table_t *table,
+                                    float *dg, uint64_t cap, uint64_t *row_off, uint64_t *n_rows) {
+    const int rc = sw_dg_check(h, "gpu_sw_dg", table, size);
+    if (rc != GAMS_OK) return rc;
+    // resize only shapes the gc statistics, which this call does not compute: any value the checks accept
+    const SwCall c(size, max, 2, 0u);
+    SwReq q(SwMode::Dg, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
+    q.dg_table = table;
+    q.dg = dg;
+    q.cap = cap;
+    q.row_off = row_off;
+    return sw_batch_impl(q);
+}
+
+extern "C" int gams_gpu_sw_text_dg(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                   const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
+                                   const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
+                                   int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
+                                   const uint32_t *rg_group, const gams_dg_table_t *table, const char **text,
+                                   uint64_t *text_bytes, const uint64_t **ctg_off, uint64_t *n_rows) {
+    if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
+    SwCall c(size, max, resize, actions, rg_ix, rg_group);
+    int rc = gams_sw_call_check(h, kSwText, c, SWC_ACTIONS, n_sel);
+    if (rc != GAMS_OK) return rc;
+    if ((rc = sw_dg_check(h, kSwText, table, size)) != GAMS_OK) return rc;
+    if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
+    SwReq q(SwMode::Text, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
+    q.tx = SwTextReq{chr, feat_id, text, text_bytes, ctg_off};
+    q.dg_table = table;
     *text = nullptr;
     *text_bytes = 0;
     return sw_batch_impl(q);

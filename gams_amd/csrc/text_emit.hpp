@@ -154,6 +154,13 @@ struct RowOut<false, Len> {
         if (l == 0u) bad = true;
         n += l > 1u ? l : 3u;
     }
+    // `{:.4}` of a ΔG (gams_fmt_dg4); NaN -- None -- is an empty field, a value it does not cover is flagged and empty
+    __device__ __forceinline__ void dg4(float v, bool &bad) {
+        if (v != v) return;
+        const uint32_t l = gams_fmt_dg4(v, nullptr);
+        if (l == 0u) bad = true;
+        n += l;
+    }
 };
 template <typename Len>
 struct RowOut<true, Len> {
@@ -188,6 +195,10 @@ struct RowOut<true, Len> {
         const uint32_t l = json_f32_covered(v) ? gams_fmt_f32_short(v, q) : 0u;
         if (l == 1u) { q[1] = '.'; q[2] = '0'; }
         q += l > 1u ? l : 3u;
+    }
+    __device__ __forceinline__ void dg4(float v, bool &) {         // (a value not covered: flagged by the counting pass)
+        if (v != v) return;
+        q += gams_fmt_dg4(v, q);
     }
 };
 

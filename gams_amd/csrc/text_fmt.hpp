@@ -101,3 +101,43 @@ GAMS_HD inline uint32_t gams_fmt_f32_short(float v, char *out) {
     }
     return 0;
 }
+
+// The ΔG column prints its f32 as `{:.4}`: the exact binary value rounded half to even at the fourth
+// decimal, the sign kept even where every digit is zero ("-0.0000") -- what "%.4f" of the widened double prints.
+// |v| = m * 2^-s with m < 2^24; below 2^20 s is at least 4, m * 10^4 stays under 2^38 and quotient and remainder by 2^s
+// are exact in 64 bits; from s = 39 on the value is below half a unit and q is 0.  The text goes to out[0..len), len <= 13
+// is returned; out == nullptr: the length only.  Returns 0 (nothing written) for NaN, an infinity and |v| >= 2^20: the
+// caller flags such a value.
+constexpr uint32_t kGamsDg4MaxLen = 13;
+GAMS_HD inline uint32_t gams_fmt_dg4(float v, char *out) {
+    uint32_t b;
+    memcpy(&b, &v, 4);
+    const uint32_t ex = (b >> 23) & 0xffu;
+    if (ex >= 147u) return 0;                       // 2^20 and beyond, infinities, NaN
+    const uint32_t s = 150u - ex;                   // >= 4
+    uint64_t q = 0;
+    if (s < 39u) {
+        const uint64_t num = (uint64_t)((b & 0x7fffffu) | 0x800000u) * 10000u;
+        q = num >> s;
+        const uint64_t r = num & ((1ull << s) - 1u), half = 1ull << (s - 1u);
+        if (r > half || (r == half && (q & 1u))) ++q;
+    }
+    const uint32_t neg = b >> 31;
+    uint32_t ip = (uint32_t)(q / 10000u), fr = (uint32_t)(q % 10000u), digits = 1;
+    for (uint32_t t = ip; t >= 10u; t /= 10u) ++digits;
+    const uint32_t len = neg + digits + 5u;
+    if (out) {
+        if (neg) out[0] = '-';
+        for (uint32_t k = digits; k > 0u; --k) {
+            out[neg + k - 1u] = (char)('0' + ip % 10u);
+            ip /= 10u;
+        }
+        char *const f = out + neg + digits;
+        f[0] = '.';
+        f[1] = (char)('0' + fr / 1000u);
+        f[2] = (char)('0' + fr / 100u % 10u);
+        f[3] = (char)('0' + fr / 10u % 10u);
+        f[4] = (char)('0' + fr % 10u);
+    }
+    return len;
+}

@@ -250,6 +250,63 @@ def sw_text_actions(eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, fe
     return rc, text, offs
 
 
+def _dg_table(table):
+    """a _lib.DgTable, or 21 floats (nn, init, sym), as the structure the C entries take"""
+    if isinstance(table, _lib.DgTable):
+        return table
+    a = np.ascontiguousarray(table, np.float32)
+    if a.size != 21:
+        raise ValueError("a ΔG table has 21 terms")
+    return _lib.DgTable.from_buffer_copy(a.tobytes())
+
+
+def range_dg_batch(eng, seqset, sel, chr_start, range_off, rs, re, table):
+    """gams_gpu_range_dg_batch -> (rc, the ΔG of every range as f32, NaN for None); rc != OK is returned, not raised"""
+    sel, cst, roff, rs, re = _sw_sel(sel, chr_start, range_off, rs, re)
+    out = np.zeros(max(rs.size, 1), np.float32)
+    t = None if table is None else _dg_table(table)
+    rc = eng.lib.gams_gpu_range_dg_batch(eng.h, seqset.p, sel.size, sel.ctypes.data, cst.ctypes.data, roff.ctypes.data,
+                                         rs.ctypes.data if rs.size else None, re.ctypes.data if re.size else None,
+                                         C.byref(t) if t is not None else None, out.ctypes.data)
+    return rc, out[:rs.size]
+
+
+def sw_dg_batch(eng, seqset, sel, chr_start, feat_off, fs, fe, size, mx, table):
+    """gams_gpu_sw_dg_batch: (the ΔG of every row in gams_gpu_sw_batch's order, row_off per selected ctg)"""
+    sel, cst, foff, fs, fe = _sw_sel(sel, chr_start, feat_off, fs, fe)
+    t = _dg_table(table)
+    n = C.c_uint64()
+    roff = np.zeros(sel.size + 1, np.uint64)
+    args = (eng.h, seqset.p, sel.size, sel.ctypes.data, cst.ctypes.data, foff.ctypes.data, fs.ctypes.data,
+            fe.ctypes.data, size, mx, C.byref(t))
+    eng.check(eng.lib.gams_gpu_sw_dg_batch(*args, None, 0, roff.ctypes.data, C.byref(n)))    # size query
+    dg = np.zeros(max(n.value, 1), np.float32)
+    eng.check(eng.lib.gams_gpu_sw_dg_batch(*args, dg.ctypes.data, dg.size, roff.ctypes.data, C.byref(n)))
+    return dg[:n.value], roff
+
+
+def sw_text_dg(eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids, size, mx, resize, actions, table,
+               index=None, rg_group=None):
+    """gams_gpu_sw_text_dg -> (rc, text bytes, per-ctg offsets); rc != OK is returned, not raised"""
+    sel, cst, foff, fs, fe = _sw_sel(sel, chr_start, feat_off, fs, fe)
+    names = (C.c_char_p * max(sel.size, 1))(*[c.encode() for c in chr_names])
+    ids = (C.c_char_p * max(len(feat_ids), 1))(*[f.encode() for f in feat_ids])
+    grp = None if rg_group is None else np.ascontiguousarray(rg_group, np.uint32)
+    t = None if table is None else _dg_table(table)
+    txt, nb, off, nrows = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+    rc = eng.lib.gams_gpu_sw_text_dg(eng.h, seqset.p, sel.size, sel.ctypes.data, names, cst.ctypes.data,
+                                     foff.ctypes.data, fs.ctypes.data, fe.ctypes.data, ids, size, mx, resize, actions,
+                                     index.p if index is not None else None,
+                                     grp.ctypes.data if grp is not None else None,
+                                     C.byref(t) if t is not None else None, C.byref(txt), C.byref(nb), C.byref(off),
+                                     C.byref(nrows))
+    if rc != _lib.OK:
+        return rc, b"", None
+    text = C.string_at(txt.value, nb.value) if nb.value else b""
+    offs = np.frombuffer((C.c_uint64 * (sel.size + 1)).from_address(off.value), np.uint64).copy()
+    return rc, text, offs
+
+
 class WavePlan:
     """Geometry + device buffers of one `wave` configuration over a SeqSet."""
 

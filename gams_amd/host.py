@@ -205,6 +205,14 @@ def load():
     L.gams_host_last_operator_device.argtypes = []
     L.gams_host_fmt_prop4.restype = C.c_void_p
     L.gams_host_fmt_prop4.argtypes = [C.c_float]
+    L.gams_host_fmt_dg4.restype = C.c_void_p
+    L.gams_host_fmt_dg4.argtypes = [C.c_float]
+    L.gams_host_sw_gibbs.restype = C.c_void_p
+    L.gams_host_sw_gibbs.argtypes = [C.c_void_p, C.c_uint32, sp, sp, ip, ip, C.c_void_p, C.c_char_p, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_uint32, C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.gams_host_dg_ranges.restype = C.c_int
+    L.gams_host_dg_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                      C.c_void_p]
     L.gams_host_fmt_f32_short.restype = C.c_void_p
     L.gams_host_fmt_f32_short.argtypes = [C.c_float]
     L.gams_host_peak_text.restype = C.c_void_p
@@ -895,6 +903,93 @@ def sw_multi(engines, ctgs, features_per_ctg, size=100, mx=20, resize=500, actio
                                                    rows.encode(), size, mx, resize, mask, _rg_lines(rg_records)))
 
 
+class DeltaG:
+    """The nearest-neighbour free energy of a DNA polymer (the reference's DeltaG, delta_g.rs): .table holds the 21 f32
+    terms of (temp, salt) as a _lib.DgTable, made once by gams_dg_table; .polymer(seq) is DeltaG::polymer on the host
+    (gams_dg_polymer_host, the twin of the device entries): a float, None for fewer than 3 bases or a byte that is none
+    of ACGTacgt."""
+
+    def __init__(self, temp=37.0, salt=1.0):
+        self.temp, self.salt = float(temp), float(salt)
+        self.table = _lib.DgTable()
+        rc = _lib.load().gams_dg_table(self.temp, self.salt, C.byref(self.table))
+        if rc != _lib.OK:
+            raise ValueError(f"DeltaG: temp {temp!r} must be finite, salt {salt!r} finite and above 0")
+
+    def polymer_f32(self, seq):
+        """the f32 itself, NaN for None"""
+        a = np.ascontiguousarray(np.frombuffer(seq.encode("latin-1") if isinstance(seq, str) else bytes(seq), np.uint8))
+        out = C.c_float()
+        rc = _lib.load().gams_dg_polymer_host(C.byref(self.table), a.ctypes.data if a.size else None, a.size, C.byref(out))
+        if rc != _lib.OK:
+            raise _lib.GamsError(rc, "gams_dg_polymer_host")
+        return np.float32(out.value)
+
+    def polymer(self, seq):
+        v = self.polymer_f32(seq)
+        return None if np.isnan(v) else float(v)
+
+
+def range_dg(eng, seqset, sel, chr_start, ranges, dg=None):
+    """The ΔG of chromosome ranges inside ctgs of a resident seqset, on the device (gams_gpu_range_dg_batch): sel[k] names
+    a slot of the seqset, chr_start[k] its first chromosome coordinate, ranges[k] its [(start, end)] -> one f32 array
+    over the concatenated ranges, NaN for None.  dg: a DeltaG (default DeltaG())."""
+    from . import engine
+
+    dg = DeltaG() if dg is None else dg
+    off = np.concatenate([[0], np.cumsum([len(r) for r in ranges])]).astype(np.uint64)
+    rs = np.array([r[0] for rl in ranges for r in rl], np.int32)
+    re_ = np.array([r[1] for rl in ranges for r in rl], np.int32)
+    rc, out = engine.range_dg_batch(eng, seqset, sel, chr_start, off, rs, re_, dg.table)
+    eng.check(rc)
+    return out
+
+
+def dg_ranges_host(dg, seqs, which, off, length, threads=16):
+    """For measurement (tools/bench_dg.py): DeltaG.polymer_f32 of the length[q] bytes at seqs[which[q]][off[q]:] for
+    every q, in C++ on `threads` host threads -> f32 array.  seqs: contiguous uint8 arrays."""
+    which, off = np.ascontiguousarray(which, np.uint32), np.ascontiguousarray(off, np.uint64)
+    length = np.ascontiguousarray(length, np.uint32)
+    ptrs = (C.c_void_p * max(len(seqs), 1))(*[s.ctypes.data for s in seqs])
+    out = np.zeros(which.size, np.float32)
+    _check_rc(load().gams_host_dg_ranges(C.byref(dg.table), ptrs, which.ctypes.data, off.ctypes.data, length.ctypes.data,
+                                         which.size, threads, out.ctypes.data))
+    return out
+
+
+def fmt_dg4(v):
+    """the ΔG column's text: `{:.4}` of an f32 (half to even on the exact value, "-0.0000" keeps its sign); "" for a
+    value the device formatter does not cover (NaN, an infinity, 2^20 or more in size)"""
+    return _take(load().gams_host_fmt_dg4(float(np.float32(v))))
+
+
+def sw_gibbs(eng, ctgs, features_per_ctg, size=100, mx=20, resize=500, actions=("gc",), rg_data=None, dg=None, seqset=None):
+    """sw_multi on one handle with the ΔG of every window as a tenth field (header("sw_gibbs")): the f32 of
+    DeltaG.polymer over the window's bases with four decimals, empty for None.  The column is this project's own:
+    upstream declares `--action gibbs` and never fills it, and actions=("gibbs",) of sw / sw_multi still prints nothing.
+    dg: a DeltaG (default DeltaG()).  seqset: a resident engine.SeqSet whose slot i holds ctgs[i] (a ctg dict may name
+    another in c["slot"]); without it the ctgs carry their bases in c["seq"].  actions as for sw_multi; rg_data: the bytes
+    of one rg file, the idx:rg: source of `count` (None: every count is 0)."""
+    if isinstance(rg_data, (list, tuple)):
+        raise ValueError("sw_gibbs takes the bytes of one rg file")
+    rg_data = None if rg_data is None else bytes(rg_data)
+    mask = sw_actions(actions)
+    dg = DeltaG() if dg is None else dg
+    n, ids, chrs, st, en = _ctg_arrays(ctgs)
+    rows = "\n".join(f"{i}\t{fid}\t{s}\t{e}" for i, fl in enumerate(features_per_ctg) for fid, s, e in fl)
+    seqs = slots = None
+    if seqset is None:
+        bufs = [np.ascontiguousarray(np.frombuffer(c["seq"], np.uint8) if not isinstance(c["seq"], np.ndarray)
+                                     else c["seq"]) for c in ctgs]
+        seqs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+    else:
+        slots = np.array([c.get("slot", i) for i, c in enumerate(ctgs)], np.uint32)
+    return _take(load().gams_host_sw_gibbs(eng.h, n, ids, chrs, st.ctypes.data, en.ctypes.data, seqs, rows.encode(), size, mx,
+                                           resize, mask, rg_data, 0 if rg_data is None else len(rg_data), C.byref(dg.table),
+                                           seqset.p if seqset is not None else None,
+                                           slots.ctypes.data if slots is not None else None))
+
+
 def last_operator_ms():
     """ms the last locate / anno call of this thread spent inside the C++ operator (without the binding's copies)"""
     return float(load().gams_host_last_operator_ms())
@@ -981,8 +1076,8 @@ def ctg_json_roundtrip(json_text):
 
 
 def header(command):
-    """the header line `gams wave` / `gams sw` print before the rows"""
-    return _take(load().gams_host_header(0 if command == "wave" else 1))
+    """the header line `gams wave` / `gams sw` print before the rows; "sw_gibbs": the sw header with the ΔG column"""
+    return _take(load().gams_host_header({"wave": 0, "sw_gibbs": 2}.get(command, 1)))
 
 
 def tsv_ctgs(ctgs):

@@ -822,7 +822,43 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
                                               const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                               uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
                                               double *index_ms, const char *rg_bytes, size_t rg_n,
-                                              const std::vector<Ctg> *located_in, const std::vector<FileBytes> *rg_files);
+                                              const std::vector<Ctg> *located_in, const std::vector<FileBytes> *rg_files,
+                                              const SwGibbs *gb = nullptr);
+
+// the rows of one ctg with the ΔG of every window as a tenth field, where the host formats them: dg[r] for row r, `{:.4}`
+// (what "%.4f" of the widened value prints, whatever its size), nothing for NaN
+static std::string sw_append_dg(const std::string &rows, const float *dg) {
+    std::string out;
+    out.reserve(rows.size() + rows.size() / 6);
+    size_t at = 0, r = 0;
+    while (at < rows.size()) {
+        const size_t nl = rows.find('\n', at);
+        out.append(rows, at, nl - at);
+        out += '\t';
+        if (dg[r] == dg[r]) {
+            char buf[64];
+            out.append(buf, (size_t)snprintf(buf, sizeof buf, "%.4f", (double)dg[r]));
+        }
+        out += '\n';
+        at = nl + 1;
+        ++r;
+    }
+    return out;
+}
+
+std::vector<std::string> sw_gibbs_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                                            const std::vector<std::vector<Feature>> &features, const SwArgs &a,
+                                            const SwGibbs &gb, uint64_t batch_bytes,
+                                            const std::map<std::string, std::vector<Range>> *rgs, const char *rg_bytes,
+                                            size_t rg_n) {
+    if (!gb.table) throw Error(GAMS_EINVAL, "sw_gibbs: null table");
+    return sw_proc_ctgs_located(h, ctgs, seqs, features, a, batch_bytes, rgs, nullptr, rg_bytes, rg_n, nullptr, nullptr, &gb);
+}
+
+std::string fmt_dg4(float v) {
+    char buf[kGamsDg4MaxLen];
+    return std::string(buf, gams_fmt_dg4(v, buf));
+}
 
 std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &handles, const std::vector<Ctg> &ctgs,
                                             const std::vector<const uint8_t *> &seqs,
@@ -1188,9 +1224,11 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
                                               const std::vector<std::vector<Feature>> &features, const SwArgs &a,
                                               uint64_t batch_bytes, const std::map<std::string, std::vector<Range>> *rgs,
                                               double *index_ms, const char *rg_bytes, size_t rg_n,
-                                              const std::vector<Ctg> *located_in, const std::vector<FileBytes> *rg_files) {
+                                              const std::vector<Ctg> *located_in, const std::vector<FileBytes> *rg_files,
+                                              const SwGibbs *gb) {
     if (rgs && (rg_bytes || rg_files)) throw Error(GAMS_EINVAL, "sw: both the rg ranges and the bytes of an rg file were given");
-    if (ctgs.size() != seqs.size() || ctgs.size() != features.size())
+    gams_seqset_t *const resident = gb ? gb->resident : nullptr;   // sw_gibbs_proc_ctgs: the bases may be on the device already
+    if ((!resident && ctgs.size() != seqs.size()) || ctgs.size() != features.size())
         throw Error(GAMS_EINVAL, "sw_proc_ctgs: ctgs / seqs / features size mismatch");
     std::vector<std::string> out(ctgs.size());
     std::vector<size_t> todo;                                           // ctgs with features, in ctg order
@@ -1204,7 +1242,7 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
         size_t e = b;
         while (e < todo.size()) {
             const uint64_t len = (uint64_t)(ctgs[todo[e]].chr_end - ctgs[todo[e]].chr_start + 1);
-            if (e > b && bytes + len > batch_bytes) break;
+            if (!resident && e > b && bytes + len > batch_bytes) break;   // (a resident seqset: one batch)
             bytes += len;
             ++e;
         }
@@ -1216,8 +1254,8 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
         for (uint32_t k = 0; k < n; ++k) {
             const Ctg &c = ctgs[todo[b + k]];
             lens[k] = (uint32_t)(c.chr_end - c.chr_start + 1);
-            ptrs[k] = seqs[todo[b + k]];
-            index[k] = k;
+            ptrs[k] = resident ? nullptr : seqs[todo[b + k]];
+            index[k] = resident ? (gb->slots ? gb->slots[todo[b + k]] : (uint32_t)todo[b + k]) : k;
             chr_start[k] = c.chr_start;
             feat_off[k + 1] = feat_off[k] + features[todo[b + k]].size();
         }
@@ -1232,15 +1270,16 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
         std::vector<uint32_t> rg_group(do_count ? n : 0);
         for (uint32_t k = 0; k < rg_group.size(); ++k) rg_group[k] = rx.group[todo[b + k]];
         SeqSetGuard sg{h};
-        check(h, gams_seqset_create(h, n, lens.data(), &sg.s));
-        // -a count alone reads no sequence byte on the device path: the bases go up only when a gc or the rows of
-        // the fallback below need them
-        bool uploaded = false;
+        if (!resident) check(h, gams_seqset_create(h, n, lens.data(), &sg.s));
+        gams_seqset_t *const set = resident ? resident : sg.s;
+        // -a count alone reads no sequence byte on the device path: the bases go up only when a gc, the ΔG column or the
+        // rows of the fallback below need them
+        bool uploaded = resident != nullptr;
         auto upload = [&]() {
-            if (!uploaded) check(h, gams_seqset_upload_all(h, sg.s, ptrs.data()));
+            if (!uploaded) check(h, gams_seqset_upload_all(h, set, ptrs.data()));
             uploaded = true;
         };
-        if (a.actions & GAMS_SW_GC) upload();
+        if ((a.actions & GAMS_SW_GC) || gb) upload();
         std::vector<uint64_t> row_off(n + 1, 0);
         uint64_t nrows = 0;
         {
@@ -1255,9 +1294,12 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
             const char *text = nullptr;
             uint64_t tbytes = 0;
             const uint64_t *toff = nullptr;
-            const int rc = gams_gpu_sw_text_actions(h, sg.s, n, index.data(), chr.data(), chr_start.data(), feat_off.data(),
+            const int rc = gb ? gams_gpu_sw_text_dg(h, set, n, index.data(), chr.data(), chr_start.data(), feat_off.data(),
                                                     fs.data(), fe.data(), ids.data(), a.size, a.max, a.resize, a.actions,
-                                                    rx.ix, rg_group.data(), &text, &tbytes, &toff, &nrows);
+                                                    rx.ix, rg_group.data(), gb->table, &text, &tbytes, &toff, &nrows)
+                              : gams_gpu_sw_text_actions(h, set, n, index.data(), chr.data(), chr_start.data(), feat_off.data(),
+                                                         fs.data(), fe.data(), ids.data(), a.size, a.max, a.resize, a.actions,
+                                                         rx.ix, rg_group.data(), &text, &tbytes, &toff, &nrows);
             if (rc == GAMS_OK) {
                 // proc_ctg's Strings: slices of the page-locked text, copied by a few host threads (one thread moves
                 // ~10 GB/s; 313 MB for the 4.1 M rows of a 30-Mb chromosome)
@@ -1270,7 +1312,7 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
             if (rc != GAMS_EUNSUPPORTED) check(h, rc);
         }
         upload();
-        check(h, gams_gpu_sw_batch(h, sg.s, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
+        check(h, gams_gpu_sw_batch(h, set, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
                                    a.size, a.max, a.resize, nullptr, 0, row_off.data(), &nrows));
         // rows land in page-locked memory: the readback runs at the rate of the link
         struct Pinned {
@@ -1280,18 +1322,23 @@ static std::vector<std::string> sw_proc_ctgs_located(gams_gpu_t *h, const std::v
         } pin{h};
         check(h, gams_gpu_host_alloc(h, std::max<uint64_t>(nrows, 1) * sizeof(gams_sw_row_t), &pin.p));
         gams_sw_row_t *rows = static_cast<gams_sw_row_t *>(pin.p);
-        check(h, gams_gpu_sw_batch(h, sg.s, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
+        check(h, gams_gpu_sw_batch(h, set, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
                                    a.size, a.max, a.resize, rows, nrows, row_off.data(), &nrows));
         std::vector<int32_t> cnt(do_count ? std::max<uint64_t>(nrows, 1) : 0);
         if (do_count)
-            check(h, gams_gpu_sw_count_batch(h, sg.s, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
+            check(h, gams_gpu_sw_count_batch(h, set, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
                                              a.size, a.max, rx.ix, rg_group.data(), cnt.data(), nrows, nullptr, &nrows));
+        std::vector<float> dg(gb ? std::max<uint64_t>(nrows, 1) : 0);
+        if (gb)
+            check(h, gams_gpu_sw_dg_batch(h, set, n, index.data(), chr_start.data(), feat_off.data(), fs.data(), fe.data(),
+                                          a.size, a.max, gb->table, dg.data(), nrows, nullptr, &nrows));
         // format: ctgs of the batch dealt to a few host threads
         const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>({16, std::thread::hardware_concurrency(), (uint64_t)n}));
         parallel_for(n, T, [&](uint32_t k) {
             out[todo[b + k]] = sw_format_rows(rows + row_off[k], row_off[k + 1] - row_off[k], ctgs[todo[b + k]],
                                               features[todo[b + k]], T > 1 ? 1 : 8, a.actions,
                                               do_count ? cnt.data() + row_off[k] : nullptr);
+            if (gb) out[todo[b + k]] = sw_append_dg(out[todo[b + k]], dg.data() + row_off[k]);
         });
         b = e;
     }

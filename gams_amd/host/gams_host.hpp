@@ -172,6 +172,28 @@ std::vector<std::string> sw_proc_ctgs_multi(const std::vector<gams_gpu_t *> &han
                                             double *index_ms = nullptr, const char *rg_bytes = nullptr, size_t rg_n = 0,
                                             const std::vector<FileBytes> *rg_files = nullptr);
 
+// sw_proc_ctgs with the nearest-neighbour ΔG (delta_g.rs) of every window as a tenth field, `{:.4}` and empty for None
+// (DESIGN.md 3.3e): gams_gpu_sw_text_dg over the same batching, on one handle.  The column is this project's own: upstream
+// declares `--action gibbs` and never fills it.  table: the terms (gams_dg_table).  resident, where given, is a seqset
+// that holds the ctgs' bases already -- ctg i in slot slots[i] (NULL: slot i) -- and `seqs` is not read; every ctg then
+// goes in one batch.  Where the device text refuses (GAMS_EUNSUPPORTED) the rows are formatted here, the column from
+// gams_gpu_sw_dg_batch.
+struct SwGibbs {
+    const gams_dg_table_t *table = nullptr;
+    gams_seqset_t *resident = nullptr;
+    const uint32_t *slots = nullptr;
+};
+std::vector<std::string> sw_gibbs_proc_ctgs(gams_gpu_t *h, const std::vector<Ctg> &ctgs, const std::vector<const uint8_t *> &seqs,
+                                            const std::vector<std::vector<Feature>> &features, const SwArgs &a,
+                                            const SwGibbs &gb, uint64_t batch_bytes = 256ull << 20,
+                                            const std::map<std::string, std::vector<Range>> *rgs = nullptr,
+                                            const char *rg_bytes = nullptr, size_t rg_n = 0);
+inline std::string sw_gibbs_header() {
+    return "id\trange\ttype\tdistance\tgc_content\tgc_mean\tgc_stddev\tgc_cv\trg_count\tgibbs\n";
+}
+// the ΔG column's text: `{:.4}` of an f32 below 2^20 in size (gams_fmt_dg4); "" for anything else
+std::string fmt_dg4(float v);
+
 // what read_range_text returns: the buckets of read_range as arrays.  Bucket k belongs to ctg ids[k] (ctg-id order, the
 // order of the reference's BTreeMap; a ctg with one located line has a bucket, and it is empty) and holds
 // start/end/line[off[k] .. off[k+1]) in file order; line = the 0-based line number of the range in the file.

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <sstream>
+#include <thread>
 
 #include "gams_host.hpp"
 
@@ -578,6 +579,27 @@ char *gams_host_sw_multi_actions_rg(gams_gpu_t *const *handles, uint32_t n_handl
     });
 }
 
+// gams::sw_gibbs_proc_ctgs on one handle: the rows of gams_host_sw_multi_actions with the ΔG of every window as a tenth
+// field.  table: the 21 terms (gams_dg_table_t); the idx:rg: source of GAMS_SW_COUNT: the rg_n bytes of an rg file
+// (rg_data == NULL: no rg range, every count is 0); seqset != NULL: the bases are resident, ctg i in slot slots[i]
+// (NULL: i), and seqs is not read.
+char *gams_host_sw_gibbs(gams_gpu_t *h, uint32_t n, const char *const *ids, const char *const *chrs, const int32_t *starts,
+                         const int32_t *ends, const uint8_t *const *seqs, const char *features, int32_t size, int32_t max,
+                         int32_t resize, uint32_t actions, const char *rg_data, uint64_t rg_n,
+                         const gams_dg_table_t *table, gams_seqset_t *seqset, const uint32_t *slots) {
+    return guarded([&] {
+        const std::map<std::string, std::vector<gams::Range>> rg_of = rg_index_of(n, ids, nullptr);   // every ctg an empty group
+        gams::SwGibbs gb;
+        gb.table = table;
+        gb.resident = seqset;
+        gb.slots = slots;
+        return join(gams::sw_gibbs_proc_ctgs(h, make_ctgs(n, ids, chrs, starts, ends),
+                                             seqset ? std::vector<const uint8_t *>() : std::vector<const uint8_t *>(seqs, seqs + n),
+                                             sw_feature_rows(n, features), sw_args(size, max, resize, actions), gb, 256ull << 20,
+                                             rg_data ? nullptr : &rg_of, rg_data, (size_t)rg_n));
+    });
+}
+
 // ... with several rg files (as gams_host_locate_rgs takes them)
 char *gams_host_sw_actions_rgs(gams_gpu_t *h, const char *ctg_id, const char *chr, int32_t chr_start, int32_t chr_end,
                                const uint8_t *seq, uint32_t nf, const char *const *feature_ids, const int32_t *fs,
@@ -750,6 +772,23 @@ int64_t gams_host_runlist_load(gams_gpu_t *h, const char *data, uint64_t n_bytes
 
 // `{:.4}` of an anno prop as the device formats it ("" outside [0, 1])
 char *gams_host_fmt_prop4(float p) { return dup(gams::fmt_prop4(p)); }
+char *gams_host_fmt_dg4(float v) { return dup(gams::fmt_dg4(v)); }
+// For measurement only, like the _timed entries of this file; no operator calls it.  gams_dg_polymer_host over n ranges on
+// `threads` host threads, what a host without the device would run (tools/bench_dg.py measures the device entries
+// against it through host.dg_ranges_host): dg[q] of the len[q] bytes at seqs[which[q]] + off[q]
+int gams_host_dg_ranges(const gams_dg_table_t *table, const uint8_t *const *seqs, const uint32_t *which, const uint64_t *off,
+                        const uint32_t *len, uint64_t n, uint32_t threads, float *dg) {
+    if (!table || !dg || (n && (!seqs || !which || !off || !len))) return GAMS_EINVAL;
+    const uint32_t T = threads ? threads : 1u;
+    std::vector<std::thread> pool;
+    for (uint32_t t = 0; t < T; ++t)
+        pool.emplace_back([=] {
+            for (uint64_t q = n * t / T; q < n * (t + 1) / T; ++q)
+                (void)gams_dg_polymer_host(table, seqs[which[q]] + off[q], len[q], &dg[q]);
+        });
+    for (std::thread &th : pool) th.join();
+    return GAMS_OK;
+}
 // `{}` of an f32 in [0, 1] as the device formats a peak amplitude ("" where it refuses)
 char *gams_host_fmt_f32_short(float v) { return dup(gams::fmt_f32_short(v)); }
 
@@ -1262,7 +1301,10 @@ char *gams_host_tsv_ctgs(uint32_t n, const char *const *ids, const char *const *
 }
 
 // header lines of `gams wave` (which == 0) and `gams sw` (which == 1)
-char *gams_host_header(int which) { return dup(which == 0 ? gams::wave_header() : gams::sw_header()); }
+char *gams_host_header(int which) {   // 0 wave, 1 sw, 2 sw with the ΔG column
+    if (which == 2) return dup(gams::sw_gibbs_header());
+    return dup(which == 0 ? gams::wave_header() : gams::sw_header());
+}
 
 // locate --count / anno coverage over several handles (one per GPU)
 int gams_host_count_multi(gams_gpu_t *const *handles, uint32_t n_handles, uint32_t n_groups, const uint64_t *group_off,

@@ -17,6 +17,8 @@
  *   gams_gpu_sw(_batch, _text) src/cmd_gams/sw.rs:141-184   (center_sw + cache_gc_content + cache_gc_stat; _text: + the rows' text, :152-190)
  *   gams_gpu_sw_text_actions, gams_gpu_sw_count_batch: + rg_count (sw.rs:28-32 `--action count`, fixed as count_rg)
  *                             = src/libs/window.rs:3-56,96-124, src/libs/utils.rs:141-213
+ *   gams_dg_*, gams_gpu_range_dg_batch, gams_gpu_sw_dg_batch, gams_gpu_sw_text_dg: src/libs/delta_g.rs (DeltaG::polymer; as a
+ *                             column of sw it is this project's own: `--action gibbs` is declared upstream and never filled)
  *   gams_gpu_count            src/libs/utils.rs:24-36       (count_rg -> Lapper::count)
  *   gams_gpu_locate           src/libs/utils.rs:7-22        (find_one_idx -> Lapper::find().next())
  *   gams_gpu_cover            src/cmd_gams/anno.rs:128-139  (IntSpan intersect cardinalities)
@@ -375,6 +377,48 @@ int gams_gpu_range_gc(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_s
 int gams_gpu_range_gc_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                             const int32_t *chr_start, const uint64_t *range_off, const int32_t *range_start,
                             const int32_t *range_end, float *gc);
+
+/* ---- nearest-neighbour free energy (src/libs/delta_g.rs: DeltaG) of ranges and sw windows ----
+ * The ΔG of a polymer is the sum of its dimers' terms, in sequence order and in f32, then the terminal terms of its first
+ * and last base, then the symmetry term when it equals its reverse complement (delta_g.rs:78-115).  None -- fewer than 3
+ * bases, or a byte that is none of ACGTacgt -- is a quiet NaN here.  The 21 terms depend on temperature and salt alone:
+ * the host makes them once and every call takes them as data, so an answer is a function of (table, bytes). */
+typedef struct {
+    float nn[16];  /* dimer XY at 4 * c(X) + c(Y), A C G T = 0 1 2 3 */
+    float init[4]; /* terminal term by base */
+    float sym;     /* symmetry term */
+} gams_dg_table_t;
+/* init_delta_g (delta_g.rs:118-207) in f32, the reference's order.  Host code, no device involved.  GAMS_EINVAL for a
+ * non-finite temp, and for a non-finite salt or salt <= 0.  DeltaG::new() is (37, 1). */
+int gams_dg_table(float temp, float salt, gams_dg_table_t *table);
+/* DeltaG::polymer over n bytes, *dg = NaN for None: the host twin of the device entries below, bit for bit.  Host code;
+ * any length. */
+int gams_dg_polymer_host(const gams_dg_table_t *table, const uint8_t *seq, uint64_t n, float *dg);
+/* The ΔG of chromosome ranges inside ctgs of the seqset, in one launch: arguments, checks, codes and messages as for
+ * gams_gpu_range_gc_batch; dg[q] for range q of the concatenated list.  GAMS_EINVAL also for a NULL table or a table with
+ * a non-finite entry, GAMS_EUNSUPPORTED for a range of more than 65535 bases (the sum is one serial chain: this is for
+ * oligos and windows), GAMS_ESTATE for a plane-only seqset. */
+int gams_gpu_range_dg_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                            const int32_t *chr_start, const uint64_t *range_off, const int32_t *range_start,
+                            const int32_t *range_end, const gams_dg_table_t *table, float *dg);
+/* The ΔG of every window of gams_gpu_sw_batch (same arguments without resize, same row order, row_off and size query:
+ * dg == NULL or cap == 0): dg[r] = the ΔG of the bases [start, end] of row r, the window its range column prints.
+ * Table, length limit and plane-only seqsets as for gams_gpu_range_dg_batch. */
+int gams_gpu_sw_dg_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                         const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start,
+                         const int32_t *feat_end, int32_t size, int32_t max, const gams_dg_table_t *table, float *dg,
+                         uint64_t cap, uint64_t *row_off, uint64_t *n_rows);
+/* gams_gpu_sw_text_actions with the ΔG of every window as a tenth field: every row ends "...\t{rg_count}\t{dg}\n", dg the
+ * f32 of gams_gpu_sw_dg_batch printed with four decimals ({:.4}: the exact value rounded half to even, "-0.0000" keeps its
+ * sign) and empty for None.  Action sets, checks, output and ownership as for gams_gpu_sw_text_actions (the text lives in
+ * the same buffer of the handle, valid until its next sw text call); the column always reads the sequence bytes.
+ * GAMS_EUNSUPPORTED also when some |dg| reaches 2^20, which takes a caller's own table. */
+int gams_gpu_sw_text_dg(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                        const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
+                        const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
+                        int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
+                        const uint32_t *rg_group, const gams_dg_table_t *table, const char **text,
+                        uint64_t *text_bytes, const uint64_t **ctg_off, uint64_t *n_rows);
 
 /* ---- sorted-interval index (replaces rust_lapper `idx:`) ---------------- */
 /* m intervals [start, stop) (stop = end+1, redis.rs:245-248,291-294) grouped

@@ -150,6 +150,15 @@ int gams_seq_gz_host_indexed_block(const uint8_t *seq, uint64_t n, uint32_t bloc
 int gams_seq_gz_host_indexed_chunk(const uint8_t *seq, uint64_t n, uint32_t block, uint32_t chunk, uint8_t *out, uint64_t cap,
                                    uint64_t *n_out);
 int gams_gpu_seq_gz_set_chunk(gams_gpu_t *h, uint32_t chunk);
+/* The ΔG kernel (gams_gpu_range_dg_batch and the sw entries above it) walks a range in stages of this many bases' worth of
+ * aligned 16-B pieces, staged as 2-bit codes in LDS: a range crosses a stage seam every GAMS_DG_STAGE_BASES bases counted
+ * from the 16-B boundary at or below its first base.  For tests that place ranges on the seams. */
+#define GAMS_DG_STAGE_BASES 512
+/* Where the walk finds the sixteen dimer terms: in LDS (the default) or in a register per lane, read with ds_bpermute.
+ * Both give the same bits; for measuring one against the other.  GAMS_EINVAL for another value. */
+#define GAMS_DG_TABLE_LDS 0
+#define GAMS_DG_TABLE_BPERMUTE 1
+int gams_gpu_dg_set_table(gams_gpu_t *h, int placement);
 
 #ifdef __cplusplus
 }
