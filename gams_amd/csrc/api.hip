@@ -268,7 +268,8 @@ int gams_seqset_create(gams_gpu_t *h, uint32_t n_ctg, const uint32_t *lengths, g
         delete s;
         return gams_fail(h, GAMS_EHIP, std::string("seqset_create: memset: ") + hipGetErrorString(e));
     }
-    // readers on the compute stream order themselves behind the memset like behind an upload
+    // readers on the compute stream order themselves behind the memset like behind an upload (the seqset protocol,
+    // common.hpp; lines of its own, not gams_seqset_write_end: this site alone tolerates a failed event creation)
     if (hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming) == hipSuccess &&
         hipEventRecord(s->uploaded, h->copy) == hipSuccess)
         s->dirty = true;
@@ -282,23 +283,12 @@ int gams_seqset_upload(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, const uint8_
     if (i >= s->n_ctg) return gams_fail(h, GAMS_EINVAL, "seqset_upload: ctg index out of range");
     GAMS_HIP(h, hipSetDevice(h->device));
     if (s->len[i] == 0) return GAMS_OK;
-    if (s->gcindex) {
-        GAMS_HIP(h, hipStreamSynchronize(h->compute));
-        gams_seqset_gcindex_free(s);  // the bytes it indexed are about to change
-    }
     // Pageable host memory -> pinned ring -> HBM: the call returns once the last piece is queued;
     // the host memcpy of piece k+1 overlaps the DMA of piece k.  Kernels that read the seqset
-    // wait on s->uploaded (gams_seqset_wait_uploads), not the host.
-    {
-        int rc = gams_stage_ring(h);
-        if (rc != GAMS_OK) return rc;
-    }
-    if (!s->uploaded) GAMS_HIP(h, hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
-    // passes queued earlier on any stream of the handle may still be reading these bytes
-    {
-        int rc = gams_order_after_readers(h, h->copy);
-        if (rc != GAMS_OK) return rc;
-    }
+    // wait on s->uploaded (gams_seqset_read_begin), not the host.
+    int rc = gams_stage_ring(h);
+    if (rc == GAMS_OK) rc = gams_seqset_write_begin(h, s, h->copy);
+    if (rc != GAMS_OK) return rc;
     const uint64_t len = s->len[i];
     for (uint64_t o = 0; o < len; o += gams_gpu::kStageBytes) {
         const size_t n = (size_t)std::min<uint64_t>(gams_gpu::kStageBytes, len - o);
@@ -312,10 +302,7 @@ int gams_seqset_upload(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, const uint8_
         GAMS_HIP(h, hipMemcpyAsync(s->d_plane + ((s->off[i] + o) >> 3), pl, (n + 7) / 8, hipMemcpyHostToDevice, h->copy));
         GAMS_HIP(h, hipEventRecord(h->stage_free[k], h->copy));
     }
-    GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
-    s->dirty = true;
-    ++s->upload_gen;
-    return GAMS_OK;
+    return gams_seqset_write_end(h, s, h->copy);
 }
 
 int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const *seqs) {
@@ -324,15 +311,9 @@ int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const
         if (s->len[i] && !seqs[i]) return gams_fail(h, GAMS_EINVAL, "seqset_upload_all: null sequence");
     GAMS_HIP(h, hipSetDevice(h->device));
     if (s->n_ctg == 0) return GAMS_OK;
-    if (s->gcindex) {
-        GAMS_HIP(h, hipStreamSynchronize(h->compute));
-        gams_seqset_gcindex_free(s);
-    }
-    {
-        int rc = gams_stage_ring(h);
-        if (rc != GAMS_OK) return rc;
-    }
-    if (!s->uploaded) GAMS_HIP(h, hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
+    int rc = gams_stage_ring(h);
+    if (rc == GAMS_OK) rc = gams_seqset_write_begin(h, s, h->copy);
+    if (rc != GAMS_OK) return rc;
     // The staging slots mirror the device layout (ctgs on 256-B boundaries, gaps zeroed), so one
     // window of kStageBytes is one DMA.  Worker t owns slot t and takes windows t, t+T, ...: its
     // memcpy of the next window overlaps the DMAs the other workers queued.
@@ -347,13 +328,8 @@ int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const
     // odd slots go through a second stream (a second DMA engine) -- the readback stream, idle during
     // an upload; a stream of its own would cost one more of the few hardware queues HIP maps
     // streams onto (GPU_MAX_HW_QUEUES, 4 by default).  It starts behind whatever `copy` already
-    // holds for this seqset (the memset of gams_seqset_create, earlier uploads).
+    // holds for this seqset (the memset of gams_seqset_create, earlier uploads, the readers write_begin queued it behind).
     hipStream_t second = h->readback;
-    // passes queued earlier on any stream of the handle may still be reading these bytes
-    {
-        int rc = gams_order_after_readers(h, h->copy);
-        if (rc != GAMS_OK) return rc;
-    }
     GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
     GAMS_HIP(h, hipStreamWaitEvent(second, s->uploaded, 0));
     // staged bytes [x0, x1) of a window are a gap: zero them and their plane bytes (x0 follows a ctg's last base,
@@ -407,9 +383,7 @@ int gams_seqset_upload_all(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *const
     }
     GAMS_HIP(h, hipEventRecord(h->copy2_ev, second));
     GAMS_HIP(h, hipStreamWaitEvent(h->copy, h->copy2_ev, 0));
-    GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
-    s->dirty = true;
-    ++s->upload_gen;
+    if ((rc = gams_seqset_write_end(h, s, h->copy)) != GAMS_OK) return rc;
     s->plane_ok = s->have_bytes = true;   // every ctg, bytes and plane
     return GAMS_OK;
 }
@@ -434,19 +408,9 @@ int gams_seqset_upload_ranges(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *im
     if (plane_image && (lo & 7u)) return gams_fail(h, GAMS_EINVAL, "seqset_upload_ranges: lo must be a multiple of 8");
     GAMS_HIP(h, hipSetDevice(h->device));
     if (lo == hi) return GAMS_OK;
-    if (s->gcindex) {
-        GAMS_HIP(h, hipStreamSynchronize(h->compute));
-        gams_seqset_gcindex_free(s);  // the bytes it indexed are about to change
-    }
-    if (!s->uploaded) GAMS_HIP(h, hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
-    // passes queued earlier on any stream of the handle may still be reading these bytes; once per
-    // generation of readers is enough, so only the first range of a burst pays the four event pairs
-    const uint64_t epoch = h->reader_epoch.load(std::memory_order_relaxed);
-    if (s->ordered_epoch != epoch) {
-        int rc = gams_order_after_readers(h, h->copy);
-        if (rc != GAMS_OK) return rc;
-        s->ordered_epoch = epoch;
-    }
+    // (once per generation of readers: only the first range of a burst pays the four event pairs)
+    const int rc = gams_seqset_write_begin(h, s, h->copy, true);
+    if (rc != GAMS_OK) return rc;
     // A pass must never read a plane that does not describe the bytes: bytes that come without their plane
     // leave it stale, a plane that comes without its bytes leaves a plane-only seqset, until gams_seqset_upload_all
     // or a range that covers every ctg brings the missing half again
@@ -458,10 +422,7 @@ int gams_seqset_upload_ranges(gams_gpu_t *h, gams_seqset_t *s, const uint8_t *im
                                    hipMemcpyHostToDevice, h->copy));
     s->have_bytes = image ? (s->have_bytes || whole) : false;
     s->plane_ok = plane_image ? (s->plane_ok || whole) : false;
-    GAMS_HIP(h, hipEventRecord(s->uploaded, h->copy));
-    s->dirty = true;
-    ++s->upload_gen;
-    return GAMS_OK;
+    return gams_seqset_write_end(h, s, h->copy);
 }
 
 int gams_seqset_download(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, uint8_t *seq, uint8_t *plane) {
@@ -556,7 +517,9 @@ int gams_stage_ring(gams_gpu_t *h) {
     return GAMS_OK;
 }
 
-int gams_order_after_readers(gams_gpu_t *h, hipStream_t st) {
+// ---- the seqset protocol: common.hpp states it above the declarations
+// make `st` wait for everything queued so far on the compute and auxiliary streams
+static int gams_order_after_readers(gams_gpu_t *h, hipStream_t st) {
     for (int k = 0; k < gams_gpu::kMaxWays; ++k) {
         hipStream_t src = k == 0 ? h->compute : h->aux[k - 1];
         if (!src) continue;
@@ -565,6 +528,32 @@ int gams_order_after_readers(gams_gpu_t *h, hipStream_t st) {
         GAMS_HIP(h, hipStreamWaitEvent(st, h->rd_ev[k], 0));
     }
     return GAMS_OK;
+}
+
+int gams_seqset_write_begin(gams_gpu_t *h, gams_seqset_t *s, hipStream_t st, bool once_per_epoch) {
+    if (s->gcindex) {
+        GAMS_HIP(h, hipStreamSynchronize(h->compute));
+        gams_seqset_gcindex_free(s);  // the bytes it indexed are about to change
+    }
+    if (!s->uploaded) GAMS_HIP(h, hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
+    // passes queued earlier on any stream of the handle may still be reading these bytes
+    const uint64_t epoch = h->reader_epoch.load(std::memory_order_relaxed);
+    if (once_per_epoch && s->ordered_epoch == epoch) return GAMS_OK;
+    const int rc = gams_order_after_readers(h, st);
+    if (rc == GAMS_OK && once_per_epoch) s->ordered_epoch = epoch;
+    return rc;
+}
+
+int gams_seqset_write_end(gams_gpu_t *h, gams_seqset_t *s, hipStream_t st) {
+    GAMS_HIP(h, hipEventRecord(s->uploaded, st));
+    s->dirty = true;
+    ++s->upload_gen;
+    return GAMS_OK;
+}
+
+int gams_seqset_read_begin(gams_gpu_t *h, gams_seqset_t *s) {
+    h->reader_epoch.fetch_add(1, std::memory_order_relaxed);
+    return gams_seqset_wait_uploads(h, s);
 }
 
 int gams_seqset_wait_uploads(gams_gpu_t *h, gams_seqset_t *s) {

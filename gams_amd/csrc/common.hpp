@@ -243,11 +243,25 @@ struct gams_seqset {
     gams_gcindex *gcindex = nullptr;  // built lazily by gams_gpu_sw, dropped by every upload
 };
 
-// make the compute stream wait for every upload queued so far (no host blocking)
-int gams_seqset_wait_uploads(gams_gpu_t *h, gams_seqset_t *s);
+// The seqset protocol (api.hip).  d_seq / d_plane are written on one stream and read on others, and only events order them.
+//   A writer (an upload, the device inflate, the place stage of gen) brackets what it queues on its stream `st`:
+//   gams_seqset_write_begin drops the G/C index of the old bytes (after draining `compute`, which may still use it), makes
+//   sure `uploaded` exists and queues `st` behind everything queued so far on the streams that run readers (`compute` and
+//   the auxiliary ones); gams_seqset_write_end records `uploaded` on `st`, sets `dirty` and counts the upload in
+//   `upload_gen`.  Nothing else writes the two buffers or these fields (gams_seqset_create, whose buffers nobody has seen
+//   yet, keeps lines of its own).
+//   A reader on the compute stream calls gams_seqset_read_begin before it queues a kernel that reads either buffer: it
+//   bumps gams_gpu::reader_epoch and, if the seqset is `dirty`, makes `compute` wait for `uploaded`.  (The ways of a wave
+//   plan run on streams of their own and compare `upload_gen`: wave.hip, which bumps the epoch itself and calls
+//   gams_seqset_wait_uploads, the wait alone, on its compute branch.)
+//   The epoch is what lets a burst of gams_seqset_upload_ranges calls pay the ordering once (once_per_epoch): a writer that
+//   ordered itself at epoch e is still behind every reader while the epoch is e.  That holds only if EVERY reader bumps it,
+//   which is why readers go through the one gate and do not type the two steps out.
+int gams_seqset_write_begin(gams_gpu_t *h, gams_seqset_t *s, hipStream_t st, bool once_per_epoch = false);
+int gams_seqset_write_end(gams_gpu_t *h, gams_seqset_t *s, hipStream_t st);
+int gams_seqset_read_begin(gams_gpu_t *h, gams_seqset_t *s);
+int gams_seqset_wait_uploads(gams_gpu_t *h, gams_seqset_t *s);   // the wait of read_begin without the bump: wave.hip only
 int gams_stage_ring(gams_gpu_t *h);   // allocate the pinned staging slots on first use
-// make `st` (a copy stream) wait for everything queued so far on the compute and auxiliary streams
-int gams_order_after_readers(gams_gpu_t *h, hipStream_t st);
 int gams_seqset_gcindex(gams_gpu_t *h, gams_seqset_t *s);
 void gams_seqset_gcindex_free(gams_seqset_t *s);
 // sw.hip, for text.hip: gc[q] = round4(gc_content) of chromosome range [rs[q], re[q]] inside the ctg rctg[q] names,
@@ -266,8 +280,8 @@ int gams_dg_table_check(gams_gpu_t *h, const std::string &who, const gams_dg_tab
 int gams_dg_seq_ready(gams_gpu_t *h, gams_seqset_t *s);
 void gams_launch_dg(gams_gpu_t *h, const gams_seqset_t *s, const unsigned long long *d_off, const uint32_t *d_len, uint32_t n,
                     const gams_dg_table_t *d_table, float *d_dg);
-// sw.hip, for dg.hip: the selected ctgs of a batch call against the seqset, `off` (named off_name in the messages) from 0
-// and not decreasing -- the check gams_gpu_range_gc_batch makes, under the entry `who` names
+// sw.hip, for range_batch.hpp as well: the selected ctgs of a batch call against the seqset, `off` (named off_name in the
+// messages) from 0 and not decreasing, under the entry `who` names
 int gams_sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
                             const uint32_t *ctg_index, const uint64_t *off);
 

@@ -20,6 +20,7 @@
 // Every LDS word read was written in this launch: the flags and the table at its top, the codes by the stage in front.
 #include "common.hpp"
 #include "dg_code.hpp"
+#include "range_batch.hpp"
 
 #include <cmath>
 #include <string>
@@ -126,8 +127,7 @@ int gams_dg_table_check(gams_gpu_t *h, const std::string &who, const gams_dg_tab
 
 int gams_dg_seq_ready(gams_gpu_t *h, gams_seqset_t *s) {
     if (!s->have_bytes) return gams_fail(h, GAMS_ESTATE, "the seqset holds the G/C plane only: this call needs the sequence bytes");
-    h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the kernel reads the sequence bytes
-    return gams_seqset_wait_uploads(h, s);
+    return gams_seqset_read_begin(h, s);
 }
 
 void gams_launch_dg(gams_gpu_t *h, const gams_seqset_t *s, const unsigned long long *d_off, const uint32_t *d_len, uint32_t n,
@@ -147,71 +147,40 @@ extern "C" int gams_gpu_dg_set_table(gams_gpu_t *h, int placement) {
     return GAMS_OK;
 }
 
-extern "C" int gams_gpu_range_dg_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
-                                       const int32_t *chr_start, const uint64_t *range_off, const int32_t *range_start,
-                                       const int32_t *range_end, const gams_dg_table_t *table, float *dg) {
-    if (!h || !s || (n_sel && (!ctg_index || !chr_start || !range_off)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_range_dg: null argument");
-    int rc = gams_dg_table_check(h, kRangeDg, table);
-    if (rc != GAMS_OK) return rc;
-    if (n_sel == 0) return GAMS_OK;
-    if ((rc = gams_sw_check_selection(h, kRangeDg, "range_off", s, n_sel, ctg_index, range_off)) != GAMS_OK) return rc;
-    const uint64_t n64 = range_off[n_sel];
-    if (n64 == 0) return GAMS_OK;
-    if (!range_start || !range_end || !dg) return gams_fail(h, GAMS_EINVAL, "gpu_range_dg: null argument");
-    if (n64 > 0x7fffff00ull) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_range_dg: too many ranges for one launch");
-    const uint32_t n = (uint32_t)n64;
-    GAMS_HIP(h, hipSetDevice(h->device));
-    // inputs in one page-locked block (one DMA): table | off | len; results in the same device block
-    struct Cols {
-        gams_dg_table_t *table;
-        unsigned long long *off;
-        uint32_t *len;
-    };
-    auto inputs = [&](Carver &c) {
-        Cols k{};
+namespace {
+struct DgCols {   // table | off | len
+    gams_dg_table_t *table;
+    unsigned long long *off;
+    uint32_t *len;
+};
+struct RangeDgEntry {   // what gams_range_batch (range_batch.hpp) asks of an entry
+    gams_gpu_t *h;
+    const RangeBatch &b;
+    const gams_dg_table_t *table;
+    int admit() const { return gams_dg_table_check(h, kRangeDg, table); }
+    DgCols inputs(Carver &c, uint32_t n) const {
+        DgCols k{};
         k.table = c.take<gams_dg_table_t>(1);
         k.off = c.take<unsigned long long>(n);
         k.len = c.take<uint32_t>(n);
         return k;
-    };
-    const size_t in_bytes = layout_bytes(inputs);
-    PoolBlock dev(h, false), pin(h, true);
-    GAMS_TRY(h, kRangeDg, pin.alloc(in_bytes));
-    const Cols in = carve(pin.p, inputs);
-    *in.table = *table;
-    for (uint32_t k = 0; k < n_sel; ++k) {
-        const uint32_t i = ctg_index[k];
-        const int32_t cs = chr_start[k];
-        const int64_t ce = (int64_t)cs + s->len[i] - 1;
-        for (uint64_t q = range_off[k]; q < range_off[k + 1]; ++q) {
-            const std::string which = "gpu_range_dg: range " + std::to_string(q - range_off[k]) +
-                                      (n_sel > 1 ? " of selected ctg " + std::to_string(k) : std::string());
-            if (range_start[q] < cs || range_end[q] > ce || range_end[q] < range_start[q])
-                return gams_fail(h, GAMS_EINVAL, which + " is not inside the ctg");
-            const uint64_t bases = (uint64_t)((int64_t)range_end[q] - range_start[q]) + 1u;
-            if (bases > kDgMaxBases) return gams_fail(h, GAMS_EUNSUPPORTED, which + " has more than 65535 bases");
-            in.off[q] = s->off[i] + (uint64_t)((int64_t)range_start[q] - cs);
-            in.len[q] = (uint32_t)bases;
-        }
     }
-    if ((rc = gams_dg_seq_ready(h, s)) != GAMS_OK) return rc;
-    Cols d{};
-    float *d_dg = nullptr;
-    auto device = [&](Carver &c) {   // the inputs | results
-        d = inputs(c);
-        d_dg = c.take<float>(n);
-    };
-    GAMS_TRY(h, kRangeDg, dev.alloc(layout_bytes(device)));
-    carve(dev.p, device);
-    GAMS_TRY(h, kRangeDg, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
-    GAMS_TRY(h, kRangeDg, hipEventRecord(h->k0, h->compute));
-    gams_launch_dg(h, s, d.off, d.len, n, d.table, d_dg);
-    GAMS_TRY(h, kRangeDg, hipGetLastError());
-    GAMS_TRY(h, kRangeDg, hipEventRecord(h->k1, h->compute));
-    h->k_valid = true;
-    h->kq_used = 0;
-    GAMS_TRY(h, kRangeDg, hipMemcpyAsync(dg, d_dg, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->compute));
-    GAMS_TRY(h, kRangeDg, hipStreamSynchronize(h->compute));
-    return GAMS_OK;
+    void head(const DgCols &in) const { *in.table = *table; }
+    int range(const DgCols &in, uint32_t k, uint64_t q) const {
+        const uint64_t bases = (uint64_t)((int64_t)b.range_end[q] - b.range_start[q]) + 1u;
+        if (bases > kDgMaxBases) return gams_fail(h, GAMS_EUNSUPPORTED, b.which(kRangeDg, k, q) + " has more than 65535 bases");
+        in.off[q] = b.s->off[b.ctg_index[k]] + (uint64_t)((int64_t)b.range_start[q] - b.chr_start[k]);
+        in.len[q] = (uint32_t)bases;
+        return GAMS_OK;
+    }
+    int ready() const { return gams_dg_seq_ready(h, b.s); }
+    void launch(const DgCols &d, uint32_t n, float *d_dg) const { gams_launch_dg(h, b.s, d.off, d.len, n, d.table, d_dg); }
+};
+}  // namespace
+
+extern "C" int gams_gpu_range_dg_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                       const int32_t *chr_start, const uint64_t *range_off, const int32_t *range_start,
+                                       const int32_t *range_end, const gams_dg_table_t *table, float *dg) {
+    const RangeBatch b{s, n_sel, ctg_index, chr_start, range_off, range_start, range_end, dg};
+    return gams_range_batch(h, kRangeDg, b, RangeDgEntry{h, b, table});
 }

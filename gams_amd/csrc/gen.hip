@@ -619,7 +619,9 @@ extern "C" int gams_gpu_gen_text(gams_gpu_t *h, const char *bytes, uint64_t n_by
         GAMS_TRY(h, who, d_tab.alloc(layout_bytes(tab)));
         carve(d_tab.p, tab);
         {
-            const int rc = gams_seqset_wait_uploads(h, s);   // the zeroing of the new buffers, on the copy stream
+            // the zeroing of the new buffers, on the copy stream.  (The gate bumps the reader epoch although nothing reads
+            // here: harmless, the next burst of gams_seqset_upload_ranges calls orders itself once more.)
+            const int rc = gams_seqset_read_begin(h, s);
             if (rc != GAMS_OK) return rc;
         }
         GAMS_TRY(h, who, stage(GEN_PLACE, true));
@@ -639,11 +641,15 @@ extern "C" int gams_gpu_gen_text(gams_gpu_t *h, const char *bytes, uint64_t n_by
         hipLaunchKernelGGL(gen_place_kernel, dim3((unsigned)((pa.n_chunks + 255) / 256)), dim3(256), 0, st, pa);
         GAMS_TRY(h, who, hipGetLastError());
         GAMS_TRY(h, who, stage(GEN_PLACE, false));
-        // readers on any stream order themselves behind the kernel as behind an upload; an upload behind it as behind a reader
+        // readers on any stream order themselves behind the kernel as behind an upload (the seqset protocol, common.hpp:
+        // nothing but the zeroing awaited above was queued on the new buffers, so there was no write_begin to make) ...
         if (!s->uploaded) GAMS_TRY(h, who, hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
-        GAMS_TRY(h, who, hipEventRecord(s->uploaded, st));
-        s->dirty = true;
-        ++s->upload_gen;
+        {
+            const int rc = gams_seqset_write_end(h, s, st);
+            if (rc != GAMS_OK) return rc;
+        }
+        // ... and an upload behind it as behind a reader: the kernel ran on the compute stream, so the epoch moves on
+        // and the next gams_seqset_upload_ranges does not take itself for ordered already
         h->reader_epoch.fetch_add(1, std::memory_order_relaxed);
         GAMS_TRY(h, who, hipStreamSynchronize(st));   // the tables above are the call's
     } else if (n_bytes) {

@@ -248,14 +248,9 @@ int upload_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t coun
     const size_t lds_bytes = ((size_t)kLdsFixed + max_block / 4u) * 4u;
     GAMS_TRY(h, who, gams_lds_attr(h, reinterpret_cast<const void *>(gunzip_decode_kernel), lds_bytes));
 
-    // the rules of an upload: the index of the old bytes goes, the copy stream queues behind every pass that may read them
-    if (s->gcindex) {
-        GAMS_HIP(h, hipStreamSynchronize(h->compute));
-        gams_seqset_gcindex_free(s);
-    }
-    if (!s->uploaded) GAMS_HIP(h, hipEventCreateWithFlags(&s->uploaded, hipEventDisableTiming));
+    // the kernels write the seqset: a writer's bracket (the seqset protocol, common.hpp)
     {
-        const int rc = gams_order_after_readers(h, st);
+        const int rc = gams_seqset_write_begin(h, s, st);
         if (rc != GAMS_OK) return rc;
     }
     GAMS_TRY(h, who, hipEventRecord(h->k0, st));
@@ -279,9 +274,10 @@ int upload_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t coun
     GAMS_TRY(h, who, hipMemcpyAsync(h_status, d_status, n_taken, hipMemcpyDeviceToHost, st));
     GAMS_TRY(h, who, stage(GU_JOIN, false));
     GAMS_TRY(h, who, hipEventRecord(h->k1, st));
-    GAMS_TRY(h, who, hipEventRecord(s->uploaded, st));
-    s->dirty = true;
-    ++s->upload_gen;
+    {
+        const int rc = gams_seqset_write_end(h, s, st);
+        if (rc != GAMS_OK) return rc;
+    }
     GAMS_TRY(h, who, hipStreamSynchronize(st));
     h->kq_used = GU_STAGES;
     h->kq_staged = true;

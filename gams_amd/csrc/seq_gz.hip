@@ -401,8 +401,7 @@ int seq_gz_run(gams_gpu_t *h, gams_seqset_t *s, uint32_t first, uint32_t count, 
     crc_shift16_fill(hd.shift16);
     const GzBlocks B{dd.src, dd.n, dd.ctg, dd.at};
 
-    h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the kernels read the sequence bytes
-    const int wrc = gams_seqset_wait_uploads(h, s);
+    const int wrc = gams_seqset_read_begin(h, s);   // the kernels read the sequence bytes
     if (wrc != GAMS_OK) return wrc;
     GAMS_TRY(h, who, hipEventRecord(h->k0, st));
     GAMS_TRY(h, who, stage(GZ_HIST, true));

@@ -27,7 +27,10 @@
 #include "interval_kernels.hpp"
 #include "text_emit.hpp"
 
+#include "range_batch.hpp"
+
 #include <string>
+#include <type_traits>
 
 #include <algorithm>
 
@@ -523,8 +526,7 @@ void gams_launch_range_gc_cols(const gams_seqset_t *s, const unsigned long long 
 int gams_seqset_gcindex(gams_gpu_t *h, gams_seqset_t *s) {
     if (!s->have_bytes) return gams_fail(h, GAMS_ESTATE, "the seqset holds the G/C plane only: this call needs the sequence bytes");
     if (s->gcindex) return GAMS_OK;
-    h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the build reads the sequence bytes
-    int wrc = gams_seqset_wait_uploads(h, s);
+    int wrc = gams_seqset_read_begin(h, s);   // the build reads the sequence bytes
     if (wrc != GAMS_OK) return wrc;
     gams_gcindex *ix = s->gcindex = new gams_gcindex();   // the seqset's from here on: one way out, gams_seqset_gcindex_free
     ix->n_chunks = s->bytes / 16;
@@ -597,6 +599,12 @@ struct SwTextArgs {
     const char *cid_bytes, *chr_bytes;
     const uint32_t *igrp;                          // per interval: its group
 };
+// ... with the tenth field (gams_gpu_sw_text_dg): the ΔG of every row, on the device
+struct SwTextDgArgs : SwTextArgs {
+    const float *dg;
+};
+__device__ __forceinline__ const float *sw_dg_col(const SwTextArgs &) { return nullptr; }
+__device__ __forceinline__ const float *sw_dg_col(const SwTextDgArgs &a) { return a.dg; }
 
 struct SwRowCtx {
     uint32_t k, f, serial;    // selected ctg, feature (index into the call's arrays), 1-based row of the feature
@@ -617,8 +625,7 @@ __device__ __forceinline__ SwRowCtx sw_row_ctx(const SwTextArgs &a, uint64_t r, 
     return c;
 }
 // the row's text, counted or written; `bad`: a value this formatter does not cover.  kDg: the tenth field behind rg_count,
-// dg[r] printed `{:.4}` and empty for NaN (gams_gpu_sw_text_dg); the column is an argument of its own, so SwTextArgs and
-// the kernels without it stay what they are
+// dg[r] printed `{:.4}` and empty for NaN (gams_gpu_sw_text_dg); the column is handed in beside SwTextArgs (sw_dg_col)
 template <bool kWrite, bool kDg = false>
 __device__ __forceinline__ void sw_row_text(const SwTextArgs &a, uint64_t r, RowOut<kWrite> &o, bool &bad,
                                             const float *dg = nullptr) {
@@ -683,7 +690,12 @@ __device__ __forceinline__ void sw_row_text(const SwTextArgs &a, uint64_t r, Row
     o.ch('\n');
 }
 
-__global__ __launch_bounds__(256) void sw_text_len_kernel(const SwTextArgs a) {
+// The two text kernels, instantiated on the argument struct: SwTextArgs, or SwTextDgArgs with the ΔG column.  The type, not
+// a flag or a wrapper over a shared body, decides (profiles/seqset_protocol_refactor.txt: the <SwTextArgs> instantiations
+// are, instruction for instruction, the kernels that had no column; profiles/dg.txt has what a flag did to them).
+template <typename A>
+__global__ __launch_bounds__(256) void sw_text_len_kernel(const A a) {
+    constexpr bool kDg = std::is_same<A, SwTextDgArgs>::value;
     __shared__ uint32_t ws[4];
     const uint64_t base = (uint64_t)blockIdx.x * kSwTextBlock;
     const uint32_t tid = threadIdx.x;
@@ -694,7 +706,7 @@ __global__ __launch_bounds__(256) void sw_text_len_kernel(const SwTextArgs a) {
         const uint64_t r = base + 2u * tid + u;
         if (r >= a.n_rows) continue;
         RowOut<false> n;
-        sw_row_text(a, r, n, bad);
+        sw_row_text<false, kDg>(a, r, n, bad, sw_dg_col(a));
         a.len[r] = n.n;
         sum += n.n;
     }
@@ -703,7 +715,9 @@ __global__ __launch_bounds__(256) void sw_text_len_kernel(const SwTextArgs a) {
     if (tid == 0u) a.blk_len[blockIdx.x] = tot;
 }
 
-__global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) {
+template <typename A>
+__global__ __launch_bounds__(256) void sw_text_write_kernel(const A a) {
+    constexpr bool kDg = std::is_same<A, SwTextDgArgs>::value;
     __shared__ uint32_t scr[4];
     __shared__ __align__(16) char stage[kSwTextStage + 16];
     const uint64_t base = (uint64_t)blockIdx.x * kSwTextBlock;
@@ -725,58 +739,7 @@ __global__ __launch_bounds__(256) void sw_text_write_kernel(const SwTextArgs a) 
         if (r >= a.n_rows) break;
         w.put(at, [&](char *p) {
             RowOut<true> o{p};
-            sw_row_text(a, r, o, bad);
-        });
-        at += l[u];
-    }
-    w.flush();
-}
-
-// The same two kernels with the tenth field (gams_gpu_sw_text_dg).  They are kernels of their own, not a flag of the two
-// above, so that the code of those stays what it was, instruction for instruction (profiles/dg.txt).
-__global__ __launch_bounds__(256) void sw_text_dg_len_kernel(const SwTextArgs a, const float *dg) {
-    __shared__ uint32_t ws[4];
-    const uint64_t base = (uint64_t)blockIdx.x * kSwTextBlock;
-    const uint32_t tid = threadIdx.x;
-    uint32_t sum = 0;
-    bool bad = false;
-#pragma unroll
-    for (uint32_t u = 0; u < 2u; ++u) {
-        const uint64_t r = base + 2u * tid + u;
-        if (r >= a.n_rows) continue;
-        RowOut<false> n;
-        sw_row_text<false, true>(a, r, n, bad, dg);
-        a.len[r] = n.n;
-        sum += n.n;
-    }
-    if (bad) a.words[1] = 1ull;
-    const uint32_t tot = block_sum_256(sum, ws);
-    if (tid == 0u) a.blk_len[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(256) void sw_text_dg_write_kernel(const SwTextArgs a, const float *dg) {
-    __shared__ uint32_t scr[4];
-    __shared__ __align__(16) char stage[kSwTextStage + 16];
-    const uint64_t base = (uint64_t)blockIdx.x * kSwTextBlock;
-    const uint32_t tid = threadIdx.x;
-    uint32_t l[2], mine = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < 2u; ++u) {
-        const uint64_t r = base + 2u * tid + u;
-        l[u] = r < a.n_rows ? a.len[r] : 0u;
-        mine += l[u];
-    }
-    BlockWriter<uint32_t> w(mine, scr, a.blk_off, a.text, a.text_cap);
-    w.stage_if(w.tot <= kSwTextStage, stage);
-    uint32_t at = w.rel;
-    bool bad = false;
-#pragma unroll
-    for (uint32_t u = 0; u < 2u; ++u) {
-        const uint64_t r = base + 2u * tid + u;
-        if (r >= a.n_rows) break;
-        w.put(at, [&](char *p) {
-            RowOut<true> o{p};
-            sw_row_text<true, true>(a, r, o, bad, dg);
+            sw_row_text<true, kDg>(a, r, o, bad, sw_dg_col(a));
         });
         at += l[u];
     }
@@ -904,10 +867,12 @@ struct SwReq {
 using SwCols = SwStage<SwCtg>;
 const std::string kSw = "gpu_sw", kSwText = "gpu_sw_text", kRangeGc = "gpu_range_gc", kSwSum = "gpu_sw_summary";
 
-// the selected ctgs of a batch call (sw and range gc): every index names a ctg of a length the kernels carry, and `off`
-// (named `off_name` in the messages) begins at 0 and does not decrease
-int sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
-                       const uint32_t *ctg_index, const uint64_t *off) {
+}  // namespace
+
+// the selected ctgs of a batch call (sw and the range batches): every index names a ctg of a length the kernels carry, and
+// `off` (named `off_name` in the messages) begins at 0 and does not decrease
+int gams_sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
+                            const uint32_t *ctg_index, const uint64_t *off) {
     if (off[0] != 0) return gams_fail(h, GAMS_EINVAL, who + ": " + off_name + "[0] must be 0");
     for (uint32_t k = 0; k < n_sel; ++k) {
         if (ctg_index[k] >= s->n_ctg) return gams_fail(h, GAMS_EINVAL, who + ": ctg index out of range");
@@ -918,6 +883,7 @@ int sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_na
     return GAMS_OK;
 }
 
+namespace {
 // 1. the arguments; *nf = the features of the call, 0 with GAMS_OK: nothing to do
 int sw_check(const SwReq &q, uint32_t *nf) {
     gams_gpu_t *h = q.h;
@@ -930,7 +896,7 @@ int sw_check(const SwReq &q, uint32_t *nf) {
     if (q.row_off)
         for (uint32_t k = 0; k <= q.n_sel; ++k) q.row_off[k] = 0;
     if (q.n_sel == 0) return GAMS_OK;
-    if ((rc = sw_check_selection(h, kSw, "feat_off", q.s, q.n_sel, q.ctg_index, q.feat_off)) != GAMS_OK) return rc;
+    if ((rc = gams_sw_check_selection(h, kSw, "feat_off", q.s, q.n_sel, q.ctg_index, q.feat_off)) != GAMS_OK) return rc;
     const uint64_t nf64 = q.feat_off[q.n_sel];
     if (nf64 == 0) return GAMS_OK;
     if (!q.feat_start || !q.feat_end) return gams_fail(h, GAMS_EINVAL, "gpu_sw: null argument");
@@ -1165,11 +1131,12 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
     const size_t n_words = (size_t)n_sel + 3;
     GAMS_TRY(h, who, hipMemsetAsync(ta.words, 0, gams_align256(n_words * 8), st));
     if (stage) GAMS_TRY(h, who, (*stage)(SWF_TLEN, true));
+    const SwTextDgArgs tda{ta, dg};
     if (nb) {
         if (dg)
-            hipLaunchKernelGGL(sw_text_dg_len_kernel, dim3(nb), dim3(256), 0, st, ta, dg);
+            hipLaunchKernelGGL(sw_text_len_kernel<SwTextDgArgs>, dim3(nb), dim3(256), 0, st, tda);
         else
-            hipLaunchKernelGGL(sw_text_len_kernel, dim3(nb), dim3(256), 0, st, ta);
+            hipLaunchKernelGGL(sw_text_len_kernel<SwTextArgs>, dim3(nb), dim3(256), 0, st, ta);
         hipLaunchKernelGGL(blk_offsets_scan_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, ta.blk_len, nb, ta.blk_off, ta.words, 0u);
     }
     if (stage) {
@@ -1178,9 +1145,9 @@ int sw_text_tail(gams_gpu_t *h, const std::string &who, const char *advice, cons
     }
     if (nb) {
         if (dg)
-            hipLaunchKernelGGL(sw_text_dg_write_kernel, dim3(nb), dim3(256), 0, st, ta, dg);
+            hipLaunchKernelGGL(sw_text_write_kernel<SwTextDgArgs>, dim3(nb), dim3(256), 0, st, tda);
         else
-            hipLaunchKernelGGL(sw_text_write_kernel, dim3(nb), dim3(256), 0, st, ta);
+            hipLaunchKernelGGL(sw_text_write_kernel<SwTextArgs>, dim3(nb), dim3(256), 0, st, ta);
         hipLaunchKernelGGL(sw_text_ctg_kernel, dim3(n_sel + 1), dim3(64), 0, st, ta);
     }
     GAMS_TRY(h, who, hipGetLastError());
@@ -1329,11 +1296,6 @@ int sw_batch_impl(const SwReq &q) {
 }
 }  // namespace
 
-int gams_sw_check_selection(gams_gpu_t *h, const std::string &who, const char *off_name, const gams_seqset_t *s, uint32_t n_sel,
-                            const uint32_t *ctg_index, const uint64_t *off) {
-    return sw_check_selection(h, who, off_name, s, n_sel, ctg_index, off);
-}
-
 int gams_launch_sw_cols(gams_gpu_t *h, const SwColsJob &J, const char **text, uint64_t *text_bytes, uint64_t *text_off,
                         uint64_t *n_rows) {
     const SwCall &call = J.call;
@@ -1464,25 +1426,6 @@ extern "C" int gams_gpu_sw_count_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t
     return sw_batch_impl(q);
 }
 
-extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
-                                        const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
-                                        const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
-                                        int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
-                                        const uint32_t *rg_group, const char **text, uint64_t *text_bytes,
-                                        const uint64_t **ctg_off, uint64_t *n_rows) {
-    if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
-    SwCall c(size, max, resize, actions, rg_ix, rg_group);
-    const int rc = gams_sw_call_check(h, kSwText, c, SWC_ACTIONS, n_sel);
-    if (rc != GAMS_OK) return rc;
-    if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
-    SwReq q(SwMode::Text, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
-    q.tx = SwTextReq{chr, feat_id, text, text_bytes, ctg_off};
-    *text = nullptr;
-    *text_bytes = 0;
-    return sw_batch_impl(q);
-}
-
 // ---- the ΔG of the windows: the rows' geometry from the kernel without actions, then dg.hip over them --
 // a window has at most `size` bases (M is the feature resized to `size`, window.rs:96-124), so the kernel's limit is one on size
 static int sw_dg_check(gams_gpu_t *h, const std::string &who, const gams_dg_table_t *table, int32_t size) {
@@ -1508,25 +1451,44 @@ extern "C" int gams_gpu_sw_dg_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_
     return sw_batch_impl(q);
 }
 
+// the two text entries: the arguments, the SwReq and the call.  with_dg: the ΔG entry, whose table and size are checked
+// between the call's actions and the feature ids
+static int sw_text_entry(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index, const char *const *chr,
+                         const int32_t *chr_start, const uint64_t *feat_off, const int32_t *feat_start, const int32_t *feat_end,
+                         const char *const *feat_id, const SwCall &c, bool with_dg, const gams_dg_table_t *table,
+                         const char **text, uint64_t *text_bytes, const uint64_t **ctg_off, uint64_t *n_rows) {
+    if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
+        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
+    int rc = gams_sw_call_check(h, kSwText, c, SWC_ACTIONS, n_sel);
+    if (rc != GAMS_OK) return rc;
+    if (with_dg && (rc = sw_dg_check(h, kSwText, table, c.size)) != GAMS_OK) return rc;
+    if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
+    SwReq q(SwMode::Text, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
+    q.tx = SwTextReq{chr, feat_id, text, text_bytes, ctg_off};
+    q.dg_table = with_dg ? table : nullptr;
+    *text = nullptr;
+    *text_bytes = 0;
+    return sw_batch_impl(q);
+}
+
+extern "C" int gams_gpu_sw_text_actions(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
+                                        const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
+                                        const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
+                                        int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
+                                        const uint32_t *rg_group, const char **text, uint64_t *text_bytes,
+                                        const uint64_t **ctg_off, uint64_t *n_rows) {
+    return sw_text_entry(h, s, n_sel, ctg_index, chr, chr_start, feat_off, feat_start, feat_end, feat_id,
+                         SwCall(size, max, resize, actions, rg_ix, rg_group), false, nullptr, text, text_bytes, ctg_off, n_rows);
+}
+
 extern "C" int gams_gpu_sw_text_dg(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                                    const char *const *chr, const int32_t *chr_start, const uint64_t *feat_off,
                                    const int32_t *feat_start, const int32_t *feat_end, const char *const *feat_id,
                                    int32_t size, int32_t max, int32_t resize, uint32_t actions, gams_index_t *rg_ix,
                                    const uint32_t *rg_group, const gams_dg_table_t *table, const char **text,
                                    uint64_t *text_bytes, const uint64_t **ctg_off, uint64_t *n_rows) {
-    if (!h || !text || !text_bytes || !n_rows || (n_sel && (!chr || !feat_off)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null argument");
-    SwCall c(size, max, resize, actions, rg_ix, rg_group);
-    int rc = gams_sw_call_check(h, kSwText, c, SWC_ACTIONS, n_sel);
-    if (rc != GAMS_OK) return rc;
-    if ((rc = sw_dg_check(h, kSwText, table, size)) != GAMS_OK) return rc;
-    if (n_sel && feat_off[n_sel] && !feat_id) return gams_fail(h, GAMS_EINVAL, "gpu_sw_text: null feature ids");
-    SwReq q(SwMode::Text, h, s, n_sel, ctg_index, chr_start, feat_off, feat_start, feat_end, c, n_rows);
-    q.tx = SwTextReq{chr, feat_id, text, text_bytes, ctg_off};
-    q.dg_table = table;
-    *text = nullptr;
-    *text_bytes = 0;
-    return sw_batch_impl(q);
+    return sw_text_entry(h, s, n_sel, ctg_index, chr, chr_start, feat_off, feat_start, feat_end, feat_id,
+                         SwCall(size, max, resize, actions, rg_ix, rg_group), true, table, text, text_bytes, ctg_off, n_rows);
 }
 
 extern "C" int gams_gpu_sw_text(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
@@ -1709,66 +1671,41 @@ extern "C" int gams_gpu_sw(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t 
 
 // gc_content (round4) of arbitrary chromosome ranges inside ctg i: gams::cache_gc_content
 // (src/libs/utils.rs:141-162) as `gams peak` uses it (src/cmd_gams/peak.rs:79).
+namespace {
+struct RangeGcEntry {   // what gams_range_batch (range_batch.hpp) asks of an entry
+    gams_gpu_t *h;
+    const RangeBatch &b;
+    int admit() const { return GAMS_OK; }
+    SwCols inputs(Carver &c, uint32_t n) const { return sw_stage_layout<SwCtg>(c, b.n_sel, n, false); }   // ctgs | rs | re | rctg
+    void head(const SwCols &in) const {
+        for (uint32_t k = 0; k < b.n_sel; ++k) {
+            const uint32_t i = b.ctg_index[k], len = b.s->len[i];
+            in.ctgs[k] = SwCtg{b.s->off[i], len, b.chr_start[k], (int32_t)((int64_t)b.chr_start[k] + len - 1), (uint32_t)b.range_off[k], UINT32_MAX, 0u};
+        }
+    }
+    int range(const SwCols &in, uint32_t k, uint64_t q) const {
+        in.fs[q] = b.range_start[q];
+        in.fe[q] = b.range_end[q];
+        in.fctg[q] = k;
+        return GAMS_OK;
+    }
+    int ready() const { return gams_seqset_gcindex(h, b.s); }
+    void launch(const SwCols &d, uint32_t n, float *d_gc) const {
+        SwArgs a{};
+        a.pm = b.s->gcindex->d_pm;
+        a.seg = b.s->gcindex->d_seg;
+        a.ctgs = d.ctgs;
+        a.fctg = d.fctg;
+        hipLaunchKernelGGL(range_gc_kernel, dim3((n + 255) / 256), dim3(256), 0, h->compute, a, d.fs, d.fe, n, d_gc);
+    }
+};
+}  // namespace
+
 extern "C" int gams_gpu_range_gc_batch(gams_gpu_t *h, gams_seqset_t *s, uint32_t n_sel, const uint32_t *ctg_index,
                                        const int32_t *chr_start, const uint64_t *range_off, const int32_t *range_start,
                                        const int32_t *range_end, float *gc) {
-    if (!h || !s || (n_sel && (!ctg_index || !chr_start || !range_off)))
-        return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: null argument");
-    if (n_sel == 0) return GAMS_OK;
-    int rc = sw_check_selection(h, kRangeGc, "range_off", s, n_sel, ctg_index, range_off);
-    if (rc != GAMS_OK) return rc;
-    const uint64_t n64 = range_off[n_sel];
-    if (n64 == 0) return GAMS_OK;
-    if (!range_start || !range_end || !gc) return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: null argument");
-    if (n64 > 0x7fffff00ull) return gams_fail(h, GAMS_EUNSUPPORTED, "gpu_range_gc: too many ranges for one launch");
-    const uint32_t n = (uint32_t)n64;
-    GAMS_HIP(h, hipSetDevice(h->device));
-    // inputs in one page-locked block (one DMA): ctgs | rs | re | rctg; results in the same device block
-    auto inputs = [&](Carver &c) { return sw_stage_layout<SwCtg>(c, n_sel, n, false); };
-    const size_t in_bytes = layout_bytes(inputs);
-    PoolBlock dev(h, false), pin(h, true);
-    GAMS_TRY(h, kRangeGc, pin.alloc(in_bytes));
-    const SwCols in = carve(pin.p, inputs);
-    for (uint32_t k = 0; k < n_sel; ++k) {
-        const uint32_t i = ctg_index[k];
-        const int32_t cs = chr_start[k];
-        const int64_t ce = (int64_t)cs + s->len[i] - 1;
-        in.ctgs[k] = SwCtg{s->off[i], s->len[i], cs, (int32_t)ce, (uint32_t)range_off[k], UINT32_MAX, 0u};
-        // utils.rs:151-156 slices seq[from-1..to): a range outside the ctg (or inverted) panics there
-        for (uint64_t q = range_off[k]; q < range_off[k + 1]; ++q) {
-            if (range_start[q] < cs || range_end[q] > ce || range_end[q] < range_start[q])
-                return gams_fail(h, GAMS_EINVAL, "gpu_range_gc: range " + std::to_string(q - range_off[k]) +
-                                                     (n_sel > 1 ? " of selected ctg " + std::to_string(k) : std::string()) +
-                                                     " is not inside the ctg");
-            in.fs[q] = range_start[q];
-            in.fe[q] = range_end[q];
-            in.fctg[q] = k;
-        }
-    }
-    if ((rc = gams_seqset_gcindex(h, s)) != GAMS_OK) return rc;
-    SwCols d{};
-    float *d_gc = nullptr;
-    auto device = [&](Carver &c) {   // the inputs | results
-        d = inputs(c);
-        d_gc = c.take<float>(n);
-    };
-    GAMS_TRY(h, kRangeGc, dev.alloc(layout_bytes(device)));
-    carve(dev.p, device);
-    GAMS_TRY(h, kRangeGc, hipMemcpyAsync(dev.p, pin.p, in_bytes, hipMemcpyHostToDevice, h->compute));
-    SwArgs a{};
-    a.pm = s->gcindex->d_pm;
-    a.seg = s->gcindex->d_seg;
-    a.ctgs = d.ctgs;
-    a.fctg = d.fctg;
-    GAMS_TRY(h, kRangeGc, hipEventRecord(h->k0, h->compute));
-    hipLaunchKernelGGL(range_gc_kernel, dim3((n + 255) / 256), dim3(256), 0, h->compute, a, d.fs, d.fe, n, d_gc);
-    GAMS_TRY(h, kRangeGc, hipGetLastError());
-    GAMS_TRY(h, kRangeGc, hipEventRecord(h->k1, h->compute));
-    h->k_valid = true;
-    h->kq_used = 0;
-    GAMS_TRY(h, kRangeGc, hipMemcpyAsync(gc, d_gc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->compute));
-    GAMS_TRY(h, kRangeGc, hipStreamSynchronize(h->compute));
-    return GAMS_OK;
+    const RangeBatch b{s, n_sel, ctg_index, chr_start, range_off, range_start, range_end, gc};
+    return gams_range_batch(h, kRangeGc, b, RangeGcEntry{h, b});
 }
 
 extern "C" int gams_gpu_range_gc(gams_gpu_t *h, gams_seqset_t *s, uint32_t i, int32_t chr_start,

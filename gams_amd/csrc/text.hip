@@ -2532,8 +2532,7 @@ int locate_seq_run(gams_gpu_t *h, const SeqJob &J, const char *bytes, uint64_t n
     GAMS_TRY(h, who, d_text.alloc(tb));
     a.text = reinterpret_cast<char *>(d_text.p);
     a.total = tb;
-    h->reader_epoch.fetch_add(1, std::memory_order_relaxed);   // the copy reads the sequence bytes
-    const int wrc = gams_seqset_wait_uploads(h, J.s);
+    const int wrc = gams_seqset_read_begin(h, J.s);   // the copy reads the sequence bytes
     if (wrc != GAMS_OK) return wrc;
     GAMS_TRY(h, who, stage(SQ_COPY, true));
     hipLaunchKernelGGL(seq_copy_kernel, dim3((uint32_t)seq_plan_chunks(tb)), dim3(256), 0, st, a);

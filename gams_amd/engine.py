@@ -230,24 +230,30 @@ def sw_count_batch(eng, seqset, sel, chr_start, feat_off, fs, fe, size, mx, inde
     return cnt[:n.value], roff
 
 
-def sw_text_actions(eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids, size, mx, resize, actions,
-                    index=None, rg_group=None):
-    """gams_gpu_sw_text_actions -> (rc, text bytes, per-ctg offsets); rc != OK is returned, not raised"""
+def _sw_text(entry, eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids, size, mx, resize, actions, index,
+             rg_group, *extra):
+    """a text entry of the library (`extra`: what it takes between rg_group and the outputs) -> (rc, text bytes,
+    per-ctg offsets); rc != OK is returned, not raised"""
     sel, cst, foff, fs, fe = _sw_sel(sel, chr_start, feat_off, fs, fe)
     names = (C.c_char_p * max(sel.size, 1))(*[c.encode() for c in chr_names])
     ids = (C.c_char_p * max(len(feat_ids), 1))(*[f.encode() for f in feat_ids])
     grp = None if rg_group is None else np.ascontiguousarray(rg_group, np.uint32)
     txt, nb, off, nrows = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-    rc = eng.lib.gams_gpu_sw_text_actions(eng.h, seqset.p, sel.size, sel.ctypes.data, names, cst.ctypes.data,
-                                          foff.ctypes.data, fs.ctypes.data, fe.ctypes.data, ids, size, mx, resize, actions,
-                                          index.p if index is not None else None,
-                                          grp.ctypes.data if grp is not None else None, C.byref(txt), C.byref(nb),
-                                          C.byref(off), C.byref(nrows))
+    rc = entry(eng.h, seqset.p, sel.size, sel.ctypes.data, names, cst.ctypes.data, foff.ctypes.data, fs.ctypes.data,
+               fe.ctypes.data, ids, size, mx, resize, actions, index.p if index is not None else None,
+               grp.ctypes.data if grp is not None else None, *extra, C.byref(txt), C.byref(nb), C.byref(off), C.byref(nrows))
     if rc != _lib.OK:
         return rc, b"", None
     text = C.string_at(txt.value, nb.value) if nb.value else b""
     offs = np.frombuffer((C.c_uint64 * (sel.size + 1)).from_address(off.value), np.uint64).copy()
     return rc, text, offs
+
+
+def sw_text_actions(eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids, size, mx, resize, actions,
+                    index=None, rg_group=None):
+    """gams_gpu_sw_text_actions -> (rc, text bytes, per-ctg offsets); rc != OK is returned, not raised"""
+    return _sw_text(eng.lib.gams_gpu_sw_text_actions, eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids,
+                    size, mx, resize, actions, index, rg_group)
 
 
 def _dg_table(table):
@@ -288,23 +294,9 @@ def sw_dg_batch(eng, seqset, sel, chr_start, feat_off, fs, fe, size, mx, table):
 def sw_text_dg(eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids, size, mx, resize, actions, table,
                index=None, rg_group=None):
     """gams_gpu_sw_text_dg -> (rc, text bytes, per-ctg offsets); rc != OK is returned, not raised"""
-    sel, cst, foff, fs, fe = _sw_sel(sel, chr_start, feat_off, fs, fe)
-    names = (C.c_char_p * max(sel.size, 1))(*[c.encode() for c in chr_names])
-    ids = (C.c_char_p * max(len(feat_ids), 1))(*[f.encode() for f in feat_ids])
-    grp = None if rg_group is None else np.ascontiguousarray(rg_group, np.uint32)
     t = None if table is None else _dg_table(table)
-    txt, nb, off, nrows = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
-    rc = eng.lib.gams_gpu_sw_text_dg(eng.h, seqset.p, sel.size, sel.ctypes.data, names, cst.ctypes.data,
-                                     foff.ctypes.data, fs.ctypes.data, fe.ctypes.data, ids, size, mx, resize, actions,
-                                     index.p if index is not None else None,
-                                     grp.ctypes.data if grp is not None else None,
-                                     C.byref(t) if t is not None else None, C.byref(txt), C.byref(nb), C.byref(off),
-                                     C.byref(nrows))
-    if rc != _lib.OK:
-        return rc, b"", None
-    text = C.string_at(txt.value, nb.value) if nb.value else b""
-    offs = np.frombuffer((C.c_uint64 * (sel.size + 1)).from_address(off.value), np.uint64).copy()
-    return rc, text, offs
+    return _sw_text(eng.lib.gams_gpu_sw_text_dg, eng, seqset, sel, chr_names, chr_start, feat_off, fs, fe, feat_ids,
+                    size, mx, resize, actions, index, rg_group, C.byref(t) if t is not None else None)
 
 
 class WavePlan:
